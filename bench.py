@@ -7,14 +7,20 @@ per-subproblem argmax) over a batch of synthetic subproblems already resident in
 ranks each rank scores its own shard of the live subproblems and ONE RCCL all-gather collects the
 padded scores for the branch selector (weak scaling: per-GPU batch fixed).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--net cifar_base_kw] [--batch 256]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--net cifar_base_kw] [--batch 256] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the description of the run).  `--full` adds everything else after the timed steps: per-kernel durations and
+the roofline figures built on them, the host-fed, two-in-flight, exact-fp32 and aggregate-only side legs and the CPU baseline
+(each of those can be left out with its `--no-...` switch).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/*.npy (`dump_outputs`); the inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no torchrun environment starts the N ranks itself (fresh child processes of
 `python -m torch.distributed.run`, spawned before this process touches the GPU) and exits with their code; under
 torchrun (RANK / WORLD_SIZE set) it is one of the ranks.  A world size that does not match --gpus is an error -- it never
 silently benchmarks one rank.
 
-Prints ONE JSON line (rank 0).  The CPU oracle is imported only for the `cpu_baseline` leg.
+Prints ONE JSON line (rank 0).  The CPU oracle is imported only for the `cpu_baseline` leg (`--full`).
 """
 import argparse
 import json
@@ -282,6 +288,30 @@ def _status_word(res):
     return v
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: what the timed path returned to its caller in the last timed step (this rank's shard), as .npy files
+      scores.npy     float32, the scores of every subproblem's ambiguous ReLUs, concatenated in batch order (ForwardResult.ragged())
+      decisions.npy  float64 (B, 2), every subproblem's branching decision (ReLU layer, node)
+    A scores vector over the size limit is replaced by a fixed sample (seed 0, positions ascending) whose positions go to
+    scores_index.npy (float64: exact integers).  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    scores = res.scores[res.masks != 0].float().cpu().numpy()
+    decisions = res.decisions.cpu().numpy().astype(np.float64)
+    arrays = {"decisions": decisions}
+    room = max(0, limit_bytes - decisions.nbytes) // (4 + 8)        # (a sampled entry costs its float32 score + its float64 position)
+    if scores.nbytes <= limit_bytes - decisions.nbytes:
+        arrays["scores"] = scores
+    else:
+        idx = np.sort(np.random.RandomState(0).choice(scores.size, size=room, replace=False))
+        arrays["scores"], arrays["scores_index"] = scores[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -319,6 +349,11 @@ def parse_args(argv=None):
                          "(1024 subproblems at --gpus 8)")
     ap.add_argument("--net", default=None)
     ap.add_argument("--batch", type=int, default=None, help="subproblems per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-kernel durations, rooflines, the side legs and the CPU baseline "
+                         "(the --no-... switches below leave single legs out of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-fp32", action="store_true", help="skip the exact-fp32 comparison leg (handle option bf3=0: exact_fp32_ms_per_step, bf3_max_abs_delta)")
     ap.add_argument("--no-aggregate-only", action="store_true", help="skip the fuse=0 leg (roofline_aggregate_only: the stand-alone edge-aggregation kernel)")
@@ -336,6 +371,10 @@ def parse_args(argv=None):
         args.batch = cfg["batch"]
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     return args
 
 
@@ -475,12 +514,43 @@ def main():
                        "status_word": int(_status_word(plain)) | (int(loop.status_acc.cpu()[0]) if loop.status_acc is not None and loop.status_acc.numel() else 0),
                        "self_launched": bool(os.environ.get("BENCH_SELF_LAUNCHED"))}
 
-        if not args.no_two_in_flight:
+        if args.full and not args.no_two_in_flight:
             try:
                 dist_record["dist_two_in_flight"] = dist_two_in_flight_leg(sd, d_args, plain, max(args.steps, 100), world * B, rank, B,
                                                                            round(1e3 * elapsed / args.steps, 4))
             except Exception as e:      # noqa: BLE001
                 dist_record["dist_two_in_flight"] = {"error": f"{type(e).__name__}: {e}"}
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
+    plan = eng.describe()
+    head = {
+        "metric": "ReLU branching scores/sec (subproblems x ambiguous-ReLUs/s)",
+        "value": round(total_amb * args.steps / elapsed, 1),
+        "unit": "scores/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        # what ran, untimed, before the K timed steps besides the W warm-up steps the contract asks for: 4 steps (allocator, first status
+        # read) + BENCH_PREWARM steps (clocks); Python's cyclic collector is run once before them and kept off while the K steps are timed
+        "prewarm_steps": 4 + prewarm, "gc_disabled": True,
+        # handle options the timed engine was created with (include/gnnb.h gnnb_set_option; {} = the library's defaults)
+        "engine_options": dict(eng.options),
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (bf16x3-split 64x64 blocks)" if plan.get("bf3") else "f32", "data": "synthetic",
+        "config": {"workload": f"{args.net}, {B} synthetic subproblems per rank x {world} rank(s) = {world * B}, T=2, p=64, shipped cifar_trained_gnn weights",
+                   "batch_per_rank": B, "ranks": world, "global_batch": world * B,
+                   "subproblems_per_s": round(world * B * args.steps / elapsed, 1),
+                   "ambiguous_per_subproblem": round(total_amb / (world * B), 1),
+                   "parallelism": f"dp{world}" + (" + 1 all-gather(scores)/step" if world > 1 else "")},
+    }
+    if not args.full:
+        # a plain run ends with its headline: nothing else is measured
+        if rank == 0:
+            print(json.dumps({**head, "dist": dist_record}))
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel durations with HIP events on the launch stream (same K steps, instrumented) ----
     eng.profile_enable(True)
@@ -499,7 +569,6 @@ def main():
         kern = {k: {"ms_total": round(v[0], 4), "launches": int(v[1]), "avg_us": round(1e3 * v[0] / max(v[1], 1), 2)}
                 for k, v in prof.items() if v[1]}
         dom = max(kern, key=lambda k: kern[k]["ms_total"])
-        plan = eng.describe()
         stats = node_stats(batch)
         alg, issued, agg_bytes = plan_flops(plan, B, stats)
         dom_s = prof[dom][0] * 1e-3 / args.steps            # seconds of the dominant kernel class per forward
@@ -622,23 +691,7 @@ def main():
         if not args.no_cpu_baseline:
             cpu = cpu_baseline(sd, args.net, args.cpu_budget)
         out = {
-            "metric": "ReLU branching scores/sec (subproblems x ambiguous-ReLUs/s)",
-            "value": round(total_amb * args.steps / elapsed, 1),
-            "unit": "scores/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # what ran, untimed, before the K timed steps besides the W warm-up steps the contract asks for: 4 steps (allocator, first status
-            # read) + BENCH_PREWARM steps (clocks); Python's cyclic collector is run once before them and kept off while the K steps are timed
-            "prewarm_steps": 4 + prewarm, "gc_disabled": True,
-            # handle options the timed engine was created with (include/gnnb.h gnnb_set_option; {} = the library's defaults)
-            "engine_options": dict(eng.options),
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (bf16x3-split 64x64 blocks)" if plan.get("bf3") else "f32", "data": "synthetic",
-            "config": {"workload": f"{args.net}, {B} synthetic subproblems per rank x {world} rank(s) = {world * B}, T=2, p=64, shipped cifar_trained_gnn weights",
-                       "batch_per_rank": B, "ranks": world, "global_batch": world * B,
-                       "subproblems_per_s": round(world * B * args.steps / elapsed, 1),
-                       "ambiguous_per_subproblem": round(total_amb / (world * B), 1),
-                       "parallelism": f"dp{world}" + (" + 1 all-gather(scores)/step" if world > 1 else "")},
+            **head,
             "roofline": roofline,
             "roofline_node_update": roofline_nu,
             "roofline_message_passing": roofline_mp,

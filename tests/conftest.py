@@ -25,7 +25,7 @@ def pytest_collection_modifyitems(config, items):
 
 
 def pytest_sessionfinish(session, exitstatus):
-    # the parity margins the GPU tests reported (tests/margins.py) -> profiles/r06_parity_margins.json
+    # the parity margins the GPU tests reported (tests/margins.py) -> records/parity_margins.json (git-ignored)
     from tests import margins
     path = margins.dump(ROOT)
     if path:

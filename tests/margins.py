@@ -1,7 +1,7 @@
 """Parity margins on record: the GPU parity tests report, per configuration, how far the HIP scores were from the oracle, how large the
-scores were and how close the closest decision was; tests/conftest.py writes what was collected to profiles/r06_parity_margins.json
-when the session ends (`pytest -q` prints dots: the numbers behind a green run would otherwise be lost).  On a gpurun box the file is
-also copied to gpurun_out/, which is what travels back."""
+scores were and how close the closest decision was; tests/conftest.py writes what was collected to records/parity_margins.json
+when the session ends (`pytest -q` prints dots: the numbers behind a green run would otherwise be lost).  GNNB_RECORDS_DIR names
+another directory.  records/ is git-ignored: a test run leaves the tree as it was, the committed profiles/r06_*.json stay as measured."""
 import json
 import os
 import time
@@ -38,15 +38,13 @@ def dump(root):
         out["library_build_id"] = _lib.library_build_id()
     except Exception:      # noqa: BLE001
         pass
-    dirs = [os.path.join(root, "profiles")]
-    if os.path.isdir(os.path.join(root, "gpurun_out")) or os.environ.get("GRAFT_REPO_ROOT"):
-        os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
-        dirs.append(os.path.join(root, "gpurun_out"))
+    dirs = [os.environ.get("GNNB_RECORDS_DIR") or os.path.join(root, "records")]
+    os.makedirs(dirs[0], exist_ok=True)
     # the wall-clock records of the BaB-loop stand-in (BASELINE config 5) go to a file of their own
     wall = out["records"].pop("bab_loop_wallclock", None)
-    files = [("r06_parity_margins.json", out)] if out["records"] else []
+    files = [("parity_margins.json", out)] if out["records"] else []
     if wall:
-        files.append(("r06_bab_loop_wallclock.json", {k: v for k, v in out.items() if k != "records"} | {
+        files.append(("bab_loop_wallclock.json", {k: v for k, v in out.items() if k != "records"} | {
             "note": "BASELINE config 5 stand-in (no Gurobi / CIFAR-10 here): the reference loop's control flow (relu_conv_gnnkwthreshold.py:126-243) on HiGHS-produced "
                     "inputs; GNN scorer calls timed on the MI355X path (GraphChoice.decision, host tensors in, synchronous) and on the CPU twin of the reference "
                     "path (oracle, 1 thread as scripts/bab_mip.sh:3-5 deploys it); tests/test_gpu_bab_trace.py", "records": wall}))

@@ -1,6 +1,7 @@
 """CPU: the accounting helpers of bench.py (no GPU, no timing): which counter summaries belong to which profile class, the
 SURVEY section 8(d) byte count of message passing, and that the committed counter summaries cover every half-pass kernel class of the
-three bench configurations (otherwise `roofline_message_passing.frac_counter` silently comes out as null)."""
+three bench configurations (otherwise `roofline_message_passing.frac_counter` silently comes out as null); the command line of a plain
+run against a --full one, and what --dump-outputs writes."""
 import json
 import os
 
@@ -44,3 +45,46 @@ def test_committed_counter_summaries_cover_the_half_pass_kernels():
             if cls in ("k_gather", "k_node_update") and not rows:
                 continue                                             # a configuration may not launch a stand-alone gather / node update at all
             assert rows and all(r["hbm_bytes_per_launch"] > 0 for r in rows), (net, cls)
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--no-cpu-baseline"])
+    assert a.full and a.dump_outputs == "out" and a.no_cpu_baseline
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit:
+            continue
+        raise AssertionError(f"{bad} accepted")
+
+
+class _Result:
+    def __init__(self, scores, masks, decisions):
+        self.scores, self.masks, self.decisions = scores, masks, decisions
+
+
+def test_dump_outputs_writes_the_scored_entries_and_samples_past_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    scores = torch.randn(4, 50, generator=g)
+    masks = (torch.rand(4, 50, generator=g) < 0.5).to(torch.int32)
+    dec = torch.randint(0, 50, (4, 2), generator=g, dtype=torch.int32)
+    res = _Result(scores, masks, dec)
+    shapes = bench.dump_outputs(res, str(tmp_path / "a"))
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert sorted(got) == ["decisions", "scores"]
+    assert got["scores"].dtype == np.float32 and got["decisions"].dtype == np.float64
+    assert np.array_equal(got["scores"], np.concatenate([r.numpy() for r in [scores[b][masks[b] != 0] for b in range(4)]]))
+    assert np.array_equal(got["decisions"], dec.numpy())
+    # over the limit: a fixed sample of the scores with its positions, the same on every call, within the limit
+    limit = got["decisions"].nbytes + 12 * 10
+    for d in ("b", "c"):
+        bench.dump_outputs(res, str(tmp_path / d), limit_bytes=limit)
+    idx, s = np.load(tmp_path / "b" / "scores_index.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert idx.dtype == np.float64 and s.dtype == np.float32 and s.size == 10 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(s, got["scores"][idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "scores_index.npy"))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit + 3 * 128    # (+ .npy headers)

@@ -120,25 +120,50 @@ def test_install_without_a_host_project(tmp_path):
     assert out.strip().endswith("ok")
 
 
-REFERENCE = "/root/reference"
+# A stand-in of the host project's BaB driver with the import form the drop-in has to serve: the driver
+# module imports the branch-and-bound helpers, choose_node_conv and GraphChoice by name at import time; graph_score_online imports
+# GraphNet from graphnet.graph_conv.  Stub files of our own, like TREE; torch is imported as a real driver does.
+DRIVER_TREE = {
+    "plnn/__init__.py": "",
+    "plnn/branch_and_bound.py": "import bisect\nimport torch\n\ndef pick_out(*a):\n    pass\n\ndef add_domain(*a):\n    pass\n\n"
+                                "def prune_domains(*a):\n    pass\n",
+    "plnn/kw_score_conv.py": "def choose_node_conv(*a):\n    return 'host'\n",
+    "plnn/modules.py": "class Flatten:\n    origin = 'host'\n",
+    "plnn/relu_conv_gnnkwthreshold.py": textwrap.dedent("""\
+        import torch
+        from plnn.branch_and_bound import pick_out, add_domain, prune_domains
+        from torch import nn
+        from plnn.kw_score_conv import choose_node_conv
+        from graphnet.graph_score import GraphChoice
+        def relu_gnn(*a):
+            return GraphChoice
+        """),
+    "graphnet/__init__.py": "",
+    "graphnet/graph_conv.py": "import torch\nclass GraphNet:\n    origin = 'host'\n",
+    "graphnet/graph_score.py": "class GraphChoice:\n    origin = 'host'\n",
+    "graphnet/graph_score_online.py": "import torch\nfrom graphnet.graph_conv import GraphNet\nclass GraphChoice:\n    origin = 'host-online'\n",
+}
 
 
 def test_reference_driver_imports_after_install(tmp_path):
-    """Authoring container only (the reference tree does not travel): the reference's own BaB driver module imports with the
-    drop-in installed and binds this package's GraphChoice -- the call order INTEGRATION.md section A documents."""
-    import pytest
-    if not os.path.isdir(os.path.join(REFERENCE, "plnn")):
-        pytest.skip("reference tree not present")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REFERENCE, ROOT]), PYTHONDONTWRITEBYTECODE="1")
-    body = textwrap.dedent("""
+    """The host project's BaB driver module (stand-in with the reference driver's import form) imports with the drop-in installed and
+    binds this package's GraphChoice -- the call order INTEGRATION.md section A documents; the host's other graphnet modules stay its own."""
+    host = tmp_path / "host"
+    for rel, text in DRIVER_TREE.items():
+        f = host / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(host), ROOT]), PYTHONDONTWRITEBYTECODE="1")
+    body = textwrap.dedent(f"""
         import gnn_branching_amd
         gnn_branching_amd.install_dropin()
         from plnn.relu_conv_gnnkwthreshold import relu_gnn
         import plnn.branch_and_bound
         import plnn.relu_conv_gnnkwthreshold as m
         assert m.GraphChoice.__module__ == "gnn_branching_amd.graphnet.graph_score"
+        assert relu_gnn() is m.GraphChoice
         import graphnet.graph_score_online as on
-        assert on.__file__.startswith("/root/reference/")
+        assert on.__file__.startswith({str(host) + os.sep!r})
         print("ok")
         """)
     r = subprocess.run([sys.executable, "-c", body], env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))

@@ -178,7 +178,7 @@ def record_wallclock(key, r, extra=None):
     """BASELINE config 5's other half ("wall-clock vs reference CPU GNN path"), for the stand-in: what the loop's scorer calls cost on the
     MI355X path (GraphChoice.decision: host tensors in, decision out, synchronous -- the reference's own call form) and on the CPU twin of
     the reference path (oracle, ONE thread as scripts/bab_mip.sh deploys it), over the same LP inputs; and what the LPs cost (HiGHS here,
-    Gurobi in the reference).  Collected by tests/margins.py into profiles/r06_bab_loop_wallclock.json."""
+    Gurobi in the reference).  Collected by tests/margins.py into records/bab_loop_wallclock.json (profiles/r06_bab_loop_wallclock.json: round 6's)."""
     from tests import margins
     c, res = r["clock"], r["res_a"]
     rec = {"branches": int(res[3]), "lp_solves_posed": int(res[2]), "branches_that_bounded_a_kw_decision": int(res[4]), "branches_that_kept_it": int(res[5]),
