@@ -32,7 +32,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include <chrono>
 #include <thread>
 #include <unistd.h>
 #include <sched.h>
@@ -99,7 +98,6 @@ struct DevGather {          // one conv edge in one direction, as MFMA gather ta
   bool ok = false;
   GatherGeom g;
   float* cmat = nullptr;
-  uint32_t* taps3 = nullptr;   // 32-node tiles: the taps in three bf16 pieces (GatherHost::taps3)
   int* koff = nullptr;
   int* ttab = nullptr;
 };
@@ -165,38 +163,21 @@ struct gnnb_handle {
   bool use_gather = true;       // MFMA gather for conv edges (false: VALU gather kernels)
   // (k_node_update: 12 waves per workgroup = 3 per SIMD with the bf16x3 blocks (142-152 VGPRs, no scratch); the fp32-MFMA-only
   // form (GNNB_BF3=0) needs 167-181 VGPRs and runs 8 waves per workgroup)
-                                // than 8 (16 waves: 27 % slower); k_gather_input_update prefers 8, k_gather 8 x 2 workgroups
-  int gather_occ = 2;           // workgroups per CU for k_gather (its LDS footprint is only the tap matrix)
   bool dense_lds = true;        // Linear edges: one workgroup per sample with the source rows in LDS (false: per-tile kernel)
-  bool restrict_last = true;    // last backward step of layer 1 only for the scored nodes (nothing else reads it)
-  bool s_in_gather = true;      // the sparse gathers compute the bias sums of their edge themselves (fewer k_livesum jobs); GNNB_S_IN_GATHER=0
-  bool zero_dead = false;       // GNNB_ZERO_DEAD=1: always write the zero rows of dead nodes (default: only where something reads them)
-  int giu_occ = 2;              // workgroups per CU of k_gather_input_update (<= 128 VGPRs: two 8-wave workgroups fit)
   bool bf3 = true;              // node update: 64x64 blocks on the bf16 matrix rate with three-piece operands (fp32 accuracy)
-  int gather_sparse = 7;        // gathers behind a ReLU layer walk only the live rows of their window: bit 0 = 16-node forward
-                                // gathers, bit 1 = 32-node gathers, bit 2 = the input-layer gather
-  bool gather16 = true;         // forward conv edges: 16-node tiles on the 16x16x4 MFMA when their window is smaller
   bool embed_fuse = true;       // round 0: the first forward gather computes the input embedding itself (no k_embed, no mu[0] rows)
   int fuse = 1;                 // conv half-passes as ONE kernel (k_gather_update_q: the aggregate never reaches HBM) wherever that kernel
                                 // exists (measured faster at every batch size and on all three networks: base B = 256 0.975 vs 1.014 ms,
                                 // deep B = 1024 6.59 vs 7.31 ms, B = 1 0.344 vs 0.359 ms); GNNB_FUSE=0: always two kernels.  Both forms
                                 // compute the same arithmetic per node -- bit-identical results -- so this is a pure scheduling choice.
-  bool scored_gather = true;    // the restricted last step's aggregate one wave per scored node (k_gather_scored); GNNB_DEV: GNNB_NO_SCORED_GATHER=1
   bool use_top = true;          // fuse the top of the network (last Linear edge, last ReLU layer, property node) into k_top
   bool top_ok = false;          // ... which the bound network allows (set by gnnb_bind_network)
   int clspre_max_b = 1;         // GNNB_CLSPRE_MAX_B: batches up to it classify and run the hoisted feature chains in one launch (k_classify_pre);
                                 // measured (base, us): B = 1 27.5 vs 7.6 + 22.1, B = 2 34.0 vs 30.0, B = 8 42.5 vs 31.8 -- a block's share of
                                 // the ambiguous nodes is uneven, so beyond one subproblem the two kernels' even dealing wins
-  bool gather_bf3 = false;      // GNNB_DEV builds only (GNNB_GATHER_BF3=1): the input update's aggregate on the bf16 matrix rate (rows of layer 1 as three bf16
-                                // pieces, gather_tile_sparse_bf3).  Measured SLOWER (base B=256: 115 -> 140 us, docs/DESIGN_HISTORY.md): not instantiated in the shipped library
   int tail_max_b = 1 << 30;     // GNNB_TAIL_MAX_B: batches up to it end in k_scored_tail (scored gather + restricted update + score head in one launch); 0: three kernels
   bool top_fuse_upd = true;     // GNNB_TOP_FUSE_UPD=0: the backward node update of layer L-1 as its own launch behind k_top (it runs inside k_top otherwise)
   int top_split_max = 4;        // GNNB_TOP_SPLIT: 4 (default) = four workgroups per sample while B <= n_cu / 4, two while B <= n_cu / 2; 2 = two at most; 1 = never
-  int per_sample_min_b = 0;     // GNNB_PER_SAMPLE_MIN_B: batches below it take the per-tile dense kernel + separate launches
-                                // instead of the one-workgroup-per-sample kernels (k_top, k_dense_*_lds), which need a batch
-                                // that fills the CUs (B=2: 0.40 vs 0.49 ms, B=64: 0.64 vs 0.66, B=128: 0.96 vs 0.88 ms; 96 is
-                                // the break-even).  Off by default: the two paths round differently, and with one path for
-                                // every batch size a sample's scores do not depend on what it is batched or sharded with.
   Packs packs;
   std::vector<float> blob;      // the GNN parameters as handed to gnnb_create / gnnb_set_weights / left by gnnb_online_step
   gnnb_train::Trainer* trainer = nullptr;     // online learning (gnnb_online_create)
@@ -249,15 +230,8 @@ static int upload(float** d, const float* h, size_t n) {
 
 // (re)build the operand packs of the scorer from a parameter blob and put them on the device
 static int load_weights(gnnb_t* h, const float* w_blob, hipStream_t st) {
-#ifdef GNNB_DEV
-  static const bool timing = std::getenv("GNNB_PACK_TIMING") != nullptr;       // dev aid: where the time of this call goes, to stderr
-#else
-  constexpr bool timing = false;
-#endif
-  const auto t_start = std::chrono::steady_clock::now();
   h->blob.assign(w_blob, w_blob + blob_floats());
   build_packs(h->blob.data(), h->packs);
-  const auto t_built = std::chrono::steady_clock::now();
   const std::vector<float>* pv[N_PACKS] = {&h->packs.embed, &h->packs.pre_fwd, &h->packs.pre_bwd, &h->packs.pre_inp, &h->packs.prop,
                                            &h->packs.upd_fwd_e, &h->packs.upd_fwd_i, &h->packs.upd_fwd_f, &h->packs.upd_bwd,
                                            &h->packs.upd_bwd_b, &h->packs.upd_inp, &h->packs.post_inp, &h->packs.score_b,
@@ -284,13 +258,7 @@ static int load_weights(gnnb_t* h, const float* w_blob, hipStream_t st) {
     off += (pv[i]->size() + 63) & ~(size_t)63;
   }
   HIPCHK(hipMemcpyAsync(h->d_pack[0], h->pack_stage, total * sizeof(float), hipMemcpyHostToDevice, st));
-  const auto t_issued = std::chrono::steady_clock::now();
   HIPCHK(hipStreamSynchronize(st));       // the staging buffer is reused by the next call
-  if (timing) {
-    const auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    fprintf(stderr, "load_weights: build %.0f us, stage+issue %.0f us (%zu KiB), wait %.0f us\n", us(t_start, t_built), us(t_built, t_issued),
-            total * sizeof(float) / 1024, us(t_issued, std::chrono::steady_clock::now()));
-  }
   return 0;
 }
 
@@ -367,26 +335,6 @@ extern "C" int gnnb_get_option(const gnnb_t* h, const char* name, int* value) {
   *value = bf ? (*bf ? 1 : 0) : *f;
   return GNNB_OK;
 }
-#ifdef GNNB_DEV
-// development builds (-DGNNB_DEV: tools/ablate) keep environment overrides for A/B runs of paths the shipped library does not expose
-static void dev_env_overrides(gnnb_t* h) {
-  if (const char* e = getenv("GNNB_ZERO_DEAD")) h->zero_dead = e[0] == '1';
-  if (const char* e = getenv("GNNB_S_IN_GATHER")) h->s_in_gather = e[0] != '0';
-  if (const char* e = getenv("GNNB_GIU_OCC")) h->giu_occ = atoi(e) < 1 ? 1 : atoi(e);
-  if (const char* e = getenv("GNNB_GATHER_OCC")) h->gather_occ = atoi(e) < 1 ? 1 : atoi(e);
-  if (const char* e = getenv("GNNB_NO_GATHER16")) h->gather16 = !(e[0] == '1');
-  if (const char* e = getenv("GNNB_SPARSE")) h->gather_sparse = atoi(e);
-  if (const char* e = getenv("GNNB_NO_RESTRICT")) h->restrict_last = !(e[0] == '1');
-  if (const char* e = getenv("GNNB_NO_SCORED_GATHER")) h->scored_gather = !(e[0] == '1');
-  if (const char* e = getenv("GNNB_PER_SAMPLE_MIN_B")) h->per_sample_min_b = atoi(e);
-  if (const char* e = getenv("GNNB_GATHER_BF3")) h->gather_bf3 = e[0] == '1';
-  for (int i = 0; i < gnnb_option_count(); ++i) {      // GNNB_OPT_<NAME>=<int> for every option of the table
-    std::string k = std::string("GNNB_OPT_") + kOptions[i].name;
-    for (auto& c : k) c = (char)toupper((unsigned char)c);
-    if (const char* e = getenv(k.c_str())) (void)gnnb_set_option(h, kOptions[i].name, atoi(e));
-  }
-}
-#endif
 
 extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, int T, int p) {
   if (!out || !w_blob) return fail(GNNB_E_INVALID, "gnnb_create: null argument");
@@ -428,13 +376,8 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   HIPCHK(hipFuncSetAttribute((const void*)k_gather16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
   HIPCHK(hipFuncSetAttribute((const void*)k_gather16<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
   HIPCHK(hipFuncSetAttribute((const void*)k_livesum, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifdef GNNB_DEV
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
   HIPCHK(hipFuncSetAttribute((const void*)k_gather<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
 
 #define FUSEDQ_ATTR(L, S, P) HIPCHK(hipFuncSetAttribute((const void*)k_gather_update_q<L, S, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
@@ -445,9 +388,6 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   HIPCHK(hipFuncSetAttribute((const void*)k_top<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_top<2>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_top<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
-#ifdef GNNB_DEV
-  dev_env_overrides(h);
-#endif
   *out = h;
   return GNNB_OK;
 }
@@ -481,7 +421,6 @@ static void free_network(gnnb_t* h) {
   for (auto* v : {&h->gf, &h->gb})
     for (auto& d : *v) {
       if (d.cmat) (void)hipFree(d.cmat);
-      if (d.taps3) (void)hipFree(d.taps3);
       if (d.koff) (void)hipFree(d.koff);
       if (d.ttab) (void)hipFree(d.ttab);
     }
@@ -667,14 +606,10 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
       for (int dir = 0; dir < 2; ++dir) {
         GatherHost gh;
         // the input layer's transposed gather is fused with its feature chain and update (132 MFMAs per tile)
-        if (!build_gather(h->edges[k], dir, dir == 1 && k > 1, gh, (dir == 1 && k == 1) ? 132 : 0, h->gather16)) continue;
+        if (!build_gather(h->edges[k], dir, dir == 1 && k > 1, gh, (dir == 1 && k == 1) ? 132 : 0, /*allow16=*/true)) continue;
         DevGather& d = dir == 0 ? h->gf[k] : h->gb[k];
         d.g = gh.g;
         if (int rc = upload(&d.cmat, gh.cmat.data(), gh.cmat.size())) return rc;
-        if (!gh.taps3.empty()) {
-          HIPCHK(hipMalloc((void**)&d.taps3, gh.taps3.size() * sizeof(uint32_t)));
-          HIPCHK(hipMemcpy(d.taps3, gh.taps3.data(), gh.taps3.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
         HIPCHK(hipMalloc((void**)&d.koff, gh.koff.size() * sizeof(int)));
         HIPCHK(hipMemcpy(d.koff, gh.koff.data(), gh.koff.size() * sizeof(int), hipMemcpyHostToDevice));
         {
@@ -718,7 +653,7 @@ static DTileMap to_dtm(const TileMap& t) {
 static DGather to_dg(const DevGather& d, const float* zero) {
   const GatherGeom& g = d.g;
   return DGather{d.cmat, reinterpret_cast<const int2*>(d.koff), d.ttab, zero, g.K2, g.tm.NCG * g.K2, g.Hs, g.Ws, g.Ns, g.ystep, g.ybase,
-                 g.xstep, g.xbase, g.WY, g.WX, g.normalise, g.kh, g.kw, g.stride, g.pad, g.lanes, reinterpret_cast<const uint2*>(d.taps3)};
+                 g.xstep, g.xbase, g.WY, g.WX, g.normalise, g.kh, g.kw, g.stride, g.pad, g.lanes};
 }
 static size_t gather_lds_bytes(const DevGather& d, size_t pack_floats) {
   return (pack_floats + (size_t)d.g.tm.NCG * d.g.K2 * 64) * 4 + (size_t)gather_slots(d.g.K2, d.g.lanes) * 12 + (size_t)((d.g.tm.TPS + 3) & ~3) * 4;
@@ -770,7 +705,7 @@ static int fusedq_qtiles(const DevGather& d, bool sparse, bool post) {
 }
 static bool fusedq_ok(const gnnb_t* h, const DevGather& d, int src_layer, bool embed_src, bool post) {
   if (h->fuse == 0 || !h->bf3 || !d.ok) return false;
-  const bool sparse = (h->gather_sparse & (d.g.lanes == 16 ? 1 : 2)) && !embed_src && src_layer >= 1;
+  const bool sparse = !embed_src && src_layer >= 1;
   if (src_layer >= 1 && !sparse) return false;
   if (d.g.lanes == 32 && !sparse) return false;
   if (d.g.lanes == 16 && post) return false;
@@ -836,7 +771,6 @@ struct WsLayout {                // plain arrays: gnnb_forward computes it on it
   size_t lf[MAXL + 2];          // live flags (B, N_k) as floats
   size_t sf[MAXL + 2], sb[MAXL + 2];   // k_livesum outputs: sf[k] (B, N_k) over edge k, sb[k] (B, N_k) over edge k+1 transposed
   size_t F1 = 0;                // rows of layer 1 after the producer-side map of the input update (PackPostInp)
-  size_t F3 = 0;                // the same as three bf16 pieces (rows3): what the input update's bf16 x 3 aggregate reads
   size_t cnt = 0, best = 0, nb = 0, Q = 0, total = 0;     // best: B 64-bit decision keys + the finished-workgroup counter of k_score
   size_t topflag = 0, topx = 0;                           // k_top's workgroup split: arrival counters, (B, 8, 64) exchange buffer
 };
@@ -866,7 +800,6 @@ static WsLayout ws_layout(const gnnb_t* h, int B) {
   for (int k = 1; k < K; ++k) { w.sf[k] = off; off += align64((size_t)B * h->N[k]); }
   for (int k = 0; k < K - 1; ++k) { w.sb[k] = off; off += align64((size_t)B * h->N[k]); }
   w.F1 = off; off += align64((size_t)B * h->N[1] * 64);
-  w.F3 = off; off += h->gather_bf3 ? align64((size_t)B * h->N[1] * ROW3_FLOATS) : 0;      // rows3 of layer 1: only the opt-in GNNB_GATHER_BF3=1 path writes / reads them (base B=256: 400 MB)
   w.Q = off; off += (size_t)map_tiles(bwd_map(h, 0), B) * 2048;
   w.total = off;
   return w;
@@ -1055,40 +988,35 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
   const int total_halfpasses = 2 * h->T;
   const int limit = h->halfpass_limit > 0 ? std::min(h->halfpass_limit, total_halfpasses) : total_halfpasses;
   const bool debug_full = h->halfpass_limit > 0;   // with a limit set nothing is restricted or skipped as dead
-  const bool per_sample = B >= h->per_sample_min_b;   // batch large enough for the one-workgroup-per-sample kernels
   // The rows of layer 1 the input-layer update aggregates went through its 64x64 map on the producer side (PackPostInp).
   // Outside inspection runs nothing else reads the plain rows of that half-pass, so the mapped rows simply take their place
   // in mu[1] (whose dead rows k_classify already zeroed); inspection runs keep both, the mapped ones in F1.
   float* const rows1_for_input = debug_full ? ws + w.F1 : mu(1);
-
-  // the input update's aggregate on the bf16 matrix rate: needs the sparse 32-node walk, the bf16 x 3 blocks and a producer that writes F as
-  // three pieces (the POST block of layer 1's backward update); inspection runs keep fp32 rows
-  const bool input_rows3 = h->gather_bf3 && h->bf3 && !debug_full && h->gb[1].ok && h->gb[1].taps3 && h->gb[1].g.lanes == 32 && (h->gather_sparse & 4);
   const bool embed_in_gather = h->embed_fuse && !debug_full && h->gf[1].ok;
-  const bool top_fused = h->use_top && h->bf3 && h->top_ok && !debug_full && per_sample;      // (k_top only exists on the bf16 x 3 rate)
+  // The one-workgroup-per-sample kernels (k_top, k_dense_*_lds) run at every batch size, although a small batch leaves CUs idle
+  // (per-tile kernels vs these: B=2 0.40 vs 0.49 ms, B=128 0.96 vs 0.88 ms): the two paths round differently, and with one path
+  // for every batch size a sample's scores do not depend on what it is batched or sharded with.
+  const bool top_fused = h->use_top && h->bf3 && h->top_ok && !debug_full;      // (k_top only exists on the bf16 x 3 rate)
   // The rows of dead nodes are zero by definition (mu = (.) * live).  Every default consumer of a layer's rows walks only the
   // live ones (sparse gathers, the compacted Linear edges of k_top, the score head), so nothing needs them in memory; they
   // are written (k_classify) only for a layer with a consumer that reads every row: VALU / non-sparse gathers, the
   // per-sample / per-tile dense kernels, k_prop, inspection runs.
   auto reads_live_rows_only = [&](int e, bool transposed) {      // edge e between layers e-1 and e; transposed: reads layer e
     if (e == L && top_fused) return transposed || TOP_LIST_OK(h->edges[L].n_in);
-    const DevGather& d = transposed ? h->gb[e] : h->gf[e];
-    if (!d.ok) return false;
-    if (transposed && e == 1) return (h->gather_sparse & 4) != 0;
-    return (h->gather_sparse & (d.g.lanes == 16 ? 1 : 2)) != 0;
+    return (transposed ? h->gb[e] : h->gf[e]).ok;
   };
   // k_top's Linear edges walk live rows only (when their lists fit, top_sample `compact` / `keep`), so they produce the bias sums
   // of edge L in both directions themselves and k_livesum skips those jobs
-  const bool s1_table = h->s_in_gather && L >= 2 && h->d_s1 != nullptr;      // bias sums of edge 1 forward: bind-time table
+  const bool s1_table = L >= 2 && h->d_s1 != nullptr;      // bias sums of edge 1 forward: bind-time table
   const int topK = L >= 1 && h->edges[L].kind == 1 ? h->edges[L].n_in : 0;
-  const bool top_s_fwd = top_fused && h->s_in_gather && TOP_LIST_OK(topK);
-  const bool top_s_bwd = top_fused && h->s_in_gather && TOP_LIST_KEEP_OK(topK) && limit >= 2;
+  const bool top_s_fwd = top_fused && TOP_LIST_OK(topK);
+  const bool top_s_bwd = top_fused && TOP_LIST_KEEP_OK(topK) && limit >= 2;
   // k_top also runs the backward node update of layer L-1 on its transposed edge's row tiles (the aggregate never reaches memory):
   // needs the kept live-row list (B2 then walks live rows only) and a layer L-1 that is not layer 1 (whose update has the
   // restricted / input-mapping forms)
   const bool top_upd = top_fused && h->top_fuse_upd && L >= 3 && TOP_LIST_KEEP_OK(topK);
   auto zero_dead_rows = [&](int k) {
-    if (debug_full || h->zero_dead) return true;
+    if (debug_full) return true;
     if (k == L) return !top_fused;                                // k_top writes every row of layer L itself
     return !(reads_live_rows_only(k + 1, false) && reads_live_rows_only(k, true));
   };
@@ -1142,11 +1070,10 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
       maxw = std::max(maxw, j.wlds);
     };
     // edges whose aggregate comes from a sparse gather get their bias sums from that gather (GArgs.sout / GIArgs.s_from_gather)
-    auto gather_has_s = [&](const DevGather& d, int bit) { return h->s_in_gather && d.ok && (h->gather_sparse & bit) != 0; };
     for (int k = 1; k <= L; ++k) {            // forward edge k: source layer k-1 (the input layer is all live)
       const Edge& e = h->edges[k];
       if (k == 1 && s1_table) continue;
-      if (k >= 2 && gather_has_s(h->gf[k], h->gf[k].g.lanes == 16 ? 1 : 2)) continue;
+      if (k >= 2 && h->gf[k].ok) continue;
       if (k == L && top_s_fwd) continue;
       push(e.kind == 0 ? 0 : 1, e, e.kind == 0 ? h->dev[k].w_fwd : h->dev[k].w_bwd, h->dev[k].ld_bwd, k > 1 ? ws + w.lf[k - 1] : nullptr,
            ws + w.sf[k], h->N[k], h->N[k - 1], 0);
@@ -1154,7 +1081,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     if (limit >= 2)
       for (int k = 0; k < L; ++k) {           // edge k+1 transposed: source layer k+1
         const Edge& e = h->edges[k + 1];
-        if (k == 0 ? gather_has_s(h->gb[1], 4) : gather_has_s(h->gb[k + 1], h->gb[k + 1].g.lanes == 16 ? 1 : 2)) continue;
+        if (h->gb[k + 1].ok) continue;
         if (k == L - 1 && top_s_bwd) continue;
         push(e.kind == 0 ? 2 : 3, e, h->dev[k + 1].w_bwd, h->dev[k + 1].ld_bwd, ws + w.lf[k + 1], ws + w.sb[k], h->N[k], h->N[k + 1],
              k >= 1 ? 1 : 0);
@@ -1207,14 +1134,15 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
   };
   auto gather = [&](const DevGather& d, int k, const float* src, bool scored, bool embed_src, int src_layer, float* sout) {      // phase A over a conv edge, MFMA
     const long nt = map_tiles(d.g.tm, B);
-    // sparse: a 16-node forward gather behind a ReLU layer skips the (zero) rows of that layer's dead nodes
-    const bool sparse = (h->gather_sparse & (d.g.lanes == 16 ? 1 : 2)) && !embed_src && src_layer >= 1;
+    // sparse: a gather behind a ReLU layer skips the (zero) rows of that layer's dead nodes
+    const bool sparse = !embed_src && src_layer >= 1;
     GArgs a{in->lb[k], in->ub[k], in->mask, src, nb, nt, scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
             EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr, sparse ? in->ub[src_layer] : nullptr,
-            sparse && h->s_in_gather ? sout : nullptr};
+            sparse ? sout : nullptr};
     const size_t lds = gather_lds_bytes(d, 0) + (sparse ? sparse_tab_bytes(d) : 0) + (d.g.lanes == 16 ? 16 + (size_t)WAVES_MLP * STAGE16_FLOATS * 4 : 0);
+    constexpr int kGatherOcc = 2;     // workgroups per CU (k_gather's launch bounds; its LDS footprint is only the tap matrix)
     long grid = (nt + WAVES_MLP - 1) / WAVES_MLP;
-    if (grid > (long)h->n_cu * h->gather_occ) grid = (long)h->n_cu * h->gather_occ;
+    if (grid > (long)h->n_cu * kGatherOcc) grid = (long)h->n_cu * kGatherOcc;
     lz.run(PC_GATHER, [&] {
       if (d.g.lanes == 16) {
         if (embed_src) hipLaunchKernelGGL((k_gather16<true>), dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
@@ -1241,7 +1169,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
       });
     } else {
       const DevEdge& de = h->dev[k];
-      if (h->dense_lds && per_sample && de.mt_fwd <= 4) {        // one workgroup per sample, source rows staged in LDS
+      if (h->dense_lds && de.mt_fwd <= 4) {        // one workgroup per sample, source rows staged in LDS
         DenseLArgs a{de.w_fwd, mu(k - 1), nb, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
         lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(k_dense_fwd_lds, dim3(B), dim3(512), 0, st, a); });
         return;
@@ -1259,13 +1187,13 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     const Edge& e = h->edges[k + 1];
     // the input layer (k = 0) aggregates the rows of layer 1 that already went through its 64x64 map (PackPostInp)
     const float* srcb = k == 0 ? rows1_for_input : mu(k + 1);
-    if (k >= 1 && scored && h->gb[k + 1].ok && h->scored_gather && (h->gather_sparse & 2) &&
+    if (k >= 1 && scored && h->gb[k + 1].ok &&
         e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride) <= GS_SLOT_LIMIT) {
       // the restricted last step as three kernels (GNNB_TAIL_MAX_B=0; the default is k_scored_tail): one wave per scored node instead of
       // every tile that holds one (k_gather_scored).  Windows up to GS_SLOT_LIMIT source nodes (base, 64 slots: 31 vs 38 us for the tile
       // gather; deep 18 vs 38; wide, 128 slots: 116 vs 99 -- kept on the list-driven form all the same, so that this path and
       // k_scored_tail evaluate a scored node's aggregate with the same arithmetic)
-      GSArgs a{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], nb, h->s_in_gather ? ws + w.sb[k] : nullptr,
+      GSArgs a{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], nb, ws + w.sb[k],
                h->N[k], e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
       lz.run(PC_GATHER, [&] { hipLaunchKernelGGL(k_gather_scored, dim3((unsigned)h->n_cu * 4), dim3(GS_WAVES * 64), 0, st, a); });
       return;
@@ -1283,7 +1211,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
       });
     } else {
       const DevEdge& de = h->dev[k + 1];
-      if (h->dense_lds && per_sample && de.kpad_bwd <= 128) {    // one workgroup per sample, the whole source layer in LDS
+      if (h->dense_lds && de.kpad_bwd <= 128) {    // one workgroup per sample, the whole source layer in LDS
         DenseLArgs a{de.w_bwd, srcb, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
         lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(k_dense_bwd_lds, dim3(B), dim3(512), 0, st, a); });
         return;
@@ -1317,8 +1245,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     // normal: list0 = live non-ambiguous nodes (short chain), list1 = ambiguous nodes; restricted: the scored nodes, general chain
     UpdArgs a{h->d_pack[pack], in->lb[k], in->ub[k], nb, ws + (fwd ? w.Pf[k] : w.Pb[k]), (post_input && !debug_full) ? nullptr : mu(k), status,
               ilist(w.live[k]), cnt + 4 * k + (scored ? 3 : 0), ilist(scored ? w.score[k] : w.amb[k]), cnt + 4 * k + (scored ? 2 : 1), sarr, smod,
-              post_input ? rows1_for_input : nullptr, nullptr, nullptr};
-    if (post_input && input_rows3) a.post3 = ws + w.F3;
+              post_input ? rows1_for_input : nullptr, nullptr};
     a.wp = h->d_pack[PK_POST_INP] + (h->bf3 ? (h->gb[1].ok ? PackPostInp::WPG3 : PackPostInp::WPN3) : (h->gb[1].ok ? PackPostInp::WPG : PackPostInp::WPN));
     return a;
   };
@@ -1360,14 +1287,14 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     const int src_layer = fwd ? k - 1 : k + 1;
     const bool embed_src = fwd && k == 1 && embed_in_gather && proj[0] == L_INP_F_1;
     if (!fusedq_ok(h, d, src_layer, embed_src, post_input)) return false;
-    const bool sparse = (h->gather_sparse & (d.g.lanes == 16 ? 1 : 2)) && !embed_src && src_layer >= 1;
+    const bool sparse = !embed_src && src_layer >= 1;
     const long nt = map_tiles(d.g.tm, B);
     {
       const int nq = fusedq_qtiles(d, sparse, post_input);
       const size_t ldsq = fusedq_lds_bytes(d, sparse, post_input, nq);
       FArgs a{};
       float* sout = fwd ? ws + w.sf[k] : ws + w.sb[k];
-      a.sw_from_gather = sparse && h->s_in_gather ? 1 : 0;
+      a.sw_from_gather = sparse ? 1 : 0;
       a.g = GArgs{in->lb[k], in->ub[k], in->mask, fwd ? mu(k - 1) : mu(k + 1), nb, nt, 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
                   EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr, sparse ? in->ub[src_layer] : nullptr,
                   a.sw_from_gather ? sout : nullptr};
@@ -1392,23 +1319,16 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     if (h->gb[1].ok) {
       const DevGather& d = h->gb[1];
       const long nt = map_tiles(d.g.tm, B);
-      const bool sparse = (h->gather_sparse & 4) != 0;
+      // the sparse walk over the live rows of layer 1, which also yields the bias sums (s_from_gather)
       GIArgs a{h->d_pack[PK_PRE_INP], h->d_pack[PK_UPD_INP], in->lb[0], in->ub[0], rows1_for_input, ws + w.sb[0], mu(0), nt, to_dtm(d.g.tm), to_dg(d, h->d_zero),
-               in->lb[1], in->ub[1], sparse && h->s_in_gather ? 1 : 0, (sparse && input_rows3) ? (const void*)(ws + w.F3) : nullptr};
-      const bool r3 = a.mu_src3 != nullptr;
-      const int nw = r3 ? GIU_R3_WAVES : WAVES_MLP;
-      const size_t lds = gather_lds_bytes(d, PackUpdInp::FLOATS + PackPreInp::FLOATS) +
-                         (sparse ? 8 + (size_t)nw * (2 * d.g.K2 + 32) * 8 : 0) + (r3 ? (size_t)d.g.tm.NCG * d.g.K2 * 128 * 4 : 0);
-      long giu_grid = (nt + nw - 1) / nw;
-      if (giu_grid > (long)h->n_cu * (r3 ? 1 : h->giu_occ)) giu_grid = (long)h->n_cu * (r3 ? 1 : h->giu_occ);
+               in->lb[1], in->ub[1], 1};
+      const size_t lds = gather_lds_bytes(d, PackUpdInp::FLOATS + PackPreInp::FLOATS) + 8 + (size_t)WAVES_MLP * (2 * d.g.K2 + 32) * 8;
+      constexpr int kGiuOcc = 2;        // workgroups per CU (<= 128 VGPRs: two 8-wave workgroups fit)
+      long giu_grid = (nt + WAVES_MLP - 1) / WAVES_MLP;
+      if (giu_grid > (long)h->n_cu * kGiuOcc) giu_grid = (long)h->n_cu * kGiuOcc;
       lz.run(PC_GATHER_INPUT, [&] {
-#ifdef GNNB_DEV
-        if (r3) { hipLaunchKernelGGL((k_gather_input_update<true, true, true>), dim3(giu_grid), dim3(GIU_R3_WAVES * 64), lds, st, a); return; }
-#endif
-        if (sparse && h->bf3) hipLaunchKernelGGL((k_gather_input_update<true, true>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
-        else if (sparse) hipLaunchKernelGGL((k_gather_input_update<true, false>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
-        else if (h->bf3) hipLaunchKernelGGL((k_gather_input_update<false, true>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
-        else hipLaunchKernelGGL((k_gather_input_update<false, false>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
+        if (h->bf3) hipLaunchKernelGGL((k_gather_input_update<true, true>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
+        else hipLaunchKernelGGL((k_gather_input_update<true, false>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
       });
       return;
     }
@@ -1460,8 +1380,8 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
   TailArgs tail{};
   auto try_tail = [&](int k) -> bool {
     const Edge& e = h->edges[k + 1];
-    if (!(B <= h->tail_max_b && h->bf3 && k == 1 && L >= 2 && h->restrict_last && !debug_full && e.kind == 0 && h->gb[k + 1].ok && h->scored_gather &&
-          (h->gather_sparse & 2) && e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride) <= GS_SLOT_LIMIT &&
+    if (!(B <= h->tail_max_b && h->bf3 && k == 1 && L >= 2 && !debug_full && e.kind == 0 && h->gb[k + 1].ok &&
+          e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride) <= GS_SLOT_LIMIT &&
           h->N[k + 1] < 65536))
       return false;
     tail.g = GSArgs{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], nullptr, nullptr,
@@ -1484,7 +1404,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
       top();                                     // F1 .. B2: both half-passes of layer L, aggregate of layer L-1 in `nb`
       for (int k = L - 1; k >= 1; --k) {
         if (k == L - 1 && top_upd) { proj[k] = L_BC4_1; continue; }      // done inside k_top
-        const bool scored = h->restrict_last && t == h->T - 1 && k == 1;
+        const bool scored = t == h->T - 1 && k == 1;
         if (scored && k < L - 1 && try_tail(k)) continue;
         if (k < L - 1 && !scored && fused_halfpass(k, false, k == 1 && t < h->T - 1)) continue;
         if (k < L - 1) agg_bwd(k, 1, scored);
@@ -1511,7 +1431,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     // backward sweep (:222-350), Gauss-Seidel order: layer k reads the already-updated mu[k+1]
     for (int k = L; k >= 1; --k) {
       // after the last backward step mu[1] is only read by the score head, i.e. at the scored nodes
-      const bool scored = h->restrict_last && !debug_full && t == h->T - 1 && k == 1;
+      const bool scored = !debug_full && t == h->T - 1 && k == 1;
       if (k < L && !scored && fused_halfpass(k, false, k == 1 && t < h->T - 1)) continue;
       if (k < L) agg_bwd(k, 1, scored);          // (k == L: k_prop already wrote the aggregate from the property node)
       node_update(k, false, scored, k == 1 && (t < h->T - 1 || debug_full));

@@ -126,10 +126,7 @@ __device__ __forceinline__ void upd_chain_frag(const UpdArgs& u, const float* ld
 #pragma unroll
     for (int R = 0; R < 32; ++R) FRAG_AT(H, R) = 0.0f;
     gemm_w64_bf3<1, PIPE>(lds + PackUpdL3::FLOATS, lane, H, [&](int s) { return FRAG_AT(H2, s); });
-    if (valid) {
-      if (u.post3) frag_store_rows3(H, u.post3, gc, h);
-      else frag_store_rows(H, u.post, gc, h);
-    }
+    if (valid) frag_store_rows(H, u.post, gc, h);
   }
 }
 

@@ -77,21 +77,8 @@ inline size_t w64_floats(int nfrag) { return (size_t)4096 * nfrag; }
 // fp64 as the fp32 MFMA) at a quarter of the matrix-pipe time.  k-step ks of input fragment f covers fragment registers
 // 8 ks .. 8 ks + 7, i.e. features 64 f + frag_feature(8 ks + j, h): entry ((f*4 + ks)*2 + ot)*3 + piece holds, for lane
 // (r, h), the 8 bf16 of W[32 ot + r][col0 + 64 f + frag_feature(8 ks + j, h)], j = 0..7 (16 bytes: one ds_read_b128).
-inline unsigned short bf16_rne(float f) {
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));   // inf / nan
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-inline float bf16_f32(unsigned short b) {
-  const unsigned u = (unsigned)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
 inline size_t w64_bf3_floats(int nfrag) { return (size_t)6144 * nfrag; }
-// three bf16 pieces of 512 weights: o[p * 512 + i] = piece p of w[i] (bf16_rne's rounding, branch-free so that it vectorises)
+// three bf16 pieces of 512 weights: o[p * 512 + i] = piece p of w[i] (round to nearest even, inf / nan kept; branch-free so that it vectorises)
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 __attribute__((target_clones("avx512f", "avx2", "default")))
 #endif
@@ -384,15 +371,8 @@ inline void build_packs(const float* blob, Packs& pk) {
   std::thread helper[2];
   bool threaded[2] = {false, false};
 #ifndef GNNB_PACK_NO_THREADS
-#ifdef GNNB_DEV
-  static const bool use_threads = [] { const char* e = std::getenv("GNNB_PACK_THREADS"); return !e || std::atoi(e) != 0; }();
-#else
-  constexpr bool use_threads = true;
-#endif
-  if (use_threads) {
-    try { helper[0] = std::thread(upd_e_i); threaded[0] = true; } catch (const std::system_error&) {}
-    try { helper[1] = std::thread(upd_f_b); threaded[1] = true; } catch (const std::system_error&) {}
-  }
+  try { helper[0] = std::thread(upd_e_i); threaded[0] = true; } catch (const std::system_error&) {}
+  try { helper[1] = std::thread(upd_f_b); threaded[1] = true; } catch (const std::system_error&) {}
 #endif
   struct Join {
     std::thread* t; bool* on;
@@ -560,7 +540,6 @@ struct GatherHost {
   GatherGeom g;
   std::vector<float> cmat;       // [NCG][K2][64]: column of slot k, dst lane j: (k / spk) * 64 + (k % spk) * lanes + j, spk = 64 / lanes
   std::vector<int32_t> koff;     // [spk*K2 + pad][2]: {row offset relative to the window origin, wy | wx << 16}
-  std::vector<uint32_t> taps3;   // 32-node tiles: [NCG][2 K2 slots][32 dst][2]: the taps in three bf16 pieces {p1 | p2 << 16, p3} (the bf16 x 3 gathers)
   long mfma_per_sample = 0;      // in units of one 32x32x2 MFMA (64 cycles): 2 per k-step
 };
 
@@ -632,24 +611,6 @@ inline void fill_gather_tables(const Edge& e, int dir, GatherHost& out) {
         out.cmat[((size_t)cg * g.K2 + sidx) * 64 + h * g.lanes + j] = w;
       }
     }
-  // the same taps as three bf16 pieces (w = p1 + p2 + p3 to 24 bits, round to nearest each time: pack_w64_bf3's split), by window slot:
-  // entry (cg, slot, dst j) sits where the sparse walk's table points with the offset it uses for cmat (slot * 32 + j)
-  out.taps3.clear();
-  if (g.lanes == 32) {
-    out.taps3.assign((size_t)g.tm.NCG * g.K2 * 64 * 2, 0u);
-    for (int cg = 0; cg < g.tm.NCG; ++cg)
-      for (int sl = 0; sl < 2 * g.K2; ++sl)
-        for (int j = 0; j < 32; ++j) {
-          const float w = out.cmat[((size_t)cg * g.K2 + sl / 2) * 64 + (sl % 2) * 32 + j];
-          const unsigned short p1 = bf16_rne(w);
-          const float r1 = w - bf16_f32(p1);
-          const unsigned short p2 = bf16_rne(r1);
-          const unsigned short p3 = bf16_rne(r1 - bf16_f32(p2));
-          const size_t o = (((size_t)cg * 2 * g.K2 + sl) * 32 + j) * 2;
-          out.taps3[o] = (uint32_t)p1 | ((uint32_t)p2 << 16);
-          out.taps3[o + 1] = (uint32_t)p3;
-        }
-  }
 }
 
 // pick the tile shape with the fewest MFMAs per sample

@@ -389,11 +389,6 @@ class ScorerEngine:
         self._ws = {}
         self._prop_cache = {}
         self._prop_host_cache = None
-        # a large batch can be cut into `n_streams` contiguous chunks on separate HIP streams; measured slower at every size tried
-        # (base B=256: 1 stream 0.84 ms, 2 streams 0.90: every kernel's fixed part is paid twice), so 1 unless a caller sets the attribute
-        self.n_streams = 1
-        self.min_chunk = 64
-        self._streams = []
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -486,8 +481,8 @@ class ScorerEngine:
         self._prop_cache[key] = (vkey, pw, pb, list(prop_layers))
         return pw, pb
 
-    def workspace(self, B, slot=0):
-        ws = self._ws.get((B, slot))
+    def workspace(self, B):
+        ws = self._ws.get(B)
         if ws is None:
             n = self.lib.gnnb_workspace_bytes(self.h, B)
             if n == 0:
@@ -495,7 +490,7 @@ class ScorerEngine:
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             if len(self._ws) > 6:
                 self._ws.clear()
-            self._ws[(B, slot)] = ws
+            self._ws[B] = ws
         return ws
 
     def _marshal(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks):
@@ -530,51 +525,26 @@ class ScorerEngine:
         return B, lbs, ubs, duals, prim, x_lp, mask, pw, pb
 
     def forward(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks, status=None):
-        """status: optional preallocated device int32 tensor; the forward's status words go to its first element(s), further elements
-        (HostFedPipeline: the scatter launch's word) are left to the caller and OR-ed in by ForwardResult.check()."""
+        """One gnnb_forward call on the current stream.  status: optional preallocated device int32 tensor; the forward's status word
+        goes to element 0, further elements (HostFedPipeline: the scatter launch's word) are left to the caller and OR-ed in by
+        ForwardResult.check()."""
         B, lbs, ubs, duals, prim, x_lp, mask, pw, pb = self._marshal(lower_bounds_all, upper_bounds_all, dual_vars, primals,
                                                                      primal_inputs, layers, masks)
         scores = torch.empty(B, self.R, dtype=torch.float32, device=self.device)
         dec = torch.empty(B, 2, dtype=torch.int32, device=self.device)
-        nchunk = self.n_streams if (self.n_streams > 1 and B >= self.n_streams * self.min_chunk) else 1
         if status is None:
-            status = torch.empty(nchunk, dtype=torch.int32, device=self.device)
-        elif status.numel() < nchunk or status.dtype != torch.int32 or status.device != self.device:
-            raise ValueError("forward: `status` must be a device int32 tensor with one element per chunk")
+            status = torch.empty(1, dtype=torch.int32, device=self.device)
+        elif status.numel() < 1 or status.dtype != torch.int32 or status.device != self.device:
+            raise ValueError("forward: `status` must be a device int32 tensor with at least one element")
         mask2 = mask.view(B, self.R)
-        bounds = [(B * c) // nchunk for c in range(nchunk + 1)]
-
-        def launch(c, stream_ptr):
-            lo, hi = bounds[c], bounds[c + 1]
-            n = hi - lo
-
-            def rows(t):                      # batch-major tensors: rows [lo, hi) of the leading B-sized blocks
-                per = t.numel() // B
-                return t.view(-1)[lo * per:hi * per]
-            ts = [[rows(t) for t in grp] for grp in (lbs, ubs, duals, prim)]
-            tabs = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in ts]
-            batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], rows(x_lp).data_ptr(), rows(pw).data_ptr(),
-                               rows(pb).data_ptr(), rows(mask).data_ptr(), len(lbs), len(duals), len(prim))
-            ws = self.workspace(n, c)
-            rc = self.lib.gnnb_forward(self.h, C.byref(batch), n, scores[lo:hi].data_ptr(), dec[lo:hi].data_ptr(),
-                                       status[c:c + 1].data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(stream_ptr))
-            _lib.check(rc, "gnnb_forward")
-
+        tabs = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in (lbs, ubs, duals, prim)]
+        batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(),
+                           len(lbs), len(duals), len(prim))
+        ws = self.workspace(B)
         with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            if nchunk == 1:
-                launch(0, cur.cuda_stream)
-            else:
-                while len(self._streams) < nchunk:
-                    self._streams.append(torch.cuda.Stream(device=self.device))
-                for c in range(nchunk):
-                    st = self._streams[c]
-                    st.wait_stream(cur)                   # inputs were produced on the caller's stream
-                    launch(c, st.cuda_stream)
-                for c in range(nchunk):
-                    # results are ordered back into the caller's stream; since every tensor used here belongs to that
-                    # stream and it now waits for the side streams, the caching allocator cannot recycle them early
-                    cur.wait_stream(self._streams[c])
+            rc = self.lib.gnnb_forward(self.h, C.byref(batch), B, scores.data_ptr(), dec.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_forward")
         return ForwardResult(scores, dec, status, mask2)
 
     # ---- the reference's own call pattern: host tensors, one or two subproblems ---------------------------------
@@ -785,8 +755,6 @@ class ScorerEngine:
         whatever was there before."""
         off, n = C.c_size_t(), C.c_size_t()
         _lib.check(self.lib.gnnb_mu_location(self.h, B, k, C.byref(off), C.byref(n)), "gnnb_mu_location")
-        if self.n_streams > 1 and B >= self.n_streams * self.min_chunk:
-            raise RuntimeError("mu() inspects a single-chunk forward: set engine.n_streams = 1 first")
         ws = self.workspace(B)
         rows = ws[off.value:off.value + 4 * n.value].view(torch.float32).view(B, self.sizes[k], self.p)
         lid = C.c_int(-1)

@@ -46,26 +46,12 @@ def test_option_table_is_the_documented_one(lib):
 
 
 def test_library_and_package_leave_the_environment_alone():
-    """The shipped library reads no environment variable (development builds, -DGNNB_DEV, do); the package never WRITES one: options reach a
+    """The library reads no environment variable: no getenv anywhere in its sources.  The package never WRITES one: options reach a
     handle through gnnb_set_option (ScorerEngine(options=...)), the GNNB_* names of _lib.OPTION_ENV are read once per engine for the tests."""
     csrc = os.path.join(ROOT, "gnn_branching_amd", "csrc")
     for f in os.listdir(csrc):
-        if not f.endswith((".hip", ".h")):
-            continue
-        depth = 0                                      # nesting depth of #ifdef GNNB_DEV blocks
-        stack = []
-        for line in open(os.path.join(csrc, f)):
-            t = line.strip()
-            if t.startswith(("#if", "#ifdef", "#ifndef")):
-                stack.append("GNNB_DEV" in t and not t.startswith("#ifndef"))
-                depth += stack[-1]
-            elif t.startswith("#else") and stack and stack[-1]:
-                stack[-1] = False
-                depth -= 1
-            elif t.startswith("#endif") and stack:
-                depth -= stack.pop()
-            elif "getenv(" in t and not t.startswith("//"):
-                assert depth > 0, f"{f}: getenv outside #ifdef GNNB_DEV: {t}"
+        if f.endswith((".hip", ".h", ".cpp")):
+            assert "getenv(" not in open(os.path.join(csrc, f)).read(), f"{f} calls getenv"
     pkg = os.path.join(ROOT, "gnn_branching_amd")
     for d, _, files in os.walk(pkg):
         for f in files:

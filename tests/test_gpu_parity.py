@@ -366,22 +366,6 @@ def test_host_entry_point_matches(case):
         eng.forward_host(batch.lower_bounds_all[:-1], *batch.forward_args()[1:])
 
 
-def test_two_stream_batch_pipelining_is_bit_identical():
-    """engine.n_streams = 2 cuts a large batch into two chunks on two HIP streams: identical bytes out."""
-    from gnn_branching_amd import synth
-    model = make_model("shipped")
-    batch = synth.make_batch("cifar_base_kw", 160, seed=77)
-    eng = model.engine()
-    with torch.no_grad():
-        one = eng.forward(*batch.forward_args()).check()
-        eng.n_streams = 2
-        try:
-            two = eng.forward(*batch.forward_args()).check()
-        finally:
-            eng.n_streams = 1
-    assert torch.equal(one.scores, two.scores) and torch.equal(one.decisions, two.decisions)
-
-
 @pytest.mark.parametrize("net,B", [("cifar_base_kw", 1), ("cifar_base_kw", 3), ("cifar_deep_kw", 2), ("cifar_wide_kw", 2), ("cifar_base_kw", 40)])
 @pytest.mark.parametrize("fam", ["shipped", "random"])
 def test_top_workgroup_split_is_bit_identical(monkeypatch, net, B, fam):
