@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -28,11 +28,13 @@ def main():
     ap.add_argument("--nodes", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--babsr", action="store_true", help="branch with the BaBSR heuristic instead of the GNN")
+    ap.add_argument("--bounds", default="kw", choices=("kw", "interval", "kw_device"),
+                    help="intermediate bounds: host fp64 Wong-Kolter, interval arithmetic, or Wong-Kolter on the GPU (gnnb_kw_bounds)")
     ap.add_argument("--threshold", type=float, default=None, help="branching_threshold of the GNN + KW fall-back loop (the reference uses 0.2)")
     args = ap.parse_args()
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
-    lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps)
+    lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
     root = lp.solve(root_mask)
     print(f"root: lb {root.lb:.5f} ub {root.ub:.5f}, undecided ReLUs per layer {[int((m == -1).sum()) for m in root.mask]}")

@@ -20,7 +20,8 @@
 //
 // One translation unit: gnnb_dev.h (fragments, GEMM blocks, tile maps), gnnb_k_mlp.h (setup + node-MLP kernels),
 // gnnb_k_gather.h (conv-edge message passing + score head), gnnb_k_fusedq.h (gather + node update in one kernel), gnnb_k_edges.h (other edges, k_top), gnnb_k_misc.h (k_livesum,
-// k_babsr, k_gather_scored), gnnb_train.h (online learning) are included below; this file holds the host side and the C-ABI.
+// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_train.h (online learning) are included below; this file
+// holds the host side and the C-ABI.
 //
 // gfx950 only.  No HIP call at load time.
 #include <hip/hip_runtime.h>
@@ -55,6 +56,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_fusedq.h"
 #include "gnnb_k_edges.h"
 #include "gnnb_k_misc.h"
+#include "gnnb_k_kw.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -83,11 +85,13 @@ static int fail(int code, const char* fmt, ...) {
 
 enum ProfClass {
   PC_EMBED, PC_PRE, PC_PRE_INP, PC_CONV_FWD, PC_CONVT_BWD, PC_DENSE_AGG, PC_PROP_FWD,
-  PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE, PC_COUNT
+  PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
+  PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
-    "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update"};
+    "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
+    "k_kw_first", "k_kw_layer", "k_kw_flag"};
 
 struct DevEdge {
   float *w_fwd = nullptr, *w_bwd = nullptr, *bias = nullptr;   // conv: tap-major copies; linear: W^T / W, zero-padded
@@ -205,6 +209,7 @@ struct gnnb_handle {
   bool bound = false;
   std::vector<Edge> edges;       // edges[k], k = 1..L (edges[0] unused)
   std::vector<DevEdge> dev;
+  std::vector<double*> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for gnnb_kw_bounds, k = 1..L (made by bind)
   std::vector<int> N;            // graph layer sizes, N[0..L+1]
   std::vector<int> relu_q;       // fixed-layer index of the ReLU of graph layer k
   std::vector<int> hw;           // nodes per bias entry of layer k
@@ -392,6 +397,12 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   return GNNB_OK;
 }
 
+static int upload64(double** d, const double* h, size_t n) {
+  HIPCHK(hipMalloc((void**)d, n * sizeof(double)));
+  HIPCHK(hipMemcpy(*d, h, n * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
 static void free_trainer(gnnb_t* h) {
   gnnb_train::Trainer* t = h->trainer;
   if (!t) return;
@@ -424,6 +435,11 @@ static void free_network(gnnb_t* h) {
       if (d.koff) (void)hipFree(d.koff);
       if (d.ttab) (void)hipFree(d.ttab);
     }
+  for (auto* v : {&h->kw_w, &h->kw_b})
+    for (double* p : *v)
+      if (p) (void)hipFree(p);
+  h->kw_w.clear();
+  h->kw_b.clear();
   h->gf.clear();
   h->gb.clear();
   h->dev.clear();
@@ -531,6 +547,8 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
   h->R = 0;
   for (int k = 1; k <= Lr; ++k) h->R += h->N[k];
   h->dev.resize(Lr + 1);
+  h->kw_w.assign(Lr + 1, nullptr);
+  h->kw_b.assign(Lr + 1, nullptr);
   for (int k = 0; k < MAXL + 2; ++k) h->last_proj[k] = -1;
   for (int k = 0; k <= Lr; ++k)
     if (h->N[k] > LIVESUM_MAXSRC) return fail(GNNB_E_INVALID, "graph layer %d has %d nodes, more than the %d k_livesum holds in LDS", k, h->N[k], LIVESUM_MAXSRC);
@@ -538,6 +556,11 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
     const Edge& e = h->edges[k];
     DevEdge& d = h->dev[k];
     if (int rc = upload(&d.bias, e.b.data(), e.b.size())) return rc;
+    {                                   // fp64 copies for gnnb_kw_bounds (fp32 -> fp64 is exact)
+      std::vector<double> w64(e.w.begin(), e.w.end()), b64(e.b.begin(), e.b.end());
+      if (int rc = upload64(&h->kw_w[k], w64.data(), w64.size())) return rc;
+      if (int rc = upload64(&h->kw_b[k], b64.data(), b64.size())) return rc;
+    }
     if (k == 1) {                       // row sums of edge 1 (for a conv: of the taps inside the image) -- k_livesum's job for this edge
       std::vector<float> s1(h->N[1], 0.0f);
       if (e.kind == 0) {
@@ -1717,6 +1740,98 @@ extern "C" int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const*
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GNNB_E_HIP, "launch of k_babsr failed: %s", hipGetErrorString(e));
   return GNNB_OK;
+}
+
+
+// ================================================================================================================
+// Wong-Kolter intermediate bounds of a batch of BaB domains (gnnb_k_kw.h; lp_producer.py LayerGraphLP.kw_bounds, reference
+// plnn/dual_network_linear_approximation.py init_kw_bounds :205-294 / update_kw_bounds :296-451)
+// ================================================================================================================
+struct KwWs { size_t pw, total; };      // byte offsets in the workspace: (d, -d l) pairs at 0, then the fp64 property layers
+static KwWs kw_ws_layout(const gnnb_t* h, int B) {
+  const int L = (int)h->N.size() - 2;
+  KwWs w;
+  w.pw = ((size_t)B * h->R * 2 * sizeof(double) + 255) & ~(size_t)255;
+  w.total = w.pw + (((size_t)B * (h->N[L] + 1) * sizeof(double) + 255) & ~(size_t)255);
+  return w;
+}
+
+extern "C" size_t gnnb_kw_workspace_bytes(const gnnb_t* h, int B) {
+  if (!h || !h->bound || B < 1) return 0;
+  return kw_ws_layout(h, B).total;
+}
+
+extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32,
+                              float* const* ub32, int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null handle");
+  if (!h->bound) return fail(GNNB_E_STATE, "gnnb_kw_bounds: call gnnb_bind_network first");
+  if (!in || !lb || !ub || !infeasible || !workspace || B < 1 || B > 65535)
+    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null argument or batch size %d outside 1..65535", B);
+  const int K = (int)h->N.size() - 1, L = K - 1;         // graph layers 0..K, K = L + 1 the property node
+  if (in->n_graph != K + 1) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: %d graph layers given, network has %d", in->n_graph, K + 1);
+  if (!in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null input pointer");
+  if ((in->parent_lb == nullptr) != (in->parent_ub == nullptr) || (in->parent_lb && !in->split_layer))
+    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: parent bounds need both tables and split_layer");
+  if ((lb32 == nullptr) != (ub32 == nullptr)) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: lb32 and ub32 go together");
+  int maxNr = 0;
+  for (int k = 1; k <= L; ++k) maxNr = std::max(maxNr, h->N[k]);
+  const size_t lds = kw_lds_doubles(maxNr) * sizeof(double);
+  if (lds > 65536)
+    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: a ReLU layer of %d nodes needs %zu bytes of LDS for the dual pass (64 KiB at most)", maxNr, lds);
+  const KwWs ws = kw_ws_layout(h, B);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_kw_bounds: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
+  KwArgs a{};
+  a.L = L; a.R = h->R; a.B = B; a.maxNr = maxNr;
+  int off = 0;
+  for (int k = 0; k <= K; ++k) {
+    a.N[k] = h->N[k];
+    if (k >= 1 && k <= L) { a.off[k] = off; off += h->N[k]; }
+  }
+  for (int k = 0; k <= L; ++k) {                          // graph layer k as (C, H, W)
+    const Edge& e = h->edges[k == 0 ? 1 : k];
+    const bool conv = e.kind == 0;
+    a.lc[k] = conv ? (k == 0 ? e.c_in : e.c_out) : h->N[k];
+    a.lh[k] = conv ? (k == 0 ? e.h_in : e.h_out) : 1;
+    a.lw[k] = conv ? (k == 0 ? e.w_in : e.w_out) : 1;
+  }
+  for (int k = 1; k <= K; ++k) {
+    if (!lb[k - 1] || !ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null output pointer for graph layer %d", k);
+    a.lb[k] = lb[k - 1]; a.ub[k] = ub[k - 1];
+    if (in->parent_lb) {
+      if (!in->parent_lb[k - 1] || !in->parent_ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null parent pointer for graph layer %d", k);
+      a.plb[k] = in->parent_lb[k - 1]; a.pub[k] = in->parent_ub[k - 1];
+    }
+    KwEdge& E = a.e[k];
+    if (k <= L) {
+      const Edge& e = h->edges[k];
+      E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0; E.kind = e.kind;
+      E.c_in = e.c_in; E.h_in = e.h_in; E.w_in = e.w_in; E.c_out = e.c_out; E.h_out = e.h_out; E.w_out = e.w_out;
+      E.kh = e.kh; E.kw = e.kw; E.stride = e.stride; E.pad = e.pad; E.n_in = e.n_in; E.n_out = e.n_out;
+    } else {                                              // the property layer: per-domain Linear(N_L, 1), fp64 copy in the workspace
+      const double* pw = (const double*)((char*)workspace + ws.pw);
+      E.w = pw; E.bias = pw + h->N[L]; E.wb = E.bb = h->N[L] + 1; E.kind = 1;
+      E.n_in = h->N[L]; E.n_out = 1;
+    }
+  }
+  for (int k = 0; k <= K; ++k)
+    if (lb32) {
+      if (!lb32[k] || !ub32[k]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null fp32 output pointer for graph layer %d", k);
+      a.lb32[k] = lb32[k]; a.ub32[k] = ub32[k];
+    }
+  a.x_lo = in->x_lo; a.x_hi = in->x_hi; a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.mask = in->mask;
+  a.split = in->parent_lb ? in->split_layer : nullptr;
+  a.dg = (double*)workspace;
+  a.pw = (double*)((char*)workspace + ws.pw);
+  a.infeasible = infeasible;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  const int span = std::max(std::max(h->N[0], h->N[1]), h->N[L] + 1);
+  const long nthreads = (long)span * B;
+  run.run(PC_KW_FIRST, [&] { hipLaunchKernelGGL(k_kw_first, dim3((unsigned)((nthreads + KW_THREADS - 1) / KW_THREADS)), dim3(KW_THREADS), 0, st, a, span); });
+  for (int k = 2; k <= K; ++k)
+    run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(h->N[k], B), dim3(KW_THREADS), lds, st, a, k); });
+  run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
+  return run.rc;
 }
 
 

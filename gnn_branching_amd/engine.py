@@ -49,6 +49,16 @@ class BabsrResult:
         return tuple(list(torch.split(t[b], self.relu_sizes)) for t in (self.scores, self.intercepts, self.masks))
 
 
+class KwBoundsResult:
+    """Device outputs of one gnnb_kw_bounds call: fp64 bounds of graph layers 1..L+1 (lists of (B, N_k) tensors, split mask applied),
+    optionally their fp32 copies laid out as GraphNet.forward's lower_bounds_all / upper_bounds_all (graph layers 0..L+1, layer 0 =
+    the box, in the shape x_lo was given in), and the (B,) int32 infeasible flags.  Nothing is synchronised."""
+    __slots__ = ("lb", "ub", "lb32", "ub32", "infeasible")
+
+    def __init__(self, lb, ub, lb32, ub32, infeasible):
+        self.lb, self.ub, self.lb32, self.ub32, self.infeasible = lb, ub, lb32, ub32, infeasible
+
+
 def _or_reduce(status):
     v = 0
     for x in status.cpu().tolist():
@@ -730,6 +740,69 @@ class ScorerEngine:
                                      icp.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_babsr")
         return BabsrResult(scores, icp, mask.view(B, self.R), self.sizes[1:-1])
+
+    # ---- Wong-Kolter intermediate bounds (lp_producer.LayerGraphLP.kw_bounds for a batch) ------------------------------------
+    def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False):
+        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) or (B, N_0) input boxes (fp64 on the device); prop_layers:
+        B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of
+        graph layers 1..L+1 (fp64); split_layers: (B,) ReLU layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
+        B = int(x_lo.shape[0])
+        self.bind(fixed_layers, tuple(x_lo.shape[1:]))
+        if len(prop_layers) != B:
+            raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
+        ng, dev = len(self.sizes), self.device
+
+        def f64(t, n, what):
+            t = torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()
+            if t.numel() != B * n:
+                raise ValueError(f"{what}: {tuple(t.shape)} does not hold {B}x{n} values")
+            return t.view(B, n)
+        xl, xu = f64(x_lo, self.sizes[0], "x_lo"), f64(x_hi, self.sizes[0], "x_hi")
+        mask = torch.as_tensor(masks).to(device=dev, dtype=torch.int8).contiguous()
+        if mask.numel() != B * self.R:
+            raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {self.R})")
+        pw, pb = self._prop(prop_layers)
+        plb = pub = split = None
+        if parents is not None:
+            if split_layers is None or len(parents[0]) != ng - 1 or len(parents[1]) != ng - 1:
+                raise ValueError("parents need n_graph-1 lower and upper tensors and split_layers")
+            plb = [f64(t, self.sizes[k + 1], f"parent lb {k + 1}") for k, t in enumerate(parents[0])]
+            pub = [f64(t, self.sizes[k + 1], f"parent ub {k + 1}") for k, t in enumerate(parents[1])]
+            split = torch.as_tensor(split_layers).to(device=dev, dtype=torch.int32).contiguous()
+            if split.numel() != B:
+                raise ValueError("split_layers must hold one entry per domain")
+        lb = [torch.empty(B, n, dtype=torch.float64, device=dev) for n in self.sizes[1:]]
+        ub = [torch.empty(B, n, dtype=torch.float64, device=dev) for n in self.sizes[1:]]
+        lb32 = ub32 = None
+        if want_fp32:
+            shapes = [tuple(x_lo.shape)] + [(B, n) for n in self.sizes[1:]]      # the box keeps its shape: bind() reads the input's from it
+            lb32 = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
+            ub32 = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
+        infeasible = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = self.kw_workspace(B)
+
+        def table(ts):
+            return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        kb = _lib.KwBatch(xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), table(plb), table(pub),
+                          split.data_ptr() if split is not None else None, ng)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_kw_bounds(self.h, C.byref(kb), B, table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_kw_bounds")
+        return KwBoundsResult(lb, ub, lb32, ub32, infeasible)
+
+    def kw_workspace(self, B):
+        key = ("kw", B)
+        ws = self._ws.get(key)
+        if ws is None:
+            n = self.lib.gnnb_kw_workspace_bytes(self.h, B)
+            if n == 0:
+                raise RuntimeError("gnnb_kw_workspace_bytes returned 0 (no network bound?)")
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+            if len(self._ws) > 6:
+                self._ws.clear()
+            self._ws[key] = ws
+        return ws
 
     def _check_primals(self, fixed, prim, B):
         def count(t):

@@ -12,7 +12,9 @@ read the primal point, the per-layer primal values and the constraint duals ``Pi
   dual_network_linear_approximation.py:205-451) intersected with interval arithmetic and, for a child domain, with its
   parent's bounds; below the split layer the parent's bounds are kept (incremental update), honouring the split mask (a
   node forced passing gets ``pre >= 0``, forced blocking ``pre <= 0``).  ``bounds="interval"`` selects plain interval
-  arithmetic (the looser relaxation round 1 used);
+  arithmetic (the looser relaxation round 1 used); ``bounds="kw_device"`` computes the same Wong-Kolter bounds in fp64 on the
+  GPU (``ScorerEngine.kw_bounds`` -> ``gnnb_kw_bounds``, a whole batch of domains per call: ``solve_many``) and rebuilds the list
+  ``kw_bounds`` returns from them;
 * the LP: one variable block per network layer, affine layers as equalities with their scipy.sparse matrix, decided
   ReLUs as equalities / fixed bounds, undecided ones as the two inequality rows (``v >= 0`` is the variable bound);
 * duals in Gurobi's sign convention: ``Pi(v >= pre) = -marginal(pre - v <= 0)``, ``Pi(v <= slope pre + bias) =
@@ -23,7 +25,7 @@ reference module imports ``plnn.model`` -> ``gurobipy`` and cannot be imported h
 numbers.  ``tests/test_lp_producer.py`` checks what can be checked without it -- soundness of every bound on sampled
 points, KW within interval, LP bound with KW >= LP bound with interval, primal feasibility, complementary slackness of the
 reported duals, monotonicity under branching, incremental == inherited below the split.
-Host-side CPU code, like the reference's; the GPU only scores.
+The LP is host-side CPU code, like the reference's; the GPU scores and, with ``bounds="kw_device"``, computes the intermediate bounds.
 """
 from dataclasses import dataclass
 from typing import List
@@ -83,12 +85,15 @@ class Subproblem:
 class LayerGraphLP:
     """LP relaxation of ``layers`` (net.layers with the folded Linear(., 1) property layer last) over an input box."""
 
-    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm"):
+    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm", engine=None):
+        """``bounds``: "kw" (host fp64 Wong-Kolter), "interval", or "kw_device" (the same bounds on the GPU; ``engine``: the
+        ScorerEngine to run them on, None = a GNN-free one created on first use)."""
         self.retry_stats = {"infeasible_first": 0, "flipped_to_feasible": 0}      # see solve(): the widened re-solve of an 'infeasible' IPM answer
         self.lp_method = lp_method
-        if bounds not in ("kw", "interval"):
+        if bounds not in ("kw", "interval", "kw_device"):
             raise ValueError(bounds)
         self.bound_mode = bounds
+        self.engine = engine
         self.layers = list(layers)
         self.input_lb, self.input_ub = input_lb.detach().double(), input_ub.detach().double()
         self.shapes = [tuple(input_lb.shape)]
@@ -242,9 +247,50 @@ class LayerGraphLP:
             ubs.append(nu)
         return lbs, ubs
 
+    def kw_device_bounds(self, items):
+        """``kw_bounds`` for several domains in ONE device call (``gnnb_kw_bounds``).  ``items``: [(mask, parent, split_layer), ...] with
+        ``parent`` None or (lbs, ubs) as ``kw_bounds`` takes it.  Returns [(lbs, ubs), ...] laid out as ``kw_bounds`` returns them (host
+        fp64; post-ReLU entries clamped, flattened entries reshaped)."""
+        if self.engine is None:
+            from .engine import ScorerEngine
+            self.engine = ScorerEngine(None)
+        eng, B = self.engine, len(items)
+        gidx = list(self.pre_relu_indices) + [len(self.layers)]                 # bounds-list entries of graph layers 1..L+1
+        x_lo = self.input_lb[None].expand((B,) + self.shapes[0])
+        x_hi = self.input_ub[None].expand((B,) + self.shapes[0])
+        masks = torch.stack([torch.cat([m.reshape(-1) for m in mask]) for mask, _, _ in items]).to(torch.int8)
+        parents = split = None
+        if any(p is not None and s is not None for _, p, s in items):
+            zero = [torch.zeros(int(np.prod(self.shapes[i])), dtype=torch.float64) for i in gidx]
+            parents = tuple([torch.stack([(p[side][i].reshape(-1) if (p is not None and s is not None) else z)
+                                          for _, p, s in items]) for i, z in zip(gidx, zero)] for side in (0, 1))
+            split = torch.tensor([s if (p is not None and s is not None) else -1 for _, p, s in items], dtype=torch.int32)
+        fixed, prop = self.layers[:-1], [self.layers[-1]] * B
+        res = eng.kw_bounds(fixed, prop, x_lo, x_hi, masks, parents, split)
+        glb = [t.cpu() for t in res.lb]
+        gub = [t.cpu() for t in res.ub]
+        out = []
+        for b in range(B):
+            lbs, ubs = [self.input_lb.clone()], [self.input_ub.clone()]
+            g = 0
+            for q, l in enumerate(self.layers):
+                if type(l) in (nn.Conv2d, nn.Linear):
+                    nl, nu = glb[g][b].reshape(self.shapes[q + 1]).clone(), gub[g][b].reshape(self.shapes[q + 1]).clone()
+                    g += 1
+                elif type(l) is nn.ReLU:
+                    nl, nu = lbs[-1].clamp(min=0), ubs[-1].clamp(min=0)
+                else:
+                    nl, nu = lbs[-1].reshape(-1), ubs[-1].reshape(-1)
+                lbs.append(nl)
+                ubs.append(nu)
+            out.append((lbs, ubs))
+        return out
+
     def bounds(self, mask, parent=None, split_layer=None):
         if self.bound_mode == "interval":
             return self.interval_bounds(mask)
+        if self.bound_mode == "kw_device":
+            return self.kw_device_bounds([(mask, parent, split_layer)])[0]
         return self.kw_bounds(mask, parent, split_layer)
 
     # ---- the LP -----------------------------------------------------------------------------
@@ -255,6 +301,20 @@ class LayerGraphLP:
         mask = [m.clone() for m in mask]
         pb = None if parent is None else parent.bounds64
         lbs, ubs = self.bounds(mask, pb, split_layer)
+        return self._solve_lp(mask, lbs, ubs)
+
+    def solve_many(self, items):
+        """``solve`` for several domains: [(mask, parent, split_layer), ...] -> [Subproblem or None, ...].  With ``bounds="kw_device"``
+        the bounds of all of them come from one device call; the LPs run one after the other."""
+        items = [([m.clone() for m in mask], None if parent is None else parent.bounds64, split) for mask, parent, split in items]
+        if self.bound_mode == "kw_device":
+            bounds = self.kw_device_bounds(items)
+        else:
+            bounds = [self.bounds(mask, pb, split) for mask, pb, split in items]
+        return [self._solve_lp(mask, lbs, ubs) for (mask, _, _), (lbs, ubs) in zip(items, bounds)]
+
+    def _solve_lp(self, mask, lbs, ubs):
+        """The LP of ``solve`` on given bounds (``mask``: the caller's copy, resolved in place)."""
         for lo, up in zip(lbs, ubs):
             if bool((lo > up + 1e-9).any()):
                 return None
@@ -447,6 +507,13 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
     ineff_kw_dc, closed_lb = {}, float("inf")
 
     def bound_children(dom, decision):
+        if getattr(lp, "bound_mode", None) == "kw_device":     # both children's bounds in one device call, then their LPs
+            items = []
+            for choice in (0, 1):
+                m = [t.clone() for t in dom.mask]
+                m[decision[0]][decision[1]] = choice
+                items.append((m, dom, decision[0]))
+            return lp.solve_many(items)
         out = []
         for choice in (0, 1):
             m = [t.clone() for t in dom.mask]

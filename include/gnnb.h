@@ -154,6 +154,39 @@ int gnnb_scatter_amb_records(gnnb_t* h, const void* dev_image, int B, float* con
 int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const* ub, int n_graph, const float* prop_w,
                const float* mask, int B, float* scores, float* intercepts, void* stream);
 
+/* Wong-Kolter intermediate bounds of B BaB domains, fp64 (reference plnn/dual_network_linear_approximation.py init_kw_bounds :205-294 and
+ * update_kw_bounds :296-451 on the dual network of convex_adversarial/dual_network.py:15-121; restated on the host by
+ * gnn_branching_amd/lp_producer.py LayerGraphLP.kw_bounds).  Per affine layer, in order: the interval image of the bounds below; from
+ * the second affine layer on, the KW bound of every output node (one dual-network backward pass per node, reading the mask-clamped
+ * bounds of the ReLUs below) intersected with it; the parent's bounds intersected; the split mask applied to the pre-activation
+ * bounds (1: lo >= 0, 0: up <= 0).  A domain with a parent (split_layer[b] >= 0) keeps the parent's bounds of graph layers
+ * 1..split_layer[b]+1 bit for bit (then the mask), the layers above are recomputed and intersected with the parent's.  The last
+ * affine layer is the domain's property layer.  A domain's bounds do not depend on B or on its place in the batch.
+ * All pointers inside the struct are DEVICE pointers; the pointer tables parent_lb / parent_ub are HOST arrays. */
+typedef struct {
+  const double* x_lo;                 /* input box (B, N_0), one per domain                                         */
+  const double* x_hi;
+  const float* prop_w;                /* property layers as in gnnb_batch: (B, N_L) and (B)                          */
+  const float* prop_b;
+  const int8_t* mask;                 /* BaB mask (B, R) in flat ReLU order: -1 undecided, 0 blocked, 1 passing     */
+  const double* const* parent_lb;     /* NULL, or n_graph-1 ptrs: the parents' bounds of graph layers 1..L+1 (B, N_k) */
+  const double* const* parent_ub;
+  const int32_t* split_layer;         /* (B): ReLU layer (0..L-1) of the split that made the domain, -1 (any negative
+                                         value) = no parent; values >= L count as L-1.  Required with parent_lb      */
+  int32_t n_graph;                    /* L + 2, as gnnb_graph_info reports                                          */
+} gnnb_kw_batch;
+
+/* Bytes of device workspace gnnb_kw_bounds needs for a batch of B (0 for a null or unbound handle). */
+size_t gnnb_kw_workspace_bytes(const gnnb_t* h, int B);
+
+/* lb / ub: HOST tables of n_graph-1 DEVICE pointers, graph layers 1..L+1, (B, N_k) fp64, mask applied.  lb32 / ub32: NULL, or n_graph
+ * pointers laid out as gnnb_batch.lb / .ub (layer 0 = the box), the same bounds rounded to fp32: they feed gnnb_babsr and gnnb_forward
+ * directly.  infeasible: device (B) int32, 1 where some lo > up + 1e-9 (the test LayerGraphLP.solve applies).  Stream-ordered, no
+ * allocation, no synchronisation; the workspace needs no initialisation.  GNNB_E_INVALID for a null handle or a network whose widest
+ * ReLU layer exceeds 4096 nodes (the dual pass holds two of them in LDS). */
+int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32, float* const* ub32,
+                   int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
