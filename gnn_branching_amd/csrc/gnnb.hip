@@ -166,22 +166,22 @@ struct gnnb_handle {
   int T = 2, p = 64, device = 0, n_cu = 256;
   bool use_gather = true;       // MFMA gather for conv edges (false: VALU gather kernels)
   // (k_node_update: 12 waves per workgroup = 3 per SIMD with the bf16x3 blocks (142-152 VGPRs, no scratch); the fp32-MFMA-only
-  // form (GNNB_BF3=0) needs 167-181 VGPRs and runs 8 waves per workgroup)
+  // form (option bf3 = 0) needs 167-181 VGPRs and runs 8 waves per workgroup)
   bool dense_lds = true;        // Linear edges: one workgroup per sample with the source rows in LDS (false: per-tile kernel)
   bool bf3 = true;              // node update: 64x64 blocks on the bf16 matrix rate with three-piece operands (fp32 accuracy)
   bool embed_fuse = true;       // round 0: the first forward gather computes the input embedding itself (no k_embed, no mu[0] rows)
   int fuse = 1;                 // conv half-passes as ONE kernel (k_gather_update_q: the aggregate never reaches HBM) wherever that kernel
                                 // exists (measured faster at every batch size and on all three networks: base B = 256 0.975 vs 1.014 ms,
-                                // deep B = 1024 6.59 vs 7.31 ms, B = 1 0.344 vs 0.359 ms); GNNB_FUSE=0: always two kernels.  Both forms
+                                // deep B = 1024 6.59 vs 7.31 ms, B = 1 0.344 vs 0.359 ms); fuse = 0: always two kernels.  Both forms
                                 // compute the same arithmetic per node -- bit-identical results -- so this is a pure scheduling choice.
   bool use_top = true;          // fuse the top of the network (last Linear edge, last ReLU layer, property node) into k_top
   bool top_ok = false;          // ... which the bound network allows (set by gnnb_bind_network)
-  int clspre_max_b = 1;         // GNNB_CLSPRE_MAX_B: batches up to it classify and run the hoisted feature chains in one launch (k_classify_pre);
+  int clspre_max_b = 1;         // option clspre_max_b: batches up to it classify and run the hoisted feature chains in one launch (k_classify_pre);
                                 // measured (base, us): B = 1 27.5 vs 7.6 + 22.1, B = 2 34.0 vs 30.0, B = 8 42.5 vs 31.8 -- a block's share of
                                 // the ambiguous nodes is uneven, so beyond one subproblem the two kernels' even dealing wins
-  int tail_max_b = 1 << 30;     // GNNB_TAIL_MAX_B: batches up to it end in k_scored_tail (scored gather + restricted update + score head in one launch); 0: three kernels
-  bool top_fuse_upd = true;     // GNNB_TOP_FUSE_UPD=0: the backward node update of layer L-1 as its own launch behind k_top (it runs inside k_top otherwise)
-  int top_split_max = 4;        // GNNB_TOP_SPLIT: 4 (default) = four workgroups per sample while B <= n_cu / 4, two while B <= n_cu / 2; 2 = two at most; 1 = never
+  int tail_max_b = 1 << 30;     // option tail_max_b: batches up to it end in k_scored_tail (scored gather + restricted update + score head in one launch); 0: three kernels
+  bool top_fuse_upd = true;     // option top_fuse_upd = 0: the backward node update of layer L-1 as its own launch behind k_top (it runs inside k_top otherwise)
+  int top_split_max = 4;        // option top_split: 4 (default) = four workgroups per sample while B <= n_cu / 4, two while B <= n_cu / 2; 2 = two at most; 1 = never
   Packs packs;
   std::vector<float> blob;      // the GNN parameters as handed to gnnb_create / gnnb_set_weights / left by gnnb_online_step
   gnnb_train::Trainer* trainer = nullptr;     // online learning (gnnb_online_create)
@@ -735,12 +735,71 @@ static bool fusedq_ok(const gnnb_t* h, const DevGather& d, int src_layer, bool e
   return fusedq_qtiles(d, sparse, post) > 0;
 }
 
+// the scored gather (k_gather_scored, k_scored_tail) keeps a node's source window in registers: C_out x ceil(kh/s) x ceil(kw/s) slots
+static int gs_slots(const Edge& e) { return e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride); }
+static bool gs_window_ok(const Edge& e) { return gs_slots(e) <= GS_SLOT_LIMIT; }
+
+#define TOP_SPLIT_MAXB 128      // k_top only splits a sample over workgroups while B x S workgroups fit the chip: B <= n_cu / 2
+
+// What gnnb_forward decides before its first launch, from the handle, the batch size and the half-pass limit alone.
+// gnnb_describe reads its decisions from the same plan (with no limit).
+struct Plan {
+  int limit;                // half-passes to run: 2 T, or fewer under an inspection limit
+  bool debug_full;          // a half-pass limit is set: nothing is restricted or skipped as dead
+  bool top_fused;           // the top of the network in k_top
+  bool top_upd;             // ... which also runs the backward node update of layer L-1
+  bool top_s_fwd, top_s_bwd;  // ... and produces the bias sums of edge L forward / transposed itself
+  bool s1_table;            // bias sums of edge 1 forward: the bind-time table
+  bool embed_in_gather;     // round 0's input embedding computed inside the first forward gather (no k_embed)
+  bool cls_pre;             // k_classify and k_pre in one launch (k_classify_pre)
+  bool need_inp;            // k_pre_inp: the input layer's feature chain for the non-fused input update
+  bool tail;                // the final round's restricted update of layer 1 and the score head in one launch (k_scored_tail)
+  int S;                    // workgroups k_top spreads one sample over
+};
+static Plan make_plan(const gnnb_t* h, int B, int halfpass_limit) {
+  const int L = (int)h->N.size() - 2;
+  Plan p;
+  p.limit = halfpass_limit > 0 ? std::min(halfpass_limit, 2 * h->T) : 2 * h->T;
+  p.debug_full = halfpass_limit > 0;
+  // The one-workgroup-per-sample kernels (k_top, k_dense_*_lds) run at every batch size, although a small batch leaves CUs idle
+  // (per-tile kernels vs these: B=2 0.40 vs 0.49 ms, B=128 0.96 vs 0.88 ms): the two paths round differently, and with one path
+  // for every batch size a sample's scores do not depend on what it is batched or sharded with.
+  p.top_fused = h->use_top && h->bf3 && h->top_ok && !p.debug_full;      // (k_top only exists on the bf16 x 3 rate)
+  // k_top's Linear edges walk live rows only (when their lists fit, top_sample `compact` / `keep`), so they produce the bias sums
+  // of edge L in both directions themselves and k_livesum skips those jobs
+  const int topK = L >= 1 && h->edges[L].kind == 1 ? h->edges[L].n_in : 0;
+  p.top_s_fwd = p.top_fused && TOP_LIST_OK(topK);
+  p.top_s_bwd = p.top_fused && TOP_LIST_KEEP_OK(topK) && p.limit >= 2;
+  // k_top also runs the backward node update of layer L-1 on its transposed edge's row tiles (the aggregate never reaches memory):
+  // needs the kept live-row list (B2 then walks live rows only) and a layer L-1 that is not layer 1 (whose update has the
+  // restricted / input-mapping forms)
+  p.top_upd = p.top_fused && h->top_fuse_upd && L >= 3 && TOP_LIST_KEEP_OK(topK);
+  p.s1_table = L >= 2 && h->d_s1 != nullptr;
+  p.embed_in_gather = h->embed_fuse && !p.debug_full && h->gf[1].ok;
+  p.cls_pre = h->bf3 && B <= h->clspre_max_b;      // default: a single subproblem
+  p.need_inp = p.limit >= 2 && (h->T > 1 || p.debug_full) && !h->gb[1].ok;    // the fused input kernel computes Q itself
+  // the final round's scored update of layer 1 as k_scored_tail: on the k_top path only, with layer 1 below the layer whose aggregate
+  // k_top leaves in `nb` (L >= 3), over a conv edge 2 with MFMA gather tables and a window the scored gather holds
+  p.tail = p.top_fused && L >= 3 && B <= h->tail_max_b && h->edges[2].kind == 0 && h->gb[2].ok && gs_window_ok(h->edges[2]) && h->N[2] < 65536;
+  // A sample's top spread over S = 2 / 4 workgroups (by output tile of both Linear edges) while all B x S of them are resident
+  // at one per CU (they wait for each other); the top_split option caps S.  The results do not depend on S.
+  // S = 4 while B <= n_cu / 4 (base B = 1: 52 -> 38 us per launch), S = 2 while B <= n_cu / 2.  (Before k_top also ran the update of
+  // layer L-1, S = 2 was a draw -- the two hand-offs cost what the shorter edges saved; with the update's tiles split over both
+  // workgroups too it wins: deep B = 128 67 -> 59 us, wide B = 128 99 -> 79 us per launch.)  topflag / xbuf are sized for
+  // TOP_SPLIT_MAXB samples.
+  p.S = 1;
+  if (h->top_split_max >= 4 && (long)B * 4 <= h->n_cu && B <= TOP_SPLIT_MAXB) p.S = 4;
+  else if (h->top_split_max >= 2 && (long)B * 2 <= h->n_cu && B <= TOP_SPLIT_MAXB) p.S = 2;
+  return p;
+}
+
 // JSON description of the launch plan of one forward (per B=1): which kernel updates which layer, tile shapes and
 // MFMA counts.  bench.py derives the algorithmic flops per kernel class from it; DESIGN.md quotes it.
 extern "C" int gnnb_describe(const gnnb_t* h, char* buf, size_t cap) {
   if (!h || !h->bound || !buf || cap < 64) return fail(GNNB_E_INVALID, "gnnb_describe: bad arguments");
   const int L = (int)h->N.size() - 2;
-  std::string o = "{\"T\": " + std::to_string(h->T) + ", \"bf3\": " + std::to_string(h->bf3 ? 1 : 0) + ", \"embed_fused\": " + std::to_string(h->embed_fuse && h->gf.size() > 1 && h->gf[1].ok ? 1 : 0) + ", \"sizes\": [";
+  const Plan p = make_plan(h, 1, 0);
+  std::string o = "{\"T\": " + std::to_string(h->T) + ", \"bf3\": " + std::to_string(h->bf3 ? 1 : 0) + ", \"embed_fused\": " + std::to_string(p.embed_in_gather ? 1 : 0) + ", \"sizes\": [";
   for (size_t k = 0; k < h->N.size(); ++k) o += (k ? ", " : "") + std::to_string(h->N[k]);
   o += "], \"updates\": [";
   auto nnz = [&](int e) -> long {     // edges of the layer graph between layer e-1 and e (no-padding upper bound)
@@ -765,7 +824,7 @@ extern "C" int gnnb_describe(const gnnb_t* h, char* buf, size_t cap) {
     }
     o += t;
   };
-  const bool top = h->use_top && h->bf3 && h->top_ok;     // k_top covers the edge into layer L, both updates of layer L and the edge back
+  const bool top = p.top_fused;     // k_top covers the edge into layer L, both updates of layer L and the edge back
   bool first = true;
   for (int k = 1; k <= L; ++k) {
     if (!first) o += ", ";
@@ -776,8 +835,8 @@ extern "C" int gnnb_describe(const gnnb_t* h, char* buf, size_t cap) {
   for (int k = L; k >= 1; --k) {
     o += ", ";
     if (k == L) item("bwd", k, nullptr, top ? "k_top+k_top" : "k_prop+k_node_update", 1);
-    else if (top && k == L - 1)      // (the update of layer L-1 rides k_top's transposed edge when its live-row list is kept: gnnb_forward `top_upd`)
-      item("bwd", k, nullptr, h->top_fuse_upd && L >= 3 && TOP_LIST_KEEP_OK(h->edges[L].n_in) ? "k_top+k_top" : "k_top+k_node_update", h->N[k + 1]);
+    else if (top && k == L - 1)      // (the update of layer L-1 rides k_top's transposed edge when its live-row list is kept: Plan::top_upd)
+      item("bwd", k, nullptr, p.top_upd ? "k_top+k_top" : "k_top+k_node_update", h->N[k + 1]);
     else item("bwd", k, &h->gb[k + 1], h->edges[k + 1].kind == 0 ? "k_convT_bwd+k_node_update" : "k_dense_agg+k_node_update", h->N[k + 1]);
   }
   o += ", ";
@@ -797,7 +856,6 @@ struct WsLayout {                // plain arrays: gnnb_forward computes it on it
   size_t cnt = 0, best = 0, nb = 0, Q = 0, total = 0;     // best: B 64-bit decision keys + the finished-workgroup counter of k_score
   size_t topflag = 0, topx = 0;                           // k_top's workgroup split: arrival counters, (B, 8, 64) exchange buffer
 };
-#define TOP_SPLIT_MAXB 128      // k_top only splits a sample over workgroups while B x S workgroups fit the chip: B <= n_cu / 2
 static size_t align64(size_t nfloats) { return (nfloats + 63) & ~(size_t)63; }
 static WsLayout ws_layout(const gnnb_t* h, int B) {
   WsLayout w;
@@ -949,16 +1007,402 @@ static int mlp_grid(const gnnb_t* h, long ntiles) {
   return (int)(g < 1 ? 1 : g);
 }
 
-template <int C>
-static void launch_conv_fwd(const ConvArgs& a, hipStream_t st) {
-  const long waves = (long)a.B * a.H_out * a.W_out;
-  hipLaunchKernelGGL(k_conv_fwd<C>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
-}
-template <int C>
-static void launch_convT(const ConvArgs& a, hipStream_t st) {
-  const long waves = (long)a.B * a.H_in * a.W_in;
-  hipLaunchKernelGGL(k_convT_bwd<C>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
-}
+// The aggregates of edges without MFMA gather tables.  VALU conv kernels, compiled for the channel counts bind admits: by output
+// channels forward, by input channels transposed (anything else than 3, 8, 16 takes the 32-channel form).  The per-tile Linear
+// kernel: [0] splits K (K >= 512), [1] does not.  (The order of the three tables is the order the kernels have in the code object.)
+static void (*const kConvFwd[4])(ConvArgs) = {k_conv_fwd<3>, k_conv_fwd<8>, k_conv_fwd<16>, k_conv_fwd<32>};
+static void (*const kDenseAgg[2])(DenseArgs) = {k_dense_agg<true>, k_dense_agg<false>};
+static void (*const kConvT[4])(ConvArgs) = {k_convT_bwd<3>, k_convT_bwd<8>, k_convT_bwd<16>, k_convT_bwd<32>};
+static int conv_channel_form(int c) { return c == 3 ? 0 : c == 8 ? 1 : c == 16 ? 2 : 3; }
+
+// The launches of one gnnb_forward call: the call's arguments, its workspace and its plan, and one method per launch (or choice of
+// launch) of a forward.  It lives on gnnb_forward's stack; proj[] is the deferred projection of the rows of mu[k] after the kernels
+// enqueued so far (gnnb_pack.h).
+struct Forward {
+  gnnb_t* h;
+  const gnnb_batch* in;
+  int B, K, L;
+  const Plan& p;
+  const WsLayout& w;
+  float* ws;
+  float* scores;
+  int32_t* decisions;
+  int32_t* status;
+  hipStream_t st;
+  int* cnt;                         // the list counters (the control block of this workspace, gnnb_handle::d_ctl)
+  Launcher lz;
+  float* nb;
+  // The rows of layer 1 the input-layer update aggregates went through its 64x64 map on the producer side (PackPostInp).
+  // Outside inspection runs nothing else reads the plain rows of that half-pass, so the mapped rows simply take their place
+  // in mu[1] (whose dead rows k_classify already zeroed); inspection runs keep both, the mapped ones in F1.
+  float* rows1_for_input;
+  int roff[MAXL + 2] = {0};         // offset of layer k inside the flat ReLU index
+  int proj[MAXL + 2];
+  int top_launches = 0;
+
+  Forward(gnnb_t* h_, const gnnb_batch* in_, int B_, const Plan& p_, const WsLayout& w_, void* workspace, float* scores_, int32_t* decisions_,
+          int32_t* status_, hipStream_t st_, int* cnt_)
+      : h(h_), in(in_), B(B_), K((int)h_->N.size() - 1), L(K - 1), p(p_), w(w_), ws((float*)workspace), scores(scores_), decisions(decisions_),
+        status(status_), st(st_), cnt(cnt_), lz{h_, st_}, nb(ws + w_.nb), rows1_for_input(p_.debug_full ? ws + w_.F1 : ws + w_.mu[1]) {
+    for (int k = 2; k <= L + 1; ++k) roff[k] = roff[k - 1] + h->N[k - 1];
+    for (int k = 0; k < MAXL + 2; ++k) proj[k] = -1;
+  }
+  float* mu(int k) const { return ws + w.mu[k]; }
+  int* ilist(size_t off) const { return reinterpret_cast<int*>(ws + off); }
+  unsigned long long* best() const { return reinterpret_cast<unsigned long long*>(ws + w.best); }
+  int* done_ctr() const { return reinterpret_cast<int*>(ws + w.best + 2 * (size_t)B); }
+
+  // The rows of dead nodes are zero by definition (mu = (.) * live).  Every default consumer of a layer's rows walks only the
+  // live ones (sparse gathers, the compacted Linear edges of k_top, the score head), so nothing needs them in memory; they
+  // are written (k_classify) only for a layer with a consumer that reads every row: VALU / non-sparse gathers, the
+  // per-sample / per-tile dense kernels, k_prop, inspection runs.
+  bool reads_live_rows_only(int e, bool transposed) const {      // edge e between layers e-1 and e; transposed: reads layer e
+    if (e == L && p.top_fused) return transposed || TOP_LIST_OK(h->edges[L].n_in);
+    return (transposed ? h->gb[e] : h->gf[e]).ok;
+  }
+  bool zero_dead_rows(int k) const {
+    if (p.debug_full) return true;
+    if (k == L) return !p.top_fused;                                // k_top writes every row of layer L itself
+    return !(reads_live_rows_only(k + 1, false) && reads_live_rows_only(k, true));
+  }
+
+  // ---- once per forward: classification lists, bias sums, input embedding, embedding-independent feature chains ----
+  PreAllArgs pre_args() const {
+    PreAllArgs a{};
+    a.pack_f = h->d_pack[PK_PRE_FWD]; a.pack_b = h->d_pack[PK_PRE_BWD];
+    a.L = L; a.do_bwd = p.limit >= 2 ? 1 : 0; a.cnt = cnt + 4;
+    for (int k = 1; k <= L; ++k) {
+      const int i = k - 1, q = h->relu_q[k];
+      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.dual[i] = in->dual[k - 1];
+      a.z_pre[i] = in->primal[q - 1]; a.z_post[i] = in->primal[q]; a.bias[i] = h->dev[k].bias;
+      a.Pf[i] = ws + w.Pf[k]; a.Pb[i] = ws + w.Pb[k]; a.list[i] = ilist(w.amb[k]);
+      a.N[i] = h->N[k]; a.hw[i] = h->hw[k];
+    }
+    return a;
+  }
+  void classify() {
+    ClassifyArgs a{};
+    a.L = L; a.mask = in->mask; a.scores = scores; a.cnt = cnt + 4; a.R = h->R;
+    a.status = status; a.best = best(); a.done = done_ctr(); a.B = B;
+    a.topflag = reinterpret_cast<int*>(ws + w.topflag); a.nflag = std::min(B, TOP_SPLIT_MAXB);
+    a.mu2 = p.debug_full ? ws + w.F1 : nullptr;      // inspection runs keep the plain rows in mu[1] and the mapped ones in F1
+    int blk = 0;
+    for (int k = 1; k <= L; ++k) {
+      const int i = k - 1;
+      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.mu[i] = mu(k); a.zero[i] = zero_dead_rows(k) ? 1 : 0;
+      a.live[i] = ilist(w.live[k]); a.amb[i] = ilist(w.amb[k]); a.score[i] = ilist(w.score[k]);
+      a.livef[i] = ws + w.lf[k];
+      a.G[i] = (long)B * h->N[k]; a.N[i] = h->N[k]; a.off[i] = roff[k];
+      a.blk0[i] = blk;
+      blk += (int)((a.G[i] + CLS_BLOCK - 1) / CLS_BLOCK);
+    }
+    a.blk0[L] = blk;
+    if (p.cls_pre) {
+      const PreAllArgs pre = pre_args();
+      lz.run(PC_CLASSIFY, [&] { hipLaunchKernelGGL(k_classify_pre, dim3((unsigned)blk), dim3(CLS_THREADS), CLSPRE_LDS_BYTES, st, a, pre); });
+    } else {
+      lz.run(PC_CLASSIFY, [&] { hipLaunchKernelGGL(k_classify, dim3((unsigned)blk), dim3(CLS_THREADS), 0, st, a); });
+    }
+  }
+  void livesum() {   // bias-sum scalars of every edge and direction (the rows carry deferred projections)
+    LiveSumArgs a{};
+    a.B = B;
+    int q = 0, maxw = 0;
+    auto push = [&](int kind, const Edge& e, const float* wt, int ld, const float* lf, float* out, int Ndst, int Nsrc, int normalise) {
+      LiveSumJob& j = a.job[q++];
+      j.kind = kind; j.w = wt; j.lf = lf; j.out = out; j.Ndst = Ndst; j.Nsrc = Nsrc; j.ld = ld; j.normalise = normalise;
+      j.c_in = e.c_in; j.h_in = e.h_in; j.w_in = e.w_in; j.c_out = e.c_out; j.h_out = e.h_out; j.w_out = e.w_out;
+      j.kh = e.kh; j.kw = e.kw; j.stride = e.stride; j.pad = e.pad;
+      const long nw = (long)e.c_in * e.c_out * e.kh * e.kw;
+      j.wlds = (e.kind == 0 && nw <= LIVESUM_MAXW) ? (int)nw : 0;
+      maxw = std::max(maxw, j.wlds);
+    };
+    // edges whose aggregate comes from a sparse gather get their bias sums from that gather (GArgs.sout / GIArgs.s_from_gather)
+    for (int k = 1; k <= L; ++k) {            // forward edge k: source layer k-1 (the input layer is all live)
+      const Edge& e = h->edges[k];
+      if (k == 1 && p.s1_table) continue;
+      if (k >= 2 && h->gf[k].ok) continue;
+      if (k == L && p.top_s_fwd) continue;
+      push(e.kind == 0 ? 0 : 1, e, e.kind == 0 ? h->dev[k].w_fwd : h->dev[k].w_bwd, h->dev[k].ld_bwd, k > 1 ? ws + w.lf[k - 1] : nullptr,
+           ws + w.sf[k], h->N[k], h->N[k - 1], 0);
+    }
+    if (p.limit >= 2)
+      for (int k = 0; k < L; ++k) {           // edge k+1 transposed: source layer k+1
+        const Edge& e = h->edges[k + 1];
+        if (h->gb[k + 1].ok) continue;
+        if (k == L - 1 && p.top_s_bwd) continue;
+        push(e.kind == 0 ? 2 : 3, e, h->dev[k + 1].w_bwd, h->dev[k + 1].ld_bwd, ws + w.lf[k + 1], ws + w.sb[k], h->N[k], h->N[k + 1],
+             k >= 1 ? 1 : 0);
+      }
+    a.njobs = q;
+    if (q == 0) return;                 // every edge's bias sums come from its gather, k_top or the bind-time table
+    int maxn = 0;
+    for (int k = 0; k <= L; ++k) maxn = std::max(maxn, h->N[k]);
+    a.lv_floats = (maxn + 3) & ~3;
+    if ((size_t)(a.lv_floats + maxw) * 4 > 160 * 1024) {      // very wide layers: leave the weights in global memory
+      for (int i = 0; i < q; ++i) a.job[i].wlds = 0;
+      maxw = 0;
+    }
+    // (running this and k_pre on a side stream under k_embed / the first aggregation was measured: 1.72 ms vs 1.59 ms in-line)
+    lz.run(PC_LIVESUM, [&] { hipLaunchKernelGGL(k_livesum, dim3((unsigned)B, (unsigned)q), dim3(256), (size_t)(a.lv_floats + maxw) * sizeof(float), st, a); });
+  }
+  void input_embedding() {
+    const long G = (long)B * h->N[0];
+    EmbedArgs a{h->d_pack[PK_EMBED] + PackEmbed::W, h->d_pack[PK_EMBED] + PackEmbed::B, in->lb[0], in->x_lp, in->ub[0], mu(0), G};
+    long grid = (G + 16 * EMBED_UNROLL - 1) / (16 * EMBED_UNROLL);
+    if (grid > (long)h->n_cu * 16) grid = (long)h->n_cu * 16;
+    // with the MFMA gather on the first edge, round 0 computes the embedding inside that gather (k_gather<true>): nothing
+    // else reads mu[0] before the input-layer update overwrites it.  Inspection runs keep the rows.
+    if (!p.embed_in_gather) lz.run(PC_EMBED, [&] { hipLaunchKernelGGL(k_embed, dim3((unsigned)grid), dim3(256), 0, st, a); });
+    proj[0] = L_INP_F_1;
+  }
+  void pre() {
+    long nt = 0;                                      // upper bound: the kernel reads the real counts on the device
+    for (int k = 1; k <= L; ++k) nt += (((long)B * h->N[k] + 31) / 32) * 2;
+    const PreAllArgs a = pre_args();
+    const size_t lds = (h->bf3 ? (size_t)PackPreBwdL3::FLOATS : (size_t)PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4;
+    void (*kern)(PreAllArgs) = h->bf3 ? k_pre<true> : k_pre<false>;
+    lz.run(PC_PRE, [&] { hipLaunchKernelGGL(kern, dim3(mlp_grid(h, nt / 8)), dim3(PRE_WAVES * 64), lds, st, a); });
+  }
+  void pre_inp() {
+    const long G = (long)B * h->N[0];
+    const TileMap tm = bwd_map(h, 0);
+    const long nt = map_tiles(tm, B);
+    PreArgs a{h->d_pack[PK_PRE_INP], in->lb[0], in->ub[0], nullptr, nullptr, nullptr, nullptr, ws + w.Q, G, nt, h->N[0], 1,
+              to_dtm(tm), nullptr, nullptr};
+    lz.run(PC_PRE_INP, [&] { hipLaunchKernelGGL(k_pre_inp, dim3(mlp_grid(h, nt)), dim3(WG_MLP), PackPreInp::FLOATS * 4, st, a); });
+  }
+
+  // ---- phase A: aggregates ----
+  // round 0's first forward gather computes the input embedding itself (no mu[0] rows: Plan::embed_in_gather)
+  bool embed_src(int k) const { return k == 1 && p.embed_in_gather && proj[0] == L_INP_F_1; }
+  // a gather over conv edge table `d` into layer k; sparse: behind a ReLU layer (src_layer), skipping the (zero) rows of that
+  // layer's dead nodes and producing the bias sums in `sout` on the way
+  GArgs gather_args(const DevGather& d, int k, const float* src, bool scored, bool sparse, int src_layer, float* sout) const {
+    return GArgs{in->lb[k], in->ub[k], in->mask, src, nb, map_tiles(d.g.tm, B), scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
+                 EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr,
+                 sparse ? in->ub[src_layer] : nullptr, sparse ? sout : nullptr};
+  }
+  void gather(const DevGather& d, int k, const float* src, bool scored, bool embed, int src_layer, float* sout) {   // MFMA
+    const bool sparse = !embed && src_layer >= 1;
+    const GArgs a = gather_args(d, k, src, scored, sparse, src_layer, sout);
+    const size_t lds = gather_lds_bytes(d, 0) + (sparse ? sparse_tab_bytes(d) : 0) + (d.g.lanes == 16 ? 16 + (size_t)WAVES_MLP * STAGE16_FLOATS * 4 : 0);
+    constexpr int kGatherOcc = 2;     // workgroups per CU (k_gather's launch bounds; its LDS footprint is only the tap matrix)
+    long grid = (a.ntiles + WAVES_MLP - 1) / WAVES_MLP;
+    if (grid > (long)h->n_cu * kGatherOcc) grid = (long)h->n_cu * kGatherOcc;
+    void (*kern)(GArgs) = d.g.lanes == 16 ? (embed ? k_gather16<true> : sparse ? k_gather16<false, true> : k_gather16<false>)
+                                          : (embed ? k_gather<true> : sparse ? k_gather<false, true> : k_gather<false>);
+    lz.run(PC_GATHER, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WG_MLP), lds, st, a); });
+  }
+  // nb <- A_e src (forward) or A_e^T src (transposed) over edge e without MFMA gather tables: the VALU conv kernels (the transposed
+  // conv divided by the tap count when `normalise`), or for a Linear edge one workgroup per sample with the source rows in LDS
+  // where they fit (dense_lds), else the per-tile kernel
+  void edge_agg(int ei, bool tr, const float* src, int normalise) {
+    const Edge& e = h->edges[ei];
+    const DevEdge& de = h->dev[ei];
+    if (e.kind == 0) {
+      const ConvArgs a{src, nb, tr ? de.w_bwd : de.w_fwd, B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
+      void (*kern)(ConvArgs) = tr ? kConvT[conv_channel_form(e.c_in)] : kConvFwd[conv_channel_form(e.c_out)];
+      const long waves = tr ? (long)B * e.h_in * e.w_in : (long)B * e.h_out * e.w_out;      // one wave per node of the output side
+      lz.run(tr ? PC_CONVT_BWD : PC_CONV_FWD, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a); });
+      return;
+    }
+    const float* At = tr ? de.w_bwd : de.w_fwd;
+    const int Ks = tr ? e.n_out : e.n_in, M = tr ? e.n_in : e.n_out, ld = tr ? de.ld_bwd : de.ld_fwd, MT = tr ? de.mt_bwd : de.mt_fwd;
+    if (h->dense_lds && (tr ? de.kpad_bwd <= 128 : de.mt_fwd <= 4)) {
+      const DenseLArgs a{At, src, nb, B, Ks, M, ld, MT, tr ? de.kpad_bwd : de.kpad_fwd};
+      void (*kern)(DenseLArgs) = tr ? k_dense_bwd_lds : k_dense_fwd_lds;
+      lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(kern, dim3(B), dim3(512), 0, st, a); });
+      return;
+    }
+    const DenseArgs a{At, src, nb, h->d_zero, B, Ks, M, ld, MT, tr ? de.ksq_bwd : de.ksq_fwd};
+    const long tiles = (long)B * MT;
+    void (*kern)(DenseArgs) = kDenseAgg[Ks >= 512 ? 0 : 1];
+    lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)(Ks >= 512 ? tiles : (tiles + 3) / 4)), dim3(256), 0, st, a); });
+  }
+  void agg_fwd(int k) {              // nb <- A_k mu[k-1]
+    if (h->gf[k].ok) gather(h->gf[k], k, mu(k - 1), false, embed_src(k), k - 1, ws + w.sf[k]);
+    else edge_agg(k, false, mu(k - 1), 0);
+  }
+  // the scored gather of the restricted last step over edge k + 1 into layer k (k_gather_scored, k_scored_tail)
+  GSArgs scored_gather_args(int k, float* out, float* sout) const {
+    const Edge& e = h->edges[k + 1];
+    return GSArgs{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], out, sout,
+                  h->N[k], e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, 1};
+  }
+  void agg_bwd(int k, bool scored) {   // nb <- A_{k+1}^T mu[k+1]  (k+1 <= L), divided by the tap count above the input layer
+    if (k >= 1 && h->gb[k + 1].ok) {
+      if (scored && gs_window_ok(h->edges[k + 1])) {
+        // the restricted last step as three kernels (tail_max_b = 0; the default is k_scored_tail): one wave per scored node instead of
+        // every tile that holds one (k_gather_scored).  Windows up to GS_SLOT_LIMIT source nodes (base, 64 slots: 31 vs 38 us for the tile
+        // gather; deep 18 vs 38; wide, 128 slots: 116 vs 99 -- kept on the list-driven form all the same, so that this path and
+        // k_scored_tail evaluate a scored node's aggregate with the same arithmetic)
+        const GSArgs a = scored_gather_args(k, nb, ws + w.sb[k]);
+        lz.run(PC_GATHER, [&] { hipLaunchKernelGGL(k_gather_scored, dim3((unsigned)h->n_cu * 4), dim3(GS_WAVES * 64), 0, st, a); });
+      } else {
+        gather(h->gb[k + 1], k, mu(k + 1), scored, false, k + 1, ws + w.sb[k]);
+      }
+      return;
+    }
+    // the input layer (k = 0) aggregates the rows of layer 1 that already went through its 64x64 map (PackPostInp)
+    edge_agg(k + 1, true, k == 0 ? rows1_for_input : mu(k + 1), k >= 1 ? 1 : 0);
+  }
+
+  // ---- phase B: node MLP over a compacted list of nodes ----
+  // post_input: this is the backward update of layer 1 and an input-layer update follows -- the kernel also applies the input
+  // update's 64x64 map to its rows (PackPostInp) and writes them to F1; only inspection runs still need the plain rows
+  // the arguments of the node update of layer k (shared by k_node_update, the fused k_gather_update, k_top and k_scored_tail)
+  UpdArgs upd_args(int k, bool fwd, bool scored, bool post_input) const {
+    // the aggregate in `nb` was built from rows whose last Linear is deferred (gnnb_pack.h), except the one k_prop writes
+    const int src_proj = fwd ? proj[k - 1] : (k < L ? proj[k + 1] : -1);
+    int pack = PK_UPD_BWD;
+    const float* sarr = nullptr;
+    int smod = 0;
+    if (fwd) {
+      pack = src_proj == L_INP_F_1 ? PK_UPD_FWD_E : (src_proj == L_INP_B2_2 ? PK_UPD_FWD_I : PK_UPD_FWD_F);
+      sarr = ws + w.sf[k];
+      if (k == 1 && p.s1_table) { sarr = h->d_s1; smod = h->N[1]; }      // the input layer is all live: one table for every sample
+    } else if (k < L) {
+      pack = PK_UPD_BWD_B;
+      sarr = ws + w.sb[k];
+    }
+    // normal: list0 = live non-ambiguous nodes (short chain), list1 = ambiguous nodes; restricted: the scored nodes, general chain
+    UpdArgs a{h->d_pack[pack], in->lb[k], in->ub[k], nb, ws + (fwd ? w.Pf[k] : w.Pb[k]), (post_input && !p.debug_full) ? nullptr : mu(k), status,
+              ilist(w.live[k]), cnt + 4 * k + (scored ? 3 : 0), ilist(scored ? w.score[k] : w.amb[k]), cnt + 4 * k + (scored ? 2 : 1), sarr, smod,
+              post_input ? rows1_for_input : nullptr, nullptr};
+    a.wp = h->d_pack[PK_POST_INP] + (h->bf3 ? (h->gb[1].ok ? PackPostInp::WPG3 : PackPostInp::WPN3) : (h->gb[1].ok ? PackPostInp::WPG : PackPostInp::WPN));
+    return a;
+  }
+  void node_update(int k, bool fwd, bool scored, bool post_input) {
+    static void (*const kern[2][2][2])(UpdArgs) = {      // [bf3][deferred][post_input]
+        {{k_node_update<8, false>, k_node_update<8, false, true>}, {k_node_update<8, true>, k_node_update<8, true, true>}},
+        {{k_node_update<12, false, false, true>, k_node_update<12, false, true, true>},
+         {k_node_update<12, true, false, true>, k_node_update<12, true, true, true>}}};
+    const long nt = ((long)B * h->N[k] + 31) / 32;
+    const UpdArgs a = upd_args(k, fwd, scored, post_input);
+    const bool bf3 = h->bf3, deferred = a.sarr != nullptr;
+    const int wv = bf3 ? 12 : 8;  // waves per workgroup (one workgroup per CU shares the LDS weights)
+    const size_t ldsb = bf3 ? (size_t)(PackUpdL3::FLOATS + (post_input ? 6144 : 0)) * 4 : (size_t)(PackUpd::FLOATS + (post_input ? 4096 : 0)) * 4;
+    long grid = (nt + wv - 1) / wv;
+    if (grid > h->n_cu) grid = h->n_cu;
+    void (*k_upd)(UpdArgs) = kern[bf3][deferred][post_input];
+    lz.run(PC_NODE_UPDATE, [&] { hipLaunchKernelGGL(k_upd, dim3((unsigned)grid), dim3(wv * 64), ldsb, st, a); });
+    proj[k] = fwd ? L_FC4_2 : L_BC4_1;
+  }
+  // One half-pass over a conv edge as ONE kernel (k_gather_update): the gather of edge k (forward) / k + 1 (transposed) and the
+  // node update of layer k, the aggregate staying in registers.  Returns false where the two-kernel path has to run: inspection
+  // runs, the restricted last step (every node it updates takes the general chain), gathers without the sparse walk behind a
+  // ReLU layer, tile forms the fused kernel is not built for, tables that do not fit beside the weights in LDS.
+  bool fused_halfpass(int k, bool fwd, bool post_input) {
+    if (p.debug_full || (!fwd && k >= L)) return false;
+    const DevGather& d = fwd ? h->gf[k] : h->gb[k + 1];
+    const int src_layer = fwd ? k - 1 : k + 1;
+    const bool embed = fwd && embed_src(k);
+    if (!fusedq_ok(h, d, src_layer, embed, post_input)) return false;
+    const bool sparse = !embed && src_layer >= 1;
+    FArgs a{};
+    a.g = gather_args(d, k, fwd ? mu(k - 1) : mu(k + 1), false, sparse, src_layer, fwd ? ws + w.sf[k] : ws + w.sb[k]);
+    a.u = upd_args(k, fwd, false, post_input);
+    a.sw_from_gather = sparse ? 1 : 0;
+    a.qtiles = fusedq_qtiles(d, sparse, post_input);
+    const size_t ldsq = fusedq_lds_bytes(d, sparse, post_input, a.qtiles);
+    const long nrounds = (a.g.ntiles + QG_WAVES - 1) / QG_WAVES;
+    void (*kern)(FArgs) = d.g.lanes == 16 ? (embed ? k_gather_update_q<16, 2, false> : sparse ? k_gather_update_q<16, 1, false> : k_gather_update_q<16, 0, false>)
+                                          : (post_input ? k_gather_update_q<32, 1, true> : k_gather_update_q<32, 1, false>);
+    const dim3 g((unsigned)std::max<long>(1, std::min<long>(nrounds, h->n_cu))), b((QG_WAVES + QC_WAVES) * 64);
+    lz.run(PC_GATHER_UPDATE, [&] { hipLaunchKernelGGL(kern, g, b, ldsq, st, a); });
+    proj[k] = fwd ? L_FC4_2 : L_BC4_1;
+    return true;
+  }
+  void halfpass(int k, bool fwd, bool scored, bool post_input) {      // phase A + phase B of layer k
+    if (!scored && fused_halfpass(k, fwd, post_input)) return;
+    if (fwd) agg_fwd(k);
+    else agg_bwd(k, scored);
+    node_update(k, fwd, scored, post_input);
+  }
+  void update_input() {
+    proj[0] = L_INP_B2_2;
+    if (h->gb[1].ok) {
+      const DevGather& d = h->gb[1];
+      const long nt = map_tiles(d.g.tm, B);
+      // the sparse walk over the live rows of layer 1, which also yields the bias sums (s_from_gather)
+      GIArgs a{h->d_pack[PK_PRE_INP], h->d_pack[PK_UPD_INP], in->lb[0], in->ub[0], rows1_for_input, ws + w.sb[0], mu(0), nt, to_dtm(d.g.tm), to_dg(d, h->d_zero),
+               in->lb[1], in->ub[1], 1};
+      const size_t lds = gather_lds_bytes(d, PackUpdInp::FLOATS + PackPreInp::FLOATS) + 8 + (size_t)WAVES_MLP * (2 * d.g.K2 + 32) * 8;
+      constexpr int kGiuOcc = 2;        // workgroups per CU (<= 128 VGPRs: two 8-wave workgroups fit)
+      long giu_grid = (nt + WAVES_MLP - 1) / WAVES_MLP;
+      if (giu_grid > (long)h->n_cu * kGiuOcc) giu_grid = (long)h->n_cu * kGiuOcc;
+      void (*kern)(GIArgs) = h->bf3 ? k_gather_input_update<true, true> : k_gather_input_update<true, false>;
+      lz.run(PC_GATHER_INPUT, [&] { hipLaunchKernelGGL(kern, dim3(giu_grid), dim3(WG_MLP), lds, st, a); });
+      return;
+    }
+    agg_bwd(0, false);
+    const long G = (long)B * h->N[0], nt = (G + 31) / 32;
+    UpdInpArgs a{h->d_pack[PK_UPD_INP], nb, ws + w.Q, ws + w.sb[0], mu(0), G, nt};
+    lz.run(PC_INPUT_UPDATE, [&] { hipLaunchKernelGGL(k_input_update, dim3(mlp_grid(h, nt)), dim3(WG_MLP), PackUpdInp::FLOATS * 4, st, a); });
+  }
+
+  // ---- the top of the network ----
+  // k_top: the forward half-pass of layer L, the property node and the backward half-pass of layer L in one launch, the aggregate of
+  // layer L-1 left in `nb` (and with Plan::top_upd the backward update of layer L-1 done as well)
+  void top() {
+    const Edge& e = h->edges[L];
+    const DevEdge& de = h->dev[L];
+    TopArgs a{};
+    a.df = DenseLArgs{de.w_fwd, mu(L - 1), nullptr, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
+    a.db = DenseLArgs{de.w_bwd, nullptr, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
+    a.pack_f = h->d_pack[PK_UPD_FWD_F]; a.pack_b = h->d_pack[PK_UPD_BWD]; a.pack_p = h->d_pack[PK_PROP];
+    a.Pf = ws + w.Pf[L]; a.Pb = ws + w.Pb[L];
+    a.sf = p.top_s_fwd ? nullptr : ws + w.sf[L];              // null: F1 walks exactly the live rows of layer L-1 and sums its weights itself
+    a.sb_out = p.top_s_bwd ? ws + w.sb[L - 1] : nullptr;
+    a.lb = in->lb[L]; a.ub = in->ub[L];
+    a.lbm = in->lb[L - 1]; a.ubm = in->ub[L - 1];
+    a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.lbK = in->lb[K]; a.ubK = in->ub[K]; a.z_out = in->primal[in->n_primal - 1];
+    a.mu_prop = mu(K); a.mu = mu(L); a.status = status; a.N = h->N[L];
+    a.xbuf = ws + w.topx; a.xflag = reinterpret_cast<int*>(ws + w.topflag); a.xbase = top_launches * 2 * p.S;
+    a.fuse_um = p.top_upd ? 1 : 0;
+    if (p.top_upd) a.um = upd_args(L - 1, false, false, false);
+    ++top_launches;
+    void (*kern)(TopArgs) = p.S == 4 ? k_top<1> : p.S == 2 ? k_top<2> : k_top<4>;
+    lz.run(PC_TOP, [&] { hipLaunchKernelGGL(kern, dim3(B * p.S), dim3(512), TOP_LDS_FLOATS * 4, st, a); });
+    proj[L] = L_BC4_1;
+  }
+  // the property node (graph_conv.py:194-210); the backward sweep starts with the edge from it, whose aggregate the same kernel writes
+  void prop(bool bwd_follows) {
+    PropArgs a{h->d_pack[PK_PROP], mu(L), in->prop_w, in->prop_b, in->lb[K], in->ub[K], in->primal[in->n_primal - 1], mu(K),
+               bwd_follows ? nb : nullptr, B, h->N[L], in->lb[L], in->ub[L]};
+    lz.run(PC_PROP_FWD, [&] { hipLaunchKernelGGL(k_prop, dim3(B), dim3(256), 0, st, a); });
+  }
+
+  // scores (graph_conv.py:442-450) and decision (graph_score.py:41-47); with Plan::tail the restricted last step (scored gather +
+  // node update of layer 1) and the score head are ONE launch, k_scored_tail (tail_max_b = 0: k_gather_scored, k_node_update, k_score)
+  void score() {
+    ScoreArgs a{};
+    a.best = best(); a.done = done_ctr(); a.dec = decisions; a.B = B; a.n_relu = L;
+    a.pack = h->d_pack[proj[1] == L_FC4_2 ? PK_SCORE_F : PK_SCORE_B]; a.scores = scores; a.L = L; a.R = h->R; a.cnt = cnt + 4; a.cnt_all = cnt;
+    long nt = 0;
+    for (int k = 1; k <= L; ++k) {
+      const int i = k - 1;
+      a.mu[i] = mu(k); a.list[i] = ilist(w.score[k]); a.N[i] = h->N[k]; a.off[i] = roff[k];
+      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k];
+      nt += ((long)B * h->N[k] + 31) / 32;
+      a.cum[k - 1] = roff[k] + h->N[k];
+    }
+    if (!p.tail) {
+      lz.run(PC_SCORE, [&] { hipLaunchKernelGGL(k_score, dim3(mlp_grid(h, nt / 4)), dim3(WG_MLP), PackScore::FLOATS * 4, st, a); });
+      return;
+    }
+    TailArgs tail{};
+    tail.g = scored_gather_args(1, nullptr, nullptr);
+    tail.f.u = upd_args(1, false, true, false);
+    tail.f.sw_from_gather = 1;
+    tail.s = a;
+    const int grid = (int)std::min<long>(h->n_cu, std::max<long>(1, ((long)B * h->N[1] + 15) / 16));
+    const int nslots = gs_slots(h->edges[2]);
+    tail.sp = tail_slots_pad(nslots);
+    lz.run(PC_SCORE, [&] { hipLaunchKernelGGL(k_scored_tail, dim3(grid), dim3(TAIL_WAVES * 64), tail_lds_bytes(nslots), st, tail); });
+  }
+};
 
 extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* scores, int32_t* decisions, int32_t* status,
                             void* workspace, size_t workspace_bytes, void* stream) {
@@ -980,14 +1424,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
   const WsLayout w = ws_layout(h, B);
   if (workspace_bytes < w.total * sizeof(float))
     return fail(GNNB_E_NOMEM, "gnnb_forward: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
-  float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  Launcher lz{h, st};
-  auto mu = [&](int k) { return ws + w.mu[k]; };
-  float* nb = ws + w.nb;
-
-  unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + w.best);
-  int* done_ctr = reinterpret_cast<int*>(ws + w.best + 2 * (size_t)B);
   // the counters' control block of this workspace (see gnnb_handle::d_ctl); a workspace seen for the first time (or after a failed
   // call) gets a freshly zeroed one -- an async memset on the stream, the only time anything but kernels is enqueued
   int slot = -1;
@@ -1001,494 +1438,42 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     h->ctl_ws[slot] = workspace;
   }
   h->ctl_age[slot] = ++h->ctl_clock;
-  int* cnt = h->d_ctl + 64 * slot;
-  auto ilist = [&](size_t off) { return reinterpret_cast<int*>(ws + off); };
-  int roff[MAXL + 2] = {0};                 // offset of layer k inside the flat ReLU index
-  for (int k = 2; k <= L + 1; ++k) roff[k] = roff[k - 1] + h->N[k - 1];
-  int proj[MAXL + 2];                       // deferred projection of the rows of mu[k] after the kernels enqueued so far (call-local)
-  for (int k = 0; k < MAXL + 2; ++k) proj[k] = -1;
 
-  const int total_halfpasses = 2 * h->T;
-  const int limit = h->halfpass_limit > 0 ? std::min(h->halfpass_limit, total_halfpasses) : total_halfpasses;
-  const bool debug_full = h->halfpass_limit > 0;   // with a limit set nothing is restricted or skipped as dead
-  // The rows of layer 1 the input-layer update aggregates went through its 64x64 map on the producer side (PackPostInp).
-  // Outside inspection runs nothing else reads the plain rows of that half-pass, so the mapped rows simply take their place
-  // in mu[1] (whose dead rows k_classify already zeroed); inspection runs keep both, the mapped ones in F1.
-  float* const rows1_for_input = debug_full ? ws + w.F1 : mu(1);
-  const bool embed_in_gather = h->embed_fuse && !debug_full && h->gf[1].ok;
-  // The one-workgroup-per-sample kernels (k_top, k_dense_*_lds) run at every batch size, although a small batch leaves CUs idle
-  // (per-tile kernels vs these: B=2 0.40 vs 0.49 ms, B=128 0.96 vs 0.88 ms): the two paths round differently, and with one path
-  // for every batch size a sample's scores do not depend on what it is batched or sharded with.
-  const bool top_fused = h->use_top && h->bf3 && h->top_ok && !debug_full;      // (k_top only exists on the bf16 x 3 rate)
-  // The rows of dead nodes are zero by definition (mu = (.) * live).  Every default consumer of a layer's rows walks only the
-  // live ones (sparse gathers, the compacted Linear edges of k_top, the score head), so nothing needs them in memory; they
-  // are written (k_classify) only for a layer with a consumer that reads every row: VALU / non-sparse gathers, the
-  // per-sample / per-tile dense kernels, k_prop, inspection runs.
-  auto reads_live_rows_only = [&](int e, bool transposed) {      // edge e between layers e-1 and e; transposed: reads layer e
-    if (e == L && top_fused) return transposed || TOP_LIST_OK(h->edges[L].n_in);
-    return (transposed ? h->gb[e] : h->gf[e]).ok;
-  };
-  // k_top's Linear edges walk live rows only (when their lists fit, top_sample `compact` / `keep`), so they produce the bias sums
-  // of edge L in both directions themselves and k_livesum skips those jobs
-  const bool s1_table = L >= 2 && h->d_s1 != nullptr;      // bias sums of edge 1 forward: bind-time table
-  const int topK = L >= 1 && h->edges[L].kind == 1 ? h->edges[L].n_in : 0;
-  const bool top_s_fwd = top_fused && TOP_LIST_OK(topK);
-  const bool top_s_bwd = top_fused && TOP_LIST_KEEP_OK(topK) && limit >= 2;
-  // k_top also runs the backward node update of layer L-1 on its transposed edge's row tiles (the aggregate never reaches memory):
-  // needs the kept live-row list (B2 then walks live rows only) and a layer L-1 that is not layer 1 (whose update has the
-  // restricted / input-mapping forms)
-  const bool top_upd = top_fused && h->top_fuse_upd && L >= 3 && TOP_LIST_KEEP_OK(topK);
-  auto zero_dead_rows = [&](int k) {
-    if (debug_full) return true;
-    if (k == L) return !top_fused;                                // k_top writes every row of layer L itself
-    return !(reads_live_rows_only(k + 1, false) && reads_live_rows_only(k, true));
-  };
-  // ---- once per forward: classification lists, input embedding, embedding-independent feature chains ----
-  PreAllArgs pre{};
-  {
-    pre.pack_f = h->d_pack[PK_PRE_FWD]; pre.pack_b = h->d_pack[PK_PRE_BWD];
-    pre.L = L; pre.do_bwd = limit >= 2 ? 1 : 0; pre.cnt = cnt + 4;
-    for (int k = 1; k <= L; ++k) {
-      const int i = k - 1, q = h->relu_q[k];
-      pre.lb[i] = in->lb[k]; pre.ub[i] = in->ub[k]; pre.dual[i] = in->dual[k - 1];
-      pre.z_pre[i] = in->primal[q - 1]; pre.z_post[i] = in->primal[q]; pre.bias[i] = h->dev[k].bias;
-      pre.Pf[i] = ws + w.Pf[k]; pre.Pb[i] = ws + w.Pb[k]; pre.list[i] = ilist(w.amb[k]);
-      pre.N[i] = h->N[k]; pre.hw[i] = h->hw[k];
-    }
-  }
-  // a single subproblem: k_classify and k_pre in one launch (k_classify_pre; GNNB_CLSPRE_MAX_B, default 1)
-  const bool cls_pre = h->bf3 && B <= h->clspre_max_b;
-  {
-    ClassifyArgs a{};
-    a.L = L; a.mask = in->mask; a.scores = scores; a.cnt = cnt + 4; a.R = h->R;
-    a.status = status; a.best = best; a.done = done_ctr; a.B = B;
-    a.topflag = reinterpret_cast<int*>(ws + w.topflag); a.nflag = std::min(B, TOP_SPLIT_MAXB);
-    a.mu2 = debug_full ? ws + w.F1 : nullptr;      // inspection runs keep the plain rows in mu[1] and the mapped ones in F1
-    int blk = 0;
-    for (int k = 1; k <= L; ++k) {
-      const int i = k - 1;
-      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.mu[i] = mu(k); a.zero[i] = zero_dead_rows(k) ? 1 : 0;
-      a.live[i] = ilist(w.live[k]); a.amb[i] = ilist(w.amb[k]); a.score[i] = ilist(w.score[k]);
-      a.livef[i] = ws + w.lf[k];
-      a.G[i] = (long)B * h->N[k]; a.N[i] = h->N[k]; a.off[i] = roff[k];
-      a.blk0[i] = blk;
-      blk += (int)((a.G[i] + CLS_BLOCK - 1) / CLS_BLOCK);
-    }
-    a.blk0[L] = blk;
-    if (cls_pre) lz.run(PC_CLASSIFY, [&] { hipLaunchKernelGGL(k_classify_pre, dim3((unsigned)blk), dim3(CLS_THREADS), CLSPRE_LDS_BYTES, st, a, pre); });
-    else lz.run(PC_CLASSIFY, [&] { hipLaunchKernelGGL(k_classify, dim3((unsigned)blk), dim3(CLS_THREADS), 0, st, a); });
-  }
-
-  {   // bias-sum scalars of every edge and direction (the rows carry deferred projections)
-    LiveSumArgs a{};
-    a.B = B;
-    int q = 0, maxw = 0;
-    auto push = [&](int kind, const Edge& e, const float* wt, int ld, const float* lf, float* out, int Ndst, int Nsrc, int normalise) {
-      LiveSumJob& j = a.job[q++];
-      j.kind = kind; j.w = wt; j.lf = lf; j.out = out; j.Ndst = Ndst; j.Nsrc = Nsrc; j.ld = ld; j.normalise = normalise;
-      j.c_in = e.c_in; j.h_in = e.h_in; j.w_in = e.w_in; j.c_out = e.c_out; j.h_out = e.h_out; j.w_out = e.w_out;
-      j.kh = e.kh; j.kw = e.kw; j.stride = e.stride; j.pad = e.pad;
-      const long nw = (long)e.c_in * e.c_out * e.kh * e.kw;
-      j.wlds = (e.kind == 0 && nw <= LIVESUM_MAXW) ? (int)nw : 0;
-      maxw = std::max(maxw, j.wlds);
-    };
-    // edges whose aggregate comes from a sparse gather get their bias sums from that gather (GArgs.sout / GIArgs.s_from_gather)
-    for (int k = 1; k <= L; ++k) {            // forward edge k: source layer k-1 (the input layer is all live)
-      const Edge& e = h->edges[k];
-      if (k == 1 && s1_table) continue;
-      if (k >= 2 && h->gf[k].ok) continue;
-      if (k == L && top_s_fwd) continue;
-      push(e.kind == 0 ? 0 : 1, e, e.kind == 0 ? h->dev[k].w_fwd : h->dev[k].w_bwd, h->dev[k].ld_bwd, k > 1 ? ws + w.lf[k - 1] : nullptr,
-           ws + w.sf[k], h->N[k], h->N[k - 1], 0);
-    }
-    if (limit >= 2)
-      for (int k = 0; k < L; ++k) {           // edge k+1 transposed: source layer k+1
-        const Edge& e = h->edges[k + 1];
-        if (h->gb[k + 1].ok) continue;
-        if (k == L - 1 && top_s_bwd) continue;
-        push(e.kind == 0 ? 2 : 3, e, h->dev[k + 1].w_bwd, h->dev[k + 1].ld_bwd, ws + w.lf[k + 1], ws + w.sb[k], h->N[k], h->N[k + 1],
-             k >= 1 ? 1 : 0);
-      }
-    a.njobs = q;
-    if (q > 0) {
-    int maxn = 0;
-    for (int k = 0; k <= L; ++k) maxn = std::max(maxn, h->N[k]);
-    a.lv_floats = (maxn + 3) & ~3;
-    if ((size_t)(a.lv_floats + maxw) * 4 > 160 * 1024) {      // very wide layers: leave the weights in global memory
-      for (int i = 0; i < q; ++i) a.job[i].wlds = 0;
-      maxw = 0;
-    }
-    // (running this and k_pre on a side stream under k_embed / the first aggregation was measured: 1.72 ms vs 1.59 ms in-line)
-    lz.run(PC_LIVESUM, [&] { hipLaunchKernelGGL(k_livesum, dim3((unsigned)B, (unsigned)q), dim3(256), (size_t)(a.lv_floats + maxw) * sizeof(float), st, a); });
-    }                                   // (q == 0: every edge's bias sums come from its gather, k_top or the bind-time table)
-  }
-  {
-    const long G = (long)B * h->N[0];
-    EmbedArgs a{h->d_pack[PK_EMBED] + PackEmbed::W, h->d_pack[PK_EMBED] + PackEmbed::B, in->lb[0], in->x_lp, in->ub[0], mu(0), G};
-    long grid = (G + 16 * EMBED_UNROLL - 1) / (16 * EMBED_UNROLL);
-    if (grid > (long)h->n_cu * 16) grid = (long)h->n_cu * 16;
-    // with the MFMA gather on the first edge, round 0 computes the embedding inside that gather (k_gather<true>): nothing
-    // else reads mu[0] before the input-layer update overwrites it.  Inspection runs keep the rows.
-    if (!embed_in_gather) lz.run(PC_EMBED, [&] { hipLaunchKernelGGL(k_embed, dim3((unsigned)grid), dim3(256), 0, st, a); });
-    proj[0] = L_INP_F_1;
-  }
-  if (!cls_pre) {
-    long nt = 0;                                      // upper bound: the kernel reads the real counts on the device
-    for (int k = 1; k <= L; ++k) nt += (((long)B * h->N[k] + 31) / 32) * 2;
-    const PreAllArgs& a = pre;
-    const size_t lds = (h->bf3 ? (size_t)PackPreBwdL3::FLOATS : (size_t)PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4;
-    lz.run(PC_PRE, [&] {
-      if (h->bf3) hipLaunchKernelGGL(k_pre<true>, dim3(mlp_grid(h, nt / 8)), dim3(PRE_WAVES * 64), lds, st, a);
-      else hipLaunchKernelGGL(k_pre<false>, dim3(mlp_grid(h, nt / 8)), dim3(PRE_WAVES * 64), lds, st, a);
-    });
-  }
-  const bool need_inp = (limit >= 2) && (h->T > 1 || debug_full) && !h->gb[1].ok;    // the fused input kernel computes Q itself
-  if (need_inp) {
-    const long G = (long)B * h->N[0];
-    const TileMap tm = bwd_map(h, 0);
-    const long nt = map_tiles(tm, B);
-    PreArgs a{h->d_pack[PK_PRE_INP], in->lb[0], in->ub[0], nullptr, nullptr, nullptr, nullptr, ws + w.Q, G, nt, h->N[0], 1,
-              to_dtm(tm), nullptr, nullptr};
-    lz.run(PC_PRE_INP, [&] { hipLaunchKernelGGL(k_pre_inp, dim3(mlp_grid(h, nt)), dim3(WG_MLP), PackPreInp::FLOATS * 4, st, a); });
-  }
-
-  auto conv_args = [&](const Edge& e, const float* src, float* dst, const float* wt, int normalise) {
-    return ConvArgs{src, dst, wt, B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
-  };
-  auto gather = [&](const DevGather& d, int k, const float* src, bool scored, bool embed_src, int src_layer, float* sout) {      // phase A over a conv edge, MFMA
-    const long nt = map_tiles(d.g.tm, B);
-    // sparse: a gather behind a ReLU layer skips the (zero) rows of that layer's dead nodes
-    const bool sparse = !embed_src && src_layer >= 1;
-    GArgs a{in->lb[k], in->ub[k], in->mask, src, nb, nt, scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
-            EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr, sparse ? in->ub[src_layer] : nullptr,
-            sparse ? sout : nullptr};
-    const size_t lds = gather_lds_bytes(d, 0) + (sparse ? sparse_tab_bytes(d) : 0) + (d.g.lanes == 16 ? 16 + (size_t)WAVES_MLP * STAGE16_FLOATS * 4 : 0);
-    constexpr int kGatherOcc = 2;     // workgroups per CU (k_gather's launch bounds; its LDS footprint is only the tap matrix)
-    long grid = (nt + WAVES_MLP - 1) / WAVES_MLP;
-    if (grid > (long)h->n_cu * kGatherOcc) grid = (long)h->n_cu * kGatherOcc;
-    lz.run(PC_GATHER, [&] {
-      if (d.g.lanes == 16) {
-        if (embed_src) hipLaunchKernelGGL((k_gather16<true>), dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-        else if (sparse) hipLaunchKernelGGL((k_gather16<false, true>), dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-        else hipLaunchKernelGGL((k_gather16<false>), dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-      } else if (embed_src) hipLaunchKernelGGL(k_gather<true>, dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-      else if (sparse) hipLaunchKernelGGL((k_gather<false, true>), dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-      else hipLaunchKernelGGL(k_gather<false>, dim3((unsigned)grid), dim3(WG_MLP), lds, st, a);
-    });
-  };
-  // phase A: nb <- A_k mu[k-1]
-  auto agg_fwd = [&](int k) {
-    const Edge& e = h->edges[k];
-    if (h->gf[k].ok) { gather(h->gf[k], k, mu(k - 1), false, k == 1 && embed_in_gather && proj[0] == L_INP_F_1, k - 1, ws + w.sf[k]); return; }
-    if (e.kind == 0) {
-      ConvArgs a = conv_args(e, mu(k - 1), nb, h->dev[k].w_fwd, 0);
-      lz.run(PC_CONV_FWD, [&] {
-        switch (e.c_out) {
-          case 3: launch_conv_fwd<3>(a, st); break;
-          case 8: launch_conv_fwd<8>(a, st); break;
-          case 16: launch_conv_fwd<16>(a, st); break;
-          default: launch_conv_fwd<32>(a, st); break;
-        }
-      });
-    } else {
-      const DevEdge& de = h->dev[k];
-      if (h->dense_lds && de.mt_fwd <= 4) {        // one workgroup per sample, source rows staged in LDS
-        DenseLArgs a{de.w_fwd, mu(k - 1), nb, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
-        lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(k_dense_fwd_lds, dim3(B), dim3(512), 0, st, a); });
-        return;
-      }
-      DenseArgs a{de.w_fwd, mu(k - 1), nb, h->d_zero, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.ksq_fwd};
-      const long tiles = (long)B * a.MT;
-      lz.run(PC_DENSE_AGG, [&] {
-        if (a.K >= 512) hipLaunchKernelGGL(k_dense_agg<true>, dim3((unsigned)tiles), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_dense_agg<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a);
-      });
-    }
-  };
-  // phase A: nb <- A_{k+1}^T mu[k+1]  (k+1 <= L), conv case divided by the tap count when `normalise`
-  auto agg_bwd = [&](int k, int normalise, bool scored) {
-    const Edge& e = h->edges[k + 1];
-    // the input layer (k = 0) aggregates the rows of layer 1 that already went through its 64x64 map (PackPostInp)
-    const float* srcb = k == 0 ? rows1_for_input : mu(k + 1);
-    if (k >= 1 && scored && h->gb[k + 1].ok &&
-        e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride) <= GS_SLOT_LIMIT) {
-      // the restricted last step as three kernels (GNNB_TAIL_MAX_B=0; the default is k_scored_tail): one wave per scored node instead of
-      // every tile that holds one (k_gather_scored).  Windows up to GS_SLOT_LIMIT source nodes (base, 64 slots: 31 vs 38 us for the tile
-      // gather; deep 18 vs 38; wide, 128 slots: 116 vs 99 -- kept on the list-driven form all the same, so that this path and
-      // k_scored_tail evaluate a scored node's aggregate with the same arithmetic)
-      GSArgs a{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], nb, ws + w.sb[k],
-               h->N[k], e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
-      lz.run(PC_GATHER, [&] { hipLaunchKernelGGL(k_gather_scored, dim3((unsigned)h->n_cu * 4), dim3(GS_WAVES * 64), 0, st, a); });
-      return;
-    }
-    if (k >= 1 && h->gb[k + 1].ok) { gather(h->gb[k + 1], k, mu(k + 1), scored, false, k + 1, ws + w.sb[k]); return; }
-    if (e.kind == 0) {
-      ConvArgs a = conv_args(e, srcb, nb, h->dev[k + 1].w_bwd, normalise);
-      lz.run(PC_CONVT_BWD, [&] {
-        switch (e.c_in) {
-          case 3: launch_convT<3>(a, st); break;
-          case 8: launch_convT<8>(a, st); break;
-          case 16: launch_convT<16>(a, st); break;
-          default: launch_convT<32>(a, st); break;
-        }
-      });
-    } else {
-      const DevEdge& de = h->dev[k + 1];
-      if (h->dense_lds && de.kpad_bwd <= 128) {    // one workgroup per sample, the whole source layer in LDS
-        DenseLArgs a{de.w_bwd, srcb, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
-        lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(k_dense_bwd_lds, dim3(B), dim3(512), 0, st, a); });
-        return;
-      }
-      DenseArgs a{de.w_bwd, srcb, nb, h->d_zero, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.ksq_bwd};
-      const long tiles = (long)B * a.MT;
-      lz.run(PC_DENSE_AGG, [&] {
-        if (a.K >= 512) hipLaunchKernelGGL(k_dense_agg<true>, dim3((unsigned)tiles), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_dense_agg<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a);
-      });
-    }
-  };
-  // phase B: node MLP over a compacted list of nodes
-  // post_input: this is the backward update of layer 1 and an input-layer update follows -- the kernel also applies the input
-  // update's 64x64 map to its rows (PackPostInp) and writes them to F1; only inspection runs still need the plain rows
-  // the arguments of the node update of layer k (shared by k_node_update and the fused k_gather_update)
-  auto upd_args = [&](int k, bool fwd, bool scored, bool post_input) {
-    // the aggregate in `nb` was built from rows whose last Linear is deferred (gnnb_pack.h), except the one k_prop writes
-    const int src_proj = fwd ? proj[k - 1] : (k < L ? proj[k + 1] : -1);
-    int pack = PK_UPD_BWD;
-    const float* sarr = nullptr;
-    int smod = 0;
-    if (fwd) {
-      pack = src_proj == L_INP_F_1 ? PK_UPD_FWD_E : (src_proj == L_INP_B2_2 ? PK_UPD_FWD_I : PK_UPD_FWD_F);
-      sarr = ws + w.sf[k];
-      if (k == 1 && s1_table) { sarr = h->d_s1; smod = h->N[1]; }      // the input layer is all live: one table for every sample
-    } else if (k < L) {
-      pack = PK_UPD_BWD_B;
-      sarr = ws + w.sb[k];
-    }
-    // normal: list0 = live non-ambiguous nodes (short chain), list1 = ambiguous nodes; restricted: the scored nodes, general chain
-    UpdArgs a{h->d_pack[pack], in->lb[k], in->ub[k], nb, ws + (fwd ? w.Pf[k] : w.Pb[k]), (post_input && !debug_full) ? nullptr : mu(k), status,
-              ilist(w.live[k]), cnt + 4 * k + (scored ? 3 : 0), ilist(scored ? w.score[k] : w.amb[k]), cnt + 4 * k + (scored ? 2 : 1), sarr, smod,
-              post_input ? rows1_for_input : nullptr, nullptr};
-    a.wp = h->d_pack[PK_POST_INP] + (h->bf3 ? (h->gb[1].ok ? PackPostInp::WPG3 : PackPostInp::WPN3) : (h->gb[1].ok ? PackPostInp::WPG : PackPostInp::WPN));
-    return a;
-  };
-  // phase B: node MLP over a compacted list of nodes
-  // post_input: this is the backward update of layer 1 and an input-layer update follows -- the kernel also applies the input
-  // update's 64x64 map to its rows (PackPostInp) and writes them to F1; only inspection runs still need the plain rows
-  auto node_update = [&](int k, bool fwd, bool scored, bool post_input = false) {
-    const long nt = ((long)B * h->N[k] + 31) / 32;
-    const UpdArgs a = upd_args(k, fwd, scored, post_input);
-    const bool deferred = a.sarr != nullptr;
-    const bool bf3 = h->bf3;
-    const int wv = bf3 ? 12 : 8;  // waves per workgroup (one workgroup per CU shares the LDS weights)
-    const size_t ldsb = bf3 ? (size_t)(PackUpdL3::FLOATS + (post_input ? 6144 : 0)) * 4 : (size_t)(PackUpd::FLOATS + (post_input ? 4096 : 0)) * 4;
-    long grid = (nt + wv - 1) / wv;
-    if (grid > h->n_cu) grid = h->n_cu;
-    lz.run(PC_NODE_UPDATE, [&] {
-      const dim3 g((unsigned)grid), b12(768), b8(512);
-      if (bf3) {
-        if (post_input && deferred) hipLaunchKernelGGL((k_node_update<12, true, true, true>), g, b12, ldsb, st, a);
-        else if (post_input) hipLaunchKernelGGL((k_node_update<12, false, true, true>), g, b12, ldsb, st, a);
-        else if (deferred) hipLaunchKernelGGL((k_node_update<12, true, false, true>), g, b12, ldsb, st, a);
-        else hipLaunchKernelGGL((k_node_update<12, false, false, true>), g, b12, ldsb, st, a);
-      } else if (post_input) {
-        if (deferred) hipLaunchKernelGGL((k_node_update<8, true, true>), g, b8, ldsb, st, a);
-        else hipLaunchKernelGGL((k_node_update<8, false, true>), g, b8, ldsb, st, a);
-      } else if (deferred) hipLaunchKernelGGL((k_node_update<8, true>), g, b8, ldsb, st, a);
-      else hipLaunchKernelGGL((k_node_update<8, false>), g, b8, ldsb, st, a);
-    });
-    proj[k] = fwd ? L_FC4_2 : L_BC4_1;
-  };
-  // One half-pass over a conv edge as ONE kernel (k_gather_update): the gather of edge k (forward) / k + 1 (transposed) and the
-  // node update of layer k, the aggregate staying in registers.  Returns false where the two-kernel path has to run: inspection
-  // runs, the restricted last step (every node it updates takes the general chain), gathers without the sparse walk behind a
-  // ReLU layer, tile forms the fused kernel is not built for, tables that do not fit beside the weights in LDS.
-  auto fused_halfpass = [&](int k, bool fwd, bool post_input) -> bool {
-    if (debug_full) return false;
-    const DevGather& d = fwd ? h->gf[k] : h->gb[k + 1];
-    if (!d.ok || (!fwd && k >= L)) return false;
-    const int src_layer = fwd ? k - 1 : k + 1;
-    const bool embed_src = fwd && k == 1 && embed_in_gather && proj[0] == L_INP_F_1;
-    if (!fusedq_ok(h, d, src_layer, embed_src, post_input)) return false;
-    const bool sparse = !embed_src && src_layer >= 1;
-    const long nt = map_tiles(d.g.tm, B);
-    {
-      const int nq = fusedq_qtiles(d, sparse, post_input);
-      const size_t ldsq = fusedq_lds_bytes(d, sparse, post_input, nq);
-      FArgs a{};
-      float* sout = fwd ? ws + w.sf[k] : ws + w.sb[k];
-      a.sw_from_gather = sparse ? 1 : 0;
-      a.g = GArgs{in->lb[k], in->ub[k], in->mask, fwd ? mu(k - 1) : mu(k + 1), nb, nt, 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
-                  EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr, sparse ? in->ub[src_layer] : nullptr,
-                  a.sw_from_gather ? sout : nullptr};
-      a.u = upd_args(k, fwd, false, post_input);
-      a.qtiles = nq;
-      const long nrounds = (nt + QG_WAVES - 1) / QG_WAVES;
-      const dim3 g((unsigned)std::max<long>(1, std::min<long>(nrounds, h->n_cu))), b((QG_WAVES + QC_WAVES) * 64);
-      lz.run(PC_GATHER_UPDATE, [&] {
-        if (d.g.lanes == 16) {
-          if (embed_src) hipLaunchKernelGGL((k_gather_update_q<16, 2, false>), g, b, ldsq, st, a);
-          else if (sparse) hipLaunchKernelGGL((k_gather_update_q<16, 1, false>), g, b, ldsq, st, a);
-          else hipLaunchKernelGGL((k_gather_update_q<16, 0, false>), g, b, ldsq, st, a);
-        } else if (post_input) hipLaunchKernelGGL((k_gather_update_q<32, 1, true>), g, b, ldsq, st, a);
-        else hipLaunchKernelGGL((k_gather_update_q<32, 1, false>), g, b, ldsq, st, a);
-      });
-      proj[k] = fwd ? L_FC4_2 : L_BC4_1;
-      return true;
-    }
-  };
-  auto update_input = [&]() {
-    proj[0] = L_INP_B2_2;
-    if (h->gb[1].ok) {
-      const DevGather& d = h->gb[1];
-      const long nt = map_tiles(d.g.tm, B);
-      // the sparse walk over the live rows of layer 1, which also yields the bias sums (s_from_gather)
-      GIArgs a{h->d_pack[PK_PRE_INP], h->d_pack[PK_UPD_INP], in->lb[0], in->ub[0], rows1_for_input, ws + w.sb[0], mu(0), nt, to_dtm(d.g.tm), to_dg(d, h->d_zero),
-               in->lb[1], in->ub[1], 1};
-      const size_t lds = gather_lds_bytes(d, PackUpdInp::FLOATS + PackPreInp::FLOATS) + 8 + (size_t)WAVES_MLP * (2 * d.g.K2 + 32) * 8;
-      constexpr int kGiuOcc = 2;        // workgroups per CU (<= 128 VGPRs: two 8-wave workgroups fit)
-      long giu_grid = (nt + WAVES_MLP - 1) / WAVES_MLP;
-      if (giu_grid > (long)h->n_cu * kGiuOcc) giu_grid = (long)h->n_cu * kGiuOcc;
-      lz.run(PC_GATHER_INPUT, [&] {
-        if (h->bf3) hipLaunchKernelGGL((k_gather_input_update<true, true>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
-        else hipLaunchKernelGGL((k_gather_input_update<true, false>), dim3(giu_grid), dim3(WG_MLP), lds, st, a);
-      });
-      return;
-    }
-    agg_bwd(0, 0, false);
-    const long G = (long)B * h->N[0], nt = (G + 31) / 32;
-    UpdInpArgs a{h->d_pack[PK_UPD_INP], nb, ws + w.Q, ws + w.sb[0], mu(0), G, nt};
-    lz.run(PC_INPUT_UPDATE, [&] { hipLaunchKernelGGL(k_input_update, dim3(mlp_grid(h, nt)), dim3(WG_MLP), PackUpdInp::FLOATS * 4, st, a); });
-  };
-
-  // the top of the network as one launch per round (k_top); with a half-pass limit (inspection) the separate kernels run
-  int top_launches = 0;
-  auto top = [&]() {
-    const Edge& e = h->edges[L];
-    const DevEdge& de = h->dev[L];
-    TopArgs a{};
-    a.df = DenseLArgs{de.w_fwd, mu(L - 1), nullptr, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
-    a.db = DenseLArgs{de.w_bwd, nullptr, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
-    a.pack_f = h->d_pack[PK_UPD_FWD_F]; a.pack_b = h->d_pack[PK_UPD_BWD]; a.pack_p = h->d_pack[PK_PROP];
-    a.Pf = ws + w.Pf[L]; a.Pb = ws + w.Pb[L];
-    a.sf = top_s_fwd ? nullptr : ws + w.sf[L];              // null: F1 walks exactly the live rows of layer L-1 and sums its weights itself
-    a.sb_out = top_s_bwd ? ws + w.sb[L - 1] : nullptr;
-    a.lb = in->lb[L]; a.ub = in->ub[L];
-    a.lbm = in->lb[L - 1]; a.ubm = in->ub[L - 1];
-    a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.lbK = in->lb[K]; a.ubK = in->ub[K]; a.z_out = in->primal[in->n_primal - 1];
-    a.mu_prop = mu(K); a.mu = mu(L); a.status = status; a.N = h->N[L];
-    // A sample's top spread over S = 2 / 4 workgroups (by output tile of both Linear edges) while all B x S of them are resident
-    // at one per CU (they wait for each other); GNNB_TOP_SPLIT = 1 / 2 / 4 caps S.  The results do not depend on S.
-    // S = 4 while B <= n_cu / 4 (base B = 1: 52 -> 38 us per launch), S = 2 while B <= n_cu / 2.  (Before k_top also ran the update of
-    // layer L-1, S = 2 was a draw -- the two hand-offs cost what the shorter edges saved; with the update's tiles split over both
-    // workgroups too it wins: deep B = 128 67 -> 59 us, wide B = 128 99 -> 79 us per launch.)
-    int S = 1;
-    if (h->top_split_max >= 4 && (long)B * 4 <= h->n_cu && B <= TOP_SPLIT_MAXB) S = 4;      // (topflag / xbuf are sized for TOP_SPLIT_MAXB samples)
-    else if (h->top_split_max >= 2 && (long)B * 2 <= h->n_cu && B <= TOP_SPLIT_MAXB) S = 2;
-    a.xbuf = ws + w.topx; a.xflag = reinterpret_cast<int*>(ws + w.topflag); a.xbase = top_launches * 2 * S;
-    a.fuse_um = top_upd ? 1 : 0;
-    if (top_upd) a.um = upd_args(L - 1, false, false, false);
-    ++top_launches;
-    lz.run(PC_TOP, [&] {
-      if (S == 4) hipLaunchKernelGGL(k_top<1>, dim3(B * 4), dim3(512), TOP_LDS_FLOATS * 4, st, a);
-      else if (S == 2) hipLaunchKernelGGL(k_top<2>, dim3(B * 2), dim3(512), TOP_LDS_FLOATS * 4, st, a);
-      else hipLaunchKernelGGL(k_top<4>, dim3(B), dim3(512), TOP_LDS_FLOATS * 4, st, a);
-    });
-    proj[L] = L_BC4_1;
-  };
-
-  // The restricted last step (scored gather + node update of layer 1) and the score head are ONE launch, k_scored_tail
-  // (GNNB_TAIL_MAX_B=0: the three kernels k_gather_scored, k_node_update, k_score)
-  bool tail_fused = false;
-  TailArgs tail{};
-  auto try_tail = [&](int k) -> bool {
-    const Edge& e = h->edges[k + 1];
-    if (!(B <= h->tail_max_b && h->bf3 && k == 1 && L >= 2 && !debug_full && e.kind == 0 && h->gb[k + 1].ok &&
-          e.c_out * ((e.kh + e.stride - 1) / e.stride) * ((e.kw + e.stride - 1) / e.stride) <= GS_SLOT_LIMIT &&
-          h->N[k + 1] < 65536))
-      return false;
-    tail.g = GSArgs{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], nullptr, nullptr,
-                    h->N[k], e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, 1};
-    tail.f = FArgs{};
-    tail.f.u = upd_args(k, false, true, false);
-    tail.f.sw_from_gather = 1;
-    tail_fused = true;
-    proj[k] = L_BC4_1;
-    return true;
-  };
+  const Plan p = make_plan(h, B, h->halfpass_limit);
+  Forward f(h, in, B, p, w, workspace, scores, decisions, status, st, h->d_ctl + 64 * slot);
+  f.classify();
+  f.livesum();
+  f.input_embedding();
+  if (!p.cls_pre) f.pre();
+  if (p.need_inp) f.pre_inp();
+  // T rounds (graph_conv.py:107-388): forward sweep up to layer last_fwd, then k_top (F1 .. B2: both half-passes of layer L) or
+  // k_prop (the property node); either leaves the aggregate of layer last_fwd in `nb` for the backward sweep, which runs in
+  // Gauss-Seidel order (layer k reads the already-updated mu[k+1]).  A half-pass limit (inspection; no k_top) may stop after the
+  // forward sweep.
+  const int last_fwd = p.top_fused ? L - 1 : L;
   int done = 0;
-  for (int t = 0; t < h->T && done < limit; ++t) {
-    if (top_fused) {
-      for (int k = 1; k < L; ++k) {
-        if (fused_halfpass(k, true, false)) continue;
-        agg_fwd(k);
-        node_update(k, true, false);
-      }
-      top();                                     // F1 .. B2: both half-passes of layer L, aggregate of layer L-1 in `nb`
-      for (int k = L - 1; k >= 1; --k) {
-        if (k == L - 1 && top_upd) { proj[k] = L_BC4_1; continue; }      // done inside k_top
-        const bool scored = t == h->T - 1 && k == 1;
-        if (scored && k < L - 1 && try_tail(k)) continue;
-        if (k < L - 1 && !scored && fused_halfpass(k, false, k == 1 && t < h->T - 1)) continue;
-        if (k < L - 1) agg_bwd(k, 1, scored);
-        node_update(k, false, scored, k == 1 && t < h->T - 1);
-      }
-      if (t < h->T - 1) update_input();
-      done += 2;
-      continue;
-    }
-    // forward sweep (graph_conv.py:107-192) + property node (:194-210)
-    for (int k = 1; k <= L; ++k) {
-      if (fused_halfpass(k, true, false)) continue;
-      agg_fwd(k);
-      node_update(k, true, false);
-    }
-    {
-      // the backward sweep starts with the edge from the property node: its aggregate is written by the same kernel
-      const bool bwd_follows = done + 1 < limit;
-      PropArgs a{h->d_pack[PK_PROP], mu(L), in->prop_w, in->prop_b, in->lb[K], in->ub[K], in->primal[in->n_primal - 1], mu(K),
-                 bwd_follows ? nb : nullptr, B, h->N[L], in->lb[L], in->ub[L]};
-      lz.run(PC_PROP_FWD, [&] { hipLaunchKernelGGL(k_prop, dim3(B), dim3(256), 0, st, a); });
-    }
-    if (++done >= limit) break;
-    // backward sweep (:222-350), Gauss-Seidel order: layer k reads the already-updated mu[k+1]
-    for (int k = L; k >= 1; --k) {
+  for (int t = 0; t < h->T && done < p.limit; ++t) {
+    const bool last_round = t == h->T - 1;
+    for (int k = 1; k <= last_fwd; ++k) f.halfpass(k, true, false, false);
+    if (p.top_fused) f.top();
+    else f.prop(done + 1 < p.limit);
+    if (++done >= p.limit) break;
+    for (int k = last_fwd; k >= 1; --k) {
       // after the last backward step mu[1] is only read by the score head, i.e. at the scored nodes
-      const bool scored = !debug_full && t == h->T - 1 && k == 1;
-      if (k < L && !scored && fused_halfpass(k, false, k == 1 && t < h->T - 1)) continue;
-      if (k < L) agg_bwd(k, 1, scored);          // (k == L: k_prop already wrote the aggregate from the property node)
-      node_update(k, false, scored, k == 1 && (t < h->T - 1 || debug_full));
+      const bool scored = !p.debug_full && last_round && k == 1, post_input = k == 1 && (!last_round || p.debug_full);
+      if (k == last_fwd && p.top_upd) f.proj[k] = L_BC4_1;            // done inside k_top
+      else if (k == last_fwd) f.node_update(k, false, scored, post_input);      // its aggregate is already in `nb`
+      else if (scored && p.tail) f.proj[k] = L_BC4_1;                  // k_scored_tail, launched with the score head
+      else f.halfpass(k, false, scored, post_input);
     }
     // input layer (:360-385): its last-round result is never read, so it only runs when another round follows
-    if (t < h->T - 1 || debug_full) update_input();
+    if (!last_round || p.debug_full) f.update_input();
     ++done;
   }
-
-  // scores (graph_conv.py:442-450) and decision (graph_score.py:41-47)
-  {
-    ScoreArgs a{};
-    a.best = best; a.done = done_ctr; a.dec = decisions; a.B = B; a.n_relu = L;
-    a.pack = h->d_pack[proj[1] == L_FC4_2 ? PK_SCORE_F : PK_SCORE_B]; a.scores = scores; a.L = L; a.R = h->R; a.cnt = cnt + 4; a.cnt_all = cnt;
-    long nt = 0;
-    for (int k = 1; k <= L; ++k) {
-      const int i = k - 1;
-      a.mu[i] = mu(k); a.list[i] = ilist(w.score[k]); a.N[i] = h->N[k]; a.off[i] = roff[k];
-      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k];
-      nt += ((long)B * h->N[k] + 31) / 32;
-      a.cum[k - 1] = roff[k] + h->N[k];
-    }
-    if (tail_fused) {
-      tail.s = a;
-      int grid = (int)std::min<long>(h->n_cu, std::max<long>(1, ((long)B * h->N[1] + 15) / 16));
-      const int nslots = tail.g.Co * ((tail.g.kh + tail.g.stride - 1) / tail.g.stride) * ((tail.g.kw + tail.g.stride - 1) / tail.g.stride);
-      tail.sp = tail_slots_pad(nslots);
-      lz.run(PC_SCORE, [&] { hipLaunchKernelGGL(k_scored_tail, dim3(grid), dim3(TAIL_WAVES * 64), tail_lds_bytes(nslots), st, tail); });
-    } else
-    lz.run(PC_SCORE, [&] { hipLaunchKernelGGL(k_score, dim3(mlp_grid(h, nt / 4)), dim3(WG_MLP), PackScore::FLOATS * 4, st, a); });
-  }
-  for (int k = 0; k < MAXL + 2; ++k) h->last_proj[k] = proj[k];      // inspection (gnnb_mu_projection); one handle per thread
-  if (lz.rc) h->ctl_ws[slot] = nullptr;          // a launch failed: the counters may be left non-zero, the block is re-zeroed on its next use
-  return lz.rc;
+  f.score();
+  for (int k = 0; k < MAXL + 2; ++k) h->last_proj[k] = f.proj[k];      // inspection (gnnb_mu_projection); one handle per thread
+  if (f.lz.rc) h->ctl_ws[slot] = nullptr;          // a launch failed: the counters may be left non-zero, the block is re-zeroed on its next use
+  return f.lz.rc;
 }
 
 // gnnb_forward for HOST inputs -- the reference's own call pattern: one or two subproblems per decision, every tensor a CPU

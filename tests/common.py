@@ -74,3 +74,31 @@ def load_golden(case):
 
 def relu_sizes(batch):
     return [int(np.prod(t.shape[1:])) for t in batch.lower_bounds_all[1:-1]]
+
+
+# Networks other than the three CIFAR models (tests/test_gpu_generic_nets.py): each takes some of the engine's other kernels.
+ARCHS = {
+    # all-dense network: Flatten first, Linear edges only, top layer through k_top
+    "toy_mlp": [("flatten",), ("linear", 3 * 32 * 32, 128), ("relu",), ("linear", 128, 64), ("relu",), ("linear", 64, 10)],
+    # 3x3 stride-1 first conv (8192-node layer), stride-2 second conv, narrow Linear head
+    "toy_conv3": [("conv", 3, 8, 3, 1, 1), ("relu",), ("conv", 8, 8, 4, 2, 1), ("relu",), ("flatten",), ("linear", 8 * 16 * 16, 48),
+                  ("relu",), ("linear", 48, 10)],
+    # last ReLU layer with 200 nodes: too wide for k_top, separate dense / update / property kernels
+    "toy_widehead": [("conv", 3, 8, 4, 2, 1), ("relu",), ("flatten",), ("linear", 8 * 16 * 16, 200), ("relu",), ("linear", 200, 10)],
+    # channel counts the VALU fallback kernels are not compiled for (12, 6): MFMA gather tables only
+    "toy_oddch": [("conv", 3, 12, 3, 1, 1), ("relu",), ("conv", 12, 6, 4, 2, 1), ("relu",), ("flatten",), ("linear", 6 * 16 * 16, 32),
+                  ("relu",), ("linear", 32, 10)],
+    # kernel sizes / strides without a compile-time stencil in the bias-sum pass: 5x5 stride 1 pad 2, 2x2 stride 2 pad 0
+    "toy_k5": [("conv", 3, 8, 5, 1, 2), ("relu",), ("conv", 8, 8, 2, 2, 0), ("relu",), ("flatten",), ("linear", 8 * 16 * 16, 40),
+               ("relu",), ("linear", 40, 10)],
+    # a 32768-node layer under the Linear head: too long for k_top's live-row list (LDS), so its forward edge walks every row
+    "toy_longk": [("conv", 3, 32, 3, 1, 1), ("relu",), ("flatten",), ("linear", 32 * 32 * 32, 72), ("relu",), ("linear", 72, 10)],
+    # a single ReLU layer (L = 1)
+    "toy_single": [("conv", 3, 8, 4, 2, 1), ("relu",), ("flatten",), ("linear", 8 * 16 * 16, 10)],
+}
+
+
+def register_toy_archs():
+    """Register ARCHS with nets (seeded random weights; the seeds are fixed by their order)."""
+    for i, (name, spec) in enumerate(ARCHS.items()):
+        nets.register_arch(name, spec, seed=100 + i)

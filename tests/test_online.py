@@ -163,12 +163,11 @@ def test_online_graph_choice_surface():
 def test_hip_step_on_other_networks(name, T):
     """Linear first layer (dense edges and their adjoints everywhere), 3x3 stride-1 / 5x5 / 2x2 convolutions, odd channel
     counts, a single ReLU layer, T = 1 and 3: gradient, loss and Adam step against the autograd oracle."""
-    from gnn_branching_amd import nets, synth
+    from gnn_branching_amd import synth
     from gnn_branching_amd.engine import ScorerEngine
     from oracle.online_oracle import OnlineOracle
-    from tests.test_gpu_generic_nets import ARCHS
-    for i, (n, spec) in enumerate(ARCHS.items()):
-        nets.register_arch(n, spec, seed=100 + i)
+    from tests.common import register_toy_archs
+    register_toy_archs()
     batch = synth.make_batch(name, 2, seed=11, props=[(3, 5), (1, 7)])
     state = state_of("random")
     kws = [int(batch.masks[b].nonzero().view(-1)[-2]) for b in range(2)]
