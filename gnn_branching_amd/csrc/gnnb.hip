@@ -393,6 +393,7 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   HIPCHK(hipFuncSetAttribute((const void*)k_top<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_top<2>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_top<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)k_babsr, hipFuncAttributeMaxDynamicSharedMemorySize, BABSR_LDS_MAX));
   *out = h;
   return GNNB_OK;
 }
@@ -1721,7 +1722,14 @@ extern "C" int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const*
     }
   }
   a.maxN = maxN;
-  hipLaunchKernelGGL(k_babsr, dim3(B), dim3(256), (size_t)2 * maxN * sizeof(float), (hipStream_t)stream, a);
+  const size_t lds = (size_t)2 * maxN * sizeof(float);
+  if (lds > BABSR_LDS_MAX) {
+    int wide = 1;
+    for (int k = 2; k <= L; ++k) if (h->N[k] > h->N[wide]) wide = k;
+    return fail(GNNB_E_INVALID, "gnnb_babsr: ReLU layer %d of %d nodes needs %zu bytes of LDS for the ratio buffers (%d at most)", wide, maxN, lds,
+                BABSR_LDS_MAX);
+  }
+  hipLaunchKernelGGL(k_babsr, dim3(B), dim3(256), lds, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GNNB_E_HIP, "launch of k_babsr failed: %s", hipGetErrorString(e));
   return GNNB_OK;

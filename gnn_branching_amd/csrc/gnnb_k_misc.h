@@ -204,6 +204,9 @@ struct BabsrArgs {
   int maxN;
 };
 
+// the two ratio buffers of the widest ReLU layer: 160 KiB (20480 nodes) at most, set at init; gnnb_babsr refuses wider networks
+#define BABSR_LDS_MAX (160 * 1024)
+
 __global__ __launch_bounds__(256) void k_babsr(BabsrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* cur = lds;
@@ -223,13 +226,15 @@ __global__ __launch_bounds__(256) void k_babsr(BabsrArgs a) {
       const float slope = upper_temp / (upper_temp - lower_temp);
       const float intercept = -1.0f * lower_temp * slope;
       const float rt = cur[n];
-      const float icand = fminf(rt, 0.0f) * intercept;                               // :84-85
+      // torch.clamp(ratio, max=0) and torch.max(bias_1, bias_2) pass a NaN through (a 0/0 slope above reaches this node
+      // through the ratio); fminf / fmaxf would drop it
+      const float icand = (rt > 0.0f ? 0.0f : rt) * intercept;                       // :84-85
       const float m = a.mask[(long)b * a.R + a.off[k] + n];
       const float bb = a.bias[k][n / a.hw[k]];
       const float b1 = bb * (rt * (slope - 1.0f));                                   // :92-93
       const float rt2 = rt * slope;                                                  // :94
       const float b2 = bb * rt2;                                                     // :95
-      a.scores[(long)b * a.R + a.off[k] + n] = fabsf(fmaxf(b1, b2) + icand) * m;     // :96-103
+      a.scores[(long)b * a.R + a.off[k] + n] = fabsf(__builtin_elementwise_maximum(b1, b2) + icand) * m;   // :96-103
       a.icp[(long)b * a.R + a.off[k] + n] = icand * m;                               // :86
       cur[n] = rt2;
     }

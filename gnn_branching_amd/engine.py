@@ -743,10 +743,13 @@ class ScorerEngine:
 
     # ---- Wong-Kolter intermediate bounds (lp_producer.LayerGraphLP.kw_bounds for a batch) ------------------------------------
     def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False):
-        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) or (B, N_0) input boxes (fp64 on the device); prop_layers:
-        B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of
-        graph layers 1..L+1 (fp64); split_layers: (B,) ReLU layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
+        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) input boxes (fp64 on the device), or (B, N_0) when the first
+        layer is not a Conv2d (the input shape is read from the box); prop_layers: B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat
+        ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of graph layers 1..L+1 (fp64); split_layers: (B,) ReLU
+        layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
         B = int(x_lo.shape[0])
+        if fixed_layers and type(fixed_layers[0]) is nn.Conv2d and (x_lo.dim() != 4 or x_hi.dim() != 4):
+            raise ValueError(f"the first layer is a Conv2d: x_lo / x_hi must be (B, C, H, W) boxes, got {tuple(x_lo.shape)} / {tuple(x_hi.shape)}")
         self.bind(fixed_layers, tuple(x_lo.shape[1:]))
         if len(prop_layers) != B:
             raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")

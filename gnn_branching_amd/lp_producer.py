@@ -82,6 +82,12 @@ class Subproblem:
         return [self.lower_all[i].unsqueeze(0) for i in idx], [self.upper_all[i].unsqueeze(0) for i in idx]
 
 
+def _check_parent(parent, split_layer):
+    """A child's parent bounds always come with the ReLU layer it was split on (the layers up to it are the parent's)."""
+    if parent is not None and split_layer is None:
+        raise ValueError("parent bounds given without split_layer")
+
+
 class LayerGraphLP:
     """LP relaxation of ``layers`` (net.layers with the folded Linear(., 1) property layer last) over an input box."""
 
@@ -217,8 +223,9 @@ class LayerGraphLP:
         incremental form of update_kw_bounds (dual_network_linear_approximation.py:296-451) -- every bound up to and including
         that layer's pre-activation is the parent's (only the split node is clamped, :311-318), later layers are recomputed and
         intersected with the parent's bounds (:398-399).  Returns (lbs, ubs) like ``interval_bounds``."""
+        _check_parent(parent, split_layer)
         lbs, ubs = [self.input_lb.clone()], [self.input_ub.clone()]
-        keep_upto = self.pre_relu_indices[split_layer] if (parent is not None and split_layer is not None) else -1
+        keep_upto = self.pre_relu_indices[split_layer] if parent is not None else -1
         r = 0
         first_affine = True
         for q, l in enumerate(self.layers):
@@ -251,6 +258,8 @@ class LayerGraphLP:
         """``kw_bounds`` for several domains in ONE device call (``gnnb_kw_bounds``).  ``items``: [(mask, parent, split_layer), ...] with
         ``parent`` None or (lbs, ubs) as ``kw_bounds`` takes it.  Returns [(lbs, ubs), ...] laid out as ``kw_bounds`` returns them (host
         fp64; post-ReLU entries clamped, flattened entries reshaped)."""
+        for _, p, s in items:
+            _check_parent(p, s)
         if self.engine is None:
             from .engine import ScorerEngine
             self.engine = ScorerEngine(None)
@@ -260,11 +269,11 @@ class LayerGraphLP:
         x_hi = self.input_ub[None].expand((B,) + self.shapes[0])
         masks = torch.stack([torch.cat([m.reshape(-1) for m in mask]) for mask, _, _ in items]).to(torch.int8)
         parents = split = None
-        if any(p is not None and s is not None for _, p, s in items):
+        if any(p is not None for _, p, _ in items):
             zero = [torch.zeros(int(np.prod(self.shapes[i])), dtype=torch.float64) for i in gidx]
-            parents = tuple([torch.stack([(p[side][i].reshape(-1) if (p is not None and s is not None) else z)
+            parents = tuple([torch.stack([(p[side][i].reshape(-1) if p is not None else z)
                                           for _, p, s in items]) for i, z in zip(gidx, zero)] for side in (0, 1))
-            split = torch.tensor([s if (p is not None and s is not None) else -1 for _, p, s in items], dtype=torch.int32)
+            split = torch.tensor([s if p is not None else -1 for _, p, s in items], dtype=torch.int32)
         fixed, prop = self.layers[:-1], [self.layers[-1]] * B
         res = eng.kw_bounds(fixed, prop, x_lo, x_hi, masks, parents, split)
         glb = [t.cpu() for t in res.lb]
@@ -287,6 +296,7 @@ class LayerGraphLP:
         return out
 
     def bounds(self, mask, parent=None, split_layer=None):
+        _check_parent(parent, split_layer)
         if self.bound_mode == "interval":
             return self.interval_bounds(mask)
         if self.bound_mode == "kw_device":

@@ -150,7 +150,9 @@ int gnnb_scatter_amb_records(gnnb_t* h, const void* dev_image, int B, float* con
  * plnn/kw_score_conv.py choose_node_conv :41-113, called at plnn/relu_conv_gnnkwthreshold.py:157).  lb/ub: HOST tables of
  * n_graph DEVICE pointers laid out like struct gnnb_batch.lb, .ub -- only the ReLU layers 1..L are read; prop_w (B, N_L); mask (B, R) 1.0 where the
  * BaB mask is -1.  Outputs, device (B, R): scores = `score` (:103), intercepts = `intercept_tb` (:86), both already
- * multiplied by the mask.  The decision rule (:115-156, with its counters and random fall-back) stays on the host. */
+ * multiplied by the mask; a 0/0 slope's NaN propagates as in torch.  The decision rule (:115-156, with its counters and random
+ * fall-back) stays on the host.  GNNB_E_INVALID before any launch when the widest ReLU layer has more than 20480 nodes (its two fp32
+ * ratio buffers would need more than 160 KiB of LDS). */
 int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const* ub, int n_graph, const float* prop_w,
                const float* mask, int B, float* scores, float* intercepts, void* stream);
 

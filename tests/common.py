@@ -102,3 +102,42 @@ def register_toy_archs():
     """Register ARCHS with nets (seeded random weights; the seeds are fixed by their order)."""
     for i, (name, spec) in enumerate(ARCHS.items()):
         nets.register_arch(name, spec, seed=100 + i)
+
+
+def _mlp_deep8():
+    spec, n = [("flatten",)], 3 * 8 * 8
+    for _ in range(8):
+        spec += [("linear", n, 32), ("relu",)]
+        n = 32
+    return spec + [("linear", 32, 10)]
+
+
+# Geometries for the Wong-Kolter bounds and BaBSR kernels (tests/test_gpu_kw_geometry.py, tests/test_gpu_babsr_geometry.py):
+# name -> (input shape, spec).  Channel counts in {3, 8, 16, 32} (bind accepts them without MFMA gather tables); the widest ReLU
+# layer stays at or below the 4096 nodes of the Wong-Kolter LDS limit except in kwg_over.
+KW_ARCHS = {
+    # Linear first layer: the input is a flat layer
+    "kwg_mlp": ((3, 8, 8), [("flatten",), ("linear", 192, 64), ("relu",), ("linear", 64, 48), ("relu",), ("linear", 48, 10)]),
+    # stride-1 support boxes that grow through two layers; L = 4
+    "kwg_s1": ((3, 16, 16), [("conv", 3, 8, 3, 1, 1), ("relu",), ("conv", 8, 8, 3, 1, 1), ("relu",), ("conv", 8, 16, 4, 2, 1), ("relu",),
+                             ("flatten",), ("linear", 1024, 32), ("relu",), ("linear", 32, 10)]),
+    # non-square input, 5x5 kernel, pad 0
+    "kwg_rect": ((3, 12, 20), [("conv", 3, 8, 5, 1, 2), ("relu",), ("conv", 8, 16, 2, 2, 0), ("relu",), ("flatten",), ("linear", 960, 24),
+                               ("relu",), ("linear", 24, 10)]),
+    # stride larger than the kernel (pixels no window reads), 1x1 conv (a one-pixel support box)
+    "kwg_gap": ((3, 20, 14), [("conv", 3, 8, 2, 3, 0), ("relu",), ("conv", 8, 16, 1, 1, 0), ("relu",), ("flatten",), ("linear", 560, 16),
+                              ("relu",), ("linear", 16, 10)]),
+    # L = 1: graph layer 1 and the property node only
+    "kwg_single": ((3, 16, 16), [("conv", 3, 8, 4, 2, 1), ("relu",), ("flatten",), ("linear", 512, 10)]),
+    # L = 8 = MAXL, the deepest network bind accepts
+    "kwg_deep8": ((3, 8, 8), _mlp_deep8()),
+    # a 4096-node ReLU layer: exactly the Wong-Kolter LDS limit (2 x 4096 doubles = 64 KiB) / one node past it
+    "kwg_cap": ((3, 8, 8), [("flatten",), ("linear", 192, 4096), ("relu",), ("linear", 4096, 16), ("relu",), ("linear", 16, 10)]),
+    "kwg_over": ((3, 8, 8), [("flatten",), ("linear", 192, 4097), ("relu",), ("linear", 4097, 16), ("relu",), ("linear", 16, 10)]),
+}
+
+
+def register_kw_archs():
+    """Register KW_ARCHS with nets (seeded random weights; the seeds are fixed by their order)."""
+    for i, (name, (_, spec)) in enumerate(KW_ARCHS.items()):
+        nets.register_arch(name, spec, seed=200 + i)

@@ -38,3 +38,20 @@ def test_kw_device_is_a_bounds_mode():
         assert lp_producer.LayerGraphLP(layers, x - 0.01, x + 0.01, bounds=mode).bound_mode == mode
     with pytest.raises(ValueError):
         lp_producer.LayerGraphLP(layers, x - 0.01, x + 0.01, bounds="kw_gpu")
+
+
+@pytest.mark.parametrize("mode", ["kw", "kw_device"])
+def test_parent_without_split_layer_is_refused(mode):
+    """A parent always comes with its split: kw_bounds would intersect with it at every layer, kw_device_bounds used to drop it."""
+    layers = nets.load_verified_net("cifar_base_kw", 3, 5)
+    x = torch.zeros(3, 32, 32)
+    lp = lp_producer.LayerGraphLP(layers, x - 0.01, x + 0.01, bounds=mode)
+    mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
+    parent = lp.interval_bounds(mask)
+    with pytest.raises(ValueError, match="split_layer"):
+        lp.bounds(mask, parent, None)
+    with pytest.raises(ValueError, match="split_layer"):
+        lp.kw_bounds(mask, parent, None)
+    with pytest.raises(ValueError, match="split_layer"):
+        lp.kw_device_bounds([(mask, None, None), (mask, parent, None)])
+    assert lp.engine is None                         # refused before a device is touched
