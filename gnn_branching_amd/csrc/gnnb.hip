@@ -1894,6 +1894,19 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     return fail(GNNB_E_INVALID, "gnnb_online_step: batch does not match the bound network");
   for (int b = 0; b < B; ++b)
     if (kw_index[b] < 0 || kw_index[b] >= R) return fail(GNNB_E_INVALID, "gnnb_online_step: kw_index[%d] = %d outside [0, %d)", b, kw_index[b], R);
+  // k_tconv lists the valid taps of a destination node in LDS arrays of TCONV_MAXTAPS entries.  Both directions of every conv edge
+  // run in a step (A and A^T, forward or as each other's adjoint): a node of A reads at most min(kh, H_in) min(kw, W_in) C_in
+  // taps, a node of A^T at most min(ceil(kh / s), H_out) min(ceil(kw / s), W_out) C_out (the taps with (y + pad - ky) % s == 0).
+  for (int k = 1; k <= L; ++k) {
+    const Edge& e = h->edges[k];
+    if (e.kind != 0) continue;
+    auto lim = [](int a, int b) { return a < b ? a : b; };
+    const long fwd = (long)lim(e.kh, e.h_in) * lim(e.kw, e.w_in) * e.c_in;
+    const long bwd = (long)lim((e.kh + e.stride - 1) / e.stride, e.h_out) * lim((e.kw + e.stride - 1) / e.stride, e.w_out) * e.c_out;
+    if (fwd > TCONV_MAXTAPS || bwd > TCONV_MAXTAPS)
+      return fail(GNNB_E_INVALID, "gnnb_online_step: the convolution into ReLU layer %d (%dx%d stride %d, %d -> %d channels) gives a node up to %ld taps, "
+                  "the training kernels hold %d", k, e.kh, e.kw, e.stride, e.c_in, e.c_out, fwd > bwd ? fwd : bwd, TCONV_MAXTAPS);
+  }
   Trainer& t = *h->trainer;
   hipStream_t st = (hipStream_t)stream;
   t.st = st;
@@ -2107,7 +2120,7 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     t.step += 1;
     const double b1 = 0.9, b2 = 0.999;
     const double bc1 = 1.0 - std::pow(b1, t.step), bc2 = 1.0 - std::pow(b2, t.step);
-    TAdam a{t.d_w, t.d_g, t.d_m, t.d_v, (int)blob_floats(), (float)(t.lr / bc1), t.wd, (float)b1, (float)b2, 1e-8f, (float)std::sqrt(bc2)};
+    TAdam a{t.d_w, t.d_g, t.d_m, t.d_v, (int)blob_floats(), (float)(t.lr / bc1), t.wd, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-8f, (float)std::sqrt(bc2)};
     hipLaunchKernelGGL(k_tadam, dim3((unsigned)((blob_floats() + 255) / 256)), dim3(256), 0, st, a);
     std::vector<float> nw(blob_floats());
     HIPCHK(hipMemcpyAsync(nw.data(), t.d_w, nw.size() * 4, hipMemcpyDeviceToHost, st));

@@ -673,7 +673,8 @@ __global__ __launch_bounds__(64) void k_tscore_bwd_w(TScoreMulti m, int nlayers)
   }
 }
 
-// loss_b = max_j s_b[j] - s_b[kw_b] + improvement_b (graph_score_online.py:73); ds = d loss / d scores
+// loss_b = max_j s_b[j] - s_b[kw_b] + improvement_b (graph_score_online.py:73); ds = d loss / d scores.
+// A sample without a finite score (nothing `v > best` holds for) gets loss = NaN, sel = {-1, -1} and no ds entry.
 struct TLoss { const float* scores; float* ds; const int* kw; const float* imp; float* loss; int R; int* sel; };
 __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
   __shared__ float sv[256];
@@ -693,6 +694,11 @@ __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
   }
   if (tid == 0) {
     const int am = si[0], kw = a.kw[b];
+    if (am >= a.R) {                     // nothing to take a maximum of (empty mask: every score -inf): no loss, no gradient from this sample
+      a.loss[b] = NAN;
+      a.sel[2 * b] = -1; a.sel[2 * b + 1] = -1;      // (k_tscore_bwd_w skips indices outside a layer)
+      return;
+    }
     a.loss[b] = sv[0] - s[kw] + a.imp[b];
     a.ds[(long)b * a.R + am] += 1.0f;
     a.ds[(long)b * a.R + kw] -= 1.0f;
@@ -701,13 +707,15 @@ __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
 }
 
 // torch.optim.Adam (not AdamW): g += wd p; m, v moments; p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-struct TAdam { float *p, *g, *m, *v; int n; float step_size, wd, b1, b2, eps, bc2s; };   // step_size = lr / (1 - b1^t), bc2s = sqrt(1 - b2^t)
+// omb1 = 1 - b1 and omb2 = 1 - b2 come from the host, rounded once from double as torch does: 1.0f - 0.999f is 1.3e-5 off 0.001, which
+// scaled the second moment against its bias correction and every step by 6e-6 (tests/test_online_gradients.py, lr = 1e-2).
+struct TAdam { float *p, *g, *m, *v; int n; float step_size, wd, omb1, b2, omb2, eps, bc2s; };   // step_size = lr / (1 - b1^t), bc2s = sqrt(1 - b2^t)
 __global__ void k_tadam(TAdam a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
   const float g = a.g[i] + a.wd * a.p[i];
-  const float m = a.m[i] + (1.0f - a.b1) * (g - a.m[i]);        // exp_avg.lerp_(grad, 1 - beta1)
-  const float v = a.b2 * a.v[i] + (1.0f - a.b2) * g * g;
+  const float m = a.m[i] + a.omb1 * (g - a.m[i]);               // exp_avg.lerp_(grad, 1 - beta1)
+  const float v = a.b2 * a.v[i] + a.omb2 * g * g;
   a.m[i] = m; a.v[i] = v;
   const float denom = sqrtf(v) / a.bc2s + a.eps;
   a.p[i] = a.p[i] - a.step_size * (m / denom);

@@ -206,9 +206,14 @@ int gnnb_online_create(gnnb_t* h, float lr, float weight_decay);
  * losses):  loss_b = max_j scores_b[j] - scores_b[kw_b] + improvement_b;  backward through GraphNet.forward;  one Adam step;
  * the scorer (gnnb_forward) uses the new parameters from the next call on.
  * in: the batch as for gnnb_forward (device pointers).  kw_index: HOST (B), the KW decision as a flat index into the R ReLU
- * nodes (trans_len[lay-1] + idx, :63-67) -- must be an undecided node of the mask.  improvement: HOST (B).  loss: HOST (B)
+ * nodes (trans_len[lay-1] + idx, :63-67) -- must be an undecided node of the mask.  A sample whose mask is empty (no score
+ * to take the maximum of) gets loss = NaN and contributes nothing to the gradient; the other samples of the batch are not
+ * affected.  improvement: HOST (B).  loss: HOST (B)
  * or NULL.  scores_padded: DEVICE (B, R) or NULL, the scores of the training-form forward before the update.  apply = 0:
  * compute the gradient only (read it with gnnb_online_grad), parameters and optimizer state untouched.
+ * Limit: a convolution of the bound network may give one node at most 512 taps in either direction
+ * (min(kh, H_in) min(kw, W_in) C_in forward, ceil(kh / stride) ceil(kw / stride) C_out transposed; 4x4 stride 2 over 32
+ * channels: 512 / 128).  A network beyond it is refused with GNNB_E_INVALID before anything is launched; the handle stays usable.
  * Synchronises `stream` before returning. */
 int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_index, const float* improvement,
                      float* loss, float* scores_padded, int apply, void* stream);

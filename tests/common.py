@@ -104,6 +104,24 @@ def register_toy_archs():
         nets.register_arch(name, spec, seed=100 + i)
 
 
+# Networks for the limits of the online-learning step (tests/test_online_gradients.py).  A dict of their own, registered with seeds of
+# their own: ARCHS parametrises other test files, and its seeds follow its order.
+ONLINE_ARCHS = {
+    # 4x4 stride-1 conv over 32 -> 32 channels: an interior node lists 4 * 4 * 32 = 512 taps in either direction, exactly what
+    # the training conv kernel's tap lists hold (TCONV_MAXTAPS)
+    "toy_taps512": [("conv", 3, 32, 4, 4, 0), ("relu",), ("conv", 32, 32, 4, 1, 1), ("relu",), ("flatten",), ("linear", 32 * 7 * 7, 24),
+                    ("relu",), ("linear", 24, 10)],
+    # 5x5 stride-1 conv over 32 channels: 800 taps, past the limit -- the online step refuses it
+    "toy_taps800": [("conv", 3, 32, 4, 4, 0), ("relu",), ("conv", 32, 8, 5, 1, 2), ("relu",), ("flatten",), ("linear", 8 * 8 * 8, 24),
+                    ("relu",), ("linear", 24, 10)],
+}
+
+
+def register_online_archs():
+    for i, (name, spec) in enumerate(ONLINE_ARCHS.items()):
+        nets.register_arch(name, spec, seed=300 + i)
+
+
 def _mlp_deep8():
     spec, n = [("flatten",)], 3 * 8 * 8
     for _ in range(8):
