@@ -207,6 +207,7 @@ struct gnnb_handle {
                                 // gnnb_forward itself keeps this state on its stack
   std::vector<DevGather> gf, gb;   // gf[k]: edge k forward (dst = layer k); gb[k]: edge k transposed (dst = layer k-1)
   bool bound = false;
+  int zero_tap[3] = {0, 0, 0};   // {k, y, x}: inner conv edge k leaves pixel (y, x) of layer k-1 without a tap (k = 0: none); set by gnnb_bind_network
   std::vector<Edge> edges;       // edges[k], k = 1..L (edges[0] unused)
   std::vector<DevEdge> dev;
   std::vector<double*> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for gnnb_kw_bounds, k = 1..L (made by bind)
@@ -475,6 +476,42 @@ extern "C" int gnnb_destroy(gnnb_t* h) {
 
 static bool conv_channels_ok(int c) { return c == 3 || c == 8 || c == 16 || c == 32; }
 
+// The transposed aggregate of an inner conv edge (graph layers k >= 2) is divided by the number of kernel taps that touch a pixel
+// (the reference's `freq`, graph_conv.py:306-312).  A stride larger than the kernel leaves pixels of layer k-1 that no window
+// reads: their count is 0 and the reference computes 0/0 and stops.  The scoring entry points refuse such a network instead of
+// letting the answer depend on which kernel the launch plan picks for the edge.  Returns the first such layer k (0: none) and
+// one of its unread pixels.  Edge 1 is not normalised (:360-376) and may have such pixels.
+static int zero_tap_layer(const gnnb_t* h, int* y0, int* x0) {
+  const int L = (int)h->N.size() - 2;
+  for (int k = 2; k <= L; ++k) {
+    const Edge& e = h->edges[k];
+    if (e.kind != 0) continue;
+    auto unread = [&](int n_in, int n_out, int ksz) {      // first position of one axis that no window covers, -1: none
+      for (int t = 0; t < n_in; ++t) {
+        int taps = 0;
+        for (int o = 0; o < n_out; ++o) taps += (t >= o * e.stride - e.pad && t < o * e.stride - e.pad + ksz);
+        if (taps == 0) return t;
+      }
+      return -1;
+    };
+    const int y = unread(e.h_in, e.h_out, e.kh), x = unread(e.w_in, e.w_out, e.kw);
+    if (y >= 0 || x >= 0) {
+      *y0 = y >= 0 ? y : 0;
+      *x0 = x >= 0 ? x : 0;
+      return k;
+    }
+  }
+  return 0;
+}
+static int refuse_zero_taps(const gnnb_t* h, const char* who) {
+  const int k = h->zero_tap[0], y = h->zero_tap[1], x = h->zero_tap[2];
+  if (!k) return GNNB_OK;
+  const Edge& e = h->edges[k];
+  return fail(GNNB_E_INVALID, "%s: the convolution into ReLU layer %d (%dx%d stride %d pad %d on %dx%d) reads no tap of pixel (%d, %d) of layer %d: "
+              "the transposed aggregate is divided by a tap count of 0 there (0/0 in the reference)", who, k, e.kh, e.kw, e.stride, e.pad,
+              e.h_in, e.w_in, y, x, k - 1);
+}
+
 extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int c0, int h0, int w0) {
   if (!h || !L || n < 2) return fail(GNNB_E_INVALID, "gnnb_bind_network: bad arguments");
   free_network(h);
@@ -658,6 +695,7 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
       return fail(GNNB_E_INVALID, "conv edge %d (%d -> %d channels): no MFMA gather tables and the fallback kernels only cover channel counts "
                   "{3, 8, 16, 32}", k, e.c_in, e.c_out);
   }
+  h->zero_tap[0] = zero_tap_layer(h, &h->zero_tap[1], &h->zero_tap[2]);
   h->bound = true;
   return GNNB_OK;
 }
@@ -1422,6 +1460,7 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     if (!in->primal[m]) return fail(GNNB_E_INVALID, "gnnb_forward: null primal pointer %d", m);
   if (!in->x_lp || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "gnnb_forward: null input pointer");
   if ((long)B * h->N[0] * 64 >= (1L << 40)) return fail(GNNB_E_INVALID, "gnnb_forward: batch too large");
+  if (int rc = refuse_zero_taps(h, "gnnb_forward")) return rc;
   const WsLayout w = ws_layout(h, B);
   if (workspace_bytes < w.total * sizeof(float))
     return fail(GNNB_E_NOMEM, "gnnb_forward: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
@@ -1487,6 +1526,7 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
   const int K = (int)h->N.size() - 1, L = K - 1, R = h->R;
   if (B < 1 || in->n_graph != K + 1 || in->n_relu != L || in->n_primal != h->n_fixed + 1)
     return fail(GNNB_E_INVALID, "gnnb_forward_host: batch does not match the bound network");
+  if (int rc = refuse_zero_taps(h, "gnnb_forward_host")) return rc;
   hipStream_t st = (hipStream_t)stream;
   // ---- slots: (host pointer, floats); primals the forward never reads are not transferred
   struct Slot { const float* src; size_t n, off; };
@@ -1894,6 +1934,7 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     return fail(GNNB_E_INVALID, "gnnb_online_step: batch does not match the bound network");
   for (int b = 0; b < B; ++b)
     if (kw_index[b] < 0 || kw_index[b] >= R) return fail(GNNB_E_INVALID, "gnnb_online_step: kw_index[%d] = %d outside [0, %d)", b, kw_index[b], R);
+  if (int rc = refuse_zero_taps(h, "gnnb_online_step")) return rc;
   // k_tconv lists the valid taps of a destination node in LDS arrays of TCONV_MAXTAPS entries.  Both directions of every conv edge
   // run in a step (A and A^T, forward or as each other's adjoint): a node of A reads at most min(kh, H_in) min(kw, W_in) C_in
   // taps, a node of A^T at most min(ceil(kh / s), H_out) min(ceil(kw / s), W_out) C_out (the taps with (y + pad - ky) % s == 0).

@@ -353,7 +353,7 @@ __device__ __forceinline__ void gather_scored_node(const GSArgs& a, int gc, int 
     }
   }
   if (a.normalise) {
-    const float f = (float)(freq > 0 ? freq : 1);
+    const float f = (float)(freq > 0 ? freq : 1);      // (no reachable zero: gnnb_forward refuses a network with a zero-tap pixel)
     acc = acc / f;
     ssum = ssum / f;
   }
@@ -528,7 +528,7 @@ __device__ __forceinline__ void gather_scored_multi(const GSArgs& a, const int (
     }
   }
   if (a.normalise) {
-    const float f = (float)(myf > 0 ? myf : 1);
+    const float f = (float)(myf > 0 ? myf : 1);        // (no reachable zero: gnnb_forward refuses a network with a zero-tap pixel)
 #pragma unroll
     for (int k = 0; k < CPL; ++k) acc[k] = acc[k] / f;
     ssum = ssum / f;

@@ -82,13 +82,15 @@ def _interval(layer, lb, ub):
     raise NotImplementedError(type(layer))
 
 
-def make_batch(net_name, B, seed=0, eps=0.02, props=None, dual_density=0.3):
+def make_batch(net_name, B, seed=0, eps=0.02, props=None, dual_density=0.3, input_shape=None):
     """Seeded synthetic batch of B subproblems on the named verified network.
 
     ``props``: list of (gt, cls) per sample (or None -> (3, 5) for all): a
     batch may mix properties (reference graph_conv.py:196-197 indexes
-    ``layers['prop_layers'][i]`` by batch element).
+    ``layers['prop_layers'][i]`` by batch element).  ``input_shape``: (C, H, W)
+    of the network's input, None -> INPUT_SHAPE.
     """
+    input_shape = INPUT_SHAPE if input_shape is None else tuple(input_shape)
     rng = np.random.RandomState(seed)
     base = build_net(net_name)
     if props is None:
@@ -101,13 +103,13 @@ def make_batch(net_name, B, seed=0, eps=0.02, props=None, dual_density=0.3):
             cache[pr] = fold_property(base, *pr)[-1]
         prop_layers.append(cache[pr])
     fixed = base[:-1]
-    shapes, _ = graph_layout(fixed + [prop_layers[0]])
+    shapes, _ = graph_layout(fixed + [prop_layers[0]], input_shape)
 
     def t(a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
 
-    x = t(rng.standard_normal((B,) + INPUT_SHAPE))
-    x_lp = x + eps * t(rng.uniform(-1, 1, (B,) + INPUT_SHAPE))
+    x = t(rng.standard_normal((B,) + input_shape))
+    x_lp = x + eps * t(rng.uniform(-1, 1, (B,) + input_shape))
     with torch.no_grad():
         lb, ub = x - eps, x + eps
         lbs, ubs = [lb], [ub]

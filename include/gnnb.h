@@ -113,7 +113,12 @@ size_t gnnb_workspace_bytes(const gnnb_t* h, int B);
  * has no ambiguous ReLU.  status: device int32[1], bit 0 set if an embedding was NaN (the reference
  * enters pdb, graph_conv.py:184-186, :339-341), bit 1 if a wait inside a kernel (k_gather_update_q's LDS ring; k_top's workgroup
  * split waiting for its partner workgroups -- option "top_split" = 1 turns that split off) hit its iteration cap (never in a correct run on a
- * GPU the caller does not share with long-running kernels; the results are then invalid).  stream: hipStream_t (NULL = default). */
+ * GPU the caller does not share with long-running kernels; the results are then invalid).  stream: hipStream_t (NULL = default).
+ * Limit: every pixel below an inner convolution (the edge into ReLU layer k >= 2) must be read by at least one of its windows.  A stride
+ * larger than the kernel leaves pixels with a tap count of 0, by which the reference divides the transposed aggregate
+ * (graph_conv.py:306-312: 0/0, it stops).  gnnb_forward, gnnb_forward_host and gnnb_online_step refuse such a network with
+ * GNNB_E_INVALID before anything is launched, naming the layer; the handle stays usable.  The first convolution is not normalised
+ * and may skip pixels; gnnb_bind_network, gnnb_kw_bounds and gnnb_babsr divide by no tap count and accept the network. */
 int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* scores_padded, int32_t* decisions,
                  int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -159,3 +159,42 @@ def register_kw_archs():
     """Register KW_ARCHS with nets (seeded random weights; the seeds are fixed by their order)."""
     for i, (name, (_, spec)) in enumerate(KW_ARCHS.items()):
         nets.register_arch(name, spec, seed=200 + i)
+
+
+# Input shapes and conv geometries for the forward scorer (tests/test_gpu_forward_geometry.py): name -> (input shape, spec).  A dict of
+# its own, registered with seeds of its own: ARCHS' seeds follow its order and parametrise golden files.  What each one covers:
+FWD_ARCHS = {
+    # H != W, 5x5, pad 0, a tile map with NBY = 6, NBX = 10
+    "fwg_rect": KW_ARCHS["kwg_rect"],
+    # stride > kernel on edge 1 (not normalised, so legal): input pixels no window reads; edge 1 has no transposed tables, so the
+    # VALU k_convT_bwd + k_input_update run behind a conv; 1x1 windows
+    "fwg_gap": KW_ARCHS["kwg_gap"],
+    # L = 4, odd extents (17x5, 9x3), widths below every tile width, origin -1 on the transposed 4/2/1
+    "fwg_tall": ((3, 34, 10), [("conv", 3, 8, 4, 2, 1), ("relu",), ("conv", 8, 8, 3, 1, 1), ("relu",), ("conv", 8, 16, 3, 2, 1), ("relu",),
+                               ("flatten",), ("linear", 432, 32), ("relu",), ("linear", 32, 10)]),
+    # kernel larger than the image (2x2, then 1x1), one mostly-masked tile per sample, a conv as the last edge
+    "fwg_tiny": ((3, 4, 4), [("conv", 3, 8, 4, 2, 1), ("relu",), ("conv", 8, 8, 4, 2, 1), ("relu",), ("flatten",), ("linear", 8, 10)]),
+    # inner edge with forward MFMA tables and NO transposed tables: the normalised VALU transposed conv, tap counts 16..49
+    "fwg_k7": ((3, 8, 8), [("conv", 3, 8, 3, 1, 1), ("relu",), ("conv", 8, 8, 7, 1, 3), ("relu",), ("flatten",), ("linear", 512, 20),
+                           ("relu",), ("linear", 20, 10)]),
+    # inner edge with no tables in either direction, between MFMA neighbours
+    "fwg_valu": ((3, 6, 6), [("conv", 3, 16, 3, 1, 1), ("relu",), ("conv", 16, 32, 5, 1, 2), ("relu",), ("flatten",), ("linear", 1152, 24),
+                             ("relu",), ("linear", 24, 10)]),
+    # L = 8 = MAXL, Linear first layer
+    "fwg_deep8": KW_ARCHS["kwg_deep8"],
+    # a flat input that is not 3072 wide through k_embed and the dense kernels
+    "fwg_mlp": KW_ARCHS["kwg_mlp"],
+    # L = 1 at 16x16
+    "fwg_single": KW_ARCHS["kwg_single"],
+}
+# An inner conv with stride > kernel: pixels of layer 1 that no window of edge 2 reads have a tap count of 0, by which the reference
+# divides (0/0).  The scoring entry points refuse it; bind, kw_bounds and babsr accept it.
+ZERO_TAP_ARCH = ("fwg_zerotap", (3, 18, 12), [("conv", 3, 8, 4, 2, 1), ("relu",), ("conv", 8, 8, 2, 3, 1), ("relu",), ("flatten",),
+                                              ("linear", 96, 16), ("relu",), ("linear", 16, 10)])
+
+
+def register_fwd_archs():
+    """Register FWD_ARCHS (seeds 500 + i, fixed by their order) and the zero-tap network (seed 599) with nets."""
+    for i, (name, (_, spec)) in enumerate(FWD_ARCHS.items()):
+        nets.register_arch(name, spec, seed=500 + i)
+    nets.register_arch(ZERO_TAP_ARCH[0], ZERO_TAP_ARCH[2], seed=599)

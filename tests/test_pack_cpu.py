@@ -352,7 +352,8 @@ GEOM = ["N", "C", "H", "W", "CT", "PY", "PX", "ay", "ax", "NBY", "NBX", "NCG", "
         "ystep", "ybase", "xstep", "xbase", "WY", "WX", "normalise", "n_cmat", "n_koff", "lanes"]
 
 
-def build_gather(packlib, w, h_in, w_in, stride, pad, direction, normalise, allow16=0):
+def build_gather(packlib, w, h_in, w_in, stride, pad, direction, normalise, allow16=0, may_be_missing=False):
+    """(geometry, tap matrix, offsets, MFMAs per sample) of gnnb_pack.h build_gather; None where it finds no tiling (may_be_missing)."""
     c_out, c_in, kh, kw = w.shape
     packlib.gnnb_pt_gather.restype = C.c_long
     packlib.gnnb_pt_gather.argtypes = [C.c_void_p] + [C.c_int] * 11 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -360,6 +361,8 @@ def build_gather(packlib, w, h_in, w_in, stride, pad, direction, normalise, allo
     geom = np.zeros(27, np.int32)
     cost = packlib.gnnb_pt_gather(w.ctypes.data, c_in, h_in, w_in, c_out, kh, kw, stride, pad, direction, normalise, allow16,
                                   geom.ctypes.data, None, 0, None, 0)
+    if may_be_missing and cost < 0:
+        return None
     assert cost > 0
     g = dict(zip(GEOM, geom.tolist()))
     cmat = np.zeros(g["n_cmat"], np.float32)
@@ -409,33 +412,99 @@ CONVS = [  # (c_in, c_out, k, stride, pad, h_in)  -- every conv of cifar_{base,w
 ]
 
 
-@pytest.mark.parametrize("cfg", CONVS)
-@pytest.mark.parametrize("direction,allow16", [(0, 0), (1, 0), (0, 1)])
-def test_gather_tables_match_torch_conv(packlib, cfg, direction, allow16):
+def check_gather_tables(packlib, cfg, direction, allow16, may_be_missing=False):
+    """The tables of one conv (c_in, c_out, k, stride, pad, h_in, w_in) in one direction, walked as the kernels walk them, against
+    F.conv2d / F.conv_transpose2d.  Returns False where build_gather has no tables for it."""
     import torch
     import torch.nn.functional as F
-    c_in, c_out, k, s, pad, h_in = cfg
+    c_in, c_out, k, s, pad, h_in, w_in = cfg
     rng = np.random.RandomState(c_in * 100 + c_out + direction)
     w = rng.standard_normal((c_out, c_in, k, k)).astype(np.float32)
-    g, cmat, koff, cost = build_gather(packlib, w, h_in, h_in, s, pad, direction, normalise=direction, allow16=allow16)
+    built = build_gather(packlib, w, h_in, w_in, s, pad, direction, normalise=direction, allow16=allow16, may_be_missing=may_be_missing)
+    if built is None:
+        return False
+    g, cmat, koff, cost = built
     assert g["lanes"] in ((16, 32) if allow16 else (32,))
     if allow16:                                      # never worse than the 32-node tiling, usually a third cheaper
-        assert cost <= build_gather(packlib, w, h_in, h_in, s, pad, direction, normalise=direction)[3]
-    h_out = (h_in + 2 * pad - k) // s + 1
+        wide = build_gather(packlib, w, h_in, w_in, s, pad, direction, normalise=direction, may_be_missing=may_be_missing)
+        assert wide is None and g["lanes"] == 16 or cost <= wide[3]      # (a 7x7 window on 8x8 only has 16-node tiles)
+    h_out, w_out = (h_in + 2 * pad - k) // s + 1, (w_in + 2 * pad - k) // s + 1
     p = 4
     if direction == 0:
-        mu = rng.standard_normal((c_in * h_in * h_in, p))
-        x = torch.from_numpy(mu.T.reshape(p, c_in, h_in, h_in))
+        mu = rng.standard_normal((c_in * h_in * w_in, p))
+        x = torch.from_numpy(mu.T.reshape(p, c_in, h_in, w_in))
         want = F.conv2d(x, torch.from_numpy(w).double(), None, s, pad).reshape(p, -1).T.numpy()
     else:
-        mu = rng.standard_normal((c_out * h_out * h_out, p))
-        x = torch.from_numpy(mu.T.reshape(p, c_out, h_out, h_out))
+        mu = rng.standard_normal((c_out * h_out * w_out, p))
+        x = torch.from_numpy(mu.T.reshape(p, c_out, h_out, w_out))
         y = F.conv_transpose2d(x, torch.from_numpy(w).double(), None, s, pad)
-        assert y.shape[-1] == h_in
+        assert tuple(y.shape[-2:]) == (h_in, w_in)
         want = y.reshape(p, -1).T.numpy()            # the tap-count division is applied by the kernel, not the tables
     got = emulate_gather(g, cmat, koff, mu)
     np.testing.assert_allclose(got, want, atol=1e-5)
     dense = cost * 2 * 32 * 32 * 2 / 2          # MACs issued per sample (each MFMA: 32x32x2)
-    useful = w.size * (h_out * h_out)           # MACs of the sparse map per channel
-    print(f"conv {cfg} dir {direction} lanes {g['lanes']}: tile {g['CT']}x{g['PY']}x{g['PX']} align ({g['ay']},{g['ax']}) window {g['WY']}x{g['WX']} "
-          f"K2={g['K2']} tiles/sample={g['TPS']} mfma/sample={cost} density={useful / (dense / 64 * 32):.2f}")
+    useful = w.size * (h_out * w_out)           # MACs of the sparse map per channel
+    print(f"conv {cfg} dir {direction} lanes {g['lanes']}: tile {g['CT']}x{g['PY']}x{g['PX']} align ({g['ay']},{g['ax']}) tiles {g['NBY']}x{g['NBX']} "
+          f"window {g['WY']}x{g['WX']} K2={g['K2']} tiles/sample={g['TPS']} mfma/sample={cost} density={useful / (dense / 64 * 32):.2f}")
+    return True
+
+
+@pytest.mark.parametrize("cfg", CONVS)
+@pytest.mark.parametrize("direction,allow16", [(0, 0), (1, 0), (0, 1)])
+def test_gather_tables_match_torch_conv(packlib, cfg, direction, allow16):
+    c_in, c_out, k, s, pad, h_in = cfg
+    assert check_gather_tables(packlib, (c_in, c_out, k, s, pad, h_in, h_in), direction, allow16)
+
+
+def fwd_arch_convs():
+    """{arch: [(graph layer k, (c_in, c_out, k, stride, pad, h_in, w_in))]} of tests/common.py FWD_ARCHS."""
+    from tests.common import FWD_ARCHS
+    out = {}
+    for name, ((_, h, w), spec) in FWD_ARCHS.items():
+        out[name], layer = [], 0
+        for sp in spec:
+            if sp[0] == "conv":
+                _, ci, co, k, st, pad = sp
+                layer += 1
+                out[name].append((layer, (ci, co, k, st, pad, h, w)))
+                h, w = (h + 2 * pad - k) // st + 1, (w + 2 * pad - k) // st + 1
+            elif sp[0] == "linear":
+                layer += 1
+    return out
+
+
+# (c_in, c_out, k, stride, pad, h_in, w_in) with h_in != w_in, kernels 1..7, strides 1..4, pad 0..3, channels 3, 6, 8, 12, 16; kernels
+# larger than the image; and every conv of FWD_ARCHS.  An exchanged H and W in the tables is invisible on the square CONVS above.
+RECT_CONVS = sorted({(3, 8, 5, 1, 2, 12, 20), (8, 16, 2, 2, 0, 12, 20), (3, 8, 2, 3, 0, 20, 14), (8, 16, 1, 1, 0, 7, 5), (3, 8, 4, 2, 1, 10, 34),
+                     (8, 8, 3, 1, 0, 9, 11), (3, 12, 3, 1, 1, 6, 6), (12, 6, 4, 2, 1, 6, 10), (3, 12, 3, 1, 1, 6, 10), (12, 6, 4, 2, 1, 6, 6),
+                     (6, 16, 3, 1, 1, 6, 10), (8, 8, 3, 3, 0, 9, 15), (8, 16, 3, 2, 1, 7, 9), (8, 8, 7, 1, 3, 8, 8), (3, 8, 4, 4, 0, 8, 12),
+                     (3, 8, 4, 2, 1, 4, 4), (8, 8, 4, 2, 1, 2, 2)} | {cfg for convs in fwd_arch_convs().values() for _, cfg in convs})
+
+
+@pytest.mark.parametrize("cfg", RECT_CONVS, ids=lambda c: "{}to{}_k{}s{}p{}_{}x{}".format(*c))
+@pytest.mark.parametrize("direction,allow16", [(0, 0), (1, 0), (0, 1)])
+def test_gather_tables_match_torch_conv_on_rectangles(packlib, cfg, direction, allow16):
+    """Where build_gather has tables for a geometry they are the conv / transposed conv (a geometry without tables takes the VALU
+    kernels: test_gather_table_map_of_the_forward_geometry_archs pins which)."""
+    if not check_gather_tables(packlib, cfg, direction, allow16, may_be_missing=True):
+        print(f"conv {cfg} dir {direction}: no tables")
+
+
+def test_gather_table_map_of_the_forward_geometry_archs(packlib):
+    """Which directions of every conv edge of FWD_ARCHS have MFMA gather tables (as gnnb_bind_network asks for them: 16-lane tiles
+    allowed).  Three of the networks are there BECAUSE an edge has none and takes the VALU conv kernels: a change to build_gather
+    that gives them tables moves them onto other kernels, and must not do so unseen."""
+    have = {}
+    for name, convs in fwd_arch_convs().items():
+        for layer, cfg in convs:
+            c_in, c_out, k, s, pad, h_in, w_in = cfg
+            w = np.ones((c_out, c_in, k, k), np.float32)
+            have[(name, layer)] = tuple(build_gather(packlib, w, h_in, w_in, s, pad, d, normalise=int(d == 1 and layer > 1), allow16=1,
+                                                     may_be_missing=True) is not None for d in (0, 1))
+            print(f"{name} edge {layer} {c_in}->{c_out} {k}x{k}/{s}/{pad} on {h_in}x{w_in}: forward tables {have[(name, layer)][0]}, "
+                  f"transposed tables {have[(name, layer)][1]}")
+    assert have[("fwg_k7", 2)] == (True, False)          # 8 -> 8 7x7/1/3 on 8x8: forward tables only
+    assert have[("fwg_valu", 2)] == (False, False)       # 16 -> 32 5x5/1/2 on 6x6: none in either direction
+    assert have[("fwg_gap", 1)][1] is False              # 3 -> 8 2x2 stride 3: no transposed tables (k_convT_bwd + k_input_update)
+    # the neighbours of the table-less edges do have them
+    assert have[("fwg_k7", 1)] == (True, True) and have[("fwg_valu", 1)] == (True, True)
