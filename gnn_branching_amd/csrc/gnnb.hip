@@ -364,7 +364,7 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   HIPCHK(hipMemset(h->d_ctl, 0, 8 * 64 * sizeof(int)));
   // > 64 KiB of dynamic LDS needs the attribute
   HIPCHK(hipFuncSetAttribute((const void*)k_pre<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_pre<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PackPreBwdL3::FLOATS * 4));
+  HIPCHK(hipFuncSetAttribute((const void*)k_pre<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE_LDS_FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_pre_inp, hipFuncAttributeMaxDynamicSharedMemorySize, PackPreInp::FLOATS * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
   HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
@@ -1199,7 +1199,7 @@ struct Forward {
     long nt = 0;                                      // upper bound: the kernel reads the real counts on the device
     for (int k = 1; k <= L; ++k) nt += (((long)B * h->N[k] + 31) / 32) * 2;
     const PreAllArgs a = pre_args();
-    const size_t lds = (h->bf3 ? (size_t)PackPreBwdL3::FLOATS : (size_t)PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4;
+    const size_t lds = (h->bf3 ? (size_t)PRE_LDS_FLOATS : (size_t)PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4;
     void (*kern)(PreAllArgs) = h->bf3 ? k_pre<true> : k_pre<false>;
     lz.run(PC_PRE, [&] { hipLaunchKernelGGL(kern, dim3(mlp_grid(h, nt / 8)), dim3(PRE_WAVES * 64), lds, st, a); });
   }

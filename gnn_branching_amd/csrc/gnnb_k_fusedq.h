@@ -18,7 +18,9 @@
 //   filled[s]          rows written into ring slot s for its current tile
 //   free_id[s]         the tile id slot s accepts (starts at s; the chain wave sets T + QTILES when it is done with tile T)
 //   done               gather waves that have finished
-//   staged             chain waves whose share of the node-update weights is in LDS (the chain waves wait for all of them)
+//   staged[s]          chain waves whose share of stage s of the node-update weights is in LDS (stage_updl3_ordered: 0 small vectors + WAS3, 1 WA1S3,
+//                      2 WCB3, 3 POST; a chain wave waits, in front of each block of its FIRST tile only, until every chain wave has counted
+//                      itself for that block's stage -- its share of a stage is only there once the stages before it are)
 // A gather wave writes its rows of tile T only after free_id[T % QTILES] == T, then adds their number to filled[.] (LDS executes
 // one wave's operations in order, so the count lands after the rows).  Tile T's rows were reserved before tile T + QTILES's, and a
 // wave publishes its part of T before it waits for T + 1: no cycle.  Chain wave c takes tiles c, c + 4, ...; it leaves when all
@@ -62,6 +64,60 @@ __device__ __forceinline__ void stage_updl3(float* lds, const float* pack, const
 static_assert(PackUpdL3::BCB == PackUpdL3::BA + 64 && PackUpdL3::WAS3 == PackUpdL3::BCB + 256 && PackUpdL3::FLOATS == PackUpdL3::WAS3 + 3 * 6144,
               "stage_updl3: layout of the LDS image");
 
+// The same image for k_gather_update_q, whose chain waves do not put a barrier behind it: the pieces are requested -- still all of them before
+// the first LDS write -- and written in the order a chain uses them, stage 0: the small vectors + WAS3, 1: WA1S3, 2: WCB3, 3: POST.  Loads come
+// back in request order, so the first blocks are in LDS while the later ones are still on their way.  pub(s) is called, by every lane
+// of a wave together, once all of the wave's pieces of stages <= s are written (threads ct of CN: whole waves).
+// (k_top and k_scored_tail keep stage_updl3 and their barriers: with this form inside it k_top<4> spilled four vector registers.)
+#define UPDL3_STAGES 4
+// CN, POST at compile time: which step completes which stage is then decided by the compiler -- a wave counts itself for a stage when the
+// workgroup's pieces up to that step cover it, at most one load later than its own last piece of the stage.  No piece is conditional (a
+// load and its write inside a branch are waited for with vmcnt(0), in front of everything requested before them): the 80 pieces of the
+// small vectors are written by every lane, the lanes from 80 on repeating one of the first 64 -- the same value to the same address.
+template <int CN, bool POST, class Pub>
+__device__ __forceinline__ void stage_updl3_ordered(float* lds, const float* pack, const float* wp, int ct, Pub pub) {
+  constexpr int NSMALL = 16 + 64, NBLK = 6144 / 4, NB = (POST ? 4 : 3) * NBLK, PER = UPDL3_BATCH - 1;
+  static_assert(CN >= NSMALL && CN % 64 == 0, "stage_updl3_ordered: whole waves, one step for the small vectors");
+  __builtin_assume(ct >= 0 && ct < CN);
+  const int j = ct < NSMALL ? ct : (ct & 63);
+  const f32x4 sv = *reinterpret_cast<const f32x4*>(pack + (j < 16 ? PackUpd::BA + 4 * j : PackUpd::BCB + 4 * (j - 16)));
+#pragma unroll
+  for (int b0 = 0; b0 < NB; b0 += PER * CN) {
+    f32x4 v[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      if (b0 + u * CN >= NB) continue;
+      const int k = b0 + u * CN + ct;
+      const float* src = pack + PackUpd::WAS3 + 4 * k;                      // stage 0
+      if (k >= NBLK) src = pack + PackUpd::WA1S3 + 4 * (k - NBLK);          // 1
+      if (k >= 2 * NBLK) src = pack + PackUpd::WCB3 + 4 * (k - 2 * NBLK);   // 2
+      if (POST && k >= 3 * NBLK) src = wp + 4 * (k - 3 * NBLK);             // 3
+      v[u] = *reinterpret_cast<const f32x4*>(b0 + (u + 1) * CN <= NB || k < NB ? src : pack);
+    }
+    if (b0 == 0) *reinterpret_cast<f32x4*>(lds + (j < 16 ? PackUpdL3::BA + 4 * j : PackUpdL3::BCB + 4 * (j - 16))) = sv;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      if (b0 + u * CN >= NB) continue;
+      const int k = b0 + u * CN + ct;
+      float* dst = lds + PackUpdL3::WAS3 + 4 * k;
+      if (k >= NBLK) dst = lds + PackUpdL3::WA1S3 + 4 * (k - NBLK);
+      if (k >= 2 * NBLK) dst = lds + PackUpdL3::WCB3 + 4 * (k - 2 * NBLK);
+      if (POST && k >= 3 * NBLK) dst = lds + PackUpdL3::FLOATS + 4 * (k - 3 * NBLK);
+      if (b0 + (u + 1) * CN <= NB || k < NB) *reinterpret_cast<f32x4*>(dst) = v[u];
+      // with this step the workgroup's pieces below b0 + (u + 1) CN are written: the stages that end in this step's range are complete
+      // (without POST stage 3 is empty and counted with stage 2)
+#pragma unroll
+      for (int s = 0; s < UPDL3_STAGES; ++s) {
+        const int end = (s + 1) * NBLK < NB ? (s + 1) * NBLK : NB;
+        if (b0 + u * CN < end && b0 + (u + 1) * CN >= end) pub(s);
+      }
+    }
+  }
+}
+static_assert(PackUpdL3::BCB == PackUpdL3::BA + 64 && PackUpdL3::WAS3 == PackUpdL3::BCB + 256 && PackUpdL3::WCB3 == PackUpdL3::WAS3 + 6144 &&
+              PackUpdL3::WA1S3 == PackUpdL3::WCB3 + 6144 && PackUpdL3::FLOATS == PackUpdL3::WA1S3 + 6144, "stage_updl3_ordered: layout of the LDS image");
+static_assert(PackUpd::BCB + 256 == PackUpd::FLOATS && PackUpd::WCB3 == PackUpd::WAS3 + 6144, "stage_updl3_ordered: layout of the pack");
+
 struct FArgs {
   GArgs g;             // the gather (k_gather / k_gather16 arguments; g.nb is unused; g.sout != null: the sparse walk computes the bias sums)
   UpdArgs u;           // the node update (k_node_update arguments; list0 / list1 / cnt0 / cnt1, nb are unused)
@@ -82,7 +138,7 @@ struct FArgs {
 #define Q_POLL_CAP (1 << 22)
 __host__ __device__ constexpr size_t fusedq_queue_floats(int qtiles) { return (size_t)qtiles * 32 * QROW + QHDR_INTS; }
 
-struct QHdr { int reserve, done, claim, staged, filled[QTILES], free_id[QTILES], pad2[4]; };
+struct QHdr { int reserve, done, claim, staged[UPDL3_STAGES], filled[QTILES], free_id[QTILES], pad2[1]; };
 static_assert(sizeof(QHdr) == QHDR_INTS * 4, "queue header");
 
 // (acquire / release at workgroup scope: LDS needs no cache maintenance, this only keeps compiler and wait counters honest)
@@ -93,11 +149,15 @@ __device__ __forceinline__ int q_ld(const int* p) { return __hip_atomic_load(p, 
 // holds a node.  `lds`: the PackUpdL3 image.  Callers: k_gather_update_q / k_scored_tail (rows out of the LDS ring) and k_top (rows
 // out of the transposed Linear edge's accumulators) -- the same arithmetic per node as k_node_update, whatever tile a node rides in.
 // keep != nullptr: the rows E are also handed back in *keep (k_scored_tail feeds them to the score head without reading them back)
-template <bool POST, bool PIPE = (GEMM_BF3_PIPE != 0)>
-__device__ __forceinline__ void upd_chain_frag(const UpdArgs& u, const float* lds, const Frag& X, int gc, float r0, float r1, bool amb, float sw,
-                                               bool valid, int lane, Frag* keep = nullptr) {
+// ready(s) is asked in front of the first read of stage s of the image (stage_updl3_ordered) and says whether the chain may go on: k_gather_update_q's
+// first tile per wave starts while the later blocks are still being staged; false = the wait gave up, the chain is abandoned (returns false).
+struct UpdL3Ready { __device__ __forceinline__ bool operator()(int) const { return true; } };
+template <bool POST, bool PIPE = (GEMM_BF3_PIPE != 0), class Ready = UpdL3Ready>
+__device__ __forceinline__ bool upd_chain_frag(const UpdArgs& u, const float* lds, const Frag& X, int gc, float r0, float r1, bool amb, float sw,
+                                               bool valid, int lane, Frag* keep = nullptr, Ready ready = Ready()) {
   const int h = lane >> 5;
   Frag H, H2;
+  if (!ready(0)) return false;
   frag_bias(H, lds + PackUpdL3::BA, h);
   {
     const float x[1] = {(h ? r1 : r0) * sw};            // + s.(r0 Wa0.bp + r1 Wa1.bp): the bias of the source rows' deferred projection
@@ -110,11 +170,13 @@ __device__ __forceinline__ void upd_chain_frag(const UpdArgs& u, const float* ld
   if (__any(amb)) {
 #endif
     const float dr = r1 - r0;
+    if (!ready(1)) return false;
     gemm_w64_bf3<1, PIPE>(lds + PackUpdL3::WA1S3, lane, H, [&](int s) { return FRAG_AT(X, s) * dr; });
   }
   // P' of an ambiguous node: its cached row (k_pre); of every other node: the bias row
   frag_load_rowptr(H2, amb ? u.P + (long)gc * 64 : u.pack + PackUpd::BCBROW, h);
   frag_relu(H);
+  if (!ready(2)) return false;
   gemm_w64_bf3<1, PIPE>(lds + PackUpdL3::WCB3, lane, H2, [&](int s) { return FRAG_AT(H, s); });
   frag_relu(H2);
   if (valid) {
@@ -125,14 +187,17 @@ __device__ __forceinline__ void upd_chain_frag(const UpdArgs& u, const float* ld
   if (POST) {
 #pragma unroll
     for (int R = 0; R < 32; ++R) FRAG_AT(H, R) = 0.0f;
+    if (!ready(3)) return false;
     gemm_w64_bf3<1, PIPE>(lds + PackUpdL3::FLOATS, lane, H, [&](int s) { return FRAG_AT(H2, s); });
     if (valid) frag_store_rows(H, u.post, gc, h);
   }
+  return true;
 }
 
 // the same on ring slot `ring` (32 rows of QROW floats); `release` runs once the rows are in registers
-template <bool POST, bool PIPE = (GEMM_BF3_PIPE != 0), class Release>
-__device__ __forceinline__ void q_chain(const FArgs& a, const float* lds, const float* ring, int nvalid, int lane, Release release, Frag* keep = nullptr) {
+template <bool POST, bool PIPE = (GEMM_BF3_PIPE != 0), class Release, class Ready = UpdL3Ready>
+__device__ __forceinline__ bool q_chain(const FArgs& a, const float* lds, const float* ring, int nvalid, int lane, Release release, Frag* keep = nullptr,
+                                        Ready ready = Ready()) {
   const int h = lane >> 5, j = lane & 31;
   const bool valid = j < nvalid;
   const float* row = ring + j * QROW;
@@ -153,7 +218,7 @@ __device__ __forceinline__ void q_chain(const FArgs& a, const float* lds, const 
   }
   __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0): the rows and scalars are in registers
   release();
-  upd_chain_frag<POST, PIPE>(a.u, lds, X, gc, r0, r1, amb, sw, valid, lane, keep);
+  return upd_chain_frag<POST, PIPE>(a.u, lds, X, gc, r0, r1, amb, sw, valid, lane, keep, ready);
 }
 
 #if defined(FUSED_TIMING) && FUSED_TIMING == 6      // dev: per-phase cycle sums of ONE k_gather_update_q template (Q_TIME_LANES / _SRC / _POST); slots 0-4 gather waves, 5-9 chain waves
@@ -216,20 +281,28 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
   if (chain_role) {
     // ---------------- chain wave ----------------
     // The node-update weights (74 KB + 24 KB of POST) are staged by the chain waves alone while the gather waves, which only need the
-    // gather's tables, already walk their first tiles; `staged` counts the chain waves whose part is in LDS.
+    // gather's tables, already walk their first tiles; `staged[s]` counts the chain waves whose part of stage s is in LDS.  Nobody waits
+    // for the whole image: the first ring tiles are full before it is (16 k against 18 k cycles), and the first block of a chain needs
+    // 24 KB of it -- the wave's first chain asks for each stage in front of the block that reads it (`ready`), later tiles ask nothing.
     {
-      const int ct = (wave - QG_WAVES) * 64 + lane, cn = QC_WAVES * 64;
-      stage_updl3(lds, a.u.pack, POST ? a.u.wp : nullptr, ct, cn);
-      __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0): this wave's part is in LDS before it is counted
-      if (lane == 0) __hip_atomic_fetch_add(&q->staged, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      bool ok = false;
+      const int ct = (wave - QG_WAVES) * 64 + lane;
+      stage_updl3_ordered<QC_WAVES * 64, POST>(lds, a.u.pack, a.u.wp, ct, [&](int s) {
+        __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's part of the stage is in LDS before it is counted
+        if (lane == 0) __hip_atomic_fetch_add(&q->staged[s], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      });
+    }
+    QT_MARK(6);                                     // this wave's share of the node-update weights staged (slot 9: its first tile waiting for a stage)
+    int nready = 0;                                 // stages of the image known to be complete (a scalar; UPDL3_STAGES after the first tile)
+    auto ready = [&](int s) {
+      if (s < nready) return true;
+      QT_MARK(8);
       for (int it = 0; it < Q_POLL_CAP; ++it) {
-        if (q_ld(&q->staged) == QC_WAVES) { ok = true; break; }
+        if (q_ld(&q->staged[s]) == QC_WAVES) { nready = s + 1; QT_MARK(9); return true; }      // (a wave counts itself for s behind s - 1: the stages below are complete too)
         __builtin_amdgcn_s_sleep(2);
       }
-      if (!ok) { if (lane == 0) atomicOr(a.u.status, 2); return false; }
-    }
-    QT_MARK(6);                                     // node-update weights staged (all chain waves)
+      if (lane == 0) atomicOr(a.u.status, 2);
+      return false;
+    };
     // claims the next tile, copies it out of its ring slot, releases the slot, runs the chain
     for (;;) {
       int T = 0;
@@ -250,14 +323,16 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
       if (nvalid < 0) { if (lane == 0) atomicOr(a.u.status, 2); return false; }
       QT_MARK(7);                                   // waiting for a tile of rows
       if (nvalid == 0) { QT_FLUSH(); return true; }
-      q_chain<POST>(a, lds, ring, nvalid, lane, [&]() {
+      const bool went = q_chain<POST>(a, lds, ring, nvalid, lane, [&]() {
         // (called once the rows are in registers) hand the slot back before the chain runs: the ring only has to cover the
         // time a tile takes to fill and to be copied out, not the ~10 us of its chain
         if (nvalid == 32 && lane == 0) {
           __hip_atomic_store(&q->filled[s], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           __hip_atomic_store(&q->free_id[s], T + NQ, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-      });
+      }, nullptr, ready);
+      if (!went) return false;
+      nready = UPDL3_STAGES;                        // (a tile without an ambiguous node skips stage 1's block: the stage behind it was asked for)
       QT_MARK(8);                                   // rows -> registers, chain, row stores
       if (nvalid < 32) { QT_FLUSH(); return true; }      // the last, partly filled tile
     }

@@ -655,13 +655,16 @@ __global__ __launch_bounds__(TAIL_WAVES * 64, 1) void k_scored_tail(TailArgs a) 
   }
   TT_MARK(wave < nchain ? 7 : 0);             // chain + score head of the last segment (chain waves)
   if (wg >= nseg) __syncthreads();            // a workgroup without a segment: the staged weights become visible here
-  // ---- the scored nodes of the other layers: the score head on their rows in memory (k_score's tiles), dealt from the LAST
-  // workgroup backwards -- those have the fewest layer-1 segments -- and to the gather waves first (they are free while the chain
-  // waves finish the last segment: no barrier in front of this phase)
+  // ---- the scored nodes of the other layers: the score head on their rows in memory (k_score's tiles), dealt ROUND-ROBIN over the
+  // workgroups and, inside a workgroup, to the gather waves first: they are free while the chain waves finish the last segment (no
+  // barrier in front of this phase), so a tile runs under the last chain.  A chain wave only gets one when its workgroup has more tiles
+  // than gather waves (base B = 256: 1 356 tiles = 5.3 per workgroup on 10 gather waves; dealt 12 per workgroup, 113 workgroups had
+  // both chain waves run one behind their last chain: 9 k cycles on the critical path).  The score weights are published by the
+  // first barrier, so a gather wave without a group cannot start earlier than that; behind its last gather is early enough.
   long ntiles = 0;
   for (int k = 1; k < a.s.L; ++k) ntiles += (a.s.cnt[4 * k + 2] + 31) / 32;
   const int slot = wave >= nchain ? wave - nchain : ngw + wave;
-  for (long tile = (long)(gridDim.x - 1 - blockIdx.x) * TAIL_WAVES + slot; tile < ntiles; tile += (long)gridDim.x * TAIL_WAVES) {
+  for (long tile = (long)slot * gridDim.x + blockIdx.x; tile < ntiles; tile += (long)gridDim.x * TAIL_WAVES) {
     int k = 1, count = 0;
     long t = tile;
     for (; k < a.s.L; ++k) {

@@ -200,12 +200,13 @@ struct PreAllArgs {       // hoisted feature chains of every ReLU layer, forward
 // BF3: the 64x64 blocks (W2 forward; W2, W3, W5 backward) on the bf16 matrix rate with three-piece operands (LDS images
 // PackPreFwdL3 / PackPreBwdL3); the 192-wide W4 and the feature layers stay on the fp32 MFMA
 // (k_pre's 16 waves sit at the 128-register step with the sequential blocks: the pipelined form spills 16 registers there)
+// w23f (BF3): where the forward chain's W23 block sits in LDS (k_pre keeps it apart from the forward small vectors)
 #ifndef PRE_PIPE
 #define PRE_PIPE false
 #endif
 template <bool BF3>
-__device__ __forceinline__ void pre_tile(const PreAllArgs& a, const float* lds, const float* lds_b, int k, bool bwd, const int* list, int count,
-                                         long t, int lane) {
+__device__ __forceinline__ void pre_tile(const PreAllArgs& a, const float* lds, const float* lds_b, const float* w23f, int k, bool bwd, const int* list,
+                                         int count, long t, int lane) {
   constexpr int F_W1 = BF3 ? (int)PackPreFwdL3::W1 : (int)PackPreFwd::W1, F_B1 = BF3 ? (int)PackPreFwdL3::B1 : (int)PackPreFwd::B1;
   constexpr int F_B2 = BF3 ? (int)PackPreFwdL3::B2 : (int)PackPreFwd::B2;
   constexpr int B_W1 = BF3 ? (int)PackPreBwdL3::W1 : (int)PackPreBwd::W1, B_B1 = BF3 ? (int)PackPreBwdL3::B1 : (int)PackPreBwd::B1;
@@ -236,7 +237,7 @@ __device__ __forceinline__ void pre_tile(const PreAllArgs& a, const float* lds, 
       frag_relu(H);
       Frag Pf;                                   // fc1_1 and the first half of fc4 are one folded 64x64 map
       frag_bias(Pf, lds + F_B2, h);
-      if (BF3) gemm_w64_bf3<1, PRE_PIPE>(lds + PackPreFwdL3::W23, lane, Pf, [&](int s) { return FRAG_AT(H, s); });
+      if (BF3) gemm_w64_bf3<1, PRE_PIPE>(w23f, lane, Pf, [&](int s) { return FRAG_AT(H, s); });
       else gemm_w64<32>(lds + PackPreFwd::W2, lane, Pf, [&](int s) { return FRAG_AT(H, s); });
       if (valid) frag_store_rows(Pf, a.Pf[k], gc, h);
     } else {
@@ -281,6 +282,12 @@ __device__ __forceinline__ void pre_tile(const PreAllArgs& a, const float* lds, 
 #ifndef PRE_WAVES
 #define PRE_WAVES 16      // the weights (150 KB) allow one workgroup per CU: 16 waves of <= 128 registers fill it
 #endif
+// k_pre<true>'s LDS: the backward image and the forward chain's small vectors (W1, B1, B2) behind it; its share of W53 per thread in registers
+#define PRE_LDS_FLOATS ((int)PackPreBwdL3::FLOATS + (int)PackPreFwdL3::W23)
+#define PRE_W53_REGS ((3072 + PRE_WAVES * 64 - 1) / (PRE_WAVES * 64))
+static_assert(PRE_LDS_FLOATS * 4 <= 160 * 1024, "k_pre: LDS");
+static_assert((int)PackPreFwdL3::FLOATS - (int)PackPreFwdL3::W23 == 6144 && (int)PackPreBwdL3::FLOATS - (int)PackPreBwdL3::W53 == 6144,
+              "k_pre: the forward W23 block waits in W53's place");
 template <bool BF3>
 __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
   long nhalf = 0;
   for (int k = 0; k < a.L; ++k) nhalf += (long)((a.cnt[4 * k + 1] + 31) / 32);
   // tile t of one direction: which layer (wave-uniform)
-  auto run = [&](long t, bool bwd, const float* lf, const float* lb) {
+  auto run = [&](long t, bool bwd, const float* lf, const float* lb, const float* w23f) {
     int k = 0, count = 0;
     for (; k < a.L; ++k) {
       count = a.cnt[4 * k + 1];
@@ -296,30 +303,51 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
       if (t < tk) break;
       t -= tk;
     }
-    pre_tile<BF3>(a, lf, lb, k, bwd, a.list[k], count, t, lane);
+    pre_tile<BF3>(a, lf, lb, w23f, k, bwd, a.list[k], count, t, lane);
   };
   if (BF3) {
-    // forward image + everything of the backward image behind its head; forward tiles; then the head; backward tiles
-    copy_to_lds(lds + PackPreFwdL3::W1, a.pack_f + PackPreFwd::W1, 512 + 64);
-    copy_to_lds(lds + PackPreFwdL3::B2, a.pack_f + PackPreFwd::B2, 64);
-    copy_to_lds(lds + PackPreFwdL3::W23, a.pack_f + PackPreFwd::W23, 6144);
-    if (a.do_bwd) {
-      copy_to_lds(lds + PackPreBwdL3::B3, a.pack_b + PackPreBwd::B3, 64);
-      copy_to_lds(lds + PackPreBwdL3::B4, a.pack_b + PackPreBwd::B4, 64);
-      copy_to_lds(lds + PackPreBwdL3::B5, a.pack_b + PackPreBwd::B5, 64);
-      copy_to_lds(lds + PackPreBwdL3::W33, a.pack_b + PackPreBwd::W33, 6144);
-      copy_to_lds(lds + PackPreBwdL3::W43, a.pack_b + PackPreBwd::W43, 18432);
-      copy_to_lds(lds + PackPreBwdL3::W53, a.pack_b + PackPreBwd::W53, 6144);
+    if (!a.do_bwd) {
+      copy_to_lds(lds + PackPreFwdL3::W1, a.pack_f + PackPreFwd::W1, 512 + 64);
+      copy_to_lds(lds + PackPreFwdL3::B2, a.pack_f + PackPreFwd::B2, 64);
+      copy_to_lds(lds + PackPreFwdL3::W23, a.pack_f + PackPreFwd::W23, 6144);
+      __syncthreads();
+      for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, false, lds, lds, lds + PackPreFwdL3::W23);
+      return;
     }
-    __syncthreads();
-    for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, false, lds, lds);
-    if (!a.do_bwd) return;
-    __syncthreads();
+    // ONE staging phase: the whole backward image except W53 -- the block a backward tile reads last -- goes to its place at entry; the
+    // forward chain's W23 has W53's size and waits in its place, the forward small vectors sit behind the image (PRE_LDS_FLOATS).  Each
+    // thread requests its share of W53 at entry too and keeps it in registers over the forward tiles (PRE_W53_REGS float2 per thread):
+    // behind the barrier that ends the forward tiles it only has to be written to LDS, where the second staging used to start a
+    // global -> LDS round trip that every wave of the workgroup waited for, tile or no tile.
+    float* lds_f = lds + PackPreBwdL3::FLOATS;                       // forward W1, B1, B2 (PackPreFwdL3 offsets; its W23 is not here)
+    float* w23f = lds + PackPreBwdL3::W53;
+    float2 w53[PRE_W53_REGS];
+#pragma unroll
+    for (int u = 0; u < PRE_W53_REGS; ++u) {
+      const int i = threadIdx.x + u * PRE_WAVES * 64;                // (float2 pieces: 3072 of them)
+      w53[u] = reinterpret_cast<const float2*>(a.pack_b + PackPreBwd::W53)[i < 3072 ? i : 0];
+    }
+    copy_to_lds(lds_f + PackPreFwdL3::W1, a.pack_f + PackPreFwd::W1, 512 + 64);
+    copy_to_lds(lds_f + PackPreFwdL3::B2, a.pack_f + PackPreFwd::B2, 64);
+    copy_to_lds(w23f, a.pack_f + PackPreFwd::W23, 6144);
     copy_to_lds(lds + PackPreBwdL3::W1, a.pack_b + PackPreBwd::W1, 512 + 64);                      // W1, B1
     copy_to_lds(lds + PackPreBwdL3::B2, a.pack_b + PackPreBwd::B2, 64);
     copy_to_lds(lds + PackPreBwdL3::W23, a.pack_b + PackPreBwd::W23, 6144);
+    copy_to_lds(lds + PackPreBwdL3::B3, a.pack_b + PackPreBwd::B3, 64);
+    copy_to_lds(lds + PackPreBwdL3::B4, a.pack_b + PackPreBwd::B4, 64);
+    copy_to_lds(lds + PackPreBwdL3::B5, a.pack_b + PackPreBwd::B5, 64);
+    copy_to_lds(lds + PackPreBwdL3::W33, a.pack_b + PackPreBwd::W33, 6144);
+    copy_to_lds(lds + PackPreBwdL3::W43, a.pack_b + PackPreBwd::W43, 18432);
     __syncthreads();
-    for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, true, lds, lds);
+    for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, false, lds_f, lds, w23f);
+    __syncthreads();                                                 // every forward tile of the workgroup has read W23
+#pragma unroll
+    for (int u = 0; u < PRE_W53_REGS; ++u) {
+      const int i = threadIdx.x + u * PRE_WAVES * 64;
+      if (i < 3072) reinterpret_cast<float2*>(lds + PackPreBwdL3::W53)[i] = w53[u];
+    }
+    __syncthreads();
+    for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, true, lds, lds, nullptr);
     return;
   }
   float* lds_b = lds + (int)PackPreFwd::FLOATS;
@@ -328,7 +356,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
   const long ntiles = nhalf * (a.do_bwd ? 2 : 1);
   for (long tile = (long)wave * gridDim.x + blockIdx.x; tile < ntiles; tile += (long)gridDim.x * PRE_WAVES) {
     const bool bwd = a.do_bwd && tile < nhalf;
-    run((a.do_bwd && !bwd) ? tile - nhalf : tile, bwd, lds, lds_b);
+    run((a.do_bwd && !bwd) ? tile - nhalf : tile, bwd, lds, lds_b, nullptr);
   }
 }
 
@@ -362,14 +390,14 @@ __global__ __launch_bounds__(CLS_THREADS) void k_classify_pre(ClassifyArgs ca, P
   const int k = __builtin_amdgcn_readfirstlane(k_);
   __syncthreads();                                   // the block's list and the images are in LDS
   const long nt = (count + 31) / 32;
-  for (long t = wave; t < nt; t += PRE_WAVES) pre_tile<true>(a, lds, lds, k, false, amb_local, count, t, lane);
+  for (long t = wave; t < nt; t += PRE_WAVES) pre_tile<true>(a, lds, lds, lds + PackPreFwdL3::W23, k, false, amb_local, count, t, lane);
   if (!a.do_bwd) return;
   __syncthreads();
   copy_to_lds(lds + PackPreBwdL3::W1, a.pack_b + PackPreBwd::W1, 512 + 64);                      // W1, B1
   copy_to_lds(lds + PackPreBwdL3::B2, a.pack_b + PackPreBwd::B2, 64);
   copy_to_lds(lds + PackPreBwdL3::W23, a.pack_b + PackPreBwd::W23, 6144);
   __syncthreads();
-  for (long t = wave; t < nt; t += PRE_WAVES) pre_tile<true>(a, lds, lds, k, true, amb_local, count, t, lane);
+  for (long t = wave; t < nt; t += PRE_WAVES) pre_tile<true>(a, lds, lds, nullptr, k, true, amb_local, count, t, lane);
 }
 
 // Q = inp_b2[:, :64] . inp_b_1(relu(inp_b([l0, u0]))) + inp_b2.bias       graph_conv.py:380-384

@@ -54,7 +54,7 @@ print("median / max end of the last chain wave by XCD (blockIdx % 8): " + "  ".j
 print(f"instrumented launch: first wave start -> last wave end {(w[:, 1].max() - w[:, 0].min()) * 0.01:.1f} us; starts spread over {(w[:, 0].max() - w[:, 0].min()) * 0.01:.1f} us, "
       f"ends over {(w[:, 1].max() - w[:, 1].min()) * 0.01:.1f} us; HIP-event durations of this forward's launches: {[(nm, round(1e3 * ms, 1)) for nm, ms in trace]}")
 names = ["G tables staged, header", "G tile decode + bounds", "G table build + walk", "G wait for ring slot", "G rows -> ring",
-         "C tables staged, header", "C weights staged (all)", "C wait for a tile", "C rows->regs, chain, stores", "-"]
+         "C tables staged, header", "C weights staged (own share)", "C wait for a tile", "C rows->regs, chain, stores", "C first tile: wait for a stage"]
 ng, nc = out[15], out[14]
 print(f"{net} B={B}: {ng / n:.0f} gather waves, {nc / n:.0f} chain waves per forward (cycles per wave, shader clock)")
 for i, nm in enumerate(names):
