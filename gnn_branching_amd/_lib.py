@@ -13,7 +13,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("GNNB_LIB", os.path.join(CSRC, "libgnnb.so"))     # GNNB_LIB: dev override (ablation builds)
-SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_train.h", "gnnb_k_kw.h"]
+SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_train.h", "gnnb_k_kw.h", "gnnb_k_dual.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread"]
 
 GNNB_CONV, GNNB_LINEAR, GNNB_RELU, GNNB_FLATTEN = 0, 1, 2, 3
@@ -38,6 +38,11 @@ class KwBatch(C.Structure):
                 ("n_graph", C.c_int32)]
 
 
+class DualBatch(C.Structure):
+    _fields_ = [("lb", C.POINTER(C.c_void_p)), ("ub", C.POINTER(C.c_void_p)), ("x_lo", C.c_void_p), ("x_hi", C.c_void_p),
+                ("prop_w", C.c_void_p), ("prop_b", C.c_void_p), ("mask", C.c_void_p), ("n_graph", C.c_int32)]
+
+
 # every symbol include/gnnb.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gnnb_create", C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
@@ -60,6 +65,10 @@ SYMBOLS = [
     ("gnnb_kw_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_kw_bounds", C.c_int, [C.c_void_p, C.POINTER(KwBatch), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_dual_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_dual_ascent", C.c_int, [C.c_void_p, C.POINTER(DualBatch), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -20,7 +20,7 @@
 //
 // One translation unit: gnnb_dev.h (fragments, GEMM blocks, tile maps), gnnb_k_mlp.h (setup + node-MLP kernels),
 // gnnb_k_gather.h (conv-edge message passing + score head), gnnb_k_fusedq.h (gather + node update in one kernel), gnnb_k_edges.h (other edges, k_top), gnnb_k_misc.h (k_livesum,
-// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_train.h (online learning) are included below; this file
+// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_k_dual.h (dual ascent, gnnb_dual_ascent), gnnb_train.h (online learning) are included below; this file
 // holds the host side and the C-ABI.
 //
 // gfx950 only.  No HIP call at load time.
@@ -57,6 +57,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_edges.h"
 #include "gnnb_k_misc.h"
 #include "gnnb_k_kw.h"
+#include "gnnb_k_dual.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -86,12 +87,12 @@ static int fail(int code, const char* fmt, ...) {
 enum ProfClass {
   PC_EMBED, PC_PRE, PC_PRE_INP, PC_CONV_FWD, PC_CONVT_BWD, PC_DENSE_AGG, PC_PROP_FWD,
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
-  PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_COUNT
+  PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
     "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
-    "k_kw_first", "k_kw_layer", "k_kw_flag"};
+    "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent"};
 
 struct DevEdge {
   float *w_fwd = nullptr, *w_bwd = nullptr, *bias = nullptr;   // conv: tap-major copies; linear: W^T / W, zero-padded
@@ -1864,6 +1865,71 @@ extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double*
   for (int k = 2; k <= K; ++k)
     run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(h->N[k], B), dim3(KW_THREADS), lds, st, a, k); });
   run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+
+// ================================================================================================================
+// Dual ascent on the subproblem LP of a batch of BaB domains (gnnb_k_dual.h; lp_producer.py LayerGraphLP.dual_ascent_host; stands in for
+// the LP of reference plnn/conv_kwinter_gen.py:179-555 where only its optimum and a primal / dual point near it are needed)
+// ================================================================================================================
+extern "C" size_t gnnb_dual_workspace_bytes(const gnnb_t* h, int B) {
+  if (!h || !h->bound || B < 1) return 0;
+  return (size_t)B * dual_ws_doubles(h->R, h->N[0]) * sizeof(double);
+}
+
+extern "C" int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int n_iter, double lr, double* alpha, double* beta, int warm,
+                                double* bound, double* grad_alpha, double* grad_beta, float* const* dual, float* const* primal, float* x_lp,
+                                float* lb32_prop, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null handle");
+  if (!h->bound) return fail(GNNB_E_STATE, "gnnb_dual_ascent: call gnnb_bind_network first");
+  if (!in || !alpha || !beta || !bound || !workspace || B < 1 || n_iter < 0)
+    return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null argument, batch size %d < 1 or %d iterations", B, n_iter);
+  const int K = (int)h->N.size() - 1, L = K - 1;
+  if (in->n_graph != K + 1) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: %d graph layers given, network has %d", in->n_graph, K + 1);
+  if (!in->lb || !in->ub || !in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask)
+    return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null input pointer");
+  if ((grad_alpha == nullptr) != (grad_beta == nullptr)) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: grad_alpha and grad_beta go together");
+  if ((dual == nullptr) != (primal == nullptr) || (dual == nullptr) != (x_lp == nullptr))
+    return fail(GNNB_E_INVALID, "gnnb_dual_ascent: dual, primal and x_lp go together");
+  if (L < 1 || L > MAXL) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: %d ReLU layers (1..%d)", L, MAXL);
+  int maxNr = 0;
+  for (int k = 1; k <= L; ++k) maxNr = std::max(maxNr, h->N[k]);
+  const size_t lds = kw_lds_doubles(maxNr) * sizeof(double);
+  if (lds > 65536)
+    return fail(GNNB_E_INVALID, "gnnb_dual_ascent: a ReLU layer of %d nodes needs %zu bytes of LDS for the dual pass (64 KiB at most)", maxNr, lds);
+  const size_t need = gnnb_dual_workspace_bytes(h, B);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "gnnb_dual_ascent: workspace %zu bytes, need %zu", workspace_bytes, need);
+  DualArgs a{};
+  a.L = L; a.R = h->R; a.maxNr = maxNr; a.n_iter = n_iter; a.warm = warm ? 1 : 0; a.lr = lr;
+  int off = 0;
+  a.N[0] = h->N[0];
+  for (int k = 1; k <= L; ++k) {
+    if (!in->lb[k - 1] || !in->ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null bounds pointer for graph layer %d", k);
+    const Edge& e = h->edges[k];
+    const int q = h->relu_q[k];
+    if (dual && (!dual[k - 1] || !primal[q - 1] || !primal[q])) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null scorer array (layer %d)", k);
+    a.N[k] = h->N[k]; a.off[k] = off; off += h->N[k];
+    a.lh[k] = e.kind == 0 ? e.h_out : 1;
+    a.lw[k] = e.kind == 0 ? e.w_out : 1;
+    a.lb[k] = in->lb[k - 1]; a.ub[k] = in->ub[k - 1];
+    KwEdge& E = a.e[k];
+    E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0; E.kind = e.kind;
+    E.c_in = e.c_in; E.h_in = e.h_in; E.w_in = e.w_in; E.c_out = e.c_out; E.h_out = e.h_out; E.w_out = e.w_out;
+    E.kh = e.kh; E.kw = e.kw; E.stride = e.stride; E.pad = e.pad; E.n_in = e.n_in; E.n_out = e.n_out;
+    if (dual) { a.dual[k] = dual[k - 1]; a.z_pre[k] = primal[q - 1]; a.z_post[k] = primal[q]; }
+  }
+  if (dual) {
+    if (!primal[h->n_fixed]) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null primals[-1]");
+    a.z_out = primal[h->n_fixed];
+  }
+  a.x_lo = in->x_lo; a.x_hi = in->x_hi; a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.mask = in->mask;
+  a.alpha = alpha; a.beta = beta; a.bound = bound; a.grad_alpha = grad_alpha; a.grad_beta = grad_beta;
+  a.x_lp = x_lp; a.lb32_prop = lb32_prop;
+  a.ws = (double*)workspace; a.ws_stride = (long)dual_ws_doubles(h->R, h->N[0]);
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_DUAL, [&] { hipLaunchKernelGGL(k_dual_ascent, dim3(B), dim3(DUAL_THREADS), lds, st, a); });
   return run.rc;
 }
 

@@ -59,6 +59,17 @@ class KwBoundsResult:
         self.lb, self.ub, self.lb32, self.ub32, self.infeasible = lb, ub, lb32, ub32, infeasible
 
 
+class DualAscentResult:
+    """Device tensors of one ``ScorerEngine.dual_ascent`` call.  bound (B,), alpha / beta (B, R): the best value of the dual and its
+    point, fp64; grad_alpha / grad_beta: None, or the supergradient at the entry point; dual / primals / x_lp: None, or the scorer's
+    inputs at the best point, fp32, as ``forward`` takes them (primals: one tensor per network layer; only the pre- and post-activation
+    of every ReLU layer and the last one are filled, the others are one-element placeholders)."""
+
+    def __init__(self, bound, alpha, beta, grad_alpha, grad_beta, dual, primals, x_lp):
+        self.bound, self.alpha, self.beta, self.grad_alpha, self.grad_beta = bound, alpha, beta, grad_alpha, grad_beta
+        self.dual, self.primals, self.x_lp = dual, primals, x_lp
+
+
 def _or_reduce(status):
     v = 0
     for x in status.cpu().tolist():
@@ -801,6 +812,89 @@ class ScorerEngine:
             n = self.lib.gnnb_kw_workspace_bytes(self.h, B)
             if n == 0:
                 raise RuntimeError("gnnb_kw_workspace_bytes returned 0 (no network bound?)")
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+            if len(self._ws) > 6:
+                self._ws.clear()
+            self._ws[key] = ws
+        return ws
+
+    # ---- dual ascent on the subproblem LPs (lp_producer.LayerGraphLP.dual_ascent_host for a batch) --------------------------------
+    def dual_ascent(self, fixed_layers, prop_layers, x_lo, x_hi, masks, lb, ub, n_iter, lr=0.1, alpha=None, beta=None, want_grad=False,
+                    want_scorer_inputs=False, lb32_prop=None, workspace=None):
+        """gnnb_dual_ascent on the current stream: ``n_iter`` steps of projected Adam on the dual of every domain's LP relaxation, the
+        intermediate bounds fixed.  x_lo / x_hi / prop_layers / masks: as ``kw_bounds`` takes them; lb / ub: n_graph-1 fp64 tensors
+        (B, N_k) of graph layers 1..L+1, mask applied (``KwBoundsResult.lb`` / ``.ub``).  alpha / beta: None (start at u / (u - l) and 0)
+        or (B, R) fp64 to start from (copied).  lb32_prop: None, or a (B,) / (B, 1) fp32 device tensor that receives the bound (the
+        property entry of ``KwBoundsResult.lb32``).  workspace: None (the engine's own), or a device uint8 tensor.  Returns a DualAscentResult."""
+        B = int(x_lo.shape[0])
+        if fixed_layers and type(fixed_layers[0]) is nn.Conv2d and (x_lo.dim() != 4 or x_hi.dim() != 4):
+            raise ValueError(f"the first layer is a Conv2d: x_lo / x_hi must be (B, C, H, W) boxes, got {tuple(x_lo.shape)} / {tuple(x_hi.shape)}")
+        self.bind(fixed_layers, tuple(x_lo.shape[1:]))
+        if len(prop_layers) != B:
+            raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together")
+        ng, dev, R = len(self.sizes), self.device, self.R
+        if len(lb) != ng - 1 or len(ub) != ng - 1:
+            raise ValueError(f"{len(lb)} / {len(ub)} bound tensors, expected {ng - 1} (graph layers 1..L+1)")
+
+        def f64(t, n, what):
+            t = torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()
+            if t.numel() != B * n:
+                raise ValueError(f"{what}: {tuple(t.shape)} does not hold {B}x{n} values")
+            return t.view(B, n)
+        xl, xu = f64(x_lo, self.sizes[0], "x_lo"), f64(x_hi, self.sizes[0], "x_hi")
+        lbs = [f64(t, self.sizes[k + 1], f"lb {k + 1}") for k, t in enumerate(lb)]
+        ubs = [f64(t, self.sizes[k + 1], f"ub {k + 1}") for k, t in enumerate(ub)]
+        mask = torch.as_tensor(masks).to(device=dev, dtype=torch.int8).contiguous()
+        if mask.numel() != B * R:
+            raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {R})")
+        pw, pb = self._prop(prop_layers)
+        warm = alpha is not None
+        al = f64(alpha, R, "alpha").clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
+        be = f64(beta, R, "beta").clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
+        bound = torch.empty(B, dtype=torch.float64, device=dev)
+        ga = gb = None
+        if want_grad:
+            ga, gb = torch.empty_like(al), torch.empty_like(al)
+        duals = prims = x_lp = None
+        if want_scorer_inputs:
+            duals = [torch.empty(B * n, 3, dtype=torch.float32, device=dev) for n in self.sizes[1:-1]]
+            prims, k = [], 0
+            for q, l in enumerate(fixed_layers):                  # primals[q]: the output of network layer q
+                nxt = fixed_layers[q + 1] if q + 1 < len(fixed_layers) else None
+                if type(l) is nn.ReLU or type(nxt) is nn.ReLU:
+                    k += type(nxt) is nn.ReLU
+                    prims.append(torch.empty(B * self.sizes[k], dtype=torch.float32, device=dev))
+                else:                                             # (gnnb_forward never reads it)
+                    prims.append(torch.zeros(1, dtype=torch.float32, device=dev))
+            prims.append(torch.empty(B, dtype=torch.float32, device=dev))
+            x_lp = torch.empty(tuple(x_lo.shape), dtype=torch.float32, device=dev)
+        if lb32_prop is not None and (lb32_prop.numel() != B or lb32_prop.dtype != torch.float32 or lb32_prop.device != dev
+                                      or not lb32_prop.is_contiguous()):
+            raise ValueError("lb32_prop must be a contiguous device fp32 tensor of B values")
+        ws = self.dual_workspace(B) if workspace is None else workspace
+
+        def table(ts):
+            return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        db = _lib.DualBatch(table(lbs), table(ubs), xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), ng)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_dual_ascent(self.h, C.byref(db), B, int(n_iter), float(lr), al.data_ptr(), be.data_ptr(), int(warm),
+                                           bound.data_ptr(), ptr(ga), ptr(gb), table(duals), table(prims), ptr(x_lp), ptr(lb32_prop),
+                                           ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_dual_ascent")
+        return DualAscentResult(bound, al, be, ga, gb, duals, prims, x_lp)
+
+    def dual_workspace(self, B):
+        key = ("dual", B)
+        ws = self._ws.get(key)
+        if ws is None:
+            n = self.lib.gnnb_dual_workspace_bytes(self.h, B)
+            if n == 0:
+                raise RuntimeError("gnnb_dual_workspace_bytes returned 0 (no network bound?)")
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             if len(self._ws) > 6:
                 self._ws.clear()

@@ -76,10 +76,22 @@ class Subproblem:
     primals: List[list]              # per network layer after the input
     mask: List[torch.Tensor]         # per ReLU layer, {-1, 0, 1}
     bounds64: tuple = None           # (lbs, ubs) in float64 as computed: what a child's bounds are intersected with
+    dual_point: tuple = None         # lp="dual_device" only: the (alpha, beta) the bound belongs to, what a child's ascent starts from
 
     def graph_bounds(self, pre_relu_indices, n_layers):
         idx = [0] + list(pre_relu_indices) + [n_layers]
         return [self.lower_all[i].unsqueeze(0) for i in idx], [self.upper_all[i].unsqueeze(0) for i in idx]
+
+
+@dataclass
+class DualAscentHost:
+    """What ``LayerGraphLP.dual_ascent_host`` yields (flat (R,) fp64 tensors in ReLU order)."""
+    bound: float                     # best g met
+    alpha: torch.Tensor              # ... and its point
+    beta: torch.Tensor
+    values: List[float]              # g of every iterate, the entry point first
+    grad_alpha: torch.Tensor         # supergradient at the entry point
+    grad_beta: torch.Tensor
 
 
 def _check_parent(parent, split_layer):
@@ -258,6 +270,10 @@ class LayerGraphLP:
         """``kw_bounds`` for several domains in ONE device call (``gnnb_kw_bounds``).  ``items``: [(mask, parent, split_layer), ...] with
         ``parent`` None or (lbs, ubs) as ``kw_bounds`` takes it.  Returns [(lbs, ubs), ...] laid out as ``kw_bounds`` returns them (host
         fp64; post-ReLU entries clamped, flattened entries reshaped)."""
+        return self._kw_device(items)[0]
+
+    def _kw_device(self, items):
+        """``kw_device_bounds`` and what its device call read and wrote: (host lists, KwBoundsResult, (fixed, prop, x_lo, x_hi, masks))."""
         for _, p, s in items:
             _check_parent(p, s)
         if self.engine is None:
@@ -293,7 +309,166 @@ class LayerGraphLP:
                 lbs.append(nl)
                 ubs.append(nu)
             out.append((lbs, ubs))
+        return out, res, (fixed, prop, x_lo, x_hi, masks)
+
+    # ---- dual ascent on the LP: the host twin of gnnb_dual_ascent ---------------------------
+    def _dual_states(self, bounds, mask):
+        """Per ReLU layer (amb, passing, s, t, m) flat: ambiguous = mask -1 and l < 0 < u with the upper relaxation s pre + t,
+        s = u / (u - l), t = -l s; passing = mask 1, or undecided with l >= 0; everything else is blocked."""
+        out = []
+        for r, i in enumerate(self.pre_relu_indices):
+            l, u = bounds[0][i].reshape(-1).double(), bounds[1][i].reshape(-1).double()
+            m = mask[r].reshape(-1)
+            amb = (m == -1) & (l < 0) & (u > 0)
+            passing = (m == 1) | ((m == -1) & (l >= 0))
+            s = torch.where(amb, u / (u - l).clamp(min=1e-300), torch.zeros_like(l))
+            out.append((amb, passing, s, -l * s, m))
         return out
+
+    def _relu_offsets(self):
+        return np.cumsum([0] + [int(np.prod(self.shapes[i + 1])) for i in self.pre_relu_indices])
+
+    def _transpose(self, l, i, nu):
+        """A^T nu for the affine layer ``self.layers[i]`` (nu shaped as its output)."""
+        if type(l) is nn.Linear:
+            return nu @ l.weight.double()
+        hin, win = self.shapes[i][1], self.shapes[i][2]
+        hout, wout = self.shapes[i + 1][1], self.shapes[i + 1][2]
+        opad = (hin - ((hout - 1) * l.stride[0] - 2 * l.padding[0] + l.kernel_size[0]),
+                win - ((wout - 1) * l.stride[1] - 2 * l.padding[1] + l.kernel_size[1]))
+        return F.conv_transpose2d(nu[None], l.weight.double(), None, l.stride, l.padding, output_padding=opad)[0]
+
+    def _affine(self, l, q):
+        if type(l) is nn.Linear:
+            return l.weight.double() @ q + l.bias.double()
+        return F.conv2d(q[None], l.weight.double(), l.bias.double(), l.stride, l.padding)[0]
+
+    def _dual_backward(self, states, alpha, beta):
+        """One backward pass of the dual network in the single direction of the property row.  Returns (g, lams, lam0): the value,
+        the node coefficients lambda of every ReLU layer (flat) and of the input."""
+        off = self._relu_offsets()
+        nu = torch.ones(1, dtype=torch.float64)
+        c = torch.zeros((), dtype=torch.float64)
+        lams = [None] * len(states)
+        r = len(states)
+        for i in range(len(self.layers) - 1, -1, -1):
+            l = self.layers[i]
+            if type(l) in (nn.Conv2d, nn.Linear):
+                b = l.bias.double()
+                c = c + ((nu.sum((1, 2)) * b).sum() if type(l) is nn.Conv2d else nu @ b)
+                nu = self._transpose(l, i, nu)
+            elif type(l) is nn.ReLU:
+                r -= 1
+                amb, passing, s, t, m = states[r]
+                lam = nu.reshape(-1)
+                a, be = alpha[off[r]:off[r + 1]], beta[off[r]:off[r + 1]]
+                pos = lam >= 0                                                   # lambda = 0 takes the alpha branch
+                mu = torch.where(amb, torch.where(pos, lam * a, lam * s), torch.where(passing, lam, torch.zeros_like(lam)))
+                c = c + torch.where(amb & ~pos, lam * t, torch.zeros_like(lam)).sum()
+                mu = mu - torch.where(m == 1, be, torch.zeros_like(be)) + torch.where(m == 0, be, torch.zeros_like(be))
+                lams[r] = lam
+                nu = mu.reshape(nu.shape)
+            else:
+                nu = nu.reshape(self.shapes[i])
+        lam0 = nu.reshape(-1)
+        xl, xu = self.input_lb.reshape(-1), self.input_ub.reshape(-1)
+        c = c + torch.where(lam0 >= 0, lam0 * xl, lam0 * xu).sum()               # lambda_0 = 0 takes x_lo
+        return c, lams, lam0
+
+    def dual_value(self, bounds, mask, alpha, beta):
+        """g(alpha, beta): a lower bound on the property output over the domain for every alpha in [0, 1], beta >= 0 (flat (R,) fp64
+        tensors in ReLU order; beta counts on split nodes only), its maximum the optimum of ``_solve_lp`` on the same bounds.
+        ``bounds`` = (lbs, ubs) as ``kw_bounds`` returns them, split mask applied.  Differentiable: torch autograd of it is the
+        supergradient ``dual_ascent_host`` computes by its forward pass."""
+        return self._dual_backward(self._dual_states(bounds, mask), alpha, beta)[0]
+
+    def _dual_forward(self, states, lams, lam0, alpha, envelope=False):
+        """The forward pass from the inner minimiser x* = (lambda_0 >= 0 ? x_lo : x_hi): per ReLU layer the pre-activation p and the
+        value q handed on -- the linearised ReLU the backward pass chose (alpha p where lambda >= 0, s p + t where lambda < 0; the
+        supergradient's pass) or, with ``envelope``, max(p, 0) in place of alpha p: a point of the relaxation (``dual_recover``).
+        Returns (x*, [p], [q], output)."""
+        off = self._relu_offsets()
+        xs = torch.where(lam0 >= 0, self.input_lb.reshape(-1), self.input_ub.reshape(-1)).reshape(self.shapes[0])
+        q, ps, qs, r = xs, [], [], 0
+        for l in self.layers:
+            if type(l) in (nn.Conv2d, nn.Linear):
+                q = self._affine(l, q)
+            elif type(l) is nn.ReLU:
+                amb, passing, s, t, m = states[r]
+                p, lam = q.reshape(-1), lams[r]
+                low = p.clamp(min=0) if envelope else alpha[off[r]:off[r + 1]] * p
+                v = torch.where(amb, torch.where(lam >= 0, low, s * p + t), torch.where(passing, p, torch.zeros_like(p)))
+                ps.append(p)
+                qs.append(v)
+                q = v.reshape(q.shape)
+                r += 1
+            else:
+                q = q.reshape(-1)
+        return xs, ps, qs, q.reshape(-1)[0]
+
+    def _dual_gradient(self, states, lams, ps):
+        ga = torch.cat([torch.where(amb, lam.clamp(min=0) * p, torch.zeros_like(p)) for (amb, _, _, _, _), lam, p in zip(states, lams, ps)])
+        gb = torch.cat([torch.where(m == 1, -p, torch.where(m == 0, p, torch.zeros_like(p))) for (_, _, _, _, m), p in zip(states, ps)])
+        return ga, gb
+
+    def dual_start(self, bounds, mask, alpha=None, beta=None):
+        """The entry point of the ascent: alpha = u / (u - l) on ambiguous nodes and beta = 0, or the projection of a given point."""
+        states = self._dual_states(bounds, mask)
+        m = torch.cat([st[4] for st in states])
+        if alpha is None:
+            return torch.cat([st[2] for st in states]), torch.zeros(len(m), dtype=torch.float64)
+        return alpha.double().clamp(0, 1), torch.where(m != -1, beta.double().clamp(min=0), torch.zeros(len(m), dtype=torch.float64))
+
+    def dual_ascent_host(self, bounds, mask, n_iter, lr=0.1, alpha=None, beta=None):
+        """Projected Adam ascent on ``dual_value`` in fp64, exactly as k_dual_ascent runs it: n_iter steps (b1 0.9, b2 0.999, eps 1e-8;
+        bias corrections from running products), after each a clamp of alpha to [0, 1] and beta to [0, inf), n_iter + 1 evaluations, the
+        best kept.  Returns a DualAscentHost: bound, alpha, beta (the best point), values (g of every iterate), grad_alpha / grad_beta (the
+        supergradient at the entry point)."""
+        with torch.no_grad():
+            states = self._dual_states(bounds, mask)
+            al, be = self.dual_start(bounds, mask, alpha, beta)
+            ma, va, mb, vb = (torch.zeros_like(al) for _ in range(4))
+            b1, b2, eps = 0.9, 0.999, 1e-8
+            omb1, omb2 = 1.0 - b1, 1.0 - b2
+            b1t = b2t = 1.0
+            best, best_pt, values, g0 = None, None, [], None
+            for it in range(n_iter + 1):
+                g, lams, lam0 = self._dual_backward(states, al, be)
+                g = float(g)
+                values.append(g)
+                if best is None or g > best:
+                    best, best_pt = g, (al.clone(), be.clone())
+                if it == n_iter and it > 0:
+                    break
+                _, ps, _, _ = self._dual_forward(states, lams, lam0, al)
+                ga, gb = self._dual_gradient(states, lams, ps)
+                if it == 0:
+                    g0 = (ga, gb)
+                if it == n_iter:
+                    break
+                b1t, b2t = b1t * b1, b2t * b2
+                ma, va = b1 * ma + omb1 * ga, b2 * va + omb2 * (ga * ga)
+                mb, vb = b1 * mb + omb1 * gb, b2 * vb + omb2 * (gb * gb)
+                al = (al + lr * ((ma / (1.0 - b1t)) / ((va / (1.0 - b2t)).sqrt() + eps))).clamp(0, 1)
+                be = (be + lr * ((mb / (1.0 - b1t)) / ((vb / (1.0 - b2t)).sqrt() + eps))).clamp(min=0)
+            return DualAscentHost(best, best_pt[0], best_pt[1], values, g0[0], g0[1])
+
+    def dual_recover(self, bounds, mask, alpha, beta):
+        """The scorer's inputs at (alpha, beta), fp64, as k_dual_ascent's recovery pass writes them in fp32: dict with x_lp, per ReLU
+        layer pre / post (the forward pass that hands on the ENVELOPE value of every ReLU: a point of the relaxation) and dual (N, 3)
+        (column 1 = alpha max(lambda, 0) >= 0, column 2 = min(lambda, 0) <= 0, zero on decided nodes), out (the property output)."""
+        with torch.no_grad():
+            states = self._dual_states(bounds, mask)
+            off = self._relu_offsets()
+            g, lams, lam0 = self._dual_backward(states, alpha, beta)
+            xs, ps, qs, out = self._dual_forward(states, lams, lam0, alpha, envelope=True)
+            duals = []
+            for r, ((amb, _, _, _, _), lam) in enumerate(zip(states, lams)):
+                d = torch.zeros(len(lam), 3, dtype=torch.float64)
+                d[:, 1] = torch.where(amb, alpha[off[r]:off[r + 1]] * lam.clamp(min=0), torch.zeros_like(lam))
+                d[:, 2] = torch.where(amb, lam.clamp(max=0), torch.zeros_like(lam))
+                duals.append(d)
+            return {"g": float(g), "x_lp": xs, "pre": ps, "post": qs, "dual": duals, "out": float(out), "lam": lams, "lam0": lam0}
 
     def bounds(self, mask, parent=None, split_layer=None):
         _check_parent(parent, split_layer)
@@ -313,15 +488,62 @@ class LayerGraphLP:
         lbs, ubs = self.bounds(mask, pb, split_layer)
         return self._solve_lp(mask, lbs, ubs)
 
-    def solve_many(self, items):
+    def solve_many(self, items, lp="highs", n_iter=100, lr=0.1):
         """``solve`` for several domains: [(mask, parent, split_layer), ...] -> [Subproblem or None, ...].  With ``bounds="kw_device"``
-        the bounds of all of them come from one device call; the LPs run one after the other."""
+        the bounds of all of them come from one device call; the LPs run one after the other.  ``lp="dual_device"``: no LP at all --
+        the bounds of the whole list from one ``gnnb_kw_bounds`` call, then ``n_iter`` steps of dual ascent on every domain in one
+        ``gnnb_dual_ascent`` call (a child starts from its parent's point when every parent has one); ``lb`` is the best dual value (a
+        sound bound, at or below the LP optimum), the primal / dual point the ascent's recovery pass, ``ub`` the real network at its
+        ``x_lp``.  A domain with crossed bounds is None, as in ``solve``."""
+        if lp not in ("highs", "dual_device"):
+            raise ValueError(lp)
+        parents = [parent for _, parent, _ in items]
         items = [([m.clone() for m in mask], None if parent is None else parent.bounds64, split) for mask, parent, split in items]
+        if lp == "dual_device":
+            return self._solve_dual_device(items, parents, n_iter, lr)
         if self.bound_mode == "kw_device":
             bounds = self.kw_device_bounds(items)
         else:
             bounds = [self.bounds(mask, pb, split) for mask, pb, split in items]
         return [self._solve_lp(mask, lbs, ubs) for (mask, _, _), (lbs, ubs) in zip(items, bounds)]
+
+    def _solve_dual_device(self, items, parents, n_iter, lr):
+        bounds, res, (fixed, prop, x_lo, x_hi, masks) = self._kw_device(items)
+        alpha = beta = None
+        if all(p is not None and p.dual_point is not None for p in parents):
+            alpha, beta = (torch.stack([p.dual_point[i] for p in parents]) for i in (0, 1))
+        da = self.engine.dual_ascent(fixed, prop, x_lo, x_hi, masks, res.lb, res.ub, n_iter, lr, alpha, beta, want_scorer_inputs=True)
+        bound, al, be, x_lp = da.bound.cpu(), da.alpha.cpu(), da.beta.cpu(), da.x_lp.cpu()
+        B = len(items)
+        duals = [d.cpu().reshape(B, -1, 3) for d in da.dual]
+        prims = [p.cpu() for p in da.primals]
+        with torch.no_grad():
+            act = x_lp
+            for l in self.layers:
+                act = l(act)
+        ubs_real = act.reshape(B)
+        out = []
+        for b, ((mask, _, _), (lbs, ubs)) in enumerate(zip(items, bounds)):
+            if any(bool((lo > up + 1e-9).any()) for lo, up in zip(lbs, ubs)):
+                out.append(None)
+                continue
+            primals = []
+            for q, l in enumerate(self.layers[:-1]):
+                if type(l) is nn.ReLU or type(self.layers[q + 1]) is nn.ReLU:
+                    primals.append(prims[q].reshape(B, -1)[b].tolist())
+                else:                                                # Flatten behind a ReLU: the same values
+                    primals.append(list(primals[-1]) if primals and _is_flatten(l) else [0.0] * int(np.prod(self.shapes[q + 1])))
+            primals.append([float(prims[-1][b])])
+            for r, i in enumerate(self.pre_relu_indices):            # bounds decide what the split mask left open, as in _solve_lp
+                m, lo, up = mask[r].reshape(-1), lbs[i].reshape(-1), ubs[i].reshape(-1)
+                m = torch.where((m == -1) & (lo >= 0), torch.ones_like(m), m)
+                mask[r] = torch.where((m == -1) & (up <= 0), torch.zeros_like(m), m).reshape(mask[r].shape)
+            lower_all = [t.float() for t in lbs]
+            upper_all = [t.float() for t in ubs]
+            lower_all[-1] = torch.tensor([float(bound[b])])
+            out.append(Subproblem(float(bound[b]), float(ubs_real[b]), x_lp[b:b + 1].reshape((1,) + self.shapes[0]), lower_all, upper_all,
+                                  [d[b] for d in duals], primals, mask, (lbs, ubs), (al[b], be[b])))
+        return out
 
     def _solve_lp(self, mask, lbs, ubs):
         """The LP of ``solve`` on given bounds (``mask``: the caller's copy, resolved in place)."""
@@ -485,7 +707,7 @@ def branch_and_bound(lp, scorer, layers, eps=1e-4, max_nodes=200, decision_bound
 
 
 def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_branches=50, decision_bound=None, branching_threshold=0.2,
-                               kwbd_threshold=10, sparsest_layer=0, log=print, dump=None):
+                               kwbd_threshold=10, sparsest_layer=0, log=print, dump=None, child_lp="highs"):
     """The BaB loop of plnn/relu_conv_gnnkwthreshold.py:126-262 WITH its control flow (the loop `bab_mip.py --bab_gnn` runs): branch on the
     GNN's decision and bound its two children (:143-146); when the GNN's improvement of the bound (:151) is below ``branching_threshold``
     (:155) ask the BaBSR heuristic (``choose_node_conv``, :157), skip a KW point that was inefficient ``kwbd_threshold`` times (:160-167),
@@ -502,8 +724,12 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
     GNN improvement 1.0 instead of the reference's division by ``-2 * lower_bound`` (with ``decision_bound`` = 0 such a domain is never
     added, :226 / :235); infeasible children count as lower bound +inf (Gurobi reports them infeasible too; the reference has no such branch
     because its children inherit feasible parents' bounds); without a ``decision_bound`` leaves closed at optimality keep the minimum honest.
+    ``child_lp``: how ``bound_children`` bounds a pair of children -- "highs" (their LPs) or "dual_device" (``solve_many(lp="dual_device")``:
+    bounds and dual ascent of both on the GPU, no LP; the root is still an LP).
     Returns (global_lb, global_ub, LP solves, branches, branches that bounded a KW decision, branches that used it)."""
     from .bab_caller import gnn_improvement, resolve_branching, trace_line
+    if child_lp not in ("highs", "dual_device"):
+        raise ValueError(child_lp)
     fixed = {"fixed_layers": list(layers[:-1]), "prop_layers": [layers[-1]]}
     n_relu = len(lp.pre_relu_indices)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
@@ -517,13 +743,13 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
     ineff_kw_dc, closed_lb = {}, float("inf")
 
     def bound_children(dom, decision):
-        if getattr(lp, "bound_mode", None) == "kw_device":     # both children's bounds in one device call, then their LPs
+        if child_lp == "dual_device" or getattr(lp, "bound_mode", None) == "kw_device":     # both children's bounds in one device call, then their LPs
             items = []
             for choice in (0, 1):
                 m = [t.clone() for t in dom.mask]
                 m[decision[0]][decision[1]] = choice
                 items.append((m, dom, decision[0]))
-            return lp.solve_many(items)
+            return lp.solve_many(items, lp=child_lp)
         out = []
         for choice in (0, 1):
             m = [t.clone() for t in dom.mask]

@@ -194,6 +194,49 @@ size_t gnnb_kw_workspace_bytes(const gnnb_t* h, int B);
 int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32, float* const* ub32,
                    int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Lower bounds of B BaB domains by dual ascent on their LP relaxation, fp64 -- stands in for the LP the reference builds and solves
+ * with Gurobi (plnn/conv_kwinter_gen.py:179-555: build_the_model, its optimum and the primal / dual point GraphChoice.decision reads)
+ * wherever the optimum is wanted to a few digits; restated on the host by gnn_branching_amd/lp_producer.py LayerGraphLP.dual_value /
+ * dual_ascent_host / dual_recover.  With the intermediate bounds of gnnb_kw_bounds fixed, the LP's dual is the
+ * Wong-Kolter dual network with a free slope alpha in [0, 1] on the lower relaxation of every ambiguous ReLU (mask -1, l < 0 < u) and
+ * one multiplier beta >= 0 per split node (mask 0 / 1).  Every (alpha, beta) gives a sound lower bound g on the property output; the
+ * maximum is the LP optimum.  One workgroup per domain runs n_iter steps of projected Adam (ascent; b1 0.9, b2 0.999, eps 1e-8, step
+ * lr) on the exact supergradient, n_iter + 1 evaluations of g, and keeps the best.  A domain's result does not depend on B or on its
+ * place in the batch.
+ * All pointers inside the struct are DEVICE pointers; the tables lb / ub are HOST arrays of n_graph-1 device pointers. */
+typedef struct {
+  const double* const* lb;            /* graph layers 1..L+1 (B, N_k) as gnnb_kw_bounds writes them (mask applied); layer L+1 is not read */
+  const double* const* ub;
+  const double* x_lo;                 /* input box (B, N_0)                                                          */
+  const double* x_hi;
+  const float* prop_w;                /* property layers as in gnnb_batch: (B, N_L) and (B)                          */
+  const float* prop_b;
+  const int8_t* mask;                 /* BaB mask (B, R) in flat ReLU order: -1 undecided, 0 blocked, 1 passing     */
+  int32_t n_graph;                    /* L + 2                                                                       */
+} gnnb_dual_batch;
+
+/* Bytes of device workspace gnnb_dual_ascent needs for a batch of B (0 for a null or unbound handle). */
+size_t gnnb_dual_workspace_bytes(const gnnb_t* h, int B);
+
+/* alpha / beta: device (B, R) fp64, flat ReLU order, in and out.  warm = 0: the start is alpha = u / (u - l), beta = 0 (g there is the
+ * property-layer lower bound gnnb_kw_bounds computes before its interval intersection); warm = 1: the start is what the arrays hold
+ * (a child starts from its parent's point), projected onto alpha in [0, 1], beta >= 0, beta = 0 on unsplit nodes.  On return they hold
+ * the best point met and bound (B) its value g; n_iter = 0 evaluates g at the start.  alpha of a node that is not ambiguous is ignored.
+ * grad_alpha / grad_beta: both NULL, or (B, R): the supergradient at the start (inspection, tests).
+ * dual / primal / x_lp: all NULL, or the scorer's inputs at the best point, fp32, laid out as gnnb_batch's (dual: n_relu pointers (B N_k, 3);
+ * primal: n_primal pointers, of which the pre- and post-activation of every ReLU layer and primals[-1] must be given and are written,
+ * any other entry may be NULL; x_lp (B, N_0)): the minimiser x* of the inner problem, the pre-activations and the ReLU ENVELOPE values of
+ * the forward pass from it (max(pre, 0) where the node's dual coefficient lambda >= 0, s pre + t where lambda < 0), the property output
+ * there, and dual[:, 0] = 0, dual[:, 1] = alpha max(lambda, 0) >= 0 (Pi of v >= pre), dual[:, 2] = min(lambda, 0) <= 0 (Pi of
+ * v <= s pre + t), zero on decided nodes -- the sign convention of the reference's Pi.  gnnb_forward reads them without a host round trip.
+ * lb32_prop: NULL, or (B) fp32: the bound, e.g. the property entry of gnnb_kw_bounds' lb32 table (where the reference puts the LP optimum).
+ * Stream-ordered, no allocation, no synchronisation; the workspace needs no initialisation.  GNNB_E_INVALID for a null handle, B < 1,
+ * n_iter < 0 or a network whose widest ReLU layer exceeds 4096 nodes (refused before a launch: two fp64 buffers of it live in LDS);
+ * GNNB_E_NOMEM for a short workspace; GNNB_E_STATE before gnnb_bind_network. */
+int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int n_iter, double lr, double* alpha, double* beta, int warm,
+                     double* bound, double* grad_alpha, double* grad_beta, float* const* dual, float* const* primal, float* x_lp,
+                     float* lb32_prop, void* workspace, size_t workspace_bytes, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
