@@ -211,7 +211,8 @@ struct gnnb_handle {
   int zero_tap[3] = {0, 0, 0};   // {k, y, x}: inner conv edge k leaves pixel (y, x) of layer k-1 without a tap (k = 0: none); set by gnnb_bind_network
   std::vector<Edge> edges;       // edges[k], k = 1..L (edges[0] unused)
   std::vector<DevEdge> dev;
-  std::vector<double*> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for gnnb_kw_bounds, k = 1..L (made by bind)
+  std::vector<double*> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for the fp64 kernels, k = 1..L (made by bind)
+  KwNet kw_net{};                   // the bound network as gnnb_kw_bounds / gnnb_dual_ascent pass it to their kernels (made by bind)
   std::vector<int> N;            // graph layer sizes, N[0..L+1]
   std::vector<int> relu_q;       // fixed-layer index of the ReLU of graph layer k
   std::vector<int> hw;           // nodes per bias entry of layer k
@@ -443,6 +444,7 @@ static void free_network(gnnb_t* h) {
       if (p) (void)hipFree(p);
   h->kw_w.clear();
   h->kw_b.clear();
+  h->kw_net = KwNet{};
   h->gf.clear();
   h->gb.clear();
   h->dev.clear();
@@ -595,7 +597,7 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
     const Edge& e = h->edges[k];
     DevEdge& d = h->dev[k];
     if (int rc = upload(&d.bias, e.b.data(), e.b.size())) return rc;
-    {                                   // fp64 copies for gnnb_kw_bounds (fp32 -> fp64 is exact)
+    {                                   // fp64 copies for the fp64 kernels (fp32 -> fp64 is exact); KwNet below points at them
       std::vector<double> w64(e.w.begin(), e.w.end()), b64(e.b.begin(), e.b.end());
       if (int rc = upload64(&h->kw_w[k], w64.data(), w64.size())) return rc;
       if (int rc = upload64(&h->kw_b[k], b64.data(), b64.size())) return rc;
@@ -697,6 +699,24 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
                   "{3, 8, 16, 32}", k, e.c_in, e.c_out);
   }
   h->zero_tap[0] = zero_tap_layer(h, &h->zero_tap[1], &h->zero_tap[2]);
+  // the description the fp64 kernels share (gnnb_k_kw.h KwNet): sizes, flat ReLU offsets, every layer as (C, H, W), the fixed edges
+  KwNet& net = h->kw_net;
+  net.L = Lr; net.R = h->R;
+  for (int k = 0; k <= Lr + 1; ++k) net.N[k] = h->N[k];
+  for (int k = 1; k <= Lr; ++k) {
+    net.off[k] = net.off[k - 1] + (k > 1 ? h->N[k - 1] : 0);
+    net.maxNr = std::max(net.maxNr, h->N[k]);
+    KwEdge& E = net.e[k];
+    static_cast<EdgeGeom&>(E) = h->edges[k];
+    E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0;
+  }
+  for (int k = 0; k <= Lr; ++k) {
+    const Edge& e = h->edges[k == 0 ? 1 : k];
+    const bool conv = e.kind == 0;
+    net.lc[k] = conv ? (k == 0 ? e.c_in : e.c_out) : h->N[k];
+    net.lh[k] = conv ? (k == 0 ? e.h_in : e.h_out) : 1;
+    net.lw[k] = conv ? (k == 0 ? e.w_in : e.w_out) : 1;
+  }
   h->bound = true;
   return GNNB_OK;
 }
@@ -1779,7 +1799,8 @@ extern "C" int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const*
 
 // ================================================================================================================
 // Wong-Kolter intermediate bounds of a batch of BaB domains (gnnb_k_kw.h; lp_producer.py LayerGraphLP.kw_bounds, reference
-// plnn/dual_network_linear_approximation.py init_kw_bounds :205-294 / update_kw_bounds :296-451)
+// plnn/dual_network_linear_approximation.py init_kw_bounds :205-294 / update_kw_bounds :296-451).  The network itself -- sizes, ReLU offsets,
+// layer shapes, edge geometry, fp64 weights -- is the handle's KwNet, made by gnnb_bind_network; a call adds only its own pointers.
 // ================================================================================================================
 struct KwWs { size_t pw, total; };      // byte offsets in the workspace: (d, -d l) pairs at 0, then the fp64 property layers
 static KwWs kw_ws_layout(const gnnb_t* h, int B) {
@@ -1795,56 +1816,44 @@ extern "C" size_t gnnb_kw_workspace_bytes(const gnnb_t* h, int B) {
   return kw_ws_layout(h, B).total;
 }
 
+// What gnnb_kw_bounds and gnnb_dual_ascent check before anything else: the handle, the bound network (1..MAXL ReLU layers, as many graph
+// layers as the caller's batch says: n_graph points into it) and the LDS their kernels need for two buffers of the widest ReLU layer.
+// *lds: that size in bytes.
+static int kw_preflight(const gnnb_t* h, const char* who, const int* n_graph, size_t* lds) {
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!h->bound) return fail(GNNB_E_STATE, "%s: call gnnb_bind_network first", who);
+  if (!n_graph) return fail(GNNB_E_INVALID, "%s: null batch", who);
+  const KwNet& net = h->kw_net;
+  if (*n_graph != net.L + 2) return fail(GNNB_E_INVALID, "%s: %d graph layers given, network has %d", who, *n_graph, net.L + 2);
+  if (net.L < 1 || net.L > MAXL) return fail(GNNB_E_INVALID, "%s: %d ReLU layers (1..%d)", who, net.L, MAXL);
+  *lds = kw_lds_doubles(net.maxNr) * sizeof(double);
+  if (*lds > 65536)
+    return fail(GNNB_E_INVALID, "%s: a ReLU layer of %d nodes needs %zu bytes of LDS for the dual pass (64 KiB at most)", who, net.maxNr, *lds);
+  return GNNB_OK;
+}
+
 extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32,
                               float* const* ub32, int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null handle");
-  if (!h->bound) return fail(GNNB_E_STATE, "gnnb_kw_bounds: call gnnb_bind_network first");
-  if (!in || !lb || !ub || !infeasible || !workspace || B < 1 || B > 65535)
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, "gnnb_kw_bounds", in ? &in->n_graph : nullptr, &lds)) return rc;
+  if (!lb || !ub || !infeasible || !workspace || B < 1 || B > 65535)      // (65535: k_kw_layer's grid is (N_k, B))
     return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null argument or batch size %d outside 1..65535", B);
-  const int K = (int)h->N.size() - 1, L = K - 1;         // graph layers 0..K, K = L + 1 the property node
-  if (in->n_graph != K + 1) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: %d graph layers given, network has %d", in->n_graph, K + 1);
   if (!in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null input pointer");
   if ((in->parent_lb == nullptr) != (in->parent_ub == nullptr) || (in->parent_lb && !in->split_layer))
     return fail(GNNB_E_INVALID, "gnnb_kw_bounds: parent bounds need both tables and split_layer");
   if ((lb32 == nullptr) != (ub32 == nullptr)) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: lb32 and ub32 go together");
-  int maxNr = 0;
-  for (int k = 1; k <= L; ++k) maxNr = std::max(maxNr, h->N[k]);
-  const size_t lds = kw_lds_doubles(maxNr) * sizeof(double);
-  if (lds > 65536)
-    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: a ReLU layer of %d nodes needs %zu bytes of LDS for the dual pass (64 KiB at most)", maxNr, lds);
   const KwWs ws = kw_ws_layout(h, B);
   if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_kw_bounds: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
   KwArgs a{};
-  a.L = L; a.R = h->R; a.B = B; a.maxNr = maxNr;
-  int off = 0;
-  for (int k = 0; k <= K; ++k) {
-    a.N[k] = h->N[k];
-    if (k >= 1 && k <= L) { a.off[k] = off; off += h->N[k]; }
-  }
-  for (int k = 0; k <= L; ++k) {                          // graph layer k as (C, H, W)
-    const Edge& e = h->edges[k == 0 ? 1 : k];
-    const bool conv = e.kind == 0;
-    a.lc[k] = conv ? (k == 0 ? e.c_in : e.c_out) : h->N[k];
-    a.lh[k] = conv ? (k == 0 ? e.h_in : e.h_out) : 1;
-    a.lw[k] = conv ? (k == 0 ? e.w_in : e.w_out) : 1;
-  }
+  a.net = h->kw_net;
+  a.B = B;
+  const int L = a.net.L, K = L + 1, NL = a.net.N[L];      // graph layers 0..K, K the property node
   for (int k = 1; k <= K; ++k) {
     if (!lb[k - 1] || !ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null output pointer for graph layer %d", k);
     a.lb[k] = lb[k - 1]; a.ub[k] = ub[k - 1];
     if (in->parent_lb) {
       if (!in->parent_lb[k - 1] || !in->parent_ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null parent pointer for graph layer %d", k);
       a.plb[k] = in->parent_lb[k - 1]; a.pub[k] = in->parent_ub[k - 1];
-    }
-    KwEdge& E = a.e[k];
-    if (k <= L) {
-      const Edge& e = h->edges[k];
-      E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0; E.kind = e.kind;
-      E.c_in = e.c_in; E.h_in = e.h_in; E.w_in = e.w_in; E.c_out = e.c_out; E.h_out = e.h_out; E.w_out = e.w_out;
-      E.kh = e.kh; E.kw = e.kw; E.stride = e.stride; E.pad = e.pad; E.n_in = e.n_in; E.n_out = e.n_out;
-    } else {                                              // the property layer: per-domain Linear(N_L, 1), fp64 copy in the workspace
-      const double* pw = (const double*)((char*)workspace + ws.pw);
-      E.w = pw; E.bias = pw + h->N[L]; E.wb = E.bb = h->N[L] + 1; E.kind = 1;
-      E.n_in = h->N[L]; E.n_out = 1;
     }
   }
   for (int k = 0; k <= K; ++k)
@@ -1856,14 +1865,17 @@ extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double*
   a.split = in->parent_lb ? in->split_layer : nullptr;
   a.dg = (double*)workspace;
   a.pw = (double*)((char*)workspace + ws.pw);
+  KwEdge& P = a.net.e[K];                                 // the property layer: per-domain Linear(N_L, 1), fp64 copy in this call's workspace
+  P.w = a.pw; P.bias = a.pw + NL; P.wb = P.bb = NL + 1; P.kind = 1;
+  P.n_in = NL; P.n_out = 1;
   a.infeasible = infeasible;
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  const int span = std::max(std::max(h->N[0], h->N[1]), h->N[L] + 1);
+  const int span = std::max(std::max(a.net.N[0], a.net.N[1]), NL + 1);
   const long nthreads = (long)span * B;
   run.run(PC_KW_FIRST, [&] { hipLaunchKernelGGL(k_kw_first, dim3((unsigned)((nthreads + KW_THREADS - 1) / KW_THREADS)), dim3(KW_THREADS), 0, st, a, span); });
   for (int k = 2; k <= K; ++k)
-    run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(h->N[k], B), dim3(KW_THREADS), lds, st, a, k); });
+    run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(a.net.N[k], B), dim3(KW_THREADS), lds, st, a, k); });
   run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
   return run.rc;
 }
@@ -1881,42 +1893,25 @@ extern "C" size_t gnnb_dual_workspace_bytes(const gnnb_t* h, int B) {
 extern "C" int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int n_iter, double lr, double* alpha, double* beta, int warm,
                                 double* bound, double* grad_alpha, double* grad_beta, float* const* dual, float* const* primal, float* x_lp,
                                 float* lb32_prop, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null handle");
-  if (!h->bound) return fail(GNNB_E_STATE, "gnnb_dual_ascent: call gnnb_bind_network first");
-  if (!in || !alpha || !beta || !bound || !workspace || B < 1 || n_iter < 0)
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, "gnnb_dual_ascent", in ? &in->n_graph : nullptr, &lds)) return rc;
+  if (!alpha || !beta || !bound || !workspace || B < 1 || n_iter < 0)
     return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null argument, batch size %d < 1 or %d iterations", B, n_iter);
-  const int K = (int)h->N.size() - 1, L = K - 1;
-  if (in->n_graph != K + 1) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: %d graph layers given, network has %d", in->n_graph, K + 1);
   if (!in->lb || !in->ub || !in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask)
     return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null input pointer");
   if ((grad_alpha == nullptr) != (grad_beta == nullptr)) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: grad_alpha and grad_beta go together");
   if ((dual == nullptr) != (primal == nullptr) || (dual == nullptr) != (x_lp == nullptr))
     return fail(GNNB_E_INVALID, "gnnb_dual_ascent: dual, primal and x_lp go together");
-  if (L < 1 || L > MAXL) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: %d ReLU layers (1..%d)", L, MAXL);
-  int maxNr = 0;
-  for (int k = 1; k <= L; ++k) maxNr = std::max(maxNr, h->N[k]);
-  const size_t lds = kw_lds_doubles(maxNr) * sizeof(double);
-  if (lds > 65536)
-    return fail(GNNB_E_INVALID, "gnnb_dual_ascent: a ReLU layer of %d nodes needs %zu bytes of LDS for the dual pass (64 KiB at most)", maxNr, lds);
   const size_t need = gnnb_dual_workspace_bytes(h, B);
   if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "gnnb_dual_ascent: workspace %zu bytes, need %zu", workspace_bytes, need);
   DualArgs a{};
-  a.L = L; a.R = h->R; a.maxNr = maxNr; a.n_iter = n_iter; a.warm = warm ? 1 : 0; a.lr = lr;
-  int off = 0;
-  a.N[0] = h->N[0];
-  for (int k = 1; k <= L; ++k) {
+  a.net = h->kw_net;
+  a.n_iter = n_iter; a.warm = warm ? 1 : 0; a.lr = lr;
+  for (int k = 1; k <= a.net.L; ++k) {
     if (!in->lb[k - 1] || !in->ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null bounds pointer for graph layer %d", k);
-    const Edge& e = h->edges[k];
     const int q = h->relu_q[k];
     if (dual && (!dual[k - 1] || !primal[q - 1] || !primal[q])) return fail(GNNB_E_INVALID, "gnnb_dual_ascent: null scorer array (layer %d)", k);
-    a.N[k] = h->N[k]; a.off[k] = off; off += h->N[k];
-    a.lh[k] = e.kind == 0 ? e.h_out : 1;
-    a.lw[k] = e.kind == 0 ? e.w_out : 1;
     a.lb[k] = in->lb[k - 1]; a.ub[k] = in->ub[k - 1];
-    KwEdge& E = a.e[k];
-    E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0; E.kind = e.kind;
-    E.c_in = e.c_in; E.h_in = e.h_in; E.w_in = e.w_in; E.c_out = e.c_out; E.h_out = e.h_out; E.w_out = e.w_out;
-    E.kh = e.kh; E.kw = e.kw; E.stride = e.stride; E.pad = e.pad; E.n_in = e.n_in; E.n_out = e.n_out;
     if (dual) { a.dual[k] = dual[k - 1]; a.z_pre[k] = primal[q - 1]; a.z_post[k] = primal[q]; }
   }
   if (dual) {
@@ -1926,7 +1921,7 @@ extern "C" int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int
   a.x_lo = in->x_lo; a.x_hi = in->x_hi; a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.mask = in->mask;
   a.alpha = alpha; a.beta = beta; a.bound = bound; a.grad_alpha = grad_alpha; a.grad_beta = grad_beta;
   a.x_lp = x_lp; a.lb32_prop = lb32_prop;
-  a.ws = (double*)workspace; a.ws_stride = (long)dual_ws_doubles(h->R, h->N[0]);
+  a.ws = (double*)workspace; a.ws_stride = (long)dual_ws_doubles(a.net.R, a.net.N[0]);
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
   run.run(PC_DUAL, [&] { hipLaunchKernelGGL(k_dual_ascent, dim3(B), dim3(DUAL_THREADS), lds, st, a); });

@@ -25,10 +25,8 @@
 #define DUAL_THREADS KW_THREADS
 
 struct DualArgs {
-  KwEdge e[MAXL + 2];                                   // e[k]: the map into graph layer k, k = 1..L (the property layer is read as prop_w / prop_b)
-  int N[MAXL + 2], off[MAXL + 2];                       // as KwArgs
-  int lh[MAXL + 2], lw[MAXL + 2];                       // graph layer k as (., H, W), k = 1..L
-  int L, R, maxNr, n_iter, warm;
+  KwNet net;                                            // e[k], k = 1..L, and graph layers 0..L (the property layer is read as prop_w / prop_b)
+  int n_iter, warm;
   double lr;
   const double* lb[MAXL + 2]; const double* ub[MAXL + 2];   // pre-activation bounds of graph layers 1..L, (B, N_k), mask applied
   const double* x_lo; const double* x_hi;               // (B, N_0)
@@ -41,6 +39,7 @@ struct DualArgs {
   float* z_out; float* x_lp; float* lb32_prop;          // (B), (B, N_0), (B)
   double* ws; long ws_stride;                           // workspace, ws_stride doubles per domain (dual_ws_doubles)
 };
+static_assert(sizeof(KwArgs) <= 4096 && sizeof(DualArgs) <= 4096, "kernel arguments are passed by value: HIP's limit is 4 KiB");
 
 // per domain, in doubles: lambda (R), x* (N_0), Adam's first and second moments of alpha and beta (4 R), the best (alpha, beta) (2 R)
 static inline size_t dual_ws_doubles(int R, int N0) { return (size_t)7 * R + N0; }
@@ -52,41 +51,26 @@ __device__ __forceinline__ int dual_state(int m, double l, double u, double& s, 
   if (m == 0) return 2;
   if (l >= 0.0) return 1;
   if (!(u > 0.0)) return 2;
-  s = u / fmax(u - l, 1e-300);
-  t = -l * s;
+  kw_relax(l, u, s, t);
   return 0;
-}
-
-// fixed tree over the workgroup's partials; red: DUAL_THREADS doubles of LDS nobody else is using (synchronises before and after)
-__device__ __forceinline__ double dual_reduce(double* red, double v, int tid) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = DUAL_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
 }
 
 // g(alpha, beta) of domain b; leaves lambda_k of every ReLU node and the minimiser x* in the workspace
 __device__ double dual_backward(const DualArgs& a, int b, int tid, double* lds, double* lam_ws, double* xs) {
   double* cur = lds;
-  double* nxt = lds + a.maxNr;
-  const double* al = a.alpha + (long)b * a.R;
-  const double* be = a.beta + (long)b * a.R;
-  const int8_t* mask = a.mask + (long)b * a.R;
+  double* nxt = lds + a.net.maxNr;
+  const double* al = a.alpha + (long)b * a.net.R;
+  const double* be = a.beta + (long)b * a.net.R;
+  const int8_t* mask = a.mask + (long)b * a.net.R;
   double c = tid == 0 ? (double)a.prop_b[b] : 0.0;
-  for (int k = a.L; k >= 1; --k) {
-    const KwEdge& E = a.e[k];
-    const int Nk = a.N[k], hw = E.kind == 0 ? E.h_out * E.w_out : 1;
+  for (int k = a.net.L; k >= 1; --k) {
+    const KwEdge& E = a.net.e[k];
+    const int Nk = a.net.N[k], hw = E.kind == 0 ? E.h_out * E.w_out : 1;
     const double* lo = a.lb[k] + (long)b * Nk;
     const double* up = a.ub[k] + (long)b * Nk;
     for (int j = tid; j < Nk; j += DUAL_THREADS) {
-      const int r = a.off[k] + j, m = mask[r];
-      const double lam = k == a.L ? (double)a.prop_w[(long)b * Nk + j] : cur[j];
+      const int r = a.net.off[k] + j, m = mask[r];
+      const double lam = k == a.net.L ? (double)a.prop_w[(long)b * Nk + j] : cur[j];
       double s, t, mu;
       const int st = dual_state(m, lo[j], up[j], s, t);
       if (st == 0) {
@@ -102,7 +86,7 @@ __device__ double dual_backward(const DualArgs& a, int b, int tid, double* lds, 
       cur[j] = mu;
     }
     __syncthreads();
-    const int Nin = a.N[k - 1], y1 = a.lh[k] - 1, x1 = a.lw[k] - 1;
+    const int Nin = a.net.N[k - 1], y1 = a.net.lh[k] - 1, x1 = a.net.lw[k] - 1;
     if (k > 1) {
       for (int m = tid; m < Nin; m += DUAL_THREADS) nxt[m] = kw_transpose_at(E, 0, m, cur, 0, y1, 0, x1);
       double* t = cur; cur = nxt; nxt = t;
@@ -118,7 +102,8 @@ __device__ double dual_backward(const DualArgs& a, int b, int tid, double* lds, 
       }
     }
   }
-  return dual_reduce(lds, c, tid);
+  kw_block_sum<1>(lds, &c, tid);
+  return c;
 }
 
 // (A_k q)_j of a conv edge, one thread per node
@@ -143,13 +128,13 @@ enum { DUAL_STEP = 1, DUAL_GRAD = 2, DUAL_RECOVER = 4 };
 
 // node j of ReLU layer k with pre-activation p: what the forward pass leaves behind; returns q_k[j]
 __device__ __forceinline__ double dual_node(const DualArgs& a, int b, int k, int j, double p, int what, double bc1, double bc2) {
-  const int r = a.off[k] + j;
-  const long at = (long)b * a.R + r;
+  const int r = a.net.off[k] + j;
+  const long at = (long)b * a.net.R + r;
   double* ws = a.ws + (long)b * a.ws_stride;
   const int m = a.mask[at];
   const double lam = ws[r];
   double s, t;
-  const int st = dual_state(m, a.lb[k][(long)b * a.N[k] + j], a.ub[k][(long)b * a.N[k] + j], s, t);
+  const int st = dual_state(m, a.lb[k][(long)b * a.net.N[k] + j], a.ub[k][(long)b * a.net.N[k] + j], s, t);
   const double al = a.alpha[at];
   double q = st == 1 ? p : 0.0;
   if (st == 0) q = lam >= 0.0 ? al * p : s * p + t;
@@ -161,17 +146,17 @@ __device__ __forceinline__ double dual_node(const DualArgs& a, int b, int k, int
   }
   if (what & DUAL_STEP) {
     const double b1 = 0.9, b2 = 0.999, omb1 = 1.0 - b1, omb2 = 1.0 - b2, eps = 1e-8;
-    double* mom = ws + a.R + a.N[0];                    // m_alpha, v_alpha, m_beta, v_beta: R doubles each
-    const double ma = b1 * mom[r] + omb1 * ga, va = b2 * mom[a.R + r] + omb2 * (ga * ga);
-    const double mb = b1 * mom[2 * a.R + r] + omb1 * gb, vb = b2 * mom[3 * a.R + r] + omb2 * (gb * gb);
-    mom[r] = ma; mom[a.R + r] = va; mom[2 * a.R + r] = mb; mom[3 * a.R + r] = vb;
+    double* mom = ws + a.net.R + a.net.N[0];                    // m_alpha, v_alpha, m_beta, v_beta: R doubles each
+    const double ma = b1 * mom[r] + omb1 * ga, va = b2 * mom[a.net.R + r] + omb2 * (ga * ga);
+    const double mb = b1 * mom[2 * a.net.R + r] + omb1 * gb, vb = b2 * mom[3 * a.net.R + r] + omb2 * (gb * gb);
+    mom[r] = ma; mom[a.net.R + r] = va; mom[2 * a.net.R + r] = mb; mom[3 * a.net.R + r] = vb;
     a.alpha[at] = fmin(fmax(al + a.lr * ((ma / bc1) / (sqrt(va / bc2) + eps)), 0.0), 1.0);
     a.beta[at] = fmax(a.beta[at] + a.lr * ((mb / bc1) / (sqrt(vb / bc2) + eps)), 0.0);
   }
   if (what & DUAL_RECOVER) {
     if (st == 0 && lam >= 0.0) q = fmax(p, 0.0);        // the envelope value, not the linearised one
     if (a.dual[k]) {
-      const long n = (long)b * a.N[k] + j;
+      const long n = (long)b * a.net.N[k] + j;
       a.z_pre[k][n] = (float)p;
       a.z_post[k][n] = (float)q;
       a.dual[k][3 * n] = 0.0f;
@@ -185,11 +170,11 @@ __device__ __forceinline__ double dual_node(const DualArgs& a, int b, int k, int
 // the forward pass at the point the last dual_backward evaluated (its lambda and x* are in the workspace)
 __device__ void dual_forward(const DualArgs& a, int b, int tid, double* lds, const double* xs, int what, double bc1, double bc2) {
   double* cur = lds;
-  double* nxt = lds + a.maxNr;
+  double* nxt = lds + a.net.maxNr;
   const int lane = tid & 63, wave = tid >> 6;
-  for (int k = 1; k <= a.L; ++k) {
-    const KwEdge& E = a.e[k];
-    const int Nk = a.N[k];
+  for (int k = 1; k <= a.net.L; ++k) {
+    const KwEdge& E = a.net.e[k];
+    const int Nk = a.net.N[k];
     const double* q = k == 1 ? xs : cur;
     double* out = k == 1 ? cur : nxt;
     if (E.kind == 0) {
@@ -208,12 +193,12 @@ __device__ void dual_forward(const DualArgs& a, int b, int tid, double* lds, con
     __syncthreads();
   }
   if (what & DUAL_RECOVER) {
-    const int NL = a.N[a.L], N0 = a.N[0];
+    const int NL = a.net.N[a.net.L], N0 = a.net.N[0];
     double part = 0.0;
     for (int j = tid; j < NL; j += DUAL_THREADS) part += (double)a.prop_w[(long)b * NL + j] * cur[j];
-    const double o = dual_reduce(lds, part, tid);       // (every thread has read its q before the buffer becomes the tree's)
+    kw_block_sum<1>(lds, &part, tid);                   // (every thread has read its q before the buffer becomes the tree's)
     if (a.dual[1]) {
-      if (tid == 0) a.z_out[b] = (float)(o + (double)a.prop_b[b]);
+      if (tid == 0) a.z_out[b] = (float)(part + (double)a.prop_b[b]);
       for (int m = tid; m < N0; m += DUAL_THREADS) a.x_lp[(long)b * N0 + m] = (float)xs[m];
     }
   }
@@ -221,20 +206,20 @@ __device__ void dual_forward(const DualArgs& a, int b, int tid, double* lds, con
 
 __global__ __launch_bounds__(DUAL_THREADS) void k_dual_ascent(DualArgs a) {
   extern __shared__ double dual_lds[];
-  const int b = blockIdx.x, tid = threadIdx.x, R = a.R;
+  const int b = blockIdx.x, tid = threadIdx.x, R = a.net.R;
   double* ws = a.ws + (long)b * a.ws_stride;
   double* lam_ws = ws;
   double* xs = ws + R;
-  double* mom = xs + a.N[0];
+  double* mom = xs + a.net.N[0];
   double* best_pt = mom + 4 * (long)R;
   double* al = a.alpha + (long)b * R;
   double* be = a.beta + (long)b * R;
   // entry point: the projection of the caller's (warm) or alpha = u / (u - l), beta = 0; Adam's moments start at zero
-  for (int k = 1; k <= a.L; ++k)
-    for (int j = tid; j < a.N[k]; j += DUAL_THREADS) {
-      const int r = a.off[k] + j, m = a.mask[(long)b * R + r];
+  for (int k = 1; k <= a.net.L; ++k)
+    for (int j = tid; j < a.net.N[k]; j += DUAL_THREADS) {
+      const int r = a.net.off[k] + j, m = a.mask[(long)b * R + r];
       double s, t;
-      const int st = dual_state(m, a.lb[k][(long)b * a.N[k] + j], a.ub[k][(long)b * a.N[k] + j], s, t);
+      const int st = dual_state(m, a.lb[k][(long)b * a.net.N[k] + j], a.ub[k][(long)b * a.net.N[k] + j], s, t);
       al[r] = a.warm ? fmin(fmax(al[r], 0.0), 1.0) : (st == 0 ? s : 0.0);
       be[r] = a.warm && m != -1 ? fmax(be[r], 0.0) : 0.0;
       mom[r] = 0.0; mom[R + r] = 0.0; mom[2 * R + r] = 0.0; mom[3 * R + r] = 0.0;

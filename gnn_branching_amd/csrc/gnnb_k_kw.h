@@ -27,19 +27,21 @@
 
 static inline size_t kw_lds_doubles(int maxNr) { return (size_t)(2 * maxNr > 5 * KW_THREADS ? 2 * maxNr : 5 * KW_THREADS); }
 
-struct KwEdge {
+struct KwEdge : EdgeGeom {      // (gnnb_pack.h: kind, the conv geometry, n_in, n_out)
   const double* w;              // conv: [co][ci][ky][kx]; linear: [o][i] (torch layout), fp64
   const double* bias;           // per output channel (conv) / node (linear)
   long wb, bb;                  // per-domain strides of w / bias in doubles (0: shared; the property layer: N_L + 1)
-  int kind;                     // 0 conv, 1 linear
-  int c_in, h_in, w_in, c_out, h_out, w_out, kh, kw, stride, pad, n_in, n_out;
+};
+
+struct KwNet {                  // the bound network as the fp64 kernels read it: made once by gnnb_bind_network, copied into every call's arguments
+  KwEdge e[MAXL + 2];                                   // e[k]: the map into graph layer k, k = 1..L (e[L + 1], the property layer: gnnb_kw_bounds, per call)
+  int N[MAXL + 2], off[MAXL + 2];                       // nodes of graph layer k; off[k]: flat ReLU index of layer k's first node
+  int lc[MAXL + 2], lh[MAXL + 2], lw[MAXL + 2];         // graph layer k as (C, H, W) (a Linear map's output: (N_k, 1, 1)), k = 0..L
+  int L, R, maxNr;                                      // maxNr: widest ReLU layer (LDS buffers)
 };
 
 struct KwArgs {
-  KwEdge e[MAXL + 2];                                   // e[k]: the map into graph layer k, k = 1..L+1
-  int N[MAXL + 2], off[MAXL + 2];                       // nodes of graph layer k; off[k]: flat ReLU index of layer k's first node
-  int lc[MAXL + 2], lh[MAXL + 2], lw[MAXL + 2];         // graph layer k as (C, H, W) (a Linear map's output: (N_k, 1, 1)), k = 0..L
-  int L, R, B, maxNr;                                   // maxNr: widest ReLU layer (LDS buffers)
+  KwNet net; int B;                                     // (net.e[L + 1]: this call's property layer); domains
   double* lb[MAXL + 2]; double* ub[MAXL + 2];           // outputs, graph layers 1..L+1, (B, N_k)
   float* lb32[MAXL + 2]; float* ub32[MAXL + 2];         // optional fp32 copies, graph layers 0..L+1 (layer 0 = box)
   const double* plb[MAXL + 2]; const double* pub[MAXL + 2];   // parent bounds, graph layers 1..L+1 (null: no parents)
@@ -52,19 +54,57 @@ struct KwArgs {
   int32_t* infeasible;                                  // (B)
 };
 
-// a child keeps its parent's bounds of graph layers 1..split+1; a split_layer past the last ReLU layer counts as the last one, so
-// the property layer (graph layer L+1) is always recomputed
-__device__ __forceinline__ bool kw_copies(const KwArgs& a, int b, int k) {
-  return a.plb[1] != nullptr && a.split != nullptr && a.split[b] >= 0 && k <= min(a.split[b], a.L - 1) + 1;
+// upper relaxation s p + t of an ambiguous ReLU with pre-activation bounds l < 0 < u
+__device__ __forceinline__ void kw_relax(double l, double u, double& s, double& t) {
+  s = u / fmax(u - l, 1e-300);
+  t = -l * s;
 }
+
+// sums of v[0..NV) over the workgroup, left in v on every thread: per-thread partials in, then a fixed tree.  red: NV * KW_THREADS
+// doubles of LDS that nobody else is using (synchronises before and after)
+template <int NV>
+__device__ __forceinline__ void kw_block_sum(double* red, double* v, int tid) {
+  __syncthreads();
+  for (int r = 0; r < NV; ++r) red[r * KW_THREADS + tid] = v[r];
+  __syncthreads();
+  for (int s = KW_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s)
+      for (int r = 0; r < NV; ++r) red[r * KW_THREADS + tid] += red[r * KW_THREADS + tid + s];
+    __syncthreads();
+  }
+  for (int r = 0; r < NV; ++r) v[r] = red[r * KW_THREADS];
+  __syncthreads();
+}
+
+struct KwBox {                  // all channels x rows y0..y1 x columns x0..x1 of a graph layer laid out (C, H, W): where nu can be non-zero
+  int y0, y1, x0, x1;
+  __device__ __forceinline__ int count(int C) const { return C * (y1 - y0 + 1) * (x1 - x0 + 1); }
+  // node of the box's t-th entry (channel-major, then rows, then columns)
+  __device__ __forceinline__ int node(int t, int H, int W) const {
+    const int bh = y1 - y0 + 1, bw = x1 - x0 + 1, c = t / (bh * bw), r = t % (bh * bw);
+    return (c * H + y0 + r / bw) * W + x0 + r % bw;
+  }
+  // the box of E's input layer (H x W) that holds the support of A^T nu: the receptive fields of a conv, the whole layer of a Linear map
+  __device__ __forceinline__ KwBox below(const KwEdge& E, int H, int W) const {
+    if (E.kind != 0) return KwBox{0, H - 1, 0, W - 1};
+    return KwBox{max(0, y0 * E.stride - E.pad), min(H - 1, y1 * E.stride - E.pad + E.kh - 1),
+                 max(0, x0 * E.stride - E.pad), min(W - 1, x1 * E.stride - E.pad + E.kw - 1)};
+  }
+};
 
 __device__ __forceinline__ bool kw_has_parent(const KwArgs& a, int b) {
   return a.plb[1] != nullptr && a.split != nullptr && a.split[b] >= 0;
 }
 
+// a child keeps its parent's bounds of graph layers 1..split+1; a split_layer past the last ReLU layer counts as the last one, so
+// the property layer (graph layer L+1) is always recomputed
+__device__ __forceinline__ bool kw_copies(const KwArgs& a, int b, int k) {
+  return kw_has_parent(a, b) && k <= min(a.split[b], a.net.L - 1) + 1;
+}
+
 // node j of graph layer k in domain b: parent intersection (or copy), split mask, outputs, ReLU relaxation
 __device__ void kw_finish(const KwArgs& a, int k, int b, int j, double nl, double nu) {
-  const int Nk = a.N[k];
+  const int Nk = a.net.N[k];
   const long at = (long)b * Nk + j;
   if (kw_copies(a, b, k)) {
     nl = a.plb[k][at];
@@ -73,16 +113,15 @@ __device__ void kw_finish(const KwArgs& a, int k, int b, int j, double nl, doubl
     nl = fmax(nl, a.plb[k][at]);
     nu = fmin(nu, a.pub[k][at]);
   }
-  if (k <= a.L) {
-    const int m = a.mask[(long)b * a.R + a.off[k] + j];
+  if (k <= a.net.L) {
+    const int m = a.mask[(long)b * a.net.R + a.net.off[k] + j];
     if (m == 1) nl = fmax(nl, 0.0);
     if (m == 0) nu = fmin(nu, 0.0);
-    const bool amb = nl < 0.0 && nu > 0.0;
-    double d = nl >= 0.0 ? 1.0 : 0.0;
-    if (amb) d = nu / fmax(nu - nl, 1e-300);
-    double* dg = a.dg + ((long)b * a.R + a.off[k] + j) * 2;
+    double d = nl >= 0.0 ? 1.0 : 0.0, g = 0.0;              // (d, -d l) of the relaxation the passes above read
+    if (nl < 0.0 && nu > 0.0) kw_relax(nl, nu, d, g);
+    double* dg = a.dg + ((long)b * a.net.R + a.net.off[k] + j) * 2;
     dg[0] = d;
-    dg[1] = amb ? -d * nl : 0.0;
+    dg[1] = g;
   }
   a.lb[k][at] = nl;
   a.ub[k][at] = nu;
@@ -129,17 +168,17 @@ __global__ __launch_bounds__(KW_THREADS) void k_kw_first(KwArgs a, int span) {
   const long gid = (long)blockIdx.x * KW_THREADS + threadIdx.x;
   if (gid >= (long)span * a.B) return;
   const int b = (int)(gid / span), n = (int)(gid % span);
-  const int N0 = a.N[0], NL = a.N[a.L];
+  const int N0 = a.net.N[0], NL = a.net.N[a.net.L];
   if (n < N0 && a.lb32[0]) {
     a.lb32[0][(long)b * N0 + n] = (float)a.x_lo[(long)b * N0 + n];
     a.ub32[0][(long)b * N0 + n] = (float)a.x_hi[(long)b * N0 + n];
   }
   if (n < NL) a.pw[(long)b * (NL + 1) + n] = (double)a.prop_w[(long)b * NL + n];
   if (n == NL) a.pw[(long)b * (NL + 1) + NL] = (double)a.prop_b[b];
-  if (n < a.N[1]) {
+  if (n < a.net.N[1]) {
     double al = 0.0, au = 0.0;
     if (!kw_copies(a, b, 1)) {
-      const KwEdge& E = a.e[1];
+      const KwEdge& E = a.net.e[1];
       kw_interval_part(E, b, n, a.x_lo + (long)b * N0, a.x_hi + (long)b * N0, false, 0, 1, al, au);
       const double c = kw_bias_of(E, b, n);
       al += c;
@@ -196,88 +235,63 @@ __global__ __launch_bounds__(KW_THREADS) void k_kw_layer(KwArgs a, int k) {
     return;
   }
   extern __shared__ double kw_lds[];
+  const KwNet& net = a.net;
   double* cur = kw_lds;
-  double* nxt = kw_lds + a.maxNr;
-  const KwEdge& E = a.e[k];
+  double* nxt = kw_lds + net.maxNr;
+  const KwEdge& E = net.e[k];
   double il = 0.0, iu = 0.0, sl = 0.0, su = 0.0, sc = 0.0;
   // interval image of node j over the post-ReLU bounds of layer k-1
-  kw_interval_part(E, b, j, a.lb[k - 1] + (long)b * a.N[k - 1], a.ub[k - 1] + (long)b * a.N[k - 1], true, tid, KW_THREADS, il, iu);
+  kw_interval_part(E, b, j, a.lb[k - 1] + (long)b * net.N[k - 1], a.ub[k - 1] + (long)b * net.N[k - 1], true, tid, KW_THREADS, il, iu);
   // support box of nu in layer k-1: the receptive field of node j (a conv node) or the whole layer
-  int y0 = 0, y1 = a.lh[k - 1] - 1, x0 = 0, x1 = a.lw[k - 1] - 1;
-  if (E.kind == 0) {
-    const int hw = E.h_out * E.w_out, oy = (j % hw) / E.w_out, ox = j % E.w_out;
-    y0 = max(0, oy * E.stride - E.pad); y1 = min(y1, oy * E.stride - E.pad + E.kh - 1);
-    x0 = max(0, ox * E.stride - E.pad); x1 = min(x1, ox * E.stride - E.pad + E.kw - 1);
-  }
+  const int oy = E.kind == 0 ? (j % (E.h_out * E.w_out)) / E.w_out : 0, ox = E.kind == 0 ? j % E.w_out : 0;
+  KwBox box = KwBox{oy, oy, ox, ox}.below(E, net.lh[k - 1], net.lw[k - 1]);
   // nu = A_k^T e_j (its bias gain b_k[j] is added after the reduction)
-  {
-    const int bh = y1 - y0 + 1, bw = x1 - x0 + 1, nb = a.lc[k - 1] * bh * bw;
-    for (int t = tid; t < nb; t += KW_THREADS) {
-      const int c = t / (bh * bw), r = t % (bh * bw);
-      const int m = (c * a.lh[k - 1] + y0 + r / bw) * a.lw[k - 1] + x0 + r % bw;
-      cur[m] = kw_row_at(E, b, j, m);
-    }
+  for (int t = tid, nb = box.count(net.lc[k - 1]); t < nb; t += KW_THREADS) {
+    const int m = box.node(t, net.lh[k - 1], net.lw[k - 1]);
+    cur[m] = kw_row_at(E, b, j, m);
   }
   for (int i = k - 1; i >= 1; --i) {
     __syncthreads();
     // ReLU of layer i: gains over the ambiguous set, nu <- d nu; then the bias gain of A_i (box nodes only: nu is 0 elsewhere)
-    const double* dg = a.dg + ((long)b * a.R + a.off[i]) * 2;
-    const KwEdge& Ei = a.e[i];
+    const double* dg = a.dg + ((long)b * net.R + net.off[i]) * 2;
+    const KwEdge& Ei = net.e[i];
     const int hw = Ei.kind == 0 ? Ei.h_out * Ei.w_out : 1;
-    {
-      const int bh = y1 - y0 + 1, bw = x1 - x0 + 1, nb = a.lc[i] * bh * bw;
-      for (int t = tid; t < nb; t += KW_THREADS) {
-        const int c = t / (bh * bw), r = t % (bh * bw);
-        const int m = (c * a.lh[i] + y0 + r / bw) * a.lw[i] + x0 + r % bw;
-        const double v = cur[m], d = dg[2 * m], g = dg[2 * m + 1];
-        sl += fmin(v, 0.0) * g;
-        su += fmax(v, 0.0) * g;
-        const double nv = v * d;
-        cur[m] = nv;
-        sc += nv * Ei.bias[(long)b * Ei.bb + m / hw];
-      }
+    for (int t = tid, nb = box.count(net.lc[i]); t < nb; t += KW_THREADS) {
+      const int m = box.node(t, net.lh[i], net.lw[i]);
+      const double v = cur[m], d = dg[2 * m], g = dg[2 * m + 1];
+      sl += fmin(v, 0.0) * g;
+      su += fmax(v, 0.0) * g;
+      const double nv = v * d;
+      cur[m] = nv;
+      sc += nv * Ei.bias[(long)b * Ei.bb + m / hw];
     }
     __syncthreads();
-    // support box in layer i-1
-    int ny0 = 0, ny1 = a.lh[i - 1] - 1, nx0 = 0, nx1 = a.lw[i - 1] - 1;
-    if (Ei.kind == 0) {
-      ny0 = max(0, y0 * Ei.stride - Ei.pad); ny1 = min(ny1, y1 * Ei.stride - Ei.pad + Ei.kh - 1);
-      nx0 = max(0, x0 * Ei.stride - Ei.pad); nx1 = min(nx1, x1 * Ei.stride - Ei.pad + Ei.kw - 1);
-    }
-    const int bh = ny1 - ny0 + 1, bw = nx1 - nx0 + 1, nb = a.lc[i - 1] * bh * bw;
+    const KwBox in = box.below(Ei, net.lh[i - 1], net.lw[i - 1]);      // support box in layer i-1
+    const int nb = in.count(net.lc[i - 1]);
     if (i > 1) {
       for (int t = tid; t < nb; t += KW_THREADS) {
-        const int c = t / (bh * bw), r = t % (bh * bw);
-        const int m = (c * a.lh[i - 1] + ny0 + r / bw) * a.lw[i - 1] + nx0 + r % bw;
-        nxt[m] = kw_transpose_at(Ei, b, m, cur, y0, y1, x0, x1);
+        const int m = in.node(t, net.lh[i - 1], net.lw[i - 1]);
+        nxt[m] = kw_transpose_at(Ei, b, m, cur, box.y0, box.y1, box.x0, box.x1);
       }
       double* t = cur; cur = nxt; nxt = t;
     } else {                                  // the input: box terms
-      const double* xl = a.x_lo + (long)b * a.N[0];
-      const double* xu = a.x_hi + (long)b * a.N[0];
+      const double* xl = a.x_lo + (long)b * net.N[0];
+      const double* xu = a.x_hi + (long)b * net.N[0];
       for (int t = tid; t < nb; t += KW_THREADS) {
-        const int c = t / (bh * bw), r = t % (bh * bw);
-        const int m = (c * a.lh[0] + ny0 + r / bw) * a.lw[0] + nx0 + r % bw;
-        const double v = kw_transpose_at(Ei, b, m, cur, y0, y1, x0, x1), vp = fmax(v, 0.0), vn = fmin(v, 0.0);
+        const int m = in.node(t, net.lh[0], net.lw[0]);
+        const double v = kw_transpose_at(Ei, b, m, cur, box.y0, box.y1, box.x0, box.x1), vp = fmax(v, 0.0), vn = fmin(v, 0.0);
         sl += vp * xl[m] + vn * xu[m];
         su += vp * xu[m] + vn * xl[m];
       }
     }
-    y0 = ny0; y1 = ny1; x0 = nx0; x1 = nx1;
+    box = in;
   }
-  __syncthreads();                            // the nu buffers become the reduction's (kw_lds_doubles: >= 5 KW_THREADS)
-  double* red = kw_lds;
-  red[tid] = il; red[KW_THREADS + tid] = iu; red[2 * KW_THREADS + tid] = sl; red[3 * KW_THREADS + tid] = su; red[4 * KW_THREADS + tid] = sc;
-  __syncthreads();
-  for (int s = KW_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int r = 0; r < 5; ++r) red[r * KW_THREADS + tid] += red[r * KW_THREADS + tid + s];
-    __syncthreads();
-  }
+  double sum[5] = {il, iu, sl, su, sc};       // the nu buffers become the reduction's (kw_lds_doubles: >= 5 KW_THREADS)
+  kw_block_sum<5>(kw_lds, sum, tid);
   if (tid == 0) {
     const double c = kw_bias_of(E, b, j);
-    const double kl = c + red[4 * KW_THREADS] + red[2 * KW_THREADS], ku = c + red[4 * KW_THREADS] + red[3 * KW_THREADS];
-    const double nl = fmax(red[0] + c, kl), nu = fmin(red[KW_THREADS] + c, ku);
+    const double kl = c + sum[4] + sum[2], ku = c + sum[4] + sum[3];
+    const double nl = fmax(sum[0] + c, kl), nu = fmin(sum[1] + c, ku);
     kw_finish(a, k, b, j, nl, nu);
   }
 }
@@ -287,9 +301,9 @@ __global__ __launch_bounds__(KW_THREADS) void k_kw_layer(KwArgs a, int k) {
 __global__ __launch_bounds__(KW_THREADS) void k_kw_flag(KwArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   int bad = 0;
-  for (int n = tid; n < a.N[0]; n += KW_THREADS) bad |= a.x_lo[(long)b * a.N[0] + n] > a.x_hi[(long)b * a.N[0] + n] + 1e-9;
-  for (int k = 1; k <= a.L + 1; ++k)
-    for (int n = tid; n < a.N[k]; n += KW_THREADS) bad |= a.lb[k][(long)b * a.N[k] + n] > a.ub[k][(long)b * a.N[k] + n] + 1e-9;
+  for (int n = tid; n < a.net.N[0]; n += KW_THREADS) bad |= a.x_lo[(long)b * a.net.N[0] + n] > a.x_hi[(long)b * a.net.N[0] + n] + 1e-9;
+  for (int k = 1; k <= a.net.L + 1; ++k)
+    for (int n = tid; n < a.net.N[k]; n += KW_THREADS) bad |= a.lb[k][(long)b * a.net.N[k] + n] > a.ub[k][(long)b * a.net.N[k] + n] + 1e-9;
   bad = __syncthreads_or(bad);
   if (tid == 0) a.infeasible[b] = bad ? 1 : 0;
 }

@@ -479,10 +479,12 @@ inline void build_packs(const float* blob, Packs& pk) {
 }
 
 // ---- verified-network (layer graph) descriptors ----
-struct Edge {          // linear map between graph layer k-1 and k
+struct EdgeGeom {      // the plain ints of a linear map between graph layer k-1 and k: what a device-side descriptor copies in one assignment
   int kind;            // 0 conv, 1 linear
   int c_in, h_in, w_in, c_out, h_out, w_out, kh, kw, stride, pad;
   int n_in, n_out;
+};
+struct Edge : EdgeGeom {
   std::vector<float> w, b;   // torch layout
 };
 

@@ -70,6 +70,23 @@ class DualAscentResult:
         self.dual, self.primals, self.x_lp = dual, primals, x_lp
 
 
+def f64(t, B, n, what, device):
+    """t as a contiguous (B, n) fp64 tensor on the device."""
+    t = torch.as_tensor(t).to(device=device, dtype=torch.float64).contiguous()
+    if t.numel() != B * n:
+        raise ValueError(f"{what}: {tuple(t.shape)} does not hold {B}x{n} values")
+    return t.view(B, n)
+
+
+def table(ts):
+    """A C array of the tensors' device pointers (None stays None)."""
+    return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _or_reduce(status):
     v = 0
     for x in status.cpu().tolist():
@@ -502,17 +519,27 @@ class ScorerEngine:
         self._prop_cache[key] = (vkey, pw, pb, list(prop_layers))
         return pw, pb
 
-    def workspace(self, B):
-        ws = self._ws.get(B)
+    def _workspace(self, key, B, sizer):
+        """The cached device workspace of (key, B) for the bound network, ``sizer`` (a gnnb_*workspace_bytes) bytes long."""
+        ws = self._ws.get((key, B))
         if ws is None:
-            n = self.lib.gnnb_workspace_bytes(self.h, B)
+            n = getattr(self.lib, sizer)(self.h, B)
             if n == 0:
-                raise RuntimeError("gnnb_workspace_bytes returned 0 (no network bound?)")
+                raise RuntimeError(f"{sizer} returned 0 (no network bound?)")
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             if len(self._ws) > 6:
                 self._ws.clear()
-            self._ws[B] = ws
+            self._ws[(key, B)] = ws
         return ws
+
+    def workspace(self, B):
+        return self._workspace("forward", B, "gnnb_workspace_bytes")
+
+    def kw_workspace(self, B):
+        return self._workspace("kw", B, "gnnb_kw_workspace_bytes")
+
+    def dual_workspace(self, B):
+        return self._workspace("dual", B, "gnnb_dual_workspace_bytes")
 
     def _marshal(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks):
         """Bind the network, move the arguments of GraphNet.forward to the device and validate their sizes."""
@@ -753,35 +780,34 @@ class ScorerEngine:
         return BabsrResult(scores, icp, mask.view(B, self.R), self.sizes[1:-1])
 
     # ---- Wong-Kolter intermediate bounds (lp_producer.LayerGraphLP.kw_bounds for a batch) ------------------------------------
-    def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False):
-        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) input boxes (fp64 on the device), or (B, N_0) when the first
-        layer is not a Conv2d (the input shape is read from the box); prop_layers: B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat
-        ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of graph layers 1..L+1 (fp64); split_layers: (B,) ReLU
-        layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
+    def _domains(self, fixed_layers, prop_layers, x_lo, x_hi, masks):
+        """What kw_bounds and dual_ascent share: bind the network (the input shape is read from the box) and bring a batch of domains to
+        the device.  Returns (B, x_lo, x_hi as (B, N_0) fp64, the (B, R) int8 mask, property weights, property biases)."""
         B = int(x_lo.shape[0])
         if fixed_layers and type(fixed_layers[0]) is nn.Conv2d and (x_lo.dim() != 4 or x_hi.dim() != 4):
             raise ValueError(f"the first layer is a Conv2d: x_lo / x_hi must be (B, C, H, W) boxes, got {tuple(x_lo.shape)} / {tuple(x_hi.shape)}")
         self.bind(fixed_layers, tuple(x_lo.shape[1:]))
         if len(prop_layers) != B:
             raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
-        ng, dev = len(self.sizes), self.device
-
-        def f64(t, n, what):
-            t = torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()
-            if t.numel() != B * n:
-                raise ValueError(f"{what}: {tuple(t.shape)} does not hold {B}x{n} values")
-            return t.view(B, n)
-        xl, xu = f64(x_lo, self.sizes[0], "x_lo"), f64(x_hi, self.sizes[0], "x_hi")
-        mask = torch.as_tensor(masks).to(device=dev, dtype=torch.int8).contiguous()
+        xl, xu = f64(x_lo, B, self.sizes[0], "x_lo", self.device), f64(x_hi, B, self.sizes[0], "x_hi", self.device)
+        mask = torch.as_tensor(masks).to(device=self.device, dtype=torch.int8).contiguous()
         if mask.numel() != B * self.R:
             raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {self.R})")
-        pw, pb = self._prop(prop_layers)
+        return (B, xl, xu, mask) + self._prop(prop_layers)
+
+    def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False):
+        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) input boxes (fp64 on the device), or (B, N_0) when the first
+        layer is not a Conv2d (the input shape is read from the box); prop_layers: B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat
+        ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of graph layers 1..L+1 (fp64); split_layers: (B,) ReLU
+        layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
+        B, xl, xu, mask, pw, pb = self._domains(fixed_layers, prop_layers, x_lo, x_hi, masks)
+        ng, dev = len(self.sizes), self.device
         plb = pub = split = None
         if parents is not None:
             if split_layers is None or len(parents[0]) != ng - 1 or len(parents[1]) != ng - 1:
                 raise ValueError("parents need n_graph-1 lower and upper tensors and split_layers")
-            plb = [f64(t, self.sizes[k + 1], f"parent lb {k + 1}") for k, t in enumerate(parents[0])]
-            pub = [f64(t, self.sizes[k + 1], f"parent ub {k + 1}") for k, t in enumerate(parents[1])]
+            plb = [f64(t, B, self.sizes[k + 1], f"parent lb {k + 1}", dev) for k, t in enumerate(parents[0])]
+            pub = [f64(t, B, self.sizes[k + 1], f"parent ub {k + 1}", dev) for k, t in enumerate(parents[1])]
             split = torch.as_tensor(split_layers).to(device=dev, dtype=torch.int32).contiguous()
             if split.numel() != B:
                 raise ValueError("split_layers must hold one entry per domain")
@@ -794,29 +820,12 @@ class ScorerEngine:
             ub32 = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
         infeasible = torch.empty(B, dtype=torch.int32, device=dev)
         ws = self.kw_workspace(B)
-
-        def table(ts):
-            return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        kb = _lib.KwBatch(xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), table(plb), table(pub),
-                          split.data_ptr() if split is not None else None, ng)
+        kb = _lib.KwBatch(xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), table(plb), table(pub), ptr(split), ng)
         with torch.cuda.device(self.device):
             rc = self.lib.gnnb_kw_bounds(self.h, C.byref(kb), B, table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(),
                                          ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_kw_bounds")
         return KwBoundsResult(lb, ub, lb32, ub32, infeasible)
-
-    def kw_workspace(self, B):
-        key = ("kw", B)
-        ws = self._ws.get(key)
-        if ws is None:
-            n = self.lib.gnnb_kw_workspace_bytes(self.h, B)
-            if n == 0:
-                raise RuntimeError("gnnb_kw_workspace_bytes returned 0 (no network bound?)")
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            if len(self._ws) > 6:
-                self._ws.clear()
-            self._ws[key] = ws
-        return ws
 
     # ---- dual ascent on the subproblem LPs (lp_producer.LayerGraphLP.dual_ascent_host for a batch) --------------------------------
     def dual_ascent(self, fixed_layers, prop_layers, x_lo, x_hi, masks, lb, ub, n_iter, lr=0.1, alpha=None, beta=None, want_grad=False,
@@ -826,33 +835,17 @@ class ScorerEngine:
         (B, N_k) of graph layers 1..L+1, mask applied (``KwBoundsResult.lb`` / ``.ub``).  alpha / beta: None (start at u / (u - l) and 0)
         or (B, R) fp64 to start from (copied).  lb32_prop: None, or a (B,) / (B, 1) fp32 device tensor that receives the bound (the
         property entry of ``KwBoundsResult.lb32``).  workspace: None (the engine's own), or a device uint8 tensor.  Returns a DualAscentResult."""
-        B = int(x_lo.shape[0])
-        if fixed_layers and type(fixed_layers[0]) is nn.Conv2d and (x_lo.dim() != 4 or x_hi.dim() != 4):
-            raise ValueError(f"the first layer is a Conv2d: x_lo / x_hi must be (B, C, H, W) boxes, got {tuple(x_lo.shape)} / {tuple(x_hi.shape)}")
-        self.bind(fixed_layers, tuple(x_lo.shape[1:]))
-        if len(prop_layers) != B:
-            raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
         if (alpha is None) != (beta is None):
             raise ValueError("alpha and beta go together")
+        B, xl, xu, mask, pw, pb = self._domains(fixed_layers, prop_layers, x_lo, x_hi, masks)
         ng, dev, R = len(self.sizes), self.device, self.R
         if len(lb) != ng - 1 or len(ub) != ng - 1:
             raise ValueError(f"{len(lb)} / {len(ub)} bound tensors, expected {ng - 1} (graph layers 1..L+1)")
-
-        def f64(t, n, what):
-            t = torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()
-            if t.numel() != B * n:
-                raise ValueError(f"{what}: {tuple(t.shape)} does not hold {B}x{n} values")
-            return t.view(B, n)
-        xl, xu = f64(x_lo, self.sizes[0], "x_lo"), f64(x_hi, self.sizes[0], "x_hi")
-        lbs = [f64(t, self.sizes[k + 1], f"lb {k + 1}") for k, t in enumerate(lb)]
-        ubs = [f64(t, self.sizes[k + 1], f"ub {k + 1}") for k, t in enumerate(ub)]
-        mask = torch.as_tensor(masks).to(device=dev, dtype=torch.int8).contiguous()
-        if mask.numel() != B * R:
-            raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {R})")
-        pw, pb = self._prop(prop_layers)
+        lbs = [f64(t, B, self.sizes[k + 1], f"lb {k + 1}", dev) for k, t in enumerate(lb)]
+        ubs = [f64(t, B, self.sizes[k + 1], f"ub {k + 1}", dev) for k, t in enumerate(ub)]
         warm = alpha is not None
-        al = f64(alpha, R, "alpha").clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
-        be = f64(beta, R, "beta").clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
+        al = f64(alpha, B, R, "alpha", dev).clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
+        be = f64(beta, B, R, "beta", dev).clone() if warm else torch.empty(B, R, dtype=torch.float64, device=dev)
         bound = torch.empty(B, dtype=torch.float64, device=dev)
         ga = gb = None
         if want_grad:
@@ -874,12 +867,6 @@ class ScorerEngine:
                                       or not lb32_prop.is_contiguous()):
             raise ValueError("lb32_prop must be a contiguous device fp32 tensor of B values")
         ws = self.dual_workspace(B) if workspace is None else workspace
-
-        def table(ts):
-            return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         db = _lib.DualBatch(table(lbs), table(ubs), xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), ng)
         with torch.cuda.device(self.device):
             rc = self.lib.gnnb_dual_ascent(self.h, C.byref(db), B, int(n_iter), float(lr), al.data_ptr(), be.data_ptr(), int(warm),
@@ -887,19 +874,6 @@ class ScorerEngine:
                                            ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_dual_ascent")
         return DualAscentResult(bound, al, be, ga, gb, duals, prims, x_lp)
-
-    def dual_workspace(self, B):
-        key = ("dual", B)
-        ws = self._ws.get(key)
-        if ws is None:
-            n = self.lib.gnnb_dual_workspace_bytes(self.h, B)
-            if n == 0:
-                raise RuntimeError("gnnb_dual_workspace_bytes returned 0 (no network bound?)")
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            if len(self._ws) > 6:
-                self._ws.clear()
-            self._ws[key] = ws
-        return ws
 
     def _check_primals(self, fixed, prim, B):
         def count(t):

@@ -100,6 +100,17 @@ def _check_parent(parent, split_layer):
         raise ValueError("parent bounds given without split_layer")
 
 
+def _relaxation(l, u, amb):
+    """The upper relaxation s pre + t of the ReLUs ``amb`` with pre-activation bounds l < 0 < u: (s, t) = (u / (u - l), -s l), 0 elsewhere."""
+    s = torch.where(amb, u / (u - l).clamp(min=1e-300), torch.zeros_like(l))
+    return s, -l * s
+
+
+def _clamp_by_mask(m, lo, up):
+    """A split tightens the PRE-activation bounds of the node (update_the_model, conv_kwinter_gen.py:573-585)."""
+    return torch.where(m == 1, lo.clamp(min=0), lo), torch.where(m == 0, up.clamp(max=0), up)
+
+
 class LayerGraphLP:
     """LP relaxation of ``layers`` (net.layers with the folded Linear(., 1) property layer last) over an input box."""
 
@@ -146,20 +157,10 @@ class LayerGraphLP:
         r = 0
         for l in self.layers:
             lo, up = lbs[-1], ubs[-1]
-            if type(l) is nn.Conv2d:
-                wp, wn = l.weight.double().clamp(min=0), l.weight.double().clamp(max=0)
-                nl = F.conv2d(lo[None], wp, l.bias.double(), l.stride, l.padding) + F.conv2d(up[None], wn, None, l.stride, l.padding)
-                nu = F.conv2d(up[None], wp, l.bias.double(), l.stride, l.padding) + F.conv2d(lo[None], wn, None, l.stride, l.padding)
-                nl, nu = nl[0], nu[0]
-            elif type(l) is nn.Linear:
-                wp, wn = l.weight.double().clamp(min=0), l.weight.double().clamp(max=0)
-                nl = wp @ lo + wn @ up + l.bias.double()
-                nu = wp @ up + wn @ lo + l.bias.double()
+            if type(l) in (nn.Conv2d, nn.Linear):
+                nl, nu = self._interval_step(l, lo, up)
             elif type(l) is nn.ReLU:
-                m = mask[r].reshape(lo.shape)
-                # a split tightens the PRE-activation bounds of the node (update_the_model, conv_kwinter_gen.py:573-585)
-                lo = torch.where(m == 1, lo.clamp(min=0), lo)
-                up = torch.where(m == 0, up.clamp(max=0), up)
+                lo, up = _clamp_by_mask(mask[r].reshape(lo.shape), lo, up)
                 lbs[-1], ubs[-1] = lo, up
                 nl, nu = lo.clamp(min=0), up.clamp(min=0)
                 r += 1
@@ -199,22 +200,17 @@ class LayerGraphLP:
                 bias = l.bias.double()
                 c = (nu.sum((2, 3)) * bias[None]).sum(1)
                 lo, up = lo + c, up + c
-                hin, win = self.shapes[i][1], self.shapes[i][2]
-                hout, wout = self.shapes[i + 1][1], self.shapes[i + 1][2]
-                opad = (hin - ((hout - 1) * l.stride[0] - 2 * l.padding[0] + l.kernel_size[0]),
-                        win - ((wout - 1) * l.stride[1] - 2 * l.padding[1] + l.kernel_size[1]))
-                nu = F.conv_transpose2d(nu, l.weight.double(), None, l.stride, l.padding, output_padding=opad)
+                nu = self._transpose(l, i, nu)
             elif type(l) is nn.Linear:
                 c = nu @ l.bias.double()
                 lo, up = lo + c, up + c
-                nu = nu @ l.weight.double()
+                nu = self._transpose(l, i, nu)
             elif type(l) is nn.ReLU:
                 pl, pu = lbs[i].reshape(-1), ubs[i].reshape(-1)
                 amb = (pl < 0) & (pu > 0)
-                d = torch.where(pl >= 0, torch.ones_like(pl), torch.zeros_like(pl))
-                d = torch.where(amb, pu / (pu - pl).clamp(min=1e-300), d)
+                s, gain = _relaxation(pl, pu, amb)                              # gain = -d l >= 0
+                d = torch.where(pl >= 0, torch.ones_like(pl), s)
                 flat = nu.reshape(n, -1)
-                gain = torch.where(amb, -d * pl, torch.zeros_like(pl))          # >= 0
                 lo = lo + (flat.clamp(max=0) * gain[None]).sum(1)
                 up = up + (flat.clamp(min=0) * gain[None]).sum(1)
                 nu = (flat * d[None]).reshape(nu.shape)
@@ -254,9 +250,7 @@ class LayerGraphLP:
                         nl, nu = torch.maximum(nl, parent[0][q + 1].double()), torch.minimum(nu, parent[1][q + 1].double())
                 first_affine = False
             elif type(l) is nn.ReLU:
-                m = mask[r].reshape(lo.shape)
-                lo = torch.where(m == 1, lo.clamp(min=0), lo)
-                up = torch.where(m == 0, up.clamp(max=0), up)
+                lo, up = _clamp_by_mask(mask[r].reshape(lo.shape), lo, up)
                 lbs[-1], ubs[-1] = lo, up
                 nl, nu = lo.clamp(min=0), up.clamp(min=0)
                 r += 1
@@ -321,22 +315,21 @@ class LayerGraphLP:
             m = mask[r].reshape(-1)
             amb = (m == -1) & (l < 0) & (u > 0)
             passing = (m == 1) | ((m == -1) & (l >= 0))
-            s = torch.where(amb, u / (u - l).clamp(min=1e-300), torch.zeros_like(l))
-            out.append((amb, passing, s, -l * s, m))
+            out.append((amb, passing) + _relaxation(l, u, amb) + (m,))
         return out
 
     def _relu_offsets(self):
         return np.cumsum([0] + [int(np.prod(self.shapes[i + 1])) for i in self.pre_relu_indices])
 
     def _transpose(self, l, i, nu):
-        """A^T nu for the affine layer ``self.layers[i]`` (nu shaped as its output)."""
+        """A^T nu for the affine layer ``self.layers[i]`` and a leading batch of directions nu (each shaped as the layer's output)."""
         if type(l) is nn.Linear:
             return nu @ l.weight.double()
         hin, win = self.shapes[i][1], self.shapes[i][2]
         hout, wout = self.shapes[i + 1][1], self.shapes[i + 1][2]
         opad = (hin - ((hout - 1) * l.stride[0] - 2 * l.padding[0] + l.kernel_size[0]),
                 win - ((wout - 1) * l.stride[1] - 2 * l.padding[1] + l.kernel_size[1]))
-        return F.conv_transpose2d(nu[None], l.weight.double(), None, l.stride, l.padding, output_padding=opad)[0]
+        return F.conv_transpose2d(nu, l.weight.double(), None, l.stride, l.padding, output_padding=opad)
 
     def _affine(self, l, q):
         if type(l) is nn.Linear:
@@ -356,7 +349,7 @@ class LayerGraphLP:
             if type(l) in (nn.Conv2d, nn.Linear):
                 b = l.bias.double()
                 c = c + ((nu.sum((1, 2)) * b).sum() if type(l) is nn.Conv2d else nu @ b)
-                nu = self._transpose(l, i, nu)
+                nu = self._transpose(l, i, nu[None])[0]
             elif type(l) is nn.ReLU:
                 r -= 1
                 amb, passing, s, t, m = states[r]
@@ -653,6 +646,51 @@ class LayerGraphLP:
         return Subproblem(float(res.fun), float(act.reshape(-1)[0]), x0[None], lower_all, upper_all, duals, primals, mask, (lbs, ubs))
 
 
+# ---- what the three BaB loops below share (their control flow stays apart: each mirrors its own reference file line by line) ----
+def _solve_root(lp):
+    """The Subproblem of the domain with every ReLU undecided."""
+    root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
+    root = lp.solve(root_mask)
+    if root is None:
+        raise RuntimeError("infeasible root domain")
+    return root
+
+
+def _bound_children(lp, dom, decision, child_lp=None):
+    """The two children of ``dom`` split at ``decision`` = [layer, idx] (blocked first, then passing): [Subproblem or None] * 2.
+    ``child_lp`` None: one ``lp.solve`` each; "highs" / "dual_device": both in one ``lp.solve_many(lp=child_lp)``."""
+    items = []
+    for choice in (0, 1):
+        m = [t.clone() for t in dom.mask]
+        m[decision[0]][decision[1]] = choice
+        items.append((m, dom, decision[0]))
+    if child_lp is not None:
+        return lp.solve_many(items, lp=child_lp)
+    return [lp.solve(m, parent=parent, split_layer=split) for m, parent, split in items]
+
+
+def _child_lb(c):                             # an infeasible child cannot contain a counter-example
+    return float("inf") if c is None else c.lb
+
+
+def _random_order(n_relu, sparsest_layer):
+    """The ReLU layers, the sparsest one first (relu_conv_gnnkwthreshold.py:97-103, relu_conv_online.py:104-109)."""
+    order = [l for l in range(n_relu) if l != sparsest_layer]
+    return ([sparsest_layer] if 0 <= sparsest_layer < n_relu else []) + order
+
+
+def _keep_or_close(children, domains, closed_lb, global_ub, eps, decision_bound):
+    """Children that can still improve the answer join ``domains``; the others lower ``closed_lb``, which is returned."""
+    for c in children:
+        if c is None:
+            continue
+        if c.lb < global_ub - eps and (decision_bound is None or c.lb < decision_bound):
+            domains.append(c)
+        else:
+            closed_lb = min(closed_lb, c.lb)
+    return closed_lb
+
+
 def branch_and_bound(lp, scorer, layers, eps=1e-4, max_nodes=200, decision_bound=None, log=print, dump=None):
     """The BaB loop of plnn/relu_conv_gnnkwthreshold.py:120-262 in its plain form: pick the domain with the lowest bound,
     split the ReLU the scorer names, bound both children, keep those that can still improve the answer.
@@ -665,10 +703,7 @@ def branch_and_bound(lp, scorer, layers, eps=1e-4, max_nodes=200, decision_bound
     Gurobi owner can diff against a ``--bab_gnn`` run's dump.  Returns (global_lb, global_ub, visited LP solves)."""
     from .bab_caller import gnn_improvement, trace_line
     fixed = {"fixed_layers": list(layers[:-1]), "prop_layers": [layers[-1]]}
-    root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
-    root = lp.solve(root_mask)
-    if root is None:
-        raise RuntimeError("infeasible root domain")
+    root = _solve_root(lp)
     global_lb, global_ub, domains, visited = root.lb, root.ub, [root], 0
     closed_lb = float("inf")                # lowest bound among the leaves that were closed (proved >= decision_bound or optimal)
     while domains and global_ub - global_lb > eps and visited < max_nodes:
@@ -681,22 +716,11 @@ def branch_and_bound(lp, scorer, layers, eps=1e-4, max_nodes=200, decision_bound
             global_lb = min([d.lb for d in domains] + [closed_lb])
             continue
         decision = scorer(dom, fixed)
-        children = []
-        for choice in (0, 1):
-            m = [t.clone() for t in dom.mask]
-            m[decision[0]][decision[1]] = choice
-            child = lp.solve(m, parent=dom, split_layer=decision[0])
-            visited += 1
-            if child is None:
-                continue
-            global_ub = min(global_ub, child.ub)
-            children.append(child)
+        children = [c for c in _bound_children(lp, dom, decision) if c is not None]
+        visited += 2
+        global_ub = min([global_ub] + [c.ub for c in children])
         log(f"branch {visited} decision {decision} parent lb {dom.lb:.5f} children lb {[round(c.lb, 5) for c in children]}")
-        for c in children:
-            if c.lb < global_ub - eps and (decision_bound is None or c.lb < decision_bound):
-                domains.append(c)
-            else:
-                closed_lb = min(closed_lb, c.lb)
+        closed_lb = _keep_or_close(children, domains, closed_lb, global_ub, eps, decision_bound)
         global_lb = min([d.lb for d in domains] + [closed_lb, global_ub])
         if dump is not None:
             lbs = [c.lb for c in children] + [float("inf")] * (2 - len(children))      # an infeasible child cannot contain a counter-example
@@ -724,7 +748,7 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
     GNN improvement 1.0 instead of the reference's division by ``-2 * lower_bound`` (with ``decision_bound`` = 0 such a domain is never
     added, :226 / :235); infeasible children count as lower bound +inf (Gurobi reports them infeasible too; the reference has no such branch
     because its children inherit feasible parents' bounds); without a ``decision_bound`` leaves closed at optimality keep the minimum honest.
-    ``child_lp``: how ``bound_children`` bounds a pair of children -- "highs" (their LPs) or "dual_device" (``solve_many(lp="dual_device")``:
+    ``child_lp``: how ``_bound_children`` bounds a pair of children -- "highs" (their LPs) or "dual_device" (``solve_many(lp="dual_device")``:
     bounds and dual ascent of both on the GPU, no LP; the root is still an LP).
     Returns (global_lb, global_ub, LP solves, branches, branches that bounded a KW decision, branches that used it)."""
     from .bab_caller import gnn_improvement, resolve_branching, trace_line
@@ -732,34 +756,14 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
         raise ValueError(child_lp)
     fixed = {"fixed_layers": list(layers[:-1]), "prop_layers": [layers[-1]]}
     n_relu = len(lp.pre_relu_indices)
-    root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
-    root = lp.solve(root_mask)
-    if root is None:
-        raise RuntimeError("infeasible root domain")
-    random_order = [l for l in range(n_relu) if l != sparsest_layer]
-    random_order = ([sparsest_layer] if 0 <= sparsest_layer < n_relu else []) + random_order      # :97-103
+    root = _solve_root(lp)
+    random_order = _random_order(n_relu, sparsest_layer)                                          # :97-103
     global_lb, global_ub, domains = root.lb, root.ub, [root]
     solves, nb_states, icp, n_kw, n_kw_used = 0, 0, 0, 0, 0
     ineff_kw_dc, closed_lb = {}, float("inf")
 
-    def bound_children(dom, decision):
-        if child_lp == "dual_device" or getattr(lp, "bound_mode", None) == "kw_device":     # both children's bounds in one device call, then their LPs
-            items = []
-            for choice in (0, 1):
-                m = [t.clone() for t in dom.mask]
-                m[decision[0]][decision[1]] = choice
-                items.append((m, dom, decision[0]))
-            return lp.solve_many(items, lp=child_lp)
-        out = []
-        for choice in (0, 1):
-            m = [t.clone() for t in dom.mask]
-            m[decision[0]][decision[1]] = choice
-            out.append(lp.solve(m, parent=dom, split_layer=decision[0]))
-        return out
-
-    def child_lb(c):                          # an infeasible child cannot contain a counter-example
-        return float("inf") if c is None else c.lb
-
+    # both children's bounds in one device call, then their LPs -- or one solve each
+    many = child_lp if child_lp == "dual_device" or getattr(lp, "bound_mode", None) == "kw_device" else None
     while domains and global_ub - global_lb > eps and nb_states < 2 * max_branches:
         if decision_bound is not None and (global_lb >= decision_bound or global_ub < decision_bound):
             break
@@ -771,17 +775,17 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
             continue
         gnn_decision = scorer(dom, fixed)                                                                  # :117 / :230 / :239
         nb_states += 2                                                                                     # :138
-        children = bound_children(dom, gnn_decision)                                                       # :143-146
+        children = _bound_children(lp, dom, gnn_decision, many)                                            # :143-146
         solves += 2
-        gnn_imp = gnn_improvement(child_lb(children[0]), child_lb(children[1]), dom.lb) if dom.lb < 0 else 1.0     # :151
+        gnn_imp = gnn_improvement(_child_lb(children[0]), _child_lb(children[1]), dom.lb) if dom.lb < 0 else 1.0     # :151
         decision, kw_decision, kw_imp = gnn_decision, None, -1
         if gnn_imp < branching_threshold:                                                                  # :155
             kw_decision, icp = kw_scorer(dom, icp, random_order, sparsest_layer)                           # :157
             if ineff_kw_dc.get(f"{kw_decision[0]}-{kw_decision[1]}", 0) < kwbd_threshold:                  # :160-167
-                kw_children = bound_children(dom, kw_decision)                                             # :168-171
+                kw_children = _bound_children(lp, dom, kw_decision, many)                                  # :168-171
                 solves += 2
                 n_kw += 1
-                kw_imp = gnn_improvement(child_lb(kw_children[0]), child_lb(kw_children[1]), dom.lb)       # :173
+                kw_imp = gnn_improvement(_child_lb(kw_children[0]), _child_lb(kw_children[1]), dom.lb)       # :173
                 decision, used_kw = resolve_branching(gnn_decision, gnn_imp, kw_decision, kw_imp, ineff_kw_dc)     # :176-192
                 if used_kw:
                     children = kw_children
@@ -791,13 +795,7 @@ def branch_and_bound_threshold(lp, scorer, kw_scorer, layers, eps=1e-4, max_bran
         for c in children:
             if c is not None:
                 global_ub = min(global_ub, c.ub)                                                           # :209-214
-        for c in children:
-            if c is None:
-                continue
-            if c.lb < global_ub - eps and (decision_bound is None or c.lb < decision_bound):               # :226, :235
-                domains.append(c)
-            else:
-                closed_lb = min(closed_lb, c.lb)
+        closed_lb = _keep_or_close(children, domains, closed_lb, global_ub, eps, decision_bound)           # :226, :235
         if decision_bound is not None:                                                                     # :251-255
             global_lb = min(d.lb for d in domains) if domains else global_ub - eps
         else:
@@ -819,25 +817,10 @@ def branch_and_bound_online(lp, graph, layers, eps=1e-4, max_nodes=200, decision
     from .plnn.kw_score_conv import choose_node_conv
     fixed = {"fixed_layers": list(layers[:-1]), "prop_layers": [layers[-1]]}
     n_relu = len(lp.pre_relu_indices)
-    root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
-    root = lp.solve(root_mask)
-    if root is None:
-        raise RuntimeError("infeasible root domain")
-    random_order = [l for l in range(n_relu) if l != sparsest_layer]
-    random_order = ([sparsest_layer] if 0 <= sparsest_layer < n_relu else []) + random_order      # :104-109
+    root = _solve_root(lp)
+    random_order = _random_order(n_relu, sparsest_layer)                                          # :104-109
     global_lb, global_ub, domains, visited, icp, steps = root.lb, root.ub, [root], 0, 0, 0
     wrong_pts_dc, closed_lb = {}, float("inf")
-
-    def bound_children(dom, decision):
-        out = []
-        for choice in (0, 1):
-            m = [t.clone() for t in dom.mask]
-            m[decision[0]][decision[1]] = choice
-            out.append(lp.solve(m, parent=dom, split_layer=decision[0]))
-        return out
-
-    def child_lb(c):                          # an infeasible child cannot contain a counter-example
-        return float("inf") if c is None else c.lb
 
     while domains and global_ub - global_lb > eps and visited < max_nodes:
         if decision_bound is not None and (global_lb >= decision_bound or global_ub < decision_bound):
@@ -850,16 +833,16 @@ def branch_and_bound_online(lp, graph, layers, eps=1e-4, max_nodes=200, decision
             continue
         lbg, ubg = dom.graph_bounds(lp.pre_relu_indices, len(lp.layers))
         gnn_decision = graph.decision(lbg, ubg, dom.dual_vars, dom.ub_point, dom.primals, fixed, dom.mask)       # :146
-        children = bound_children(dom, gnn_decision)
+        children = _bound_children(lp, dom, gnn_decision)
         visited += 2
-        gnn_imp = gnn_improvement(child_lb(children[0]), child_lb(children[1]), dom.lb) if dom.lb < 0 else 1.0     # :156
+        gnn_imp = gnn_improvement(_child_lb(children[0]), _child_lb(children[1]), dom.lb) if dom.lb < 0 else 1.0     # :156
         kw_decision, kw_imp, kw_children = None, -1, None
         if gnn_imp < branching_threshold:                                                                         # :158-166
             kw_decision, icp = choose_node_conv(dom.lower_all, dom.upper_all, dom.mask, lp.layers, lp.pre_relu_indices, icp,
                                                 random_order, sparsest_layer)
-            kw_children = bound_children(dom, kw_decision)
+            kw_children = _bound_children(lp, dom, kw_decision)
             visited += 2
-            kw_imp = gnn_improvement(child_lb(kw_children[0]), child_lb(kw_children[1]), dom.lb)
+            kw_imp = gnn_improvement(_child_lb(kw_children[0]), _child_lb(kw_children[1]), dom.lb)
         decision, used_kw, learn, improve = resolve_online(gnn_decision, gnn_imp, kw_decision, kw_imp, wrong_pts_dc, online_threshold)
         if used_kw:
             children = kw_children
@@ -872,13 +855,7 @@ def branch_and_bound_online(lp, graph, layers, eps=1e-4, max_nodes=200, decision
             if c is None:
                 continue
             global_ub = min(global_ub, c.ub)
-        for c in children:
-            if c is None:
-                continue
-            if c.lb < global_ub - eps and (decision_bound is None or c.lb < decision_bound):
-                domains.append(c)
-            else:
-                closed_lb = min(closed_lb, c.lb)
+        closed_lb = _keep_or_close(children, domains, closed_lb, global_ub, eps, decision_bound)
         global_lb = min([d.lb for d in domains] + [closed_lb, global_ub])
     return global_lb, global_ub, visited, steps
 
