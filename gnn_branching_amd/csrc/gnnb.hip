@@ -39,10 +39,12 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 
 #include "../../include/gnnb.h"
 #include "gnnb_pack.h"
+#include "gnnb_mem.h"
 #include "gnnb_train.h"
 
 using namespace gnnb;
@@ -63,6 +65,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
        PK_UPD_INP, PK_POST_INP, PK_SCORE_B, PK_SCORE_F, PK_COUNT };
 static_assert(PK_COUNT == N_PACKS, "pack table");
+static_assert(kMaxReluLayers == MAXL && kMaxLayerNodes == LIVESUM_MAXSRC && kDenseChunk == DENSE_CH, "gnnb_pack.h: the kernels' limits");
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -94,17 +97,29 @@ static const char* kProfNames[PC_COUNT] = {
     "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
     "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent"};
 
-struct DevEdge {
-  float *w_fwd = nullptr, *w_bwd = nullptr, *bias = nullptr;   // conv: tap-major copies; linear: W^T / W, zero-padded
-  int ld_fwd = 0, mt_fwd = 0, ksq_fwd = 0, ld_bwd = 0, mt_bwd = 0, ksq_bwd = 0, kpad_fwd = 0, kpad_bwd = 0;
+struct DevEdge : DenseGeom {
+  DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
 };
 
 struct DevGather {          // one conv edge in one direction, as MFMA gather tables on the device
   bool ok = false;
   GatherGeom g;
-  float* cmat = nullptr;
-  int* koff = nullptr;
-  int* ttab = nullptr;
+  DevBuf<float> cmat;
+  DevBuf<int> koff, ttab;
+};
+
+// Everything gnnb_bind_network produces.  A bind builds a fresh one and move-assigns it into the handle on success; dropping it
+// releases the network's device memory.
+struct BoundNet : LayerGraph {
+  bool bound = false;
+  std::vector<DevEdge> dev;
+  std::vector<DevGather> gf, gb;   // gf[k]: edge k forward (dst = layer k); gb[k]: edge k transposed (dst = layer k-1)
+  std::vector<DevBuf<double>> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for the fp64 kernels, k = 1..L
+  KwNet kw_net{};                   // the bound network as gnnb_kw_bounds / gnnb_dual_ascent pass it to their kernels
+  bool top_ok = false;              // the network allows k_top (option `top`)
+  int zero_tap[3] = {0, 0, 0};      // {k, y, x}: inner conv edge k leaves pixel (y, x) of layer k-1 without a tap (k = 0: none)
+  DevBuf<float> d_s1;               // (N_1) bias sums of edge 1 forward over the (all live) input layer: sum of the weights that reach each node
+  std::vector<DevBuf<float>> edge_w;   // torch-layout weights of the edges for the trainer, made by the first gnnb_online_step
 };
 
 // Host helper threads of a handle, created on the first call that wants them (gnnb_pack_amb_records) and joined by gnnb_destroy: creating
@@ -162,7 +177,7 @@ struct WorkPool {
   }
 };
 
-struct gnnb_handle {
+struct gnnb_handle : BoundNet {
   WorkPool* work_pool = nullptr;      // see WorkPool
   int T = 2, p = 64, device = 0, n_cu = 256;
   bool use_gather = true;       // MFMA gather for conv edges (false: VALU gather kernels)
@@ -175,8 +190,7 @@ struct gnnb_handle {
                                 // exists (measured faster at every batch size and on all three networks: base B = 256 0.975 vs 1.014 ms,
                                 // deep B = 1024 6.59 vs 7.31 ms, B = 1 0.344 vs 0.359 ms); fuse = 0: always two kernels.  Both forms
                                 // compute the same arithmetic per node -- bit-identical results -- so this is a pure scheduling choice.
-  bool use_top = true;          // fuse the top of the network (last Linear edge, last ReLU layer, property node) into k_top
-  bool top_ok = false;          // ... which the bound network allows (set by gnnb_bind_network)
+  bool use_top = true;          // fuse the top of the network (last Linear edge, last ReLU layer, property node) into k_top (where BoundNet::top_ok)
   int clspre_max_b = 1;         // option clspre_max_b: batches up to it classify and run the hoisted feature chains in one launch (k_classify_pre);
                                 // measured (base, us): B = 1 27.5 vs 7.6 + 22.1, B = 2 34.0 vs 30.0, B = 8 42.5 vs 31.8 -- a block's share of
                                 // the ambiguous nodes is uneven, so beyond one subproblem the two kernels' even dealing wins
@@ -185,38 +199,27 @@ struct gnnb_handle {
   int top_split_max = 4;        // option top_split: 4 (default) = four workgroups per sample while B <= n_cu / 4, two while B <= n_cu / 2; 2 = two at most; 1 = never
   Packs packs;
   std::vector<float> blob;      // the GNN parameters as handed to gnnb_create / gnnb_set_weights / left by gnnb_online_step
-  gnnb_train::Trainer* trainer = nullptr;     // online learning (gnnb_online_create)
-  float* d_pack[N_PACKS] = {nullptr};
-  float* d_zero = nullptr;      // 64 zero floats: where masked gather loads point
+  std::unique_ptr<gnnb_train::Trainer> trainer;     // online learning (gnnb_online_create)
+  DevBuf<float> pack_block;     // the weight packs, one block ...
+  float* d_pack[N_PACKS] = {nullptr};      // ... and where pack i starts in it (load_weights)
+  DevBuf<float> d_zero;         // 64 zero floats: where masked gather loads point
   // List counters of a forward (64 ints) live HERE, not in the caller's workspace: a control block per workspace address (CTL_SLOTS
   // of them, least recently used replaced), zero whenever no forward is running on it -- the last workgroup of k_score, the last
   // kernel of a forward and the last reader of the counters, puts them back to zero.  So no launch has to zero them first
   // (k_reset is gone), and what the caller's workspace holds between calls does not matter.
-  float* pack_stage = nullptr; size_t pack_stage_floats = 0;     // pinned staging of the weight packs (load_weights)
-  int* d_ctl = nullptr;
+  PinnedBuf<float> pack_stage;  // pinned staging of the weight packs (load_weights)
+  DevBuf<int> d_ctl;
   const void* ctl_ws[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   unsigned long ctl_age[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long ctl_clock = 0;
   // gnnb_forward_host: pinned staging of the host inputs, their device image, workspace and outputs (grown on demand)
-  float* hs_pinned = nullptr; float* hs_dev = nullptr; size_t hs_floats = 0;
-  void* hs_ws = nullptr; size_t hs_ws_bytes = 0;
-  float* hs_scores = nullptr; int32_t* hs_dec = nullptr; size_t hs_out_B = 0;
-  float* hs_out_pinned = nullptr;
-  float* d_s1 = nullptr;        // (N_1) bias sums of edge 1 forward over the (all live) input layer: sum of the weights that reach each node
+  PinnedBuf<float> hs_pinned, hs_out_pinned;
+  DevBuf<float> hs_dev, hs_scores;
+  DevBuf<char> hs_ws;
+  DevBuf<int32_t> hs_dec;
   int last_proj[MAXL + 2];      // per graph layer: which Linear (LayerId) the rows of mu[k] written by the LAST forward still have to
                                 // go through (-1: final) -- the "deferred projection" of gnnb_pack.h; inspection only (gnnb_mu_projection),
                                 // gnnb_forward itself keeps this state on its stack
-  std::vector<DevGather> gf, gb;   // gf[k]: edge k forward (dst = layer k); gb[k]: edge k transposed (dst = layer k-1)
-  bool bound = false;
-  int zero_tap[3] = {0, 0, 0};   // {k, y, x}: inner conv edge k leaves pixel (y, x) of layer k-1 without a tap (k = 0: none); set by gnnb_bind_network
-  std::vector<Edge> edges;       // edges[k], k = 1..L (edges[0] unused)
-  std::vector<DevEdge> dev;
-  std::vector<double*> kw_w, kw_b;  // fp64 copies of edge k's weights (torch layout) and bias for the fp64 kernels, k = 1..L (made by bind)
-  KwNet kw_net{};                   // the bound network as gnnb_kw_bounds / gnnb_dual_ascent pass it to their kernels (made by bind)
-  std::vector<int> N;            // graph layer sizes, N[0..L+1]
-  std::vector<int> relu_q;       // fixed-layer index of the ReLU of graph layer k
-  std::vector<int> hw;           // nodes per bias entry of layer k
-  int n_fixed = 0, R = 0;
   int halfpass_limit = 0;
   bool prof = false;
   struct Ev { int cls; hipEvent_t a, b; };
@@ -230,12 +233,6 @@ struct gnnb_handle {
 };
 
 
-static int upload(float** d, const float* h, size_t n) {
-  HIPCHK(hipMalloc((void**)d, n * sizeof(float)));
-  HIPCHK(hipMemcpy(*d, h, n * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
-}
-
 // (re)build the operand packs of the scorer from a parameter blob and put them on the device
 static int load_weights(gnnb_t* h, const float* w_blob, hipStream_t st) {
   h->blob.assign(w_blob, w_blob + blob_floats());
@@ -248,24 +245,18 @@ static int load_weights(gnnb_t* h, const float* w_blob, hipStream_t st) {
   // runtime (0.3 ms of the 1.4 ms this call took behind every online-learning step)
   size_t total = 0;
   for (int i = 0; i < N_PACKS; ++i) total += (pv[i]->size() + 63) & ~(size_t)63;
-  if (h->pack_stage_floats < total) {
-    if (h->pack_stage) (void)hipHostFree(h->pack_stage);
-    h->pack_stage = nullptr; h->pack_stage_floats = 0;
-    HIPCHK(hipHostMalloc((void**)&h->pack_stage, total * sizeof(float), hipHostMallocDefault));
-    h->pack_stage_floats = total;
-  }
-  if (!h->d_pack[0]) {                    // one device block, pack i at the offset it has in the staging buffer: one copy per call
-    float* base = nullptr;
-    HIPCHK(hipMalloc((void**)&base, total * sizeof(float)));
+  HIPCHK(h->pack_stage.grow(total));
+  if (!h->pack_block.get()) {             // one device block, pack i at the offset it has in the staging buffer: one copy per call
+    HIPCHK(h->pack_block.alloc(total));
     size_t o = 0;
-    for (int i = 0; i < N_PACKS; ++i) { h->d_pack[i] = base + o; o += (pv[i]->size() + 63) & ~(size_t)63; }
+    for (int i = 0; i < N_PACKS; ++i) { h->d_pack[i] = h->pack_block.get() + o; o += (pv[i]->size() + 63) & ~(size_t)63; }
   }
   size_t off = 0;
   for (int i = 0; i < N_PACKS; ++i) {
-    std::memcpy(h->pack_stage + off, pv[i]->data(), pv[i]->size() * sizeof(float));
+    std::memcpy(h->pack_stage.get() + off, pv[i]->data(), pv[i]->size() * sizeof(float));
     off += (pv[i]->size() + 63) & ~(size_t)63;
   }
-  HIPCHK(hipMemcpyAsync(h->d_pack[0], h->pack_stage, total * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(h->pack_block.get(), h->pack_stage.get(), total * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));       // the staging buffer is reused by the next call
   return 0;
 }
@@ -344,6 +335,11 @@ extern "C" int gnnb_get_option(const gnnb_t* h, const char* name, int* value) {
   return GNNB_OK;
 }
 
+struct LdsAttr {      // a kernel and the dynamic LDS it may be launched with
+  const void* fn; size_t bytes;
+  template <class F> LdsAttr(F* f, size_t b) : fn((const void*)f), bytes(b) {}
+};
+
 extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, int T, int p) {
   if (!out || !w_blob) return fail(GNNB_E_INVALID, "gnnb_create: null argument");
   if (p != P) return fail(GNNB_E_INVALID, "gnnb_create: embedding size %d unsupported (kernels are built for p=64)", p);
@@ -352,160 +348,50 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0) return fail(GNNB_E_HIP, "gnnb_create: no HIP device (%s)", hipGetErrorString(e));
-  gnnb_t* h = new gnnb_handle();
+  std::unique_ptr<gnnb_handle> h(new gnnb_handle());      // (a failure below releases it and what it holds)
   h->T = T;
   h->p = p;
   HIPCHK(hipGetDevice(&h->device));
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, h->device));
   h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (int rc = load_weights(h, w_blob, nullptr)) return rc;
-  HIPCHK(hipMalloc((void**)&h->d_zero, 256 * sizeof(float)));
-  HIPCHK(hipMemset(h->d_zero, 0, 256 * sizeof(float)));
-  HIPCHK(hipMalloc((void**)&h->d_ctl, 8 * 64 * sizeof(int)));
-  HIPCHK(hipMemset(h->d_ctl, 0, 8 * 64 * sizeof(int)));
+  if (int rc = load_weights(h.get(), w_blob, nullptr)) return rc;
+  HIPCHK(h->d_zero.alloc(256));
+  HIPCHK(hipMemset(h->d_zero.get(), 0, 256 * sizeof(float)));
+  HIPCHK(h->d_ctl.alloc(8 * 64));
+  HIPCHK(hipMemset(h->d_ctl.get(), 0, 8 * 64 * sizeof(int)));
   // > 64 KiB of dynamic LDS needs the attribute
-  HIPCHK(hipFuncSetAttribute((const void*)k_pre<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_pre<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE_LDS_FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_pre_inp, hipFuncAttributeMaxDynamicSharedMemorySize, PackPreInp::FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpd::FLOATS + 4096) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<12, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpdL3::FLOATS + 6144) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<12, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpdL3::FLOATS + 6144) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<12, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpdL3::FLOATS + 6144) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_node_update<12, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (PackUpdL3::FLOATS + 6144) * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_input_update, hipFuncAttributeMaxDynamicSharedMemorySize, PackUpdInp::FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_score, hipFuncAttributeMaxDynamicSharedMemorySize, PackScore::FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather16<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_livesum, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather_input_update<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)k_gather<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-
-#define FUSEDQ_ATTR(L, S, P) HIPCHK(hipFuncSetAttribute((const void*)k_gather_update_q<L, S, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-  FUSEDQ_ATTR(16, 0, false); FUSEDQ_ATTR(16, 1, false); FUSEDQ_ATTR(16, 2, false); FUSEDQ_ATTR(32, 1, false); FUSEDQ_ATTR(32, 1, true);
-#undef FUSEDQ_ATTR
-  HIPCHK(hipFuncSetAttribute((const void*)k_classify_pre, hipFuncAttributeMaxDynamicSharedMemorySize, CLSPRE_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void*)k_scored_tail, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));      // (the kernel also has a few static words)
-  HIPCHK(hipFuncSetAttribute((const void*)k_top<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_top<2>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_top<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TOP_LDS_FLOATS * 4));
-  HIPCHK(hipFuncSetAttribute((const void*)k_babsr, hipFuncAttributeMaxDynamicSharedMemorySize, BABSR_LDS_MAX));
-  *out = h;
+  constexpr size_t kUpd = (PackUpd::FLOATS + 4096) * 4, kUpd3 = (PackUpdL3::FLOATS + 6144) * 4, k128 = 128 * 1024, k160 = 160 * 1024;
+  static const LdsAttr attrs[] = {
+      {k_pre<false>, (PackPreFwd::FLOATS + PackPreBwd::FLOATS) * 4}, {k_pre<true>, PRE_LDS_FLOATS * 4}, {k_pre_inp, PackPreInp::FLOATS * 4},
+      {k_node_update<8, false>, kUpd}, {k_node_update<8, true>, kUpd}, {k_node_update<8, false, true>, kUpd}, {k_node_update<8, true, true>, kUpd},
+      {k_node_update<12, false, false, true>, kUpd3}, {k_node_update<12, true, false, true>, kUpd3},
+      {k_node_update<12, false, true, true>, kUpd3}, {k_node_update<12, true, true, true>, kUpd3},
+      {k_input_update, PackUpdInp::FLOATS * 4}, {k_score, PackScore::FLOATS * 4},
+      {k_gather<false>, k128}, {k_gather<true>, k128}, {k_gather16<false>, k128}, {k_gather16<true>, k128}, {k_gather16<false, true>, k128},
+      {k_livesum, k160}, {k_gather_input_update<true, false>, k160}, {k_gather_input_update<true, true>, k160}, {k_gather<false, true>, k128},
+      {k_gather_update_q<16, 0, false>, k160}, {k_gather_update_q<16, 1, false>, k160}, {k_gather_update_q<16, 2, false>, k160},
+      {k_gather_update_q<32, 1, false>, k160}, {k_gather_update_q<32, 1, true>, k160},
+      {k_classify_pre, CLSPRE_LDS_BYTES}, {k_scored_tail, k160 - 256},      // (k_scored_tail also has a few static words)
+      {k_top<4>, TOP_LDS_FLOATS * 4}, {k_top<2>, TOP_LDS_FLOATS * 4}, {k_top<1>, TOP_LDS_FLOATS * 4}, {k_babsr, BABSR_LDS_MAX},
+  };
+  for (const LdsAttr& a : attrs) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.bytes));
+  *out = h.release();
   return GNNB_OK;
-}
-
-static int upload64(double** d, const double* h, size_t n) {
-  HIPCHK(hipMalloc((void**)d, n * sizeof(double)));
-  HIPCHK(hipMemcpy(*d, h, n * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-
-static void free_trainer(gnnb_t* h) {
-  gnnb_train::Trainer* t = h->trainer;
-  if (!t) return;
-  for (float* p : {t->d_w, t->d_g, t->d_m, t->d_v, t->d_scores, t->d_ds, t->d_loss, t->d_imp})
-    if (p) (void)hipFree(p);
-  if (t->d_kw) (void)hipFree(t->d_kw);
-  if (t->d_sel) (void)hipFree(t->d_sel);
-  for (float* p : t->edge_w)
-    if (p) (void)hipFree(p);
-  t->arena.release();
-  if (t->desc) (void)hipHostFree(t->desc);
-  delete t;
-  h->trainer = nullptr;
-}
-
-static void free_network(gnnb_t* h) {
-  if (h->trainer) {                       // the edge weights of the trainer belong to the network that goes away
-    for (float* p : h->trainer->edge_w)
-      if (p) (void)hipFree(p);
-    h->trainer->edge_w.clear();
-  }
-  for (auto& d : h->dev) {
-    if (d.w_fwd) (void)hipFree(d.w_fwd);
-    if (d.w_bwd) (void)hipFree(d.w_bwd);
-    if (d.bias) (void)hipFree(d.bias);
-  }
-  for (auto* v : {&h->gf, &h->gb})
-    for (auto& d : *v) {
-      if (d.cmat) (void)hipFree(d.cmat);
-      if (d.koff) (void)hipFree(d.koff);
-      if (d.ttab) (void)hipFree(d.ttab);
-    }
-  for (auto* v : {&h->kw_w, &h->kw_b})
-    for (double* p : *v)
-      if (p) (void)hipFree(p);
-  h->kw_w.clear();
-  h->kw_b.clear();
-  h->kw_net = KwNet{};
-  h->gf.clear();
-  h->gb.clear();
-  h->dev.clear();
-  h->edges.clear();
-  h->N.clear();
-  h->relu_q.clear();
-  h->hw.clear();
-  h->bound = false;
 }
 
 extern "C" int gnnb_destroy(gnnb_t* h) {
   if (!h) return GNNB_OK;
-  free_network(h);
-  if (h->d_pack[0]) (void)hipFree(h->d_pack[0]);      // one block (load_weights)
-  if (h->d_zero) (void)hipFree(h->d_zero);
-  if (h->d_ctl) (void)hipFree(h->d_ctl);
-  if (h->pack_stage) (void)hipHostFree(h->pack_stage);
-  if (h->d_s1) (void)hipFree(h->d_s1);
-  if (h->hs_pinned) (void)hipHostFree(h->hs_pinned);
-  if (h->hs_out_pinned) (void)hipHostFree(h->hs_out_pinned);
-  if (h->hs_dev) (void)hipFree(h->hs_dev);
-  if (h->hs_ws) (void)hipFree(h->hs_ws);
-  if (h->hs_scores) (void)hipFree(h->hs_scores);
-  if (h->hs_dec) (void)hipFree(h->hs_dec);
-  free_trainer(h);
   if (h->work_pool && h->work_pool->owner == getpid()) delete h->work_pool;
   for (auto& ev : h->pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   for (auto& ev : h->pool) (void)hipEventDestroy(ev);
-  delete h;
+  delete h;      // the bound network, the trainer and every buffer go with their owners
   return GNNB_OK;
 }
 
 static bool conv_channels_ok(int c) { return c == 3 || c == 8 || c == 16 || c == 32; }
 
-// The transposed aggregate of an inner conv edge (graph layers k >= 2) is divided by the number of kernel taps that touch a pixel
-// (the reference's `freq`, graph_conv.py:306-312).  A stride larger than the kernel leaves pixels of layer k-1 that no window
-// reads: their count is 0 and the reference computes 0/0 and stops.  The scoring entry points refuse such a network instead of
-// letting the answer depend on which kernel the launch plan picks for the edge.  Returns the first such layer k (0: none) and
-// one of its unread pixels.  Edge 1 is not normalised (:360-376) and may have such pixels.
-static int zero_tap_layer(const gnnb_t* h, int* y0, int* x0) {
-  const int L = (int)h->N.size() - 2;
-  for (int k = 2; k <= L; ++k) {
-    const Edge& e = h->edges[k];
-    if (e.kind != 0) continue;
-    auto unread = [&](int n_in, int n_out, int ksz) {      // first position of one axis that no window covers, -1: none
-      for (int t = 0; t < n_in; ++t) {
-        int taps = 0;
-        for (int o = 0; o < n_out; ++o) taps += (t >= o * e.stride - e.pad && t < o * e.stride - e.pad + ksz);
-        if (taps == 0) return t;
-      }
-      return -1;
-    };
-    const int y = unread(e.h_in, e.h_out, e.kh), x = unread(e.w_in, e.w_out, e.kw);
-    if (y >= 0 || x >= 0) {
-      *y0 = y >= 0 ? y : 0;
-      *x0 = x >= 0 ? x : 0;
-      return k;
-    }
-  }
-  return 0;
-}
+// a network with an inner conv edge that leaves a pixel unread (gnnb_pack.h zero_tap_layer) is refused by the scoring entry points
 static int refuse_zero_taps(const gnnb_t* h, const char* who) {
   const int k = h->zero_tap[0], y = h->zero_tap[1], x = h->zero_tap[2];
   if (!k) return GNNB_OK;
@@ -517,207 +403,75 @@ static int refuse_zero_taps(const gnnb_t* h, const char* who) {
 
 extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int c0, int h0, int w0) {
   if (!h || !L || n < 2) return fail(GNNB_E_INVALID, "gnnb_bind_network: bad arguments");
-  free_network(h);
-  int C = c0, H = h0, W = w0;
-  bool flat = false;
-  int nflat = c0 * h0 * w0;
-  h->N.push_back(nflat);
-  h->edges.emplace_back();
-  h->relu_q.push_back(-1);
-  h->hw.push_back(1);
-  Edge pend;
-  bool have = false;
-  int pend_hw = 1;
-  for (int q = 0; q < n; ++q) {
-    const gnnb_layer_desc& d = L[q];
-    if (d.kind == GNNB_CONV) {
-      if (flat) return fail(GNNB_E_INVALID, "layer %d: conv after flatten", q);
-      if (have) return fail(GNNB_E_INVALID, "layer %d: two linear maps without a ReLU between them", q);
-      if (d.c_in != C) return fail(GNNB_E_INVALID, "layer %d: conv expects %d input channels, graph has %d", q, d.c_in, C);
-      if (!d.weight || !d.bias) return fail(GNNB_E_INVALID, "layer %d: null weight/bias", q);
-      Edge e;
-      e.kind = 0;
-      e.c_in = C; e.h_in = H; e.w_in = W; e.c_out = d.c_out; e.kh = d.kh; e.kw = d.kw; e.stride = d.stride; e.pad = d.pad;
-      if (d.stride < 1 || d.kh < 1 || d.kw < 1) return fail(GNNB_E_INVALID, "layer %d: bad conv geometry", q);
-      if ((H + 2 * d.pad - d.kh) % d.stride || (W + 2 * d.pad - d.kw) % d.stride)
-        return fail(GNNB_E_INVALID, "layer %d: conv geometry leaves a remainder (conv_transpose2d of the reference would need output_padding)", q);
-      e.h_out = (H + 2 * d.pad - d.kh) / d.stride + 1;
-      e.w_out = (W + 2 * d.pad - d.kw) / d.stride + 1;
-      e.n_in = C * H * W;
-      e.n_out = e.c_out * e.h_out * e.w_out;
-      e.w.assign(d.weight, d.weight + (size_t)e.c_out * e.c_in * e.kh * e.kw);
-      e.b.assign(d.bias, d.bias + e.c_out);
-      C = e.c_out; H = e.h_out; W = e.w_out;
-      nflat = e.n_out;
-      pend_hw = H * W;
-      pend = e;
-      have = true;
-    } else if (d.kind == GNNB_LINEAR) {
-      if (have) return fail(GNNB_E_INVALID, "layer %d: two linear maps without a ReLU between them", q);
-      if (d.n_in != nflat) return fail(GNNB_E_INVALID, "layer %d: linear expects %d inputs, graph has %d", q, d.n_in, nflat);
-      if (!d.weight || !d.bias) return fail(GNNB_E_INVALID, "layer %d: null weight/bias", q);
-      Edge e;
-      e.kind = 1;
-      e.n_in = d.n_in; e.n_out = d.n_out;
-      e.c_in = e.h_in = e.w_in = e.c_out = e.h_out = e.w_out = e.kh = e.kw = e.stride = e.pad = 0;
-      e.w.assign(d.weight, d.weight + (size_t)d.n_out * d.n_in);
-      e.b.assign(d.bias, d.bias + d.n_out);
-      nflat = d.n_out;
-      flat = true;
-      pend_hw = 1;
-      pend = e;
-      have = true;
-    } else if (d.kind == GNNB_RELU) {
-      if (!have) return fail(GNNB_E_INVALID, "layer %d: ReLU without a preceding conv/linear", q);
-      h->N.push_back(nflat);
-      h->edges.push_back(pend);
-      h->relu_q.push_back(q);
-      h->hw.push_back(pend_hw);
-      have = false;
-    } else if (d.kind == GNNB_FLATTEN) {
-      flat = true;
-    } else {
-      return fail(GNNB_E_INVALID, "layer %d: unknown kind %d", q, d.kind);
-    }
-  }
-  if (have) return fail(GNNB_E_INVALID, "fixed layers must end after a ReLU (the property layer is passed per batch)");
-  const int Lr = (int)h->N.size() - 1;
-  if (Lr < 1 || Lr > MAXL) return fail(GNNB_E_INVALID, "unsupported number of ReLU layers %d (max %d)", Lr, MAXL);
-  h->N.push_back(1);   // property node
-  h->n_fixed = n;
-  h->R = 0;
-  for (int k = 1; k <= Lr; ++k) h->R += h->N[k];
-  h->dev.resize(Lr + 1);
-  h->kw_w.assign(Lr + 1, nullptr);
-  h->kw_b.assign(Lr + 1, nullptr);
-  for (int k = 0; k < MAXL + 2; ++k) h->last_proj[k] = -1;
-  for (int k = 0; k <= Lr; ++k)
-    if (h->N[k] > LIVESUM_MAXSRC) return fail(GNNB_E_INVALID, "graph layer %d has %d nodes, more than the %d k_livesum holds in LDS", k, h->N[k], LIVESUM_MAXSRC);
+  static_cast<BoundNet&>(*h) = BoundNet();      // the old network goes first; the handle stays unbound unless everything below succeeds
+  BoundNet net;
+  const std::string refusal = parse_layers(L, n, c0, h0, w0, net);
+  if (!refusal.empty()) return fail(GNNB_E_INVALID, "%s", refusal.c_str());
+  const int Lr = (int)net.N.size() - 2;
+  net.dev.resize(Lr + 1);
+  net.kw_w.resize(Lr + 1);
+  net.kw_b.resize(Lr + 1);
+  fill_kw_geometry(net.kw_net, net);
   for (int k = 1; k <= Lr; ++k) {
-    const Edge& e = h->edges[k];
-    DevEdge& d = h->dev[k];
-    if (int rc = upload(&d.bias, e.b.data(), e.b.size())) return rc;
-    {                                   // fp64 copies for the fp64 kernels (fp32 -> fp64 is exact); KwNet below points at them
+    const Edge& e = net.edges[k];
+    DevEdge& d = net.dev[k];
+    HIPCHK(d.bias.upload(e.b.data(), e.b.size()));
+    {                                   // fp64 copies for the fp64 kernels (fp32 -> fp64 is exact); KwNet points at them
       std::vector<double> w64(e.w.begin(), e.w.end()), b64(e.b.begin(), e.b.end());
-      if (int rc = upload64(&h->kw_w[k], w64.data(), w64.size())) return rc;
-      if (int rc = upload64(&h->kw_b[k], b64.data(), b64.size())) return rc;
+      HIPCHK(net.kw_w[k].upload(w64.data(), w64.size()));
+      HIPCHK(net.kw_b[k].upload(b64.data(), b64.size()));
+      net.kw_net.e[k].w = net.kw_w[k].get(); net.kw_net.e[k].bias = net.kw_b[k].get();
     }
-    if (k == 1) {                       // row sums of edge 1 (for a conv: of the taps inside the image) -- k_livesum's job for this edge
-      std::vector<float> s1(h->N[1], 0.0f);
-      if (e.kind == 0) {
-        for (int co = 0; co < e.c_out; ++co)
-          for (int oy = 0; oy < e.h_out; ++oy)
-            for (int ox = 0; ox < e.w_out; ++ox) {
-              float acc = 0.0f;
-              for (int ci = 0; ci < e.c_in; ++ci)
-                for (int ky = 0; ky < e.kh; ++ky) {
-                  const int iy = oy * e.stride - e.pad + ky;
-                  if (iy < 0 || iy >= e.h_in) continue;
-                  for (int kx = 0; kx < e.kw; ++kx) {
-                    const int ix = ox * e.stride - e.pad + kx;
-                    if (ix < 0 || ix >= e.w_in) continue;
-                    acc += e.w[(((size_t)co * e.c_in + ci) * e.kh + ky) * e.kw + kx];
-                  }
-                }
-              s1[((size_t)co * e.h_out + oy) * e.w_out + ox] = acc;
-            }
-      } else {
-        for (int i = 0; i < e.n_out; ++i) {
-          float acc = 0.0f;
-          for (int q = 0; q < e.n_in; ++q) acc += e.w[(size_t)i * e.n_in + q];
-          s1[i] = acc;
-        }
-      }
-      if (h->d_s1) { (void)hipFree(h->d_s1); h->d_s1 = nullptr; }
-      if (int rc = upload(&h->d_s1, s1.data(), s1.size())) return rc;
+    if (k == 1) {                       // k_livesum's job for this edge, done once
+      const std::vector<float> s1 = edge1_row_sums(e);
+      HIPCHK(net.d_s1.upload(s1.data(), s1.size()));
     }
     if (e.kind == 0) {
       std::vector<float> t(e.w.size());
       pack_conv_fwd(t.data(), e);
-      if (int rc = upload(&d.w_fwd, t.data(), t.size())) return rc;
+      HIPCHK(d.w_fwd.upload(t.data(), t.size()));
       pack_conv_bwd(t.data(), e);
-      if (int rc = upload(&d.w_bwd, t.data(), t.size())) return rc;
+      HIPCHK(d.w_bwd.upload(t.data(), t.size()));
     } else {
-      // k_dense_agg operands At[k][i] = A[i][k], zero-padded to 32*MT columns and 8*ksq rows (ksq = k-steps per wave)
-      auto ksq_of = [](int K) { return (((K + 1) / 2 + 3) / 4 + DENSE_CH - 1) / DENSE_CH * DENSE_CH; };
-      d.mt_fwd = (e.n_out + 31) / 32;
-      d.ld_fwd = d.mt_fwd * 32;
-      d.ksq_fwd = ksq_of(e.n_in);
-      d.kpad_fwd = (e.n_in + 63) / 64 * 64;
-      d.kpad_bwd = (e.n_out + 15) / 16 * 16;
-      const size_t rows_f = std::max<size_t>(8 * d.ksq_fwd + 2 * DENSE_CH, d.kpad_fwd + 32);
-      std::vector<float> t(rows_f * d.ld_fwd, 0.f);           // forward: A = W, k = input node
-      for (int o = 0; o < e.n_out; ++o)
-        for (int i = 0; i < e.n_in; ++i) t[(size_t)i * d.ld_fwd + o] = e.w[(size_t)o * e.n_in + i];
-      if (int rc = upload(&d.w_fwd, t.data(), t.size())) return rc;
-      d.mt_bwd = (e.n_in + 31) / 32;
-      d.ld_bwd = d.mt_bwd * 32;
-      d.ksq_bwd = ksq_of(e.n_out);
-      const size_t rows_b = std::max<size_t>(8 * d.ksq_bwd + 2 * DENSE_CH, d.kpad_bwd + 64);   // k_dense_bwd_lds reads up to 3 chunks past kpad
-      t.assign(rows_b * d.ld_bwd, 0.f);                        // transposed: A = W^T, k = output node
-      for (int o = 0; o < e.n_out; ++o)
-        for (int i = 0; i < e.n_in; ++i) t[(size_t)o * d.ld_bwd + i] = e.w[(size_t)o * e.n_in + i];
-      if (int rc = upload(&d.w_bwd, t.data(), t.size())) return rc;
+      const DenseHost dh = dense_operands(e);
+      static_cast<DenseGeom&>(d) = dh.g;
+      HIPCHK(d.w_fwd.upload(dh.fwd.data(), dh.fwd.size()));
+      HIPCHK(d.w_bwd.upload(dh.bwd.data(), dh.bwd.size()));
     }
   }
-  h->top_ok = Lr >= 2 && h->edges[Lr].kind == 1 && h->N[Lr] <= 128 && h->dense_lds && h->dev[Lr].mt_fwd <= 4 && h->dev[Lr].kpad_bwd <= 128;
+  net.top_ok = Lr >= 2 && net.edges[Lr].kind == 1 && net.N[Lr] <= 128 && h->dense_lds && net.dev[Lr].mt_fwd <= 4 && net.dev[Lr].kpad_bwd <= 128;
   // MFMA gather tables for every conv edge, both directions (the input layer's transposed edge is not normalised)
-  h->gf.assign(Lr + 1, DevGather());
-  h->gb.assign(Lr + 1, DevGather());
+  net.gf.resize(Lr + 1);
+  net.gb.resize(Lr + 1);
   if (h->use_gather)
     for (int k = 1; k <= Lr; ++k) {
-      if (h->edges[k].kind != 0) continue;
+      if (net.edges[k].kind != 0) continue;
       for (int dir = 0; dir < 2; ++dir) {
         GatherHost gh;
         // the input layer's transposed gather is fused with its feature chain and update (132 MFMAs per tile)
-        if (!build_gather(h->edges[k], dir, dir == 1 && k > 1, gh, (dir == 1 && k == 1) ? 132 : 0, /*allow16=*/true)) continue;
-        DevGather& d = dir == 0 ? h->gf[k] : h->gb[k];
+        if (!build_gather(net.edges[k], dir, dir == 1 && k > 1, gh, (dir == 1 && k == 1) ? 132 : 0, /*allow16=*/true)) continue;
+        std::vector<int> tt;
+        if (!tile_table(gh.g.tm, tt)) return fail(GNNB_E_INVALID, "layer %d: tile table overflow", k);
+        DevGather& d = dir == 0 ? net.gf[k] : net.gb[k];
         d.g = gh.g;
-        if (int rc = upload(&d.cmat, gh.cmat.data(), gh.cmat.size())) return rc;
-        HIPCHK(hipMalloc((void**)&d.koff, gh.koff.size() * sizeof(int)));
-        HIPCHK(hipMemcpy(d.koff, gh.koff.data(), gh.koff.size() * sizeof(int), hipMemcpyHostToDevice));
-        {
-          const TileMap& tm = gh.g.tm;
-          if (tm.NCG > 255 || tm.NBY > 4095 || tm.NBX > 4095) return fail(GNNB_E_INVALID, "layer %d: tile table overflow", k);
-          std::vector<int> tt(tm.TPS);
-          for (int t = 0; t < tm.TPS; ++t) {
-            const int cg = t / (tm.NBY * tm.NBX), rem = t % (tm.NBY * tm.NBX);
-            tt[t] = cg | ((rem / tm.NBX) << 8) | ((rem % tm.NBX) << 20);
-          }
-          HIPCHK(hipMalloc((void**)&d.ttab, tt.size() * sizeof(int)));
-          HIPCHK(hipMemcpy(d.ttab, tt.data(), tt.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
+        HIPCHK(d.cmat.upload(gh.cmat.data(), gh.cmat.size()));
+        HIPCHK(d.koff.upload(gh.koff.data(), gh.koff.size()));
+        HIPCHK(d.ttab.upload(tt.data(), tt.size()));
         d.ok = true;
       }
     }
   // an edge without MFMA gather tables falls back to the VALU gathers, which are compiled for a few channel counts only
   for (int k = 1; k <= Lr; ++k) {
-    const Edge& e = h->edges[k];
+    const Edge& e = net.edges[k];
     if (e.kind != 0) continue;
-    if ((!h->gf[k].ok && !conv_channels_ok(e.c_out)) || (!h->gb[k].ok && !conv_channels_ok(e.c_in)))
+    if ((!net.gf[k].ok && !conv_channels_ok(e.c_out)) || (!net.gb[k].ok && !conv_channels_ok(e.c_in)))
       return fail(GNNB_E_INVALID, "conv edge %d (%d -> %d channels): no MFMA gather tables and the fallback kernels only cover channel counts "
                   "{3, 8, 16, 32}", k, e.c_in, e.c_out);
   }
-  h->zero_tap[0] = zero_tap_layer(h, &h->zero_tap[1], &h->zero_tap[2]);
-  // the description the fp64 kernels share (gnnb_k_kw.h KwNet): sizes, flat ReLU offsets, every layer as (C, H, W), the fixed edges
-  KwNet& net = h->kw_net;
-  net.L = Lr; net.R = h->R;
-  for (int k = 0; k <= Lr + 1; ++k) net.N[k] = h->N[k];
-  for (int k = 1; k <= Lr; ++k) {
-    net.off[k] = net.off[k - 1] + (k > 1 ? h->N[k - 1] : 0);
-    net.maxNr = std::max(net.maxNr, h->N[k]);
-    KwEdge& E = net.e[k];
-    static_cast<EdgeGeom&>(E) = h->edges[k];
-    E.w = h->kw_w[k]; E.bias = h->kw_b[k]; E.wb = 0; E.bb = 0;
-  }
-  for (int k = 0; k <= Lr; ++k) {
-    const Edge& e = h->edges[k == 0 ? 1 : k];
-    const bool conv = e.kind == 0;
-    net.lc[k] = conv ? (k == 0 ? e.c_in : e.c_out) : h->N[k];
-    net.lh[k] = conv ? (k == 0 ? e.h_in : e.h_out) : 1;
-    net.lw[k] = conv ? (k == 0 ? e.w_in : e.w_out) : 1;
-  }
-  h->bound = true;
+  net.zero_tap[0] = zero_tap_layer(net, &net.zero_tap[1], &net.zero_tap[2]);
+  net.bound = true;
+  static_cast<BoundNet&>(*h) = std::move(net);
+  for (int k = 0; k < MAXL + 2; ++k) h->last_proj[k] = -1;
   return GNNB_OK;
 }
 
@@ -735,7 +489,7 @@ static DTileMap to_dtm(const TileMap& t) {
 }
 static DGather to_dg(const DevGather& d, const float* zero) {
   const GatherGeom& g = d.g;
-  return DGather{d.cmat, reinterpret_cast<const int2*>(d.koff), d.ttab, zero, g.K2, g.tm.NCG * g.K2, g.Hs, g.Ws, g.Ns, g.ystep, g.ybase,
+  return DGather{d.cmat.get(), reinterpret_cast<const int2*>(d.koff.get()), d.ttab.get(), zero, g.K2, g.tm.NCG * g.K2, g.Hs, g.Ws, g.Ns, g.ystep, g.ybase,
                  g.xstep, g.xbase, g.WY, g.WX, g.normalise, g.kh, g.kw, g.stride, g.pad, g.lanes};
 }
 static size_t gather_lds_bytes(const DevGather& d, size_t pack_floats) {
@@ -834,7 +588,7 @@ static Plan make_plan(const gnnb_t* h, int B, int halfpass_limit) {
   // needs the kept live-row list (B2 then walks live rows only) and a layer L-1 that is not layer 1 (whose update has the
   // restricted / input-mapping forms)
   p.top_upd = p.top_fused && h->top_fuse_upd && L >= 3 && TOP_LIST_KEEP_OK(topK);
-  p.s1_table = L >= 2 && h->d_s1 != nullptr;
+  p.s1_table = L >= 2 && h->d_s1.get() != nullptr;
   p.embed_in_gather = h->embed_fuse && !p.debug_full && h->gf[1].ok;
   p.cls_pre = h->bf3 && B <= h->clspre_max_b;      // default: a single subproblem
   p.need_inp = p.limit >= 2 && (h->T > 1 || p.debug_full) && !h->gb[1].ok;    // the fused input kernel computes Q itself
@@ -1134,7 +888,7 @@ struct Forward {
     for (int k = 1; k <= L; ++k) {
       const int i = k - 1, q = h->relu_q[k];
       a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.dual[i] = in->dual[k - 1];
-      a.z_pre[i] = in->primal[q - 1]; a.z_post[i] = in->primal[q]; a.bias[i] = h->dev[k].bias;
+      a.z_pre[i] = in->primal[q - 1]; a.z_post[i] = in->primal[q]; a.bias[i] = h->dev[k].bias.get();
       a.Pf[i] = ws + w.Pf[k]; a.Pb[i] = ws + w.Pb[k]; a.list[i] = ilist(w.amb[k]);
       a.N[i] = h->N[k]; a.hw[i] = h->hw[k];
     }
@@ -1183,7 +937,7 @@ struct Forward {
       if (k == 1 && p.s1_table) continue;
       if (k >= 2 && h->gf[k].ok) continue;
       if (k == L && p.top_s_fwd) continue;
-      push(e.kind == 0 ? 0 : 1, e, e.kind == 0 ? h->dev[k].w_fwd : h->dev[k].w_bwd, h->dev[k].ld_bwd, k > 1 ? ws + w.lf[k - 1] : nullptr,
+      push(e.kind == 0 ? 0 : 1, e, e.kind == 0 ? h->dev[k].w_fwd.get() : h->dev[k].w_bwd.get(), h->dev[k].ld_bwd, k > 1 ? ws + w.lf[k - 1] : nullptr,
            ws + w.sf[k], h->N[k], h->N[k - 1], 0);
     }
     if (p.limit >= 2)
@@ -1191,7 +945,7 @@ struct Forward {
         const Edge& e = h->edges[k + 1];
         if (h->gb[k + 1].ok) continue;
         if (k == L - 1 && p.top_s_bwd) continue;
-        push(e.kind == 0 ? 2 : 3, e, h->dev[k + 1].w_bwd, h->dev[k + 1].ld_bwd, ws + w.lf[k + 1], ws + w.sb[k], h->N[k], h->N[k + 1],
+        push(e.kind == 0 ? 2 : 3, e, h->dev[k + 1].w_bwd.get(), h->dev[k + 1].ld_bwd, ws + w.lf[k + 1], ws + w.sb[k], h->N[k], h->N[k + 1],
              k >= 1 ? 1 : 0);
       }
     a.njobs = q;
@@ -1239,7 +993,7 @@ struct Forward {
   // a gather over conv edge table `d` into layer k; sparse: behind a ReLU layer (src_layer), skipping the (zero) rows of that
   // layer's dead nodes and producing the bias sums in `sout` on the way
   GArgs gather_args(const DevGather& d, int k, const float* src, bool scored, bool sparse, int src_layer, float* sout) const {
-    return GArgs{in->lb[k], in->ub[k], in->mask, src, nb, map_tiles(d.g.tm, B), scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero),
+    return GArgs{in->lb[k], in->ub[k], in->mask, src, nb, map_tiles(d.g.tm, B), scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero.get()),
                  EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr,
                  sparse ? in->ub[src_layer] : nullptr, sparse ? sout : nullptr};
   }
@@ -1261,13 +1015,13 @@ struct Forward {
     const Edge& e = h->edges[ei];
     const DevEdge& de = h->dev[ei];
     if (e.kind == 0) {
-      const ConvArgs a{src, nb, tr ? de.w_bwd : de.w_fwd, B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
+      const ConvArgs a{src, nb, tr ? de.w_bwd.get() : de.w_fwd.get(), B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, normalise};
       void (*kern)(ConvArgs) = tr ? kConvT[conv_channel_form(e.c_in)] : kConvFwd[conv_channel_form(e.c_out)];
       const long waves = tr ? (long)B * e.h_in * e.w_in : (long)B * e.h_out * e.w_out;      // one wave per node of the output side
       lz.run(tr ? PC_CONVT_BWD : PC_CONV_FWD, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a); });
       return;
     }
-    const float* At = tr ? de.w_bwd : de.w_fwd;
+    const float* At = tr ? de.w_bwd.get() : de.w_fwd.get();
     const int Ks = tr ? e.n_out : e.n_in, M = tr ? e.n_in : e.n_out, ld = tr ? de.ld_bwd : de.ld_fwd, MT = tr ? de.mt_bwd : de.mt_fwd;
     if (h->dense_lds && (tr ? de.kpad_bwd <= 128 : de.mt_fwd <= 4)) {
       const DenseLArgs a{At, src, nb, B, Ks, M, ld, MT, tr ? de.kpad_bwd : de.kpad_fwd};
@@ -1275,7 +1029,7 @@ struct Forward {
       lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(kern, dim3(B), dim3(512), 0, st, a); });
       return;
     }
-    const DenseArgs a{At, src, nb, h->d_zero, B, Ks, M, ld, MT, tr ? de.ksq_bwd : de.ksq_fwd};
+    const DenseArgs a{At, src, nb, h->d_zero.get(), B, Ks, M, ld, MT, tr ? de.ksq_bwd : de.ksq_fwd};
     const long tiles = (long)B * MT;
     void (*kern)(DenseArgs) = kDenseAgg[Ks >= 512 ? 0 : 1];
     lz.run(PC_DENSE_AGG, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)(Ks >= 512 ? tiles : (tiles + 3) / 4)), dim3(256), 0, st, a); });
@@ -1287,7 +1041,7 @@ struct Forward {
   // the scored gather of the restricted last step over edge k + 1 into layer k (k_gather_scored, k_scored_tail)
   GSArgs scored_gather_args(int k, float* out, float* sout) const {
     const Edge& e = h->edges[k + 1];
-    return GSArgs{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd, in->lb[k + 1], in->ub[k + 1], out, sout,
+    return GSArgs{ilist(w.score[k]), cnt + 4 * k + 2, mu(k + 1), h->dev[k + 1].w_bwd.get(), in->lb[k + 1], in->ub[k + 1], out, sout,
                   h->N[k], e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, 1};
   }
   void agg_bwd(int k, bool scored) {   // nb <- A_{k+1}^T mu[k+1]  (k+1 <= L), divided by the tap count above the input layer
@@ -1321,7 +1075,7 @@ struct Forward {
     if (fwd) {
       pack = src_proj == L_INP_F_1 ? PK_UPD_FWD_E : (src_proj == L_INP_B2_2 ? PK_UPD_FWD_I : PK_UPD_FWD_F);
       sarr = ws + w.sf[k];
-      if (k == 1 && p.s1_table) { sarr = h->d_s1; smod = h->N[1]; }      // the input layer is all live: one table for every sample
+      if (k == 1 && p.s1_table) { sarr = h->d_s1.get(); smod = h->N[1]; }      // the input layer is all live: one table for every sample
     } else if (k < L) {
       pack = PK_UPD_BWD_B;
       sarr = ws + w.sb[k];
@@ -1386,7 +1140,7 @@ struct Forward {
       const DevGather& d = h->gb[1];
       const long nt = map_tiles(d.g.tm, B);
       // the sparse walk over the live rows of layer 1, which also yields the bias sums (s_from_gather)
-      GIArgs a{h->d_pack[PK_PRE_INP], h->d_pack[PK_UPD_INP], in->lb[0], in->ub[0], rows1_for_input, ws + w.sb[0], mu(0), nt, to_dtm(d.g.tm), to_dg(d, h->d_zero),
+      GIArgs a{h->d_pack[PK_PRE_INP], h->d_pack[PK_UPD_INP], in->lb[0], in->ub[0], rows1_for_input, ws + w.sb[0], mu(0), nt, to_dtm(d.g.tm), to_dg(d, h->d_zero.get()),
                in->lb[1], in->ub[1], 1};
       const size_t lds = gather_lds_bytes(d, PackUpdInp::FLOATS + PackPreInp::FLOATS) + 8 + (size_t)WAVES_MLP * (2 * d.g.K2 + 32) * 8;
       constexpr int kGiuOcc = 2;        // workgroups per CU (<= 128 VGPRs: two 8-wave workgroups fit)
@@ -1409,8 +1163,8 @@ struct Forward {
     const Edge& e = h->edges[L];
     const DevEdge& de = h->dev[L];
     TopArgs a{};
-    a.df = DenseLArgs{de.w_fwd, mu(L - 1), nullptr, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
-    a.db = DenseLArgs{de.w_bwd, nullptr, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
+    a.df = DenseLArgs{de.w_fwd.get(), mu(L - 1), nullptr, B, e.n_in, e.n_out, de.ld_fwd, de.mt_fwd, de.kpad_fwd};
+    a.db = DenseLArgs{de.w_bwd.get(), nullptr, nb, B, e.n_out, e.n_in, de.ld_bwd, de.mt_bwd, de.kpad_bwd};
     a.pack_f = h->d_pack[PK_UPD_FWD_F]; a.pack_b = h->d_pack[PK_UPD_BWD]; a.pack_p = h->d_pack[PK_PROP];
     a.Pf = ws + w.Pf[L]; a.Pb = ws + w.Pb[L];
     a.sf = p.top_s_fwd ? nullptr : ws + w.sf[L];              // null: F1 walks exactly the live rows of layer L-1 and sums its weights itself
@@ -1495,13 +1249,13 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
     slot = 0;
     for (int i = 1; i < 8; ++i)
       if (h->ctl_age[i] < h->ctl_age[slot]) slot = i;
-    HIPCHK(hipMemsetAsync(h->d_ctl + 64 * slot, 0, 64 * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(h->d_ctl.get() + 64 * slot, 0, 64 * sizeof(int), st));
     h->ctl_ws[slot] = workspace;
   }
   h->ctl_age[slot] = ++h->ctl_clock;
 
   const Plan p = make_plan(h, B, h->halfpass_limit);
-  Forward f(h, in, B, p, w, workspace, scores, decisions, status, st, h->d_ctl + 64 * slot);
+  Forward f(h, in, B, p, w, workspace, scores, decisions, status, st, h->d_ctl.get() + 64 * slot);
   f.classify();
   f.livesum();
   f.input_embedding();
@@ -1574,35 +1328,16 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
     if (at.type == hipMemoryTypeDevice) return fail(GNNB_E_INVALID, "gnnb_forward_host: an input pointer is device memory; this entry point takes host pointers (gnnb_forward takes device pointers)");
   }
   // ---- buffers
-  if (h->hs_floats < total) {
-    if (h->hs_pinned) (void)hipHostFree(h->hs_pinned);
-    if (h->hs_dev) (void)hipFree(h->hs_dev);
-    h->hs_pinned = nullptr; h->hs_dev = nullptr; h->hs_floats = 0;
-    HIPCHK(hipHostMalloc((void**)&h->hs_pinned, total * sizeof(float), hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&h->hs_dev, total * sizeof(float)));
-    h->hs_floats = total;
-  }
-  const size_t wsb = gnnb_workspace_bytes(h, B);
-  if (h->hs_ws_bytes < wsb) {
-    if (h->hs_ws) (void)hipFree(h->hs_ws);
-    h->hs_ws = nullptr; h->hs_ws_bytes = 0;
-    HIPCHK(hipMalloc(&h->hs_ws, wsb));
-    h->hs_ws_bytes = wsb;
-  }
-  if (h->hs_out_B < (size_t)B) {
-    if (h->hs_scores) (void)hipFree(h->hs_scores);
-    if (h->hs_dec) (void)hipFree(h->hs_dec);
-    if (h->hs_out_pinned) (void)hipHostFree(h->hs_out_pinned);
-    h->hs_scores = nullptr; h->hs_dec = nullptr; h->hs_out_pinned = nullptr; h->hs_out_B = 0;
-    HIPCHK(hipMalloc((void**)&h->hs_scores, (size_t)B * R * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&h->hs_dec, ((size_t)B * 2 + 1) * sizeof(int32_t)));          // decisions, then the status word
-    HIPCHK(hipHostMalloc((void**)&h->hs_out_pinned, ((size_t)B * R + (size_t)B * 2 + 1) * sizeof(float), hipHostMallocDefault));
-    h->hs_out_B = B;
-  }
+  HIPCHK(h->hs_pinned.grow(total));
+  HIPCHK(h->hs_dev.grow(total));
+  HIPCHK(h->hs_ws.grow(gnnb_workspace_bytes(h, B)));
+  HIPCHK(h->hs_scores.grow((size_t)B * R));
+  HIPCHK(h->hs_dec.grow((size_t)B * 2 + 1));          // decisions, then the status word
+  HIPCHK(h->hs_out_pinned.grow((size_t)B * R + (size_t)B * 2 + 1));
   // ---- stage, one transfer, forward
   // staging: one memcpy per input tensor; big batches (36.5 MB at base B = 256: 2.3 ms on one thread) are split over a few helper threads
   if (total * sizeof(float) < (size_t)4 << 20) {
-    for (const Slot& sl : slots) memcpy(h->hs_pinned + sl.off, sl.src, sl.n * sizeof(float));
+    for (const Slot& sl : slots) memcpy(h->hs_pinned.get() + sl.off, sl.src, sl.n * sizeof(float));
   } else {
     const int nthr = 8;
     const size_t chunk = (size_t)1 << 18;                 // floats (1 MB) per work item
@@ -1614,7 +1349,7 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
       for (size_t it = next.fetch_add(1); it < items.size(); it = next.fetch_add(1)) {
         const Slot& sl = slots[items[it].first];
         const size_t o = items[it].second, n = std::min(chunk, sl.n - o);
-        memcpy(h->hs_pinned + sl.off + o, sl.src + o, n * sizeof(float));
+        memcpy(h->hs_pinned.get() + sl.off + o, sl.src + o, n * sizeof(float));
       }
     };
     std::vector<std::thread> pool;
@@ -1622,19 +1357,20 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
     work();
     for (auto& t : pool) t.join();
   }
-  HIPCHK(hipMemcpyAsync(h->hs_dev, h->hs_pinned, total * sizeof(float), hipMemcpyHostToDevice, st));
+  float* const dev = h->hs_dev.get();
+  HIPCHK(hipMemcpyAsync(dev, h->hs_pinned.get(), total * sizeof(float), hipMemcpyHostToDevice, st));
   std::vector<const float*> lb(K + 1), ub(K + 1), dual(L), prim(in->n_primal);
-  for (int k = 0; k <= K; ++k) { lb[k] = h->hs_dev + slots[i_lb[k]].off; ub[k] = h->hs_dev + slots[i_ub[k]].off; }
-  for (int k = 0; k < L; ++k) dual[k] = h->hs_dev + slots[i_dual[k]].off;
-  for (int m = 0; m < in->n_primal; ++m) prim[m] = i_prim[m] == (size_t)-1 ? h->hs_dev : h->hs_dev + slots[i_prim[m]].off;   // (unread ones: any valid pointer)
-  gnnb_batch dv{lb.data(), ub.data(), dual.data(), prim.data(), h->hs_dev + slots[i_x].off, h->hs_dev + slots[i_pw].off,
-                h->hs_dev + slots[i_pb].off, h->hs_dev + slots[i_mask].off, in->n_graph, in->n_relu, in->n_primal};
-  int32_t* d_status = h->hs_dec + (size_t)B * 2;
-  if (int rc = gnnb_forward(h, &dv, B, h->hs_scores, h->hs_dec, d_status, h->hs_ws, h->hs_ws_bytes, stream)) return rc;
-  int32_t* out_i = reinterpret_cast<int32_t*>(h->hs_out_pinned);
-  HIPCHK(hipMemcpyAsync(out_i, h->hs_dec, ((size_t)B * 2 + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  float* out_s = h->hs_out_pinned + (size_t)B * 2 + 1;
-  if (scores) HIPCHK(hipMemcpyAsync(out_s, h->hs_scores, (size_t)B * R * sizeof(float), hipMemcpyDeviceToHost, st));
+  for (int k = 0; k <= K; ++k) { lb[k] = dev + slots[i_lb[k]].off; ub[k] = dev + slots[i_ub[k]].off; }
+  for (int k = 0; k < L; ++k) dual[k] = dev + slots[i_dual[k]].off;
+  for (int m = 0; m < in->n_primal; ++m) prim[m] = i_prim[m] == (size_t)-1 ? dev : dev + slots[i_prim[m]].off;   // (unread ones: any valid pointer)
+  gnnb_batch dv{lb.data(), ub.data(), dual.data(), prim.data(), dev + slots[i_x].off, dev + slots[i_pw].off,
+                dev + slots[i_pb].off, dev + slots[i_mask].off, in->n_graph, in->n_relu, in->n_primal};
+  int32_t* const d_dec = h->hs_dec.get();
+  if (int rc = gnnb_forward(h, &dv, B, h->hs_scores.get(), d_dec, d_dec + (size_t)B * 2, h->hs_ws.get(), h->hs_ws.size(), stream)) return rc;
+  int32_t* out_i = reinterpret_cast<int32_t*>(h->hs_out_pinned.get());
+  HIPCHK(hipMemcpyAsync(out_i, d_dec, ((size_t)B * 2 + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  float* out_s = h->hs_out_pinned.get() + (size_t)B * 2 + 1;
+  if (scores) HIPCHK(hipMemcpyAsync(out_s, h->hs_scores.get(), (size_t)B * R * sizeof(float), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   memcpy(decisions, out_i, (size_t)B * 2 * sizeof(int32_t));
   *status = out_i[(size_t)B * 2];
@@ -1772,12 +1508,12 @@ extern "C" int gnnb_babsr(gnnb_t* h, const float* const* lb, const float* const*
   for (int k = 1; k <= L; ++k) {
     const int i = k - 1;
     if (!lb[k] || !ub[k]) return fail(GNNB_E_INVALID, "gnnb_babsr: null bounds pointer for graph layer %d", k);
-    a.lb[i] = lb[k]; a.ub[i] = ub[k]; a.bias[i] = h->dev[k].bias; a.N[i] = h->N[k]; a.hw[i] = h->hw[k]; a.off[i] = off;
+    a.lb[i] = lb[k]; a.ub[i] = ub[k]; a.bias[i] = h->dev[k].bias.get(); a.N[i] = h->N[k]; a.hw[i] = h->hw[k]; a.off[i] = off;
     off += h->N[k];
     maxN = std::max(maxN, h->N[k]);
     if (k < L) {                              // edge k+1 (between graph layers k and k+1)
       const Edge& e = h->edges[k + 1];
-      a.ekind[i] = e.kind; a.ew[i] = h->dev[k + 1].w_bwd;
+      a.ekind[i] = e.kind; a.ew[i] = h->dev[k + 1].w_bwd.get();
       a.c_in[i] = e.c_in; a.h_in[i] = e.h_in; a.w_in[i] = e.w_in; a.c_out[i] = e.c_out; a.h_out[i] = e.h_out; a.w_out[i] = e.w_out;
       a.kh[i] = e.kh; a.kw[i] = e.kw; a.stride[i] = e.stride; a.pad[i] = e.pad; a.ld[i] = h->dev[k + 1].ld_bwd;
     }
@@ -1944,37 +1680,36 @@ extern "C" int gnnb_set_weights(gnnb_t* h, const float* w_blob, size_t n_floats)
   if (n_floats != blob_floats()) return fail(GNNB_E_INVALID, "gnnb_set_weights: %zu floats, expected %zu", n_floats, blob_floats());
   HIPCHK(hipDeviceSynchronize());          // no forward may still be reading the packs
   if (int rc = load_weights(h, w_blob, nullptr)) return rc;
-  if (h->trainer) HIPCHK(hipMemcpy(h->trainer->d_w, w_blob, n_floats * sizeof(float), hipMemcpyHostToDevice));
+  if (h->trainer) HIPCHK(hipMemcpy(h->trainer->d_w.get(), w_blob, n_floats * sizeof(float), hipMemcpyHostToDevice));
   return GNNB_OK;
 }
 
 // torch.optim.Adam(model.parameters(), lr, weight_decay) of graph_score_online.py:15; the moments start at zero
 extern "C" int gnnb_online_create(gnnb_t* h, float lr, float weight_decay) {
   if (!h) return fail(GNNB_E_INVALID, "gnnb_online_create: null handle");
-  free_trainer(h);
-  gnnb_train::Trainer* t = new gnnb_train::Trainer();
-  h->trainer = t;
+  h->trainer.reset(new gnnb_train::Trainer());
+  gnnb_train::Trainer* t = h->trainer.get();
   t->lr = lr; t->wd = weight_decay;
   const size_t n = blob_floats();
-  for (float** p : {&t->d_w, &t->d_g, &t->d_m, &t->d_v}) {
-    HIPCHK(hipMalloc((void**)p, n * sizeof(float)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(float)));
+  for (DevBuf<float>* p : {&t->d_w, &t->d_g, &t->d_m, &t->d_v}) {
+    HIPCHK(p->alloc(n));
+    HIPCHK(hipMemset(p->get(), 0, n * sizeof(float)));
   }
-  HIPCHK(hipMemcpy(t->d_w, h->blob.data(), n * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipHostMalloc((void**)&t->desc, sizeof(gnnb_train::TChain) * gnnb_train::Trainer::kDescCap, hipHostMallocDefault));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd_multi<TL_ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd_multi<TL_ROWS_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd_multi<TL_ROWS_TINY>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd<TL_ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd<TL_ROWS_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void*)gnnb_train::k_tchain_fwd<TL_ROWS_TINY>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+  HIPCHK(hipMemcpy(t->d_w.get(), h->blob.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(t->desc.alloc(gnnb_train::Trainer::kDescCap));
+  using namespace gnnb_train;
+  static const LdsAttr attrs[] = {
+      {k_tchain_fwd_multi<TL_ROWS>, 96 * 1024}, {k_tchain_fwd_multi<TL_ROWS_SMALL>, 96 * 1024}, {k_tchain_fwd_multi<TL_ROWS_TINY>, 96 * 1024},
+      {k_tchain_fwd<TL_ROWS>, 96 * 1024}, {k_tchain_fwd<TL_ROWS_SMALL>, 96 * 1024}, {k_tchain_fwd<TL_ROWS_TINY>, 96 * 1024},
+  };
+  for (const LdsAttr& a : attrs) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.bytes));
   return GNNB_OK;
 }
 
 extern "C" int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats) {
   if (!h || !grad || !h->trainer) return fail(GNNB_E_STATE, "gnnb_online_grad: no trainer (gnnb_online_create)");
   if (n_floats != blob_floats()) return fail(GNNB_E_INVALID, "gnnb_online_grad: %zu floats, expected %zu", n_floats, blob_floats());
-  HIPCHK(hipMemcpy(grad, h->trainer->d_g, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(grad, h->trainer->d_g.get(), n_floats * sizeof(float), hipMemcpyDeviceToHost));
   return GNNB_OK;
 }
 
@@ -2016,27 +1751,22 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   t.tape.clear();
   t.ndesc = 0;
   if (t.arena.reset(st)) return fail(GNNB_E_HIP, "gnnb_online_step: arena reset failed");
-  if (t.edge_w.empty()) {                                  // torch-layout copies of the verified network's weights
-    t.edge_w.assign(h->edges.size(), nullptr);
-    for (int k = 1; k <= L; ++k)
-      if (int rc = upload(&t.edge_w[k], h->edges[k].w.data(), h->edges[k].w.size())) return rc;
+  if (h->edge_w.empty()) {                                 // torch-layout copies of the verified network's weights: they belong to the bound network
+    std::vector<DevBuf<float>> ew(h->edges.size());
+    for (int k = 1; k <= L; ++k) HIPCHK(ew[k].upload(h->edges[k].w.data(), h->edges[k].w.size()));
+    h->edge_w = std::move(ew);
   }
-  if (t.cap_B < B) {
-    for (float** p : {&t.d_scores, &t.d_ds, &t.d_loss, &t.d_imp}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (t.d_kw) (void)hipFree(t.d_kw);
-    if (t.d_sel) (void)hipFree(t.d_sel);
-    HIPCHK(hipMalloc((void**)&t.d_sel, (size_t)B * 8));
-    HIPCHK(hipMalloc((void**)&t.d_scores, (size_t)B * R * 4));
-    HIPCHK(hipMalloc((void**)&t.d_ds, (size_t)B * R * 4));
-    HIPCHK(hipMalloc((void**)&t.d_loss, (size_t)B * 4));
-    HIPCHK(hipMalloc((void**)&t.d_imp, (size_t)B * 4));
-    HIPCHK(hipMalloc((void**)&t.d_kw, (size_t)B * 4));
-    t.cap_B = B;
-  }
-  HIPCHK(hipMemcpyAsync(t.d_kw, kw_index, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(t.d_imp, improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(t.d_ds, 0, (size_t)B * R * 4, st));
-  HIPCHK(hipMemsetAsync(t.d_g, 0, blob_floats() * 4, st));
+  HIPCHK(t.d_sel.grow((size_t)B * 2));
+  HIPCHK(t.d_scores.grow((size_t)B * R));
+  HIPCHK(t.d_ds.grow((size_t)B * R));
+  HIPCHK(t.d_loss.grow(B));
+  HIPCHK(t.d_imp.grow(B));
+  HIPCHK(t.d_kw.grow(B));
+  float *const d_w = t.d_w.get(), *const d_g = t.d_g.get(), *const d_scores = t.d_scores.get(), *const d_ds = t.d_ds.get();
+  HIPCHK(hipMemcpyAsync(t.d_kw.get(), kw_index, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.d_imp.get(), improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d_ds, 0, (size_t)B * R * 4, st));
+  HIPCHK(hipMemsetAsync(d_g, 0, blob_floats() * 4, st));
 
   // ---- per-node constants ----
   struct LC { float *r0, *r1, *amb, *live, *nd2, *d1, *ff, *fb; Trainer::List ambl, livel; };
@@ -2057,7 +1787,7 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
       int* buf = reinterpret_cast<int*>(t.arena.alloc(2 * n + 2));
       if (t.arena.err || !buf) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
       const int q = h->relu_q[k];
-      pm.a[k - 1] = TPrepArgs{in->lb[k], in->ub[k], in->dual[k - 1], in->primal[q - 1], in->primal[q], h->dev[k].bias, h->N[k], h->hw[k], n,
+      pm.a[k - 1] = TPrepArgs{in->lb[k], in->ub[k], in->dual[k - 1], in->primal[q - 1], in->primal[q], h->dev[k].bias.get(), h->N[k], h->hw[k], n,
                               c.r0, c.r1, c.amb, c.live, c.nd2, c.d1, c.ff, c.fb};
       c.ambl = Trainer::List{buf, buf + 2 * n, n};
       c.livel = Trainer::List{buf + n, buf + 2 * n + 1, n};
@@ -2088,14 +1818,14 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     const Edge& e = h->edges[k];
     TT y = t.rows((long)B * (dir == 0 ? h->N[k] : h->N[k - 1]));
     if (e.kind == 0) {
-      TConv a{src.v, y.v, t.edge_w[k], B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, dir, norm, 0};
+      TConv a{src.v, y.v, h->edge_w[k].get(), B, e.c_in, e.h_in, e.w_in, e.c_out, e.h_out, e.w_out, e.kh, e.kw, e.stride, e.pad, dir, norm, 0};
       hipLaunchKernelGGL(k_tconv, dim3((unsigned)((y.n + 3) / 4)), dim3(256), 0, st, a);
       TConv b = a;
       b.src = y.g; b.dst = src.g; b.dir = 1 - dir; b.acc = 1;
       const long nsrc = src.n;
       t.tape.push_back([b, nsrc, st]() { hipLaunchKernelGGL(k_tconv, dim3((unsigned)((nsrc + 3) / 4)), dim3(256), 0, st, b); });
     } else {
-      TDense a{t.edge_w[k], 0, src.v, y.v, B, e.n_out, e.n_in, dir, 0};
+      TDense a{h->edge_w[k].get(), 0, src.v, y.v, B, e.n_out, e.n_in, dir, 0};
       hipLaunchKernelGGL(k_tdense, dim3((unsigned)y.n), dim3(TD_WAVES * 64), 0, st, a);
       TDense b = a;
       b.src = y.g; b.dst = src.g; b.dir = 1 - dir; b.acc = 1;
@@ -2191,8 +1921,8 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     for (int k = 1; k <= L; ++k) {
       const long n = (long)B * h->N[k];
       nmax = n > nmax ? n : nmax;
-      sm.a[k - 1] = TScore{hk[k - 1][0].v, hk[k - 1][0].g, t.d_w + weight_offset(L_FSCORE), t.d_w + bias_offset(L_FSCORE), in->mask, t.d_scores,
-                           t.d_ds, h->N[k], R, off, n, t.d_g + weight_offset(L_FSCORE), t.d_g + bias_offset(L_FSCORE), t.d_sel, B};
+      sm.a[k - 1] = TScore{hk[k - 1][0].v, hk[k - 1][0].g, d_w + weight_offset(L_FSCORE), d_w + bias_offset(L_FSCORE), in->mask, d_scores,
+                           d_ds, h->N[k], R, off, n, d_g + weight_offset(L_FSCORE), d_g + bias_offset(L_FSCORE), t.d_sel.get(), B};
       off += h->N[k];
     }
     const dim3 grid((unsigned)((nmax + 3) / 4), (unsigned)L);
@@ -2203,8 +1933,8 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     });
   }
   if (t.arena.err) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
-  if (scores_padded) HIPCHK(hipMemcpyAsync(scores_padded, t.d_scores, (size_t)B * R * 4, hipMemcpyDeviceToDevice, st));
-  TLoss la{t.d_scores, t.d_ds, t.d_kw, t.d_imp, t.d_loss, R, t.d_sel};
+  if (scores_padded) HIPCHK(hipMemcpyAsync(scores_padded, d_scores, (size_t)B * R * 4, hipMemcpyDeviceToDevice, st));
+  TLoss la{d_scores, d_ds, t.d_kw.get(), t.d_imp.get(), t.d_loss.get(), R, t.d_sel.get()};
   hipLaunchKernelGGL(k_tloss, dim3(B), dim3(256), 0, st, la);
   // ---- backward: the tape in reverse ----
   t.wops.clear();
@@ -2216,16 +1946,16 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   if (e != hipSuccess) return fail(GNNB_E_HIP, "gnnb_online_step: a launch failed: %s", hipGetErrorString(e));
   if (loss) {
     t.h_loss.resize(B);
-    HIPCHK(hipMemcpyAsync(t.h_loss.data(), t.d_loss, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(t.h_loss.data(), t.d_loss.get(), (size_t)B * 4, hipMemcpyDeviceToHost, st));
   }
   if (apply) {
     t.step += 1;
     const double b1 = 0.9, b2 = 0.999;
     const double bc1 = 1.0 - std::pow(b1, t.step), bc2 = 1.0 - std::pow(b2, t.step);
-    TAdam a{t.d_w, t.d_g, t.d_m, t.d_v, (int)blob_floats(), (float)(t.lr / bc1), t.wd, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-8f, (float)std::sqrt(bc2)};
+    TAdam a{d_w, d_g, t.d_m.get(), t.d_v.get(), (int)blob_floats(), (float)(t.lr / bc1), t.wd, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-8f, (float)std::sqrt(bc2)};
     hipLaunchKernelGGL(k_tadam, dim3((unsigned)((blob_floats() + 255) / 256)), dim3(256), 0, st, a);
     std::vector<float> nw(blob_floats());
-    HIPCHK(hipMemcpyAsync(nw.data(), t.d_w, nw.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(nw.data(), d_w, nw.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (int rc = load_weights(h, nw.data(), st)) return rc;      // the scorer's folded packs follow the new parameters
   } else {

@@ -17,13 +17,19 @@
 // next layer takes register R = s of the fragment; half h of the wave then contributes input feature
 // f(s,h), and the A operand of that k-step must hold W[out][f(s,h)] -- the permutation baked in here.
 #pragma once
+#include <algorithm>
+#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include <thread>
 #include <system_error>
+
+#include "../../include/gnnb.h"
 
 namespace gnnb {
 
@@ -640,6 +646,233 @@ inline bool build_gather(const Edge& e, int dir, bool normalise, GatherHost& bes
   best.g.normalise = normalise ? 1 : 0;
   fill_gather_tables(e, dir, best);
   return true;
+}
+
+// ------------------------------------------------------------------------------------------
+// The host half of gnnb_bind_network: the layer list as a layer graph, and the host images of what bind uploads.
+// Pure functions of their arguments (tests/test_pack_cpu.py); gnnb.hip only uploads what they return.
+// ------------------------------------------------------------------------------------------
+// limits of the kernels (gnnb.hip asserts that they are the kernels' own constants)
+constexpr int kMaxReluLayers = 8;          // MAXL: ReLU layers the merged per-layer kernels take
+constexpr int kMaxLayerNodes = 40000;      // LIVESUM_MAXSRC: source nodes of a sample k_livesum holds in LDS
+constexpr int kDenseChunk = 8;             // DENSE_CH: k-steps per chunk of the per-tile Linear kernel
+
+struct LayerGraph {
+  std::vector<int> N;            // graph layer sizes, N[0..L+1] (N[L+1] = 1: the property node)
+  std::vector<Edge> edges;       // edges[k], k = 1..L (edges[0] unused)
+  std::vector<int> relu_q;       // fixed-layer index of the ReLU of graph layer k
+  std::vector<int> hw;           // nodes per bias entry of layer k
+  int n_fixed = 0, R = 0;        // fixed layers in the list; ReLU nodes in all
+};
+
+inline std::string strf(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return buf;
+}
+
+// The fixed layers (conv / linear / relu / flatten) on a c0 x h0 x w0 input as a layer graph: one graph layer per ReLU.
+// Returns the refusal, or an empty string and the graph in `g`.
+inline std::string parse_layers(const gnnb_layer_desc* L, int n, int c0, int h0, int w0, LayerGraph& g) {
+  g = LayerGraph();
+  int C = c0, H = h0, W = w0;
+  bool flat = false;
+  int nflat = c0 * h0 * w0;
+  g.N.push_back(nflat);
+  g.edges.emplace_back();
+  g.relu_q.push_back(-1);
+  g.hw.push_back(1);
+  Edge pend;
+  bool have = false;
+  int pend_hw = 1;
+  for (int q = 0; q < n; ++q) {
+    const gnnb_layer_desc& d = L[q];
+    if (d.kind == GNNB_CONV) {
+      if (flat) return strf("layer %d: conv after flatten", q);
+      if (have) return strf("layer %d: two linear maps without a ReLU between them", q);
+      if (d.c_in != C) return strf("layer %d: conv expects %d input channels, graph has %d", q, d.c_in, C);
+      if (!d.weight || !d.bias) return strf("layer %d: null weight/bias", q);
+      Edge e;
+      e.kind = 0;
+      e.c_in = C; e.h_in = H; e.w_in = W; e.c_out = d.c_out; e.kh = d.kh; e.kw = d.kw; e.stride = d.stride; e.pad = d.pad;
+      if (d.stride < 1 || d.kh < 1 || d.kw < 1) return strf("layer %d: bad conv geometry", q);
+      if ((H + 2 * d.pad - d.kh) % d.stride || (W + 2 * d.pad - d.kw) % d.stride)
+        return strf("layer %d: conv geometry leaves a remainder (conv_transpose2d of the reference would need output_padding)", q);
+      e.h_out = (H + 2 * d.pad - d.kh) / d.stride + 1;
+      e.w_out = (W + 2 * d.pad - d.kw) / d.stride + 1;
+      e.n_in = C * H * W;
+      e.n_out = e.c_out * e.h_out * e.w_out;
+      e.w.assign(d.weight, d.weight + (size_t)e.c_out * e.c_in * e.kh * e.kw);
+      e.b.assign(d.bias, d.bias + e.c_out);
+      C = e.c_out; H = e.h_out; W = e.w_out;
+      nflat = e.n_out;
+      pend_hw = H * W;
+      pend = e;
+      have = true;
+    } else if (d.kind == GNNB_LINEAR) {
+      if (have) return strf("layer %d: two linear maps without a ReLU between them", q);
+      if (d.n_in != nflat) return strf("layer %d: linear expects %d inputs, graph has %d", q, d.n_in, nflat);
+      if (!d.weight || !d.bias) return strf("layer %d: null weight/bias", q);
+      Edge e;
+      e.kind = 1;
+      e.n_in = d.n_in; e.n_out = d.n_out;
+      e.c_in = e.h_in = e.w_in = e.c_out = e.h_out = e.w_out = e.kh = e.kw = e.stride = e.pad = 0;
+      e.w.assign(d.weight, d.weight + (size_t)d.n_out * d.n_in);
+      e.b.assign(d.bias, d.bias + d.n_out);
+      nflat = d.n_out;
+      flat = true;
+      pend_hw = 1;
+      pend = e;
+      have = true;
+    } else if (d.kind == GNNB_RELU) {
+      if (!have) return strf("layer %d: ReLU without a preceding conv/linear", q);
+      g.N.push_back(nflat);
+      g.edges.push_back(pend);
+      g.relu_q.push_back(q);
+      g.hw.push_back(pend_hw);
+      have = false;
+    } else if (d.kind == GNNB_FLATTEN) {
+      flat = true;
+    } else {
+      return strf("layer %d: unknown kind %d", q, d.kind);
+    }
+  }
+  if (have) return "fixed layers must end after a ReLU (the property layer is passed per batch)";
+  const int Lr = (int)g.N.size() - 1;
+  if (Lr < 1 || Lr > kMaxReluLayers) return strf("unsupported number of ReLU layers %d (max %d)", Lr, kMaxReluLayers);
+  g.N.push_back(1);   // property node
+  g.n_fixed = n;
+  for (int k = 1; k <= Lr; ++k) g.R += g.N[k];
+  for (int k = 0; k <= Lr; ++k)
+    if (g.N[k] > kMaxLayerNodes) return strf("graph layer %d has %d nodes, more than the %d k_livesum holds in LDS", k, g.N[k], kMaxLayerNodes);
+  return "";
+}
+
+// Row sums of edge 1 (for a conv: of the taps inside the image): the bias sums of the edge over the all-live input layer, the
+// weights that reach each node added in fp32 in torch-layout order.
+inline std::vector<float> edge1_row_sums(const Edge& e) {
+  std::vector<float> s1(e.n_out, 0.0f);
+  if (e.kind == 0) {
+    for (int co = 0; co < e.c_out; ++co)
+      for (int oy = 0; oy < e.h_out; ++oy)
+        for (int ox = 0; ox < e.w_out; ++ox) {
+          float acc = 0.0f;
+          for (int ci = 0; ci < e.c_in; ++ci)
+            for (int ky = 0; ky < e.kh; ++ky) {
+              const int iy = oy * e.stride - e.pad + ky;
+              if (iy < 0 || iy >= e.h_in) continue;
+              for (int kx = 0; kx < e.kw; ++kx) {
+                const int ix = ox * e.stride - e.pad + kx;
+                if (ix < 0 || ix >= e.w_in) continue;
+                acc += e.w[(((size_t)co * e.c_in + ci) * e.kh + ky) * e.kw + kx];
+              }
+            }
+          s1[((size_t)co * e.h_out + oy) * e.w_out + ox] = acc;
+        }
+  } else {
+    for (int i = 0; i < e.n_out; ++i) {
+      float acc = 0.0f;
+      for (int q = 0; q < e.n_in; ++q) acc += e.w[(size_t)i * e.n_in + q];
+      s1[i] = acc;
+    }
+  }
+  return s1;
+}
+
+// The operands of a Linear edge for the dense kernels: At[k][i] = A[i][k], zero-padded to 32 * mt columns (ld) and to the rows the
+// kernels read past K: 8 * ksq (ksq = k-steps per wave of the per-tile kernel) + 2 chunks, or kpad (the LDS kernels' K) + 32 forward /
+// + 64 transposed (k_dense_bwd_lds reads up to 3 chunks past kpad).
+struct DenseGeom { int ld_fwd = 0, mt_fwd = 0, ksq_fwd = 0, ld_bwd = 0, mt_bwd = 0, ksq_bwd = 0, kpad_fwd = 0, kpad_bwd = 0; };
+struct DenseHost {
+  DenseGeom g;
+  std::vector<float> fwd, bwd;     // forward: A = W, k = input node, [k][o]; transposed: A = W^T, k = output node, [k][i]
+};
+inline DenseHost dense_operands(const Edge& e) {
+  DenseHost d;
+  DenseGeom& g = d.g;
+  auto ksq_of = [](int K) { return (((K + 1) / 2 + 3) / 4 + kDenseChunk - 1) / kDenseChunk * kDenseChunk; };
+  g.mt_fwd = (e.n_out + 31) / 32;
+  g.ld_fwd = g.mt_fwd * 32;
+  g.ksq_fwd = ksq_of(e.n_in);
+  g.kpad_fwd = (e.n_in + 63) / 64 * 64;
+  g.mt_bwd = (e.n_in + 31) / 32;
+  g.ld_bwd = g.mt_bwd * 32;
+  g.ksq_bwd = ksq_of(e.n_out);
+  g.kpad_bwd = (e.n_out + 15) / 16 * 16;
+  const size_t rows_f = std::max<size_t>(8 * g.ksq_fwd + 2 * kDenseChunk, g.kpad_fwd + 32);
+  const size_t rows_b = std::max<size_t>(8 * g.ksq_bwd + 2 * kDenseChunk, g.kpad_bwd + 64);
+  d.fwd.assign(rows_f * g.ld_fwd, 0.f);
+  d.bwd.assign(rows_b * g.ld_bwd, 0.f);
+  for (int o = 0; o < e.n_out; ++o)
+    for (int i = 0; i < e.n_in; ++i) {
+      d.fwd[(size_t)i * g.ld_fwd + o] = e.w[(size_t)o * e.n_in + i];
+      d.bwd[(size_t)o * g.ld_bwd + i] = e.w[(size_t)o * e.n_in + i];
+    }
+  return d;
+}
+
+// Tile t of a sample as one word: channel group | block row << 8 | block column << 20.  False where a field overflows.
+inline bool tile_table(const TileMap& tm, std::vector<int>& tt) {
+  if (tm.NCG > 255 || tm.NBY > 4095 || tm.NBX > 4095) return false;
+  tt.resize(tm.TPS);
+  for (int t = 0; t < tm.TPS; ++t) {
+    const int cg = t / (tm.NBY * tm.NBX), rem = t % (tm.NBY * tm.NBX);
+    tt[t] = cg | ((rem / tm.NBX) << 8) | ((rem % tm.NBX) << 20);
+  }
+  return true;
+}
+
+// The transposed aggregate of an inner conv edge (graph layers k >= 2) is divided by the number of kernel taps that touch a pixel
+// (the reference's `freq`, graph_conv.py:306-312).  A stride larger than the kernel leaves pixels of layer k-1 that no window
+// reads: their count is 0 and the reference computes 0/0 and stops.  The scoring entry points refuse such a network instead of
+// letting the answer depend on which kernel the launch plan picks for the edge.  Returns the first such layer k (0: none) and
+// one of its unread pixels.  Edge 1 is not normalised (:360-376) and may have such pixels.
+inline int zero_tap_layer(const LayerGraph& g, int* y0, int* x0) {
+  const int L = (int)g.N.size() - 2;
+  for (int k = 2; k <= L; ++k) {
+    const Edge& e = g.edges[k];
+    if (e.kind != 0) continue;
+    auto unread = [&](int n_in, int n_out, int ksz) {      // first position of one axis that no window covers, -1: none
+      for (int t = 0; t < n_in; ++t) {
+        int taps = 0;
+        for (int o = 0; o < n_out; ++o) taps += (t >= o * e.stride - e.pad && t < o * e.stride - e.pad + ksz);
+        if (taps == 0) return t;
+      }
+      return -1;
+    };
+    const int y = unread(e.h_in, e.h_out, e.kh), x = unread(e.w_in, e.w_out, e.kw);
+    if (y >= 0 || x >= 0) {
+      *y0 = y >= 0 ? y : 0;
+      *x0 = x >= 0 ? x : 0;
+      return k;
+    }
+  }
+  return 0;
+}
+
+// The description the fp64 kernels share (gnnb_k_kw.h KwNet; a template because that header is device code): sizes, flat ReLU
+// offsets, every layer as (C, H, W), the geometry of the fixed edges.  The weight pointers of net.e[k] are the caller's.
+template <class Net>
+inline void fill_kw_geometry(Net& net, const LayerGraph& g) {
+  const int Lr = (int)g.N.size() - 2;
+  net = Net{};
+  net.L = Lr; net.R = g.R;
+  for (int k = 0; k <= Lr + 1; ++k) net.N[k] = g.N[k];
+  for (int k = 1; k <= Lr; ++k) {
+    net.off[k] = net.off[k - 1] + (k > 1 ? g.N[k - 1] : 0);
+    net.maxNr = std::max(net.maxNr, g.N[k]);
+    static_cast<EdgeGeom&>(net.e[k]) = g.edges[k];
+  }
+  for (int k = 0; k <= Lr; ++k) {
+    const Edge& e = g.edges[k == 0 ? 1 : k];
+    const bool conv = e.kind == 0;
+    net.lc[k] = conv ? (k == 0 ? e.c_in : e.c_out) : g.N[k];
+    net.lh[k] = conv ? (k == 0 ? e.h_in : e.h_out) : 1;
+    net.lw[k] = conv ? (k == 0 ? e.w_in : e.w_out) : 1;
+  }
 }
 
 }  // namespace gnnb

@@ -17,7 +17,7 @@
 // (op, row chunk), k_tlin_reduce_all adding the partials in tape order).  Every sum keeps the order of the one-launch-per-op form,
 // so values and gradients are bit-identical to it.
 //
-// Included at the end of gnnb.hip (one translation unit: it uses the bound network of gnnb_handle).
+// Included by gnnb.hip (one translation unit: it uses the bound network of gnnb_handle) behind gnnb_mem.h, whose owners hold its memory.
 #pragma once
 #include <functional>
 
@@ -27,29 +27,27 @@ typedef float tf4 __attribute__((ext_vector_type(4)));
 
 // ---- device memory: a bump arena, zeroed at the start of every step (gradient buffers start at 0) ----
 struct Arena {
-  struct Chunk { char* p; size_t cap, used; };
+  struct Chunk { DevBuf<char> p; size_t used; };      // (released with the arena)
   std::vector<Chunk> chunks;
   size_t chunk_bytes = (size_t)256 << 20;
   int err = 0;
   float* alloc(size_t nfloats) {
     const size_t bytes = (nfloats * 4 + 255) & ~(size_t)255;
     for (auto& c : chunks)
-      if (c.cap - c.used >= bytes) { float* r = (float*)(c.p + c.used); c.used += bytes; return r; }
-    Chunk c{nullptr, bytes > chunk_bytes ? bytes : chunk_bytes, 0};
-    if (hipMalloc((void**)&c.p, c.cap) != hipSuccess) { err = 1; return nullptr; }
-    if (hipMemset(c.p, 0, c.cap) != hipSuccess) { err = 1; return nullptr; }
-    c.used = bytes;
-    chunks.push_back(c);
-    return (float*)c.p;
+      if (c.p.size() - c.used >= bytes) { float* r = (float*)(c.p.get() + c.used); c.used += bytes; return r; }
+    Chunk c{{}, bytes};
+    const size_t cap = bytes > chunk_bytes ? bytes : chunk_bytes;
+    if (c.p.alloc(cap) != hipSuccess || hipMemset(c.p.get(), 0, cap) != hipSuccess) { err = 1; return nullptr; }
+    chunks.push_back(std::move(c));
+    return (float*)chunks.back().p.get();
   }
   int reset(hipStream_t st) {          // everything handed out so far back to zero, arena empty
     for (auto& c : chunks) {
-      if (c.used && hipMemsetAsync(c.p, 0, c.used, st) != hipSuccess) return 1;
+      if (c.used && hipMemsetAsync(c.p.get(), 0, c.used, st) != hipSuccess) return 1;
       c.used = 0;
     }
     return 0;
   }
-  void release() { for (auto& c : chunks) (void)hipFree(c.p); chunks.clear(); }
 };
 
 struct TT { float* v = nullptr; float* g = nullptr; long n = 0; };   // rows (n, 64): value and gradient
@@ -723,16 +721,15 @@ __global__ void k_tadam(TAdam a) {
 
 // ---- the tape ----
 struct Trainer {
-  float *d_w = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
+  DevBuf<float> d_w, d_g, d_m, d_v;      // parameters (blob order), their gradient, Adam's moments
   int step = 0;
   float lr = 1e-4f, wd = 1e-4f;
   Arena arena;
-  std::vector<float*> edge_w;            // torch-layout weights of the bound network's edges, device
   std::vector<std::function<void()>> tape;
   hipStream_t st = nullptr;
   int n_cu = 256;
-  float *d_scores = nullptr, *d_ds = nullptr, *d_loss = nullptr, *d_imp = nullptr; int *d_kw = nullptr, *d_sel = nullptr;
-  int cap_B = 0;
+  DevBuf<float> d_scores, d_ds, d_loss, d_imp;      // per batch, grown on demand (gnnb_online_step)
+  DevBuf<int> d_kw, d_sel;
   std::vector<float> h_loss;
 
   TT rows(long n) { TT t; t.n = n; t.v = arena.alloc((size_t)n * 64); t.g = arena.alloc((size_t)n * 64); return t; }
@@ -757,8 +754,8 @@ struct Trainer {
       TT y = rows(list && !sp.out_full ? list->cap : n);
       TLin& a = c.op[i];
       a.layer = sp.layer;
-      a.W = d_w + weight_offset(sp.layer); a.b = d_w + bias_offset(sp.layer);
-      a.gW = d_g + weight_offset(sp.layer); a.gb = d_g + bias_offset(sp.layer);
+      a.W = d_w.get() + weight_offset(sp.layer); a.b = d_w.get() + bias_offset(sp.layer);
+      a.gW = d_g.get() + weight_offset(sp.layer); a.gb = d_g.get() + bias_offset(sp.layer);
       a.K = kLin[sp.layer].in; a.nseg = (int)sp.segs.size(); a.kf = sp.feat ? a.K : 0;
       for (int j = 0; j < a.nseg; ++j) {
         a.seg[j] = sp.segs[j];
@@ -801,13 +798,14 @@ struct Trainer {
   // Several independent chains (the same chain of different ReLU layers) as ONE launch forward and one backward: blockIdx.y =
   // chain, the descriptors uploaded once and read from memory by both launches.  Returns the outputs per chain.
   struct Job { std::vector<Spec> specs; long n; const List* list; };
-  TChain* desc = nullptr;                // pinned, device-visible descriptor slots of the step in flight (every step ends in a sync)
+  PinnedBuf<TChain> desc;                // pinned, device-visible descriptor slots of the step in flight (every step ends in a sync)
   int ndesc = 0;
   static constexpr int kDescCap = 8 * T_MAXL;
   std::vector<std::vector<TT>> chain_multi(const std::vector<Job>& jobs) {
     std::vector<std::vector<TT>> outs;
     const int nj = (int)jobs.size();
-    if (!desc || ndesc + nj > kDescCap) { arena.err = true; return std::vector<std::vector<TT>>(nj, std::vector<TT>(TC_MAXOPS)); }
+    TChain* const slots = desc.get();
+    if (!slots || ndesc + nj > kDescCap) { arena.err = true; return std::vector<std::vector<TT>>(nj, std::vector<TT>(TC_MAXOPS)); }
     const int base = ndesc;
     long maxrows = 0;
     int Kmax = 0;
@@ -820,8 +818,8 @@ struct Trainer {
         TT y = rows(jb.list && !sp.out_full ? jb.list->cap : jb.n);
         TLin& a = c.op[i];
         a.layer = sp.layer;
-        a.W = d_w + weight_offset(sp.layer); a.b = d_w + bias_offset(sp.layer);
-        a.gW = d_g + weight_offset(sp.layer); a.gb = d_g + bias_offset(sp.layer);
+        a.W = d_w.get() + weight_offset(sp.layer); a.b = d_w.get() + bias_offset(sp.layer);
+        a.gW = d_g.get() + weight_offset(sp.layer); a.gb = d_g.get() + bias_offset(sp.layer);
         a.K = kLin[sp.layer].in; a.nseg = (int)sp.segs.size(); a.kf = sp.feat ? a.K : 0;
         for (int j = 0; j < a.nseg; ++j) {
           a.seg[j] = sp.segs[j];
@@ -840,17 +838,17 @@ struct Trainer {
       }
       const long nrows = jb.list ? jb.list->cap : jb.n;
       maxrows = nrows > maxrows ? nrows : maxrows;
-      desc[ndesc++] = c;
+      slots[ndesc++] = c;
       outs.push_back(out);
     }
-    const TChain* d_cs = desc + base;
+    const TChain* d_cs = slots + base;
     const int R = maxrows <= 16L * n_cu ? TL_ROWS_TINY : (maxrows <= 128L * n_cu ? TL_ROWS_SMALL : TL_ROWS);
     const dim3 grid((unsigned)((maxrows + R - 1) / R), (unsigned)nj);
     const size_t lds = ((size_t)(Kmax | 1) * 64 + (size_t)R * Kmax + (size_t)R * 64) * 4;
     if (R == TL_ROWS_TINY) hipLaunchKernelGGL(k_tchain_fwd_multi<TL_ROWS_TINY>, grid, dim3(256), lds, st, d_cs);
     else if (R == TL_ROWS_SMALL) hipLaunchKernelGGL(k_tchain_fwd_multi<TL_ROWS_SMALL>, grid, dim3(256), lds, st, d_cs);
     else hipLaunchKernelGGL(k_tchain_fwd_multi<TL_ROWS>, grid, dim3(256), lds, st, d_cs);
-    std::vector<TChain> cs(desc + base, desc + ndesc);
+    std::vector<TChain> cs(slots + base, slots + ndesc);
     tape.push_back([this, cs, d_cs, grid, R]() {
       bool any = false;
       for (const TChain& c : cs)

@@ -508,3 +508,188 @@ def test_gather_table_map_of_the_forward_geometry_archs(packlib):
     assert have[("fwg_gap", 1)][1] is False              # 3 -> 8 2x2 stride 3: no transposed tables (k_convT_bwd + k_input_update)
     # the neighbours of the table-less edges do have them
     assert have[("fwg_k7", 1)] == (True, True) and have[("fwg_valu", 1)] == (True, True)
+
+
+# ---- the host half of gnnb_bind_network (gnnb_pack.h parse_layers .. zero_tap_layer) ----
+def layer_list(spec, null_weight_at=None):
+    """(ctypes array, keep-alive) of a layer list written as in tests/common.py: ("conv", c_in, c_out, k, stride, pad),
+    ("linear", n_in, n_out), ("relu",), ("flatten",), or ("kind", i) for a raw kind number."""
+    from gnn_branching_amd._lib import GNNB_CONV, GNNB_FLATTEN, GNNB_LINEAR, GNNB_RELU, LayerDesc
+    descs, keep = (LayerDesc * len(spec))(), []
+    rng = np.random.RandomState(5)
+    for q, (d, sp) in enumerate(zip(descs, spec)):
+        if sp[0] == "conv":
+            _, ci, co, k, st, pad = sp
+            w, b = rng.standard_normal((co, ci, k, k)).astype(np.float32), rng.standard_normal(co).astype(np.float32)
+            d.kind, d.c_in, d.c_out, d.kh, d.kw, d.stride, d.pad = GNNB_CONV, ci, co, k, k, st, pad
+        elif sp[0] == "linear":
+            _, ni, no = sp
+            w, b = rng.standard_normal((no, ni)).astype(np.float32), rng.standard_normal(no).astype(np.float32)
+            d.kind, d.n_in, d.n_out = GNNB_LINEAR, ni, no
+        else:
+            d.kind = {"relu": GNNB_RELU, "flatten": GNNB_FLATTEN}.get(sp[0], sp[-1])
+            continue
+        keep += [w, b]
+        if q != null_weight_at:
+            d.weight, d.bias = w.ctypes.data, b.ctypes.data
+    return descs, keep
+
+
+def parse(packlib, spec, shape, **kw):
+    """parse_layers: (N, relu_q, hw, R, n_fixed), or the refusal as a string."""
+    descs, keep = layer_list(spec, **kw)
+    N, rq, hw, rn = (np.zeros(16, np.int32) for _ in range(4))
+    err = C.create_string_buffer(512)
+    packlib.gnnb_pt_parse.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
+    K = packlib.gnnb_pt_parse(descs, len(spec), *shape, N.ctypes.data, rq.ctypes.data, hw.ctypes.data, 16, rn.ctypes.data, err, 512)
+    if K < 0:
+        return err.value.decode()
+    return N[:K].tolist(), rq[:K - 1].tolist(), hw[:K - 1].tolist(), int(rn[0]), int(rn[1])
+
+
+RELU, FLAT = ("relu",), ("flatten",)
+REFUSALS = [
+    ([FLAT, ("conv", 3, 8, 3, 1, 1), RELU], (3, 4, 4), {}, "layer 1: conv after flatten"),
+    ([("conv", 3, 8, 3, 1, 1), ("conv", 8, 8, 3, 1, 1), RELU], (3, 4, 4), {}, "layer 1: two linear maps without a ReLU between them"),
+    ([FLAT, ("linear", 48, 6), ("linear", 6, 4), RELU], (3, 4, 4), {}, "layer 2: two linear maps without a ReLU between them"),
+    ([("conv", 4, 8, 3, 1, 1), RELU], (3, 4, 4), {}, "layer 0: conv expects 4 input channels, graph has 3"),
+    ([FLAT, ("linear", 10, 6), RELU], (3, 4, 4), {}, "layer 1: linear expects 10 inputs, graph has 48"),
+    ([("conv", 3, 8, 3, 1, 1), RELU], (3, 4, 4), {"null_weight_at": 0}, "layer 0: null weight/bias"),
+    ([FLAT, ("linear", 48, 6), RELU], (3, 4, 4), {"null_weight_at": 1}, "layer 1: null weight/bias"),
+    ([("conv", 3, 8, 3, 0, 1), RELU], (3, 4, 4), {}, "layer 0: bad conv geometry"),
+    ([("conv", 3, 8, 3, 2, 0), RELU], (3, 4, 4), {},
+     "layer 0: conv geometry leaves a remainder (conv_transpose2d of the reference would need output_padding)"),
+    ([FLAT, ("linear", 48, 6), RELU, ("linear", 6, 4)], (3, 4, 4), {}, "fixed layers must end after a ReLU (the property layer is passed per batch)"),
+    ([FLAT, ("linear", 48, 4), RELU] + [("linear", 4, 4), RELU] * 8, (3, 4, 4), {}, "unsupported number of ReLU layers 9 (max 8)"),
+    ([FLAT, FLAT], (3, 4, 4), {}, "unsupported number of ReLU layers 0 (max 8)"),
+    ([FLAT, ("linear", 40368, 2), RELU], (3, 116, 116), {}, "graph layer 0 has 40368 nodes, more than the 40000 k_livesum holds in LDS"),
+    ([RELU, FLAT], (3, 4, 4), {}, "layer 0: ReLU without a preceding conv/linear"),
+    ([("kind", 7), RELU], (3, 4, 4), {}, "layer 0: unknown kind 7"),
+]
+
+
+@pytest.mark.parametrize("spec,shape,kw,message", REFUSALS, ids=[r[3][:40].replace(" ", "_") for r in REFUSALS])
+def test_layer_list_refusals(packlib, spec, shape, kw, message):
+    """One minimal layer list per refusal of parse_layers, with the wording gnnb_bind_network reports."""
+    assert parse(packlib, spec, shape, **kw) == message
+
+
+def test_layer_list_accepted(packlib):
+    """Two convs and two linear maps on 3x8x8: one graph layer per ReLU, the input in front and the property node behind."""
+    spec = [("conv", 3, 8, 4, 2, 1), RELU, ("conv", 8, 16, 4, 2, 1), RELU, FLAT, ("linear", 64, 20), RELU, ("linear", 20, 10), RELU]
+    N, relu_q, hw, R, n_fixed = parse(packlib, spec, (3, 8, 8))
+    assert N == [192, 8 * 4 * 4, 16 * 2 * 2, 20, 10, 1]
+    assert R == 128 + 64 + 20 + 10 and n_fixed == len(spec)
+    assert relu_q == [-1, 1, 3, 6, 8]              # the ReLU of graph layer k in the fixed-layer list
+    assert hw == [1, 16, 4, 1, 1]                  # nodes per bias entry: H x W of a conv's output, 1 behind a Linear
+
+
+def row_sums(packlib, w, geom=None):
+    w = np.ascontiguousarray(w, np.float32)
+    if geom is None:
+        n_out, n_in = w.shape
+        args, n = (1, 0, 0, 0, 0, 0, 0, 0, 0, n_in, n_out), n_out
+    else:
+        (c_out, c_in, kh, kw), (h_in, w_in, stride, pad) = w.shape, geom
+        n = c_out * ((h_in + 2 * pad - kh) // stride + 1) * ((w_in + 2 * pad - kw) // stride + 1)
+        args = (0, c_in, h_in, w_in, c_out, kh, kw, stride, pad, 0, 0)
+    out = np.zeros(n, np.float32)
+    packlib.gnnb_pt_row_sums.argtypes = [C.c_void_p] + [C.c_int] * 11 + [C.c_void_p]
+    assert packlib.gnnb_pt_row_sums(w.ctypes.data, *args, out.ctypes.data) == n
+    return out
+
+
+@pytest.mark.parametrize("k,stride,pad,h_in,w_in", [(4, 2, 1, 8, 8), (3, 1, 0, 5, 7)])
+def test_row_sums_of_a_conv_edge_1(packlib, k, stride, pad, h_in, w_in):
+    """s[node] = the sum of the weights of the taps that lie inside the image (the border nodes of a padded conv lose taps), added
+    in fp32: within n 2^-24 sum|w| of the fp64 sum over the same n taps."""
+    w = np.random.RandomState(k).standard_normal((8, 3, k, k)).astype(np.float32)
+    h_out, w_out = (h_in + 2 * pad - k) // stride + 1, (w_in + 2 * pad - k) // stride + 1
+    got = row_sums(packlib, w, (h_in, w_in, stride, pad)).reshape(8, h_out, w_out)
+    lost = 0
+    for oy in range(h_out):
+        for ox in range(w_out):
+            ys = [ky for ky in range(k) if 0 <= oy * stride - pad + ky < h_in]
+            xs = [kx for kx in range(k) if 0 <= ox * stride - pad + kx < w_in]
+            taps = w[:, :, ys][:, :, :, xs].astype(np.float64).reshape(8, -1)
+            lost += taps.shape[1] < 3 * k * k
+            bound = taps.shape[1] * 2.0 ** -24 * np.abs(taps).sum(1)
+            assert (np.abs(got[:, oy, ox] - taps.sum(1)) <= bound).all(), (oy, ox)
+    assert (lost > 0) == (pad > 0)
+
+
+def test_row_sums_of_a_linear_edge_1(packlib):
+    w = np.random.RandomState(1).standard_normal((6, 10)).astype(np.float32)
+    got = row_sums(packlib, w)
+    assert (np.abs(got - w.astype(np.float64).sum(1)) <= 10 * 2.0 ** -24 * np.abs(w.astype(np.float64)).sum(1)).all()
+
+
+@pytest.mark.parametrize("n_in,n_out", [(10, 6), (64, 32), (65, 33), (130, 100)])
+def test_dense_operands_of_a_linear_edge(packlib, n_in, n_out):
+    """Both padded images of a Linear edge and their mt / ld / ksq / kpad.  The expected geometry is written out here from the
+    formulas the dense kernels were built against (DENSE_CH = 8 k-steps per chunk), not read from the code under test."""
+    w = np.random.RandomState(n_in).standard_normal((n_out, n_in)).astype(np.float32)
+    geom = np.zeros(10, np.int32)
+    packlib.gnnb_pt_dense.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    packlib.gnnb_pt_dense.restype = None
+    packlib.gnnb_pt_dense(w.ctypes.data, n_in, n_out, geom.ctypes.data, None, 0, None, 0)
+    ld_fwd, mt_fwd, ksq_fwd, ld_bwd, mt_bwd, ksq_bwd, kpad_fwd, kpad_bwd, n_fwd, n_bwd = geom.tolist()
+
+    def ksq_of(K):          # k-steps per wave: ceil(ceil(K / 2) / 4) rounded up to whole chunks of 8
+        return ((((K + 1) // 2 + 3) // 4 + 7) // 8) * 8
+    assert (mt_fwd, ld_fwd, ksq_fwd, kpad_fwd) == ((n_out + 31) // 32, (n_out + 31) // 32 * 32, ksq_of(n_in), (n_in + 63) // 64 * 64)
+    assert (mt_bwd, ld_bwd, ksq_bwd, kpad_bwd) == ((n_in + 31) // 32, (n_in + 31) // 32 * 32, ksq_of(n_out), (n_out + 15) // 16 * 16)
+    rows_f, rows_b = max(8 * ksq_fwd + 16, kpad_fwd + 32), max(8 * ksq_bwd + 16, kpad_bwd + 64)
+    assert (n_fwd, n_bwd) == (rows_f * ld_fwd, rows_b * ld_bwd)
+    fwd, bwd = np.full(n_fwd, np.nan, np.float32), np.full(n_bwd, np.nan, np.float32)
+    packlib.gnnb_pt_dense(w.ctypes.data, n_in, n_out, geom.ctypes.data, fwd.ctypes.data, n_fwd, bwd.ctypes.data, n_bwd)
+    fwd, bwd = fwd.reshape(rows_f, ld_fwd), bwd.reshape(rows_b, ld_bwd)
+    np.testing.assert_array_equal(fwd[:n_in, :n_out], w.T)           # forward image [i][o] == W[o][i]
+    np.testing.assert_array_equal(bwd[:n_out, :n_in], w)             # transposed image [o][i] == W[o][i]
+    fwd[:n_in, :n_out] = 0
+    bwd[:n_out, :n_in] = 0
+    assert not fwd.view(np.uint32).any() and not bwd.view(np.uint32).any()      # every padded entry is exactly +0
+
+
+def test_tile_table_of_the_forward_geometry_archs(packlib):
+    """The packed tile table of every gather geometry test_gather_table_map_of_the_forward_geometry_archs builds: entry t is
+    (channel group, block row, block column) = (t / (NBY NBX), (t % (NBY NBX)) / NBX, t % NBX) in 8 + 12 + 12 bits."""
+    packlib.gnnb_pt_tile_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    seen = 0
+    for name, convs in fwd_arch_convs().items():
+        for layer, (c_in, c_out, k, s, pad, h_in, w_in) in convs:
+            w = np.ones((c_out, c_in, k, k), np.float32)
+            for d in (0, 1):
+                built = build_gather(packlib, w, h_in, w_in, s, pad, d, normalise=int(d == 1 and layer > 1), allow16=1, may_be_missing=True)
+                if built is None:
+                    continue
+                g = built[0]
+                tt = np.full(g["TPS"], -1, np.int32)
+                assert packlib.gnnb_pt_tile_table(g["NCG"], g["NBY"], g["NBX"], tt.ctypes.data) == 1
+                t = np.arange(g["TPS"])
+                per = g["NBY"] * g["NBX"]
+                np.testing.assert_array_equal(tt & 0xff, t // per)
+                np.testing.assert_array_equal((tt >> 8) & 0xfff, (t % per) // g["NBX"])
+                np.testing.assert_array_equal((tt >> 20) & 0xfff, t % g["NBX"])
+                seen += 1
+    assert seen >= 8
+    tt = np.zeros(1, np.int32)
+    for over in ((256, 1, 1), (1, 4096, 1), (1, 1, 4096)):          # a field that does not fit its bits: refused, nothing written
+        assert packlib.gnnb_pt_tile_table(*over, tt.ctypes.data) == 0
+
+
+def zero_tap(packlib, spec, shape):
+    descs, keep = layer_list(spec)
+    yx = np.full(2, -1, np.int32)
+    packlib.gnnb_pt_zero_tap.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
+    return packlib.gnnb_pt_zero_tap(descs, len(spec), *shape, yx.ctypes.data), tuple(yx.tolist())
+
+
+def test_zero_tap_layer(packlib):
+    """An inner conv with stride > kernel leaves pixels of the layer below that no window reads (2x2 windows every 3 pixels: row /
+    column 2 is the first).  Edge 1 is not normalised and may; a covering conv has none."""
+    gap = ("conv", 8, 8, 2, 3, 0)                       # on 8x8: windows at 0-1, 3-4, 6-7
+    k, (y, x) = zero_tap(packlib, [("conv", 3, 8, 3, 1, 1), RELU, gap, RELU], (3, 8, 8))
+    assert k == 2 and (y, x) == (2, 2)
+    assert zero_tap(packlib, [("conv", 8, 8, 2, 3, 0), RELU, ("conv", 8, 8, 3, 1, 1), RELU], (8, 8, 8))[0] == 0      # the same conv as edge 1
+    assert zero_tap(packlib, [("conv", 3, 8, 3, 1, 1), RELU, ("conv", 8, 8, 4, 2, 1), RELU], (3, 8, 8))[0] == 0      # a covering conv
