@@ -1,9 +1,12 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
+
+--frontier K keeps the open domains in device memory and expands the K of lowest bound per round (gnn_branching_amd/frontier.py): bounds by
+gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -31,9 +34,19 @@ def main():
     ap.add_argument("--bounds", default="kw", choices=("kw", "interval", "kw_device"),
                     help="intermediate bounds: host fp64 Wong-Kolter, interval arithmetic, or Wong-Kolter on the GPU (gnnb_kw_bounds)")
     ap.add_argument("--threshold", type=float, default=None, help="branching_threshold of the GNN + KW fall-back loop (the reference uses 0.2)")
+    ap.add_argument("--frontier", type=int, default=None, metavar="K", help="device-resident frontier: expand the K most promising domains per round")
     args = ap.parse_args()
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
+    if args.frontier is not None:
+        from gnn_branching_amd.frontier import branch_and_bound_frontier
+        lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device")
+        choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
+                                                                      max_rounds=max(1, args.nodes // (2 * args.frontier)))
+        verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
+        print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
+        return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
     root = lp.solve(root_mask)

@@ -13,7 +13,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("GNNB_LIB", os.path.join(CSRC, "libgnnb.so"))     # GNNB_LIB: dev override (ablation builds)
-SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_kw.h", "gnnb_k_dual.h"]
+SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_kw.h", "gnnb_k_dual.h", "gnnb_k_frontier.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread"]
 
 GNNB_CONV, GNNB_LINEAR, GNNB_RELU, GNNB_FLATTEN = 0, 1, 2, 3
@@ -36,6 +36,21 @@ class KwBatch(C.Structure):
     _fields_ = [("x_lo", C.c_void_p), ("x_hi", C.c_void_p), ("prop_w", C.c_void_p), ("prop_b", C.c_void_p), ("mask", C.c_void_p),
                 ("parent_lb", C.POINTER(C.c_void_p)), ("parent_ub", C.POINTER(C.c_void_p)), ("split_layer", C.c_void_p),
                 ("n_graph", C.c_int32)]
+
+
+class Pool(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("lb", C.POINTER(C.c_void_p)), ("ub", C.POINTER(C.c_void_p)), ("alpha", C.c_void_p), ("beta", C.c_void_p),
+                ("bound", C.c_void_p), ("open", C.c_void_p), ("capacity", C.c_int32), ("n_graph", C.c_int32)]
+
+
+class Children(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("lb", C.POINTER(C.c_void_p)), ("ub", C.POINTER(C.c_void_p)), ("infeasible", C.c_void_p),
+                ("bound", C.c_void_p), ("alpha", C.c_void_p), ("beta", C.c_void_p), ("ub_value", C.c_void_p), ("live", C.c_void_p),
+                ("n_graph", C.c_int32)]
+
+
+FRONTIER_STATE_DOUBLES = 9          # GNNB_FRONTIER_STATE_DOUBLES
+FS_GLOBAL_UB, FS_CLOSED_LB, FS_LOWEST_OPEN, FS_N_OPEN, FS_IN_USE, FS_KEPT, FS_CLOSED, FS_INFEASIBLE, FS_OVERFLOW = range(9)
 
 
 class DualBatch(C.Structure):
@@ -69,6 +84,16 @@ SYMBOLS = [
     ("gnnb_dual_ascent", C.c_int, [C.c_void_p, C.POINTER(DualBatch), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_gather", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    ("gnnb_frontier_expand", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gnnb_net_eval_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_net_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_commit_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_commit", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.POINTER(Children), C.c_double, C.c_double, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -20,7 +20,8 @@
 //
 // One translation unit: gnnb_dev.h (fragments, GEMM blocks, tile maps), gnnb_k_mlp.h (setup + node-MLP kernels),
 // gnnb_k_gather.h (conv-edge message passing + score head), gnnb_k_fusedq.h (gather + node update in one kernel), gnnb_k_edges.h (other edges, k_top), gnnb_k_misc.h (k_livesum,
-// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_k_dual.h (dual ascent, gnnb_dual_ascent), gnnb_train.h (online learning) are included below; this file
+// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_k_dual.h (dual ascent, gnnb_dual_ascent), gnnb_k_frontier.h (the steps of a BaB round on a
+// device-resident frontier, gnnb_frontier_* / gnnb_net_eval), gnnb_train.h (online learning) are included below; this file
 // holds the host side and the C-ABI.
 //
 // gfx950 only.  No HIP call at load time.
@@ -60,6 +61,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_misc.h"
 #include "gnnb_k_kw.h"
 #include "gnnb_k_dual.h"
+#include "gnnb_k_frontier.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -90,12 +92,14 @@ static int fail(int code, const char* fmt, ...) {
 enum ProfClass {
   PC_EMBED, PC_PRE, PC_PRE_INP, PC_CONV_FWD, PC_CONVT_BWD, PC_DENSE_AGG, PC_PROP_FWD,
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
-  PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL, PC_COUNT
+  PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
+  PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
     "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
-    "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent"};
+    "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent",
+    "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1661,6 +1665,147 @@ extern "C" int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
   run.run(PC_DUAL, [&] { hipLaunchKernelGGL(k_dual_ascent, dim3(B), dim3(DUAL_THREADS), lds, st, a); });
+  return run.rc;
+}
+
+
+// ================================================================================================================
+// A branch-and-bound frontier in device memory (gnnb_k_frontier.h): the steps of a round between the batch entry
+// points above.  Each checks everything before its first launch and launches on the caller's stream.
+// ================================================================================================================
+static int frontier_preflight(const gnnb_t* h, const char* who, int K, const int* n_graph) {
+  size_t lds = 0;
+  if (K < 1 || K > 32767) return fail(GNNB_E_INVALID, "%s: K = %d outside 1..32767", who, K);
+  return kw_preflight(h, who, n_graph, &lds);
+}
+
+static FrShape fr_shape(const gnnb_t* h) {
+  FrShape s{};
+  const KwNet& n = h->kw_net;
+  s.L = n.L; s.R = n.R;
+  for (int k = 0; k <= n.L; ++k) { s.N[k] = n.N[k]; s.off[k] = n.off[k]; }
+  s.N[n.L + 1] = 1;                                     // the property node
+  return s;
+}
+
+static int fr_pool(const gnnb_t* h, const char* who, const gnnb_pool* pool, FrPool* p) {
+  if (!pool->mask || !pool->lb || !pool->ub || !pool->alpha || !pool->beta || !pool->bound || !pool->open || pool->capacity < 1)
+    return fail(GNNB_E_INVALID, "%s: null pool array or capacity %d < 1", who, pool->capacity);
+  p->mask = pool->mask; p->alpha = pool->alpha; p->beta = pool->beta; p->bound = pool->bound; p->open = pool->open; p->cap = pool->capacity;
+  for (int k = 1; k <= h->kw_net.L + 1; ++k) {
+    if (!pool->lb[k - 1] || !pool->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null pool bounds pointer for graph layer %d", who, k);
+    p->lb[k] = pool->lb[k - 1]; p->ub[k] = pool->ub[k - 1];
+  }
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_frontier_gather(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const double* x_lo, const double* x_hi,
+                                    int8_t* mask, double* const* lb, double* const* ub, float* const* lb32, float* const* ub32, double* alpha,
+                                    double* beta, float* scorer_mask, void* stream) {
+  if (int rc = frontier_preflight(h, "gnnb_frontier_gather", K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !x_lo || !x_hi || !mask || !lb || !ub || !lb32 || !ub32 || !alpha || !beta || !scorer_mask)
+    return fail(GNNB_E_INVALID, "gnnb_frontier_gather: null argument");
+  FrGatherArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, "gnnb_frontier_gather", pool, &a.p)) return rc;
+  for (int k = 0; k <= a.s.L + 1; ++k) {
+    if (!lb32[k] || !ub32[k] || (k > 0 && (!lb[k - 1] || !ub[k - 1]))) return fail(GNNB_E_INVALID, "gnnb_frontier_gather: null output pointer for graph layer %d", k);
+    a.lb32[k] = lb32[k]; a.ub32[k] = ub32[k];
+    if (k > 0) { a.lb[k] = lb[k - 1]; a.ub[k] = ub[k - 1]; }
+  }
+  a.slots = slots; a.K = K; a.x_lo = x_lo; a.x_hi = x_hi; a.mask = mask; a.alpha = alpha; a.beta = beta; a.amb = scorer_mask;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_GATHER, [&] { hipLaunchKernelGGL(k_frontier_gather, dim3(K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_expand(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, const int32_t* decisions, int K, int8_t* mask,
+                                    double* const* parent_lb, double* const* parent_ub, int32_t* split_layer, double* alpha, double* beta,
+                                    int32_t* live, void* stream) {
+  if (int rc = frontier_preflight(h, "gnnb_frontier_expand", K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !decisions || !mask || !parent_lb || !parent_ub || !split_layer || !alpha || !beta || !live)
+    return fail(GNNB_E_INVALID, "gnnb_frontier_expand: null argument");
+  FrExpandArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, "gnnb_frontier_expand", pool, &a.p)) return rc;
+  for (int k = 1; k <= a.s.L + 1; ++k) {
+    if (!parent_lb[k - 1] || !parent_ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_frontier_expand: null output pointer for graph layer %d", k);
+    a.plb[k] = parent_lb[k - 1]; a.pub[k] = parent_ub[k - 1];
+  }
+  a.slots = slots; a.decisions = decisions; a.K = K; a.mask = mask; a.split = split_layer; a.alpha = alpha; a.beta = beta; a.live = live;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_EXPAND, [&] { hipLaunchKernelGGL(k_frontier_expand, dim3(2 * K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" size_t gnnb_net_eval_workspace_bytes(const gnnb_t* h, int B) {
+  if (!h || !h->bound || B < 1) return 0;
+  return (size_t)B * 2 * net_eval_width(h->kw_net) * sizeof(double);
+}
+
+extern "C" int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, const float* prop_b, int B, double* out, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (B < 1) return fail(GNNB_E_INVALID, "gnnb_net_eval: B = %d", B);
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_net_eval: null handle");      // (before h->bound is read)
+  const int ng = h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, "gnnb_net_eval", &ng, &lds)) return rc;
+  if (!x || !prop_w || !prop_b || !out || !workspace) return fail(GNNB_E_INVALID, "gnnb_net_eval: null argument");
+  const size_t need = gnnb_net_eval_workspace_bytes(h, B);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "gnnb_net_eval: workspace %zu bytes, need %zu", workspace_bytes, need);
+  NetEvalArgs a{};
+  a.net = h->kw_net;
+  a.x = x; a.prop_w = prop_w; a.prop_b = prop_b; a.out = out;
+  a.ws = (double*)workspace; a.ws_stride = 2L * net_eval_width(h->kw_net);
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_NET_EVAL, [&] { hipLaunchKernelGGL(k_net_eval, dim3(B), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+struct FrWs { size_t undecided, dest, total; };     // byte offsets in gnnb_frontier_commit's workspace: the resolved masks at 0
+static FrWs fr_ws_layout(const gnnb_t* h, int K) {
+  FrWs w;
+  w.undecided = ((size_t)2 * K * h->R + 255) & ~(size_t)255;
+  w.dest = w.undecided + (((size_t)2 * K * sizeof(int32_t) + 255) & ~(size_t)255);
+  w.total = w.dest + (((size_t)2 * K * sizeof(int32_t) + 255) & ~(size_t)255);
+  return w;
+}
+
+extern "C" size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K) {
+  if (!h || !h->bound || K < 1) return 0;
+  return fr_ws_layout(h, K).total;
+}
+
+extern "C" int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* ch, double eps,
+                                    double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = frontier_preflight(h, "gnnb_frontier_commit", K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !ch || !state || !workspace) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null argument");
+  if (ch->n_graph != pool->n_graph) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: the children have %d graph layers, the pool %d", ch->n_graph, pool->n_graph);
+  if (!ch->mask || !ch->lb || !ch->ub || !ch->infeasible || !ch->bound || !ch->alpha || !ch->beta || !ch->ub_value || !ch->live)
+    return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null array among the children's");
+  if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: eps = %g", eps);
+  const FrWs ws = fr_ws_layout(h, K);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_frontier_commit: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
+  FrCommitArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, "gnnb_frontier_commit", pool, &a.p)) return rc;
+  for (int k = 1; k <= a.s.L + 1; ++k) {
+    if (!ch->lb[k - 1] || !ch->ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null bounds pointer for graph layer %d", k);
+    a.lb[k] = ch->lb[k - 1]; a.ub[k] = ch->ub[k - 1];
+  }
+  a.slots = slots; a.K = K; a.mask = ch->mask; a.infeasible = ch->infeasible; a.bound = ch->bound; a.alpha = ch->alpha; a.beta = ch->beta;
+  a.ubv = ch->ub_value; a.live = ch->live; a.eps = eps; a.decision_bound = decision_bound; a.state = state;
+  a.rmask = (int8_t*)workspace;
+  a.undecided = (int32_t*)((char*)workspace + ws.undecided);
+  a.dest = (int32_t*)((char*)workspace + ws.dest);
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * K), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide, dim3(1), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 

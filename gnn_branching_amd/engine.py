@@ -875,6 +875,106 @@ class ScorerEngine:
         _lib.check(rc, "gnnb_dual_ascent")
         return DualAscentResult(bound, al, be, ga, gb, duals, prims, x_lp)
 
+    # ---- the real network at a batch of points, fp64 (the BaB loop's upper bound at the LP's input point) ---------------------------
+    def net_eval(self, fixed_layers, prop_layers, x, out=None, prop=None, workspace=None):
+        """gnnb_net_eval on the current stream.  x: (B, C, H, W) (or (B, N_0)) points, fp32 on the device (``DualAscentResult.x_lp``);
+        prop_layers: B Linear(N_L, 1), or ``prop`` = (weights (B, N_L), biases (B,)) fp32 device tensors.  Returns the (B,) fp64 values of
+        property layer b on the network's output at point b (``out``: a tensor to write them to).  Nothing is synchronised."""
+        B = int(x.shape[0])
+        self.bind(fixed_layers, tuple(x.shape[1:]))
+        x = self._rows(x, B, self.sizes[0], torch.float32, "x")
+        pw, pb = self._prop(prop_layers) if prop is None else prop
+        pw, pb = self._rows(pw, B, self.sizes[-2], torch.float32, "property weights"), self._rows(pb, B, 1, torch.float32, "property biases")
+        out = torch.empty(B, dtype=torch.float64, device=self.device) if out is None else self._rows(out, B, 1, torch.float64, "out")
+        ws = self._workspace("net_eval", B, "gnnb_net_eval_workspace_bytes") if workspace is None else workspace
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_net_eval(self.h, x.data_ptr(), pw.data_ptr(), pb.data_ptr(), B, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_net_eval")
+        return out.reshape(-1)[:B]
+
+    # ---- a BaB frontier in device memory (frontier.py runs the loop; include/gnnb.h gnnb_frontier_*) ---------------------------------
+    def _rows(self, t, n, cols, dtype, what):
+        """t as it is, checked: a contiguous device tensor of ``dtype`` holding at least n rows of ``cols`` (the steps below copy nothing)."""
+        if not torch.is_tensor(t) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.numel() < n * cols:
+            raise ValueError(f"{what}: expected a contiguous {dtype} tensor on {self.device} with at least {n}x{cols} values")
+        return t
+
+    def _layer_rows(self, ts, n, first, dtype, what):
+        sizes = self.sizes[first:]
+        if len(ts) != len(sizes):
+            raise ValueError(f"{what}: {len(ts)} tensors, expected {len(sizes)} (graph layers {first}..L+1)")
+        return table([self._rows(t, n, s, dtype, f"{what}[{k}]") for k, (t, s) in enumerate(zip(ts, sizes))])
+
+    def _pool(self, pool):
+        """The gnnb_pool of a ``frontier.DomainPool`` (any object with its attributes) and what must outlive the call."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        cap, R = int(pool.capacity), self.R
+        tl, tu = self._layer_rows(pool.lb, cap, 1, torch.float64, "pool.lb"), self._layer_rows(pool.ub, cap, 1, torch.float64, "pool.ub")
+        st = _lib.Pool(self._rows(pool.mask, cap, R, torch.int8, "pool.mask").data_ptr(), tl, tu,
+                       self._rows(pool.alpha, cap, R, torch.float64, "pool.alpha").data_ptr(),
+                       self._rows(pool.beta, cap, R, torch.float64, "pool.beta").data_ptr(),
+                       self._rows(pool.bound, cap, 1, torch.float64, "pool.bound").data_ptr(),
+                       self._rows(pool.open, cap, 1, torch.int32, "pool.open").data_ptr(), cap, len(self.sizes))
+        return st, (tl, tu)
+
+    def frontier_gather(self, pool, slots, x_lo, x_hi, mask, lb, ub, lb32, ub32, alpha, beta, scorer_mask):
+        """gnnb_frontier_gather on the current stream: the pool rows of ``slots`` ((K,) int32, distinct) into row i of the given tensors:
+        mask (K, R) int8, lb / ub (graph layers 1..L+1, fp64), lb32 / ub32 (graph layers 0..L+1, fp32, layer 0 from x_lo / x_hi (K, N_0)
+        fp64), alpha / beta (K, R) fp64, scorer_mask (K, R) fp32.  Every tensor is a device tensor of the caller's; nothing is copied."""
+        K = int(slots.numel())
+        st, keep = self._pool(pool)
+        R, N0 = self.R, self.sizes[0]
+        args = (self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, self._rows(x_lo, K, N0, torch.float64, "x_lo").data_ptr(),
+                self._rows(x_hi, K, N0, torch.float64, "x_hi").data_ptr(), self._rows(mask, K, R, torch.int8, "mask").data_ptr(),
+                self._layer_rows(lb, K, 1, torch.float64, "lb"), self._layer_rows(ub, K, 1, torch.float64, "ub"),
+                self._layer_rows(lb32, K, 0, torch.float32, "lb32"), self._layer_rows(ub32, K, 0, torch.float32, "ub32"),
+                self._rows(alpha, K, R, torch.float64, "alpha").data_ptr(), self._rows(beta, K, R, torch.float64, "beta").data_ptr(),
+                self._rows(scorer_mask, K, R, torch.float32, "scorer_mask").data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_gather(self.h, C.byref(st), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_gather")
+
+    def frontier_expand(self, pool, slots, decisions, mask, parent_lb, parent_ub, split_layer, alpha, beta, live):
+        """gnnb_frontier_expand on the current stream: the 2K children of the parents in ``slots`` split at ``decisions`` ((K, 2) int32,
+        ``ForwardResult.decisions``), rows 2i (blocked) and 2i + 1 (passing) of mask (2K, R) int8, parent_lb / parent_ub (graph layers
+        1..L+1, fp64), split_layer (2K,) int32, alpha / beta (2K, R) fp64, live (2K,) int32 -- the inputs of ``kw_bounds`` / ``dual_ascent``."""
+        K = int(slots.numel())
+        st, keep = self._pool(pool)
+        R = self.R
+        args = (self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), self._rows(decisions, K, 2, torch.int32, "decisions").data_ptr(), K,
+                self._rows(mask, 2 * K, R, torch.int8, "mask").data_ptr(), self._layer_rows(parent_lb, 2 * K, 1, torch.float64, "parent_lb"),
+                self._layer_rows(parent_ub, 2 * K, 1, torch.float64, "parent_ub"),
+                self._rows(split_layer, 2 * K, 1, torch.int32, "split_layer").data_ptr(),
+                self._rows(alpha, 2 * K, R, torch.float64, "alpha").data_ptr(), self._rows(beta, 2 * K, R, torch.float64, "beta").data_ptr(),
+                self._rows(live, 2 * K, 1, torch.int32, "live").data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_expand(self.h, C.byref(st), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_expand")
+
+    def frontier_commit(self, pool, slots, mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live, state, eps=1e-4, decision_bound=None,
+                        workspace=None):
+        """gnnb_frontier_commit on the current stream: resolve, keep or close the 2K children of the parents in ``slots``, store the kept
+        ones in the pool and update ``state`` (``_lib.FRONTIER_STATE_DOUBLES`` device doubles, indices ``_lib.FS_*``).  mask / live: what
+        ``frontier_expand`` wrote; lb / ub / infeasible: ``kw_bounds``'; bound / alpha / beta: ``dual_ascent``'s; ub_value: ``net_eval``'s."""
+        K = int(slots.numel())
+        st, keep = self._pool(pool)
+        R, n = self.R, 2 * K
+        tl, tu = self._layer_rows(lb, n, 1, torch.float64, "lb"), self._layer_rows(ub, n, 1, torch.float64, "ub")
+        ch = _lib.Children(self._rows(mask, n, R, torch.int8, "mask").data_ptr(), tl, tu,
+                           self._rows(infeasible, n, 1, torch.int32, "infeasible").data_ptr(),
+                           self._rows(bound, n, 1, torch.float64, "bound").data_ptr(), self._rows(alpha, n, R, torch.float64, "alpha").data_ptr(),
+                           self._rows(beta, n, R, torch.float64, "beta").data_ptr(), self._rows(ub_value, n, 1, torch.float64, "ub_value").data_ptr(),
+                           self._rows(live, n, 1, torch.int32, "live").data_ptr(), len(self.sizes))
+        self._rows(state, _lib.FRONTIER_STATE_DOUBLES, 1, torch.float64, "state")
+        ws = self._workspace("commit", K, "gnnb_frontier_commit_workspace_bytes") if workspace is None else workspace
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_commit(self.h, C.byref(st), self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, C.byref(ch),
+                                               float(eps), float("nan") if decision_bound is None else float(decision_bound), state.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_commit")
+
     def _check_primals(self, fixed, prim, B):
         def count(t):
             return t.numel() if torch.is_tensor(t) else t.size      # (tensors, numpy arrays, _HostBuf)

@@ -237,6 +237,82 @@ int gnnb_dual_ascent(gnnb_t* h, const gnnb_dual_batch* in, int B, int n_iter, do
                      double* bound, double* grad_alpha, double* grad_beta, float* const* dual, float* const* primal, float* x_lp,
                      float* lb32_prop, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- a branch-and-bound frontier in device memory (gnn_branching_amd/frontier.py runs the loop) ----
+ * The steps of one BaB round (reference plnn/relu_conv_gnnkwthreshold.py:126-262: pick a domain, split it, bound the children, keep or
+ * close them) that the batch entry points above do not cover, for K domains at once, reading and writing DEVICE arrays only.  A round:
+ * frontier_gather -> dual_ascent (n_iter 0, warm 1, scorer inputs) -> forward -> frontier_expand -> kw_bounds -> dual_ascent ->
+ * net_eval -> frontier_commit, then one copy of the state record to the host.  All of them are stream-ordered, allocate nothing and never
+ * synchronise; GNNB_E_INVALID for a null handle or argument, K < 1 (K > 32767) or a network whose widest ReLU layer exceeds 4096 nodes
+ * (the cap of the kernels they run between), GNNB_E_STATE before gnnb_bind_network, GNNB_E_NOMEM for a short workspace -- all before any
+ * launch.  No kernel waits on another workgroup; every minimum and count is a fixed tree in a fixed order.
+ *
+ * The POOL: `capacity` slots the caller owns, a struct of device arrays.  lb / ub are HOST tables of n_graph-1 device pointers. */
+typedef struct {
+  int8_t* mask;                       /* (capacity, R) BaB masks, resolved by the bounds                               */
+  double* const* lb;                  /* graph layers 1..L+1 (capacity, N_k), mask applied, as gnnb_kw_bounds writes them */
+  double* const* ub;
+  double* alpha;                      /* (capacity, R) the dual point `bound` belongs to (gnnb_dual_ascent's best)     */
+  double* beta;
+  double* bound;                      /* (capacity) lower bound of the domain                                          */
+  int32_t* open;                      /* (capacity) 1: the slot holds an open domain.  The caller zeroes it once       */
+  int32_t capacity, n_graph;
+} gnnb_pool;
+
+/* The 2K children of a round as the batch entry points left them (row 2i: parent i with the decided node blocked, 2i+1: passing). */
+typedef struct {
+  const int8_t* mask;                 /* (2K, R) as gnnb_frontier_expand wrote it                                      */
+  const double* const* lb;            /* gnnb_kw_bounds' outputs, HOST tables of n_graph-1 device pointers (2K, N_k)   */
+  const double* const* ub;
+  const int32_t* infeasible;          /* (2K) gnnb_kw_bounds                                                           */
+  const double* bound;                /* (2K) gnnb_dual_ascent                                                         */
+  const double* alpha;                /* (2K, R)                                                                       */
+  const double* beta;
+  const double* ub_value;             /* (2K) gnnb_net_eval at gnnb_dual_ascent's x_lp                                 */
+  const int32_t* live;                /* (2K) gnnb_frontier_expand                                                     */
+  int32_t n_graph;
+} gnnb_children;
+
+/* The state record: GNNB_FRONTIER_STATE_DOUBLES device doubles (counts are whole numbers): [0] global_ub, [1] closed_lb (lowest bound
+ * of a closed leaf), [2] lowest open bound (+inf: none), [3] open domains, [4] slots in use (1 + the highest slot ever written),
+ * [5] / [6] / [7] children kept / closed / infeasible in the last commit, [8] kept children that found no slot (closed at their bound
+ * instead, which keeps closed_lb sound; never with slots_in_use + 2K <= capacity).  Start: {+inf, +inf, +inf, 0, 0, ...}. */
+#define GNNB_FRONTIER_STATE_DOUBLES 9
+
+/* slots: device (K) int32, distinct slots of the pool.  x_lo / x_hi: device (K, N_0), the box of every row.  Writes row i of: mask (K, R);
+ * lb / ub (HOST tables of n_graph-1 device pointers, (K, N_k) fp64); lb32 / ub32 (n_graph pointers laid out as gnnb_batch.lb / .ub: layer 0
+ * the box, the others the pool's bounds rounded to nearest, as gnnb_kw_bounds' lb32); alpha / beta (K, R); scorer_mask (K, R) fp32, 1.0
+ * where the mask is -1 (gnnb_batch.mask).  gnnb_dual_ascent with n_iter = 0, warm = 1 on these rows re-derives the scorer's inputs. */
+int gnnb_frontier_gather(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const double* x_lo, const double* x_hi, int8_t* mask,
+                         double* const* lb, double* const* ub, float* const* lb32, float* const* ub32, double* alpha, double* beta,
+                         float* scorer_mask, void* stream);
+
+/* decisions: device (K, 2) int32 as gnnb_forward writes them.  Writes rows 2i (blocked) and 2i+1 (passing) of: mask (2K, R), the parent's
+ * with the decided node set to 0 / 1; parent_lb / parent_ub (HOST tables of n_graph-1 device pointers (2K, N_k)) and split_layer (2K):
+ * gnnb_kw_batch's; alpha / beta (2K, R): the parent's point, the warm start; live (2K) int32.  A parent whose decision is [-1, -1]
+ * (or names no node) yields two rows with live = 0, the parent's mask and split_layer = L-1: complete rows the batch entry points can
+ * run on, which gnnb_frontier_commit ignores. */
+int gnnb_frontier_expand(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, const int32_t* decisions, int K, int8_t* mask,
+                         double* const* parent_lb, double* const* parent_ub, int32_t* split_layer, double* alpha, double* beta, int32_t* live,
+                         void* stream);
+
+/* The bound network followed by row b of the property layers at B points, fp64 (the upper bound the BaB loop takes from a forward pass at
+ * the LP's input point, reference plnn/conv_kwinter_gen.py:514-519).  x: device (B, N_0) fp32 as gnnb_dual_ascent writes x_lp; prop_w
+ * (B, N_L), prop_b (B) as in gnnb_batch; out: device (B) fp64.  A point's value does not depend on B or on its row. */
+size_t gnnb_net_eval_workspace_bytes(const gnnb_t* h, int B);
+int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, const float* prop_b, int B, double* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* Closes a round.  slots: the K parents (as given to gnnb_frontier_expand); eps; decision_bound (NaN: none); state: the record above,
+ * read and updated.  In order: every live child's mask is resolved by its bounds (-1 with lo >= 0 -> 1, -1 with up <= 0 -> 0);
+ * global_ub = min(global_ub, ub_value of every live feasible child); a live feasible child with an undecided node, bound <
+ * global_ub - eps and (with a decision bound) bound < decision_bound is KEPT, every other live feasible child lowers closed_lb; a parent
+ * without a live child lowers closed_lb by its own bound; the parents' slots are freed; the kept child of rank r (among the kept, in
+ * child order) is stored in slot slots[r], from r = K on in slot in_use + (r - K) (in_use: state[4] before the call); the record is
+ * updated.  The root enters a pool the same way: K = 1, slots = {0}, the root as child row 0 and live = {1, 0}. */
+size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K);
+int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* children, double eps,
+                         double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
