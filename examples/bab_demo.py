@@ -1,12 +1,14 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--props 18]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
 
 --frontier K keeps the open domains in device memory and expands the K of lowest bound per round (gnn_branching_amd/frontier.py): bounds by
-gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.
+gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.  With --props N it
+verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
+the true one, every round's launches serving all the properties in flight; one verdict line per property.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -35,7 +37,28 @@ def main():
                     help="intermediate bounds: host fp64 Wong-Kolter, interval arithmetic, or Wong-Kolter on the GPU (gnnb_kw_bounds)")
     ap.add_argument("--threshold", type=float, default=None, help="branching_threshold of the GNN + KW fall-back loop (the reference uses 0.2)")
     ap.add_argument("--frontier", type=int, default=None, metavar="K", help="device-resident frontier: expand the K most promising domains per round")
+    ap.add_argument("--props", type=int, default=None, metavar="N", help="with --frontier: verify N properties (seeds x wrong classes) in one frontier")
     args = ap.parse_args()
+    if args.props is not None and (args.frontier is None or args.props < 1):
+        ap.error("--props N needs --frontier K and N >= 1")
+
+    def verdict_of(glb, gub):
+        return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
+    if args.props is not None:
+        from gnn_branching_amd.frontier import FrontierJob, verify_properties
+        wrong, jobs, names = [c for c in range(10) if c != 3], [], []
+        for j in range(args.props):
+            seed, cls = args.seed + j // 9, wrong[j % 9]
+            prop = nets.load_verified_net(args.net, 3, cls)
+            x = torch.from_numpy(np.random.RandomState(seed).standard_normal((3, 32, 32)).astype(np.float32))
+            jobs.append(FrontierJob(x - args.eps, x + args.eps, prop[-1], 0.0))
+            names.append(f"seed {seed} class 3 vs {cls}")
+        lp = lp_producer.LayerGraphLP(prop, x - args.eps, x + args.eps, bounds="kw_device")
+        choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        results = verify_properties(choice, prop[:-1], jobs, K=args.frontier, max_rounds=max(1, args.nodes // (2 * args.frontier)), log=lambda s: None)
+        for name, (glb, gub, rounds, bounded, reason) in zip(names, results):
+            print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
+        return
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
     if args.frontier is not None:

@@ -49,6 +49,11 @@ class Children(C.Structure):
                 ("n_graph", C.c_int32)]
 
 
+class Plan(C.Structure):
+    _fields_ = [("host", C.c_void_p), ("device", C.c_void_p), ("n_entries", C.c_int32), ("n", C.c_int32), ("segments", C.c_int32),
+                ("seg_cap", C.c_int32)]
+
+
 FRONTIER_STATE_DOUBLES = 9          # GNNB_FRONTIER_STATE_DOUBLES
 FS_GLOBAL_UB, FS_CLOSED_LB, FS_LOWEST_OPEN, FS_N_OPEN, FS_IN_USE, FS_KEPT, FS_CLOSED, FS_INFEASIBLE, FS_OVERFLOW = range(9)
 
@@ -94,6 +99,11 @@ SYMBOLS = [
     ("gnnb_frontier_commit_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_frontier_commit", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.POINTER(Children), C.c_double, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_pick_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gnnb_frontier_rows_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p] + [C.c_void_p] * 12 + [C.c_void_p]),
+    ("gnnb_frontier_commit_jobs_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_commit_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_void_p, C.POINTER(Children), C.c_double, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

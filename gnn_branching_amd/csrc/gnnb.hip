@@ -93,13 +93,14 @@ enum ProfClass {
   PC_EMBED, PC_PRE, PC_PRE_INP, PC_CONV_FWD, PC_CONVT_BWD, PC_DENSE_AGG, PC_PROP_FWD,
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
-  PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_COUNT
+  PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
     "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
     "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent",
-    "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store"};
+    "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store",
+    "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1806,6 +1807,108 @@ extern "C" int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int3
   run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * K), dim3(FR_THREADS), 0, st, a); });
   run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide, dim3(1), dim3(FR_THREADS), 0, st, a); });
   run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+// ---- many jobs in one pool: a pool of plan->segments segments of plan->seg_cap slots, one record per segment ----
+// Everything a kernel would trust is checked here on the host copy of the plan: the entries tile the rows [0, n) in order.
+static int fr_plan(const gnnb_t* h, const char* who, const gnnb_plan* plan, const int* n_graph, FrPlan* j) {
+  if (!plan) return fail(GNNB_E_INVALID, "%s: null plan", who);
+  if (plan->n_entries < 1 || plan->n < 1 || plan->n > 32767)
+    return fail(GNNB_E_INVALID, "%s: %d plan entries, n = %d rows (at least one entry, n in 1..32767)", who, plan->n_entries, plan->n);
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, who, n_graph, &lds)) return rc;
+  if (!plan->host || !plan->device) return fail(GNNB_E_INVALID, "%s: null plan array", who);
+  if (plan->segments < 1 || plan->seg_cap < 1 || (long)plan->segments * plan->seg_cap > 2147483647L)
+    return fail(GNNB_E_INVALID, "%s: %d segments of %d slots", who, plan->segments, plan->seg_cap);
+  long row = 0;
+  for (int e = 0; e < plan->n_entries; ++e) {
+    const int seg = plan->host[3 * e], row0 = plan->host[3 * e + 1], k = plan->host[3 * e + 2];
+    if (seg < 0 || seg >= plan->segments) return fail(GNNB_E_INVALID, "%s: plan entry %d names segment %d outside the pool's 0..%d", who, e, seg, plan->segments - 1);
+    if (k < 1) return fail(GNNB_E_INVALID, "%s: plan entry %d has k = %d < 1", who, e, k);
+    if (row0 != row) return fail(GNNB_E_INVALID, "%s: plan entry %d starts at row %d, the entries before it end at %ld", who, e, row0, row);
+    row += k;
+    if (row > plan->n) break;
+  }
+  if (row != plan->n) return fail(GNNB_E_INVALID, "%s: the plan's entries hold %ld rows, n = %d", who, row, plan->n);
+  j->plan = plan->device; j->n_entries = plan->n_entries; j->n = plan->n; j->S = plan->segments; j->seg_cap = plan->seg_cap;
+  return GNNB_OK;
+}
+
+static int fr_plan_pool(const gnnb_t* h, const char* who, const gnnb_plan* plan, const gnnb_pool* pool, FrPool* p) {
+  if (int rc = fr_pool(h, who, pool, p)) return rc;
+  if ((long)plan->segments * plan->seg_cap != pool->capacity)
+    return fail(GNNB_E_INVALID, "%s: %d segments of %d slots in a pool of %d", who, plan->segments, plan->seg_cap, pool->capacity);
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_frontier_pick_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const double* state, int32_t* slots,
+                                       int32_t* row_seg, void* stream) {
+  FrPickArgs a{};
+  if (int rc = fr_plan(h, "gnnb_frontier_pick_jobs", plan, pool ? &pool->n_graph : nullptr, &a.j)) return rc;
+  if (!state || !slots || !row_seg) return fail(GNNB_E_INVALID, "gnnb_frontier_pick_jobs: null argument");
+  if (int rc = fr_plan_pool(h, "gnnb_frontier_pick_jobs", plan, pool, &a.p)) return rc;
+  a.state = state; a.slots = slots; a.row_seg = row_seg;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_PICK_JOBS, [&] { hipLaunchKernelGGL(k_frontier_pick_jobs, dim3(a.j.n_entries), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_rows_jobs(gnnb_t* h, const gnnb_plan* plan, const int32_t* row_seg, const double* seg_x_lo, const double* seg_x_hi,
+                                       const float* seg_prop_w, const float* seg_prop_b, double* x_lo, double* x_hi, float* prop_w, float* prop_b,
+                                       double* child_x_lo, double* child_x_hi, float* child_prop_w, float* child_prop_b, void* stream) {
+  FrRowsArgs a{};
+  const int ng = (h && h->bound) ? h->kw_net.L + 2 : 0;
+  if (int rc = fr_plan(h, "gnnb_frontier_rows_jobs", plan, &ng, &a.j)) return rc;
+  if (!row_seg || !seg_x_lo || !seg_x_hi || !seg_prop_w || !seg_prop_b || !x_lo || !x_hi || !prop_w || !prop_b || !child_x_lo || !child_x_hi ||
+      !child_prop_w || !child_prop_b)
+    return fail(GNNB_E_INVALID, "gnnb_frontier_rows_jobs: null argument");
+  a.N0 = h->kw_net.N[0]; a.NL = h->kw_net.N[h->kw_net.L];
+  a.row_seg = row_seg; a.seg_x_lo = seg_x_lo; a.seg_x_hi = seg_x_hi; a.seg_pw = seg_prop_w; a.seg_pb = seg_prop_b;
+  a.x_lo[0] = x_lo; a.x_hi[0] = x_hi; a.pw[0] = prop_w; a.pb[0] = prop_b;
+  a.x_lo[1] = child_x_lo; a.x_hi[1] = child_x_hi; a.pw[1] = child_prop_w; a.pb[1] = child_prop_b;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_ROWS_JOBS, [&] { hipLaunchKernelGGL(k_frontier_rows_jobs, dim3(3 * a.j.n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" size_t gnnb_frontier_commit_jobs_workspace_bytes(const gnnb_t* h, int n) {
+  if (!h || !h->bound || n < 1) return 0;
+  return fr_ws_layout(h, n).total;
+}
+
+extern "C" int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_children* ch,
+                                         double eps, const double* decision_bound, double* state, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  const char* who = "gnnb_frontier_commit_jobs";
+  FrPlan j{};
+  if (int rc = fr_plan(h, who, plan, pool ? &pool->n_graph : nullptr, &j)) return rc;
+  if (!slots || !ch || !decision_bound || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (ch->n_graph != pool->n_graph) return fail(GNNB_E_INVALID, "%s: the children have %d graph layers, the pool %d", who, ch->n_graph, pool->n_graph);
+  if (!ch->mask || !ch->lb || !ch->ub || !ch->infeasible || !ch->bound || !ch->alpha || !ch->beta || !ch->ub_value || !ch->live)
+    return fail(GNNB_E_INVALID, "%s: null array among the children's", who);
+  if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "%s: eps = %g", who, eps);
+  const FrWs ws = fr_ws_layout(h, j.n);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
+  FrCommitArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_plan_pool(h, who, plan, pool, &a.p)) return rc;
+  for (int k = 1; k <= a.s.L + 1; ++k) {
+    if (!ch->lb[k - 1] || !ch->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null bounds pointer for graph layer %d", who, k);
+    a.lb[k] = ch->lb[k - 1]; a.ub[k] = ch->ub[k - 1];
+  }
+  a.slots = slots; a.K = j.n; a.mask = ch->mask; a.infeasible = ch->infeasible; a.bound = ch->bound; a.alpha = ch->alpha; a.beta = ch->beta;
+  a.ubv = ch->ub_value; a.live = ch->live; a.eps = eps; a.decision_bound = 0.0; a.state = state;
+  a.rmask = (int8_t*)workspace;
+  a.undecided = (int32_t*)((char*)workspace + ws.undecided);
+  a.dest = (int32_t*)((char*)workspace + ws.dest);
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * j.n), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_decide_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, decision_bound); });
+  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * j.n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 

@@ -17,7 +17,8 @@
 //   * k_frontier_resolve  per child: the mask resolved by the bounds (-1 with lo >= 0 -> 1, -1 with up <= 0 -> 0) and whether an
 //                         undecided node is left.
 //   * k_frontier_decide   ONE workgroup: global_ub, keep or close every child, the parents' slots freed, the kept children's
-//                         destination slots by a prefix sum over the 2K keep flags in child order, the state record.
+//                         destination slots by a prefix sum over the 2K keep flags in child order, the state record (fr_decide on
+//                         the view of the whole pool; k_frontier_decide_jobs at the end of this file runs it per job on a segment).
 //   * k_frontier_store    kept children -> their pool slots.
 //
 // A kept child of rank r (its number among the kept ones, in child order) goes to the r-th parent slot in the order of `slots`; from
@@ -208,36 +209,49 @@ __device__ __forceinline__ double fr_block_min(double* red, double v, int tid) {
   return out;
 }
 
-__global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) {
-  __shared__ double red[FR_THREADS];
-  __shared__ int cnt[FR_THREADS + 1];
-  const int tid = threadIdx.x, K = a.K, n = 2 * K;
+// What one job's commit sees of the pool and the children: the slots [base, base + cap) (in_use and every destination above the parents'
+// slots count from base), the parents' rows [row0, row0 + K) of `slots`, their children [2 row0, 2 row0 + 2K), the job's record and
+// decision bound.  k_frontier_decide is the view {0, pool capacity, 0, K, state, decision_bound}.
+struct FrView {
+  int base, cap, row0, K;
+  double* state;
+  double decision_bound;
+};
+
+__device__ __forceinline__ bool fr_view_ok(const FrView& v, int s) { return s >= v.base && s < v.base + v.cap; }
+
+// global_ub, keep or close every child of the view, its parents' slots freed, the kept children's destination slots by a prefix sum
+// over the 2K keep flags in child order, the record.  One workgroup; red: FR_THREADS doubles, cnt: FR_THREADS + 1 ints of LDS.
+__device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v, double* red, int* cnt) {
+  const int tid = threadIdx.x, K = v.K, n = 2 * K;
+  const int32_t* slots = a.slots + v.row0;
+  const long ch0 = 2L * v.row0;                         // the view's first child row
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
-  const int in_use = min(max((int)a.state[FS_IN_USE], 0), a.p.cap);
+  const int in_use = min(max((int)v.state[FS_IN_USE], 0), v.cap);
   // 2. the incumbent: every live feasible child's network value at its LP point
-  double v = inf;
+  double val = inf;
   for (int c = tid; c < n; c += FR_THREADS)
-    if (a.live[c] && !a.infeasible[c]) v = fmin(v, a.ubv[c]);
-  const double gub = fmin(a.state[FS_GLOBAL_UB], fr_block_min(red, v, tid));
+    if (a.live[ch0 + c] && !a.infeasible[ch0 + c]) val = fmin(val, a.ubv[ch0 + c]);
+  const double gub = fmin(v.state[FS_GLOBAL_UB], fr_block_min(red, val, tid));
   // 3. - 5. keep or close (each thread a contiguous run of children, so that ranks follow child order)
   const int per = (n + FR_THREADS - 1) / FR_THREADS, c0 = min(tid * per, n), c1 = min(c0 + per, n);
-  const bool have_db = a.decision_bound == a.decision_bound;
+  const bool have_db = v.decision_bound == v.decision_bound;
   double closed = inf;
   int kept = 0, n_closed = 0, n_inf = 0;
   for (int c = c0; c < c1; ++c) {
-    if (!a.live[c]) continue;
-    if (a.infeasible[c]) { ++n_inf; continue; }
-    const double lb = a.bound[c];
-    if (a.undecided[c] && lb < gub - a.eps && (!have_db || lb < a.decision_bound)) ++kept;
+    if (!a.live[ch0 + c]) continue;
+    if (a.infeasible[ch0 + c]) { ++n_inf; continue; }
+    const double lb = a.bound[ch0 + c];
+    if (a.undecided[ch0 + c] && lb < gub - a.eps && (!have_db || lb < v.decision_bound)) ++kept;
     else { closed = fmin(closed, lb); ++n_closed; }
   }
   for (int i = tid; i < K; i += FR_THREADS) {           // a parent without a live child (decision [-1, -1]) is closed at its own bound
-    const int s = a.slots[i];
-    if (fr_slot_ok(a.p, s) && !a.live[2 * i] && !a.live[2 * i + 1]) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
+    const int s = slots[i];
+    if (fr_view_ok(v, s) && !a.live[ch0 + 2 * i] && !a.live[ch0 + 2 * i + 1]) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
   }
   // 6. the parents leave the pool
   for (int i = tid; i < K; i += FR_THREADS)
-    if (fr_slot_ok(a.p, a.slots[i])) a.p.open[a.slots[i]] = 0;
+    if (fr_view_ok(v, slots[i])) a.p.open[slots[i]] = 0;
   // 7. ranks of the kept children: exclusive prefix sum of the per-thread counts
   cnt[tid + 1] = kept;
   if (tid == 0) cnt[0] = 0;
@@ -249,31 +263,31 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) 
   const int total_kept = cnt[FR_THREADS];
   for (int c = c0; c < c1; ++c) {
     int d = -1;
-    if (a.live[c] && !a.infeasible[c]) {
-      const double lb = a.bound[c];
-      if (a.undecided[c] && lb < gub - a.eps && (!have_db || lb < a.decision_bound)) {
-        d = rank < K ? a.slots[rank] : in_use + (rank - K);
+    if (a.live[ch0 + c] && !a.infeasible[ch0 + c]) {
+      const double lb = a.bound[ch0 + c];
+      if (a.undecided[ch0 + c] && lb < gub - a.eps && (!have_db || lb < v.decision_bound)) {
+        d = rank < K ? slots[rank] : v.base + in_use + (rank - K);
         ++rank;
-        if (!fr_slot_ok(a.p, d)) {                      // no room (the caller checks the capacity before a round): the bound is not lost
+        if (!fr_view_ok(v, d)) {                        // no room (the caller checks the capacity before a round): the bound is not lost
           d = -1;
           closed = fmin(closed, lb);
           ++dropped;
         } else {
-          top = max(top, d + 1);
+          top = max(top, d - v.base + 1);
         }
       }
     }
-    a.dest[c] = d;
+    a.dest[ch0 + c] = d;
   }
-  // 8. the state record: what stays open is the pool's open slots (the parents are out) and the kept children
+  // 8. the state record: what stays open is the view's open slots (the parents are out) and the kept children
   double low = inf;
   int n_open = 0;
   for (int s = tid; s < in_use; s += FR_THREADS)
-    if (a.p.open[s]) { low = fmin(low, a.p.bound[s]); ++n_open; }
+    if (a.p.open[v.base + s]) { low = fmin(low, a.p.bound[v.base + s]); ++n_open; }
   for (int c = c0; c < c1; ++c)
-    if (a.dest[c] >= 0) { low = fmin(low, a.bound[c]); ++n_open; }
+    if (a.dest[ch0 + c] >= 0) { low = fmin(low, a.bound[ch0 + c]); ++n_open; }
   low = fr_block_min(red, low, tid);
-  closed = fmin(a.state[FS_CLOSED_LB], fr_block_min(red, closed, tid));
+  closed = fmin(v.state[FS_CLOSED_LB], fr_block_min(red, closed, tid));
   double sums[4] = {(double)n_open, (double)n_closed, (double)n_inf, (double)dropped};
   double tops = fr_block_min(red, -(double)top, tid);
   for (int q = 0; q < 4; ++q) {                         // whole numbers below 2^53: exact in any order; the tree is fixed all the same
@@ -282,16 +296,23 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) 
     sums[q] = w;
   }
   if (tid == 0) {
-    a.state[FS_GLOBAL_UB] = gub;
-    a.state[FS_CLOSED_LB] = closed;
-    a.state[FS_LOWEST_OPEN] = low;
-    a.state[FS_N_OPEN] = sums[0];
-    a.state[FS_IN_USE] = fmax((double)in_use, -tops);
-    a.state[FS_KEPT] = (double)(total_kept) - sums[3];
-    a.state[FS_CLOSED] = sums[1] + sums[3];
-    a.state[FS_INFEASIBLE] = sums[2];
-    a.state[FS_OVERFLOW] = sums[3];
+    v.state[FS_GLOBAL_UB] = gub;
+    v.state[FS_CLOSED_LB] = closed;
+    v.state[FS_LOWEST_OPEN] = low;
+    v.state[FS_N_OPEN] = sums[0];
+    v.state[FS_IN_USE] = fmax((double)in_use, -tops);
+    v.state[FS_KEPT] = (double)(total_kept) - sums[3];
+    v.state[FS_CLOSED] = sums[1] + sums[3];
+    v.state[FS_INFEASIBLE] = sums[2];
+    v.state[FS_OVERFLOW] = sums[3];
   }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) {
+  __shared__ double red[FR_THREADS];
+  __shared__ int cnt[FR_THREADS + 1];
+  const FrView v{0, a.p.cap, 0, a.K, a.state, a.decision_bound};
+  fr_decide(a, v, red, cnt);
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_store(FrCommitArgs a) {
@@ -315,4 +336,110 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_store(FrCommitArgs a) {
     a.p.bound[d] = a.bound[c];
     a.p.open[d] = 1;
   }
+}
+
+// ---- many jobs in one pool --------------------------------------------------------------------------------
+// The pool is S segments of seg_cap slots; a segment holds one job (a box, a property row, a decision bound) and has its own record,
+// so the state is (S, FS_COUNT).  A round's PLAN is one entry {segment, row0, k} per job that takes part: its k parents are rows
+// [row0, row0 + k) of the batch, its children rows [2 row0, 2 row0 + 2k).  The kernels below work per entry on that segment alone:
+// no reduction mixes entries, no atomic places a row, no workgroup waits on another, so an entry's result does not depend on the other
+// entries, their number or their order.  gather / expand / resolve / store run unchanged: they index slots and rows globally.
+//
+//   * k_frontier_pick_jobs    one workgroup per entry: the k slots of lowest key among the segment's first in_use, ascending, the key
+//                             being (open ? bound : +inf, slot) -- torch.sort(where(open > 0, bound, inf), stable=True)[:k].
+//   * k_frontier_rows_jobs    the boxes and property rows of the n parent and 2n child rows from per-segment tables.  Plain copies.
+//   * k_frontier_decide_jobs  one workgroup per entry: fr_decide on the entry's view.
+
+struct FrPlan {
+  const int32_t* plan;                                  // (n_entries, 3) {segment, row0, k}
+  int n_entries, n, S, seg_cap;
+};
+
+struct FrPickArgs {
+  FrPlan j; FrPool p;
+  const double* state;                                  // (S, FS_COUNT)
+  int32_t* slots; int32_t* row_seg;                     // (n)
+};
+
+struct FrRowsArgs {
+  FrPlan j;
+  int N0, NL;
+  const int32_t* row_seg;
+  const double* seg_x_lo; const double* seg_x_hi; const float* seg_pw; const float* seg_pb;     // (S, N_0), (S, N_L), (S)
+  double* x_lo[2]; double* x_hi[2]; float* pw[2]; float* pb[2];                                  // [0]: the n parent rows, [1]: the 2n child rows
+};
+
+// an entry the host would have refused names no rows: its workgroup leaves
+__device__ __forceinline__ bool fr_entry(const FrPlan& j, int e, int* seg, int* row0, int* k) {
+  *seg = j.plan[3 * e]; *row0 = j.plan[3 * e + 1]; *k = j.plan[3 * e + 2];
+  return *seg >= 0 && *seg < j.S && *k >= 1 && *row0 >= 0 && *row0 + *k <= j.n;
+}
+
+// (key a, slot sa) before (key b, slot sb) in torch.sort's stable ascending order: NaN after every number, equal keys by slot
+__device__ __forceinline__ bool fr_key_less(double a, int sa, double b, int sb) {
+  const bool an = a != a, bn = b != b;
+  if (an || bn) return an == bn ? sa < sb : bn;
+  return a < b || (a == b && sa < sb);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_pick_jobs(FrPickArgs a) {
+  __shared__ double rk[FR_THREADS];
+  __shared__ int rs[FR_THREADS];
+  const int tid = threadIdx.x;
+  int seg, row0, k;
+  if (!fr_entry(a.j, blockIdx.x, &seg, &row0, &k)) return;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  const int base = seg * a.j.seg_cap;
+  const int in_use = min(max((int)a.state[(long)seg * FS_COUNT + FS_IN_USE], 0), a.j.seg_cap);
+  double last = 0.0;
+  int last_s = -1;                                      // the slots picked so far: every (key, slot) up to (last, last_s)
+  for (int r = 0; r < k; ++r) {                         // pick r: the lowest (key, slot) after the last one -- a total order, so the minimum is one slot
+    double best = 0.0;
+    int best_s = -1;
+    for (int s = tid; s < in_use; s += FR_THREADS) {
+      const double key = a.p.open[base + s] > 0 ? a.p.bound[base + s] : inf;
+      if (last_s >= 0 && !fr_key_less(last, last_s, key, s)) continue;
+      if (best_s < 0 || fr_key_less(key, s, best, best_s)) { best = key; best_s = s; }
+    }
+    rk[tid] = best; rs[tid] = best_s;
+    __syncthreads();
+    for (int w = FR_THREADS / 2; w > 0; w >>= 1) {
+      if (tid < w) {
+        const int o = rs[tid + w];
+        if (o >= 0 && (rs[tid] < 0 || fr_key_less(rk[tid + w], o, rk[tid], rs[tid]))) { rk[tid] = rk[tid + w]; rs[tid] = o; }
+      }
+      __syncthreads();
+    }
+    last = rk[0]; last_s = rs[0];
+    __syncthreads();
+    if (last_s < 0) {                                   // fewer than k slots in use: the rows left name no slot (gather and expand skip them)
+      for (int q = r + tid; q < k; q += FR_THREADS) { a.slots[row0 + q] = -1; a.row_seg[row0 + q] = seg; }
+      return;
+    }
+    if (tid == 0) { a.slots[row0 + r] = base + last_s; a.row_seg[row0 + r] = seg; }
+  }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_rows_jobs(FrRowsArgs a) {
+  const int t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int child = (int)blockIdx.x >= a.j.n ? 1 : 0, r = (int)blockIdx.x - child * a.j.n;      // r: the row of its array
+  const int seg = a.row_seg[child ? r >> 1 : r];
+  if (seg < 0 || seg >= a.j.S) return;
+  for (int m = t0; m < a.N0; m += dt) {
+    a.x_lo[child][(long)r * a.N0 + m] = a.seg_x_lo[(long)seg * a.N0 + m];
+    a.x_hi[child][(long)r * a.N0 + m] = a.seg_x_hi[(long)seg * a.N0 + m];
+  }
+  for (int m = t0; m < a.NL; m += dt) a.pw[child][(long)r * a.NL + m] = a.seg_pw[(long)seg * a.NL + m];
+  if (t0 == 0) a.pb[child][r] = a.seg_pb[seg];
+}
+
+static_assert(sizeof(FrCommitArgs) + sizeof(FrPlan) + sizeof(double*) <= 4096, "kernel arguments: 4 KiB");
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_decide_jobs(FrCommitArgs a, FrPlan j, const double* decision_bound) {
+  __shared__ double red[FR_THREADS];
+  __shared__ int cnt[FR_THREADS + 1];
+  int seg, row0, k;
+  if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
+  const FrView v{seg * j.seg_cap, j.seg_cap, row0, k, a.state + (long)seg * FS_COUNT, decision_bound[seg]};
+  fr_decide(a, v, red, cnt);
 }

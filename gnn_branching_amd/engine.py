@@ -975,6 +975,70 @@ class ScorerEngine:
                                                ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_frontier_commit")
 
+    # ---- many jobs in one pool (frontier.py verify_properties; include/gnnb.h gnnb_frontier_*_jobs) ------------------------------------
+    def _plan(self, plan):
+        """The gnnb_plan of a ``frontier.RoundPlan`` (any object with its attributes): host (E, 3) int32 CPU tensor, device the same values
+        on the device, n_entries, n, segments, seg_cap."""
+        if not torch.is_tensor(plan.host) or plan.host.dtype != torch.int32 or plan.host.device.type != "cpu" or not plan.host.is_contiguous() \
+                or plan.host.numel() < 3 * plan.n_entries:
+            raise ValueError(f"plan.host: expected a contiguous int32 CPU tensor with at least {plan.n_entries}x3 values")
+        self._rows(plan.device, max(int(plan.n_entries), 0), 3, torch.int32, "plan.device")
+        return _lib.Plan(plan.host.data_ptr(), plan.device.data_ptr(), int(plan.n_entries), int(plan.n), int(plan.segments), int(plan.seg_cap))
+
+    def frontier_pick_jobs(self, pool, plan, state, slots, row_seg):
+        """gnnb_frontier_pick_jobs on the current stream: per plan entry the k slots of lowest bound of its segment (``FrontierRun.pick``'s
+        rule on the segment) as global slot numbers into slots[row0:row0 + k], the segment into row_seg[row0:row0 + k] ((n,) int32 each).
+        state: the (segments, ``_lib.FRONTIER_STATE_DOUBLES``) records."""
+        st, keep = self._pool(pool)
+        pl, n = self._plan(plan), max(int(plan.n), 0)
+        args = (self._rows(state, max(int(plan.segments), 0), _lib.FRONTIER_STATE_DOUBLES, torch.float64, "state").data_ptr(),
+                self._rows(slots, n, 1, torch.int32, "slots").data_ptr(), self._rows(row_seg, n, 1, torch.int32, "row_seg").data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_pick_jobs(self.h, C.byref(st), C.byref(pl), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_pick_jobs")
+
+    def frontier_rows_jobs(self, plan, row_seg, seg_x_lo, seg_x_hi, seg_prop_w, seg_prop_b, x_lo, x_hi, prop_w, prop_b, child_x_lo, child_x_hi,
+                           child_prop_w, child_prop_b):
+        """gnnb_frontier_rows_jobs on the current stream: the boxes and property rows of the n parent rows (x_lo / x_hi (n, N_0) fp64, prop_w
+        (n, N_L), prop_b (n,) fp32) and of the 2n child rows (child_*) from the per-segment tables seg_* by row_seg ((n,) int32)."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        pl, n, S, N0, NL = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), self.sizes[0], self.sizes[-2]
+        f64, f32 = torch.float64, torch.float32
+        args = (self._rows(row_seg, n, 1, torch.int32, "row_seg").data_ptr(),
+                self._rows(seg_x_lo, S, N0, f64, "seg_x_lo").data_ptr(), self._rows(seg_x_hi, S, N0, f64, "seg_x_hi").data_ptr(),
+                self._rows(seg_prop_w, S, NL, f32, "seg_prop_w").data_ptr(), self._rows(seg_prop_b, S, 1, f32, "seg_prop_b").data_ptr(),
+                self._rows(x_lo, n, N0, f64, "x_lo").data_ptr(), self._rows(x_hi, n, N0, f64, "x_hi").data_ptr(),
+                self._rows(prop_w, n, NL, f32, "prop_w").data_ptr(), self._rows(prop_b, n, 1, f32, "prop_b").data_ptr(),
+                self._rows(child_x_lo, 2 * n, N0, f64, "child_x_lo").data_ptr(), self._rows(child_x_hi, 2 * n, N0, f64, "child_x_hi").data_ptr(),
+                self._rows(child_prop_w, 2 * n, NL, f32, "child_prop_w").data_ptr(), self._rows(child_prop_b, 2 * n, 1, f32, "child_prop_b").data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_rows_jobs(self.h, C.byref(pl), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_rows_jobs")
+
+    def frontier_commit_jobs(self, pool, plan, slots, mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live, state, decision_bound, eps=1e-4,
+                             workspace=None):
+        """gnnb_frontier_commit_jobs on the current stream: ``frontier_commit`` per plan entry on its children (rows [2 row0, 2 row0 + 2k) of
+        the 2n-row tensors), its parents' slots (slots (n,) int32, global numbers), its segment, its record of ``state`` ((segments, 9)
+        fp64) and its entry of ``decision_bound`` ((segments,) fp64 on the device, NaN: none)."""
+        st, keep = self._pool(pool)
+        pl, n, S, R = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), self.R
+        tl, tu = self._layer_rows(lb, 2 * n, 1, torch.float64, "lb"), self._layer_rows(ub, 2 * n, 1, torch.float64, "ub")
+        ch = _lib.Children(self._rows(mask, 2 * n, R, torch.int8, "mask").data_ptr(), tl, tu,
+                           self._rows(infeasible, 2 * n, 1, torch.int32, "infeasible").data_ptr(),
+                           self._rows(bound, 2 * n, 1, torch.float64, "bound").data_ptr(), self._rows(alpha, 2 * n, R, torch.float64, "alpha").data_ptr(),
+                           self._rows(beta, 2 * n, R, torch.float64, "beta").data_ptr(),
+                           self._rows(ub_value, 2 * n, 1, torch.float64, "ub_value").data_ptr(),
+                           self._rows(live, 2 * n, 1, torch.int32, "live").data_ptr(), len(self.sizes))
+        self._rows(state, S, _lib.FRONTIER_STATE_DOUBLES, torch.float64, "state")
+        self._rows(decision_bound, S, 1, torch.float64, "decision_bound")
+        ws = self._workspace("commit_jobs", max(n, 1), "gnnb_frontier_commit_jobs_workspace_bytes") if workspace is None else workspace
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_commit_jobs(self.h, C.byref(st), C.byref(pl), self._rows(slots, n, 1, torch.int32, "slots").data_ptr(),
+                                                    C.byref(ch), float(eps), decision_bound.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_commit_jobs")
+
     def _check_primals(self, fixed, prim, B):
         def count(t):
             return t.numel() if torch.is_tensor(t) else t.size      # (tensors, numpy arrays, _HostBuf)

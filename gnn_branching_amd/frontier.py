@@ -9,6 +9,10 @@ between are the kernels of csrc/gnnb_k_frontier.h (gather, expand, net_eval, com
 The rule of a round is ``branch_and_bound``'s, for K domains at once: the children of all K parents are bounded, then
 global_ub = min(global_ub, ub of every feasible child), then every child is kept (lb < global_ub - eps, below the decision bound, an
 undecided ReLU left) or closed against that one global_ub.  With K = 1 this is ``branch_and_bound`` with ``child_lp="dual_device"``.
+
+``verify_properties`` runs many JOBS -- a box, a property row, a decision bound, all on one bound network -- through
+the same round of launches: the pool is cut into segments of ``capacity`` slots, a segment holds one job and has its own record, and inside
+its segment a job runs the rule above unchanged, so it gets the result ``branch_and_bound_frontier`` gives it alone, bit for bit.
 """
 import ctypes as C
 import math
@@ -114,7 +118,68 @@ def _check_args(K, n_iter, lr, eps, max_rounds, capacity):
     return capacity
 
 
-class FrontierRun:
+class _Round:
+    """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
+
+    def _buffers(self, n_parents, n_children, in_shape, parent_side):
+        """The rows, workspaces and argument structs of a round of up to n_parents parents.  self.x_lo / x_hi / pw / pb: the children's
+        boxes and property rows; parent_side: the parents' (the same tensors when every row has one box and one property)."""
+        eng, dev = self.eng, self.eng.device
+        self.P = _Rows(eng, self.fixed, n_parents, in_shape, True)
+        self.Ch = _Rows(eng, self.fixed, n_children, in_shape, False)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def ws(sizer, B):
+            return torch.empty(max(1, getattr(self.lib, sizer)(eng.h, B)), dtype=torch.uint8, device=dev)
+        self.ws_fwd, self.ws_kw = ws("gnnb_workspace_bytes", n_parents), ws("gnnb_kw_workspace_bytes", n_children)
+        self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
+        self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
+        # the argument structs of the existing batch entry points over these rows (pointers never change; B does)
+        P, Ch = self.P, self.Ch
+        self._keep = [table(g) for g in (P.lb, P.ub, P.lb32, P.ub32, P.dual, P.prims, Ch.lb, Ch.ub, Ch.plb, Ch.pub, Ch.dual, Ch.prims)]
+        t = self._keep
+        px_lo, px_hi, ppw, ppb = parent_side
+        self.dual_P = _lib.DualBatch(t[0], t[1], px_lo.data_ptr(), px_hi.data_ptr(), ppw.data_ptr(), ppb.data_ptr(), P.mask.data_ptr(), self.ng)
+        self.fwd_P = _lib.Batch(t[2], t[3], t[4], t[5], P.x_lp.data_ptr(), ppw.data_ptr(), ppb.data_ptr(), P.amb.data_ptr(), self.ng,
+                                len(P.dual), len(P.prims))
+        self.kw_Ch = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), t[8], t[9],
+                                  Ch.split.data_ptr(), self.ng)
+        self.dual_Ch = _lib.DualBatch(t[6], t[7], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), self.ng)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def _bound_children(self, B, warm):
+        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B child rows."""
+        Ch, lib, h, t = self.Ch, self.lib, self.eng.h, self._keep
+        with torch.cuda.device(self.eng.device):
+            _lib.check(lib.gnnb_kw_bounds(h, C.byref(self.kw_Ch), B, t[6], t[7], None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
+                                          self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
+            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_Ch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
+                                            Ch.bound.data_ptr(), None, None, t[10], t[11], Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
+                                            self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
+        self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=(self.pw, self.pb), workspace=self.ws_eval)
+
+    def _score_parents(self, B):
+        """gnnb_dual_ascent at n_iter = 0 (the scorer's inputs at the stored best point: one evaluation of g instead of ~120 KB of fp32
+        inputs per open domain) and gnnb_forward over the first B parent rows."""
+        P, lib, h, t = self.P, self.lib, self.eng.h, self._keep
+        with torch.cuda.device(self.eng.device):
+            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_P), B, 0, self.lr, P.alpha.data_ptr(), P.beta.data_ptr(), 1, P.bound.data_ptr(), None, None,
+                                            t[4], t[5], P.x_lp.data_ptr(), P.lb32[-1].data_ptr(), self.ws_dual.data_ptr(), self.ws_dual.numel(),
+                                            self._stream()), "gnnb_dual_ascent")
+            _lib.check(lib.gnnb_forward(h, C.byref(self.fwd_P), B, P.scores.data_ptr(), P.dec.data_ptr(), self.status.data_ptr(), self.ws_fwd.data_ptr(),
+                                        self.ws_fwd.numel(), self._stream()), "gnnb_forward")
+        self.status_all |= self.status
+
+    def check_status(self):
+        from .engine import _raise_for_status
+        _raise_for_status(int(self.status_all.cpu()[0]))
+
+
+class FrontierRun(_Round):
     """The device side of ``branch_and_bound_frontier``: ``root()`` once, then per round ``launch_round(k)`` (device work only, nothing
     synchronises) and ``read_state()`` (the round's one device-to-host copy)."""
 
@@ -136,42 +201,8 @@ class FrontierRun:
         self.x_hi = lp.input_ub.reshape(1, -1).to(dev, torch.float64).expand(n, -1).contiguous()
         self.pw = self.prop_layer.weight.detach().reshape(1, -1).to(dev, torch.float32).expand(n, -1).contiguous()
         self.pb = self.prop_layer.bias.detach().reshape(1).to(dev, torch.float32).expand(n).contiguous()
-        self.P = _Rows(eng, self.fixed, K, in_shape, True)
-        self.Ch = _Rows(eng, self.fixed, n, in_shape, False)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def ws(sizer, B):
-            return torch.empty(max(1, getattr(self.lib, sizer)(eng.h, B)), dtype=torch.uint8, device=dev)
-        self.ws_fwd, self.ws_kw, self.ws_dual = ws("gnnb_workspace_bytes", K), ws("gnnb_kw_workspace_bytes", n), ws("gnnb_dual_workspace_bytes", n)
-        self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n), ws("gnnb_frontier_commit_workspace_bytes", K)
-        # the argument structs of the existing batch entry points over these rows (pointers never change; B does)
-        P, Ch = self.P, self.Ch
-        self._keep = [table(g) for g in (P.lb, P.ub, P.lb32, P.ub32, P.dual, P.prims, Ch.lb, Ch.ub, Ch.plb, Ch.pub, Ch.dual, Ch.prims)]
-        t = self._keep
-        self.dual_P = _lib.DualBatch(t[0], t[1], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), P.mask.data_ptr(), self.ng)
-        self.fwd_P = _lib.Batch(t[2], t[3], t[4], t[5], P.x_lp.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), P.amb.data_ptr(), self.ng,
-                                len(P.dual), len(P.prims))
-        self.kw_Ch = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), t[8], t[9],
-                                  Ch.split.data_ptr(), self.ng)
-        self.dual_Ch = _lib.DualBatch(t[6], t[7], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), self.ng)
+        self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
         self.slots = None
-
-    # ---- the existing batch entry points on the preallocated rows ------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _bound_children(self, B, warm):
-        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B child rows."""
-        Ch, lib, h, t = self.Ch, self.lib, self.eng.h, self._keep
-        with torch.cuda.device(self.eng.device):
-            _lib.check(lib.gnnb_kw_bounds(h, C.byref(self.kw_Ch), B, t[6], t[7], None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
-                                          self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
-            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_Ch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
-                                            Ch.bound.data_ptr(), None, None, t[10], t[11], Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
-                                            self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
-        self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=(self.pw, self.pb), workspace=self.ws_eval)
 
     def _commit(self, slots):
         Ch = self.Ch
@@ -200,17 +231,10 @@ class FrontierRun:
 
     def launch_round(self, k, in_use):
         """One round over the k <= K open domains of lowest bound.  Device work only."""
-        P, Ch, eng, lib, h, t, pool = self.P, self.Ch, self.eng, self.lib, self.eng.h, self._keep, self.pool
+        P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
         slots = self.slots = self.pick(k, in_use)
         eng.frontier_gather(pool, slots, self.x_lo, self.x_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
-        with torch.cuda.device(eng.device):
-            # the scorer's inputs at the stored best point: one evaluation of g (n_iter = 0) instead of ~120 KB of fp32 inputs per open domain
-            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_P), k, 0, self.lr, P.alpha.data_ptr(), P.beta.data_ptr(), 1, P.bound.data_ptr(), None, None,
-                                            t[4], t[5], P.x_lp.data_ptr(), P.lb32[-1].data_ptr(), self.ws_dual.data_ptr(), self.ws_dual.numel(),
-                                            self._stream()), "gnnb_dual_ascent")
-            _lib.check(lib.gnnb_forward(h, C.byref(self.fwd_P), k, P.scores.data_ptr(), P.dec.data_ptr(), self.status.data_ptr(), self.ws_fwd.data_ptr(),
-                                        self.ws_fwd.numel(), self._stream()), "gnnb_forward")
-        self.status_all |= self.status
+        self._score_parents(k)
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(2 * k, warm=True)
         self._commit(slots)
@@ -218,10 +242,6 @@ class FrontierRun:
     def read_state(self):
         """The state record as a list of Python floats: the one device-to-host copy of a round."""
         return self.pool.state.cpu().tolist()
-
-    def check_status(self):
-        from .engine import _raise_for_status
-        _raise_for_status(int(self.status_all.cpu()[0]))
 
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
@@ -284,3 +304,293 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
             f"lb {glb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     run.check_status()
     return global_lb, global_ub, rounds, bounded, reason
+
+
+# ---- many jobs in one pool --------------------------------------------------------------------------------------
+class FrontierJob:
+    """One verification job on the bound network: the box [input_lb, input_ub], the folded property layer Linear(N_L, 1) and the decision
+    bound (None: run to the gap)."""
+
+    def __init__(self, input_lb, input_ub, prop_layer, decision_bound=None):
+        self.input_lb, self.input_ub, self.prop_layer, self.decision_bound = input_lb, input_ub, prop_layer, decision_bound
+
+
+def _start_record():
+    inf = float("inf")
+    return [inf, inf, inf] + [0.0] * (_lib.FRONTIER_STATE_DOUBLES - 3)
+
+
+def _global_lb(st):
+    return min(st[_lib.FS_LOWEST_OPEN], st[_lib.FS_CLOSED_LB], st[_lib.FS_GLOBAL_UB])
+
+
+def _stop_reason(st, eps, decision_bound, rounds, max_rounds):
+    """``branch_and_bound_frontier``'s stop conditions on a record, but for "capacity", which ``plan_round`` decides."""
+    global_lb, global_ub = _global_lb(st), st[_lib.FS_GLOBAL_UB]
+    if int(st[_lib.FS_N_OPEN]) == 0:
+        return "exhausted"
+    if not global_ub - global_lb > eps:
+        return "gap"
+    if decision_bound is not None and (global_lb >= decision_bound or global_ub < decision_bound):
+        return "decision"
+    if rounds >= max_rounds:
+        return "max_rounds"
+    return None
+
+
+def plan_round(records, K, cap):
+    """The plan of a round from the host's copy of the records: a pure function.  records: per segment its record (a sequence of
+    ``_lib.FRONTIER_STATE_DOUBLES`` numbers), or None for a segment that takes no part (free, or its job has stopped).
+
+    Returns (entries, compact, stopped).  entries: [(segment, row0, k)] in segment order with k = min(K, open domains of the segment) and
+    row0 the running sum of k; compact: per segment, whether it must be compacted before the round (slots in use + k > cap, as
+    ``branch_and_bound_frontier`` does for its pool); stopped: the segments whose open domains leave no room for k more (open + k > cap:
+    the "capacity" stop), which get no entry.  A segment without an open domain gets no entry either."""
+    entries, compact, stopped, row0 = [], [False] * len(records), [], 0
+    for s, st in enumerate(records):
+        if st is None:
+            continue
+        n_open, in_use = int(st[_lib.FS_N_OPEN]), int(st[_lib.FS_IN_USE])
+        k = min(K, n_open)
+        if k < 1:
+            continue
+        if n_open + k > cap:
+            stopped.append(s)
+            continue
+        compact[s] = in_use + k > cap
+        entries.append((s, row0, k))
+        row0 += k
+    return entries, compact, stopped
+
+
+class RoundPlan:
+    """A plan on both sides of the link: ``host`` is pinned, ``device`` receives it by a non_blocking copy (3 int32 per entry)."""
+
+    def __init__(self, device, max_entries, segments, seg_cap):
+        self.host = torch.zeros(max_entries, 3, dtype=torch.int32).pin_memory()
+        self.device = torch.zeros(max_entries, 3, dtype=torch.int32, device=device)
+        self.n_entries, self.n, self.segments, self.seg_cap = 0, 0, segments, seg_cap
+
+    def send(self, entries):
+        self.n_entries, self.n = len(entries), sum(e[2] for e in entries)
+        self.host[:len(entries)] = torch.tensor(entries, dtype=torch.int32).reshape(-1, 3)
+        self.device.copy_(self.host, non_blocking=True)
+
+
+def _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds):
+    jobs = list(jobs)
+    if not jobs:
+        raise ValueError("no job")
+    if not isinstance(K, int) or isinstance(K, bool) or K < 1:
+        raise ValueError(f"K = {K!r}: a positive integer")
+    if capacity is None:
+        capacity = max(256, 4 * K + 1)
+    capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)
+    if segments is None:
+        segments = max(1, min(len(jobs), 64, 16383 // K))
+    if not isinstance(segments, int) or isinstance(segments, bool) or segments < 1 or segments * K > 16383:
+        raise ValueError(f"segments = {segments!r}: a positive integer with segments * K <= 16383 (a full round's 2n child rows stay within 32767)")
+    if segments * capacity > 2 ** 31 - 1:
+        raise ValueError(f"{segments} segments of {capacity} slots: more than 2^31 - 1 slots")
+    shape = None
+    for j, job in enumerate(jobs):
+        if type(job.prop_layer) is not nn.Linear or job.prop_layer.out_features != 1:
+            raise ValueError(f"job {j}: the property layer must be the folded Linear(., 1)")
+        if tuple(job.input_lb.shape) != tuple(job.input_ub.shape) or (shape is not None and tuple(job.input_lb.shape) != shape):
+            raise ValueError(f"job {j}: every box must have one input shape")
+        shape = tuple(job.input_lb.shape)
+    return jobs, segments, capacity, shape
+
+
+class JobsRun(_Round):
+    """The device side of ``verify_properties``: a pool of ``segments`` segments of ``cap`` slots with one record each, the jobs' boxes and
+    property rows as device tables, and the rows of a round of up to segments * K parents.  ``launch_roots`` / ``launch_round`` are device
+    work only; ``read_state`` is the one synchronising copy."""
+
+    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps):
+        self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
+        self.fixed = list(fixed_layers)
+        eng = self.eng = choice.model.engine()
+        eng.bind(self.fixed, in_shape)
+        dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        N0, NL, S, n = eng.sizes[0], eng.sizes[-2], segments, segments * K
+        self.pool = DomainPool(eng, S * cap)
+        self.start = torch.tensor(_start_record(), dtype=f64, device=dev)
+        self.pool.state = self.start.repeat(S, 1)
+        # the jobs (J, .) and what the segments hold of them (S, .)
+        self.job_x_lo = torch.stack([j.input_lb.reshape(-1) for j in jobs]).to(dev, f64)
+        self.job_x_hi = torch.stack([j.input_ub.reshape(-1) for j in jobs]).to(dev, f64)
+        self.job_pw = torch.stack([j.prop_layer.weight.detach().reshape(-1) for j in jobs]).to(dev, f32)
+        self.job_pb = torch.stack([j.prop_layer.bias.detach().reshape(()) for j in jobs]).to(dev, f32)
+        self.job_db = torch.tensor([float("nan") if j.decision_bound is None else float(j.decision_bound) for j in jobs], dtype=f64).to(dev)
+        self.seg_x_lo, self.seg_x_hi = torch.zeros(S, N0, dtype=f64, device=dev), torch.zeros(S, N0, dtype=f64, device=dev)
+        self.seg_pw, self.seg_pb = torch.zeros(S, NL, dtype=f32, device=dev), torch.zeros(S, dtype=f32, device=dev)
+        self.seg_db = torch.full((S,), float("nan"), dtype=f64, device=dev)
+        # the rows' boxes and property rows: the parents' and the children's (k_frontier_rows_jobs fills both)
+        self.px_lo, self.px_hi = torch.zeros(n, N0, dtype=f64, device=dev), torch.zeros(n, N0, dtype=f64, device=dev)
+        self.ppw, self.ppb = torch.zeros(n, NL, dtype=f32, device=dev), torch.zeros(n, dtype=f32, device=dev)
+        self.x_lo, self.x_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
+        self.pw, self.pb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
+        self._buffers(n, 2 * n, in_shape, (self.px_lo, self.px_hi, self.ppw, self.ppb))
+        self.ws_commit = torch.empty(max(1, self.lib.gnnb_frontier_commit_jobs_workspace_bytes(eng.h, n)), dtype=torch.uint8, device=dev)
+        self.slots, self.row_seg = torch.zeros(n, dtype=i32, device=dev), torch.zeros(n, dtype=i32, device=dev)
+        self.plan = RoundPlan(dev, S, S, cap)
+        self.root_live = torch.tensor([1, 0] * S, dtype=i32).to(dev)
+        self.flags_host = torch.zeros(S, dtype=i32).pin_memory()
+        self.flags = torch.zeros(S, dtype=i32, device=dev)
+        self.slot_seg = torch.arange(S * cap, device=dev) // cap
+
+    def release(self, seg):
+        """The job of segment ``seg`` leaves: no open slot, the start record."""
+        self.pool.open[seg * self.cap:(seg + 1) * self.cap].zero_()
+        self.pool.state[seg].copy_(self.start)
+
+    def admit(self, seg, job):
+        """Job number ``job`` takes the (released) segment ``seg``: its box, property row and decision bound, device to device."""
+        self.seg_x_lo[seg].copy_(self.job_x_lo[job])
+        self.seg_x_hi[seg].copy_(self.job_x_hi[job])
+        self.seg_pw[seg].copy_(self.job_pw[job])
+        self.seg_pb[seg].copy_(self.job_pb[job])
+        self.seg_db[seg].copy_(self.job_db[job])
+
+    def _commit(self, n):
+        Ch = self.Ch
+        self.eng.frontier_commit_jobs(self.pool, self.plan, self.slots[:n], Ch.mask, Ch.lb, Ch.ub, Ch.infeasible, Ch.bound, Ch.alpha, Ch.beta, Ch.ubv,
+                                      Ch.live, self.pool.state, self.seg_db, eps=self.eps, workspace=self.ws_commit)
+
+    def _rows_of_plan(self):
+        self.eng.frontier_rows_jobs(self.plan, self.row_seg, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.px_lo, self.px_hi, self.ppw,
+                                    self.ppb, self.x_lo, self.x_hi, self.pw, self.pb)
+
+    def launch_roots(self, segs):
+        """The root phase: the roots of the jobs just admitted to ``segs`` (ascending), one plan entry of k = 1 each.  Child row 2e is the
+        root of entry e -- every ReLU undecided, no parent, the default start of the ascent -- and row 2e + 1 its dead sibling (the same
+        problem, live = 0); the commit puts the root into the segment's first slot, as ``FrontierRun.root`` enters its pool."""
+        E, Ch = len(segs), self.Ch
+        self.plan.send([(s, e, 1) for e, s in enumerate(segs)])
+        self.row_seg[:E] = self.plan.device[:E, 0]
+        self.slots[:E] = self.plan.device[:E, 0] * self.cap
+        self._rows_of_plan()
+        Ch.mask[:2 * E].fill_(-1)
+        Ch.split[:2 * E].fill_(-1)
+        Ch.live[:2 * E] = self.root_live[:2 * E]
+        self._bound_children(2 * E, warm=False)
+        self._commit(E)
+
+    def compact(self, flagged):
+        """``DomainPool.compact``'s rule inside every segment of ``flagged`` (a list of booleans per segment), the others left in place: one
+        stable sort of the whole pool on the key 2 segment + (segment flagged and slot closed), then indexing.  No synchronisation."""
+        pool = self.pool
+        self.flags_host.copy_(torch.tensor(flagged, dtype=torch.int32))
+        self.flags.copy_(self.flags_host, non_blocking=True)
+        flag = self.flags[self.slot_seg] > 0
+        order = torch.sort(2 * self.slot_seg + (flag & (pool.open == 0)), stable=True).indices
+        pool.mask, pool.alpha, pool.beta, pool.bound, pool.open = (t[order].contiguous() for t in (pool.mask, pool.alpha, pool.beta, pool.bound, pool.open))
+        pool.lb = [t[order].contiguous() for t in pool.lb]
+        pool.ub = [t[order].contiguous() for t in pool.ub]
+        pool.state[:, _lib.FS_IN_USE] = torch.where(self.flags > 0, pool.state[:, _lib.FS_N_OPEN], pool.state[:, _lib.FS_IN_USE])
+
+    def launch_round(self, entries):
+        """One round over the plan's entries [(segment, row0, k)].  Device work only."""
+        P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
+        self.plan.send(entries)
+        n = self.plan.n
+        eng.frontier_pick_jobs(pool, self.plan, pool.state, self.slots, self.row_seg)
+        self._rows_of_plan()
+        slots = self.slots[:n]
+        eng.frontier_gather(pool, slots, self.px_lo, self.px_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
+        self._score_parents(n)
+        eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
+        self._bound_children(2 * n, warm=True)
+        self._commit(n)
+
+    def read_state(self):
+        """The (segments, 9) records as lists of Python floats: the one device-to-host copy of a round."""
+        return self.pool.state.cpu().tolist()
+
+
+def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
+    """Branch and bound on many jobs at once: every job gets the result ``branch_and_bound_frontier`` gives it alone with
+    ``capacity=capacity``, bit for bit, while a round's launches serve all the jobs in flight.
+
+    choice: a ``GraphChoice``; fixed_layers: the network without a property layer (bound once); jobs: ``FrontierJob``s of one input shape.
+    The pool is ``segments`` segments (None: min(len(jobs), 64, 16383 // K)) of ``capacity`` slots (None: max(256, 4K + 1)); a segment
+    holds one job at a time.  Per iteration: the finished jobs leave, waiting jobs take the free segments in list order (lowest segment
+    first) and their roots are bounded in a root phase; then one round expands the up-to-K open domains of lowest bound of every job in
+    flight (``plan_round``).  K, n_iter, lr, eps, max_rounds are ``branch_and_bound_frontier``'s, per job.  A job whose root is infeasible
+    ends with the reason "infeasible_root" and the bounds (+inf, +inf).  trace: None, or a list that receives per round and per entry a
+    dict of the one-job trace's keys (slots are global: segment * capacity + the job's own) plus "job", "segment" and "round" (extra
+    device-to-host copies: off in a timed run).
+
+    Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps)
+    F = _lib
+    results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
+    seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
+    waiting = list(range(len(jobs)))
+
+    def check(st):
+        if st[F.FS_OVERFLOW] != 0 or math.isnan(st[F.FS_GLOBAL_UB]):
+            raise RuntimeError(f"frontier state record is inconsistent: {st}")
+
+    def reason_of(s):
+        j = seg_job[s]
+        if rec[s][F.FS_INFEASIBLE] > 0 and rounds[j] == 0:
+            return "infeasible_root"
+        return "capacity" if capacity_stop[s] else _stop_reason(rec[s], eps, jobs[j].decision_bound, rounds[j], max_rounds)
+
+    while True:
+        for s in range(S):                                        # 1. the finished jobs leave
+            j = seg_job[s]
+            reason = None if j is None else reason_of(s)
+            if reason is not None:
+                inf = float("inf")
+                results[j] = (inf, inf, 0, 1, reason) if reason == "infeasible_root" else (_global_lb(rec[s]), rec[s][F.FS_GLOBAL_UB], rounds[j], bounded[j], reason)
+                log(f"job {j} segment {s}: {reason} after {rounds[j]} rounds, lb {results[j][0]:.5f} ub {results[j][1]:.5f}")
+                run.release(s)
+                seg_job[s], rec[s], capacity_stop[s] = None, None, False
+        admitted = []
+        for s in range(S):                                        # 2. waiting jobs take the free segments, lowest first
+            if seg_job[s] is None and waiting:
+                seg_job[s] = waiting.pop(0)
+                run.admit(s, seg_job[s])
+                admitted.append(s)
+        if admitted:                                              # 3. the root phase
+            run.launch_roots(admitted)
+            st = run.read_state()
+            for s in admitted:
+                rec[s], bounded[seg_job[s]] = st[s], 1
+                if not rec[s][F.FS_INFEASIBLE] > 0:
+                    check(rec[s])
+                log(f"job {seg_job[s]} segment {s}: root lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
+        if all(j is None for j in seg_job):
+            break
+        entries, compact, stopped = plan_round([None if seg_job[s] is None or reason_of(s) is not None else rec[s] for s in range(S)], K, cap)
+        for s in stopped:
+            capacity_stop[s] = True
+        if not entries:
+            continue
+        if any(compact):
+            run.compact(compact)
+        run.launch_round(entries)
+        if trace is not None:
+            P, Ch = run.P, run.Ch
+            for s, row0, k in entries:
+                a, b, c, d = row0, row0 + k, 2 * row0, 2 * row0 + 2 * k
+                trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], "slots": run.slots[a:b].cpu().tolist(),
+                              "parent_bounds": P.bound[a:b].cpu().tolist(), "decisions": P.dec[a:b].cpu().tolist(),
+                              "child_bounds": Ch.bound[c:d].cpu().tolist(), "child_ub": Ch.ubv[c:d].cpu().tolist(),
+                              "live": Ch.live[c:d].cpu().tolist(), "infeasible": Ch.infeasible[c:d].cpu().tolist()})
+        st = run.read_state()
+        for s, _, k in entries:
+            j = seg_job[s]
+            rec[s] = st[s]
+            check(rec[s])
+            rounds[j] += 1
+            bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
+            log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
+                f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
+    run.check_status()
+    return results

@@ -313,6 +313,46 @@ size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K);
 int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* children, double eps,
                          double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- many jobs in one pool (gnn_branching_amd/frontier.py verify_properties runs the loop) ----
+ * A JOB is a box, a property row and a decision bound on the bound network.  The pool is `segments` segments of `seg_cap` slots (segment
+ * s: slots [s seg_cap, (s+1) seg_cap)), gnnb_pool.capacity = segments * seg_cap; a segment holds one job at a time and has its own state
+ * record, so `state` is (segments, GNNB_FRONTIER_STATE_DOUBLES) and slots-in-use counts from the segment's first slot.  Inside its
+ * segment a job runs the rule above with capacity = seg_cap, whatever else is in flight.
+ *
+ * A round's PLAN: n_entries entries {segment, row0, k} of int32, one per job that takes part, row0 the running sum of k, n the sum.
+ * The job's k parents are rows [row0, row0 + k) of every (n, .) array, its children rows [2 row0, 2 row0 + 2k) of every (2n, .) array;
+ * between the three entry points below run gnnb_frontier_gather / _expand (K = n) and the batch entry points (B = n or 2n) on global slot
+ * numbers.  The entry points read `host` for their checks (before any launch), the kernels read `device`, which holds the same values.
+ * Refused with GNNB_E_INVALID: a null handle or argument; no entry, n < 1 or n > 32767; an entry whose segment lies outside the pool or
+ * whose k < 1; entries that do not tile the rows [0, n) in order; a pool whose capacity is not segments * seg_cap; a network past the
+ * 4096-node cap.  GNNB_E_STATE before gnnb_bind_network, GNNB_E_NOMEM for a short workspace.  Stream-ordered, no allocation, no
+ * synchronisation; no kernel waits on another workgroup, no reduction mixes two entries: an entry's result depends on its segment alone. */
+typedef struct {
+  const int32_t* host;                /* (n_entries, 3) {segment, row0, k}                                             */
+  const int32_t* device;              /* the same values in device memory                                              */
+  int32_t n_entries, n;
+  int32_t segments, seg_cap;
+} gnnb_plan;
+
+/* Per entry: the k slots of lowest key among the segment's first slots-in-use, ascending, the key being the bound of an open slot and
+ * +inf of a closed one, equal keys by slot.  Writes slots[row0 + r] (GLOBAL slot numbers) and row_seg[row0 + r] = segment; device (n). */
+int gnnb_frontier_pick_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const double* state, int32_t* slots, int32_t* row_seg,
+                            void* stream);
+
+/* The rows the batch entry points read, from per-segment tables seg_x_lo / seg_x_hi (segments, N_0) fp64, seg_prop_w (segments, N_L),
+ * seg_prop_b (segments) fp32: parent row i (x_lo / x_hi (n, N_0), prop_w (n, N_L), prop_b (n)) gets segment row_seg[i], child row c
+ * (child_* with 2n rows) segment row_seg[c >> 1].  row_seg: device (n), as gnnb_frontier_pick_jobs wrote it. */
+int gnnb_frontier_rows_jobs(gnnb_t* h, const gnnb_plan* plan, const int32_t* row_seg, const double* seg_x_lo, const double* seg_x_hi,
+                            const float* seg_prop_w, const float* seg_prop_b, double* x_lo, double* x_hi, float* prop_w, float* prop_b,
+                            double* child_x_lo, double* child_x_hi, float* child_prop_w, float* child_prop_b, void* stream);
+
+/* gnnb_frontier_commit per entry: its children, its parents' slots (slots: device (n), global numbers), its segment (a kept child beyond
+ * the segment's end is closed at its bound and counted in record [8]), its record, its decision bound (decision_bound: device
+ * (segments) fp64, NaN: none).  children: the 2n rows.  Segments without an entry are not touched. */
+size_t gnnb_frontier_commit_jobs_workspace_bytes(const gnnb_t* h, int n);
+int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_children* children,
+                              double eps, const double* decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
