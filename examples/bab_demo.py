@@ -1,12 +1,14 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--props 18]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 | --props 18]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
 
 --frontier K keeps the open domains in device memory and expands the K of lowest bound per round (gnn_branching_amd/frontier.py): bounds by
-gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.  With --props N it
+gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.  With --threshold T
+the rounds run --threshold's control flow on the device: the parents whose GNN split improves the bound by less than
+T get their BaBSR split bounded too, in the same round, and the better pair is kept.  With --props N it
 verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
 the true one, every round's launches serving all the properties in flight; one verdict line per property.
 
@@ -41,6 +43,8 @@ def main():
     args = ap.parse_args()
     if args.props is not None and (args.frontier is None or args.props < 1):
         ap.error("--props N needs --frontier K and N >= 1")
+    if args.props is not None and args.threshold is not None:
+        ap.error("--threshold is not available with --props (verify_properties branches on the GNN alone)")
 
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
@@ -65,10 +69,13 @@ def main():
         from gnn_branching_amd.frontier import branch_and_bound_frontier
         lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device")
         choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        stats = {}
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
-                                                                      max_rounds=max(1, args.nodes // (2 * args.frontier)))
+                                                                      max_rounds=max(1, args.nodes // (2 * args.frontier)),
+                                                                      branching_threshold=args.threshold, stats=stats)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
-        print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
+        kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
+        print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]

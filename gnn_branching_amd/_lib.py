@@ -49,6 +49,13 @@ class Children(C.Structure):
                 ("n_graph", C.c_int32)]
 
 
+class Fallback(C.Structure):
+    _fields_ = [("live", C.c_void_p), ("infeasible", C.c_void_p), ("bound", C.c_void_p), ("scores", C.c_void_p), ("intercepts", C.c_void_p),
+                ("scorer_mask", C.c_void_p), ("branching_threshold", C.c_double), ("decision_threshold", C.c_double),
+                ("kwbd_threshold", C.c_int32), ("sparsest_layer", C.c_int32), ("random_order", C.POINTER(C.c_int32)), ("n_order", C.c_int32),
+                ("icp", C.c_void_p), ("ineff", C.c_void_p)]
+
+
 class Plan(C.Structure):
     _fields_ = [("host", C.c_void_p), ("device", C.c_void_p), ("n_entries", C.c_int32), ("n", C.c_int32), ("segments", C.c_int32),
                 ("seg_cap", C.c_int32)]
@@ -104,6 +111,11 @@ SYMBOLS = [
     ("gnnb_frontier_commit_jobs_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_frontier_commit_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_void_p, C.POINTER(Children), C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_fallback_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_fallback", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.POINTER(Fallback)] + [C.c_void_p] * 6 +
+     [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_choose", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Children), C.POINTER(Children)] +
+     [C.c_void_p] * 4 + [C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -93,14 +93,16 @@ enum ProfClass {
   PC_EMBED, PC_PRE, PC_PRE_INP, PC_CONV_FWD, PC_CONVT_BWD, PC_DENSE_AGG, PC_PROP_FWD,
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
-  PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS, PC_COUNT
+  PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
+  PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
     "k_node_update", "k_input_update", "k_score", "k_argmax", "k_gather", "k_gather_input_update", "k_classify", "k_livesum", "k_top", "k_gather_update",
     "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent",
     "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store",
-    "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs"};
+    "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs",
+    "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1909,6 +1911,86 @@ extern "C" int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const
   run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * j.n), dim3(FR_THREADS), 0, st, a); });
   run.run(PC_FR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_decide_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, decision_bound); });
   run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * j.n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+// ---- the BaBSR fall-back below a branching threshold (reference plnn/relu_conv_gnnkwthreshold.py:151-195, the
+// decision rule of plnn/kw_score_conv.py:115-156) ----
+extern "C" size_t gnnb_frontier_fallback_workspace_bytes(const gnnb_t* h, int K) {
+  if (!h || !h->bound || K < 1) return 0;
+  return (size_t)K * FC_COUNT * sizeof(int32_t);
+}
+
+extern "C" int gnnb_frontier_fallback(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_fallback* in,
+                                      double* gnn_improvement, int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots,
+                                      int32_t* sel_decisions, int32_t* m, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_fallback";
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !in || !gnn_improvement || !kw_decisions || !sel_rows || !sel_slots || !sel_decisions || !m || !workspace)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (!in->live || !in->infeasible || !in->bound || !in->scores || !in->intercepts || !in->scorer_mask || !in->icp || !in->ineff ||
+      (in->n_order > 0 && !in->random_order))
+    return fail(GNNB_E_INVALID, "%s: null array among the inputs", who);
+  if (!(in->branching_threshold > 0.0 && in->branching_threshold <= 1.0) || in->kwbd_threshold < 0 || in->decision_threshold != in->decision_threshold)
+    return fail(GNNB_E_INVALID, "%s: branching_threshold = %g (0 < . <= 1), kwbd_threshold = %d (>= 0), decision_threshold = %g", who,
+                in->branching_threshold, in->kwbd_threshold, in->decision_threshold);
+  if (in->n_order < 0 || in->n_order > MAXL) return fail(GNNB_E_INVALID, "%s: random_order of %d layers (0..%d)", who, in->n_order, MAXL);
+  const size_t need = gnnb_frontier_fallback_workspace_bytes(h, K);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  FrFallbackArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
+  a.slots = slots; a.K = K; a.live = in->live; a.infeasible = in->infeasible; a.bound = in->bound;
+  a.scores = in->scores; a.icp_tb = in->intercepts; a.amb = in->scorer_mask;
+  a.branching_threshold = in->branching_threshold; a.decision_threshold = in->decision_threshold;
+  a.kwbd_threshold = in->kwbd_threshold; a.sparsest_layer = in->sparsest_layer; a.n_order = in->n_order;
+  for (int q = 0; q < in->n_order; ++q) a.order[q] = in->random_order[q];
+  a.icp = in->icp; a.ineff = in->ineff;
+  a.gnn_imp = gnn_improvement; a.kw_dec = kw_decisions; a.sel_rows = sel_rows; a.sel_slots = sel_slots; a.sel_dec = sel_decisions; a.m = m;
+  a.cand = (int32_t*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CANDIDATES, [&] { hipLaunchKernelGGL(k_frontier_candidates, dim3(K), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_FALLBACK, [&] { hipLaunchKernelGGL(k_frontier_fallback, dim3(1), dim3(64), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_choose(gnnb_t* h, const gnnb_pool* pool, int K, int m, const int32_t* sel_rows, const int32_t* sel_slots,
+                                    const int32_t* sel_decisions, const int32_t* gnn_decisions, const double* gnn_improvement,
+                                    const gnnb_children_rw* pa, const gnnb_children* pb, int32_t* ineff, double* kw_improvement,
+                                    int32_t* used_kw, int32_t* decisions, void* stream) {
+  const char* who = "gnnb_frontier_choose";
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (m < 0 || m > K) return fail(GNNB_E_INVALID, "%s: m = %d selected parents of K = %d", who, m, K);
+  if (!sel_rows || !sel_slots || !sel_decisions || !gnn_decisions || !gnn_improvement || !pa || !ineff || !kw_improvement || !used_kw || !decisions ||
+      (m > 0 && !pb))
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrChooseArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
+  if (m > 0) {
+    if (pa->n_graph != pool->n_graph || pb->n_graph != pool->n_graph)
+      return fail(GNNB_E_INVALID, "%s: the children have %d / %d graph layers, the pool %d", who, pa->n_graph, pb->n_graph, pool->n_graph);
+    if (!pa->mask || !pa->lb || !pa->ub || !pa->infeasible || !pa->bound || !pa->alpha || !pa->beta || !pa->ub_value || !pa->live ||
+        !pb->mask || !pb->lb || !pb->ub || !pb->infeasible || !pb->bound || !pb->alpha || !pb->beta || !pb->ub_value || !pb->live)
+      return fail(GNNB_E_INVALID, "%s: null array among the children's", who);
+    for (int k = 1; k <= a.s.L + 1; ++k) {
+      if (!pa->lb[k - 1] || !pa->ub[k - 1] || !pb->lb[k - 1] || !pb->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null bounds pointer for graph layer %d", who, k);
+      a.A.lb[k] = pa->lb[k - 1]; a.A.ub[k] = pa->ub[k - 1];
+      a.B.lb[k] = const_cast<double*>(pb->lb[k - 1]); a.B.ub[k] = const_cast<double*>(pb->ub[k - 1]);     // (B is only read)
+    }
+    a.A.mask = pa->mask; a.A.infeasible = pa->infeasible; a.A.bound = pa->bound; a.A.alpha = pa->alpha; a.A.beta = pa->beta; a.A.ubv = pa->ub_value;
+    a.A.live = pa->live;
+    a.B.mask = const_cast<int8_t*>(pb->mask); a.B.infeasible = const_cast<int32_t*>(pb->infeasible); a.B.bound = const_cast<double*>(pb->bound);
+    a.B.alpha = const_cast<double*>(pb->alpha); a.B.beta = const_cast<double*>(pb->beta); a.B.ubv = const_cast<double*>(pb->ub_value);
+    a.B.live = const_cast<int32_t*>(pb->live);
+  }
+  a.K = K; a.m = m; a.sel_rows = sel_rows; a.sel_slots = sel_slots; a.sel_dec = sel_decisions; a.gnn_dec = gnn_decisions; a.gnn_imp = gnn_improvement;
+  a.ineff = ineff; a.kw_imp = kw_improvement; a.used = used_kw; a.dec = decisions;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CHOOSE, [&] { hipLaunchKernelGGL(k_frontier_choose, dim3(1), dim3(FR_THREADS), 0, st, a); });
+  if (m > 0) run.run(PC_FR_CHOOSE_COPY, [&] { hipLaunchKernelGGL(k_frontier_choose_copy, dim3(2 * m, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 

@@ -1,5 +1,6 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
-// gnnb_frontier_gather, gnnb_frontier_expand, gnnb_net_eval, gnnb_frontier_commit.  Between them run the existing batch kernels
+// gnnb_frontier_gather, gnnb_frontier_expand, gnnb_net_eval, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
+// a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose).  Between them run the existing batch kernels
 // (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched.
 //
 // The POOL is a struct of arrays over `capacity` slots: mask (cap, R) int8, the fp64 bounds of graph layers 1..L+1 (cap, N_k) exactly as
@@ -442,4 +443,242 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide_jobs(FrCommitArg
   if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
   const FrView v{seg * j.seg_cap, j.seg_cap, row0, k, a.state + (long)seg * FS_COUNT, decision_bound[seg]};
   fr_decide(a, v, red, cnt);
+}
+
+// ---- the BaBSR fall-back below a branching threshold ---------------------------------------------------------
+// Reference plnn/relu_conv_gnnkwthreshold.py:151-195 for the K parents of a round, once the GNN decisions' children (pair A) are bounded:
+//
+//   * k_frontier_candidates   one workgroup per parent row: the GNN's improvement of the bound (:151) and the three decisions
+//                             plnn/kw_score_conv.py:115-156 can return for the row -- by score, by intercept, by layer order -- from
+//                             gnnb_babsr's scores and intercepts.  Per ReLU layer the first maximum, the first minimum and the first
+//                             undecided node: per-thread partials in index order, then a fixed tree on the total order (value, index),
+//                             as fr_key_less is for the pick; the thread layout cannot change the result.
+//   * k_frontier_fallback     one workgroup per view, ONE thread walking the view's rows in order (fr_fallback_walk): the threshold test
+//                             (:155), the intercept counter's logic, the lookup of the node's inefficiency count (:160-167); writes the
+//                             KW decisions, the dense list of selected parents and their number m.
+//   * k_frontier_choose       one workgroup per view (fr_choose): the KW improvement (:173) and bab_caller.resolve_branching (:176-192)
+//                             per selected parent, the ineff counts by one thread in row order, the final decisions.
+//   * k_frontier_choose_copy  pair B's rows over pair A's, only for the parents that chose pair B; spread over workgroups as
+//                             k_frontier_expand.
+//
+// fp32 scores are compared after promotion to double (Python's .item()); the improvement is fp64 in the reference's operation order
+// (2 bound is exact, so contraction cannot change it; the division is correctly rounded).
+
+enum { FC_SCORE_LAY, FC_SCORE_IDX, FC_SCORE_HOLDS, FC_ICP_LAY, FC_ICP_IDX, FC_ORDER_LAY, FC_ORDER_IDX, FC_VALID, FC_COUNT };   // a row's candidates
+
+struct FrFallbackArgs {
+  FrShape s; FrPool p;
+  const int32_t* slots; int K;
+  const int32_t* live; const int32_t* infeasible; const double* bound;          // pair A (2K)
+  const float* scores; const float* icp_tb; const float* amb;                   // (K, R)
+  double branching_threshold, decision_threshold;
+  int kwbd_threshold, sparsest_layer, n_order;
+  int order[MAXL];
+  int32_t* icp; const int32_t* ineff;
+  double* gnn_imp; int32_t* kw_dec; int32_t* sel_rows; int32_t* sel_slots; int32_t* sel_dec; int32_t* m;
+  int32_t* cand;                                                                // workspace (K, FC_COUNT)
+};
+
+struct FrRowsRW {               // child rows (gnnb_children / gnnb_children_rw); lb / ub: graph layers 1..L+1
+  int8_t* mask; double* lb[MAXL + 2]; double* ub[MAXL + 2];
+  int32_t* infeasible; double* bound; double* alpha; double* beta; double* ubv; int32_t* live;
+};
+
+struct FrChooseArgs {
+  FrShape s; FrPool p;
+  int K, m;
+  const int32_t* sel_rows; const int32_t* sel_slots; const int32_t* sel_dec; const int32_t* gnn_dec; const double* gnn_imp;
+  FrRowsRW A, B;                                                                // B is only read
+  int32_t* ineff; double* kw_imp; int32_t* used; int32_t* dec;
+};
+static_assert(sizeof(FrFallbackArgs) <= 4096 && sizeof(FrChooseArgs) <= 4096, "kernel arguments: 4 KiB");
+
+// What one job's fall-back sees of a round: its parents' rows [row0, row0 + K) (its dense selection starts at row0 too), its intercept
+// counter, its table of inefficient points, its m.  One job: {0, K, icp, ineff, m}.
+struct FrFbView {
+  int row0, K;
+  int32_t* icp; int32_t* ineff; int32_t* m;
+};
+
+__device__ __forceinline__ double fr_min0(double v) { return 0.0 < v ? 0.0 : v; }      // Python's min(v, 0)
+
+// bab_caller.gnn_improvement (relu_conv_gnnkwthreshold.py:151), its operation order
+__device__ __forceinline__ double fr_improvement(double lb0, double lb1, double bound) {
+  return (fr_min0(lb0) + fr_min0(lb1) - 2.0 * bound) / (-2.0 * bound);
+}
+
+__device__ __forceinline__ double fr_child_lb(const int32_t* infeasible, const double* bound, long c) {
+  return infeasible[c] ? __longlong_as_double(0x7ff0000000000000LL) : bound[c];       // an infeasible child cannot hold a counter-example
+}
+
+__device__ __forceinline__ bool fr_node(const FrShape& s, int lay, int idx, int* node) {
+  if (lay < 0 || lay >= s.L || idx < 0 || idx >= s.N[lay + 1]) return false;
+  *node = s.off[lay + 1] + idx;
+  return true;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_candidates(FrFallbackArgs a) {
+  __shared__ float sv[FR_THREADS], mv[FR_THREADS];
+  __shared__ int si[FR_THREADS], mi[FR_THREADS], ui[FR_THREADS], first[MAXL];
+  const int i = blockIdx.x, tid = threadIdx.x, R = a.s.R, L = a.s.L;
+  int32_t* out = a.cand + (long)i * FC_COUNT;
+  const int s = a.slots[i];
+  if (!fr_slot_ok(a.p, s) || !a.live[2 * i]) {          // no live GNN decision: the row takes no part (the whole workgroup leaves)
+    if (tid == 0) {
+      a.gnn_imp[i] = __longlong_as_double(0x7ff8000000000000LL);
+      for (int q = 0; q < FC_COUNT; ++q) out[q] = q == FC_VALID || q == FC_SCORE_HOLDS ? 0 : -1;
+    }
+    return;
+  }
+  int nan = 0, any_open = 0;
+  int best_l = -1, best_i = -1, icp_l = -1, icp_i = -1;
+  float best_v = 0.0f;
+  for (int k = 1; k <= L; ++k) {
+    const int Nk = a.s.N[k];
+    const long base = (long)i * R + a.s.off[k];
+    float bv = 0.0f, wv = 0.0f;
+    int bi = -1, wi = -1, u = -1;
+    for (int j = tid; j < Nk; j += FR_THREADS) {        // index order: a strict comparison keeps the first of equal values
+      const float v = a.scores[base + j], w = a.icp_tb[base + j];
+      nan |= (v != v) | (w != w);
+      if (bi < 0 || v > bv) { bv = v; bi = j; }
+      if (wi < 0 || w < wv) { wv = w; wi = j; }
+      if (u < 0 && a.amb[base + j] != 0.0f) u = j;
+    }
+    __syncthreads();                                    // (the previous layer's results have been read)
+    sv[tid] = bv; si[tid] = bi; mv[tid] = wv; mi[tid] = wi; ui[tid] = u;
+    __syncthreads();
+    for (int w = FR_THREADS / 2; w > 0; w >>= 1) {      // the total orders (value, index): the first maximum, the first minimum, the first index
+      if (tid < w) {
+        int o = si[tid + w];
+        if (o >= 0 && (si[tid] < 0 || sv[tid + w] > sv[tid] || (sv[tid + w] == sv[tid] && o < si[tid]))) { sv[tid] = sv[tid + w]; si[tid] = o; }
+        o = mi[tid + w];
+        if (o >= 0 && (mi[tid] < 0 || mv[tid + w] < mv[tid] || (mv[tid + w] == mv[tid] && o < mi[tid]))) { mv[tid] = mv[tid + w]; mi[tid] = o; }
+        o = ui[tid + w];
+        if (o >= 0 && (ui[tid] < 0 || o < ui[tid])) ui[tid] = o;
+      }
+      __syncthreads();
+    }
+    // between layers: the maximum of the tuples (value, index), the first layer that holds it; the LAST layer with an intercept below -1e-4
+    if (si[0] >= 0 && (best_l < 0 || sv[0] > best_v || (sv[0] == best_v && si[0] > best_i))) { best_l = k - 1; best_i = si[0]; best_v = sv[0]; }
+    if (mi[0] >= 0 && (double)mv[0] < -1e-4) { icp_l = k - 1; icp_i = mi[0]; }
+    if (tid == 0) first[k - 1] = ui[0];                 // (thread 0 alone reads it back)
+    any_open |= ui[0] >= 0;
+  }
+  nan = __syncthreads_or(nan);
+  if (tid != 0) return;
+  int ord_l = -1, ord_i = -1;
+  for (int q = a.n_order - 1; q >= 0 && ord_l < 0; --q) {         // random_order popped from its end: the first layer with an undecided node
+    const int l = a.order[q];
+    if (l >= 0 && l < L && first[l] >= 0) { ord_l = l; ord_i = first[l]; }
+  }
+  const double bound = a.p.bound[s];
+  a.gnn_imp[i] = bound < 0.0 ? fr_improvement(fr_child_lb(a.infeasible, a.bound, 2L * i), fr_child_lb(a.infeasible, a.bound, 2L * i + 1), bound) : 1.0;
+  out[FC_SCORE_LAY] = best_l; out[FC_SCORE_IDX] = best_i;
+  out[FC_SCORE_HOLDS] = best_l >= 0 && best_l != a.sparsest_layer && (double)best_v > a.decision_threshold;
+  out[FC_ICP_LAY] = icp_l; out[FC_ICP_IDX] = icp_i;
+  out[FC_ORDER_LAY] = ord_l; out[FC_ORDER_IDX] = ord_i;
+  out[FC_VALID] = !nan && any_open;
+}
+
+// The walk over a view's rows in order, by one thread: kw_score_conv.py:115-156 with the counter carried from row to row, then the
+// selection.  The counts in ineff are read as they stood before the round (nothing here writes them).
+__device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const FrFbView& v) {
+  const int tid = threadIdx.x;
+  for (int q = tid; q < 2 * v.K; q += blockDim.x) a.kw_dec[2L * v.row0 + q] = -1;
+  __syncthreads();
+  if (tid != 0) return;
+  int icp = *v.icp, m = 0;
+  for (int i = 0; i < v.K; ++i) {
+    const int row = v.row0 + i;
+    const int32_t* c = a.cand + (long)row * FC_COUNT;
+    if (!c[FC_VALID] || !(a.gnn_imp[row] < a.branching_threshold)) continue;        // :155
+    int lay, idx;
+    if (c[FC_SCORE_HOLDS]) {
+      lay = c[FC_SCORE_LAY]; idx = c[FC_SCORE_IDX];
+    } else if (c[FC_ICP_LAY] >= 0 && icp < 2) {
+      lay = c[FC_ICP_LAY]; idx = c[FC_ICP_IDX];
+      icp = lay != 0 ? 0 : icp + 1;
+    } else if (c[FC_ORDER_LAY] >= 0) {
+      lay = c[FC_ORDER_LAY]; idx = c[FC_ORDER_IDX];
+      icp = 0;
+    } else {
+      continue;                                         // random_order names no layer with an undecided node: no decision, the counter stays
+    }
+    a.kw_dec[2L * row] = lay; a.kw_dec[2L * row + 1] = idx;
+    int node;
+    if (!fr_node(a.s, lay, idx, &node) || !(v.ineff[node] < a.kwbd_threshold)) continue;        // :160-167
+    const int q = v.row0 + m++;
+    a.sel_rows[q] = row; a.sel_slots[q] = a.slots[row];
+    a.sel_dec[2L * q] = lay; a.sel_dec[2L * q + 1] = idx;
+  }
+  *v.icp = icp;
+  *v.m = m;
+}
+
+__global__ __launch_bounds__(64) void k_frontier_fallback(FrFallbackArgs a) {
+  const FrFbView v{0, a.K, a.icp, const_cast<int32_t*>(a.ineff), a.m};
+  fr_fallback_walk(a, v);
+}
+
+// bab_caller.resolve_branching for the view's m selected parents (entries [row0, row0 + m) of the dense lists, pair B's rows 2q, 2q + 1).
+__device__ __forceinline__ void fr_choose(const FrChooseArgs& a, const FrFbView& v, int m) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < v.K; i += blockDim.x) {
+    const long row = v.row0 + i;
+    a.dec[2 * row] = a.gnn_dec[2 * row]; a.dec[2 * row + 1] = a.gnn_dec[2 * row + 1];
+    a.kw_imp[row] = -1.0;
+    a.used[row] = 0;
+  }
+  __syncthreads();
+  for (int j = tid; j < m; j += blockDim.x) {
+    const long q = v.row0 + j;
+    const int row = a.sel_rows[q], s = a.sel_slots[q];
+    if (row < v.row0 || row >= v.row0 + v.K || !fr_slot_ok(a.p, s) || !a.B.live[2 * q]) continue;
+    const double kw = fr_improvement(fr_child_lb(a.B.infeasible, a.B.bound, 2 * q), fr_child_lb(a.B.infeasible, a.B.bound, 2 * q + 1), a.p.bound[s]);
+    const double gnn = a.gnn_imp[row];
+    a.kw_imp[row] = kw;
+    if (kw > gnn) {                                     // :185-192 (the inefficient case, :176-184, is counted below)
+      a.used[row] = 1;
+      a.dec[2L * row] = a.sel_dec[2 * q]; a.dec[2L * row + 1] = a.sel_dec[2 * q + 1];
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int j = 0; j < m; ++j) {                         // row order: two parents that name one node both count
+    const long q = v.row0 + j;
+    const int row = a.sel_rows[q], s = a.sel_slots[q];
+    int node;
+    if (row < v.row0 || row >= v.row0 + v.K || !fr_slot_ok(a.p, s) || !a.B.live[2 * q] || !fr_node(a.s, a.sel_dec[2 * q], a.sel_dec[2 * q + 1], &node)) continue;
+    const double kw = a.kw_imp[row];
+    if (kw < a.gnn_imp[row] && kw < 0.05) v.ineff[node] += 1;
+  }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_choose(FrChooseArgs a) {
+  const FrFbView v{0, a.K, nullptr, a.ineff, nullptr};
+  fr_choose(a, v, a.m);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_copy(FrChooseArgs a) {
+  const int c = blockIdx.x, q = c >> 1, t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int row = a.sel_rows[q];
+  if (row < 0 || row >= a.K || !a.used[row]) return;
+  const long d = 2L * row + (c & 1);
+  const int R = a.s.R, K1 = a.s.L + 1;
+  for (int r = t0; r < R; r += dt) {
+    a.A.mask[d * R + r] = a.B.mask[(long)c * R + r];
+    a.A.alpha[d * R + r] = a.B.alpha[(long)c * R + r];
+    a.A.beta[d * R + r] = a.B.beta[(long)c * R + r];
+  }
+  for (int k = 1; k <= K1; ++k) {
+    const int Nk = a.s.N[k];
+    for (int j = t0; j < Nk; j += dt) {
+      a.A.lb[k][d * Nk + j] = a.B.lb[k][(long)c * Nk + j];
+      a.A.ub[k][d * Nk + j] = a.B.ub[k][(long)c * Nk + j];
+    }
+  }
+  if (t0 == 0) {
+    a.A.infeasible[d] = a.B.infeasible[c]; a.A.bound[d] = a.B.bound[c]; a.A.ubv[d] = a.B.ubv[c]; a.A.live[d] = a.B.live[c];
+  }
 }

@@ -975,6 +975,87 @@ class ScorerEngine:
                                                ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_frontier_commit")
 
+    def babsr_rows(self, lb32, ub32, prop_w, scorer_mask, B, scores, intercepts):
+        """gnnb_babsr on the current stream over the first B of the parent rows ``frontier_gather`` wrote (lb32 / ub32: graph layers
+        0..L+1 fp32; prop_w (B, N_L) fp32; scorer_mask (B, R) fp32) into scores / intercepts (B, R) fp32.  Nothing is copied."""
+        R = self.R
+        tl, tu = self._layer_rows(lb32, B, 0, torch.float32, "lb32"), self._layer_rows(ub32, B, 0, torch.float32, "ub32")
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_babsr(self.h, tl, tu, len(self.sizes), self._rows(prop_w, B, self.sizes[-2], torch.float32, "prop_w").data_ptr(),
+                                     self._rows(scorer_mask, B, R, torch.float32, "scorer_mask").data_ptr(), B,
+                                     self._rows(scores, B, R, torch.float32, "scores").data_ptr(),
+                                     self._rows(intercepts, B, R, torch.float32, "intercepts").data_ptr(),
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_babsr")
+
+    def frontier_fallback(self, pool, slots, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, gnn_improvement, kw_decisions,
+                          sel_rows, sel_slots, sel_decisions, m, branching_threshold, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001,
+                          random_order=None, workspace=None):
+        """gnnb_frontier_fallback on the current stream: for the K parents in ``slots`` whose GNN children (pair A:
+        live / infeasible / bound, 2K rows) are bounded, the GNN's improvement of the bound into gnn_improvement (K,) fp64, the BaBSR
+        decision of every parent below ``branching_threshold`` into kw_decisions (K, 2) int32 ([-1, -1]: none), and the parents whose KW
+        point was inefficient fewer than ``kwbd_threshold`` times as a dense list in row order: sel_rows / sel_slots (K,), sel_decisions
+        (K, 2), their number m (1,), all int32.  scores / intercepts: ``babsr_rows`` on the parents' rows; icp (1,) int32 the run's
+        intercept counter (read and updated), ineff (R,) int32 the counts of inefficient KW points (read).  random_order: the ReLU layers
+        popped from the end (None: ``lp_producer._random_order``)."""
+        from .lp_producer import _random_order
+        K = int(slots.numel())
+        st, keep = self._pool(pool)
+        R, i32 = self.R, torch.int32
+        order = list(_random_order(len(self.sizes) - 2, sparsest_layer) if random_order is None else random_order)
+        order_c = (C.c_int32 * max(1, len(order)))(*order)
+        fb = _lib.Fallback(self._rows(live, 2 * K, 1, i32, "live").data_ptr(), self._rows(infeasible, 2 * K, 1, i32, "infeasible").data_ptr(),
+                           self._rows(bound, 2 * K, 1, torch.float64, "bound").data_ptr(), self._rows(scores, K, R, torch.float32, "scores").data_ptr(),
+                           self._rows(intercepts, K, R, torch.float32, "intercepts").data_ptr(),
+                           self._rows(scorer_mask, K, R, torch.float32, "scorer_mask").data_ptr(), float(branching_threshold), float(decision_threshold),
+                           int(kwbd_threshold), int(sparsest_layer), order_c, len(order), self._rows(icp, 1, 1, i32, "icp").data_ptr(),
+                           self._rows(ineff, R, 1, i32, "ineff").data_ptr())
+        ws = self._workspace("fallback", K, "gnnb_frontier_fallback_workspace_bytes") if workspace is None else workspace
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_fallback(self.h, C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K, C.byref(fb),
+                                                 self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(),
+                                                 self._rows(kw_decisions, K, 2, i32, "kw_decisions").data_ptr(),
+                                                 self._rows(sel_rows, K, 1, i32, "sel_rows").data_ptr(), self._rows(sel_slots, K, 1, i32, "sel_slots").data_ptr(),
+                                                 self._rows(sel_decisions, K, 2, i32, "sel_decisions").data_ptr(), self._rows(m, 1, 1, i32, "m").data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_fallback")
+
+    def _children(self, ch, n, what):
+        """The gnnb_children of a set of child rows (any object with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live) and what must
+        outlive the call."""
+        R = self.R
+        tl, tu = self._layer_rows(ch.lb, n, 1, torch.float64, what + ".lb"), self._layer_rows(ch.ub, n, 1, torch.float64, what + ".ub")
+        st = _lib.Children(self._rows(ch.mask, n, R, torch.int8, what + ".mask").data_ptr(), tl, tu,
+                           self._rows(ch.infeasible, n, 1, torch.int32, what + ".infeasible").data_ptr(),
+                           self._rows(ch.bound, n, 1, torch.float64, what + ".bound").data_ptr(),
+                           self._rows(ch.alpha, n, R, torch.float64, what + ".alpha").data_ptr(), self._rows(ch.beta, n, R, torch.float64, what + ".beta").data_ptr(),
+                           self._rows(ch.ubv, n, 1, torch.float64, what + ".ubv").data_ptr(), self._rows(ch.live, n, 1, torch.int32, what + ".live").data_ptr(),
+                           len(self.sizes))
+        return st, (tl, tu)
+
+    def frontier_choose(self, pool, K, m, sel_rows, sel_slots, sel_decisions, gnn_decisions, gnn_improvement, pair_a, pair_b, ineff, kw_improvement,
+                        used_kw, decisions):
+        """gnnb_frontier_choose on the current stream: ``bab_caller.resolve_branching`` for the m selected parents of ``frontier_fallback``
+        once their KW children (pair_b: 2m rows, rows 2j / 2j + 1 those of sel_rows[j]) are bounded.  A parent whose KW pair improves the
+        bound more than its GNN pair gets pair_b's rows copied over rows 2 sel_rows[j], + 1 of pair_a (2K rows) and the KW decision; one
+        whose KW pair improves less, and less than 0.05, adds 1 to ineff[node].  Writes kw_improvement (K,) fp64 (-1: not selected),
+        used_kw (K,) and decisions (K, 2) int32.  pair_a / pair_b: objects with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live."""
+        st, keep = self._pool(pool)
+        i32 = torch.int32
+        pa, keep_a = self._children(pair_a, 2 * K, "pair_a")
+        pb, keep_b = self._children(pair_b, 2 * max(m, 1), "pair_b")
+        with torch.cuda.device(self.device):
+            rc = self.lib.gnnb_frontier_choose(self.h, C.byref(st), K, m, self._rows(sel_rows, max(m, 1), 1, i32, "sel_rows").data_ptr(),
+                                               self._rows(sel_slots, max(m, 1), 1, i32, "sel_slots").data_ptr(),
+                                               self._rows(sel_decisions, max(m, 1), 2, i32, "sel_decisions").data_ptr(),
+                                               self._rows(gnn_decisions, K, 2, i32, "gnn_decisions").data_ptr(),
+                                               self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(), C.byref(pa), C.byref(pb),
+                                               self._rows(ineff, self.R, 1, i32, "ineff").data_ptr(),
+                                               self._rows(kw_improvement, K, 1, torch.float64, "kw_improvement").data_ptr(),
+                                               self._rows(used_kw, K, 1, i32, "used_kw").data_ptr(), self._rows(decisions, K, 2, i32, "decisions").data_ptr(),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "gnnb_frontier_choose")
+
     # ---- many jobs in one pool (frontier.py verify_properties; include/gnnb.h gnnb_frontier_*_jobs) ------------------------------------
     def _plan(self, plan):
         """The gnnb_plan of a ``frontier.RoundPlan`` (any object with its attributes): host (E, 3) int32 CPU tensor, device the same values

@@ -22,6 +22,7 @@ from torch import nn
 
 from . import _lib
 from .engine import table
+from .lp_producer import _random_order
 
 
 class DomainPool:
@@ -118,6 +119,16 @@ def _check_args(K, n_iter, lr, eps, max_rounds, capacity):
     return capacity
 
 
+def _check_threshold(branching_threshold, kwbd_threshold):
+    """The threshold mode's arguments (None: the mode is off)."""
+    if branching_threshold is None:
+        return
+    if isinstance(branching_threshold, bool) or not isinstance(branching_threshold, (int, float)) or not 0 < branching_threshold <= 1:
+        raise ValueError(f"branching_threshold = {branching_threshold!r}: None, or a number with 0 < branching_threshold <= 1")
+    if not isinstance(kwbd_threshold, int) or isinstance(kwbd_threshold, bool) or kwbd_threshold < 0:
+        raise ValueError(f"kwbd_threshold = {kwbd_threshold!r}: an integer >= 0")
+
+
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
 
@@ -147,18 +158,30 @@ class _Round:
         self.kw_Ch = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), t[8], t[9],
                                   Ch.split.data_ptr(), self.ng)
         self.dual_Ch = _lib.DualBatch(t[6], t[7], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), self.ng)
+        self._side_a = (Ch, self.kw_Ch, self.dual_Ch, t[6], t[7], t[10], t[11])
+
+    def _second_children(self, n_children, in_shape):
+        """A second set of child rows (pair B of the threshold mode) on the same boxes, property rows and
+        workspaces: everything is stream-ordered, so the two pairs never use a workspace at the same time."""
+        ChB = self.ChB = _Rows(self.eng, self.fixed, n_children, in_shape, False)
+        self._keep_b = t = [table(g) for g in (ChB.lb, ChB.ub, ChB.plb, ChB.pub, ChB.dual, ChB.prims)]
+        kw = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), ChB.mask.data_ptr(), t[2], t[3],
+                          ChB.split.data_ptr(), self.ng)
+        dual = _lib.DualBatch(t[0], t[1], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), ChB.mask.data_ptr(), self.ng)
+        self._side_b = (ChB, kw, dual, t[0], t[1], t[4], t[5])
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def _bound_children(self, B, warm):
-        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B child rows."""
-        Ch, lib, h, t = self.Ch, self.lib, self.eng.h, self._keep
+    def _bound_children(self, B, warm, side=None):
+        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B child rows (side: None, or the second set's ``_side_b``)."""
+        lib, h = self.lib, self.eng.h
+        Ch, kw, dual, t_lb, t_ub, t_dual, t_prims = self._side_a if side is None else side
         with torch.cuda.device(self.eng.device):
-            _lib.check(lib.gnnb_kw_bounds(h, C.byref(self.kw_Ch), B, t[6], t[7], None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
+            _lib.check(lib.gnnb_kw_bounds(h, C.byref(kw), B, t_lb, t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
                                           self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
-            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_Ch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
-                                            Ch.bound.data_ptr(), None, None, t[10], t[11], Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
+            _lib.check(lib.gnnb_dual_ascent(h, C.byref(dual), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
+                                            Ch.bound.data_ptr(), None, None, t_dual, t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
         self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=(self.pw, self.pb), workspace=self.ws_eval)
 
@@ -181,10 +204,16 @@ class _Round:
 
 class FrontierRun(_Round):
     """The device side of ``branch_and_bound_frontier``: ``root()`` once, then per round ``launch_round(k)`` (device work only, nothing
-    synchronises) and ``read_state()`` (the round's one device-to-host copy)."""
+    synchronises) and ``read_state()`` (the round's one device-to-host copy).
 
-    def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None):
+    With a ``branching_threshold`` the run also owns a second set of child rows, the table ``ineff`` of
+    inefficient KW points and the intercept counter ``icp``, and a round reads one more number, the count of selected parents
+    (``read_selected``, 4 bytes), between its two halves."""
+
+    def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
+                 kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001):
         self.capacity = _check_args(K, n_iter, lr, eps, 0, capacity)
+        _check_threshold(branching_threshold, kwbd_threshold)
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
@@ -203,6 +232,19 @@ class FrontierRun(_Round):
         self.pb = self.prop_layer.bias.detach().reshape(1).to(dev, torch.float32).expand(n).contiguous()
         self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
         self.slots = None
+        self.threshold, self.m, self.keep_pairs, self.pair_a = branching_threshold, 0, False, None
+        if branching_threshold is not None:
+            f64, f32, i32, R = torch.float64, torch.float32, torch.int32, eng.R
+            self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
+            self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
+            self._second_children(n, in_shape)
+            self.ineff, self.icp = torch.zeros(R, dtype=i32, device=dev), torch.zeros(1, dtype=i32, device=dev)
+            self.kw_scores, self.kw_icp = torch.zeros(K, R, dtype=f32, device=dev), torch.zeros(K, R, dtype=f32, device=dev)
+            self.gnn_imp, self.kw_imp = torch.zeros(K, dtype=f64, device=dev), torch.zeros(K, dtype=f64, device=dev)
+            self.kw_dec, self.sel_dec, self.dec = (torch.zeros(K, 2, dtype=i32, device=dev) for _ in range(3))
+            self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(K, dtype=i32, device=dev) for _ in range(3))
+            self.m_dev, self.n_used = torch.zeros(1, dtype=i32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+            self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_workspace_bytes(eng.h, K)), dtype=torch.uint8, device=dev)
 
     def _commit(self, slots):
         Ch = self.Ch
@@ -237,15 +279,40 @@ class FrontierRun(_Round):
         self._score_parents(k)
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(2 * k, warm=True)
+        if self.threshold is not None:
+            self._fall_back(k)
         self._commit(slots)
 
+    def _fall_back(self, k):
+        """The threshold mode between the bounding of pair A and the commit: BaBSR on the parents' rows, the
+        improvement test and the selection (gnnb_frontier_fallback), the read of m, and for m > 0 pair B and the choice."""
+        P, Ch, ChB, eng, pool, slots = self.P, self.Ch, self.ChB, self.eng, self.pool, self.slots
+        eng.babsr_rows(P.lb32, P.ub32, self.pw, P.amb, k, self.kw_scores, self.kw_icp)
+        eng.frontier_fallback(pool, slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, P.amb, self.icp, self.ineff, self.gnn_imp,
+                              self.kw_dec, self.sel_rows, self.sel_slots, self.sel_dec, self.m_dev, self.threshold, self.kwbd_threshold,
+                              self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+        if self.keep_pairs:                                       # (a traced run: pair A as it was bounded, before the choice overwrites rows)
+            self.pair_a = (Ch.bound[:2 * k].clone(), Ch.infeasible[:2 * k].clone())
+        m = self.m = self.read_selected()
+        if m == 0:
+            return
+        eng.frontier_expand(pool, self.sel_slots[:m], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
+        self._bound_children(2 * m, warm=True, side=self._side_b)
+        eng.frontier_choose(pool, k, m, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff, self.kw_imp,
+                            self.used_kw, self.dec)
+        self.n_used += self.used_kw[:k].sum()
+
+    def read_selected(self):
+        """m, the number of parents whose KW decision gets bounded: the 4 bytes a threshold round reads between its halves."""
+        return int(self.m_dev.cpu()[0])
+
     def read_state(self):
-        """The state record as a list of Python floats: the one device-to-host copy of a round."""
+        """The state record as a list of Python floats: the one device-to-host copy of a round (of its second half, in threshold mode)."""
         return self.pool.state.cpu().tolist()
 
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
-                              trace=None):
+                              trace=None, branching_threshold=None, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001, stats=None):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -259,9 +326,24 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     and global_ub.  trace: None, or a list that receives per round a dict of the picked slots, their bounds, the decisions, the
     children's bounds / upper values / live and infeasible flags (extra device-to-host copies: off in a timed run).
 
+    branching_threshold (None: off, and nothing below applies): the control flow of ``lp_producer.branch_and_bound_threshold`` (reference
+    plnn/relu_conv_gnnkwthreshold.py:151-195) inside a round, DESIGN.md section 7.5.  A parent whose GNN split improves the bound by less
+    than ``branching_threshold`` (0 < . <= 1) asks the BaBSR heuristic (``sparsest_layer``, ``decision_threshold``: ``kw_score_conv.decide``'s);
+    unless that point was inefficient ``kwbd_threshold`` times its two children are bounded too, and the better pair is committed.  The
+    intercept counter and the inefficiency counts are read and updated in parent row order within a round.  A parent whose BaBSR scores
+    hold a NaN, or that has no undecided node, keeps its GNN pair (the host rule would raise).  The trace's "decisions" are then the
+    final ones and it also carries "gnn_decisions", "gnn_improvement", "kw_decisions" ([-1, -1]: not asked), "kw_improvement" (-1: not
+    bounded), "selected" (rows), "used_kw" and both pairs' bounds as they were bounded ("gnn_child_bounds" / "gnn_child_infeasible",
+    "kw_child_bounds" / "kw_child_infeasible", two per selected row).  stats: None, or a dict that receives "branches" (parents
+    expanded), "kw_bounded", "kw_used" and "domains_bounded"; domains_bounded counts the children of both pairs.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     _check_args(K, n_iter, lr, eps, max_rounds, capacity)
-    run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity)
+    _check_threshold(branching_threshold, kwbd_threshold)
+    run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
+                      decision_threshold)
+    run.keep_pairs = trace is not None
+    branches = kw_bounded = 0
     S = _lib
     st = run.root()
     rounds, bounded = 0, 1
@@ -295,15 +377,33 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
             trace.append({"slots": run.slots.cpu().tolist(), "parent_bounds": P.bound[:k].cpu().tolist(), "decisions": P.dec[:k].cpu().tolist(),
                           "child_bounds": Ch.bound[:2 * k].cpu().tolist(), "child_ub": Ch.ubv[:2 * k].cpu().tolist(),
                           "live": Ch.live[:2 * k].cpu().tolist(), "infeasible": Ch.infeasible[:2 * k].cpu().tolist()})
+            if branching_threshold is not None:
+                trace[-1].update(_threshold_trace(run, k))
         st = run.read_state()
         if st[S.FS_OVERFLOW] != 0 or math.isnan(st[S.FS_GLOBAL_UB]):
             raise RuntimeError(f"frontier state record is inconsistent: {st}")
         rounds += 1
-        bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE])
+        bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE]) + 2 * run.m
+        branches, kw_bounded = branches + k, kw_bounded + run.m
         log(f"round {rounds} picked {k} kept {int(st[S.FS_KEPT])} closed {int(st[S.FS_CLOSED])} infeasible {int(st[S.FS_INFEASIBLE])} open {int(st[S.FS_N_OPEN])} "
             f"lb {glb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     run.check_status()
+    if stats is not None:
+        stats.update(branches=branches, kw_bounded=kw_bounded, domains_bounded=bounded,
+                     kw_used=int(run.n_used.cpu()[0]) if branching_threshold is not None else 0)
     return global_lb, global_ub, rounds, bounded, reason
+
+
+def _threshold_trace(run, k):
+    """The threshold mode's part of a round's trace (device-to-host copies).  With m = 0 no choice was launched: every row kept its GNN pair."""
+    P, ChB, m = run.P, run.ChB, run.m
+    gnn_dec = P.dec[:k].cpu().tolist()
+    a_bound, a_inf = run.pair_a
+    return {"gnn_decisions": gnn_dec, "gnn_improvement": run.gnn_imp[:k].cpu().tolist(), "kw_decisions": run.kw_dec[:k].cpu().tolist(),
+            "kw_improvement": run.kw_imp[:k].cpu().tolist() if m else [-1.0] * k, "selected": run.sel_rows[:m].cpu().tolist(),
+            "used_kw": run.used_kw[:k].cpu().tolist() if m else [0] * k, "decisions": run.dec[:k].cpu().tolist() if m else gnn_dec,
+            "gnn_child_bounds": a_bound.cpu().tolist(), "gnn_child_infeasible": a_inf.cpu().tolist(),
+            "kw_child_bounds": ChB.bound[:2 * m].cpu().tolist(), "kw_child_infeasible": ChB.infeasible[:2 * m].cpu().tolist()}
 
 
 # ---- many jobs in one pool (DESIGN.md section 7.4) --------------------------------------------------------------------------------------

@@ -353,6 +353,72 @@ size_t gnnb_frontier_commit_jobs_workspace_bytes(const gnnb_t* h, int n);
 int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_children* children,
                               double eps, const double* decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the BaBSR fall-back below a branching threshold, inside a round ----
+ * The control flow of reference plnn/relu_conv_gnnkwthreshold.py:151-195 for the K parents of a round, between the bounding of the GNN
+ * decisions' children (pair A) and gnnb_frontier_commit: the improvement test (:151, :155), the BaBSR decision rule
+ * (plnn/kw_score_conv.py:115-156, on gnnb_babsr's scores and intercepts of the parent rows), the skip of a point that was inefficient
+ * kwbd_threshold times (:160-167) and, once the selected parents' second pair of children (pair B) is bounded, the choice between the two
+ * pairs (:176-192).  The run's intercept counter and the table of inefficient points are read and updated in parent row order.
+ * Both entry points are stream-ordered, allocate nothing and never synchronise; no atomics, no kernel waits on another workgroup, every
+ * arg-max / arg-min is a fixed tree on the total order (value, index).  GNNB_E_INVALID for a null handle or argument, K < 1 (K > 32767),
+ * m > K, thresholds outside their ranges or a network past the 4096-node cap, GNNB_E_STATE before gnnb_bind_network, GNNB_E_NOMEM for a
+ * short workspace -- all before any launch. */
+typedef struct {
+  const int32_t* live;                /* (2K) pair A: gnnb_frontier_expand on the GNN's decisions                       */
+  const int32_t* infeasible;          /* (2K) gnnb_kw_bounds                                                            */
+  const double* bound;                /* (2K) gnnb_dual_ascent                                                          */
+  const float* scores;                /* (K, R) gnnb_babsr on the parent rows gnnb_frontier_gather wrote                */
+  const float* intercepts;            /* (K, R)                                                                         */
+  const float* scorer_mask;           /* (K, R) gnnb_frontier_gather's: non-zero where the node is undecided            */
+  double branching_threshold;         /* 0 < . <= 1: a parent whose GNN improvement is below it asks BaBSR (:155)       */
+  double decision_threshold;          /* kw_score_conv.py:41 (0.001)                                                    */
+  int32_t kwbd_threshold;             /* >= 0: a node counted inefficient this often is not bounded again (:160)        */
+  int32_t sparsest_layer;
+  const int32_t* random_order;        /* HOST (n_order): ReLU layers, popped from the end (relu_conv_gnnkwthreshold.py:97-103) */
+  int32_t n_order;                    /* 0..8                                                                           */
+  int32_t* icp;                       /* device (1): the intercept counter (icp_score, :119), read and updated          */
+  const int32_t* ineff;               /* device (R): per flat ReLU node how often its KW split was inefficient          */
+} gnnb_fallback;
+
+/* Per parent row i with a live pair A: gnn_improvement[i] = (min(lbA0, 0) + min(lbA1, 0) - 2 bound) / (-2 bound) in fp64 in that order,
+ * an infeasible child counting as +inf, bound the pool's bound of slots[i]; 1.0 when bound >= 0; NaN for a row without a live pair.
+ * Then, walking the rows in order: a row with gnn_improvement < branching_threshold gets kw_decisions[i] = the decision of
+ * kw_score_conv.py:115-156 (fp32 values compared after promotion to double; the first maximum / minimum of a layer; between layers the
+ * maximum of the tuples (value, index)), the counter *icp carried from row to row; every other row, a row whose scores or intercepts hold
+ * a NaN and a row without an undecided node get [-1, -1] and leave the counter alone.  A row with a KW decision whose node's count in
+ * ineff is below kwbd_threshold is SELECTED: sel_rows / sel_slots (K) and sel_decisions (K, 2) receive its row, slot and KW decision,
+ * densely and in row order, *m their number.  All outputs are device arrays; workspace: gnnb_frontier_fallback_workspace_bytes. */
+size_t gnnb_frontier_fallback_workspace_bytes(const gnnb_t* h, int K);
+int gnnb_frontier_fallback(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_fallback* in, double* gnn_improvement,
+                           int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots, int32_t* sel_decisions, int32_t* m,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* gnnb_children whose rows gnnb_frontier_choose overwrites. */
+typedef struct {
+  int8_t* mask;
+  double* const* lb;
+  double* const* ub;
+  int32_t* infeasible;
+  double* bound;
+  double* alpha;
+  double* beta;
+  double* ub_value;
+  int32_t* live;
+  int32_t n_graph;
+} gnnb_children_rw;
+
+/* m (0..K, the host's copy of *m): the selected parents; pair_b: their 2m children, rows 2j and 2j+1 those of sel_rows[j], bounded like
+ * pair A after gnnb_frontier_expand on (sel_slots, sel_decisions).  Per selected parent kw_improvement = the formula above on pair B, then
+ * bab_caller.resolve_branching: kw < gnn and kw < 0.05 adds 1 to ineff[node] (by one thread, in row order: two parents naming one node both
+ * count); kw > gnn copies rows 2j, 2j+1 of pair_b over rows 2 sel_rows[j], + 1 of pair_a (mask, lb / ub of every graph layer, infeasible,
+ * bound, alpha, beta, ub_value, live) and makes the KW decision the row's; otherwise pair A stays.  Writes for every row of K:
+ * kw_improvement (-1.0 unless selected), used_kw (0 / 1) and decisions (K, 2) (gnn_decisions unless the KW pair was taken).  With m = 0
+ * pair_b is not read.  sel_rows must be distinct rows of [0, K). */
+int gnnb_frontier_choose(gnnb_t* h, const gnnb_pool* pool, int K, int m, const int32_t* sel_rows, const int32_t* sel_slots,
+                         const int32_t* sel_decisions, const int32_t* gnn_decisions, const double* gnn_improvement,
+                         const gnnb_children_rw* pair_a, const gnnb_children* pair_b, int32_t* ineff, double* kw_improvement,
+                         int32_t* used_kw, int32_t* decisions, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
