@@ -1702,6 +1702,14 @@ static int fr_pool(const gnnb_t* h, const char* who, const gnnb_pool* pool, FrPo
   return GNNB_OK;
 }
 
+// the pool of many jobs (section 7.4): the plan's segments fill it
+static int fr_plan_pool(const gnnb_t* h, const char* who, const gnnb_plan* plan, const gnnb_pool* pool, FrPool* p) {
+  if (int rc = fr_pool(h, who, pool, p)) return rc;
+  if ((long)plan->segments * plan->seg_cap != pool->capacity)
+    return fail(GNNB_E_INVALID, "%s: %d segments of %d slots in a pool of %d", who, plan->segments, plan->seg_cap, pool->capacity);
+  return GNNB_OK;
+}
+
 extern "C" int gnnb_frontier_gather(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const double* x_lo, const double* x_hi,
                                     int8_t* mask, double* const* lb, double* const* ub, float* const* lb32, float* const* ub32, double* alpha,
                                     double* beta, float* scorer_mask, void* stream) {
@@ -1734,9 +1742,9 @@ extern "C" int gnnb_frontier_expand(gnnb_t* h, const gnnb_pool* pool, const int3
   if (int rc = fr_pool(h, "gnnb_frontier_expand", pool, &a.p)) return rc;
   for (int k = 1; k <= a.s.L + 1; ++k) {
     if (!parent_lb[k - 1] || !parent_ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_frontier_expand: null output pointer for graph layer %d", k);
-    a.plb[k] = parent_lb[k - 1]; a.pub[k] = parent_ub[k - 1];
+    a.ch.lb[k] = parent_lb[k - 1]; a.ch.ub[k] = parent_ub[k - 1];
   }
-  a.slots = slots; a.decisions = decisions; a.K = K; a.mask = mask; a.split = split_layer; a.alpha = alpha; a.beta = beta; a.live = live;
+  a.slots = slots; a.decisions = decisions; a.K = K; a.ch.mask = mask; a.split = split_layer; a.ch.alpha = alpha; a.ch.beta = beta; a.live = live;
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
   run.run(PC_FR_EXPAND, [&] { hipLaunchKernelGGL(k_frontier_expand, dim3(2 * K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
@@ -1782,34 +1790,56 @@ extern "C" size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K) {
   return fr_ws_layout(h, K).total;
 }
 
-extern "C" int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* ch, double eps,
-                                    double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = frontier_preflight(h, "gnnb_frontier_commit", K, pool ? &pool->n_graph : nullptr)) return rc;
-  if (!slots || !ch || !state || !workspace) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null argument");
-  if (ch->n_graph != pool->n_graph) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: the children have %d graph layers, the pool %d", ch->n_graph, pool->n_graph);
+// A gnnb_children / gnnb_children_rw checked against the pool's n_graph, as the kernels' struct of it (lb / ub of graph layer k at [k]).
+template <class Ch, class Rows>
+static int fr_children(const gnnb_t* h, const char* who, const Ch* ch, int n_graph, Rows* r) {
+  if (ch->n_graph != n_graph) return fail(GNNB_E_INVALID, "%s: the children have %d graph layers, the pool %d", who, ch->n_graph, n_graph);
   if (!ch->mask || !ch->lb || !ch->ub || !ch->infeasible || !ch->bound || !ch->alpha || !ch->beta || !ch->ub_value || !ch->live)
-    return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null array among the children's");
-  if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: eps = %g", eps);
-  const FrWs ws = fr_ws_layout(h, K);
-  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_frontier_commit: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
-  FrCommitArgs a{};
-  a.s = fr_shape(h);
-  if (int rc = fr_pool(h, "gnnb_frontier_commit", pool, &a.p)) return rc;
-  for (int k = 1; k <= a.s.L + 1; ++k) {
-    if (!ch->lb[k - 1] || !ch->ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_frontier_commit: null bounds pointer for graph layer %d", k);
-    a.lb[k] = ch->lb[k - 1]; a.ub[k] = ch->ub[k - 1];
+    return fail(GNNB_E_INVALID, "%s: null array among the children's", who);
+  for (int k = 1; k <= h->kw_net.L + 1; ++k) {
+    if (!ch->lb[k - 1] || !ch->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null bounds pointer for graph layer %d", who, k);
+    r->lb[k] = ch->lb[k - 1]; r->ub[k] = ch->ub[k - 1];
   }
-  a.slots = slots; a.K = K; a.mask = ch->mask; a.infeasible = ch->infeasible; a.bound = ch->bound; a.alpha = ch->alpha; a.beta = ch->beta;
-  a.ubv = ch->ub_value; a.live = ch->live; a.eps = eps; a.decision_bound = decision_bound; a.state = state;
+  r->mask = ch->mask; r->alpha = ch->alpha; r->beta = ch->beta;
+  r->infeasible = ch->infeasible; r->bound = ch->bound; r->ubv = ch->ub_value; r->live = ch->live;
+  return GNNB_OK;
+}
+
+// What gnnb_frontier_commit and gnnb_frontier_commit_jobs share once their own preflight is through: the 2n children of the parents in
+// slots[0..n), checked, then resolve, decide (the caller's launch: one workgroup on the pool, or one per plan entry) and store.
+// plan: null, or the plan whose segments the pool must hold.
+template <class Decide>
+static int fr_commit(gnnb_t* h, const char* who, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, int n, const gnnb_children* ch,
+                     double eps, double* state, void* workspace, size_t workspace_bytes, void* stream, Decide decide) {
+  FrCommitArgs a{};
+  if (int rc = fr_children(h, who, ch, pool->n_graph, &a.ch)) return rc;
+  if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "%s: eps = %g", who, eps);
+  const FrWs ws = fr_ws_layout(h, n);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
+  a.s = fr_shape(h);
+  if (int rc = plan ? fr_plan_pool(h, who, plan, pool, &a.p) : fr_pool(h, who, pool, &a.p)) return rc;
+  a.slots = slots; a.K = n; a.eps = eps; a.state = state;
   a.rmask = (int8_t*)workspace;
   a.undecided = (int32_t*)((char*)workspace + ws.undecided);
   a.dest = (int32_t*)((char*)workspace + ws.dest);
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * K), dim3(FR_THREADS), 0, st, a); });
-  run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide, dim3(1), dim3(FR_THREADS), 0, st, a); });
-  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * K, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * n), dim3(FR_THREADS), 0, st, a); });
+  decide(run, st, a);
+  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
+}
+
+extern "C" int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* ch, double eps,
+                                    double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_commit";
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !ch || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  return fr_commit(h, who, pool, nullptr, slots, K, ch, eps, state, workspace, workspace_bytes, stream,
+                   [&](Launcher& run, hipStream_t st, FrCommitArgs& a) {
+                     a.decision_bound = decision_bound;
+                     run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide, dim3(1), dim3(FR_THREADS), 0, st, a); });
+                   });
 }
 
 // ---- many jobs in one pool: a pool of plan->segments segments of plan->seg_cap slots, one record per segment ----
@@ -1834,13 +1864,6 @@ static int fr_plan(const gnnb_t* h, const char* who, const gnnb_plan* plan, cons
   }
   if (row != plan->n) return fail(GNNB_E_INVALID, "%s: the plan's entries hold %ld rows, n = %d", who, row, plan->n);
   j->plan = plan->device; j->n_entries = plan->n_entries; j->n = plan->n; j->S = plan->segments; j->seg_cap = plan->seg_cap;
-  return GNNB_OK;
-}
-
-static int fr_plan_pool(const gnnb_t* h, const char* who, const gnnb_plan* plan, const gnnb_pool* pool, FrPool* p) {
-  if (int rc = fr_pool(h, who, pool, p)) return rc;
-  if ((long)plan->segments * plan->seg_cap != pool->capacity)
-    return fail(GNNB_E_INVALID, "%s: %d segments of %d slots in a pool of %d", who, plan->segments, plan->seg_cap, pool->capacity);
   return GNNB_OK;
 }
 
@@ -1888,30 +1911,10 @@ extern "C" int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const
   FrPlan j{};
   if (int rc = fr_plan(h, who, plan, pool ? &pool->n_graph : nullptr, &j)) return rc;
   if (!slots || !ch || !decision_bound || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
-  if (ch->n_graph != pool->n_graph) return fail(GNNB_E_INVALID, "%s: the children have %d graph layers, the pool %d", who, ch->n_graph, pool->n_graph);
-  if (!ch->mask || !ch->lb || !ch->ub || !ch->infeasible || !ch->bound || !ch->alpha || !ch->beta || !ch->ub_value || !ch->live)
-    return fail(GNNB_E_INVALID, "%s: null array among the children's", who);
-  if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "%s: eps = %g", who, eps);
-  const FrWs ws = fr_ws_layout(h, j.n);
-  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
-  FrCommitArgs a{};
-  a.s = fr_shape(h);
-  if (int rc = fr_plan_pool(h, who, plan, pool, &a.p)) return rc;
-  for (int k = 1; k <= a.s.L + 1; ++k) {
-    if (!ch->lb[k - 1] || !ch->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null bounds pointer for graph layer %d", who, k);
-    a.lb[k] = ch->lb[k - 1]; a.ub[k] = ch->ub[k - 1];
-  }
-  a.slots = slots; a.K = j.n; a.mask = ch->mask; a.infeasible = ch->infeasible; a.bound = ch->bound; a.alpha = ch->alpha; a.beta = ch->beta;
-  a.ubv = ch->ub_value; a.live = ch->live; a.eps = eps; a.decision_bound = 0.0; a.state = state;
-  a.rmask = (int8_t*)workspace;
-  a.undecided = (int32_t*)((char*)workspace + ws.undecided);
-  a.dest = (int32_t*)((char*)workspace + ws.dest);
-  hipStream_t st = (hipStream_t)stream;
-  Launcher run{h, st};
-  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * j.n), dim3(FR_THREADS), 0, st, a); });
-  run.run(PC_FR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_decide_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, decision_bound); });
-  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * j.n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
-  return run.rc;
+  return fr_commit(h, who, pool, plan, slots, j.n, ch, eps, state, workspace, workspace_bytes, stream,
+                   [&](Launcher& run, hipStream_t st, FrCommitArgs& a) {
+                     run.run(PC_FR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_decide_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, decision_bound); });
+                   });
 }
 
 // ---- the BaBSR fall-back below a branching threshold (reference plnn/relu_conv_gnnkwthreshold.py:151-195, the
@@ -1969,21 +1972,8 @@ extern "C" int gnnb_frontier_choose(gnnb_t* h, const gnnb_pool* pool, int K, int
   a.s = fr_shape(h);
   if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
   if (m > 0) {
-    if (pa->n_graph != pool->n_graph || pb->n_graph != pool->n_graph)
-      return fail(GNNB_E_INVALID, "%s: the children have %d / %d graph layers, the pool %d", who, pa->n_graph, pb->n_graph, pool->n_graph);
-    if (!pa->mask || !pa->lb || !pa->ub || !pa->infeasible || !pa->bound || !pa->alpha || !pa->beta || !pa->ub_value || !pa->live ||
-        !pb->mask || !pb->lb || !pb->ub || !pb->infeasible || !pb->bound || !pb->alpha || !pb->beta || !pb->ub_value || !pb->live)
-      return fail(GNNB_E_INVALID, "%s: null array among the children's", who);
-    for (int k = 1; k <= a.s.L + 1; ++k) {
-      if (!pa->lb[k - 1] || !pa->ub[k - 1] || !pb->lb[k - 1] || !pb->ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null bounds pointer for graph layer %d", who, k);
-      a.A.lb[k] = pa->lb[k - 1]; a.A.ub[k] = pa->ub[k - 1];
-      a.B.lb[k] = const_cast<double*>(pb->lb[k - 1]); a.B.ub[k] = const_cast<double*>(pb->ub[k - 1]);     // (B is only read)
-    }
-    a.A.mask = pa->mask; a.A.infeasible = pa->infeasible; a.A.bound = pa->bound; a.A.alpha = pa->alpha; a.A.beta = pa->beta; a.A.ubv = pa->ub_value;
-    a.A.live = pa->live;
-    a.B.mask = const_cast<int8_t*>(pb->mask); a.B.infeasible = const_cast<int32_t*>(pb->infeasible); a.B.bound = const_cast<double*>(pb->bound);
-    a.B.alpha = const_cast<double*>(pb->alpha); a.B.beta = const_cast<double*>(pb->beta); a.B.ubv = const_cast<double*>(pb->ub_value);
-    a.B.live = const_cast<int32_t*>(pb->live);
+    if (int rc = fr_children(h, who, pa, pool->n_graph, &a.A)) return rc;
+    if (int rc = fr_children(h, who, pb, pool->n_graph, &a.B)) return rc;
   }
   a.K = K; a.m = m; a.sel_rows = sel_rows; a.sel_slots = sel_slots; a.sel_dec = sel_decisions; a.gnn_dec = gnn_decisions; a.gnn_imp = gnn_improvement;
   a.ineff = ineff; a.kw_imp = kw_improvement; a.used = used_kw; a.dec = decisions;

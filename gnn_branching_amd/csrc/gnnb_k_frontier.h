@@ -22,6 +22,10 @@
 //                         the view of the whole pool; k_frontier_decide_jobs at the end of this file runs it per job on a segment).
 //   * k_frontier_store    kept children -> their pool slots.
 //
+// The arrays of a set of domains -- the pool's slots, a round's child rows -- are one struct, FrDomainsT (FrChildrenT adds what a bounded
+// child has: infeasible, bound, ubv, live; FrPool what a slot has: bound, open), writable or read-only by its parameter, and fr_copy_row
+// is the one copy of a row between two sets: k_frontier_expand, k_frontier_store and k_frontier_choose_copy call it.
+//
 // A kept child of rank r (its number among the kept ones, in child order) goes to the r-th parent slot in the order of `slots`; from
 // rank K on to slot in_use + (r - K), in_use the state record's count before the call.  No atomics, no workgroup waits on another;
 // minima and counts are per-thread partials in a fixed order, then a fixed tree: nothing depends on K or on a row's place.
@@ -38,9 +42,24 @@ struct FrShape {                // the sizes the copy kernels need of the bound 
   int L, R;
 };
 
-struct FrPool {
-  int8_t* mask; double* lb[MAXL + 2]; double* ub[MAXL + 2];     // lb / ub: graph layers 1..L+1
-  double* alpha; double* beta; double* bound; int32_t* open;
+// The arrays of a set of domains, one row per domain -- the pool's slots, a round's child rows -- and what child rows add to them.  Q makes
+// the element types: FrRW for a set a kernel writes, FrRO for one it only reads.
+template <class T> using FrRW = T;
+template <class T> using FrRO = const T;
+
+template <template <class> class Q> struct FrDomainsT {
+  Q<int8_t>* mask; Q<double>* lb[MAXL + 2]; Q<double>* ub[MAXL + 2];     // lb / ub: graph layers 1..L+1
+  Q<double>* alpha; Q<double>* beta;
+};
+template <template <class> class Q> struct FrChildrenT : FrDomainsT<Q> {  // gnnb_children / gnnb_children_rw
+  Q<int32_t>* infeasible; Q<double>* bound; Q<double>* ubv; Q<int32_t>* live;
+};
+using FrDomains = FrDomainsT<FrRW>;
+using FrChildren = FrChildrenT<FrRW>;
+using FrChildrenRO = FrChildrenT<FrRO>;
+
+struct FrPool : FrDomains {
+  double* bound; int32_t* open;
   int cap;
 };
 
@@ -56,15 +75,14 @@ struct FrGatherArgs {
 struct FrExpandArgs {
   FrShape s; FrPool p;
   const int32_t* slots; const int32_t* decisions; int K;
-  int8_t* mask; double* plb[MAXL + 2]; double* pub[MAXL + 2];
-  int32_t* split; double* alpha; double* beta; int32_t* live;
+  FrDomains ch;                                         // the 2K children; lb / ub: gnnb_kw_bounds' parent tables
+  int32_t* split; int32_t* live;
 };
 
 struct FrCommitArgs {
   FrShape s; FrPool p;
   const int32_t* slots; int K;
-  const int8_t* mask; const double* lb[MAXL + 2]; const double* ub[MAXL + 2];    // the 2K children
-  const int32_t* infeasible; const double* bound; const double* alpha; const double* beta; const double* ubv; const int32_t* live;
+  FrChildrenRO ch;                                      // the 2K children
   double eps, decision_bound;
   double* state;
   int8_t* rmask; int32_t* undecided; int32_t* dest;     // workspace: (2K, R), (2K), (2K)
@@ -72,6 +90,26 @@ struct FrCommitArgs {
 static_assert(sizeof(FrGatherArgs) <= 4096 && sizeof(FrExpandArgs) <= 4096 && sizeof(FrCommitArgs) <= 4096, "kernel arguments: 4 KiB");
 
 __device__ __forceinline__ bool fr_slot_ok(const FrPool& p, int s) { return s >= 0 && s < p.cap; }
+
+// Row c of `src` to row d of `dst`: mask / alpha / beta over the R ReLU nodes, lb / ub of graph layers 1..L+1, the row spread over the
+// FR_SPLIT workgroups of blockIdx.y.  mask: the source of the mask's row (src.mask, or the resolved masks of a commit).
+template <template <class> class Q>
+__device__ __forceinline__ void fr_copy_row(const FrShape& s, const FrDomains& dst, long d, const FrDomainsT<Q>& src, const int8_t* mask, long c) {
+  const int t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int R = s.R, K1 = s.L + 1;
+  for (int r = t0; r < R; r += dt) {
+    dst.mask[d * R + r] = mask[c * R + r];
+    dst.alpha[d * R + r] = src.alpha[c * R + r];
+    dst.beta[d * R + r] = src.beta[c * R + r];
+  }
+  for (int k = 1; k <= K1; ++k) {
+    const int Nk = s.N[k];
+    for (int j = t0; j < Nk; j += dt) {
+      dst.lb[k][d * Nk + j] = src.lb[k][c * Nk + j];
+      dst.ub[k][d * Nk + j] = src.ub[k][c * Nk + j];
+    }
+  }
+}
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_gather(FrGatherArgs a) {
   const int i = blockIdx.x, t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
@@ -108,22 +146,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_expand(FrExpandArgs a) 
     if (t0 == 0) { a.live[c] = 0; a.split[c] = -1; }
     return;
   }
-  const int R = a.s.R, K1 = a.s.L + 1;
   const int lay = a.decisions[2 * i], idx = a.decisions[2 * i + 1];
   const bool live = lay >= 0 && lay < a.s.L && idx >= 0 && idx < a.s.N[lay + 1];
   const int node = live ? a.s.off[lay + 1] + idx : -1;
-  for (int r = t0; r < R; r += dt) {
-    a.mask[(long)c * R + r] = r == node ? (int8_t)choice : a.p.mask[(long)s * R + r];
-    a.alpha[(long)c * R + r] = a.p.alpha[(long)s * R + r];
-    a.beta[(long)c * R + r] = a.p.beta[(long)s * R + r];
-  }
-  for (int k = 1; k <= K1; ++k) {
-    const int Nk = a.s.N[k];
-    for (int j = t0; j < Nk; j += dt) {
-      a.plb[k][(long)c * Nk + j] = a.p.lb[k][(long)s * Nk + j];
-      a.pub[k][(long)c * Nk + j] = a.p.ub[k][(long)s * Nk + j];
-    }
-  }
+  fr_copy_row(a.s, a.ch, c, a.p, a.p.mask, s);
+  if (live && node % dt == t0) a.ch.mask[(long)c * a.s.R + node] = (int8_t)choice;      // by the thread that copied the entry: no second pass
   if (t0 == 0) {
     a.live[c] = live ? 1 : 0;
     a.split[c] = live ? lay : a.s.L - 1;                // a dead row keeps every bound of its parent
@@ -179,14 +206,14 @@ __global__ __launch_bounds__(FR_THREADS) void k_net_eval(NetEvalArgs a) {
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_resolve(FrCommitArgs a) {
   const int c = blockIdx.x, tid = threadIdx.x, R = a.s.R;
   int open = 0;
-  if (a.live[c]) {                                      // (a dead row's arrays are never read)
+  if (a.ch.live[c]) {                                   // (a dead row's arrays are never read)
     for (int k = 1; k <= a.s.L; ++k) {
       const int Nk = a.s.N[k];
       for (int j = tid; j < Nk; j += FR_THREADS) {
         const long r = (long)c * R + a.s.off[k] + j;
-        int m = a.mask[r];
-        if (m == -1 && a.lb[k][(long)c * Nk + j] >= 0.0) m = 1;
-        if (m == -1 && a.ub[k][(long)c * Nk + j] <= 0.0) m = 0;
+        int m = a.ch.mask[r];
+        if (m == -1 && a.ch.lb[k][(long)c * Nk + j] >= 0.0) m = 1;
+        if (m == -1 && a.ch.ub[k][(long)c * Nk + j] <= 0.0) m = 0;
         a.rmask[r] = (int8_t)m;
         open |= m == -1;
       }
@@ -232,7 +259,7 @@ __device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v
   // 2. the incumbent: every live feasible child's network value at its LP point
   double val = inf;
   for (int c = tid; c < n; c += FR_THREADS)
-    if (a.live[ch0 + c] && !a.infeasible[ch0 + c]) val = fmin(val, a.ubv[ch0 + c]);
+    if (a.ch.live[ch0 + c] && !a.ch.infeasible[ch0 + c]) val = fmin(val, a.ch.ubv[ch0 + c]);
   const double gub = fmin(v.state[FS_GLOBAL_UB], fr_block_min(red, val, tid));
   // 3. - 5. keep or close (each thread a contiguous run of children, so that ranks follow child order)
   const int per = (n + FR_THREADS - 1) / FR_THREADS, c0 = min(tid * per, n), c1 = min(c0 + per, n);
@@ -240,15 +267,15 @@ __device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v
   double closed = inf;
   int kept = 0, n_closed = 0, n_inf = 0;
   for (int c = c0; c < c1; ++c) {
-    if (!a.live[ch0 + c]) continue;
-    if (a.infeasible[ch0 + c]) { ++n_inf; continue; }
-    const double lb = a.bound[ch0 + c];
+    if (!a.ch.live[ch0 + c]) continue;
+    if (a.ch.infeasible[ch0 + c]) { ++n_inf; continue; }
+    const double lb = a.ch.bound[ch0 + c];
     if (a.undecided[ch0 + c] && lb < gub - a.eps && (!have_db || lb < v.decision_bound)) ++kept;
     else { closed = fmin(closed, lb); ++n_closed; }
   }
   for (int i = tid; i < K; i += FR_THREADS) {           // a parent without a live child (decision [-1, -1]) is closed at its own bound
     const int s = slots[i];
-    if (fr_view_ok(v, s) && !a.live[ch0 + 2 * i] && !a.live[ch0 + 2 * i + 1]) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
+    if (fr_view_ok(v, s) && !a.ch.live[ch0 + 2 * i] && !a.ch.live[ch0 + 2 * i + 1]) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
   }
   // 6. the parents leave the pool
   for (int i = tid; i < K; i += FR_THREADS)
@@ -264,8 +291,8 @@ __device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v
   const int total_kept = cnt[FR_THREADS];
   for (int c = c0; c < c1; ++c) {
     int d = -1;
-    if (a.live[ch0 + c] && !a.infeasible[ch0 + c]) {
-      const double lb = a.bound[ch0 + c];
+    if (a.ch.live[ch0 + c] && !a.ch.infeasible[ch0 + c]) {
+      const double lb = a.ch.bound[ch0 + c];
       if (a.undecided[ch0 + c] && lb < gub - a.eps && (!have_db || lb < v.decision_bound)) {
         d = rank < K ? slots[rank] : v.base + in_use + (rank - K);
         ++rank;
@@ -286,7 +313,7 @@ __device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v
   for (int s = tid; s < in_use; s += FR_THREADS)
     if (a.p.open[v.base + s]) { low = fmin(low, a.p.bound[v.base + s]); ++n_open; }
   for (int c = c0; c < c1; ++c)
-    if (a.dest[ch0 + c] >= 0) { low = fmin(low, a.bound[ch0 + c]); ++n_open; }
+    if (a.dest[ch0 + c] >= 0) { low = fmin(low, a.ch.bound[ch0 + c]); ++n_open; }
   low = fr_block_min(red, low, tid);
   closed = fmin(v.state[FS_CLOSED_LB], fr_block_min(red, closed, tid));
   double sums[4] = {(double)n_open, (double)n_closed, (double)n_inf, (double)dropped};
@@ -317,24 +344,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) 
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_store(FrCommitArgs a) {
-  const int c = blockIdx.x, t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
-  const int d = a.dest[c];
+  const int c = blockIdx.x, d = a.dest[c];
   if (d < 0) return;
-  const int R = a.s.R, K1 = a.s.L + 1;
-  for (int r = t0; r < R; r += dt) {
-    a.p.mask[(long)d * R + r] = a.rmask[(long)c * R + r];
-    a.p.alpha[(long)d * R + r] = a.alpha[(long)c * R + r];
-    a.p.beta[(long)d * R + r] = a.beta[(long)c * R + r];
-  }
-  for (int k = 1; k <= K1; ++k) {
-    const int Nk = a.s.N[k];
-    for (int j = t0; j < Nk; j += dt) {
-      a.p.lb[k][(long)d * Nk + j] = a.lb[k][(long)c * Nk + j];
-      a.p.ub[k][(long)d * Nk + j] = a.ub[k][(long)c * Nk + j];
-    }
-  }
-  if (t0 == 0) {
-    a.p.bound[d] = a.bound[c];
+  fr_copy_row(a.s, a.p, d, a.ch, a.rmask, c);
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
+    a.p.bound[d] = a.ch.bound[c];
     a.p.open[d] = 1;
   }
 }
@@ -479,16 +493,11 @@ struct FrFallbackArgs {
   int32_t* cand;                                                                // workspace (K, FC_COUNT)
 };
 
-struct FrRowsRW {               // child rows (gnnb_children / gnnb_children_rw); lb / ub: graph layers 1..L+1
-  int8_t* mask; double* lb[MAXL + 2]; double* ub[MAXL + 2];
-  int32_t* infeasible; double* bound; double* alpha; double* beta; double* ubv; int32_t* live;
-};
-
 struct FrChooseArgs {
   FrShape s; FrPool p;
   int K, m;
   const int32_t* sel_rows; const int32_t* sel_slots; const int32_t* sel_dec; const int32_t* gnn_dec; const double* gnn_imp;
-  FrRowsRW A, B;                                                                // B is only read
+  FrChildren A; FrChildrenRO B;
   int32_t* ineff; double* kw_imp; int32_t* used; int32_t* dec;
 };
 static_assert(sizeof(FrFallbackArgs) <= 4096 && sizeof(FrChooseArgs) <= 4096, "kernel arguments: 4 KiB");
@@ -661,24 +670,12 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose(FrChooseArgs a) 
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_copy(FrChooseArgs a) {
-  const int c = blockIdx.x, q = c >> 1, t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int c = blockIdx.x, q = c >> 1;
   const int row = a.sel_rows[q];
   if (row < 0 || row >= a.K || !a.used[row]) return;
   const long d = 2L * row + (c & 1);
-  const int R = a.s.R, K1 = a.s.L + 1;
-  for (int r = t0; r < R; r += dt) {
-    a.A.mask[d * R + r] = a.B.mask[(long)c * R + r];
-    a.A.alpha[d * R + r] = a.B.alpha[(long)c * R + r];
-    a.A.beta[d * R + r] = a.B.beta[(long)c * R + r];
-  }
-  for (int k = 1; k <= K1; ++k) {
-    const int Nk = a.s.N[k];
-    for (int j = t0; j < Nk; j += dt) {
-      a.A.lb[k][d * Nk + j] = a.B.lb[k][(long)c * Nk + j];
-      a.A.ub[k][d * Nk + j] = a.B.ub[k][(long)c * Nk + j];
-    }
-  }
-  if (t0 == 0) {
+  fr_copy_row(a.s, a.A, d, a.B, a.B.mask, c);
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
     a.A.infeasible[d] = a.B.infeasible[c]; a.A.bound[d] = a.B.bound[c]; a.A.ubv[d] = a.B.ubv[c]; a.A.live[d] = a.B.live[c];
   }
 }

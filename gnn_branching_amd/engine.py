@@ -4,6 +4,7 @@
 network and a workspace per batch size.  Tensors are only carriers of device
 memory here (``data_ptr()``); all arithmetic of the hot path runs in libgnnb.so.
 """
+import collections
 import ctypes as C
 import time
 
@@ -113,6 +114,10 @@ def _raise_for_status(st):
         msg = "mu contains nan"
         print(f"[gnn_branching_amd] {msg}", flush=True)
         raise FloatingPointError(msg)
+
+
+# a set of child rows given as loose tensors (ScorerEngine.frontier_commit / frontier_commit_jobs)
+_ChildRows = collections.namedtuple("_ChildRows", "mask lb ub infeasible bound alpha beta ubv live")
 
 
 class ForwardResult:
@@ -491,6 +496,12 @@ class ScorerEngine:
         self._ws.clear()
 
     # ---- one forward ------------------------------------------------------------------------
+    def _call(self, name, *args):
+        """Entry point ``name`` of the library with the handle in front of ``args`` and the current stream behind them; a failure raises."""
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(self.h, *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, name)
+
     def _dev(self, t):
         if not torch.is_tensor(t):
             t = torch.tensor(t, dtype=torch.float32)       # python lists of LP primals (graph_score.py:30)
@@ -589,10 +600,7 @@ class ScorerEngine:
         batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(),
                            len(lbs), len(duals), len(prim))
         ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_forward(self.h, C.byref(batch), B, scores.data_ptr(), dec.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_forward")
+        self._call("gnnb_forward", C.byref(batch), B, scores.data_ptr(), dec.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
         return ForwardResult(scores, dec, status, mask2)
 
     # ---- the reference's own call pattern: host tensors, one or two subproblems ---------------------------------
@@ -773,10 +781,7 @@ class ScorerEngine:
         icp = torch.empty(B, self.R, dtype=torch.float32, device=self.device)
         tl = (C.c_void_p * ng)(*[t.data_ptr() for t in lbs])
         tu = (C.c_void_p * ng)(*[t.data_ptr() for t in ubs])
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_babsr(self.h, tl, tu, ng, pw.data_ptr(), mask.data_ptr(), B, scores.data_ptr(),
-                                     icp.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_babsr")
+        self._call("gnnb_babsr", tl, tu, ng, pw.data_ptr(), mask.data_ptr(), B, scores.data_ptr(), icp.data_ptr())
         return BabsrResult(scores, icp, mask.view(B, self.R), self.sizes[1:-1])
 
     # ---- Wong-Kolter intermediate bounds (lp_producer.LayerGraphLP.kw_bounds for a batch) ------------------------------------
@@ -821,10 +826,7 @@ class ScorerEngine:
         infeasible = torch.empty(B, dtype=torch.int32, device=dev)
         ws = self.kw_workspace(B)
         kb = _lib.KwBatch(xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), table(plb), table(pub), ptr(split), ng)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_kw_bounds(self.h, C.byref(kb), B, table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_kw_bounds")
+        self._call("gnnb_kw_bounds", C.byref(kb), B, table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(), ws.data_ptr(), ws.numel())
         return KwBoundsResult(lb, ub, lb32, ub32, infeasible)
 
     # ---- dual ascent on the subproblem LPs (lp_producer.LayerGraphLP.dual_ascent_host for a batch) --------------------------------
@@ -868,11 +870,8 @@ class ScorerEngine:
             raise ValueError("lb32_prop must be a contiguous device fp32 tensor of B values")
         ws = self.dual_workspace(B) if workspace is None else workspace
         db = _lib.DualBatch(table(lbs), table(ubs), xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), ng)
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_dual_ascent(self.h, C.byref(db), B, int(n_iter), float(lr), al.data_ptr(), be.data_ptr(), int(warm),
-                                           bound.data_ptr(), ptr(ga), ptr(gb), table(duals), table(prims), ptr(x_lp), ptr(lb32_prop),
-                                           ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_dual_ascent")
+        self._call("gnnb_dual_ascent", C.byref(db), B, int(n_iter), float(lr), al.data_ptr(), be.data_ptr(), int(warm), bound.data_ptr(), ptr(ga),
+                   ptr(gb), table(duals), table(prims), ptr(x_lp), ptr(lb32_prop), ws.data_ptr(), ws.numel())
         return DualAscentResult(bound, al, be, ga, gb, duals, prims, x_lp)
 
     # ---- the real network at a batch of points, fp64 (the BaB loop's upper bound at the LP's input point) ---------------------------
@@ -887,10 +886,7 @@ class ScorerEngine:
         pw, pb = self._rows(pw, B, self.sizes[-2], torch.float32, "property weights"), self._rows(pb, B, 1, torch.float32, "property biases")
         out = torch.empty(B, dtype=torch.float64, device=self.device) if out is None else self._rows(out, B, 1, torch.float64, "out")
         ws = self._workspace("net_eval", B, "gnnb_net_eval_workspace_bytes") if workspace is None else workspace
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_net_eval(self.h, x.data_ptr(), pw.data_ptr(), pb.data_ptr(), B, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_net_eval")
+        self._call("gnnb_net_eval", x.data_ptr(), pw.data_ptr(), pb.data_ptr(), B, out.data_ptr(), ws.data_ptr(), ws.numel())
         return out.reshape(-1)[:B]
 
     # ---- a BaB frontier in device memory (frontier.py runs the loop; include/gnnb.h gnnb_frontier_*) ---------------------------------
@@ -932,9 +928,7 @@ class ScorerEngine:
                 self._layer_rows(lb32, K, 0, torch.float32, "lb32"), self._layer_rows(ub32, K, 0, torch.float32, "ub32"),
                 self._rows(alpha, K, R, torch.float64, "alpha").data_ptr(), self._rows(beta, K, R, torch.float64, "beta").data_ptr(),
                 self._rows(scorer_mask, K, R, torch.float32, "scorer_mask").data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_gather(self.h, C.byref(st), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_gather")
+        self._call("gnnb_frontier_gather", C.byref(st), *args)
 
     def frontier_expand(self, pool, slots, decisions, mask, parent_lb, parent_ub, split_layer, alpha, beta, live):
         """gnnb_frontier_expand on the current stream: the 2K children of the parents in ``slots`` split at ``decisions`` ((K, 2) int32,
@@ -949,9 +943,7 @@ class ScorerEngine:
                 self._rows(split_layer, 2 * K, 1, torch.int32, "split_layer").data_ptr(),
                 self._rows(alpha, 2 * K, R, torch.float64, "alpha").data_ptr(), self._rows(beta, 2 * K, R, torch.float64, "beta").data_ptr(),
                 self._rows(live, 2 * K, 1, torch.int32, "live").data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_expand(self.h, C.byref(st), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_expand")
+        self._call("gnnb_frontier_expand", C.byref(st), *args)
 
     def frontier_commit(self, pool, slots, mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live, state, eps=1e-4, decision_bound=None,
                         workspace=None):
@@ -960,33 +952,20 @@ class ScorerEngine:
         ``frontier_expand`` wrote; lb / ub / infeasible: ``kw_bounds``'; bound / alpha / beta: ``dual_ascent``'s; ub_value: ``net_eval``'s."""
         K = int(slots.numel())
         st, keep = self._pool(pool)
-        R, n = self.R, 2 * K
-        tl, tu = self._layer_rows(lb, n, 1, torch.float64, "lb"), self._layer_rows(ub, n, 1, torch.float64, "ub")
-        ch = _lib.Children(self._rows(mask, n, R, torch.int8, "mask").data_ptr(), tl, tu,
-                           self._rows(infeasible, n, 1, torch.int32, "infeasible").data_ptr(),
-                           self._rows(bound, n, 1, torch.float64, "bound").data_ptr(), self._rows(alpha, n, R, torch.float64, "alpha").data_ptr(),
-                           self._rows(beta, n, R, torch.float64, "beta").data_ptr(), self._rows(ub_value, n, 1, torch.float64, "ub_value").data_ptr(),
-                           self._rows(live, n, 1, torch.int32, "live").data_ptr(), len(self.sizes))
+        ch, keep_ch = self._children(_ChildRows(mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live), 2 * K)
         self._rows(state, _lib.FRONTIER_STATE_DOUBLES, 1, torch.float64, "state")
         ws = self._workspace("commit", K, "gnnb_frontier_commit_workspace_bytes") if workspace is None else workspace
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_commit(self.h, C.byref(st), self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, C.byref(ch),
-                                               float(eps), float("nan") if decision_bound is None else float(decision_bound), state.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_commit")
+        self._call("gnnb_frontier_commit", C.byref(st), self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, C.byref(ch), float(eps),
+                   float("nan") if decision_bound is None else float(decision_bound), state.data_ptr(), ws.data_ptr(), ws.numel())
 
     def babsr_rows(self, lb32, ub32, prop_w, scorer_mask, B, scores, intercepts):
         """gnnb_babsr on the current stream over the first B of the parent rows ``frontier_gather`` wrote (lb32 / ub32: graph layers
         0..L+1 fp32; prop_w (B, N_L) fp32; scorer_mask (B, R) fp32) into scores / intercepts (B, R) fp32.  Nothing is copied."""
         R = self.R
         tl, tu = self._layer_rows(lb32, B, 0, torch.float32, "lb32"), self._layer_rows(ub32, B, 0, torch.float32, "ub32")
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_babsr(self.h, tl, tu, len(self.sizes), self._rows(prop_w, B, self.sizes[-2], torch.float32, "prop_w").data_ptr(),
-                                     self._rows(scorer_mask, B, R, torch.float32, "scorer_mask").data_ptr(), B,
-                                     self._rows(scores, B, R, torch.float32, "scores").data_ptr(),
-                                     self._rows(intercepts, B, R, torch.float32, "intercepts").data_ptr(),
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_babsr")
+        self._call("gnnb_babsr", tl, tu, len(self.sizes), self._rows(prop_w, B, self.sizes[-2], torch.float32, "prop_w").data_ptr(),
+                   self._rows(scorer_mask, B, R, torch.float32, "scorer_mask").data_ptr(), B,
+                   self._rows(scores, B, R, torch.float32, "scores").data_ptr(), self._rows(intercepts, B, R, torch.float32, "intercepts").data_ptr())
 
     def frontier_fallback(self, pool, slots, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, gnn_improvement, kw_decisions,
                           sel_rows, sel_slots, sel_decisions, m, branching_threshold, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001,
@@ -1011,27 +990,24 @@ class ScorerEngine:
                            int(kwbd_threshold), int(sparsest_layer), order_c, len(order), self._rows(icp, 1, 1, i32, "icp").data_ptr(),
                            self._rows(ineff, R, 1, i32, "ineff").data_ptr())
         ws = self._workspace("fallback", K, "gnnb_frontier_fallback_workspace_bytes") if workspace is None else workspace
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_fallback(self.h, C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K, C.byref(fb),
-                                                 self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(),
-                                                 self._rows(kw_decisions, K, 2, i32, "kw_decisions").data_ptr(),
-                                                 self._rows(sel_rows, K, 1, i32, "sel_rows").data_ptr(), self._rows(sel_slots, K, 1, i32, "sel_slots").data_ptr(),
-                                                 self._rows(sel_decisions, K, 2, i32, "sel_decisions").data_ptr(), self._rows(m, 1, 1, i32, "m").data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_fallback")
+        self._call("gnnb_frontier_fallback", C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K, C.byref(fb),
+                   self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(),
+                   self._rows(kw_decisions, K, 2, i32, "kw_decisions").data_ptr(), self._rows(sel_rows, K, 1, i32, "sel_rows").data_ptr(),
+                   self._rows(sel_slots, K, 1, i32, "sel_slots").data_ptr(), self._rows(sel_decisions, K, 2, i32, "sel_decisions").data_ptr(),
+                   self._rows(m, 1, 1, i32, "m").data_ptr(), ws.data_ptr(), ws.numel())
 
-    def _children(self, ch, n, what):
+    def _children(self, ch, n, what=None):
         """The gnnb_children of a set of child rows (any object with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live) and what must
-        outlive the call."""
-        R = self.R
-        tl, tu = self._layer_rows(ch.lb, n, 1, torch.float64, what + ".lb"), self._layer_rows(ch.ub, n, 1, torch.float64, what + ".ub")
-        st = _lib.Children(self._rows(ch.mask, n, R, torch.int8, what + ".mask").data_ptr(), tl, tu,
-                           self._rows(ch.infeasible, n, 1, torch.int32, what + ".infeasible").data_ptr(),
-                           self._rows(ch.bound, n, 1, torch.float64, what + ".bound").data_ptr(),
-                           self._rows(ch.alpha, n, R, torch.float64, what + ".alpha").data_ptr(), self._rows(ch.beta, n, R, torch.float64, what + ".beta").data_ptr(),
-                           self._rows(ch.ubv, n, 1, torch.float64, what + ".ubv").data_ptr(), self._rows(ch.live, n, 1, torch.int32, what + ".live").data_ptr(),
-                           len(self.sizes))
-        return st, (tl, tu)
+        outlive the call.  what: the rows' name in a message (None: loose tensors, named as ``frontier_commit`` takes them)."""
+        R, f64, i32 = self.R, torch.float64, torch.int32
+
+        def name(a):
+            return f"{what}.{a}" if what else {"ubv": "ub_value"}.get(a, a)
+        tl, tu = self._layer_rows(ch.lb, n, 1, f64, name("lb")), self._layer_rows(ch.ub, n, 1, f64, name("ub"))
+        ptrs = [self._rows(getattr(ch, a), n, cols, dtype, name(a)).data_ptr()
+                for a, cols, dtype in (("mask", R, torch.int8), ("infeasible", 1, i32), ("bound", 1, f64), ("alpha", R, f64), ("beta", R, f64),
+                                       ("ubv", 1, f64), ("live", 1, i32))]
+        return _lib.Children(ptrs[0], tl, tu, *ptrs[1:], len(self.sizes)), (tl, tu)
 
     def frontier_choose(self, pool, K, m, sel_rows, sel_slots, sel_decisions, gnn_decisions, gnn_improvement, pair_a, pair_b, ineff, kw_improvement,
                         used_kw, decisions):
@@ -1044,17 +1020,14 @@ class ScorerEngine:
         i32 = torch.int32
         pa, keep_a = self._children(pair_a, 2 * K, "pair_a")
         pb, keep_b = self._children(pair_b, 2 * max(m, 1), "pair_b")
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_choose(self.h, C.byref(st), K, m, self._rows(sel_rows, max(m, 1), 1, i32, "sel_rows").data_ptr(),
-                                               self._rows(sel_slots, max(m, 1), 1, i32, "sel_slots").data_ptr(),
-                                               self._rows(sel_decisions, max(m, 1), 2, i32, "sel_decisions").data_ptr(),
-                                               self._rows(gnn_decisions, K, 2, i32, "gnn_decisions").data_ptr(),
-                                               self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(), C.byref(pa), C.byref(pb),
-                                               self._rows(ineff, self.R, 1, i32, "ineff").data_ptr(),
-                                               self._rows(kw_improvement, K, 1, torch.float64, "kw_improvement").data_ptr(),
-                                               self._rows(used_kw, K, 1, i32, "used_kw").data_ptr(), self._rows(decisions, K, 2, i32, "decisions").data_ptr(),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_choose")
+        self._call("gnnb_frontier_choose", C.byref(st), K, m, self._rows(sel_rows, max(m, 1), 1, i32, "sel_rows").data_ptr(),
+                   self._rows(sel_slots, max(m, 1), 1, i32, "sel_slots").data_ptr(),
+                   self._rows(sel_decisions, max(m, 1), 2, i32, "sel_decisions").data_ptr(),
+                   self._rows(gnn_decisions, K, 2, i32, "gnn_decisions").data_ptr(),
+                   self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(), C.byref(pa), C.byref(pb),
+                   self._rows(ineff, self.R, 1, i32, "ineff").data_ptr(),
+                   self._rows(kw_improvement, K, 1, torch.float64, "kw_improvement").data_ptr(),
+                   self._rows(used_kw, K, 1, i32, "used_kw").data_ptr(), self._rows(decisions, K, 2, i32, "decisions").data_ptr())
 
     # ---- many jobs in one pool (frontier.py verify_properties; include/gnnb.h gnnb_frontier_*_jobs) ------------------------------------
     def _plan(self, plan):
@@ -1074,9 +1047,7 @@ class ScorerEngine:
         pl, n = self._plan(plan), max(int(plan.n), 0)
         args = (self._rows(state, max(int(plan.segments), 0), _lib.FRONTIER_STATE_DOUBLES, torch.float64, "state").data_ptr(),
                 self._rows(slots, n, 1, torch.int32, "slots").data_ptr(), self._rows(row_seg, n, 1, torch.int32, "row_seg").data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_pick_jobs(self.h, C.byref(st), C.byref(pl), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_pick_jobs")
+        self._call("gnnb_frontier_pick_jobs", C.byref(st), C.byref(pl), *args)
 
     def frontier_rows_jobs(self, plan, row_seg, seg_x_lo, seg_x_hi, seg_prop_w, seg_prop_b, x_lo, x_hi, prop_w, prop_b, child_x_lo, child_x_hi,
                            child_prop_w, child_prop_b):
@@ -1093,9 +1064,7 @@ class ScorerEngine:
                 self._rows(prop_w, n, NL, f32, "prop_w").data_ptr(), self._rows(prop_b, n, 1, f32, "prop_b").data_ptr(),
                 self._rows(child_x_lo, 2 * n, N0, f64, "child_x_lo").data_ptr(), self._rows(child_x_hi, 2 * n, N0, f64, "child_x_hi").data_ptr(),
                 self._rows(child_prop_w, 2 * n, NL, f32, "child_prop_w").data_ptr(), self._rows(child_prop_b, 2 * n, 1, f32, "child_prop_b").data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_rows_jobs(self.h, C.byref(pl), *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_rows_jobs")
+        self._call("gnnb_frontier_rows_jobs", C.byref(pl), *args)
 
     def frontier_commit_jobs(self, pool, plan, slots, mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live, state, decision_bound, eps=1e-4,
                              workspace=None):
@@ -1103,22 +1072,13 @@ class ScorerEngine:
         the 2n-row tensors), its parents' slots (slots (n,) int32, global numbers), its segment, its record of ``state`` ((segments, 9)
         fp64) and its entry of ``decision_bound`` ((segments,) fp64 on the device, NaN: none)."""
         st, keep = self._pool(pool)
-        pl, n, S, R = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), self.R
-        tl, tu = self._layer_rows(lb, 2 * n, 1, torch.float64, "lb"), self._layer_rows(ub, 2 * n, 1, torch.float64, "ub")
-        ch = _lib.Children(self._rows(mask, 2 * n, R, torch.int8, "mask").data_ptr(), tl, tu,
-                           self._rows(infeasible, 2 * n, 1, torch.int32, "infeasible").data_ptr(),
-                           self._rows(bound, 2 * n, 1, torch.float64, "bound").data_ptr(), self._rows(alpha, 2 * n, R, torch.float64, "alpha").data_ptr(),
-                           self._rows(beta, 2 * n, R, torch.float64, "beta").data_ptr(),
-                           self._rows(ub_value, 2 * n, 1, torch.float64, "ub_value").data_ptr(),
-                           self._rows(live, 2 * n, 1, torch.int32, "live").data_ptr(), len(self.sizes))
+        pl, n, S = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0)
+        ch, keep_ch = self._children(_ChildRows(mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live), 2 * n)
         self._rows(state, S, _lib.FRONTIER_STATE_DOUBLES, torch.float64, "state")
         self._rows(decision_bound, S, 1, torch.float64, "decision_bound")
         ws = self._workspace("commit_jobs", max(n, 1), "gnnb_frontier_commit_jobs_workspace_bytes") if workspace is None else workspace
-        with torch.cuda.device(self.device):
-            rc = self.lib.gnnb_frontier_commit_jobs(self.h, C.byref(st), C.byref(pl), self._rows(slots, n, 1, torch.int32, "slots").data_ptr(),
-                                                    C.byref(ch), float(eps), decision_bound.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "gnnb_frontier_commit_jobs")
+        self._call("gnnb_frontier_commit_jobs", C.byref(st), C.byref(pl), self._rows(slots, n, 1, torch.int32, "slots").data_ptr(), C.byref(ch),
+                   float(eps), decision_bound.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel())
 
     def _check_primals(self, fixed, prim, B):
         def count(t):

@@ -25,6 +25,12 @@ from .engine import table
 from .lp_producer import _random_order
 
 
+def _start_record():
+    """The state record of a pool (or of a segment) nothing has been committed to."""
+    inf = float("inf")
+    return [inf, inf, inf] + [0.0] * (_lib.FRONTIER_STATE_DOUBLES - 3)
+
+
 class DomainPool:
     """``capacity`` slots of open domains as device tensors (the gnnb_pool of include/gnnb.h) and the loop's state record.
 
@@ -44,8 +50,7 @@ class DomainPool:
         self.beta = torch.zeros(cap, R, dtype=torch.float64, device=dev)
         self.bound = torch.zeros(cap, dtype=torch.float64, device=dev)
         self.open = torch.zeros(cap, dtype=torch.int32, device=dev)
-        inf = float("inf")
-        self.state = torch.tensor([inf, inf, inf] + [0.0] * (_lib.FRONTIER_STATE_DOUBLES - 3), dtype=torch.float64, device=dev)
+        self.state = torch.tensor(_start_record(), dtype=torch.float64, device=dev)
 
     @staticmethod
     def bytes_per_domain(sizes, R):
@@ -55,21 +60,27 @@ class DomainPool:
     def arrays(self):
         return [self.mask] + self.lb + self.ub + [self.alpha, self.beta, self.bound, self.open]
 
+    def reorder(self, order):
+        """Slot i takes what slot order[i] holds, in every array (torch indexing on the device, no synchronisation)."""
+        ts, L = [t[order].contiguous() for t in self.arrays()], len(self.lb)
+        self.mask, self.lb, self.ub = ts[0], ts[1:1 + L], ts[1 + L:1 + 2 * L]
+        self.alpha, self.beta, self.bound, self.open = ts[1 + 2 * L:]
+
     def compact(self, n_open):
-        """Move the open slots to the front, in slot order (torch indexing on the device, no synchronisation).  ``n_open``: their number,
-        which the host knows from the state record; the record's slots-in-use becomes it."""
-        order = torch.sort(self.open, descending=True, stable=True).indices
-        self.mask, self.alpha, self.beta, self.bound, self.open = (t[order].contiguous() for t in (self.mask, self.alpha, self.beta, self.bound, self.open))
-        self.lb = [t[order].contiguous() for t in self.lb]
-        self.ub = [t[order].contiguous() for t in self.ub]
+        """Move the open slots to the front, in slot order.  ``n_open``: their number, which the host knows from the state record; the
+        record's slots-in-use becomes it."""
+        self.reorder(torch.sort(self.open, descending=True, stable=True).indices)
         self.state[_lib.FS_IN_USE] = float(n_open)
 
 
 class _Rows:
-    """Dense batch rows for n domains: what the batch kernels read and write, allocated once."""
+    """Dense batch rows for n domains: what the batch kernels read and write, allocated once, with the pointer tables and the argument
+    structs of the batch entry points over them (the pointers never change; the B of a call does).  box: the rows' boxes and property
+    rows (x_lo, x_hi (n, N_0) fp64, prop_w (n, N_L), prop_b (n,) fp32), the caller's.  child: the bounding side (gnnb_kw_bounds,
+    gnnb_dual_ascent, the commit) instead of the scorer's (gnnb_dual_ascent at n_iter 0, gnnb_forward)."""
 
-    def __init__(self, eng, fixed, n, in_shape, with_fp32):
-        dev, R, sizes = eng.device, eng.R, eng.sizes
+    def __init__(self, eng, fixed, n, in_shape, box, child):
+        dev, R, sizes, ng = eng.device, eng.R, eng.sizes, len(eng.sizes)
         f64, f32, i32 = torch.float64, torch.float32, torch.int32
         self.mask = torch.zeros(n, R, dtype=torch.int8, device=dev)
         self.lb = [torch.zeros(n, s, dtype=f64, device=dev) for s in sizes[1:]]
@@ -88,12 +99,19 @@ class _Rows:
                 self.prims.append(torch.zeros(1, dtype=f32, device=dev))
         self.prims.append(torch.zeros(n, dtype=f32, device=dev))
         self.x_lp = torch.zeros((n,) + tuple(in_shape), dtype=f32, device=dev)
-        if with_fp32:                                             # the picked parents: the scorer's side
+        self.box = box
+        x_lo, x_hi, pw, pb = (t.data_ptr() for t in box)
+        self.t_lb, self.t_ub, self.t_dual, self.t_prims = table(self.lb), table(self.ub), table(self.dual), table(self.prims)
+        self.dual_batch = _lib.DualBatch(self.t_lb, self.t_ub, x_lo, x_hi, pw, pb, self.mask.data_ptr(), ng)
+        if not child:                                             # the picked parents: the scorer's side
             self.lb32 = [torch.zeros(n, s, dtype=f32, device=dev) for s in sizes]
             self.ub32 = [torch.zeros(n, s, dtype=f32, device=dev) for s in sizes]
             self.amb = torch.zeros(n, R, dtype=f32, device=dev)
             self.scores = torch.zeros(n, R, dtype=f32, device=dev)
             self.dec = torch.zeros(n, 2, dtype=i32, device=dev)
+            self.t_lb32, self.t_ub32 = table(self.lb32), table(self.ub32)
+            self.fwd_batch = _lib.Batch(self.t_lb32, self.t_ub32, self.t_dual, self.t_prims, self.x_lp.data_ptr(), pw, pb, self.amb.data_ptr(), ng,
+                                        len(self.dual), len(self.prims))
         else:                                                     # the children: the bounding side
             self.plb = [torch.zeros(n, s, dtype=f64, device=dev) for s in sizes[1:]]
             self.pub = [torch.zeros(n, s, dtype=f64, device=dev) for s in sizes[1:]]
@@ -101,6 +119,12 @@ class _Rows:
             self.live = torch.zeros(n, dtype=i32, device=dev)
             self.infeasible = torch.zeros(n, dtype=i32, device=dev)
             self.ubv = torch.zeros(n, dtype=f64, device=dev)
+            self.t_plb, self.t_pub = table(self.plb), table(self.pub)
+            self.kw_batch = _lib.KwBatch(x_lo, x_hi, pw, pb, self.mask.data_ptr(), self.t_plb, self.t_pub, self.split.data_ptr(), ng)
+
+    def children(self):
+        """The child rows as ``ScorerEngine.frontier_commit`` takes them after the slots (the engine makes the gnnb_children of them)."""
+        return self.mask, self.lb, self.ub, self.infeasible, self.bound, self.alpha, self.beta, self.ubv, self.live
 
 
 def _check_args(K, n_iter, lr, eps, max_rounds, capacity):
@@ -133,11 +157,11 @@ class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
 
     def _buffers(self, n_parents, n_children, in_shape, parent_side):
-        """The rows, workspaces and argument structs of a round of up to n_parents parents.  self.x_lo / x_hi / pw / pb: the children's
-        boxes and property rows; parent_side: the parents' (the same tensors when every row has one box and one property)."""
+        """The rows and workspaces of a round of up to n_parents parents.  self.x_lo / x_hi / pw / pb: the children's boxes and property
+        rows; parent_side: the parents' (the same tensors when every row has one box and one property)."""
         eng, dev = self.eng, self.eng.device
-        self.P = _Rows(eng, self.fixed, n_parents, in_shape, True)
-        self.Ch = _Rows(eng, self.fixed, n_children, in_shape, False)
+        self.P = _Rows(eng, self.fixed, n_parents, in_shape, parent_side, child=False)
+        self.Ch = self._child_rows(n_children, in_shape)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
         self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -147,53 +171,35 @@ class _Round:
         self.ws_fwd, self.ws_kw = ws("gnnb_workspace_bytes", n_parents), ws("gnnb_kw_workspace_bytes", n_children)
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
-        # the argument structs of the existing batch entry points over these rows (pointers never change; B does)
-        P, Ch = self.P, self.Ch
-        self._keep = [table(g) for g in (P.lb, P.ub, P.lb32, P.ub32, P.dual, P.prims, Ch.lb, Ch.ub, Ch.plb, Ch.pub, Ch.dual, Ch.prims)]
-        t = self._keep
-        px_lo, px_hi, ppw, ppb = parent_side
-        self.dual_P = _lib.DualBatch(t[0], t[1], px_lo.data_ptr(), px_hi.data_ptr(), ppw.data_ptr(), ppb.data_ptr(), P.mask.data_ptr(), self.ng)
-        self.fwd_P = _lib.Batch(t[2], t[3], t[4], t[5], P.x_lp.data_ptr(), ppw.data_ptr(), ppb.data_ptr(), P.amb.data_ptr(), self.ng,
-                                len(P.dual), len(P.prims))
-        self.kw_Ch = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), t[8], t[9],
-                                  Ch.split.data_ptr(), self.ng)
-        self.dual_Ch = _lib.DualBatch(t[6], t[7], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), Ch.mask.data_ptr(), self.ng)
-        self._side_a = (Ch, self.kw_Ch, self.dual_Ch, t[6], t[7], t[10], t[11])
 
-    def _second_children(self, n_children, in_shape):
-        """A second set of child rows (pair B of the threshold mode) on the same boxes, property rows and
-        workspaces: everything is stream-ordered, so the two pairs never use a workspace at the same time."""
-        ChB = self.ChB = _Rows(self.eng, self.fixed, n_children, in_shape, False)
-        self._keep_b = t = [table(g) for g in (ChB.lb, ChB.ub, ChB.plb, ChB.pub, ChB.dual, ChB.prims)]
-        kw = _lib.KwBatch(self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), ChB.mask.data_ptr(), t[2], t[3],
-                          ChB.split.data_ptr(), self.ng)
-        dual = _lib.DualBatch(t[0], t[1], self.x_lo.data_ptr(), self.x_hi.data_ptr(), self.pw.data_ptr(), self.pb.data_ptr(), ChB.mask.data_ptr(), self.ng)
-        self._side_b = (ChB, kw, dual, t[0], t[1], t[4], t[5])
+    def _child_rows(self, n_children, in_shape):
+        """A set of child rows on the children's boxes and property rows.  A second set (pair B of the threshold mode, DESIGN.md section
+        7.5) shares the workspaces: everything is stream-ordered, so the two pairs never use one at the same time."""
+        return _Rows(self.eng, self.fixed, n_children, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb), child=True)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def _bound_children(self, B, warm, side=None):
-        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B child rows (side: None, or the second set's ``_side_b``)."""
+    def _bound_children(self, Ch, B, warm):
+        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``."""
         lib, h = self.lib, self.eng.h
-        Ch, kw, dual, t_lb, t_ub, t_dual, t_prims = self._side_a if side is None else side
         with torch.cuda.device(self.eng.device):
-            _lib.check(lib.gnnb_kw_bounds(h, C.byref(kw), B, t_lb, t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
+            _lib.check(lib.gnnb_kw_bounds(h, C.byref(Ch.kw_batch), B, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
                                           self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
-            _lib.check(lib.gnnb_dual_ascent(h, C.byref(dual), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
-                                            Ch.bound.data_ptr(), None, None, t_dual, t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
+            _lib.check(lib.gnnb_dual_ascent(h, C.byref(Ch.dual_batch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
+                                            Ch.bound.data_ptr(), None, None, Ch.t_dual, Ch.t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
         self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=(self.pw, self.pb), workspace=self.ws_eval)
 
     def _score_parents(self, B):
         """gnnb_dual_ascent at n_iter = 0 (the scorer's inputs at the stored best point: one evaluation of g instead of ~120 KB of fp32
         inputs per open domain) and gnnb_forward over the first B parent rows."""
-        P, lib, h, t = self.P, self.lib, self.eng.h, self._keep
+        P, lib, h = self.P, self.lib, self.eng.h
         with torch.cuda.device(self.eng.device):
-            _lib.check(lib.gnnb_dual_ascent(h, C.byref(self.dual_P), B, 0, self.lr, P.alpha.data_ptr(), P.beta.data_ptr(), 1, P.bound.data_ptr(), None, None,
-                                            t[4], t[5], P.x_lp.data_ptr(), P.lb32[-1].data_ptr(), self.ws_dual.data_ptr(), self.ws_dual.numel(),
+            _lib.check(lib.gnnb_dual_ascent(h, C.byref(P.dual_batch), B, 0, self.lr, P.alpha.data_ptr(), P.beta.data_ptr(), 1, P.bound.data_ptr(), None, None,
+                                            P.t_dual, P.t_prims, P.x_lp.data_ptr(), P.lb32[-1].data_ptr(), self.ws_dual.data_ptr(), self.ws_dual.numel(),
                                             self._stream()), "gnnb_dual_ascent")
-            _lib.check(lib.gnnb_forward(h, C.byref(self.fwd_P), B, P.scores.data_ptr(), P.dec.data_ptr(), self.status.data_ptr(), self.ws_fwd.data_ptr(),
+            _lib.check(lib.gnnb_forward(h, C.byref(P.fwd_batch), B, P.scores.data_ptr(), P.dec.data_ptr(), self.status.data_ptr(), self.ws_fwd.data_ptr(),
                                         self.ws_fwd.numel(), self._stream()), "gnnb_forward")
         self.status_all |= self.status
 
@@ -237,7 +243,7 @@ class FrontierRun(_Round):
             f64, f32, i32, R = torch.float64, torch.float32, torch.int32, eng.R
             self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
             self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
-            self._second_children(n, in_shape)
+            self.ChB = self._child_rows(n, in_shape)
             self.ineff, self.icp = torch.zeros(R, dtype=i32, device=dev), torch.zeros(1, dtype=i32, device=dev)
             self.kw_scores, self.kw_icp = torch.zeros(K, R, dtype=f32, device=dev), torch.zeros(K, R, dtype=f32, device=dev)
             self.gnn_imp, self.kw_imp = torch.zeros(K, dtype=f64, device=dev), torch.zeros(K, dtype=f64, device=dev)
@@ -247,9 +253,8 @@ class FrontierRun(_Round):
             self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_workspace_bytes(eng.h, K)), dtype=torch.uint8, device=dev)
 
     def _commit(self, slots):
-        Ch = self.Ch
-        self.eng.frontier_commit(self.pool, slots, Ch.mask, Ch.lb, Ch.ub, Ch.infeasible, Ch.bound, Ch.alpha, Ch.beta, Ch.ubv, Ch.live, self.pool.state,
-                                 eps=self.eps, decision_bound=self.decision_bound, workspace=self.ws_commit)
+        self.eng.frontier_commit(self.pool, slots, *self.Ch.children(), self.pool.state, eps=self.eps, decision_bound=self.decision_bound,
+                                 workspace=self.ws_commit)
 
     def root(self):
         """Bound the domain with every ReLU undecided (no parent, the default start of the ascent) and commit it as the first open domain:
@@ -258,7 +263,7 @@ class FrontierRun(_Round):
         Ch.mask[:1].fill_(-1)
         Ch.split[:2].fill_(-1)
         Ch.live[:2] = torch.tensor([1, 0], dtype=torch.int32).to(Ch.live.device)
-        self._bound_children(1, warm=False)
+        self._bound_children(Ch, 1, warm=False)
         self._commit(self.root_slot)
         st = self.read_state()
         if st[_lib.FS_INFEASIBLE] > 0:
@@ -278,7 +283,7 @@ class FrontierRun(_Round):
         eng.frontier_gather(pool, slots, self.x_lo, self.x_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
         self._score_parents(k)
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
-        self._bound_children(2 * k, warm=True)
+        self._bound_children(Ch, 2 * k, warm=True)
         if self.threshold is not None:
             self._fall_back(k)
         self._commit(slots)
@@ -297,7 +302,7 @@ class FrontierRun(_Round):
         if m == 0:
             return
         eng.frontier_expand(pool, self.sel_slots[:m], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
-        self._bound_children(2 * m, warm=True, side=self._side_b)
+        self._bound_children(ChB, 2 * m, warm=True)
         eng.frontier_choose(pool, k, m, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff, self.kw_imp,
                             self.used_kw, self.dec)
         self.n_used += self.used_kw[:k].sum()
@@ -347,46 +352,27 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     S = _lib
     st = run.root()
     rounds, bounded = 0, 1
-
-    def glb(st):
-        return min(st[S.FS_LOWEST_OPEN], st[S.FS_CLOSED_LB], st[S.FS_GLOBAL_UB])
-    log(f"root lb {glb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
+    log(f"root lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     while True:
-        global_lb, global_ub, n_open, in_use = glb(st), st[S.FS_GLOBAL_UB], int(st[S.FS_N_OPEN]), int(st[S.FS_IN_USE])
-        if n_open == 0:
-            reason = "exhausted"
-        elif not global_ub - global_lb > eps:
-            reason = "gap"
-        elif decision_bound is not None and (global_lb >= decision_bound or global_ub < decision_bound):
-            reason = "decision"
-        elif rounds >= max_rounds:
-            reason = "max_rounds"
-        elif n_open + min(K, n_open) > run.capacity:
-            reason = "capacity"
-        else:
-            reason = None
+        global_lb, global_ub, n_open, in_use = _global_lb(st), st[S.FS_GLOBAL_UB], int(st[S.FS_N_OPEN]), int(st[S.FS_IN_USE])
+        reason, k, compact = _one_job_round(st, K, run.capacity, eps, decision_bound, rounds, max_rounds)
         if reason is not None:
             break
-        k = min(K, n_open)
-        if in_use + k > run.capacity:                             # the kept children beyond the k parents' slots go above in_use
+        if compact:                                               # the kept children beyond the k parents' slots go above in_use
             run.pool.compact(n_open)
             in_use = n_open
         run.launch_round(k, in_use)
         if trace is not None:
-            P, Ch = run.P, run.Ch
-            trace.append({"slots": run.slots.cpu().tolist(), "parent_bounds": P.bound[:k].cpu().tolist(), "decisions": P.dec[:k].cpu().tolist(),
-                          "child_bounds": Ch.bound[:2 * k].cpu().tolist(), "child_ub": Ch.ubv[:2 * k].cpu().tolist(),
-                          "live": Ch.live[:2 * k].cpu().tolist(), "infeasible": Ch.infeasible[:2 * k].cpu().tolist()})
+            trace.append(_trace_rows(run, 0, k))
             if branching_threshold is not None:
                 trace[-1].update(_threshold_trace(run, k))
         st = run.read_state()
-        if st[S.FS_OVERFLOW] != 0 or math.isnan(st[S.FS_GLOBAL_UB]):
-            raise RuntimeError(f"frontier state record is inconsistent: {st}")
+        _check_record(st)
         rounds += 1
         bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE]) + 2 * run.m
         branches, kw_bounded = branches + k, kw_bounded + run.m
         log(f"round {rounds} picked {k} kept {int(st[S.FS_KEPT])} closed {int(st[S.FS_CLOSED])} infeasible {int(st[S.FS_INFEASIBLE])} open {int(st[S.FS_N_OPEN])} "
-            f"lb {glb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
+            f"lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     run.check_status()
     if stats is not None:
         stats.update(branches=branches, kw_bounded=kw_bounded, domains_bounded=bounded,
@@ -413,11 +399,6 @@ class FrontierJob:
 
     def __init__(self, input_lb, input_ub, prop_layer, decision_bound=None):
         self.input_lb, self.input_ub, self.prop_layer, self.decision_bound = input_lb, input_ub, prop_layer, decision_bound
-
-
-def _start_record():
-    inf = float("inf")
-    return [inf, inf, inf] + [0.0] * (_lib.FRONTIER_STATE_DOUBLES - 3)
 
 
 def _global_lb(st):
@@ -461,6 +442,31 @@ def plan_round(records, K, cap):
         entries.append((s, row0, k))
         row0 += k
     return entries, compact, stopped
+
+
+def _one_job_round(st, K, capacity, eps, decision_bound, rounds, max_rounds):
+    """What ``branch_and_bound_frontier`` does on the record ``st``: (reason, k, compact) -- a stop reason, or None and a round of k parents
+    after a compaction of the pool if ``compact``.  The rule is ``verify_properties``' for a pool of one segment."""
+    reason = _stop_reason(st, eps, decision_bound, rounds, max_rounds)
+    if reason is not None:
+        return reason, 0, False
+    entries, compact, stopped = plan_round([st], K, capacity)
+    if stopped:
+        return "capacity", 0, False
+    return None, entries[0][2], compact[0]
+
+
+def _check_record(st):
+    if st[_lib.FS_OVERFLOW] != 0 or math.isnan(st[_lib.FS_GLOBAL_UB]):
+        raise RuntimeError(f"frontier state record is inconsistent: {st}")
+
+
+def _trace_rows(run, a, b):
+    """A round's trace of the parent rows [a, b) and their children (device-to-host copies)."""
+    P, Ch, c, d = run.P, run.Ch, 2 * a, 2 * b
+    return {"slots": run.slots[a:b].cpu().tolist(), "parent_bounds": P.bound[a:b].cpu().tolist(), "decisions": P.dec[a:b].cpu().tolist(),
+            "child_bounds": Ch.bound[c:d].cpu().tolist(), "child_ub": Ch.ubv[c:d].cpu().tolist(), "live": Ch.live[c:d].cpu().tolist(),
+            "infeasible": Ch.infeasible[c:d].cpu().tolist()}
 
 
 class RoundPlan:
@@ -555,9 +561,8 @@ class JobsRun(_Round):
         self.seg_db[seg].copy_(self.job_db[job])
 
     def _commit(self, n):
-        Ch = self.Ch
-        self.eng.frontier_commit_jobs(self.pool, self.plan, self.slots[:n], Ch.mask, Ch.lb, Ch.ub, Ch.infeasible, Ch.bound, Ch.alpha, Ch.beta, Ch.ubv,
-                                      Ch.live, self.pool.state, self.seg_db, eps=self.eps, workspace=self.ws_commit)
+        self.eng.frontier_commit_jobs(self.pool, self.plan, self.slots[:n], *self.Ch.children(), self.pool.state, self.seg_db, eps=self.eps,
+                                      workspace=self.ws_commit)
 
     def _rows_of_plan(self):
         self.eng.frontier_rows_jobs(self.plan, self.row_seg, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.px_lo, self.px_hi, self.ppw,
@@ -575,7 +580,7 @@ class JobsRun(_Round):
         Ch.mask[:2 * E].fill_(-1)
         Ch.split[:2 * E].fill_(-1)
         Ch.live[:2 * E] = self.root_live[:2 * E]
-        self._bound_children(2 * E, warm=False)
+        self._bound_children(Ch, 2 * E, warm=False)
         self._commit(E)
 
     def compact(self, flagged):
@@ -585,10 +590,7 @@ class JobsRun(_Round):
         self.flags_host.copy_(torch.tensor(flagged, dtype=torch.int32))
         self.flags.copy_(self.flags_host, non_blocking=True)
         flag = self.flags[self.slot_seg] > 0
-        order = torch.sort(2 * self.slot_seg + (flag & (pool.open == 0)), stable=True).indices
-        pool.mask, pool.alpha, pool.beta, pool.bound, pool.open = (t[order].contiguous() for t in (pool.mask, pool.alpha, pool.beta, pool.bound, pool.open))
-        pool.lb = [t[order].contiguous() for t in pool.lb]
-        pool.ub = [t[order].contiguous() for t in pool.ub]
+        pool.reorder(torch.sort(2 * self.slot_seg + (flag & (pool.open == 0)), stable=True).indices)
         pool.state[:, _lib.FS_IN_USE] = torch.where(self.flags > 0, pool.state[:, _lib.FS_N_OPEN], pool.state[:, _lib.FS_IN_USE])
 
     def launch_round(self, entries):
@@ -602,7 +604,7 @@ class JobsRun(_Round):
         eng.frontier_gather(pool, slots, self.px_lo, self.px_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
         self._score_parents(n)
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
-        self._bound_children(2 * n, warm=True)
+        self._bound_children(Ch, 2 * n, warm=True)
         self._commit(n)
 
     def read_state(self):
@@ -630,10 +632,6 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
     results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
     seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
     waiting = list(range(len(jobs)))
-
-    def check(st):
-        if st[F.FS_OVERFLOW] != 0 or math.isnan(st[F.FS_GLOBAL_UB]):
-            raise RuntimeError(f"frontier state record is inconsistent: {st}")
 
     def reason_of(s):
         j = seg_job[s]
@@ -663,7 +661,7 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
             for s in admitted:
                 rec[s], bounded[seg_job[s]] = st[s], 1
                 if not rec[s][F.FS_INFEASIBLE] > 0:
-                    check(rec[s])
+                    _check_record(rec[s])
                 log(f"job {seg_job[s]} segment {s}: root lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
         if all(j is None for j in seg_job):
             break
@@ -676,18 +674,13 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
             run.compact(compact)
         run.launch_round(entries)
         if trace is not None:
-            P, Ch = run.P, run.Ch
             for s, row0, k in entries:
-                a, b, c, d = row0, row0 + k, 2 * row0, 2 * row0 + 2 * k
-                trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], "slots": run.slots[a:b].cpu().tolist(),
-                              "parent_bounds": P.bound[a:b].cpu().tolist(), "decisions": P.dec[a:b].cpu().tolist(),
-                              "child_bounds": Ch.bound[c:d].cpu().tolist(), "child_ub": Ch.ubv[c:d].cpu().tolist(),
-                              "live": Ch.live[c:d].cpu().tolist(), "infeasible": Ch.infeasible[c:d].cpu().tolist()})
+                trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], **_trace_rows(run, row0, row0 + k)})
         st = run.read_state()
         for s, _, k in entries:
             j = seg_job[s]
             rec[s] = st[s]
-            check(rec[s])
+            _check_record(rec[s])
             rounds[j] += 1
             bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
             log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "

@@ -93,3 +93,86 @@ def test_smallest_capacity_is_accepted_by_the_argument_check():
 def test_bytes_per_open_domain():
     """DESIGN.md section 7.3's figure for cifar_base_kw: R = 3172 ReLU nodes, graph layers 3072 / 2048 / 1024 / 100 / 1."""
     assert frontier.DomainPool.bytes_per_domain([3072, 2048, 1024, 100, 1], 3172) == 3172 * 17 + 16 * 3173 + 12
+
+
+def test_start_record_is_what_a_new_pool_holds():
+    """Three +inf (global_ub, closed_lb, lowest open bound), then zeros: the first FRONTIER_STATE_DOUBLES values ``DomainPool`` starts from."""
+    inf = float("inf")
+    assert _lib.FRONTIER_STATE_DOUBLES == 9
+    assert frontier._start_record() == [inf, inf, inf, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+
+
+def _inline_round(st, K, capacity, eps, decision_bound, rounds, max_rounds):
+    """The rule ``branch_and_bound_frontier`` had inline before it shared ``_stop_reason`` and ``plan_round`` with ``verify_properties``."""
+    global_lb, global_ub = min(st[_lib.FS_LOWEST_OPEN], st[_lib.FS_CLOSED_LB], st[_lib.FS_GLOBAL_UB]), st[_lib.FS_GLOBAL_UB]
+    n_open, in_use = int(st[_lib.FS_N_OPEN]), int(st[_lib.FS_IN_USE])
+    if n_open == 0:
+        return "exhausted", 0, False
+    if not global_ub - global_lb > eps:
+        return "gap", 0, False
+    if decision_bound is not None and (global_lb >= decision_bound or global_ub < decision_bound):
+        return "decision", 0, False
+    if rounds >= max_rounds:
+        return "max_rounds", 0, False
+    if n_open + min(K, n_open) > capacity:
+        return "capacity", 0, False
+    k = min(K, n_open)
+    return None, k, in_use + k > capacity
+
+
+def _record(n_open, in_use, gub=1.0, closed=float("inf"), low=-1.0):
+    return [gub, closed, low, float(n_open), float(in_use), 0.0, 0.0, 0.0, 0.0]
+
+
+# (record, K, capacity, eps, decision_bound, rounds, max_rounds) -> (reason, k, compact), written out by hand.  global_lb = min(low, closed,
+# gub) = -1 and global_ub = 1 unless the record says otherwise.
+ROUND_CASES = [
+    # a plain round: fewer open domains than K, and more
+    ((_record(3, 5), 4, 20, 1e-4, None, 0, 5), (None, 3, False)),
+    ((_record(9, 9), 4, 20, 1e-4, None, 0, 5), (None, 4, False)),
+    # each stop reason alone
+    ((_record(0, 5), 4, 20, 1e-4, None, 0, 5), ("exhausted", 0, False)),
+    ((_record(3, 5, gub=1.0, low=1.0 - 5e-5), 4, 20, 1e-4, None, 0, 5), ("gap", 0, False)),
+    ((_record(3, 5, gub=1.0, low=0.5), 4, 20, 0.5, None, 0, 5), ("gap", 0, False)),                   # (a gap equal to eps stops)
+    ((_record(3, 5, gub=1.0, low=0.25), 4, 20, 0.5, None, 0, 5), (None, 3, False)),
+    ((_record(3, 5), 4, 20, 1e-4, 2.0, 0, 5), ("decision", 0, False)),                                 # global_ub below the bound
+    ((_record(3, 5), 4, 20, 1e-4, -2.0, 0, 5), ("decision", 0, False)),                                # global_lb above it
+    ((_record(3, 5), 4, 20, 1e-4, None, 5, 5), ("max_rounds", 0, False)),
+    ((_record(18, 18), 4, 20, 1e-4, None, 0, 5), ("capacity", 0, False)),
+    # in pairs: exhausted > gap > decision > max_rounds > capacity
+    ((_record(0, 5, gub=1.0, low=1.0), 4, 20, 1e-4, None, 0, 5), ("exhausted", 0, False)),
+    ((_record(0, 5), 4, 20, 1e-4, 2.0, 0, 5), ("exhausted", 0, False)),
+    ((_record(0, 5), 4, 20, 1e-4, None, 5, 5), ("exhausted", 0, False)),
+    ((_record(3, 5, gub=1.0, low=1.0), 4, 20, 1e-4, 2.0, 0, 5), ("gap", 0, False)),
+    ((_record(3, 5, gub=1.0, low=1.0), 4, 20, 1e-4, None, 5, 5), ("gap", 0, False)),
+    ((_record(18, 18, gub=1.0, low=1.0), 4, 20, 1e-4, None, 0, 5), ("gap", 0, False)),
+    ((_record(3, 5), 4, 20, 1e-4, 2.0, 5, 5), ("decision", 0, False)),
+    ((_record(18, 18), 4, 20, 1e-4, 2.0, 0, 5), ("decision", 0, False)),
+    ((_record(18, 18), 4, 20, 1e-4, None, 5, 5), ("max_rounds", 0, False)),
+    # the bound closed_lb or global_ub gives, not the lowest open one
+    ((_record(3, 5, gub=1.0, closed=-3.0, low=-1.0), 4, 20, 1e-4, -2.0, 0, 5), (None, 3, False)),
+    ((_record(3, 5, gub=1.0, closed=0.5, low=2.0), 4, 20, 1e-4, 0.5, 0, 5), ("decision", 0, False)),
+    # n_open + min(K, n_open) equal to the capacity, and one above it
+    ((_record(16, 16), 4, 20, 1e-4, None, 0, 5), (None, 4, False)),
+    ((_record(17, 17), 4, 20, 1e-4, None, 0, 5), ("capacity", 0, False)),
+    ((_record(2, 2), 4, 4, 1e-4, None, 0, 5), (None, 2, False)),                                       # (min(K, n_open) = n_open)
+    ((_record(3, 3), 4, 5, 1e-4, None, 0, 5), ("capacity", 0, False)),
+    # in_use + k equal to the capacity, and one above it: the compaction flag
+    ((_record(3, 17), 4, 20, 1e-4, None, 0, 5), (None, 3, False)),
+    ((_record(3, 18), 4, 20, 1e-4, None, 0, 5), (None, 3, True)),
+    ((_record(9, 16), 4, 20, 1e-4, None, 0, 5), (None, 4, False)),
+    ((_record(9, 17), 4, 20, 1e-4, None, 0, 5), (None, 4, True)),
+    # no decision bound, and one equal to global_lb (>= stops)
+    ((_record(3, 5), 4, 20, 1e-4, None, 0, 5), (None, 3, False)),
+    ((_record(3, 5), 4, 20, 1e-4, -1.0, 0, 5), ("decision", 0, False)),
+    ((_record(3, 5), 4, 20, 1e-4, 1.0, 0, 5), (None, 3, False)),                                       # (global_ub equal to it does not)
+    ((_record(3, 5), 4, 20, 1e-4, 0.0, 0, 5), (None, 3, False)),
+    # max_rounds = 0 stops before the first round
+    ((_record(1, 1), 4, 20, 1e-4, None, 0, 0), ("max_rounds", 0, False)),
+]
+
+
+@pytest.mark.parametrize("args,expected", ROUND_CASES)
+def test_the_one_job_loop_decides_its_round_by_the_rule_it_had_inline(args, expected):
+    assert _inline_round(*args) == expected                   # the table itself, against the restated rule
+    assert frontier._one_job_round(*args) == expected
