@@ -129,7 +129,7 @@ struct BoundNet : LayerGraph {
   std::vector<DevBuf<float>> edge_w;   // torch-layout weights of the edges for the trainer, made by the first gnnb_online_step
 };
 
-// Host helper threads of a handle, created on the first call that wants them (gnnb_pack_amb_records) and joined by gnnb_destroy: creating
+// Host helper threads of a handle, created by the first call that wants them (work_pool below) and joined by gnnb_destroy: creating
 // and joining threads per call cost 0.25 ms of a 0.65-ms pack.  Idle workers sleep on a condition variable.  (A handle is created in the
 // process that uses it -- the BaB harness forks first, bab_mip.py:244-249 -- so no thread ever has to survive a fork.)
 struct WorkPool {
@@ -140,7 +140,7 @@ struct WorkPool {
   long gen = 0;
   int busy = 0;
   bool stop = false;
-  pid_t owner = getpid();             // a forked child inherits the object but not the threads: it makes a pool of its own (gnnb_pack_amb_records)
+  pid_t owner = getpid();             // a forked child inherits the object but not the threads: it makes a pool of its own (work_pool)
   explicit WorkPool(int n) {
     for (int i = 0; i < n; ++i)
       th.emplace_back([this] {
@@ -185,7 +185,8 @@ struct WorkPool {
 };
 
 struct gnnb_handle : BoundNet {
-  WorkPool* work_pool = nullptr;      // see WorkPool
+  WorkPool* work_pool = nullptr;      // see WorkPool; made and replaced by work_pool(h) alone, under pool_mutex
+  std::mutex pool_mutex;
   int T = 2, p = 64, device = 0, n_cu = 256;
   bool use_gather = true;       // MFMA gather for conv edges (false: VALU gather kernels)
   // (k_node_update: 12 waves per workgroup = 3 per SIMD with the bf16x3 blocks (142-152 VGPRs, no scratch); the fp32-MFMA-only
@@ -397,6 +398,26 @@ extern "C" int gnnb_destroy(gnnb_t* h) {
 }
 
 static bool conv_channels_ok(int c) { return c == 3 || c == 8 || c == 16 || c == 32; }
+
+// The handle's helper threads, made on first use: what the machine (or the cgroup's CPU set) offers, a dozen threads with the caller at
+// most.  After a fork the parent's threads are not here: its object is left alone and the child gets a pool of its own.
+static WorkPool& work_pool(gnnb_t* h) {
+  std::lock_guard<std::mutex> lk(h->pool_mutex);
+  if (!h->work_pool || h->work_pool->owner != getpid()) {
+    const unsigned hc = std::thread::hardware_concurrency();
+    cpu_set_t set;
+    int avail = (sched_getaffinity(0, sizeof set, &set) == 0) ? CPU_COUNT(&set) : (int)hc;
+    if (avail < 1) avail = hc ? (int)hc : 1;
+    h->work_pool = new WorkPool(std::max(0, std::min(avail, 12) - 1));
+  }
+  return *h->work_pool;
+}
+
+// gnnb_pack.h check_batch for entry point `who`
+static int refuse_batch(const gnnb_t* h, const gnnb_batch* in, int B, const BatchNeeds& need, const char* who) {
+  const std::string refusal = check_batch(*h, *in, B, need);
+  return refusal.empty() ? GNNB_OK : fail(GNNB_E_INVALID, "%s: %s", who, refusal.c_str());
+}
 
 // a network with an inner conv edge that leaves a pixel unread (gnnb_pack.h zero_tap_layer) is refused by the scoring entry points
 static int refuse_zero_taps(const gnnb_t* h, const char* who) {
@@ -893,9 +914,9 @@ struct Forward {
     a.pack_f = h->d_pack[PK_PRE_FWD]; a.pack_b = h->d_pack[PK_PRE_BWD];
     a.L = L; a.do_bwd = p.limit >= 2 ? 1 : 0; a.cnt = cnt + 4;
     for (int k = 1; k <= L; ++k) {
-      const int i = k - 1, q = h->relu_q[k];
-      a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.dual[i] = in->dual[k - 1];
-      a.z_pre[i] = in->primal[q - 1]; a.z_post[i] = in->primal[q]; a.bias[i] = h->dev[k].bias.get();
+      const int i = k - 1;
+      const ReluRows r = relu_rows(*h, *in, B, k);
+      a.lb[i] = r.lb; a.ub[i] = r.ub; a.dual[i] = r.dual; a.z_pre[i] = r.z_pre; a.z_post[i] = r.z_post; a.bias[i] = h->dev[k].bias.get();
       a.Pf[i] = ws + w.Pf[k]; a.Pb[i] = ws + w.Pb[k]; a.list[i] = ilist(w.amb[k]);
       a.N[i] = h->N[k]; a.hw[i] = h->hw[k];
     }
@@ -1229,20 +1250,9 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
                             void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !in || !scores || !decisions || !status || !workspace) return fail(GNNB_E_INVALID, "gnnb_forward: null argument");
   if (!h->bound) return fail(GNNB_E_STATE, "gnnb_forward: call gnnb_bind_network first");
-  if (B < 1) return fail(GNNB_E_INVALID, "gnnb_forward: B=%d", B);
-  const int K = (int)h->N.size() - 1, L = K - 1;
-  if (in->n_graph != K + 1 || in->n_relu != L || in->n_primal != h->n_fixed + 1)
-    return fail(GNNB_E_INVALID, "gnnb_forward: batch has %d graph layers / %d dual / %d primal tensors, network needs %d / %d / %d",
-                in->n_graph, in->n_relu, in->n_primal, K + 1, L, h->n_fixed + 1);
-  for (int k = 0; k <= K; ++k)
-    if (!in->lb[k] || !in->ub[k]) return fail(GNNB_E_INVALID, "gnnb_forward: null bounds pointer for graph layer %d", k);
-  for (int k = 0; k < L; ++k)
-    if (!in->dual[k]) return fail(GNNB_E_INVALID, "gnnb_forward: null dual pointer %d", k);
-  for (int m = 0; m < in->n_primal; ++m)
-    if (!in->primal[m]) return fail(GNNB_E_INVALID, "gnnb_forward: null primal pointer %d", m);
-  if (!in->x_lp || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "gnnb_forward: null input pointer");
-  if ((long)B * h->N[0] * 64 >= (1L << 40)) return fail(GNNB_E_INVALID, "gnnb_forward: batch too large");
   if (int rc = refuse_zero_taps(h, "gnnb_forward")) return rc;
+  if (int rc = refuse_batch(h, in, B, kNeedsForward, "gnnb_forward")) return rc;
+  const int L = (int)h->N.size() - 2;
   const WsLayout w = ws_layout(h, B);
   if (workspace_bytes < w.total * sizeof(float))
     return fail(GNNB_E_NOMEM, "gnnb_forward: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
@@ -1305,10 +1315,9 @@ extern "C" int gnnb_forward(gnnb_t* h, const gnnb_batch* in, int B, float* score
 extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* scores, int32_t* decisions, int32_t* status, void* stream) {
   if (!h || !in || !decisions || !status) return fail(GNNB_E_INVALID, "gnnb_forward_host: null argument");
   if (!h->bound) return fail(GNNB_E_STATE, "gnnb_forward_host: call gnnb_bind_network first");
-  const int K = (int)h->N.size() - 1, L = K - 1, R = h->R;
-  if (B < 1 || in->n_graph != K + 1 || in->n_relu != L || in->n_primal != h->n_fixed + 1)
-    return fail(GNNB_E_INVALID, "gnnb_forward_host: batch does not match the bound network");
   if (int rc = refuse_zero_taps(h, "gnnb_forward_host")) return rc;
+  if (int rc = refuse_batch(h, in, B, kNeedsForwardHost, "gnnb_forward_host")) return rc;
+  const int K = (int)h->N.size() - 1, L = K - 1, R = h->R;
   hipStream_t st = (hipStream_t)stream;
   // ---- slots: (host pointer, floats); primals the forward never reads are not transferred
   struct Slot { const float* src; size_t n, off; };
@@ -1318,16 +1327,13 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
   std::vector<size_t> i_lb(K + 1), i_ub(K + 1), i_dual(L), i_prim(in->n_primal, (size_t)-1);
   for (int k = 0; k <= K; ++k) { i_lb[k] = add(in->lb[k], (size_t)B * h->N[k]); i_ub[k] = add(in->ub[k], (size_t)B * h->N[k]); }
   for (int k = 0; k < L; ++k) i_dual[k] = add(in->dual[k], (size_t)B * h->N[k + 1] * 3);
-  for (int k = 1; k <= L; ++k) {
-    const int q = h->relu_q[k];
-    for (int m : {q - 1, q})
+  for (int k = 1; k <= L; ++k)
+    for (int m : {h->relu_q[k] - 1, h->relu_q[k]})
       if (i_prim[m] == (size_t)-1) i_prim[m] = add(in->primal[m], (size_t)B * h->N[k]);
-  }
   if (i_prim[in->n_primal - 1] == (size_t)-1) i_prim[in->n_primal - 1] = add(in->primal[in->n_primal - 1], (size_t)B);
   const size_t i_x = add(in->x_lp, (size_t)B * h->N[0]), i_pw = add(in->prop_w, (size_t)B * h->N[L]), i_pb = add(in->prop_b, (size_t)B);
   const size_t i_mask = add(in->mask, (size_t)B * R);
   for (const Slot& sl : slots) {
-    if (!sl.src) return fail(GNNB_E_INVALID, "gnnb_forward_host: null input pointer");
     // these are read by memcpy on the host: device memory here is a caller bug (e.g. data_ptr() of a `.cuda()` tensor), refused
     // rather than dereferenced.  ~0.2 us per pointer: the runtime's allocation map, no driver call
     hipPointerAttribute_t at{};
@@ -1342,27 +1348,22 @@ extern "C" int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* 
   HIPCHK(h->hs_dec.grow((size_t)B * 2 + 1));          // decisions, then the status word
   HIPCHK(h->hs_out_pinned.grow((size_t)B * R + (size_t)B * 2 + 1));
   // ---- stage, one transfer, forward
-  // staging: one memcpy per input tensor; big batches (36.5 MB at base B = 256: 2.3 ms on one thread) are split over a few helper threads
+  // staging: one memcpy per input tensor; big batches (36.5 MB at base B = 256: 2.3 ms on one thread) are split over the handle's helper threads
   if (total * sizeof(float) < (size_t)4 << 20) {
     for (const Slot& sl : slots) memcpy(h->hs_pinned.get() + sl.off, sl.src, sl.n * sizeof(float));
   } else {
-    const int nthr = 8;
     const size_t chunk = (size_t)1 << 18;                 // floats (1 MB) per work item
     std::vector<std::pair<size_t, size_t>> items;         // (slot, first float)
     for (size_t i = 0; i < slots.size(); ++i)
       for (size_t o = 0; o < slots[i].n; o += chunk) items.emplace_back(i, o);
     std::atomic<size_t> next{0};
-    auto work = [&]() {
+    work_pool(h).run([&]() {
       for (size_t it = next.fetch_add(1); it < items.size(); it = next.fetch_add(1)) {
         const Slot& sl = slots[items[it].first];
         const size_t o = items[it].second, n = std::min(chunk, sl.n - o);
         memcpy(h->hs_pinned.get() + sl.off + o, sl.src + o, n * sizeof(float));
       }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nthr; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
   }
   float* const dev = h->hs_dev.get();
   HIPCHK(hipMemcpyAsync(dev, h->hs_pinned.get(), total * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1398,16 +1399,8 @@ extern "C" int gnnb_pack_amb_records(const gnnb_t* hc, const gnnb_batch* in, int
   gnnb_t* h = const_cast<gnnb_t*>(hc);                  // (the helper threads live in the handle)
   if (!h || !in || !dst || !used) return fail(GNNB_E_INVALID, "gnnb_pack_amb_records: null argument");
   if (!h->bound) return fail(GNNB_E_STATE, "gnnb_pack_amb_records: call gnnb_bind_network first");
-  const int K = (int)h->N.size() - 1, L = K - 1;
-  if (B < 1 || L > MAXL || in->n_graph != K + 1 || in->n_relu != L || in->n_primal != h->n_fixed + 1)
-    return fail(GNNB_E_INVALID, "gnnb_pack_amb_records: batch does not match the bound network");
-  for (int k = 1; k <= L; ++k) {
-    const int q = h->relu_q[k];
-    if (!in->lb[k] || !in->ub[k] || !in->dual[k - 1] || !in->primal[q - 1] || !in->primal[q])
-      return fail(GNNB_E_INVALID, "gnnb_pack_amb_records: null input pointer (layer %d)", k);
-    if ((long)B * h->N[k] > 0x7fffffffL) return fail(GNNB_E_INVALID, "gnnb_pack_amb_records: batch too large");
-  }
-  if (!in->primal[in->n_primal - 1]) return fail(GNNB_E_INVALID, "gnnb_pack_amb_records: null primals[-1]");
+  if (int rc = refuse_batch(h, in, B, kNeedsPack, "gnnb_pack_amb_records")) return rc;
+  const int L = (int)h->N.size() - 2;
   const size_t zwords = (size_t)((B + 3) & ~3);
   if (cap < (16 + zwords) * 4) return fail(GNNB_E_NOMEM, "gnnb_pack_amb_records: buffer of %zu bytes is too small", cap);
   const size_t max_rec = (cap / 4 - 16 - zwords) / AMBREC_WORDS;
@@ -1429,8 +1422,9 @@ extern "C" int gnnb_pack_amb_records(const gnnb_t* hc, const gnnb_batch* in, int
     int32_t local[BLK * AMBREC_WORDS];
     for (size_t it = next.fetch_add(1); it < items.size(); it = next.fetch_add(1)) {
       const Item& w = items[it];
-      const int k = w.k, q = h->relu_q[k];
-      const float *lb = in->lb[k], *ub = in->ub[k], *du = in->dual[k - 1], *zp = in->primal[q - 1], *zq = in->primal[q];
+      const int k = w.k;
+      const ReluRows r = relu_rows(*h, *in, B, k);
+      const float *lb = r.lb, *ub = r.ub, *du = r.dual, *zp = r.z_pre, *zq = r.z_post;
       int n = 0;
       auto flush = [&]() {
         if (!n) return;
@@ -1451,19 +1445,8 @@ extern "C" int gnnb_pack_amb_records(const gnnb_t* hc, const gnnb_batch* in, int
       flush();
     }
   };
-  if (items.size() >= 8) {
-    if (h->work_pool && h->work_pool->owner != getpid()) h->work_pool = nullptr;      // (after a fork: the parent's threads are not here; its object is left alone)
-    if (!h->work_pool) {                                 // helpers: what the machine (or the cgroup's CPU set) offers, a dozen threads with the caller at most
-      const unsigned hc = std::thread::hardware_concurrency();
-      cpu_set_t set;
-      int avail = (sched_getaffinity(0, sizeof set, &set) == 0) ? CPU_COUNT(&set) : (int)hc;
-      if (avail < 1) avail = hc ? (int)hc : 1;
-      h->work_pool = new WorkPool(std::max(0, std::min(avail, 12) - 1));
-    }
-    h->work_pool->run(work);
-  } else {
-    work();
-  }
+  if (items.size() >= 8) work_pool(h).run(work);
+  else work();
   const size_t total = cursor.load();
   if (overflow.load() || total > max_rec) return fail(GNNB_E_NOMEM, "gnnb_pack_amb_records: %zu records do not fit a buffer of %zu bytes", total, cap);
   memset(img, 0, 64);
@@ -2046,11 +2029,10 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   if (!h->bound) return fail(GNNB_E_STATE, "gnnb_online_step: call gnnb_bind_network first");
   if (!h->trainer) return fail(GNNB_E_STATE, "gnnb_online_step: call gnnb_online_create first");
   const int K = (int)h->N.size() - 1, L = K - 1, R = h->R, T = h->T;
-  if (B < 1 || in->n_graph != K + 1 || in->n_relu != L || in->n_primal < h->n_fixed)
-    return fail(GNNB_E_INVALID, "gnnb_online_step: batch does not match the bound network");
+  if (int rc = refuse_zero_taps(h, "gnnb_online_step")) return rc;
+  if (int rc = refuse_batch(h, in, B, kNeedsOnline, "gnnb_online_step")) return rc;
   for (int b = 0; b < B; ++b)
     if (kw_index[b] < 0 || kw_index[b] >= R) return fail(GNNB_E_INVALID, "gnnb_online_step: kw_index[%d] = %d outside [0, %d)", b, kw_index[b], R);
-  if (int rc = refuse_zero_taps(h, "gnnb_online_step")) return rc;
   // k_tconv lists the valid taps of a destination node in LDS arrays of TCONV_MAXTAPS entries.  Both directions of every conv edge
   // run in a step (A and A^T, forward or as each other's adjoint): a node of A reads at most min(kh, H_in) min(kw, W_in) C_in
   // taps, a node of A^T at most min(ceil(kh / s), H_out) min(ceil(kw / s), W_out) C_out (the taps with (y + pad - ky) % s == 0).
@@ -2106,8 +2088,8 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
       // node lists: the relaxation chains run over the ambiguous nodes, the update chains over the live ones
       int* buf = reinterpret_cast<int*>(t.arena.alloc(2 * n + 2));
       if (t.arena.err || !buf) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
-      const int q = h->relu_q[k];
-      pm.a[k - 1] = TPrepArgs{in->lb[k], in->ub[k], in->dual[k - 1], in->primal[q - 1], in->primal[q], h->dev[k].bias.get(), h->N[k], h->hw[k], n,
+      const ReluRows r = relu_rows(*h, *in, B, k);
+      pm.a[k - 1] = TPrepArgs{r.lb, r.ub, r.dual, r.z_pre, r.z_post, h->dev[k].bias.get(), h->N[k], h->hw[k], n,
                               c.r0, c.r1, c.amb, c.live, c.nd2, c.d1, c.ff, c.fb};
       c.ambl = Trainer::List{buf, buf + 2 * n, n};
       c.livel = Trainer::List{buf + n, buf + 2 * n + 1, n};

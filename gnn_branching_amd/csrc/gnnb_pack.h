@@ -751,6 +751,47 @@ inline std::string parse_layers(const gnnb_layer_desc* L, int n, int c0, int h0,
   return "";
 }
 
+// The rows of ReLU layer k in a batch -- bounds, dual_vars, pre- and post-activation primals -- and their number B N_k.
+struct ReluRows { const float *lb, *ub, *dual, *z_pre, *z_post; long G; };
+inline ReluRows relu_rows(const LayerGraph& g, const gnnb_batch& in, int B, int k) {
+  const int q = g.relu_q[k];
+  return ReluRows{in.lb[k], in.ub[k], in.dual[k - 1], in.primal[q - 1], in.primal[q], (long)B * g.N[k]};
+}
+
+// What an entry point reads of a gnnb_batch beyond the rows of the ReLU layers and primals[-1], which all of them read.
+struct BatchNeeds {
+  bool outer_bounds;    // lb / ub of the input layer and of the property node
+  bool all_primals;     // every primal entry (else: the two of each ReLU layer and the last)
+  bool loose;           // x_lp, prop_w, prop_b, mask
+  bool more_primals;    // n_primal >= n_fixed (gnnb_online_step's rule) instead of == n_fixed + 1
+  int limit;            // 0 none; 1: B N_0 64 < 2^40 (the forward's row offsets); 2: B N_k <= INT_MAX (the packer's record index)
+};
+constexpr BatchNeeds kNeedsForward{true, true, true, false, 1}, kNeedsForwardHost{true, false, true, false, 0},
+    kNeedsPack{false, false, false, false, 2}, kNeedsOnline{true, false, true, true, 0};
+
+// A batch of B subproblems against the bound layer graph.  Returns the refusal, or an empty string: then every count matches, and every
+// table and every entry `need` names is there, so the entry point may index them.
+inline std::string check_batch(const LayerGraph& g, const gnnb_batch& in, int B, const BatchNeeds& need) {
+  const int K = (int)g.N.size() - 1, L = K - 1, NP = g.n_fixed + 1;
+  const char* const no = "the batch does not match the bound network: ";
+  if (B < 1) return strf("%sB = %d", no, B);
+  if (in.n_graph != K + 1 || in.n_relu != L || (need.more_primals ? in.n_primal < NP - 1 : in.n_primal != NP))
+    return strf("%s%d graph layers / %d dual / %d primal tensors, the network has %d / %d / %d", no, in.n_graph, in.n_relu, in.n_primal, K + 1, L, NP);
+  if (!in.lb || !in.ub || !in.dual || !in.primal) return strf("%snull pointer table", no);
+  for (int k = need.outer_bounds ? 0 : 1; k <= (need.outer_bounds ? K : L); ++k)
+    if (!in.lb[k] || !in.ub[k]) return strf("%snull bounds pointer of graph layer %d", no, k);
+  for (int k = 1; k <= L; ++k) {
+    const ReluRows r = relu_rows(g, in, B, k);
+    if (!r.dual || !r.z_pre || !r.z_post) return strf("%snull dual or primal pointer of ReLU layer %d", no, k);
+    if (need.limit == 2 && r.G > 0x7fffffffL) return strf("%sbatch too large", no);
+  }
+  for (int m = need.all_primals ? 0 : in.n_primal - 1; m < in.n_primal; ++m)
+    if (!in.primal[m]) return strf("%snull primal pointer %d", no, m);
+  if (need.loose && (!in.x_lp || !in.prop_w || !in.prop_b || !in.mask)) return strf("%snull x_lp, prop_w, prop_b or mask", no);
+  if (need.limit == 1 && (long)B * g.N[0] * 64 >= (1L << 40)) return strf("%sbatch too large", no);
+  return "";
+}
+
 // Row sums of edge 1 (for a conv: of the taps inside the image): the bias sums of the edge over the all-live input layer, the
 // weights that reach each node added in fp32 in torch-layout order.
 inline std::vector<float> edge1_row_sums(const Edge& e) {

@@ -1,7 +1,7 @@
 // CPU-only test shim for gnnb_pack.h (built with g++ by tests/test_pack_cpu.py).  It exposes the operand-order packs and the
 // gather tables, so that a numpy emulation of the MFMA lane maps can be checked against a plain matmul / torch conv, and the host
 // half of gnnb_bind_network: the layer-list parser with its refusals, the row sums of edge 1, the padded operands of a Linear
-// edge, the packed tile table and zero_tap_layer.
+// edge, the packed tile table and zero_tap_layer; and check_batch, the one check of a gnnb_batch against a layer graph.
 #include "gnnb_pack.h"
 
 static gnnb::Edge conv_edge(const float* w, int c_in, int h_in, int w_in, int c_out, int kh, int kw, int stride, int pad) {
@@ -66,6 +66,17 @@ int gnnb_pt_parse(const gnnb_layer_desc* L, int n, int c0, int h0, int w0, int* 
   }
   rn[0] = g.R; rn[1] = g.n_fixed;
   return K;
+}
+
+// check_batch of `in` against a layer list parse_layers accepts, with the needs of entry point `which` (0 gnnb_forward, 1 gnnb_forward_host,
+// 2 gnnb_pack_amb_records, 3 gnnb_online_step): 1 accepted, 0 refused with the refusal in err, -1 the list is refused
+int gnnb_pt_check_batch(const gnnb_layer_desc* L, int n, int c0, int h0, int w0, const gnnb_batch* in, int B, int which, char* err, size_t err_cap) {
+  gnnb::LayerGraph g;
+  if (which < 0 || which > 3 || !gnnb::parse_layers(L, n, c0, h0, w0, g).empty()) return -1;
+  const gnnb::BatchNeeds needs[4] = {gnnb::kNeedsForward, gnnb::kNeedsForwardHost, gnnb::kNeedsPack, gnnb::kNeedsOnline};
+  const std::string refusal = gnnb::check_batch(g, *in, B, needs[which]);
+  snprintf(err, err_cap, "%s", refusal.c_str());
+  return refusal.empty() ? 1 : 0;
 }
 
 // zero_tap_layer of a layer list parse_layers accepts: the layer (0: none), yx = one of its unread pixels; -1: the list is refused

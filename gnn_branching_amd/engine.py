@@ -5,6 +5,7 @@ network and a workspace per batch size.  Tensors are only carriers of device
 memory here (``data_ptr()``); all arithmetic of the hot path runs in libgnnb.so.
 """
 import collections
+import contextlib
 import ctypes as C
 import time
 
@@ -79,13 +80,81 @@ def f64(t, B, n, what, device):
     return t.view(B, n)
 
 
-def table(ts):
-    """A C array of the tensors' device pointers (None stays None)."""
-    return None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+class _HostBuf:
+    """address + element count of a float32 C-contiguous host buffer (a CPU tensor as it is, or a numpy copy of a python list /
+    array / tensor of another layout); holds the owner alive.  (A decision is ~0.3 ms of device work: numpy views and
+    ``.ctypes`` objects for two dozen small inputs were a tenth of that again.)"""
+    __slots__ = ("ptr", "size", "keep")
+
+    def __init__(self, t):
+        # data_ptr() is taken as a HOST address only of a tensor that lives on the host: a device tensor slipping through
+        # here would be a wild host read inside gnnb_forward_host, so it is copied back by _host instead
+        if torch.is_tensor(t) and t.device.type == "cpu" and t.dtype == torch.float32 and t.is_contiguous() \
+                and not t.requires_grad:
+            self.ptr, self.size, self.keep = t.data_ptr(), t.numel(), t
+        else:
+            a = ScorerEngine._host(t)
+            self.ptr, self.size, self.keep = a.ctypes.data, a.size, a
+
+
+def count(t):
+    """Elements of a tensor, a numpy array or a ``_HostBuf``."""
+    return t.size if type(t) is _HostBuf or isinstance(t, np.ndarray) else t.numel()
 
 
 def ptr(t):
-    return None if t is None else t.data_ptr()
+    """Address of a tensor (of either side), a numpy array or a ``_HostBuf``; None stays None."""
+    if t is None:
+        return None
+    return t.ptr if type(t) is _HostBuf else t.ctypes.data if isinstance(t, np.ndarray) else t.data_ptr()
+
+
+def table(ts):
+    """A C array of the entries' addresses (None stays None); the carriers of the per-decision paths are taken without a call to ``ptr``."""
+    if ts is None:
+        return None
+    return (C.c_void_p * len(ts))(*[t.ptr if type(t) is _HostBuf else t.data_ptr() if type(t) is torch.Tensor else ptr(t) for t in ts])
+
+
+def batch_size(first, prop_layers):
+    """B of the batch whose first tensor is ``first``: one property layer per subproblem."""
+    B = int(first.shape[0])
+    if len(prop_layers) != B:
+        raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
+    return B
+
+
+def check_batch(sizes, R, fixed_layers, B, lbs, ubs, duals=None, prim=None, x_lp=None, mask=None):
+    """THE size rule of a scorer batch: ValueError unless every group given holds what B subproblems on the bound network hold
+    (``sizes``: its graph layers, ``R``: its ReLU nodes, ``fixed_layers``: its layer list).  The groups hold tensors, numpy arrays or
+    ``_HostBuf`` objects; a group that is None is not looked at (``babsr`` has neither duals nor primals).  Needs no GPU and no handle."""
+    ng, npr = len(sizes), len(fixed_layers) + 1
+    bounds = {k: B * n for k, n in enumerate(sizes)}
+    primals, k = {npr - 1: B}, 0                      # primals[q] is the output of network layer q: read on both sides of a ReLU, and the last one
+    for q, l in enumerate(fixed_layers):
+        if type(l) is nn.ReLU:
+            k += 1
+            primals[q - 1] = primals[q] = bounds[k]
+    for what, g, n, want in (("lower_bounds_all[{}]", lbs, ng, bounds), ("upper_bounds_all[{}]", ubs, ng, bounds),
+                             ("dual_vars[{}]", duals, ng - 2, {k: 3 * B * n for k, n in enumerate(sizes[1:-1])}), ("primals[{}]", prim, npr, primals),
+                             ("masks", None if mask is None else [mask], 1, {0: B * R}), ("primal_inputs", None if x_lp is None else [x_lp], 1, {0: bounds[0]})):
+        if g is None:
+            continue
+        if len(g) != n:
+            raise ValueError(f"{what.split('[')[0]}: {len(g)} tensors, expected {n} (a layer graph of {ng} layers, {npr - 1} network layers)")
+        for k, c in want.items():
+            t = g[k]                                  # (count(t), the two carriers of the per-decision paths without the call)
+            if (t.size if type(t) is _HostBuf else t.numel() if type(t) is torch.Tensor else count(t)) != c:
+                raise ValueError(f"{what.format(k)} holds {count(t)} values, expected {c} (a batch of {B})")
+
+
+def make_batch(lbs, ubs, duals, prim, x_lp, mask, pw=None, pb=None):
+    """(gnnb_batch, what must outlive the call) of the named groups: anything ``ptr`` takes, of the side the entry point reads."""
+    tabs = [table(g) for g in (lbs, ubs, duals, prim)]
+    return _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], ptr(x_lp), ptr(pw), ptr(pb), ptr(mask), len(lbs), len(duals), len(prim)), tabs
+
+
+_NO_CONTEXT = contextlib.nullcontext()
 
 
 def _or_reduce(status):
@@ -118,6 +187,9 @@ def _raise_for_status(st):
 
 # a set of child rows given as loose tensors (ScorerEngine.frontier_commit / frontier_commit_jobs)
 _ChildRows = collections.namedtuple("_ChildRows", "mask lb ub infeasible bound alpha beta ubv live")
+# the tensor arguments of GraphNet.forward in check_batch's and make_batch's order; what ScorerEngine._marshal returns (inputs on the device)
+_Inputs = collections.namedtuple("_Inputs", "lbs ubs duals prim x_lp mask")
+_Marshalled = collections.namedtuple("_Marshalled", "B lbs ubs duals prim x_lp mask pw pb")
 
 
 class ForwardResult:
@@ -152,6 +224,45 @@ class ForwardResult:
         return [self.scores[b][self.masks[b] != 0] for b in range(self.scores.shape[0])]
 
 
+def _sent(inp, compact=False):
+    """The tensors of an _Inputs that cross the link whole, in copy order (compact: dual_vars / primals go as records instead)."""
+    return [*inp.lbs, *inp.ubs, *([] if compact else [*inp.duals, *inp.prim]), inp.x_lp, inp.mask]
+
+
+class _FedSlot:
+    """One set of device input buffers of a HostFedPipeline: ``dev`` (an _Inputs of full-size device tensors), ``sent`` (those of it that
+    are copied whole) and ``offs`` (per entry of ``sent`` its offset in the slot's shared small block; None: a tensor of its own).
+    Tensors below ``small_bytes`` share ONE pinned staging block and ONE device block (a copy of a few KB costs ~10 us of the copy
+    queue's time each, tools/hostfed_probe.py: a batch has a dozen of them).  ev_copy: behind the slot's last copies; ev_done: behind
+    the forward that last read it; img_cap / pin_img / dev_img: the record image of a compact slot."""
+
+    def __init__(self, key, host, compact, device, small_bytes):
+        def padded(t):
+            return (t.numel() + 63) & ~63
+        tot = sum(padded(t) for t in _sent(host, compact) if t.numel() * 4 < small_bytes)
+        self.key, self.used, self.offs = key, False, []
+        self.dev_small = torch.empty(max(tot, 1), dtype=torch.float32, device=device)
+        self.pin_small = torch.empty(max(tot, 1), dtype=torch.float32, pin_memory=True)
+        self.pin_np = self.pin_small.numpy()
+        at = 0
+
+        def twin(t, whole=True):
+            nonlocal at
+            if not whole:                      # filled by the scatter (entries of nodes that are never ambiguous are never read: zero, not garbage)
+                return torch.zeros(t.shape, dtype=torch.float32, device=device)
+            if t.numel() * 4 >= small_bytes:
+                self.offs.append(None)
+                return torch.empty(t.shape, dtype=torch.float32, device=device)
+            self.offs.append(at)
+            at += padded(t)
+            return self.dev_small[self.offs[-1]:self.offs[-1] + t.numel()].view(t.shape)
+        self.dev = _Inputs([twin(t) for t in host.lbs], [twin(t) for t in host.ubs], [twin(t, not compact) for t in host.duals],
+                           [twin(t, not compact) for t in host.prim], twin(host.x_lp), twin(host.mask))
+        self.sent = _sent(self.dev, compact)
+        self.ev_copy, self.ev_done = torch.cuda.Event(), torch.cuda.Event()
+        self.img_cap, self.pin_img, self.dev_img = 0, None, None
+
+
 class HostFedPipeline:
     """Cross-batch double buffering for batches that arrive as HOST tensors (the reference pays its host->device copies inside the
     call, graph_score.py:26-30; SURVEY 8(d): "H2D reported separately").
@@ -159,7 +270,7 @@ class HostFedPipeline:
     ``submit(*forward_args)`` enqueues the copies of batch i + 1 on a COPY stream while the forward of batch i runs on the caller's
     stream, and returns that batch's ForwardResult without synchronising: `depth` (2) sets of device input buffers, each guarded by
     two events -- the copy stream waits for the forward that last read a set before overwriting it, the compute stream waits for the
-    set's copies before its forward.  Host tensors are copied straight from where they are, in pieces of 2 MB (see `submit`): from
+    set's copies before its forward.  Host tensors are copied straight from where they are, in pieces of 2 MB (see `_enqueue_copies`): from
     pinned memory the copies are asynchronous DMA that hides under the running forward; from pageable memory the runtime stages them
     (the host blocks per piece, the GPU still overlaps them with the previous forward).
     ``compact`` (default): of ``dual_vars`` and ``primals`` the forward reads only the entries of AMBIGUOUS nodes (and primals[-1]), so those
@@ -177,144 +288,123 @@ class HostFedPipeline:
         self.compact = bool(compact)
         self.link_bytes = 0
         self.copy_stream = torch.cuda.Stream(device=engine.device)
-        self.slots = [None] * self.depth          # per slot: dict(key=shape signature, dev=[tensors], pin=[tensors or None], ev_copy, ev_done)
+        self.slots = [None] * self.depth
         self.i = 0
 
     @staticmethod
-    def _flat_inputs(lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, masks):
-        ts = list(lower_bounds_all) + list(upper_bounds_all) + list(dual_vars) + list(primals) + [primal_inputs, masks]
-        out = []
-        for t in ts:
+    def _inputs(lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, masks):
+        def f32(t):
             if not torch.is_tensor(t):
                 t = torch.tensor(t, dtype=torch.float32)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.to(torch.float32).contiguous()
-            out.append(t)
-        return out
+            return t
+        return _Inputs([f32(t) for t in lower_bounds_all], [f32(t) for t in upper_bounds_all], [f32(t) for t in dual_vars],
+                       [f32(t) for t in primals], f32(primal_inputs), f32(masks))
+
+    def _slot(self, host, compact, B):
+        """The next slot, shaped for this batch and free: its staging block has left the host, the copy stream waits for its last forward."""
+        eng, k = self.eng, self.i % self.depth
+        self.i += 1
+        key = (compact,) + tuple(tuple(t.shape) for t in _sent(host))
+        sl = self.slots[k]
+        if sl is None or sl.key != key:
+            if sl is not None:
+                sl.ev_done.synchronize()
+            sl = self.slots[k] = _FedSlot(key, host, compact, eng.device, self.SMALL)
+            if compact:
+                sl.img_cap = int(eng.lib.gnnb_amb_records_bytes(eng.h, B))
+                sl.pin_img = torch.empty(sl.img_cap // 4, dtype=torch.int32, pin_memory=True)
+                sl.dev_img = torch.empty(sl.img_cap // 4, dtype=torch.int32, device=eng.device)
+        if sl.used:
+            sl.ev_copy.synchronize()                 # the staging block of this set is free again (its last copies have left the host)
+            self.copy_stream.wait_event(sl.ev_done)  # the forward that last read this set has finished
+        return sl
+
+    def _pack(self, sl, host, B):
+        """gnnb_pack_amb_records of the host batch into the slot's pinned image; returns the image's length in words."""
+        eng = self.eng
+        hb, keep = make_batch(*host)
+        used = C.c_size_t(0)
+        _lib.check(eng.lib.gnnb_pack_amb_records(eng.h, C.byref(hb), B, sl.pin_img.data_ptr(), sl.img_cap, C.byref(used)), "gnnb_pack_amb_records")
+        return (used.value + 3) // 4
 
     @staticmethod
-    def _check_sizes(eng, host, nb, nd, npr):
-        """ValueError (not a segfault in the C packer) for tensors that do not hold what the bound network needs."""
-        B, sizes = int(host[0].shape[0]), eng.sizes
-        if nb != len(sizes) or nd != len(sizes) - 2:
-            raise ValueError(f"{nb} bound tensors / {nd} dual tensors, layer graph has {len(sizes)} layers")
-        for k in range(nb):
-            for t, what in ((host[k], "lower"), (host[nb + k], "upper")):
-                if t.numel() != B * sizes[k]:
-                    raise ValueError(f"{what} bounds of graph layer {k}: {tuple(t.shape)} does not hold {B}x{sizes[k]} values")
-        for k in range(nd):
-            if host[2 * nb + k].numel() != B * sizes[k + 1] * 3:
-                raise ValueError(f"dual_vars[{k}] has {tuple(host[2 * nb + k].shape)}, expected ({B * sizes[k + 1]}, 3)")
-        eng._check_primals(eng._net_keepalive, host[2 * nb + nd:2 * nb + nd + npr], B)
-        if host[-1].numel() != B * eng.R:
-            raise ValueError(f"masks has {tuple(host[-1].shape)}, expected ({B}, {eng.R})")
-        if host[-2].numel() != B * sizes[0]:
-            raise ValueError("primal_inputs has the wrong size")
+    def _stage(sl, src):
+        """Host memcpy of the small tensors into the slot's shared staging block (< 1 MB in all)."""
+        for t, o in zip(src, sl.offs):
+            if o is not None and t.device.type == "cpu":
+                sl.pin_np[o:o + t.numel()] = t.reshape(-1).numpy()
+
+    def _enqueue_copies(self, sl, src, used_words, cur):
+        """On the copy stream: the small block, the record image, then every big tensor, in pieces; ev_copy behind them."""
+        dev_src = [t for t in src if t.device.type != "cpu"]
+        if dev_src:
+            # sources that already live on the device (or temporaries _inputs made from them) were produced on the caller's
+            # stream: the copy stream must not read them before that work is done, nor may the allocator recycle them under it
+            self.copy_stream.wait_stream(cur)
+            for t in dev_src:
+                t.record_stream(self.copy_stream)
+        small = [(d, t) for d, t, o in zip(sl.sent, src, sl.offs) if o is not None]
+        with torch.cuda.stream(self.copy_stream):
+            if small:
+                if any(t.device.type != "cpu" for _, t in small):
+                    for d, t in small:
+                        d.copy_(t, non_blocking=True)
+                else:
+                    sl.dev_small.copy_(sl.pin_small, non_blocking=True)
+            for o in range(0, used_words, self.PIECE):                 # the record image of the ambiguous nodes
+                sl.dev_img[o:min(o + self.PIECE, used_words)].copy_(sl.pin_img[o:min(o + self.PIECE, used_words)], non_blocking=True)
+            for d, t, off in zip(sl.sent, src, sl.offs):
+                if off is not None:
+                    continue
+                # pieces of at most 2 MB: measured on MI355X / ROCm 7.2 (tools/hostfed_probe.py), 21 pinned copies of 1.7 MB on a side
+                # stream hide completely under the forward (0.85 ms with or without them), ONE 36.5 MB copy beside the same forward
+                # takes 3.1 ms.  Pageable tensors go through the runtime's own staging (synchronous for the host, still beside the
+                # previous forward on the GPU); packing them into pinned memory here first cost 10 ms per batch.
+                dv, sv = d.view(-1), t.reshape(-1)
+                for o in range(0, sv.numel(), self.PIECE):
+                    dv[o:o + self.PIECE].copy_(sv[o:o + self.PIECE], non_blocking=True)
+            sl.ev_copy.record(self.copy_stream)
+
+    def _scatter(self, sl, B, cur):
+        """Records -> the slot's full-size dual / primal tensors, one launch in front of the forward.  Returns the status words
+        [forward, scatter]: the scatter raises bit 2 on a foreign / corrupt image."""
+        eng, d = self.eng, sl.dev
+        status = torch.zeros(2, dtype=torch.int32, device=eng.device)
+        _lib.check(eng.lib.gnnb_scatter_amb_records(eng.h, sl.dev_img.data_ptr(), B, table(d.duals), len(d.duals), table(d.prim), len(d.prim),
+                                                    status[1:].data_ptr(), C.c_void_p(cur.cuda_stream)), "gnnb_scatter_amb_records")
+        return status
 
     def submit(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks):
         eng = self.eng
-        host = self._flat_inputs(lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, masks)
-        nb, nd, npr = len(lower_bounds_all), len(dual_vars), len(primals)
-        compact = self.compact and all(t.device.type == "cpu" for t in host)
-        skip = set(range(2 * nb, 2 * nb + nd + npr)) if compact else set()      # dual_vars / primals: records instead of whole tensors
-        key = (compact,) + tuple((tuple(t.shape)) for t in host)
-        k = self.i % self.depth
-        self.i += 1
-        sl = self.slots[k]
+        host = self._inputs(lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, masks)
+        compact = self.compact and all(t.device.type == "cpu" for t in _sent(host))
+        B = int(host.lbs[0].shape[0])
         if compact:
             # the packer walks raw host pointers with the sizes of whatever network the HANDLE is bound to: bind (cached by key) on every
             # submit -- another pipeline or eng.forward on the shared engine may have rebound it since this slot was shaped -- and check every
             # element count against that binding before the C side sees a pointer
-            eng.bind(layers["fixed_layers"], tuple(host[0].shape[1:]))
-            self._check_sizes(eng, host, nb, nd, npr)
+            eng.bind(layers["fixed_layers"], tuple(host.lbs[0].shape[1:]))
+            check_batch(eng.sizes, eng.R, eng._net_keepalive, B, *host)
         with torch.cuda.device(eng.device):
             cur = torch.cuda.current_stream()
-            if sl is None or sl["key"] != key:
-                if sl is not None:
-                    sl["ev_done"].synchronize()
-                # tensors below SMALL bytes share ONE pinned staging block and ONE device block (a copy of a few KB costs ~10 us of the copy
-                # queue's time each, tools/hostfed_probe.py: a batch has a dozen of them); the big ones get their own device tensors
-                small = [j for j, t in enumerate(host) if t.numel() * 4 < self.SMALL and j not in skip]
-                offs, tot = {}, 0
-                for j in small:
-                    offs[j] = tot
-                    tot += (host[j].numel() + 63) & ~63
-                dev_small = torch.empty(max(tot, 1), dtype=torch.float32, device=eng.device)
-                pin_small = torch.empty(max(tot, 1), dtype=torch.float32, pin_memory=True)
-                dev = [dev_small[offs[j]:offs[j] + t.numel()].view(t.shape) if j in offs else torch.empty(t.shape, dtype=torch.float32, device=eng.device)
-                       for j, t in enumerate(host)]
-                sl = {"key": key, "dev": dev, "offs": offs, "dev_small": dev_small, "pin_small": pin_small, "pin_np": pin_small.numpy(),
-                      "ev_copy": torch.cuda.Event(), "ev_done": torch.cuda.Event(), "used": False}
-                if compact:
-                    for j in skip:
-                        dev[j].zero_()                # (entries of nodes that are never ambiguous are never read: zero, not garbage)
-                    cap = int(eng.lib.gnnb_amb_records_bytes(eng.h, int(host[0].shape[0])))
-                    sl["img_cap"] = cap
-                    sl["pin_img"] = torch.empty(cap // 4, dtype=torch.int32, pin_memory=True)
-                    sl["dev_img"] = torch.empty(cap // 4, dtype=torch.int32, device=eng.device)
-                self.slots[k] = sl
-            if sl["used"]:
-                sl["ev_copy"].synchronize()          # the staging block of this set is free again (its last copies have left the host)
-            self.copy_stream.wait_event(sl["ev_done"]) if sl["used"] else None      # the forward that last read this set has finished
-            used_words = 0
-            if compact:
-                B = int(host[0].shape[0])
-                tabs = [(C.c_void_p * n)(*[t.data_ptr() for t in g]) for n, g in
-                        ((nb, host[:nb]), (nb, host[nb:2 * nb]), (nd, host[2 * nb:2 * nb + nd]), (npr, host[2 * nb + nd:2 * nb + nd + npr]))]
-                hb = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], host[-2].data_ptr(), None, None, host[-1].data_ptr(), nb, nd, npr)
-                used = C.c_size_t(0)
-                _lib.check(eng.lib.gnnb_pack_amb_records(eng.h, C.byref(hb), B, sl["pin_img"].data_ptr(), sl["img_cap"], C.byref(used)),
-                           "gnnb_pack_amb_records")
-                used_words = (used.value + 3) // 4
-            offs, pin_np = sl["offs"], sl["pin_np"]
-            for j, o in offs.items():                # (host memcpy of the small tensors into the shared staging block: < 1 MB in all)
-                t = host[j]
-                if t.device.type == "cpu":
-                    pin_np[o:o + t.numel()] = t.reshape(-1).numpy()
-            dev_src = [t for t in host if t.device.type != "cpu"]
-            if dev_src:
-                # sources that already live on the device (or temporaries _flat_inputs made from them) were produced on the caller's
-                # stream: the copy stream must not read them before that work is done, nor may the allocator recycle them under it
-                self.copy_stream.wait_stream(cur)
-                for t in dev_src:
-                    t.record_stream(self.copy_stream)
-            with torch.cuda.stream(self.copy_stream):
-                if offs:
-                    if any(host[j].device.type != "cpu" for j in offs):
-                        for j, o in offs.items():
-                            sl["dev"][j].copy_(host[j], non_blocking=True)
-                    else:
-                        sl["dev_small"].copy_(sl["pin_small"], non_blocking=True)
-                for o in range(0, used_words, self.PIECE):                 # the record image of the ambiguous nodes
-                    sl["dev_img"][o:min(o + self.PIECE, used_words)].copy_(sl["pin_img"][o:min(o + self.PIECE, used_words)], non_blocking=True)
-                for j, t in enumerate(host):
-                    if j in offs or j in skip:
-                        continue
-                    # pieces of at most 2 MB: measured on MI355X / ROCm 7.2 (tools/hostfed_probe.py), 21 pinned copies of 1.7 MB on a side
-                    # stream hide completely under the forward (0.85 ms with or without them), ONE 36.5 MB copy beside the same forward
-                    # takes 3.1 ms.  Pageable tensors go through the runtime's own staging (synchronous for the host, still beside the
-                    # previous forward on the GPU); packing them into pinned memory here first cost 10 ms per batch.
-                    dv, sv = sl["dev"][j].view(-1), t.reshape(-1)
-                    for o in range(0, sv.numel(), self.PIECE):
-                        dv[o:o + self.PIECE].copy_(sv[o:o + self.PIECE], non_blocking=True)
-                sl["ev_copy"].record(self.copy_stream)
-            cur.wait_event(sl["ev_copy"])
-            self.link_bytes = 4 * (used_words + sum(t.numel() for j, t in enumerate(host) if j not in skip))      # what this submit sent over the link
-            d = sl["dev"]
-            status = None
-            if compact:                              # records -> the slot's full-size dual / primal tensors, one launch in front of the forward
-                dptr = (C.c_void_p * nd)(*[t.data_ptr() for t in d[2 * nb:2 * nb + nd]])
-                pptr = (C.c_void_p * npr)(*[t.data_ptr() for t in d[2 * nb + nd:2 * nb + nd + npr]])
-                status = torch.zeros(2, dtype=torch.int32, device=eng.device)      # [forward, scatter]: the scatter raises bit 2 on a foreign / corrupt image
-                _lib.check(eng.lib.gnnb_scatter_amb_records(eng.h, sl["dev_img"].data_ptr(), int(host[0].shape[0]), dptr, nd, pptr, npr,
-                                                            status[1:].data_ptr(), C.c_void_p(cur.cuda_stream)), "gnnb_scatter_amb_records")
-            res = eng.forward(d[:nb], d[nb:2 * nb], d[2 * nb:2 * nb + nd], d[2 * nb + nd:2 * nb + nd + npr], d[-2], layers, d[-1], status=status)
+            sl = self._slot(host, compact, B)
+            used_words = self._pack(sl, host, B) if compact else 0
+            src = _sent(host, compact)
+            self._stage(sl, src)
+            self._enqueue_copies(sl, src, used_words, cur)
+            cur.wait_event(sl.ev_copy)
+            self.link_bytes = 4 * (used_words + sum(t.numel() for t in src))      # what this submit sent over the link
+            status = self._scatter(sl, B, cur) if compact else None
+            d = sl.dev
+            res = eng.forward(d.lbs, d.ubs, d.duals, d.prim, d.x_lp, layers, d.mask, status=status)
             # the result outlives the slot: its mask must not be a view of the slot's device buffer, which the submit `depth` calls
             # later overwrites (a held result's ragged() would then be cut with another batch's mask).  Cloned on the compute stream,
             # behind the copies it waited for and in front of ev_done.
             res.masks = res.masks.clone()
-            sl["ev_done"].record(cur)
-            sl["used"] = True
+            sl.ev_done.record(cur)
+            sl.used = True
         return res
 
 
@@ -411,8 +501,9 @@ class ScorerEngine:
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("gnn_branching_amd needs an AMD GPU (MI355X / gfx950); there is no CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.index is None:             # always with its index: comparisons against a tensor's device mean what they say
+            self.device = torch.device(self.device.type, torch.cuda.current_device())
         self.T, self.p = T, p
         # state_dict None: a handle for the GNN-free entry points only (gnnb_babsr) -- all-zero GNN weights
         blob = state_blob(state_dict) if state_dict is not None else np.zeros(GNN_BLOB_FLOATS, dtype=np.float32)
@@ -553,55 +644,32 @@ class ScorerEngine:
         return self._workspace("dual", B, "gnnb_dual_workspace_bytes")
 
     def _marshal(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks):
-        """Bind the network, move the arguments of GraphNet.forward to the device and validate their sizes."""
+        """Bind the network, move the arguments of GraphNet.forward to the device and validate their sizes: a _Marshalled."""
         fixed = layers["fixed_layers"]
         self.bind(fixed, tuple(lower_bounds_all[0].shape[1:]))
-        B = int(lower_bounds_all[0].shape[0])
-        if len(layers["prop_layers"]) != B:
-            raise ValueError(f"{len(layers['prop_layers'])} property layers for a batch of {B}")
-        lbs = [self._dev(t) for t in lower_bounds_all]
-        ubs = [self._dev(t) for t in upper_bounds_all]
-        duals = [self._dev(t) for t in dual_vars]
-        prim = [self._dev(t) for t in primals]
-        x_lp = self._dev(primal_inputs)
-        mask = self._dev(masks)
-        ng = len(self.sizes)
-        if len(lbs) != ng or len(ubs) != ng:
-            raise ValueError(f"{len(lbs)} bound tensors, layer graph has {ng} layers")
-        for k, (l, u) in enumerate(zip(lbs, ubs)):
-            if l.numel() != B * self.sizes[k] or u.numel() != B * self.sizes[k]:
-                raise ValueError(f"bounds of graph layer {k}: {tuple(l.shape)} does not hold {B}x{self.sizes[k]} values")
-        for k, d in enumerate(duals):
-            if d.numel() != B * self.sizes[k + 1] * 3:
-                raise ValueError(f"dual_vars[{k}] has {tuple(d.shape)}, expected ({B * self.sizes[k + 1]}, 3)")
-        if mask.numel() != B * self.R:
-            raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {self.R})")
-        if x_lp.numel() != B * self.sizes[0]:
-            raise ValueError("primal_inputs has the wrong size")
-        self._check_primals(fixed, prim, B)
-        pw, pb = self._prop(layers["prop_layers"])
-        self._last_bounds = list(zip(lbs, ubs))           # for mu() (inspection)
-        return B, lbs, ubs, duals, prim, x_lp, mask, pw, pb
+        B = batch_size(lower_bounds_all[0], layers["prop_layers"])
+        m = _Marshalled(B, [self._dev(t) for t in lower_bounds_all], [self._dev(t) for t in upper_bounds_all], [self._dev(t) for t in dual_vars],
+                        [self._dev(t) for t in primals], self._dev(primal_inputs), self._dev(masks), *self._prop(layers["prop_layers"]))
+        check_batch(self.sizes, self.R, fixed, B, m.lbs, m.ubs, m.duals, m.prim, m.x_lp, m.mask)
+        self._last_bounds = list(zip(m.lbs, m.ubs))           # for mu() (inspection)
+        return m
 
     def forward(self, lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks, status=None):
         """One gnnb_forward call on the current stream.  status: optional preallocated device int32 tensor; the forward's status word
         goes to element 0, further elements (HostFedPipeline: the scatter launch's word) are left to the caller and OR-ed in by
         ForwardResult.check()."""
-        B, lbs, ubs, duals, prim, x_lp, mask, pw, pb = self._marshal(lower_bounds_all, upper_bounds_all, dual_vars, primals,
-                                                                     primal_inputs, layers, masks)
+        m = self._marshal(lower_bounds_all, upper_bounds_all, dual_vars, primals, primal_inputs, layers, masks)
+        B = m.B
         scores = torch.empty(B, self.R, dtype=torch.float32, device=self.device)
         dec = torch.empty(B, 2, dtype=torch.int32, device=self.device)
         if status is None:
             status = torch.empty(1, dtype=torch.int32, device=self.device)
         elif status.numel() < 1 or status.dtype != torch.int32 or status.device != self.device:
             raise ValueError("forward: `status` must be a device int32 tensor with at least one element")
-        mask2 = mask.view(B, self.R)
-        tabs = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in (lbs, ubs, duals, prim)]
-        batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(),
-                           len(lbs), len(duals), len(prim))
+        batch, keep = make_batch(m.lbs, m.ubs, m.duals, m.prim, m.x_lp, m.mask, m.pw, m.pb)
         ws = self.workspace(B)
         self._call("gnnb_forward", C.byref(batch), B, scores.data_ptr(), dec.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
-        return ForwardResult(scores, dec, status, mask2)
+        return ForwardResult(scores, dec, status, m.mask.view(B, self.R))
 
     # ---- the reference's own call pattern: host tensors, one or two subproblems ---------------------------------
     @staticmethod
@@ -624,21 +692,7 @@ class ScorerEngine:
                 pass
         return np.ascontiguousarray(t, dtype=np.float32)
 
-    class _HostBuf:
-        """address + element count of a float32 C-contiguous host buffer (a CPU tensor as it is, or a numpy copy of a python list /
-        array / tensor of another layout); holds the owner alive.  (A decision is ~0.3 ms of device work: numpy views and
-        ``.ctypes`` objects for two dozen small inputs were a tenth of that again.)"""
-        __slots__ = ("ptr", "size", "keep")
-
-        def __init__(self, t):
-            # data_ptr() is taken as a HOST address only of a tensor that lives on the host: a device tensor slipping through
-            # here would be a wild host read inside gnnb_forward_host, so it is copied back by _host instead
-            if torch.is_tensor(t) and t.device.type == "cpu" and t.dtype == torch.float32 and t.is_contiguous() \
-                    and not t.requires_grad:
-                self.ptr, self.size, self.keep = t.data_ptr(), t.numel(), t
-            else:
-                a = ScorerEngine._host(t)
-                self.ptr, self.size, self.keep = a.ctypes.data, a.size, a
+    _HostBuf = _HostBuf
 
     def _prop_host(self, props):
         """(B, N_L) weights and (B,) biases of the property layers as numpy arrays, cached on the layer objects' identity + version"""
@@ -661,45 +715,19 @@ class ScorerEngine:
         float32 array or None); raises FloatingPointError like ``ForwardResult.check``."""
         fixed = layers["fixed_layers"]
         self.bind(fixed, tuple(lower_bounds_all[0].shape[1:]))
-        B = int(lower_bounds_all[0].shape[0])
-        if len(layers["prop_layers"]) != B:
-            raise ValueError(f"{len(layers['prop_layers'])} property layers for a batch of {B}")
+        B = batch_size(lower_bounds_all[0], layers["prop_layers"])
         HB = self._HostBuf
-        lbs = [HB(t) for t in lower_bounds_all]
-        ubs = [HB(t) for t in upper_bounds_all]
-        duals = [HB(t) for t in dual_vars]
-        prim = [HB(t) for t in primals]
-        x_lp, mask = HB(primal_inputs), HB(masks)
-        ng = len(self.sizes)
-        if len(lbs) != ng or len(ubs) != ng:
-            raise ValueError(f"{len(lbs)} bound tensors, layer graph has {ng} layers")
-        for k, (l, u) in enumerate(zip(lbs, ubs)):
-            if l.size != B * self.sizes[k] or u.size != B * self.sizes[k]:
-                raise ValueError(f"bounds of graph layer {k}: {l.size} values, expected {B}x{self.sizes[k]}")
-        for k, d in enumerate(duals):
-            if d.size != B * self.sizes[k + 1] * 3:
-                raise ValueError(f"dual_vars[{k}] has {d.size} values, expected ({B * self.sizes[k + 1]}, 3)")
-        if mask.size != B * self.R:
-            raise ValueError(f"masks has {mask.size} values, expected ({B}, {self.R})")
-        if x_lp.size != B * self.sizes[0]:
-            raise ValueError("primal_inputs has the wrong size")
-        self._check_primals(fixed, prim, B)
-        pw, pb = self._prop_host(layers["prop_layers"])
-        tabs = [(C.c_void_p * len(g))(*[a.ptr for a in g]) for g in (lbs, ubs, duals, prim)]
-        batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.ptr, pw.ctypes.data, pb.ctypes.data, mask.ptr,
-                           len(lbs), len(duals), len(prim))
+        host = _Inputs([HB(t) for t in lower_bounds_all], [HB(t) for t in upper_bounds_all], [HB(t) for t in dual_vars], [HB(t) for t in primals],
+                       HB(primal_inputs), HB(masks))
+        check_batch(self.sizes, self.R, fixed, B, *host)
+        batch, keep = make_batch(*host, *self._prop_host(layers["prop_layers"]))
         dec = np.empty((B, 2), dtype=np.int32)
         status = np.zeros(1, dtype=np.int32)
         scores = np.empty((B, self.R), dtype=np.float32) if want_scores else None
-        if torch.cuda.current_device() == self._dev_index:
-            st = torch.cuda.current_stream().cuda_stream
+        # (no device context where the current device is already the engine's: this is the BaB loop's per-decision call)
+        with _NO_CONTEXT if torch.cuda.current_device() == self.device.index else torch.cuda.device(self.device):
             rc = self.lib.gnnb_forward_host(self.h, C.byref(batch), B, scores.ctypes.data if want_scores else None, dec.ctypes.data,
-                                            status.ctypes.data, C.c_void_p(st))
-        else:
-            with torch.cuda.device(self.device):
-                st = torch.cuda.current_stream().cuda_stream
-                rc = self.lib.gnnb_forward_host(self.h, C.byref(batch), B, scores.ctypes.data if want_scores else None, dec.ctypes.data,
-                                                status.ctypes.data, C.c_void_p(st))
+                                            status.ctypes.data, C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "gnnb_forward_host")
         _raise_for_status(int(status[0]))
         return dec, scores
@@ -728,20 +756,19 @@ class ScorerEngine:
         indices into the R ReLU nodes, improvement (B).  Returns (loss (B) numpy, scores (B, R) device tensor or None)."""
         if not getattr(self, "_online", False):
             raise RuntimeError("online_step: call online_create first")
-        B, lbs, ubs, duals, prim, x_lp, mask, pw, pb = self._marshal(*args)
+        m = self._marshal(*args)
+        B = m.B
         kw = np.ascontiguousarray(kw_index, dtype=np.int32).reshape(-1)
         imp = np.ascontiguousarray(improvement, dtype=np.float32).reshape(-1)
         if kw.size != B or imp.size != B:
             raise ValueError(f"online_step: {kw.size} KW decisions / {imp.size} improvements for a batch of {B}")
-        mask_host = mask.view(B, self.R).cpu()
+        mask_host = m.mask.view(B, self.R).cpu()
         for b in range(B):
             if not (0 <= kw[b] < self.R) or mask_host[b, kw[b]] == 0:
                 raise IndexError(f"online_step: KW decision {int(kw[b])} of subproblem {b} is not an undecided ReLU of its mask")
         loss = np.empty(B, dtype=np.float32)
         scores = torch.empty(B, self.R, dtype=torch.float32, device=self.device) if want_scores else None
-        tabs = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in (lbs, ubs, duals, prim)]
-        batch = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(),
-                           len(lbs), len(duals), len(prim))
+        batch, keep = make_batch(m.lbs, m.ubs, m.duals, m.prim, m.x_lp, m.mask, m.pw, m.pb)
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream().cuda_stream
             rc = self.lib.gnnb_online_step(self.h, C.byref(batch), B, kw.ctypes.data_as(C.c_void_p), imp.ctypes.data_as(C.c_void_p),
@@ -762,26 +789,13 @@ class ScorerEngine:
         ``forward``; returns a BabsrResult (device tensors, no synchronisation)."""
         fixed = layers["fixed_layers"]
         self.bind(fixed, tuple(lower_bounds_all[0].shape[1:]))
-        B = int(lower_bounds_all[0].shape[0])
-        if len(layers["prop_layers"]) != B:
-            raise ValueError(f"{len(layers['prop_layers'])} property layers for a batch of {B}")
-        ng = len(self.sizes)
-        if len(lower_bounds_all) != ng or len(upper_bounds_all) != ng:
-            raise ValueError(f"{len(lower_bounds_all)} bound tensors, layer graph has {ng} layers")
-        lbs = [self._dev(t) for t in lower_bounds_all]
-        ubs = [self._dev(t) for t in upper_bounds_all]
-        for k, (l, u) in enumerate(zip(lbs, ubs)):
-            if l.numel() != B * self.sizes[k] or u.numel() != B * self.sizes[k]:
-                raise ValueError(f"bounds of graph layer {k}: {tuple(l.shape)} does not hold {B}x{self.sizes[k]} values")
-        mask = self._dev(masks)
-        if mask.numel() != B * self.R:
-            raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {self.R})")
+        B = batch_size(lower_bounds_all[0], layers["prop_layers"])
+        lbs, ubs, mask = [self._dev(t) for t in lower_bounds_all], [self._dev(t) for t in upper_bounds_all], self._dev(masks)
+        check_batch(self.sizes, self.R, fixed, B, lbs, ubs, mask=mask)
         pw, _ = self._prop(layers["prop_layers"])
         scores = torch.empty(B, self.R, dtype=torch.float32, device=self.device)
         icp = torch.empty(B, self.R, dtype=torch.float32, device=self.device)
-        tl = (C.c_void_p * ng)(*[t.data_ptr() for t in lbs])
-        tu = (C.c_void_p * ng)(*[t.data_ptr() for t in ubs])
-        self._call("gnnb_babsr", tl, tu, ng, pw.data_ptr(), mask.data_ptr(), B, scores.data_ptr(), icp.data_ptr())
+        self._call("gnnb_babsr", table(lbs), table(ubs), len(lbs), pw.data_ptr(), mask.data_ptr(), B, scores.data_ptr(), icp.data_ptr())
         return BabsrResult(scores, icp, mask.view(B, self.R), self.sizes[1:-1])
 
     # ---- Wong-Kolter intermediate bounds (lp_producer.LayerGraphLP.kw_bounds for a batch) ------------------------------------
@@ -792,8 +806,7 @@ class ScorerEngine:
         if fixed_layers and type(fixed_layers[0]) is nn.Conv2d and (x_lo.dim() != 4 or x_hi.dim() != 4):
             raise ValueError(f"the first layer is a Conv2d: x_lo / x_hi must be (B, C, H, W) boxes, got {tuple(x_lo.shape)} / {tuple(x_hi.shape)}")
         self.bind(fixed_layers, tuple(x_lo.shape[1:]))
-        if len(prop_layers) != B:
-            raise ValueError(f"{len(prop_layers)} property layers for a batch of {B}")
+        batch_size(x_lo, prop_layers)
         xl, xu = f64(x_lo, B, self.sizes[0], "x_lo", self.device), f64(x_hi, B, self.sizes[0], "x_hi", self.device)
         mask = torch.as_tensor(masks).to(device=self.device, dtype=torch.int8).contiguous()
         if mask.numel() != B * self.R:
@@ -1079,21 +1092,6 @@ class ScorerEngine:
         ws = self._workspace("commit_jobs", max(n, 1), "gnnb_frontier_commit_jobs_workspace_bytes") if workspace is None else workspace
         self._call("gnnb_frontier_commit_jobs", C.byref(st), C.byref(pl), self._rows(slots, n, 1, torch.int32, "slots").data_ptr(), C.byref(ch),
                    float(eps), decision_bound.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel())
-
-    def _check_primals(self, fixed, prim, B):
-        def count(t):
-            return t.numel() if torch.is_tensor(t) else t.size      # (tensors, numpy arrays, _HostBuf)
-        if len(prim) != len(fixed) + 1:
-            raise ValueError(f"{len(prim)} primal tensors for {len(fixed) + 1} network layers")
-        k = 0
-        for q, l in enumerate(fixed):
-            if type(l) is nn.ReLU:
-                k += 1
-                n = B * self.sizes[k]
-                if count(prim[q - 1]) != n or count(prim[q]) != n:
-                    raise ValueError(f"primals[{q - 1}], primals[{q}] must hold {n} values each")
-        if count(prim[-1]) != B:
-            raise ValueError("primals[-1] must hold one value per subproblem")
 
     # ---- inspection (tests / bench) ---------------------------------------------------------
     def mu_rows(self, B, k):

@@ -138,8 +138,10 @@ int gnnb_forward_host(gnnb_t* h, const gnnb_batch* in, int B, float* scores, int
  *                            lb < 0 < ub -- a superset of the nodes the device classifies as ambiguous -- as records {layer, flat index
  *                            b N_k + n, dual[:, 1], dual[:, 2], primal_pre, primal_post} in no particular order, then primals[-1];
  *                            *used = bytes written.  Runs on up to a dozen helper threads that belong to the handle (created on first
- *                            use, joined by gnnb_destroy); calls on one handle are serialised, every tensor's element count is the
- *                            caller's responsibility (B N_k per bound / primal tensor, 3 B N_k per dual tensor of the BOUND network).
+ *                            use under a lock in the handle, shared with gnnb_forward_host's staging, joined by gnnb_destroy); the
+ *                            handle gives them one job at a time, so concurrent packs on one handle take turns.  Every tensor's
+ *                            element count is the caller's responsibility (B N_k per bound / primal tensor, 3 B N_k per dual tensor
+ *                            of the BOUND network); x_lp, prop_w, prop_b and mask are not read and may be NULL.
  *   gnnb_scatter_amb_records DEVICE: one launch on `stream` that writes the records of an image copied to device memory into full-size
  *                            device arrays dual[k] (B N_k, 3) / primal[m] laid out as gnnb_forward expects them; entries of other nodes
  *                            are left as they are (the forward never reads them).  Then call gnnb_forward on those arrays: scores are

@@ -50,7 +50,7 @@ def test_amb_record_image_and_scatter(net, B):
     layer, in index order, with dual[:, 1], dual[:, 2] and the two primals of the node -- and primals[-1]; scattered into poisoned
     full-size arrays, those entries (and only those) carry the batch's values.  LP-like signed duals and decided nodes included."""
     import ctypes as C
-    from gnn_branching_amd import _lib, synth
+    from gnn_branching_amd import _lib, engine as E, synth
     model = make_model("shipped")
     eng = model.engine()
     batch = synth.make_batch(net, B, seed=21)
@@ -59,10 +59,9 @@ def test_amb_record_image_and_scatter(net, B):
     args[2] = [torch.from_numpy(rng.standard_normal(tuple(t.shape)).astype(np.float32)) for t in args[2]]      # duals of either sign
     lbs, ubs, duals, prims, x, layers, mask = args
     eng.bind(layers["fixed_layers"], tuple(lbs[0].shape[1:]))
-    nb, nd, npr = len(lbs), len(duals), len(prims)
-    host = [t.float().contiguous() for t in list(lbs) + list(ubs) + list(duals) + list(prims)]
-    tabs = [(C.c_void_p * n)(*[t.data_ptr() for t in g]) for n, g in ((nb, host[:nb]), (nb, host[nb:2 * nb]), (nd, host[2 * nb:2 * nb + nd]), (npr, host[2 * nb + nd:]))]
-    hb = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], None, None, None, None, nb, nd, npr)
+    nd, npr = len(duals), len(prims)
+    host = [[t.float().contiguous() for t in g] for g in (lbs, ubs, duals, prims)]
+    hb, keep = E.make_batch(*host, None, None)           # (the packer reads neither x_lp nor the mask nor the property rows)
     cap = int(eng.lib.gnnb_amb_records_bytes(eng.h, B))
     img = torch.zeros(cap // 4, dtype=torch.int32)
     used = C.c_size_t(0)
@@ -163,3 +162,58 @@ def test_two_networks_alternate_through_one_engine_and_pipeline():
     bad[2] = [t[:-3] for t in bad[2]]                             # dual_vars three rows short
     with pytest.raises(ValueError):
         pipe.submit(*bad)
+
+
+def device_args(batch, dev):
+    args = batch.forward_args()
+    d = [[t.to(dev) for t in g] if isinstance(g, list) else g for g in args]
+    d[4], d[6] = args[4].to(dev), args[6].to(dev)
+    return d
+
+
+def test_forward_host_stages_through_the_handles_helper_threads():
+    """gnnb_forward_host copies a staging block of 4 MiB or more on the handle's helper threads -- the pool gnnb_pack_amb_records also
+    uses -- and a smaller one on the calling thread.  cifar_base_kw stages ~34.7k floats per sample: B = 32 is past the threshold, B = 2
+    far below it.  Either way scores and decisions are the bits of the device-resident forward, on every call (the pool is reused) and
+    after a compact HostFedPipeline.submit on the same engine (both users share one pool), whose own result stays bit-identical too."""
+    from gnn_branching_amd import engine as E, synth
+    from tests.common import shipped_state
+    eng = E.ScorerEngine(shipped_state())
+    big, small = synth.make_batch("cifar_base_kw", 32, seed=41), synth.make_batch("cifar_base_kw", 2, seed=42)
+    want = {}
+    with torch.no_grad():
+        for b in (big, small):
+            r = eng.forward(*device_args(b, eng.device)).check()
+            want[b.batch_size] = (r.scores.cpu().numpy(), r.decisions.cpu().numpy())
+    # what gnnb_forward_host stages, in 64-float slots: both bounds of every graph layer, the duals, the two primals of every ReLU layer
+    # and primals[-1], the input point, the property rows and the mask (the engine's sizes: nothing of it can silently shrink)
+    def staged_bytes(B):
+        pad = lambda n: (n + 63) & ~63
+        n = sum(2 * pad(B * s) for s in eng.sizes) + sum(pad(3 * B * s) + 2 * pad(B * s) for s in eng.sizes[1:-1]) + pad(B)
+        return 4 * (n + pad(B * eng.sizes[0]) + pad(B * eng.sizes[-2]) + pad(B) + pad(B * eng.R))
+    assert staged_bytes(32) > (4 << 20) > staged_bytes(2)
+
+    def host_calls():
+        for b in (big, small, big, small):
+            dec, scores = eng.forward_host(*b.forward_args(), want_scores=True)
+            assert np.array_equal(scores, want[b.batch_size][0], equal_nan=True) and np.array_equal(dec, want[b.batch_size][1])
+    host_calls()
+    with torch.no_grad():
+        r = E.HostFedPipeline(eng, compact=True).submit(*big.forward_args()).check()
+    assert np.array_equal(r.scores.cpu().numpy(), want[32][0], equal_nan=True) and np.array_equal(r.decisions.cpu().numpy(), want[32][1])
+    host_calls()
+
+
+def test_pipeline_on_an_engine_made_with_an_index_less_device():
+    """ScorerEngine(state, device="cuda") keeps the device WITH its index, so the status tensor the compact pipeline allocates on it
+    passes forward's device check (it used to raise: cuda != cuda:0)."""
+    from gnn_branching_amd import engine as E, synth
+    from tests.common import register_toy_archs, shipped_state
+    register_toy_archs()
+    eng = E.ScorerEngine(shipped_state(), device="cuda")
+    assert eng.device == torch.device("cuda", torch.cuda.current_device())
+    batch = synth.make_batch("toy_single", 2, seed=7)            # one ReLU layer: the smallest network of tests/common.py
+    with torch.no_grad():
+        want = eng.forward(*device_args(batch, eng.device)).check()
+        got = E.HostFedPipeline(eng, compact=True).submit(*batch.forward_args()).check()
+    assert torch.equal(got.scores, want.scores) and torch.equal(got.decisions, want.decisions)

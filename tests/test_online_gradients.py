@@ -594,7 +594,7 @@ def test_sample_with_an_empty_mask():
     """Through the C entry point (ScorerEngine.online_step refuses a KW node outside the mask): B = 2, sample 1's mask empty.
     loss[1] is NaN; loss[0] and the gradient are bit-equal to sample 0 stepped alone."""
     from gnn_branching_amd import _lib
-    from gnn_branching_amd.engine import ScorerEngine
+    from gnn_branching_amd.engine import ScorerEngine, make_batch
     state = state_of("random")
     batch = make("cifar_base_kw", 2, seed=21)
     kws = middle_kw(batch.masks)
@@ -604,12 +604,12 @@ def test_sample_with_an_empty_mask():
     args[6][1] = 0
     eng = ScorerEngine(state)
     eng.online_create()
-    B, lbs, ubs, duals, prim, x_lp, mask, pw, pb = eng._marshal(*args)
+    m = eng._marshal(*args)
+    B = m.B
     kw = np.asarray(kws, np.int32)
     imp = np.asarray([0.1, 0.2], np.float32)
     loss = np.zeros(B, np.float32)
-    tabs = [(C.c_void_p * len(g))(*[t.data_ptr() for t in g]) for g in (lbs, ubs, duals, prim)]
-    cb = _lib.Batch(tabs[0], tabs[1], tabs[2], tabs[3], x_lp.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), len(lbs), len(duals), len(prim))
+    cb, keep = make_batch(m.lbs, m.ubs, m.duals, m.prim, m.x_lp, m.mask, m.pw, m.pb)
     with torch.cuda.device(eng.device):
         rc = eng.lib.gnnb_online_step(eng.h, C.byref(cb), B, kw.ctypes.data_as(C.c_void_p), imp.ctypes.data_as(C.c_void_p),
                                       loss.ctypes.data_as(C.c_void_p), None, 0, C.c_void_p(torch.cuda.current_stream().cuda_stream))

@@ -693,3 +693,65 @@ def test_zero_tap_layer(packlib):
     assert k == 2 and (y, x) == (2, 2)
     assert zero_tap(packlib, [("conv", 8, 8, 2, 3, 0), RELU, ("conv", 8, 8, 3, 1, 1), RELU], (8, 8, 8))[0] == 0      # the same conv as edge 1
     assert zero_tap(packlib, [("conv", 3, 8, 3, 1, 1), RELU, ("conv", 8, 8, 4, 2, 1), RELU], (3, 8, 8))[0] == 0      # a covering conv
+
+
+# ---- the one check of a gnnb_batch against a layer graph (gnnb_pack.h check_batch) ----
+# conv 3 -> 8 4x4 stride 2 pad 1 on 3x8x8, ReLU, flatten, Linear 128 -> 33, ReLU (tools/bind_host_sanitize.cpp): N = [192, 128, 33, 1],
+# 4 bound, 2 dual and 6 primal tensors; the ReLUs are network layers 1 and 4, so primals 0, 1, 3, 4 and the last (5) are read, 2 is not.
+BATCH_SPEC, BATCH_SHAPE = [("conv", 3, 8, 4, 2, 1), RELU, FLAT, ("linear", 128, 33), RELU], (3, 8, 8)
+ENTRY_POINTS = ("gnnb_forward", "gnnb_forward_host", "gnnb_pack_amb_records", "gnnb_online_step")
+ALL, NONE = (True,) * 4, (False,) * 4
+# (case, change to the valid batch, accepted by (forward, forward_host, pack_amb_records, online_step)) -- every verdict written by hand
+BATCH_CASES = [
+    ("valid", {}, ALL),
+    ("B=0", {"B": 0}, NONE),
+    ("n_graph-1", {"n_graph": 3}, NONE), ("n_graph+1", {"n_graph": 5}, NONE),
+    ("n_relu-1", {"n_relu": 1}, NONE), ("n_relu+1", {"n_relu": 3}, NONE),
+    # n_primal: exactly n_fixed + 1 = 6 everywhere but in gnnb_online_step, whose own rule is n_primal >= n_fixed = 5 (it reads the two
+    # primals of every ReLU layer, at most entry n_fixed - 1, and the LAST entry given): 5 is its boundary, 4 is below it
+    ("n_primal-1", {"n_primal": 5}, (False, False, False, True)), ("n_primal+1", {"n_primal": 7}, (False, False, False, True)),
+    ("n_primal-2", {"n_primal": 4}, NONE),
+    ("lb table NULL", {"lb": None}, NONE), ("ub table NULL", {"ub": None}, NONE),
+    ("dual table NULL", {"dual": None}, NONE), ("primal table NULL", {"primal": None}, NONE),
+    # entries: the packer reads only the ReLU layers' rows and primals[-1]; the host form and the online step skip the unread primal
+    ("lb[0] NULL", {"lb": 0}, (False, False, True, False)), ("lb[1] NULL", {"lb": 1}, NONE), ("lb[2] NULL", {"lb": 2}, NONE),
+    ("lb[3] NULL", {"lb": 3}, (False, False, True, False)),
+    ("ub[0] NULL", {"ub": 0}, (False, False, True, False)), ("ub[1] NULL", {"ub": 1}, NONE), ("ub[2] NULL", {"ub": 2}, NONE),
+    ("ub[3] NULL", {"ub": 3}, (False, False, True, False)),
+    ("dual[0] NULL", {"dual": 0}, NONE), ("dual[1] NULL", {"dual": 1}, NONE),
+    ("primal[0] NULL", {"primal": 0}, NONE), ("primal[1] NULL", {"primal": 1}, NONE),
+    ("primal[2] NULL", {"primal": 2}, (False, True, True, True)),
+    ("primal[3] NULL", {"primal": 3}, NONE), ("primal[4] NULL", {"primal": 4}, NONE), ("primal[5] NULL", {"primal": 5}, NONE),
+    ("x_lp NULL", {"x_lp": None}, (False, False, True, False)), ("prop_w NULL", {"prop_w": None}, (False, False, True, False)),
+    ("prop_b NULL", {"prop_b": None}, (False, False, True, False)), ("mask NULL", {"mask": None}, (False, False, True, False)),
+]
+
+
+@pytest.mark.parametrize("case,change,accepted", BATCH_CASES, ids=[c[0].replace(" ", "_") for c in BATCH_CASES])
+def test_check_batch(packlib, case, change, accepted):
+    """A batch with the right counts and every pointer set passes under the needs of each entry point; a batch size below 1, a count that
+    is off, a NULL table and a NULL entry the entry point reads are refused -- before anything is indexed: the tables hold exactly as many
+    entries as the batch says -- and an entry the entry point does not read may be NULL."""
+    from gnn_branching_amd._lib import Batch
+    descs, keep = layer_list(BATCH_SPEC)
+    some = np.zeros(1, np.float32).ctypes.data             # (check_batch looks at no tensor's memory)
+    counts = {"n_graph": 4, "n_relu": 2, "n_primal": 6}
+    counts.update({k: v for k, v in change.items() if k in counts})
+    tabs = {"lb": [some] * counts["n_graph"], "ub": [some] * counts["n_graph"], "dual": [some] * counts["n_relu"], "primal": [some] * counts["n_primal"]}
+    loose = {"x_lp": some, "prop_w": some, "prop_b": some, "mask": some}
+    for name, v in change.items():
+        if name in tabs and v is None:
+            tabs[name] = None
+        elif name in tabs:
+            tabs[name][v] = None
+        elif name in loose:
+            loose[name] = None
+    ctabs = {k: None if t is None else (C.c_void_p * len(t))(*t) for k, t in tabs.items()}
+    batch = Batch(ctabs["lb"], ctabs["ub"], ctabs["dual"], ctabs["primal"], loose["x_lp"], loose["prop_w"], loose["prop_b"], loose["mask"],
+                  counts["n_graph"], counts["n_relu"], counts["n_primal"])
+    err = C.create_string_buffer(512)
+    packlib.gnnb_pt_check_batch.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    for which, (entry, want) in enumerate(zip(ENTRY_POINTS, accepted)):
+        got = packlib.gnnb_pt_check_batch(descs, len(BATCH_SPEC), *BATCH_SHAPE, C.byref(batch), change.get("B", 2), which, err, 512)
+        assert got == int(want), (case, entry, err.value.decode())
+        assert (err.value == b"") == want and (want or err.value.startswith(b"the batch does not match the bound network: "))

@@ -2,7 +2,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DGNNB_PACK_NO_THREADS \
 //       -o /tmp/bind_host_sanitize tools/bind_host_sanitize.cpp && /tmp/bind_host_sanitize
 // It parses one accepted and one refused layer list and builds the row sums of edge 1, the dense operands of a 65 -> 33 Linear
-// edge, a tile table, the zero-tap scan and the fp64 kernels' geometry.  Exit status 0 and "ok" when nothing was flagged.
+// edge, a tile table, the zero-tap scan and the fp64 kernels' geometry, and runs check_batch on an accepted batch and on one refusal of
+// each kind (batch size, count, null table, null entry, null loose pointer).  Exit status 0 and "ok" when nothing was flagged.
 #include <cstdio>
 
 #include "../gnn_branching_amd/csrc/gnnb_pack.h"
@@ -38,6 +39,22 @@ int main() {
   const int zk = zero_tap_layer(g, &y, &x);
   Net net;
   fill_kw_geometry(net, g);
+  // check_batch: N = {192, 128, 33, 1}, five fixed layers -> 4 bound, 2 dual, 6 primal tensors; the checker looks at no tensor's memory
+  const float f = 0.f;
+  const float *four[4] = {&f, &f, &f, &f}, *two[2] = {&f, &f}, *six[6] = {&f, &f, &f, &f, &f, &f}, *hole[6] = {&f, &f, nullptr, &f, &f, &f},
+              *gap[6] = {&f, nullptr, &f, &f, &f, &f};
+  const gnnb_batch fine{four, four, two, six, &f, &f, &f, &f, 4, 2, 6};
+  gnnb_batch count = fine, tab = fine, unread = fine, entry = fine, loose = fine;
+  count.n_relu = 1; tab.dual = nullptr; unread.primal = hole; entry.primal = gap; loose.mask = nullptr;
+  const std::string verdicts[] = {check_batch(g, fine, 2, kNeedsForward), check_batch(g, fine, 0, kNeedsForward), check_batch(g, count, 2, kNeedsPack),
+                                  check_batch(g, tab, 2, kNeedsForwardHost), check_batch(g, unread, 2, kNeedsForward),
+                                  check_batch(g, unread, 2, kNeedsForwardHost), check_batch(g, entry, 2, kNeedsOnline),
+                                  check_batch(g, loose, 2, kNeedsOnline), check_batch(g, loose, 2, kNeedsPack)};
+  const bool accepted[] = {true, false, false, false, false, true, false, false, true};
+  for (int i = 0; i < 9; ++i) {
+    printf("check_batch %d: %s\n", i, verdicts[i].empty() ? "accepted" : verdicts[i].c_str());
+    if (verdicts[i].empty() != accepted[i]) return 4;
+  }
   printf("ok: %zu row sums (corner %g, centre %g), dense images %zu + %zu floats, %zu tiles, zero-tap layer %d, widest ReLU layer %d\n",
          s1.size(), s1[0], s1[5], d.fwd.size(), d.bwd.size(), tt.size(), zk, net.maxNr);
   return s1.size() == 128 && zk == 0 && net.maxNr == 128 ? 0 : 3;

@@ -16,7 +16,7 @@ for B in [int(v) for v in os.environ.get("ONLINE_B", "1,8").split(",")]:
     imps = [0.1] * B
     args = batch.forward_args()
     dev = eng._marshal(*args)          # inputs resident
-    args_dev = (dev[1], dev[2], dev[3], dev[4], dev[5], args[5], dev[6].view(B, -1))
+    args_dev = (dev.lbs, dev.ubs, dev.duals, dev.prim, dev.x_lp, args[5], dev.mask.view(B, -1))
     for _ in range(3):
         eng.online_step(args_dev, kws, imps)
     torch.cuda.synchronize()
