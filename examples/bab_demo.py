@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 | --props 18]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2] [--props 18]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -10,7 +10,9 @@ gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K)
 the rounds run --threshold's control flow on the device: the parents whose GNN split improves the bound by less than
 T get their BaBSR split bounded too, in the same round, and the better pair is kept.  With --props N it
 verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
-the true one, every round's launches serving all the properties in flight; one verdict line per property.
+the true one, every round's launches serving all the properties in flight; one verdict line per property.  --props N with --threshold T runs
+the fall-back for every property (frontier.verify_properties_threshold): each has its own intercept counter and table of
+inefficient points, and one round bounds the second pairs of all the properties' selected parents together.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -43,13 +45,11 @@ def main():
     args = ap.parse_args()
     if args.props is not None and (args.frontier is None or args.props < 1):
         ap.error("--props N needs --frontier K and N >= 1")
-    if args.props is not None and args.threshold is not None:
-        ap.error("--threshold is not available with --props (verify_properties branches on the GNN alone)")
 
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
     if args.props is not None:
-        from gnn_branching_amd.frontier import FrontierJob, verify_properties
+        from gnn_branching_amd.frontier import FrontierJob, verify_properties, verify_properties_threshold
         wrong, jobs, names = [c for c in range(10) if c != 3], [], []
         for j in range(args.props):
             seed, cls = args.seed + j // 9, wrong[j % 9]
@@ -59,9 +59,15 @@ def main():
             names.append(f"seed {seed} class 3 vs {cls}")
         lp = lp_producer.LayerGraphLP(prop, x - args.eps, x + args.eps, bounds="kw_device")
         choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
-        results = verify_properties(choice, prop[:-1], jobs, K=args.frontier, max_rounds=max(1, args.nodes // (2 * args.frontier)), log=lambda s: None)
-        for name, (glb, gub, rounds, bounded, reason) in zip(names, results):
-            print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
+        max_rounds, stats = max(1, args.nodes // (2 * args.frontier)), []
+        if args.threshold is None:
+            results = verify_properties(choice, prop[:-1], jobs, K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+        else:
+            results = verify_properties_threshold(choice, prop[:-1], jobs, args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
+                                                  stats=stats)
+        for j, (name, (glb, gub, rounds, bounded, reason)) in enumerate(zip(names, results)):
+            kw = f"; {stats[j]['kw_bounded']} of {stats[j]['branches']} parents bounded a KW decision, {stats[j]['kw_used']} kept it" if stats else ""
+            print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
         return
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))

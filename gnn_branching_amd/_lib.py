@@ -116,6 +116,11 @@ SYMBOLS = [
      [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_choose", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Children), C.POINTER(Children)] +
      [C.c_void_p] * 4 + [C.c_void_p]),
+    ("gnnb_frontier_fallback_jobs_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_fallback_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_void_p, C.POINTER(Fallback)] + [C.c_void_p] * 14 +
+     [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_choose_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_int] + [C.c_void_p] * 6 +
+     [C.POINTER(Children), C.POINTER(Children)] + [C.c_void_p] * 4 + [C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

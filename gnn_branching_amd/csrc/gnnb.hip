@@ -94,7 +94,7 @@ enum ProfClass {
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
-  PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_COUNT
+  PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -102,7 +102,8 @@ static const char* kProfNames[PC_COUNT] = {
     "k_kw_first", "k_kw_layer", "k_kw_flag", "k_dual_ascent",
     "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store",
     "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs",
-    "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy"};
+    "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
+    "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1907,13 +1908,8 @@ extern "C" size_t gnnb_frontier_fallback_workspace_bytes(const gnnb_t* h, int K)
   return (size_t)K * FC_COUNT * sizeof(int32_t);
 }
 
-extern "C" int gnnb_frontier_fallback(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_fallback* in,
-                                      double* gnn_improvement, int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots,
-                                      int32_t* sel_decisions, int32_t* m, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "gnnb_frontier_fallback";
-  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
-  if (!slots || !in || !gnn_improvement || !kw_decisions || !sel_rows || !sel_slots || !sel_decisions || !m || !workspace)
-    return fail(GNNB_E_INVALID, "%s: null argument", who);
+// The checks gnnb_frontier_fallback and gnnb_frontier_fallback_jobs share on a gnnb_fallback, and its values as the kernels' arguments.
+static int fr_fallback_in(const char* who, const gnnb_fallback* in, FrFallbackArgs* a) {
   if (!in->live || !in->infeasible || !in->bound || !in->scores || !in->intercepts || !in->scorer_mask || !in->icp || !in->ineff ||
       (in->n_order > 0 && !in->random_order))
     return fail(GNNB_E_INVALID, "%s: null array among the inputs", who);
@@ -1921,17 +1917,29 @@ extern "C" int gnnb_frontier_fallback(gnnb_t* h, const gnnb_pool* pool, const in
     return fail(GNNB_E_INVALID, "%s: branching_threshold = %g (0 < . <= 1), kwbd_threshold = %d (>= 0), decision_threshold = %g", who,
                 in->branching_threshold, in->kwbd_threshold, in->decision_threshold);
   if (in->n_order < 0 || in->n_order > MAXL) return fail(GNNB_E_INVALID, "%s: random_order of %d layers (0..%d)", who, in->n_order, MAXL);
+  a->live = in->live; a->infeasible = in->infeasible; a->bound = in->bound;
+  a->scores = in->scores; a->icp_tb = in->intercepts; a->amb = in->scorer_mask;
+  a->branching_threshold = in->branching_threshold; a->decision_threshold = in->decision_threshold;
+  a->kwbd_threshold = in->kwbd_threshold; a->sparsest_layer = in->sparsest_layer; a->n_order = in->n_order;
+  for (int q = 0; q < in->n_order; ++q) a->order[q] = in->random_order[q];
+  a->icp = in->icp; a->ineff = in->ineff;
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_frontier_fallback(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_fallback* in,
+                                      double* gnn_improvement, int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots,
+                                      int32_t* sel_decisions, int32_t* m, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_fallback";
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !in || !gnn_improvement || !kw_decisions || !sel_rows || !sel_slots || !sel_decisions || !m || !workspace)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrFallbackArgs a{};
+  if (int rc = fr_fallback_in(who, in, &a)) return rc;
   const size_t need = gnnb_frontier_fallback_workspace_bytes(h, K);
   if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
-  FrFallbackArgs a{};
   a.s = fr_shape(h);
   if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
-  a.slots = slots; a.K = K; a.live = in->live; a.infeasible = in->infeasible; a.bound = in->bound;
-  a.scores = in->scores; a.icp_tb = in->intercepts; a.amb = in->scorer_mask;
-  a.branching_threshold = in->branching_threshold; a.decision_threshold = in->decision_threshold;
-  a.kwbd_threshold = in->kwbd_threshold; a.sparsest_layer = in->sparsest_layer; a.n_order = in->n_order;
-  for (int q = 0; q < in->n_order; ++q) a.order[q] = in->random_order[q];
-  a.icp = in->icp; a.ineff = in->ineff;
+  a.slots = slots; a.K = K;
   a.gnn_imp = gnn_improvement; a.kw_dec = kw_decisions; a.sel_rows = sel_rows; a.sel_slots = sel_slots; a.sel_dec = sel_decisions; a.m = m;
   a.cand = (int32_t*)workspace;
   hipStream_t st = (hipStream_t)stream;
@@ -1964,6 +1972,94 @@ extern "C" int gnnb_frontier_choose(gnnb_t* h, const gnnb_pool* pool, int K, int
   Launcher run{h, st};
   run.run(PC_FR_CHOOSE, [&] { hipLaunchKernelGGL(k_frontier_choose, dim3(1), dim3(FR_THREADS), 0, st, a); });
   if (m > 0) run.run(PC_FR_CHOOSE_COPY, [&] { hipLaunchKernelGGL(k_frontier_choose_copy, dim3(2 * m, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+// ---- the fall-back for many jobs in one pool: the two steps above per plan entry, on the segment's counter
+// icp[segment] and table ineff[segment]; the selected parents of all entries form one dense list in plan order ----
+struct FrFbWs { size_t st_rows, st_slots, st_dec, m_stage, total; };     // byte offsets in gnnb_frontier_fallback_jobs' workspace: the candidates at 0
+static FrFbWs fr_fb_ws_layout(int n) {
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  FrFbWs w;
+  w.st_rows = up((size_t)n * FC_COUNT * sizeof(int32_t));
+  w.st_slots = w.st_rows + up((size_t)n * sizeof(int32_t));
+  w.st_dec = w.st_slots + up((size_t)n * sizeof(int32_t));
+  w.m_stage = w.st_dec + up((size_t)2 * n * sizeof(int32_t));
+  w.total = w.m_stage + up((size_t)n * sizeof(int32_t));                 // (an entry holds at least one row: n_entries <= n)
+  return w;
+}
+
+extern "C" size_t gnnb_frontier_fallback_jobs_workspace_bytes(const gnnb_t* h, int n) {
+  if (!h || !h->bound || n < 1) return 0;
+  return fr_fb_ws_layout(n).total;
+}
+
+extern "C" int gnnb_frontier_fallback_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_fallback* in,
+                                           const double* seg_x_lo, const double* seg_x_hi, const float* seg_prop_w, const float* seg_prop_b,
+                                           double* gnn_improvement, int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots,
+                                           int32_t* sel_decisions, int32_t* m_entry, double* b_x_lo, double* b_x_hi, float* b_prop_w,
+                                           float* b_prop_b, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_fallback_jobs";
+  FrSelArgs sel{};
+  if (int rc = fr_plan(h, who, plan, pool ? &pool->n_graph : nullptr, &sel.j)) return rc;
+  if (!slots || !in || !seg_x_lo || !seg_x_hi || !seg_prop_w || !seg_prop_b || !gnn_improvement || !kw_decisions || !sel_rows || !sel_slots ||
+      !sel_decisions || !m_entry || !b_x_lo || !b_x_hi || !b_prop_w || !b_prop_b || !workspace)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrFallbackArgs a{};
+  if (int rc = fr_fallback_in(who, in, &a)) return rc;
+  const int n = sel.j.n;
+  const FrFbWs ws = fr_fb_ws_layout(n);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
+  a.s = fr_shape(h);
+  if (int rc = fr_plan_pool(h, who, plan, pool, &a.p)) return rc;
+  char* w = (char*)workspace;
+  int32_t* m_stage = (int32_t*)(w + ws.m_stage);
+  a.slots = slots; a.K = n;
+  a.gnn_imp = gnn_improvement; a.kw_dec = kw_decisions;
+  a.sel_rows = (int32_t*)(w + ws.st_rows); a.sel_slots = (int32_t*)(w + ws.st_slots); a.sel_dec = (int32_t*)(w + ws.st_dec); a.m = nullptr;
+  a.cand = (int32_t*)w;
+  sel.m_stage = m_stage; sel.st_rows = a.sel_rows; sel.st_slots = a.sel_slots; sel.st_dec = a.sel_dec;
+  sel.sel_rows = sel_rows; sel.sel_slots = sel_slots; sel.sel_dec = sel_decisions; sel.m_entry = m_entry;
+  sel.N0 = h->kw_net.N[0]; sel.NL = h->kw_net.N[h->kw_net.L];
+  sel.seg_x_lo = seg_x_lo; sel.seg_x_hi = seg_x_hi; sel.seg_pw = seg_prop_w; sel.seg_pb = seg_prop_b;
+  sel.b_x_lo = b_x_lo; sel.b_x_hi = b_x_hi; sel.b_pw = b_prop_w; sel.b_pb = b_prop_b;
+  const FrPlan j = sel.j;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CANDIDATES, [&] { hipLaunchKernelGGL(k_frontier_candidates, dim3(n), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_FALLBACK_JOBS, [&] { hipLaunchKernelGGL(k_frontier_fallback_jobs, dim3(j.n_entries), dim3(64), 0, st, a, j, m_stage); });
+  run.run(PC_FR_SELECT_JOBS, [&] { hipLaunchKernelGGL(k_frontier_select_jobs, dim3(1), dim3(FR_THREADS), 0, st, sel); });
+  run.run(PC_FR_ROWS_SEL, [&] { hipLaunchKernelGGL(k_frontier_rows_sel, dim3(2 * n, FR_SPLIT), dim3(FR_THREADS), 0, st, sel); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, int M, const int32_t* m_entry,
+                                         const int32_t* sel_rows, const int32_t* sel_slots, const int32_t* sel_decisions,
+                                         const int32_t* gnn_decisions, const double* gnn_improvement, const gnnb_children_rw* pa,
+                                         const gnnb_children* pb, int32_t* ineff, double* kw_improvement, int32_t* used_kw, int32_t* decisions,
+                                         void* stream) {
+  const char* who = "gnnb_frontier_choose_jobs";
+  FrPlan j{};
+  if (plan && plan->n >= 1 && plan->n <= 32767 && (M < 0 || M > plan->n))      // (as K's range: before the handle is looked at)
+    return fail(GNNB_E_INVALID, "%s: M = %d selected parents of n = %d", who, M, plan->n);
+  if (int rc = fr_plan(h, who, plan, pool ? &pool->n_graph : nullptr, &j)) return rc;
+  if (M < 0 || M > j.n) return fail(GNNB_E_INVALID, "%s: M = %d selected parents of n = %d", who, M, j.n);
+  if (!m_entry || !sel_rows || !sel_slots || !sel_decisions || !gnn_decisions || !gnn_improvement || !pa || !ineff || !kw_improvement || !used_kw ||
+      !decisions || (M > 0 && !pb))
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrChooseArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_plan_pool(h, who, plan, pool, &a.p)) return rc;
+  if (M > 0) {
+    if (int rc = fr_children(h, who, pa, pool->n_graph, &a.A)) return rc;
+    if (int rc = fr_children(h, who, pb, pool->n_graph, &a.B)) return rc;
+  }
+  a.K = j.n; a.m = M; a.sel_rows = sel_rows; a.sel_slots = sel_slots; a.sel_dec = sel_decisions; a.gnn_dec = gnn_decisions; a.gnn_imp = gnn_improvement;
+  a.ineff = ineff; a.kw_imp = kw_improvement; a.used = used_kw; a.dec = decisions;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CHOOSE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_choose_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, m_entry); });
+  if (M > 0) run.run(PC_FR_CHOOSE_COPY, [&] { hipLaunchKernelGGL(k_frontier_choose_copy, dim3(2 * M, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 

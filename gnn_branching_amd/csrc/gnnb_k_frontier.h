@@ -1,6 +1,6 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
 // gnnb_frontier_gather, gnnb_frontier_expand, gnnb_net_eval, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
-// a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose).  Between them run the existing batch kernels
+// a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, and their many-job form of section 7.6).  Between them run the existing batch kernels
 // (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched.
 //
 // The POOL is a struct of arrays over `capacity` slots: mask (cap, R) int8, the fp64 bounds of graph layers 1..L+1 (cap, N_k) exactly as
@@ -502,10 +502,10 @@ struct FrChooseArgs {
 };
 static_assert(sizeof(FrFallbackArgs) <= 4096 && sizeof(FrChooseArgs) <= 4096, "kernel arguments: 4 KiB");
 
-// What one job's fall-back sees of a round: its parents' rows [row0, row0 + K) (its dense selection starts at row0 too), its intercept
-// counter, its table of inefficient points, its m.  One job: {0, K, icp, ineff, m}.
+// What one job's fall-back sees of a round: its parents' rows [row0, row0 + K), the first index sel0 of its entries in the dense lists
+// of selected parents, its intercept counter, its table of inefficient points, its m.  One job: {0, K, 0, icp, ineff, m}.
 struct FrFbView {
-  int row0, K;
+  int row0, K, sel0;
   int32_t* icp; int32_t* ineff; int32_t* m;
 };
 
@@ -617,7 +617,7 @@ __device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const 
     a.kw_dec[2L * row] = lay; a.kw_dec[2L * row + 1] = idx;
     int node;
     if (!fr_node(a.s, lay, idx, &node) || !(v.ineff[node] < a.kwbd_threshold)) continue;        // :160-167
-    const int q = v.row0 + m++;
+    const int q = v.sel0 + m++;
     a.sel_rows[q] = row; a.sel_slots[q] = a.slots[row];
     a.sel_dec[2L * q] = lay; a.sel_dec[2L * q + 1] = idx;
   }
@@ -626,11 +626,11 @@ __device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const 
 }
 
 __global__ __launch_bounds__(64) void k_frontier_fallback(FrFallbackArgs a) {
-  const FrFbView v{0, a.K, a.icp, const_cast<int32_t*>(a.ineff), a.m};
+  const FrFbView v{0, a.K, 0, a.icp, const_cast<int32_t*>(a.ineff), a.m};
   fr_fallback_walk(a, v);
 }
 
-// bab_caller.resolve_branching for the view's m selected parents (entries [row0, row0 + m) of the dense lists, pair B's rows 2q, 2q + 1).
+// bab_caller.resolve_branching for the view's m selected parents (entries [sel0, sel0 + m) of the dense lists, pair B's rows 2q, 2q + 1).
 __device__ __forceinline__ void fr_choose(const FrChooseArgs& a, const FrFbView& v, int m) {
   const int tid = threadIdx.x;
   for (int i = tid; i < v.K; i += blockDim.x) {
@@ -641,7 +641,7 @@ __device__ __forceinline__ void fr_choose(const FrChooseArgs& a, const FrFbView&
   }
   __syncthreads();
   for (int j = tid; j < m; j += blockDim.x) {
-    const long q = v.row0 + j;
+    const long q = v.sel0 + j;
     const int row = a.sel_rows[q], s = a.sel_slots[q];
     if (row < v.row0 || row >= v.row0 + v.K || !fr_slot_ok(a.p, s) || !a.B.live[2 * q]) continue;
     const double kw = fr_improvement(fr_child_lb(a.B.infeasible, a.B.bound, 2 * q), fr_child_lb(a.B.infeasible, a.B.bound, 2 * q + 1), a.p.bound[s]);
@@ -655,7 +655,7 @@ __device__ __forceinline__ void fr_choose(const FrChooseArgs& a, const FrFbView&
   __syncthreads();
   if (tid != 0) return;
   for (int j = 0; j < m; ++j) {                         // row order: two parents that name one node both count
-    const long q = v.row0 + j;
+    const long q = v.sel0 + j;
     const int row = a.sel_rows[q], s = a.sel_slots[q];
     int node;
     if (row < v.row0 || row >= v.row0 + v.K || !fr_slot_ok(a.p, s) || !a.B.live[2 * q] || !fr_node(a.s, a.sel_dec[2 * q], a.sel_dec[2 * q + 1], &node)) continue;
@@ -665,7 +665,7 @@ __device__ __forceinline__ void fr_choose(const FrChooseArgs& a, const FrFbView&
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose(FrChooseArgs a) {
-  const FrFbView v{0, a.K, nullptr, a.ineff, nullptr};
+  const FrFbView v{0, a.K, 0, nullptr, a.ineff, nullptr};
   fr_choose(a, v, a.m);
 }
 
@@ -678,4 +678,104 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_copy(FrChooseArg
   if (blockIdx.y == 0 && threadIdx.x == 0) {
     a.A.infeasible[d] = a.B.infeasible[c]; a.A.bound[d] = a.B.bound[c]; a.A.ubv[d] = a.B.ubv[c]; a.A.live[d] = a.B.live[c];
   }
+}
+
+// ---- the fall-back for many jobs in one pool ----------------------------------------------------------------
+// The steps above per plan entry {segment, row0, k}, with the segment's intercept counter icp[segment] and its table ineff[segment]:
+//
+//   * k_frontier_fallback_jobs  one workgroup per entry: fr_fallback_walk on the entry's view.  The selection goes to STAGING lists at
+//                               the entry's own rows ([row0, row0 + m_e)), its number to m_stage[entry]: no entry needs another's count.
+//   * k_frontier_select_jobs    ONE workgroup: m_entry = {m_e per entry, M = their sum}, the exclusive prefix sum sel0 over the entries in
+//                               plan order (each thread a contiguous run of entries, then a serial pass over the FR_THREADS partial sums:
+//                               a fixed order for any number of entries), and entry e's staged selection to [sel0_e, sel0_e + m_e) of the
+//                               dense lists.
+//   * k_frontier_rows_sel       the boxes and property rows of pair B's child rows 2q, 2q + 1 (q < M) from the per-segment tables, by the
+//                               segment of the selected parent's slot.  The grid covers the 2n possible rows; a workgroup with q >= M leaves.
+//   * k_frontier_choose_jobs    one workgroup per entry: fr_choose on the entry's view, its dense range [sel0_e, sel0_e + m_e) from m_entry.
+//
+// k_frontier_candidates and k_frontier_choose_copy run unchanged on global rows (K = n).
+
+struct FrSelArgs {
+  FrPlan j;
+  const int32_t* m_stage; const int32_t* st_rows; const int32_t* st_slots; const int32_t* st_dec;      // staging: (n_entries), (n), (n), (n, 2)
+  int32_t* sel_rows; int32_t* sel_slots; int32_t* sel_dec; int32_t* m_entry;                           // (n), (n), (n, 2), (n_entries + 1)
+  int N0, NL;
+  const double* seg_x_lo; const double* seg_x_hi; const float* seg_pw; const float* seg_pb;            // (S, N_0), (S, N_L), (S)
+  double* b_x_lo; double* b_x_hi; float* b_pw; float* b_pb;                                            // pair B's 2n rows
+};
+static_assert(sizeof(FrFallbackArgs) + sizeof(FrPlan) + sizeof(int32_t*) <= 4096 && sizeof(FrChooseArgs) + sizeof(FrPlan) + sizeof(int32_t*) <= 4096 &&
+              sizeof(FrSelArgs) <= 4096, "kernel arguments: 4 KiB");
+
+__global__ __launch_bounds__(64) void k_frontier_fallback_jobs(FrFallbackArgs a, FrPlan j, int32_t* m_stage) {
+  int seg, row0, k;
+  if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
+  const FrFbView v{row0, k, row0, a.icp + seg, const_cast<int32_t*>(a.ineff) + (long)seg * a.s.R, m_stage + blockIdx.x};
+  fr_fallback_walk(a, v);
+}
+
+// m_e as the walk staged it (0 for an entry the host would have refused) and the entry's first row
+__device__ __forceinline__ int fr_staged(const FrSelArgs& a, int e, int* row0) {
+  int seg, k;
+  if (!fr_entry(a.j, e, &seg, row0, &k)) return 0;
+  return min(max(a.m_stage[e], 0), k);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_select_jobs(FrSelArgs a) {
+  __shared__ int cnt[FR_THREADS + 1];
+  const int tid = threadIdx.x, E = a.j.n_entries;
+  const int per = (E + FR_THREADS - 1) / FR_THREADS, e0 = min(tid * per, E), e1 = min(e0 + per, E);
+  int row0, sum = 0;
+  for (int e = e0; e < e1; ++e) sum += fr_staged(a, e, &row0);
+  cnt[tid + 1] = sum;
+  if (tid == 0) cnt[0] = 0;
+  __syncthreads();
+  if (tid == 0)
+    for (int t = 1; t <= FR_THREADS; ++t) cnt[t] += cnt[t - 1];
+  __syncthreads();
+  int q = cnt[tid];
+  for (int e = e0; e < e1; ++e) {
+    const int m = fr_staged(a, e, &row0);
+    a.m_entry[e] = m;
+    for (int i = 0; i < m && q + i < a.j.n; ++i) {
+      const int p = row0 + i, d = q + i;
+      a.sel_rows[d] = a.st_rows[p]; a.sel_slots[d] = a.st_slots[p];
+      a.sel_dec[2L * d] = a.st_dec[2L * p]; a.sel_dec[2L * d + 1] = a.st_dec[2L * p + 1];
+    }
+    q += m;
+  }
+  if (tid == 0) a.m_entry[E] = min(cnt[FR_THREADS], a.j.n);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_rows_sel(FrSelArgs a) {
+  const int t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int c = blockIdx.x, q = c >> 1;
+  if (q >= a.m_entry[a.j.n_entries]) return;
+  const int s = a.sel_slots[q];
+  if (s < 0 || s / a.j.seg_cap >= a.j.S) return;
+  const int seg = s / a.j.seg_cap;
+  for (int m = t0; m < a.N0; m += dt) {
+    a.b_x_lo[(long)c * a.N0 + m] = a.seg_x_lo[(long)seg * a.N0 + m];
+    a.b_x_hi[(long)c * a.N0 + m] = a.seg_x_hi[(long)seg * a.N0 + m];
+  }
+  for (int m = t0; m < a.NL; m += dt) a.b_pw[(long)c * a.NL + m] = a.seg_pw[(long)seg * a.NL + m];
+  if (t0 == 0) a.b_pb[c] = a.seg_pb[seg];
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_jobs(FrChooseArgs a, FrPlan j, const int32_t* m_entry) {
+  __shared__ int red[FR_THREADS];
+  const int tid = threadIdx.x, e = blockIdx.x;
+  int seg, row0, k;
+  if (!fr_entry(j, e, &seg, &row0, &k)) return;
+  int part = 0;                                         // sel0: the m of the entries before this one (whole numbers: exact in any order)
+  for (int i = tid; i < e; i += FR_THREADS) part += min(max(m_entry[i], 0), j.n);
+  red[tid] = part;
+  __syncthreads();
+  for (int w = FR_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  const int sel0 = red[0];
+  const int m = min(min(max(m_entry[e], 0), k), max(a.m - sel0, 0));      // a.m: M, the host's copy of the sum
+  const FrFbView v{row0, k, sel0, nullptr, a.ineff + (long)seg * a.s.R, nullptr};
+  fr_choose(a, v, m);
 }

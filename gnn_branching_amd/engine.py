@@ -980,6 +980,22 @@ class ScorerEngine:
                    self._rows(scorer_mask, B, R, torch.float32, "scorer_mask").data_ptr(), B,
                    self._rows(scores, B, R, torch.float32, "scores").data_ptr(), self._rows(intercepts, B, R, torch.float32, "intercepts").data_ptr())
 
+    def _fallback(self, K, S, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, branching_threshold, kwbd_threshold, sparsest_layer,
+                  decision_threshold, random_order):
+        """The gnnb_fallback of K parent rows whose counters and tables are S rows long (1: one job; the segments of a plan), and what must
+        outlive the call."""
+        from .lp_producer import _random_order
+        R, i32 = self.R, torch.int32
+        order = list(_random_order(len(self.sizes) - 2, sparsest_layer) if random_order is None else random_order)
+        order_c = (C.c_int32 * max(1, len(order)))(*order)
+        fb = _lib.Fallback(self._rows(live, 2 * K, 1, i32, "live").data_ptr(), self._rows(infeasible, 2 * K, 1, i32, "infeasible").data_ptr(),
+                           self._rows(bound, 2 * K, 1, torch.float64, "bound").data_ptr(), self._rows(scores, K, R, torch.float32, "scores").data_ptr(),
+                           self._rows(intercepts, K, R, torch.float32, "intercepts").data_ptr(),
+                           self._rows(scorer_mask, K, R, torch.float32, "scorer_mask").data_ptr(), float(branching_threshold), float(decision_threshold),
+                           int(kwbd_threshold), int(sparsest_layer), order_c, len(order), self._rows(icp, S, 1, i32, "icp").data_ptr(),
+                           self._rows(ineff, S, R, i32, "ineff").data_ptr())
+        return fb, order_c
+
     def frontier_fallback(self, pool, slots, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, gnn_improvement, kw_decisions,
                           sel_rows, sel_slots, sel_decisions, m, branching_threshold, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001,
                           random_order=None, workspace=None):
@@ -990,18 +1006,11 @@ class ScorerEngine:
         (K, 2), their number m (1,), all int32.  scores / intercepts: ``babsr_rows`` on the parents' rows; icp (1,) int32 the run's
         intercept counter (read and updated), ineff (R,) int32 the counts of inefficient KW points (read).  random_order: the ReLU layers
         popped from the end (None: ``lp_producer._random_order``)."""
-        from .lp_producer import _random_order
         K = int(slots.numel())
         st, keep = self._pool(pool)
-        R, i32 = self.R, torch.int32
-        order = list(_random_order(len(self.sizes) - 2, sparsest_layer) if random_order is None else random_order)
-        order_c = (C.c_int32 * max(1, len(order)))(*order)
-        fb = _lib.Fallback(self._rows(live, 2 * K, 1, i32, "live").data_ptr(), self._rows(infeasible, 2 * K, 1, i32, "infeasible").data_ptr(),
-                           self._rows(bound, 2 * K, 1, torch.float64, "bound").data_ptr(), self._rows(scores, K, R, torch.float32, "scores").data_ptr(),
-                           self._rows(intercepts, K, R, torch.float32, "intercepts").data_ptr(),
-                           self._rows(scorer_mask, K, R, torch.float32, "scorer_mask").data_ptr(), float(branching_threshold), float(decision_threshold),
-                           int(kwbd_threshold), int(sparsest_layer), order_c, len(order), self._rows(icp, 1, 1, i32, "icp").data_ptr(),
-                           self._rows(ineff, R, 1, i32, "ineff").data_ptr())
+        i32 = torch.int32
+        fb, keep_fb = self._fallback(K, 1, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, branching_threshold, kwbd_threshold,
+                                     sparsest_layer, decision_threshold, random_order)
         ws = self._workspace("fallback", K, "gnnb_frontier_fallback_workspace_bytes") if workspace is None else workspace
         self._call("gnnb_frontier_fallback", C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K, C.byref(fb),
                    self._rows(gnn_improvement, K, 1, torch.float64, "gnn_improvement").data_ptr(),
@@ -1092,6 +1101,49 @@ class ScorerEngine:
         ws = self._workspace("commit_jobs", max(n, 1), "gnnb_frontier_commit_jobs_workspace_bytes") if workspace is None else workspace
         self._call("gnnb_frontier_commit_jobs", C.byref(st), C.byref(pl), self._rows(slots, n, 1, torch.int32, "slots").data_ptr(), C.byref(ch),
                    float(eps), decision_bound.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel())
+
+    def frontier_fallback_jobs(self, pool, plan, slots, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, seg_x_lo, seg_x_hi,
+                               seg_prop_w, seg_prop_b, gnn_improvement, kw_decisions, sel_rows, sel_slots, sel_decisions, m_entry, b_x_lo, b_x_hi,
+                               b_prop_w, b_prop_b, branching_threshold, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001, random_order=None,
+                               workspace=None):
+        """gnnb_frontier_fallback_jobs on the current stream: ``frontier_fallback`` per plan entry on its rows with
+        its segment's counter icp[segment] ((segments,) int32) and table ineff[segment] ((segments, R) int32).  gnn_improvement (n,) and
+        kw_decisions (n, 2) by global row; the selected parents of all entries as one dense list in plan order -- sel_rows (global rows),
+        sel_slots (global slots) (n,), sel_decisions (n, 2) -- and m_entry (n_entries + 1,) int32: m per entry, then their sum M.  The
+        boxes and property rows of pair B's rows 2q, 2q + 1 (q < M) go from the seg_* tables to b_x_lo / b_x_hi (2n, N_0), b_prop_w
+        (2n, N_L), b_prop_b (2n,)."""
+        st, keep = self._pool(pool)
+        pl, n, S, E = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), max(int(plan.n_entries), 0)
+        N0, NL, f64, f32, i32 = self.sizes[0], self.sizes[-2], torch.float64, torch.float32, torch.int32
+        fb, keep_fb = self._fallback(n, S, live, infeasible, bound, scores, intercepts, scorer_mask, icp, ineff, branching_threshold, kwbd_threshold,
+                                     sparsest_layer, decision_threshold, random_order)
+        ws = self._workspace("fallback_jobs", max(n, 1), "gnnb_frontier_fallback_jobs_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_frontier_fallback_jobs", C.byref(st), C.byref(pl), self._rows(slots, n, 1, i32, "slots").data_ptr(), C.byref(fb),
+                   self._rows(seg_x_lo, S, N0, f64, "seg_x_lo").data_ptr(), self._rows(seg_x_hi, S, N0, f64, "seg_x_hi").data_ptr(),
+                   self._rows(seg_prop_w, S, NL, f32, "seg_prop_w").data_ptr(), self._rows(seg_prop_b, S, 1, f32, "seg_prop_b").data_ptr(),
+                   self._rows(gnn_improvement, n, 1, f64, "gnn_improvement").data_ptr(), self._rows(kw_decisions, n, 2, i32, "kw_decisions").data_ptr(),
+                   self._rows(sel_rows, n, 1, i32, "sel_rows").data_ptr(), self._rows(sel_slots, n, 1, i32, "sel_slots").data_ptr(),
+                   self._rows(sel_decisions, n, 2, i32, "sel_decisions").data_ptr(), self._rows(m_entry, E + 1, 1, i32, "m_entry").data_ptr(),
+                   self._rows(b_x_lo, 2 * n, N0, f64, "b_x_lo").data_ptr(), self._rows(b_x_hi, 2 * n, N0, f64, "b_x_hi").data_ptr(),
+                   self._rows(b_prop_w, 2 * n, NL, f32, "b_prop_w").data_ptr(), self._rows(b_prop_b, 2 * n, 1, f32, "b_prop_b").data_ptr(),
+                   ws.data_ptr(), ws.numel())
+
+    def frontier_choose_jobs(self, pool, plan, M, m_entry, sel_rows, sel_slots, sel_decisions, gnn_decisions, gnn_improvement, pair_a, pair_b, ineff,
+                             kw_improvement, used_kw, decisions):
+        """gnnb_frontier_choose_jobs on the current stream: ``frontier_choose`` per plan entry on its range of the dense lists
+        (``frontier_fallback_jobs``' outputs; M: the host's copy of m_entry[n_entries]) with ineff[segment] ((segments, R) int32).  pair_a:
+        the 2n child rows, pair_b: the 2M rows bounded for the selected parents.  Writes kw_improvement (n,), used_kw (n,), decisions (n, 2)."""
+        st, keep = self._pool(pool)
+        pl, n, S, E = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), max(int(plan.n_entries), 0)
+        i32, lists = torch.int32, max(int(M), 1)
+        pa, keep_a = self._children(pair_a, 2 * n, "pair_a")
+        pb, keep_b = self._children(pair_b, 2 * lists, "pair_b")
+        self._call("gnnb_frontier_choose_jobs", C.byref(st), C.byref(pl), int(M), self._rows(m_entry, E + 1, 1, i32, "m_entry").data_ptr(),
+                   self._rows(sel_rows, lists, 1, i32, "sel_rows").data_ptr(), self._rows(sel_slots, lists, 1, i32, "sel_slots").data_ptr(),
+                   self._rows(sel_decisions, lists, 2, i32, "sel_decisions").data_ptr(), self._rows(gnn_decisions, n, 2, i32, "gnn_decisions").data_ptr(),
+                   self._rows(gnn_improvement, n, 1, torch.float64, "gnn_improvement").data_ptr(), C.byref(pa), C.byref(pb),
+                   self._rows(ineff, S, self.R, i32, "ineff").data_ptr(), self._rows(kw_improvement, n, 1, torch.float64, "kw_improvement").data_ptr(),
+                   self._rows(used_kw, n, 1, i32, "used_kw").data_ptr(), self._rows(decisions, n, 2, i32, "decisions").data_ptr())
 
     # ---- inspection (tests / bench) ---------------------------------------------------------
     def mu_rows(self, B, k):

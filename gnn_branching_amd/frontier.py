@@ -10,7 +10,7 @@ The rule of a round is ``branch_and_bound``'s, for K domains at once: the childr
 global_ub = min(global_ub, ub of every feasible child), then every child is kept (lb < global_ub - eps, below the decision bound, an
 undecided ReLU left) or closed against that one global_ub.  With K = 1 this is ``branch_and_bound`` with ``child_lp="dual_device"``.
 
-``verify_properties`` runs many JOBS -- a box, a property row, a decision bound, all on one bound network -- through
+``verify_properties`` (``verify_properties_threshold``, section 7.6, with the BaBSR fall-back) runs many JOBS -- a box, a property row, a decision bound, all on one bound network -- through
 the same round of launches: the pool is cut into segments of ``capacity`` slots, a segment holds one job and has its own record, and inside
 its segment a job runs the rule above unchanged, so it gets the result ``branch_and_bound_frontier`` gives it alone, bit for bit.
 """
@@ -172,10 +172,11 @@ class _Round:
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
 
-    def _child_rows(self, n_children, in_shape):
-        """A set of child rows on the children's boxes and property rows.  A second set (pair B of the threshold mode, DESIGN.md section
-        7.5) shares the workspaces: everything is stream-ordered, so the two pairs never use one at the same time."""
-        return _Rows(self.eng, self.fixed, n_children, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb), child=True)
+    def _child_rows(self, n_children, in_shape, box=None):
+        """A set of child rows on the children's boxes and property rows (box: its own, where its rows belong to other jobs than the
+        children's).  A second set (pair B of the threshold mode) shares the workspaces: everything is
+        stream-ordered, so the two pairs never use one at the same time."""
+        return _Rows(self.eng, self.fixed, n_children, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb) if box is None else box, child=True)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -189,7 +190,7 @@ class _Round:
             _lib.check(lib.gnnb_dual_ascent(h, C.byref(Ch.dual_batch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
                                             Ch.bound.data_ptr(), None, None, Ch.t_dual, Ch.t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
-        self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=(self.pw, self.pb), workspace=self.ws_eval)
+        self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_eval)
 
     def _score_parents(self, B):
         """gnnb_dual_ascent at n_iter = 0 (the scorer's inputs at the stored best point: one evaluation of g instead of ~120 KB of fp32
@@ -511,9 +512,15 @@ def _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds):
 class JobsRun(_Round):
     """The device side of ``verify_properties``: a pool of ``segments`` segments of ``cap`` slots with one record each, the jobs' boxes and
     property rows as device tables, and the rows of a round of up to segments * K parents.  ``launch_roots`` / ``launch_round`` are device
-    work only; ``read_state`` is the one synchronising copy."""
+    work only; ``read_state`` is the one synchronising copy.
 
-    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps):
+    With a ``branching_threshold`` (``verify_properties_threshold``) the run also owns, per segment, the intercept
+    counter ``icp`` and the table ``ineff`` of inefficient KW points, a second set of child rows with boxes of its own, and a round reads
+    one more array, ``m_entry`` (``read_selected``), between its two halves."""
+
+    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=10,
+                 sparsest_layer=0, decision_threshold=0.001):
+        _check_threshold(branching_threshold, kwbd_threshold)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
         eng = self.eng = choice.model.engine()
@@ -546,6 +553,24 @@ class JobsRun(_Round):
         self.flags_host = torch.zeros(S, dtype=i32).pin_memory()
         self.flags = torch.zeros(S, dtype=i32, device=dev)
         self.slot_seg = torch.arange(S * cap, device=dev) // cap
+        self.threshold, self.m_e, self.M, self.keep_pairs, self.pair_a = branching_threshold, [0], 0, False, None
+        if branching_threshold is not None:
+            R = eng.R
+            self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
+            self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
+            self.icp, self.ineff = torch.zeros(S, dtype=i32, device=dev), torch.zeros(S, R, dtype=i32, device=dev)
+            # pair B's rows belong to the selected parents' jobs: boxes and property rows of their own (gnnb_frontier_fallback_jobs fills them)
+            self.bx_lo, self.bx_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
+            self.bpw, self.bpb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
+            self.ChB = self._child_rows(2 * n, in_shape, (self.bx_lo, self.bx_hi, self.bpw, self.bpb))
+            self.kw_scores, self.kw_icp = torch.zeros(n, R, dtype=f32, device=dev), torch.zeros(n, R, dtype=f32, device=dev)
+            self.gnn_imp, self.kw_imp = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, dtype=f64, device=dev)
+            self.kw_dec, self.sel_dec, self.dec = (torch.zeros(n, 2, dtype=i32, device=dev) for _ in range(3))
+            self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(n, dtype=i32, device=dev) for _ in range(3))
+            self.m_entry = torch.zeros(S + 1, dtype=i32, device=dev)
+            self.n_used = torch.zeros(S, dtype=torch.int64, device=dev)              # KW pairs taken, per segment since its job was admitted
+            self.job_used = torch.zeros(len(jobs), dtype=torch.int64, device=dev)    # ... per job, once it has left
+            self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_jobs_workspace_bytes(eng.h, n)), dtype=torch.uint8, device=dev)
 
     def release(self, seg):
         """The job of segment ``seg`` leaves: no open slot, the start record."""
@@ -559,6 +584,14 @@ class JobsRun(_Round):
         self.seg_pw[seg].copy_(self.job_pw[job])
         self.seg_pb[seg].copy_(self.job_pb[job])
         self.seg_db[seg].copy_(self.job_db[job])
+        if self.threshold is not None:                            # the job starts with its own counter and table: zero, device-side
+            self.icp[seg].zero_()
+            self.ineff[seg].zero_()
+            self.n_used[seg].zero_()
+
+    def keep_used(self, seg, job):
+        """The job of segment ``seg`` leaves: its count of KW pairs taken, device to device (read once, when the run ends)."""
+        self.job_used[job].copy_(self.n_used[seg])
 
     def _commit(self, n):
         self.eng.frontier_commit_jobs(self.pool, self.plan, self.slots[:n], *self.Ch.children(), self.pool.state, self.seg_db, eps=self.eps,
@@ -605,11 +638,55 @@ class JobsRun(_Round):
         self._score_parents(n)
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(Ch, 2 * n, warm=True)
+        if self.threshold is not None:
+            self._fall_back(n)
         self._commit(n)
 
+    def _fall_back(self, n):
+        """The threshold mode between the bounding of pair A and the commit: BaBSR on the n parent rows, the
+        improvement test and the selection per entry (gnnb_frontier_fallback_jobs), the read of m_entry, and for M > 0 ONE pair B chain
+        for the selected parents of all the jobs and the choice per entry."""
+        P, Ch, ChB, eng, pool = self.P, self.Ch, self.ChB, self.eng, self.pool
+        eng.babsr_rows(P.lb32, P.ub32, self.ppw, P.amb, n, self.kw_scores, self.kw_icp)
+        eng.frontier_fallback_jobs(pool, self.plan, self.slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, P.amb, self.icp, self.ineff,
+                                   self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.gnn_imp, self.kw_dec, self.sel_rows, self.sel_slots,
+                                   self.sel_dec, self.m_entry, self.bx_lo, self.bx_hi, self.bpw, self.bpb, self.threshold, self.kwbd_threshold,
+                                   self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+        if self.keep_pairs:                                       # (a traced run: pair A as it was bounded, before the choice overwrites rows)
+            self.pair_a = (Ch.bound[:2 * n].clone(), Ch.infeasible[:2 * n].clone())
+        self.m_e = self.read_selected()
+        M = self.M = self.m_e[-1]
+        if M == 0:
+            return
+        eng.frontier_expand(pool, self.sel_slots[:M], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
+        self._bound_children(ChB, 2 * M, warm=True)
+        eng.frontier_choose_jobs(pool, self.plan, M, self.m_entry, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff,
+                                 self.kw_imp, self.used_kw, self.dec)
+        self.n_used.index_add_(0, self.row_seg[:n].long(), self.used_kw[:n].long())
+
+    def read_selected(self):
+        """m per plan entry, then their sum M: the 4 (entries + 1) bytes a threshold round reads between its halves."""
+        return self.m_entry[:self.plan.n_entries + 1].cpu().tolist()
+
     def read_state(self):
-        """The (segments, 9) records as lists of Python floats: the one device-to-host copy of a round."""
+        """The (segments, 9) records as lists of Python floats: the one device-to-host copy of a round (of its second half, in threshold
+        mode)."""
         return self.pool.state.cpu().tolist()
+
+
+def _threshold_trace_jobs(run, e, row0, k):
+    """``_threshold_trace`` for entry number ``e`` of the round's plan, rows [row0, row0 + k): its range of the dense lists starts at the
+    sum of the m of the entries before it.  "selected" counts from the entry's first row."""
+    P, ChB, M, m = run.P, run.ChB, run.M, run.m_e[e]
+    a, b, q0 = row0, row0 + k, sum(run.m_e[:e])
+    q1 = q0 + m
+    gnn_dec = P.dec[a:b].cpu().tolist()
+    a_bound, a_inf = run.pair_a
+    return {"gnn_decisions": gnn_dec, "gnn_improvement": run.gnn_imp[a:b].cpu().tolist(), "kw_decisions": run.kw_dec[a:b].cpu().tolist(),
+            "kw_improvement": run.kw_imp[a:b].cpu().tolist() if M else [-1.0] * k, "selected": [r - row0 for r in run.sel_rows[q0:q1].cpu().tolist()],
+            "used_kw": run.used_kw[a:b].cpu().tolist() if M else [0] * k, "decisions": run.dec[a:b].cpu().tolist() if M else gnn_dec,
+            "gnn_child_bounds": a_bound[2 * a:2 * b].cpu().tolist(), "gnn_child_infeasible": a_inf[2 * a:2 * b].cpu().tolist(),
+            "kw_child_bounds": ChB.bound[2 * q0:2 * q1].cpu().tolist(), "kw_child_infeasible": ChB.infeasible[2 * q0:2 * q1].cpu().tolist()}
 
 
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
@@ -627,9 +704,42 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps)
-    F = _lib
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace)
+
+
+def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
+                                max_rounds=50, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001, log=print, trace=None, stats=None):
+    """``verify_properties`` with the BaBSR fall-back below ``branching_threshold`` for every job: every job gets
+    the result ``branch_and_bound_frontier(..., capacity=capacity, branching_threshold=branching_threshold, kwbd_threshold=...,
+    sparsest_layer=..., decision_threshold=...)`` gives it alone, bit for bit, whatever else is in flight, whichever segment it got and
+    whenever it was admitted.
+
+    Every job has its own intercept counter and its own table of inefficient KW points, both zero when it is admitted, read and updated
+    in the job's parent row order within a round and carried from round to round.  A round bounds the second pairs of the selected
+    parents of ALL jobs in one chain of launches, and reads one more array than ``verify_properties``' round: m per plan entry and their
+    sum.  stats: None, or a list that receives per job, in job order, the dict ``branch_and_bound_frontier`` fills ("branches",
+    "kw_bounded", "kw_used", "domains_bounded").  trace: ``verify_properties``' keys per round and per entry plus the keys of the one-job
+    threshold trace ("gnn_decisions", "gnn_improvement", "kw_decisions", "kw_improvement", "selected" -- rows counted from the entry's
+    first --, "used_kw", both pairs' bounds and infeasible flags; "decisions" are the final ones).
+
+    Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
+    if branching_threshold is None:
+        raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
+    _check_threshold(branching_threshold, kwbd_threshold)
+    threshold = {"branching_threshold": branching_threshold, "kwbd_threshold": kwbd_threshold, "sparsest_layer": sparsest_layer,
+                 "decision_threshold": decision_threshold}
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats)
+
+
+def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None):
+    """The loop of ``verify_properties`` and ``verify_properties_threshold`` on checked arguments.  threshold: None, or the threshold mode's
+    arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists."""
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}))
+    run.keep_pairs = trace is not None
+    F, thr = _lib, threshold is not None
     results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
+    branches, kw_bounded = [0] * len(jobs), [0] * len(jobs)
     seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
     waiting = list(range(len(jobs)))
 
@@ -647,6 +757,8 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
                 inf = float("inf")
                 results[j] = (inf, inf, 0, 1, reason) if reason == "infeasible_root" else (_global_lb(rec[s]), rec[s][F.FS_GLOBAL_UB], rounds[j], bounded[j], reason)
                 log(f"job {j} segment {s}: {reason} after {rounds[j]} rounds, lb {results[j][0]:.5f} ub {results[j][1]:.5f}")
+                if thr:
+                    run.keep_used(s, j)
                 run.release(s)
                 seg_job[s], rec[s], capacity_stop[s] = None, None, False
         admitted = []
@@ -674,16 +786,24 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
             run.compact(compact)
         run.launch_round(entries)
         if trace is not None:
-            for s, row0, k in entries:
+            for e, (s, row0, k) in enumerate(entries):
                 trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], **_trace_rows(run, row0, row0 + k)})
+                if thr:
+                    trace[-1].update(_threshold_trace_jobs(run, e, row0, k))
         st = run.read_state()
-        for s, _, k in entries:
+        for e, (s, _, k) in enumerate(entries):
             j = seg_job[s]
             rec[s] = st[s]
             _check_record(rec[s])
             rounds[j] += 1
             bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
+            if thr:                                               # the children of both pairs
+                bounded[j], branches[j], kw_bounded[j] = bounded[j] + 2 * run.m_e[e], branches[j] + k, kw_bounded[j] + run.m_e[e]
             log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
                 f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
     run.check_status()
+    if thr and stats is not None:
+        used = run.job_used.cpu().tolist()
+        stats.extend({"branches": branches[j], "kw_bounded": kw_bounded[j], "domains_bounded": results[j][3], "kw_used": int(used[j])}
+                     for j in range(len(jobs)))
     return results

@@ -378,8 +378,8 @@ typedef struct {
   int32_t sparsest_layer;
   const int32_t* random_order;        /* HOST (n_order): ReLU layers, popped from the end (relu_conv_gnnkwthreshold.py:97-103) */
   int32_t n_order;                    /* 0..8                                                                           */
-  int32_t* icp;                       /* device (1): the intercept counter (icp_score, :119), read and updated          */
-  const int32_t* ineff;               /* device (R): per flat ReLU node how often its KW split was inefficient          */
+  int32_t* icp;                       /* device (1) ((segments) in the jobs form): the intercept counter (:119), read and updated */
+  const int32_t* ineff;               /* device (R) ((segments, R) in the jobs form): how often a node's KW split was inefficient */
 } gnnb_fallback;
 
 /* Per parent row i with a live pair A: gnn_improvement[i] = (min(lbA0, 0) + min(lbA1, 0) - 2 bound) / (-2 bound) in fp64 in that order,
@@ -420,6 +420,41 @@ int gnnb_frontier_choose(gnnb_t* h, const gnnb_pool* pool, int K, int m, const i
                          const int32_t* sel_decisions, const int32_t* gnn_decisions, const double* gnn_improvement,
                          const gnnb_children_rw* pair_a, const gnnb_children* pair_b, int32_t* ineff, double* kw_improvement,
                          int32_t* used_kw, int32_t* decisions, void* stream);
+
+/* ---- the fall-back for many jobs in one pool (gnn_branching_amd/frontier.py verify_properties_threshold) ----
+ * The two steps above per plan entry {segment, row0, k} of a gnnb_plan: every job has its own intercept counter and its own table of
+ * inefficient points, so in the gnnb_fallback of these entry points icp is device (segments) and ineff device (segments, R) (both the
+ * caller zeroes when a job takes a segment); the thresholds, sparsest_layer and random_order are the run's, the same for every job.  Per
+ * entry the result is exactly gnnb_frontier_fallback's / gnnb_frontier_choose's on the rows [row0, row0 + k) with icp[segment] and
+ * ineff[segment]: nothing mixes two entries, and a segment without an entry is not touched.  Refused with GNNB_E_INVALID before any launch:
+ * everything the plan checks of section 7.4 refuse, gnnb_frontier_fallback's argument and range checks, M < 0 or M > n, a null array, a
+ * network past the 4096-node cap; GNNB_E_STATE before gnnb_bind_network, GNNB_E_NOMEM for a short workspace.  Stream-ordered, no
+ * allocation, no synchronisation, no atomics, no kernel waits on another workgroup; the prefix over the entries is a fixed order.
+ *
+ * gnnb_frontier_fallback_jobs: slots (n) global slot numbers; in: pair A's 2n rows, the parents' n rows of scores / intercepts /
+ * scorer_mask.  gnn_improvement (n) and kw_decisions (n, 2) are indexed by global row.  The selected parents of all entries form ONE dense
+ * list, in plan-entry order and within an entry in row order: sel_rows (n) holds GLOBAL rows, sel_slots (n) global slots, sel_decisions
+ * (n, 2) the KW decisions; entry e occupies [sel0_e, sel0_e + m_e), sel0 the exclusive prefix sum of m over the entries in plan order.
+ * m_entry: device (n_entries + 1) int32, m_e per entry, then M = their sum.  Entries of the lists from M on are not written.  The boxes
+ * and property rows of pair B's child rows 2q and 2q + 1 (q < M) are copied from seg_x_lo / seg_x_hi (segments, N_0), seg_prop_w
+ * (segments, N_L), seg_prop_b (segments) by the selected parent's segment into b_x_lo / b_x_hi (2n, N_0), b_prop_w (2n, N_L), b_prop_b
+ * (2n): the host needs M (one read of m_entry) only for the launches behind -- gnnb_frontier_expand with K = M on (sel_slots,
+ * sel_decisions), gnnb_kw_bounds / gnnb_dual_ascent / gnnb_net_eval with B = 2M -- and launches none of them, nor the choice, with M = 0. */
+size_t gnnb_frontier_fallback_jobs_workspace_bytes(const gnnb_t* h, int n);
+int gnnb_frontier_fallback_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_fallback* in,
+                                const double* seg_x_lo, const double* seg_x_hi, const float* seg_prop_w, const float* seg_prop_b,
+                                double* gnn_improvement, int32_t* kw_decisions, int32_t* sel_rows, int32_t* sel_slots, int32_t* sel_decisions,
+                                int32_t* m_entry, double* b_x_lo, double* b_x_hi, float* b_prop_w, float* b_prop_b, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* gnnb_frontier_choose per entry on its m_e selected parents (its range of the dense lists, pair_b's rows 2q, 2q + 1) with ineff[segment]
+ * (ineff: device (segments, R)), updated by one thread in row order; then pair B's rows are copied over pair A's for the parents that took
+ * the KW pair.  M: the host's copy of m_entry[n_entries]; pair_a: the 2n rows; pair_b: 2M rows (not read with M = 0).  Writes
+ * kw_improvement (n), used_kw (n) and decisions (n, 2) for every row of every entry. */
+int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, int M, const int32_t* m_entry, const int32_t* sel_rows,
+                              const int32_t* sel_slots, const int32_t* sel_decisions, const int32_t* gnn_decisions,
+                              const double* gnn_improvement, const gnnb_children_rw* pair_a, const gnnb_children* pair_b, int32_t* ineff,
+                              double* kw_improvement, int32_t* used_kw, int32_t* decisions, void* stream);
 
 int gnnb_destroy(gnnb_t* h);
 
