@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2] [--props 18]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -8,7 +8,9 @@ below T makes the loop ask the BaBSR heuristic too (on the device), bound its ch
 --frontier K keeps the open domains in device memory and expands the K of lowest bound per round (gnn_branching_amd/frontier.py): bounds by
 gnnb_kw_bounds and 20 steps of gnnb_dual_ascent, GNN decisions, --nodes // (2 K) rounds at least one; no LP is solved.  With --threshold T
 the rounds run --threshold's control flow on the device: the parents whose GNN split improves the bound by less than
-T get their BaBSR split bounded too, in the same round, and the better pair is kept.  With --props N it
+T get their BaBSR split bounded too, in the same round, and the better pair is kept.  With --online N on top the
+run also learns, as plnn/relu_conv_online.py does: a GNN decision that lost to BaBSR's N times makes its parent a learn row, and the round
+takes one Adam step over its learn rows on the device.  With --props N it
 verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
 the true one, every round's launches serving all the properties in flight; one verdict line per property.  --props N with --threshold T runs
 the fall-back for every property (frontier.verify_properties_threshold): each has its own intercept counter and table of
@@ -41,10 +43,13 @@ def main():
                     help="intermediate bounds: host fp64 Wong-Kolter, interval arithmetic, or Wong-Kolter on the GPU (gnnb_kw_bounds)")
     ap.add_argument("--threshold", type=float, default=None, help="branching_threshold of the GNN + KW fall-back loop (the reference uses 0.2)")
     ap.add_argument("--frontier", type=int, default=None, metavar="K", help="device-resident frontier: expand the K most promising domains per round")
+    ap.add_argument("--online", type=int, default=None, metavar="N", help="with --frontier K --threshold T: learn online, online_threshold N (the reference uses 5)")
     ap.add_argument("--props", type=int, default=None, metavar="N", help="with --frontier: verify N properties (seeds x wrong classes) in one frontier")
     args = ap.parse_args()
     if args.props is not None and (args.frontier is None or args.props < 1):
         ap.error("--props N needs --frontier K and N >= 1")
+    if args.online is not None and (args.frontier is None or args.threshold is None or args.props is not None or args.online < 1):
+        ap.error("--online N needs --frontier K --threshold T, N >= 1, and no --props (the jobs of one pool share one GNN)")
 
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
@@ -74,13 +79,17 @@ def main():
     if args.frontier is not None:
         from gnn_branching_amd.frontier import branch_and_bound_frontier
         lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device")
-        choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        if args.online is not None:
+            from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice
+        choice = (GraphChoice if args.online is None else OnlineGraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         stats = {}
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
-                                                                      branching_threshold=args.threshold, stats=stats)
+                                                                      branching_threshold=args.threshold, stats=stats, online_threshold=args.online)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
+        if args.online is not None:
+            kw += f"; {stats['online_steps']} learning steps over {stats['online_rows']} learn rows"
         print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)

@@ -121,6 +121,7 @@ SYMBOLS = [
      [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_choose_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_int] + [C.c_void_p] * 6 +
      [C.POINTER(Children), C.POINTER(Children)] + [C.c_void_p] * 4 + [C.c_void_p]),
+    ("gnnb_frontier_learn", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -128,6 +129,8 @@ SYMBOLS = [
     ("gnnb_online_create", C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     ("gnnb_online_step", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p]),
+    ("gnnb_online_step_rows", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p]),
     ("gnnb_online_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("gnnb_last_error", C.c_char_p, []),
     ("gnnb_abi_version", C.c_int, []),

@@ -94,7 +94,8 @@ enum ProfClass {
   PC_NODE_UPDATE, PC_INPUT_UPDATE, PC_SCORE, PC_ARGMAX, PC_GATHER, PC_GATHER_INPUT, PC_CLASSIFY, PC_LIVESUM, PC_TOP, PC_GATHER_UPDATE,
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
-  PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS, PC_COUNT
+  PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS,
+  PC_FR_LEARN, PC_TROWS_GATHER, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -103,7 +104,8 @@ static const char* kProfNames[PC_COUNT] = {
     "k_frontier_gather", "k_frontier_expand", "k_net_eval", "k_frontier_resolve", "k_frontier_decide", "k_frontier_store",
     "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs",
     "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
-    "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs"};
+    "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs",
+    "k_frontier_learn", "k_trows_gather"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -2063,6 +2065,27 @@ extern "C" int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const
   return run.rc;
 }
 
+// ---- the learn rows of an online round (reference plnn/relu_conv_online.py:183-207) ----
+extern "C" int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decisions, const int32_t* kw_decisions, const int32_t* used_kw,
+                                   const double* gnn_improvement, const double* kw_improvement, int online_threshold, int32_t* wrong,
+                                   int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* n_learn, void* stream) {
+  const char* who = "gnnb_frontier_learn";
+  const int ng = h && h->bound ? h->kw_net.L + 2 : 0;
+  if (int rc = frontier_preflight(h, who, K, &ng)) return rc;
+  if (online_threshold < 1) return fail(GNNB_E_INVALID, "%s: online_threshold = %d (>= 1)", who, online_threshold);
+  if (!gnn_decisions || !kw_decisions || !used_kw || !gnn_improvement || !kw_improvement || !wrong || !learn_rows || !learn_kw || !learn_imp || !n_learn)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrLearnArgs a{};
+  a.s = fr_shape(h);
+  a.K = K; a.gnn_dec = gnn_decisions; a.kw_dec = kw_decisions; a.used = used_kw; a.gnn_imp = gnn_improvement; a.kw_imp = kw_improvement;
+  a.online_threshold = online_threshold;
+  a.wrong = wrong; a.learn_rows = learn_rows; a.learn_kw = learn_kw; a.learn_imp = learn_imp; a.n_learn = n_learn;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_LEARN, [&] { hipLaunchKernelGGL(k_frontier_learn, dim3(1), dim3(64), 0, st, a); });
+  return run.rc;
+}
+
 
 // ================================================================================================================
 // Online learning (reference graphnet/graph_score_online.py:9-23, :62-77)
@@ -2112,23 +2135,14 @@ extern "C" int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats) {
   return GNNB_OK;
 }
 
-// One GraphChoice.online_learning step (graph_score_online.py:62-77) for B subproblems (the reference: B = 1):
-//   loss = sum_b ( max_j scores_b[j] - scores_b[kw_b] + improvement_b );  backward;  Adam step;  scorer packs rebuilt.
-// in: the batch exactly as for gnnb_forward.  kw_index (HOST, B): the KW decision as a flat index into the R ReLU nodes
-// (trans_len[lay-1] + idx, :63-67), which must be an undecided node of the mask.  improvement (HOST, B).  loss (HOST, B,
-// may be NULL).  scores_padded (DEVICE (B, R), may be NULL): the scores of the training-form forward BEFORE the update.
-// apply = 0: gradient only (gnnb_online_grad), the parameters and the Adam state stay as they are.
-extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_index, const float* improvement,
-                                float* loss, float* scores_padded, int apply, void* stream) {
+// What gnnb_online_step and gnnb_online_step_rows check of the handle and of a batch of B before anything is launched.
+static int online_preflight(gnnb_t* h, const gnnb_batch* in, int B, const char* who) {
   using namespace gnnb_train;
-  if (!h || !in || !kw_index || !improvement) return fail(GNNB_E_INVALID, "gnnb_online_step: null argument");
-  if (!h->bound) return fail(GNNB_E_STATE, "gnnb_online_step: call gnnb_bind_network first");
-  if (!h->trainer) return fail(GNNB_E_STATE, "gnnb_online_step: call gnnb_online_create first");
-  const int K = (int)h->N.size() - 1, L = K - 1, R = h->R, T = h->T;
-  if (int rc = refuse_zero_taps(h, "gnnb_online_step")) return rc;
-  if (int rc = refuse_batch(h, in, B, kNeedsOnline, "gnnb_online_step")) return rc;
-  for (int b = 0; b < B; ++b)
-    if (kw_index[b] < 0 || kw_index[b] >= R) return fail(GNNB_E_INVALID, "gnnb_online_step: kw_index[%d] = %d outside [0, %d)", b, kw_index[b], R);
+  if (!h->bound) return fail(GNNB_E_STATE, "%s: call gnnb_bind_network first", who);
+  if (!h->trainer) return fail(GNNB_E_STATE, "%s: call gnnb_online_create first", who);
+  const int L = (int)h->N.size() - 2;
+  if (int rc = refuse_zero_taps(h, who)) return rc;
+  if (int rc = refuse_batch(h, in, B, kNeedsOnline, who)) return rc;
   // k_tconv lists the valid taps of a destination node in LDS arrays of TCONV_MAXTAPS entries.  Both directions of every conv edge
   // run in a step (A and A^T, forward or as each other's adjoint): a node of A reads at most min(kh, H_in) min(kw, W_in) C_in
   // taps, a node of A^T at most min(ceil(kh / s), H_out) min(ceil(kw / s), W_out) C_out (the taps with (y + pad - ky) % s == 0).
@@ -2139,16 +2153,30 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
     const long fwd = (long)lim(e.kh, e.h_in) * lim(e.kw, e.w_in) * e.c_in;
     const long bwd = (long)lim((e.kh + e.stride - 1) / e.stride, e.h_out) * lim((e.kw + e.stride - 1) / e.stride, e.w_out) * e.c_out;
     if (fwd > TCONV_MAXTAPS || bwd > TCONV_MAXTAPS)
-      return fail(GNNB_E_INVALID, "gnnb_online_step: the convolution into ReLU layer %d (%dx%d stride %d, %d -> %d channels) gives a node up to %ld taps, "
-                  "the training kernels hold %d", k, e.kh, e.kw, e.stride, e.c_in, e.c_out, fwd > bwd ? fwd : bwd, TCONV_MAXTAPS);
+      return fail(GNNB_E_INVALID, "%s: the convolution into ReLU layer %d (%dx%d stride %d, %d -> %d channels) gives a node up to %ld taps, "
+                  "the training kernels hold %d", who, k, e.kh, e.kw, e.stride, e.c_in, e.c_out, fwd > bwd ? fwd : bwd, TCONV_MAXTAPS);
   }
+  if (L > T_MAXL) return fail(GNNB_E_INVALID, "%s: more than %d ReLU layers", who, T_MAXL);
+  return GNNB_OK;
+}
+
+// One GraphChoice.online_learning step (graph_score_online.py:62-77) for B subproblems (the reference: B = 1):
+//   loss = sum_b ( max_j scores_b[j] - scores_b[kw_b] + improvement_b );  backward;  Adam step;  scorer packs rebuilt.
+// The body gnnb_online_step and gnnb_online_step_rows share, behind online_preflight.  in: the batch exactly as for gnnb_forward.
+// d_kw (DEVICE, B): the KW decision as a flat index into the R ReLU nodes (trans_len[lay-1] + idx, :63-67); d_imp (DEVICE, B).
+// loss_host (B) / loss_dev (B) / scores_padded (DEVICE (B, R): the scores of the training-form forward BEFORE the update) / status
+// (DEVICE int32[1], k_tloss's bit 3) may be NULL.  apply = 0: gradient only (gnnb_online_grad), the parameters and the Adam state stay
+// as they are.  arena_ready: the caller has reset the trainer's arena and holds buffers from it (the gathered rows).
+static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* d_kw, const float* d_imp, float* loss_host, float* loss_dev,
+                              float* scores_padded, int32_t* status, int apply, hipStream_t st, bool arena_ready, const char* who) {
+  using namespace gnnb_train;
+  const int K = (int)h->N.size() - 1, L = K - 1, R = h->R, T = h->T;
   Trainer& t = *h->trainer;
-  hipStream_t st = (hipStream_t)stream;
   t.st = st;
   t.n_cu = h->n_cu;
   t.tape.clear();
   t.ndesc = 0;
-  if (t.arena.reset(st)) return fail(GNNB_E_HIP, "gnnb_online_step: arena reset failed");
+  if (!arena_ready && t.arena.reset(st)) return fail(GNNB_E_HIP, "%s: arena reset failed", who);
   if (h->edge_w.empty()) {                                 // torch-layout copies of the verified network's weights: they belong to the bound network
     std::vector<DevBuf<float>> ew(h->edges.size());
     for (int k = 1; k <= L; ++k) HIPCHK(ew[k].upload(h->edges[k].w.data(), h->edges[k].w.size()));
@@ -2158,18 +2186,13 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   HIPCHK(t.d_scores.grow((size_t)B * R));
   HIPCHK(t.d_ds.grow((size_t)B * R));
   HIPCHK(t.d_loss.grow(B));
-  HIPCHK(t.d_imp.grow(B));
-  HIPCHK(t.d_kw.grow(B));
   float *const d_w = t.d_w.get(), *const d_g = t.d_g.get(), *const d_scores = t.d_scores.get(), *const d_ds = t.d_ds.get();
-  HIPCHK(hipMemcpyAsync(t.d_kw.get(), kw_index, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(t.d_imp.get(), improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d_ds, 0, (size_t)B * R * 4, st));
   HIPCHK(hipMemsetAsync(d_g, 0, blob_floats() * 4, st));
 
   // ---- per-node constants ----
   struct LC { float *r0, *r1, *amb, *live, *nd2, *d1, *ff, *fb; Trainer::List ambl, livel; };
   std::vector<LC> lc(L + 1);
-  if (L > T_MAXL) return fail(GNNB_E_INVALID, "gnnb_online_step: more than %d ReLU layers", T_MAXL);
   {
     TPrepMulti pm{};
     TCompactMulti cm{};
@@ -2183,7 +2206,7 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
       c.fb = t.arena.alloc(7 * n);
       // node lists: the relaxation chains run over the ambiguous nodes, the update chains over the live ones
       int* buf = reinterpret_cast<int*>(t.arena.alloc(2 * n + 2));
-      if (t.arena.err || !buf) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
+      if (t.arena.err || !buf) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
       const ReluRows r = relu_rows(*h, *in, B, k);
       pm.a[k - 1] = TPrepArgs{r.lb, r.ub, r.dual, r.z_pre, r.z_post, h->dev[k].bias.get(), h->N[k], h->hw[k], n,
                               c.r0, c.r1, c.amb, c.live, c.nd2, c.d1, c.ff, c.fb};
@@ -2330,22 +2353,23 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
       hipLaunchKernelGGL(k_tscore_bwd_w, dim3(1), dim3(64), 0, st, sm, L);
     });
   }
-  if (t.arena.err) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
+  if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
   if (scores_padded) HIPCHK(hipMemcpyAsync(scores_padded, d_scores, (size_t)B * R * 4, hipMemcpyDeviceToDevice, st));
-  TLoss la{d_scores, d_ds, t.d_kw.get(), t.d_imp.get(), t.d_loss.get(), R, t.d_sel.get()};
+  TLoss la{d_scores, d_ds, d_kw, d_imp, t.d_loss.get(), R, t.d_sel.get(), in->mask, status};
   hipLaunchKernelGGL(k_tloss, dim3(B), dim3(256), 0, st, la);
   // ---- backward: the tape in reverse ----
   t.wops.clear();
   for (auto it = t.tape.rbegin(); it != t.tape.rend(); ++it) (*it)();
   t.tape.clear();
-  if (t.weight_grads()) return fail(GNNB_E_HIP, "gnnb_online_step: the weight-gradient launches failed");
-  if (t.arena.err) return fail(GNNB_E_NOMEM, "gnnb_online_step: out of device memory");
+  if (t.weight_grads()) return fail(GNNB_E_HIP, "%s: the weight-gradient launches failed", who);
+  if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(GNNB_E_HIP, "gnnb_online_step: a launch failed: %s", hipGetErrorString(e));
-  if (loss) {
+  if (e != hipSuccess) return fail(GNNB_E_HIP, "%s: a launch failed: %s", who, hipGetErrorString(e));
+  if (loss_host) {
     t.h_loss.resize(B);
     HIPCHK(hipMemcpyAsync(t.h_loss.data(), t.d_loss.get(), (size_t)B * 4, hipMemcpyDeviceToHost, st));
   }
+  if (loss_dev) HIPCHK(hipMemcpyAsync(loss_dev, t.d_loss.get(), (size_t)B * 4, hipMemcpyDeviceToDevice, st));
   if (apply) {
     t.step += 1;
     const double b1 = 0.9, b2 = 0.999;
@@ -2359,6 +2383,67 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   } else {
     HIPCHK(hipStreamSynchronize(st));
   }
-  if (loss) memcpy(loss, t.h_loss.data(), (size_t)B * 4);
+  if (loss_host) memcpy(loss_host, t.h_loss.data(), (size_t)B * 4);
   return GNNB_OK;
+}
+
+// in: the batch exactly as for gnnb_forward.  kw_index (HOST, B), which must name an undecided node of the mask; improvement (HOST, B);
+// loss (HOST, B, may be NULL): the host checks and the two small copies in front of online_step_device.
+extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_index, const float* improvement,
+                                float* loss, float* scores_padded, int apply, void* stream) {
+  const char* who = "gnnb_online_step";
+  if (!h || !in || !kw_index || !improvement) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (int rc = online_preflight(h, in, B, who)) return rc;
+  for (int b = 0; b < B; ++b)
+    if (kw_index[b] < 0 || kw_index[b] >= h->R) return fail(GNNB_E_INVALID, "%s: kw_index[%d] = %d outside [0, %d)", who, b, kw_index[b], h->R);
+  gnnb_train::Trainer& t = *h->trainer;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(t.d_imp.grow(B));
+  HIPCHK(t.d_kw.grow(B));
+  HIPCHK(hipMemcpyAsync(t.d_kw.get(), kw_index, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.d_imp.get(), improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  return online_step_device(h, in, B, t.d_kw.get(), t.d_imp.get(), loss, nullptr, scores_padded, nullptr, apply, st, false, who);
+}
+
+// gnnb_online_step on the rows rows[0..n) of the K-row device batch `in`, in list order, nothing crossing the link: k_trows_gather copies
+// the listed rows of every tensor the step reads into dense n-row buffers out of the trainer's arena, then online_step_device runs at B = n
+// on them.  Synchronises where gnnb_online_step does.
+extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index,
+                                     const float* improvement, float* loss, int32_t* status, int apply, void* stream) {
+  using namespace gnnb_train;
+  const char* who = "gnnb_online_step_rows";
+  if (K < 1 || n < 1 || n > K) return fail(GNNB_E_INVALID, "%s: n = %d rows of a batch of K = %d (1 <= n <= K)", who, n, K);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!in || !rows || !kw_index || !improvement) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (int rc = online_preflight(h, in, K, who)) return rc;
+  const int NG = (int)h->N.size(), L = NG - 2, R = h->R;
+  Trainer& t = *h->trainer;
+  hipStream_t st = (hipStream_t)stream;
+  if (t.arena.reset(st)) return fail(GNNB_E_HIP, "%s: arena reset failed", who);
+  TGather g{};
+  g.K = K; g.rows = rows; g.status = status;
+  auto dense = [&](const float* src, long w) -> const float* {          // the n listed rows of a (K, w) tensor
+    float* d = t.arena.alloc((size_t)n * w);
+    g.t[g.nt++] = TGatherT{src, d, (int)w};
+    return d;
+  };
+  std::vector<const float*> lb(NG), ub(NG), dual(L), primal(in->primal, in->primal + in->n_primal);      // (entries the step does not read stay)
+  for (int k = 0; k < NG; ++k) { lb[k] = dense(in->lb[k], h->N[k]); ub[k] = dense(in->ub[k], h->N[k]); }
+  std::vector<char> done(in->n_primal, 0);
+  for (int k = 1; k <= L; ++k) {
+    dual[k - 1] = dense(in->dual[k - 1], 3L * h->N[k]);
+    for (int q : {h->relu_q[k] - 1, h->relu_q[k]})
+      if (!done[q]) { primal[q] = dense(in->primal[q], h->N[k]); done[q] = 1; }
+  }
+  if (!done[in->n_primal - 1]) primal[in->n_primal - 1] = dense(in->primal[in->n_primal - 1], 1);
+  gnnb_batch dn = *in;
+  dn.lb = lb.data(); dn.ub = ub.data(); dn.dual = dual.data(); dn.primal = primal.data();
+  dn.x_lp = dense(in->x_lp, h->N[0]); dn.prop_w = dense(in->prop_w, h->N[L]); dn.prop_b = dense(in->prop_b, 1);
+  g.mask_t = g.nt;
+  dn.mask = dense(in->mask, R);
+  if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
+  Launcher run{h, st};
+  run.run(PC_TROWS_GATHER, [&] { hipLaunchKernelGGL(k_trows_gather, dim3(n, TG_SPLIT), dim3(TG_THREADS), 0, st, g); });
+  if (run.rc) return run.rc;
+  return online_step_device(h, &dn, n, kw_index, improvement, nullptr, loss, nullptr, status, apply, st, true, who);
 }

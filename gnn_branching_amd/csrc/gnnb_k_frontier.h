@@ -1,6 +1,7 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
 // gnnb_frontier_gather, gnnb_frontier_expand, gnnb_net_eval, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
-// a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, and their many-job form of section 7.6).  Between them run the existing batch kernels
+// a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, their many-job form of section 7.6, and the selection
+// of the rows an online round learns from, section 7.7: gnnb_frontier_learn).  Between them run the existing batch kernels
 // (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched.
 //
 // The POOL is a struct of arrays over `capacity` slots: mask (cap, R) int8, the fp64 bounds of graph layers 1..L+1 (cap, N_k) exactly as
@@ -778,4 +779,40 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_jobs(FrChooseArg
   const int m = min(min(max(m_entry[e], 0), k), max(a.m - sel0, 0));      // a.m: M, the host's copy of the sum
   const FrFbView v{row0, k, sel0, nullptr, a.ineff + (long)seg * a.s.R, nullptr};
   fr_choose(a, v, m);
+}
+
+// ---- the learn rows of an online round ----------------------------------------------------------------------
+// Reference plnn/relu_conv_online.py:183-207 (bab_caller.resolve_online) for the K parents of a round, once k_frontier_choose has made the
+// choice: `wrong` (R) is the reference's wrong_pts_dc keyed by the flat index of the GNN's decision.
+//
+//   * k_frontier_learn   ONE workgroup, one thread walking the rows in order (as fr_fallback_walk does): a row that took its KW pair adds 1
+//                        to wrong[flat(gnn decision)]; with the count at or above online_threshold it is a LEARN row: its row number, the
+//                        flat index of its KW decision and improve = (kw_imp - gnn_imp > 0.1 ? 1 : 0), the difference in fp64, go to the
+//                        dense lists in row order, n_learn their number.  Two rows that name one GNN node both count.  A row whose
+//                        decisions name no node of the network is no learn row and leaves the table alone.  Entries of the lists from
+//                        n_learn on are not written.
+
+struct FrLearnArgs {
+  FrShape s; int K;
+  const int32_t* gnn_dec; const int32_t* kw_dec; const int32_t* used; const double* gnn_imp; const double* kw_imp;
+  int online_threshold;
+  int32_t* wrong; int32_t* learn_rows; int32_t* learn_kw; float* learn_imp; int32_t* n_learn;
+};
+static_assert(sizeof(FrLearnArgs) <= 4096, "kernel arguments: 4 KiB");
+
+__global__ __launch_bounds__(64) void k_frontier_learn(FrLearnArgs a) {
+  if (threadIdx.x != 0) return;
+  int n = 0;
+  for (int i = 0; i < a.K; ++i) {
+    if (!a.used[i]) continue;
+    int gnn, kw;
+    if (!fr_node(a.s, a.gnn_dec[2L * i], a.gnn_dec[2L * i + 1], &gnn) || !fr_node(a.s, a.kw_dec[2L * i], a.kw_dec[2L * i + 1], &kw)) continue;
+    const int count = a.wrong[gnn] + 1;
+    a.wrong[gnn] = count;
+    if (count < a.online_threshold) continue;
+    a.learn_rows[n] = i; a.learn_kw[n] = kw;
+    a.learn_imp[n] = a.kw_imp[i] - a.gnn_imp[i] > 0.1 ? 1.0f : 0.0f;                 // :203-206, strictly greater
+    ++n;
+  }
+  *a.n_learn = n;
 }

@@ -17,6 +17,9 @@
 // (op, row chunk), k_tlin_reduce_all adding the partials in tape order).  Every sum keeps the order of the one-launch-per-op form,
 // so values and gradients are bit-identical to it.
 //
+// gnnb_online_step_rows runs the same step on listed rows of a K-row device batch: k_trows_gather copies them into dense buffers out of
+// the arena, and the tape behind is the one above at B = n.
+//
 // Included by gnnb.hip (one translation unit: it uses the bound network of gnnb_handle) behind gnnb_mem.h, whose owners hold its memory.
 #pragma once
 #include <functional>
@@ -673,7 +676,9 @@ __global__ __launch_bounds__(64) void k_tscore_bwd_w(TScoreMulti m, int nlayers)
 
 // loss_b = max_j s_b[j] - s_b[kw_b] + improvement_b (graph_score_online.py:73); ds = d loss / d scores.
 // A sample without a finite score (nothing `v > best` holds for) gets loss = NaN, sel = {-1, -1} and no ds entry.
-struct TLoss { const float* scores; float* ds; const int* kw; const float* imp; float* loss; int R; int* sel; };
+// kw may come from the device (gnnb_online_step_rows), where no host check has seen it: an index outside [0, R) or naming a node whose
+// mask entry is 0 is treated the same way and sets bit 3 (value 8) of *status (may be null); nothing is read out of bounds.
+struct TLoss { const float* scores; float* ds; const int* kw; const float* imp; float* loss; int R; int* sel; const float* mask; int* status; };
 __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
   __shared__ float sv[256];
   __shared__ int si[256];
@@ -697,10 +702,51 @@ __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
       a.sel[2 * b] = -1; a.sel[2 * b + 1] = -1;      // (k_tscore_bwd_w skips indices outside a layer)
       return;
     }
+    if (kw < 0 || kw >= a.R || a.mask[(long)b * a.R + kw] == 0.0f) {
+      a.loss[b] = NAN;
+      a.sel[2 * b] = -1; a.sel[2 * b + 1] = -1;
+      if (a.status) *a.status = *a.status | 8;         // (every writer of a launch stores the same bit: no atomic needed)
+      return;
+    }
     a.loss[b] = sv[0] - s[kw] + a.imp[b];
     a.ds[(long)b * a.R + am] += 1.0f;
     a.ds[(long)b * a.R + kw] -= 1.0f;
     a.sel[2 * b] = am; a.sel[2 * b + 1] = kw;
+  }
+}
+
+// ---- the listed rows of a K-row device batch as a dense n-row batch (gnnb_online_step_rows) ----
+// Row i of every destination = row rows[i] of its source, for every tensor the step reads; a row is spread over the TG_SPLIT workgroups
+// of blockIdx.y (as fr_copy_row of gnnb_k_frontier.h spreads a domain's row), 16-byte copies where both sides allow them.  A rows entry
+// outside [0, K) names no row: its sample is skipped -- its mask row stays as the arena handed it out, all zero, so it gets loss = NaN
+// and no ds entry like any sample with an empty mask, and its other tensors receive row 0 (finite inputs: all-zero bounds would put
+// 0 / 0 into k_tprep's slopes and NaN into every weight gradient) -- and bit 3 (value 8) of *status (may be null) is set.
+#define TG_THREADS 256
+#define TG_SPLIT 8
+#define TG_MAXT (5 * T_MAXL + 12)
+struct TGatherT { const float* src; float* dst; int w; };     // w: floats per row
+struct TGather { TGatherT t[TG_MAXT]; int nt, K, mask_t; const int* rows; int* status; };      // mask_t: the entry of t that is the mask
+static_assert(sizeof(TGather) <= 4096, "kernel arguments: 4 KiB");
+__global__ __launch_bounds__(TG_THREADS) void k_trows_gather(TGather a) {
+  const int i = blockIdx.x, t0 = blockIdx.y * TG_THREADS + threadIdx.x, dt = TG_SPLIT * TG_THREADS;
+  int r = a.rows[i];
+  const bool skip = r < 0 || r >= a.K;
+  if (skip) {
+    if (t0 == 0 && a.status) *a.status = *a.status | 8;  // (every writer of a launch stores the same bit: no atomic needed)
+    r = 0;
+  }
+  for (int q = 0; q < a.nt; ++q) {
+    if (skip && q == a.mask_t) continue;
+    const TGatherT& t = a.t[q];
+    const float* s = t.src + (long)r * t.w;
+    float* d = t.dst + (long)i * t.w;
+    if ((t.w & 3) == 0 && (((unsigned long long)s | (unsigned long long)d) & 15ull) == 0) {
+      const tf4* s4 = reinterpret_cast<const tf4*>(s);
+      tf4* d4 = reinterpret_cast<tf4*>(d);
+      for (int j = t0; j < (t.w >> 2); j += dt) d4[j] = s4[j];
+    } else {
+      for (int j = t0; j < t.w; j += dt) d[j] = s[j];
+    }
   }
 }
 

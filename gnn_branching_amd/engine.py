@@ -777,6 +777,20 @@ class ScorerEngine:
         _lib.check(rc, "gnnb_online_step")
         return loss, scores
 
+    def online_step_rows(self, batch, K, rows, kw_index, improvement, loss=None, status=None, apply=True):
+        """gnnb_online_step_rows on the current stream: ``online_step`` on the rows ``rows`` ((n,) int32 device tensor, in list order) of the
+        K-row device batch ``batch`` (a ``_lib.Batch`` over device tensors, as ``make_batch`` builds it), with nothing crossing the link.
+        kw_index (n,) int32 / improvement (n,) fp32: device tensors; loss: None, or a (n,) fp32 device tensor that receives the losses;
+        status: None, or a zeroed (1,) int32 device tensor whose bit 3 (value 8) reports a row that named no undecided node or no row of
+        the batch (that row's loss is NaN, the others are not affected).  Synchronises the stream, as ``online_step`` does."""
+        if not getattr(self, "_online", False):
+            raise RuntimeError("online_step_rows: call online_create first")
+        n, i32, f32 = int(rows.numel()), torch.int32, torch.float32
+        self._call("gnnb_online_step_rows", C.byref(batch), int(K), self._rows(rows, n, 1, i32, "rows").data_ptr(), n,
+                   self._rows(kw_index, n, 1, i32, "kw_index").data_ptr(), self._rows(improvement, n, 1, f32, "improvement").data_ptr(),
+                   None if loss is None else self._rows(loss, n, 1, f32, "loss").data_ptr(),
+                   None if status is None else self._rows(status, 1, 1, i32, "status").data_ptr(), 1 if apply else 0)
+
     def online_grad(self):
         """d loss / d parameters of the last online_step, flat float32 array in checkpoint order."""
         out = np.empty(GNN_BLOB_FLOATS, dtype=np.float32)
@@ -1050,6 +1064,22 @@ class ScorerEngine:
                    self._rows(ineff, self.R, 1, i32, "ineff").data_ptr(),
                    self._rows(kw_improvement, K, 1, torch.float64, "kw_improvement").data_ptr(),
                    self._rows(used_kw, K, 1, i32, "used_kw").data_ptr(), self._rows(decisions, K, 2, i32, "decisions").data_ptr())
+
+    def frontier_learn(self, K, gnn_decisions, kw_decisions, used_kw, gnn_improvement, kw_improvement, online_threshold, wrong, learn_rows, learn_kw,
+                       learn_imp, n_learn):
+        """gnnb_frontier_learn on the current stream: ``bab_caller.resolve_online``'s count of wrong points for the
+        K parents of a round once ``frontier_choose`` has run.  A row with used_kw = 1 adds 1 to wrong[flat index of its GNN decision]
+        (wrong: (R,) int32, read and updated in row order); once that count reaches ``online_threshold`` the row is a learn row: learn_rows /
+        learn_kw (the flat index of its KW decision) (K,) int32 and learn_imp (K,) fp32 (1.0 if the KW pair improved the bound by more than
+        0.1 over the GNN's, else 0.0) receive it densely and in row order, n_learn (1,) int32 their number."""
+        i32, f64 = torch.int32, torch.float64
+        self._call("gnnb_frontier_learn", K, self._rows(gnn_decisions, K, 2, i32, "gnn_decisions").data_ptr(),
+                   self._rows(kw_decisions, K, 2, i32, "kw_decisions").data_ptr(), self._rows(used_kw, K, 1, i32, "used_kw").data_ptr(),
+                   self._rows(gnn_improvement, K, 1, f64, "gnn_improvement").data_ptr(),
+                   self._rows(kw_improvement, K, 1, f64, "kw_improvement").data_ptr(), int(online_threshold),
+                   self._rows(wrong, self.R, 1, i32, "wrong").data_ptr(), self._rows(learn_rows, K, 1, i32, "learn_rows").data_ptr(),
+                   self._rows(learn_kw, K, 1, i32, "learn_kw").data_ptr(), self._rows(learn_imp, K, 1, torch.float32, "learn_imp").data_ptr(),
+                   self._rows(n_learn, 1, 1, i32, "n_learn").data_ptr())
 
     # ---- many jobs in one pool (frontier.py verify_properties; include/gnnb.h gnnb_frontier_*_jobs) ------------------------------------
     def _plan(self, plan):

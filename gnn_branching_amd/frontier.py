@@ -13,6 +13,10 @@ undecided ReLU left) or closed against that one global_ub.  With K = 1 this is `
 ``verify_properties`` (``verify_properties_threshold``, section 7.6, with the BaBSR fall-back) runs many JOBS -- a box, a property row, a decision bound, all on one bound network -- through
 the same round of launches: the pool is cut into segments of ``capacity`` slots, a segment holds one job and has its own record, and inside
 its segment a job runs the rule above unchanged, so it gets the result ``branch_and_bound_frontier`` gives it alone, bit for bit.
+
+``branch_and_bound_frontier(..., branching_threshold=T, online_threshold=N)`` is the reference's online loop
+(``lp_producer.branch_and_bound_online``) on the same round: a parent whose KW pair won counts its GNN decision as a wrong point, from the
+N-th time on it is a learn row, and behind the commit the round takes one Adam step over its learn rows on the device.
 """
 import ctypes as C
 import math
@@ -153,6 +157,26 @@ def _check_threshold(branching_threshold, kwbd_threshold):
         raise ValueError(f"kwbd_threshold = {kwbd_threshold!r}: an integer >= 0")
 
 
+KWBD_DEFAULT = 10                   # kwbd_threshold's default
+KWBD_NEVER = 2 ** 31 - 1            # online mode: no count of inefficient points reaches it, every KW decision is bounded
+
+
+def _check_online(online_threshold, branching_threshold, kwbd_threshold, choice):
+    """The online mode's arguments (None: the mode is off), before a device is touched."""
+    if online_threshold is None:
+        return
+    if not isinstance(online_threshold, int) or isinstance(online_threshold, bool) or online_threshold < 1:
+        raise ValueError(f"online_threshold = {online_threshold!r}: None, or an integer >= 1")
+    if branching_threshold is None:
+        raise ValueError("online_threshold needs a branching_threshold: a parent learns from the KW decision the threshold mode bounds")
+    if kwbd_threshold != KWBD_DEFAULT:
+        raise ValueError(f"kwbd_threshold = {kwbd_threshold!r} with online_threshold: the online loop has no table of inefficient KW points "
+                         "(reference plnn/relu_conv_online.py:166-177); leave kwbd_threshold at its default")
+    from .graphnet.graph_score_online import GraphChoice
+    if not isinstance(choice, GraphChoice):
+        raise TypeError(f"online_threshold needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
+
+
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
 
@@ -215,18 +239,23 @@ class FrontierRun(_Round):
 
     With a ``branching_threshold`` the run also owns a second set of child rows, the table ``ineff`` of
     inefficient KW points and the intercept counter ``icp``, and a round reads one more number, the count of selected parents
-    (``read_selected``, 4 bytes), between its two halves."""
+    (``read_selected``, 4 bytes), between its two halves.
+
+    With an ``online_threshold`` it also owns the table ``wrong`` of wrong GNN points, the dense lists of a round's
+    learn rows and their number ``n_learn``; a round with m > 0 reads ``n_learn`` (4 bytes) behind the state record and, when it is not
+    zero, takes one learning step over those rows (``gnnb_online_step_rows``, which synchronises)."""
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
-                 kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001):
+                 kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None):
         self.capacity = _check_args(K, n_iter, lr, eps, 0, capacity)
         _check_threshold(branching_threshold, kwbd_threshold)
+        _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
         self.K, self.n_iter, self.lr, self.eps, self.decision_bound = K, n_iter, float(lr), float(eps), decision_bound
         self.fixed, self.prop_layer = layers[:-1], layers[-1]
-        eng = self.eng = choice.model.engine()
+        eng = self.eng = choice.model.engine() if online_threshold is None else choice._eng()      # (_eng: the engine with its optimizer)
         in_shape = tuple(lp.input_lb.shape)
         eng.bind(self.fixed, in_shape)
         dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
@@ -252,6 +281,14 @@ class FrontierRun(_Round):
             self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(K, dtype=i32, device=dev) for _ in range(3))
             self.m_dev, self.n_used = torch.zeros(1, dtype=i32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
             self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_workspace_bytes(eng.h, K)), dtype=torch.uint8, device=dev)
+        self.online, self.k, self.learn_pending, self.last_learn = online_threshold, 0, False, 0
+        self.online_steps = self.online_rows = 0
+        if online_threshold is not None:
+            self.kwbd_threshold = KWBD_NEVER
+            self.wrong = torch.zeros(eng.R, dtype=torch.int32, device=dev)
+            self.learn_rows, self.learn_kw, self.n_learn = (torch.zeros(n, dtype=torch.int32, device=dev) for n in (K, K, 1))
+            self.learn_imp, self.loss = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float32, device=dev)
+            self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _commit(self, slots):
         self.eng.frontier_commit(self.pool, slots, *self.Ch.children(), self.pool.state, eps=self.eps, decision_bound=self.decision_bound,
@@ -307,18 +344,52 @@ class FrontierRun(_Round):
         eng.frontier_choose(pool, k, m, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff, self.kw_imp,
                             self.used_kw, self.dec)
         self.n_used += self.used_kw[:k].sum()
+        if self.online is not None:                               # the learn rows of the round (section 7.7): read behind the state record
+            eng.frontier_learn(k, P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong, self.learn_rows,
+                               self.learn_kw, self.learn_imp, self.n_learn)
+            self.k, self.learn_pending = k, True
+
+    def _learn(self):
+        """The learning half of an online round with m > 0, behind the commit and the read of the state record: the read of n_learn
+        (4 bytes) and, with n_learn > 0, ONE step over the learn rows on the parent rows' scorer inputs, which the round's gather and
+        gnnb_dual_ascent(n_iter 0) left in ``P`` (intact until the next gather).  The next round's forward scores with the new parameters."""
+        self.learn_pending = False
+        n = self.last_learn = self.read_learn()
+        if n == 0:
+            return
+        self.step_status.zero_()
+        self.eng.online_step_rows(self.P.fwd_batch, self.k, self.learn_rows[:n], self.learn_kw[:n], self.learn_imp[:n], loss=self.loss[:n],
+                                  status=self.step_status)
+        self.status_all |= self.step_status
+        self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
+
+    def read_learn(self):
+        """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
+        return int(self.n_learn.cpu()[0])
+
+    def check_status(self):
+        st = int(self.status_all.cpu()[0])
+        if st & 8:
+            raise RuntimeError("gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask")
+        from .engine import _raise_for_status
+        _raise_for_status(st)
 
     def read_selected(self):
         """m, the number of parents whose KW decision gets bounded: the 4 bytes a threshold round reads between its halves."""
         return int(self.m_dev.cpu()[0])
 
     def read_state(self):
-        """The state record as a list of Python floats: the one device-to-host copy of a round (of its second half, in threshold mode)."""
-        return self.pool.state.cpu().tolist()
+        """The state record as a list of Python floats: the one device-to-host copy of a round (of its second half, in threshold mode).
+        An online round with m > 0 then reads n_learn and takes its learning step (``_learn``)."""
+        st = self.pool.state.cpu().tolist()
+        if self.learn_pending:
+            self._learn()
+        return st
 
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
-                              trace=None, branching_threshold=None, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001, stats=None):
+                              trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
+                              online_threshold=None):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -343,12 +414,34 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     "kw_child_bounds" / "kw_child_infeasible", two per selected row).  stats: None, or a dict that receives "branches" (parents
     expanded), "kw_bounded", "kw_used" and "domains_bounded"; domains_bounded counts the children of both pairs.
 
+    online_threshold (None: off, and nothing below applies; needs a ``branching_threshold`` and the default ``kwbd_threshold``): the control
+    flow of ``lp_producer.branch_and_bound_online`` (reference plnn/relu_conv_online.py:126-276) inside a round, DESIGN.md section 7.7.
+    ``choice`` must be a ``graphnet.graph_score_online.GraphChoice``.  Every parent with a KW decision gets its second pair bounded (the
+    online loop has no table of inefficient points); a parent that took its KW pair counts its GNN decision as a wrong point, and once a
+    node has been wrong ``online_threshold`` times the parent is a learn row: behind the commit the round takes ONE Adam step on the summed
+    loss (max score - score of the KW node + improve) of its learn rows, all scored with the round's opening parameters, and the next
+    round's forward uses the new ones.  With K = 1 that is the reference's step per parent.  When the run ends (or raises) after a step,
+    ``choice.model`` receives the device's parameters.  stats then also holds "online_steps" and "online_rows", and a round's trace
+    "learn_rows", "learn_kw" (flat ReLU indices), "learn_improve" and "loss" (per learn row), and the bounds after the round, "global_lb"
+    and "global_ub".
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     _check_args(K, n_iter, lr, eps, max_rounds, capacity)
     _check_threshold(branching_threshold, kwbd_threshold)
+    _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold)
+                      decision_threshold, online_threshold)
     run.keep_pairs = trace is not None
+    try:
+        return _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
+    finally:
+        if run.online_steps:                                      # the nn.Module mirrors the device, as GraphChoice.online_learning leaves it
+            choice.model.load_blob(run.eng.get_weights())
+
+
+def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
+    """``branch_and_bound_frontier``'s loop on a checked ``FrontierRun``."""
+    branching_threshold = run.threshold
     branches = kw_bounded = 0
     S = _lib
     st = run.root()
@@ -368,6 +461,8 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
             if branching_threshold is not None:
                 trace[-1].update(_threshold_trace(run, k))
         st = run.read_state()
+        if trace is not None and run.online is not None:
+            trace[-1].update(_online_trace(run, st))
         _check_record(st)
         rounds += 1
         bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE]) + 2 * run.m
@@ -378,7 +473,18 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     if stats is not None:
         stats.update(branches=branches, kw_bounded=kw_bounded, domains_bounded=bounded,
                      kw_used=int(run.n_used.cpu()[0]) if branching_threshold is not None else 0)
+        if run.online is not None:
+            stats.update(online_steps=run.online_steps, online_rows=run.online_rows)
     return global_lb, global_ub, rounds, bounded, reason
+
+
+def _online_trace(run, st):
+    """The online mode's part of a round's trace, behind ``read_state`` (device-to-host copies): the learn rows of the round just read, the
+    flat indices of their KW nodes, improve and the loss of each row in the step; the bounds of the record ``st``."""
+    n = run.last_learn if run.m else 0
+    return {"global_lb": _global_lb(st), "global_ub": st[_lib.FS_GLOBAL_UB],
+            "learn_rows": run.learn_rows[:n].cpu().tolist(), "learn_kw": run.learn_kw[:n].cpu().tolist(),
+            "learn_improve": run.learn_imp[:n].cpu().tolist(), "loss": run.loss[:n].cpu().tolist()}
 
 
 def _threshold_trace(run, k):

@@ -456,6 +456,22 @@ int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan*
                               const double* gnn_improvement, const gnnb_children_rw* pair_a, const gnnb_children* pair_b, int32_t* ineff,
                               double* kw_improvement, int32_t* used_kw, int32_t* decisions, void* stream);
 
+/* ---- learning online inside the frontier (reference plnn/relu_conv_online.py:183-207) ----
+ * The selection of the rows an online round learns from, after gnnb_frontier_choose: wrong (device (R) int32, zero at the start of a run)
+ * is the reference's wrong_pts_dc, keyed by the flat ReLU index (the layer's offset + idx, graph_score_online.py:63-68) of the GNN's
+ * decision.  One thread walks the K rows in order: a row with used_kw = 1 adds 1 to wrong[flat(gnn_decisions[i])]; when the count after
+ * the increment is >= online_threshold the row is a LEARN row and learn_rows (its row), learn_kw (flat(kw_decisions[i])) and learn_imp
+ * (1.0f if kw_improvement[i] - gnn_improvement[i] > 0.1, the difference in fp64, strictly greater, else 0.0f) receive it, densely and in row
+ * order; *n_learn is their number.  Two rows that name one GNN node both count.  A row whose decisions name no node ([-1, -1]) or a node
+ * outside its layer is never a learn row and leaves wrong alone.  Entries of the lists from *n_learn on are not written.  gnn_decisions /
+ * kw_decisions: device (K, 2) int32 as gnnb_forward / gnnb_frontier_fallback wrote them; used_kw (K), gnn_improvement / kw_improvement (K)
+ * as gnnb_frontier_choose and gnnb_frontier_fallback wrote them; learn_rows / learn_kw (K) int32, learn_imp (K) fp32, n_learn (1) int32.
+ * Stream-ordered, no allocation, no synchronisation, no atomics.  GNNB_E_INVALID for a null handle or argument, K < 1, K > 32767 or
+ * online_threshold < 1, GNNB_E_STATE before gnnb_bind_network -- all before the launch. */
+int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decisions, const int32_t* kw_decisions, const int32_t* used_kw,
+                        const double* gnn_improvement, const double* kw_improvement, int online_threshold, int32_t* wrong,
+                        int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* n_learn, void* stream);
+
 int gnnb_destroy(gnnb_t* h);
 
 /* ---- online learning (reference graphnet/graph_score_online.py) ----
@@ -485,7 +501,21 @@ int gnnb_online_create(gnnb_t* h, float lr, float weight_decay);
 int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_index, const float* improvement,
                      float* loss, float* scores_padded, int apply, void* stream);
 
-/* d loss / d parameters of the last gnnb_online_step (before weight decay), HOST, blob order. */
+/* gnnb_online_step on the rows rows[0..n) of the K-row DEVICE batch `in`, in list order, with nothing crossing the link: rows (device (n)
+ * int32), kw_index (device (n) int32), improvement (device (n) fp32), loss (device (n) fp32 or NULL), status (device int32[1] the caller
+ * zeroed, or NULL).  The listed rows of every tensor the step reads (the bounds of every graph layer, dual, the primals it reads, x_lp,
+ * prop_w, prop_b, mask) are first copied into dense n-row buffers that belong to the handle; then the step runs at B = n: loss, gradient
+ * and parameters are the bits of gnnb_online_step on the same rows given as a compact batch.  `in` is not written.
+ * A device-fed index is checked on the device: a kw_index outside [0, R) or naming a node whose mask entry is 0, and a rows entry outside
+ * [0, K), give that row loss = NaN and no gradient and set status bit 3 (value 8); nothing is read out of bounds and the other rows are not
+ * affected (a rows entry that names no row is skipped: its sample runs on row 0's inputs under an empty mask).  GNNB_E_INVALID for n < 1 or n > K, a null handle or argument and gnnb_online_step's limits (taps, 8 ReLU layers, a
+ * zero-tap network); GNNB_E_STATE before gnnb_bind_network or gnnb_online_create.  Synchronises `stream` before returning, where
+ * gnnb_online_step does (the scorer's packs are rebuilt on the host from the new parameters): inside a frontier run a learning round is
+ * rare by construction -- a GNN node has to lose online_threshold times first -- and every other round stays free of it. */
+int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index, const float* improvement,
+                          float* loss, int32_t* status, int apply, void* stream);
+
+/* d loss / d parameters of the last gnnb_online_step or gnnb_online_step_rows (before weight decay), HOST, blob order. */
 int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats);
 
 const char* gnnb_last_error(void);
