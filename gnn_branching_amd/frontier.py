@@ -183,24 +183,43 @@ class _Round:
     def _buffers(self, n_parents, n_children, in_shape, parent_side):
         """The rows and workspaces of a round of up to n_parents parents.  self.x_lo / x_hi / pw / pb: the children's boxes and property
         rows; parent_side: the parents' (the same tensors when every row has one box and one property)."""
-        eng, dev = self.eng, self.eng.device
+        eng, dev, ws = self.eng, self.eng.device, self._ws
+        self.in_shape = in_shape
         self.P = _Rows(eng, self.fixed, n_parents, in_shape, parent_side, child=False)
-        self.Ch = self._child_rows(n_children, in_shape)
+        self.Ch = self._child_rows(n_children)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
         self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def ws(sizer, B):
-            return torch.empty(max(1, getattr(self.lib, sizer)(eng.h, B)), dtype=torch.uint8, device=dev)
         self.ws_fwd, self.ws_kw = ws("gnnb_workspace_bytes", n_parents), ws("gnnb_kw_workspace_bytes", n_children)
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
+        self.keep_pairs, self.pair_a = False, None
 
-    def _child_rows(self, n_children, in_shape, box=None):
+    def _ws(self, sizer, B):
+        return torch.empty(max(1, getattr(self.lib, sizer)(self.eng.h, B)), dtype=torch.uint8, device=self.eng.device)
+
+    def _child_rows(self, n_children, box=None):
         """A set of child rows on the children's boxes and property rows (box: its own, where its rows belong to other jobs than the
         children's).  A second set (pair B of the threshold mode) shares the workspaces: everything is
         stream-ordered, so the two pairs never use one at the same time."""
-        return _Rows(self.eng, self.fixed, n_children, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb) if box is None else box, child=True)
+        return _Rows(self.eng, self.fixed, n_children, self.in_shape, (self.x_lo, self.x_hi, self.pw, self.pb) if box is None else box, child=True)
+
+    def _threshold_buffers(self, n_parents, counters, box_b, ws_sizer, kwbd_threshold, sparsest_layer, decision_threshold):
+        """The threshold mode's state for rounds of up to n_parents parents (DESIGN.md sections 7.5 and 7.6).  counters: the shapes of the
+        intercept counters ``icp`` (and of ``n_used``, the KW pairs taken) and of the tables ``ineff`` of inefficient KW points; box_b: pair
+        B's own boxes and property rows (None: the children's); ws_sizer: the selection's workspace sizer."""
+        dev, R, n = self.eng.device, self.eng.R, n_parents
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
+        self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
+        self.icp, self.ineff = torch.zeros(counters[0], dtype=i32, device=dev), torch.zeros(counters[1], dtype=i32, device=dev)
+        self.n_used = torch.zeros(counters[0], dtype=torch.int64, device=dev)
+        self.ChB = self._child_rows(2 * n, box_b)
+        self.kw_scores, self.kw_icp = torch.zeros(n, R, dtype=f32, device=dev), torch.zeros(n, R, dtype=f32, device=dev)
+        self.gnn_imp, self.kw_imp = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, dtype=f64, device=dev)
+        self.kw_dec, self.sel_dec, self.dec = (torch.zeros(n, 2, dtype=i32, device=dev) for _ in range(3))
+        self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(n, dtype=i32, device=dev) for _ in range(3))
+        self.ws_fallback = self._ws(ws_sizer, n)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -228,9 +247,39 @@ class _Round:
                                         self.ws_fwd.numel(), self._stream()), "gnnb_forward")
         self.status_all |= self.status
 
+    def _launch(self, slots, n):
+        """The launches of a round over the n parents in ``slots`` (their boxes: the parent rows' own), from the gather to the commit."""
+        P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
+        eng.frontier_gather(pool, slots, P.box[0], P.box[1], P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
+        self._score_parents(n)
+        eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
+        self._bound_children(Ch, 2 * n, warm=True)
+        if self.threshold is not None:
+            self._fall_back(n)
+        self._commit(slots)
+
+    def _fall_back(self, n):
+        """The threshold mode between the bounding of pair A and the commit (DESIGN.md sections 7.5 and 7.6): BaBSR on the n parent rows,
+        the improvement test and the selection (``_select``), the read of the number M of selected parents (``_read_selected``), and for
+        M > 0 ONE pair B chain for all of them and the choice with what the run keeps of its outcome (``_choose``)."""
+        P, Ch, ChB, eng, pool = self.P, self.Ch, self.ChB, self.eng, self.pool
+        eng.babsr_rows(P.lb32, P.ub32, P.box[2], P.amb, n, self.kw_scores, self.kw_icp)
+        self._select(n)
+        if self.keep_pairs:                                       # (a traced run: pair A as it was bounded, before the choice overwrites rows)
+            self.pair_a = (Ch.bound[:2 * n].clone(), Ch.infeasible[:2 * n].clone())
+        M = self._read_selected()
+        if M == 0:
+            return
+        eng.frontier_expand(pool, self.sel_slots[:M], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
+        self._bound_children(ChB, 2 * M, warm=True)
+        self._choose(n, M)
+
     def check_status(self):
+        self._raise_for(int(self.status_all.cpu()[0]))
+
+    def _raise_for(self, st):
         from .engine import _raise_for_status
-        _raise_for_status(int(self.status_all.cpu()[0]))
+        _raise_for_status(st)
 
 
 class FrontierRun(_Round):
@@ -246,8 +295,8 @@ class FrontierRun(_Round):
     zero, takes one learning step over those rows (``gnnb_online_step_rows``, which synchronises)."""
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
-                 kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None):
-        self.capacity = _check_args(K, n_iter, lr, eps, 0, capacity)
+                 kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0):
+        self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
         _check_threshold(branching_threshold, kwbd_threshold)
         _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         layers = list(layers)
@@ -268,19 +317,10 @@ class FrontierRun(_Round):
         self.pb = self.prop_layer.bias.detach().reshape(1).to(dev, torch.float32).expand(n).contiguous()
         self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
         self.slots = None
-        self.threshold, self.m, self.keep_pairs, self.pair_a = branching_threshold, 0, False, None
+        self.threshold, self.m, self.m_e, self.M = branching_threshold, 0, [0], 0      # (m_e, M: the round as a plan of one entry)
         if branching_threshold is not None:
-            f64, f32, i32, R = torch.float64, torch.float32, torch.int32, eng.R
-            self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
-            self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
-            self.ChB = self._child_rows(n, in_shape)
-            self.ineff, self.icp = torch.zeros(R, dtype=i32, device=dev), torch.zeros(1, dtype=i32, device=dev)
-            self.kw_scores, self.kw_icp = torch.zeros(K, R, dtype=f32, device=dev), torch.zeros(K, R, dtype=f32, device=dev)
-            self.gnn_imp, self.kw_imp = torch.zeros(K, dtype=f64, device=dev), torch.zeros(K, dtype=f64, device=dev)
-            self.kw_dec, self.sel_dec, self.dec = (torch.zeros(K, 2, dtype=i32, device=dev) for _ in range(3))
-            self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(K, dtype=i32, device=dev) for _ in range(3))
-            self.m_dev, self.n_used = torch.zeros(1, dtype=i32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
-            self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_workspace_bytes(eng.h, K)), dtype=torch.uint8, device=dev)
+            self._threshold_buffers(K, ((1,), (eng.R,)), None, "gnnb_frontier_fallback_workspace_bytes", kwbd_threshold, sparsest_layer, decision_threshold)
+            self.m_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.online, self.k, self.learn_pending, self.last_learn = online_threshold, 0, False, 0
         self.online_steps = self.online_rows = 0
         if online_threshold is not None:
@@ -316,37 +356,28 @@ class FrontierRun(_Round):
 
     def launch_round(self, k, in_use):
         """One round over the k <= K open domains of lowest bound.  Device work only."""
-        P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
-        slots = self.slots = self.pick(k, in_use)
-        eng.frontier_gather(pool, slots, self.x_lo, self.x_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
-        self._score_parents(k)
-        eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
-        self._bound_children(Ch, 2 * k, warm=True)
-        if self.threshold is not None:
-            self._fall_back(k)
-        self._commit(slots)
+        self.slots = self.pick(k, in_use)
+        self._launch(self.slots, k)
 
-    def _fall_back(self, k):
-        """The threshold mode between the bounding of pair A and the commit: BaBSR on the parents' rows, the
-        improvement test and the selection (gnnb_frontier_fallback), the read of m, and for m > 0 pair B and the choice."""
-        P, Ch, ChB, eng, pool, slots = self.P, self.Ch, self.ChB, self.eng, self.pool, self.slots
-        eng.babsr_rows(P.lb32, P.ub32, self.pw, P.amb, k, self.kw_scores, self.kw_icp)
-        eng.frontier_fallback(pool, slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, P.amb, self.icp, self.ineff, self.gnn_imp,
-                              self.kw_dec, self.sel_rows, self.sel_slots, self.sel_dec, self.m_dev, self.threshold, self.kwbd_threshold,
-                              self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
-        if self.keep_pairs:                                       # (a traced run: pair A as it was bounded, before the choice overwrites rows)
-            self.pair_a = (Ch.bound[:2 * k].clone(), Ch.infeasible[:2 * k].clone())
-        m = self.m = self.read_selected()
-        if m == 0:
-            return
-        eng.frontier_expand(pool, self.sel_slots[:m], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
-        self._bound_children(ChB, 2 * m, warm=True)
-        eng.frontier_choose(pool, k, m, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff, self.kw_imp,
-                            self.used_kw, self.dec)
+    # ``_Round._fall_back``'s steps for one job (DESIGN.md section 7.5): gnnb_frontier_fallback, the read of m, gnnb_frontier_choose
+    def _select(self, k):
+        Ch = self.Ch
+        self.eng.frontier_fallback(self.pool, self.slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, self.P.amb, self.icp, self.ineff,
+                                   self.gnn_imp, self.kw_dec, self.sel_rows, self.sel_slots, self.sel_dec, self.m_dev, self.threshold, self.kwbd_threshold,
+                                   self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+
+    def _read_selected(self):
+        m = self.m = self.M = self.read_selected()
+        self.m_e = [m]
+        return m
+
+    def _choose(self, k, m):
+        self.eng.frontier_choose(self.pool, k, m, self.sel_rows, self.sel_slots, self.sel_dec, self.P.dec, self.gnn_imp, self.Ch, self.ChB, self.ineff,
+                                 self.kw_imp, self.used_kw, self.dec)
         self.n_used += self.used_kw[:k].sum()
         if self.online is not None:                               # the learn rows of the round (section 7.7): read behind the state record
-            eng.frontier_learn(k, P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong, self.learn_rows,
-                               self.learn_kw, self.learn_imp, self.n_learn)
+            self.eng.frontier_learn(k, self.P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong, self.learn_rows,
+                                    self.learn_kw, self.learn_imp, self.n_learn)
             self.k, self.learn_pending = k, True
 
     def _learn(self):
@@ -367,12 +398,10 @@ class FrontierRun(_Round):
         """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
         return int(self.n_learn.cpu()[0])
 
-    def check_status(self):
-        st = int(self.status_all.cpu()[0])
+    def _raise_for(self, st):
         if st & 8:
             raise RuntimeError("gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask")
-        from .engine import _raise_for_status
-        _raise_for_status(st)
+        super()._raise_for(st)
 
     def read_selected(self):
         """m, the number of parents whose KW decision gets bounded: the 4 bytes a threshold round reads between its halves."""
@@ -426,11 +455,8 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     and "global_ub".
 
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    _check_args(K, n_iter, lr, eps, max_rounds, capacity)
-    _check_threshold(branching_threshold, kwbd_threshold)
-    _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold)
+                      decision_threshold, online_threshold, max_rounds)       # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         return _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
@@ -487,16 +513,20 @@ def _online_trace(run, st):
             "learn_improve": run.learn_imp[:n].cpu().tolist(), "loss": run.loss[:n].cpu().tolist()}
 
 
-def _threshold_trace(run, k):
-    """The threshold mode's part of a round's trace (device-to-host copies).  With m = 0 no choice was launched: every row kept its GNN pair."""
-    P, ChB, m = run.P, run.ChB, run.m
-    gnn_dec = P.dec[:k].cpu().tolist()
+def _threshold_trace(run, k, e=0, row0=0):
+    """The threshold mode's part of a round's trace (device-to-host copies) for entry number ``e`` of the round's plan, the parent rows
+    [row0, row0 + k); a one-job round is a plan of one entry.  The entry's range of the dense lists starts at the sum of the m of the
+    entries before it, and "selected" counts from the entry's first row.  With M = 0 no choice was launched: every row kept its GNN pair."""
+    P, ChB, M, m = run.P, run.ChB, run.M, run.m_e[e]
+    a, b, q0 = row0, row0 + k, sum(run.m_e[:e])
+    q1 = q0 + m
+    gnn_dec = P.dec[a:b].cpu().tolist()
     a_bound, a_inf = run.pair_a
-    return {"gnn_decisions": gnn_dec, "gnn_improvement": run.gnn_imp[:k].cpu().tolist(), "kw_decisions": run.kw_dec[:k].cpu().tolist(),
-            "kw_improvement": run.kw_imp[:k].cpu().tolist() if m else [-1.0] * k, "selected": run.sel_rows[:m].cpu().tolist(),
-            "used_kw": run.used_kw[:k].cpu().tolist() if m else [0] * k, "decisions": run.dec[:k].cpu().tolist() if m else gnn_dec,
-            "gnn_child_bounds": a_bound.cpu().tolist(), "gnn_child_infeasible": a_inf.cpu().tolist(),
-            "kw_child_bounds": ChB.bound[:2 * m].cpu().tolist(), "kw_child_infeasible": ChB.infeasible[:2 * m].cpu().tolist()}
+    return {"gnn_decisions": gnn_dec, "gnn_improvement": run.gnn_imp[a:b].cpu().tolist(), "kw_decisions": run.kw_dec[a:b].cpu().tolist(),
+            "kw_improvement": run.kw_imp[a:b].cpu().tolist() if M else [-1.0] * k, "selected": [r - row0 for r in run.sel_rows[q0:q1].cpu().tolist()],
+            "used_kw": run.used_kw[a:b].cpu().tolist() if M else [0] * k, "decisions": run.dec[a:b].cpu().tolist() if M else gnn_dec,
+            "gnn_child_bounds": a_bound[2 * a:2 * b].cpu().tolist(), "gnn_child_infeasible": a_inf[2 * a:2 * b].cpu().tolist(),
+            "kw_child_bounds": ChB.bound[2 * q0:2 * q1].cpu().tolist(), "kw_child_infeasible": ChB.infeasible[2 * q0:2 * q1].cpu().tolist()}
 
 
 # ---- many jobs in one pool (DESIGN.md section 7.4) --------------------------------------------------------------------------------------
@@ -624,7 +654,7 @@ class JobsRun(_Round):
     counter ``icp`` and the table ``ineff`` of inefficient KW points, a second set of child rows with boxes of its own, and a round reads
     one more array, ``m_entry`` (``read_selected``), between its two halves."""
 
-    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=10,
+    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
                  sparsest_layer=0, decision_threshold=0.001):
         _check_threshold(branching_threshold, kwbd_threshold)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
@@ -652,31 +682,23 @@ class JobsRun(_Round):
         self.x_lo, self.x_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
         self.pw, self.pb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
         self._buffers(n, 2 * n, in_shape, (self.px_lo, self.px_hi, self.ppw, self.ppb))
-        self.ws_commit = torch.empty(max(1, self.lib.gnnb_frontier_commit_jobs_workspace_bytes(eng.h, n)), dtype=torch.uint8, device=dev)
+        self.ws_commit = self._ws("gnnb_frontier_commit_jobs_workspace_bytes", n)
         self.slots, self.row_seg = torch.zeros(n, dtype=i32, device=dev), torch.zeros(n, dtype=i32, device=dev)
         self.plan = RoundPlan(dev, S, S, cap)
         self.root_live = torch.tensor([1, 0] * S, dtype=i32).to(dev)
         self.flags_host = torch.zeros(S, dtype=i32).pin_memory()
         self.flags = torch.zeros(S, dtype=i32, device=dev)
         self.slot_seg = torch.arange(S * cap, device=dev) // cap
-        self.threshold, self.m_e, self.M, self.keep_pairs, self.pair_a = branching_threshold, [0], 0, False, None
+        self.threshold, self.m_e, self.M = branching_threshold, [0], 0
         if branching_threshold is not None:
-            R = eng.R
-            self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
-            self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
-            self.icp, self.ineff = torch.zeros(S, dtype=i32, device=dev), torch.zeros(S, R, dtype=i32, device=dev)
             # pair B's rows belong to the selected parents' jobs: boxes and property rows of their own (gnnb_frontier_fallback_jobs fills them)
             self.bx_lo, self.bx_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
             self.bpw, self.bpb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
-            self.ChB = self._child_rows(2 * n, in_shape, (self.bx_lo, self.bx_hi, self.bpw, self.bpb))
-            self.kw_scores, self.kw_icp = torch.zeros(n, R, dtype=f32, device=dev), torch.zeros(n, R, dtype=f32, device=dev)
-            self.gnn_imp, self.kw_imp = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, dtype=f64, device=dev)
-            self.kw_dec, self.sel_dec, self.dec = (torch.zeros(n, 2, dtype=i32, device=dev) for _ in range(3))
-            self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(n, dtype=i32, device=dev) for _ in range(3))
+            # per segment: the counter, the table and n_used, the KW pairs taken since its job was admitted
+            self._threshold_buffers(n, ((S,), (S, eng.R)), (self.bx_lo, self.bx_hi, self.bpw, self.bpb), "gnnb_frontier_fallback_jobs_workspace_bytes",
+                                    kwbd_threshold, sparsest_layer, decision_threshold)
             self.m_entry = torch.zeros(S + 1, dtype=i32, device=dev)
-            self.n_used = torch.zeros(S, dtype=torch.int64, device=dev)              # KW pairs taken, per segment since its job was admitted
-            self.job_used = torch.zeros(len(jobs), dtype=torch.int64, device=dev)    # ... per job, once it has left
-            self.ws_fallback = torch.empty(max(1, self.lib.gnnb_frontier_fallback_jobs_workspace_bytes(eng.h, n)), dtype=torch.uint8, device=dev)
+            self.job_used = torch.zeros(len(jobs), dtype=torch.int64, device=dev)    # KW pairs taken per job, once it has left
 
     def release(self, seg):
         """The job of segment ``seg`` leaves: no open slot, the start record."""
@@ -699,8 +721,8 @@ class JobsRun(_Round):
         """The job of segment ``seg`` leaves: its count of KW pairs taken, device to device (read once, when the run ends)."""
         self.job_used[job].copy_(self.n_used[seg])
 
-    def _commit(self, n):
-        self.eng.frontier_commit_jobs(self.pool, self.plan, self.slots[:n], *self.Ch.children(), self.pool.state, self.seg_db, eps=self.eps,
+    def _commit(self, slots):
+        self.eng.frontier_commit_jobs(self.pool, self.plan, slots, *self.Ch.children(), self.pool.state, self.seg_db, eps=self.eps,
                                       workspace=self.ws_commit)
 
     def _rows_of_plan(self):
@@ -720,7 +742,7 @@ class JobsRun(_Round):
         Ch.split[:2 * E].fill_(-1)
         Ch.live[:2 * E] = self.root_live[:2 * E]
         self._bound_children(Ch, 2 * E, warm=False)
-        self._commit(E)
+        self._commit(self.slots[:E])
 
     def compact(self, flagged):
         """``DomainPool.compact``'s rule inside every segment of ``flagged`` (a list of booleans per segment), the others left in place: one
@@ -734,40 +756,27 @@ class JobsRun(_Round):
 
     def launch_round(self, entries):
         """One round over the plan's entries [(segment, row0, k)].  Device work only."""
-        P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
         self.plan.send(entries)
-        n = self.plan.n
-        eng.frontier_pick_jobs(pool, self.plan, pool.state, self.slots, self.row_seg)
+        self.eng.frontier_pick_jobs(self.pool, self.plan, self.pool.state, self.slots, self.row_seg)
         self._rows_of_plan()
-        slots = self.slots[:n]
-        eng.frontier_gather(pool, slots, self.px_lo, self.px_hi, P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
-        self._score_parents(n)
-        eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
-        self._bound_children(Ch, 2 * n, warm=True)
-        if self.threshold is not None:
-            self._fall_back(n)
-        self._commit(n)
+        self._launch(self.slots[:self.plan.n], self.plan.n)
 
-    def _fall_back(self, n):
-        """The threshold mode between the bounding of pair A and the commit: BaBSR on the n parent rows, the
-        improvement test and the selection per entry (gnnb_frontier_fallback_jobs), the read of m_entry, and for M > 0 ONE pair B chain
-        for the selected parents of all the jobs and the choice per entry."""
-        P, Ch, ChB, eng, pool = self.P, self.Ch, self.ChB, self.eng, self.pool
-        eng.babsr_rows(P.lb32, P.ub32, self.ppw, P.amb, n, self.kw_scores, self.kw_icp)
-        eng.frontier_fallback_jobs(pool, self.plan, self.slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, P.amb, self.icp, self.ineff,
-                                   self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.gnn_imp, self.kw_dec, self.sel_rows, self.sel_slots,
-                                   self.sel_dec, self.m_entry, self.bx_lo, self.bx_hi, self.bpw, self.bpb, self.threshold, self.kwbd_threshold,
-                                   self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
-        if self.keep_pairs:                                       # (a traced run: pair A as it was bounded, before the choice overwrites rows)
-            self.pair_a = (Ch.bound[:2 * n].clone(), Ch.infeasible[:2 * n].clone())
+    # ``_Round._fall_back``'s steps for the jobs of a plan (DESIGN.md section 7.6): the selection and the choice per entry, the read of m_entry
+    def _select(self, n):
+        Ch = self.Ch
+        self.eng.frontier_fallback_jobs(self.pool, self.plan, self.slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, self.P.amb, self.icp,
+                                        self.ineff, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.gnn_imp, self.kw_dec, self.sel_rows,
+                                        self.sel_slots, self.sel_dec, self.m_entry, self.bx_lo, self.bx_hi, self.bpw, self.bpb, self.threshold,
+                                        self.kwbd_threshold, self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+
+    def _read_selected(self):
         self.m_e = self.read_selected()
-        M = self.M = self.m_e[-1]
-        if M == 0:
-            return
-        eng.frontier_expand(pool, self.sel_slots[:M], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
-        self._bound_children(ChB, 2 * M, warm=True)
-        eng.frontier_choose_jobs(pool, self.plan, M, self.m_entry, self.sel_rows, self.sel_slots, self.sel_dec, P.dec, self.gnn_imp, Ch, ChB, self.ineff,
-                                 self.kw_imp, self.used_kw, self.dec)
+        self.M = self.m_e[-1]
+        return self.M
+
+    def _choose(self, n, M):
+        self.eng.frontier_choose_jobs(self.pool, self.plan, M, self.m_entry, self.sel_rows, self.sel_slots, self.sel_dec, self.P.dec, self.gnn_imp, self.Ch,
+                                      self.ChB, self.ineff, self.kw_imp, self.used_kw, self.dec)
         self.n_used.index_add_(0, self.row_seg[:n].long(), self.used_kw[:n].long())
 
     def read_selected(self):
@@ -778,21 +787,6 @@ class JobsRun(_Round):
         """The (segments, 9) records as lists of Python floats: the one device-to-host copy of a round (of its second half, in threshold
         mode)."""
         return self.pool.state.cpu().tolist()
-
-
-def _threshold_trace_jobs(run, e, row0, k):
-    """``_threshold_trace`` for entry number ``e`` of the round's plan, rows [row0, row0 + k): its range of the dense lists starts at the
-    sum of the m of the entries before it.  "selected" counts from the entry's first row."""
-    P, ChB, M, m = run.P, run.ChB, run.M, run.m_e[e]
-    a, b, q0 = row0, row0 + k, sum(run.m_e[:e])
-    q1 = q0 + m
-    gnn_dec = P.dec[a:b].cpu().tolist()
-    a_bound, a_inf = run.pair_a
-    return {"gnn_decisions": gnn_dec, "gnn_improvement": run.gnn_imp[a:b].cpu().tolist(), "kw_decisions": run.kw_dec[a:b].cpu().tolist(),
-            "kw_improvement": run.kw_imp[a:b].cpu().tolist() if M else [-1.0] * k, "selected": [r - row0 for r in run.sel_rows[q0:q1].cpu().tolist()],
-            "used_kw": run.used_kw[a:b].cpu().tolist() if M else [0] * k, "decisions": run.dec[a:b].cpu().tolist() if M else gnn_dec,
-            "gnn_child_bounds": a_bound[2 * a:2 * b].cpu().tolist(), "gnn_child_infeasible": a_inf[2 * a:2 * b].cpu().tolist(),
-            "kw_child_bounds": ChB.bound[2 * q0:2 * q1].cpu().tolist(), "kw_child_infeasible": ChB.infeasible[2 * q0:2 * q1].cpu().tolist()}
 
 
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
@@ -814,7 +808,7 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
 
 
 def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
-                                max_rounds=50, kwbd_threshold=10, sparsest_layer=0, decision_threshold=0.001, log=print, trace=None, stats=None):
+                                max_rounds=50, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, log=print, trace=None, stats=None):
     """``verify_properties`` with the BaBSR fall-back below ``branching_threshold`` for every job: every job gets
     the result ``branch_and_bound_frontier(..., capacity=capacity, branching_threshold=branching_threshold, kwbd_threshold=...,
     sparsest_layer=..., decision_threshold=...)`` gives it alone, bit for bit, whatever else is in flight, whichever segment it got and
@@ -832,7 +826,6 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if branching_threshold is None:
         raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
-    _check_threshold(branching_threshold, kwbd_threshold)
     threshold = {"branching_threshold": branching_threshold, "kwbd_threshold": kwbd_threshold, "sparsest_layer": sparsest_layer,
                  "decision_threshold": decision_threshold}
     return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats)
@@ -895,7 +888,7 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
             for e, (s, row0, k) in enumerate(entries):
                 trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], **_trace_rows(run, row0, row0 + k)})
                 if thr:
-                    trace[-1].update(_threshold_trace_jobs(run, e, row0, k))
+                    trace[-1].update(_threshold_trace(run, k, e, row0))
         st = run.read_state()
         for e, (s, _, k) in enumerate(entries):
             j = seg_job[s]

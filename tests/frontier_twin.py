@@ -1,0 +1,231 @@
+"""The host twin of a frontier round, for tests/test_gpu_frontier.py, tests/test_gpu_frontier_threshold.py and
+tests/test_gpu_frontier_online.py: ONE loop made of public pieces (lp.solve_many(lp="dual_device"), GraphChoice.decision /
+BatchedGraphChoice.decision_many and kw_decision_many, gnn_improvement, resolve_branching / resolve_online, ScorerEngine.online_step and
+the keep-or-close rule), the toy_kw problem it runs on, and the module fixture of the three files."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_branching_amd import bab_caller, lp_producer, nets
+from gnn_branching_amd.bab_caller import gnn_improvement, resolve_branching, resolve_online
+from tests.common import register_kw_archs, register_toy_archs
+from tests.test_dual_ascent_cpu import KW_SPEC
+from tests.test_gpu_kw_geometry import Net
+
+CKPT = os.path.join(os.path.dirname(__file__), "..", "models", "cifar_trained_gnn", "best_snapshot_None_0_val_acc_0.826_loss_val_0.1036_epoch_57.pt")
+INF = float("inf")
+LR = 0.1
+N_ITER = 20
+EPS_BAB = 1e-4
+PROP, BOX_EPS = (2, 6), 0.04
+_shared = {}
+
+
+@pytest.fixture(scope="module")
+def engine():
+    from gnn_branching_amd.engine import ScorerEngine
+    register_kw_archs()
+    register_toy_archs()
+    return ScorerEngine(None)
+
+
+def bind(engine, name):
+    """Bind ``name`` (a KW_ARCHS network, or toy_kw) and return the ReLU layer sizes."""
+    if name == "toy_kw":
+        nets.register_arch("toy_kw", KW_SPEC, seed=77)
+        engine.bind(nets.build_net("toy_kw")[:-1], (3, 32, 32))
+    else:
+        net = Net(name)
+        engine.bind(net.fixed, tuple(net.shape))
+    return list(engine.sizes[1:-1])
+
+
+def toy_lp0(prop=None, eps=None):
+    """toy_kw as tests/test_dual_ascent_cpu.py toy_kw_domains builds it (seed 77, x from RandomState(9)) on the host bounds: property
+    PROP at BOX_EPS."""
+    prop, eps = PROP if prop is None else prop, BOX_EPS if eps is None else eps
+    nets.register_arch("toy_kw", KW_SPEC, seed=77)
+    layers = nets.load_verified_net("toy_kw", *prop)
+    x = torch.from_numpy(np.random.RandomState(9).standard_normal((3, 32, 32)).astype(np.float32))
+    return lp_producer.LayerGraphLP(layers, x - eps, x + eps)
+
+
+def toy(online=False, prop=None, eps=None):
+    """(lp on the device bounds, the choice, root mask) on toy_lp0, one engine for both sides.  The choice is a BatchedGraphChoice, made
+    once per problem and shared; with ``online`` a fresh graph_score_online.GraphChoice per call: a run that learns changes its parameters
+    and its optimizer."""
+    key = ("toy", prop, eps)
+    if online or key not in _shared:
+        register_toy_archs()
+        lp0 = toy_lp0(prop, eps)
+        root_mask = [torch.full((int(np.prod(lp0.shapes[i + 1])),), -1, dtype=torch.long) for i in lp0.pre_relu_indices]
+        if online:
+            from gnn_branching_amd.graphnet.graph_score_online import GraphChoice
+            choice = GraphChoice(root_mask, CKPT)
+        else:
+            choice = bab_caller.BatchedGraphChoice(root_mask, CKPT)
+        choice.verbose = False
+        made = (lp_producer.LayerGraphLP(lp0.layers, lp0.input_lb.float(), lp0.input_ub.float(), bounds="kw_device", engine=choice.model.engine()), choice, root_mask)
+        if online:
+            return made
+        _shared[key] = made
+    return _shared[key]
+
+
+def ub64(lp, sub):
+    """The network in fp64 at the domain's fp32 upper-bound point cast up."""
+    with torch.no_grad():
+        act = sub.ub_point.double()
+        for l in lp.layers:
+            act = copy.deepcopy(l).double()(act)
+    return float(act.reshape(()))
+
+
+def masked(bounds, infeasible, live=None):
+    return [INF if (inf or (live is not None and not live[c])) else b for c, (b, inf) in enumerate(zip(bounds, infeasible))]
+
+
+ROUND_KEYS = ("decisions", "child_bounds")
+THRESHOLD_KEYS = ("gnn_decisions", "kw_decisions", "used_kw", "gnn_improvement", "kw_improvement", "selected")
+
+
+def twin(K, rounds, threshold=None, kwbd=10, online_threshold=None, sides=False, prop=None, eps=None):
+    """The frontier rule as a host loop of public pieces, in the three modes of ``branch_and_bound_frontier``.
+
+    threshold None: the plain round; with K = 1 it is branch_and_bound's branch on solve_many(lp="dual_device") children.  Returns
+    per-round "decisions" and "child_bounds", "branches", "global_lb", "global_ub".
+
+    threshold T: the rule of a threshold round; with K = 1 it is branch_and_bound_threshold's branch.  Also
+    returns per round the keys of THRESHOLD_KEYS and both pairs' bounds as they were bounded, and "asked", the parents below T.
+
+    online_threshold N (with a threshold): the rule of an online round (section 7.7): no table of inefficient points, resolve_online for
+    the choice and, behind the round, ONE ScorerEngine.online_step over the learn rows' own forward arguments, the parameters frozen for
+    the round; with K = 1 it is branch_and_bound_online's branch.  Returns per round the keys of THRESHOLD_KEYS, the learn rows with their
+    KW nodes, improve and losses, "global_lb" and "global_ub" after the round; "steps", "weights", "weights_start" and "wrong".
+
+    Asserts ITS OWN conditions: no two open bounds equal at a pick; no keep-or-close comparison and no improvement within 1e-9 of its
+    threshold; online, no improvement test between the pairs and no improve test within 1e-9 of its threshold (but for a KW decision
+    that is the GNN's own node, whose improvement is the GNN's bit for bit: not greater, on both sides); with ``sides``, at least one
+    asked parent on each side of ``threshold``."""
+    online = online_threshold is not None
+    lp, choice, root_mask = toy(online, prop, eps)
+    fixed = {"fixed_layers": lp.layers[:-1], "prop_layers": [lp.layers[-1]]}
+    n_layers, order = len(lp.layers), lp_producer._random_order(len(lp.pre_relu_indices), 0)
+    off = [0] + list(np.cumsum([int(m.numel()) for m in root_mask]))
+    if online:
+        eng = choice._eng()
+        w_start = eng.get_weights().copy()
+
+    def clear(a, b):
+        assert abs(a - b) > 1e-9, ("the twin's comparison is within 1e-9 of its threshold", a, b)
+
+    def as_sub(d):
+        return bab_caller.Subproblem(*d.graph_bounds(lp.pre_relu_indices, n_layers), d.dual_vars, d.ub_point, d.primals, d.mask)
+
+    def children_of(pairs):
+        items = []
+        for d, dec in pairs:
+            for c in (0, 1):
+                m = [t.clone() for t in d.mask]
+                m[dec[0]][dec[1]] = c
+                items.append((m, d, dec[0]))
+        return lp.solve_many(items, lp="dual_device", n_iter=N_ITER, lr=LR)
+
+    def bounds_of(subs):
+        return [INF if c is None else c.lb for c in subs]
+
+    root = lp.solve_many([(root_mask, None, None)], lp="dual_device", n_iter=N_ITER, lr=LR)[0]
+    gub, closed, domains = ub64(lp, root), INF, []
+    keys = ROUND_KEYS if threshold is None else ROUND_KEYS + THRESHOLD_KEYS + (
+        ("learn_rows", "learn_kw", "learn_improve", "loss", "global_lb", "global_ub") if online else ("gnn_child_bounds", "kw_child_bounds"))
+    out = {k: [] for k in keys}
+    below = above = 0
+
+    def keep_or_close(subs, gub, closed):
+        for c in subs:
+            if c is None:
+                continue
+            clear(c.lb, gub - EPS_BAB)
+            if any(bool((m == -1).any()) for m in c.mask) and c.lb < gub - EPS_BAB:
+                domains.append(c)
+            else:
+                closed = min(closed, c.lb)
+        return closed
+
+    def global_lb():
+        return min([d.lb for d in domains] + [closed, gub])
+    closed = keep_or_close([root], gub, closed)
+    icp, ineff, wrong, steps, branches = 0, {}, {}, 0, 0
+    for _ in range(rounds):
+        if not domains or not gub - global_lb() > EPS_BAB:
+            break
+        domains.sort(key=lambda d: d.lb)
+        assert len({d.lb for d in domains}) == len(domains), "two open bounds are equal at a pick"
+        picked, domains[:] = domains[:K], domains[K:]
+        k = len(picked)
+        subs = [as_sub(d) for d in picked]
+        decs = [lp_producer.gnn_scorer(choice, lp)(picked[0], fixed)] if K == 1 else bab_caller.BatchedGraphChoice.decision_many(choice, subs, fixed)
+        decs = [[int(d[0]), int(d[1])] for d in decs]
+        children = children_of(zip(picked, decs))
+        row, l_rows, l_kw, l_imp = {"decisions": decs}, [], [], []
+        if threshold is not None:
+            lbs = bounds_of(children)
+            imps = [gnn_improvement(lbs[2 * i], lbs[2 * i + 1], d.lb) if d.lb < 0 else 1.0 for i, d in enumerate(picked)]
+            kws, selected = [[-1, -1] for _ in picked], []
+            for i, d in enumerate(picked):                  # row order: the intercept counter is carried from parent to parent
+                clear(imps[i], threshold)
+                if d.lb < 0:
+                    below, above = below + (imps[i] < threshold), above + (imps[i] > threshold)
+                if imps[i] < threshold:
+                    (kw,), (icp,) = bab_caller.BatchedGraphChoice.kw_decision_many(choice, [subs[i]], fixed, [icp], order, 0)
+                    kws[i] = [int(kw[0]), int(kw[1])]
+                    # online: no table of inefficient points, every KW decision is bounded; else the counts as they stood before the round
+                    if online or ineff.get(f"{kws[i][0]}-{kws[i][1]}", 0) < kwbd:
+                        selected.append(i)
+            kw_children = children_of([(picked[i], kws[i]) for i in selected]) if selected else []
+            kw_lbs = bounds_of(kw_children)
+            final, used, kw_imps = [list(d) for d in decs], [0] * k, [-1.0] * k
+            for j, i in enumerate(selected):                # row order: two parents that name one node both count
+                kw_imps[i] = gnn_improvement(kw_lbs[2 * j], kw_lbs[2 * j + 1], picked[i].lb)
+                if not online:
+                    dec, u = resolve_branching(decs[i], imps[i], kws[i], kw_imps[i], ineff)
+                else:
+                    if kws[i] == decs[i]:                   # BaBSR names the GNN's node: the same two children, the same bounds
+                        assert kw_imps[i] == imps[i]
+                    else:
+                        clear(kw_imps[i], imps[i])
+                    clear(kw_imps[i] - imps[i], 0.1)
+                    dec, u, learn, improve = resolve_online(decs[i], imps[i], kws[i], kw_imps[i], wrong, online_threshold)
+                    if learn:
+                        l_rows.append(i)
+                        l_kw.append(off[kws[i][0]] + kws[i][1])
+                        l_imp.append(float(improve))
+                final[i], used[i] = [int(dec[0]), int(dec[1])], int(u)
+                if u:
+                    children[2 * i], children[2 * i + 1] = kw_children[2 * j], kw_children[2 * j + 1]
+            row = {"decisions": final, "gnn_decisions": decs, "kw_decisions": kws, "used_kw": used, "gnn_improvement": imps, "kw_improvement": kw_imps,
+                   "selected": selected, "gnn_child_bounds": lbs, "kw_child_bounds": kw_lbs}
+        gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
+        closed = keep_or_close(children, gub, closed)       # the commit does not depend on the parameters: first commit, then learn
+        branches += k
+        if online:
+            loss = []
+            if l_rows:
+                args, _ = bab_caller.collate([subs[i] for i in l_rows], fixed)
+                loss = eng.online_step(args, l_kw, l_imp)[0].tolist()
+                steps += 1
+            row.update(learn_rows=l_rows, learn_kw=l_kw, learn_improve=l_imp, loss=loss, global_lb=global_lb(), global_ub=gub)
+        row["child_bounds"] = bounds_of(children)
+        for key in keys:
+            out[key].append(row[key])
+    if sides:
+        assert below >= 1 and above >= 1, ("the threshold does not split the twin's parents", below, above)
+    if online:
+        out["steps"], out["weights"], out["weights_start"], out["wrong"] = steps, eng.get_weights().copy(), w_start, wrong
+    else:
+        out["global_lb"], out["global_ub"] = global_lb(), gub
+        out.update({"branches": branches} if threshold is None else {"asked": below})
+    return out

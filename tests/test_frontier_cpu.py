@@ -176,3 +176,44 @@ ROUND_CASES = [
 def test_the_one_job_loop_decides_its_round_by_the_rule_it_had_inline(args, expected):
     assert _inline_round(*args) == expected                   # the table itself, against the restated rule
     assert frontier._one_job_round(*args) == expected
+
+
+def _traced(m_e, sel_rows):
+    """A hand-made run of 5 parent rows after a threshold round, as ``_threshold_trace`` reads it: row i decides [0, i] (GNN), [1, 10 + i]
+    (KW) and [2, 20 + i] (final); improvements i / 8 (GNN) and i / 4 (KW); pair A's child c bound -c, pair B's child c bound -c / 2."""
+    import types
+    import torch
+    i5, i10 = torch.arange(5), torch.arange(10)
+    dec = lambda layer, first: torch.stack([torch.full((5,), layer), first + i5], dim=1).to(torch.int32)      # noqa: E731
+    return types.SimpleNamespace(
+        P=types.SimpleNamespace(dec=dec(0, 0)), kw_dec=dec(1, 10), dec=dec(2, 20), gnn_imp=i5.double() / 8, kw_imp=i5.double() / 4,
+        used_kw=torch.tensor([1, 0, 1, 0, 1], dtype=torch.int32), sel_rows=torch.tensor(sel_rows + [77] * (5 - len(sel_rows)), dtype=torch.int32),
+        pair_a=(-i10.double(), (i10 % 3 == 0).to(torch.int32)), ChB=types.SimpleNamespace(bound=-i10.double() / 2, infeasible=(i10 % 4 == 1).to(torch.int32)),
+        m_e=m_e, M=m_e[-1])
+
+
+THRESHOLD_TRACE_CASES = {
+    "one job, nobody selected": ((_traced([0], []), 2), {
+        "gnn_decisions": [[0, 0], [0, 1]], "gnn_improvement": [0.0, 0.125], "kw_decisions": [[1, 10], [1, 11]], "kw_improvement": [-1.0, -1.0], "selected": [],
+        "used_kw": [0, 0], "decisions": [[0, 0], [0, 1]], "gnn_child_bounds": [-0.0, -1.0, -2.0, -3.0], "gnn_child_infeasible": [1, 0, 0, 1],
+        "kw_child_bounds": [], "kw_child_infeasible": []}),
+    "one job, rows 0 and 2 selected": ((_traced([2], [0, 2]), 3), {
+        "gnn_decisions": [[0, 0], [0, 1], [0, 2]], "gnn_improvement": [0.0, 0.125, 0.25], "kw_decisions": [[1, 10], [1, 11], [1, 12]],
+        "kw_improvement": [0.0, 0.25, 0.5], "selected": [0, 2], "used_kw": [1, 0, 1], "decisions": [[2, 20], [2, 21], [2, 22]],
+        "gnn_child_bounds": [-0.0, -1.0, -2.0, -3.0, -4.0, -5.0], "gnn_child_infeasible": [1, 0, 0, 1, 0, 0],
+        "kw_child_bounds": [-0.0, -0.5, -1.0, -1.5], "kw_child_infeasible": [0, 1, 0, 0]}),
+    # entries (rows [0, 2), m = 1) and (rows [2, 5), m = 2): entry 1's selected rows 2 and 4 count from row 2, its pair B is children 2..5
+    "entry 1 of a two-entry plan": ((_traced([1, 2, 3], [1, 2, 4]), 3, 1, 2), {
+        "gnn_decisions": [[0, 2], [0, 3], [0, 4]], "gnn_improvement": [0.25, 0.375, 0.5], "kw_decisions": [[1, 12], [1, 13], [1, 14]],
+        "kw_improvement": [0.5, 0.75, 1.0], "selected": [0, 2], "used_kw": [1, 0, 1], "decisions": [[2, 22], [2, 23], [2, 24]],
+        "gnn_child_bounds": [-4.0, -5.0, -6.0, -7.0, -8.0, -9.0], "gnn_child_infeasible": [0, 0, 1, 0, 0, 1],
+        "kw_child_bounds": [-1.0, -1.5, -2.0, -2.5], "kw_child_infeasible": [0, 0, 0, 1]}),
+}
+
+
+@pytest.mark.parametrize("case", list(THRESHOLD_TRACE_CASES))
+def test_the_threshold_trace_of_a_plan_entry_is_the_dict_written_out_by_hand(case):
+    """``_threshold_trace`` serves the one-job round (entry 0, row 0) and every entry of a many-job round: the keys and values of both
+    public docstrings, with "selected" counted from the entry's first row and pair B's range from the sum of the m before the entry."""
+    args, expected = THRESHOLD_TRACE_CASES[case]
+    assert frontier._threshold_trace(*args) == expected

@@ -4,39 +4,26 @@
 2. gnnb_frontier_gather / _expand against torch indexing, exact;
 3. gnnb_frontier_commit against a Python restatement written here, exact;
 4. / 5. branch_and_bound_frontier at K = 1 and K = 4 on toy_kw against a host loop made of the existing public pieces
-   (lp.solve_many(lp="dual_device"), GraphChoice.decision / BatchedGraphChoice.decision_many, the keep-or-close rule);
+   (tests/frontier_twin.py: lp.solve_many(lp="dual_device"), GraphChoice.decision / BatchedGraphChoice.decision_many, the keep-or-close rule);
 6. soundness of the returned bounds; 7. nothing but the state record crosses to the host in a round; 8. the limits."""
 import copy
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from gnn_branching_amd import _lib, lp_producer
-from gnn_branching_amd import bab_caller
 from gnn_branching_amd.frontier import DomainPool, FrontierRun, branch_and_bound_frontier
 from tests import margins
-from tests.common import register_kw_archs, register_toy_archs
+from tests.frontier_twin import CKPT, EPS_BAB, INF, LR, N_ITER, engine, masked, toy, twin   # noqa: F401  (engine: the module's fixture)
 from tests.test_dual_ascent_cpu import toy_kw_domains
 from tests.test_gpu_kw_geometry import Net, seeded_domain
 
 pytestmark = pytest.mark.gpu
 
 NETS = ["kwg_mlp", "kwg_rect", "kwg_gap", "kwg_single", "kwg_s1", "kwg_deep8"]
-LR = 0.1
-CKPT = os.path.join(os.path.dirname(__file__), "..", "models", "cifar_trained_gnn", "best_snapshot_None_0_val_acc_0.826_loss_val_0.1036_epoch_57.pt")
 S = _lib
-INF = float("inf")
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from gnn_branching_amd.engine import ScorerEngine
-    register_kw_archs()
-    register_toy_archs()
-    return ScorerEngine(None)
 
 
 def torch_fp64(layers, x):
@@ -320,76 +307,7 @@ def test_compaction_moves_the_open_slots_to_the_front_in_slot_order(engine):
 
 
 # ---- 4. - 6. the loop on toy_kw against a host loop of the existing pieces --------------------------------------------
-EPS_BAB = 1e-4
-N_ITER = 20
 _shared = {}
-
-
-def toy(engine_unused=None):
-    """(lp on the device bounds, GraphChoice, layers): toy_kw of tests/test_dual_ascent_cpu.py, one engine for both sides."""
-    if "toy" not in _shared:
-        register_toy_archs()
-        lp0, _ = toy_kw_domains()
-        root_mask = [torch.full((int(np.prod(lp0.shapes[i + 1])),), -1, dtype=torch.long) for i in lp0.pre_relu_indices]
-        choice = bab_caller.BatchedGraphChoice(root_mask, CKPT)
-        choice.verbose = False
-        lp = lp_producer.LayerGraphLP(lp0.layers, lp0.input_lb.float(), lp0.input_ub.float(), bounds="kw_device", engine=choice.model.engine())
-        _shared["toy"] = (lp, choice, root_mask)
-    return _shared["toy"]
-
-
-def twin_loop(K, rounds):
-    """The frontier rule as a host loop of public pieces.  Returns a dict: per-round decisions and children's bounds, global_lb,
-    global_ub; asserts ITS OWN conditions: no two open bounds equal at a pick, no keep-or-close comparison within 1e-9 of its threshold."""
-    lp, choice, root_mask = toy()
-    fixed = {"fixed_layers": lp.layers[:-1], "prop_layers": [lp.layers[-1]]}
-
-    def ub64(sub):
-        return float(torch_fp64(lp.layers, sub.ub_point).reshape(()))
-
-    def clear(a, b):
-        assert abs(a - b) > 1e-9, ("the twin's comparison is within 1e-9 of its threshold", a, b)
-    root = lp.solve_many([(root_mask, None, None)], lp="dual_device", n_iter=N_ITER, lr=LR)[0]
-    gub, closed, domains, out = ub64(root), INF, [], {"decisions": [], "child_bounds": [], "branches": 0}
-
-    def keep_or_close(subs, gub, closed):
-        for c in subs:
-            if c is None:
-                continue
-            clear(c.lb, gub - EPS_BAB)
-            if any(bool((m == -1).any()) for m in c.mask) and c.lb < gub - EPS_BAB:
-                domains.append(c)
-            else:
-                closed = min(closed, c.lb)
-        return closed
-    closed = keep_or_close([root], gub, closed)
-    for _ in range(rounds):
-        glb = min([d.lb for d in domains] + [closed, gub])
-        if not domains or not gub - glb > EPS_BAB:
-            break
-        domains.sort(key=lambda d: d.lb)
-        assert len({d.lb for d in domains}) == len(domains), "two open bounds are equal at a pick"
-        picked, domains[:] = domains[:K], domains[K:]
-        if K == 1:
-            decs = [lp_producer.gnn_scorer(choice, lp)(picked[0], fixed)]
-        else:
-            n_layers = len(lp.layers)
-            decs = choice.decision_many([bab_caller.Subproblem(*d.graph_bounds(lp.pre_relu_indices, n_layers), d.dual_vars, d.ub_point, d.primals, d.mask)
-                                         for d in picked], fixed)
-        items = []
-        for d, dec in zip(picked, decs):
-            for c in (0, 1):
-                m = [t.clone() for t in d.mask]
-                m[dec[0]][dec[1]] = c
-                items.append((m, d, dec[0]))
-        children = lp.solve_many(items, lp="dual_device", n_iter=N_ITER, lr=LR)
-        gub = min([gub] + [ub64(c) for c in children if c is not None])
-        closed = keep_or_close(children, gub, closed)
-        out["decisions"].append([list(d) for d in decs])
-        out["child_bounds"].append([INF if c is None else c.lb for c in children])
-        out["branches"] += len(picked)
-    out["global_lb"], out["global_ub"] = min([d.lb for d in domains] + [closed, gub]), gub
-    return out
 
 
 def runs(K, rounds):
@@ -397,7 +315,7 @@ def runs(K, rounds):
         lp, choice, _ = toy()
         trace = []
         res = branch_and_bound_frontier(lp, choice, lp.layers, K=K, n_iter=N_ITER, lr=LR, eps=EPS_BAB, max_rounds=rounds, log=lambda s: None, trace=trace)
-        _shared[(K, rounds)] = (twin_loop(K, rounds), res, trace)
+        _shared[(K, rounds)] = (twin(K, rounds), res, trace)
     return _shared[(K, rounds)]
 
 
@@ -405,8 +323,7 @@ def assert_same_run(twin, res, trace):
     glb, gub, rounds, bounded, reason = res
     print("twin", twin, "frontier", res)
     assert [t["decisions"] for t in trace] == twin["decisions"]
-    got = [[INF if (inf or not live) else b for b, inf, live in zip(t["child_bounds"], t["infeasible"], t["live"])] for t in trace]
-    assert got == twin["child_bounds"]                    # bit for bit: Python floats of the same fp64 values
+    assert [masked(t["child_bounds"], t["infeasible"], t["live"]) for t in trace] == twin["child_bounds"]   # bit for bit: Python floats of the same fp64 values
     assert glb == twin["global_lb"]
     assert abs(gub - twin["global_ub"]) <= 1e-9 * max(1.0, abs(twin["global_ub"]))
     assert bounded == 1 + sum(len(t["live"]) for t in trace)

@@ -6,50 +6,29 @@ csrc/gnnb_k_frontier.h k_frontier_learn; csrc/gnnb_train.h k_trows_gather):
 2. gnnb_online_step_rows against gnnb_online_step on the same rows picked with torch indexing (a compact B = n batch), bit for bit, the
    device-side guard of a bad index, and the limits;
 3. branch_and_bound_frontier(online_threshold=...) on toy_kw against a host loop made of public pieces (the twin of
-   tests/test_gpu_frontier_threshold.py with resolve_online and ScorerEngine.online_step): K = 1 and K = 4, a threshold that is never
+   tests/frontier_twin.py with resolve_online and ScorerEngine.online_step): K = 1 and K = 4, a threshold that is never
    reached against the plain threshold run, what crosses the link in a round, and soundness."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from gnn_branching_amd import _lib, bab_caller, frontier, lp_producer, nets, synth
-from gnn_branching_amd.bab_caller import gnn_improvement, resolve_online
+from gnn_branching_amd import _lib, frontier, synth
+from gnn_branching_amd.bab_caller import resolve_online
 from gnn_branching_amd.engine import ScorerEngine, make_batch, state_blob
 from gnn_branching_amd.frontier import FrontierRun, branch_and_bound_frontier
-from gnn_branching_amd.graphnet.graph_score_online import GraphChoice
-from tests.common import KW_ARCHS, register_kw_archs, register_toy_archs, state_of
-from tests.test_dual_ascent_cpu import KW_SPEC
-from tests.test_gpu_kw_geometry import Net
+from tests.common import KW_ARCHS, register_kw_archs, state_of
+from tests.frontier_twin import EPS_BAB, LR, N_ITER, bind, engine, masked, toy, toy_lp0, twin   # noqa: F401  (engine: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
-CKPT = os.path.join(os.path.dirname(__file__), "..", "models", "cifar_trained_gnn", "best_snapshot_None_0_val_acc_0.826_loss_val_0.1036_epoch_57.pt")
 S = _lib
-INF = float("inf")
-LR = 0.1
-N_ITER = 20
-EPS_BAB = 1e-4
 
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@pytest.fixture(scope="module")
-def engine():
-    register_kw_archs()
-    register_toy_archs()
-    return ScorerEngine(None)
-
-
-def bind(engine, name):
-    net = Net(name)
-    engine.bind(net.fixed, tuple(net.shape))
-    return list(engine.sizes[1:-1])
 
 
 # ---- 1. gnnb_frontier_learn -------------------------------------------------------------------------------------------
@@ -346,145 +325,10 @@ def test_step_rows_limits():
 
 # ---- 3. the loop on toy_kw against a host loop of public pieces -------------------------------------------------------
 _shared = {}
-PROP, BOX_EPS = (2, 6), 0.04
-
-
-def toy_lp0(prop=None, eps=None):
-    """toy_kw as tests/test_dual_ascent_cpu.py toy_kw_domains builds it (seed 77, x from RandomState(9)) on the host bounds: property
-    PROP at BOX_EPS."""
-    prop, eps = PROP if prop is None else prop, BOX_EPS if eps is None else eps
-    nets.register_arch("toy_kw", KW_SPEC, seed=77)
-    layers = nets.load_verified_net("toy_kw", *prop)
-    x = torch.from_numpy(np.random.RandomState(9).standard_normal((3, 32, 32)).astype(np.float32))
-    return lp_producer.LayerGraphLP(layers, x - eps, x + eps)
-
-
-def toy(prop=None, eps=None):
-    """(lp on the device bounds, a fresh online GraphChoice, root mask) on toy_lp0.  A fresh choice per call: a run that learns changes
-    its parameters and its optimizer."""
-    register_toy_archs()
-    lp0 = toy_lp0(prop, eps)
-    root_mask = [torch.full((int(np.prod(lp0.shapes[i + 1])),), -1, dtype=torch.long) for i in lp0.pre_relu_indices]
-    choice = GraphChoice(root_mask, CKPT)
-    choice.verbose = False
-    lp = lp_producer.LayerGraphLP(lp0.layers, lp0.input_lb.float(), lp0.input_ub.float(), bounds="kw_device", engine=choice.model.engine())
-    return lp, choice, root_mask
-
-
-def ub64(lp, sub):
-    import copy
-    with torch.no_grad():
-        act = sub.ub_point.double()
-        for l in lp.layers:
-            act = copy.deepcopy(l).double()(act)
-    return float(act.reshape(()))
-
-
-def twin_online(K, rounds, online_threshold, threshold=1.0, prop=None, eps=None):
-    """The rule of an online round as a host loop of public pieces: twin_threshold of
-    tests/test_gpu_frontier_threshold.py without the table of inefficient points, resolve_online for the choice and, behind the round,
-    ONE ScorerEngine.online_step over the learn rows' own forward arguments, the parameters frozen for the round.  With K = 1 it is
-    branch_and_bound_online's branch on solve_many(lp="dual_device") children.  Asserts ITS OWN conditions: no two open bounds equal at a
-    pick, no keep-or-close comparison, no improvement test and no improve test within 1e-9 of its threshold (but for a KW decision that
-    is the GNN's own node, whose improvement is the GNN's bit for bit: not greater, on both sides)."""
-    lp, choice, root_mask = toy(prop, eps)
-    eng = choice._eng()
-    fixed = {"fixed_layers": lp.layers[:-1], "prop_layers": [lp.layers[-1]]}
-    n_layers, order = len(lp.layers), lp_producer._random_order(len(lp.pre_relu_indices), 0)
-    relu = [int(m.numel()) for m in root_mask]
-    off = [0] + list(np.cumsum(relu))
-    w_start = eng.get_weights().copy()
-
-    def clear(a, b):
-        assert abs(a - b) > 1e-9, ("the twin's comparison is within 1e-9 of its threshold", a, b)
-
-    def as_sub(d):
-        return bab_caller.Subproblem(*d.graph_bounds(lp.pre_relu_indices, n_layers), d.dual_vars, d.ub_point, d.primals, d.mask)
-
-    def children_of(pairs):
-        items = []
-        for d, dec in pairs:
-            for c in (0, 1):
-                m = [t.clone() for t in d.mask]
-                m[dec[0]][dec[1]] = c
-                items.append((m, d, dec[0]))
-        return lp.solve_many(items, lp="dual_device", n_iter=N_ITER, lr=LR)
-
-    root = lp.solve_many([(root_mask, None, None)], lp="dual_device", n_iter=N_ITER, lr=LR)[0]
-    gub, closed, domains = ub64(lp, root), INF, []
-    out = {k: [] for k in ("decisions", "gnn_decisions", "kw_decisions", "used_kw", "gnn_improvement", "kw_improvement", "child_bounds", "selected",
-                           "learn_rows", "learn_kw", "learn_improve", "loss", "global_lb", "global_ub")}
-
-    def keep_or_close(subs, gub, closed):
-        for c in subs:
-            if c is None:
-                continue
-            clear(c.lb, gub - EPS_BAB)
-            if any(bool((m == -1).any()) for m in c.mask) and c.lb < gub - EPS_BAB:
-                domains.append(c)
-            else:
-                closed = min(closed, c.lb)
-        return closed
-    closed = keep_or_close([root], gub, closed)
-    icp, wrong, steps = 0, {}, 0
-    for _ in range(rounds):
-        glb = min([d.lb for d in domains] + [closed, gub])
-        if not domains or not gub - glb > EPS_BAB:
-            break
-        domains.sort(key=lambda d: d.lb)
-        assert len({d.lb for d in domains}) == len(domains), "two open bounds are equal at a pick"
-        picked, domains[:] = domains[:K], domains[K:]
-        k = len(picked)
-        subs = [as_sub(d) for d in picked]
-        decs = [lp_producer.gnn_scorer(choice, lp)(picked[0], fixed)] if K == 1 else bab_caller.BatchedGraphChoice.decision_many(choice, subs, fixed)
-        decs = [[int(d[0]), int(d[1])] for d in decs]
-        children = children_of(zip(picked, decs))
-        lbs = [INF if c is None else c.lb for c in children]
-        imps = [gnn_improvement(lbs[2 * i], lbs[2 * i + 1], d.lb) if d.lb < 0 else 1.0 for i, d in enumerate(picked)]
-        kws, selected = [[-1, -1] for _ in picked], []
-        for i, d in enumerate(picked):                      # row order: the intercept counter is carried from parent to parent
-            clear(imps[i], threshold)
-            if imps[i] < threshold:
-                (kw,), (icp,) = bab_caller.BatchedGraphChoice.kw_decision_many(choice, [subs[i]], fixed, [icp], order, 0)
-                kws[i] = [int(kw[0]), int(kw[1])]
-                selected.append(i)                          # no table of inefficient points: every KW decision is bounded
-        kw_children = children_of([(picked[i], kws[i]) for i in selected]) if selected else []
-        kw_lbs = [INF if c is None else c.lb for c in kw_children]
-        final, used, kw_imps = [list(d) for d in decs], [0] * k, [-1.0] * k
-        l_rows, l_kw, l_imp = [], [], []
-        for j, i in enumerate(selected):                    # row order: two parents that name one GNN node both count
-            kw_imps[i] = gnn_improvement(kw_lbs[2 * j], kw_lbs[2 * j + 1], picked[i].lb)
-            if kws[i] == decs[i]:                            # BaBSR names the GNN's node: the same two children, the same bounds
-                assert kw_imps[i] == imps[i]
-            else:
-                clear(kw_imps[i], imps[i])
-            clear(kw_imps[i] - imps[i], 0.1)
-            dec, u, learn, improve = resolve_online(decs[i], imps[i], kws[i], kw_imps[i], wrong, online_threshold)
-            final[i], used[i] = [int(dec[0]), int(dec[1])], int(u)
-            if u:
-                children[2 * i], children[2 * i + 1] = kw_children[2 * j], kw_children[2 * j + 1]
-            if learn:
-                l_rows.append(i)
-                l_kw.append(off[kws[i][0]] + kws[i][1])
-                l_imp.append(float(improve))
-        gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
-        closed = keep_or_close(children, gub, closed)       # the commit does not depend on the parameters: first commit, then learn
-        loss = []
-        if l_rows:
-            args, _ = bab_caller.collate([subs[i] for i in l_rows], fixed)
-            loss = eng.online_step(args, l_kw, l_imp)[0].tolist()
-            steps += 1
-        for key, v in (("decisions", final), ("gnn_decisions", decs), ("kw_decisions", kws), ("used_kw", used), ("gnn_improvement", imps),
-                       ("kw_improvement", kw_imps), ("selected", selected), ("child_bounds", [INF if c is None else c.lb for c in children]),
-                       ("learn_rows", l_rows), ("learn_kw", l_kw), ("learn_improve", l_imp), ("loss", loss),
-                       ("global_lb", min([d.lb for d in domains] + [closed, gub])), ("global_ub", gub)):
-            out[key].append(v)
-    out["steps"], out["weights"], out["weights_start"], out["wrong"] = steps, eng.get_weights().copy(), w_start, wrong
-    return out
 
 
 def frontier_online(K, rounds, online_threshold, threshold=1.0):
-    lp, choice, _ = toy()
+    lp, choice, _ = toy(online=True)
     trace, stats = [], {}
     res = branch_and_bound_frontier(lp, choice, lp.layers, K=K, n_iter=N_ITER, lr=LR, eps=EPS_BAB, max_rounds=rounds, log=lambda s: None, trace=trace,
                                     branching_threshold=threshold, stats=stats, online_threshold=online_threshold)
@@ -494,12 +338,8 @@ def frontier_online(K, rounds, online_threshold, threshold=1.0):
 def runs(K, rounds, online_threshold):
     key = (K, rounds, online_threshold)
     if key not in _shared:
-        _shared[key] = (twin_online(K, rounds, online_threshold), frontier_online(K, rounds, online_threshold))
+        _shared[key] = (twin(K, rounds, 1.0, online_threshold=online_threshold), frontier_online(K, rounds, online_threshold))
     return _shared[key]
-
-
-def masked(bounds, infeasible, live):
-    return [INF if (inf or not live[c]) else b for c, (b, inf) in enumerate(zip(bounds, infeasible))]
 
 
 def learned_then_decided(twin):
@@ -534,7 +374,7 @@ def assert_same_run(twin, run):
     np.testing.assert_array_equal(bits(state_blob(choice.model.state_dict())), bits(got_w))          # the nn.Module mirrors the device
 
 
-# Source: twin_online ALONE on the MI355X, online_threshold = 1 and branching_threshold = 1.0 on toy_kw's property (2, 6) at eps 0.04, 12
+# Source: the online twin ALONE on the MI355X, online_threshold = 1 and branching_threshold = 1.0 on toy_kw's property (2, 6) at eps 0.04, 12
 # rounds.  The root parent's KW pair wins in round 1 at either K, so the fewest rounds after which the twin has taken a learning step and
 # picked parents again (learned_then_decided, asserted again by every test) is 2.  The tests run a few more, for what 2 rounds cannot hold:
 # K = 1 four rounds as tests/test_gpu_frontier_threshold.py (a second Adam step: the moments and the bias correction carried over); K = 4
@@ -568,7 +408,7 @@ def test_a_threshold_never_reached_is_the_threshold_run_with_every_kw_point_boun
             super().__init__(*a, **k)
             made.append(self)
     monkeypatch.setattr(frontier, "FrontierRun", Spy)
-    lp, choice, root_mask = toy()
+    lp, choice, root_mask = toy(online=True)
     w0 = choice._eng().get_weights().copy()
     ref_trace, ref_stats = [], {}
     ref = branch_and_bound_frontier(lp, choice, lp.layers, K=4, n_iter=N_ITER, lr=LR, eps=EPS_BAB, max_rounds=4, log=lambda s: None, trace=ref_trace,
@@ -644,7 +484,7 @@ def test_an_online_round_copies_nothing_but_m_the_state_record_and_n_learn():
         pytest.skip("torch.cuda.set_sync_debug_mode is not available in the installed torch")
     before = torch.cuda.get_sync_debug_mode()
     for threshold in (1.0, 1e-300):
-        lp, choice, _ = toy()
+        lp, choice, _ = toy(online=True)
         run = FrontierRun(lp, choice, lp.layers, K=4, n_iter=N_ITER, lr=LR, eps=EPS_BAB, branching_threshold=threshold, online_threshold=1)
         st = run.root()
         if not sync_mode_is_live(run):
