@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18] [--witness] [--pgd 4]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -14,10 +14,13 @@ takes one Adam step over its learn rows on the device.  With --props N it
 verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
 the true one, every round's launches serving all the properties in flight; one verdict line per property.  --props N with --threshold T runs
 the fall-back for every property (frontier.verify_properties_threshold): each has its own intercept counter and table of
-inefficient points, and one round bounds the second pairs of all the properties' selected parents together.
+inefficient points, and one round bounds the second pairs of all the properties' selected parents together.  --witness (with --frontier)
+also returns the input point the upper bound belongs to -- the counter-example, when the verdict is one -- and prints the network's value
+at it; --pgd N lowers every child's upper bound by up to N projected gradient steps on the network from its LP point.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
+import copy
 import os
 import sys
 
@@ -45,7 +48,22 @@ def main():
     ap.add_argument("--frontier", type=int, default=None, metavar="K", help="device-resident frontier: expand the K most promising domains per round")
     ap.add_argument("--online", type=int, default=None, metavar="N", help="with --frontier K --threshold T: learn online, online_threshold N (the reference uses 5)")
     ap.add_argument("--props", type=int, default=None, metavar="N", help="with --frontier: verify N properties (seeds x wrong classes) in one frontier")
+    ap.add_argument("--witness", action="store_true", help="with --frontier: return the point of the upper bound and print the network's value at it")
+    ap.add_argument("--pgd", type=int, default=None, metavar="N", help="with --frontier: up to N projected gradient steps from every child's LP point")
     args = ap.parse_args()
+    if (args.witness or args.pgd is not None) and (args.frontier is None or (args.pgd is not None and args.pgd < 0)):
+        ap.error("--witness and --pgd N need --frontier K, and N >= 0")
+    upper = {"witness": [] if args.witness else None, "pgd_steps": args.pgd}
+
+    def witness_of(point, fixed, prop_layer):
+        """The network's value (fp64, torch on the host) at a witness."""
+        if point is None:
+            return "; no upper bound point"
+        with torch.no_grad():
+            act = point[None].double()
+            for l in list(fixed) + [prop_layer]:
+                act = copy.deepcopy(l).double()(act)
+        return f"; network value at the witness {float(act.reshape(())):.5f}"
     if args.props is not None and (args.frontier is None or args.props < 1):
         ap.error("--props N needs --frontier K and N >= 1")
     if args.online is not None and (args.frontier is None or args.threshold is None or args.props is not None or args.online < 1):
@@ -54,7 +72,7 @@ def main():
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
     if args.props is not None:
-        from gnn_branching_amd.frontier import FrontierJob, verify_properties, verify_properties_threshold
+        from gnn_branching_amd.frontier import FrontierJob, FrontierJobs, verify_properties, verify_properties_threshold
         wrong, jobs, names = [c for c in range(10) if c != 3], [], []
         for j in range(args.props):
             seed, cls = args.seed + j // 9, wrong[j % 9]
@@ -66,12 +84,14 @@ def main():
         choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         max_rounds, stats = max(1, args.nodes // (2 * args.frontier)), []
         if args.threshold is None:
-            results = verify_properties(choice, prop[:-1], jobs, K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+            results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         else:
-            results = verify_properties_threshold(choice, prop[:-1], jobs, args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
+            results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
                                                   stats=stats)
         for j, (name, (glb, gub, rounds, bounded, reason)) in enumerate(zip(names, results)):
             kw = f"; {stats[j]['kw_bounded']} of {stats[j]['branches']} parents bounded a KW decision, {stats[j]['kw_used']} kept it" if stats else ""
+            if args.witness:
+                kw += witness_of(upper["witness"][j], prop[:-1], jobs[j].prop_layer)
             print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
         return
     layers = nets.load_verified_net(args.net, 3, 5)
@@ -85,11 +105,14 @@ def main():
         stats = {}
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
-                                                                      branching_threshold=args.threshold, stats=stats, online_threshold=args.online)
+                                                                      branching_threshold=args.threshold, stats=stats, online_threshold=args.online,
+                                                                      **upper)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
         if args.online is not None:
             kw += f"; {stats['online_steps']} learning steps over {stats['online_rows']} learn rows"
+        if args.witness:
+            kw += witness_of(upper["witness"][0], layers[:-1], layers[-1])
         print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)

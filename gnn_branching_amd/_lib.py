@@ -61,6 +61,10 @@ class Plan(C.Structure):
                 ("seg_cap", C.c_int32)]
 
 
+class WitnessSrc(C.Structure):
+    _fields_ = [("x_a", C.c_void_p), ("x_b", C.c_void_p), ("used_kw", C.c_void_p), ("sel_rows", C.c_void_p), ("m", C.c_int32)]
+
+
 FRONTIER_STATE_DOUBLES = 9          # GNNB_FRONTIER_STATE_DOUBLES
 FS_GLOBAL_UB, FS_CLOSED_LB, FS_LOWEST_OPEN, FS_N_OPEN, FS_IN_USE, FS_KEPT, FS_CLOSED, FS_INFEASIBLE, FS_OVERFLOW = range(9)
 
@@ -103,6 +107,8 @@ SYMBOLS = [
                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gnnb_net_eval_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_net_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_net_descend_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_net_descend", C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_commit_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_frontier_commit", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.POINTER(Children), C.c_double, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -122,6 +128,9 @@ SYMBOLS = [
     ("gnnb_frontier_choose_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_int] + [C.c_void_p] * 6 +
      [C.POINTER(Children), C.POINTER(Children)] + [C.c_void_p] * 4 + [C.c_void_p]),
     ("gnnb_frontier_learn", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),
+    ("gnnb_frontier_witness", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gnnb_frontier_witness_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_int, C.c_void_p, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     ("gnnb_mu_projection", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("gnnb_destroy", C.c_int, [C.c_void_p]),
     ("gnnb_get_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -95,7 +95,7 @@ enum ProfClass {
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
   PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS,
-  PC_FR_LEARN, PC_TROWS_GATHER, PC_COUNT
+  PC_FR_LEARN, PC_TROWS_GATHER, PC_NET_DESCEND, PC_FR_WITNESS, PC_FR_WITNESS_JOBS, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -105,7 +105,7 @@ static const char* kProfNames[PC_COUNT] = {
     "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs",
     "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
     "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs",
-    "k_frontier_learn", "k_trows_gather"};
+    "k_frontier_learn", "k_trows_gather", "k_net_descend", "k_frontier_witness", "k_frontier_witness_jobs"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1762,6 +1762,40 @@ extern "C" int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, con
   return run.rc;
 }
 
+// ---- projected signed-gradient descent from a batch of points (reference plnn/conv_kwinter_gen.py:54-135) ----
+extern "C" size_t gnnb_net_descend_workspace_bytes(const gnnb_t* h, int B) {
+  if (!h || !h->bound || B < 1) return 0;
+  return (size_t)B * net_descend_doubles(h->kw_net) * sizeof(double);
+}
+
+extern "C" int gnnb_net_descend(gnnb_t* h, const float* x0, const double* x_lo, const double* x_hi, const float* prop_w, const float* prop_b, int B,
+                                int n_steps, double step, float* x_best, double* value, double* grad0, int32_t* steps_taken, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_net_descend";
+  if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
+  if (n_steps < 0) return fail(GNNB_E_INVALID, "%s: n_steps = %d", who, n_steps);
+  if (!(step > 0.0 && step <= 1.0)) return fail(GNNB_E_INVALID, "%s: step = %g (0 < . <= 1)", who, step);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
+  const int ng = h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (!x0 || !x_lo || !x_hi || !prop_w || !prop_b || !x_best || !value || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (x_best == x0) return fail(GNNB_E_INVALID, "%s: x_best must not overlap x0", who);
+  const size_t need = gnnb_net_descend_workspace_bytes(h, B);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  NetDescendArgs a{};
+  a.net = h->kw_net;
+  a.x0 = x0; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
+  a.n_steps = n_steps; a.step = step;
+  a.x_best = x_best; a.value = value; a.grad0 = grad0; a.steps_taken = steps_taken;
+  a.ws = (double*)workspace; a.ws_stride = net_descend_doubles(h->kw_net); a.width = net_eval_width(h->kw_net);
+  for (int k = 0; k <= a.net.L; ++k) a.act_off[k + 1] = a.act_off[k] + a.net.N[k];
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_NET_DESCEND, [&] { hipLaunchKernelGGL(k_net_descend, dim3(B), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
 struct FrWs { size_t undecided, dest, total; };     // byte offsets in gnnb_frontier_commit's workspace: the resolved masks at 0
 static FrWs fr_ws_layout(const gnnb_t* h, int K) {
   FrWs w;
@@ -2083,6 +2117,57 @@ extern "C" int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decision
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
   run.run(PC_FR_LEARN, [&] { hipLaunchKernelGGL(k_frontier_learn, dim3(1), dim3(64), 0, st, a); });
+  return run.rc;
+}
+
+// ---- the witness of the upper bound (reference plnn/branch_and_bound.py:157 global_ub_point) ----
+// The checks gnnb_frontier_witness and gnnb_frontier_witness_jobs share on the children and a gnnb_witness_src over n parents, m of them selected.
+static int fr_witness_in(const gnnb_t* h, const char* who, int n, int m, const gnnb_children* ch, const gnnb_witness_src* src, double* best_value,
+                         float* best_point, FrWitnessArgs* a) {
+  if (!ch || !src || !best_value || !best_point || !src->x_a) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (src->used_kw && m > 0 && (!src->x_b || !src->sel_rows)) return fail(GNNB_E_INVALID, "%s: used_kw with m = %d needs x_b and sel_rows", who, m);
+  FrChildrenRO rows{};
+  if (int rc = fr_children(h, who, ch, h->kw_net.L + 2, &rows)) return rc;
+  a->N0 = h->kw_net.N[0];
+  a->live = rows.live; a->infeasible = rows.infeasible; a->ubv = rows.ubv;
+  a->x_a = src->x_a; a->x_b = src->x_b;
+  a->used = m > 0 ? src->used_kw : nullptr; a->sel_rows = src->sel_rows;      // (without a selected parent no row is pair B's)
+  a->K = n; a->m = m;
+  a->best_value = best_value; a->best_point = best_point;
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_frontier_witness(gnnb_t* h, int K, const gnnb_children* children, const gnnb_witness_src* src, double* best_value,
+                                     float* best_point, void* stream) {
+  const char* who = "gnnb_frontier_witness";
+  if (K < 1 || K > 32767) return fail(GNNB_E_INVALID, "%s: K = %d outside 1..32767", who, K);
+  if (src && (src->m < 0 || src->m > K)) return fail(GNNB_E_INVALID, "%s: m = %d selected parents of K = %d", who, src->m, K);
+  const int ng = h && h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  FrWitnessArgs a{};
+  if (int rc = fr_witness_in(h, who, K, src ? src->m : 0, children, src, best_value, best_point, &a)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_WITNESS, [&] { hipLaunchKernelGGL(k_frontier_witness, dim3(1), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_witness_jobs(gnnb_t* h, const gnnb_plan* plan, int M, const int32_t* m_entry, const gnnb_children* children,
+                                          const gnnb_witness_src* src, double* best_value, float* best_point, void* stream) {
+  const char* who = "gnnb_frontier_witness_jobs";
+  FrPlan j{};
+  if (plan && plan->n >= 1 && plan->n <= 32767 && (M < 0 || M > plan->n))      // (as K's range: before the handle is looked at)
+    return fail(GNNB_E_INVALID, "%s: M = %d selected parents of n = %d", who, M, plan->n);
+  const int ng = h && h->bound ? h->kw_net.L + 2 : 0;
+  if (int rc = fr_plan(h, who, plan, &ng, &j)) return rc;
+  if (M < 0 || M > j.n) return fail(GNNB_E_INVALID, "%s: M = %d selected parents of n = %d", who, M, j.n);
+  if (M > 0 && src && src->used_kw && !m_entry) return fail(GNNB_E_INVALID, "%s: null m_entry with M = %d", who, M);
+  FrWitnessArgs a{};
+  if (int rc = fr_witness_in(h, who, j.n, M, children, src, best_value, best_point, &a)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_WITNESS_JOBS, [&] { hipLaunchKernelGGL(k_frontier_witness_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, m_entry); });
   return run.rc;
 }
 

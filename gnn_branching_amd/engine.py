@@ -916,6 +916,30 @@ class ScorerEngine:
         self._call("gnnb_net_eval", x.data_ptr(), pw.data_ptr(), pb.data_ptr(), B, out.data_ptr(), ws.data_ptr(), ws.numel())
         return out.reshape(-1)[:B]
 
+    def net_descend(self, fixed_layers, prop_layers, x0, x_lo, x_hi, n_steps, step=1.0 / 64, x_best=None, value=None, want_grad=False,
+                    want_steps=False, prop=None, workspace=None):
+        """gnnb_net_descend on the current stream: up to ``n_steps`` projected signed-gradient steps of ``step``
+        times the box's width on the bound network followed by property row b, from each of the B points x0 ((B, C, H, W) or (B, N_0)
+        fp32 on the device) inside [x_lo, x_hi] ((B, N_0) fp64 device tensors).  prop_layers / prop: as ``net_eval``.  x_best (B, N_0)
+        fp32 and value (B,) fp64: tensors to write to (None: new ones; x_best must not be x0).  Returns (x_best, value, grad0, steps):
+        the best point seen, the network's value there (``net_eval``'s, bit for bit), the gradient at x0 ((B, N_0) fp64) with
+        ``want_grad`` and the number of steps evaluated ((B,) int32) with ``want_steps``, else None.  Nothing is synchronised."""
+        B = int(x0.shape[0])
+        self.bind(fixed_layers, tuple(x0.shape[1:]))
+        N0, f64, f32 = self.sizes[0], torch.float64, torch.float32
+        x0 = self._rows(x0, B, N0, f32, "x0")
+        pw, pb = self._prop(prop_layers) if prop is None else prop
+        pw, pb = self._rows(pw, B, self.sizes[-2], f32, "property weights"), self._rows(pb, B, 1, f32, "property biases")
+        x_best = torch.empty(B, N0, dtype=f32, device=self.device) if x_best is None else self._rows(x_best, B, N0, f32, "x_best")
+        value = torch.empty(B, dtype=f64, device=self.device) if value is None else self._rows(value, B, 1, f64, "value")
+        grad0 = torch.empty(B, N0, dtype=f64, device=self.device) if want_grad else None
+        steps = torch.empty(B, dtype=torch.int32, device=self.device) if want_steps else None
+        ws = self._workspace("net_descend", B, "gnnb_net_descend_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_net_descend", x0.data_ptr(), self._rows(x_lo, B, N0, f64, "x_lo").data_ptr(), self._rows(x_hi, B, N0, f64, "x_hi").data_ptr(),
+                   pw.data_ptr(), pb.data_ptr(), B, int(n_steps), float(step), x_best.data_ptr(), value.data_ptr(), ptr(grad0), ptr(steps),
+                   ws.data_ptr(), ws.numel())
+        return x_best, value, grad0, steps
+
     # ---- a BaB frontier in device memory (frontier.py runs the loop; include/gnnb.h gnnb_frontier_*) ---------------------------------
     def _rows(self, t, n, cols, dtype, what):
         """t as it is, checked: a contiguous device tensor of ``dtype`` holding at least n rows of ``cols`` (the steps below copy nothing)."""
@@ -1081,6 +1105,27 @@ class ScorerEngine:
                    self._rows(learn_kw, K, 1, i32, "learn_kw").data_ptr(), self._rows(learn_imp, K, 1, torch.float32, "learn_imp").data_ptr(),
                    self._rows(n_learn, 1, 1, i32, "n_learn").data_ptr())
 
+    def _witness_src(self, n, m, x_a, x_b, used_kw, sel_rows):
+        """The gnnb_witness_src of a round of n parents, m of them selected (x_b / used_kw / sel_rows: None, or pair B's)."""
+        N0, i32, lists = self.sizes[0], torch.int32, max(int(m), 1)
+        return _lib.WitnessSrc(self._rows(x_a, 2 * n, N0, torch.float32, "x_a").data_ptr(),
+                               None if x_b is None else self._rows(x_b, 2 * lists, N0, torch.float32, "x_b").data_ptr(),
+                               None if used_kw is None else self._rows(used_kw, n, 1, i32, "used_kw").data_ptr(),
+                               None if sel_rows is None else self._rows(sel_rows, lists, 1, i32, "sel_rows").data_ptr(), int(m))
+
+    def frontier_witness(self, K, children, x_a, best_value, best_point, x_b=None, used_kw=None, sel_rows=None, m=0):
+        """gnnb_frontier_witness on the current stream, between the choice and ``frontier_commit``: the lowest
+        ub_value among the live feasible rows of ``children`` (2K rows; an object with mask, lb, ub, infeasible, bound, alpha, beta, ubv,
+        live), equal values by row; when it is strictly below best_value ((1,) fp64, +inf at the start of a run) the point it was
+        evaluated at goes to best_point ((N_0,) fp32) and the value to best_value.  x_a (2K, N_0) fp32: the rows' points; a row whose
+        parent has used_kw set takes row 2j + (c & 1) of x_b ((2m, N_0) fp32) with sel_rows[j] its parent, as ``frontier_choose`` left them."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        ch, keep = self._children(children, 2 * K, "children")
+        src = self._witness_src(K, m, x_a, x_b, used_kw, sel_rows)
+        self._call("gnnb_frontier_witness", K, C.byref(ch), C.byref(src), self._rows(best_value, 1, 1, torch.float64, "best_value").data_ptr(),
+                   self._rows(best_point, 1, self.sizes[0], torch.float32, "best_point").data_ptr())
+
     # ---- many jobs in one pool (frontier.py verify_properties; include/gnnb.h gnnb_frontier_*_jobs) ------------------------------------
     def _plan(self, plan):
         """The gnnb_plan of a ``frontier.RoundPlan`` (any object with its attributes): host (E, 3) int32 CPU tensor, device the same values
@@ -1174,6 +1219,19 @@ class ScorerEngine:
                    self._rows(gnn_improvement, n, 1, torch.float64, "gnn_improvement").data_ptr(), C.byref(pa), C.byref(pb),
                    self._rows(ineff, S, self.R, i32, "ineff").data_ptr(), self._rows(kw_improvement, n, 1, torch.float64, "kw_improvement").data_ptr(),
                    self._rows(used_kw, n, 1, i32, "used_kw").data_ptr(), self._rows(decisions, n, 2, i32, "decisions").data_ptr())
+
+    def frontier_witness_jobs(self, plan, children, x_a, best_value, best_point, M=0, m_entry=None, x_b=None, used_kw=None, sel_rows=None):
+        """gnnb_frontier_witness_jobs on the current stream: ``frontier_witness`` per plan entry on its rows of ``children`` (2n rows) and
+        its range of the dense lists (M, m_entry: ``frontier_fallback_jobs``'), with best_value[segment] ((segments,) fp64) and
+        best_point[segment] ((segments, N_0) fp32)."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        pl, n, S, E = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), max(int(plan.n_entries), 0)
+        ch, keep = self._children(children, 2 * n, "children")
+        src = self._witness_src(n, M, x_a, x_b, used_kw, sel_rows)
+        self._call("gnnb_frontier_witness_jobs", C.byref(pl), int(M), None if m_entry is None else self._rows(m_entry, E + 1, 1, torch.int32, "m_entry").data_ptr(),
+                   C.byref(ch), C.byref(src), self._rows(best_value, S, 1, torch.float64, "best_value").data_ptr(),
+                   self._rows(best_point, S, self.sizes[0], torch.float32, "best_point").data_ptr())
 
     # ---- inspection (tests / bench) ---------------------------------------------------------
     def mu_rows(self, B, k):

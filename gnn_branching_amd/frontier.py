@@ -177,8 +177,34 @@ def _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         raise TypeError(f"online_threshold needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
 
 
+PGD_STEP_DEFAULT = 1.0 / 64
+
+
+def _check_witness(witness, pgd_steps, pgd_step):
+    """The witness and descent options (None: off), before a device is touched."""
+    if witness is not None and not isinstance(witness, list):
+        raise ValueError(f"witness = {witness!r}: None, or a list that receives the point")
+    if pgd_steps is not None and (not isinstance(pgd_steps, int) or isinstance(pgd_steps, bool) or pgd_steps < 0):
+        raise ValueError(f"pgd_steps = {pgd_steps!r}: None, or an integer >= 0")
+    if isinstance(pgd_step, bool) or not isinstance(pgd_step, (int, float)) or not 0 < pgd_step <= 1:
+        raise ValueError(f"pgd_step = {pgd_step!r}: a number with 0 < pgd_step <= 1")
+
+
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
+    witness_on, pgd_steps, pgd_step = False, None, PGD_STEP_DEFAULT
+
+    def _upper_bound_options(self, witness, pgd_steps, pgd_step):
+        """The options of DESIGN.md section 7.8, checked; set before the rows are made (``_child_rows`` gives them ``x_ub`` under PGD)."""
+        _check_witness(witness, pgd_steps, pgd_step)
+        self.witness_on, self.pgd_steps, self.pgd_step = witness is not None, pgd_steps, float(pgd_step)
+
+    def _witness_buffers(self, segments):
+        """Per segment the incumbent's value (+inf: none yet; the record's global_ub after every commit) and its point."""
+        if self.witness_on:
+            dev = self.eng.device
+            self.best_value = torch.full((segments,), float("inf"), dtype=torch.float64, device=dev)
+            self.best_point = torch.zeros(segments, self.eng.sizes[0], dtype=torch.float32, device=dev)
 
     def _buffers(self, n_parents, n_children, in_shape, parent_side):
         """The rows and workspaces of a round of up to n_parents parents.  self.x_lo / x_hi / pw / pb: the children's boxes and property
@@ -193,6 +219,8 @@ class _Round:
         self.ws_fwd, self.ws_kw = ws("gnnb_workspace_bytes", n_parents), ws("gnnb_kw_workspace_bytes", n_children)
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
+        if self.pgd_steps is not None:
+            self.ws_descend = ws("gnnb_net_descend_workspace_bytes", n_children)
         self.keep_pairs, self.pair_a = False, None
 
     def _ws(self, sizer, B):
@@ -202,7 +230,10 @@ class _Round:
         """A set of child rows on the children's boxes and property rows (box: its own, where its rows belong to other jobs than the
         children's).  A second set (pair B of the threshold mode) shares the workspaces: everything is
         stream-ordered, so the two pairs never use one at the same time."""
-        return _Rows(self.eng, self.fixed, n_children, self.in_shape, (self.x_lo, self.x_hi, self.pw, self.pb) if box is None else box, child=True)
+        rows = _Rows(self.eng, self.fixed, n_children, self.in_shape, (self.x_lo, self.x_hi, self.pw, self.pb) if box is None else box, child=True)
+        if self.pgd_steps is not None:                            # the points ubv is the network's value at (x_lp stays the LP's)
+            rows.x_ub = torch.zeros_like(rows.x_lp)
+        return rows
 
     def _threshold_buffers(self, n_parents, counters, box_b, ws_sizer, kwbd_threshold, sparsest_layer, decision_threshold):
         """The threshold mode's state for rounds of up to n_parents parents (DESIGN.md sections 7.5 and 7.6).  counters: the shapes of the
@@ -225,7 +256,9 @@ class _Round:
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def _bound_children(self, Ch, B, warm):
-        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``."""
+        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
+        gnnb_net_descend from the rows' x_lp takes gnnb_net_eval's place: its f(x0) is that value, ubv the best value
+        it reached and x_ub the point."""
         lib, h = self.lib, self.eng.h
         with torch.cuda.device(self.eng.device):
             _lib.check(lib.gnnb_kw_bounds(h, C.byref(Ch.kw_batch), B, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
@@ -233,7 +266,21 @@ class _Round:
             _lib.check(lib.gnnb_dual_ascent(h, C.byref(Ch.dual_batch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
                                             Ch.bound.data_ptr(), None, None, Ch.t_dual, Ch.t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
-        self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_eval)
+        if self.pgd_steps is None:
+            self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_eval)
+        else:
+            self.eng.net_descend(self.fixed, None, Ch.x_lp[:B], Ch.box[0], Ch.box[1], self.pgd_steps, self.pgd_step, x_best=Ch.x_ub, value=Ch.ubv,
+                                 prop=Ch.box[2:], workspace=self.ws_descend)
+
+    def _ub_points(self, Ch):
+        """The points the rows' ubv are the network's values at."""
+        return Ch.x_lp if self.pgd_steps is None else Ch.x_ub
+
+    def _pair_b_source(self, M):
+        """The witness step's view of pair B: nothing without a selected parent (no choice was launched, used_kw is a past round's)."""
+        if self.threshold is None or M == 0:
+            return {}
+        return {"x_b": self._ub_points(self.ChB), "used_kw": self.used_kw, "sel_rows": self.sel_rows}
 
     def _score_parents(self, B):
         """gnnb_dual_ascent at n_iter = 0 (the scorer's inputs at the stored best point: one evaluation of g instead of ~120 KB of fp32
@@ -256,6 +303,8 @@ class _Round:
         self._bound_children(Ch, 2 * n, warm=True)
         if self.threshold is not None:
             self._fall_back(n)
+        if self.witness_on:
+            self._witness(n, self.M)
         self._commit(slots)
 
     def _fall_back(self, n):
@@ -295,8 +344,10 @@ class FrontierRun(_Round):
     zero, takes one learning step over those rows (``gnnb_online_step_rows``, which synchronises)."""
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
-                 kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0):
+                 kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
+        self._upper_bound_options(witness, pgd_steps, pgd_step)
         _check_threshold(branching_threshold, kwbd_threshold)
         _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         layers = list(layers)
@@ -316,6 +367,7 @@ class FrontierRun(_Round):
         self.pw = self.prop_layer.weight.detach().reshape(1, -1).to(dev, torch.float32).expand(n, -1).contiguous()
         self.pb = self.prop_layer.bias.detach().reshape(1).to(dev, torch.float32).expand(n).contiguous()
         self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
+        self._witness_buffers(1)
         self.slots = None
         self.threshold, self.m, self.m_e, self.M = branching_threshold, 0, [0], 0      # (m_e, M: the round as a plan of one entry)
         if branching_threshold is not None:
@@ -342,6 +394,8 @@ class FrontierRun(_Round):
         Ch.split[:2].fill_(-1)
         Ch.live[:2] = torch.tensor([1, 0], dtype=torch.int32).to(Ch.live.device)
         self._bound_children(Ch, 1, warm=False)
+        if self.witness_on:
+            self._witness(1, 0)
         self._commit(self.root_slot)
         st = self.read_state()
         if st[_lib.FS_INFEASIBLE] > 0:
@@ -379,6 +433,16 @@ class FrontierRun(_Round):
             self.eng.frontier_learn(k, self.P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong, self.learn_rows,
                                     self.learn_kw, self.learn_imp, self.n_learn)
             self.k, self.learn_pending = k, True
+
+    def _witness(self, k, M):
+        """gnnb_frontier_witness on the rows the commit will see."""
+        self.eng.frontier_witness(k, self.Ch, self._ub_points(self.Ch), self.best_value, self.best_point, m=M, **self._pair_b_source(M))
+
+    def witness(self):
+        """The incumbent's point as a CPU fp32 tensor of the input shape (None while global_ub is +inf): N_0 floats, read once per run."""
+        if not self.witness_on or math.isinf(float(self.best_value.cpu()[0])):
+            return None
+        return self.best_point[0].cpu().reshape(self.in_shape)
 
     def _learn(self):
         """The learning half of an online round with m > 0, behind the commit and the read of the state record: the read of n_learn
@@ -418,7 +482,7 @@ class FrontierRun(_Round):
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
-                              online_threshold=None):
+                              online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -454,12 +518,24 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     "learn_rows", "learn_kw" (flat ReLU indices), "learn_improve" and "loss" (per learn row), and the bounds after the round, "global_lb"
     and "global_ub".
 
+    witness, pgd_steps, pgd_step (with ``witness`` and ``pgd_steps`` at None no launch, read or argument of a round
+    changes).  witness: None, or a list that receives, when the run ends, the point global_ub is the network's value at -- one CPU fp32
+    tensor of the input shape, or None while global_ub is +inf -- as every loop of the reference returns global_ub_point
+    (plnn/branch_and_bound.py:157): per round one more launch keeps the point on the device, and N_0 floats cross the link once.
+    pgd_steps: None, or an integer >= 0: every child's upper value is the best of up to ``pgd_steps`` projected signed-gradient steps on
+    the network from its LP point (``gnnb_net_descend``; reference plnn/conv_kwinter_gen.py:54-135 without its restarts), each moving a
+    coordinate by ``pgd_step`` (0 < . <= 1) times its box width; 0 computes what None computes.  A traced round of a run with a witness
+    also carries "global_ub" and "witness_value", the device's copy of it.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds)       # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step)       # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
-        return _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
+        out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
+        if witness is not None:
+            witness.append(run.witness())
+        return out
     finally:
         if run.online_steps:                                      # the nn.Module mirrors the device, as GraphChoice.online_learning leaves it
             choice.model.load_blob(run.eng.get_weights())
@@ -489,6 +565,8 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
         st = run.read_state()
         if trace is not None and run.online is not None:
             trace[-1].update(_online_trace(run, st))
+        if trace is not None and run.witness_on:
+            trace[-1].update(global_ub=st[S.FS_GLOBAL_UB], witness_value=float(run.best_value.cpu()[0]))
         _check_record(st)
         rounds += 1
         bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE]) + 2 * run.m
@@ -655,8 +733,9 @@ class JobsRun(_Round):
     one more array, ``m_entry`` (``read_selected``), between its two halves."""
 
     def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
-                 sparsest_layer=0, decision_threshold=0.001):
+                 sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
         _check_threshold(branching_threshold, kwbd_threshold)
+        self._upper_bound_options(witness, pgd_steps, pgd_step)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
         eng = self.eng = choice.model.engine()
@@ -683,6 +762,9 @@ class JobsRun(_Round):
         self.pw, self.pb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
         self._buffers(n, 2 * n, in_shape, (self.px_lo, self.px_hi, self.ppw, self.ppb))
         self.ws_commit = self._ws("gnnb_frontier_commit_jobs_workspace_bytes", n)
+        self._witness_buffers(S)
+        if self.witness_on:
+            self.job_point = torch.zeros(len(jobs), N0, dtype=f32, device=dev)       # a job's witness, once it has left
         self.slots, self.row_seg = torch.zeros(n, dtype=i32, device=dev), torch.zeros(n, dtype=i32, device=dev)
         self.plan = RoundPlan(dev, S, S, cap)
         self.root_live = torch.tensor([1, 0] * S, dtype=i32).to(dev)
@@ -712,6 +794,8 @@ class JobsRun(_Round):
         self.seg_pw[seg].copy_(self.job_pw[job])
         self.seg_pb[seg].copy_(self.job_pb[job])
         self.seg_db[seg].copy_(self.job_db[job])
+        if self.witness_on:                                       # no incumbent yet
+            self.best_value[seg].fill_(float("inf"))
         if self.threshold is not None:                            # the job starts with its own counter and table: zero, device-side
             self.icp[seg].zero_()
             self.ineff[seg].zero_()
@@ -720,6 +804,15 @@ class JobsRun(_Round):
     def keep_used(self, seg, job):
         """The job of segment ``seg`` leaves: its count of KW pairs taken, device to device (read once, when the run ends)."""
         self.job_used[job].copy_(self.n_used[seg])
+
+    def keep_witness(self, seg, job):
+        """The job of segment ``seg`` leaves: its incumbent's point, device to device (read once, when the run ends)."""
+        self.job_point[job].copy_(self.best_point[seg])
+
+    def _witness(self, n, M):
+        """gnnb_frontier_witness_jobs on the rows the commit will see."""
+        self.eng.frontier_witness_jobs(self.plan, self.Ch, self._ub_points(self.Ch), self.best_value, self.best_point, M=M,
+                                       m_entry=self.m_entry if M else None, **self._pair_b_source(M))
 
     def _commit(self, slots):
         self.eng.frontier_commit_jobs(self.pool, self.plan, slots, *self.Ch.children(), self.pool.state, self.seg_db, eps=self.eps,
@@ -742,6 +835,8 @@ class JobsRun(_Round):
         Ch.split[:2 * E].fill_(-1)
         Ch.live[:2 * E] = self.root_live[:2 * E]
         self._bound_children(Ch, 2 * E, warm=False)
+        if self.witness_on:
+            self._witness(E, 0)
         self._commit(self.slots[:E])
 
     def compact(self, flagged):
@@ -789,6 +884,24 @@ class JobsRun(_Round):
         return self.pool.state.cpu().tolist()
 
 
+class FrontierJobs(list):
+    """A list of ``FrontierJob`` together with the upper-bound options of the run that verifies them: how
+    ``verify_properties`` and ``verify_properties_threshold`` take ``branch_and_bound_frontier``'s witness, pgd_steps and pgd_step.  (Their
+    own parameter lists are fixed.)  witness: None, or a list that receives one entry per job, in job order, when the run ends."""
+
+    def __init__(self, jobs, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
+        super().__init__(jobs)
+        self.witness, self.pgd_steps, self.pgd_step = witness, pgd_steps, pgd_step
+
+
+def _upper_of(jobs):
+    """The witness and descent options a ``FrontierJobs`` carries, checked (None for any other sequence of jobs: everything off)."""
+    if not isinstance(jobs, FrontierJobs):
+        return None
+    _check_witness(jobs.witness, jobs.pgd_steps, jobs.pgd_step)
+    return {"witness": jobs.witness, "pgd_steps": jobs.pgd_steps, "pgd_step": jobs.pgd_step}
+
+
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
     """Branch and bound on many jobs at once: every job gets the result ``branch_and_bound_frontier`` gives it alone with
     ``capacity=capacity``, bit for bit, while a round's launches serve all the jobs in flight.
@@ -800,11 +913,14 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
     flight (``plan_round``).  K, n_iter, lr, eps, max_rounds are ``branch_and_bound_frontier``'s, per job.  A job whose root is infeasible
     ends with the reason "infeasible_root" and the bounds (+inf, +inf).  trace: None, or a list that receives per round and per entry a
     dict of the one-job trace's keys (slots are global: segment * capacity + the job's own) plus "job", "segment" and "round" (extra
-    device-to-host copies: off in a timed run).
+    device-to-host copies: off in a timed run).  jobs given as ``FrontierJobs(jobs, witness=[], pgd_steps=N, pgd_step=s)`` run with
+    ``branch_and_bound_frontier``'s options of those names: ``witness`` receives one entry per job, in job order,
+    and a job's witness and bounds are what it gets alone with the same options.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    upper = _upper_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace)
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, upper=upper)
 
 
 def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
@@ -820,21 +936,25 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     sum.  stats: None, or a list that receives per job, in job order, the dict ``branch_and_bound_frontier`` fills ("branches",
     "kw_bounded", "kw_used", "domains_bounded").  trace: ``verify_properties``' keys per round and per entry plus the keys of the one-job
     threshold trace ("gnn_decisions", "gnn_improvement", "kw_decisions", "kw_improvement", "selected" -- rows counted from the entry's
-    first --, "used_kw", both pairs' bounds and infeasible flags; "decisions" are the final ones).
+    first --, "used_kw", both pairs' bounds and infeasible flags; "decisions" are the final ones).  A ``FrontierJobs`` carries
+    the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    upper = _upper_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if branching_threshold is None:
         raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
     threshold = {"branching_threshold": branching_threshold, "kwbd_threshold": kwbd_threshold, "sparsest_layer": sparsest_layer,
                  "decision_threshold": decision_threshold}
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats)
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats, upper)
 
 
-def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None):
+def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None):
     """The loop of ``verify_properties`` and ``verify_properties_threshold`` on checked arguments.  threshold: None, or the threshold mode's
-    arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists."""
-    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}))
+    arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists.  upper: None, or the witness and descent
+    options of section 7.8."""
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}))
+    witness = (upper or {}).get("witness")
     run.keep_pairs = trace is not None
     F, thr = _lib, threshold is not None
     results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
@@ -858,6 +978,8 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
                 log(f"job {j} segment {s}: {reason} after {rounds[j]} rounds, lb {results[j][0]:.5f} ub {results[j][1]:.5f}")
                 if thr:
                     run.keep_used(s, j)
+                if run.witness_on:
+                    run.keep_witness(s, j)
                 run.release(s)
                 seg_job[s], rec[s], capacity_stop[s] = None, None, False
         admitted = []
@@ -890,6 +1012,10 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
                 if thr:
                     trace[-1].update(_threshold_trace(run, k, e, row0))
         st = run.read_state()
+        if trace is not None and run.witness_on:
+            values = run.best_value.cpu().tolist()
+            for e, (s, _, _) in enumerate(entries):
+                trace[e - len(entries)].update(global_ub=st[s][F.FS_GLOBAL_UB], witness_value=values[s])
         for e, (s, _, k) in enumerate(entries):
             j = seg_job[s]
             rec[s] = st[s]
@@ -901,6 +1027,9 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
             log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
                 f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
     run.check_status()
+    if witness is not None:                                       # N_0 floats per job, read once
+        points = run.job_point.cpu()
+        witness.extend(None if math.isinf(results[j][1]) else points[j].reshape(in_shape) for j in range(len(jobs)))
     if thr and stats is not None:
         used = run.job_used.cpu().tolist()
         stats.extend({"branches": branches[j], "kw_bounded": kw_bounded[j], "domains_bounded": results[j][3], "kw_used": int(used[j])}

@@ -304,6 +304,31 @@ size_t gnnb_net_eval_workspace_bytes(const gnnb_t* h, int B);
 int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, const float* prop_b, int B, double* out, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- the second half of the reference's upper bound: descent on the real network from the LP point ----
+ * Projected signed-gradient descent on f(x) = gnnb_net_eval's value at the fp32 point x, per point, fp64: what get_upper_bound_pgd
+ * (reference plnn/conv_kwinter_gen.py:54-135) does from each child's LP point once the incumbent is positive
+ * (plnn/relu_conv_any_kw.py:143-149).  g(x) is the backward pass through the activations of f's own forward pass: g_L = prop_w where the
+ * last ReLU layer is positive, down every edge by its transpose, gated by 1[activation > 0] at every ReLU layer (torch's ReLU gradient),
+ * every sum in a fixed order.  The rule, per point: best = (f(x0), x0), unconditionally; for t = 0 .. n_steps - 1
+ *   x_{t+1}[m] = fl32(min(max((double)x_t[m] - step (x_hi[m] - x_lo[m]) sgn(g_t[m]), x_lo[m]), x_hi[m])),  sgn(0) = 0,
+ * rounded to nearest and, where rounding leaves [x_lo, x_hi], moved to the neighbouring float inside; f(x_{t+1}) < best, strictly, makes
+ * it the best; if not f(x_{t+1}) < f(x_t) the point stops (the reference's stop rule, :110; no comparison holds for a NaN).  A point with
+ * a NaN coordinate in x0, or whose f(x0) is NaN, takes no step.  Deliberately NOT the reference's: its 2056 random restarts (a caller who
+ * wants restarts passes B start points) and its step size, a min over the whole batch (:113-122), which would make a row depend on its
+ * batch.
+ * x0: device (B, N_0) fp32; x_lo / x_hi: device (B, N_0) fp64; prop_w (B, N_L), prop_b (B) fp32 as in gnnb_net_eval; step in (0, 1]: the
+ * share of the box's width a coordinate moves per step.  Outputs, device: x_best (B, N_0) fp32 (must not overlap x0); value (B) fp64 =
+ * f(x_best), bit for bit gnnb_net_eval's; grad0: NULL, or (B, N_0) fp64, g(x0), for inspection; steps_taken: NULL, or (B) int32, the
+ * steps evaluated.  n_steps = 0 gives x_best = x0 and value = gnnb_net_eval(x0), bit for bit.  One workgroup per point; the workspace
+ * holds the activations of every graph layer 0..L and two gradient buffers of the widest layer per point.  Stream-ordered, no allocation,
+ * no synchronisation, no atomics, no workgroup waits on another; a point's result does not depend on B or on its row.  GNNB_E_INVALID
+ * before any launch for a null handle or argument, B < 1, n_steps < 0 or a step outside (0, 1]; GNNB_E_STATE before gnnb_bind_network;
+ * GNNB_E_NOMEM for a short workspace. */
+size_t gnnb_net_descend_workspace_bytes(const gnnb_t* h, int B);
+int gnnb_net_descend(gnnb_t* h, const float* x0, const double* x_lo, const double* x_hi, const float* prop_w, const float* prop_b, int B,
+                     int n_steps, double step, float* x_best, double* value, double* grad0, int32_t* steps_taken, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Closes a round.  slots: the K parents (as given to gnnb_frontier_expand); eps; decision_bound (NaN: none); state: the record above,
  * read and updated.  In order: every live child's mask is resolved by its bounds (-1 with lo >= 0 -> 1, -1 with up <= 0 -> 0);
  * global_ub = min(global_ub, ub_value of every live feasible child); a live feasible child with an undecided node, bound <
@@ -471,6 +496,36 @@ int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan*
 int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decisions, const int32_t* kw_decisions, const int32_t* used_kw,
                         const double* gnn_improvement, const double* kw_improvement, int online_threshold, int32_t* wrong,
                         int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* n_learn, void* stream);
+
+/* ---- the witness of the upper bound ----
+ * Every loop of the reference returns global_ub_point next to global_ub (plnn/branch_and_bound.py:157, plnn/relu_conv_gnnkwthreshold.py:
+ * 209-214 and :268, plnn/relu_conv_online.py:225-228 and :276; experiments/bab_mip.py:50 stores it).  gnnb_frontier_witness keeps that point
+ * on the device: it runs after the choice and before gnnb_frontier_commit, on the child rows the commit will see, takes the minimum of
+ * ub_value over the live, feasible children on the total order (value, child index) -- a fixed tree with fmin semantics, a NaN never
+ * wins -- and, if that minimum is strictly below *best_value, copies the child's N_0 floats to best_point and writes *best_value.  The
+ * child's point is row c of x_a, unless used_kw[c >> 1] is set: then it is row 2j + (c & 1) of x_b with sel_rows[j] == c >> 1.  The caller
+ * starts best_value at +inf; after every commit *best_value is the state record's global upper bound, bit for bit.
+ * best_value: device (1) fp64 ((segments) in the jobs form); best_point: device (N_0) fp32 ((segments, N_0)).  children: the 2K rows
+ * (only live, infeasible and ub_value are read).  Stream-ordered, no allocation, no synchronisation, no atomics.  GNNB_E_INVALID before
+ * the launch for a null handle or argument, K outside 1..32767, m < 0 or m > K, used_kw with m > 0 but no x_b / sel_rows; GNNB_E_STATE
+ * before gnnb_bind_network. */
+typedef struct {
+  const float* x_a;            /* (2K, N_0): the points ub_value of pair A's rows was evaluated at      */
+  const float* x_b;            /* NULL, or pair B's (2m, N_0)                                          */
+  const int32_t* used_kw;      /* NULL, or (K) as gnnb_frontier_choose wrote it                        */
+  const int32_t* sel_rows;     /* NULL, or (m): row j of pair B belongs to parent row sel_rows[j]      */
+  int32_t m;
+} gnnb_witness_src;
+int gnnb_frontier_witness(gnnb_t* h, int K, const gnnb_children* children, const gnnb_witness_src* src, double* best_value,
+                          float* best_point, void* stream);
+
+/* gnnb_frontier_witness per plan entry {segment, row0, k} on its children (rows [2 row0, 2 row0 + 2k) of the 2n), with its range
+ * [sel0_e, sel0_e + m_e) of the dense lists (m_entry: device (n_entries + 1) as gnnb_frontier_fallback_jobs wrote it; M: the host's copy
+ * of their sum; src->m is not read; m_entry may be NULL when M = 0 or used_kw is NULL), on best_value[segment] and best_point[segment].
+ * Segments without an entry are not touched and nothing mixes two entries.  Refused like gnnb_frontier_witness, and for everything the
+ * plan checks of section 7.4 refuse and for M < 0 or M > n. */
+int gnnb_frontier_witness_jobs(gnnb_t* h, const gnnb_plan* plan, int M, const int32_t* m_entry, const gnnb_children* children,
+                               const gnnb_witness_src* src, double* best_value, float* best_point, void* stream);
 
 int gnnb_destroy(gnnb_t* h);
 
