@@ -380,8 +380,10 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
       {k_node_update<12, false, true, true>, kUpd3}, {k_node_update<12, true, true, true>, kUpd3},
       {k_input_update, PackUpdInp::FLOATS * 4}, {k_score, PackScore::FLOATS * 4},
       {k_gather<false>, k128}, {k_gather<true>, k128}, {k_gather16<false>, k128}, {k_gather16<true>, k128}, {k_gather16<false, true>, k128},
+      {k_gather16<false, false, true>, k128}, {k_gather16<true, false, true>, k128},
       {k_livesum, k160}, {k_gather_input_update<true, false>, k160}, {k_gather_input_update<true, true>, k160}, {k_gather<false, true>, k128},
       {k_gather_update_q<16, 0, false>, k160}, {k_gather_update_q<16, 1, false>, k160}, {k_gather_update_q<16, 2, false>, k160},
+      {k_gather_update_q<16, 0, false, true>, k160}, {k_gather_update_q<16, 2, false, true>, k160},
       {k_gather_update_q<32, 1, false>, k160}, {k_gather_update_q<32, 1, true>, k160},
       {k_classify_pre, CLSPRE_LDS_BYTES}, {k_scored_tail, k160 - 256},      // (k_scored_tail also has a few static words)
       {k_top<4>, TOP_LDS_FLOATS * 4}, {k_top<2>, TOP_LDS_FLOATS * 4}, {k_top<1>, TOP_LDS_FLOATS * 4}, {k_babsr, BABSR_LDS_MAX},
@@ -483,6 +485,14 @@ extern "C" int gnnb_bind_network(gnnb_t* h, const gnnb_layer_desc* L, int n, int
         if (!build_gather(net.edges[k], dir, dir == 1 && k > 1, gh, (dir == 1 && k == 1) ? 132 : 0, /*allow16=*/true)) continue;
         std::vector<int> tt;
         if (!tile_table(gh.g.tm, tt)) return fail(GNNB_E_INVALID, "layer %d: tile table overflow", k);
+        // edge 1 forward (dense source rows or the round-0 embedding, never the sparse walk): its tiles in block form where the walk exists
+        static_assert(BLK_NCY == kBlocktapRows, "the block-form walk is written for the window rows blocktap_ok asks for");
+        if (k == 1 && blocktap_ok(net.edges[k], dir, gh.g)) {
+          gh.g.block = BLOCKTAP_FORMS;
+          gh.g.ncy = blocktap_rows(net.edges[k]);
+          const std::vector<float> img = blocktap_image(net.edges[k], gh.g);
+          gh.cmat.insert(gh.cmat.end(), img.begin(), img.end());
+        }
         DevGather& d = dir == 0 ? net.gf[k] : net.gb[k];
         d.g = gh.g;
         HIPCHK(d.cmat.upload(gh.cmat.data(), gh.cmat.size()));
@@ -518,13 +528,15 @@ static DTileMap to_dtm(const TileMap& t) {
   return DTileMap{t.mode, t.N, t.C, t.H, t.W, t.CT, t.PY, t.PX, t.ay, t.ax, t.NBY, t.NBX, t.NCG, t.TPS, ilog2(t.PY), ilog2(t.PX),
                   t.TPS > 1 ? (unsigned)((1ull << 32) / (unsigned)t.TPS) + 1u : 0u};      // tile_sample (gnnb_dev.h); TPS <= 1 is handled there
 }
+// rows of 64 floats of an edge's tap images in LDS: the tap matrix, and behind it the block-form image where the edge has one
+static int cm_rows(const GatherGeom& g) { return g.tm.NCG * (g.K2 + (g.block ? g.ncy : 0)); }
 static DGather to_dg(const DevGather& d, const float* zero) {
   const GatherGeom& g = d.g;
-  return DGather{d.cmat.get(), reinterpret_cast<const int2*>(d.koff.get()), d.ttab.get(), zero, g.K2, g.tm.NCG * g.K2, g.Hs, g.Ws, g.Ns, g.ystep, g.ybase,
-                 g.xstep, g.xbase, g.WY, g.WX, g.normalise, g.kh, g.kw, g.stride, g.pad, g.lanes};
+  return DGather{d.cmat.get(), reinterpret_cast<const int2*>(d.koff.get()), d.ttab.get(), zero, g.K2, cm_rows(g), g.Hs, g.Ws, g.Ns, g.ystep, g.ybase,
+                 g.xstep, g.xbase, g.WY, g.WX, g.normalise, g.kh, g.kw, g.stride, g.pad, g.lanes, g.block, g.tm.NCG * g.K2 * 64};
 }
 static size_t gather_lds_bytes(const DevGather& d, size_t pack_floats) {
-  return (pack_floats + (size_t)d.g.tm.NCG * d.g.K2 * 64) * 4 + (size_t)gather_slots(d.g.K2, d.g.lanes) * 12 + (size_t)((d.g.tm.TPS + 3) & ~3) * 4;
+  return (pack_floats + (size_t)cm_rows(d.g) * 64) * 4 + (size_t)gather_slots(d.g.K2, d.g.lanes) * 12 + (size_t)((d.g.tm.TPS + 3) & ~3) * 4;
 }
 
 // per-wave live-slot tables of the sparse gathers (behind the shared tables, 8-byte aligned)
@@ -560,7 +572,7 @@ extern "C" int gnnb_graph_info(const gnnb_t* h, int* n_graph, int* sizes, int* n
 // k_gather_update_q over conv edge `d`: dynamic LDS bytes (weights, row queue, gather tables, per-gather-wave slot tables), and
 // whether the edge can take it at all (a sparse walk behind a ReLU layer, 16-node tiles without POST, everything in 160 KB)
 static size_t fusedq_lds_bytes(const DevGather& d, bool sparse, bool post, int qtiles) {
-  const size_t tables = (size_t)d.g.tm.NCG * d.g.K2 * 64 * 4 + (size_t)gather_slots(d.g.K2, d.g.lanes) * 8 + (size_t)((d.g.tm.TPS + 3) & ~3) * 4 +
+  const size_t tables = (size_t)cm_rows(d.g) * 64 * 4 + (size_t)gather_slots(d.g.K2, d.g.lanes) * 8 + (size_t)((d.g.tm.TPS + 3) & ~3) * 4 +
                         (size_t)((gather_slots(d.g.K2, d.g.lanes) + 3) & ~3) * 4;
   return (size_t)(PackUpdL3::FLOATS + (post ? 6144 : 0) + fusedq_queue_floats(qtiles)) * 4 + tables +
          (sparse ? (size_t)QG_WAVES * ((d.g.lanes == 16 ? 4 : 2) * d.g.K2 + 32) * 8 : 0);
@@ -1035,7 +1047,9 @@ struct Forward {
     constexpr int kGatherOcc = 2;     // workgroups per CU (k_gather's launch bounds; its LDS footprint is only the tap matrix)
     long grid = (a.ntiles + WAVES_MLP - 1) / WAVES_MLP;
     if (grid > (long)h->n_cu * kGatherOcc) grid = (long)h->n_cu * kGatherOcc;
-    void (*kern)(GArgs) = d.g.lanes == 16 ? (embed ? k_gather16<true> : sparse ? k_gather16<false, true> : k_gather16<false>)
+    const bool block = !sparse && (d.g.block & (embed ? 2 : 1));      // (a block-form edge: see gnnb_pack.h blocktap_ok)
+    void (*kern)(GArgs) = d.g.lanes == 16 ? (embed ? (block ? k_gather16<true, false, true> : k_gather16<true>) : sparse ? k_gather16<false, true>
+                                                    : (block ? k_gather16<false, false, true> : k_gather16<false>))
                                           : (embed ? k_gather<true> : sparse ? k_gather<false, true> : k_gather<false>);
     lz.run(PC_GATHER, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WG_MLP), lds, st, a); });
   }
@@ -1152,7 +1166,10 @@ struct Forward {
     a.qtiles = fusedq_qtiles(d, sparse, post_input);
     const size_t ldsq = fusedq_lds_bytes(d, sparse, post_input, a.qtiles);
     const long nrounds = (a.g.ntiles + QG_WAVES - 1) / QG_WAVES;
-    void (*kern)(FArgs) = d.g.lanes == 16 ? (embed ? k_gather_update_q<16, 2, false> : sparse ? k_gather_update_q<16, 1, false> : k_gather_update_q<16, 0, false>)
+    const bool block = !sparse && (d.g.block & (embed ? 2 : 1));
+    void (*kern)(FArgs) = d.g.lanes == 16 ? (embed ? (block ? k_gather_update_q<16, 2, false, true> : k_gather_update_q<16, 2, false>)
+                                                    : sparse ? k_gather_update_q<16, 1, false>
+                                                    : (block ? k_gather_update_q<16, 0, false, true> : k_gather_update_q<16, 0, false>))
                                           : (post_input ? k_gather_update_q<32, 1, true> : k_gather_update_q<32, 1, false>);
     const dim3 g((unsigned)std::max<long>(1, std::min<long>(nrounds, h->n_cu))), b((QG_WAVES + QC_WAVES) * 64);
     lz.run(PC_GATHER_UPDATE, [&] { hipLaunchKernelGGL(kern, g, b, ldsq, st, a); });

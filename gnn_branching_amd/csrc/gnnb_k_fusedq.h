@@ -242,8 +242,9 @@ __device__ unsigned long long g_qt_wall[2 * 16 * 1024];
 // is a ReLU layer), 2 round-0 embedding computed in the gather (16-node tiles only).  POST: see UpdArgs.
 // fusedq_body: one half-pass by this workgroup (all 16 waves call it; it starts with workgroup barriers; k_scored_tail shares q_chain).  Returns false when a wait hit its
 // iteration cap (status bit 1 is raised; the caller must leave the kernel), true when this wave's part of the half-pass is done.
-template <int LANES, int SRC, bool POST>
+template <int LANES, int SRC, bool POST, bool BLOCK = false>
 __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
+  static_assert(!BLOCK || (LANES == 16 && SRC != 1), "block form: 16-node tiles over dense or embedded source rows");
   constexpr bool SPARSE = SRC == 1, EMBED = SRC == 2;
   QT_DECL;
   float* qbase = lds + PackUpdL3::FLOATS + (POST ? 6144 : 0);
@@ -390,7 +391,7 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
     Frag X;
     f32x4 acc[4];
     if (LANES == 32) gather_compute_tile<false, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, el, lane, X, ssum);
-    else gather_compute_tile16<EMBED, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
+    else gather_compute_tile16<EMBED, SPARSE, BLOCK>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
     if (!a.sw_from_gather) ssum = __int_as_float(a.u.smod > 0 ? tc.n : gc);      // (q_chain: the index of the node's entry in u.sarr)
 
     QT_MARK(2);                                     // table build + walk
@@ -421,6 +422,9 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
             *reinterpret_cast<float2*>(d + 2 * (rr & 3) + 16 * (rr >> 2)) = make_float2(X.t[0][rr], X.t[1][rr]);
           if (h == 0)
             *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
+        } else if (BLOCK) {
+          if (lane < 16)                            // (block form: the node's own row only carries its trailer here, the channels follow below)
+            *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
         } else {
           const int gq = lane >> 4;                 // lane (j, g'): channels 16 g' + 4 r + t
           f32x4* d = reinterpret_cast<f32x4*>(row + 16 * gq);
@@ -428,6 +432,15 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
           for (int rr = 0; rr < 4; ++rr) d[rr] = f32x4{acc[0][rr], acc[1][rr], acc[2][rr], acc[3][rr]};
           if (gq == 0)
             *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
+        }
+      }
+      if (BLOCK) {
+        // block form: acc[pg] of lane (b, c) = channels 4b .. 4b+3 of tile lane blk_dst(pg, lane), whose ring row that lane knows
+        const int mypos = need ? pos : -1;
+#pragma unroll
+        for (int pg = 0; pg < 4; ++pg) {
+          const int pd = __shfl(mypos, blk_dst(pg, lane));
+          if (pd >= 0 && (pd >> 5) == T) *reinterpret_cast<f32x4*>(qbase + ((size_t)s * 32 + (pd & 31)) * QROW + 4 * (lane >> 2)) = acc[pg];
         }
       }
       const int lo = T * 32 > base ? T * 32 : base, hi = (T + 1) * 32 < base + n ? (T + 1) * 32 : base + n;
@@ -443,8 +456,8 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
   return !stuck;
 }
 
-template <int LANES, int SRC, bool POST>
+template <int LANES, int SRC, bool POST, bool BLOCK = false>
 __global__ __launch_bounds__((QG_WAVES + QC_WAVES) * 64, 4) void k_gather_update_q(FArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  fusedq_body<LANES, SRC, POST>(a, lds);
+  fusedq_body<LANES, SRC, POST, BLOCK>(a, lds);
 }

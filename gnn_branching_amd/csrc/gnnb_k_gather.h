@@ -16,6 +16,8 @@ struct DGather {
   const float* zero;     // 64 zero floats
   int K2, ncg_k2, Hs, Ws, Ns, ystep, ybase, xstep, xbase, WY, WX, normalise, kh, kw, stride, pad;
   int lanes;             // dst nodes per tile: 32 (32x32x2 MFMA, 2 window slots per k-step) or 16 (16x16x4, 4 slots per k-step)
+  int block, blk_off;        // block bit 0 / 1: the dense-row / round-0 embedding walk of 16-node tiles runs in block form (the BLOCK kernels) (gather_tile16_block): blocktap_image follows the tap matrix (ncg_k2 counts its
+                         // rows of 64 floats too) at float blk_off of the LDS image
 };
 
 #define STAGE16_FLOATS (16 * 68 + 16)      // per-wave LDS image of the gathers' row stores (store_tile16 / frag_store_rows_*_staged<16>)
@@ -267,6 +269,8 @@ __device__ __forceinline__ void gather_tile_embed(Frag& X, const float* cm, cons
 }
 
 // ---- 16-node tiles on v_mfma_f32_16x16x4_f32 (forward conv edges: a third less window per node than 32-node tiles) ----
+// (Edge 1 of a 3-channel 4 x 4 stride-2 first convolution, tile [8, 1, 2], does not take this form: its tap products run on the 16-block
+// v_mfma_f32_4x4x1_16b_f32, one position at a time -- "BLOCK form" below, the BLOCK kernels.)
 // lane l = (i = l & 15, g = l >> 4).  k-step s covers window slots 4s .. 4s+3; lane (i, g) loads channels 4i .. 4i+3 of slot 4s+g
 // (one b128; the 16 lanes of a group read one whole 256-B row) and feeds channel 4i+t to the MFMA of M-tile t; the B operand
 // is the tap weight of (slot 4s+g, dst node i).  D of tile t: lane (j, g'), register r = channel 16g' + 4r + t of dst node j,
@@ -674,8 +678,146 @@ __device__ __forceinline__ void gather_tile16_embed_mfma(f32x4 (&acc)[4], const 
   }
 }
 
-// the aggregate of one 16-node tile (forward edges only: no tap-count division): acc[t][r] of lane (j, g') = channel 16 g' + 4 r + t
-template <bool EMBED, bool SPARSE>
+// ---- 16-node forward tiles in BLOCK form: the tap products on v_mfma_f32_4x4x1_16b_f32 (gnnb_pack.h blocktap_ok / blocktap_image) ----
+// One instruction = 16 independent 4 x 4 x 1 outer products, 8 cycles.  A: lane e = channel e of ONE source row (block b = channels
+// 4b .. 4b+3; one coalesced 256-B dword load per row), B: lane (b, c) = the tap of that row for destination channel 4 gr + c of ONE
+// position (the same four values in all 16 blocks: every lane reads them from LDS, 16 bytes = the kw = 4 taps of a window row at once).
+// D = acc[pg], pg = 2 p + gr: lane (b, c), register v = channel 4b + v of destination node (channel 4 gr + c, position p), i.e. of tile
+// lane blk_dst(pg, lane).  The tile [8, 1, 2] walks its window rows (cs, ky); the six source rows of one are loaded once, position p
+// takes columns 2p .. 2p+3.  Per destination node this is the 16-column form's fma chain in the same slot order without the links whose
+// tap is structurally zero (the other position's columns, the k padding): the same bits for finite rows (a row that is already
+// non-finite no longer spreads through a zero tap: fewer neighbours raise the NaN status bit), at 16 x 8 = 128 cycles of the vector pipe
+// per window row, 1536 per tile, where the 16-column form spends 20 k-steps x 4 x 32 = 2560 (tools/micro/blocktap_cycles.hip).
+#ifndef BLOCKTAP_FORMS
+#define BLOCKTAP_FORMS 3      // DGather.block of an edge that can take the block form (dev A/B: 0 none, 1 dense rows only, 2 embedding only)
+#endif
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ int blk_dst(int pg, int lane) { return 2 * (4 * (pg & 1) + (lane & 3)) + (pg >> 1); }
+
+// The walk is straight-line code for BLK_NCY = 3 channels x BLK_KH = 4 window rows (blocktap_ok asks for exactly that first convolution):
+// with a run-time row count the loads sit behind branches, hipcc then waits for EVERY outstanding load in front of the first use of any
+// (s_waitcnt vmcnt(0) at the joins), and a tile paid one memory round trip per window row -- 18 % slower than the 16-column form.
+#define BLK_KH 4
+#define BLK_NCY (3 * BLK_KH)
+// dense source rows.  A gather wave lives on memory latency, not on its MFMAs (a tile's taps are ~1 us of the ~6 us a wave spends on it),
+// so what counts is how many rows it has in flight: a ring of BLK_DEPTH window rows (6 registers each) -- the registers of a window row
+// are requested again, for the window row BLK_DEPTH further on, as soon as its taps have run.
+#ifndef BLK_DEPTH
+#define BLK_DEPTH 6
+#endif
+template <bool INTERIOR>
+__device__ __forceinline__ void gather_tile16_block(f32x4 (&acc)[4], const float* img, __amdgpu_buffer_rsrc_t rsrc, int wy0, int wx0, int Hs, int Ws, int lane) {
+#pragma unroll
+  for (int pg = 0; pg < 4; ++pg) acc[pg] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x4* tp = reinterpret_cast<const f32x4*>(img) + (lane & 3);
+  const unsigned lane_off = 4u * (unsigned)lane;
+  float r[BLK_DEPTH][6];
+  auto load = [&](float (&d)[6], int cy) {
+    const int cs = cy / BLK_KH, wy = wy0 + cy % BLK_KH;
+    const int row0 = (cs * Hs + wy) * Ws + wx0;
+    if (INTERIOR) {
+      const unsigned soff = (unsigned)row0 * 256u;
+#pragma unroll
+      for (int x = 0; x < 6; ++x) d[x] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, lane_off + 256u * x, soff, 0));
+    } else {
+      const bool yin = (unsigned)wy < (unsigned)Hs;
+#pragma unroll
+      for (int x = 0; x < 6; ++x) {
+        const unsigned o = (yin && (unsigned)(wx0 + x) < (unsigned)Ws) ? (unsigned)(row0 + x) * 256u + lane_off : BUF_OOB;
+        d[x] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, o, 0, 0));
+      }
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < BLK_DEPTH && d < BLK_NCY; ++d) load(r[d], d);
+#pragma unroll
+  for (int cy = 0; cy < BLK_NCY; ++cy) {
+    f32x4 t[4];
+#pragma unroll
+    for (int pg = 0; pg < 4; ++pg) t[pg] = tp[(cy * 4 + pg) * 4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int pg = 0; pg < 4; ++pg) acc[pg] = mfma4(r[cy % BLK_DEPTH][x + 2 * (pg >> 1)], t[pg][x], acc[pg]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (cy + BLK_DEPTH < BLK_NCY) load(r[cy % BLK_DEPTH], cy + BLK_DEPTH);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// round 0: the rows are the input embedding E0 = relu(inp_f [l, x, u] + b), computed on the same instruction: rows = 4 window slots
+// (A = scalar k of slot x0 + i), columns x blocks = the 64 channels (B: lane = channel, its weight k), four instructions k = l, x, u, 1
+// chained from zero -- the K = 4 chain of gather_tile16_embed_mfma, rounding for rounding -- and D has lane = channel, register v =
+// slot x0 + v: the A operand of the tap instructions as it stands.  Two groups x0 = 0, 4 cover the six columns of a window row.
+// The scalars: lane (b, i) loads those of slot 4 (b & 1) + i of window row cy0 + (b >> 1), so ONE register per kind holds eight window
+// rows, and the embedding instruction of (row u, group g) takes block 2u + g of it for all 16 blocks (cbsz = 4, abid = 2u + g): two
+// sets of three loads, all requested before the first instruction -- one memory round trip per tile.  An out-of-range slot feeds
+// zeros, its 1 included: its embedding is relu(0) = 0.
+template <int ABID>
+__device__ __forceinline__ f32x4 mfma4_bc(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, ABID, 0); }
+struct BlkIn { float l, x, u, one; };
+template <int U>
+__device__ __forceinline__ void blk_embed_row(f32x4 (&acc)[4], const BlkIn& s, const f32x4* tp, int cy, float w0, float w1, float w2, float w3) {
+  float r[8];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    f32x4 e = g ? mfma4_bc<2 * U + 1>(s.l, w0, f32x4{0.f, 0.f, 0.f, 0.f}) : mfma4_bc<2 * U>(s.l, w0, f32x4{0.f, 0.f, 0.f, 0.f});
+    e = g ? mfma4_bc<2 * U + 1>(s.x, w1, e) : mfma4_bc<2 * U>(s.x, w1, e);
+    e = g ? mfma4_bc<2 * U + 1>(s.u, w2, e) : mfma4_bc<2 * U>(s.u, w2, e);
+    e = g ? mfma4_bc<2 * U + 1>(s.one, w3, e) : mfma4_bc<2 * U>(s.one, w3, e);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) r[4 * g + v] = relu_max(e[v]);
+  }
+  f32x4 t[4];
+#pragma unroll
+  for (int pg = 0; pg < 4; ++pg) t[pg] = tp[(cy * 4 + pg) * 4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x)
+#pragma unroll
+    for (int pg = 0; pg < 4; ++pg) acc[pg] = mfma4(r[x + 2 * (pg >> 1)], t[pg][x], acc[pg]);
+}
+__device__ __forceinline__ void gather_tile16_block_embed(f32x4 (&acc)[4], const float* img, __amdgpu_buffer_rsrc_t rl, __amdgpu_buffer_rsrc_t rx,
+                                                          __amdgpu_buffer_rsrc_t ru, const float* wb, int wy0, int wx0, int Hs, int Ws, int lane) {
+  static_assert(BLK_NCY > 8 && BLK_NCY <= 16, "two sets of eight window rows");
+#pragma unroll
+  for (int pg = 0; pg < 4; ++pg) acc[pg] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float w0 = wb[3 * lane], w1 = wb[3 * lane + 1], w2 = wb[3 * lane + 2], w3 = wb[192 + lane];
+  const f32x4* tp = reinterpret_cast<const f32x4*>(img) + (lane & 3);
+  const int i = lane & 3, g = (lane >> 2) & 1, du = lane >> 3;
+  const int wx = wx0 + 4 * g + i;
+  const bool xin = 4 * g + i < 6 && (unsigned)wx < (unsigned)Ws;
+  auto fetch = [&](BlkIn& s, int cy0) {
+    const int cy = cy0 + du;
+    const int cs = cy / BLK_KH, wy = wy0 + cy % BLK_KH;
+    const bool inb = xin && cy < BLK_NCY && (unsigned)wy < (unsigned)Hs;
+    const unsigned o = inb ? (unsigned)((cs * Hs + wy) * Ws + wx) * 4u : BUF_OOB;
+    s.l = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, o, 0, 0));
+    s.x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, o, 0, 0));
+    s.u = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ru, o, 0, 0));
+    s.one = inb ? 1.0f : 0.0f;
+  };
+  BlkIn s0, s1;
+  fetch(s0, 0);
+  fetch(s1, 8);
+  __builtin_amdgcn_sched_barrier(0);
+  blk_embed_row<0>(acc, s0, tp, 0, w0, w1, w2, w3);
+  blk_embed_row<1>(acc, s0, tp, 1, w0, w1, w2, w3);
+  blk_embed_row<2>(acc, s0, tp, 2, w0, w1, w2, w3);
+  blk_embed_row<3>(acc, s0, tp, 3, w0, w1, w2, w3);
+  blk_embed_row<4>(acc, s0, tp, 4, w0, w1, w2, w3);
+  blk_embed_row<5>(acc, s0, tp, 5, w0, w1, w2, w3);
+  blk_embed_row<6>(acc, s0, tp, 6, w0, w1, w2, w3);
+  blk_embed_row<7>(acc, s0, tp, 7, w0, w1, w2, w3);
+  if (BLK_NCY > 8) blk_embed_row<0>(acc, s1, tp, 8, w0, w1, w2, w3);
+  if (BLK_NCY > 9) blk_embed_row<1>(acc, s1, tp, 9, w0, w1, w2, w3);
+  if (BLK_NCY > 10) blk_embed_row<2>(acc, s1, tp, 10, w0, w1, w2, w3);
+  if (BLK_NCY > 11) blk_embed_row<3>(acc, s1, tp, 11, w0, w1, w2, w3);
+  static_assert(BLK_NCY <= 12, "blk_embed_row calls above");
+}
+
+// the aggregate of one 16-node tile (forward edges only: no tap-count division): acc[t][r] of lane (j, g') = channel 16 g' + 4 r + t;
+// a block-form edge (a.g.block): acc[pg][v] of lane (b, c) = channel 4b + v of tile lane blk_dst(pg, lane)
+template <bool EMBED, bool SPARSE, bool BLOCK = false>
 __device__ __forceinline__ void gather_compute_tile16(const GArgs& a, const TileCtx& tc, int sample, const float* lds_cm, const int2* lds_ko,
                                                       const unsigned* lds_kvo, uint2* tab, const float (&ew)[4][3], const float (&eb)[4], int lane,
                                                       f32x4 (&acc)[4], float& ssum) {
@@ -683,6 +825,22 @@ __device__ __forceinline__ void gather_compute_tile16(const GArgs& a, const Tile
   const int wy0 = tc.by * a.g.ystep + a.g.ybase, wx0 = tc.bx * a.g.xstep + a.g.xbase;
   const int uy = __builtin_amdgcn_readfirstlane(wy0), ux = __builtin_amdgcn_readfirstlane(wx0);
   const bool interior = uy >= 0 && ux >= 0 && uy + a.g.WY <= a.g.Hs && ux + a.g.WX <= a.g.Ws;
+  if constexpr (BLOCK) {
+    const float* img = lds_cm + a.g.blk_off + tc.cg * (BLK_NCY * 64);
+    if (EMBED) {
+      const long sb = (long)sample * a.g.Ns;
+      const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)(a.es.lb + sb), 0, a.g.Ns * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.es.x + sb), 0, a.g.Ns * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(a.es.ub + sb), 0, a.g.Ns * 4, 0x00020000);
+      gather_tile16_block_embed(acc, img, rl, rx, ru, a.es.wb, uy, ux, a.g.Hs, a.g.Ws, lane);
+    } else {
+      const float* sbase = a.mu_src + (long)sample * a.g.Ns * 64;
+      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, a.g.Ns * 256, 0x00020000);
+      if (interior) gather_tile16_block<true>(acc, img, rsrc, uy, ux, a.g.Hs, a.g.Ws, lane);
+      else gather_tile16_block<false>(acc, img, rsrc, uy, ux, a.g.Hs, a.g.Ws, lane);
+    }
+    return;
+  }
   const float* cmt = lds_cm + tc.cg * a.g.K2 * 64;
   if (EMBED) {
     const long sb = (long)sample * a.g.Ns;
@@ -714,8 +872,17 @@ __device__ __forceinline__ void gather_compute_tile16(const GArgs& a, const Tile
 // The aggregate rows of a 16-node tile -> HBM.  Lane (j, g') holds channels 16 g' + 4 r + t of node j; stored straight from
 // there one wave instruction writes 16-B pieces at a 64-B stride (every 64-B sector a quarter full, four times).  Through a
 // 4.3 KB per-wave LDS image (rows padded to 68 floats) each instruction writes four whole 256-B rows instead.
-__device__ __forceinline__ void store_tile16(const f32x4 (&acc)[4], float* stage, float* nb, long gc, bool need, int lane) {
+__device__ __forceinline__ void store_tile16(const f32x4 (&acc)[4], float* stage, float* nb, long gc, bool need, int lane, bool block = false) {
   const int j = lane & 15, gq = lane >> 4;
+  if (block) {      // block form: acc[pg] of lane (b, c) = channels 4b .. 4b+3 of tile lane blk_dst(pg, lane): one instruction writes four whole rows
+    const int mine = need ? (int)gc : -1;
+#pragma unroll
+    for (int pg = 0; pg < 4; ++pg) {
+      const int g = __shfl(mine, blk_dst(pg, lane));
+      if (g >= 0) *reinterpret_cast<f32x4*>(nb + (long)g * 64 + 4 * (lane >> 2)) = acc[pg];
+    }
+    return;
+  }
   if (!stage) {
     if (need) {
       f32x4* p = reinterpret_cast<f32x4*>(nb + gc * 64 + 16 * gq);
@@ -740,7 +907,7 @@ __device__ __forceinline__ void store_tile16(const f32x4 (&acc)[4], float* stage
   __builtin_amdgcn_wave_barrier();
 }
 
-template <bool EMBED, bool SPARSE>
+template <bool EMBED, bool SPARSE, bool BLOCK = false>
 __device__ __forceinline__ void gather_process_tile16(const GArgs& a, const TileCtx& tc, int sample, const float* lds_cm, const int2* lds_ko,
                                                       const unsigned* lds_kvo, uint2* tab, const float (&ew)[4][3], const float (&eb)[4], int lane,
                                                       float* stage = nullptr) {
@@ -752,9 +919,9 @@ __device__ __forceinline__ void gather_process_tile16(const GArgs& a, const Tile
   else need = tc.valid && node_is_live(a.lb[gc], a.ub[gc]);
   if (!__any(need)) return;
   f32x4 acc[4];
-  gather_compute_tile16<EMBED, SPARSE>(a, tc, sample, lds_cm, lds_ko, lds_kvo, tab, ew, eb, lane, acc, ssum);
+  gather_compute_tile16<EMBED, SPARSE, BLOCK>(a, tc, sample, lds_cm, lds_ko, lds_kvo, tab, ew, eb, lane, acc, ssum);
   if (SPARSE && need && gq == 0 && a.sout) a.sout[gc] = ssum;
-  store_tile16(acc, stage, a.nb, gc, need, lane);
+  store_tile16(acc, stage, a.nb, gc, need, lane, BLOCK);
 }
 
 // LDS image of a gather's tables: tap matrix, window offsets (two forms), tile table
@@ -799,7 +966,7 @@ __global__ __launch_bounds__(WG_MLP, 2) void k_gather(GArgs a) {
 
 // the 16-node-tile form of k_gather (forward conv edges)
 // (4 waves per SIMD: the embedding variant sits right at 128 VGPRs, and at 130 it loses a quarter of its waves and 10 %)
-template <bool EMBED, bool SPARSE = false>
+template <bool EMBED, bool SPARSE = false, bool BLOCK = false>      // BLOCK: the edge's tiles in block form (DGather.block; never with SPARSE)
 __global__ __launch_bounds__(WG_MLP, 4) void k_gather16(GArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const GatherLds gl = gather_lds(lds, a.g, a.tm.TPS);
@@ -847,14 +1014,10 @@ __global__ __launch_bounds__(WG_MLP, 4) void k_gather16(GArgs a) {
       if (!__any(need)) { FT_MARK(1); continue; }
       FT_MARK(1);                               // bounds of the dst nodes (one memory round trip)
       f32x4 acc[4];
-      gather_compute_tile16<EMBED, SPARSE>(a, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
+      gather_compute_tile16<EMBED, SPARSE, BLOCK>(a, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
       FT_MARK(2);                               // walk
-      if (need) {
-        f32x4* p = reinterpret_cast<f32x4*>(a.nb + gc * 64 + 16 * gq);
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) p[r4] = f32x4{acc[0][r4], acc[1][r4], acc[2][r4], acc[3][r4]};
-        if (SPARSE && gq == 0 && a.sout) a.sout[gc] = ssum;
-      }
+      store_tile16(acc, nullptr, a.nb, gc, need, lane, BLOCK);
+      if (need && SPARSE && gq == 0 && a.sout) a.sout[gc] = ssum;
       FT_MARK(3);                               // store issue
 #if FUSED_TIMING > 1
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -862,7 +1025,7 @@ __global__ __launch_bounds__(WG_MLP, 4) void k_gather16(GArgs a) {
 #endif
     }
 #else
-    gather_process_tile16<EMBED, SPARSE>(a, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, stage);
+    gather_process_tile16<EMBED, SPARSE, BLOCK>(a, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, stage);
 #endif
   }
 #ifdef FUSED_TIMING

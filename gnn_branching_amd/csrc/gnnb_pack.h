@@ -542,6 +542,8 @@ struct GatherGeom {     // everything the kernel needs besides the tables
   int ystep = 0, ybase = 0, xstep = 0, xbase = 0;   // window origin: wy0 = by*ystep + ybase
   int WY = 0, WX = 0;
   int normalise = 0, kh = 0, kw = 0, stride = 0, pad = 0;
+  int block = 0;        // forward 16-node tiles in block form (blocktap_ok): blocktap_image follows the tap matrix in `cmat`; ncy: its window rows per tile
+  int ncy = 0;
 };
 
 struct GatherHost {
@@ -646,6 +648,38 @@ inline bool build_gather(const Edge& e, int dir, bool normalise, GatherHost& bes
   best.g.normalise = normalise ? 1 : 0;
   fill_gather_tables(e, dir, best);
   return true;
+}
+
+// ------------------------------------------------------------------------------------------
+// Block form of a forward 16-node tile (gather_tile16_block, gnnb_k_gather.h): the tap products on v_mfma_f32_4x4x1_16b_f32.  One
+// instruction is 16 independent 4 x 4 x 1 outer products: block b = channels 4b .. 4b+3 of ONE source row, the 4 columns = 4 destination
+// channels of ONE position, so a position walks only its own kh x kw x Cs taps (the 16-column form multiplies the union window of the
+// tile's positions by every destination, structural zeros included) in the same (cs, ky, kx) order: the same fma chain per destination
+// node without the links whose tap is structurally zero.
+// The walk is written for the tile every 4 x 4 stride-2 first convolution of the shipped networks gets: CT = 8 channels x PX = 2
+// positions along x (4 accumulators: position p, channel group gr), kw = 4 taps per window row = one 16-byte read per lane, 3 x 4 window rows.
+// Image (behind the 16-column tap matrix in `cmat`, which the edge's other walks keep):
+//   [cg][cy = cs * kh + ky][pg = 2 p + gr][c = 0..3][kx = 0..3]  =  w[co = 8 cg + 4 gr + c][cs][ky][kx]      (the same for both positions p)
+// ------------------------------------------------------------------------------------------
+constexpr int kBlocktapRows = 12;      // window rows (cs, ky) of the walk: 3 channels x 4 (BLK_NCY of gnnb_k_gather.h: straight-line code)
+inline bool blocktap_ok(const Edge& e, int dir, const GatherGeom& g) {
+  return dir == 0 && e.kind == 0 && e.kh == 4 && e.c_in * e.kh == kBlocktapRows && g.lanes == 16 && g.tm.mode == 1 && g.tm.CT == 8 && g.tm.PY == 1 && g.tm.PX == 2 && e.kw == 4 && e.stride == 2 &&
+         g.WX == 6 && g.WY == e.kh;
+}
+inline int blocktap_rows(const Edge& e) { return e.c_in * e.kh; }      // window rows (cs, ky) a tile walks
+inline std::vector<float> blocktap_image(const Edge& e, const GatherGeom& g) {
+  const int ncy = blocktap_rows(e);
+  std::vector<float> img((size_t)g.tm.NCG * ncy * 64, 0.f);
+  for (int cg = 0; cg < g.tm.NCG; ++cg)
+    for (int cs = 0; cs < e.c_in; ++cs)
+      for (int ky = 0; ky < e.kh; ++ky)
+        for (int pg = 0; pg < 4; ++pg)
+          for (int c = 0; c < 4; ++c)
+            for (int kx = 0; kx < 4; ++kx) {
+              const int co = cg * 8 + 4 * (pg & 1) + c;
+              img[(((size_t)cg * ncy + cs * e.kh + ky) * 4 + pg) * 16 + c * 4 + kx] = e.w[(((size_t)co * e.c_in + cs) * e.kh + ky) * e.kw + kx];
+            }
+  return img;
 }
 
 // ------------------------------------------------------------------------------------------
