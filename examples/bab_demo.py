@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18] [--witness] [--pgd 4]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -16,7 +16,8 @@ the true one, every round's launches serving all the properties in flight; one v
 the fall-back for every property (frontier.verify_properties_threshold): each has its own intercept counter and table of
 inefficient points, and one round bounds the second pairs of all the properties' selected parents together.  --witness (with --frontier)
 also returns the input point the upper bound belongs to -- the counter-example, when the verdict is one -- and prints the network's value
-at it; --pgd N lowers every child's upper bound by up to N projected gradient steps on the network from its LP point.
+at it; --pgd N lowers every child's upper bound by up to N projected gradient steps on the network from its LP point (DESIGN.md section 7.8);
+--restarts R with --pgd N also descends from R uniform points of every child's box and keeps the least value (section 7.9; --pgd 0: the points alone).
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -50,10 +51,13 @@ def main():
     ap.add_argument("--props", type=int, default=None, metavar="N", help="with --frontier: verify N properties (seeds x wrong classes) in one frontier")
     ap.add_argument("--witness", action="store_true", help="with --frontier: return the point of the upper bound and print the network's value at it")
     ap.add_argument("--pgd", type=int, default=None, metavar="N", help="with --frontier: up to N projected gradient steps from every child's LP point")
+    ap.add_argument("--restarts", type=int, default=None, metavar="R", help="with --pgd N: also descend from R uniform points of every child's box")
     args = ap.parse_args()
+    if args.restarts is not None and (args.pgd is None or not 0 <= args.restarts <= 4096):
+        ap.error("--restarts R needs --pgd N, and 0 <= R <= 4096")
     if (args.witness or args.pgd is not None) and (args.frontier is None or (args.pgd is not None and args.pgd < 0)):
         ap.error("--witness and --pgd N need --frontier K, and N >= 0")
-    upper = {"witness": [] if args.witness else None, "pgd_steps": args.pgd}
+    upper = {"witness": [] if args.witness else None, "pgd_steps": args.pgd, "pgd_restarts": args.restarts}
 
     def witness_of(point, fixed, prop_layer):
         """The network's value (fp64, torch on the host) at a witness."""

@@ -62,6 +62,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_kw.h"
 #include "gnnb_k_dual.h"
 #include "gnnb_k_frontier.h"
+#include "gnnb_k_starts.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -95,7 +96,8 @@ enum ProfClass {
   PC_KW_FIRST, PC_KW_LAYER, PC_KW_FLAG, PC_DUAL,
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
   PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS,
-  PC_FR_LEARN, PC_TROWS_GATHER, PC_NET_DESCEND, PC_FR_WITNESS, PC_FR_WITNESS_JOBS, PC_COUNT
+  PC_FR_LEARN, PC_TROWS_GATHER, PC_NET_DESCEND, PC_FR_WITNESS, PC_FR_WITNESS_JOBS,
+  PC_NET_STARTS, PC_NET_DESCEND_TILE, PC_NET_STARTS_PICK, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -105,7 +107,8 @@ static const char* kProfNames[PC_COUNT] = {
     "k_frontier_pick_jobs", "k_frontier_rows_jobs", "k_frontier_decide_jobs",
     "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
     "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs",
-    "k_frontier_learn", "k_trows_gather", "k_net_descend", "k_frontier_witness", "k_frontier_witness_jobs"};
+    "k_frontier_learn", "k_trows_gather", "k_net_descend", "k_frontier_witness", "k_frontier_witness_jobs",
+    "k_net_starts", "k_net_descend_tile", "k_net_starts_pick"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -1810,6 +1813,78 @@ extern "C" int gnnb_net_descend(gnnb_t* h, const float* x0, const double* x_lo, 
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
   run.run(PC_NET_DESCEND, [&] { hipLaunchKernelGGL(k_net_descend, dim3(B), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+// ---- the upper bound from many starts (reference plnn/conv_kwinter_gen.py:20-52 and :54-135) ----
+extern "C" int gnnb_net_starts(gnnb_t* h, const float* x0, const double* x_lo, const double* x_hi, int B, int R, uint64_t seed, float* starts,
+                               void* stream) {
+  const char* who = "gnnb_net_starts";
+  if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
+  if (R < 0 || R > NS_MAX_RANDOM) return fail(GNNB_E_INVALID, "%s: R = %d outside 0..%d", who, R, NS_MAX_RANDOM);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
+  const int ng = h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (!x0 || !x_lo || !x_hi || !starts) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (starts == x0) return fail(GNNB_E_INVALID, "%s: starts must not overlap x0", who);
+  NetStartsArgs a{};
+  a.x0 = x0; a.x_lo = x_lo; a.x_hi = x_hi; a.starts = starts; a.N0 = h->kw_net.N[0]; a.R = R; a.seed = seed;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_NET_STARTS, [&] { hipLaunchKernelGGL(k_net_starts, dim3(B, (R + NS_SLOTS) / NS_SLOTS), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_net_descend_starts_tile(void) { return NS_TILE; }
+
+struct NsWs { size_t val, xb, total; };              // byte offsets in gnnb_net_descend_starts' workspace: the tiles' activations and gradients at 0
+static NsWs ns_ws_layout(const gnnb_t* h, int B, int n_starts) {
+  const size_t tiles = (size_t)B * ((n_starts + NS_TILE - 1) / NS_TILE);
+  NsWs w;
+  w.val = (tiles * NS_TILE * net_descend_doubles(h->kw_net) * sizeof(double) + 255) & ~(size_t)255;
+  w.xb = w.val + (((size_t)B * n_starts * sizeof(double) + 255) & ~(size_t)255);
+  w.total = w.xb + (((size_t)B * n_starts * h->kw_net.N[0] * sizeof(float) + 255) & ~(size_t)255);
+  return w;
+}
+
+extern "C" size_t gnnb_net_descend_starts_workspace_bytes(const gnnb_t* h, int B, int n_starts) {
+  if (!h || !h->bound || B < 1 || n_starts < 1 || n_starts > NS_MAX_RANDOM + 1) return 0;
+  return ns_ws_layout(h, B, n_starts).total;
+}
+
+extern "C" int gnnb_net_descend_starts(gnnb_t* h, const float* starts, int n_starts, const double* x_lo, const double* x_hi, const float* prop_w,
+                                       const float* prop_b, int B, int n_steps, double step, float* x_best, double* value, int32_t* start_index,
+                                       double* start_value, int32_t* start_steps, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_net_descend_starts";
+  if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
+  if (n_starts < 1 || n_starts > NS_MAX_RANDOM + 1) return fail(GNNB_E_INVALID, "%s: n_starts = %d outside 1..%d", who, n_starts, NS_MAX_RANDOM + 1);
+  if (n_steps < 0) return fail(GNNB_E_INVALID, "%s: n_steps = %d", who, n_steps);
+  if (!(step > 0.0 && step <= 1.0)) return fail(GNNB_E_INVALID, "%s: step = %g (0 < . <= 1)", who, step);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
+  const int ng = h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (!starts || !x_lo || !x_hi || !prop_w || !prop_b || !x_best || !value || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (x_best == starts) return fail(GNNB_E_INVALID, "%s: x_best must not overlap starts", who);
+  if ((long)B * ((n_starts + NS_TILE - 1) / NS_TILE) > 0x7fffffffL) return fail(GNNB_E_INVALID, "%s: B = %d rows of %d starts: too many tiles", who, B, n_starts);
+  const NsWs w = ns_ws_layout(h, B, n_starts);
+  if (workspace_bytes < w.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, w.total);
+  const int tiles = B * ((n_starts + NS_TILE - 1) / NS_TILE);
+  NetTileArgs a{};
+  a.net = h->kw_net;
+  a.starts = starts; a.n_starts = n_starts; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
+  a.n_steps = n_steps; a.step = step;
+  a.ws = (double*)workspace; a.ws_stride = (long)NS_TILE * net_descend_doubles(h->kw_net); a.width = net_eval_width(h->kw_net);
+  a.val = (double*)((char*)workspace + w.val); a.xb = (float*)((char*)workspace + w.xb); a.steps_taken = start_steps;
+  for (int k = 0; k <= a.net.L; ++k) a.act_off[k + 1] = a.act_off[k] + a.net.N[k];
+  NetPickArgs p{};
+  p.xb = a.xb; p.val = a.val; p.n_starts = n_starts; p.N0 = a.net.N[0];
+  p.x_best = x_best; p.value = value; p.start_index = start_index; p.start_value = start_value;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_NET_DESCEND_TILE, [&] { hipLaunchKernelGGL(k_net_descend_tile<NS_TILE>, dim3(tiles), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_NET_STARTS_PICK, [&] { hipLaunchKernelGGL(k_net_starts_pick, dim3(B), dim3(FR_THREADS), 0, st, p); });
   return run.rc;
 }
 

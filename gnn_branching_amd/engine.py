@@ -940,6 +940,65 @@ class ScorerEngine:
                    ws.data_ptr(), ws.numel())
         return x_best, value, grad0, steps
 
+    def net_starts(self, fixed_layers, x0, x_lo, x_hi, n_random, seed=0, starts=None):
+        """gnnb_net_starts on the current stream: the start points of B rows, (B, n_random + 1, N_0) fp32.  Slot 0
+        of row b is x0[b] ((B, C, H, W) or (B, N_0) fp32 on the device); slot r >= 1 is a counter-based uniform point of the row's box
+        [x_lo, x_hi] ((B, N_0) fp64 device tensors) that depends on the row's own x0, box and ``seed`` (0..2^64 - 1) only.  starts: a tensor
+        to write to (None: a new one).  Nothing is synchronised."""
+        B, R = int(x0.shape[0]), int(n_random)
+        self.bind(fixed_layers, tuple(x0.shape[1:]))
+        N0, f64, f32 = self.sizes[0], torch.float64, torch.float32
+        x0 = self._rows(x0, B, N0, f32, "x0")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed = {seed!r}: an integer in 0..2^64 - 1")
+        n = max(R, 0) + 1
+        starts = torch.empty(B, n, N0, dtype=f32, device=self.device) if starts is None else self._rows(starts, B, n * N0, f32, "starts")
+        self._call("gnnb_net_starts", x0.data_ptr(), self._rows(x_lo, B, N0, f64, "x_lo").data_ptr(), self._rows(x_hi, B, N0, f64, "x_hi").data_ptr(),
+                   B, R, seed, starts.data_ptr())
+        return starts
+
+    def net_descend_starts(self, fixed_layers, prop_layers, starts, x_lo, x_hi, n_steps, step=1.0 / 64, x_best=None, value=None,
+                           want_index=False, want_values=False, want_steps=False, prop=None, workspace=None, in_shape=None):
+        """gnnb_net_descend_starts on the current stream: ``net_descend``'s rule from every one of the n_starts
+        start points of every row -- starts: (B, n_starts, N_0) fp32 on the device, row b's inside [x_lo[b], x_hi[b]] ((B, N_0) fp64)
+        under property row b (prop_layers / prop: as ``net_eval``) -- and per row the minimum of the starts' best values in the order
+        (value, start index), a NaN never winning.  x_best (B, N_0) fp32 and value (B,) fp64: tensors to write to (None: new ones; x_best
+        must not be starts).  Returns (x_best, value, index, values, steps): the winner's point and value (``net_eval``'s, bit for bit),
+        its slot ((B,) int32) with ``want_index``, every start's best value ((B, n_starts) fp64) with ``want_values`` and steps evaluated
+        ((B, n_starts) int32) with ``want_steps``, else None.  in_shape: the network's input shape (None: the one the engine is bound
+        with, ``net_starts``' for instance).  Nothing is synchronised."""
+        if not torch.is_tensor(starts) or starts.dim() != 3:
+            raise ValueError("starts: expected a (B, n_starts, N_0) tensor")
+        B, n = int(starts.shape[0]), int(starts.shape[1])
+        if in_shape is None:                                      # (the start points are flat: the shape comes from the bind before, net_starts' say)
+            if self._net_key is None:
+                raise ValueError("in_shape: the network's input shape is needed to bind it")
+            in_shape = self._net_key[2]
+        self.bind(fixed_layers, tuple(in_shape))
+        N0, f64, f32, i32 = self.sizes[0], torch.float64, torch.float32, torch.int32
+        starts = self._rows(starts, B, n * N0, f32, "starts")
+        pw, pb = self._prop(prop_layers) if prop is None else prop
+        pw, pb = self._rows(pw, B, self.sizes[-2], f32, "property weights"), self._rows(pb, B, 1, f32, "property biases")
+        x_best = torch.empty(B, N0, dtype=f32, device=self.device) if x_best is None else self._rows(x_best, B, N0, f32, "x_best")
+        value = torch.empty(B, dtype=f64, device=self.device) if value is None else self._rows(value, B, 1, f64, "value")
+        index = torch.empty(B, dtype=i32, device=self.device) if want_index else None
+        values = torch.empty(B, n, dtype=f64, device=self.device) if want_values else None
+        steps = torch.empty(B, n, dtype=i32, device=self.device) if want_steps else None
+        if workspace is None:
+            workspace = self._starts_workspace(B, n)
+        self._call("gnnb_net_descend_starts", starts.data_ptr(), n, self._rows(x_lo, B, N0, f64, "x_lo").data_ptr(),
+                   self._rows(x_hi, B, N0, f64, "x_hi").data_ptr(), pw.data_ptr(), pb.data_ptr(), B, int(n_steps), float(step), x_best.data_ptr(),
+                   value.data_ptr(), ptr(index), ptr(values), ptr(steps), workspace.data_ptr(), workspace.numel())
+        return x_best, value, index, values, steps
+
+    def _starts_workspace(self, B, n_starts):
+        """The engine's own workspace of ``net_descend_starts``, grown on demand."""
+        need = max(1, self.lib.gnnb_net_descend_starts_workspace_bytes(self.h, B, n_starts))
+        ws = getattr(self, "_ws_starts", None)
+        if ws is None or ws.numel() < need:
+            ws = self._ws_starts = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
     # ---- a BaB frontier in device memory (frontier.py runs the loop; include/gnnb.h gnnb_frontier_*) ---------------------------------
     def _rows(self, t, n, cols, dtype, what):
         """t as it is, checked: a contiguous device tensor of ``dtype`` holding at least n rows of ``cols`` (the steps below copy nothing)."""

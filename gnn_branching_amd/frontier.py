@@ -190,9 +190,30 @@ def _check_witness(witness, pgd_steps, pgd_step):
         raise ValueError(f"pgd_step = {pgd_step!r}: a number with 0 < pgd_step <= 1")
 
 
+def _check_restarts(pgd_restarts, pgd_seed, pgd_steps):
+    """The restart options of DESIGN.md section 7.9 (None: off), before a device is touched."""
+    if pgd_restarts is not None and (not isinstance(pgd_restarts, int) or isinstance(pgd_restarts, bool) or pgd_restarts < 0):
+        raise ValueError(f"pgd_restarts = {pgd_restarts!r}: None, or an integer >= 0")
+    if pgd_restarts is not None and pgd_restarts > PGD_RESTARTS_MAX:
+        raise ValueError(f"pgd_restarts = {pgd_restarts!r}: {PGD_RESTARTS_MAX} at most")
+    if pgd_restarts is not None and pgd_steps is None:
+        raise ValueError(f"pgd_restarts = {pgd_restarts!r} needs pgd_steps (0: the random starts and the LP point, no descent)")
+    if not isinstance(pgd_seed, int) or isinstance(pgd_seed, bool) or not 0 <= pgd_seed < 2 ** 64:
+        raise ValueError(f"pgd_seed = {pgd_seed!r}: an integer in 0..2^64 - 1")
+
+
+PGD_RESTARTS_MAX = 4096             # gnnb_net_starts' R
+
+
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
     witness_on, pgd_steps, pgd_step = False, None, PGD_STEP_DEFAULT
+    restarts, pgd_seed = 0, 0
+
+    def _restart_options(self, pgd_restarts, pgd_seed):
+        """The options of DESIGN.md section 7.9, checked, behind ``_upper_bound_options``; ``restarts`` 0: off, and nothing of a round differs."""
+        _check_restarts(pgd_restarts, pgd_seed, self.pgd_steps)
+        self.restarts, self.pgd_seed = pgd_restarts or 0, pgd_seed
 
     def _upper_bound_options(self, witness, pgd_steps, pgd_step):
         """The options of DESIGN.md section 7.8, checked; set before the rows are made (``_child_rows`` gives them ``x_ub`` under PGD)."""
@@ -221,6 +242,10 @@ class _Round:
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
         if self.pgd_steps is not None:
             self.ws_descend = ws("gnnb_net_descend_workspace_bytes", n_children)
+        if self.restarts:                                         # every row's start points, and the tiles' workspace
+            n_starts = self.restarts + 1
+            self.starts = torch.zeros(n_children, n_starts, eng.sizes[0], dtype=torch.float32, device=dev)
+            self.ws_starts = torch.empty(max(1, self.lib.gnnb_net_descend_starts_workspace_bytes(eng.h, n_children, n_starts)), dtype=torch.uint8, device=dev)
         self.keep_pairs, self.pair_a = False, None
 
     def _ws(self, sizer, B):
@@ -258,7 +283,8 @@ class _Round:
     def _bound_children(self, Ch, B, warm):
         """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
         gnnb_net_descend from the rows' x_lp takes gnnb_net_eval's place: its f(x0) is that value, ubv the best value
-        it reached and x_ub the point."""
+        it reached and x_ub the point.  With ``pgd_restarts`` gnnb_net_starts and gnnb_net_descend_starts take its place in turn (section 7.9):
+        the descent from the LP point and from ``restarts`` uniform points of the row's box, ubv the least of their best values."""
         lib, h = self.lib, self.eng.h
         with torch.cuda.device(self.eng.device):
             _lib.check(lib.gnnb_kw_bounds(h, C.byref(Ch.kw_batch), B, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
@@ -268,9 +294,13 @@ class _Round:
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
         if self.pgd_steps is None:
             self.eng.net_eval(self.fixed, None, Ch.x_lp[:B], out=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_eval)
-        else:
+        elif not self.restarts:
             self.eng.net_descend(self.fixed, None, Ch.x_lp[:B], Ch.box[0], Ch.box[1], self.pgd_steps, self.pgd_step, x_best=Ch.x_ub, value=Ch.ubv,
                                  prop=Ch.box[2:], workspace=self.ws_descend)
+        else:                                                     # the seed of every launch is pgd_seed: rows differ through their keys
+            self.eng.net_starts(self.fixed, Ch.x_lp[:B], Ch.box[0], Ch.box[1], self.restarts, self.pgd_seed, starts=self.starts)
+            self.eng.net_descend_starts(self.fixed, None, self.starts[:B], Ch.box[0], Ch.box[1], self.pgd_steps, self.pgd_step, x_best=Ch.x_ub,
+                                        value=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_starts, in_shape=self.in_shape)
 
     def _ub_points(self, Ch):
         """The points the rows' ubv are the network's values at."""
@@ -345,9 +375,10 @@ class FrontierRun(_Round):
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
                  kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
-                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
         self._upper_bound_options(witness, pgd_steps, pgd_step)
+        self._restart_options(pgd_restarts, pgd_seed)
         _check_threshold(branching_threshold, kwbd_threshold)
         _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         layers = list(layers)
@@ -482,7 +513,7 @@ class FrontierRun(_Round):
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
-                              online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
+                              online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -527,9 +558,17 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     coordinate by ``pgd_step`` (0 < . <= 1) times its box width; 0 computes what None computes.  A traced round of a run with a witness
     also carries "global_ub" and "witness_value", the device's copy of it.
 
+    pgd_restarts, pgd_seed (with ``pgd_restarts`` at None or 0 no launch, read or argument of a round changes).
+    pgd_restarts: None, or an integer R >= 0 (it needs ``pgd_steps``): every child descends from its LP point and from R uniform points of
+    its box (``gnnb_net_starts``, ``gnnb_net_descend_starts``), and its upper value is the least of their best values.  With
+    ``pgd_steps=0`` that is the reference's get_upper_bound_random (plnn/conv_kwinter_gen.py:20-52) with the LP point added; with
+    ``pgd_steps=N`` the restarts of get_upper_bound_pgd (:54-135) under ``pgd_steps``' per-row rule.  pgd_seed: an integer in 0..2^64 - 1,
+    the seed of every launch: a row's points depend on its own LP point, box and the seed only, so a run repeats itself and a job in a pool
+    gets what it gets alone.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step)       # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
@@ -733,9 +772,11 @@ class JobsRun(_Round):
     one more array, ``m_entry`` (``read_selected``), between its two halves."""
 
     def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
-                 sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
+                 sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
+                 pgd_seed=0):
         _check_threshold(branching_threshold, kwbd_threshold)
         self._upper_bound_options(witness, pgd_steps, pgd_step)
+        self._restart_options(pgd_restarts, pgd_seed)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
         eng = self.eng = choice.model.engine()
@@ -887,11 +928,12 @@ class JobsRun(_Round):
 class FrontierJobs(list):
     """A list of ``FrontierJob`` together with the upper-bound options of the run that verifies them: how
     ``verify_properties`` and ``verify_properties_threshold`` take ``branch_and_bound_frontier``'s witness, pgd_steps and pgd_step.  (Their
-    own parameter lists are fixed.)  witness: None, or a list that receives one entry per job, in job order, when the run ends."""
+    own parameter lists are fixed.)  pgd_restarts / pgd_seed: the restart options of section 7.9.  witness: None, or a list that receives one entry per job, in job order, when the run ends."""
 
-    def __init__(self, jobs, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT):
+    def __init__(self, jobs, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
         super().__init__(jobs)
         self.witness, self.pgd_steps, self.pgd_step = witness, pgd_steps, pgd_step
+        self.pgd_restarts, self.pgd_seed = pgd_restarts, pgd_seed              # (section 7.9)
 
 
 def _upper_of(jobs):
@@ -900,6 +942,14 @@ def _upper_of(jobs):
         return None
     _check_witness(jobs.witness, jobs.pgd_steps, jobs.pgd_step)
     return {"witness": jobs.witness, "pgd_steps": jobs.pgd_steps, "pgd_step": jobs.pgd_step}
+
+
+def _restarts_of(jobs):
+    """The restart options a ``FrontierJobs`` carries, checked (None for any other sequence of jobs: off)."""
+    if not isinstance(jobs, FrontierJobs):
+        return None
+    _check_restarts(jobs.pgd_restarts, jobs.pgd_seed, jobs.pgd_steps)
+    return {"pgd_restarts": jobs.pgd_restarts, "pgd_seed": jobs.pgd_seed}
 
 
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
@@ -918,9 +968,9 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
     and a job's witness and bounds are what it gets alone with the same options.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper = _upper_of(jobs)
+    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, upper=upper)
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, upper=upper, restarts=restarts)
 
 
 def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
@@ -940,20 +990,21 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper = _upper_of(jobs)
+    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if branching_threshold is None:
         raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
     threshold = {"branching_threshold": branching_threshold, "kwbd_threshold": kwbd_threshold, "sparsest_layer": sparsest_layer,
                  "decision_threshold": decision_threshold}
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats, upper)
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats, upper, restarts)
 
 
-def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None):
+def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None,
+                 restarts=None):
     """The loop of ``verify_properties`` and ``verify_properties_threshold`` on checked arguments.  threshold: None, or the threshold mode's
     arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists.  upper: None, or the witness and descent
-    options of section 7.8."""
-    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}))
+    options of section 7.8; restarts: None, or the restart options of section 7.9."""
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}), **(restarts or {}))
     witness = (upper or {}).get("witness")
     run.keep_pairs = trace is not None
     F, thr = _lib, threshold is not None

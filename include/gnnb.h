@@ -313,8 +313,8 @@ int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, const float* p
  *   x_{t+1}[m] = fl32(min(max((double)x_t[m] - step (x_hi[m] - x_lo[m]) sgn(g_t[m]), x_lo[m]), x_hi[m])),  sgn(0) = 0,
  * rounded to nearest and, where rounding leaves [x_lo, x_hi], moved to the neighbouring float inside; f(x_{t+1}) < best, strictly, makes
  * it the best; if not f(x_{t+1}) < f(x_t) the point stops (the reference's stop rule, :110; no comparison holds for a NaN).  A point with
- * a NaN coordinate in x0, or whose f(x0) is NaN, takes no step.  Deliberately NOT the reference's: its 2056 random restarts (a caller who
- * wants restarts passes B start points) and its step size, a min over the whole batch (:113-122), which would make a row depend on its
+ * a NaN coordinate in x0, or whose f(x0) is NaN, takes no step.  Deliberately NOT the reference's: its 2056 random restarts (they are
+ * gnnb_net_starts / gnnb_net_descend_starts below) and its step size, a min over the whole batch (:113-122), which would make a row depend on its
  * batch.
  * x0: device (B, N_0) fp32; x_lo / x_hi: device (B, N_0) fp64; prop_w (B, N_L), prop_b (B) fp32 as in gnnb_net_eval; step in (0, 1]: the
  * share of the box's width a coordinate moves per step.  Outputs, device: x_best (B, N_0) fp32 (must not overlap x0); value (B) fp64 =
@@ -328,6 +328,39 @@ size_t gnnb_net_descend_workspace_bytes(const gnnb_t* h, int B);
 int gnnb_net_descend(gnnb_t* h, const float* x0, const double* x_lo, const double* x_hi, const float* prop_w, const float* prop_b, int B,
                      int n_steps, double step, float* x_best, double* value, double* grad0, int32_t* steps_taken, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* ---- the upper bound from many starts: get_upper_bound_pgd's restarts (reference plnn/conv_kwinter_gen.py:54-135:
+ * the LP point in slot 0, uniform points of the domain in the others) and get_upper_bound_random (:20-52) on the device ----
+ * gnnb_net_starts writes the start points of B rows.  x0: device (B, N_0) fp32; x_lo / x_hi: device (B, N_0) fp64; starts: device
+ * (B, R + 1, N_0) fp32 (must not overlap x0); R in 0..4096 random starts per row; seed: any 64 bits.  Slot 0 of row b is x0[b], bit for
+ * bit.  Slot r >= 1 is a counter-based uniform point of the row's box, with all integer arithmetic mod 2^64:
+ *   G = 0x9E3779B97F4A7C15;  mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *   key_b = seed + sum_m mix(bits32(x0[b, m]) + (m << 32))          u(b, r, m) = (mix(key_b + G (r N_0 + m + 1)) >> 11) 2^-53, in [0, 1)
+ *   value = fma(x_hi - x_lo, u, x_lo) in fp64, rounded to the nearest fp32, moved to the neighbouring float inside [x_lo, x_hi] where that
+ *   rounding left it (gnnb_net_descend's move).
+ * No generator state, no atomics: a row's starts depend on its own x0, box and seed only -- not on B, on its index or on what ran before.
+ * A NaN in x0 stays in slot 0 (it reaches the other slots through the key only, by its bits).
+ *
+ * gnnb_net_descend_starts runs gnnb_net_descend's rule, unchanged, from every one of the n_starts (1..4097) start points of every row --
+ * starts: device (B, n_starts, N_0) fp32, all of row b inside row b's box [x_lo[b], x_hi[b]] under row b's property row -- and picks per
+ * row the minimum of the starts' best values in the total order (value, start index): strict <, in start order, a NaN never wins, the
+ * first of equal values wins, and where every value is a NaN the result is start 0 and its NaN.  One workgroup carries
+ * gnnb_net_descend_starts_tile() starts of one row through every layer together; start r of row b ends, bit for bit, where
+ * gnnb_net_descend ends on that point as a row of its own, and value[b] is gnnb_net_eval(x_best[b]) bit for bit.  The one exception: a
+ * start with a NaN coordinate takes no step, as there, but its value is a NaN (a ReLU swallows the NaN, and what gnnb_net_descend reports for
+ * such a point is the network's value at no point of the box), so it never wins.  Outputs, device: x_best
+ * (B, N_0) fp32 (must not overlap starts), value (B) fp64: the winner's; start_index: NULL, or (B) int32, the winner's slot; start_value:
+ * NULL, or (B, n_starts) fp64, every start's best value; start_steps: NULL, or (B, n_starts) int32, every start's steps evaluated.
+ * Both are stream-ordered, allocate nothing, never synchronise, use no atomics, and no workgroup waits on another.  GNNB_E_INVALID before
+ * any launch for a null handle or required argument, B < 1, R outside 0..4096, n_starts outside 1..4097, n_steps < 0, a step outside
+ * (0, 1] or an overlapping output; GNNB_E_STATE before gnnb_bind_network; GNNB_E_NOMEM for a short workspace. */
+int gnnb_net_starts(gnnb_t* h, const float* x0, const double* x_lo, const double* x_hi, int B, int R, uint64_t seed, float* starts,
+                    void* stream);
+int gnnb_net_descend_starts_tile(void);
+size_t gnnb_net_descend_starts_workspace_bytes(const gnnb_t* h, int B, int n_starts);
+int gnnb_net_descend_starts(gnnb_t* h, const float* starts, int n_starts, const double* x_lo, const double* x_hi, const float* prop_w,
+                            const float* prop_b, int B, int n_steps, double step, float* x_best, double* value, int32_t* start_index,
+                            double* start_value, int32_t* start_steps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Closes a round.  slots: the K parents (as given to gnnb_frontier_expand); eps; decision_bound (NaN: none); state: the record above,
  * read and updated.  In order: every live child's mask is resolved by its bounds (-1 with lo >= 0 -> 1, -1 with up <= 0 -> 0);
