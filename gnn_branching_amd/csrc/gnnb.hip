@@ -20,8 +20,9 @@
 //
 // One translation unit: gnnb_dev.h (fragments, GEMM blocks, tile maps), gnnb_k_mlp.h (setup + node-MLP kernels),
 // gnnb_k_gather.h (conv-edge message passing + score head), gnnb_k_fusedq.h (gather + node update in one kernel), gnnb_k_edges.h (other edges, k_top), gnnb_k_misc.h (k_livesum,
-// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_k_dual.h (dual ascent, gnnb_dual_ascent), gnnb_k_frontier.h (the steps of a BaB round on a
-// device-resident frontier, gnnb_frontier_* / gnnb_net_eval), gnnb_train.h (online learning) are included below; this file
+// k_babsr, k_gather_scored), gnnb_k_kw.h (Wong-Kolter bounds, gnnb_kw_bounds), gnnb_k_dual.h (dual ascent, gnnb_dual_ascent), gnnb_k_net.h (the fp64 walk of the
+// bound network, gnnb_net_eval / gnnb_net_descend / gnnb_net_descend_starts), gnnb_k_frontier.h (the steps of a BaB round on a
+// device-resident frontier, gnnb_frontier_*), gnnb_k_starts.h (start points and the pick), gnnb_train.h (online learning) are included below; this file
 // holds the host side and the C-ABI.
 //
 // gfx950 only.  No HIP call at load time.
@@ -61,6 +62,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_misc.h"
 #include "gnnb_k_kw.h"
 #include "gnnb_k_dual.h"
+#include "gnnb_k_net.h"
 #include "gnnb_k_frontier.h"
 #include "gnnb_k_starts.h"
 
@@ -1757,6 +1759,24 @@ extern "C" int gnnb_frontier_expand(gnnb_t* h, const gnnb_pool* pool, const int3
   return run.rc;
 }
 
+// What the gnnb_net_* entry points check of the handle, after their own sizes: it exists, and its bound network passes kw_preflight.
+static int net_preflight(const gnnb_t* h, const char* who) {
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
+  const int ng = h->bound ? h->kw_net.L + 2 : 0;
+  size_t lds = 0;
+  return kw_preflight(h, who, &ng, &lds);
+}
+
+// The walk's argument block but for the caller's arrays: the network, where each layer's activations start, one point per workgroup,
+// and the workspace at ws_stride doubles per workgroup.
+static NetArgs net_args(const gnnb_t* h, void* workspace, long ws_stride) {
+  NetArgs a{};
+  a.net = h->kw_net; a.n_starts = 1;
+  a.ws = (double*)workspace; a.ws_stride = ws_stride; a.width = net_eval_width(a.net);
+  for (int k = 0; k <= a.net.L; ++k) a.act_off[k + 1] = a.act_off[k] + a.net.N[k];
+  return a;
+}
+
 extern "C" size_t gnnb_net_eval_workspace_bytes(const gnnb_t* h, int B) {
   if (!h || !h->bound || B < 1) return 0;
   return (size_t)B * 2 * net_eval_width(h->kw_net) * sizeof(double);
@@ -1764,21 +1784,17 @@ extern "C" size_t gnnb_net_eval_workspace_bytes(const gnnb_t* h, int B) {
 
 extern "C" int gnnb_net_eval(gnnb_t* h, const float* x, const float* prop_w, const float* prop_b, int B, double* out, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  if (B < 1) return fail(GNNB_E_INVALID, "gnnb_net_eval: B = %d", B);
-  if (!h) return fail(GNNB_E_INVALID, "gnnb_net_eval: null handle");      // (before h->bound is read)
-  const int ng = h->bound ? h->kw_net.L + 2 : 0;
-  size_t lds = 0;
-  if (int rc = kw_preflight(h, "gnnb_net_eval", &ng, &lds)) return rc;
-  if (!x || !prop_w || !prop_b || !out || !workspace) return fail(GNNB_E_INVALID, "gnnb_net_eval: null argument");
+  const char* who = "gnnb_net_eval";
+  if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
+  if (int rc = net_preflight(h, who)) return rc;
+  if (!x || !prop_w || !prop_b || !out || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
   const size_t need = gnnb_net_eval_workspace_bytes(h, B);
-  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "gnnb_net_eval: workspace %zu bytes, need %zu", workspace_bytes, need);
-  NetEvalArgs a{};
-  a.net = h->kw_net;
-  a.x = x; a.prop_w = prop_w; a.prop_b = prop_b; a.out = out;
-  a.ws = (double*)workspace; a.ws_stride = 2L * net_eval_width(h->kw_net);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  NetArgs a = net_args(h, workspace, 2L * net_eval_width(h->kw_net));
+  a.x = x; a.prop_w = prop_w; a.prop_b = prop_b; a.val = out;
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  run.run(PC_NET_EVAL, [&] { hipLaunchKernelGGL(k_net_eval, dim3(B), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_NET_EVAL, [&] { hipLaunchKernelGGL(k_net_eval, dim3(B), dim3(NET_THREADS), 0, st, a); });
   return run.rc;
 }
 
@@ -1795,24 +1811,18 @@ extern "C" int gnnb_net_descend(gnnb_t* h, const float* x0, const double* x_lo, 
   if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
   if (n_steps < 0) return fail(GNNB_E_INVALID, "%s: n_steps = %d", who, n_steps);
   if (!(step > 0.0 && step <= 1.0)) return fail(GNNB_E_INVALID, "%s: step = %g (0 < . <= 1)", who, step);
-  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
-  const int ng = h->bound ? h->kw_net.L + 2 : 0;
-  size_t lds = 0;
-  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (int rc = net_preflight(h, who)) return rc;
   if (!x0 || !x_lo || !x_hi || !prop_w || !prop_b || !x_best || !value || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
   if (x_best == x0) return fail(GNNB_E_INVALID, "%s: x_best must not overlap x0", who);
   const size_t need = gnnb_net_descend_workspace_bytes(h, B);
   if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
-  NetDescendArgs a{};
-  a.net = h->kw_net;
-  a.x0 = x0; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
+  NetArgs a = net_args(h, workspace, net_descend_doubles(h->kw_net));
+  a.x = x0; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
   a.n_steps = n_steps; a.step = step;
-  a.x_best = x_best; a.value = value; a.grad0 = grad0; a.steps_taken = steps_taken;
-  a.ws = (double*)workspace; a.ws_stride = net_descend_doubles(h->kw_net); a.width = net_eval_width(h->kw_net);
-  for (int k = 0; k <= a.net.L; ++k) a.act_off[k + 1] = a.act_off[k] + a.net.N[k];
+  a.xb = x_best; a.val = value; a.grad0 = grad0; a.steps_taken = steps_taken;
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  run.run(PC_NET_DESCEND, [&] { hipLaunchKernelGGL(k_net_descend, dim3(B), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_NET_DESCEND, [&] { hipLaunchKernelGGL(k_net_descend, dim3(B), dim3(NET_THREADS), 0, st, a); });
   return run.rc;
 }
 
@@ -1822,10 +1832,7 @@ extern "C" int gnnb_net_starts(gnnb_t* h, const float* x0, const double* x_lo, c
   const char* who = "gnnb_net_starts";
   if (B < 1) return fail(GNNB_E_INVALID, "%s: B = %d", who, B);
   if (R < 0 || R > NS_MAX_RANDOM) return fail(GNNB_E_INVALID, "%s: R = %d outside 0..%d", who, R, NS_MAX_RANDOM);
-  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
-  const int ng = h->bound ? h->kw_net.L + 2 : 0;
-  size_t lds = 0;
-  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (int rc = net_preflight(h, who)) return rc;
   if (!x0 || !x_lo || !x_hi || !starts) return fail(GNNB_E_INVALID, "%s: null argument", who);
   if (starts == x0) return fail(GNNB_E_INVALID, "%s: starts must not overlap x0", who);
   NetStartsArgs a{};
@@ -1861,29 +1868,23 @@ extern "C" int gnnb_net_descend_starts(gnnb_t* h, const float* starts, int n_sta
   if (n_starts < 1 || n_starts > NS_MAX_RANDOM + 1) return fail(GNNB_E_INVALID, "%s: n_starts = %d outside 1..%d", who, n_starts, NS_MAX_RANDOM + 1);
   if (n_steps < 0) return fail(GNNB_E_INVALID, "%s: n_steps = %d", who, n_steps);
   if (!(step > 0.0 && step <= 1.0)) return fail(GNNB_E_INVALID, "%s: step = %g (0 < . <= 1)", who, step);
-  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);           // (before h->bound is read)
-  const int ng = h->bound ? h->kw_net.L + 2 : 0;
-  size_t lds = 0;
-  if (int rc = kw_preflight(h, who, &ng, &lds)) return rc;
+  if (int rc = net_preflight(h, who)) return rc;
   if (!starts || !x_lo || !x_hi || !prop_w || !prop_b || !x_best || !value || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
   if (x_best == starts) return fail(GNNB_E_INVALID, "%s: x_best must not overlap starts", who);
   if ((long)B * ((n_starts + NS_TILE - 1) / NS_TILE) > 0x7fffffffL) return fail(GNNB_E_INVALID, "%s: B = %d rows of %d starts: too many tiles", who, B, n_starts);
   const NsWs w = ns_ws_layout(h, B, n_starts);
   if (workspace_bytes < w.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, w.total);
   const int tiles = B * ((n_starts + NS_TILE - 1) / NS_TILE);
-  NetTileArgs a{};
-  a.net = h->kw_net;
-  a.starts = starts; a.n_starts = n_starts; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
+  NetArgs a = net_args(h, workspace, (long)NS_TILE * net_descend_doubles(h->kw_net));
+  a.x = starts; a.n_starts = n_starts; a.x_lo = x_lo; a.x_hi = x_hi; a.prop_w = prop_w; a.prop_b = prop_b;
   a.n_steps = n_steps; a.step = step;
-  a.ws = (double*)workspace; a.ws_stride = (long)NS_TILE * net_descend_doubles(h->kw_net); a.width = net_eval_width(h->kw_net);
   a.val = (double*)((char*)workspace + w.val); a.xb = (float*)((char*)workspace + w.xb); a.steps_taken = start_steps;
-  for (int k = 0; k <= a.net.L; ++k) a.act_off[k + 1] = a.act_off[k] + a.net.N[k];
   NetPickArgs p{};
   p.xb = a.xb; p.val = a.val; p.n_starts = n_starts; p.N0 = a.net.N[0];
   p.x_best = x_best; p.value = value; p.start_index = start_index; p.start_value = start_value;
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  run.run(PC_NET_DESCEND_TILE, [&] { hipLaunchKernelGGL(k_net_descend_tile<NS_TILE>, dim3(tiles), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_NET_DESCEND_TILE, [&] { hipLaunchKernelGGL(k_net_descend_tile<NS_TILE>, dim3(tiles), dim3(NET_THREADS), 0, st, a); });
   run.run(PC_NET_STARTS_PICK, [&] { hipLaunchKernelGGL(k_net_starts_pick, dim3(B), dim3(FR_THREADS), 0, st, p); });
   return run.rc;
 }

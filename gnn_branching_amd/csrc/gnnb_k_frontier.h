@@ -1,9 +1,10 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
-// gnnb_frontier_gather, gnnb_frontier_expand, gnnb_net_eval, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
+// gnnb_frontier_gather, gnnb_frontier_expand, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
 // a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, their many-job form of section 7.6, and the selection
-// of the rows an online round learns from, section 7.7: gnnb_frontier_learn; behind k_net_eval the descent on the network that can take its
-// place, gnnb_net_descend, and last the witness of the upper bound, section 7.8: gnnb_frontier_witness).  Between them run the existing batch kernels
-// (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched.
+// of the rows an online round learns from, section 7.7: gnnb_frontier_learn; last the witness of the upper bound, section 7.8:
+// gnnb_frontier_witness).  Between them run the existing batch kernels (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs,
+// gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched, and the network's value at a round's points: gnnb_net_eval or the descent
+// that can take its place, gnnb_net_descend (gnnb_k_net.h).
 //
 // The POOL is a struct of arrays over `capacity` slots: mask (cap, R) int8, the fp64 bounds of graph layers 1..L+1 (cap, N_k) exactly as
 // gnnb_kw_bounds wrote them, the best dual point alpha / beta (cap, R), its value bound (cap) and the flag open (cap).
@@ -14,10 +15,6 @@
 //                         one entry set, the parent's bounds as gnnb_kw_bounds' parent tables, split_layer, the parent's dual point,
 //                         live.  A parent without a decision ([-1, -1]) yields two complete rows with live = 0 (the batch kernels
 //                         behind run on them like on any other row; commit ignores them).
-//   * k_net_eval          the bound network + a property row at B points in fp64: one workgroup per point, activations in the
-//                         workspace (two buffers of the widest graph layer), a conv node per thread (dual_conv_at), a Linear row per
-//                         wave with the fixed butterfly -- the shapes of dual_forward.  The layer loop is net_forward, which k_net_descend
-//                         calls too.
 //   * k_frontier_resolve  per child: the mask resolved by the bounds (-1 with lo >= 0 -> 1, -1 with up <= 0 -> 0) and whether an
 //                         undecided node is left.
 //   * k_frontier_decide   ONE workgroup: global_ub, keep or close every child, the parents' slots freed, the kept children's
@@ -157,172 +154,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_expand(FrExpandArgs a) 
   if (t0 == 0) {
     a.live[c] = live ? 1 : 0;
     a.split[c] = live ? lay : a.s.L - 1;                // a dead row keeps every bound of its parent
-  }
-}
-
-struct NetEvalArgs {
-  KwNet net;
-  const float* x; const float* prop_w; const float* prop_b;     // (B, N_0), (B, N_L), (B)
-  double* out;                                                  // (B)
-  double* ws; long ws_stride;                                   // 2 * widest graph layer doubles per point
-};
-
-static inline int net_eval_width(const KwNet& n) {
-  int w = 1;
-  for (int k = 0; k <= n.L; ++k) w = n.N[k] > w ? n.N[k] : w;
-  return w;
-}
-
-// The bound network's layers 1..L and the property row at one point, fp64, by one workgroup: at(k) is where graph layer k's activations
-// live (layer 0 filled and synchronised by the caller), a conv node per thread, a Linear row per wave with the fixed butterfly.  Returns
-// prop_w . act_L + prop_b on every thread.  red: FR_THREADS doubles of LDS.  k_net_eval and k_net_descend both evaluate f through it.
-template <class At>
-__device__ __forceinline__ double net_forward(const KwNet& net, const float* prop_w, float prop_b, At at, double* red, int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-  for (int k = 1; k <= net.L; ++k) {
-    const KwEdge& E = net.e[k];
-    const int Nk = net.N[k];
-    const double* cur = at(k - 1);
-    double* nxt = at(k);
-    if (E.kind == 0) {
-      const int hw = E.h_out * E.w_out;
-      for (int j = tid; j < Nk; j += FR_THREADS) nxt[j] = fmax(dual_conv_at(E, j, cur) + E.bias[j / hw], 0.0);
-    } else {
-      for (int j = wave; j < Nk; j += FR_THREADS / 64) {
-        const double* row = E.w + (long)j * E.n_in;
-        double acc = 0.0;
-        for (int t = lane; t < E.n_in; t += 64) acc += row[t] * cur[t];
-        for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
-        if (lane == 0) nxt[j] = fmax(acc + E.bias[j], 0.0);
-      }
-    }
-    __syncthreads();
-  }
-  const int NL = net.N[net.L];
-  const double* cur = at(net.L);
-  double part = 0.0;
-  for (int j = tid; j < NL; j += FR_THREADS) part += (double)prop_w[j] * cur[j];
-  kw_block_sum<1>(red, &part, tid);
-  return part + (double)prop_b;
-}
-
-__global__ __launch_bounds__(FR_THREADS) void k_net_eval(NetEvalArgs a) {
-  __shared__ double red[FR_THREADS];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  double* buf = a.ws + (long)b * a.ws_stride;
-  const long half = a.ws_stride / 2;
-  const int N0 = a.net.N[0];
-  for (int m = tid; m < N0; m += FR_THREADS) buf[m] = (double)a.x[(long)b * N0 + m];
-  __syncthreads();
-  const double f = net_forward(a.net, a.prop_w + (long)b * a.net.N[a.net.L], a.prop_b[b], [&](int k) { return buf + (k & 1) * half; }, red, tid);
-  if (tid == 0) a.out[b] = f;
-}
-
-// ---- projected signed-gradient descent on the bound network ------------------------------------------------
-// Reference plnn/conv_kwinter_gen.py:54-135 (get_upper_bound_pgd), called from each child's LP point by plnn/relu_conv_any_kw.py:143-149.
-//
-//   * k_net_descend   one workgroup per point.  f is net_forward, with the activations of EVERY graph layer 0..L kept in the workspace;
-//                     g is the fp64 backward pass through them: g_L = prop_w . 1[act_L > 0], down each edge by its transpose
-//                     (kw_transpose_at: a conv's taps in a fixed order, a Linear map's column), gated by 1[act_k > 0] at every ReLU layer
-//                     (torch's ReLU gradient).  best = (f(x0), x0); then up to n_steps times
-//                       x'[m] = fl32(min(max(x[m] - step (x_hi[m] - x_lo[m]) sgn(g[m]), x_lo[m]), x_hi[m]))   (sgn(0) = 0; fp64, then nearest fp32,
-//                                                                                                    moved inside the box if rounding left it)
-//                     f(x') < best, strictly, makes it the best; not f(x') < f(x) stops the point (:110).  A point with a NaN among its
-//                     coordinates, or whose f(x0) is NaN, takes no step.  Layer 0's activations ARE the current point (fp32 values held
-//                     as doubles).  No atomics, no workgroup waits on another; every sum runs in a fixed order, so a point's result does
-//                     not depend on B or on its row.
-
-struct NetDescendArgs {
-  KwNet net;
-  const float* x0; const double* x_lo; const double* x_hi; const float* prop_w; const float* prop_b;     // (B, N_0) x 3, (B, N_L), (B)
-  int n_steps; double step;
-  float* x_best; double* value; double* grad0; int32_t* steps_taken;                                       // (B, N_0), (B), null or (B, N_0), null or (B)
-  double* ws; long ws_stride;                           // per point: the activations of graph layers 0..L, then two gradient buffers of `width`
-  int act_off[MAXL + 2], width;                         // act_off[k]: layer k's first activation; act_off[L + 1]: their total
-};
-static_assert(sizeof(NetDescendArgs) <= 4096, "kernel arguments: 4 KiB");
-
-static inline long net_descend_doubles(const KwNet& n) {
-  long s = 0;
-  for (int k = 0; k <= n.L; ++k) s += n.N[k];
-  return s + 2L * net_eval_width(n);
-}
-
-// g(x) from the activations `act` of the forward pass at x: returns the buffer (ga or gb) that holds the N_0 entries, synchronised
-__device__ __forceinline__ double* net_backward(const NetDescendArgs& a, const double* act, const float* prop_w, double* ga, double* gb, int tid) {
-  const KwNet& net = a.net;
-  const double* top = act + a.act_off[net.L];
-  for (int j = tid; j < net.N[net.L]; j += FR_THREADS) ga[j] = top[j] > 0.0 ? (double)prop_w[j] : 0.0;
-  __syncthreads();
-  double* cur = ga;
-  double* nxt = gb;
-  for (int k = net.L; k >= 1; --k) {
-    const KwEdge& E = net.e[k];
-    const double* below = act + a.act_off[k - 1];
-    for (int m = tid; m < net.N[k - 1]; m += FR_THREADS)        // (a gated node is exactly 0; the input layer has no gate)
-      nxt[m] = (k == 1 || below[m] > 0.0) ? kw_transpose_at(E, 0, m, cur, 0, E.h_out - 1, 0, E.w_out - 1) : 0.0;
-    double* t = cur; cur = nxt; nxt = t;
-    __syncthreads();
-  }
-  return cur;
-}
-
-__global__ __launch_bounds__(FR_THREADS) void k_net_descend(NetDescendArgs a) {
-  __shared__ double red[FR_THREADS];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const KwNet& net = a.net;
-  const int N0 = net.N[0];
-  double* act = a.ws + (long)b * a.ws_stride;
-  double* ga = act + a.act_off[net.L + 1];
-  double* gb = ga + a.width;
-  const float* x0 = a.x0 + (long)b * N0;
-  float* xb = a.x_best + (long)b * N0;
-  const double* lo = a.x_lo + (long)b * N0;
-  const double* hi = a.x_hi + (long)b * N0;
-  const float* pw = a.prop_w + (long)b * net.N[net.L];
-  const float pb = a.prop_b[b];
-  const auto at = [&](int k) { return act + a.act_off[k]; };
-  int nan = 0;
-  for (int m = tid; m < N0; m += FR_THREADS) {
-    const float v = x0[m];
-    xb[m] = v;                                          // best = (f(x0), x0), unconditionally
-    act[m] = (double)v;
-    nan |= v != v;
-  }
-  nan = __syncthreads_or(nan);
-  double f = net_forward(net, pw, pb, at, red, tid), best = f;
-  const bool go = a.n_steps > 0 && !nan && f == f;
-  int steps = 0;
-  const double* g = nullptr;
-  if (a.grad0 || go) {
-    g = net_backward(a, act, pw, ga, gb, tid);
-    if (a.grad0)
-      for (int m = tid; m < N0; m += FR_THREADS) a.grad0[(long)b * N0 + m] = g[m];
-  }
-  for (int t = 0; go && t < a.n_steps; ++t) {           // (f, best and so every branch below are the same on all threads)
-    for (int m = tid; m < N0; m += FR_THREADS) {
-      const double x = act[m], l = lo[m], h = hi[m], d = a.step * (h - l), gm = g[m];
-      double v = gm > 0.0 ? x - d : (gm < 0.0 ? x + d : x);
-      v = fmin(fmax(v, l), h);
-      float r = (float)v;                               // to nearest; where that leaves [l, h], the neighbouring float inside
-      if ((double)r < l) r = nextafterf(r, __builtin_inff());
-      else if ((double)r > h) r = nextafterf(r, -__builtin_inff());
-      act[m] = (double)r;
-    }
-    __syncthreads();
-    const double fn = net_forward(net, pw, pb, at, red, tid);
-    ++steps;
-    if (fn < best) {
-      best = fn;
-      for (int m = tid; m < N0; m += FR_THREADS) xb[m] = (float)act[m];
-    }
-    if (!(fn < f)) break;                               // the reference's stop rule; a NaN stops here too
-    f = fn;
-    if (t + 1 < a.n_steps) g = net_backward(a, act, pw, ga, gb, tid);
-  }
-  if (tid == 0) {
-    a.value[b] = best;
-    if (a.steps_taken) a.steps_taken[b] = steps;
   }
 }
 

@@ -100,7 +100,7 @@ def test_new_symbols_are_declared_bound_and_exported(lib):
     for n in NEW:
         assert n in names and hasattr(lib, n) and n + "(" in header, n
     assert lib.gnnb_abi_version() == 2 and "#define GNNB_ABI_VERSION 2" in header      # the additions are additive
-    assert "gnnb_k_starts.h" in _lib.SOURCES
+    assert "gnnb_k_starts.h" in _lib.SOURCES and "gnnb_k_net.h" in _lib.SOURCES
     assert lib.gnnb_net_descend_starts_tile() >= 1
     from gnn_branching_amd.engine import ScorerEngine
     for m in ("net_starts", "net_descend_starts"):

@@ -22,8 +22,18 @@ cifar_base_kw, eps 0.09, seeded N(0,1) image (RandomState(4)), property 3 vs 5: 
     bounded.  "off" against "parent": the ratio of the medians beside the parent's own spread; bounds and counts must be identical.
 
     python tools/net_starts_timing.py --parent-tree PATH [--out profiles/net_starts_timing.json]
+
+--parent-lib PATH (the walk of the bound network as one template, gnnb_k_net.h): this tree against the PARENT COMMIT'S LIBRARY
+(tools/mklib.sh <parent> parent), a worker of this tree with GNNB_LIB set -- the Python side is the same on both.  (a) gnnb_net_eval, the flat
+gnnb_net_descend and gnnb_net_descend_starts at the same B x n_starts sizes, the results asserted identical between the libraries first; (b) the
+sides off, pgd4 and pgd4_r16, each against the parent's library under the same options: bounds and counts must be identical.  The sides
+alternate repeat by repeat.  The bar at every size and side: this tree's median no more than three times the larger A/A spread of the two above
+the parent's.
+
+    python tools/net_starts_timing.py --parent-lib tools/ablate/parent.so --repeats 9 [--out profiles/net_walk_refactor_timing.json]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -67,8 +77,8 @@ def worker(tree):
     def kernels(prof):
         return {k: {"launches": int(prof[k][1]), "ms_per_launch": round(prof[k][0] / prof[k][1], 5) if prof[k][1] else None} for k in KERNELS if k in prof}
 
-    def tile_against_flat(cmd):
-        B, n, calls, repeats = cmd["B"], cmd["n_starts"], cmd["calls"], cmd["repeats"]
+    def walk_calls(B, n):
+        """(starts, x0, lo, hi, {call: closure}) of part (a): B root-box rows x n starts"""
         dev, f64 = eng.device, torch.float64
         lo = (x - EPS).reshape(1, -1).to(dev, f64).expand(B, -1).contiguous()
         hi = (x + EPS).reshape(1, -1).to(dev, f64).expand(B, -1).contiguous()
@@ -83,6 +93,21 @@ def worker(tree):
         flat = lambda: eng.net_descend(*flat_args, prop=flat_prop, want_steps=True)          # noqa: E731
         tile = lambda: eng.net_descend_starts(fixed, None, starts, lo, hi, STEPS, STEP, prop=(pw, pb), want_index=True, want_values=True,  # noqa: E731
                                               want_steps=True, in_shape=(3, 32, 32))
+        ev = lambda: eng.net_eval(fixed, None, flat_args[2], prop=flat_prop)          # noqa: E731
+        return starts, x0, lo, hi, {"eval": ev, "flat": flat, "tile": tile}
+
+    def timed(f, calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            f()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / calls
+
+    def tile_against_flat(cmd):
+        B, n, calls, repeats = cmd["B"], cmd["n_starts"], cmd["calls"], cmd["repeats"]
+        starts, x0, lo, hi, call = walk_calls(B, n)
+        flat, tile, dev = call["flat"], call["tile"], eng.device
         fx, fv, _, fs = flat()
         x_best, value, index, values, steps = tile()
         torch.cuda.synchronize()
@@ -92,18 +117,11 @@ def worker(tree):
         same = same and bool(torch.equal(x_best, fx[rows, index.long()]) and torch.equal(value.view(torch.int64), fv[rows, index.long()].view(torch.int64)))
         assert same, ("gnnb_net_descend_starts and the flat batch of gnnb_net_descend differ", B, n)
 
-        def timed(f):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(calls):
-                f()
-            torch.cuda.synchronize()
-            return 1e3 * (time.perf_counter() - t0) / calls
-        timed(flat), timed(tile)                                           # warm-up
+        timed(flat, calls), timed(tile, calls)                             # warm-up
         ms = {"flat": [], "tile": []}
         for _ in range(repeats):                                            # alternating
-            ms["flat"].append(timed(flat))
-            ms["tile"].append(timed(tile))
+            ms["flat"].append(timed(flat, calls))
+            ms["tile"].append(timed(tile, calls))
         eng.profile_enable(1)
         eng.profile_read(reset=True)
         eng.net_starts(fixed, x0, lo, hi, n - 1, SEED, starts=starts)
@@ -118,8 +136,29 @@ def worker(tree):
         out.update(flat_over_tile=round(gain, 3), three_times_the_larger_spread=round(bar, 4), gain_beyond_three_spreads=bool(gain - 1 > bar))
         return out
 
+    walk = {}
+
+    def walk_setup(cmd):
+        """the three calls at one size, warmed up; a digest of everything they return"""
+        walk.clear()
+        walk.update(walk_calls(cmd["B"], cmd["n_starts"])[4])
+        h = hashlib.sha256()
+        for name in sorted(walk):
+            out = walk[name]()
+            for t in (out if isinstance(out, tuple) else (out,)):
+                if t is not None:
+                    h.update(t.contiguous().cpu().numpy().tobytes())
+            timed(walk[name], cmd["calls"])
+        return {"results_sha256": h.hexdigest()}
+
     for line in sys.stdin:
         cmd = json.loads(line)
+        if cmd.get("what") == "walk_setup":
+            print(json.dumps(walk_setup(cmd)), flush=True)
+            continue
+        if cmd.get("what") == "walk_repeat":
+            print(json.dumps({name: timed(f, cmd["calls"]) for name, f in sorted(walk.items())}), flush=True)
+            continue
         if cmd.get("what") == "tile":
             print(json.dumps({"tile": eng.lib.gnnb_net_descend_starts_tile()}), flush=True)
             continue
@@ -146,9 +185,10 @@ def worker(tree):
 
 
 class Worker:
-    def __init__(self, tree):
+    def __init__(self, tree, lib=None):
+        env = dict(os.environ, GNNB_LIB=os.path.abspath(lib)) if lib else None
         self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", tree], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True,
-                                  cwd=tree)
+                                  cwd=tree, env=env)
         self.info = self._read()
 
     def _read(self):
@@ -182,8 +222,77 @@ def summary(runs):
             "same_result_in_every_repeat": all(key(r) == key(last) for r in runs)}
 
 
+def against(new, old):
+    """the project's bar: this tree's median no more than three times the larger A/A spread of the two sides above the parent's"""
+    ratio, width = new["median"] / old["median"], 3 * max(new["aa_spread"], old["aa_spread"])
+    return {"tree_over_parent": round(ratio, 4), "three_times_the_larger_spread": round(width, 4), "within_the_bar": bool(ratio - 1 <= width)}
+
+
+def refactor(args):
+    """this tree against the parent commit's library: part (a)'s three calls, part (b)'s sides off / pgd4 / pgd4_r16"""
+    libs = {"tree": Worker(ROOT), "parent": Worker(ROOT, lib=args.parent_lib)}
+    S = libs["tree"].ask({"what": "tile"})["tile"]
+    sides = {"off": {}, "pgd4": {"witness": True, "pgd_steps": 4}, "pgd4_r16": {"witness": True, "pgd_steps": 4, "pgd_restarts": 16}}
+    rec = {"what": f"{NET}, eps {EPS}, property 3 vs 5: this tree (the walk of the bound network as one template) against the parent commit's library, "
+                   f"one worker process per library, the same Python.  kernel: gnnb_net_eval, gnnb_net_descend on B * n_starts points and "
+                   f"gnnb_net_descend_starts (S = {S}), {STEPS} steps of 1/64, root-box rows; ms per call, wall clock on the host around {args.calls} "
+                   f"back-to-back calls; one warm-up, {args.repeats} repeats per side, the sides alternating repeat by repeat; median, min / max and "
+                   f"the A/A spread (max - min) / median.  frontier: branch_and_bound_frontier(branching_threshold={args.threshold}), n_iter {N_ITER}, "
+                   f"lr {LR}, BaB eps {EPS_BAB}, each side on both libraries, alternating.  The bar: tree / parent - 1 <= three times the larger spread",
+           "device": libs["tree"].info["device"], "library_build_id": libs["tree"].info["library_build_id"],
+           "parent_commit_library_build_id": libs["parent"].info["library_build_id"], "tile": S, "kernel": [], "frontier": []}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+
+    def save():
+        rec["every_size_within_the_bar"] = all(v["within_the_bar"] for e in rec["kernel"] + rec["frontier"] for v in e["against_parent"].values())
+        rec["every_result_identical"] = all(e["identical"] for e in rec["kernel"] + rec["frontier"])
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+    try:
+        if args.skip != "kernel":
+            for B in [int(b) for b in args.bs.split(",")]:
+                for n in [S if n == "S" else int(n) for n in args.starts.split(",")]:
+                    size = {"B": B, "n_starts": n, "calls": args.calls}
+                    digests = {lib: w.ask({"what": "walk_setup", **size})["results_sha256"] for lib, w in libs.items()}
+                    ms = {lib: {} for lib in libs}
+                    for _ in range(args.repeats):                         # alternating
+                        for lib, w in libs.items():
+                            for call, v in w.ask({"what": "walk_repeat", "calls": args.calls}).items():
+                                ms[lib].setdefault(call, []).append(v)
+                    entry = {"B": B, "n_starts": n, "points": B * n, "identical": digests["tree"] == digests["parent"],
+                             "ms": {lib: {call: spread(v) for call, v in m.items()} for lib, m in ms.items()}}
+                    entry["against_parent"] = {call: against(entry["ms"]["tree"][call], entry["ms"]["parent"][call]) for call in entry["ms"]["tree"]}
+                    rec["kernel"].append(entry)
+                    print(json.dumps(entry), flush=True)
+                    save()
+        if args.skip != "frontier":
+            same = ("global_lb", "global_ub", "domains_bounded", "rounds", "stop", "kw_pairs_bounded", "kw_pairs_used", "same_result_in_every_repeat")
+            for K, rounds in zip([int(k) for k in args.ks.split(",")], [int(r) for r in args.rounds.split(",")]):
+                common = (K, rounds, args.capacity, args.threshold)
+                entry = {"K": K, "max_rounds": rounds, "sides": {}, "against_parent": {}, "identical": True}
+                for side, options in sides.items():
+                    for w in libs.values():                               # warm-up: allocations, first launches
+                        w.run(K, min(rounds, 4), args.capacity, args.threshold, options)
+                    runs = {lib: [] for lib in libs}
+                    for _ in range(args.repeats):                         # alternating
+                        for lib, w in libs.items():
+                            runs[lib].append(w.run(*common, options))
+                    sums = {lib: summary(r) for lib, r in runs.items()}
+                    entry["sides"][side] = sums
+                    entry["against_parent"][side] = against(sums["tree"]["ms_per_round"], sums["parent"]["ms_per_round"])
+                    entry["identical"] = entry["identical"] and all(sums["tree"][k] == sums["parent"][k] for k in same)
+                rec["frontier"].append(entry)
+                print(json.dumps(entry), flush=True)
+                save()
+    finally:
+        for w in libs.values():
+            w.close()
+    print("written", args.out, "every size within the bar:", rec.get("every_size_within_the_bar"), "identical:", rec.get("every_result_identical"))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", help="the parent commit's library (tools/mklib.sh): the record of the one-template walk, this tree against it")
     ap.add_argument("--worker", help="(internal) serve runs on the tree at this path")
     ap.add_argument("--parent-tree", help="a checkout of the parent commit with its library built")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "net_starts_timing.json"))
@@ -199,6 +308,8 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(args.worker)
+    if args.parent_lib:
+        return refactor(args)
     new = Worker(ROOT)
     old = Worker(os.path.abspath(args.parent_tree)) if args.parent_tree and args.skip != "frontier" else None
     S = new.ask({"what": "tile"})["tile"]
