@@ -529,9 +529,12 @@ static TileMap bwd_map(const gnnb_t* h, int k) {
 }
 static long map_tiles(const TileMap& t, int B) { return t.mode ? (long)B * t.TPS : ((long)B * t.N + 31) / 32; }
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+static int pairs_per_sample(const TileMap& t) { return t.NCG * ((t.NBY + 1) / 2) * t.NBX; }      // row pairs of the block-form tiles (fusedq_gather_pairs)
 static DTileMap to_dtm(const TileMap& t) {
+  const int pps = t.mode ? pairs_per_sample(t) : 0;
   return DTileMap{t.mode, t.N, t.C, t.H, t.W, t.CT, t.PY, t.PX, t.ay, t.ax, t.NBY, t.NBX, t.NCG, t.TPS, ilog2(t.PY), ilog2(t.PX),
-                  t.TPS > 1 ? (unsigned)((1ull << 32) / (unsigned)t.TPS) + 1u : 0u};      // tile_sample (gnnb_dev.h); TPS <= 1 is handled there
+                  t.TPS > 1 ? (unsigned)((1ull << 32) / (unsigned)t.TPS) + 1u : 0u,      // tile_sample (gnnb_dev.h); TPS <= 1 is handled there
+                  pps, pps > 1 ? (unsigned)((1ull << 32) / (unsigned)pps) + 1u : 0u};     // pair_sample
 }
 // rows of 64 floats of an edge's tap images in LDS: the tap matrix, and behind it the block-form image where the edge has one
 static int cm_rows(const GatherGeom& g) { return g.tm.NCG * (g.K2 + (g.block ? g.ncy : 0)); }
@@ -1170,8 +1173,9 @@ struct Forward {
     a.sw_from_gather = sparse ? 1 : 0;
     a.qtiles = fusedq_qtiles(d, sparse, post_input);
     const size_t ldsq = fusedq_lds_bytes(d, sparse, post_input, a.qtiles);
-    const long nrounds = (a.g.ntiles + QG_WAVES - 1) / QG_WAVES;
     const bool block = !sparse && (d.g.block & (embed ? 2 : 1));
+    a.npairs = block ? (long)B * pairs_per_sample(d.g.tm) : 0;      // the block-form kernels deal row pairs, not tiles, to their gather waves
+    const long nrounds = ((block ? a.npairs : a.g.ntiles) + QG_WAVES - 1) / QG_WAVES;
     void (*kern)(FArgs) = d.g.lanes == 16 ? (embed ? (block ? k_gather_update_q<16, 2, false, true> : k_gather_update_q<16, 2, false>)
                                                     : sparse ? k_gather_update_q<16, 1, false>
                                                     : (block ? k_gather_update_q<16, 0, false, true> : k_gather_update_q<16, 0, false>))

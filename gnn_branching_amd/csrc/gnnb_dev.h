@@ -306,7 +306,7 @@ __device__ __forceinline__ void stage_pack(float* lds, const float* pack, int nf
 }
 
 // ---- tile -> node mapping (gnnb_pack.h TileMap) ----
-struct DTileMap { int mode, N, C, H, W, CT, PY, PX, ay, ax, NBY, NBX, NCG, TPS, lpy, lpx; unsigned tps_magic; };
+struct DTileMap { int mode, N, C, H, W, CT, PY, PX, ay, ax, NBY, NBX, NCG, TPS, lpy, lpx; unsigned tps_magic; int PPS; unsigned pps_magic; };      // PPS: row pairs per sample (pair_sample)
 // sample = tile / TPS for a wave-uniform tile index: the loops carry it as a `long`, and a 64-bit signed division by a run-time divisor is ~60 vector
 // instructions per tile (an eighth of what a tile of the input update issues, profiles/r06_vector_trims_ab.txt).  tps_magic = floor(2^32 / TPS) + 1 (host,
 // to_dtm): the high word of tile * magic is the quotient or one above it for every tile < 2^32, the compare puts it right -- three scalar instructions.
@@ -314,6 +314,14 @@ __device__ __forceinline__ int tile_sample(const DTileMap& tm, long tile) {
   const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)tile), d = (unsigned)tm.TPS;
   if (d <= 1u) return (int)n;
   unsigned q = __umulhi(n, tm.tps_magic);      // floor(n / d) or one above it (magic > 2^32 / d)
+  if (q * d > n) --q;
+  return (int)q;
+}
+// the same for the row pairs of the block-form tiles (k_gather_update_q<.., BLOCK>): PPS = NCG x ceil(NBY / 2) x NBX pairs per sample, pps_magic as tps_magic
+__device__ __forceinline__ int pair_sample(const DTileMap& tm, long pair) {
+  const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)pair), d = (unsigned)tm.PPS;
+  if (d <= 1u) return (int)n;
+  unsigned q = __umulhi(n, tm.pps_magic);
   if (q * d > n) --q;
   return (int)q;
 }

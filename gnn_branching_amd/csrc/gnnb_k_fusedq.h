@@ -123,6 +123,7 @@ struct FArgs {
   UpdArgs u;           // the node update (k_node_update arguments; list0 / list1 / cnt0 / cnt1, nb are unused)
   int sw_from_gather;  // 1: the bias-sum scalar of a node comes out of its (sparse) gather; 0: u.sarr holds it (table / k_livesum)
   int qtiles;          // ring slots (2..QTILES): as many as fit beside the weights and the gather's tables in LDS
+  long npairs;         // BLOCK kernels: row pairs of the half-pass, B x DTileMap.PPS (fusedq_gather_pairs)
 };
 
 #ifndef QG_WAVES
@@ -221,6 +222,113 @@ __device__ __forceinline__ bool q_chain(const FArgs& a, const float* lds, const 
   return upd_chain_frag<POST, PIPE>(a.u, lds, X, gc, r0, r1, amb, sw, valid, lane, keep, ready);
 }
 
+// The gather waves of a BLOCK half-pass (edge 1 forward, tile [8, 1, 2]): they enumerate ROW PAIRS -- the tiles (by, bx) and (by + 1, bx) of one
+// sample and channel group, walked together (gather_pair16_block / _embed) -- not tiles: ceil(NBY / 2) x NBX pairs per channel group, a last
+// odd block row being a pair whose lower tile is masked.  `ptab` (the tile table's place in LDS, rewritten by fusedq_body) holds pair t of a
+// sample as cg | upper block row << 8 | block column << 20.  Lane j < 32: node (channel (j & 15) >> 1, position j & 1) of tile j >> 4; the
+// lanes above repeat them.  One decode and one bounds fetch per pair, one pair ahead; the live rows of BOTH tiles go to the ring under one
+// reservation (at most 32 rows: two ring tiles, the loop the 32-node tiles already run).  Returns true when a poll gave up.
+template <bool EMBED>
+__device__ __forceinline__ bool fusedq_gather_pairs(const FArgs& a, QHdr* q, float* qbase, const float* cm, const int* ptab, int NQ, int wave, int lane_in) {
+  const DTileMap& tm = a.g.tm;
+  const DGather& g = a.g.g;
+  int wg = blockIdx.x;
+  const int nwg = gridDim.x;
+  if ((nwg & 7) == 0) wg = (wg & 7) * (nwg >> 3) + (wg >> 3);      // workgroups b, b + 8, ... share an XCD: give them neighbouring rounds of pairs
+  const long npr = a.npairs;
+  const long nrounds = (npr + QG_WAVES - 1) / QG_WAVES;
+  const long r0 = wg, rstep = nwg;
+  bool stuck = false;
+  struct Next { int sample, cg, by, bx, n, gc; bool in, valid; float lb, ub; } nx;
+  auto fetch = [&](long r, int ln) {
+    const int hf = (ln >> 4) & 1, cl = (ln & 15) >> 1, px = ln & 1;
+    const long pair = r * QG_WAVES + wave;
+    nx.in = r < nrounds && pair < npr;
+    const long pl = nx.in ? pair : 0;
+    nx.sample = pair_sample(tm, pl);
+    const int t = __builtin_amdgcn_readfirstlane((int)(pl - (long)nx.sample * tm.PPS));
+    const int e = ptab[t];
+    nx.cg = e & 0xff;
+    nx.by = (e >> 8) & 0xfff;
+    nx.bx = (e >> 20) & 0xfff;
+    const int y = nx.by + hf + tm.ay, x = nx.bx * 2 + tm.ax + px;      // (PY = 1, PX = 2: blocktap_ok)
+    nx.valid = nx.by + hf < tm.NBY && (unsigned)y < (unsigned)tm.H && (unsigned)x < (unsigned)tm.W;
+    nx.n = nx.valid ? ((nx.cg * 8 + cl) * tm.H + y) * tm.W + x : 0;
+    nx.gc = (int)((long)nx.sample * tm.N + nx.n);
+    nx.lb = a.g.lb[nx.gc];
+    nx.ub = a.g.ub[nx.gc];
+  };
+  fetch(r0, lane_in);
+  for (long r = r0; r < nrounds && !stuck; r += rstep) {
+    if (!nx.in) break;
+    // (the lane index goes through an opaque asm once per pair: what depends on it alone is then computed here, next to its use, where hipcc otherwise
+    // hoists two dozen lane constants in front of the loop and spills them around it)
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
+    const int jn = lane & 31;
+    const int sample = nx.sample, cg = nx.cg, by = nx.by, bx = nx.bx, nn = nx.n, gc = nx.gc;
+    const bool valid = nx.valid;
+    const float lb = nx.lb, ub = nx.ub;
+    fetch(r + rstep, lane);
+    const bool need = valid && node_is_live(lb, ub);
+    const unsigned bal = (unsigned)__ballot(need);      // lanes 0 .. 31: the pair's 32 nodes
+    if (bal == 0u) continue;
+    f32x4 acc[8];
+    {
+      const int uy = __builtin_amdgcn_readfirstlane(by * g.ystep + g.ybase), ux = __builtin_amdgcn_readfirstlane(bx * g.xstep + g.xbase);
+      const float* img = cm + g.blk_off + cg * (BLK_NCY * 64);
+      if (EMBED) {
+        const long sb = (long)sample * g.Ns;
+        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)(a.g.es.lb + sb), 0, g.Ns * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.g.es.x + sb), 0, g.Ns * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(a.g.es.ub + sb), 0, g.Ns * 4, 0x00020000);
+        gather_pair16_block_embed(acc, img, rl, rx, ru, a.g.es.wb, uy, ux, g.Hs, g.Ws, lane);
+      } else {
+        const float* sbase = a.g.mu_src + (long)sample * g.Ns * 64;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, g.Ns * 256, 0x00020000);
+        const bool interior = uy >= 0 && ux >= 0 && uy + BLKP_WY <= g.Hs && ux + g.WX <= g.Ws;
+        if (interior) gather_pair16_block<true>(acc, img, rsrc, uy, ux, g.Hs, g.Ws, lane);
+        else gather_pair16_block<false>(acc, img, rsrc, uy, ux, g.Hs, g.Ws, lane);
+      }
+    }
+    const Ratio rt = compute_ratio(lb, ub);
+    const float sidx = __int_as_float(a.u.smod > 0 ? nn : gc);      // (q_chain: the index of the node's entry in u.sarr)
+    // ---- the live nodes of the pair -> consecutive rows of the ring ----
+    const int n = __popc(bal);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&q->reserve, n);
+    base = __builtin_amdgcn_readfirstlane(base);
+    const int pos = base + __popc(bal & ((1u << jn) - 1u));          // this lane's node (if needed) goes to row `pos`
+    const int mypos = need ? pos : -1;
+    // acc[4 hf + pg] of lane (b, c) = channels 4b .. 4b+3 of pair lane 16 hf + blk_dst(pg, lane), which knows its ring row
+    int colpos[8];                                                   // the ring row of each accumulator's node (-1: none)
+#pragma unroll
+    for (int pk = 0; pk < 8; ++pk) colpos[pk] = __shfl(mypos, 16 * (pk >> 2) + blk_dst(pk & 3, lane));
+    const int T0 = base >> 5, T1 = (base + n - 1) >> 5;
+    for (int T = T0; T <= T1; ++T) {
+      const int s = T % NQ;
+      bool ok = false;
+      for (int it = 0; it < Q_POLL_CAP; ++it) {
+        if (q_ld(&q->free_id[s]) == T) { ok = true; break; }
+        __builtin_amdgcn_s_sleep(4);
+      }
+      if (!ok) { if (lane == 0) atomicOr(a.u.status, 2); stuck = true; break; }
+      if (need && lane < 32 && (pos >> 5) == T)                      // the node's own lane writes the trailer of its row, the column lanes its channels
+        *reinterpret_cast<f32x4*>(qbase + ((size_t)s * 32 + (pos & 31)) * QROW + 64) =
+            f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, sidx};
+#pragma unroll
+      for (int pk = 0; pk < 8; ++pk) {
+        const int pd = colpos[pk];
+        if (pd >= 0 && (pd >> 5) == T) *reinterpret_cast<f32x4*>(qbase + ((size_t)s * 32 + (pd & 31)) * QROW + 4 * (lane >> 2)) = acc[pk];
+      }
+      const int lo = T * 32 > base ? T * 32 : base, hi = (T + 1) * 32 < base + n ? (T + 1) * 32 : base + n;
+      __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0): the rows are in LDS before their count is
+      if (lane == 0) __hip_atomic_fetch_add(&q->filled[s], hi - lo, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  return stuck;
+}
+
 #if defined(FUSED_TIMING) && FUSED_TIMING == 6      // dev: per-phase cycle sums of ONE k_gather_update_q template (Q_TIME_LANES / _SRC / _POST); slots 0-4 gather waves, 5-9 chain waves
 #ifndef Q_TIME_LANES
 #define Q_TIME_LANES 32
@@ -255,6 +363,14 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
   stage_gather(gl.cm, gl.ko, gl.tt, gl.kvo, a.g.g, a.g.tm.TPS);
   if (threadIdx.x < QHDR_INTS) reinterpret_cast<int*>(q)[threadIdx.x] = 0;
   __syncthreads();
+  if (BLOCK) {      // the gather waves walk row pairs (fusedq_gather_pairs): the pair table takes the tile table's place (PPS <= TPS, nobody reads either before the barrier below)
+    const DTileMap& tm = a.g.tm;
+    const int pby = (tm.NBY + 1) / 2;
+    for (int i = threadIdx.x; i < tm.PPS; i += blockDim.x) {
+      const int rw = i / tm.NBX, cg = rw / pby;
+      gl.tt[i] = cg | ((2 * (rw - cg * pby)) << 8) | ((i - rw * tm.NBX) << 20);
+    }
+  }
   if (threadIdx.x < QTILES) q->free_id[threadIdx.x] = threadIdx.x;
   __syncthreads();
   // (the thread index goes through an opaque asm so that hipcc derives the lane addresses here, behind the barriers, not in the prologue: the
@@ -340,6 +456,12 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
   }
 
   // ---------------- gather wave ----------------
+  if constexpr (BLOCK) {
+    const bool gave_up = fusedq_gather_pairs<EMBED>(a, q, qbase, gl.cm, gl.tt, NQ, wave, lane);
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    if (lane == 0) __hip_atomic_fetch_add(&q->done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return !gave_up;
+  }
   const int jn = LANES == 16 ? (lane & 15) : (lane & 31);
   const int h = lane >> 5;
   char* wsc = reinterpret_cast<char*>(gl.kvo + ((gather_slots(a.g.g.K2, LANES) + 3) & ~3));
@@ -391,7 +513,7 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
     Frag X;
     f32x4 acc[4];
     if (LANES == 32) gather_compute_tile<false, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, el, lane, X, ssum);
-    else gather_compute_tile16<EMBED, SPARSE, BLOCK>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
+    else gather_compute_tile16<EMBED, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
     if (!a.sw_from_gather) ssum = __int_as_float(a.u.smod > 0 ? tc.n : gc);      // (q_chain: the index of the node's entry in u.sarr)
 
     QT_MARK(2);                                     // table build + walk
@@ -422,9 +544,6 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
             *reinterpret_cast<float2*>(d + 2 * (rr & 3) + 16 * (rr >> 2)) = make_float2(X.t[0][rr], X.t[1][rr]);
           if (h == 0)
             *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
-        } else if (BLOCK) {
-          if (lane < 16)                            // (block form: the node's own row only carries its trailer here, the channels follow below)
-            *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
         } else {
           const int gq = lane >> 4;                 // lane (j, g'): channels 16 g' + 4 r + t
           f32x4* d = reinterpret_cast<f32x4*>(row + 16 * gq);
@@ -432,15 +551,6 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
           for (int rr = 0; rr < 4; ++rr) d[rr] = f32x4{acc[0][rr], acc[1][rr], acc[2][rr], acc[3][rr]};
           if (gq == 0)
             *reinterpret_cast<f32x4*>(row + 64) = f32x4{__int_as_float(gc | (rt.amb != 0.0f ? (int)0x80000000 : 0)), rt.r0, rt.r1, ssum};
-        }
-      }
-      if (BLOCK) {
-        // block form: acc[pg] of lane (b, c) = channels 4b .. 4b+3 of tile lane blk_dst(pg, lane), whose ring row that lane knows
-        const int mypos = need ? pos : -1;
-#pragma unroll
-        for (int pg = 0; pg < 4; ++pg) {
-          const int pd = __shfl(mypos, blk_dst(pg, lane));
-          if (pd >= 0 && (pd >> 5) == T) *reinterpret_cast<f32x4*>(qbase + ((size_t)s * 32 + (pd & 31)) * QROW + 4 * (lane >> 2)) = acc[pg];
         }
       }
       const int lo = T * 32 > base ? T * 32 : base, hi = (T + 1) * 32 < base + n ? (T + 1) * 32 : base + n;

@@ -815,6 +815,141 @@ __device__ __forceinline__ void gather_tile16_block_embed(f32x4 (&acc)[4], const
   static_assert(BLK_NCY <= 12, "blk_embed_row calls above");
 }
 
+// ---- the PAIR walk (k_gather_update_q<.., BLOCK>): the tiles (y, xp) and (y + 1, xp) of one sample together ----
+// With stride 2 the lower tile's window starts two rows below the upper tile's: per source channel the pair walks the window rows
+// wy = 0 .. 5, each loaded (or embedded) ONCE -- 18 window rows where two tiles walk 24.  The upper tile takes row wy as ky = wy (wy < 4),
+// the lower tile as ky = wy - 2 (wy >= 2), from the same image rows: per destination node the products still run in (cs, ky, kx) order
+// from a zero accumulator, the chain of gather_tile16_block link for link.  acc[4 hf + pg]: tile hf (0 upper, 1 lower), pg as there.
+// (Not built into this walk: issuing only the groups of a position's LIVE channels, packed.  Built as one asm statement per accumulator
+// and window row -- a C++ branch around the MFMAs makes hipcc sink loads into it -- the four MFMAs of a statement are a dependent chain
+// with two wait states per link, and both launches were slower than with every group issued: DESIGN.md section 5.1a.)
+#define BLKP_WY 6
+#define BLKP_NCW (3 * BLKP_WY)
+#ifndef BLKP_DEPTH
+#define BLKP_DEPTH 4          // window rows in flight (dense rows): 4 measured best for the 18 rows of a pair (6: +2.3 us on the launch)
+#endif
+template <bool UP, bool LO>
+__device__ __forceinline__ void blkp_taps(f32x4 (&acc)[8], const float (&r)[6], const f32x4* tp, int cs, int wy) {
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    if (!(hf ? LO : UP)) continue;
+    const int cy = cs * BLK_KH + (hf ? wy - 2 : wy);
+    const f32x4 t[2] = {tp[(cy * 4 + 0) * 4], tp[(cy * 4 + 1) * 4]};      // group gr of position 0: the image holds the same taps for position 1
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int pg = 0; pg < 4; ++pg) acc[4 * hf + pg] = mfma4(r[x + 2 * (pg >> 1)], t[pg & 1][x], acc[4 * hf + pg]);
+  }
+}
+// dense source rows: a ring of BLKP_DEPTH window rows in flight, as in gather_tile16_block
+template <bool INTERIOR>
+__device__ __forceinline__ void gather_pair16_block(f32x4 (&acc)[8], const float* img, __amdgpu_buffer_rsrc_t rsrc, int wy0, int wx0, int Hs, int Ws,
+                                                    int lane) {
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x4* tp = reinterpret_cast<const f32x4*>(img) + (lane & 3);
+  const unsigned lane_off = 4u * (unsigned)lane;
+  float r[BLKP_DEPTH][6];
+  unsigned xin = 0;                                   // border pairs: which of the six window columns lie in the source layer (wave-uniform: one scalar for the walk)
+  if (!INTERIOR) {
+#pragma unroll
+    for (int x = 0; x < 6; ++x) xin |= (unsigned)((unsigned)(wx0 + x) < (unsigned)Ws) << x;
+  }
+  auto load = [&](float (&d)[6], int cw) {
+    const int cs = cw / BLKP_WY, wy = wy0 + cw % BLKP_WY;
+    const int row0 = (cs * Hs + wy) * Ws + wx0;
+    if (INTERIOR) {
+      const unsigned soff = (unsigned)row0 * 256u;
+#pragma unroll
+      for (int x = 0; x < 6; ++x) d[x] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, lane_off + 256u * x, soff, 0));
+    } else {
+      const unsigned in = (unsigned)wy < (unsigned)Hs ? xin : 0u;
+#pragma unroll
+      for (int x = 0; x < 6; ++x) {
+        const unsigned o = (in >> x & 1u) ? (unsigned)(row0 + x) * 256u + lane_off : BUF_OOB;
+        d[x] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, o, 0, 0));
+      }
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < BLKP_DEPTH && d < BLKP_NCW; ++d) load(r[d], d);
+#pragma unroll
+  for (int cw = 0; cw < BLKP_NCW; ++cw) {
+    const int cs = cw / BLKP_WY, wy = cw % BLKP_WY;
+    if (wy < 2) blkp_taps<true, false>(acc, r[cw % BLKP_DEPTH], tp, cs, wy);
+    else if (wy < 4) blkp_taps<true, true>(acc, r[cw % BLKP_DEPTH], tp, cs, wy);
+    else blkp_taps<false, true>(acc, r[cw % BLKP_DEPTH], tp, cs, wy);
+    __builtin_amdgcn_sched_barrier(0);
+    if (cw + BLKP_DEPTH < BLKP_NCW) load(r[cw % BLKP_DEPTH], cw + BLKP_DEPTH);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// round 0: the 18 window rows embedded once each (blk_embed_row's chain); three sets of eight window rows of scalars, all requested first
+template <int U, bool UP, bool LO>
+__device__ __forceinline__ void blkp_embed_row(f32x4 (&acc)[8], const BlkIn& s, const f32x4* tp, int cs, int wy, float w0, float w1, float w2, float w3) {
+  float r[8];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    f32x4 e = g ? mfma4_bc<2 * U + 1>(s.l, w0, f32x4{0.f, 0.f, 0.f, 0.f}) : mfma4_bc<2 * U>(s.l, w0, f32x4{0.f, 0.f, 0.f, 0.f});
+    e = g ? mfma4_bc<2 * U + 1>(s.x, w1, e) : mfma4_bc<2 * U>(s.x, w1, e);
+    e = g ? mfma4_bc<2 * U + 1>(s.u, w2, e) : mfma4_bc<2 * U>(s.u, w2, e);
+    e = g ? mfma4_bc<2 * U + 1>(s.one, w3, e) : mfma4_bc<2 * U>(s.one, w3, e);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) r[4 * g + v] = relu_max(e[v]);
+  }
+  const float r6[6] = {r[0], r[1], r[2], r[3], r[4], r[5]};
+  blkp_taps<UP, LO>(acc, r6, tp, cs, wy);
+}
+template <int CW>
+__device__ __forceinline__ void blkp_embed_cw(f32x4 (&acc)[8], const BlkIn& s, const f32x4* tp, float w0, float w1, float w2, float w3) {
+  constexpr int cs = CW / BLKP_WY, wy = CW % BLKP_WY;
+  blkp_embed_row<CW % 8, (wy < 4), (wy >= 2)>(acc, s, tp, cs, wy, w0, w1, w2, w3);
+}
+__device__ __forceinline__ void gather_pair16_block_embed(f32x4 (&acc)[8], const float* img, __amdgpu_buffer_rsrc_t rl, __amdgpu_buffer_rsrc_t rx,
+                                                          __amdgpu_buffer_rsrc_t ru, const float* wb, int wy0, int wx0, int Hs, int Ws, int lane) {
+  static_assert(BLKP_NCW == 18, "three sets of eight window rows, the calls below");
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float w0 = wb[3 * lane], w1 = wb[3 * lane + 1], w2 = wb[3 * lane + 2], w3 = wb[192 + lane];
+  const f32x4* tp = reinterpret_cast<const f32x4*>(img) + (lane & 3);
+  const int i = lane & 3, g = (lane >> 2) & 1, du = lane >> 3;
+  const int wx = wx0 + 4 * g + i;
+  const bool xin = 4 * g + i < 6 && (unsigned)wx < (unsigned)Ws;
+  auto fetch = [&](BlkIn& s, int cw0) {
+    const int cw = cw0 + du;
+    const int cs = cw / BLKP_WY, wy = wy0 + cw % BLKP_WY;
+    const bool inb = xin && cw < BLKP_NCW && (unsigned)wy < (unsigned)Hs;
+    const unsigned o = inb ? (unsigned)((cs * Hs + wy) * Ws + wx) * 4u : BUF_OOB;
+    s.l = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, o, 0, 0));
+    s.x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, o, 0, 0));
+    s.u = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ru, o, 0, 0));
+    s.one = inb ? 1.0f : 0.0f;
+  };
+  BlkIn s0, s1, s2;
+  fetch(s0, 0);
+  fetch(s1, 8);
+  fetch(s2, 16);
+  __builtin_amdgcn_sched_barrier(0);
+  blkp_embed_cw<0>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<1>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<2>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<3>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<4>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<5>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<6>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<7>(acc, s0, tp, w0, w1, w2, w3);
+  blkp_embed_cw<8>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<9>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<10>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<11>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<12>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<13>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<14>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<15>(acc, s1, tp, w0, w1, w2, w3);
+  blkp_embed_cw<16>(acc, s2, tp, w0, w1, w2, w3);
+  blkp_embed_cw<17>(acc, s2, tp, w0, w1, w2, w3);
+}
+
 // the aggregate of one 16-node tile (forward edges only: no tap-count division): acc[t][r] of lane (j, g') = channel 16 g' + 4 r + t;
 // a block-form edge (a.g.block): acc[pg][v] of lane (b, c) = channel 4b + v of tile lane blk_dst(pg, lane)
 template <bool EMBED, bool SPARSE, bool BLOCK = false>
