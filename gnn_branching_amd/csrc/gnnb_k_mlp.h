@@ -282,12 +282,84 @@ __device__ __forceinline__ void pre_tile(const PreAllArgs& a, const float* lds, 
 #ifndef PRE_WAVES
 #define PRE_WAVES 16      // the weights (150 KB) allow one workgroup per CU: 16 waves of <= 128 registers fill it
 #endif
-// k_pre<true>'s LDS: the backward image and the forward chain's small vectors (W1, B1, B2) behind it; its share of W53 per thread in registers
+// k_pre<true>'s LDS: a forward workgroup holds the forward image, a backward workgroup the backward image, each at offset 0; a lone
+// workgroup the backward image and the forward chain's small vectors (W1, B1, B2) behind it, its share of W53 per thread in registers
 #define PRE_LDS_FLOATS ((int)PackPreBwdL3::FLOATS + (int)PackPreFwdL3::W23)
 #define PRE_W53_REGS ((3072 + PRE_WAVES * 64 - 1) / (PRE_WAVES * 64))
 static_assert(PRE_LDS_FLOATS * 4 <= 160 * 1024, "k_pre: LDS");
 static_assert((int)PackPreFwdL3::FLOATS - (int)PackPreFwdL3::W23 == 6144 && (int)PackPreBwdL3::FLOATS - (int)PackPreBwdL3::W53 == 6144,
               "k_pre: the forward W23 block waits in W53's place");
+// k_pre<true>, two workgroups or more: which workgroups run the forward tiles.  One workgroup of every PRE_NF_DIV consecutive ones, at a
+// place that moves on by one from group to group, so the forward workgroups are not all b % 8 == const (observed: workgroups b and b + 8
+// share an XCD; with 4 they take four of the eight residues, and a rotation that takes all eight was no faster: 52.8 against 53.3 us on
+// wide, equal elsewhere).  A forward tile is one 64x64 block behind the feature layer, a backward tile five: a forward wave runs several
+// tiles while a backward wave runs its one or two.
+#ifndef PRE_NF_DIV
+#define PRE_NF_DIV 4      // (pre= us, base B=256 / wide B=256 / deep B=128: 8: 40.0 / 75.7 / 34.9, 6: 33.0 / 61.8 / 29.7, 5: 31.9 / 56.4 / 27.4,
+                          // 4: 32.3 / 53.3 / 30.0, 3: 32.0 / 56.7 / 30.2; parent 38.5 / 68.9 / 36.1: profiles/pre_roles_ab.txt)
+#endif
+// One piece (NF floats, a compile-time size) of an LDS image staged by the PRE_WAVES * 64 threads of k_pre: load() requests the thread's
+// share, store() writes it.  A role's staging calls load() for all its pieces and then store() for all of them, in the same order, so
+// the whole image is ONE batch of requests in flight (copy_to_lds per piece is a global -> LDS round trip per piece, nine in a row for
+// the backward image); the loads are unconditional (an index past the piece reads its first element), only the LDS writes are guarded.
+template <int NF>
+struct PrePiece {
+  static constexpr int T = PRE_WAVES * 64, N4 = NF / 4, R = (N4 + T - 1) / T;
+  static_assert(NF % 4 == 0, "whole f32x4");
+  f32x4 v[R];
+  __device__ __forceinline__ void load(const float* src) {
+    const f32x4* g = reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int i = (int)threadIdx.x + u * T;
+      v[u] = g[i < N4 ? i : 0];
+    }
+  }
+  __device__ __forceinline__ void store(float* lds) const {
+    f32x4* l = reinterpret_cast<f32x4*>(lds);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const int i = (int)threadIdx.x + u * T;
+      if (i < N4) l[i] = v[u];
+    }
+  }
+};
+struct PreRole { bool fwd; int rank, n; };      // rank among the n workgroups of the same role
+__host__ __device__ constexpr PreRole pre_role(int grid, int b) {
+  constexpr int D = PRE_NF_DIV;
+  const int q = b / D, ph = b % D, qg = grid / D;
+  const int nf = qg + (qg % D < grid % D ? 1 : 0);                   // the last, partial group has its forward workgroup or not
+  if (ph == q % D) return PreRole{true, q, nf};
+  return PreRole{false, b - q - (ph > q % D ? 1 : 0), grid - nf};
+}
+constexpr bool pre_role_check(int grid) {      // both roles present, ranks 0 .. n-1 in workgroup order
+  int nf = 0, nb = 0;
+  for (int b = 0; b < grid; ++b) {
+    const PreRole r = pre_role(grid, b);
+    if (r.rank != (r.fwd ? nf : nb) || r.n != pre_role(grid, 0).n + (r.fwd ? 0 : grid - 2 * pre_role(grid, 0).n)) return false;
+    ++(r.fwd ? nf : nb);
+  }
+  return nf >= 1 && nb >= 1 && nf == pre_role(grid, 0).n;
+}
+constexpr bool pre_role_check_all() {
+  for (int grid = 2; grid <= 2 * PRE_NF_DIV * PRE_NF_DIV + 2; ++grid)      // (the pattern repeats every PRE_NF_DIV^2 workgroups)
+    if (!pre_role_check(grid)) return false;
+  return pre_role_check(256) && pre_role_check(304);
+}
+static_assert(PRE_NF_DIV >= 2 && pre_role_check_all(), "k_pre: every workgroup has one role and one rank in it");
+// tile t (< the tiles of one direction) of the role loops: which layer (wave-uniform), then the tile
+template <bool BF3>
+__device__ __forceinline__ void pre_tile_at(const PreAllArgs& a, const float* lf, const float* lb, const float* w23f, bool bwd, long t, int lane) {
+  int k = 0, count = 0;
+  for (; k < a.L; ++k) {
+    count = a.cnt[4 * k + 1];
+    const long tk = (count + 31) / 32;
+    if (t < tk) break;
+    t -= tk;
+  }
+  pre_tile<BF3>(a, lf, lb, w23f, k, bwd, a.list[k], count, t, lane);
+}
+
 template <bool BF3>
 __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -314,6 +386,45 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_pre(PreAllArgs a) {
       for (long t = (long)wave * gridDim.x + blockIdx.x; t < nhalf; t += (long)gridDim.x * PRE_WAVES) run(t, false, lds, lds, lds + PackPreFwdL3::W23);
       return;
     }
+    if (gridDim.x >= 2) {
+      // ROLES: a workgroup runs tiles of ONE direction.  Forward workgroups stage the 27 KB forward image and nothing else, backward
+      // workgroups the backward image with W53 in its own place: one barrier, no block waiting in another's slot, and a backward tile
+      // -- the launch's critical path -- has only its own staging in front of it.  Tiles go to all 16 waves, strided over the role's
+      // workgroups.  (Asking for a wave's first tile's scalars before the staging, and for a forward wave's next tile's under the
+      // current one, was built and measured: no gain in this launch at this split, taken out -- profiles/pre_roles_ab.txt.)
+      const PreRole role = pre_role((int)gridDim.x, (int)blockIdx.x);
+      const long stride = (long)role.n * PRE_WAVES;
+      // (the wave's number through a scalar register: the tile index, the layer walk and the layer's pointers are then scalar as well)
+      long t = (long)__builtin_amdgcn_readfirstlane(wave) * role.n + role.rank;
+      if (role.fwd) {
+        PrePiece<512 + 64> w1;                                         // W1, B1
+        PrePiece<64> b2;
+        PrePiece<6144> w23;
+        w1.load(a.pack_f + PackPreFwd::W1); b2.load(a.pack_f + PackPreFwd::B2); w23.load(a.pack_f + PackPreFwd::W23);
+        w1.store(lds + PackPreFwdL3::W1); b2.store(lds + PackPreFwdL3::B2); w23.store(lds + PackPreFwdL3::W23);
+        __syncthreads();
+        for (; t < nhalf; t += stride) pre_tile_at<BF3>(a, lds, lds, lds + PackPreFwdL3::W23, false, t, lane);
+        return;
+      }
+      {                                                                // 16 requests of 16 B per thread, in the order a tile reads the blocks
+        PrePiece<512 + 64> w1;                                         // W1, B1
+        PrePiece<64> b2, b3, b4, b5;
+        PrePiece<6144> w23, w33, w53;
+        PrePiece<18432> w43;
+        w1.load(a.pack_b + PackPreBwd::W1); b2.load(a.pack_b + PackPreBwd::B2); w23.load(a.pack_b + PackPreBwd::W23);
+        b3.load(a.pack_b + PackPreBwd::B3); w33.load(a.pack_b + PackPreBwd::W33);
+        b4.load(a.pack_b + PackPreBwd::B4); w43.load(a.pack_b + PackPreBwd::W43);
+        b5.load(a.pack_b + PackPreBwd::B5); w53.load(a.pack_b + PackPreBwd::W53);
+        w1.store(lds + PackPreBwdL3::W1); b2.store(lds + PackPreBwdL3::B2); w23.store(lds + PackPreBwdL3::W23);
+        b3.store(lds + PackPreBwdL3::B3); w33.store(lds + PackPreBwdL3::W33);
+        b4.store(lds + PackPreBwdL3::B4); w43.store(lds + PackPreBwdL3::W43);
+        b5.store(lds + PackPreBwdL3::B5); w53.store(lds + PackPreBwdL3::W53);
+      }
+      __syncthreads();
+      for (; t < nhalf; t += stride) pre_tile_at<BF3>(a, lds, lds, nullptr, true, t, lane);
+      return;
+    }
+    // A LONE WORKGROUP (tiny batches) runs both directions itself, in
     // ONE staging phase: the whole backward image except W53 -- the block a backward tile reads last -- goes to its place at entry; the
     // forward chain's W23 has W53's size and waits in its place, the forward small vectors sit behind the image (PRE_LDS_FLOATS).  Each
     // thread requests its share of W53 at entry too and keeps it in registers over the forward tiles (PRE_W53_REGS float2 per thread):
