@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -18,6 +18,9 @@ inefficient points, and one round bounds the second pairs of all the properties'
 also returns the input point the upper bound belongs to -- the counter-example, when the verdict is one -- and prints the network's value
 at it; --pgd N lowers every child's upper bound by up to N projected gradient steps on the network from its LP point (DESIGN.md section 7.8);
 --restarts R with --pgd N also descends from R uniform points of every child's box and keeps the least value (section 7.9; --pgd 0: the points alone).
+--frontier K --branching babsr branches on the BaBSR heuristic alone, as the reference's relu_bab does: the same
+rounds, bounds and pick rule with gnnb_babsr and the decision rule on the device in the GNN's place -- what the GNN's branch count is compared
+with; with --props N every property has its own intercept counter (frontier.verify_properties_babsr).  (--babsr alone is the host loop.)
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -52,7 +55,13 @@ def main():
     ap.add_argument("--witness", action="store_true", help="with --frontier: return the point of the upper bound and print the network's value at it")
     ap.add_argument("--pgd", type=int, default=None, metavar="N", help="with --frontier: up to N projected gradient steps from every child's LP point")
     ap.add_argument("--restarts", type=int, default=None, metavar="R", help="with --pgd N: also descend from R uniform points of every child's box")
+    ap.add_argument("--branching", default=None, choices=("gnn", "babsr"), help="with --frontier K: what picks the split, the GNN (default) or the BaBSR heuristic alone")
     args = ap.parse_args()
+    if args.branching is not None and args.frontier is None:
+        ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
+    if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
+        ap.error("--branching babsr takes no --threshold and no --online: it never asks the GNN")
+    branching = args.branching or "gnn"
     if args.restarts is not None and (args.pgd is None or not 0 <= args.restarts <= 4096):
         ap.error("--restarts R needs --pgd N, and 0 <= R <= 4096")
     if (args.witness or args.pgd is not None) and (args.frontier is None or (args.pgd is not None and args.pgd < 0)):
@@ -76,7 +85,7 @@ def main():
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
     if args.props is not None:
-        from gnn_branching_amd.frontier import FrontierJob, FrontierJobs, verify_properties, verify_properties_threshold
+        from gnn_branching_amd.frontier import FrontierJob, FrontierJobs, verify_properties, verify_properties_babsr, verify_properties_threshold
         wrong, jobs, names = [c for c in range(10) if c != 3], [], []
         for j in range(args.props):
             seed, cls = args.seed + j // 9, wrong[j % 9]
@@ -87,7 +96,9 @@ def main():
         lp = lp_producer.LayerGraphLP(prop, x - args.eps, x + args.eps, bounds="kw_device")
         choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         max_rounds, stats = max(1, args.nodes // (2 * args.frontier)), []
-        if args.threshold is None:
+        if branching == "babsr":
+            results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+        elif args.threshold is None:
             results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         else:
             results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
@@ -110,14 +121,15 @@ def main():
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
                                                                       branching_threshold=args.threshold, stats=stats, online_threshold=args.online,
-                                                                      **upper)
+                                                                      branching=branching, **upper)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
         if args.online is not None:
             kw += f"; {stats['online_steps']} learning steps over {stats['online_rows']} learn rows"
         if args.witness:
             kw += witness_of(upper["witness"][0], layers[:-1], layers[-1])
-        print(f"after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
+        by = "" if args.branching is None else f"{stats['branches']} branches by {branching}, "
+        print(f"after {rounds} rounds ({by}{bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]

@@ -132,6 +132,11 @@ SYMBOLS = [
      [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_choose_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_int] + [C.c_void_p] * 6 +
      [C.POINTER(Children), C.POINTER(Children)] + [C.c_void_p] * 4 + [C.c_void_p]),
+    ("gnnb_frontier_babsr_decide_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_babsr_decide", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_double, C.c_int, C.POINTER(C.c_int32), C.c_int] +
+     [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_babsr_decide_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan)] + [C.c_void_p] * 3 + [C.c_double, C.c_int, C.POINTER(C.c_int32), C.c_int] +
+     [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_learn", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),
     ("gnnb_frontier_witness", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gnnb_frontier_witness_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_int, C.c_void_p, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p,

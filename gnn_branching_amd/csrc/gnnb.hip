@@ -99,7 +99,7 @@ enum ProfClass {
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
   PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS,
   PC_FR_LEARN, PC_TROWS_GATHER, PC_NET_DESCEND, PC_FR_WITNESS, PC_FR_WITNESS_JOBS,
-  PC_NET_STARTS, PC_NET_DESCEND_TILE, PC_NET_STARTS_PICK, PC_COUNT
+  PC_NET_STARTS, PC_NET_DESCEND_TILE, PC_NET_STARTS_PICK, PC_FR_BABSR_DECIDE, PC_FR_BABSR_DECIDE_JOBS, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -110,7 +110,7 @@ static const char* kProfNames[PC_COUNT] = {
     "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
     "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs",
     "k_frontier_learn", "k_trows_gather", "k_net_descend", "k_frontier_witness", "k_frontier_witness_jobs",
-    "k_net_starts", "k_net_descend_tile", "k_net_starts_pick"};
+    "k_net_starts", "k_net_descend_tile", "k_net_starts_pick", "k_frontier_babsr_decide", "k_frontier_babsr_decide_jobs"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -2055,7 +2055,7 @@ static int fr_fallback_in(const char* who, const gnnb_fallback* in, FrFallbackAr
   a->branching_threshold = in->branching_threshold; a->decision_threshold = in->decision_threshold;
   a->kwbd_threshold = in->kwbd_threshold; a->sparsest_layer = in->sparsest_layer; a->n_order = in->n_order;
   for (int q = 0; q < in->n_order; ++q) a->order[q] = in->random_order[q];
-  a->icp = in->icp; a->ineff = in->ineff;
+  a->icp = in->icp; a->ineff = in->ineff; a->pair_a = 1;
   return GNNB_OK;
 }
 
@@ -2193,6 +2193,73 @@ extern "C" int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const
   Launcher run{h, st};
   run.run(PC_FR_CHOOSE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_choose_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, m_entry); });
   if (M > 0) run.run(PC_FR_CHOOSE_COPY, [&] { hipLaunchKernelGGL(k_frontier_choose_copy, dim3(2 * M, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+// ---- BaBSR alone: the decision of every parent row (reference plnn/relu_conv_any_kw.py:45-181, the decision
+// rule of plnn/kw_score_conv.py:115-156) ----
+extern "C" size_t gnnb_frontier_babsr_decide_workspace_bytes(const gnnb_t* h, int K) {
+  if (!h || !h->bound || K < 1) return 0;
+  return (size_t)K * FC_COUNT * sizeof(int32_t);
+}
+
+// The checks gnnb_frontier_babsr_decide and gnnb_frontier_babsr_decide_jobs share on the rule's own arguments, before the handle is looked
+// at (as K's range is), and the arguments of k_frontier_candidates / fr_fallback_walk without a pair A.
+static int fr_babsr_ranges(const char* who, int n_order, double decision_threshold) {
+  if (n_order < 0 || n_order > MAXL) return fail(GNNB_E_INVALID, "%s: random_order of n_order = %d layers (0..%d)", who, n_order, MAXL);
+  if (decision_threshold != decision_threshold) return fail(GNNB_E_INVALID, "%s: decision_threshold = %g", who, decision_threshold);
+  return GNNB_OK;
+}
+
+static int fr_babsr_args(const gnnb_t* h, const char* who, int n, const float* scores, const float* intercepts, const float* scorer_mask,
+                         double decision_threshold, int sparsest_layer, const int32_t* random_order, int n_order, int32_t* icp, int32_t* decisions,
+                         void* workspace, size_t workspace_bytes, FrFallbackArgs* a) {
+  if (!scores || !intercepts || !scorer_mask || !icp || !decisions || !workspace || (n_order > 0 && !random_order))
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  const size_t need = (size_t)n * FC_COUNT * sizeof(int32_t);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  a->s = fr_shape(h);
+  a->K = n; a->scores = scores; a->icp_tb = intercepts; a->amb = scorer_mask;
+  a->decision_threshold = decision_threshold; a->sparsest_layer = sparsest_layer; a->n_order = n_order;
+  for (int q = 0; q < n_order; ++q) a->order[q] = random_order[q];
+  a->icp = icp; a->kw_dec = decisions; a->cand = (int32_t*)workspace; a->pair_a = 0;
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_frontier_babsr_decide(gnnb_t* h, int K, const float* scores, const float* intercepts, const float* scorer_mask,
+                                          double decision_threshold, int sparsest_layer, const int32_t* random_order, int n_order, int32_t* icp,
+                                          int32_t* decisions, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_babsr_decide";
+  if (K < 1 || K > 32767) return fail(GNNB_E_INVALID, "%s: K = %d outside 1..32767", who, K);
+  if (int rc = fr_babsr_ranges(who, n_order, decision_threshold)) return rc;
+  if (int rc = net_preflight(h, who)) return rc;
+  FrFallbackArgs a{};
+  if (int rc = fr_babsr_args(h, who, K, scores, intercepts, scorer_mask, decision_threshold, sparsest_layer, random_order, n_order, icp, decisions,
+                             workspace, workspace_bytes, &a))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CANDIDATES, [&] { hipLaunchKernelGGL(k_frontier_candidates, dim3(K), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_BABSR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_babsr_decide, dim3(1), dim3(64), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_frontier_babsr_decide_jobs(gnnb_t* h, const gnnb_plan* plan, const float* scores, const float* intercepts,
+                                               const float* scorer_mask, double decision_threshold, int sparsest_layer, const int32_t* random_order,
+                                               int n_order, int32_t* icp, int32_t* decisions, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_babsr_decide_jobs";
+  if (int rc = fr_babsr_ranges(who, n_order, decision_threshold)) return rc;
+  FrPlan j{};
+  const int ng = h && h->bound ? h->kw_net.L + 2 : 0;
+  if (int rc = fr_plan(h, who, plan, &ng, &j)) return rc;
+  FrFallbackArgs a{};
+  if (int rc = fr_babsr_args(h, who, j.n, scores, intercepts, scorer_mask, decision_threshold, sparsest_layer, random_order, n_order, icp, decisions,
+                             workspace, workspace_bytes, &a))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_CANDIDATES, [&] { hipLaunchKernelGGL(k_frontier_candidates, dim3(j.n), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_BABSR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_babsr_decide_jobs, dim3(j.n_entries), dim3(64), 0, st, a, j); });
   return run.rc;
 }
 

@@ -1,10 +1,10 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
 // gnnb_frontier_gather, gnnb_frontier_expand, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
 // a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, their many-job form of section 7.6, and the selection
-// of the rows an online round learns from, section 7.7: gnnb_frontier_learn; last the witness of the upper bound, section 7.8:
-// gnnb_frontier_witness).  Between them run the existing batch kernels (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs,
-// gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched, and the network's value at a round's points: gnnb_net_eval or the descent
-// that can take its place, gnnb_net_descend (gnnb_k_net.h).
+// of the rows an online round learns from, section 7.7: gnnb_frontier_learn; the witness of the upper bound, section 7.8:
+// gnnb_frontier_witness; and BaBSR alone in the GNN's place, section 7.10: gnnb_frontier_babsr_decide).  Between them run the existing
+// batch kernels (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched, and
+// the network's value at a round's points: gnnb_net_eval or the descent that can take its place, gnnb_net_descend (gnnb_k_net.h).
 //
 // The POOL is a struct of arrays over `capacity` slots: mask (cap, R) int8, the fp64 bounds of graph layers 1..L+1 (cap, N_k) exactly as
 // gnnb_kw_bounds wrote them, the best dual point alpha / beta (cap, R), its value bound (cap) and the flag open (cap).
@@ -431,6 +431,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide_jobs(FrCommitArg
 //
 // fp32 scores are compared after promotion to double (Python's .item()); the improvement is fp64 in the reference's operation order
 // (2 bound is exact, so contraction cannot change it; the division is correctly rounded).
+//
+// The decision rule itself -- the per-layer reduction of k_frontier_candidates and the three-way choice of fr_fallback_walk -- has this one
+// text.  FrFallbackArgs.pair_a = 0 (section 7.10, at the end of this part) runs it without a pair A: every row takes part, no improvement
+// is computed or tested, no inefficiency count is looked up and no selection list is written.
 
 enum { FC_SCORE_LAY, FC_SCORE_IDX, FC_SCORE_HOLDS, FC_ICP_LAY, FC_ICP_IDX, FC_ORDER_LAY, FC_ORDER_IDX, FC_VALID, FC_COUNT };   // a row's candidates
 
@@ -445,6 +449,7 @@ struct FrFallbackArgs {
   int32_t* icp; const int32_t* ineff;
   double* gnn_imp; int32_t* kw_dec; int32_t* sel_rows; int32_t* sel_slots; int32_t* sel_dec; int32_t* m;
   int32_t* cand;                                                                // workspace (K, FC_COUNT)
+  int pair_a;                                                                   // 0: BaBSR alone (section 7.10) -- no pair A, no improvement test, no selection
 };
 
 struct FrChooseArgs {
@@ -485,8 +490,8 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_candidates(FrFallbackAr
   __shared__ int si[FR_THREADS], mi[FR_THREADS], ui[FR_THREADS], first[MAXL];
   const int i = blockIdx.x, tid = threadIdx.x, R = a.s.R, L = a.s.L;
   int32_t* out = a.cand + (long)i * FC_COUNT;
-  const int s = a.slots[i];
-  if (!fr_slot_ok(a.p, s) || !a.live[2 * i]) {          // no live GNN decision: the row takes no part (the whole workgroup leaves)
+  const int s = a.pair_a ? a.slots[i] : 0;
+  if (a.pair_a && (!fr_slot_ok(a.p, s) || !a.live[2 * i])) {      // no live GNN decision: the row takes no part (the whole workgroup leaves)
     if (tid == 0) {
       a.gnn_imp[i] = __longlong_as_double(0x7ff8000000000000LL);
       for (int q = 0; q < FC_COUNT; ++q) out[q] = q == FC_VALID || q == FC_SCORE_HOLDS ? 0 : -1;
@@ -535,8 +540,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_candidates(FrFallbackAr
     const int l = a.order[q];
     if (l >= 0 && l < L && first[l] >= 0) { ord_l = l; ord_i = first[l]; }
   }
-  const double bound = a.p.bound[s];
-  a.gnn_imp[i] = bound < 0.0 ? fr_improvement(fr_child_lb(a.infeasible, a.bound, 2L * i), fr_child_lb(a.infeasible, a.bound, 2L * i + 1), bound) : 1.0;
+  if (a.pair_a) {
+    const double bound = a.p.bound[s];
+    a.gnn_imp[i] = bound < 0.0 ? fr_improvement(fr_child_lb(a.infeasible, a.bound, 2L * i), fr_child_lb(a.infeasible, a.bound, 2L * i + 1), bound) : 1.0;
+  }
   out[FC_SCORE_LAY] = best_l; out[FC_SCORE_IDX] = best_i;
   out[FC_SCORE_HOLDS] = best_l >= 0 && best_l != a.sparsest_layer && (double)best_v > a.decision_threshold;
   out[FC_ICP_LAY] = icp_l; out[FC_ICP_IDX] = icp_i;
@@ -555,7 +562,7 @@ __device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const 
   for (int i = 0; i < v.K; ++i) {
     const int row = v.row0 + i;
     const int32_t* c = a.cand + (long)row * FC_COUNT;
-    if (!c[FC_VALID] || !(a.gnn_imp[row] < a.branching_threshold)) continue;        // :155
+    if (!c[FC_VALID] || (a.pair_a && !(a.gnn_imp[row] < a.branching_threshold))) continue;        // :155
     int lay, idx;
     if (c[FC_SCORE_HOLDS]) {
       lay = c[FC_SCORE_LAY]; idx = c[FC_SCORE_IDX];
@@ -569,6 +576,7 @@ __device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const 
       continue;                                         // random_order names no layer with an undecided node: no decision, the counter stays
     }
     a.kw_dec[2L * row] = lay; a.kw_dec[2L * row + 1] = idx;
+    if (!a.pair_a) continue;                            // BaBSR alone: no table of inefficient points, no selection list
     int node;
     if (!fr_node(a.s, lay, idx, &node) || !(v.ineff[node] < a.kwbd_threshold)) continue;        // :160-167
     const int q = v.sel0 + m++;
@@ -576,7 +584,7 @@ __device__ __forceinline__ void fr_fallback_walk(const FrFallbackArgs& a, const 
     a.sel_dec[2L * q] = lay; a.sel_dec[2L * q + 1] = idx;
   }
   *v.icp = icp;
-  *v.m = m;
+  if (v.m) *v.m = m;
 }
 
 __global__ __launch_bounds__(64) void k_frontier_fallback(FrFallbackArgs a) {
@@ -732,6 +740,26 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_jobs(FrChooseArg
   const int m = min(min(max(m_entry[e], 0), k), max(a.m - sel0, 0));      // a.m: M, the host's copy of the sum
   const FrFbView v{row0, k, sel0, nullptr, a.ineff + (long)seg * a.s.R, nullptr};
   fr_choose(a, v, m);
+}
+
+// ---- BaBSR alone: relu_bab's branching -----------------------------------------------------------------------
+// Reference plnn/relu_conv_any_kw.py:45-181 with split_decision = 'kw': every parent row gets the decision of kw_score_conv.py:115-156 and
+// nothing else.  The rule has ONE text: k_frontier_candidates with pair_a = 0 (no slot, no pair A, no improvement: every row takes part)
+// and fr_fallback_walk with pair_a = 0 (no threshold test, no table of inefficient points, no selection list), by
+//
+//   * k_frontier_babsr_decide        one workgroup, ONE thread walking the K rows in order with the counter *icp;
+//   * k_frontier_babsr_decide_jobs   one workgroup per plan entry: the walk on the entry's rows with icp[segment].
+
+__global__ __launch_bounds__(64) void k_frontier_babsr_decide(FrFallbackArgs a) {
+  const FrFbView v{0, a.K, 0, a.icp, nullptr, nullptr};
+  fr_fallback_walk(a, v);
+}
+
+__global__ __launch_bounds__(64) void k_frontier_babsr_decide_jobs(FrFallbackArgs a, FrPlan j) {
+  int seg, row0, k;
+  if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
+  const FrFbView v{row0, k, row0, a.icp + seg, nullptr, nullptr};
+  fr_fallback_walk(a, v);
 }
 
 // ---- the learn rows of an online round ----------------------------------------------------------------------

@@ -1115,6 +1115,42 @@ class ScorerEngine:
                    self._rows(sel_slots, K, 1, i32, "sel_slots").data_ptr(), self._rows(sel_decisions, K, 2, i32, "sel_decisions").data_ptr(),
                    self._rows(m, 1, 1, i32, "m").data_ptr(), ws.data_ptr(), ws.numel())
 
+    def _babsr_rule(self, n, S, scores, intercepts, scorer_mask, icp, decisions, sparsest_layer, decision_threshold, random_order):
+        """The arguments ``gnnb_frontier_babsr_decide`` and its jobs form share, for n parent rows and S counters, and what must outlive
+        the call."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        from .lp_producer import _random_order
+        R, i32, f32 = self.R, torch.int32, torch.float32
+        order = list(_random_order(len(self.sizes) - 2, sparsest_layer) if random_order is None else random_order)
+        order_c = (C.c_int32 * max(1, len(order)))(*order)
+        args = (self._rows(scores, n, R, f32, "scores").data_ptr(), self._rows(intercepts, n, R, f32, "intercepts").data_ptr(),
+                self._rows(scorer_mask, n, R, f32, "scorer_mask").data_ptr(), float(decision_threshold), int(sparsest_layer), order_c, len(order),
+                self._rows(icp, S, 1, i32, "icp").data_ptr(), self._rows(decisions, n, 2, i32, "decisions").data_ptr())
+        return args, order_c
+
+    def frontier_babsr_decide(self, scores, intercepts, scorer_mask, icp, decisions, K=None, sparsest_layer=0, decision_threshold=0.001,
+                              random_order=None, workspace=None):
+        """gnnb_frontier_babsr_decide on the current stream: the BaBSR decision (``kw_score_conv.decide``) of
+        each of the first K rows (None: every row of ``decisions``) of scores / intercepts (``babsr_rows``) and scorer_mask
+        (``frontier_gather``), all (K, R) fp32, into decisions (K, 2) int32 ([-1, -1]: a NaN row, a row without an undecided node);
+        icp (1,) int32, the run's intercept counter, is read and updated in row order.  random_order: the ReLU layers popped from the
+        end (None: ``lp_producer._random_order``).  Nothing is copied."""
+        K = int(decisions.numel()) // 2 if K is None else int(K)
+        args, keep = self._babsr_rule(max(K, 0), 1, scores, intercepts, scorer_mask, icp, decisions, sparsest_layer, decision_threshold, random_order)
+        ws = self._workspace("babsr_decide", K, "gnnb_frontier_babsr_decide_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_frontier_babsr_decide", K, *args, ws.data_ptr(), ws.numel())
+
+    def frontier_babsr_decide_jobs(self, plan, scores, intercepts, scorer_mask, icp, decisions, sparsest_layer=0, decision_threshold=0.001,
+                                   random_order=None, workspace=None):
+        """gnnb_frontier_babsr_decide_jobs on the current stream: ``frontier_babsr_decide`` per plan entry on its rows of the (n, R) /
+        (n, 2) tensors with its segment's counter icp[segment] ((segments,) int32).  A segment without an entry and rows from n on are
+        not touched."""
+        pl, n, S = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0)
+        args, keep = self._babsr_rule(n, S, scores, intercepts, scorer_mask, icp, decisions, sparsest_layer, decision_threshold, random_order)
+        ws = self._workspace("babsr_decide", max(n, 1), "gnnb_frontier_babsr_decide_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_frontier_babsr_decide_jobs", C.byref(pl), *args, ws.data_ptr(), ws.numel())
+
     def _children(self, ch, n, what=None):
         """The gnnb_children of a set of child rows (any object with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live) and what must
         outlive the call.  what: the rows' name in a message (None: loose tensors, named as ``frontier_commit`` takes them)."""

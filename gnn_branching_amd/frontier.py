@@ -17,6 +17,10 @@ its segment a job runs the rule above unchanged, so it gets the result ``branch_
 ``branch_and_bound_frontier(..., branching_threshold=T, online_threshold=N)`` is the reference's online loop
 (``lp_producer.branch_and_bound_online``) on the same round: a parent whose KW pair won counts its GNN decision as a wrong point, from the
 N-th time on it is a learn row, and behind the commit the round takes one Adam step over its learn rows on the device.
+
+``branch_and_bound_frontier(..., branching="babsr")`` and ``verify_properties_babsr`` are the reference's
+``relu_bab`` on the same round: every parent is split at the BaBSR heuristic's decision (``gnnb_babsr``, ``gnnb_frontier_babsr_decide``), one
+intercept counter carried through the run (per job), and the GNN is never run.
 """
 import ctypes as C
 import math
@@ -177,6 +181,18 @@ def _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         raise TypeError(f"online_threshold needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
 
 
+BRANCHINGS = ("gnn", "babsr")
+
+
+def _check_branching(branching, branching_threshold, online_threshold):
+    """The branching mode, before a device is touched."""
+    if not isinstance(branching, str) or branching not in BRANCHINGS:
+        raise ValueError(f"branching = {branching!r}: one of {BRANCHINGS}")
+    if branching == "babsr" and (branching_threshold is not None or online_threshold is not None):
+        raise ValueError('branching="babsr" branches on the BaBSR heuristic alone (relu_bab): it takes no branching_threshold and no online_threshold, '
+                         "which compare the heuristic with the GNN")
+
+
 PGD_STEP_DEFAULT = 1.0 / 64
 
 
@@ -209,6 +225,7 @@ class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
     witness_on, pgd_steps, pgd_step = False, None, PGD_STEP_DEFAULT
     restarts, pgd_seed = 0, 0
+    branching = "gnn"
 
     def _restart_options(self, pgd_restarts, pgd_seed):
         """The options of DESIGN.md section 7.9, checked, behind ``_upper_bound_options``; ``restarts`` 0: off, and nothing of a round differs."""
@@ -237,7 +254,8 @@ class _Round:
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
         self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws_fwd, self.ws_kw = ws("gnnb_workspace_bytes", n_parents), ws("gnnb_kw_workspace_bytes", n_children)
+        self.ws_fwd = ws("gnnb_workspace_bytes", n_parents) if self.branching == "gnn" else None     # (a BaBSR round runs no gnnb_forward)
+        self.ws_kw = ws("gnnb_kw_workspace_bytes", n_children)
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
         if self.pgd_steps is not None:
@@ -276,6 +294,16 @@ class _Round:
         self.kw_dec, self.sel_dec, self.dec = (torch.zeros(n, 2, dtype=i32, device=dev) for _ in range(3))
         self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(n, dtype=i32, device=dev) for _ in range(3))
         self.ws_fallback = self._ws(ws_sizer, n)
+
+    def _babsr_buffers(self, n_parents, counters, sparsest_layer, decision_threshold):
+        """The state of ``branching="babsr"`` for rounds of up to n_parents parents.  counters: the shape of the
+        intercept counters ``icp`` (one per run, or one per segment)."""
+        dev, R, f32 = self.eng.device, self.eng.R, torch.float32
+        self.sparsest_layer, self.decision_threshold = int(sparsest_layer), float(decision_threshold)
+        self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
+        self.icp = torch.zeros(counters, dtype=torch.int32, device=dev)
+        self.kw_scores, self.kw_icp = torch.zeros(n_parents, R, dtype=f32, device=dev), torch.zeros(n_parents, R, dtype=f32, device=dev)
+        self.ws_babsr = self._ws("gnnb_frontier_babsr_decide_workspace_bytes", n_parents)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -324,11 +352,23 @@ class _Round:
                                         self.ws_fwd.numel(), self._stream()), "gnnb_forward")
         self.status_all |= self.status
 
+    def _babsr_parents(self, n):
+        """``branching="babsr"`` in ``_score_parents``' place: gnnb_babsr on the n parent rows the gather wrote and
+        the BaBSR decision of every row (``_decide``) into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward."""
+        P = self.P
+        self.eng.babsr_rows(P.lb32, P.ub32, P.box[2], P.amb, n, self.kw_scores, self.kw_icp)
+        self._decide(n)
+
     def _launch(self, slots, n):
         """The launches of a round over the n parents in ``slots`` (their boxes: the parent rows' own), from the gather to the commit."""
         P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
         eng.frontier_gather(pool, slots, P.box[0], P.box[1], P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
-        self._score_parents(n)
+        if self.branching == "gnn":
+            self._score_parents(n)
+        else:
+            self._babsr_parents(n)
+            if self.keep_pairs:                                   # (a traced run: "parent_bounds", which gnnb_dual_ascent at n_iter 0 would have left)
+                P.bound[:n] = pool.bound[slots[:n].long().clamp(min=0)]
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(Ch, 2 * n, warm=True)
         if self.threshold is not None:
@@ -375,8 +415,10 @@ class FrontierRun(_Round):
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
                  kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
-                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, branching="gnn"):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
+        _check_branching(branching, branching_threshold, online_threshold)
+        self.branching = branching
         self._upper_bound_options(witness, pgd_steps, pgd_step)
         self._restart_options(pgd_restarts, pgd_seed)
         _check_threshold(branching_threshold, kwbd_threshold)
@@ -404,6 +446,8 @@ class FrontierRun(_Round):
         if branching_threshold is not None:
             self._threshold_buffers(K, ((1,), (eng.R,)), None, "gnnb_frontier_fallback_workspace_bytes", kwbd_threshold, sparsest_layer, decision_threshold)
             self.m_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        if branching == "babsr":                                  # one intercept counter per run, zero at its start (relu_conv_any_kw.py:100)
+            self._babsr_buffers(K, (1,), sparsest_layer, decision_threshold)
         self.online, self.k, self.learn_pending, self.last_learn = online_threshold, 0, False, 0
         self.online_steps = self.online_rows = 0
         if online_threshold is not None:
@@ -450,6 +494,10 @@ class FrontierRun(_Round):
         self.eng.frontier_fallback(self.pool, self.slots, Ch.live, Ch.infeasible, Ch.bound, self.kw_scores, self.kw_icp, self.P.amb, self.icp, self.ineff,
                                    self.gnn_imp, self.kw_dec, self.sel_rows, self.sel_slots, self.sel_dec, self.m_dev, self.threshold, self.kwbd_threshold,
                                    self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+
+    def _decide(self, k):
+        self.eng.frontier_babsr_decide(self.kw_scores, self.kw_icp, self.P.amb, self.icp, self.P.dec, k, self.sparsest_layer, self.decision_threshold,
+                                       self.random_order, workspace=self.ws_babsr)
 
     def _read_selected(self):
         m = self.m = self.M = self.read_selected()
@@ -513,7 +561,8 @@ class FrontierRun(_Round):
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
-                              online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
+                              online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0,
+                              branching="gnn"):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -566,9 +615,18 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     the seed of every launch: a row's points depend on its own LP point, box and the seed only, so a run repeats itself and a job in a pool
     gets what it gets alone.
 
+    branching (with "gnn", the default, no launch, read or argument of a round changes).  "babsr": the reference's
+    relu_bab (plnn/relu_conv_any_kw.py:45-181 with split_decision='kw'): every parent is split at the BaBSR heuristic's decision
+    (``gnnb_babsr`` on the parent rows, then ``gnnb_frontier_babsr_decide``: ``kw_score_conv.decide`` with ``sparsest_layer`` and
+    ``decision_threshold``, the layer order ``lp_producer._random_order``), one intercept counter starting at 0 and carried through the
+    rows of a round and from round to round.  The round runs no ``gnnb_dual_ascent`` at n_iter 0 on the parents and no ``gnnb_forward``:
+    ``choice`` supplies the engine, its GNN is never run.  Bounding, the witness, PGD, the restarts and the commit are unchanged.  A parent
+    whose scores hold a NaN, or that has no undecided node, gets no decision and is closed at its own bound (the host rule would raise).  It
+    takes no ``branching_threshold`` and no ``online_threshold``.  A traced round's "decisions" are BaBSR's.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed)      # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, branching)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
@@ -773,8 +831,10 @@ class JobsRun(_Round):
 
     def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
                  sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
-                 pgd_seed=0):
+                 pgd_seed=0, branching="gnn"):
         _check_threshold(branching_threshold, kwbd_threshold)
+        _check_branching(branching, branching_threshold, None)
+        self.branching = branching
         self._upper_bound_options(witness, pgd_steps, pgd_step)
         self._restart_options(pgd_restarts, pgd_seed)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
@@ -822,6 +882,8 @@ class JobsRun(_Round):
                                     kwbd_threshold, sparsest_layer, decision_threshold)
             self.m_entry = torch.zeros(S + 1, dtype=i32, device=dev)
             self.job_used = torch.zeros(len(jobs), dtype=torch.int64, device=dev)    # KW pairs taken per job, once it has left
+        if branching == "babsr":                                  # per segment: the intercept counter of its job (section 7.10)
+            self._babsr_buffers(n, (S,), sparsest_layer, decision_threshold)
 
     def release(self, seg):
         """The job of segment ``seg`` leaves: no open slot, the start record."""
@@ -841,6 +903,8 @@ class JobsRun(_Round):
             self.icp[seg].zero_()
             self.ineff[seg].zero_()
             self.n_used[seg].zero_()
+        if self.branching == "babsr":                             # the job starts with its own counter: zero, device-side
+            self.icp[seg].zero_()
 
     def keep_used(self, seg, job):
         """The job of segment ``seg`` leaves: its count of KW pairs taken, device to device (read once, when the run ends)."""
@@ -904,6 +968,10 @@ class JobsRun(_Round):
                                         self.ineff, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, self.gnn_imp, self.kw_dec, self.sel_rows,
                                         self.sel_slots, self.sel_dec, self.m_entry, self.bx_lo, self.bx_hi, self.bpw, self.bpb, self.threshold,
                                         self.kwbd_threshold, self.sparsest_layer, self.decision_threshold, self.random_order, workspace=self.ws_fallback)
+
+    def _decide(self, n):
+        self.eng.frontier_babsr_decide_jobs(self.plan, self.kw_scores, self.kw_icp, self.P.amb, self.icp, self.P.dec, self.sparsest_layer,
+                                            self.decision_threshold, self.random_order, workspace=self.ws_babsr)
 
     def _read_selected(self):
         self.m_e = self.read_selected()
@@ -999,12 +1067,32 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats, upper, restarts)
 
 
+def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, sparsest_layer=0,
+                            decision_threshold=0.001, log=print, trace=None, stats=None):
+    """``verify_properties`` with every job branching on the BaBSR heuristic alone: every job gets the result
+    ``branch_and_bound_frontier(..., branching="babsr", capacity=capacity, sparsest_layer=..., decision_threshold=...)`` gives it alone, bit
+    for bit, whatever else is in flight, whichever segment it got and whenever it was admitted.
+
+    Every job has its own intercept counter, zero when it is admitted, read and updated in the job's parent row order within a round and
+    carried from round to round.  ``choice`` supplies the engine; its GNN is never run.  stats: None, or a list that receives per job, in
+    job order, a dict of "branches" (parents expanded) and "domains_bounded".  trace: ``verify_properties``' keys per round and per entry;
+    "decisions" are BaBSR's.  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
+
+    Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
+    babsr = {"branching": "babsr", "sparsest_layer": sparsest_layer, "decision_threshold": decision_threshold}
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, None, stats, upper, restarts, babsr)
+
+
 def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None,
-                 restarts=None):
-    """The loop of ``verify_properties`` and ``verify_properties_threshold`` on checked arguments.  threshold: None, or the threshold mode's
-    arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists.  upper: None, or the witness and descent
-    options of section 7.8; restarts: None, or the restart options of section 7.9."""
-    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}), **(restarts or {}))
+                 restarts=None, babsr=None):
+    """The loop of ``verify_properties``, ``verify_properties_threshold`` and ``verify_properties_babsr`` on checked arguments.  threshold:
+    None, or the threshold mode's arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists.  upper:
+    None, or the witness and descent options of section 7.8; restarts: None, or the restart options of section 7.9; babsr: None, or the
+    arguments of ``JobsRun`` that make every job branch on BaBSR alone (section 7.10)."""
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}), **(restarts or {}),
+                  **(babsr or {}))
     witness = (upper or {}).get("witness")
     run.keep_pairs = trace is not None
     F, thr = _lib, threshold is not None
@@ -1075,6 +1163,8 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
             bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
             if thr:                                               # the children of both pairs
                 bounded[j], branches[j], kw_bounded[j] = bounded[j] + 2 * run.m_e[e], branches[j] + k, kw_bounded[j] + run.m_e[e]
+            elif babsr is not None:
+                branches[j] += k
             log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
                 f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
     run.check_status()
@@ -1085,4 +1175,6 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
         used = run.job_used.cpu().tolist()
         stats.extend({"branches": branches[j], "kw_bounded": kw_bounded[j], "domains_bounded": results[j][3], "kw_used": int(used[j])}
                      for j in range(len(jobs)))
+    if babsr is not None and stats is not None:
+        stats.extend({"branches": branches[j], "domains_bounded": results[j][3]} for j in range(len(jobs)))
     return results

@@ -514,6 +514,36 @@ int gnnb_frontier_choose_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan*
                               const double* gnn_improvement, const gnnb_children_rw* pair_a, const gnnb_children* pair_b, int32_t* ineff,
                               double* kw_improvement, int32_t* used_kw, int32_t* decisions, void* stream);
 
+/* ---- BaBSR alone: the decision of every parent row (gnn_branching_amd/frontier.py branching="babsr") ----
+ * The branching of reference plnn/relu_conv_any_kw.py:45-181 with split_decision = 'kw' (relu_bab): every parent of a round gets the
+ * decision of plnn/kw_score_conv.py:115-156 and one intercept counter is carried through the run (:100, :113).  scores / intercepts /
+ * scorer_mask: device (K, R) fp32 as gnnb_babsr and gnnb_frontier_gather write them.  The rows are walked in order by one thread with the
+ * counter *icp carried from row to row, and row i gets exactly what gnnb_frontier_fallback gives a row below its branching threshold:
+ * the score decision if its layer is not sparsest_layer and its value, promoted to double, exceeds decision_threshold; otherwise the
+ * intercept decision if some layer's minimum is below -1e-4 and the counter is below 2 (the LAST such layer; the counter becomes 0 unless
+ * that layer is 0, then it is incremented); otherwise the first undecided node of the first layer, popping random_order (HOST, n_order
+ * entries in 0..8) from its end, that has one (the counter becomes 0).  A row with a NaN in its scores or intercepts, a row without an
+ * undecided node and a row for which random_order names no usable layer get [-1, -1] and leave the counter alone (gnnb_frontier_expand
+ * makes two dead children of them and the commit closes the parent at its own bound; the host rule would raise).  There is no pair A, no
+ * improvement, no table of inefficient points and no selection list.  The rule's text is the fall-back's: the same kernel reduces every
+ * layer (k_frontier_candidates) and the same walk takes the three-way decision.  decisions: device (K, 2) int32; icp: device (1) int32,
+ * read and updated; workspace: gnnb_frontier_babsr_decide_workspace_bytes (0 for a null or unbound handle).
+ * Stream-ordered, no allocation, no synchronisation, no atomics, no workgroup waits on another; every arg-max / arg-min is the fixed tree
+ * on the total order (value, index).  GNNB_E_INVALID before any launch for a null handle or argument, K outside 1..32767, n_order outside
+ * 0..8, a NaN decision_threshold; GNNB_E_STATE before gnnb_bind_network; GNNB_E_NOMEM for a short workspace. */
+size_t gnnb_frontier_babsr_decide_workspace_bytes(const gnnb_t* h, int K);
+int gnnb_frontier_babsr_decide(gnnb_t* h, int K, const float* scores, const float* intercepts, const float* scorer_mask,
+                               double decision_threshold, int sparsest_layer, const int32_t* random_order, int n_order, int32_t* icp,
+                               int32_t* decisions, void* workspace, size_t workspace_bytes, void* stream);
+
+/* gnnb_frontier_babsr_decide per plan entry {segment, row0, k} on the rows [row0, row0 + k) of the n-row arrays with the counter
+ * icp[segment] (icp: device (segments); the caller zeroes it when a job takes the segment).  Nothing mixes two entries, a segment without
+ * an entry is not touched, rows from n on are not written.  Also refused: everything the plan checks of section 7.4 refuse.  workspace:
+ * gnnb_frontier_babsr_decide_workspace_bytes(h, n). */
+int gnnb_frontier_babsr_decide_jobs(gnnb_t* h, const gnnb_plan* plan, const float* scores, const float* intercepts, const float* scorer_mask,
+                                    double decision_threshold, int sparsest_layer, const int32_t* random_order, int n_order, int32_t* icp,
+                                    int32_t* decisions, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- learning online inside the frontier (reference plnn/relu_conv_online.py:183-207) ----
  * The selection of the rows an online round learns from, after gnnb_frontier_choose: wrong (device (R) int32, zero at the start of a run)
  * is the reference's wrong_pts_dc, keyed by the flat ReLU index (the layer's offset + idx, graph_score_online.py:63-68) of the GNN's
