@@ -390,6 +390,7 @@ extern "C" int gnnb_create(gnnb_t** out, const float* w_blob, size_t n_floats, i
       {k_gather_update_q<16, 0, false>, k160}, {k_gather_update_q<16, 1, false>, k160}, {k_gather_update_q<16, 2, false>, k160},
       {k_gather_update_q<16, 0, false, true>, k160}, {k_gather_update_q<16, 2, false, true>, k160},
       {k_gather_update_q<32, 1, false>, k160}, {k_gather_update_q<32, 1, true>, k160},
+      {k_gather_update_q<16, 3, false>, k160}, {k_gather_update_q<32, 3, false>, k160}, {k_gather_update_q<32, 3, true>, k160},
       {k_classify_pre, CLSPRE_LDS_BYTES}, {k_scored_tail, k160 - 256},      // (k_scored_tail also has a few static words)
       {k_top<4>, TOP_LDS_FLOATS * 4}, {k_top<2>, TOP_LDS_FLOATS * 4}, {k_top<1>, TOP_LDS_FLOATS * 4}, {k_babsr, BABSR_LDS_MAX},
   };
@@ -716,6 +717,8 @@ extern "C" int gnnb_describe(const gnnb_t* h, char* buf, size_t cap) {
 struct WsLayout {                // plain arrays: gnnb_forward computes it on its stack (no allocation in the call)
   size_t mu[MAXL + 2], Pf[MAXL + 2], Pb[MAXL + 2], live[MAXL + 2], amb[MAXL + 2], score[MAXL + 2];
   size_t lf[MAXL + 2];          // live flags (B, N_k) as floats
+  size_t lbits[MAXL + 2];       // the same flags one bit per node (k_classify's ballots), read as 32-bit words by the sparse gathers (BitsLive); inside Q
+  bool bits = false;            // the bitmaps have a place (else k_classify writes none and every sparse table build reads the bounds)
   size_t sf[MAXL + 2], sb[MAXL + 2];   // k_livesum outputs: sf[k] (B, N_k) over edge k, sb[k] (B, N_k) over edge k+1 transposed
   size_t F1 = 0;                // rows of layer 1 after the producer-side map of the input update (PackPostInp)
   size_t cnt = 0, best = 0, nb = 0, Q = 0, total = 0;     // best: B 64-bit decision keys + the finished-workgroup counter of k_score
@@ -724,7 +727,7 @@ struct WsLayout {                // plain arrays: gnnb_forward computes it on it
 static size_t align64(size_t nfloats) { return (nfloats + 63) & ~(size_t)63; }
 static WsLayout ws_layout(const gnnb_t* h, int B) {
   WsLayout w;
-  for (int k = 0; k < MAXL + 2; ++k) w.mu[k] = w.Pf[k] = w.Pb[k] = w.live[k] = w.amb[k] = w.score[k] = w.lf[k] = w.sf[k] = w.sb[k] = 0;
+  for (int k = 0; k < MAXL + 2; ++k) w.mu[k] = w.Pf[k] = w.Pb[k] = w.live[k] = w.amb[k] = w.score[k] = w.lf[k] = w.lbits[k] = w.sf[k] = w.sb[k] = 0;
   const int K = (int)h->N.size() - 1;
   size_t off = 0;
   w.cnt = off; off += 64;                      // (unused: the list counters live in the handle's control blocks)
@@ -748,6 +751,15 @@ static WsLayout ws_layout(const gnnb_t* h, int B) {
   w.F1 = off; off += align64((size_t)B * h->N[1] * 64);
   w.Q = off; off += (size_t)map_tiles(bwd_map(h, 0), B) * 2048;
   w.total = off;
+  // The live bitmaps take the front of Q, which only the unfused input update writes and reads (k_pre_inp, k_input_update: no transposed
+  // gather tables on edge 1), so the workspace keeps its size.  Per ReLU layer: ceil(B N_k / 64) 64-bit words, then LIVEBITS_PAD 32-bit
+  // words nobody writes -- a gather wave reads the 64 words from its sample's first one on without a guard (the words behind the sample's
+  // last node are never selected).
+  if (K >= 2 && h->gb[1].ok) {
+    size_t o = w.Q;
+    for (int k = 1; k < K; ++k) { w.lbits[k] = o; o += align64(2 * (((size_t)B * h->N[k] + 63) / 64) + LIVEBITS_PAD); }
+    w.bits = o <= w.total;
+  }
   return w;
 }
 
@@ -957,6 +969,7 @@ struct Forward {
       a.lb[i] = in->lb[k]; a.ub[i] = in->ub[k]; a.mu[i] = mu(k); a.zero[i] = zero_dead_rows(k) ? 1 : 0;
       a.live[i] = ilist(w.live[k]); a.amb[i] = ilist(w.amb[k]); a.score[i] = ilist(w.score[k]);
       a.livef[i] = ws + w.lf[k];
+      a.lbits[i] = w.bits ? reinterpret_cast<unsigned long long*>(ws + w.lbits[k]) : nullptr;
       a.G[i] = (long)B * h->N[k]; a.N[i] = h->N[k]; a.off[i] = roff[k];
       a.blk0[i] = blk;
       blk += (int)((a.G[i] + CLS_BLOCK - 1) / CLS_BLOCK);
@@ -1046,7 +1059,8 @@ struct Forward {
   GArgs gather_args(const DevGather& d, int k, const float* src, bool scored, bool sparse, int src_layer, float* sout) const {
     return GArgs{in->lb[k], in->ub[k], in->mask, src, nb, map_tiles(d.g.tm, B), scored ? 1 : 0, h->R, roff[k], to_dtm(d.g.tm), to_dg(d, h->d_zero.get()),
                  EmbedSrc{in->lb[0], in->x_lp, in->ub[0], h->d_pack[PK_EMBED]}, sparse ? in->lb[src_layer] : nullptr,
-                 sparse ? in->ub[src_layer] : nullptr, sparse ? sout : nullptr};
+                 sparse ? in->ub[src_layer] : nullptr, sparse && w.bits ? reinterpret_cast<const unsigned*>(ws + w.lbits[src_layer]) : nullptr,
+                 sparse ? sout : nullptr};
   }
   void gather(const DevGather& d, int k, const float* src, bool scored, bool embed, int src_layer, float* sout) {   // MFMA
     const bool sparse = !embed && src_layer >= 1;
@@ -1176,10 +1190,13 @@ struct Forward {
     const bool block = !sparse && (d.g.block & (embed ? 2 : 1));
     a.npairs = block ? (long)B * pairs_per_sample(d.g.tm) : 0;      // the block-form kernels deal row pairs, not tiles, to their gather waves
     const long nrounds = ((block ? a.npairs : a.g.ntiles) + QG_WAVES - 1) / QG_WAVES;
+    // a sparse table build reads the source layer's live bitmap where a sample's bits fit one register per lane (BitsLive), else its bounds
+    const bool bits = sparse && w.bits && livebits_ok(d.g.Ns) && d.g.Ns == h->N[src_layer];
     void (*kern)(FArgs) = d.g.lanes == 16 ? (embed ? (block ? k_gather_update_q<16, 2, false, true> : k_gather_update_q<16, 2, false>)
-                                                    : sparse ? k_gather_update_q<16, 1, false>
+                                                    : sparse ? (bits ? k_gather_update_q<16, 3, false> : k_gather_update_q<16, 1, false>)
                                                     : (block ? k_gather_update_q<16, 0, false, true> : k_gather_update_q<16, 0, false>))
-                                          : (post_input ? k_gather_update_q<32, 1, true> : k_gather_update_q<32, 1, false>);
+                                          : (post_input ? (bits ? k_gather_update_q<32, 3, true> : k_gather_update_q<32, 1, true>)
+                                                        : (bits ? k_gather_update_q<32, 3, false> : k_gather_update_q<32, 1, false>));
     const dim3 g((unsigned)std::max<long>(1, std::min<long>(nrounds, h->n_cu))), b((QG_WAVES + QC_WAVES) * 64);
     lz.run(PC_GATHER_UPDATE, [&] { hipLaunchKernelGGL(kern, g, b, ldsq, st, a); });
     proj[k] = fwd ? L_FC4_2 : L_BC4_1;

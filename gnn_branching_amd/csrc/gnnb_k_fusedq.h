@@ -347,13 +347,14 @@ __device__ unsigned long long g_qt_wall[2 * 16 * 1024];
 #define QT_FLUSH()
 #endif
 // LANES: dst nodes per gather tile (16: forward edges, 32: transposed edges).  SRC: 0 dense source rows, 1 sparse walk (the source
-// is a ReLU layer), 2 round-0 embedding computed in the gather (16-node tiles only).  POST: see UpdArgs.
+// is a ReLU layer), 2 round-0 embedding computed in the gather (16-node tiles only), 3 the sparse walk with its table built from the source
+// layer's live bitmap (BitsLive; bound where livebits_ok(Ns)) instead of its bounds.  POST: see UpdArgs.
 // fusedq_body: one half-pass by this workgroup (all 16 waves call it; it starts with workgroup barriers; k_scored_tail shares q_chain).  Returns false when a wait hit its
 // iteration cap (status bit 1 is raised; the caller must leave the kernel), true when this wave's part of the half-pass is done.
 template <int LANES, int SRC, bool POST, bool BLOCK = false>
 __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
-  static_assert(!BLOCK || (LANES == 16 && SRC != 1), "block form: 16-node tiles over dense or embedded source rows");
-  constexpr bool SPARSE = SRC == 1, EMBED = SRC == 2;
+  static_assert(!BLOCK || (LANES == 16 && SRC != 1 && SRC != 3), "block form: 16-node tiles over dense or embedded source rows");
+  constexpr bool SPARSE = SRC == 1 || SRC == 3, EMBED = SRC == 2, BITS = SRC == 3;
   QT_DECL;
   float* qbase = lds + PackUpdL3::FLOATS + (POST ? 6144 : 0);
   const int NQ = a.qtiles;
@@ -484,8 +485,9 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
   const long r0 = wg, rstep = nwg;
   bool stuck = false;
   // The bounds of a tile's dst nodes are fetched one tile ahead (they decide which lanes are live: the tile cannot start without
-  // them, and a gather wave spent 14 % of its time waiting for them).
-  struct Next { TileCtx tc; int sample, gc; bool in; float lb, ub; } nx;
+  // them, and a gather wave spent 14 % of its time waiting for them).  BITS: so is this lane's word of the source sample's live bitmap, which
+  // the table build then reads with a permute: no memory round trip between the window decode and the walk.
+  struct Next { TileCtx tc; int sample, gc; bool in; float lb, ub; unsigned lbits; } nx;
   auto fetch = [&](long r) {
     const long tile = r * QG_WAVES + wave;
     nx.in = r < nrounds && tile < ntl;
@@ -497,6 +499,7 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
     nx.gc = (int)(nx.tc.sample * a.g.tm.N + nx.tc.n);
     nx.lb = a.g.lb[nx.gc];
     nx.ub = a.g.ub[nx.gc];
+    nx.lbits = BITS ? livebits_load(a.g.src_bits, si, a.g.g.Ns, lane) : 0u;
   };
   fetch(r0);
   for (long r = r0; r < nrounds && !stuck; r += rstep) {
@@ -504,6 +507,7 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
     const TileCtx tc = nx.tc;
     const int sample = nx.sample, gc = nx.gc;
     const float lb = nx.lb, ub = nx.ub;
+    const unsigned lbits = nx.lbits;
     fetch(r + rstep);
     const bool need = tc.valid && node_is_live(lb, ub);
     QT_MARK(1);                                     // tile decode, its bounds (requested one tile ahead)
@@ -512,8 +516,8 @@ __device__ __forceinline__ bool fusedq_body(const FArgs& a, float* lds) {
     float ssum = 0.0f;
     Frag X;
     f32x4 acc[4];
-    if (LANES == 32) gather_compute_tile<false, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, el, lane, X, ssum);
-    else gather_compute_tile16<EMBED, SPARSE>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum);
+    if (LANES == 32) gather_compute_tile<false, SPARSE, BITS>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, el, lane, X, ssum, lbits);
+    else gather_compute_tile16<EMBED, SPARSE, false, BITS>(a.g, tc, sample, gl.cm, gl.ko, gl.kvo, tab, ew, eb, lane, acc, ssum, lbits);
     if (!a.sw_from_gather) ssum = __int_as_float(a.u.smod > 0 ? tc.n : gc);      // (q_chain: the index of the node's entry in u.sarr)
 
     QT_MARK(2);                                     // table build + walk

@@ -99,14 +99,37 @@ __device__ __forceinline__ void gather_tile(Frag& X, const float* cm, const int2
 
 __device__ __forceinline__ bool node_is_live(float lb, float ub);
 
+// Where a sparse table build takes "source node `row` of this sample is live" from (a compile-time choice of the kernel):
+//   BoundsLive: the node's bounds, two dependent global loads per window slot in front of the walk;
+//   BitsLive:   k_classify's bitmap of the layer (bit g of the flat node index g = sample Ns + row, the same predicate op for op).  Lane l holds
+//               32-bit word w0 + l, w0 = (sample Ns) >> 5, requested a tile ahead; the build fetches a row's word with one cross-lane permute.
+//               The host binds it only where a sample's bits fit the 64 words (livebits_ok): no memory access between the window decode and the table.
+struct BoundsLive {
+  const float *slb, *sub;
+  __device__ __forceinline__ bool operator()(int row) const { return node_is_live(slb[row], sub[row]); }
+};
+struct BitsLive {
+  unsigned reg; int bit0;          // bit0 = (sample Ns) & 31: the sample's first bit in word w0
+  __device__ __forceinline__ bool operator()(int row) const {      // called by every lane of the wave (a permute)
+    const int bit = bit0 + row;
+    const unsigned word = (unsigned)__shfl((int)reg, (bit >> 5) & 63);
+    return (word >> (bit & 31)) & 1u;
+  }
+};
+#define LIVEBITS_PAD 64            // 32-bit words behind a layer's bitmap, so that a wave's 64-word read from any sample's w0 stays inside the region
+__host__ __device__ inline bool livebits_ok(int Ns) { return (Ns % 32 == 0 ? Ns : Ns + 31) <= 2048; }
+__device__ __forceinline__ unsigned livebits_load(const unsigned* bits, int sample, int Ns, int lane) { return bits[(((long)sample * Ns) >> 5) + lane]; }
+__device__ __forceinline__ int livebits_bit0(int sample, int Ns) { return (int)(((long)sample * Ns) & 31); }
+
 // Sparse variant (source = a ReLU layer): the rows of its dead nodes are exactly zero, so the tile first compacts the live,
 // in-range slots of its window into a per-wave LDS table {byte offset of the row, tap-matrix row} and walks only those.
-// `tab`: 2*K2 + 32 entries of this wave; slb / sub: bounds of the source layer of this sample.
+// `tab`: 2*K2 + 32 entries of this wave; srclive: liveness of the source layer's nodes of this sample (BoundsLive / BitsLive).
 #ifndef GATHER_CHS
 #define GATHER_CHS 4    // k-steps per prefetch chunk of the sparse walk (8 live slots: 3 % faster than 16)
 #endif
+template <class LS>
 __device__ __forceinline__ void gather_tile_sparse(Frag& X, const float* cm, const int2* ko, uint2* tab, int K2, __amdgpu_buffer_rsrc_t rsrc,
-                                                   const float* slb, const float* sub, int j, int wy0, int wx0, int Hs, int Ws, int lane,
+                                                   const LS& srclive, int j, int wy0, int wx0, int Hs, int Ws, int lane,
                                                    bool keep = false, float* ssum = nullptr) {
   // ssum: also return s[dst node j] = sum of the tap weights of the live window slots = sum_n A[n', n] live_n, the scalar the
   // bias of the source rows' deferred projection is multiplied with (gnnb_pack.h; otherwise computed by k_livesum)
@@ -125,7 +148,12 @@ __device__ __forceinline__ void gather_tile_sparse(Frag& X, const float* cm, con
     const int wy = wy0 + (ey & 0xffff), wx = wx0 + (ey >> 16);
     const bool inb = sl < 2 * K2 && (unsigned)wy < (unsigned)Hs && (unsigned)wx < (unsigned)Ws;      // (table padding: 0x7fff, never in range)
     const int row = inb ? origin + ex : 0;
-    const bool live = inb && node_is_live(slb[row], sub[row]);
+#ifdef LIVE_ABL            // dev, timing only (wrong results): a memory-free predicate of the same density (~54 % live) -- the table build without its round trip
+    const bool live = inb && (unsigned)row * 2654435761u < 0x8a3d70a3u;
+#else
+    const bool lrow = srclive(row);          // (every lane asks: BitsLive permutes)
+    const bool live = inb && lrow;
+#endif
     const unsigned long long bal = __ballot(live);
     if (live) tab[n + __popcll(bal & ((1ull << lane) - 1ull))] = make_uint2((unsigned)row * 256u, (unsigned)sl * 32u);
     n += __popcll(bal);
@@ -184,14 +212,15 @@ __device__ __forceinline__ void gather_tile_sparse(Frag& X, const float* cm, con
 
 
 // `sbase` = first row of this sample's source layer; must be built from wave-uniform values
-// tab != nullptr: sparse walk (slb / sub = bounds of the source layer of this sample)
+// tab != nullptr: sparse walk (srclive = liveness of the source layer's nodes of this sample)
+template <class LS = BoundsLive>
 __device__ __forceinline__ void gather_dispatch(Frag& X, const float* cm, const int2* ko, const unsigned* kvo, const DGather& g,
                                                 const float* sbase, int j, int wy0, int wx0, int lane,
-                                                uint2* tab = nullptr, const float* slb = nullptr, const float* sub = nullptr, bool keep = false,
+                                                uint2* tab = nullptr, const LS& srclive = LS{}, bool keep = false,
                                                 float* ssum = nullptr) {
   const int uy = __builtin_amdgcn_readfirstlane(wy0), ux = __builtin_amdgcn_readfirstlane(wx0);
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, g.Ns * 256, 0x00020000);
-  if (tab) { gather_tile_sparse(X, cm, ko, tab, g.K2, rsrc, slb, sub, j, uy, ux, g.Hs, g.Ws, lane, keep, ssum); return; }
+  if (tab) { gather_tile_sparse(X, cm, ko, tab, g.K2, rsrc, srclive, j, uy, ux, g.Hs, g.Ws, lane, keep, ssum); return; }
   if (uy >= 0 && ux >= 0 && uy + g.WY <= g.Hs && ux + g.WX <= g.Ws)
     gather_tile<true>(X, cm, ko, kvo, g.K2, rsrc, j, uy, ux, g.Hs, g.Ws, lane, keep);
   else
@@ -336,12 +365,13 @@ __device__ __forceinline__ void gather_tile16(f32x4 (&acc)[4], const float* cm, 
 
 // Sparse variant: the rows of dead source nodes are exactly zero, so a tile first compacts the live, in-range slots of its
 // window into a per-wave LDS table {byte offset of the row, tap-matrix row} and then walks only those (-35..45 % k-steps
-// behind a ReLU layer).  `tab`: 4*K2 + 32 entries of this wave; slb / sub: bounds of the source layer of this sample.
+// behind a ReLU layer).  `tab`: 4*K2 + 32 entries of this wave; srclive: see gather_tile_sparse.
 #ifndef GATHER_CHS16
 #define GATHER_CHS16 4
 #endif
+template <class LS>
 __device__ __forceinline__ void gather_tile16_sparse(f32x4 (&acc)[4], const float* cm, const int2* ko, uint2* tab, int K2,
-                                                     __amdgpu_buffer_rsrc_t rsrc, const float* slb, const float* sub, int wy0, int wx0,
+                                                     __amdgpu_buffer_rsrc_t rsrc, const LS& srclive, int wy0, int wx0,
                                                      int Hs, int Ws, int lane, float* ssum = nullptr) {
   const int g = lane >> 4, i = lane & 15;
   float sacc = 0.0f;                                  // ssum: see gather_tile_sparse
@@ -356,7 +386,12 @@ __device__ __forceinline__ void gather_tile16_sparse(f32x4 (&acc)[4], const floa
     const int wy = wy0 + (ey & 0xffff), wx = wx0 + (ey >> 16);
     const bool inb = sl < 4 * K2 && (unsigned)wy < (unsigned)Hs && (unsigned)wx < (unsigned)Ws;      // (table padding: 0x7fff, never in range)
     const int row = inb ? origin + ex : 0;
-    const bool live = inb && node_is_live(slb[row], sub[row]);
+#ifdef LIVE_ABL            // dev, timing only (wrong results): see gather_tile_sparse
+    const bool live = inb && (unsigned)row * 2654435761u < 0x8a3d70a3u;
+#else
+    const bool lrow = srclive(row);          // (every lane asks: BitsLive permutes)
+    const bool live = inb && lrow;
+#endif
     const unsigned long long bal = __ballot(live);
     if (live) tab[n + __popcll(bal & ((1ull << lane) - 1ull))] = make_uint2((unsigned)row * 256u, (unsigned)sl * 16u);
     n += __popcll(bal);
@@ -531,6 +566,7 @@ struct GArgs {
   DGather g;
   EmbedSrc es;              // EMBED: the source rows are computed from the input scalars (mu_src unused)
   const float *src_lb, *src_ub;   // SPARSE: bounds of the source layer (B, Ns): the rows of its dead nodes are zero and skipped
+  const unsigned* src_bits;       // SPARSE: the source layer's live bitmap as 32-bit words (the BitsLive forms of k_gather_update_q read it instead of the bounds)
   float* sout;                    // SPARSE: (B, N) bias-sum scalars s = sum_n A[n', n] live_n written beside nb (null: k_livesum has them)
 };
 
@@ -552,9 +588,11 @@ __device__ __forceinline__ EmbedLane embed_lane(const GArgs& a, int j) {
 
 // the aggregate of one 32-node tile into X (gather channel map), tap-count division included; ssum: the bias-sum scalar of the
 // sparse walk (see gather_tile_sparse), normalised like the aggregate
-template <bool EMBED, bool SPARSE>
+// BITS: the sparse table build reads `lbits`, this lane's word of the sample's live bitmap (BitsLive), instead of the source bounds
+template <bool EMBED, bool SPARSE, bool BITS = false>
 __device__ __forceinline__ void gather_compute_tile(const GArgs& a, const TileCtx& tc, int sample, const float* lds_cm, const int2* lds_ko,
-                                                    const unsigned* lds_kvo, uint2* tab, const EmbedLane& el, int lane, Frag& X, float& ssum) {
+                                                    const unsigned* lds_kvo, uint2* tab, const EmbedLane& el, int lane, Frag& X, float& ssum,
+                                                    unsigned lbits = 0u) {
   const int j = lane & 31;
   ssum = 0.0f;
   const int wy0 = tc.by * a.g.ystep + a.g.ybase, wx0 = tc.bx * a.g.xstep + a.g.xbase;
@@ -570,9 +608,12 @@ __device__ __forceinline__ void gather_compute_tile(const GArgs& a, const TileCt
     else
       gather_tile_embed<false>(X, cmt, lds_ko, lds_kvo, a.g.K2, rl, rx, ru, el.w, el.b, uy, ux, a.g.Hs, a.g.Ws, lane);
   } else {
-    if (SPARSE)
+    if (SPARSE && BITS)
       gather_dispatch(X, lds_cm + tc.cg * a.g.K2 * 64, lds_ko, lds_kvo, a.g, a.mu_src + (long)sample * a.g.Ns * 64, j, wy0, wx0, lane, tab,
-                      a.src_lb + (long)sample * a.g.Ns, a.src_ub + (long)sample * a.g.Ns, false, a.sout ? &ssum : nullptr);
+                      BitsLive{lbits, livebits_bit0(sample, a.g.Ns)}, false, a.sout ? &ssum : nullptr);
+    else if (SPARSE)
+      gather_dispatch(X, lds_cm + tc.cg * a.g.K2 * 64, lds_ko, lds_kvo, a.g, a.mu_src + (long)sample * a.g.Ns * 64, j, wy0, wx0, lane, tab,
+                      BoundsLive{a.src_lb + (long)sample * a.g.Ns, a.src_ub + (long)sample * a.g.Ns}, false, a.sout ? &ssum : nullptr);
     else
       gather_dispatch(X, lds_cm + tc.cg * a.g.K2 * 64, lds_ko, lds_kvo, a.g, a.mu_src + (long)sample * a.g.Ns * 64, j, wy0, wx0, lane);
   }
@@ -952,10 +993,10 @@ __device__ __forceinline__ void gather_pair16_block_embed(f32x4 (&acc)[8], const
 
 // the aggregate of one 16-node tile (forward edges only: no tap-count division): acc[t][r] of lane (j, g') = channel 16 g' + 4 r + t;
 // a block-form edge (a.g.block): acc[pg][v] of lane (b, c) = channel 4b + v of tile lane blk_dst(pg, lane)
-template <bool EMBED, bool SPARSE, bool BLOCK = false>
+template <bool EMBED, bool SPARSE, bool BLOCK = false, bool BITS = false>
 __device__ __forceinline__ void gather_compute_tile16(const GArgs& a, const TileCtx& tc, int sample, const float* lds_cm, const int2* lds_ko,
                                                       const unsigned* lds_kvo, uint2* tab, const float (&ew)[4][3], const float (&eb)[4], int lane,
-                                                      f32x4 (&acc)[4], float& ssum) {
+                                                      f32x4 (&acc)[4], float& ssum, unsigned lbits = 0u) {
   ssum = 0.0f;
   const int wy0 = tc.by * a.g.ystep + a.g.ybase, wx0 = tc.bx * a.g.xstep + a.g.xbase;
   const int uy = __builtin_amdgcn_readfirstlane(wy0), ux = __builtin_amdgcn_readfirstlane(wx0);
@@ -994,9 +1035,12 @@ __device__ __forceinline__ void gather_compute_tile16(const GArgs& a, const Tile
   } else {
     const float* sbase = a.mu_src + (long)sample * a.g.Ns * 64;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, a.g.Ns * 256, 0x00020000);
-    if (SPARSE) {
+    if (SPARSE && BITS) {
+      gather_tile16_sparse(acc, cmt, lds_ko, tab, a.g.K2, rsrc, BitsLive{lbits, livebits_bit0(sample, a.g.Ns)}, uy, ux, a.g.Hs, a.g.Ws, lane,
+                           a.sout ? &ssum : nullptr);
+    } else if (SPARSE) {
       const long sb = (long)sample * a.g.Ns;
-      gather_tile16_sparse(acc, cmt, lds_ko, tab, a.g.K2, rsrc, a.src_lb + sb, a.src_ub + sb, uy, ux, a.g.Hs, a.g.Ws, lane,
+      gather_tile16_sparse(acc, cmt, lds_ko, tab, a.g.K2, rsrc, BoundsLive{a.src_lb + sb, a.src_ub + sb}, uy, ux, a.g.Hs, a.g.Ws, lane,
                            a.sout ? &ssum : nullptr);
     } else if (interior) gather_tile16<true>(acc, cmt, lds_ko, lds_kvo, a.g.K2, rsrc, uy, ux, a.g.Hs, a.g.Ws, lane);
     else gather_tile16<false>(acc, cmt, lds_ko, lds_kvo, a.g.K2, rsrc, uy, ux, a.g.Hs, a.g.Ws, lane);
@@ -1216,10 +1260,10 @@ __device__ __forceinline__ void input_update_tile(const GIArgs& a, const TileCtx
 #endif
   if (SPARSE)
     gather_dispatch(H, gl.cm + tc.cg * a.g.K2 * 64, gl.ko, gl.kvo, a.g, a.mu_src + (long)sample * a.g.Ns * 64, j, wy0, wx0, lane, tab,
-                    a.src_lb + (long)sample * a.g.Ns, a.src_ub + (long)sample * a.g.Ns, true, &ssum /* (always: a pointer chosen at run time would pin `ssum` to the stack; it is only used when own_s) */);
+                    BoundsLive{a.src_lb + (long)sample * a.g.Ns, a.src_ub + (long)sample * a.g.Ns}, true, &ssum /* (always: a pointer chosen at run time would pin `ssum` to the stack; it is only used when own_s) */);
   else
     gather_dispatch(H, gl.cm + tc.cg * a.g.K2 * 64, gl.ko, gl.kvo, a.g, a.mu_src + (long)sample * a.g.Ns * 64, j, wy0, wx0, lane, nullptr,
-                    nullptr, nullptr, true);
+                    BoundsLive{}, true);
   if (own_s) {
     const float xs[1] = {h ? 0.0f : ssum};
     gemm_small<1>(lds_upd + PackUpdInp::VC, lane, H, xs);

@@ -64,6 +64,7 @@ struct ClassifyArgs {    // every ReLU layer of the network in one launch
   int zero[MAXL];                  // 1: some consumer of this layer's rows reads the rows of dead nodes too -> they are zeroed here
   int* live[MAXL]; int* amb[MAXL]; int* score[MAXL];
   float* livef[MAXL];              // (B*N_k) 1.0 / 0.0: [r0 != 0], read by k_livesum
+  unsigned long long* lbits[MAXL]; // the same flags, one bit per node: word g >> 6 = the ballot of nodes [64 (g >> 6), +64) (BitsLive, gnnb_k_gather.h); null: not kept
   long G[MAXL];
   int N[MAXL], off[MAXL], blk0[MAXL + 1];   // first workgroup of each layer
   const float* mask;
@@ -119,6 +120,9 @@ __device__ __forceinline__ int classify_block(const ClassifyArgs& a, int* amb_lo
       a.scores[sidx] = -INFINITY;
       a.livef[k][g] = live[i] ? 1.0f : 0.0f;
     }
+    // a wave's first node is a multiple of 64 (CLS_THREADS and CLS_BLOCK are): its ballot is one whole word of the bitmap, invalid lanes 0
+    const unsigned long long lbal = __ballot(live[i]);
+    if (a.lbits[k] && lane == 0 && valid[i]) a.lbits[k][g >> 6] = lbal;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       bal[i][c] = __ballot(flag[i][c]);
