@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -21,6 +21,9 @@ at it; --pgd N lowers every child's upper bound by up to N projected gradient st
 --frontier K --branching babsr branches on the BaBSR heuristic alone, as the reference's relu_bab does: the same
 rounds, bounds and pick rule with gnnb_babsr and the decision rule on the device in the GNN's place -- what the GNN's branch count is compared
 with; with --props N every property has its own intercept counter (frontier.verify_properties_babsr).  (--babsr alone is the host loop.)
+--frontier K --branching strong is strong branching, the strategy the GNN was trained to imitate: both children of
+every candidate split of every parent are bounded on the device and the parent splits where its bound improves most; --candidates M keeps
+the M undecided nodes of highest BaBSR score as candidates (without it every undecided node is one: thousands per parent on the CIFAR nets).
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -55,12 +58,18 @@ def main():
     ap.add_argument("--witness", action="store_true", help="with --frontier: return the point of the upper bound and print the network's value at it")
     ap.add_argument("--pgd", type=int, default=None, metavar="N", help="with --frontier: up to N projected gradient steps from every child's LP point")
     ap.add_argument("--restarts", type=int, default=None, metavar="R", help="with --pgd N: also descend from R uniform points of every child's box")
-    ap.add_argument("--branching", default=None, choices=("gnn", "babsr"), help="with --frontier K: what picks the split, the GNN (default) or the BaBSR heuristic alone")
+    ap.add_argument("--branching", default=None, choices=("gnn", "babsr", "strong"),
+                    help="with --frontier K: what picks the split, the GNN (default), the BaBSR heuristic alone, or strong branching")
+    ap.add_argument("--candidates", type=int, default=None, metavar="M", help="with --branching strong: bound the M undecided nodes of highest BaBSR score only")
     args = ap.parse_args()
     if args.branching is not None and args.frontier is None:
         ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
     if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
         ap.error("--branching babsr takes no --threshold and no --online: it never asks the GNN")
+    if args.branching == "strong" and (args.threshold is not None or args.online is not None or args.props is not None):
+        ap.error("--branching strong takes no --threshold, no --online and no --props: it never asks the GNN, and it runs one property")
+    if args.candidates is not None and (args.branching != "strong" or args.candidates < 1):
+        ap.error("--candidates M needs --branching strong, and M >= 1")
     branching = args.branching or "gnn"
     if args.restarts is not None and (args.pgd is None or not 0 <= args.restarts <= 4096):
         ap.error("--restarts R needs --pgd N, and 0 <= R <= 4096")
@@ -121,7 +130,7 @@ def main():
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
                                                                       branching_threshold=args.threshold, stats=stats, online_threshold=args.online,
-                                                                      branching=branching, **upper)
+                                                                      strong_candidates=args.candidates, branching=branching, **upper)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
         if args.online is not None:
@@ -129,6 +138,8 @@ def main():
         if args.witness:
             kw += witness_of(upper["witness"][0], layers[:-1], layers[-1])
         by = "" if args.branching is None else f"{stats['branches']} branches by {branching}, "
+        if branching == "strong":
+            by += f"{stats['strong_bounded']} candidate children bounded, "
         print(f"after {rounds} rounds ({by}{bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
     lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)

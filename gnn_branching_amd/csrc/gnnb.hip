@@ -65,6 +65,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_net.h"
 #include "gnnb_k_frontier.h"
 #include "gnnb_k_starts.h"
+#include "gnnb_k_strong.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -99,7 +100,8 @@ enum ProfClass {
   PC_FR_GATHER, PC_FR_EXPAND, PC_NET_EVAL, PC_FR_RESOLVE, PC_FR_DECIDE, PC_FR_STORE, PC_FR_PICK_JOBS, PC_FR_ROWS_JOBS, PC_FR_DECIDE_JOBS,
   PC_FR_CANDIDATES, PC_FR_FALLBACK, PC_FR_CHOOSE, PC_FR_CHOOSE_COPY, PC_FR_FALLBACK_JOBS, PC_FR_SELECT_JOBS, PC_FR_ROWS_SEL, PC_FR_CHOOSE_JOBS,
   PC_FR_LEARN, PC_TROWS_GATHER, PC_NET_DESCEND, PC_FR_WITNESS, PC_FR_WITNESS_JOBS,
-  PC_NET_STARTS, PC_NET_DESCEND_TILE, PC_NET_STARTS_PICK, PC_FR_BABSR_DECIDE, PC_FR_BABSR_DECIDE_JOBS, PC_COUNT
+  PC_NET_STARTS, PC_NET_DESCEND_TILE, PC_NET_STARTS_PICK, PC_FR_BABSR_DECIDE, PC_FR_BABSR_DECIDE_JOBS,
+  PC_STRONG_COUNT, PC_STRONG_COMPACT, PC_STRONG_PICK, PC_COUNT
 };
 static const char* kProfNames[PC_COUNT] = {
     "k_embed", "k_pre", "k_pre_inp", "k_conv_fwd", "k_convT_bwd", "k_dense_agg", "k_prop",
@@ -110,7 +112,8 @@ static const char* kProfNames[PC_COUNT] = {
     "k_frontier_candidates", "k_frontier_fallback", "k_frontier_choose", "k_frontier_choose_copy",
     "k_frontier_fallback_jobs", "k_frontier_select_jobs", "k_frontier_rows_sel", "k_frontier_choose_jobs",
     "k_frontier_learn", "k_trows_gather", "k_net_descend", "k_frontier_witness", "k_frontier_witness_jobs",
-    "k_net_starts", "k_net_descend_tile", "k_net_starts_pick", "k_frontier_babsr_decide", "k_frontier_babsr_decide_jobs"};
+    "k_net_starts", "k_net_descend_tile", "k_net_starts_pick", "k_frontier_babsr_decide", "k_frontier_babsr_decide_jobs",
+    "k_strong_count", "k_strong_compact", "k_strong_pick"};
 
 struct DevEdge : DenseGeom {
   DevBuf<float> w_fwd, w_bwd, bias;   // conv: tap-major copies; linear: W^T / W, zero-padded (gnnb_pack.h dense_operands)
@@ -2277,6 +2280,53 @@ extern "C" int gnnb_frontier_babsr_decide_jobs(gnnb_t* h, const gnnb_plan* plan,
   Launcher run{h, st};
   run.run(PC_FR_CANDIDATES, [&] { hipLaunchKernelGGL(k_frontier_candidates, dim3(j.n), dim3(FR_THREADS), 0, st, a); });
   run.run(PC_FR_BABSR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_babsr_decide_jobs, dim3(j.n_entries), dim3(64), 0, st, a, j); });
+  return run.rc;
+}
+
+// ---- strong branching (gnnb_k_strong.h): the candidates of every parent row, and the best of them ----
+extern "C" size_t gnnb_strong_list_workspace_bytes(const gnnb_t* h, int K) {
+  if (!h || !h->bound || K < 1) return 0;
+  return (size_t)K * SC_FIELDS * sizeof(int32_t);
+}
+
+extern "C" int gnnb_strong_list(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const float* scorer_mask, const float* scores,
+                                int top_m, int32_t* cand0, int32_t* cand_row, int32_t* cand_slot, int32_t* cand_dec, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_strong_list";
+  if (K < 1 || K > 32767) return fail(GNNB_E_INVALID, "%s: K = %d outside 1..32767", who, K);
+  if (top_m < 0) return fail(GNNB_E_INVALID, "%s: top_m = %d (0: every undecided node, or the number of candidates per row)", who, top_m);
+  if (top_m > 0 && !scores) return fail(GNNB_E_INVALID, "%s: top_m = %d needs scores (null)", who, top_m);
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !scorer_mask || !cand0 || !cand_row || !cand_slot || !cand_dec || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  const size_t need = gnnb_strong_list_workspace_bytes(h, K);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  StrongListArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
+  a.slots = slots; a.K = K; a.amb = scorer_mask; a.scores = scores; a.top_m = top_m;
+  a.cand0 = cand0; a.cand_row = cand_row; a.cand_slot = cand_slot; a.cand_dec = cand_dec; a.rows = (int32_t*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_STRONG_COUNT, [&] { hipLaunchKernelGGL(k_strong_count, dim3(K), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_STRONG_COMPACT, [&] { hipLaunchKernelGGL(k_strong_compact, dim3(K), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const int32_t* cand0, const int32_t* cand_dec,
+                                const int32_t* live, const int32_t* infeasible, const double* bound, int32_t* decisions,
+                                double* best_improvement, double* improvement, double* table, void* stream) {
+  const char* who = "gnnb_strong_pick";
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !cand0 || !cand_dec || !live || !infeasible || !bound || !decisions || !best_improvement || !improvement)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  StrongPickArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
+  a.slots = slots; a.K = K; a.cand0 = cand0; a.cand_dec = cand_dec; a.live = live; a.infeasible = infeasible; a.bound = bound;
+  a.decisions = decisions; a.best = best_improvement; a.imp = improvement; a.table = table;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_STRONG_PICK, [&] { hipLaunchKernelGGL(k_strong_pick, dim3(K), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 

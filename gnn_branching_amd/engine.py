@@ -1151,6 +1151,41 @@ class ScorerEngine:
         ws = self._workspace("babsr_decide", max(n, 1), "gnnb_frontier_babsr_decide_workspace_bytes") if workspace is None else workspace
         self._call("gnnb_frontier_babsr_decide_jobs", C.byref(pl), *args, ws.data_ptr(), ws.numel())
 
+    def strong_list(self, pool, slots, scorer_mask, scores, top_m, cand0, cand_row, cand_slot, cand_dec, workspace=None):
+        """gnnb_strong_list on the current stream: the candidate splits of the K parents in ``slots`` ((K,) int32)
+        as dense lists in row order.  scorer_mask (K, R) fp32 (``frontier_gather``); top_m 0: every undecided node, scores None; top_m
+        M > 0: the M first on (score descending, flat index ascending), scores (K, R) fp32 (``babsr_rows``).  cand0 (K + 1,) int32 receives
+        the exclusive prefix of the rows' counts (cand0[K] = n), cand_row / cand_slot (n,) and cand_dec (n, 2) int32 the lists; they hold
+        K * min(R, top_m or R) entries, and entries from n on are not written.  Nothing is copied."""
+        K, top_m = int(slots.numel()), int(top_m)
+        st, keep = self._pool(pool)
+        R, i32, f32 = self.R, torch.int32, torch.float32
+        cap = max(K, 0) * (min(R, top_m) if top_m > 0 else R)
+        ws = self._workspace("strong_list", K, "gnnb_strong_list_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_strong_list", C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K,
+                   self._rows(scorer_mask, K, R, f32, "scorer_mask").data_ptr(),
+                   None if scores is None else self._rows(scores, K, R, f32, "scores").data_ptr(), top_m,
+                   self._rows(cand0, K + 1, 1, i32, "cand0").data_ptr(), self._rows(cand_row, cap, 1, i32, "cand_row").data_ptr(),
+                   self._rows(cand_slot, cap, 1, i32, "cand_slot").data_ptr(), self._rows(cand_dec, cap, 2, i32, "cand_dec").data_ptr(),
+                   ws.data_ptr(), ws.numel())
+
+    def strong_pick(self, pool, slots, cand0, cand_dec, n, live, infeasible, bound, decisions, best_improvement, improvement, table=None):
+        """gnnb_strong_pick on the current stream: the improvement of each of the n listed candidates from its two
+        bounded child rows (live / infeasible (2n,) int32, bound (2n,) fp64, list order) into improvement (n,) fp64, and per parent row
+        the arg-max into decisions (K, 2) int32 ([-1, -1]: none) and best_improvement (K,) fp64 (NaN: none); table: None, or (K, R) fp64
+        that receives imp at every candidate's flat index and NaN elsewhere.  n: the host's copy of cand0[K], for the shape checks only --
+        the kernel reads its own.  Nothing is copied."""
+        K, n = int(slots.numel()), max(int(n), 0)
+        st, keep = self._pool(pool)
+        i32, f64 = torch.int32, torch.float64
+        self._call("gnnb_strong_pick", C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K,
+                   self._rows(cand0, K + 1, 1, i32, "cand0").data_ptr(), self._rows(cand_dec, n, 2, i32, "cand_dec").data_ptr(),
+                   self._rows(live, 2 * n, 1, i32, "live").data_ptr(), self._rows(infeasible, 2 * n, 1, i32, "infeasible").data_ptr(),
+                   self._rows(bound, 2 * n, 1, f64, "bound").data_ptr(), self._rows(decisions, K, 2, i32, "decisions").data_ptr(),
+                   self._rows(best_improvement, K, 1, f64, "best_improvement").data_ptr(),
+                   self._rows(improvement, n, 1, f64, "improvement").data_ptr(),
+                   None if table is None else self._rows(table, K, self.R, f64, "table").data_ptr())
+
     def _children(self, ch, n, what=None):
         """The gnnb_children of a set of child rows (any object with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live) and what must
         outlive the call.  what: the rows' name in a message (None: loose tensors, named as ``frontier_commit`` takes them)."""

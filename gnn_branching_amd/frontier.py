@@ -21,6 +21,11 @@ N-th time on it is a learn row, and behind the commit the round takes one Adam s
 ``branch_and_bound_frontier(..., branching="babsr")`` and ``verify_properties_babsr`` are the reference's
 ``relu_bab`` on the same round: every parent is split at the BaBSR heuristic's decision (``gnnb_babsr``, ``gnnb_frontier_babsr_decide``), one
 intercept counter carried through the run (per job), and the GNN is never run.
+
+``branch_and_bound_frontier(..., branching="strong")`` is strong branching, the GNN's teacher, on the same round:
+both children of every candidate split of every parent are bounded in chunks (``gnnb_strong_list``, then ``gnnb_frontier_expand``,
+``gnnb_kw_bounds`` and ``gnnb_dual_ascent`` per chunk) and every parent is split where its bound improves most (``gnnb_strong_pick``);
+``strong_audit=[]`` computes the same table next to a "gnn" or "babsr" run and records how far the committed decision is from the best.
 """
 import ctypes as C
 import math
@@ -135,6 +140,25 @@ class _Rows:
         return self.mask, self.lb, self.ub, self.infeasible, self.bound, self.alpha, self.beta, self.ubv, self.live
 
 
+class _StrongRows:
+    """The child rows of a chunk of strong-branching candidates: what gnnb_frontier_expand writes and
+    gnnb_kw_bounds / gnnb_dual_ascent read and write of n rows -- ``_Rows``' bounding side without the scorer's inputs, the LP point and
+    the upper value, which no candidate gets; live, infeasible and bound are the run's (2n) arrays."""
+
+    def __init__(self, eng, n, box):
+        dev, R, sizes, ng = eng.device, eng.R, eng.sizes, len(eng.sizes)
+        f64 = torch.float64
+        self.mask = torch.zeros(n, R, dtype=torch.int8, device=dev)
+        self.lb, self.ub, self.plb, self.pub = ([torch.zeros(n, s, dtype=f64, device=dev) for s in sizes[1:]] for _ in range(4))
+        self.alpha, self.beta = torch.zeros(n, R, dtype=f64, device=dev), torch.zeros(n, R, dtype=f64, device=dev)
+        self.split = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.box = box
+        x_lo, x_hi, pw, pb = (t.data_ptr() for t in box)
+        self.t_lb, self.t_ub, self.t_plb, self.t_pub = table(self.lb), table(self.ub), table(self.plb), table(self.pub)
+        self.dual_batch = _lib.DualBatch(self.t_lb, self.t_ub, x_lo, x_hi, pw, pb, self.mask.data_ptr(), ng)
+        self.kw_batch = _lib.KwBatch(x_lo, x_hi, pw, pb, self.mask.data_ptr(), self.t_plb, self.t_pub, self.split.data_ptr(), ng)
+
+
 def _check_args(K, n_iter, lr, eps, max_rounds, capacity):
     if not isinstance(K, int) or isinstance(K, bool) or K < 1 or K > 32767:
         raise ValueError(f"K = {K!r}: an integer in 1..32767")
@@ -181,7 +205,8 @@ def _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         raise TypeError(f"online_threshold needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
 
 
-BRANCHINGS = ("gnn", "babsr")
+BRANCHINGS = ("gnn", "babsr", "strong")
+STRONG_CHUNK_DEFAULT = 256          # strong_chunk's default, candidates per bounding chunk: the best of 32..256 measured
 
 
 def _check_branching(branching, branching_threshold, online_threshold):
@@ -191,6 +216,26 @@ def _check_branching(branching, branching_threshold, online_threshold):
     if branching == "babsr" and (branching_threshold is not None or online_threshold is not None):
         raise ValueError('branching="babsr" branches on the BaBSR heuristic alone (relu_bab): it takes no branching_threshold and no online_threshold, '
                          "which compare the heuristic with the GNN")
+    if branching == "strong" and (branching_threshold is not None or online_threshold is not None):
+        raise ValueError('branching="strong" branches where the bound improves most (DESIGN.md section 7.11): it takes no branching_threshold and no '
+                         "online_threshold, which compare the heuristic with the GNN")
+
+
+def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold):
+    """The strong-branching options of DESIGN.md section 7.11, before a device is touched."""
+    if strong_candidates is not None and (not isinstance(strong_candidates, int) or isinstance(strong_candidates, bool) or strong_candidates < 1):
+        raise ValueError(f"strong_candidates = {strong_candidates!r}: None (every undecided node), or an integer >= 1")
+    if not isinstance(strong_chunk, int) or isinstance(strong_chunk, bool) or strong_chunk < 1:
+        raise ValueError(f"strong_chunk = {strong_chunk!r}: an integer >= 1, the candidates per bounding chunk")
+    if strong_audit is not None and not isinstance(strong_audit, list):
+        raise ValueError(f"strong_audit = {strong_audit!r}: None, or a list that receives one dict per parent")
+    if branching != "strong" and strong_audit is None:
+        if strong_candidates is not None:
+            raise ValueError(f'strong_candidates = {strong_candidates!r} without branching="strong" or a strong_audit: nothing would use it')
+        if strong_chunk != STRONG_CHUNK_DEFAULT:
+            raise ValueError(f'strong_chunk = {strong_chunk!r} without branching="strong" or a strong_audit: nothing would use it')
+    if strong_audit is not None and (branching_threshold is not None or online_threshold is not None):
+        raise ValueError("strong_audit audits the one decision a round commits per parent: it takes no branching_threshold and no online_threshold")
 
 
 PGD_STEP_DEFAULT = 1.0 / 64
@@ -226,6 +271,14 @@ class _Round:
     witness_on, pgd_steps, pgd_step = False, None, PGD_STEP_DEFAULT
     restarts, pgd_seed = 0, 0
     branching = "gnn"
+    strong_on, strong_M, strong_chunk, strong_audit = False, 0, STRONG_CHUNK_DEFAULT, None
+
+    def _strong_options(self, strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold):
+        """The options of DESIGN.md section 7.11, checked; set before the rows are made (``_buffers`` sizes the workspaces by them).
+        ``strong_on`` False: nothing of a round differs."""
+        _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold)
+        self.strong_on = branching == "strong" or strong_audit is not None
+        self.strong_M, self.strong_chunk, self.strong_audit = strong_candidates or 0, strong_chunk, strong_audit
 
     def _restart_options(self, pgd_restarts, pgd_seed):
         """The options of DESIGN.md section 7.9, checked, behind ``_upper_bound_options``; ``restarts`` 0: off, and nothing of a round differs."""
@@ -254,9 +307,10 @@ class _Round:
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
         self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws_fwd = ws("gnnb_workspace_bytes", n_parents) if self.branching == "gnn" else None     # (a BaBSR round runs no gnnb_forward)
-        self.ws_kw = ws("gnnb_kw_workspace_bytes", n_children)
-        self.ws_dual = ws("gnnb_dual_workspace_bytes", n_children)
+        self.ws_fwd = ws("gnnb_workspace_bytes", n_parents) if self.branching == "gnn" else None     # (a BaBSR or strong round runs no gnnb_forward)
+        n_bound = max(n_children, 2 * self.strong_chunk) if self.strong_on else n_children      # (the candidates' chunks share the workspaces)
+        self.ws_kw = ws("gnnb_kw_workspace_bytes", n_bound)
+        self.ws_dual = ws("gnnb_dual_workspace_bytes", n_bound)
         self.ws_eval, self.ws_commit = ws("gnnb_net_eval_workspace_bytes", n_children), ws("gnnb_frontier_commit_workspace_bytes", n_parents)
         if self.pgd_steps is not None:
             self.ws_descend = ws("gnnb_net_descend_workspace_bytes", n_children)
@@ -305,8 +359,59 @@ class _Round:
         self.kw_scores, self.kw_icp = torch.zeros(n_parents, R, dtype=f32, device=dev), torch.zeros(n_parents, R, dtype=f32, device=dev)
         self.ws_babsr = self._ws("gnnb_frontier_babsr_decide_workspace_bytes", n_parents)
 
+    def _strong_buffers(self, n_parents, box):
+        """The state of strong branching for rounds of up to n_parents parents.  box: the boxes and property rows
+        of the 2 * strong_chunk candidate child rows ``ChS``.  The dense lists hold n_parents * min(R, strong_candidates or R) candidates
+        and the run-long arrays live / infeasible / bound two children each; ``strong_bounded`` counts the candidate children bounded."""
+        dev, R, n = self.eng.device, self.eng.R, n_parents
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        cap = n * (min(R, self.strong_M) if self.strong_M else R)
+        self.ChS = _StrongRows(self.eng, 2 * self.strong_chunk, box)
+        self.s_scores, self.s_icp = (torch.zeros(n, R, dtype=f32, device=dev) for _ in range(2)) if self.strong_M else (None, None)
+        self.cand0 = torch.zeros(n + 1, dtype=i32, device=dev)
+        self.cand_row, self.cand_slot, self.cand_dec = (torch.zeros(s, dtype=i32, device=dev) for s in ((cap,), (cap,), (cap, 2)))
+        self.s_live, self.s_infeasible = torch.zeros(2 * cap, dtype=i32, device=dev), torch.zeros(2 * cap, dtype=i32, device=dev)
+        self.s_bound, self.s_imp = torch.zeros(2 * cap, dtype=f64, device=dev), torch.zeros(cap, dtype=f64, device=dev)
+        self.s_best, self.s_dec = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, 2, dtype=i32, device=dev)
+        self.ws_strong = self._ws("gnnb_strong_list_workspace_bytes", n)
+        self.strong_n, self.strong_bounded = 0, 0
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def read_candidates(self, n):
+        """cand0[n], the number of candidates of a round of n parents: the 4 bytes a strong round reads between the list and its chunks."""
+        return int(self.cand0[n:n + 1].cpu()[0])
+
+    def _strong_table(self, slots, n, dec):
+        """Steps 2-6 of a strong round over the n parent rows the gather wrote: gnnb_babsr for the pre-filter (with
+        ``strong_candidates``), gnnb_strong_list, the read of the number of candidates, per chunk of ``strong_chunk`` candidates
+        gnnb_frontier_expand into ``ChS``, gnnb_kw_bounds and gnnb_dual_ascent (no scorer inputs, no LP point; live, infeasible and bound go
+        to the run-long arrays at the chunk's offset), and gnnb_strong_pick into ``dec`` ((n, 2) int32).  No gnnb_net_eval, no PGD, no
+        witness: a candidate is only ever a lower bound."""
+        P, S, eng, pool, lib, h = self.P, self.ChS, self.eng, self.pool, self.lib, self.eng.h
+        if self.strong_M:
+            eng.babsr_rows(P.lb32, P.ub32, P.box[2], P.amb, n, self.s_scores, self.s_icp)
+        eng.strong_list(pool, slots, P.amb, self.s_scores, self.strong_M, self.cand0, self.cand_row, self.cand_slot, self.cand_dec,
+                        workspace=self.ws_strong)
+        n_c = self.strong_n = self.read_candidates(n)
+        for q0 in range(0, n_c, self.strong_chunk):               # a chunk may span parents
+            c = min(self.strong_chunk, n_c - q0)
+            eng.frontier_expand(pool, self.cand_slot[q0:q0 + c], self.cand_dec[q0:q0 + c], S.mask, S.plb, S.pub, S.split, S.alpha, S.beta,
+                                self.s_live[2 * q0:])
+            with torch.cuda.device(eng.device):
+                _lib.check(lib.gnnb_kw_bounds(h, C.byref(S.kw_batch), 2 * c, S.t_lb, S.t_ub, None, None, self.s_infeasible[2 * q0:].data_ptr(),
+                                              self.ws_kw.data_ptr(), self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
+                _lib.check(lib.gnnb_dual_ascent(h, C.byref(S.dual_batch), 2 * c, self.n_iter, self.lr, S.alpha.data_ptr(), S.beta.data_ptr(), 1,
+                                                self.s_bound[2 * q0:].data_ptr(), None, None, None, None, None, None, self.ws_dual.data_ptr(),
+                                                self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
+        self.strong_bounded += 2 * n_c
+        eng.strong_pick(pool, slots, self.cand0, self.cand_dec, n_c, self.s_live, self.s_infeasible, self.s_bound, dec, self.s_best, self.s_imp)
+
+    def _strong_parents(self, n):
+        """``branching="strong"`` in ``_score_parents``' place: the table of the n parent rows the gather wrote and
+        its arg-max per row into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward."""
+        self._strong_table(self.slots, n, self.P.dec)
 
     def _bound_children(self, Ch, B, warm):
         """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
@@ -366,9 +471,16 @@ class _Round:
         if self.branching == "gnn":
             self._score_parents(n)
         else:
-            self._babsr_parents(n)
+            if self.branching == "strong":
+                self._strong_parents(n)
+            else:
+                self._babsr_parents(n)
             if self.keep_pairs:                                   # (a traced run: "parent_bounds", which gnnb_dual_ascent at n_iter 0 would have left)
                 P.bound[:n] = pool.bound[slots[:n].long().clamp(min=0)]
+        if self.strong_audit is not None and self.branching != "strong":      # the same table next to the round's own decisions (P.dec untouched)
+            self._strong_table(slots, n, self.s_dec)
+        if self.strong_on and (self.keep_pairs or self.strong_audit is not None):      # (a traced or audited run: the bounds the commit overwrites)
+            self.parent_bound = pool.bound[slots[:n].long().clamp(min=0)]
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(Ch, 2 * n, warm=True)
         if self.threshold is not None:
@@ -415,10 +527,12 @@ class FrontierRun(_Round):
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
                  kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
-                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, branching="gnn"):
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
+                 strong_audit=None, branching="gnn"):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
         _check_branching(branching, branching_threshold, online_threshold)
         self.branching = branching
+        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold)
         self._upper_bound_options(witness, pgd_steps, pgd_step)
         self._restart_options(pgd_restarts, pgd_seed)
         _check_threshold(branching_threshold, kwbd_threshold)
@@ -448,6 +562,8 @@ class FrontierRun(_Round):
             self.m_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         if branching == "babsr":                                  # one intercept counter per run, zero at its start (relu_conv_any_kw.py:100)
             self._babsr_buffers(K, (1,), sparsest_layer, decision_threshold)
+        if self.strong_on:                                        # the candidates' rows: the run's one box and property, 2 * strong_chunk times
+            self._strong_buffers(K, tuple(t[:1].expand(2 * strong_chunk, *t.shape[1:]).contiguous() for t in (self.x_lo, self.x_hi, self.pw, self.pb)))
         self.online, self.k, self.learn_pending, self.last_learn = online_threshold, 0, False, 0
         self.online_steps = self.online_rows = 0
         if online_threshold is not None:
@@ -562,7 +678,7 @@ class FrontierRun(_Round):
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
                               online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0,
-                              branching="gnn"):
+                              strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -624,9 +740,31 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     whose scores hold a NaN, or that has no undecided node, gets no decision and is closed at its own bound (the host rule would raise).  It
     takes no ``branching_threshold`` and no ``online_threshold``.  A traced round's "decisions" are BaBSR's.
 
+    branching="strong", strong_candidates, strong_chunk, strong_audit (with ``branching`` "gnn" or "babsr" and
+    ``strong_audit`` at None no launch, read, buffer or argument of a round changes).  "strong": strong branching, the strategy the GNN was
+    trained to imitate: for every parent both children of every CANDIDATE split are bounded exactly as a round bounds children
+    (``gnnb_kw_bounds``, ``n_iter`` warm-started steps of ``gnnb_dual_ascent``) and the parent is split at the candidate whose
+    ``bab_caller.gnn_improvement`` is largest (equal values: the lowest flat ReLU index).  strong_candidates: None, every undecided node,
+    or an integer M >= 1, the M undecided nodes of highest BaBSR score (``gnnb_babsr``; equal scores: the lowest index).  The candidates of
+    all parents form one dense list (``gnnb_strong_list``) that is bounded in chunks of ``strong_chunk`` candidates (2 * strong_chunk child
+    rows per launch chain; a chunk may span parents), then ``gnnb_strong_pick`` writes the decisions; the round's one extra read is the
+    number of candidates (``FrontierRun.read_candidates``, 4 bytes).  The winners' children are then bounded again as any round's are,
+    which gives them their LP points and upper values: by the batch kernels' row independence their bounds are the candidates' bit for
+    bit.  ``choice`` supplies the engine, its GNN is never run.  A parent without a candidate (no undecided node, a NaN BaBSR score at an
+    undecided node) or whose every candidate has a dead child gets no decision and is closed at its own bound.  It takes no
+    ``branching_threshold`` and no ``online_threshold``.  A traced round also carries "strong_candidates" (flat indices) and
+    "strong_improvement", one list per parent; stats gains "strong_bounded", the candidate children bounded -- ``domains_bounded`` keeps
+    its meaning, the rounds' 2k children.  strong_audit: None, or a list; legal with every ``branching``, not with a threshold or online
+    learning.  Every round then also computes the table of its parents (in "strong" mode the one already there; otherwise the steps
+    above into buffers of their own, the round's decisions untouched) and appends one dict per parent: "slot", "decision" (the one
+    committed), "improvement" (of that decision, from the round's own children through ``bab_caller.gnn_improvement``; NaN for a dead
+    pair), "strong_decision", "best_improvement", "candidates" (flat indices) and "improvements" -- extra device-to-host copies, like
+    ``trace``'s: off in a timed run.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, branching)      # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, strong_candidates, strong_chunk,
+                      strong_audit, branching)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
@@ -659,6 +797,12 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
             trace.append(_trace_rows(run, 0, k))
             if branching_threshold is not None:
                 trace[-1].update(_threshold_trace(run, k))
+        if run.strong_on and (trace is not None or run.strong_audit is not None):
+            rows = _strong_rows(run, k)
+            if trace is not None and run.branching == "strong":
+                trace[-1].update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
+            if run.strong_audit is not None:
+                run.strong_audit.extend(rows)
         st = run.read_state()
         if trace is not None and run.online is not None:
             trace[-1].update(_online_trace(run, st))
@@ -676,7 +820,36 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
                      kw_used=int(run.n_used.cpu()[0]) if branching_threshold is not None else 0)
         if run.online is not None:
             stats.update(online_steps=run.online_steps, online_rows=run.online_rows)
+        if run.strong_on:
+            stats.update(strong_bounded=run.strong_bounded)
     return global_lb, global_ub, rounds, bounded, reason
+
+
+def _strong_rows(run, k):
+    """One dict per parent of the round just launched (device-to-host copies; a traced or audited run only): its slot, the decision the
+    round committed and that decision's improvement from the round's own children, the table's decision and best improvement, and the
+    row's candidates (flat ReLU indices) with their improvements."""
+    from .bab_caller import gnn_improvement
+    inf, nan = float("inf"), float("nan")
+    Ch, n = run.Ch, run.strong_n
+    off = [0]
+    for s in run.eng.sizes[1:-1]:
+        off.append(off[-1] + s)
+    slots = run.slots[:k].cpu().tolist()
+    dec = run.P.dec[:k].cpu().tolist()
+    s_dec = dec if run.branching == "strong" else run.s_dec[:k].cpu().tolist()
+    parent = run.parent_bound[:k].cpu().tolist()
+    live, infeasible, bound = (t[:2 * k].cpu().tolist() for t in (Ch.live, Ch.infeasible, Ch.bound))
+    cand0, best = run.cand0[:k + 1].cpu().tolist(), run.s_best[:k].cpu().tolist()
+    cand_dec, imp = run.cand_dec[:n].cpu().tolist(), run.s_imp[:n].cpu().tolist()
+    rows = []
+    for i in range(k):
+        lbs = [inf if infeasible[c] else bound[c] for c in (2 * i, 2 * i + 1)]
+        own = nan if not (live[2 * i] and live[2 * i + 1]) else (gnn_improvement(lbs[0], lbs[1], parent[i]) if parent[i] < 0 else 1.0)
+        a, b = cand0[i], cand0[i + 1]
+        rows.append({"slot": slots[i], "decision": dec[i], "improvement": own, "strong_decision": s_dec[i], "best_improvement": best[i],
+                     "candidates": [off[l] + j for l, j in cand_dec[a:b]], "improvements": imp[a:b]})
+    return rows
 
 
 def _online_trace(run, st):

@@ -544,6 +544,42 @@ int gnnb_frontier_babsr_decide_jobs(gnnb_t* h, const gnnb_plan* plan, const floa
                                     double decision_threshold, int sparsest_layer, const int32_t* random_order, int n_order, int32_t* icp,
                                     int32_t* decisions, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- strong branching: bound every candidate split (gnn_branching_amd/frontier.py branching="strong") ----
+ * The teacher of the GNN: for a parent row i of a round (pool slot slots[i], pool bound b, scorer_mask as gnnb_frontier_gather wrote it)
+ * both children of every candidate ReLU are bounded and the row splits where the bound improves most.
+ *
+ * CANDIDATES (gnnb_strong_list).  top_m = 0: every node r with scorer_mask[i, r] != 0, in ascending flat ReLU index.  top_m = M > 0: the M
+ * nodes of that set that come first in the total order (score descending, flat index ascending), emitted in ascending flat index; scores:
+ * gnnb_babsr's, device (K, R) fp32, compared as float VALUES (-0.0 == +0.0: the index decides; +-inf are ordinary values); fewer than M
+ * undecided nodes: all of them.  With top_m > 0 a row in which an undecided node's score is NaN gets no candidates (a NaN at a decided node
+ * is ignored); a row whose slot is outside the pool gets none.  cand0: device (K + 1) int32, the exclusive prefix of the rows' counts in
+ * row order, cand0[K] = n; the dense lists cand_row (n), cand_slot (n) and cand_dec (n, 2) as [layer, idx] -- cand_slot and cand_dec are
+ * gnnb_frontier_expand's slots and decisions as they are.  Entries from n on are not written; the caller sizes the lists for
+ * K * min(R, top_m or R) entries.  Two launches: k_strong_count (per row the count and, by bisection over the order-preserving integer key
+ * of the float, the cut), k_strong_compact (the prefix over the K counts in row order, the row's candidates by a block scan in index order).
+ * workspace: gnnb_strong_list_workspace_bytes (0 for a null or unbound handle).
+ *
+ * SCORE AND DECISION (gnnb_strong_pick).  live / infeasible / bound: device (2n), the candidates' children in list order (rows 2q blocked,
+ * 2q + 1 passing) as gnnb_frontier_expand, gnnb_kw_bounds and gnnb_dual_ascent left them, in chunks of any size.  imp_q = b < 0 ?
+ * (min(lb0, 0) + min(lb1, 0) - 2b) / (-2b) : 1.0, an infeasible child counting as +inf -- gnnb_frontier_fallback's formula, its operation
+ * order; a candidate with a child row whose live == 0 has imp = NaN.  The decision of a row is the arg-max of imp over its candidates on
+ * the total order (value descending, list position ascending), a fixed tree, NaN below every number; a row with no candidates or whose
+ * every imp is NaN gets [-1, -1] (gnnb_frontier_expand makes two dead children of it and the commit closes the parent at its own bound).
+ * Writes decisions (K, 2) int32 as gnnb_forward lays them out, best_improvement (K) fp64 (NaN without a decision), improvement (n) fp64
+ * and, with table (NULL, or device (K, R) fp64), imp at (row, flat index) of every candidate and NaN everywhere else of the K rows.  n is
+ * read from cand0[K] on the device.
+ *
+ * Both: stream-ordered, no allocation, no synchronisation, no atomics, no workgroup waits on another.  GNNB_E_INVALID before any launch for
+ * a null handle or required argument, K outside 1..32767, top_m < 0, top_m > 0 with null scores, or a network past the 4096-node cap;
+ * GNNB_E_STATE before gnnb_bind_network; GNNB_E_NOMEM for a short workspace. */
+size_t gnnb_strong_list_workspace_bytes(const gnnb_t* h, int K);
+int gnnb_strong_list(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const float* scorer_mask, const float* scores, int top_m,
+                     int32_t* cand0, int32_t* cand_row, int32_t* cand_slot, int32_t* cand_dec, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const int32_t* cand0, const int32_t* cand_dec,
+                     const int32_t* live, const int32_t* infeasible, const double* bound, int32_t* decisions, double* best_improvement,
+                     double* improvement, double* table, void* stream);
+
 /* ---- learning online inside the frontier (reference plnn/relu_conv_online.py:183-207) ----
  * The selection of the rows an online round learns from, after gnnb_frontier_choose: wrong (device (R) int32, zero at the start of a run)
  * is the reference's wrong_pts_dc, keyed by the flat ReLU index (the layer's offset + idx, graph_score_online.py:63-68) of the GNN's

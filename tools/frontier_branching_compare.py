@@ -1,18 +1,20 @@
 #!/usr/bin/env python
-"""GNN branching against BaBSR branching inside the device-resident frontier, on the same bounds, the same pick
-rule and the same K (GPU box).
+"""GNN branching against BaBSR branching and against strong branching, the GNN's teacher, inside the device-resident frontier (DESIGN.md
+sections 7.10 and 7.11), on the same bounds, the same pick rule and the same K (GPU box).
 
 Problems: toy_kw (the problem of tests/frontier_twin.py: property 2 vs 6 at eps 0.04) and cifar_base_kw, property 3 vs 5 at the demo's
 default eps 0.03 on the seeded N(0,1) images of seeds 0..3 (examples/bab_demo.py --seed).  For each, at K = 1 and K = 16, with
-decision_bound = 0, n_iter 20, lr 0.1, BaB eps 1e-4 and --rounds rounds at most: ``branching="gnn"`` against ``branching="babsr"``.
+decision_bound = 0, n_iter 20, lr 0.1, BaB eps 1e-4 and --rounds rounds at most: ``branching="gnn"`` against ``branching="babsr"`` and
+against ``branching="strong"`` over the --candidates (16) undecided nodes of highest BaBSR score per parent.
 Every one of those is decided at its root (no branch on either side), so two groups are run on top, marked "beyond_the_root": the same
 problems with no decision bound (to the gap or --rounds), and cifar_base_kw at --hard-eps (0.09, the eps of tools/frontier_timing.py) on
 the same seeds with decision_bound = 0.
-Recorded per run: rounds, branches (parents expanded), domains bounded, stop reason, final lb / ub, and the median device ms per round --
+Recorded per run: rounds, branches (parents expanded), domains bounded (strong: also the candidate children bounded), stop reason, final
+lb / ub, and the median device ms per round --
 HIP events around ``FrontierRun.launch_round`` (the round's launches, from the pick to the commit), the first two rounds of a run left
 out as warm-up, after one untimed run of the same mode and K.  Nothing is asserted about who wins.
 
-    python tools/frontier_branching_compare.py [--out profiles/frontier_branching_compare.json] [--ks 1,16] [--rounds 40] [--seeds 0,1,2,3]
+    python tools/frontier_branching_compare.py [--out profiles/frontier_branching_compare.json] [--ks 1,16] [--rounds 40] [--seeds 0,1,2,3] [--candidates 16]
 """
 import argparse
 import datetime
@@ -33,10 +35,10 @@ N_ITER, LR, EPS_BAB, WARMUP_ROUNDS = 20, 0.1, 1e-4, 2
 CKPT = os.path.join(ROOT, "models", "cifar_trained_gnn", "best_snapshot_None_0_val_acc_0.826_loss_val_0.1036_epoch_57.pt")
 
 
-def one_run(lp, choice, K, rounds, branching, decision_bound):
+def one_run(lp, choice, K, rounds, branching, decision_bound, **mode):
     """``branch_and_bound_frontier``'s loop (``frontier._one_job_round`` decides every round) with an event pair around each launch_round."""
     run = frontier.FrontierRun(lp, choice, lp.layers, K=K, n_iter=N_ITER, lr=LR, eps=EPS_BAB, decision_bound=decision_bound, max_rounds=rounds,
-                               branching=branching)
+                               branching=branching, **mode)
     st = run.root()
     done, bounded, branches, ms = 0, 1, 0, []
     while True:
@@ -57,7 +59,8 @@ def one_run(lp, choice, K, rounds, branching, decision_bound):
         bounded += int(st[_lib.FS_KEPT] + st[_lib.FS_CLOSED] + st[_lib.FS_INFEASIBLE])
     run.check_status()
     timed = ms[WARMUP_ROUNDS:]
-    return {"rounds": done, "branches": branches, "domains_bounded": bounded, "stop": reason, "global_lb": frontier._global_lb(st),
+    strong = {"strong_bounded": run.strong_bounded} if run.strong_on else {}
+    return {"rounds": done, "branches": branches, "domains_bounded": bounded, **strong, "stop": reason, "global_lb": frontier._global_lb(st),
             "global_ub": st[_lib.FS_GLOBAL_UB], "timed_rounds": len(timed),
             "median_device_ms_per_round": round(statistics.median(timed), 4) if timed else None}
 
@@ -87,9 +90,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=40)
     ap.add_argument("--seeds", default="0,1,2,3")
     ap.add_argument("--hard-eps", type=float, default=0.09)
+    ap.add_argument("--candidates", type=int, default=16, help="strong_candidates of the strong mode")
     args = ap.parse_args()
     torch.set_num_threads(16)
-    rec = {"what": f"branch_and_bound_frontier with branching='gnn' against branching='babsr': n_iter {N_ITER}, lr {LR}, BaB eps "
+    rec = {"what": f"branch_and_bound_frontier with branching='gnn' against branching='babsr' and branching='strong' (strong_candidates "
+                   f"{args.candidates}): n_iter {N_ITER}, lr {LR}, BaB eps "
                    f"{EPS_BAB}, at most {args.rounds} rounds; device ms per round from HIP events around launch_round, median over a run's rounds but its "
                    f"first {WARMUP_ROUNDS}, after one untimed run of the same mode and K",
            "date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(), "library_build_id": _lib.library_build_id(), "runs": []}
@@ -99,8 +104,9 @@ def main():
             for K in (int(k) for k in args.ks.split(",")):
                 entry = {"problem": name, "decision_bound": db, "K": K, "beyond_the_root": db is None or f"eps {args.hard_eps} " in name}
                 for branching in frontier.BRANCHINGS:
-                    one_run(lp, choice, K, min(args.rounds, WARMUP_ROUNDS + 1), branching, db)      # warm-up: allocations, first launches of every shape
-                    entry[branching] = one_run(lp, choice, K, args.rounds, branching, db)
+                    mode = {"strong_candidates": args.candidates} if branching == "strong" else {}
+                    one_run(lp, choice, K, min(args.rounds, WARMUP_ROUNDS + 1), branching, db, **mode)      # warm-up: allocations, first launches of every shape
+                    entry[branching] = one_run(lp, choice, K, args.rounds, branching, db, **mode)
                 rec["runs"].append(entry)
                 print(json.dumps(entry), flush=True)
                 with open(args.out, "w") as f:
