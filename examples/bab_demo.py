@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -24,6 +24,9 @@ with; with --props N every property has its own intercept counter (frontier.veri
 --frontier K --branching strong is strong branching, the strategy the GNN was trained to imitate: both children of
 every candidate split of every parent are bounded on the device and the parent splits where its bound improves most; --candidates M keeps
 the M undecided nodes of highest BaBSR score as candidates (without it every undecided node is one: thousands per parent on the CIFAR nets).
+--frontier K --imitate N (with the GNN or --branching strong) makes every N-th round a learning round: its parents'
+strong-branching table stays on the device and the GNN takes one Adam step towards ranking the table's best candidate first, by
+--imitate-margin M times the difference of the improvements.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -61,15 +64,22 @@ def main():
     ap.add_argument("--branching", default=None, choices=("gnn", "babsr", "strong"),
                     help="with --frontier K: what picks the split, the GNN (default), the BaBSR heuristic alone, or strong branching")
     ap.add_argument("--candidates", type=int, default=None, metavar="M", help="with --branching strong: bound the M undecided nodes of highest BaBSR score only")
+    ap.add_argument("--imitate", type=int, default=None, metavar="N", help="with --frontier K: every N-th round learns the GNN from its strong-branching table")
+    ap.add_argument("--imitate-margin", type=float, default=None, metavar="M", help="with --imitate N: the margin per unit of improvement (default 1.0)")
     args = ap.parse_args()
+    if args.imitate is not None and (args.frontier is None or args.imitate < 1 or args.branching == "babsr" or args.threshold is not None
+                                     or args.online is not None or args.props is not None):
+        ap.error("--imitate N needs --frontier K and N >= 1, and takes no --branching babsr, --threshold, --online or --props")
+    if args.imitate_margin is not None and (args.imitate is None or not args.imitate_margin >= 0):
+        ap.error("--imitate-margin M needs --imitate N, and M >= 0")
     if args.branching is not None and args.frontier is None:
         ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
     if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
         ap.error("--branching babsr takes no --threshold and no --online: it never asks the GNN")
     if args.branching == "strong" and (args.threshold is not None or args.online is not None or args.props is not None):
         ap.error("--branching strong takes no --threshold, no --online and no --props: it never asks the GNN, and it runs one property")
-    if args.candidates is not None and (args.branching != "strong" or args.candidates < 1):
-        ap.error("--candidates M needs --branching strong, and M >= 1")
+    if args.candidates is not None and ((args.branching != "strong" and args.imitate is None) or args.candidates < 1):
+        ap.error("--candidates M needs --branching strong or --imitate N, and M >= 1")
     branching = args.branching or "gnn"
     if args.restarts is not None and (args.pgd is None or not 0 <= args.restarts <= 4096):
         ap.error("--restarts R needs --pgd N, and 0 <= R <= 4096")
@@ -123,10 +133,13 @@ def main():
     if args.frontier is not None:
         from gnn_branching_amd.frontier import branch_and_bound_frontier
         lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device")
-        if args.online is not None:
+        learns = args.online is not None or args.imitate is not None
+        if learns:
             from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice
-        choice = (GraphChoice if args.online is None else OnlineGraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        choice = (OnlineGraphChoice if learns else GraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         stats = {}
+        if args.imitate is not None:
+            upper.update(imitate=args.imitate, **({} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}))
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
                                                                       branching_threshold=args.threshold, stats=stats, online_threshold=args.online,
@@ -135,6 +148,8 @@ def main():
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
         if args.online is not None:
             kw += f"; {stats['online_steps']} learning steps over {stats['online_rows']} learn rows"
+        if args.imitate is not None:
+            kw += f"; {stats['imitation_steps']} imitation steps over {stats['imitation_rows']} parent rows"
         if args.witness:
             kw += witness_of(upper["witness"][0], layers[:-1], layers[-1])
         by = "" if args.branching is None else f"{stats['branches']} branches by {branching}, "

@@ -154,6 +154,9 @@ SYMBOLS = [
                                    C.c_int, C.c_void_p]),
     ("gnnb_online_step_rows", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p]),
+    ("gnnb_imitation_step_rows", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double] + [C.c_void_p] * 4 +
+     [C.c_int, C.c_void_p]),
+    ("gnnb_imitation_loss", C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p]),
     ("gnnb_online_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("gnnb_last_error", C.c_char_p, []),
     ("gnnb_abi_version", C.c_int, []),

@@ -2483,7 +2483,14 @@ static int online_preflight(gnnb_t* h, const gnnb_batch* in, int B, const char* 
 // loss_host (B) / loss_dev (B) / scores_padded (DEVICE (B, R): the scores of the training-form forward BEFORE the update) / status
 // (DEVICE int32[1], k_tloss's bit 3) may be NULL.  apply = 0: gradient only (gnnb_online_grad), the parameters and the Adam state stay
 // as they are.  arena_ready: the caller has reset the trainer's arena and holds buffers from it (the gathered rows).
-static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* d_kw, const float* d_imp, float* loss_host, float* loss_dev,
+// The loss is a parameter: the KW form above (d_kw, d_imp; k_tloss, k_tscore_bwd_w over its two nodes per sample) or the table form of
+// gnnb_imitation_step_rows (table != null: k_tloss_table over the (B, R) fp64 rows, k_tscore_bwd_w_dense over the dense ds; report_i (B, 4) and
+// regret (B), DEVICE, may be NULL).  Everything else is shared.
+struct StepLoss {
+  const int32_t* d_kw = nullptr; const float* d_imp = nullptr;                                            // KW form
+  const double* table = nullptr; double margin = 0.0; int32_t* report_i = nullptr; double* regret = nullptr;      // table form
+};
+static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const StepLoss& lf, float* loss_host, float* loss_dev,
                               float* scores_padded, int32_t* status, int apply, hipStream_t st, bool arena_ready, const char* who) {
   using namespace gnnb_train;
   const int K = (int)h->N.size() - 1, L = K - 1, R = h->R, T = h->T;
@@ -2664,17 +2671,35 @@ static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const int3
     }
     const dim3 grid((unsigned)((nmax + 3) / 4), (unsigned)L);
     hipLaunchKernelGGL(k_tscore_fwd, grid, dim3(256), 0, st, sm);
-    t.tape.push_back([sm, grid, L, st]() {
+    TScoreDense sd{};                                      // table form: the chunk partials of the dense fscore gradient
+    if (lf.table) {
+      for (int k = 1; k <= L; ++k) sd.part_off[k] = sd.part_off[k - 1] + (int)(((long)B * h->N[k] + TSD_CHUNK - 1) / TSD_CHUNK);
+      sd.part = reinterpret_cast<double*>(t.arena.alloc((size_t)sd.part_off[L] * 65 * 2));      // (fp64 partials; the arena hands out 256-byte aligned blocks)
+    }
+    const bool dense = lf.table != nullptr;
+    const dim3 dgrid((unsigned)((nmax + TSD_CHUNK - 1) / TSD_CHUNK), (unsigned)L);
+    t.tape.push_back([sm, sd, grid, dgrid, dense, L, st]() {
       hipLaunchKernelGGL(k_tscore_bwd, grid, dim3(256), 0, st, sm);
-      hipLaunchKernelGGL(k_tscore_bwd_w, dim3(1), dim3(64), 0, st, sm, L);
+      if (dense) {
+        hipLaunchKernelGGL(k_tscore_bwd_w_dense, dgrid, dim3(256), 0, st, sm, sd);
+        hipLaunchKernelGGL(k_tscore_reduce_dense, dim3(1), dim3(128), 0, st, sm, sd, L);
+      } else {
+        hipLaunchKernelGGL(k_tscore_bwd_w, dim3(1), dim3(64), 0, st, sm, L);
+      }
     });
   }
   if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
   if (scores_padded) HIPCHK(hipMemcpyAsync(scores_padded, d_scores, (size_t)B * R * 4, hipMemcpyDeviceToDevice, st));
-  TLoss la{d_scores, d_ds, d_kw, d_imp, t.d_loss.get(), R, t.d_sel.get(), in->mask, status};
-  hipLaunchKernelGGL(k_tloss, dim3(B), dim3(256), 0, st, la);
+  if (lf.table) {
+    TLossTable la{d_scores, in->mask, lf.table, d_ds, t.d_loss.get(), lf.report_i, lf.regret, status, R, lf.margin};
+    hipLaunchKernelGGL(k_tloss_table, dim3(B), dim3(256), 0, st, la);
+  } else {
+    TLoss la{d_scores, d_ds, lf.d_kw, lf.d_imp, t.d_loss.get(), R, t.d_sel.get(), in->mask, status};
+    hipLaunchKernelGGL(k_tloss, dim3(B), dim3(256), 0, st, la);
+  }
   // ---- backward: the tape in reverse ----
   t.wops.clear();
+  t.wide_reduce = lf.table != nullptr;
   for (auto it = t.tape.rbegin(); it != t.tape.rend(); ++it) (*it)();
   t.tape.clear();
   if (t.weight_grads()) return fail(GNNB_E_HIP, "%s: the weight-gradient launches failed", who);
@@ -2718,20 +2743,17 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   HIPCHK(t.d_kw.grow(B));
   HIPCHK(hipMemcpyAsync(t.d_kw.get(), kw_index, (size_t)B * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(t.d_imp.get(), improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  return online_step_device(h, in, B, t.d_kw.get(), t.d_imp.get(), loss, nullptr, scores_padded, nullptr, apply, st, false, who);
+  StepLoss lf;
+  lf.d_kw = t.d_kw.get(); lf.d_imp = t.d_imp.get();
+  return online_step_device(h, in, B, lf, loss, nullptr, scores_padded, nullptr, apply, st, false, who);
 }
 
-// gnnb_online_step on the rows rows[0..n) of the K-row device batch `in`, in list order, nothing crossing the link: k_trows_gather copies
-// the listed rows of every tensor the step reads into dense n-row buffers out of the trainer's arena, then online_step_device runs at B = n
-// on them.  Synchronises where gnnb_online_step does.
-extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index,
-                                     const float* improvement, float* loss, int32_t* status, int apply, void* stream) {
+// The body gnnb_online_step_rows and gnnb_imitation_step_rows share behind their checks: the gather, then online_step_device under `lf`.
+// lf.table is the (K, R) table of the SOURCE batch: its listed rows are gathered with the other tensors (a fp64 row is 2 R floats to
+// k_trows_gather), and the step reads the gathered copy.
+static int step_rows_device(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, StepLoss lf, float* loss, int32_t* status, int apply,
+                            void* stream, const char* who) {
   using namespace gnnb_train;
-  const char* who = "gnnb_online_step_rows";
-  if (K < 1 || n < 1 || n > K) return fail(GNNB_E_INVALID, "%s: n = %d rows of a batch of K = %d (1 <= n <= K)", who, n, K);
-  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
-  if (!in || !rows || !kw_index || !improvement) return fail(GNNB_E_INVALID, "%s: null argument", who);
-  if (int rc = online_preflight(h, in, K, who)) return rc;
   const int NG = (int)h->N.size(), L = NG - 2, R = h->R;
   Trainer& t = *h->trainer;
   hipStream_t st = (hipStream_t)stream;
@@ -2757,9 +2779,61 @@ extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, con
   dn.x_lp = dense(in->x_lp, h->N[0]); dn.prop_w = dense(in->prop_w, h->N[L]); dn.prop_b = dense(in->prop_b, 1);
   g.mask_t = g.nt;
   dn.mask = dense(in->mask, R);
+  if (lf.table) lf.table = reinterpret_cast<const double*>(dense(reinterpret_cast<const float*>(lf.table), 2L * R));
   if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
   Launcher run{h, st};
   run.run(PC_TROWS_GATHER, [&] { hipLaunchKernelGGL(k_trows_gather, dim3(n, TG_SPLIT), dim3(TG_THREADS), 0, st, g); });
   if (run.rc) return run.rc;
-  return online_step_device(h, &dn, n, kw_index, improvement, nullptr, loss, nullptr, status, apply, st, true, who);
+  return online_step_device(h, &dn, n, lf, nullptr, loss, nullptr, status, apply, st, true, who);
+}
+
+// gnnb_online_step on the rows rows[0..n) of the K-row device batch `in`, in list order, nothing crossing the link: k_trows_gather copies
+// the listed rows of every tensor the step reads into dense n-row buffers out of the trainer's arena, then online_step_device runs at B = n
+// on them.  Synchronises where gnnb_online_step does.
+extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index,
+                                     const float* improvement, float* loss, int32_t* status, int apply, void* stream) {
+  const char* who = "gnnb_online_step_rows";
+  if (K < 1 || n < 1 || n > K) return fail(GNNB_E_INVALID, "%s: n = %d rows of a batch of K = %d (1 <= n <= K)", who, n, K);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!in || !rows || !kw_index || !improvement) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (int rc = online_preflight(h, in, K, who)) return rc;
+  StepLoss lf;
+  lf.d_kw = kw_index; lf.d_imp = improvement;
+  return step_rows_device(h, in, K, rows, n, lf, loss, status, apply, stream, who);
+}
+
+// ---- the imitation step: gnnb_online_step_rows under the table loss of k_tloss_table ----
+// table (DEVICE, (K, R) fp64, row = batch row): what gnnb_strong_pick leaves, NaN where a node is no candidate.  loss (n) fp32, report_i
+// (n, 4) int32 [teacher, pick, n_cand, n_viol], regret (n) fp64 and status (int32[1], zeroed by the caller) are DEVICE memory and may be
+// NULL.  Synchronises where gnnb_online_step_rows does.
+extern "C" int gnnb_imitation_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const double* table, double margin,
+                                        float* loss, int32_t* report_i, double* regret, int32_t* status, int apply, void* stream) {
+  const char* who = "gnnb_imitation_step_rows";
+  if (K < 1 || n < 1 || n > K) return fail(GNNB_E_INVALID, "%s: n = %d rows of a batch of K = %d (1 <= n <= K)", who, n, K);
+  if (!(margin >= 0.0)) return fail(GNNB_E_INVALID, "%s: margin = %g (a number >= 0)", who, margin);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!in || !rows || !table) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (int rc = online_preflight(h, in, K, who)) return rc;
+  StepLoss lf;
+  lf.table = table; lf.margin = margin; lf.report_i = report_i; lf.regret = regret;
+  return step_rows_device(h, in, K, rows, n, lf, loss, status, apply, stream, who);
+}
+
+// k_tloss_table alone on caller-owned DEVICE arrays (an inspection hook, as gnnb_strong_pick's table is): scores, mask (n, R) fp32, table
+// (n, R) fp64, ds (n, R) fp32 zeroed by the caller; loss, report_i, regret, status as above (may be NULL).  Needs a bound handle (for R)
+// and no trainer.  Does not synchronise.
+extern "C" int gnnb_imitation_loss(gnnb_t* h, const float* scores, const float* mask, const double* table, int n, double margin, float* loss,
+                                   float* ds, int32_t* report_i, double* regret, int32_t* status, void* stream) {
+  const char* who = "gnnb_imitation_loss";
+  if (n < 1) return fail(GNNB_E_INVALID, "%s: n = %d rows (>= 1)", who, n);
+  if (!(margin >= 0.0)) return fail(GNNB_E_INVALID, "%s: margin = %g (a number >= 0)", who, margin);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!scores || !mask || !table || !ds) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (!h->bound) return fail(GNNB_E_STATE, "%s: call gnnb_bind_network first", who);
+  hipStream_t st = (hipStream_t)stream;
+  gnnb_train::TLossTable la{scores, mask, table, ds, loss, report_i, regret, status, h->R, margin};
+  hipLaunchKernelGGL(gnnb_train::k_tloss_table, dim3(n), dim3(256), 0, st, la);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GNNB_E_HIP, "%s: the launch failed: %s", who, hipGetErrorString(e));
+  return GNNB_OK;
 }

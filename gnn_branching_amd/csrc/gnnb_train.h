@@ -20,6 +20,10 @@
 // gnnb_online_step_rows runs the same step on listed rows of a K-row device batch: k_trows_gather copies them into dense buffers out of
 // the arena, and the tape behind is the one above at B = n.
 //
+// gnnb_imitation_step_rows is the same step under another loss: k_tloss_table, a ranking hinge over a row of a
+// strong-branching table, takes k_tloss's place; its ds is dense, so the fscore weight gradient comes from k_tscore_bwd_w_dense and the
+// chunk partials of every other weight gradient are reduced in fp64 (k_tlin_reduce_all_wide).  The online step's kernels are untouched.
+//
 // Included by gnnb.hip (one translation unit: it uses the bound network of gnnb_handle) behind gnnb_mem.h, whose owners hold its memory.
 #pragma once
 #include <functional>
@@ -456,6 +460,27 @@ __global__ void k_tlin_reduce_all(const TLin* ops, int nops) {
   }
 }
 
+// The same reduction for the imitation step (k_tloss_table's ds): there a sample's rows carry +1 per violator and minus their number at the
+// teacher, so the chunk partials and the ops of a layer are large numbers that cancel, and adding them up in fp32 costs several ulp of
+// the result (measured on fnode.bias: 9 ulp, the partials of three ReLU layers cancelling).  Here the chunks of an
+// op and the ops of a layer, in the same fixed order, are added in fp64 and rounded once into gW / gb (zero before: one writer per entry).
+// The online step keeps k_tlin_reduce_all and its bits.
+__global__ void k_tlin_reduce_all_wide(const TLin* ops, int nops) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x, layer = blockIdx.y;
+  double tot = 0.0;
+  float* dst = nullptr;
+  for (int q = 0; q < nops; ++q) {
+    if (ops[q].layer != layer) continue;
+    const TLin a = ops[q];
+    if (o >= 64 * (a.K + 1)) return;
+    const int nch = (int)((tl_rows(a) + TL_CHUNK - 1) / TL_CHUNK);
+    for (int ch = 0; ch < nch; ++ch) tot += (double)a.part[(long)ch * 64 * (a.K + 1) + o];
+    const int cq = o / (a.K + 1), col = o - cq * (a.K + 1);
+    dst = col < a.K ? a.gW + cq * a.K + col : a.gb + cq;
+  }
+  if (dst) *dst += (float)tot;
+}
+
 // ordered list of the rows with a non-zero flag, and their number: one workgroup
 struct TCompact { const float* flag; int* idx; int* cnt; long n; };
 struct TCompactMulti { TCompact a[2 * T_MAXL]; };      // one workgroup per list: blockIdx.x = list
@@ -645,7 +670,7 @@ __global__ __launch_bounds__(256) void k_tscore_fwd(TScoreMulti m) {
   const long f = (row / a.N) * a.R + a.off + row % a.N;
   if (lane == 0) a.scores[f] = a.mask[f] != 0.0f ? v + a.b[0] : -INFINITY;
 }
-__global__ __launch_bounds__(256) void k_tscore_bwd(TScoreMulti m) {        // gh = ds w^T  (ds is zero except at <= 2 nodes per sample)
+__global__ __launch_bounds__(256) void k_tscore_bwd(TScoreMulti m) {        // gh = ds w^T  (ds is dense: any number of non-zero entries per sample)
   const TScore& a = m.a[blockIdx.y];
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -715,6 +740,142 @@ __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
   }
 }
 
+// ---- the imitation loss: a margin-rescaled ranking hinge over one row of a strong-branching table ----
+// tau = the sample's table row (fp64, NaN: not a candidate -- what gnnb_strong_pick writes), C = its candidates in ascending flat index,
+// t = arg-max of tau over C on (value descending, index ascending) -- the teacher, gnnb_strong_pick's own decision.  For q in C, q != t:
+//   delta_q = (float)(margin * (tau[t] - tau[q]))  (fp64 product, rounded once);  term_q = (s[q] - s[t]) + delta_q  (fp32);  violator iff term_q > 0
+//   loss = (float) sum over the violators of (double) term_q;  ds[q] += 1 per violator;  ds[t] -= the number of violators.
+// The sum runs in a fixed order (a thread's strided slice in ascending index, then the 256 slices in a tree), so a run repeats bit for bit.
+// A candidate at a node whose mask entry is 0, or with tau = +-inf, refuses the sample: loss = NaN, no ds entry, bit 3 (value 8) of
+// *status, as k_tloss refuses a bad kw_index.  No candidate at all: loss = NaN, no ds entry and no status bit (a parent without
+// candidates).  One candidate: loss = 0, no ds entry.  report (4 per sample): teacher, pick (the arg-max of s over C, value descending,
+// index ascending), |C|, violators; regret = tau[teacher] - tau[pick]; a refused or empty sample reports -1, -1, 0, 0, NaN.
+// loss, report, regret and status may be null.  One workgroup per sample, any R (strided).
+struct TLossTable {
+  const float* scores; const float* mask; const double* table; float* ds; float* loss; int* report; double* regret; int* status;
+  int R; double margin;
+};
+__global__ __launch_bounds__(256) void k_tloss_table(TLossTable a) {
+  __shared__ double s_tv[256];      // teacher: tau, then the partial sums of the terms
+  __shared__ int s_ti[256];
+  __shared__ float s_pv[256];       // pick: score
+  __shared__ int s_pi[256];
+  __shared__ int s_cnt[256];        // candidates, then violators
+  __shared__ int s_bad[256];
+  const int b = blockIdx.x, tid = threadIdx.x, R = a.R;
+  const float* s = a.scores + (long)b * R;
+  const float* mk = a.mask + (long)b * R;
+  const double* tau = a.table + (long)b * R;
+  const int none = 0x7fffffff;
+  double tv = 0.0; int ti = none;
+  float pv = 0.0f; int pi = none;
+  int cnt = 0, bad = 0;
+  for (int i = tid; i < R; i += 256) {
+    const double v = tau[i];
+    if (v != v) continue;
+    ++cnt;
+    if (mk[i] == 0.0f || v - v != 0.0) { bad = 1; continue; }
+    if (ti == none || v > tv) { tv = v; ti = i; }         // first maximum of an ascending strided slice
+    const float sc = s[i];
+    if (pi == none || sc > pv) { pv = sc; pi = i; }
+  }
+  s_tv[tid] = tv; s_ti[tid] = ti; s_pv[tid] = pv; s_pi[tid] = pi; s_cnt[tid] = cnt; s_bad[tid] = bad;
+  __syncthreads();
+  for (int o = 128; o; o >>= 1) {
+    if (tid < o) {
+      const int j = s_ti[tid + o];
+      if (j != none && (s_ti[tid] == none || s_tv[tid + o] > s_tv[tid] || (s_tv[tid + o] == s_tv[tid] && j < s_ti[tid]))) {
+        s_tv[tid] = s_tv[tid + o]; s_ti[tid] = j;
+      }
+      const int q = s_pi[tid + o];
+      if (q != none && (s_pi[tid] == none || s_pv[tid + o] > s_pv[tid] || (s_pv[tid + o] == s_pv[tid] && q < s_pi[tid]))) {
+        s_pv[tid] = s_pv[tid + o]; s_pi[tid] = q;
+      }
+      s_cnt[tid] += s_cnt[tid + o];
+      s_bad[tid] |= s_bad[tid + o];
+    }
+    __syncthreads();
+  }
+  const int t = s_ti[0], pick = s_pi[0], ncand = s_cnt[0], refused = s_bad[0];
+  const double tt = s_tv[0];
+  __syncthreads();                             // everybody holds the result before the arrays are reused
+  if (refused || ncand == 0) {
+    if (tid == 0) {
+      if (a.loss) a.loss[b] = NAN;
+      if (a.report) { int* r = a.report + 4 * b; r[0] = -1; r[1] = -1; r[2] = 0; r[3] = 0; }
+      if (a.regret) a.regret[b] = (double)NAN;
+      if (refused && a.status) *a.status = *a.status | 8;      // (every writer of a launch stores the same bit: no atomic needed)
+    }
+    return;
+  }
+  const float st = s[t];
+  float* ds = a.ds + (long)b * R;
+  double sum = 0.0; int nv = 0;
+  for (int i = tid; i < R; i += 256) {
+    const double v = tau[i];
+    if (v != v || i == t) continue;
+    const float delta = (float)(a.margin * (tt - v));
+    const float term = (s[i] - st) + delta;
+    if (term > 0.0f) { sum += (double)term; ++nv; ds[i] += 1.0f; }
+  }
+  s_tv[tid] = sum; s_cnt[tid] = nv;
+  __syncthreads();
+  for (int o = 128; o; o >>= 1) {
+    if (tid < o) { s_tv[tid] += s_tv[tid + o]; s_cnt[tid] += s_cnt[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int v = s_cnt[0];
+    if (v) ds[t] -= (float)v;
+    if (a.loss) a.loss[b] = (float)s_tv[0];
+    if (a.report) { int* r = a.report + 4 * b; r[0] = t; r[1] = pick; r[2] = ncand; r[3] = v; }
+    if (a.regret) a.regret[b] = tt - tau[pick];
+  }
+}
+
+// d loss / d fscore for a dense ds (the imitation loss: any number of entries per sample; k_tscore_bwd_w serves the two-node loss only).
+// Per ReLU layer gw[lane] += sum_b sum_node ds h[row][lane], gb += sum ds, in an order the launch cannot change: the rows of a layer in
+// chunks of TSD_CHUNK, a chunk's four 64-row quarters each walked in row order by one wave and added in wave order into
+// part[chunk][0..63] (gw) and part[chunk][64] (gb); k_tscore_reduce_dense then adds the chunks in order, last layer first as
+// k_tscore_bwd_w adds its layers.  A row whose ds is zero is skipped (it adds +-0).  blockIdx.y = layer, part_off[l] = first chunk of it.
+// The sums run in fp64 and are rounded once, into gw / gb: ds holds +1 per violator and minus their number at the teacher, large
+// partial sums that cancel (see k_tlin_reduce_all_wide).
+#define TSD_CHUNK 256
+struct TScoreDense { double* part; int part_off[T_MAXL + 1]; };
+__global__ __launch_bounds__(256) void k_tscore_bwd_w_dense(TScoreMulti m, TScoreDense p) {
+  __shared__ double red[4][65];
+  const TScore& a = m.a[blockIdx.y];
+  const long row0 = (long)blockIdx.x * TSD_CHUNK;
+  if (row0 >= a.n) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double gw = 0.0, gb = 0.0;
+  for (int r = 0; r < 64; ++r) {
+    const long row = row0 + 64 * wave + r;
+    if (row >= a.n) break;
+    const float d = a.ds[(row / a.N) * a.R + a.off + row % a.N];       // (wave-uniform)
+    if (d == 0.0f) continue;
+    gw += (double)d * (double)a.h[row * 64 + lane];
+    gb += (double)d;
+  }
+  red[wave][lane] = gw;
+  if (lane == 0) red[wave][64] = gb;
+  __syncthreads();
+  if (threadIdx.x < 65) {
+    const int c = threadIdx.x;
+    p.part[((long)p.part_off[blockIdx.y] + blockIdx.x) * 65 + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+  }
+}
+__global__ __launch_bounds__(128) void k_tscore_reduce_dense(TScoreMulti m, TScoreDense p, int nlayers) {
+  const int c = threadIdx.x;
+  if (c >= 65) return;
+  double tot = 0.0;
+  for (int l = nlayers - 1; l >= 0; --l)
+    for (int ch = p.part_off[l]; ch < p.part_off[l + 1]; ++ch) tot += p.part[(long)ch * 65 + c];
+  const TScore& a = m.a[0];                    // (every layer's gw / gb is fscore's)
+  if (c < 64) a.gw[c] += (float)tot;
+  else a.gb[0] += (float)tot;
+}
+
 // ---- the listed rows of a K-row device batch as a dense n-row batch (gnnb_online_step_rows) ----
 // Row i of every destination = row rows[i] of its source, for every tensor the step reads; a row is spread over the TG_SPLIT workgroups
 // of blockIdx.y (as fr_copy_row of gnnb_k_frontier.h spreads a domain's row), 16-byte copies where both sides allow them.  A rows entry
@@ -723,7 +884,7 @@ __global__ __launch_bounds__(256) void k_tloss(TLoss a) {
 // 0 / 0 into k_tprep's slopes and NaN into every weight gradient) -- and bit 3 (value 8) of *status (may be null) is set.
 #define TG_THREADS 256
 #define TG_SPLIT 8
-#define TG_MAXT (5 * T_MAXL + 12)
+#define TG_MAXT (5 * T_MAXL + 12)      // (gnnb_imitation_step_rows adds the table row: 5 L + 10 tensors at most)
 struct TGatherT { const float* src; float* dst; int w; };     // w: floats per row
 struct TGather { TGatherT t[TG_MAXT]; int nt, K, mask_t; const int* rows; int* status; };      // mask_t: the entry of t that is the mask
 static_assert(sizeof(TGather) <= 4096, "kernel arguments: 4 KiB");
@@ -916,6 +1077,7 @@ struct Trainer {
   }
   // the weight gradients of every recorded op: two launches behind the backward walk
   std::vector<int> h_first;
+  bool wide_reduce = false;              // the imitation step: k_tlin_reduce_all_wide
   int weight_grads() {
     const int nops = (int)wops.size();
     if (!nops) return 0;
@@ -928,7 +1090,8 @@ struct Trainer {
     if (hipMemcpyAsync(d_ops, wops.data(), sizeof(TLin) * nops, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
     if (hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (nops + 1), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
     hipLaunchKernelGGL(k_tlin_bwd_w_all, dim3((unsigned)h_first[nops], 3), dim3(256), 0, st, d_ops, d_first, nops);
-    hipLaunchKernelGGL(k_tlin_reduce_all, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
+    if (wide_reduce) hipLaunchKernelGGL(k_tlin_reduce_all_wide, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
+    else hipLaunchKernelGGL(k_tlin_reduce_all, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
     return 0;
   }
   static TSeg seg(const TT& t, const float* s = nullptr, bool full = false) { return TSeg{t.v, s, t.g, full ? 1 : 0}; }

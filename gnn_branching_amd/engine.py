@@ -791,8 +791,79 @@ class ScorerEngine:
                    None if loss is None else self._rows(loss, n, 1, f32, "loss").data_ptr(),
                    None if status is None else self._rows(status, 1, 1, i32, "status").data_ptr(), 1 if apply else 0)
 
+    # ---- the imitation step ----------------------------------------------
+    @staticmethod
+    def _margin(margin, what):
+        if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) or not float(margin) >= 0.0:
+            raise ValueError(f"{what}: margin = {margin!r} (a real number >= 0)")
+        return float(margin)
+
+    def imitation_step_rows(self, batch, K, rows, table, margin=1.0, loss=None, report=None, regret=None, status=None, apply=True):
+        """gnnb_imitation_step_rows on the current stream: ``online_step_rows`` under the table loss (include/gnnb.h states the rule).
+        rows (n,) int32 and table (K, R) fp64 (row = batch row, NaN: not a candidate -- what ``strong_pick`` leaves in ``table``) are
+        device tensors; loss (n,) fp32, report (n, 4) int32 [teacher, pick, n_cand, n_viol], regret (n,) fp64 and status (1,) int32
+        (zeroed by the caller; bit 3: a refused row) are None or device tensors that receive them.  Synchronises the stream, as
+        ``online_step_rows`` does."""
+        if not getattr(self, "_online", False):
+            raise RuntimeError("imitation_step_rows: call online_create first")
+        margin = self._margin(margin, "imitation_step_rows")
+        n, i32, f32, f64 = int(rows.numel()), torch.int32, torch.float32, torch.float64
+        self._call("gnnb_imitation_step_rows", C.byref(batch), int(K), self._rows(rows, n, 1, i32, "rows").data_ptr(), n,
+                   self._rows(table, int(K), self.R, f64, "table").data_ptr(), margin,
+                   None if loss is None else self._rows(loss, n, 1, f32, "loss").data_ptr(),
+                   None if report is None else self._rows(report, n, 4, i32, "report").data_ptr(),
+                   None if regret is None else self._rows(regret, n, 1, f64, "regret").data_ptr(),
+                   None if status is None else self._rows(status, 1, 1, i32, "status").data_ptr(), 1 if apply else 0)
+
+    def imitation_step(self, args, table, margin=1.0, apply=True):
+        """One imitation step on the batch ``args`` (the argument tuple of GraphNet.forward) and its (B, R) table (host or device, any
+        float type; NaN: not a candidate): marshals and calls ``imitation_step_rows`` with rows = arange(B).  Returns (loss (B,) fp32,
+        report (B, 4) int32, regret (B,) fp64) as numpy; raises IndexError when a row was refused (a candidate at a decided node, or an
+        infinite table entry)."""
+        if not getattr(self, "_online", False):
+            raise RuntimeError("imitation_step: call online_create first")
+        margin = self._margin(margin, "imitation_step")
+        m = self._marshal(*args)
+        B, dev = m.B, self.device
+        tab = torch.as_tensor(table).to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if tab.numel() != B * self.R:
+            raise ValueError(f"imitation_step: a table of {tab.numel()} values for a batch of {B} x {self.R} ReLU nodes")
+        rows = torch.arange(B, dtype=torch.int32, device=dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        report = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        regret = torch.empty(B, dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        batch, keep = make_batch(m.lbs, m.ubs, m.duals, m.prim, m.x_lp, m.mask, m.pw, m.pb)
+        self.imitation_step_rows(batch, B, rows, tab, margin, loss, report, regret, status, apply)
+        if int(status.cpu()[0]) & 8:
+            raise IndexError("imitation_step: a table row names a candidate that is no undecided ReLU of its mask, or holds an infinite entry")
+        return loss.cpu().numpy(), report.cpu().numpy(), regret.cpu().numpy()
+
+    def imitation_loss(self, scores, mask, table, margin=1.0, ds=None, loss=None, report=None, regret=None, status=None):
+        """gnnb_imitation_loss on the current stream: the loss rule alone on caller-owned device tensors (an inspection hook).  scores,
+        mask (n, R) fp32; table (n, R) fp64; ds None (a zeroed one is made) or (n, R) fp32, which receives d loss / d scores on top of
+        what it holds; loss (n,) fp32, report (n, 4) int32, regret (n,) fp64, status (1,) int32: None (made here, status zeroed) or
+        given.  Needs a bound network and no trainer.  Returns (loss, ds, report, regret, status) as device tensors; no synchronisation."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        margin = self._margin(margin, "imitation_loss")
+        R, dev, i32, f32, f64 = self.R, self.device, torch.int32, torch.float32, torch.float64
+        if not torch.is_tensor(scores) or scores.numel() % R or scores.numel() == 0:
+            raise ValueError(f"imitation_loss: scores must hold n x {R} values")
+        n = scores.numel() // R
+        ds = torch.zeros(n, R, dtype=f32, device=dev) if ds is None else ds
+        loss = torch.empty(n, dtype=f32, device=dev) if loss is None else loss
+        report = torch.empty(n, 4, dtype=i32, device=dev) if report is None else report
+        regret = torch.empty(n, dtype=f64, device=dev) if regret is None else regret
+        status = torch.zeros(1, dtype=i32, device=dev) if status is None else status
+        self._call("gnnb_imitation_loss", self._rows(scores, n, R, f32, "scores").data_ptr(), self._rows(mask, n, R, f32, "mask").data_ptr(),
+                   self._rows(table, n, R, f64, "table").data_ptr(), n, margin, self._rows(loss, n, 1, f32, "loss").data_ptr(),
+                   self._rows(ds, n, R, f32, "ds").data_ptr(), self._rows(report, n, 4, i32, "report").data_ptr(),
+                   self._rows(regret, n, 1, f64, "regret").data_ptr(), self._rows(status, 1, 1, i32, "status").data_ptr())
+        return loss, ds, report, regret, status
+
     def online_grad(self):
-        """d loss / d parameters of the last online_step, flat float32 array in checkpoint order."""
+        """d loss / d parameters of the last online_step or imitation step, flat float32 array in checkpoint order."""
         out = np.empty(GNN_BLOB_FLOATS, dtype=np.float32)
         _lib.check(self.lib.gnnb_online_grad(self.h, out.ctypes.data_as(C.c_void_p), out.size), "gnnb_online_grad")
         return out

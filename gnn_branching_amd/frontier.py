@@ -26,6 +26,10 @@ intercept counter carried through the run (per job), and the GNN is never run.
 both children of every candidate split of every parent are bounded in chunks (``gnnb_strong_list``, then ``gnnb_frontier_expand``,
 ``gnnb_kw_bounds`` and ``gnnb_dual_ascent`` per chunk) and every parent is split where its bound improves most (``gnnb_strong_pick``);
 ``strong_audit=[]`` computes the same table next to a "gnn" or "babsr" run and records how far the committed decision is from the best.
+
+``branch_and_bound_frontier(..., imitate=N)`` connects the two: every N-th round leaves its table in device memory
+and, behind the commit, takes one Adam step of the GNN on it (``gnnb_imitation_step_rows``), so a "gnn" or "strong" run labels its own
+states with the teacher and learns from them without the table, the scorer inputs or the gradient crossing the link.
 """
 import ctypes as C
 import math
@@ -205,6 +209,28 @@ def _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
         raise TypeError(f"online_threshold needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
 
 
+IMITATE_MARGIN_DEFAULT = 1.0
+
+
+def _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice):
+    """The imitation options of DESIGN.md section 7.12 (None: off), before a device is touched."""
+    if imitate is not None and (not isinstance(imitate, int) or isinstance(imitate, bool) or imitate < 1):
+        raise ValueError(f"imitate = {imitate!r}: None, or an integer N >= 1 (every N-th round learns)")
+    if isinstance(imitate_margin, bool) or not isinstance(imitate_margin, (int, float)) or not imitate_margin >= 0:
+        raise ValueError(f"imitate_margin = {imitate_margin!r}: a real number >= 0")
+    if imitate is None:
+        if imitate_margin != IMITATE_MARGIN_DEFAULT:
+            raise ValueError(f"imitate_margin = {imitate_margin!r} without imitate: nothing would use it")
+        return
+    if branching == "babsr":
+        raise ValueError('imitate with branching="babsr": a BaBSR run never prepares the GNN\'s inputs; imitate is legal with "gnn" and "strong"')
+    if branching_threshold is not None or online_threshold is not None:
+        raise ValueError("imitate takes no branching_threshold and no online_threshold: a round learns from one loss, the table's")
+    from .graphnet.graph_score_online import GraphChoice
+    if not isinstance(choice, GraphChoice):
+        raise TypeError(f"imitate needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
+
+
 BRANCHINGS = ("gnn", "babsr", "strong")
 STRONG_CHUNK_DEFAULT = 256          # strong_chunk's default, candidates per bounding chunk: the best of 32..256 measured (DESIGN.md section 7.11)
 
@@ -221,7 +247,7 @@ def _check_branching(branching, branching_threshold, online_threshold):
                          "online_threshold, which compare the heuristic with the GNN")
 
 
-def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold):
+def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None):
     """The strong-branching options of DESIGN.md section 7.11, before a device is touched."""
     if strong_candidates is not None and (not isinstance(strong_candidates, int) or isinstance(strong_candidates, bool) or strong_candidates < 1):
         raise ValueError(f"strong_candidates = {strong_candidates!r}: None (every undecided node), or an integer >= 1")
@@ -229,11 +255,11 @@ def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, bran
         raise ValueError(f"strong_chunk = {strong_chunk!r}: an integer >= 1, the candidates per bounding chunk")
     if strong_audit is not None and not isinstance(strong_audit, list):
         raise ValueError(f"strong_audit = {strong_audit!r}: None, or a list that receives one dict per parent")
-    if branching != "strong" and strong_audit is None:
+    if branching != "strong" and strong_audit is None and imitate is None:
         if strong_candidates is not None:
-            raise ValueError(f'strong_candidates = {strong_candidates!r} without branching="strong" or a strong_audit: nothing would use it')
+            raise ValueError(f'strong_candidates = {strong_candidates!r} without branching="strong", a strong_audit or imitate: nothing would use it')
         if strong_chunk != STRONG_CHUNK_DEFAULT:
-            raise ValueError(f'strong_chunk = {strong_chunk!r} without branching="strong" or a strong_audit: nothing would use it')
+            raise ValueError(f'strong_chunk = {strong_chunk!r} without branching="strong", a strong_audit or imitate: nothing would use it')
     if strong_audit is not None and (branching_threshold is not None or online_threshold is not None):
         raise ValueError("strong_audit audits the one decision a round commits per parent: it takes no branching_threshold and no online_threshold")
 
@@ -272,12 +298,13 @@ class _Round:
     restarts, pgd_seed = 0, 0
     branching = "gnn"
     strong_on, strong_M, strong_chunk, strong_audit = False, 0, STRONG_CHUNK_DEFAULT, None
+    imitate, learning, im_table = None, False, None
 
-    def _strong_options(self, strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold):
+    def _strong_options(self, strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None):
         """The options of DESIGN.md section 7.11, checked; set before the rows are made (``_buffers`` sizes the workspaces by them).
-        ``strong_on`` False: nothing of a round differs."""
-        _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold)
-        self.strong_on = branching == "strong" or strong_audit is not None
+        ``strong_on`` False: nothing of a round differs.  ``imitate`` (section 7.12) needs the table too."""
+        _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate)
+        self.strong_on = branching == "strong" or strong_audit is not None or imitate is not None
         self.strong_M, self.strong_chunk, self.strong_audit = strong_candidates or 0, strong_chunk, strong_audit
 
     def _restart_options(self, pgd_restarts, pgd_seed):
@@ -383,12 +410,12 @@ class _Round:
         """cand0[n], the number of candidates of a round of n parents: the 4 bytes a strong round reads between the list and its chunks."""
         return int(self.cand0[n:n + 1].cpu()[0])
 
-    def _strong_table(self, slots, n, dec):
+    def _strong_table(self, slots, n, dec, table=None):
         """Steps 2-6 of a strong round over the n parent rows the gather wrote: gnnb_babsr for the pre-filter (with
         ``strong_candidates``), gnnb_strong_list, the read of the number of candidates, per chunk of ``strong_chunk`` candidates
         gnnb_frontier_expand into ``ChS``, gnnb_kw_bounds and gnnb_dual_ascent (no scorer inputs, no LP point; live, infeasible and bound go
-        to the run-long arrays at the chunk's offset), and gnnb_strong_pick into ``dec`` ((n, 2) int32).  No gnnb_net_eval, no PGD, no
-        witness: a candidate is only ever a lower bound."""
+        to the run-long arrays at the chunk's offset), and gnnb_strong_pick into ``dec`` ((n, 2) int32) and, on a learning round (section
+        7.12), into ``table`` ((n, R) fp64).  No gnnb_net_eval, no PGD, no witness: a candidate is only ever a lower bound."""
         P, S, eng, pool, lib, h = self.P, self.ChS, self.eng, self.pool, self.lib, self.eng.h
         if self.strong_M:
             eng.babsr_rows(P.lb32, P.ub32, P.box[2], P.amb, n, self.s_scores, self.s_icp)
@@ -406,12 +433,16 @@ class _Round:
                                                 self.s_bound[2 * q0:].data_ptr(), None, None, None, None, None, None, self.ws_dual.data_ptr(),
                                                 self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
         self.strong_bounded += 2 * n_c
-        eng.strong_pick(pool, slots, self.cand0, self.cand_dec, n_c, self.s_live, self.s_infeasible, self.s_bound, dec, self.s_best, self.s_imp)
+        eng.strong_pick(pool, slots, self.cand0, self.cand_dec, n_c, self.s_live, self.s_infeasible, self.s_bound, dec, self.s_best, self.s_imp, table)
 
     def _strong_parents(self, n):
         """``branching="strong"`` in ``_score_parents``' place: the table of the n parent rows the gather wrote and
-        its arg-max per row into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward."""
-        self._strong_table(self.slots, n, self.P.dec)
+        its arg-max per row into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward.  A learning round (section 7.12) keeps the
+        table and then runs gnnb_dual_ascent at n_iter = 0 on the parent rows, so that the scorer inputs the step reads exist; still no
+        gnnb_forward."""
+        self._strong_table(self.slots, n, self.P.dec, self.im_table if self.learning else None)
+        if self.learning:
+            self._scorer_inputs(n)
 
     def _bound_children(self, Ch, B, warm):
         """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
@@ -445,14 +476,20 @@ class _Round:
             return {}
         return {"x_b": self._ub_points(self.ChB), "used_kw": self.used_kw, "sel_rows": self.sel_rows}
 
-    def _score_parents(self, B):
-        """gnnb_dual_ascent at n_iter = 0 (the scorer's inputs at the stored best point: one evaluation of g instead of ~120 KB of fp32
-        inputs per open domain) and gnnb_forward over the first B parent rows."""
+    def _scorer_inputs(self, B):
+        """gnnb_dual_ascent at n_iter = 0 over the first B parent rows: the scorer's inputs at the stored best point (one evaluation of g
+        instead of ~120 KB of fp32 inputs per open domain)."""
         P, lib, h = self.P, self.lib, self.eng.h
         with torch.cuda.device(self.eng.device):
             _lib.check(lib.gnnb_dual_ascent(h, C.byref(P.dual_batch), B, 0, self.lr, P.alpha.data_ptr(), P.beta.data_ptr(), 1, P.bound.data_ptr(), None, None,
                                             P.t_dual, P.t_prims, P.x_lp.data_ptr(), P.lb32[-1].data_ptr(), self.ws_dual.data_ptr(), self.ws_dual.numel(),
                                             self._stream()), "gnnb_dual_ascent")
+
+    def _score_parents(self, B):
+        """``_scorer_inputs`` and gnnb_forward over the first B parent rows."""
+        P, lib, h = self.P, self.lib, self.eng.h
+        self._scorer_inputs(B)
+        with torch.cuda.device(self.eng.device):
             _lib.check(lib.gnnb_forward(h, C.byref(P.fwd_batch), B, P.scores.data_ptr(), P.dec.data_ptr(), self.status.data_ptr(), self.ws_fwd.data_ptr(),
                                         self.ws_fwd.numel(), self._stream()), "gnnb_forward")
         self.status_all |= self.status
@@ -477,8 +514,8 @@ class _Round:
                 self._babsr_parents(n)
             if self.keep_pairs:                                   # (a traced run: "parent_bounds", which gnnb_dual_ascent at n_iter 0 would have left)
                 P.bound[:n] = pool.bound[slots[:n].long().clamp(min=0)]
-        if self.strong_audit is not None and self.branching != "strong":      # the same table next to the round's own decisions (P.dec untouched)
-            self._strong_table(slots, n, self.s_dec)
+        if (self.strong_audit is not None or self.learning) and self.branching != "strong":      # the same table next to the round's own decisions (P.dec untouched)
+            self._strong_table(slots, n, self.s_dec, self.im_table if self.learning else None)
         if self.strong_on and (self.keep_pairs or self.strong_audit is not None):      # (a traced or audited run: the bounds the commit overwrites)
             self.parent_bound = pool.bound[slots[:n].long().clamp(min=0)]
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
@@ -523,16 +560,21 @@ class FrontierRun(_Round):
 
     With an ``online_threshold`` it also owns the table ``wrong`` of wrong GNN points, the dense lists of a round's
     learn rows and their number ``n_learn``; a round with m > 0 reads ``n_learn`` (4 bytes) behind the state record and, when it is not
-    zero, takes one learning step over those rows (``gnnb_online_step_rows``, which synchronises)."""
+    zero, takes one learning step over those rows (``gnnb_online_step_rows``, which synchronises).
+
+    With ``imitate`` = N every round whose 1-based number is a multiple of N is a learning round: its table stays
+    in ``im_table`` ((K, R) fp64) and, behind the state record, when the round listed a candidate, ONE ``gnnb_imitation_step_rows`` (which
+    synchronises) runs over all its parent rows."""
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
                  kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
-                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
-                 strong_audit=None, branching="gnn"):
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT,
+                 strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
+        _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice)
         _check_branching(branching, branching_threshold, online_threshold)
         self.branching = branching
-        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold)
+        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate)
         self._upper_bound_options(witness, pgd_steps, pgd_step)
         self._restart_options(pgd_restarts, pgd_seed)
         _check_threshold(branching_threshold, kwbd_threshold)
@@ -542,7 +584,7 @@ class FrontierRun(_Round):
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
         self.K, self.n_iter, self.lr, self.eps, self.decision_bound = K, n_iter, float(lr), float(eps), decision_bound
         self.fixed, self.prop_layer = layers[:-1], layers[-1]
-        eng = self.eng = choice.model.engine() if online_threshold is None else choice._eng()      # (_eng: the engine with its optimizer)
+        eng = self.eng = choice.model.engine() if online_threshold is None and imitate is None else choice._eng()      # (_eng: the engine with its optimizer)
         in_shape = tuple(lp.input_lb.shape)
         eng.bind(self.fixed, in_shape)
         dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
@@ -571,6 +613,14 @@ class FrontierRun(_Round):
             self.wrong = torch.zeros(eng.R, dtype=torch.int32, device=dev)
             self.learn_rows, self.learn_kw, self.n_learn = (torch.zeros(n, dtype=torch.int32, device=dev) for n in (K, K, 1))
             self.learn_imp, self.loss = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float32, device=dev)
+            self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.imitate, self.imitate_margin, self.round, self.learning, self.imitate_pending = imitate, float(imitate_margin), 0, False, False
+        self.imitation_steps = self.imitation_rows = self.last_imitation = 0
+        if imitate is not None:
+            self.im_table = torch.zeros(K, eng.R, dtype=torch.float64, device=dev)
+            self.im_rows = torch.arange(K, dtype=torch.int32, device=dev)
+            self.im_loss, self.im_regret = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float64, device=dev)
+            self.im_report = torch.zeros(K, 4, dtype=torch.int32, device=dev)
             self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _commit(self, slots):
@@ -602,6 +652,10 @@ class FrontierRun(_Round):
     def launch_round(self, k, in_use):
         """One round over the k <= K open domains of lowest bound.  Device work only."""
         self.slots = self.pick(k, in_use)
+        if self.imitate is not None:                              # (a learning round: its table stays, its step runs behind the state record)
+            self.round += 1
+            self.learning = self.imitate_pending = self.round % self.imitate == 0
+            self.k, self.last_imitation = k, 0
         self._launch(self.slots, k)
 
     # ``_Round._fall_back``'s steps for one job (DESIGN.md section 7.5): gnnb_frontier_fallback, the read of m, gnnb_frontier_choose
@@ -653,11 +707,30 @@ class FrontierRun(_Round):
         self.status_all |= self.step_status
         self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
 
+    def _imitate(self):
+        """The learning half of a learning round, behind the commit and the read of the state record.  When the
+        round listed a candidate -- ``strong_n``, the 4 bytes the round already read -- ONE step over ALL k parent rows on the scorer inputs
+        the round left in ``P`` (intact until the next gather), every row scored with the round's opening parameters; a row without a
+        candidate contributes nothing.  If every candidate's improvement is NaN (a dead child each) the gradient is zero and the step is
+        weight decay alone.  The next round's forward scores with the new parameters."""
+        self.imitate_pending, self.last_imitation = False, 0
+        if self.strong_n <= 0:
+            return
+        k = self.last_imitation = self.k
+        self.step_status.zero_()
+        self.eng.imitation_step_rows(self.P.fwd_batch, k, self.im_rows[:k], self.im_table, self.imitate_margin, loss=self.im_loss[:k],
+                                     report=self.im_report[:k], regret=self.im_regret[:k], status=self.step_status)
+        self.status_all |= self.step_status
+        self.imitation_steps, self.imitation_rows = self.imitation_steps + 1, self.imitation_rows + k
+
     def read_learn(self):
         """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
         return int(self.n_learn.cpu()[0])
 
     def _raise_for(self, st):
+        if st & 8 and self.imitate is not None:
+            raise RuntimeError("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
+                               "row's mask, or holds an infinite improvement")
         if st & 8:
             raise RuntimeError("gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask")
         super()._raise_for(st)
@@ -668,17 +741,21 @@ class FrontierRun(_Round):
 
     def read_state(self):
         """The state record as a list of Python floats: the one device-to-host copy of a round (of its second half, in threshold mode).
-        An online round with m > 0 then reads n_learn and takes its learning step (``_learn``)."""
+        An online round with m > 0 then reads n_learn and takes its learning step (``_learn``); a learning round of ``imitate`` takes its
+        step (``_imitate``)."""
         st = self.pool.state.cpu().tolist()
         if self.learn_pending:
             self._learn()
+        if self.imitate_pending:
+            self._imitate()
         return st
 
 
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
                               online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0,
-                              strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
+                              imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
+                              strong_audit=None, branching="gnn"):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -761,10 +838,28 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     pair), "strong_decision", "best_improvement", "candidates" (flat indices) and "improvements" -- extra device-to-host copies, like
     ``trace``'s: off in a timed run.
 
+    imitate, imitate_margin (with ``imitate`` at None no launch, read, buffer or argument of a round changes).
+    imitate: None, or an integer N >= 1: every round whose 1-based number is a multiple of N is a LEARNING round.  Legal with ``branching``
+    "gnn" and "strong" and together with ``strong_audit``, ``strong_candidates`` and ``strong_chunk``, which shape the table as they shape
+    a strong round's; not with "babsr", a ``branching_threshold`` or an ``online_threshold``.  ``choice`` must be a
+    ``graphnet.graph_score_online.GraphChoice`` (it owns lr and wd).  A learning round leaves its table -- per parent the improvement of
+    every candidate, NaN elsewhere -- in device memory: in "strong" mode the round's own, in "gnn" mode the audit's steps next to the
+    round's decisions (other rounds do not compute it unless an audit asks); in "strong" mode it also runs ``gnnb_dual_ascent`` at n_iter 0
+    on the parents, so that the scorer inputs exist, and still no ``gnnb_forward``.  Commit first, then learn: behind the read of the state
+    record, when the round listed a candidate, ONE ``gnnb_imitation_step_rows`` takes an Adam step on the summed loss of all k parent rows
+    -- a margin-rescaled ranking hinge that asks the GNN to score the table's best candidate above every other by ``imitate_margin`` times
+    the difference of their improvements (include/gnnb.h states it) -- all scored with the round's opening parameters; the next round's
+    forward uses the new ones.  A row without a candidate contributes nothing; if every candidate of the round has a NaN improvement (a
+    dead child each) the gradient is zero and the step is weight decay alone.  When the run ends (or raises) after a step ``choice.model``
+    receives the device's parameters.  stats then also holds "imitation_steps" and "imitation_rows" (the parent rows handed to the steps),
+    and a traced learning round "imitation_loss", "imitation_regret" (the table's best improvement minus that of the GNN's best candidate)
+    and "imitation_report" ([teacher, pick, candidates, violators] as flat ReLU indices and counts), one per parent row; every traced round
+    of such a run carries the bounds after it, "global_lb" and "global_ub".
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, strong_candidates, strong_chunk,
-                      strong_audit, branching)      # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, imitate, imitate_margin,
+                      strong_candidates, strong_chunk, strong_audit, branching)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
@@ -772,7 +867,7 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
             witness.append(run.witness())
         return out
     finally:
-        if run.online_steps:                                      # the nn.Module mirrors the device, as GraphChoice.online_learning leaves it
+        if run.online_steps or run.imitation_steps:               # the nn.Module mirrors the device, as GraphChoice.online_learning leaves it
             choice.model.load_blob(run.eng.get_weights())
 
 
@@ -797,7 +892,7 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
             trace.append(_trace_rows(run, 0, k))
             if branching_threshold is not None:
                 trace[-1].update(_threshold_trace(run, k))
-        if run.strong_on and (trace is not None or run.strong_audit is not None):
+        if (run.branching == "strong" and trace is not None) or run.strong_audit is not None:
             rows = _strong_rows(run, k)
             if trace is not None and run.branching == "strong":
                 trace[-1].update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
@@ -806,6 +901,12 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
         st = run.read_state()
         if trace is not None and run.online is not None:
             trace[-1].update(_online_trace(run, st))
+        if trace is not None and run.imitate is not None and run.last_imitation:
+            n = run.last_imitation
+            trace[-1].update(imitation_loss=run.im_loss[:n].cpu().tolist(), imitation_regret=run.im_regret[:n].cpu().tolist(),
+                             imitation_report=run.im_report[:n].cpu().tolist())
+        if trace is not None and run.imitate is not None:
+            trace[-1].update(global_lb=_global_lb(st), global_ub=st[S.FS_GLOBAL_UB])
         if trace is not None and run.witness_on:
             trace[-1].update(global_ub=st[S.FS_GLOBAL_UB], witness_value=float(run.best_value.cpu()[0]))
         _check_record(st)
@@ -822,6 +923,8 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
             stats.update(online_steps=run.online_steps, online_rows=run.online_rows)
         if run.strong_on:
             stats.update(strong_bounded=run.strong_bounded)
+        if run.imitate is not None:
+            stats.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows)
     return global_lb, global_ub, rounds, bounded, reason
 
 

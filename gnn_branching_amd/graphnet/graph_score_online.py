@@ -81,6 +81,20 @@ class GraphChoice:
         self.model.load_blob(eng.get_weights())                   # the nn.Module mirrors the device parameters (state_dict(), save)
         self.last_loss = float(loss[0])
 
+    def imitation_learning(self, table, margin=1.0):
+        """One step on the last decision's arguments under the imitation loss (no counterpart in the reference,
+        which holds no supervised training script).  table: R values, the bound improvement of splitting each flat ReLU index (what
+        strong branching measures), NaN where a node is not a candidate.  Leaves ``last_loss`` and ``last_regret`` (the teacher's
+        improvement minus that of the GNN's best candidate; NaN for a table without a candidate)."""
+        if self._last is None:
+            raise RuntimeError("imitation_learning: no decision to learn from (call decision first)")
+        if self.verbose:
+            print('updating the trained model')
+        eng = self._eng()
+        loss, _, regret = eng.imitation_step(self._last, torch.as_tensor(table, dtype=torch.float64).reshape(1, -1), margin)
+        self.model.load_blob(eng.get_weights())
+        self.last_loss, self.last_regret = float(loss[0]), float(regret[0])
+
     def del_score(self):                                          # :79-83
         for name in ("scores", "gnn_score", "mask_1d"):
             if hasattr(self, name):

@@ -669,7 +669,35 @@ int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_i
 int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index, const float* improvement,
                           float* loss, int32_t* status, int apply, void* stream);
 
-/* d loss / d parameters of the last gnnb_online_step or gnnb_online_step_rows (before weight decay), HOST, blob order. */
+/* ---- the imitation step: learn the scorer from a strong-branching table ----
+ * gnnb_online_step_rows under another loss.  The reference tree holds no supervised training script, so the loss is this library's own:
+ * the online loss generalised from one named node to a whole table row, a margin-rescaled ranking hinge.  Per listed row, with s the
+ * training-form scores (fp32 over the R flat ReLU indices, -inf at decided nodes), tau the row of `table` (fp64, NaN = not a
+ * candidate: exactly what gnnb_strong_pick writes into its `table`) and margin >= 0:
+ *   C = { r : tau[r] is not NaN };  t = arg-max of tau over C on (value descending, flat index ascending): the teacher;
+ *   for q in C, q != t:  delta_q = (float)(margin (tau[t] - tau[q])) (fp64 product, rounded once);  term_q = (s[q] - s[t]) + delta_q in fp32;
+ *   q is a violator iff term_q > 0;  loss = (float) sum over the violators of (double) term_q, in a fixed order;
+ *   d loss / d s[q] = +1 per violator, d loss / d s[t] = - the number of violators.
+ * A candidate whose mask entry is 0 or whose tau is +-inf refuses the row: loss = NaN, no gradient, status bit 3 (value 8).  A row without
+ * a candidate: loss = NaN, no gradient, NO status bit.  One candidate: loss = 0, no gradient.  n > 1 sums the row losses un-normalised
+ * (every d loss / d s entry is a small integer, so the gradient of fscore.bias is exactly 0).  If no row has a violator the gradient is
+ * zero and apply = 1 still takes the Adam step: weight decay alone moves the parameters.
+ * rows (n) int32, table (K, R) fp64 with row = batch row, loss (n) fp32 or NULL, report_i (n, 4) int32 or NULL = [teacher, pick, n_cand,
+ * n_viol] (pick: the arg-max of s over C, value descending, index ascending), regret (n) fp64 or NULL = tau[teacher] - tau[pick], status
+ * int32[1] zeroed by the caller or NULL: all DEVICE memory.  A refused or empty row reports -1, -1, 0, 0 and regret NaN.  Everything else --
+ * the gather, the guards on `rows`, apply, the limits, the error codes, where it synchronises -- is gnnb_online_step_rows; loss, gradient
+ * (gnnb_online_grad) and parameters are the bits of the same call on those rows given as a compact batch.  GNNB_E_INVALID also for a
+ * margin that is negative or NaN. */
+int gnnb_imitation_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const double* table, double margin,
+                             float* loss, int32_t* report_i, double* regret, int32_t* status, int apply, void* stream);
+
+/* Inspection: the loss rule above alone, on caller-owned DEVICE arrays: scores and mask (n, R) fp32, table (n, R) fp64, ds (n, R) fp32
+ * zeroed by the caller (receives d loss / d s; entries that are neither a violator nor the teacher are not written); loss, report_i,
+ * regret, status as above.  Needs a bound handle (for R) and no trainer; stream-ordered, does not synchronise. */
+int gnnb_imitation_loss(gnnb_t* h, const float* scores, const float* mask, const double* table, int n, double margin, float* loss, float* ds,
+                        int32_t* report_i, double* regret, int32_t* status, void* stream);
+
+/* d loss / d parameters of the last gnnb_online_step, gnnb_online_step_rows or gnnb_imitation_step_rows (before weight decay), HOST, blob order. */
 int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats);
 
 const char* gnnb_last_error(void);
