@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]] [--props 18] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]] [--props 18 [--branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -27,6 +27,9 @@ the M undecided nodes of highest BaBSR score as candidates (without it every und
 --frontier K --imitate N (with the GNN or --branching strong) makes every N-th round a learning round: its parents'
 strong-branching table stays on the device and the GNN takes one Adam step towards ranking the table's best candidate first, by
 --imitate-margin M times the difference of the improvements.
+--props N with --branching strong, or with --imitate N, runs both for every property in one pool (frontier.verify_properties_strong,
+DESIGN.md section 7.13): the candidates of all properties' parents are bounded in the same chunks, and a learning round -- every N-th round
+the run launches -- takes ONE step over the parents of all the properties in flight, which share the GNN.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -68,16 +71,16 @@ def main():
     ap.add_argument("--imitate-margin", type=float, default=None, metavar="M", help="with --imitate N: the margin per unit of improvement (default 1.0)")
     args = ap.parse_args()
     if args.imitate is not None and (args.frontier is None or args.imitate < 1 or args.branching == "babsr" or args.threshold is not None
-                                     or args.online is not None or args.props is not None):
-        ap.error("--imitate N needs --frontier K and N >= 1, and takes no --branching babsr, --threshold, --online or --props")
+                                     or args.online is not None):
+        ap.error("--imitate N needs --frontier K and N >= 1, and takes no --branching babsr, --threshold or --online")
     if args.imitate_margin is not None and (args.imitate is None or not args.imitate_margin >= 0):
         ap.error("--imitate-margin M needs --imitate N, and M >= 0")
     if args.branching is not None and args.frontier is None:
         ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
     if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
         ap.error("--branching babsr takes no --threshold and no --online: it never asks the GNN")
-    if args.branching == "strong" and (args.threshold is not None or args.online is not None or args.props is not None):
-        ap.error("--branching strong takes no --threshold, no --online and no --props: it never asks the GNN, and it runs one property")
+    if args.branching == "strong" and (args.threshold is not None or args.online is not None):
+        ap.error("--branching strong takes no --threshold and no --online: it never asks the GNN")
     if args.candidates is not None and ((args.branching != "strong" and args.imitate is None) or args.candidates < 1):
         ap.error("--candidates M needs --branching strong or --imitate N, and M >= 1")
     branching = args.branching or "gnn"
@@ -104,7 +107,8 @@ def main():
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
     if args.props is not None:
-        from gnn_branching_amd.frontier import FrontierJob, FrontierJobs, verify_properties, verify_properties_babsr, verify_properties_threshold
+        from gnn_branching_amd.frontier import (FrontierJob, FrontierJobs, verify_properties, verify_properties_babsr, verify_properties_strong,
+                                                verify_properties_threshold)
         wrong, jobs, names = [c for c in range(10) if c != 3], [], []
         for j in range(args.props):
             seed, cls = args.seed + j // 9, wrong[j % 9]
@@ -113,9 +117,16 @@ def main():
             jobs.append(FrontierJob(x - args.eps, x + args.eps, prop[-1], 0.0))
             names.append(f"seed {seed} class 3 vs {cls}")
         lp = lp_producer.LayerGraphLP(prop, x - args.eps, x + args.eps, bounds="kw_device")
-        choice = GraphChoice([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
-        max_rounds, stats = max(1, args.nodes // (2 * args.frontier)), []
-        if branching == "babsr":
+        if args.imitate is not None:                             # the properties of a pool share the GNN that learns
+            from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice
+        choice = (GraphChoice if args.imitate is None else OnlineGraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        max_rounds, stats, learned = max(1, args.nodes // (2 * args.frontier)), [], {}
+        if branching == "strong" or args.imitate is not None:
+            margin = {} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}
+            results = verify_properties_strong(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
+                                               stats=stats, learned=learned, imitate=args.imitate, strong_candidates=args.candidates, branching=branching,
+                                               **margin)
+        elif branching == "babsr":
             results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         elif args.threshold is None:
             results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
@@ -123,10 +134,16 @@ def main():
             results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
                                                   stats=stats)
         for j, (name, (glb, gub, rounds, bounded, reason)) in enumerate(zip(names, results)):
-            kw = f"; {stats[j]['kw_bounded']} of {stats[j]['branches']} parents bounded a KW decision, {stats[j]['kw_used']} kept it" if stats else ""
+            kw = ""
+            if stats and "kw_bounded" in stats[j]:
+                kw = f"; {stats[j]['kw_bounded']} of {stats[j]['branches']} parents bounded a KW decision, {stats[j]['kw_used']} kept it"
+            if stats and "strong_bounded" in stats[j]:
+                kw = f"; {stats[j]['branches']} branches by {branching}, {stats[j]['strong_bounded']} candidate children bounded"
             if args.witness:
                 kw += witness_of(upper["witness"][j], prop[:-1], jobs[j].prop_layer)
             print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
+        if args.imitate is not None:
+            print(f"{learned['imitation_steps']} imitation steps over {learned['imitation_rows']} parent rows in {learned['rounds']} rounds of the pool")
         return
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))

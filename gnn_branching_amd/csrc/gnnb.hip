@@ -2330,6 +2330,26 @@ extern "C" int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t*
   return run.rc;
 }
 
+// ---- strong branching for many jobs in one pool: the candidates' boxes and property rows, by the segment of
+// their slot.  The copy is k_frontier_rows_sel's and launches under its class: no profile class was added ----
+extern "C" int gnnb_strong_rows_jobs(gnnb_t* h, const int32_t* cand_slot, int c, int segments, int seg_cap, const double* seg_x_lo,
+                                     const double* seg_x_hi, const float* seg_prop_w, const float* seg_prop_b, double* x_lo, double* x_hi,
+                                     float* prop_w, float* prop_b, void* stream) {
+  const char* who = "gnnb_strong_rows_jobs";
+  if (c < 1 || c > 32767) return fail(GNNB_E_INVALID, "%s: c = %d outside 1..32767", who, c);
+  if (segments < 1 || seg_cap < 1) return fail(GNNB_E_INVALID, "%s: segments = %d of seg_cap = %d slots (both at least 1)", who, segments, seg_cap);
+  if (int rc = net_preflight(h, who)) return rc;
+  if (!cand_slot || !seg_x_lo || !seg_x_hi || !seg_prop_w || !seg_prop_b || !x_lo || !x_hi || !prop_w || !prop_b)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  StrongRowsArgs a{};
+  a.cand_slot = cand_slot; a.c = c; a.S = segments; a.seg_cap = seg_cap;
+  a.r = FrSegRows{h->kw_net.N[0], h->kw_net.N[h->kw_net.L], seg_x_lo, seg_x_hi, seg_prop_w, seg_prop_b, x_lo, x_hi, prop_w, prop_b};
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_ROWS_SEL, [&] { hipLaunchKernelGGL(k_strong_rows_jobs, dim3(2 * c, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
 // ---- the learn rows of an online round (reference plnn/relu_conv_online.py:183-207) ----
 extern "C" int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decisions, const int32_t* kw_decisions, const int32_t* used_kw,
                                    const double* gnn_improvement, const double* kw_improvement, int online_threshold, int32_t* wrong,

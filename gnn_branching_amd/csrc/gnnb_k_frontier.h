@@ -708,19 +708,31 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_select_jobs(FrSelArgs a
   if (tid == 0) a.m_entry[E] = min(cnt[FR_THREADS], a.j.n);
 }
 
-__global__ __launch_bounds__(FR_THREADS) void k_frontier_rows_sel(FrSelArgs a) {
+// The box and property row of segment `seg` into row c of a set of child rows: N_0 doubles twice, N_L floats, one float, over the FR_SPLIT
+// workgroups of the row (blockIdx.y).  Plain copies; k_frontier_rows_sel and k_strong_rows_jobs (gnnb_k_strong.h) share it.
+struct FrSegRows {
+  int N0, NL;
+  const double* seg_x_lo; const double* seg_x_hi; const float* seg_pw; const float* seg_pb;            // (S, N_0), (S, N_L), (S)
+  double* x_lo; double* x_hi; float* pw; float* pb;                                                    // the rows
+};
+
+__device__ __forceinline__ void fr_seg_row(const FrSegRows& r, int seg, int c) {
   const int t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  for (int m = t0; m < r.N0; m += dt) {
+    r.x_lo[(long)c * r.N0 + m] = r.seg_x_lo[(long)seg * r.N0 + m];
+    r.x_hi[(long)c * r.N0 + m] = r.seg_x_hi[(long)seg * r.N0 + m];
+  }
+  for (int m = t0; m < r.NL; m += dt) r.pw[(long)c * r.NL + m] = r.seg_pw[(long)seg * r.NL + m];
+  if (t0 == 0) r.pb[c] = r.seg_pb[seg];
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_rows_sel(FrSelArgs a) {
   const int c = blockIdx.x, q = c >> 1;
   if (q >= a.m_entry[a.j.n_entries]) return;
   const int s = a.sel_slots[q];
   if (s < 0 || s / a.j.seg_cap >= a.j.S) return;
-  const int seg = s / a.j.seg_cap;
-  for (int m = t0; m < a.N0; m += dt) {
-    a.b_x_lo[(long)c * a.N0 + m] = a.seg_x_lo[(long)seg * a.N0 + m];
-    a.b_x_hi[(long)c * a.N0 + m] = a.seg_x_hi[(long)seg * a.N0 + m];
-  }
-  for (int m = t0; m < a.NL; m += dt) a.b_pw[(long)c * a.NL + m] = a.seg_pw[(long)seg * a.NL + m];
-  if (t0 == 0) a.b_pb[c] = a.seg_pb[seg];
+  const FrSegRows r{a.N0, a.NL, a.seg_x_lo, a.seg_x_hi, a.seg_pw, a.seg_pb, a.b_x_lo, a.b_x_hi, a.b_pw, a.b_pb};
+  fr_seg_row(r, s / a.j.seg_cap, c);
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_choose_jobs(FrChooseArgs a, FrPlan j, const int32_t* m_entry) {

@@ -16,6 +16,12 @@
 //                       the operation order of the fall-back), the arg-max on (value descending, list position ascending) by per-thread
 //                       partials in position order and a fixed tree, NaN below every number; optionally the (K, R) table.
 //
+//   * k_strong_rows_jobs  many jobs in one pool (gnnb_strong_rows_jobs): the boxes and property rows of a chunk's
+//                       candidate child rows 2q, 2q + 1 from the per-segment tables, by the segment cand_slot[q] / seg_cap of the
+//                       candidate's slot.  Grid (2c, FR_SPLIT); the copy is fr_seg_row, k_frontier_rows_sel's, and the kernel launches
+//                       under that kernel's profile class (PC_FR_ROWS_SEL): it has none of its own.  A slot < 0 or of a segment
+//                       >= segments leaves its two rows unwritten and reads no table.
+//
 // No atomics, no workgroup waits on another; nothing depends on K or on a row's place.
 
 enum { SC_MODE, SC_COUNT_, SC_KEY, SC_TIES, SC_FIELDS };     // workspace of gnnb_strong_list: (K, SC_FIELDS) int32
@@ -37,7 +43,11 @@ struct StrongPickArgs {
   const int32_t* live; const int32_t* infeasible; const double* bound;          // (2n), list order
   int32_t* decisions; double* best; double* imp; double* table;
 };
-static_assert(sizeof(StrongListArgs) <= 4096 && sizeof(StrongPickArgs) <= 4096, "kernel arguments: 4 KiB");
+struct StrongRowsArgs {
+  const int32_t* cand_slot; int c, S, seg_cap;          // (c) slots of the chunk's candidates; the pool's segments
+  FrSegRows r;
+};
+static_assert(sizeof(StrongListArgs) <= 4096 && sizeof(StrongPickArgs) <= 4096 && sizeof(StrongRowsArgs) <= 4096, "kernel arguments: 4 KiB");
 
 // The order-preserving key of a score: a > b as floats <=> key(a) > key(b) as unsigned, with -0.0 keyed as +0.0.  (Not for NaN.)
 __device__ __forceinline__ unsigned st_key(float v) {
@@ -200,4 +210,12 @@ __global__ __launch_bounds__(FR_THREADS) void k_strong_pick(StrongPickArgs a) {
     a.decisions[2 * i + 1] = q >= 0 ? a.cand_dec[2L * q + 1] : -1;
     a.best[i] = q >= 0 ? sv[0] : nan;
   }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_strong_rows_jobs(StrongRowsArgs a) {
+  const int row = blockIdx.x, q = row >> 1;
+  if (q >= a.c) return;
+  const int s = a.cand_slot[q];
+  if (s < 0 || s / a.seg_cap >= a.S) return;            // (gnnb_strong_list lists no such slot: the guard protects memory)
+  fr_seg_row(a.r, s / a.seg_cap, row);
 }

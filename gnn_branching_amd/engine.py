@@ -1257,6 +1257,21 @@ class ScorerEngine:
                    self._rows(improvement, n, 1, f64, "improvement").data_ptr(),
                    None if table is None else self._rows(table, K, self.R, f64, "table").data_ptr())
 
+    def strong_rows_jobs(self, cand_slot, c, segments, seg_cap, seg_x_lo, seg_x_hi, seg_prop_w, seg_prop_b, x_lo, x_hi, prop_w, prop_b):
+        """gnnb_strong_rows_jobs on the current stream: child rows 2q and 2q + 1 of x_lo / x_hi (2c, N_0) fp64,
+        prop_w (2c, N_L) and prop_b (2c,) fp32 receive the box and property row of segment cand_slot[q] // seg_cap from the per-segment
+        tables seg_x_lo / seg_x_hi (segments, N_0), seg_prop_w (segments, N_L), seg_prop_b (segments,); cand_slot (c,) int32 is a chunk of
+        ``strong_list``'s.  A slot outside the pool leaves its two rows unwritten.  Nothing is copied by the host."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        c, S = int(c), int(segments)
+        n, N0, NL, i32, f32, f64 = max(c, 0), self.sizes[0], self.sizes[-2], torch.int32, torch.float32, torch.float64
+        self._call("gnnb_strong_rows_jobs", self._rows(cand_slot, n, 1, i32, "cand_slot").data_ptr(), c, S, int(seg_cap),
+                   self._rows(seg_x_lo, max(S, 0), N0, f64, "seg_x_lo").data_ptr(), self._rows(seg_x_hi, max(S, 0), N0, f64, "seg_x_hi").data_ptr(),
+                   self._rows(seg_prop_w, max(S, 0), NL, f32, "seg_prop_w").data_ptr(), self._rows(seg_prop_b, max(S, 0), 1, f32, "seg_prop_b").data_ptr(),
+                   self._rows(x_lo, 2 * n, N0, f64, "x_lo").data_ptr(), self._rows(x_hi, 2 * n, N0, f64, "x_hi").data_ptr(),
+                   self._rows(prop_w, 2 * n, NL, f32, "prop_w").data_ptr(), self._rows(prop_b, 2 * n, 1, f32, "prop_b").data_ptr())
+
     def _children(self, ch, n, what=None):
         """The gnnb_children of a set of child rows (any object with mask, lb, ub, infeasible, bound, alpha, beta, ubv, live) and what must
         outlive the call.  what: the rows' name in a message (None: loose tensors, named as ``frontier_commit`` takes them)."""

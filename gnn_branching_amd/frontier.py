@@ -30,6 +30,10 @@ both children of every candidate split of every parent are bounded in chunks (``
 ``branch_and_bound_frontier(..., imitate=N)`` connects the two: every N-th round leaves its table in device memory
 and, behind the commit, takes one Adam step of the GNN on it (``gnnb_imitation_step_rows``), so a "gnn" or "strong" run labels its own
 states with the teacher and learns from them without the table, the scorer inputs or the gradient crossing the link.
+
+``verify_properties_strong`` runs both for many jobs in one pool: the candidates of all jobs' parents form one list
+bounded in shared chunks, each candidate's child rows taking their own job's box and property row (``gnnb_strong_rows_jobs``), and with
+``imitate=N`` every N-th round the pool launches takes one step over the parents of all jobs in flight, which share the scorer.
 """
 import ctypes as C
 import math
@@ -299,6 +303,11 @@ class _Round:
     branching = "gnn"
     strong_on, strong_M, strong_chunk, strong_audit = False, 0, STRONG_CHUNK_DEFAULT, None
     imitate, learning, im_table = None, False, None
+    imitate_pending, strong_n, imitation_steps, imitation_rows, last_imitation = False, 0, 0, 0, 0
+
+    def _engine_of(self, choice):
+        """The engine of a run that never learns: the model's (a learning run takes ``choice._eng()``, the engine with its optimizer)."""
+        return choice.model.engine()
 
     def _strong_options(self, strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None):
         """The options of DESIGN.md section 7.11, checked; set before the rows are made (``_buffers`` sizes the workspaces by them).
@@ -424,6 +433,7 @@ class _Round:
         n_c = self.strong_n = self.read_candidates(n)
         for q0 in range(0, n_c, self.strong_chunk):               # a chunk may span parents
             c = min(self.strong_chunk, n_c - q0)
+            self._strong_chunk_rows(q0, c)
             eng.frontier_expand(pool, self.cand_slot[q0:q0 + c], self.cand_dec[q0:q0 + c], S.mask, S.plb, S.pub, S.split, S.alpha, S.beta,
                                 self.s_live[2 * q0:])
             with torch.cuda.device(eng.device):
@@ -435,12 +445,17 @@ class _Round:
         self.strong_bounded += 2 * n_c
         eng.strong_pick(pool, slots, self.cand0, self.cand_dec, n_c, self.s_live, self.s_infeasible, self.s_bound, dec, self.s_best, self.s_imp, table)
 
+    def _strong_chunk_rows(self, q0, c):
+        """The boxes and property rows of ``ChS`` for the chunk of candidates [q0, q0 + c), in front of its gnnb_frontier_expand.  A
+        one-job run has nothing to do: every row holds the run's one box and property, filled once.  ``StrongJobsRun`` (DESIGN.md section
+        7.13) copies each candidate's own job's."""
+
     def _strong_parents(self, n):
         """``branching="strong"`` in ``_score_parents``' place: the table of the n parent rows the gather wrote and
         its arg-max per row into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward.  A learning round (section 7.12) keeps the
         table and then runs gnnb_dual_ascent at n_iter = 0 on the parent rows, so that the scorer inputs the step reads exist; still no
         gnnb_forward."""
-        self._strong_table(self.slots, n, self.P.dec, self.im_table if self.learning else None)
+        self._strong_table(self.slots[:n], n, self.P.dec, self.im_table if self.learning else None)      # (a one-job run's slots are its n)
         if self.learning:
             self._scorer_inputs(n)
 
@@ -546,8 +561,28 @@ class _Round:
         self._raise_for(int(self.status_all.cpu()[0]))
 
     def _raise_for(self, st):
+        if st & 8 and self.imitate is not None:
+            raise RuntimeError("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
+                               "row's mask, or holds an infinite improvement")
         from .engine import _raise_for_status
         _raise_for_status(st)
+
+    def _imitate(self):
+        """The learning half of a learning round (DESIGN.md section 7.12), behind the commit and the read of the state record.  When the
+        round listed a candidate -- ``strong_n``, the 4 bytes the round already read -- ONE step over ALL k parent rows on the scorer inputs
+        the round left in ``P`` (intact until the next gather), every row scored with the round's opening parameters; a row without a
+        candidate contributes nothing.  If every candidate's improvement is NaN (a dead child each) the gradient is zero and the step is
+        weight decay alone.  The next round's forward scores with the new parameters.  ``k``: the number of parent rows of the round (of
+        all its entries, in a many-jobs run)."""
+        self.imitate_pending, self.last_imitation = False, 0
+        if self.strong_n <= 0:
+            return
+        k = self.last_imitation = self.k
+        self.step_status.zero_()
+        self.eng.imitation_step_rows(self.P.fwd_batch, k, self.im_rows[:k], self.im_table, self.imitate_margin, loss=self.im_loss[:k],
+                                     report=self.im_report[:k], regret=self.im_regret[:k], status=self.step_status)
+        self.status_all |= self.step_status
+        self.imitation_steps, self.imitation_rows = self.imitation_steps + 1, self.imitation_rows + k
 
 
 class FrontierRun(_Round):
@@ -707,31 +742,12 @@ class FrontierRun(_Round):
         self.status_all |= self.step_status
         self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
 
-    def _imitate(self):
-        """The learning half of a learning round (DESIGN.md section 7.12), behind the commit and the read of the state record.  When the
-        round listed a candidate -- ``strong_n``, the 4 bytes the round already read -- ONE step over ALL k parent rows on the scorer inputs
-        the round left in ``P`` (intact until the next gather), every row scored with the round's opening parameters; a row without a
-        candidate contributes nothing.  If every candidate's improvement is NaN (a dead child each) the gradient is zero and the step is
-        weight decay alone.  The next round's forward scores with the new parameters."""
-        self.imitate_pending, self.last_imitation = False, 0
-        if self.strong_n <= 0:
-            return
-        k = self.last_imitation = self.k
-        self.step_status.zero_()
-        self.eng.imitation_step_rows(self.P.fwd_batch, k, self.im_rows[:k], self.im_table, self.imitate_margin, loss=self.im_loss[:k],
-                                     report=self.im_report[:k], regret=self.im_regret[:k], status=self.step_status)
-        self.status_all |= self.step_status
-        self.imitation_steps, self.imitation_rows = self.imitation_steps + 1, self.imitation_rows + k
-
     def read_learn(self):
         """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
         return int(self.n_learn.cpu()[0])
 
     def _raise_for(self, st):
-        if st & 8 and self.imitate is not None:
-            raise RuntimeError("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
-                               "row's mask, or holds an infinite improvement")
-        if st & 8:
+        if st & 8 and self.imitate is None:
             raise RuntimeError("gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask")
         super()._raise_for(st)
 
@@ -928,23 +944,26 @@ def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
     return global_lb, global_ub, rounds, bounded, reason
 
 
-def _strong_rows(run, k):
-    """One dict per parent of the round just launched (device-to-host copies; a traced or audited run only): its slot, the decision the
-    round committed and that decision's improvement from the round's own children, the table's decision and best improvement, and the
-    row's candidates (flat ReLU indices) with their improvements."""
+def _strong_rows(run, k, row0=0):
+    """One dict per parent of the rows [row0, row0 + k) of the round just launched (device-to-host copies; a traced or audited run
+    only): its slot, the decision the round committed and that decision's improvement from the round's own children, the table's decision
+    and best improvement, and the row's candidates (flat ReLU indices) with their improvements.  A one-job round is the rows [0, k); an
+    entry of a many-jobs round its own, whose candidates are the range [cand0[row0], cand0[row0 + k]) of the lists."""
     from .bab_caller import gnn_improvement
     inf, nan = float("inf"), float("nan")
-    Ch, n = run.Ch, run.strong_n
+    Ch, r1 = run.Ch, row0 + k
     off = [0]
     for s in run.eng.sizes[1:-1]:
         off.append(off[-1] + s)
-    slots = run.slots[:k].cpu().tolist()
-    dec = run.P.dec[:k].cpu().tolist()
-    s_dec = dec if run.branching == "strong" else run.s_dec[:k].cpu().tolist()
-    parent = run.parent_bound[:k].cpu().tolist()
-    live, infeasible, bound = (t[:2 * k].cpu().tolist() for t in (Ch.live, Ch.infeasible, Ch.bound))
-    cand0, best = run.cand0[:k + 1].cpu().tolist(), run.s_best[:k].cpu().tolist()
-    cand_dec, imp = run.cand_dec[:n].cpu().tolist(), run.s_imp[:n].cpu().tolist()
+    slots = run.slots[row0:r1].cpu().tolist()
+    dec = run.P.dec[row0:r1].cpu().tolist()
+    s_dec = dec if run.branching == "strong" else run.s_dec[row0:r1].cpu().tolist()
+    parent = run.parent_bound[row0:r1].cpu().tolist()
+    live, infeasible, bound = (t[2 * row0:2 * r1].cpu().tolist() for t in (Ch.live, Ch.infeasible, Ch.bound))
+    cand0, best = run.cand0[row0:r1 + 1].cpu().tolist(), run.s_best[row0:r1].cpu().tolist()
+    q0 = cand0[0]
+    cand0 = [q - q0 for q in cand0]
+    cand_dec, imp = run.cand_dec[q0:q0 + cand0[-1]].cpu().tolist(), run.s_imp[q0:q0 + cand0[-1]].cpu().tolist()
     rows = []
     for i in range(k):
         lbs = [inf if infeasible[c] else bound[c] for c in (2 * i, 2 * i + 1)]
@@ -1115,7 +1134,7 @@ class JobsRun(_Round):
         self._restart_options(pgd_restarts, pgd_seed)
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
-        eng = self.eng = choice.model.engine()
+        eng = self.eng = self._engine_of(choice)
         eng.bind(self.fixed, in_shape)
         dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
         f64, f32, i32 = torch.float64, torch.float32, torch.int32
@@ -1269,6 +1288,89 @@ class JobsRun(_Round):
         return self.pool.state.cpu().tolist()
 
 
+def _check_jobs_strong(branching, strong_audit, imitate):
+    """The modes of a many-jobs run with a table: "strong", or "gnn" next to an audit or the imitation step."""
+    if branching == "babsr":
+        raise ValueError('branching="babsr": verify_properties_babsr runs the jobs on BaBSR alone; a table next to it is not built for many jobs')
+    if branching == "gnn" and strong_audit is None and imitate is None:
+        raise ValueError('branching="gnn" with neither strong_audit nor imitate: nothing would compute a table; verify_properties runs the jobs on the GNN')
+
+
+class StrongJobsRun(JobsRun):
+    """The device side of ``verify_properties_strong``: ``JobsRun`` with the table of section 7.11 over the parent
+    rows of ALL entries of a round and, with ``imitate`` = N, the step of section 7.12 behind every N-th launched round.  The candidates
+    of a round form one dense list over all its jobs; a chunk may span parents and jobs, so in front of every chunk
+    ``gnnb_strong_rows_jobs`` gives each candidate's two child rows their own job's box and property row.  ``launch_round`` is device work
+    only but for the round's one extra read, ``read_candidates``: 4 (entries + 1) bytes."""
+
+    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
+                 sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
+                 pgd_seed=0, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
+                 strong_audit=None, branching="strong"):
+        _check_branching(branching, branching_threshold, None)
+        _check_imitate(imitate, imitate_margin, branching, branching_threshold, None, choice)
+        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, None, imitate)      # (_buffers sizes by strong_on)
+        _check_jobs_strong(branching, strong_audit, imitate)
+        self.imitate, self.imitate_margin = imitate, float(imitate_margin)
+        super().__init__(choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold, kwbd_threshold, sparsest_layer,
+                         decision_threshold, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, branching)
+        eng, dev, n = self.eng, self.eng.device, segments * K
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        N0, NL, rows = eng.sizes[0], eng.sizes[-2], 2 * strong_chunk
+        # the candidates' rows belong to the jobs of their parents: boxes and property rows of their own (gnnb_strong_rows_jobs fills them)
+        self._strong_buffers(n, (torch.zeros(rows, N0, dtype=f64, device=dev), torch.zeros(rows, N0, dtype=f64, device=dev),
+                                 torch.zeros(rows, NL, dtype=f32, device=dev), torch.zeros(rows, dtype=f32, device=dev)))
+        self.cand_idx = torch.zeros(segments + 1, dtype=torch.int64, device=dev)      # the rows of cand0 a round reads: every entry's row0, and n
+        self.cand_entry = None
+        self.round, self.k = 0, 0
+        if imitate is not None:
+            self.im_table = torch.zeros(n, eng.R, dtype=f64, device=dev)
+            self.im_rows = torch.arange(n, dtype=i32, device=dev)
+            self.im_loss, self.im_regret = torch.zeros(n, dtype=f32, device=dev), torch.zeros(n, dtype=f64, device=dev)
+            self.im_report = torch.zeros(n, 4, dtype=i32, device=dev)
+            self.step_status = torch.zeros(1, dtype=i32, device=dev)
+
+    def _engine_of(self, choice):
+        return choice.model.engine() if self.imitate is None else choice._eng()      # (_eng: the engine with its optimizer)
+
+    def _strong_chunk_rows(self, q0, c):
+        box = self.ChS.box
+        self.eng.strong_rows_jobs(self.cand_slot[q0:q0 + c], c, self.S, self.cap, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, *box)
+
+    def launch_round(self, entries):
+        """``JobsRun.launch_round`` as launched round number ``round`` of the run (1-based; root phases do not count): a learning round
+        when that number is a multiple of ``imitate``."""
+        self.round += 1
+        self.learning = self.imitate_pending = self.imitate is not None and self.round % self.imitate == 0
+        self.k, self.last_imitation, self.cand_entry = sum(e[2] for e in entries), 0, None
+        super().launch_round(entries)
+
+    def read_candidates(self, n):
+        """cand0 at every entry's first row and cand0[n]: the 4 (entries + 1) bytes a round with a table reads between the list and its
+        chunks, in ONE copy.  The differences are the entries' candidates (``cand_entry`` keeps the list); the last is the round's."""
+        E, idx = self.plan.n_entries, self.cand_idx
+        idx[:E] = self.plan.device[:E, 1]
+        idx[E] = n
+        self.cand_entry = self.cand0[idx[:E + 1]].cpu().tolist()
+        return self.cand_entry[-1]
+
+    def _imitate(self):
+        try:
+            super()._imitate()
+        except RuntimeError as e:                                 # (GNNB_E_NOMEM: the step's buffers grow with the rows of a round)
+            if "(-4)" not in str(e):
+                raise
+            raise RuntimeError(f"the imitation step over the {self.k} parent rows of a round found no device memory: lower segments or K "
+                               f"(segments * K = {self.S * self.K} rows at most per step)") from e
+
+    def read_state(self):
+        """``JobsRun.read_state``; a learning round then takes its step (``_imitate``), behind the records."""
+        st = super().read_state()
+        if self.imitate_pending:
+            self._imitate()
+        return st
+
+
 class FrontierJobs(list):
     """A list of ``FrontierJob`` together with the upper-bound options of the run that verifies them: how
     ``verify_properties`` and ``verify_properties_threshold`` take ``branch_and_bound_frontier``'s witness, pgd_steps and pgd_step.  (Their
@@ -1361,19 +1463,75 @@ def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, cap
     return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, None, stats, upper, restarts, babsr)
 
 
+def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print,
+                             trace=None, stats=None, learned=None, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None,
+                             strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="strong"):
+    """``verify_properties`` with strong branching, its audit and the imitation step for every job.  WITHOUT
+    ``imitate`` every job gets the result ``branch_and_bound_frontier(..., branching=branching, capacity=capacity, strong_candidates=...,
+    strong_chunk=...)`` gives it alone, bit for bit, whatever else is in flight, whichever segment it got, whenever it was admitted and
+    wherever the chunks fall.
+
+    branching: "strong" -- every parent of every job is split where its bound improves most over its candidates -- or "gnn", legal only
+    with ``strong_audit`` or ``imitate`` (``verify_properties`` runs the jobs on the GNN without a table; ``verify_properties_babsr`` on
+    BaBSR).  strong_candidates, strong_chunk, strong_audit, imitate, imitate_margin: ``branch_and_bound_frontier``'s.  The candidates of
+    all parent rows of a round, of all jobs, form ONE dense list that is bounded in chunks of ``strong_chunk``; a chunk may span parents
+    and jobs, and ``gnnb_strong_rows_jobs`` gives every candidate's child rows their own job's box and property row first.  The round's
+    one extra read is cand0 at every entry's first row and the total (``StrongJobsRun.read_candidates``, 4 (entries + 1) bytes).
+
+    imitate = N: the LEARNING rounds are the run's launched rounds (root phases do not count) whose 1-based number is a multiple of N.
+    Every parent row of every entry then gets the table, and behind the commit and the read of the records, when the round listed a
+    candidate, ONE ``gnnb_imitation_step_rows`` runs over all the round's rows in plan row order; the next round of every job scores with
+    the new parameters.  The jobs of a pool share ONE scorer: with ``imitate`` a job's result depends on what else is in flight (which
+    rows shared its steps, and when it was admitted); without ``imitate`` it does not.  ``choice`` must then be a
+    ``graphnet.graph_score_online.GraphChoice``, and when the run ends (or raises) after a step ``choice.model`` receives the device's
+    parameters.  A step that finds no device memory raises a RuntimeError that says to lower ``segments`` or ``K``.
+
+    stats: None, or a list that receives per job, in job order, {"branches", "domains_bounded", "strong_bounded"} (the job's candidate
+    children).  learned: None, or a dict that receives "imitation_steps", "imitation_rows" and "rounds" (launched) of the run.  trace:
+    ``verify_properties``' keys per round and per entry; in "strong" mode also "strong_candidates" and "strong_improvement" per parent, on a
+    learning round "imitation_loss" / "imitation_report" / "imitation_regret" of the entry's rows, and in a run with ``imitate`` the
+    entry's "global_lb" / "global_ub" after the round.  strong_audit receives per parent the one-job audit's dict plus "job", "segment"
+    and "round".  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
+
+    Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
+    _check_branching(branching, None, None)
+    _check_imitate(imitate, imitate_margin, branching, None, None, choice)
+    _check_strong(strong_candidates, strong_chunk, strong_audit, branching, None, None, imitate)
+    _check_jobs_strong(branching, strong_audit, imitate)
+    if learned is not None and not isinstance(learned, dict):
+        raise ValueError(f"learned = {learned!r}: None, or a dict that receives the run's learning counts")
+    strong = {"imitate": imitate, "imitate_margin": imitate_margin, "strong_candidates": strong_candidates, "strong_chunk": strong_chunk,
+              "strong_audit": strong_audit, "branching": branching}
+    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, None, stats, upper, restarts, None,
+                        strong, learned)
+
+
 def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None,
-                 restarts=None, babsr=None):
-    """The loop of ``verify_properties``, ``verify_properties_threshold`` and ``verify_properties_babsr`` on checked arguments.  threshold:
-    None, or the threshold mode's arguments of ``JobsRun``; with None a round launches and reads exactly what section 7.4 lists.  upper:
-    None, or the witness and descent options of section 7.8; restarts: None, or the restart options of section 7.9; babsr: None, or the
-    arguments of ``JobsRun`` that make every job branch on BaBSR alone (section 7.10)."""
-    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}), **(upper or {}), **(restarts or {}),
-                  **(babsr or {}))
-    witness = (upper or {}).get("witness")
+                 restarts=None, babsr=None, strong=None, learned=None):
+    """The loop of ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr`` and ``verify_properties_strong`` on
+    checked arguments.  threshold: None, or the threshold mode's arguments of ``JobsRun``; with None a round launches and reads exactly what
+    section 7.4 lists.  upper: None, or the witness and descent options of section 7.8; restarts: None, or the restart options of section
+    7.9; babsr: None, or the arguments of ``JobsRun`` that make every job branch on BaBSR alone (section 7.10); strong: None, or the
+    arguments ``StrongJobsRun`` adds to ``JobsRun``'s (section 7.13), which make the run one of that class; learned: None, or the dict that
+    receives such a run's "imitation_steps", "imitation_rows" and launched "rounds"."""
+    run = (JobsRun if strong is None else StrongJobsRun)(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}),
+                                                         **(upper or {}), **(restarts or {}), **(babsr or {}), **(strong or {}))
     run.keep_pairs = trace is not None
+    try:
+        return _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, threshold, stats, upper, babsr, strong, learned)
+    finally:
+        if run.imitation_steps:                                   # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it
+            choice.model.load_blob(run.eng.get_weights())
+
+
+def _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, threshold, stats, upper, babsr, strong, learned):
+    """``_verify_jobs``' loop on its run."""
+    witness = (upper or {}).get("witness")
     F, thr = _lib, threshold is not None
     results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
-    branches, kw_bounded = [0] * len(jobs), [0] * len(jobs)
+    branches, kw_bounded, strong_bounded = [0] * len(jobs), [0] * len(jobs), [0] * len(jobs)
     seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
     waiting = list(range(len(jobs)))
 
@@ -1426,7 +1584,21 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
                 trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], **_trace_rows(run, row0, row0 + k)})
                 if thr:
                     trace[-1].update(_threshold_trace(run, k, e, row0))
+        if strong is not None and ((run.branching == "strong" and trace is not None) or run.strong_audit is not None) and run.cand_entry is not None:
+            for e, (s, row0, k) in enumerate(entries):            # section 7.11's rows, per entry
+                rows = _strong_rows(run, k, row0)
+                if trace is not None and run.branching == "strong":
+                    trace[e - len(entries)].update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
+                if run.strong_audit is not None:
+                    run.strong_audit.extend({**r, "job": seg_job[s], "segment": s, "round": rounds[seg_job[s]]} for r in rows)
         st = run.read_state()
+        if trace is not None and run.imitate is not None:         # the learning round's step, per entry, and the bounds after the round
+            for e, (s, row0, k) in enumerate(entries):
+                if run.last_imitation:
+                    trace[e - len(entries)].update(imitation_loss=run.im_loss[row0:row0 + k].cpu().tolist(),
+                                                   imitation_regret=run.im_regret[row0:row0 + k].cpu().tolist(),
+                                                   imitation_report=run.im_report[row0:row0 + k].cpu().tolist())
+                trace[e - len(entries)].update(global_lb=_global_lb(st[s]), global_ub=st[s][F.FS_GLOBAL_UB])
         if trace is not None and run.witness_on:
             values = run.best_value.cpu().tolist()
             for e, (s, _, _) in enumerate(entries):
@@ -1439,8 +1611,10 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
             bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
             if thr:                                               # the children of both pairs
                 bounded[j], branches[j], kw_bounded[j] = bounded[j] + 2 * run.m_e[e], branches[j] + k, kw_bounded[j] + run.m_e[e]
-            elif babsr is not None:
+            elif babsr is not None or strong is not None:
                 branches[j] += k
+            if strong is not None and run.cand_entry is not None:  # the entry's candidate children (a round without a table bounds none)
+                strong_bounded[j] += 2 * (run.cand_entry[e + 1] - run.cand_entry[e])
             log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
                 f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
     run.check_status()
@@ -1453,4 +1627,8 @@ def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, ep
                      for j in range(len(jobs)))
     if babsr is not None and stats is not None:
         stats.extend({"branches": branches[j], "domains_bounded": results[j][3]} for j in range(len(jobs)))
+    if strong is not None and stats is not None:
+        stats.extend({"branches": branches[j], "domains_bounded": results[j][3], "strong_bounded": strong_bounded[j]} for j in range(len(jobs)))
+    if strong is not None and learned is not None:
+        learned.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows, rounds=run.round)
     return results

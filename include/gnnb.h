@@ -580,6 +580,20 @@ int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int
                      const int32_t* live, const int32_t* infeasible, const double* bound, int32_t* decisions, double* best_improvement,
                      double* improvement, double* table, void* stream);
 
+/* Strong branching for many jobs in one pool (frontier.verify_properties_strong): the boxes and property rows of a
+ * chunk of c candidates, by the segment of their slot.  cand_slot: device (c) int32, a chunk of gnnb_strong_list's cand_slot; the pool is
+ * `segments` segments of seg_cap slots and seg_x_lo / seg_x_hi (segments, N_0) fp64, seg_prop_w (segments, N_L) fp32, seg_prop_b
+ * (segments) fp32 hold each segment's box and property row (as gnnb_frontier_fallback_jobs takes them).  Child rows 2q and 2q + 1 of
+ * x_lo / x_hi (2c, N_0), prop_w (2c, N_L), prop_b (2c) receive the row of segment cand_slot[q] / seg_cap: plain copies, the ones
+ * gnnb_frontier_fallback_jobs makes for pair B (one launch, under that copy's profile class k_frontier_rows_sel).  A slot < 0, or one whose
+ * segment is >= segments, leaves its two rows unwritten and reads nothing out of bounds; gnnb_strong_list never lists such a slot.  Rows
+ * from 2c on are not written.  Stream-ordered, no allocation, no synchronisation, no atomics, no workgroup waits on another.
+ * GNNB_E_INVALID before any launch for c outside 1..32767, segments < 1 or seg_cap < 1 (before the handle is looked at), a null handle or
+ * a null argument; GNNB_E_STATE before gnnb_bind_network. */
+int gnnb_strong_rows_jobs(gnnb_t* h, const int32_t* cand_slot, int c, int segments, int seg_cap, const double* seg_x_lo,
+                          const double* seg_x_hi, const float* seg_prop_w, const float* seg_prop_b, double* x_lo, double* x_hi, float* prop_w,
+                          float* prop_b, void* stream);
+
 /* ---- learning online inside the frontier (reference plnn/relu_conv_online.py:183-207) ----
  * The selection of the rows an online round learns from, after gnnb_frontier_choose: wrong (device (R) int32, zero at the start of a run)
  * is the reference's wrong_pts_dc, keyed by the flat ReLU index (the layer's offset + idx, graph_score_online.py:63-68) of the GNN's
