@@ -298,33 +298,41 @@ PGD_RESTARTS_MAX = 4096             # gnnb_net_starts' R
 
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
-    witness_on, pgd_steps, pgd_step = False, None, PGD_STEP_DEFAULT
-    restarts, pgd_seed = 0, 0
-    branching = "gnn"
-    strong_on, strong_M, strong_chunk, strong_audit = False, 0, STRONG_CHUNK_DEFAULT, None
-    imitate, learning, im_table = None, False, None
-    imitate_pending, strong_n, imitation_steps, imitation_rows, last_imitation = False, 0, 0, 0, 0
+    branching, strong_on, imitate, learning = "gnn", False, None, False      # (what a run is before ``_set_options``: everything off)
 
-    def _engine_of(self, choice):
-        """The engine of a run that never learns: the model's (a learning run takes ``choice._eng()``, the engine with its optimizer)."""
-        return choice.model.engine()
-
-    def _strong_options(self, strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None):
-        """The options of DESIGN.md section 7.11, checked; set before the rows are made (``_buffers`` sizes the workspaces by them).
-        ``strong_on`` False: nothing of a round differs.  ``imitate`` (section 7.12) needs the table too."""
+    def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
+                     online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
+                     imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None):
+        """The options of a run, checked in ONE order -- imitate, branching, strong, witness, restarts, threshold, online -- and stored with
+        everything derived from them, before anything touches ``choice`` or a device; a constructor passes the keywords it has and the
+        others stay off.  Everything behind it (``_engine_of``, ``_buffers``, ``_launch``, the loops) reads the run, never an argument:
+        ``strong_on`` (a round computes the table of section 7.11: "strong", an audit, or ``imitate``), ``strong_M`` (0: every undecided
+        node), ``witness_on`` and ``witness_to`` (the caller's list), ``restarts`` (0: off), ``threshold``, ``online``, ``learns`` (the
+        scorer's parameters move: the run takes the engine with the optimizer), and the counters of a run before its first round."""
+        _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice)
+        _check_branching(branching, branching_threshold, online_threshold)
         _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate)
+        _check_witness(witness, pgd_steps, pgd_step)
+        _check_restarts(pgd_restarts, pgd_seed, pgd_steps)
+        _check_threshold(branching_threshold, kwbd_threshold)
+        _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
+        self.branching, self.threshold, self.online = branching, branching_threshold, online_threshold
+        self.kwbd_threshold = kwbd_threshold if online_threshold is None else KWBD_NEVER
+        self.sparsest_layer, self.decision_threshold = sparsest_layer, decision_threshold
+        if branching_threshold is not None or branching == "babsr":      # (the BaBSR heuristic's: converted where a round uses them)
+            self.sparsest_layer, self.decision_threshold = int(sparsest_layer), float(decision_threshold)
+        self.witness_on, self.witness_to, self.pgd_steps, self.pgd_step = witness is not None, witness, pgd_steps, float(pgd_step)
+        self.restarts, self.pgd_seed = pgd_restarts or 0, pgd_seed
+        self.imitate, self.imitate_margin, self.learns = imitate, float(imitate_margin), online_threshold is not None or imitate is not None
         self.strong_on = branching == "strong" or strong_audit is not None or imitate is not None
         self.strong_M, self.strong_chunk, self.strong_audit = strong_candidates or 0, strong_chunk, strong_audit
+        self.round = self.k = self.strong_n = self.imitation_steps = self.imitation_rows = self.last_imitation = 0
+        self.learning, self.imitate_pending, self.cand_entry, self.im_table = False, False, None, None
 
-    def _restart_options(self, pgd_restarts, pgd_seed):
-        """The options of DESIGN.md section 7.9, checked, behind ``_upper_bound_options``; ``restarts`` 0: off, and nothing of a round differs."""
-        _check_restarts(pgd_restarts, pgd_seed, self.pgd_steps)
-        self.restarts, self.pgd_seed = pgd_restarts or 0, pgd_seed
-
-    def _upper_bound_options(self, witness, pgd_steps, pgd_step):
-        """The options of DESIGN.md section 7.8, checked; set before the rows are made (``_child_rows`` gives them ``x_ub`` under PGD)."""
-        _check_witness(witness, pgd_steps, pgd_step)
-        self.witness_on, self.pgd_steps, self.pgd_step = witness is not None, pgd_steps, float(pgd_step)
+    def _engine_of(self, choice):
+        """The engine of the run: the model's, or for a run that learns (online or by imitation) ``choice._eng()``, the engine with its
+        optimizer."""
+        return choice._eng() if self.learns else choice.model.engine()
 
     def _witness_buffers(self, segments):
         """Per segment the incumbent's value (+inf: none yet; the record's global_ub after every commit) and its point."""
@@ -368,13 +376,12 @@ class _Round:
             rows.x_ub = torch.zeros_like(rows.x_lp)
         return rows
 
-    def _threshold_buffers(self, n_parents, counters, box_b, ws_sizer, kwbd_threshold, sparsest_layer, decision_threshold):
+    def _threshold_buffers(self, n_parents, counters, box_b, ws_sizer):
         """The threshold mode's state for rounds of up to n_parents parents (DESIGN.md sections 7.5 and 7.6).  counters: the shapes of the
         intercept counters ``icp`` (and of ``n_used``, the KW pairs taken) and of the tables ``ineff`` of inefficient KW points; box_b: pair
         B's own boxes and property rows (None: the children's); ws_sizer: the selection's workspace sizer."""
         dev, R, n = self.eng.device, self.eng.R, n_parents
         f64, f32, i32 = torch.float64, torch.float32, torch.int32
-        self.kwbd_threshold, self.sparsest_layer, self.decision_threshold = kwbd_threshold, int(sparsest_layer), float(decision_threshold)
         self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
         self.icp, self.ineff = torch.zeros(counters[0], dtype=i32, device=dev), torch.zeros(counters[1], dtype=i32, device=dev)
         self.n_used = torch.zeros(counters[0], dtype=torch.int64, device=dev)
@@ -385,11 +392,10 @@ class _Round:
         self.sel_rows, self.sel_slots, self.used_kw = (torch.zeros(n, dtype=i32, device=dev) for _ in range(3))
         self.ws_fallback = self._ws(ws_sizer, n)
 
-    def _babsr_buffers(self, n_parents, counters, sparsest_layer, decision_threshold):
+    def _babsr_buffers(self, n_parents, counters):
         """The state of ``branching="babsr"`` for rounds of up to n_parents parents.  counters: the shape of the
         intercept counters ``icp`` (one per run, or one per segment)."""
         dev, R, f32 = self.eng.device, self.eng.R, torch.float32
-        self.sparsest_layer, self.decision_threshold = int(sparsest_layer), float(decision_threshold)
         self.random_order = _random_order(self.ng - 2, self.sparsest_layer)
         self.icp = torch.zeros(counters, dtype=torch.int32, device=dev)
         self.kw_scores, self.kw_icp = torch.zeros(n_parents, R, dtype=f32, device=dev), torch.zeros(n_parents, R, dtype=f32, device=dev)
@@ -410,14 +416,41 @@ class _Round:
         self.s_bound, self.s_imp = torch.zeros(2 * cap, dtype=f64, device=dev), torch.zeros(cap, dtype=f64, device=dev)
         self.s_best, self.s_dec = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, 2, dtype=i32, device=dev)
         self.ws_strong = self._ws("gnnb_strong_list_workspace_bytes", n)
-        self.strong_n, self.strong_bounded = 0, 0
+        self.strong_bounded = 0
+
+    def _imitation_buffers(self, n_parents):
+        """The state of a run with ``imitate`` for learning rounds of up to n_parents parent rows: the table a
+        learning round keeps, the rows its step takes (all of them, in row order) and what the step reports per row."""
+        if self.imitate is None:
+            return
+        dev, n = self.eng.device, n_parents
+        self.im_table = torch.zeros(n, self.eng.R, dtype=torch.float64, device=dev)
+        self.im_rows = torch.arange(n, dtype=torch.int32, device=dev)
+        self.im_loss, self.im_regret = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
+        self.im_report = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+        self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _begin_round(self, k):
+        """The top of ``launch_round``: launched round number ``round`` of the run (1-based; root phases do not count), of k parent rows over
+        all its entries.  With ``imitate`` = N it is a learning round when that number is a multiple of N: its table stays, and its step
+        runs behind the read of the state.  No candidate has been counted yet (``cand_entry``)."""
+        self.round += 1
+        self.learning = self.imitate_pending = self.imitate is not None and self.round % self.imitate == 0
+        self.k, self.last_imitation, self.cand_entry = k, 0, None
+
+    def _step_behind_read(self):
+        """Behind the read of the state: a learning round takes its step (``_imitate``)."""
+        if self.imitate_pending:
+            self._imitate()
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def read_candidates(self, n):
-        """cand0[n], the number of candidates of a round of n parents: the 4 bytes a strong round reads between the list and its chunks."""
-        return int(self.cand0[n:n + 1].cpu()[0])
+        """cand0[n], the number of candidates of a round of n parents: the 4 bytes a strong round reads between the list and its chunks.
+        ``cand_entry`` keeps it as the candidate range of the round's one entry."""
+        self.cand_entry = [0, int(self.cand0[n:n + 1].cpu()[0])]
+        return self.cand_entry[-1]
 
     def _strong_table(self, slots, n, dec, table=None):
         """Steps 2-6 of a strong round over the n parent rows the gather wrote: gnnb_babsr for the pre-filter (with
@@ -606,20 +639,16 @@ class FrontierRun(_Round):
                  pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT,
                  strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
-        _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice)
-        _check_branching(branching, branching_threshold, online_threshold)
-        self.branching = branching
-        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate)
-        self._upper_bound_options(witness, pgd_steps, pgd_step)
-        self._restart_options(pgd_restarts, pgd_seed)
-        _check_threshold(branching_threshold, kwbd_threshold)
-        _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
+        self._set_options(choice, branching=branching, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold, sparsest_layer=sparsest_layer,
+                          decision_threshold=decision_threshold, online_threshold=online_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step,
+                          pgd_restarts=pgd_restarts, pgd_seed=pgd_seed, imitate=imitate, imitate_margin=imitate_margin,
+                          strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit)
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
         self.K, self.n_iter, self.lr, self.eps, self.decision_bound = K, n_iter, float(lr), float(eps), decision_bound
         self.fixed, self.prop_layer = layers[:-1], layers[-1]
-        eng = self.eng = choice.model.engine() if online_threshold is None and imitate is None else choice._eng()      # (_eng: the engine with its optimizer)
+        eng = self.eng = self._engine_of(choice)
         in_shape = tuple(lp.input_lb.shape)
         eng.bind(self.fixed, in_shape)
         dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
@@ -633,30 +662,21 @@ class FrontierRun(_Round):
         self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
         self._witness_buffers(1)
         self.slots = None
-        self.threshold, self.m, self.m_e, self.M = branching_threshold, 0, [0], 0      # (m_e, M: the round as a plan of one entry)
-        if branching_threshold is not None:
-            self._threshold_buffers(K, ((1,), (eng.R,)), None, "gnnb_frontier_fallback_workspace_bytes", kwbd_threshold, sparsest_layer, decision_threshold)
+        self.m, self.m_e, self.M = 0, [0], 0                      # (m_e, M: the round as a plan of one entry)
+        if self.threshold is not None:
+            self._threshold_buffers(K, ((1,), (eng.R,)), None, "gnnb_frontier_fallback_workspace_bytes")
             self.m_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         if branching == "babsr":                                  # one intercept counter per run, zero at its start (relu_conv_any_kw.py:100)
-            self._babsr_buffers(K, (1,), sparsest_layer, decision_threshold)
+            self._babsr_buffers(K, (1,))
         if self.strong_on:                                        # the candidates' rows: the run's one box and property, 2 * strong_chunk times
             self._strong_buffers(K, tuple(t[:1].expand(2 * strong_chunk, *t.shape[1:]).contiguous() for t in (self.x_lo, self.x_hi, self.pw, self.pb)))
-        self.online, self.k, self.learn_pending, self.last_learn = online_threshold, 0, False, 0
-        self.online_steps = self.online_rows = 0
-        if online_threshold is not None:
-            self.kwbd_threshold = KWBD_NEVER
+        self.learn_pending, self.last_learn, self.online_steps, self.online_rows = False, 0, 0, 0
+        if self.online is not None:
             self.wrong = torch.zeros(eng.R, dtype=torch.int32, device=dev)
             self.learn_rows, self.learn_kw, self.n_learn = (torch.zeros(n, dtype=torch.int32, device=dev) for n in (K, K, 1))
             self.learn_imp, self.loss = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float32, device=dev)
             self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.imitate, self.imitate_margin, self.round, self.learning, self.imitate_pending = imitate, float(imitate_margin), 0, False, False
-        self.imitation_steps = self.imitation_rows = self.last_imitation = 0
-        if imitate is not None:
-            self.im_table = torch.zeros(K, eng.R, dtype=torch.float64, device=dev)
-            self.im_rows = torch.arange(K, dtype=torch.int32, device=dev)
-            self.im_loss, self.im_regret = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float64, device=dev)
-            self.im_report = torch.zeros(K, 4, dtype=torch.int32, device=dev)
-            self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._imitation_buffers(K)
 
     def _commit(self, slots):
         self.eng.frontier_commit(self.pool, slots, *self.Ch.children(), self.pool.state, eps=self.eps, decision_bound=self.decision_bound,
@@ -687,10 +707,7 @@ class FrontierRun(_Round):
     def launch_round(self, k, in_use):
         """One round over the k <= K open domains of lowest bound.  Device work only."""
         self.slots = self.pick(k, in_use)
-        if self.imitate is not None:                              # (a learning round: its table stays, its step runs behind the state record)
-            self.round += 1
-            self.learning = self.imitate_pending = self.round % self.imitate == 0
-            self.k, self.last_imitation = k, 0
+        self._begin_round(k)
         self._launch(self.slots, k)
 
     # ``_Round._fall_back``'s steps for one job (DESIGN.md section 7.5): gnnb_frontier_fallback, the read of m, gnnb_frontier_choose
@@ -716,7 +733,7 @@ class FrontierRun(_Round):
         if self.online is not None:                               # the learn rows of the round (section 7.7): read behind the state record
             self.eng.frontier_learn(k, self.P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong, self.learn_rows,
                                     self.learn_kw, self.learn_imp, self.n_learn)
-            self.k, self.learn_pending = k, True
+            self.learn_pending = True                             # (k: the round's, ``_begin_round`` kept it)
 
     def _witness(self, k, M):
         """gnnb_frontier_witness on the rows the commit will see."""
@@ -762,8 +779,7 @@ class FrontierRun(_Round):
         st = self.pool.state.cpu().tolist()
         if self.learn_pending:
             self._learn()
-        if self.imitate_pending:
-            self._imitate()
+        self._step_behind_read()
         return st
 
 
@@ -878,7 +894,7 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
                       strong_candidates, strong_chunk, strong_audit, branching)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
-        out = _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats)
+        out = _one_job_loop(run, max_rounds, log, trace, stats)
         if witness is not None:
             witness.append(run.witness())
         return out
@@ -887,61 +903,102 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
             choice.model.load_blob(run.eng.get_weights())
 
 
-def _one_job_loop(run, K, eps, max_rounds, decision_bound, log, trace, stats):
-    """``branch_and_bound_frontier``'s loop on a checked ``FrontierRun``."""
-    branching_threshold = run.threshold
-    branches = kw_bounded = 0
+def _one_job_loop(run, max_rounds, log, trace, stats):
+    """``branch_and_bound_frontier``'s loop on a checked ``FrontierRun``: every round is a plan of the one entry (segment 0, row 0, k)."""
     S = _lib
     st = run.root()
-    rounds, bounded = 0, 1
+    tally = _new_tally()
     log(f"root lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     while True:
         global_lb, global_ub, n_open, in_use = _global_lb(st), st[S.FS_GLOBAL_UB], int(st[S.FS_N_OPEN]), int(st[S.FS_IN_USE])
-        reason, k, compact = _one_job_round(st, K, run.capacity, eps, decision_bound, rounds, max_rounds)
+        reason, k, compact = _one_job_round(st, run.K, run.capacity, run.eps, run.decision_bound, tally["rounds"], max_rounds)
         if reason is not None:
             break
         if compact:                                               # the kept children beyond the k parents' slots go above in_use
             run.pool.compact(n_open)
             in_use = n_open
         run.launch_round(k, in_use)
-        if trace is not None:
-            trace.append(_trace_rows(run, 0, k))
-            if branching_threshold is not None:
-                trace[-1].update(_threshold_trace(run, k))
-        if (run.branching == "strong" and trace is not None) or run.strong_audit is not None:
-            rows = _strong_rows(run, k)
-            if trace is not None and run.branching == "strong":
-                trace[-1].update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
-            if run.strong_audit is not None:
-                run.strong_audit.extend(rows)
+        t = _report_launched(run, trace, 0, 0, k, {})
         st = run.read_state()
-        if trace is not None and run.online is not None:
-            trace[-1].update(_online_trace(run, st))
-        if trace is not None and run.imitate is not None and run.last_imitation:
-            n = run.last_imitation
-            trace[-1].update(imitation_loss=run.im_loss[:n].cpu().tolist(), imitation_regret=run.im_regret[:n].cpu().tolist(),
-                             imitation_report=run.im_report[:n].cpu().tolist())
-        if trace is not None and run.imitate is not None:
-            trace[-1].update(global_lb=_global_lb(st), global_ub=st[S.FS_GLOBAL_UB])
-        if trace is not None and run.witness_on:
-            trace[-1].update(global_ub=st[S.FS_GLOBAL_UB], witness_value=float(run.best_value.cpu()[0]))
+        if t is not None:
+            if run.online is not None:
+                t.update(_online_trace(run, st))
+            _report_read(run, t, 0, 0, k, st, _witness_values(run))
         _check_record(st)
-        rounds += 1
-        bounded += int(st[S.FS_KEPT] + st[S.FS_CLOSED] + st[S.FS_INFEASIBLE]) + 2 * run.m
-        branches, kw_bounded = branches + k, kw_bounded + run.m
-        log(f"round {rounds} picked {k} kept {int(st[S.FS_KEPT])} closed {int(st[S.FS_CLOSED])} infeasible {int(st[S.FS_INFEASIBLE])} open {int(st[S.FS_N_OPEN])} "
-            f"lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
+        _tally_entry(run, tally, 0, k, st)
+        log(f"round {tally['rounds']} picked {k} kept {int(st[S.FS_KEPT])} closed {int(st[S.FS_CLOSED])} infeasible {int(st[S.FS_INFEASIBLE])} "
+            f"open {int(st[S.FS_N_OPEN])} lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     run.check_status()
     if stats is not None:
-        stats.update(branches=branches, kw_bounded=kw_bounded, domains_bounded=bounded,
-                     kw_used=int(run.n_used.cpu()[0]) if branching_threshold is not None else 0)
+        stats.update({key: tally[key] for key in ("branches", "kw_bounded", "domains_bounded")},
+                     kw_used=int(run.n_used.cpu()[0]) if run.threshold is not None else 0)
         if run.online is not None:
             stats.update(online_steps=run.online_steps, online_rows=run.online_rows)
         if run.strong_on:
-            stats.update(strong_bounded=run.strong_bounded)
+            stats.update(strong_bounded=tally["strong_bounded"])
         if run.imitate is not None:
             stats.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows)
-    return global_lb, global_ub, rounds, bounded, reason
+    return global_lb, global_ub, tally["rounds"], tally["domains_bounded"], reason
+
+
+# ---- the report of a round, per plan entry: a one-job round is the entry (segment 0, row 0, k) -------------------------------------------
+def _report_launched(run, trace, e, row0, k, tag):
+    """The first half of the report of entry number ``e`` of the round just launched, the parent rows [row0, row0 + k), before
+    ``read_state`` (device-to-host copies; a traced or audited run only).  Appends the entry's dict to ``trace`` (unless None) and returns
+    it: ``tag``, ``_trace_rows``, the threshold part, and in "strong" mode the candidates and their improvements per parent; extends
+    ``run.strong_audit`` (unless None) by ``_strong_rows``' dicts with ``tag``.  tag: {} in a one-job run, the entry's "job", "segment"
+    and "round" in a many-jobs run.  (A round that computed no table -- ``cand_entry`` None -- has no strong rows.)"""
+    t = None
+    if trace is not None:
+        t = {**tag, **_trace_rows(run, row0, row0 + k)}
+        if run.threshold is not None:
+            t.update(_threshold_trace(run, k, e, row0))
+        trace.append(t)
+    traced_strong = t is not None and run.branching == "strong"
+    if (traced_strong or run.strong_audit is not None) and run.cand_entry is not None:
+        rows = _strong_rows(run, k, row0)
+        if traced_strong:
+            t.update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
+        if run.strong_audit is not None:
+            run.strong_audit.extend({**r, **tag} for r in rows)
+    return t
+
+
+def _witness_values(run):
+    """The ONE host copy of ``best_value`` a traced round of a run with a witness makes, behind ``read_state`` (None without a witness)."""
+    return run.best_value.cpu().tolist() if run.witness_on else None
+
+
+def _report_read(run, t, seg, row0, k, st, values):
+    """The second half, behind ``read_state``, into the entry's trace dict ``t``: on a learning round that took a step the loss, regret
+    and report of the entry's rows; in a run with ``imitate`` the bounds of the entry's record ``st`` after the round; in a run with a
+    witness global_ub and the device's copy of it, element ``seg`` of ``values`` (``_witness_values``)."""
+    a, b = row0, row0 + k
+    if run.imitate is not None:
+        if run.last_imitation:
+            t.update(imitation_loss=run.im_loss[a:b].cpu().tolist(), imitation_regret=run.im_regret[a:b].cpu().tolist(),
+                     imitation_report=run.im_report[a:b].cpu().tolist())
+        t.update(global_lb=_global_lb(st), global_ub=st[_lib.FS_GLOBAL_UB])
+    if run.witness_on:
+        t.update(global_ub=st[_lib.FS_GLOBAL_UB], witness_value=values[seg])
+
+
+def _new_tally():
+    """The tally of a job whose root has been bounded."""
+    return {"rounds": 0, "domains_bounded": 1, "branches": 0, "kw_bounded": 0, "strong_bounded": 0}
+
+
+def _tally_entry(run, tally, e, k, st):
+    """Entry number ``e`` of the round just read, k parents with the record ``st``, added to its job's tally: the round, the domains
+    bounded (what the commit kept, closed or found infeasible, and in threshold mode both children of the entry's m KW pairs), the
+    parents branched, the KW pairs bounded and the candidate children (none in a round without a table)."""
+    m = run.m_e[e] if run.threshold is not None else 0
+    c = run.cand_entry
+    tally["rounds"] += 1
+    tally["domains_bounded"] += int(st[_lib.FS_KEPT] + st[_lib.FS_CLOSED] + st[_lib.FS_INFEASIBLE]) + 2 * m
+    tally["branches"], tally["kw_bounded"] = tally["branches"] + k, tally["kw_bounded"] + m
+    if c is not None:
+        tally["strong_bounded"] += 2 * (c[e + 1] - c[e])
 
 
 def _strong_rows(run, k, row0=0):
@@ -1127,11 +1184,13 @@ class JobsRun(_Round):
     def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
                  sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
                  pgd_seed=0, branching="gnn"):
-        _check_threshold(branching_threshold, kwbd_threshold)
-        _check_branching(branching, branching_threshold, None)
-        self.branching = branching
-        self._upper_bound_options(witness, pgd_steps, pgd_step)
-        self._restart_options(pgd_restarts, pgd_seed)
+        self._set_options(choice, branching=branching, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold, sparsest_layer=sparsest_layer,
+                          decision_threshold=decision_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step, pgd_restarts=pgd_restarts,
+                          pgd_seed=pgd_seed)
+        self._make(choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps)
+
+    def _make(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps):
+        """The pool, the jobs' tables and the rows of a run whose options are set (``_set_options``)."""
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
         eng = self.eng = self._engine_of(choice)
@@ -1167,18 +1226,17 @@ class JobsRun(_Round):
         self.flags_host = torch.zeros(S, dtype=i32).pin_memory()
         self.flags = torch.zeros(S, dtype=i32, device=dev)
         self.slot_seg = torch.arange(S * cap, device=dev) // cap
-        self.threshold, self.m_e, self.M = branching_threshold, [0], 0
-        if branching_threshold is not None:
+        self.m_e, self.M = [0], 0
+        if self.threshold is not None:
             # pair B's rows belong to the selected parents' jobs: boxes and property rows of their own (gnnb_frontier_fallback_jobs fills them)
             self.bx_lo, self.bx_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
             self.bpw, self.bpb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
             # per segment: the counter, the table and n_used, the KW pairs taken since its job was admitted
-            self._threshold_buffers(n, ((S,), (S, eng.R)), (self.bx_lo, self.bx_hi, self.bpw, self.bpb), "gnnb_frontier_fallback_jobs_workspace_bytes",
-                                    kwbd_threshold, sparsest_layer, decision_threshold)
+            self._threshold_buffers(n, ((S,), (S, eng.R)), (self.bx_lo, self.bx_hi, self.bpw, self.bpb), "gnnb_frontier_fallback_jobs_workspace_bytes")
             self.m_entry = torch.zeros(S + 1, dtype=i32, device=dev)
             self.job_used = torch.zeros(len(jobs), dtype=torch.int64, device=dev)    # KW pairs taken per job, once it has left
-        if branching == "babsr":                                  # per segment: the intercept counter of its job (section 7.10)
-            self._babsr_buffers(n, (S,), sparsest_layer, decision_threshold)
+        if self.branching == "babsr":                             # per segment: the intercept counter of its job (section 7.10)
+            self._babsr_buffers(n, (S,))
 
     def release(self, seg):
         """The job of segment ``seg`` leaves: no open slot, the start record."""
@@ -1250,8 +1308,10 @@ class JobsRun(_Round):
         pool.state[:, _lib.FS_IN_USE] = torch.where(self.flags > 0, pool.state[:, _lib.FS_N_OPEN], pool.state[:, _lib.FS_IN_USE])
 
     def launch_round(self, entries):
-        """One round over the plan's entries [(segment, row0, k)].  Device work only."""
+        """One round over the plan's entries [(segment, row0, k)], launched round number ``round`` of the run (``_begin_round``).  Device
+        work only -- but for the one read of a run with a table, ``StrongJobsRun.read_candidates``."""
         self.plan.send(entries)
+        self._begin_round(self.plan.n)
         self.eng.frontier_pick_jobs(self.pool, self.plan, self.pool.state, self.slots, self.row_seg)
         self._rows_of_plan()
         self._launch(self.slots[:self.plan.n], self.plan.n)
@@ -1307,43 +1367,24 @@ class StrongJobsRun(JobsRun):
                  sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
                  pgd_seed=0, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
                  strong_audit=None, branching="strong"):
-        _check_branching(branching, branching_threshold, None)
-        _check_imitate(imitate, imitate_margin, branching, branching_threshold, None, choice)
-        self._strong_options(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, None, imitate)      # (_buffers sizes by strong_on)
+        self._set_options(choice, branching=branching, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold, sparsest_layer=sparsest_layer,
+                          decision_threshold=decision_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step, pgd_restarts=pgd_restarts,
+                          pgd_seed=pgd_seed, imitate=imitate, imitate_margin=imitate_margin, strong_candidates=strong_candidates,
+                          strong_chunk=strong_chunk, strong_audit=strong_audit)
         _check_jobs_strong(branching, strong_audit, imitate)
-        self.imitate, self.imitate_margin = imitate, float(imitate_margin)
-        super().__init__(choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold, kwbd_threshold, sparsest_layer,
-                         decision_threshold, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, branching)
+        self._make(choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps)      # (``JobsRun``'s, on the options set here)
         eng, dev, n = self.eng, self.eng.device, segments * K
-        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        f64, f32 = torch.float64, torch.float32
         N0, NL, rows = eng.sizes[0], eng.sizes[-2], 2 * strong_chunk
         # the candidates' rows belong to the jobs of their parents: boxes and property rows of their own (gnnb_strong_rows_jobs fills them)
         self._strong_buffers(n, (torch.zeros(rows, N0, dtype=f64, device=dev), torch.zeros(rows, N0, dtype=f64, device=dev),
                                  torch.zeros(rows, NL, dtype=f32, device=dev), torch.zeros(rows, dtype=f32, device=dev)))
         self.cand_idx = torch.zeros(segments + 1, dtype=torch.int64, device=dev)      # the rows of cand0 a round reads: every entry's row0, and n
-        self.cand_entry = None
-        self.round, self.k = 0, 0
-        if imitate is not None:
-            self.im_table = torch.zeros(n, eng.R, dtype=f64, device=dev)
-            self.im_rows = torch.arange(n, dtype=i32, device=dev)
-            self.im_loss, self.im_regret = torch.zeros(n, dtype=f32, device=dev), torch.zeros(n, dtype=f64, device=dev)
-            self.im_report = torch.zeros(n, 4, dtype=i32, device=dev)
-            self.step_status = torch.zeros(1, dtype=i32, device=dev)
-
-    def _engine_of(self, choice):
-        return choice.model.engine() if self.imitate is None else choice._eng()      # (_eng: the engine with its optimizer)
+        self._imitation_buffers(n)
 
     def _strong_chunk_rows(self, q0, c):
         box = self.ChS.box
         self.eng.strong_rows_jobs(self.cand_slot[q0:q0 + c], c, self.S, self.cap, self.seg_x_lo, self.seg_x_hi, self.seg_pw, self.seg_pb, *box)
-
-    def launch_round(self, entries):
-        """``JobsRun.launch_round`` as launched round number ``round`` of the run (1-based; root phases do not count): a learning round
-        when that number is a multiple of ``imitate``."""
-        self.round += 1
-        self.learning = self.imitate_pending = self.imitate is not None and self.round % self.imitate == 0
-        self.k, self.last_imitation, self.cand_entry = sum(e[2] for e in entries), 0, None
-        super().launch_round(entries)
 
     def read_candidates(self, n):
         """cand0 at every entry's first row and cand0[n]: the 4 (entries + 1) bytes a round with a table reads between the list and its
@@ -1366,8 +1407,7 @@ class StrongJobsRun(JobsRun):
     def read_state(self):
         """``JobsRun.read_state``; a learning round then takes its step (``_imitate``), behind the records."""
         st = super().read_state()
-        if self.imitate_pending:
-            self._imitate()
+        self._step_behind_read()
         return st
 
 
@@ -1382,20 +1422,11 @@ class FrontierJobs(list):
         self.pgd_restarts, self.pgd_seed = pgd_restarts, pgd_seed              # (section 7.9)
 
 
-def _upper_of(jobs):
-    """The witness and descent options a ``FrontierJobs`` carries, checked (None for any other sequence of jobs: everything off)."""
+def _options_of(jobs):
+    """The keywords of ``JobsRun`` a ``FrontierJobs`` carries ({} for any other sequence of jobs: everything off).  The run checks them."""
     if not isinstance(jobs, FrontierJobs):
-        return None
-    _check_witness(jobs.witness, jobs.pgd_steps, jobs.pgd_step)
-    return {"witness": jobs.witness, "pgd_steps": jobs.pgd_steps, "pgd_step": jobs.pgd_step}
-
-
-def _restarts_of(jobs):
-    """The restart options a ``FrontierJobs`` carries, checked (None for any other sequence of jobs: off)."""
-    if not isinstance(jobs, FrontierJobs):
-        return None
-    _check_restarts(jobs.pgd_restarts, jobs.pgd_seed, jobs.pgd_steps)
-    return {"pgd_restarts": jobs.pgd_restarts, "pgd_seed": jobs.pgd_seed}
+        return {}
+    return {"witness": jobs.witness, "pgd_steps": jobs.pgd_steps, "pgd_step": jobs.pgd_step, "pgd_restarts": jobs.pgd_restarts, "pgd_seed": jobs.pgd_seed}
 
 
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
@@ -1414,9 +1445,10 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
     and a job's witness and bounds are what it gets alone with the same options.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    options = _options_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, upper=upper, restarts=restarts)
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **options)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace)
 
 
 def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
@@ -1436,13 +1468,13 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    options = _options_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if branching_threshold is None:
         raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
-    threshold = {"branching_threshold": branching_threshold, "kwbd_threshold": kwbd_threshold, "sparsest_layer": sparsest_layer,
-                 "decision_threshold": decision_threshold}
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold, stats, upper, restarts)
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold,
+                  sparsest_layer=sparsest_layer, decision_threshold=decision_threshold, **options)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats)
 
 
 def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, sparsest_layer=0,
@@ -1457,10 +1489,11 @@ def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, cap
     "decisions" are BaBSR's.  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    options = _options_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    babsr = {"branching": "babsr", "sparsest_layer": sparsest_layer, "decision_threshold": decision_threshold}
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, None, stats, upper, restarts, babsr)
+    run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, sparsest_layer=sparsest_layer, decision_threshold=decision_threshold,
+                  branching="babsr", **options)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats)
 
 
 def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print,
@@ -1494,61 +1527,51 @@ def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, ca
     and "round".  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    upper, restarts = _upper_of(jobs), _restarts_of(jobs)
+    options = _options_of(jobs)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
-    _check_branching(branching, None, None)
-    _check_imitate(imitate, imitate_margin, branching, None, None, choice)
-    _check_strong(strong_candidates, strong_chunk, strong_audit, branching, None, None, imitate)
-    _check_jobs_strong(branching, strong_audit, imitate)
     if learned is not None and not isinstance(learned, dict):
         raise ValueError(f"learned = {learned!r}: None, or a dict that receives the run's learning counts")
-    strong = {"imitate": imitate, "imitate_margin": imitate_margin, "strong_candidates": strong_candidates, "strong_chunk": strong_chunk,
-              "strong_audit": strong_audit, "branching": branching}
-    return _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, None, stats, upper, restarts, None,
-                        strong, learned)
+    run = StrongJobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, imitate=imitate, imitate_margin=imitate_margin,
+                        strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit, branching=branching, **options)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, learned)
 
 
-def _verify_jobs(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, max_rounds, log, trace, threshold=None, stats=None, upper=None,
-                 restarts=None, babsr=None, strong=None, learned=None):
-    """The loop of ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr`` and ``verify_properties_strong`` on
-    checked arguments.  threshold: None, or the threshold mode's arguments of ``JobsRun``; with None a round launches and reads exactly what
-    section 7.4 lists.  upper: None, or the witness and descent options of section 7.8; restarts: None, or the restart options of section
-    7.9; babsr: None, or the arguments of ``JobsRun`` that make every job branch on BaBSR alone (section 7.10); strong: None, or the
-    arguments ``StrongJobsRun`` adds to ``JobsRun``'s (section 7.13), which make the run one of that class; learned: None, or the dict that
-    receives such a run's "imitation_steps", "imitation_rows" and launched "rounds"."""
-    run = (JobsRun if strong is None else StrongJobsRun)(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **(threshold or {}),
-                                                         **(upper or {}), **(restarts or {}), **(babsr or {}), **(strong or {}))
+def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=None):
+    """``_jobs_loop`` on a checked run, for ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr`` and
+    ``verify_properties_strong``; when the run ends (or raises) after a learning step, ``choice.model`` receives the device's parameters."""
     run.keep_pairs = trace is not None
     try:
-        return _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, threshold, stats, upper, babsr, strong, learned)
+        return _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned)
     finally:
         if run.imitation_steps:                                   # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it
             choice.model.load_blob(run.eng.get_weights())
 
 
-def _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, threshold, stats, upper, babsr, strong, learned):
-    """``_verify_jobs``' loop on its run."""
-    witness = (upper or {}).get("witness")
-    F, thr = _lib, threshold is not None
-    results, rounds, bounded = [None] * len(jobs), [0] * len(jobs), [0] * len(jobs)
-    branches, kw_bounded, strong_bounded = [0] * len(jobs), [0] * len(jobs), [0] * len(jobs)
+def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):
+    """``_verify_jobs``' loop on its run, which knows the rest: K, the segments and their capacity, eps, and what is on -- ``threshold``
+    (a round has a second half, and stats are the threshold mode's), ``branching`` and ``strong_on`` (theirs), ``witness_on``.  stats:
+    None, or the list that receives per job the mode's part of its tally; learned: None, or the dict that receives the run's
+    "imitation_steps", "imitation_rows" and launched "rounds"."""
+    F, K, S, cap, thr = _lib, run.K, run.S, run.cap, run.threshold is not None
+    results, tally = [None] * len(jobs), [None] * len(jobs)
     seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
     waiting = list(range(len(jobs)))
 
     def reason_of(s):
         j = seg_job[s]
-        if rec[s][F.FS_INFEASIBLE] > 0 and rounds[j] == 0:
+        if rec[s][F.FS_INFEASIBLE] > 0 and tally[j]["rounds"] == 0:
             return "infeasible_root"
-        return "capacity" if capacity_stop[s] else _stop_reason(rec[s], eps, jobs[j].decision_bound, rounds[j], max_rounds)
+        return "capacity" if capacity_stop[s] else _stop_reason(rec[s], run.eps, jobs[j].decision_bound, tally[j]["rounds"], max_rounds)
 
     while True:
         for s in range(S):                                        # 1. the finished jobs leave
             j = seg_job[s]
             reason = None if j is None else reason_of(s)
             if reason is not None:
-                inf = float("inf")
-                results[j] = (inf, inf, 0, 1, reason) if reason == "infeasible_root" else (_global_lb(rec[s]), rec[s][F.FS_GLOBAL_UB], rounds[j], bounded[j], reason)
-                log(f"job {j} segment {s}: {reason} after {rounds[j]} rounds, lb {results[j][0]:.5f} ub {results[j][1]:.5f}")
+                inf, rounds = float("inf"), tally[j]["rounds"]
+                results[j] = ((inf, inf, 0, 1, reason) if reason == "infeasible_root" else
+                              (_global_lb(rec[s]), rec[s][F.FS_GLOBAL_UB], rounds, tally[j]["domains_bounded"], reason))
+                log(f"job {j} segment {s}: {reason} after {rounds} rounds, lb {results[j][0]:.5f} ub {results[j][1]:.5f}")
                 if thr:
                     run.keep_used(s, j)
                 if run.witness_on:
@@ -1565,7 +1588,7 @@ def _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, thre
             run.launch_roots(admitted)
             st = run.read_state()
             for s in admitted:
-                rec[s], bounded[seg_job[s]] = st[s], 1
+                rec[s], tally[seg_job[s]] = st[s], _new_tally()
                 if not rec[s][F.FS_INFEASIBLE] > 0:
                     _check_record(rec[s])
                 log(f"job {seg_job[s]} segment {s}: root lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
@@ -1579,56 +1602,30 @@ def _jobs_loop(run, jobs, in_shape, K, S, cap, eps, max_rounds, log, trace, thre
         if any(compact):
             run.compact(compact)
         run.launch_round(entries)
-        if trace is not None:
-            for e, (s, row0, k) in enumerate(entries):
-                trace.append({"job": seg_job[s], "segment": s, "round": rounds[seg_job[s]], **_trace_rows(run, row0, row0 + k)})
-                if thr:
-                    trace[-1].update(_threshold_trace(run, k, e, row0))
-        if strong is not None and ((run.branching == "strong" and trace is not None) or run.strong_audit is not None) and run.cand_entry is not None:
-            for e, (s, row0, k) in enumerate(entries):            # section 7.11's rows, per entry
-                rows = _strong_rows(run, k, row0)
-                if trace is not None and run.branching == "strong":
-                    trace[e - len(entries)].update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
-                if run.strong_audit is not None:
-                    run.strong_audit.extend({**r, "job": seg_job[s], "segment": s, "round": rounds[seg_job[s]]} for r in rows)
+        traced = [_report_launched(run, trace, e, row0, k, {"job": seg_job[s], "segment": s, "round": tally[seg_job[s]]["rounds"]})
+                  for e, (s, row0, k) in enumerate(entries)]
         st = run.read_state()
-        if trace is not None and run.imitate is not None:         # the learning round's step, per entry, and the bounds after the round
-            for e, (s, row0, k) in enumerate(entries):
-                if run.last_imitation:
-                    trace[e - len(entries)].update(imitation_loss=run.im_loss[row0:row0 + k].cpu().tolist(),
-                                                   imitation_regret=run.im_regret[row0:row0 + k].cpu().tolist(),
-                                                   imitation_report=run.im_report[row0:row0 + k].cpu().tolist())
-                trace[e - len(entries)].update(global_lb=_global_lb(st[s]), global_ub=st[s][F.FS_GLOBAL_UB])
-        if trace is not None and run.witness_on:
-            values = run.best_value.cpu().tolist()
-            for e, (s, _, _) in enumerate(entries):
-                trace[e - len(entries)].update(global_ub=st[s][F.FS_GLOBAL_UB], witness_value=values[s])
+        if trace is not None:
+            values = _witness_values(run)
+            for (s, row0, k), t in zip(entries, traced):
+                _report_read(run, t, s, row0, k, st[s], values)
         for e, (s, _, k) in enumerate(entries):
             j = seg_job[s]
             rec[s] = st[s]
             _check_record(rec[s])
-            rounds[j] += 1
-            bounded[j] += int(rec[s][F.FS_KEPT] + rec[s][F.FS_CLOSED] + rec[s][F.FS_INFEASIBLE])
-            if thr:                                               # the children of both pairs
-                bounded[j], branches[j], kw_bounded[j] = bounded[j] + 2 * run.m_e[e], branches[j] + k, kw_bounded[j] + run.m_e[e]
-            elif babsr is not None or strong is not None:
-                branches[j] += k
-            if strong is not None and run.cand_entry is not None:  # the entry's candidate children (a round without a table bounds none)
-                strong_bounded[j] += 2 * (run.cand_entry[e + 1] - run.cand_entry[e])
-            log(f"job {j} round {rounds[j]} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
+            _tally_entry(run, tally[j], e, k, rec[s])
+            log(f"job {j} round {tally[j]['rounds']} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
                 f"infeasible {int(rec[s][F.FS_INFEASIBLE])} open {int(rec[s][F.FS_N_OPEN])} lb {_global_lb(rec[s]):.5f} ub {rec[s][F.FS_GLOBAL_UB]:.5f}")
     run.check_status()
-    if witness is not None:                                       # N_0 floats per job, read once
+    if run.witness_on:                                            # N_0 floats per job, read once
         points = run.job_point.cpu()
-        witness.extend(None if math.isinf(results[j][1]) else points[j].reshape(in_shape) for j in range(len(jobs)))
-    if thr and stats is not None:
+        run.witness_to.extend(None if math.isinf(results[j][1]) else points[j].reshape(run.in_shape) for j in range(len(jobs)))
+    if stats is not None and thr:
         used = run.job_used.cpu().tolist()
-        stats.extend({"branches": branches[j], "kw_bounded": kw_bounded[j], "domains_bounded": results[j][3], "kw_used": int(used[j])}
-                     for j in range(len(jobs)))
-    if babsr is not None and stats is not None:
-        stats.extend({"branches": branches[j], "domains_bounded": results[j][3]} for j in range(len(jobs)))
-    if strong is not None and stats is not None:
-        stats.extend({"branches": branches[j], "domains_bounded": results[j][3], "strong_bounded": strong_bounded[j]} for j in range(len(jobs)))
-    if strong is not None and learned is not None:
+        stats.extend({**{key: t[key] for key in ("branches", "kw_bounded", "domains_bounded")}, "kw_used": int(used[j])} for j, t in enumerate(tally))
+    elif stats is not None:                                       # BaBSR: the first two; a run with a table: all three
+        keys = ("branches", "domains_bounded", "strong_bounded")[:3 if run.strong_on else 2]
+        stats.extend({key: t[key] for key in keys} for t in tally)
+    if learned is not None:
         learned.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows, rounds=run.round)
     return results

@@ -217,3 +217,187 @@ def test_the_threshold_trace_of_a_plan_entry_is_the_dict_written_out_by_hand(cas
     public docstrings, with "selected" counted from the entry's first row and pair B's range from the sum of the m before the entry."""
     args, expected = THRESHOLD_TRACE_CASES[case]
     assert frontier._threshold_trace(*args) == expected
+
+
+# ---- the report of a round, per plan entry -------------------------------------------------------------------------------------------------
+def _launched(branching="strong", audit=None, imitate=None, last_imitation=0, witness=False):
+    """A hand-made run of 5 parent rows (10 children) and 7 candidates after ``launch_round``, as the report reads it.  Row i: slot 10 + i,
+    decision [0, i], table decision [1, i], parent bound -2 (row 3: 0.5); child c: bound -c / 4, upper value c / 2, live, infeasible
+    only for c = 3.  Candidate q: improvement q / 8; rows 0..4 hold 2, 0, 3, 1, 1 of them (cand0 below), graph layers of 10 and 6 ReLUs.
+    The step's loss i / 2, regret i / 4 and report [i, i + 1, i + 2, i + 3]; the incumbents' values 7, 8, 9 for segments 0, 1, 2."""
+    import types
+    import torch
+    i5, i10, ns = torch.arange(5), torch.arange(10), types.SimpleNamespace
+    dec = lambda layer: torch.stack([torch.full((5,), layer), i5], dim=1).to(torch.int32)      # noqa: E731
+    parent = torch.tensor([-2.0, -2.0, -2.0, 0.5, -2.0], dtype=torch.float64)
+    return ns(branching=branching, threshold=None, strong_audit=audit, imitate=imitate, last_imitation=last_imitation, witness_on=witness,
+              eng=ns(sizes=[4, 10, 6, 1]), slots=(10 + i5).to(torch.int32), P=ns(bound=parent, dec=dec(0)), parent_bound=parent, s_dec=dec(1),
+              Ch=ns(bound=-i10.double() / 4, ubv=i10.double() / 2, live=torch.ones(10, dtype=torch.int32), infeasible=(i10 == 3).to(torch.int32)),
+              cand0=torch.tensor([0, 2, 2, 5, 6, 7], dtype=torch.int32), cand_entry=[0, 7], s_best=torch.tensor([0.125, -1.0, 0.5, 0.625, 0.75]).double(),
+              cand_dec=torch.tensor([[0, 1], [1, 2], [0, 3], [0, 4], [1, 0], [1, 5], [0, 9]], dtype=torch.int32), s_imp=torch.arange(7).double() / 8,
+              im_loss=i5.float() / 2, im_regret=i5.double() / 4, im_report=torch.stack([i5 + d for d in range(4)], dim=1).to(torch.int32),
+              best_value=torch.tensor([7.0, 8.0, 9.0], dtype=torch.float64))
+
+
+ONE_JOB = [(0, 0, 5)]
+TWO_JOBS = [(0, 0, 2), (2, 2, 3)]                             # (segment, row0, k): the second entry starts at row 2, child 4, candidate 2
+TAGS = [{"job": 5, "segment": 0, "round": 3}, {"job": 6, "segment": 2, "round": 0}]
+RECORDS = [_record(3, 5), None, _record(4, 6, gub=3.0, closed=-4.0)]      # per segment: bounds (-1, 1) and (-4, 3)
+ROWS = {"slots": [10, 11, 12, 13, 14], "parent_bounds": [-2.0, -2.0, -2.0, 0.5, -2.0], "decisions": [[0, 0], [0, 1], [0, 2], [0, 3], [0, 4]],
+        "child_bounds": [0.0, -0.25, -0.5, -0.75, -1.0, -1.25, -1.5, -1.75, -2.0, -2.25], "child_ub": [0.0, 0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5, 4.0, 4.5],
+        "live": [1] * 10, "infeasible": [0, 0, 0, 1, 0, 0, 0, 0, 0, 0]}
+CANDIDATES = {"strong_candidates": [[1, 12], [], [3, 4, 10], [15], [9]], "strong_improvement": [[0.0, 0.125], [], [0.25, 0.375, 0.5], [0.625], [0.75]]}
+ENTRY_0 = {"slots": [10, 11], "parent_bounds": [-2.0, -2.0], "decisions": [[0, 0], [0, 1]], "child_bounds": [0.0, -0.25, -0.5, -0.75],
+           "child_ub": [0.0, 0.5, 1.0, 1.5], "live": [1, 1, 1, 1], "infeasible": [0, 0, 0, 1], "strong_candidates": [[1, 12], []],
+           "strong_improvement": [[0.0, 0.125], []]}
+ENTRY_1 = {"slots": [12, 13, 14], "parent_bounds": [-2.0, 0.5, -2.0], "decisions": [[0, 2], [0, 3], [0, 4]],
+           "child_bounds": [-1.0, -1.25, -1.5, -1.75, -2.0, -2.25], "child_ub": [2.0, 2.5, 3.0, 3.5, 4.0, 4.5], "live": [1] * 6, "infeasible": [0] * 6,
+           "strong_candidates": [[3, 4, 10], [15], [9]], "strong_improvement": [[0.25, 0.375, 0.5], [0.625], [0.75]]}
+# improvement of the committed pair: (min(lb0, 0) + min(lb1, 0) + 4) / 4 on the parent bound -2, an infeasible child counting 0; 1 for row 3
+OWN = [(0 - 0.25 + 4) / 4, (-0.5 + 0 + 4) / 4, (-1 - 1.25 + 4) / 4, 1.0, (-2 - 2.25 + 4) / 4]
+
+
+def _audit_rows(strong_decision_layer, tags=None):
+    return [{"slot": 10 + i, "decision": [0, i], "improvement": OWN[i], "strong_decision": [strong_decision_layer, i],
+             "best_improvement": [0.125, -1.0, 0.5, 0.625, 0.75][i], "candidates": CANDIDATES["strong_candidates"][i],
+             "improvements": CANDIDATES["strong_improvement"][i], **(tags[i >= 2] if tags else {})} for i in range(5)]
+
+
+def _report(run, entries, tags):
+    """Both halves of the report over a plan's entries, as the two loops call them around ``read_state``."""
+    trace = []
+    made = [frontier._report_launched(run, trace, e, row0, k, tags[e]) for e, (s, row0, k) in enumerate(entries)]
+    assert all(a is b for a, b in zip(made, trace)) and len(trace) == len(entries)
+    values = frontier._witness_values(run)
+    for (s, row0, k), t in zip(entries, trace):
+        frontier._report_read(run, t, s, row0, k, RECORDS[s], values)
+    return trace
+
+
+def _concatenated(one, two):
+    """The one-job report of rows [0, 5) is the two entries' reports joined key by key, the tags and the per-record keys aside."""
+    per_record = ("global_lb", "global_ub", "witness_value")
+    assert set(one) == set(two[0]) - set(TAGS[0]) == set(two[1]) - set(TAGS[1]) and not set(one) & set(TAGS[0])
+    for key in set(one) - set(per_record):
+        assert one[key] == two[0][key] + two[1][key], key
+
+
+def test_the_report_of_a_round_is_per_entry_the_dict_written_out_by_hand():
+    # 1. and 2.: "strong" mode, traced and audited: the one-job entry, then the two entries of a plan
+    run = _launched(audit=[])
+    one, = _report(run, ONE_JOB, [{}])
+    assert one == {**ROWS, **CANDIDATES} and run.strong_audit == _audit_rows(0)
+    run = _launched(audit=[])
+    two = _report(run, TWO_JOBS, TAGS)
+    assert two == [{**TAGS[0], **ENTRY_0}, {**TAGS[1], **ENTRY_1}] and run.strong_audit == _audit_rows(0, TAGS)
+    _concatenated(one, two)
+    # 3. "gnn" with an audit: the table's own decisions are read, and the trace has no strong key
+    run = _launched("gnn", audit=[])
+    one, = _report(run, ONE_JOB, [{}])
+    assert one == ROWS and run.strong_audit == _audit_rows(1)
+    run = _launched("gnn", audit=[])
+    two = _report(run, TWO_JOBS, TAGS)
+    assert run.strong_audit == _audit_rows(1, TAGS) and not any(key.startswith("strong") for t in two for key in t)
+    _concatenated(one, two)
+    run = _launched("gnn")                                    # (neither: the strong rows are not read at all)
+    del run.cand0, run.s_best, run.cand_dec, run.s_imp, run.s_dec, run.parent_bound
+    assert _report(run, ONE_JOB, [{}]) == [ROWS]
+    # 4. a learning round that took a step, and one that took none: the bounds stay
+    step = {"imitation_loss": [0.0, 0.5, 1.0, 1.5, 2.0], "imitation_regret": [0.0, 0.25, 0.5, 0.75, 1.0],
+            "imitation_report": [[0, 1, 2, 3], [1, 2, 3, 4], [2, 3, 4, 5], [3, 4, 5, 6], [4, 5, 6, 7]]}
+    one, = _report(_launched(imitate=2, last_imitation=5), ONE_JOB, [{}])
+    assert one == {**ROWS, **CANDIDATES, **step, "global_lb": -1.0, "global_ub": 1.0}
+    two = _report(_launched(imitate=2, last_imitation=5), TWO_JOBS, TAGS)
+    assert two[1] == {**TAGS[1], **ENTRY_1, **{key: v[2:] for key, v in step.items()}, "global_lb": -4.0, "global_ub": 3.0}
+    assert (two[0]["global_lb"], two[0]["global_ub"]) == (-1.0, 1.0)
+    _concatenated(one, two)
+    one, = _report(_launched(imitate=2, last_imitation=0), ONE_JOB, [{}])
+    assert one == {**ROWS, **CANDIDATES, "global_lb": -1.0, "global_ub": 1.0}
+    two = _report(_launched(imitate=2, last_imitation=0), TWO_JOBS, TAGS)
+    assert two[1] == {**TAGS[1], **ENTRY_1, "global_lb": -4.0, "global_ub": 3.0}
+    _concatenated(one, two)
+    # 5. a run with a witness: element 0, or element ``segment``, of the one host copy
+    one, = _report(_launched("gnn", witness=True), ONE_JOB, [{}])
+    assert one == {**ROWS, "global_ub": 1.0, "witness_value": 7.0}
+    two = _report(_launched("gnn", witness=True), TWO_JOBS, TAGS)
+    assert [(t["global_ub"], t["witness_value"]) for t in two] == [(1.0, 7.0), (3.0, 9.0)]
+    _concatenated(one, two)
+    # an untraced, unaudited run reads nothing: no tensor is there to be read
+    import types
+    bare = types.SimpleNamespace(branching="strong", strong_audit=None, cand_entry=[0, 7])
+    assert frontier._report_launched(bare, None, 0, 0, 5, {}) is None
+
+
+def test_the_tally_of_a_job_is_counted_per_entry():
+    import types
+    record = _record(3, 5)
+    record[_lib.FS_KEPT], record[_lib.FS_CLOSED], record[_lib.FS_INFEASIBLE] = 3.0, 2.0, 1.0
+    tally = frontier._new_tally()
+    assert tally == {"rounds": 0, "domains_bounded": 1, "branches": 0, "kw_bounded": 0, "strong_bounded": 0}       # the root
+    frontier._tally_entry(types.SimpleNamespace(threshold=None, m_e=[0], cand_entry=None), tally, 1, 3, record)     # (m_e is not a plan's: not read)
+    assert tally == {"rounds": 1, "domains_bounded": 7, "branches": 3, "kw_bounded": 0, "strong_bounded": 0}
+    frontier._tally_entry(types.SimpleNamespace(threshold=0.5, m_e=[1, 2, 3], cand_entry=None), tally, 1, 4, record)      # both children of 2 KW pairs
+    assert tally == {"rounds": 2, "domains_bounded": 17, "branches": 7, "kw_bounded": 2, "strong_bounded": 0}
+    frontier._tally_entry(types.SimpleNamespace(threshold=None, m_e=[0], cand_entry=[0, 4, 9]), tally, 1, 2, record)      # 5 candidates, two children each
+    assert tally == {"rounds": 3, "domains_bounded": 23, "branches": 9, "kw_bounded": 2, "strong_bounded": 10}
+
+
+# ---- the options of a run ------------------------------------------------------------------------------------------------------------------
+def _options(choice=None, **kw):
+    import types
+    run = types.SimpleNamespace()
+    frontier._Round._set_options(run, choice, **kw)
+    return run
+
+
+def test_the_option_setter_leaves_every_kind_of_run_with_every_attribute():
+    """``_Round._set_options`` on a bare object with the keywords of ``FrontierRun``, ``JobsRun`` and ``StrongJobsRun``: what ``_launch``,
+    ``_buffers`` and the loops read exists, off where the kind does not take it; the derived values; the engine a run takes."""
+    import types
+    from gnn_branching_amd.graphnet.graph_score_online import GraphChoice
+
+    class Choice(GraphChoice):
+        model = types.SimpleNamespace(engine=lambda: "the model's engine")
+
+        def __init__(self):
+            pass
+
+        def _eng(self):
+            return "the engine with its optimizer"
+    upper = {"witness": None, "pgd_steps": None, "pgd_step": 1.0 / 64, "pgd_restarts": None, "pgd_seed": 0}
+    jobs = {"branching_threshold": None, "kwbd_threshold": 10, "sparsest_layer": 0, "decision_threshold": 0.001, "branching": "gnn", **upper}
+    strong = {**jobs, "imitate": None, "imitate_margin": 1.0, "strong_candidates": None, "strong_chunk": 256, "strong_audit": None, "branching": "strong"}
+    one = {**strong, "online_threshold": None, "branching": "gnn"}
+    off = {"threshold": None, "online": None, "kwbd_threshold": 10, "sparsest_layer": 0, "decision_threshold": 0.001, "witness_on": False,
+           "witness_to": None, "pgd_steps": None, "pgd_step": 1.0 / 64, "restarts": 0, "pgd_seed": 0, "imitate": None, "imitate_margin": 1.0, "learns": False,
+           "strong_M": 0, "strong_chunk": 256, "strong_audit": None, "round": 0, "k": 0, "strong_n": 0, "imitation_steps": 0, "imitation_rows": 0,
+           "last_imitation": 0, "learning": False, "imitate_pending": False, "cand_entry": None, "im_table": None}
+    assert vars(_options(**one)) == vars(_options(**jobs)) == vars(_options()) == {**off, "branching": "gnn", "strong_on": False}
+    assert vars(_options(**strong)) == {**off, "branching": "strong", "strong_on": True}
+    # the derived values
+    audit, point = [], []
+    assert _options(strong_audit=audit).strong_on and _options(strong_audit=audit).strong_audit is audit and _options(strong_audit=audit).branching == "gnn"
+    assert _options(Choice(), imitate=3).strong_on and _options(Choice(), imitate=3, imitate_margin=2).imitate_margin == 2.0
+    assert not _options(branching="babsr").strong_on and _options(branching="babsr", sparsest_layer=True).sparsest_layer == 1
+    assert (_options(branching="strong", strong_candidates=8).strong_M, _options(branching="strong", strong_chunk=7).strong_chunk) == (8, 7)
+    run = _options(witness=point, pgd_steps=4, pgd_step=1, pgd_restarts=3, pgd_seed=11)
+    assert (run.witness_on, run.witness_to is point, run.pgd_steps, run.pgd_step, run.restarts, run.pgd_seed) == (True, True, 4, 1.0, 3, 11)
+    assert type(run.pgd_step) is float and _options(pgd_steps=4, pgd_restarts=0).restarts == 0
+    run = _options(branching_threshold=0.25, kwbd_threshold=3, sparsest_layer=1, decision_threshold=1)
+    assert (run.threshold, run.kwbd_threshold, run.sparsest_layer, run.decision_threshold, run.online) == (0.25, 3, 1, 1.0, None)
+    run = _options(Choice(), branching_threshold=0.25, online_threshold=5)
+    assert (run.online, run.kwbd_threshold, run.learns, run.imitate) == (5, frontier.KWBD_NEVER, True, None)
+    # the engine: the one with the optimizer where the parameters move
+    engine_of = lambda **kw: frontier._Round._engine_of(_options(Choice(), **kw), Choice())      # noqa: E731
+    assert engine_of() == engine_of(branching="strong") == engine_of(strong_audit=[]) == engine_of(branching_threshold=0.5) == "the model's engine"
+    assert engine_of(imitate=1) == engine_of(imitate=2, branching="strong") == engine_of(branching_threshold=0.5, online_threshold=1) \
+        == "the engine with its optimizer"
+    # the checks run in the one stated order: imitate, branching, strong, witness, restarts, threshold, online
+    order = [("imitate", {"imitate": 0}), ("branching", {"branching": "x"}), ("strong_chunk", {"strong_chunk": 0}), ("pgd_step", {"pgd_step": 0}),
+             ("pgd_seed", {"pgd_seed": -1}), ("branching_threshold", {"branching_threshold": 2}), ("online_threshold", {"online_threshold": 0})]
+    for i, (name, _) in enumerate(order):
+        bad = {}
+        for _, kw in order[i:]:
+            bad.update(kw)
+        with pytest.raises(ValueError, match=name + " = "):
+            _options(**bad)

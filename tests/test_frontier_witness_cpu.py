@@ -117,9 +117,10 @@ def test_the_jobs_loops_take_the_options_on_their_jobs():
     point = []
     jobs = frontier.FrontierJobs([job(), job()], witness=point, pgd_steps=4, pgd_step=0.25)
     assert isinstance(jobs, list) and len(jobs) == 2
-    assert frontier._upper_of(jobs) == {"witness": point, "pgd_steps": 4, "pgd_step": 0.25} and frontier._upper_of(jobs)["witness"] is point
-    assert frontier._upper_of(list(jobs)) is None and frontier._upper_of(frontier.FrontierJobs([job()])) == {"witness": None, "pgd_steps": None,
-                                                                                                            "pgd_step": 1.0 / 64}
+    off = {"pgd_restarts": None, "pgd_seed": 0}              # (the restart options, tests/test_net_starts_cpu.py)
+    assert frontier._options_of(jobs) == {"witness": point, "pgd_steps": 4, "pgd_step": 0.25, **off} and frontier._options_of(jobs)["witness"] is point
+    assert frontier._options_of(list(jobs)) == {} and frontier._options_of(frontier.FrontierJobs([job()])) == {"witness": None, "pgd_steps": None,
+                                                                                                              "pgd_step": 1.0 / 64, **off}
 
 
 def test_good_options_pass_the_check():

@@ -172,10 +172,11 @@ def test_the_jobs_loops_take_the_options_on_their_jobs_and_upper_of_is_unchanged
     point = []
     jobs = frontier.FrontierJobs([job(), job()], witness=point, pgd_steps=4, pgd_step=0.25, pgd_restarts=3, pgd_seed=11)
     assert isinstance(jobs, list) and len(jobs) == 2
-    assert frontier._upper_of(jobs) == {"witness": point, "pgd_steps": 4, "pgd_step": 0.25}
-    assert frontier._restarts_of(jobs) == {"pgd_restarts": 3, "pgd_seed": 11}
-    assert frontier._restarts_of(list(jobs)) is None
-    assert frontier._restarts_of(frontier.FrontierJobs([job()])) == {"pgd_restarts": None, "pgd_seed": 0}
+    assert frontier._options_of(jobs) == {"witness": point, "pgd_steps": 4, "pgd_step": 0.25, "pgd_restarts": 3, "pgd_seed": 11}
+    assert frontier._options_of(jobs)["witness"] is point
+    assert frontier._options_of(list(jobs)) == {}
+    assert frontier._options_of(frontier.FrontierJobs([job()])) == {"witness": None, "pgd_steps": None, "pgd_step": 1.0 / 64, "pgd_restarts": None,
+                                                                    "pgd_seed": 0}
 
 
 # ---- the generator's restatement -------------------------------------------------------------------------------------------------------
