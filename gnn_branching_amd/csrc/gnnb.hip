@@ -2719,7 +2719,6 @@ static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const Step
   }
   // ---- backward: the tape in reverse ----
   t.wops.clear();
-  t.wide_reduce = lf.table != nullptr;
   for (auto it = t.tape.rbegin(); it != t.tape.rend(); ++it) (*it)();
   t.tape.clear();
   if (t.weight_grads()) return fail(GNNB_E_HIP, "%s: the weight-gradient launches failed", who);

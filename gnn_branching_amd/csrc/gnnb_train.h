@@ -14,15 +14,21 @@
 // chain over the same rows (fc3 -> fc3_2 -> fc4 -> fc4_2, bc1 -> ... -> bc2_1, ...) are ONE launch forward (k_tchain_fwd: a row
 // tile goes through all of them, each output kept in memory for the backward pass and handed to the next layer through LDS) and
 // ONE launch backward (k_tchain_bwd_x); all weight gradients of a step are two launches at its end (k_tlin_bwd_w_all over every
-// (op, row chunk), k_tlin_reduce_all adding the partials in tape order).  Every sum keeps the order of the one-launch-per-op form,
-// so values and gradients are bit-identical to it.
+// (op, row chunk), k_tlin_reduce_all_wide adding the partials in tape order).  Every sum keeps a fixed order: two runs give the same bits.
+//
+// Precision: values and gradients are stored in fp32, and every sum of products -- a Linear's output and its input gradient, a conv or
+// dense edge's aggregate in either direction, a weight-gradient partial, the reduction of the partials -- is accumulated in fp64 and
+// rounded once.  With fp32 accumulators the gradient of inp_f, which reaches the scores only through every sweep of every round in
+// sequence, was 4.16 / 4.24 times the error of fp32 autograd itself against fp64 at T = 3 on fwg_gap / fwg_tall (inp_f.bias;
+// tests/test_online_geometry.py, bar 4; 3.08 on cifar_base_kw); it is 0.49 / 0.59 now, the worst tensor of any case of the step's tests
+// 1.24 (3.57 before), for +7 % .. +9 % of a step's wall time (cifar_base_kw B = 1: 1.69 -> 1.80 ms, B = 8: 3.75 -> 4.09 ms).
 //
 // gnnb_online_step_rows runs the same step on listed rows of a K-row device batch: k_trows_gather copies them into dense buffers out of
 // the arena, and the tape behind is the one above at B = n.
 //
 // gnnb_imitation_step_rows is the same step under another loss: k_tloss_table, a ranking hinge over a row of a
 // strong-branching table, takes k_tloss's place; its ds is dense, so the fscore weight gradient comes from k_tscore_bwd_w_dense and the
-// chunk partials of every other weight gradient are reduced in fp64 (k_tlin_reduce_all_wide).  The online step's kernels are untouched.
+// other weight gradients come from the kernels both steps share.
 //
 // Included by gnnb.hip (one translation unit: it uses the bound network of gnnb_handle) behind gnnb_mem.h, whose owners hold its memory.
 #pragma once
@@ -114,7 +120,7 @@ struct TLin {
   float* y; const float* gy; long n;      // n: rows (compact form: capacity of the list)
   const int* ridx; const int* n_dev; int out_full;
   float* part; int nchunks;
-  int layer;      // index of this Linear in the checkpoint (k_tlin_reduce_all adds up the ops of one layer in tape order)
+  int layer;      // index of this Linear in the checkpoint (k_tlin_reduce_all_wide adds up the ops of one layer in tape order)
   unsigned prev;  // bit j: segment j is the output tile of the PREVIOUS op of the chain (read from LDS, not from memory)
 };
 #define TC_MAXOPS 5
@@ -140,7 +146,7 @@ __device__ __forceinline__ void tl_stage_rows(const TLin& a, long row0, long n, 
 
 // A chain of Linears over one set of rows, forward: a tile of TL_ROWS rows goes through op 0 .. nops-1; every output is written
 // to memory (the backward pass needs it) and stays in LDS (`Ys`) for the segments of the next op that read it (TLin.prev).
-// Per op the arithmetic of the former one-launch-per-Linear kernel: acc = bias, then one fma per input feature in order.
+// Per op: acc = bias, then one fp64 fma per input feature in order, rounded to fp32 once.
 template <int R>
 __device__ __forceinline__ void tchain_fwd_body(const TChain& c, float* tl_lds) {
   __shared__ int Rs[R];
@@ -216,23 +222,24 @@ __device__ __forceinline__ void tchain_fwd_body(const TChain& c, float* tl_lds) 
     }
     __syncthreads();
     const int cc = tid & 63, rq = tid >> 6;
-    float acc[R / 4];
-    const float bias = a.b[cc];
+    double acc[R / 4];                        // fp64 sums, rounded once per output ("Precision" at the top of the file)
+    const double bias = (double)a.b[cc];
 #pragma unroll
     for (int r = 0; r < R / 4; ++r) acc[r] = bias;
     const float* xr = Xs + rq * (R / 4) * K;
     const float* wr = Ws + cc * KP;
     for (int k = 0; k < K; ++k) {
-      const float w = wr[k];
+      const double w = (double)wr[k];
 #pragma unroll
-      for (int r = 0; r < R / 4; ++r) acc[r] = fmaf(xr[r * K + k], w, acc[r]);
+      for (int r = 0; r < R / 4; ++r) acc[r] = fma((double)xr[r * K + k], w, acc[r]);
     }
 #pragma unroll
     for (int r = 0; r < R / 4; ++r) {
       const int node = Rs[rq * (R / 4) + r];
       float v = 0.0f;
       if (node >= 0) {
-        v = a.relu ? fmaxf(acc[r], 0.0f) : acc[r];
+        const float y = (float)acc[r];
+        v = a.relu ? fmaxf(y, 0.0f) : y;
         if (a.omask) v *= a.omask[node];
         a.y[(a.out_full ? (long)node : row0 + rq * (R / 4) + r) * 64 + cc] = v;
       }
@@ -329,14 +336,17 @@ __device__ __forceinline__ void tchain_bwd_x_body(const TChain& c) {
         for (int u = 0; u < 4; ++u) { const int q = tid + 256 * u; *reinterpret_cast<tf4*>(Ws + (q >> 4) * 64 + 4 * (q & 15)) = wv[u]; }
       }
       __syncthreads();
+      double acc64[R / 4];
+#pragma unroll
+      for (int r = 0; r < R / 4; ++r) acc64[r] = 0.0;
+      for (int cc = 0; cc < 64; ++cc) {
+        const double w = (double)Ws[cc * 64 + k];
+#pragma unroll
+        for (int r = 0; r < R / 4; ++r) acc64[r] = fma((double)Ds[(rq * (R / 4) + r) * 64 + cc], w, acc64[r]);
+      }
       float acc[R / 4];
 #pragma unroll
-      for (int r = 0; r < R / 4; ++r) acc[r] = 0.0f;
-      for (int cc = 0; cc < 64; ++cc) {
-        const float w = Ws[cc * 64 + k];
-#pragma unroll
-        for (int r = 0; r < R / 4; ++r) acc[r] = fmaf(Ds[(rq * (R / 4) + r) * 64 + cc], w, acc[r]);
-      }
+      for (int r = 0; r < R / 4; ++r) acc[r] = (float)acc64[r];
 #pragma unroll
       for (int r = 0; r < R / 4; ++r) {
         const int node = Rs[rq * (R / 4) + r];
@@ -412,59 +422,42 @@ __global__ __launch_bounds__(256) void k_tlin_bwd_w_all(const TLin* ops, const i
   float* part = a.part + (long)chunk * 64 * (a.K + 1);
   if (a.nseg) {                    // 64 x 64 outputs: a 4 x 4 block per thread, two b128 LDS reads per row
     const int c0 = (tid >> 4) * 4, k0 = (tid & 15) * 4;
-    float acc[4][4];
+    double acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
+      for (int q = 0; q < 4; ++q) acc[i][q] = 0.0;
     for (int r = 0; r < TL_CHUNK; ++r) {
       const float4 d = *reinterpret_cast<const float4*>(&Ds[r * 64 + c0]);
       const float4 x = *reinterpret_cast<const float4*>(&Xs[r * 64 + k0]);
-      const float dv[4] = {d.x, d.y, d.z, d.w}, xv[4] = {x.x, x.y, x.z, x.w};
+      const double dv[4] = {d.x, d.y, d.z, d.w}, xv[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[i][q] = fmaf(dv[i], xv[q], acc[i][q]);
+        for (int q = 0; q < 4; ++q) acc[i][q] = fma(dv[i], xv[q], acc[i][q]);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) part[(c0 + i) * (a.K + 1) + 64 * j + k0 + q] = acc[i][q];
+      for (int q = 0; q < 4; ++q) part[(c0 + i) * (a.K + 1) + 64 * j + k0 + q] = (float)acc[i][q];
   } else
   for (int o = tid; o < 64 * KW; o += 256) {
     const int cq = o / KW, k = o - cq * KW;
-    float sm = 0.0f;
-    for (int r = 0; r < TL_CHUNK; ++r) sm = fmaf(Ds[r * 64 + cq], Xs[r * KW + k], sm);
-    part[cq * (a.K + 1) + 64 * j + k] = sm;
+    double sm = 0.0;
+    for (int r = 0; r < TL_CHUNK; ++r) sm = fma((double)Ds[r * 64 + cq], (double)Xs[r * KW + k], sm);
+    part[cq * (a.K + 1) + 64 * j + k] = (float)sm;
   }
   if (j == 0 && tid < 64) {
-    float sm = 0.0f;
-    for (int r = 0; r < TL_CHUNK; ++r) sm += Ds[r * 64 + tid];
-    part[tid * (a.K + 1) + a.K] = sm;
+    double sm = 0.0;
+    for (int r = 0; r < TL_CHUNK; ++r) sm += (double)Ds[r * 64 + tid];
+    part[tid * (a.K + 1) + a.K] = (float)sm;
   }
 }
-// gW / gb += the chunk partials of every op of a layer: the ops in tape order, the chunks of an op in chunk order (deterministic,
-// and the order of the former one-reduction-per-op form).  blockIdx.y = Linear of the checkpoint.
-__global__ void k_tlin_reduce_all(const TLin* ops, int nops) {
-  const int o = blockIdx.x * blockDim.x + threadIdx.x, layer = blockIdx.y;
-  for (int q = 0; q < nops; ++q) {
-    if (ops[q].layer != layer) continue;
-    const TLin a = ops[q];
-    if (o >= 64 * (a.K + 1)) return;
-    const int nch = (int)((tl_rows(a) + TL_CHUNK - 1) / TL_CHUNK);
-    float sm = 0.0f;
-    for (int ch = 0; ch < nch; ++ch) sm += a.part[(long)ch * 64 * (a.K + 1) + o];
-    const int cq = o / (a.K + 1), col = o - cq * (a.K + 1);
-    if (col < a.K) a.gW[cq * a.K + col] += sm;
-    else a.gb[cq] += sm;
-  }
-}
-
-// The same reduction for the imitation step (k_tloss_table's ds): there a sample's rows carry +1 per violator and minus their number at the
-// teacher, so the chunk partials and the ops of a layer are large numbers that cancel, and adding them up in fp32 costs several ulp of
-// the result (measured on fnode.bias: 9 ulp, the partials of three ReLU layers cancelling).  Here the chunks of an
-// op and the ops of a layer, in the same fixed order, are added in fp64 and rounded once into gW / gb (zero before: one writer per entry).
-// The online step keeps k_tlin_reduce_all and its bits.
+// gW / gb = the chunk partials of every op of a layer: the ops in tape order, the chunks of an op in chunk order (deterministic),
+// added in fp64 and rounded once into gW / gb (zero before: one writer per entry).  blockIdx.y = Linear of the checkpoint.  Under the
+// imitation loss (k_tloss_table's ds) a sample's rows carry +1 per violator and minus their number at the teacher, so the chunk partials
+// and the ops of a layer are large numbers that cancel: added up in fp32 they cost several ulp of the result (measured on fnode.bias:
+// 9 ulp, the partials of three ReLU layers cancelling).
 __global__ void k_tlin_reduce_all_wide(const TLin* ops, int nops) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x, layer = blockIdx.y;
   double tot = 0.0;
@@ -582,7 +575,7 @@ __global__ __launch_bounds__(256) void k_tconv(TConv a) {
   __builtin_amdgcn_wave_barrier();
   const float* src = a.src + sbase * 64 + lane;
   const bool nrm0 = a.dir == 0 && a.norm;
-  float acc = 0.0f;
+  double acc64 = 0.0;
   for (int q = 0; q < nl; q += TCONV_BATCH) {
     float v[TCONV_BATCH], w[TCONV_BATCH], f[TCONV_BATCH];
 #pragma unroll
@@ -597,10 +590,11 @@ __global__ __launch_bounds__(256) void k_tconv(TConv a) {
       if (q + u < nl) {
         float vv = v[u];
         if (nrm0) vv = vv / f[u];
-        acc = fmaf(w[u], vv, acc);
+        acc64 = fma((double)w[u], (double)vv, acc64);
       }
     }
   }
+  float acc = (float)acc64;
   if (a.dir == 1 && a.norm) acc = acc / post;
   if (a.acc) a.dst[wv * 64 + lane] += acc;
   else a.dst[wv * 64 + lane] = acc;
@@ -618,14 +612,14 @@ struct TDense {
 // edge in 16 dependent batches: 20 us per launch.)
 #define TD_WAVES 16
 __global__ __launch_bounds__(TD_WAVES * 64) void k_tdense(TDense a) {
-  __shared__ float red[TD_WAVES][64];
+  __shared__ double red[TD_WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long wv = blockIdx.x;
   const int nd = a.dir == 0 ? a.n_out : a.n_in, ns = a.dir == 0 ? a.n_in : a.n_out;
   const int i = (int)(wv % nd), b = (int)(wv / nd);
   const float* A = a.A + (long)b * a.a_bstride;
   const float* src = a.src + (long)b * ns * 64 + lane;
-  float acc = 0.0f;
+  double acc = 0.0;
   for (int k0 = wave; k0 < ns; k0 += 16 * TD_WAVES) {
     float w[16], v[16];
 #pragma unroll
@@ -637,7 +631,7 @@ __global__ __launch_bounds__(TD_WAVES * 64) void k_tdense(TDense a) {
     }
 #pragma unroll
     for (int u = 0; u < 16; ++u)
-      if (k0 + TD_WAVES * u < ns) acc = fmaf(w[u], v[u], acc);
+      if (k0 + TD_WAVES * u < ns) acc = fma((double)w[u], (double)v[u], acc);
   }
   red[wave][lane] = acc;
   __syncthreads();
@@ -645,8 +639,8 @@ __global__ __launch_bounds__(TD_WAVES * 64) void k_tdense(TDense a) {
   acc = red[0][lane];
 #pragma unroll
   for (int w = 1; w < TD_WAVES; ++w) acc += red[w][lane];
-  if (a.acc) a.dst[wv * 64 + lane] += acc;
-  else a.dst[wv * 64 + lane] = acc;
+  if (a.acc) a.dst[wv * 64 + lane] += (float)acc;
+  else a.dst[wv * 64 + lane] = (float)acc;
 }
 
 // ---- score head (graph_conv.py:442-450): s = fscore(relu(fnode(mu))) for the masked nodes, -inf elsewhere ----
@@ -1077,7 +1071,6 @@ struct Trainer {
   }
   // the weight gradients of every recorded op: two launches behind the backward walk
   std::vector<int> h_first;
-  bool wide_reduce = false;              // the imitation step: k_tlin_reduce_all_wide
   int weight_grads() {
     const int nops = (int)wops.size();
     if (!nops) return 0;
@@ -1090,8 +1083,7 @@ struct Trainer {
     if (hipMemcpyAsync(d_ops, wops.data(), sizeof(TLin) * nops, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
     if (hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (nops + 1), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
     hipLaunchKernelGGL(k_tlin_bwd_w_all, dim3((unsigned)h_first[nops], 3), dim3(256), 0, st, d_ops, d_first, nops);
-    if (wide_reduce) hipLaunchKernelGGL(k_tlin_reduce_all_wide, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
-    else hipLaunchKernelGGL(k_tlin_reduce_all, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
+    hipLaunchKernelGGL(k_tlin_reduce_all_wide, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
     return 0;
   }
   static TSeg seg(const TT& t, const float* s = nullptr, bool full = false) { return TSeg{t.v, s, t.g, full ? 1 : 0}; }

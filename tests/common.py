@@ -122,6 +122,29 @@ def register_online_archs():
         nets.register_arch(name, spec, seed=300 + i)
 
 
+# Networks at the clamped tap bound of the learning step (tests/test_online_geometry.py): name -> (input shape, spec).  gnnb_online_step
+# admits a conv edge whose largest tap list, min(k, extent) per axis forward and min(ceil(k / s), extent) transposed, is at most 512.
+ONLINE_GEOM_ARCHS = {
+    # 5x5 stride 1 over a 4x4 layer of 32 channels: 25 * 32 = 800 unclamped, 4 * 4 * 32 = 512 clamped in both directions, and the four
+    # centre nodes list all 512; only the min(k, extent) clamp admits it
+    "onl_clamp512": ((3, 16, 16), [("conv", 3, 32, 4, 4, 0), ("relu",), ("conv", 32, 32, 5, 1, 2), ("relu",), ("flatten",), ("linear", 512, 24),
+                                   ("relu",), ("linear", 24, 10)]),
+    # 8x8 stride 2 pad 3, 8 -> 32 channels on 16x16: forward 8 * 8 * 8 = 512, transposed ceil(8 / 2)^2 * 32 = 512, both reached by interior
+    # nodes; only the ceil(k / s) term admits it
+    "onl_s2_512": ((3, 16, 16), [("conv", 3, 8, 3, 1, 1), ("relu",), ("conv", 8, 32, 8, 2, 3), ("relu",), ("flatten",), ("linear", 2048, 24),
+                                 ("relu",), ("linear", 24, 10)]),
+    # the same 5x5 edge over a 5x4 layer: clamped bound 5 * 4 * 32 = 640, which node (y = 2, x = 2) really lists -- refused
+    "onl_clamp640": ((3, 20, 16), [("conv", 3, 32, 4, 4, 0), ("relu",), ("conv", 32, 32, 5, 1, 2), ("relu",), ("flatten",), ("linear", 640, 24),
+                                   ("relu",), ("linear", 24, 10)]),
+}
+
+
+def register_online_geom_archs():
+    """Register ONLINE_GEOM_ARCHS with nets (seeds 700 + i, fixed by their order)."""
+    for i, (name, (_, spec)) in enumerate(ONLINE_GEOM_ARCHS.items()):
+        nets.register_arch(name, spec, seed=700 + i)
+
+
 def _mlp_deep8():
     spec, n = [("flatten",)], 3 * 8 * 8
     for _ in range(8):

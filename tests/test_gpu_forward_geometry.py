@@ -92,9 +92,9 @@ def decisions_of(scores, batch):
             for b in range(batch.batch_size)]
 
 
-def conv_edges(name):
-    """[(layer index, c_in, c_out, k, stride, pad, h_in, w_in)] of the network's convolutions."""
-    shape, spec = (ZERO_TAP_ARCH[1], ZERO_TAP_ARCH[2]) if name == ZERO_TAP_ARCH[0] else FWD_ARCHS[name]
+def conv_edges(name, archs=FWD_ARCHS):
+    """[(layer index, c_in, c_out, k, stride, pad, h_in, w_in)] of the network's convolutions (archs: name -> (input shape, spec))."""
+    shape, spec = (ZERO_TAP_ARCH[1], ZERO_TAP_ARCH[2]) if name == ZERO_TAP_ARCH[0] else archs[name]
     out, (_, h, w) = [], shape
     for i, s in enumerate(spec):
         if s[0] == "conv":
@@ -125,12 +125,12 @@ def test_batches_are_well_posed(name):
     assert ref["noise"] <= ref["bar"]
 
 
-def _mutations(name, batch, every=False):
-    """(what, layers) with one smallest indexing error each: the last kernel column of one convolution zeroed (MUTATED_CONV names it;
-    the two networks without a convolution have no such mutation), and the property layers of samples 0 and 1 exchanged."""
+def _mutations(name, batch, every=False, conv=None, archs=FWD_ARCHS):
+    """(what, layers) with one smallest indexing error each: the last kernel column of one convolution zeroed (MUTATED_CONV names it,
+    or `conv`; the two networks without a convolution have no such mutation), and the property layers of samples 0 and 1 exchanged."""
     fixed, props = batch.layers["fixed_layers"], batch.layers["prop_layers"]
-    for i, _, _, k, st, pad, _, w in conv_edges(name):
-        if every or i == MUTATED_CONV[name]:
+    for i, _, _, k, st, pad, _, w in conv_edges(name, archs):
+        if every or i == (MUTATED_CONV[name] if conv is None else conv):
             mut = [copy.deepcopy(l) if j == i else l for j, l in enumerate(fixed)]
             with torch.no_grad():
                 mut[i].weight[..., -1] = 0
