@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]] [--props 18 [--branching strong [--candidates 16] | --imitate 1 [--imitate-margin 1.0] [--candidates 16]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -24,6 +24,8 @@ with; with --props N every property has its own intercept counter (frontier.veri
 --frontier K --branching strong is strong branching, the strategy the GNN was trained to imitate: both children of
 every candidate split of every parent are bounded on the device and the parent splits where its bound improves most; --candidates M keeps
 the M undecided nodes of highest BaBSR score as candidates (without it every undecided node is one: thousands per parent on the CIFAR nets).
+--gnn-candidates G shortlists the G undecided nodes of highest GNN score as well, or alone without --candidates
+(frontier.Shortlist): the GNN proposes, the bounds dispose, and with --imitate the table always labels the split the GNN made.
 --frontier K --imitate N (with the GNN or --branching strong) makes every N-th round a learning round: its parents'
 strong-branching table stays on the device and the GNN takes one Adam step towards ranking the table's best candidate first, by
 --imitate-margin M times the difference of the improvements.
@@ -67,6 +69,7 @@ def main():
     ap.add_argument("--branching", default=None, choices=("gnn", "babsr", "strong"),
                     help="with --frontier K: what picks the split, the GNN (default), the BaBSR heuristic alone, or strong branching")
     ap.add_argument("--candidates", type=int, default=None, metavar="M", help="with --branching strong: bound the M undecided nodes of highest BaBSR score only")
+    ap.add_argument("--gnn-candidates", type=int, default=None, metavar="G", help="with --branching strong or --imitate N: also bound the G undecided nodes of highest GNN score")
     ap.add_argument("--imitate", type=int, default=None, metavar="N", help="with --frontier K: every N-th round learns the GNN from its strong-branching table")
     ap.add_argument("--imitate-margin", type=float, default=None, metavar="M", help="with --imitate N: the margin per unit of improvement (default 1.0)")
     args = ap.parse_args()
@@ -83,7 +86,13 @@ def main():
         ap.error("--branching strong takes no --threshold and no --online: it never asks the GNN")
     if args.candidates is not None and ((args.branching != "strong" and args.imitate is None) or args.candidates < 1):
         ap.error("--candidates M needs --branching strong or --imitate N, and M >= 1")
+    if args.gnn_candidates is not None and ((args.branching != "strong" and args.imitate is None) or args.gnn_candidates < 1):
+        ap.error("--gnn-candidates G needs --branching strong or --imitate N, and G >= 1")
     branching = args.branching or "gnn"
+    candidates = args.candidates
+    if args.gnn_candidates is not None:                          # the value of strong_candidates that names both shortlists
+        from gnn_branching_amd.frontier import Shortlist
+        candidates = Shortlist(babsr=args.candidates, gnn=args.gnn_candidates)
     if args.restarts is not None and (args.pgd is None or not 0 <= args.restarts <= 4096):
         ap.error("--restarts R needs --pgd N, and 0 <= R <= 4096")
     if (args.witness or args.pgd is not None) and (args.frontier is None or (args.pgd is not None and args.pgd < 0)):
@@ -124,7 +133,7 @@ def main():
         if branching == "strong" or args.imitate is not None:
             margin = {} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}
             results = verify_properties_strong(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
-                                               stats=stats, learned=learned, imitate=args.imitate, strong_candidates=args.candidates, branching=branching,
+                                               stats=stats, learned=learned, imitate=args.imitate, strong_candidates=candidates, branching=branching,
                                                **margin)
         elif branching == "babsr":
             results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
@@ -160,7 +169,7 @@ def main():
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
                                                                       branching_threshold=args.threshold, stats=stats, online_threshold=args.online,
-                                                                      strong_candidates=args.candidates, branching=branching, **upper)
+                                                                      strong_candidates=candidates, branching=branching, **upper)
         verdict = "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
         kw = "" if args.threshold is None else f"; {stats['kw_bounded']} of {stats['branches']} parents bounded a KW decision, {stats['kw_used']} kept it"
         if args.online is not None:

@@ -140,6 +140,9 @@ SYMBOLS = [
     ("gnnb_strong_list_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_strong_list", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
      [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_strong_list_union_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_strong_list_union", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] +
+     [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_strong_pick", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_void_p]),
     ("gnnb_strong_rows_jobs", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]),
     ("gnnb_frontier_learn", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),

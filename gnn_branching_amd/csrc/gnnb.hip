@@ -2312,6 +2312,45 @@ extern "C" int gnnb_strong_list(gnnb_t* h, const gnnb_pool* pool, const int32_t*
   return run.rc;
 }
 
+// ---- the union of two shortlists: k_strong_count per array, then the union's count and its compaction ----
+extern "C" size_t gnnb_strong_list_union_workspace_bytes(const gnnb_t* h, int K) {
+  if (!h || !h->bound || K < 1) return 0;
+  return (size_t)K * (2 * SC_FIELDS + 1) * sizeof(int32_t);   // both arrays' records and the rows' union counts
+}
+
+extern "C" int gnnb_strong_list_union(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const float* scorer_mask,
+                                      const float* scores_a, int top_a, const float* scores_b, int top_b, int32_t* cand0, int32_t* cand_row,
+                                      int32_t* cand_slot, int32_t* cand_dec, int32_t* cand_src, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  const char* who = "gnnb_strong_list_union";
+  if (K < 1 || K > 32767) return fail(GNNB_E_INVALID, "%s: K = %d outside 1..32767", who, K);
+  if (top_a < 1 || top_b < 1)
+    return fail(GNNB_E_INVALID, "%s: top_a = %d , top_b = %d (both at least 1; one list alone is gnnb_strong_list)", who, top_a, top_b);
+  if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !scorer_mask || !scores_a || !scores_b || !cand0 || !cand_row || !cand_slot || !cand_dec || !cand_src || !workspace)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  const size_t need = gnnb_strong_list_union_workspace_bytes(h, K);
+  if (workspace_bytes < need) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
+  StrongListArgs ca{};
+  ca.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &ca.p)) return rc;
+  int32_t* ws = (int32_t*)workspace;
+  ca.slots = slots; ca.K = K; ca.amb = scorer_mask; ca.scores = scores_a; ca.top_m = top_a; ca.rows = ws;
+  StrongListArgs cb = ca;
+  cb.scores = scores_b; cb.top_m = top_b; cb.rows = ws + (size_t)K * SC_FIELDS;
+  StrongUnionArgs u{};
+  u.s = ca.s; u.slots = slots; u.K = K; u.amb = scorer_mask; u.scores_a = scores_a; u.scores_b = scores_b;
+  u.cand0 = cand0; u.cand_row = cand_row; u.cand_slot = cand_slot; u.cand_dec = cand_dec; u.cand_src = cand_src;
+  u.rows_a = ca.rows; u.rows_b = cb.rows; u.count = ws + (size_t)K * 2 * SC_FIELDS;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_STRONG_COUNT, [&] { hipLaunchKernelGGL(k_strong_count, dim3(K), dim3(FR_THREADS), 0, st, ca); });
+  run.run(PC_STRONG_COUNT, [&] { hipLaunchKernelGGL(k_strong_count, dim3(K), dim3(FR_THREADS), 0, st, cb); });
+  run.run(PC_STRONG_COUNT, [&] { hipLaunchKernelGGL(k_strong_union_count, dim3(K), dim3(FR_THREADS), 0, st, u); });
+  run.run(PC_STRONG_COMPACT, [&] { hipLaunchKernelGGL(k_strong_union_compact, dim3(K), dim3(FR_THREADS), 0, st, u); });
+  return run.rc;
+}
+
 extern "C" int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const int32_t* cand0, const int32_t* cand_dec,
                                 const int32_t* live, const int32_t* infeasible, const double* bound, int32_t* decisions,
                                 double* best_improvement, double* improvement, double* table, void* stream) {

@@ -22,6 +22,11 @@
 //                       under that kernel's profile class (PC_FR_ROWS_SEL): it has none of its own.  A slot < 0 or of a segment
 //                       >= segments leaves its two rows unwritten and reads no table.
 //
+//   * k_strong_union_count / k_strong_union_compact  the union of two shortlists (gnnb_strong_list_union): behind
+//                       one k_strong_count per array, the walk that takes a node if either array's cut takes it -- the row's total, then
+//                       k_strong_compact's prefix and the entries with their source.  They launch under k_strong_count's and
+//                       k_strong_compact's profile classes.
+//
 // No atomics, no workgroup waits on another; nothing depends on K or on a row's place.
 
 enum { SC_MODE, SC_COUNT_, SC_KEY, SC_TIES, SC_FIELDS };     // workspace of gnnb_strong_list: (K, SC_FIELDS) int32
@@ -169,6 +174,95 @@ __global__ __launch_bounds__(FR_THREADS) void k_strong_compact(StrongListArgs a)
       a.cand_dec[2 * q + 1] = r - a.s.off[k];
     }
   }
+}
+
+// ---- the union of two shortlists (gnnb_strong_list_union; include/gnnb.h states the rule) ----
+// k_strong_count runs once per array and leaves one (mode, count, key, ties) record per row and array; a row takes part when both records
+// do (a bad slot, no undecided node, a NaN in either array: none).  The walk below goes over the row in tiles of FR_THREADS nodes with one
+// running tie rank PER ARRAY, so "the first `ties` nodes with key == T in index order" holds for each array on its own; a node is taken if
+// either array takes it.  k_strong_union_count keeps the walk's total per row (under k_strong_count's profile class), k_strong_union_compact
+// walks again behind the prefix over those totals in row order and emits (under k_strong_compact's class).
+struct StrongUnionArgs {
+  FrShape s;
+  const int32_t* slots; int K;
+  const float* amb; const float* scores_a; const float* scores_b;        // (K, R)
+  int32_t* cand0; int32_t* cand_row; int32_t* cand_slot; int32_t* cand_dec; int32_t* cand_src;
+  const int32_t* rows_a; const int32_t* rows_b;         // workspace: (K, SC_FIELDS) each, k_strong_count's records
+  int32_t* count;                                       // workspace: (K), the rows' union counts
+};
+static_assert(sizeof(StrongUnionArgs) <= 4096, "kernel arguments: 4 KiB");
+
+struct StCut {                                          // one array's record of a row and its running tie rank
+  int mode, ties, n_ties;
+  unsigned T;
+  const float* sc;
+};
+
+__device__ __forceinline__ StCut st_cut(const int32_t* rec, const float* sc) {
+  return StCut{rec[SC_MODE], rec[SC_TIES], 0, (unsigned)rec[SC_KEY], sc};
+}
+
+// whether the array takes node r of the tile (every thread of the workgroup calls it: mode is uniform over the workgroup)
+__device__ __forceinline__ bool st_takes(StCut& c, int* wsum, bool open, int r, int tid) {
+  if (c.mode != SM_CUT) return open;                    // (SM_ALL: every undecided node)
+  const unsigned key = open ? st_key(c.sc[r]) : 0u;
+  const bool tie = open && key == c.T;
+  int tile_ties;
+  const int rank = c.n_ties + st_block_scan(wsum, tie, tid, &tile_ties);
+  c.n_ties += tile_ties;
+  return open && (key > c.T || (tie && rank < c.ties));
+}
+
+// The walk over row i: the number of nodes either array takes and, with EMIT, their entries from list position q0 on (at most `count`).
+template <bool EMIT>
+__device__ __forceinline__ int st_union_walk(const StrongUnionArgs& a, int i, int* wsum, int q0, int count) {
+  const int tid = threadIdx.x, R = a.s.R;
+  StCut ca = st_cut(a.rows_a + (long)i * SC_FIELDS, a.scores_a + (long)i * R), cb = st_cut(a.rows_b + (long)i * SC_FIELDS, a.scores_b + (long)i * R);
+  if (ca.mode == SM_NONE || cb.mode == SM_NONE) return 0;      // (uniform over the workgroup)
+  const int slot = a.slots[i];
+  const float* amb = a.amb + (long)i * R;
+  int n_out = 0;
+  for (int r0 = 0; r0 < R; r0 += FR_THREADS) {
+    const int r = r0 + tid;
+    const bool open = r < R && amb[r] != 0.0f;
+    const bool in_a = st_takes(ca, wsum, open, r, tid), in_b = st_takes(cb, wsum, open, r, tid);
+    const bool sel = in_a || in_b;
+    int tile_out;
+    const int pos = n_out + st_block_scan(wsum, sel, tid, &tile_out);
+    n_out += tile_out;
+    if (EMIT && sel && pos < count) {                   // (pos < count always holds: the bound of the lists' size, kept as a guard)
+      int k = 1;
+      while (k < a.s.L && r >= a.s.off[k + 1]) ++k;
+      const long q = (long)q0 + pos;
+      a.cand_row[q] = i;
+      a.cand_slot[q] = slot;
+      a.cand_dec[2 * q] = k - 1;
+      a.cand_dec[2 * q + 1] = r - a.s.off[k];
+      a.cand_src[q] = (in_a ? 1 : 0) | (in_b ? 2 : 0);
+    }
+  }
+  return n_out;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_strong_union_count(StrongUnionArgs a) {
+  __shared__ int wsum[FR_THREADS / 64];
+  const int i = blockIdx.x;
+  const int n = st_union_walk<false>(a, i, wsum, 0, 0);
+  if (threadIdx.x == 0) a.count[i] = n;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_strong_union_compact(StrongUnionArgs a) {
+  __shared__ int red[FR_THREADS];
+  __shared__ int wsum[FR_THREADS / 64];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  int before = 0;
+  for (int j = tid; j < i; j += FR_THREADS) before += a.count[j];
+  const int q0 = st_block_sum(red, before, tid), count = a.count[i];
+  if (tid == 0) {
+    a.cand0[i] = q0;
+    if (i == a.K - 1) a.cand0[a.K] = q0 + count;
+  }
+  st_union_walk<true>(a, i, wsum, q0, count);
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_strong_pick(StrongPickArgs a) {

@@ -1240,6 +1240,25 @@ class ScorerEngine:
                    self._rows(cand_slot, cap, 1, i32, "cand_slot").data_ptr(), self._rows(cand_dec, cap, 2, i32, "cand_dec").data_ptr(),
                    ws.data_ptr(), ws.numel())
 
+    def strong_list_union(self, pool, slots, scorer_mask, scores_a, top_a, scores_b, top_b, cand0, cand_row, cand_slot, cand_dec, cand_src,
+                          workspace=None):
+        """gnnb_strong_list_union on the current stream: per parent the union of ``strong_list``'s candidates for
+        (scores_a, top_a) and for (scores_b, top_b), each node once, in ascending flat index; both score arrays (K, R) fp32, both counts at
+        least 1.  cand_src (n,) int32 receives 1 (in A's set only), 2 (in B's only) or 3 (in both); the other lists are ``strong_list``'s and
+        hold K * min(R, top_a + top_b) entries; entries from n on are not written.  A NaN at an undecided node of either array empties the
+        row.  Nothing is copied."""
+        K, top_a, top_b = int(slots.numel()), int(top_a), int(top_b)
+        st, keep = self._pool(pool)
+        R, i32, f32 = self.R, torch.int32, torch.float32
+        cap = max(K, 0) * min(R, max(top_a, 0) + max(top_b, 0))
+        ws = self._workspace("strong_list_union", K, "gnnb_strong_list_union_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_strong_list_union", C.byref(st), self._rows(slots, K, 1, i32, "slots").data_ptr(), K,
+                   self._rows(scorer_mask, K, R, f32, "scorer_mask").data_ptr(), self._rows(scores_a, K, R, f32, "scores_a").data_ptr(), top_a,
+                   self._rows(scores_b, K, R, f32, "scores_b").data_ptr(), top_b, self._rows(cand0, K + 1, 1, i32, "cand0").data_ptr(),
+                   self._rows(cand_row, cap, 1, i32, "cand_row").data_ptr(), self._rows(cand_slot, cap, 1, i32, "cand_slot").data_ptr(),
+                   self._rows(cand_dec, cap, 2, i32, "cand_dec").data_ptr(), self._rows(cand_src, cap, 1, i32, "cand_src").data_ptr(),
+                   ws.data_ptr(), ws.numel())
+
     def strong_pick(self, pool, slots, cand0, cand_dec, n, live, infeasible, bound, decisions, best_improvement, improvement, table=None):
         """gnnb_strong_pick on the current stream: the improvement of each of the n listed candidates from its two
         bounded child rows (live / infeasible (2n,) int32, bound (2n,) fp64, list order) into improvement (n,) fp64, and per parent row

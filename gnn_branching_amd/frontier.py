@@ -34,6 +34,9 @@ states with the teacher and learns from them without the table, the scorer input
 ``verify_properties_strong`` runs both for many jobs in one pool: the candidates of all jobs' parents form one list
 bounded in shared chunks, each candidate's child rows taking their own job's box and property row (``gnnb_strong_rows_jobs``), and with
 ``imitate=N`` every N-th round the pool launches takes one step over the parents of all jobs in flight, which share the scorer.
+
+``strong_candidates=Shortlist(babsr=M, gnn=G)`` shortlists the candidates by the GNN's own scores as well, or by
+them alone (``gnnb_strong_list_union``, ``gnnb_strong_list``), so that the table always labels the scorer's own decision.
 """
 import ctypes as C
 import math
@@ -251,9 +254,49 @@ def _check_branching(branching, branching_threshold, online_threshold):
                          "online_threshold, which compare the heuristic with the GNN")
 
 
-def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None):
-    """The strong-branching options of DESIGN.md section 7.11, before a device is touched."""
-    if strong_candidates is not None and (not isinstance(strong_candidates, int) or isinstance(strong_candidates, bool) or strong_candidates < 1):
+class Shortlist:
+    """A value of ``strong_candidates`` that says where a parent's candidates come from.  babsr: None, or M >= 1,
+    the M undecided nodes BaBSR ranks first -- ``Shortlist(babsr=M)`` is ``strong_candidates=M``.  gnn: None, or G >= 1, the G undecided
+    nodes the run's own scorer ranks first (``gnnb_forward``'s scores of the parent rows), so that the GNN's decision always has an entry
+    in the table.  Both: the union of the two sets (``gnnb_strong_list_union``).  At least one count must be given; the run checks them."""
+
+    def __init__(self, babsr=None, gnn=None):
+        self.babsr, self.gnn = babsr, gnn
+
+    def __repr__(self):
+        return f"Shortlist(babsr={self.babsr!r}, gnn={self.gnn!r})"
+
+
+def _shortlist_counts(strong_candidates):
+    """(M, G) of a checked ``strong_candidates``: BaBSR's count and the scorer's, 0 for none ((0, 0): every undecided node)."""
+    if isinstance(strong_candidates, Shortlist):
+        return strong_candidates.babsr or 0, strong_candidates.gnn or 0
+    return strong_candidates or 0, 0
+
+
+def _check_shortlist(s, branching, choice):
+    """A ``Shortlist`` as the value of ``strong_candidates``, before a device is touched."""
+    counts = (s.babsr, s.gnn)
+    if s.babsr is None and s.gnn is None:
+        raise ValueError(f"strong_candidates = {s!r}: a Shortlist needs a babsr count, a gnn count or both (None: every undecided node)")
+    if any(c is not None and (not isinstance(c, int) or isinstance(c, bool) or c < 1) for c in counts):
+        raise ValueError(f"strong_candidates = {s!r}: a count is None, or an integer >= 1")
+    if s.gnn is None:
+        return
+    if branching == "babsr":
+        raise ValueError(f'strong_candidates = {s!r} with branching="babsr": a BaBSR run never prepares the GNN\'s inputs, so there are no scores '
+                         'to shortlist by; a gnn count is legal with "gnn" and "strong"')
+    from .graphnet.graph_conv import GraphNet
+    if not isinstance(getattr(choice, "model", None), GraphNet):
+        raise ValueError(f"strong_candidates = {s!r}: a gnn count needs a choice whose model is a graphnet.graph_conv.GraphNet, the scorer to run, "
+                         f"not {type(choice).__name__}")
+
+
+def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None, choice=None):
+    """The strong-branching options of DESIGN.md sections 7.11 and 7.14, before a device is touched."""
+    if isinstance(strong_candidates, Shortlist):
+        _check_shortlist(strong_candidates, branching, choice)
+    elif strong_candidates is not None and (not isinstance(strong_candidates, int) or isinstance(strong_candidates, bool) or strong_candidates < 1):
         raise ValueError(f"strong_candidates = {strong_candidates!r}: None (every undecided node), or an integer >= 1")
     if not isinstance(strong_chunk, int) or isinstance(strong_chunk, bool) or strong_chunk < 1:
         raise ValueError(f"strong_chunk = {strong_chunk!r}: an integer >= 1, the candidates per bounding chunk")
@@ -299,6 +342,7 @@ PGD_RESTARTS_MAX = 4096             # gnnb_net_starts' R
 class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
     branching, strong_on, imitate, learning = "gnn", False, None, False      # (what a run is before ``_set_options``: everything off)
+    strong_G, cand_src = 0, None    # (section 7.14: the scorer's count of a ``Shortlist`` and the union's sources; off unless a run sets them)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
                      online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
@@ -306,12 +350,12 @@ class _Round:
         """The options of a run, checked in ONE order -- imitate, branching, strong, witness, restarts, threshold, online -- and stored with
         everything derived from them, before anything touches ``choice`` or a device; a constructor passes the keywords it has and the
         others stay off.  Everything behind it (``_engine_of``, ``_buffers``, ``_launch``, the loops) reads the run, never an argument:
-        ``strong_on`` (a round computes the table of section 7.11: "strong", an audit, or ``imitate``), ``strong_M`` (0: every undecided
-        node), ``witness_on`` and ``witness_to`` (the caller's list), ``restarts`` (0: off), ``threshold``, ``online``, ``learns`` (the
+        ``strong_on`` (a round computes the table of section 7.11: "strong", an audit, or ``imitate``), ``strong_M`` (BaBSR's count; 0: none) and
+        ``strong_G`` (the scorer's count of a ``Shortlist``, section 7.14; both 0: every undecided node), ``witness_on`` and ``witness_to`` (the caller's list), ``restarts`` (0: off), ``threshold``, ``online``, ``learns`` (the
         scorer's parameters move: the run takes the engine with the optimizer), and the counters of a run before its first round."""
         _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice)
         _check_branching(branching, branching_threshold, online_threshold)
-        _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate)
+        _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate, choice)
         _check_witness(witness, pgd_steps, pgd_step)
         _check_restarts(pgd_restarts, pgd_seed, pgd_steps)
         _check_threshold(branching_threshold, kwbd_threshold)
@@ -325,7 +369,10 @@ class _Round:
         self.restarts, self.pgd_seed = pgd_restarts or 0, pgd_seed
         self.imitate, self.imitate_margin, self.learns = imitate, float(imitate_margin), online_threshold is not None or imitate is not None
         self.strong_on = branching == "strong" or strong_audit is not None or imitate is not None
-        self.strong_M, self.strong_chunk, self.strong_audit = strong_candidates or 0, strong_chunk, strong_audit
+        self.strong_M, G = _shortlist_counts(strong_candidates)
+        self.strong_chunk, self.strong_audit = strong_chunk, strong_audit
+        if G:                                                     # (set only where given: without a gnn count a run is the run it was)
+            self.strong_G = G
         self.round = self.k = self.strong_n = self.imitation_steps = self.imitation_rows = self.last_imitation = 0
         self.learning, self.imitate_pending, self.cand_entry, self.im_table = False, False, None, None
 
@@ -351,7 +398,8 @@ class _Round:
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.status_all = torch.zeros(1, dtype=torch.int32, device=dev)
         self.root_slot = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws_fwd = ws("gnnb_workspace_bytes", n_parents) if self.branching == "gnn" else None     # (a BaBSR or strong round runs no gnnb_forward)
+        # (a BaBSR or strong round runs no gnnb_forward, unless the scorer shortlists the candidates: section 7.14)
+        self.ws_fwd = ws("gnnb_workspace_bytes", n_parents) if self.branching == "gnn" or self.strong_G else None
         n_bound = max(n_children, 2 * self.strong_chunk) if self.strong_on else n_children      # (the candidates' chunks share the workspaces)
         self.ws_kw = ws("gnnb_kw_workspace_bytes", n_bound)
         self.ws_dual = ws("gnnb_dual_workspace_bytes", n_bound)
@@ -403,11 +451,14 @@ class _Round:
 
     def _strong_buffers(self, n_parents, box):
         """The state of strong branching for rounds of up to n_parents parents.  box: the boxes and property rows
-        of the 2 * strong_chunk candidate child rows ``ChS``.  The dense lists hold n_parents * min(R, strong_candidates or R) candidates
-        and the run-long arrays live / infeasible / bound two children each; ``strong_bounded`` counts the candidate children bounded."""
+        of the 2 * strong_chunk candidate child rows ``ChS``.  The dense lists hold n_parents * min(R, M + G or R) candidates (M, G:
+        BaBSR's count and the scorer's, section 7.14) and the run-long arrays live / infeasible / bound two children each; BaBSR's scores
+        exist only with M, the union's ``cand_src`` and workspace only with both counts; ``strong_bounded`` counts the candidate children
+        bounded."""
         dev, R, n = self.eng.device, self.eng.R, n_parents
         f64, f32, i32 = torch.float64, torch.float32, torch.int32
-        cap = n * (min(R, self.strong_M) if self.strong_M else R)
+        top, union = self.strong_M + self.strong_G, self.strong_M > 0 and self.strong_G > 0
+        cap = n * (min(R, top) if top else R)
         self.ChS = _StrongRows(self.eng, 2 * self.strong_chunk, box)
         self.s_scores, self.s_icp = (torch.zeros(n, R, dtype=f32, device=dev) for _ in range(2)) if self.strong_M else (None, None)
         self.cand0 = torch.zeros(n + 1, dtype=i32, device=dev)
@@ -415,7 +466,9 @@ class _Round:
         self.s_live, self.s_infeasible = torch.zeros(2 * cap, dtype=i32, device=dev), torch.zeros(2 * cap, dtype=i32, device=dev)
         self.s_bound, self.s_imp = torch.zeros(2 * cap, dtype=f64, device=dev), torch.zeros(cap, dtype=f64, device=dev)
         self.s_best, self.s_dec = torch.zeros(n, dtype=f64, device=dev), torch.zeros(n, 2, dtype=i32, device=dev)
-        self.ws_strong = self._ws("gnnb_strong_list_workspace_bytes", n)
+        self.ws_strong = self._ws("gnnb_strong_list_union_workspace_bytes" if union else "gnnb_strong_list_workspace_bytes", n)
+        if union:
+            self.cand_src = torch.zeros(cap, dtype=i32, device=dev)
         self.strong_bounded = 0
 
     def _imitation_buffers(self, n_parents):
@@ -454,15 +507,22 @@ class _Round:
 
     def _strong_table(self, slots, n, dec, table=None):
         """Steps 2-6 of a strong round over the n parent rows the gather wrote: gnnb_babsr for the pre-filter (with
-        ``strong_candidates``), gnnb_strong_list, the read of the number of candidates, per chunk of ``strong_chunk`` candidates
+        a BaBSR count), gnnb_strong_list on BaBSR's scores or on the scorer's (``P.scores``, with a gnn count alone) or
+        gnnb_strong_list_union on both (section 7.14), the read of the number of candidates, per chunk of ``strong_chunk`` candidates
         gnnb_frontier_expand into ``ChS``, gnnb_kw_bounds and gnnb_dual_ascent (no scorer inputs, no LP point; live, infeasible and bound go
         to the run-long arrays at the chunk's offset), and gnnb_strong_pick into ``dec`` ((n, 2) int32) and, on a learning round (section
         7.12), into ``table`` ((n, R) fp64).  No gnnb_net_eval, no PGD, no witness: a candidate is only ever a lower bound."""
         P, S, eng, pool, lib, h = self.P, self.ChS, self.eng, self.pool, self.lib, self.eng.h
-        if self.strong_M:
+        M, G = self.strong_M, self.strong_G
+        lists = (self.cand0, self.cand_row, self.cand_slot, self.cand_dec)
+        if M:
             eng.babsr_rows(P.lb32, P.ub32, P.box[2], P.amb, n, self.s_scores, self.s_icp)
-        eng.strong_list(pool, slots, P.amb, self.s_scores, self.strong_M, self.cand0, self.cand_row, self.cand_slot, self.cand_dec,
-                        workspace=self.ws_strong)
+        if M and G:                                               # (section 7.14: P.scores are the round's gnnb_forward's, already there)
+            eng.strong_list_union(pool, slots, P.amb, self.s_scores, M, P.scores, G, *lists, self.cand_src, workspace=self.ws_strong)
+        elif G:
+            eng.strong_list(pool, slots, P.amb, P.scores, G, *lists, workspace=self.ws_strong)
+        else:
+            eng.strong_list(pool, slots, P.amb, self.s_scores, M, *lists, workspace=self.ws_strong)
         n_c = self.strong_n = self.read_candidates(n)
         for q0 in range(0, n_c, self.strong_chunk):               # a chunk may span parents
             c = min(self.strong_chunk, n_c - q0)
@@ -487,9 +547,12 @@ class _Round:
         """``branching="strong"`` in ``_score_parents``' place: the table of the n parent rows the gather wrote and
         its arg-max per row into ``P.dec``.  No gnnb_dual_ascent at n_iter = 0, no gnnb_forward.  A learning round (section 7.12) keeps the
         table and then runs gnnb_dual_ascent at n_iter = 0 on the parent rows, so that the scorer inputs the step reads exist; still no
-        gnnb_forward."""
+        gnnb_forward.  With a gnn count (section 7.14) the scorer shortlists the candidates: ``_score_parents`` runs in front of the list
+        (its decisions in ``P.dec`` are overwritten by the pick), and a learning round has its scorer inputs from that one ascent."""
+        if self.strong_G:
+            self._score_parents(n)
         self._strong_table(self.slots[:n], n, self.P.dec, self.im_table if self.learning else None)      # (a one-job run's slots are its n)
-        if self.learning:
+        if self.learning and not self.strong_G:
             self._scorer_inputs(n)
 
     def _bound_children(self, Ch, B, warm):
@@ -888,6 +951,16 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     and "imitation_report" ([teacher, pick, candidates, violators] as flat ReLU indices and counts), one per parent row; every traced round
     of such a run carries the bounds after it, "global_lb" and "global_ub".
 
+    strong_candidates=Shortlist(babsr=M, gnn=G) (with an integer or None no launch, read, buffer or argument of a
+    round changes, and ``Shortlist(babsr=M)`` is the run ``strong_candidates=M``).  gnn=G: the candidates of a parent are its G undecided
+    nodes of highest GNN score -- ``gnnb_forward``'s scores of the parent rows, through the same ``gnnb_strong_list`` --, with both counts
+    the union of the two shortlists (``gnnb_strong_list_union``; at most M + G per parent).  In a "gnn" run the committed decision, the
+    scorer's arg-max, is then always a candidate: its table row has an entry there, and a learning round's report ``pick`` is the decision
+    that was made.  In a "strong" run the round runs ``gnnb_dual_ascent`` at n_iter 0 and ``gnnb_forward`` on the parents in front of the
+    list ("the GNN proposes, the bounds dispose"); a learning round does not run that ascent a second time.  A gnn count needs a choice
+    whose model is a GraphNet and is refused with "babsr".  No read is added.  Audit dicts of such a run also hold "sources" (per candidate
+    1: BaBSR's shortlist only, 2: the GNN's only, 3: both) and a traced strong round "strong_sources".
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
                       decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, imitate, imitate_margin,
@@ -959,6 +1032,8 @@ def _report_launched(run, trace, e, row0, k, tag):
         rows = _strong_rows(run, k, row0)
         if traced_strong:
             t.update(strong_candidates=[r["candidates"] for r in rows], strong_improvement=[r["improvements"] for r in rows])
+            if rows and "sources" in rows[0]:                     # (a run with a gnn count, section 7.14)
+                t.update(strong_sources=[r["sources"] for r in rows])
         if run.strong_audit is not None:
             run.strong_audit.extend({**r, **tag} for r in rows)
     return t
@@ -1004,7 +1079,8 @@ def _tally_entry(run, tally, e, k, st):
 def _strong_rows(run, k, row0=0):
     """One dict per parent of the rows [row0, row0 + k) of the round just launched (device-to-host copies; a traced or audited run
     only): its slot, the decision the round committed and that decision's improvement from the round's own children, the table's decision
-    and best improvement, and the row's candidates (flat ReLU indices) with their improvements.  A one-job round is the rows [0, k); an
+    and best improvement, and the row's candidates (flat ReLU indices) with their improvements and, in a run with a gnn count (DESIGN.md section
+    7.14), their "sources" (1: BaBSR's shortlist only, 2: the scorer's only, 3: both).  A one-job round is the rows [0, k); an
     entry of a many-jobs round its own, whose candidates are the range [cand0[row0], cand0[row0 + k]) of the lists."""
     from .bab_caller import gnn_improvement
     inf, nan = float("inf"), float("nan")
@@ -1021,6 +1097,9 @@ def _strong_rows(run, k, row0=0):
     q0 = cand0[0]
     cand0 = [q - q0 for q in cand0]
     cand_dec, imp = run.cand_dec[q0:q0 + cand0[-1]].cpu().tolist(), run.s_imp[q0:q0 + cand0[-1]].cpu().tolist()
+    src = None                                                    # (a run without a gnn count is the run it was: no "sources")
+    if getattr(run, "strong_G", 0):                               # the union's cand_src; the scorer's shortlist alone: every candidate is its own
+        src = [2] * cand0[-1] if getattr(run, "cand_src", None) is None else run.cand_src[q0:q0 + cand0[-1]].cpu().tolist()
     rows = []
     for i in range(k):
         lbs = [inf if infeasible[c] else bound[c] for c in (2 * i, 2 * i + 1)]
@@ -1028,6 +1107,8 @@ def _strong_rows(run, k, row0=0):
         a, b = cand0[i], cand0[i + 1]
         rows.append({"slot": slots[i], "decision": dec[i], "improvement": own, "strong_decision": s_dec[i], "best_improvement": best[i],
                      "candidates": [off[l] + j for l, j in cand_dec[a:b]], "improvements": imp[a:b]})
+        if src is not None:
+            rows[-1]["sources"] = src[a:b]
     return rows
 
 
@@ -1506,7 +1587,8 @@ def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, ca
 
     branching: "strong" -- every parent of every job is split where its bound improves most over its candidates -- or "gnn", legal only
     with ``strong_audit`` or ``imitate`` (``verify_properties`` runs the jobs on the GNN without a table; ``verify_properties_babsr`` on
-    BaBSR).  strong_candidates, strong_chunk, strong_audit, imitate, imitate_margin: ``branch_and_bound_frontier``'s.  The candidates of
+    BaBSR).  strong_candidates (a ``Shortlist`` included: the jobs of a pool share the scorer that shortlists, as they share it for
+    ``imitate``), strong_chunk, strong_audit, imitate, imitate_margin: ``branch_and_bound_frontier``'s.  The candidates of
     all parent rows of a round, of all jobs, form ONE dense list that is bounded in chunks of ``strong_chunk``; a chunk may span parents
     and jobs, and ``gnnb_strong_rows_jobs`` gives every candidate's child rows their own job's box and property row first.  The round's
     one extra read is cand0 at every entry's first row and the total (``StrongJobsRun.read_candidates``, 4 (entries + 1) bytes).

@@ -580,6 +580,31 @@ int gnnb_strong_pick(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int
                      const int32_t* live, const int32_t* infeasible, const double* bound, int32_t* decisions, double* best_improvement,
                      double* improvement, double* table, void* stream);
 
+/* The union of two shortlists (frontier.Shortlist(babsr=M, gnn=G)): the candidates of gnnb_strong_list from two
+ * score arrays at once, e.g. gnnb_babsr's and gnnb_forward's scores_padded, so that a parent's table holds the scorer's own choice.
+ *
+ * THE RULE.  For row i let S_a be exactly the candidate set gnnb_strong_list gives for (scores_a, top_a): the first top_a undecided nodes
+ * (scorer_mask[i, r] != 0) in the total order (score descending as float VALUES, flat index ascending; -0.0 == +0.0, +-inf are ordinary
+ * values; fewer than top_a undecided nodes: all of them), and S_b the same for (scores_b, top_b).  The row's candidates are S_a u S_b,
+ * each node once, emitted in ascending flat ReLU index.  cand_src[q] (device (n) int32, required) is 1 for a node in S_a only, 2 for one
+ * in S_b only, 3 for one in both.  A NaN at an undecided node in EITHER array empties the row; a NaN at a decided node is ignored.  A row
+ * whose slot is outside the pool gets no candidates, a row with no undecided node none.  cand0, cand_row, cand_slot and cand_dec mean what
+ * they mean for gnnb_strong_list: cand0[K] = n, entries from n on are not written; the caller sizes the lists for
+ * K * min(R, top_a + top_b) entries.
+ *
+ * Four launches: k_strong_count once per array (its bisection, one (mode, count, key, ties) record per row and array), then
+ * k_strong_union_count (the walk over the row in tiles of 256 nodes with one running tie rank per array; the row's union count) and
+ * k_strong_union_compact (k_strong_compact's prefix over the rows' counts in row order, the walk again, the entries).  The first three run
+ * under the profile class k_strong_count, the last under k_strong_compact.  Stream-ordered, no allocation, no synchronisation, no atomics,
+ * no workgroup waits on another; nothing depends on K or on a row's place.  GNNB_E_INVALID before any launch for a null handle or
+ * required argument, K outside 1..32767, top_a < 1 or top_b < 1 (one list alone is gnnb_strong_list), or a network past the 4096-node cap;
+ * GNNB_E_STATE before gnnb_bind_network; GNNB_E_NOMEM for a short workspace (gnnb_strong_list_union_workspace_bytes; 0 for a null or
+ * unbound handle). */
+size_t gnnb_strong_list_union_workspace_bytes(const gnnb_t* h, int K);
+int gnnb_strong_list_union(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const float* scorer_mask, const float* scores_a,
+                           int top_a, const float* scores_b, int top_b, int32_t* cand0, int32_t* cand_row, int32_t* cand_slot,
+                           int32_t* cand_dec, int32_t* cand_src, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Strong branching for many jobs in one pool (frontier.verify_properties_strong): the boxes and property rows of a
  * chunk of c candidates, by the segment of their slot.  cand_slot: device (c) int32, a chunk of gnnb_strong_list's cand_slot; the pool is
  * `segments` segments of seg_cap slots and seg_x_lo / seg_x_hi (segments, N_0) fp64, seg_prop_w (segments, N_L) fp32, seg_prop_b
