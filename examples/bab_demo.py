@@ -72,12 +72,17 @@ def main():
     ap.add_argument("--gnn-candidates", type=int, default=None, metavar="G", help="with --branching strong or --imitate N: also bound the G undecided nodes of highest GNN score")
     ap.add_argument("--imitate", type=int, default=None, metavar="N", help="with --frontier K: every N-th round learns the GNN from its strong-branching table")
     ap.add_argument("--imitate-margin", type=float, default=None, metavar="M", help="with --imitate N: the margin per unit of improvement (default 1.0)")
+    ap.add_argument("--repack", default=None, choices=("host", "device"),
+                    help="with --frontier K and --online N or --imitate N, one property: where the scorer's packs are rebuilt after a learning step "
+                         "(device: on the stream, the step does not wait; DESIGN.md section 7.15)")
     args = ap.parse_args()
     if args.imitate is not None and (args.frontier is None or args.imitate < 1 or args.branching == "babsr" or args.threshold is not None
                                      or args.online is not None):
         ap.error("--imitate N needs --frontier K and N >= 1, and takes no --branching babsr, --threshold or --online")
     if args.imitate_margin is not None and (args.imitate is None or not args.imitate_margin >= 0):
         ap.error("--imitate-margin M needs --imitate N, and M >= 0")
+    if args.repack is not None and (args.frontier is None or args.props is not None or (args.online is None and args.imitate is None)):
+        ap.error("--repack needs --frontier K with --online N or --imitate N, and one property (no --props)")
     if args.branching is not None and args.frontier is None:
         ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
     if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
@@ -166,6 +171,8 @@ def main():
         stats = {}
         if args.imitate is not None:
             upper.update(imitate=args.imitate, **({} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}))
+        if args.repack is not None:
+            upper.update(repack=args.repack)
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
                                                                       max_rounds=max(1, args.nodes // (2 * args.frontier)),
                                                                       branching_threshold=args.threshold, stats=stats, online_threshold=args.online,

@@ -66,6 +66,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_frontier.h"
 #include "gnnb_k_starts.h"
 #include "gnnb_k_strong.h"
+#include "gnnb_k_repack.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -221,6 +222,13 @@ struct gnnb_handle : BoundNet {
   std::unique_ptr<gnnb_train::Trainer> trainer;     // online learning (gnnb_online_create)
   DevBuf<float> pack_block;     // the weight packs, one block ...
   float* d_pack[N_PACKS] = {nullptr};      // ... and where pack i starts in it (load_weights)
+  // the device pack builder (gnnb_k_repack.h; made with the trainer): fold scratch and segment table; repack_mode 1: the packs follow
+  // the trainer's d_w on the stream and `blob` is refreshed from it on demand (fresh_blob)
+  int repack_mode = 0;
+  bool blob_stale = false;
+  DevBuf<float> repack_scr;
+  DevBuf<RepackSeg> repack_segs;
+  int repack_nseg = 0, repack_nblocks = 0;
   DevBuf<float> d_zero;         // 64 zero floats: where masked gather loads point
   // List counters of a forward (64 ints) live HERE, not in the caller's workspace: a control block per workspace address (CTL_SLOTS
   // of them, least recently used replaced), zero whenever no forward is running on it -- the last workgroup of k_score, the last
@@ -264,6 +272,9 @@ static int load_weights(gnnb_t* h, const float* w_blob, hipStream_t st) {
   // runtime (0.3 ms of the 1.4 ms this call took behind every online-learning step)
   size_t total = 0;
   for (int i = 0; i < N_PACKS; ++i) total += (pv[i]->size() + 63) & ~(size_t)63;
+  for (int i = 0; i < N_PACKS; ++i)
+    if (pv[i]->size() != (size_t)kPackFloats[i]) return fail(GNNB_E_INVALID, "load_weights: pack %d has %zu floats, kPackFloats says %d", i, pv[i]->size(), kPackFloats[i]);
+  h->blob_stale = false;
   HIPCHK(h->pack_stage.grow(total));
   if (!h->pack_block.get()) {             // one device block, pack i at the offset it has in the staging buffer: one copy per call
     HIPCHK(h->pack_block.alloc(total));
@@ -2465,9 +2476,31 @@ extern "C" int gnnb_frontier_witness_jobs(gnnb_t* h, const gnnb_plan* plan, int 
 // ================================================================================================================
 // Online learning (reference graphnet/graph_score_online.py:9-23, :62-77)
 // ================================================================================================================
+// The device pack builder: the packs from the trainer's d_w, in place, on `st` (k_repack_fold, k_repack_emit).  Allocates nothing and
+// does not synchronise.
+static int repack_device(gnnb_t* h, hipStream_t st) {
+  const float* d_w = h->trainer->d_w.get();
+  float* scr = h->repack_scr.get();
+  hipLaunchKernelGGL(k_repack_fold, dim3((kFoldJobElems + kRepackBlock - 1) / kRepackBlock, kFoldJobs), dim3(kRepackBlock), 0, st, d_w, scr);
+  hipLaunchKernelGGL(k_repack_emit, dim3((unsigned)h->repack_nblocks), dim3(kRepackBlock), 0, st, h->repack_segs.get(), h->repack_nseg, d_w,
+                     (const float*)scr, h->pack_block.get());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GNNB_E_HIP, "launch of k_repack_fold / k_repack_emit failed: %s", hipGetErrorString(e));
+  return GNNB_OK;
+}
+// h->blob as the trainer's d_w has it: a step in repack mode 1 leaves the host copy behind (every reader of h->blob calls this first)
+static int fresh_blob(gnnb_t* h) {
+  if (!h->blob_stale) return GNNB_OK;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h->blob.data(), h->trainer->d_w.get(), blob_floats() * sizeof(float), hipMemcpyDeviceToHost));
+  h->blob_stale = false;
+  return GNNB_OK;
+}
+
 extern "C" int gnnb_get_weights(const gnnb_t* h, float* w_blob, size_t n_floats) {
   if (!h || !w_blob) return fail(GNNB_E_INVALID, "gnnb_get_weights: null argument");
   if (n_floats != blob_floats()) return fail(GNNB_E_INVALID, "gnnb_get_weights: %zu floats, expected %zu", n_floats, blob_floats());
+  if (int rc = fresh_blob(const_cast<gnnb_t*>(h))) return rc;
   memcpy(w_blob, h->blob.data(), n_floats * sizeof(float));
   return GNNB_OK;
 }
@@ -2476,14 +2509,88 @@ extern "C" int gnnb_set_weights(gnnb_t* h, const float* w_blob, size_t n_floats)
   if (!h || !w_blob) return fail(GNNB_E_INVALID, "gnnb_set_weights: null argument");
   if (n_floats != blob_floats()) return fail(GNNB_E_INVALID, "gnnb_set_weights: %zu floats, expected %zu", n_floats, blob_floats());
   HIPCHK(hipDeviceSynchronize());          // no forward may still be reading the packs
+  if (h->trainer && h->repack_mode == 1) {      // the packs come from the mode's builder: blob to d_w, then the device builder
+    h->blob.assign(w_blob, w_blob + n_floats);
+    h->blob_stale = false;
+    HIPCHK(hipMemcpy(h->trainer->d_w.get(), w_blob, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = repack_device(h, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return GNNB_OK;
+  }
   if (int rc = load_weights(h, w_blob, nullptr)) return rc;
   if (h->trainer) HIPCHK(hipMemcpy(h->trainer->d_w.get(), w_blob, n_floats * sizeof(float), hipMemcpyHostToDevice));
+  return GNNB_OK;
+}
+
+// Which builder rebuilds the packs after a learning step: 0 (default) build_packs on the host, 1 the device builder on the step's stream.
+extern "C" int gnnb_online_set_repack(gnnb_t* h, int mode) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_online_set_repack: null handle");
+  if (!h->trainer) return fail(GNNB_E_STATE, "gnnb_online_set_repack: no trainer (gnnb_online_create)");
+  if (mode != 0 && mode != 1) return fail(GNNB_E_INVALID, "gnnb_online_set_repack: mode = %d (0: host builder, 1: device builder)", mode);
+  if (mode == h->repack_mode) return GNNB_OK;
+  HIPCHK(hipDeviceSynchronize());          // no forward may still be reading the packs
+  if (mode == 1) {
+    if (int rc = repack_device(h, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+  } else {
+    if (int rc = fresh_blob(h)) return rc;
+    const std::vector<float> w(h->blob);
+    if (int rc = load_weights(h, w.data(), nullptr)) return rc;
+  }
+  h->repack_mode = mode;
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_repack(gnnb_t* h, void* stream) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_repack: null handle");
+  if (!h->trainer) return fail(GNNB_E_STATE, "gnnb_repack: no trainer (gnnb_online_create)");
+  return repack_device(h, (hipStream_t)stream);
+}
+
+// Inspection: every float of the pack block becomes a NaN (tests: a builder that runs next has to write them all).  Device-synchronising.
+extern "C" int gnnb_debug_poison_packs(gnnb_t* h) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_debug_poison_packs: null handle");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemset(h->pack_block.get(), 0xff, h->pack_block.size() * sizeof(float)));
+  HIPCHK(hipDeviceSynchronize());
+  return GNNB_OK;
+}
+
+// Inspection: pack `which` (0..13: embed, pre_fwd, pre_bwd, pre_inp, prop, upd_fwd_e, upd_fwd_i, upd_fwd_f, upd_bwd, upd_bwd_b, upd_inp,
+// post_inp, score_b, score_f) as it stands in device memory, after a device synchronise.
+extern "C" int gnnb_pack_image(const gnnb_t* h, int which, float* host_buf, size_t cap, size_t* n_floats) {
+  if (!h) return fail(GNNB_E_INVALID, "gnnb_pack_image: null handle");
+  if (which < 0 || which >= N_PACKS) return fail(GNNB_E_INVALID, "gnnb_pack_image: which = %d outside [0, %d)", which, N_PACKS);
+  const size_t n = (size_t)kPackFloats[which];
+  if (n_floats) *n_floats = n;
+  if (!host_buf && cap == 0 && n_floats) return GNNB_OK;      // a size query
+  if (!host_buf) return fail(GNNB_E_INVALID, "gnnb_pack_image: null buffer");
+  if (cap < n) return fail(GNNB_E_INVALID, "gnnb_pack_image: room for %zu floats, pack %d has %zu", cap, which, n);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(host_buf, h->d_pack[which], n * sizeof(float), hipMemcpyDeviceToHost));
   return GNNB_OK;
 }
 
 // torch.optim.Adam(model.parameters(), lr, weight_decay) of graph_score_online.py:15; the moments start at zero
 extern "C" int gnnb_online_create(gnnb_t* h, float lr, float weight_decay) {
   if (!h) return fail(GNNB_E_INVALID, "gnnb_online_create: null handle");
+  if (int rc = fresh_blob(h)) return rc;           // (a trainer in repack mode 1 is being replaced: its parameters are the handle's)
+  if (h->repack_mode == 1) {                       // the mode goes back to 0: the packs come from the host builder again
+    HIPCHK(hipDeviceSynchronize());
+    const std::vector<float> w(h->blob);
+    if (int rc = load_weights(h, w.data(), nullptr)) return rc;
+    h->repack_mode = 0;
+  }
+  if (!h->repack_segs.get()) {
+    const std::vector<RepackSeg> segs = repack_segments(&h->repack_nblocks);
+    for (const RepackSeg& s : segs)
+      if (s.dst < 0 || (size_t)s.dst + repack_seg_floats(s) > h->pack_block.size())
+        return fail(GNNB_E_INVALID, "gnnb_online_create: a pack segment ends outside the pack block");
+    HIPCHK(h->repack_segs.upload(segs.data(), segs.size()));
+    h->repack_nseg = (int)segs.size();
+    HIPCHK(h->repack_scr.alloc(RepackScr::FLOATS));
+    HIPCHK(hipMemset(h->repack_scr.get(), 0, RepackScr::FLOATS * sizeof(float)));
+  }
   h->trainer.reset(new gnnb_train::Trainer());
   gnnb_train::Trainer* t = h->trainer.get();
   t->lr = lr; t->wd = weight_decay;
@@ -2506,6 +2613,7 @@ extern "C" int gnnb_online_create(gnnb_t* h, float lr, float weight_decay) {
 extern "C" int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats) {
   if (!h || !grad || !h->trainer) return fail(GNNB_E_STATE, "gnnb_online_grad: no trainer (gnnb_online_create)");
   if (n_floats != blob_floats()) return fail(GNNB_E_INVALID, "gnnb_online_grad: %zu floats, expected %zu", n_floats, blob_floats());
+  if (h->repack_mode == 1) HIPCHK(hipDeviceSynchronize());      // a mode-1 step may still be running on a stream the copy does not wait for
   HIPCHK(hipMemcpy(grad, h->trainer->d_g.get(), n_floats * sizeof(float), hipMemcpyDeviceToHost));
   return GNNB_OK;
 }
@@ -2555,6 +2663,7 @@ static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const Step
   const int K = (int)h->N.size() - 1, L = K - 1, R = h->R, T = h->T;
   Trainer& t = *h->trainer;
   t.st = st;
+  t.ordered = h->repack_mode == 1 && apply && !loss_host;      // this call returns without synchronising
   t.n_cu = h->n_cu;
   t.tape.clear();
   t.ndesc = 0;
@@ -2775,10 +2884,16 @@ static int online_step_device(gnnb_t* h, const gnnb_batch* in, int B, const Step
     const double bc1 = 1.0 - std::pow(b1, t.step), bc2 = 1.0 - std::pow(b2, t.step);
     TAdam a{d_w, d_g, t.d_m.get(), t.d_v.get(), (int)blob_floats(), (float)(t.lr / bc1), t.wd, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-8f, (float)std::sqrt(bc2)};
     hipLaunchKernelGGL(k_tadam, dim3((unsigned)((blob_floats() + 255) / 256)), dim3(256), 0, st, a);
-    std::vector<float> nw(blob_floats());
-    HIPCHK(hipMemcpyAsync(nw.data(), d_w, nw.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (int rc = load_weights(h, nw.data(), st)) return rc;      // the scorer's folded packs follow the new parameters
+    if (h->repack_mode == 1) {              // the packs follow on the stream; nothing crosses the link, nothing waits
+      if (int rc = repack_device(h, st)) return rc;
+      h->blob_stale = true;
+      if (loss_host) HIPCHK(hipStreamSynchronize(st));
+    } else {
+      std::vector<float> nw(blob_floats());
+      HIPCHK(hipMemcpyAsync(nw.data(), d_w, nw.size() * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (int rc = load_weights(h, nw.data(), st)) return rc;      // the scorer's folded packs follow the new parameters
+    }
   } else {
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -2803,7 +2918,9 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   HIPCHK(hipMemcpyAsync(t.d_imp.get(), improvement, (size_t)B * 4, hipMemcpyHostToDevice, st));
   StepLoss lf;
   lf.d_kw = t.d_kw.get(); lf.d_imp = t.d_imp.get();
-  return online_step_device(h, in, B, lf, loss, nullptr, scores_padded, nullptr, apply, st, false, who);
+  if (int rc = online_step_device(h, in, B, lf, loss, nullptr, scores_padded, nullptr, apply, st, false, who)) return rc;
+  if (h->repack_mode == 1 && apply && !loss) HIPCHK(hipStreamSynchronize(st));      // this entry point always returns a finished step
+  return GNNB_OK;
 }
 
 // The body gnnb_online_step_rows and gnnb_imitation_step_rows share behind their checks: the gather, then online_step_device under `lf`.
@@ -2847,7 +2964,8 @@ static int step_rows_device(gnnb_t* h, const gnnb_batch* in, int K, const int32_
 
 // gnnb_online_step on the rows rows[0..n) of the K-row device batch `in`, in list order, nothing crossing the link: k_trows_gather copies
 // the listed rows of every tensor the step reads into dense n-row buffers out of the trainer's arena, then online_step_device runs at B = n
-// on them.  Synchronises where gnnb_online_step does.
+// on them.  Repack mode 0: synchronises where gnnb_online_step does.  Mode 1 with apply = 1: the step and the pack rebuild are issued on the
+// stream and the call returns without synchronising (include/gnnb.h, gnnb_online_set_repack).
 extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index,
                                      const float* improvement, float* loss, int32_t* status, int apply, void* stream) {
   const char* who = "gnnb_online_step_rows";
@@ -2863,7 +2981,7 @@ extern "C" int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, con
 // ---- the imitation step: gnnb_online_step_rows under the table loss of k_tloss_table ----
 // table (DEVICE, (K, R) fp64, row = batch row): what gnnb_strong_pick leaves, NaN where a node is no candidate.  loss (n) fp32, report_i
 // (n, 4) int32 [teacher, pick, n_cand, n_viol], regret (n) fp64 and status (int32[1], zeroed by the caller) are DEVICE memory and may be
-// NULL.  Synchronises where gnnb_online_step_rows does.
+// NULL.  Synchronises where gnnb_online_step_rows does (repack mode 1 with apply = 1: not at all).
 extern "C" int gnnb_imitation_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const double* table, double margin,
                                         float* loss, int32_t* report_i, double* regret, int32_t* status, int apply, void* stream) {
   const char* who = "gnnb_imitation_step_rows";

@@ -31,12 +31,19 @@
 
 #include "../../include/gnnb.h"
 
+// functions the device pack builder (gnnb_k_repack.h) runs per thread and tests/test_repack_cpu.py runs as plain loops
+#if defined(__HIPCC__)
+#define GNNB_HD __host__ __device__
+#else
+#define GNNB_HD
+#endif
+
 namespace gnnb {
 
 constexpr int P = 64;  // embedding width (reference graph_score.py:9: GraphNet(2, 64))
 
 // feature index held by fragment register R in lane half h
-inline int frag_feature(int R, int h) { return 8 * (R >> 2) + 4 * h + (R & 3); }
+GNNB_HD inline int frag_feature(int R, int h) { return 8 * (R >> 2) + 4 * h + (R & 3); }
 
 // ---- the 26 Linear layers in state-dict order ----
 enum LayerId {
@@ -45,7 +52,7 @@ enum LayerId {
   L_BC4, L_BC4_1, L_FNODE, L_FSCORE, L_COUNT
 };
 struct LinDef { int out, in; };
-static const LinDef kLin[L_COUNT] = {
+static constexpr LinDef kLin[L_COUNT] = {
     {64, 3},  {64, 64}, {64, 2},  {64, 64},  {64, 128}, {64, 64}, {64, 7},   {64, 64}, {64, 128},
     {64, 64}, {64, 128}, {64, 64}, {64, 4},  {64, 128}, {64, 64}, {64, 7},   {64, 64}, {64, 64},
     {64, 192}, {64, 64}, {64, 128}, {64, 64}, {64, 128}, {64, 64}, {64, 64}, {1, 64}};
@@ -55,12 +62,21 @@ inline size_t blob_floats() {
   for (int i = 0; i < L_COUNT; ++i) n += (size_t)kLin[i].out * kLin[i].in + kLin[i].out;
   return n;  // 117825
 }
-inline size_t weight_offset(int id) {
-  size_t n = 0;
-  for (int i = 0; i < id; ++i) n += (size_t)kLin[i].out * kLin[i].in + kLin[i].out;
-  return n;
+// where layer id's weight and bias start in the blob, and its input width: one table, folded at compile time, that host code and the
+// device pack builder (gnnb_k_repack.h) both read
+struct LinTab { int w[L_COUNT], b[L_COUNT], in[L_COUNT]; };
+constexpr LinTab make_lin_tab() {
+  LinTab t{};
+  int n = 0;
+  for (int i = 0; i < L_COUNT; ++i) {
+    t.w[i] = n; t.b[i] = n + kLin[i].out * kLin[i].in; t.in[i] = kLin[i].in;
+    n += kLin[i].out * kLin[i].in + kLin[i].out;
+  }
+  return t;
 }
-inline size_t bias_offset(int id) { return weight_offset(id) + (size_t)kLin[id].out * kLin[id].in; }
+GNNB_HD inline size_t weight_offset(int id) { constexpr LinTab t = make_lin_tab(); return (size_t)t.w[id]; }
+GNNB_HD inline size_t bias_offset(int id) { constexpr LinTab t = make_lin_tab(); return (size_t)t.b[id]; }
+GNNB_HD inline int lin_in(int id) { constexpr LinTab t = make_lin_tab(); return t.in[id]; }
 
 // ---- operand-order packing ----
 // 64 x (64*nfrag) block of W (row stride ldw, starting at column col0), A-operand order for
@@ -150,7 +166,7 @@ inline void pack_vec64(float* dst, const float* v) {
     for (int R = 0; R < 32; ++R) dst[h * 32 + R] = v[frag_feature(R, h)];
 }
 
-inline int gather_feature(int R, int h) {           // channel held by register R = 16*it + r after a gather
+GNNB_HD inline int gather_feature(int R, int h) {         // channel held by register R = 16*it + r after a gather
   const int it = R >> 4, r = R & 15;
   return 2 * ((r & 3) + 8 * (r >> 2) + 4 * h) + it;
 }
@@ -483,6 +499,267 @@ inline void build_packs(const float* blob, Packs& pk) {
   pack_transposed(&pk.prop[PackProp::W3T], W(L_OUT3), 64, 64);
   std::memcpy(&pk.prop[PackProp::B3], Bv(L_OUT3), 64 * sizeof(float));
 }
+
+// ------------------------------------------------------------------------------------------
+// The pack image element by element: what the device builder (gnnb_k_repack.h) runs, one thread per element.
+// Two steps.  FOLD: every folded quantity of build_packs, row-major, fp32, into a scratch block (RepackScr) -- one fp64 accumulator
+// per entry, k ascending, one explicit fma per term, rounded to fp32 where build_packs rounds; a fold that starts from another
+// fold's rounded value (B2 and B5 from bcb) recomputes that one entry itself, so there is one dependency level.  EMIT: every float
+// (or 16-byte group of bf16 pieces) of the 14 packs from the parameter blob or the scratch block through an index map
+// (destination index -> source index); the maps below are build_packs' loops read backwards.  tests/test_repack_cpu.py compares
+// the result with build_packs on the CPU; the device runs the same functions.
+// ------------------------------------------------------------------------------------------
+constexpr int kPacks = 14;      // in the order of gnnb_pt_pack / load_weights
+constexpr int kPackFloats[kPacks] = {PackEmbed::FLOATS, PackPreFwd::FLOATS3, PackPreBwd::FLOATS3, PackPreInp::FLOATS, PackProp::FLOATS,
+                                     PackUpd::FLOATS_ALL, PackUpd::FLOATS_ALL, PackUpd::FLOATS_ALL, PackUpd::FLOATS_ALL, PackUpd::FLOATS_ALL,
+                                     PackUpdInp::FLOATS, PackPostInp::FLOATS, PackScore::FLOATS, PackScore::FLOATS};
+inline size_t pack_block_offset(int which) {      // pack `which` inside the handle's block: every pack starts on a multiple of 64 floats
+  size_t o = 0;
+  for (int i = 0; i < which; ++i) o += ((size_t)kPackFloats[i] + 63) & ~(size_t)63;
+  return o;
+}
+
+// the fold scratch: row-major fp32 blocks
+struct RepackScr {
+  enum { CBF_W = 0, CBF_B = CBF_W + 4096, CBB_W = CBF_B + 64, CBB_B = CBB_W + 4096,       // Wcb, bcb: forward (fc3_2, fc4), backward (bc3_1, bc4)
+         UP = CBB_B + 64, UP_WA = 0, UP_WAS = 8192, UP_VAW = 12288, UP_STRIDE = 12416,    // the four updates with a folded projection (e, i, f, b)
+         WASB = UP + 4 * UP_STRIDE,                                                       // summed halves of bc3 (upd_bwd: no projection)
+         PF_W2 = WASB + 4096, PF_B2 = PF_W2 + 4096, PB_W5 = PF_B2 + 64, PB_B5 = PB_W5 + 4096, PI_W2 = PB_B5 + 64, PI_B2 = PI_W2 + 4096,
+         WC = PI_B2 + 64, VC = WC + 4096,                                                 // post_inp's map; upd_inp's [t, 0] pairs (128)
+         SB_W1 = VC + 128, SB_V1 = SB_W1 + 4096, SF_W1 = SB_V1 + 128, SF_V1 = SF_W1 + 4096,   // score heads: bc4_1 / fc4_2 deferred
+         PR_W2B = SF_V1 + 128, PR_V2 = PR_W2B + 4096, FLOATS = PR_V2 + 64 };
+};
+constexpr int kFoldJobs = 14, kFoldJobElems = 4096 + 64;      // per job: a 64 x 64 block (element i * 64 + j), then a 64-vector
+
+enum { FJ_MV, FJ_UPD, FJ_SUM, FJ_PRE };
+// FJ_MV : block = A[:, acol:acol+64] . W(b);  vector = A[:, acol:acol+64] . bias(b) + bias(y0)  (y0 < 0: none; pair: stored as [v, 0] pairs)
+// FJ_UPD: a = Wa, b = the deferred projection: t0 = Wa[:, :64].Wp, t1 = Wa[:, 64:].Wp in fp64 -> WA = [t0, t1], WAS = t0 + t1; VAW pairs
+// FJ_SUM: WAS = Wa[:, :64] + Wa[:, 64:]
+// FJ_PRE: block = W(a)[:, :64] . W(b);  vector = W(a)[:, :64] . bias(b) + bcb,  bcb = bias(a) + W(a)[:, 64:] . bias(c) rounded to fp32 first
+struct FoldJob { int kind, a, acol, b, y0, pair, c, dw, dv; };
+GNNB_HD inline FoldJob repack_fold_job(int j) {
+  typedef RepackScr S;
+  switch (j) {
+    case 0: return FoldJob{FJ_MV, L_FC4, 64, L_FC3_2, L_FC4, 0, 0, S::CBF_W, S::CBF_B};
+    case 1: return FoldJob{FJ_MV, L_BC4, 64, L_BC3_1, L_BC4, 0, 0, S::CBB_W, S::CBB_B};
+    case 2: return FoldJob{FJ_UPD, L_FC3, 0, L_INP_F_1, -1, 0, 0, S::UP + 0 * S::UP_STRIDE, 0};
+    case 3: return FoldJob{FJ_UPD, L_FC3, 0, L_INP_B2_2, -1, 0, 0, S::UP + 1 * S::UP_STRIDE, 0};
+    case 4: return FoldJob{FJ_UPD, L_FC3, 0, L_FC4_2, -1, 0, 0, S::UP + 2 * S::UP_STRIDE, 0};
+    case 5: return FoldJob{FJ_UPD, L_BC3, 0, L_BC4_1, -1, 0, 0, S::UP + 3 * S::UP_STRIDE, 0};
+    case 6: return FoldJob{FJ_SUM, L_BC3, 0, 0, -1, 0, 0, S::WASB, 0};
+    case 7: return FoldJob{FJ_PRE, L_FC4, 0, L_FC1_1, -1, 0, L_FC3_2, S::PF_W2, S::PF_B2};
+    case 8: return FoldJob{FJ_PRE, L_BC4, 0, L_BC2_1, -1, 0, L_BC3_1, S::PB_W5, S::PB_B5};
+    case 9: return FoldJob{FJ_MV, L_INP_B2, 0, L_INP_B_1, L_INP_B2, 0, 0, S::PI_W2, S::PI_B2};
+    case 10: return FoldJob{FJ_MV, L_INP_B2, 64, L_BC4_1, -1, 1, 0, S::WC, S::VC};
+    case 11: return FoldJob{FJ_MV, L_FNODE, 0, L_BC4_1, -1, 1, 0, S::SB_W1, S::SB_V1};
+    case 12: return FoldJob{FJ_MV, L_FNODE, 0, L_FC4_2, -1, 1, 0, S::SF_W1, S::SF_V1};
+    default: return FoldJob{FJ_MV, L_OUT2, 64, L_FC4_2, -1, 0, 0, S::PR_W2B, S::PR_V2};
+  }
+}
+// acc + sum_k a[k] b[k * sb], k = 0..63 ascending, one fp64 fma per term
+GNNB_HD inline double fold_dot64(const float* a, const float* b, int sb, double acc) {
+  for (int k = 0; k < 64; ++k) acc = __builtin_fma((double)a[k], (double)b[(size_t)k * sb], acc);
+  return acc;
+}
+// element e (< kFoldJobElems) of fold job j
+GNNB_HD inline void repack_fold_elem(const float* blob, float* scr, int j, int e) {
+  const FoldJob f = repack_fold_job(j);
+  const float* A = blob + (int)weight_offset(f.a);
+  const int lda = lin_in(f.a);
+  if (e < 4096) {
+    const int i = e >> 6, c = e & 63;
+    if (f.kind == FJ_SUM) {
+      scr[f.dw + e] = (float)((double)A[i * 128 + c] + (double)A[i * 128 + 64 + c]);
+    } else if (f.kind == FJ_UPD) {
+      const float* Wp = blob + (int)weight_offset(f.b) + c;
+      const double t0 = fold_dot64(A + i * 128, Wp, 64, 0.0), t1 = fold_dot64(A + i * 128 + 64, Wp, 64, 0.0);
+      float* u = scr + f.dw;
+      u[RepackScr::UP_WA + i * 128 + c] = (float)t0;
+      u[RepackScr::UP_WA + i * 128 + 64 + c] = (float)t1;
+      u[RepackScr::UP_WAS + e] = (float)(t0 + t1);
+    } else {
+      scr[f.dw + e] = (float)fold_dot64(A + (size_t)i * lda + f.acol, blob + (int)weight_offset(f.b) + c, 64, 0.0);
+    }
+    return;
+  }
+  const int i = e - 4096;
+  const float* x = blob + (int)bias_offset(f.b);
+  if (f.kind == FJ_UPD) {
+    float* vaw = scr + f.dw + RepackScr::UP_VAW;
+    vaw[2 * i] = (float)fold_dot64(A + i * 128, x, 1, 0.0);
+    vaw[2 * i + 1] = (float)fold_dot64(A + i * 128 + 64, x, 1, 0.0);
+  } else if (f.kind == FJ_PRE) {
+    const float bcb = (float)fold_dot64(A + i * 128 + 64, blob + (int)bias_offset(f.c), 1, (double)blob[(int)bias_offset(f.a) + i]);
+    scr[f.dv + i] = (float)fold_dot64(A + i * 128, x, 1, (double)bcb);
+  } else if (f.kind == FJ_MV) {
+    const float v = (float)fold_dot64(A + (size_t)i * lda + f.acol, x, 1, f.y0 >= 0 ? (double)blob[(int)bias_offset(f.y0) + i] : 0.0);
+    if (f.pair) { scr[f.dv + 2 * i] = v; scr[f.dv + 2 * i + 1] = 0.0f; }
+    else scr[f.dv + i] = v;
+  }
+}
+
+// ---- index maps: destination index -> source index ----
+GNNB_HD inline int map_w64(int d, int ldw, int col0) {                 // pack_w64
+  const int q = d >> 2, lane = q & 63, t = q >> 6, it = t & 1, s = ((t >> 1) << 2) | (d & 3);
+  return (32 * it + (lane & 31)) * ldw + col0 + 64 * (s >> 5) + frag_feature(s & 31, lane >> 5);
+}
+// pack_w64_bf3: 16-byte group g = (((f * 8 + ks * 2 + ot) * 3 + piece) * 64 + lane) holds entries j = 0..7; source row and the column of j = 0
+// (entry j: column + frag_feature(8 ks + j, h) - frag_feature(8 ks, h), see map_bf3_col)
+GNNB_HD inline int map_bf3_piece(int g) { return (g >> 6) % 3; }
+GNNB_HD inline int map_bf3_row(int g) { const int lane = g & 63, c = (g / 192) & 7; return 32 * (c & 1) + (lane & 31); }
+GNNB_HD inline int map_bf3_col(int g, int j, int col0) {
+  const int lane = g & 63, c = (g / 192) & 7, f = g / 1536;
+  return col0 + 64 * f + frag_feature(8 * (c >> 1) + j, lane >> 5);
+}
+GNNB_HD inline int map_wsmall(int d, int K) {                          // pack_wsmall; -1: zero padding
+  const int lane = d & 63, it = (d >> 6) & 1, s = d >> 7, in = 2 * s + (lane >> 5);
+  return in < K ? (32 * it + (lane & 31)) * K + in : -1;
+}
+GNNB_HD inline int map_vec64(int d) { return frag_feature(d & 31, d >> 5); }      // pack_vec64
+GNNB_HD inline int map_transposed(int d, int out, int ld) { return (d % out) * ld + d / out; }      // pack_transposed, source row stride ld
+// PackPostInp::WPG: row o of the permuted matrix is row map_gather_row(o) of the natural one (gather_feature(R, h) = o -> frag_feature(R, h))
+GNNB_HD inline int map_gather_row(int o) {
+  const int it = o & 1, q = o >> 1, h = (q >> 2) & 1, r = (q & 3) + 4 * (q >> 3);
+  return frag_feature(16 * it + r, h);
+}
+// piece p (0..2) of x as bf16 bits: bf3_split_512's rule
+GNNB_HD inline unsigned bf3_piece(float x, int p) {
+  unsigned b = 0;
+  for (int q = 0; q <= p; ++q) {
+    unsigned u;
+    __builtin_memcpy(&u, &x, 4);
+    const unsigned special = (u >> 16) | ((u & 0xffffu) ? 0x40u : 0u);
+    const unsigned rounded = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    b = (((u & 0x7f800000u) == 0x7f800000u) ? special : rounded) & 0xffffu;
+    const unsigned back = b << 16;
+    float bf;
+    __builtin_memcpy(&bf, &back, 4);
+    x -= bf;
+  }
+  return b;
+}
+
+enum { RS_COPY, RS_ZERO, RS_W64, RS_W64G, RS_BF3, RS_BF3G, RS_WSMALL, RS_VEC64, RS_TRANS };
+// One segment of the pack block.  dst: float offset in the block; src: float offset in the scratch block (scr != 0) or the parameter
+// blob; threads: elements (RS_BF3*: 16-byte groups); block0: its first workgroup of kRepackBlock threads in the emit grid.
+//   RS_W64*, RS_BF3*: p0 = ldw, p1 = col0 (nfrag follows from threads; ..G: rows through map_gather_row)
+//   RS_WSMALL: p0 = K      RS_TRANS: p0 = out, p1 = source row stride
+struct RepackSeg { int kind, scr, src, dst, p0, p1, threads, block0; };
+constexpr int kRepackBlock = 256;
+struct alignas(16) RepackU4 { unsigned x, y, z, w; };
+
+GNNB_HD inline void repack_emit_elem(const RepackSeg& s, int t, const float* blob, const float* scr, float* block) {
+  const float* src = (s.scr ? scr : blob) + s.src;
+  float* dst = block + s.dst;
+  switch (s.kind) {
+    case RS_COPY: dst[t] = src[t]; break;
+    case RS_ZERO: dst[t] = 0.0f; break;
+    case RS_W64: dst[t] = src[map_w64(t, s.p0, s.p1)]; break;
+    case RS_W64G: {
+      const int m = map_w64(t, s.p0, s.p1), row = m / s.p0;
+      dst[t] = src[map_gather_row(row) * s.p0 + (m - row * s.p0)];
+      break;
+    }
+    case RS_BF3:
+    case RS_BF3G: {
+      const int p = map_bf3_piece(t);
+      int row = map_bf3_row(t);
+      if (s.kind == RS_BF3G) row = map_gather_row(row);
+      unsigned w[4] = {0, 0, 0, 0};
+      for (int j = 0; j < 8; ++j) w[j >> 1] |= bf3_piece(src[row * s.p0 + map_bf3_col(t, j, s.p1)], p) << (16 * (j & 1));
+      *reinterpret_cast<RepackU4*>(dst + 4 * (size_t)t) = RepackU4{w[0], w[1], w[2], w[3]};
+      break;
+    }
+    case RS_WSMALL: { const int m = map_wsmall(t, s.p0); dst[t] = m >= 0 ? src[m] : 0.0f; break; }
+    case RS_VEC64: dst[t] = src[map_vec64(t)]; break;
+    default: dst[t] = src[map_transposed(t, s.p0, s.p1)]; break;
+  }
+}
+
+// the segments of all 14 packs, block0 filled; *nblocks: workgroups of the emit grid
+inline std::vector<RepackSeg> repack_segments(int* nblocks) {
+  std::vector<RepackSeg> v;
+  int which = 0;
+  auto add = [&](int kind, int scr, int src, int dst, int threads, int p0 = 0, int p1 = 0) {
+    v.push_back(RepackSeg{kind, scr, src, (int)pack_block_offset(which) + dst, p0, p1, threads, 0});
+  };
+  auto w64 = [&](int scr, int src, int dst, int dst3, int ldw, int col0, int nfrag) {      // fp32 form at dst (< 0: none), bf16 x 3 at dst3 (< 0: none)
+    if (dst >= 0) add(RS_W64, scr, src, dst, 4096 * nfrag, ldw, col0);
+    if (dst3 >= 0) add(RS_BF3, scr, src, dst3, 1536 * nfrag, ldw, col0);
+  };
+  typedef RepackScr S;
+  // 0 embed
+  add(RS_COPY, 0, (int)weight_offset(L_INP_F), PackEmbed::W, 192);
+  add(RS_COPY, 0, (int)bias_offset(L_INP_F), PackEmbed::B, 64);
+  which = 1;
+  add(RS_WSMALL, 0, (int)weight_offset(L_FC1), PackPreFwd::W1, 512, 7);
+  add(RS_VEC64, 0, (int)bias_offset(L_FC1), PackPreFwd::B1, 64);
+  w64(1, S::PF_W2, PackPreFwd::W2, PackPreFwd::W23, 64, 0, 1);
+  add(RS_VEC64, 1, S::PF_B2, PackPreFwd::B2, 64);
+  which = 2;
+  add(RS_WSMALL, 0, (int)weight_offset(L_BC1), PackPreBwd::W1, 512, 7);
+  add(RS_VEC64, 0, (int)bias_offset(L_BC1), PackPreBwd::B1, 64);
+  w64(0, (int)weight_offset(L_BC1_1), PackPreBwd::W2, PackPreBwd::W23, 64, 0, 1);
+  add(RS_VEC64, 0, (int)bias_offset(L_BC1_1), PackPreBwd::B2, 64);
+  w64(0, (int)weight_offset(L_BC1_2), PackPreBwd::W3, PackPreBwd::W33, 64, 0, 1);
+  add(RS_VEC64, 0, (int)bias_offset(L_BC1_2), PackPreBwd::B3, 64);
+  w64(0, (int)weight_offset(L_BC2), PackPreBwd::W4, PackPreBwd::W43, 192, 0, 3);
+  add(RS_VEC64, 0, (int)bias_offset(L_BC2), PackPreBwd::B4, 64);
+  w64(1, S::PB_W5, PackPreBwd::W5, PackPreBwd::W53, 64, 0, 1);
+  add(RS_VEC64, 1, S::PB_B5, PackPreBwd::B5, 64);
+  which = 3;
+  add(RS_WSMALL, 0, (int)weight_offset(L_INP_B), PackPreInp::W1, 128, 2);
+  add(RS_VEC64, 0, (int)bias_offset(L_INP_B), PackPreInp::B1, 64);
+  w64(1, S::PI_W2, PackPreInp::W2, PackPreInp::W23, 64, 0, 1);
+  add(RS_VEC64, 1, S::PI_B2, PackPreInp::B2, 64);
+  which = 4;
+  add(RS_TRANS, 0, (int)weight_offset(L_OUT1), PackProp::W1T, 256, 64, 4);
+  add(RS_COPY, 0, (int)bias_offset(L_OUT1), PackProp::B1, 64);
+  add(RS_TRANS, 0, (int)weight_offset(L_OUT2), PackProp::W2T, 4096, 64, 128);
+  add(RS_TRANS, 1, S::PR_W2B, PackProp::W2T + 4096, 4096, 64, 64);
+  add(RS_COPY, 0, (int)bias_offset(L_OUT2), PackProp::B2, 64);
+  add(RS_TRANS, 0, (int)weight_offset(L_OUT3), PackProp::W3T, 4096, 64, 64);
+  add(RS_COPY, 0, (int)bias_offset(L_OUT3), PackProp::B3, 64);
+  add(RS_COPY, 1, S::PR_V2, PackProp::V2, 64);
+  // 5..9 node updates: Wa layer, forward / backward Wcb, the slot of the folded projection (< 0: none)
+  const int upd[5][3] = {{L_FC3, 0, 0}, {L_FC3, 0, 1}, {L_FC3, 0, 2}, {L_BC3, 1, -1}, {L_BC3, 1, 3}};
+  for (int u = 0; u < 5; ++u) {
+    which = 5 + u;
+    const int a = upd[u][0], slot = upd[u][2], up = S::UP + (slot < 0 ? 0 : slot) * S::UP_STRIDE;
+    const int cbw = upd[u][1] ? S::CBB_W : S::CBF_W, cbb = upd[u][1] ? S::CBB_B : S::CBF_B;
+    const int wa_scr = slot >= 0, wa = slot >= 0 ? up + S::UP_WA : (int)weight_offset(a), was = slot >= 0 ? up + S::UP_WAS : S::WASB;
+    add(RS_W64, wa_scr, wa, PackUpd::WA, 8192, 128, 0);
+    w64(1, was, PackUpd::WAS, PackUpd::WAS3, 64, 0, 1);
+    add(RS_VEC64, 0, (int)bias_offset(a), PackUpd::BA, 64);
+    w64(1, cbw, PackUpd::WCB, PackUpd::WCB3, 64, 0, 1);
+    add(RS_VEC64, 1, cbb, PackUpd::BCB, 64);
+    add(RS_COPY, 1, cbb, PackUpd::BCBROW, 64);
+    if (slot >= 0) add(RS_WSMALL, 1, up + S::UP_VAW, PackUpd::VAW, 128, 2);
+    else add(RS_ZERO, 0, 0, PackUpd::VAW, 128);
+    w64(wa_scr, wa, -1, PackUpd::WA1S3, 128, 64, 1);
+  }
+  which = 10;
+  add(RS_WSMALL, 1, S::VC, PackUpdInp::VC, 128, 2);
+  which = 11;
+  w64(1, S::WC, PackPostInp::WPN, PackPostInp::WPN3, 64, 0, 1);
+  add(RS_W64G, 1, S::WC, PackPostInp::WPG, 4096, 64, 0);
+  add(RS_BF3G, 1, S::WC, PackPostInp::WPG3, 1536, 64, 0);
+  for (int q = 0; q < 2; ++q) {
+    which = 12 + q;
+    w64(1, q ? S::SF_W1 : S::SB_W1, PackScore::W1, -1, 64, 0, 1);
+    add(RS_VEC64, 0, (int)bias_offset(L_FNODE), PackScore::B1, 64);
+    add(RS_VEC64, 0, (int)weight_offset(L_FSCORE), PackScore::WS, 64);
+    add(RS_COPY, 0, (int)bias_offset(L_FSCORE), PackScore::BS, 1);
+    add(RS_ZERO, 0, 0, PackScore::BS + 1, 3);
+    add(RS_WSMALL, 1, q ? S::SF_V1 : S::SB_V1, PackScore::V1, 128, 2);
+  }
+  int b = 0;
+  for (RepackSeg& s : v) { s.block0 = b; b += (s.threads + kRepackBlock - 1) / kRepackBlock; }
+  if (nblocks) *nblocks = b;
+  return v;
+}
+// floats segment s writes
+inline int repack_seg_floats(const RepackSeg& s) { return (s.kind == RS_BF3 || s.kind == RS_BF3G) ? 4 * s.threads : s.threads; }
 
 // ---- verified-network (layer graph) descriptors ----
 struct EdgeGeom {      // the plain ints of a linear map between graph layer k-1 and k: what a device-side descriptor copies in one assignment

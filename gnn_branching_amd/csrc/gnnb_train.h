@@ -920,8 +920,29 @@ __global__ void k_tadam(TAdam a) {
   a.p[i] = a.p[i] - a.step_size * (m / denom);
 }
 
+// A small host table into device memory as a kernel argument: the launch captures the words, so the copy is ordered on the stream and
+// nothing of it stays on the host (a step that returns without synchronising may be followed by another that builds new tables).
+#define TPUT_WORDS 896
+struct TPutBlock { unsigned w[TPUT_WORDS]; };
+__global__ void k_tput(TPutBlock v, unsigned* dst, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = v.w[i];
+}
+
 // ---- the tape ----
 struct Trainer {
+  bool ordered = false;                  // the step in flight returns without synchronising: host tables go to the device through k_tput
+  int put(void* dst, const void* src, size_t bytes) {      // dst: device memory with room for bytes rounded up to 4
+    const unsigned char* s = static_cast<const unsigned char*>(src);
+    unsigned* d = static_cast<unsigned*>(dst);
+    for (size_t o = 0; o < bytes; o += sizeof(TPutBlock)) {
+      TPutBlock b;
+      const size_t nb = bytes - o < sizeof(TPutBlock) ? bytes - o : sizeof(TPutBlock);
+      memset(b.w, 0, sizeof b.w);
+      memcpy(b.w, s + o, nb);
+      hipLaunchKernelGGL(k_tput, dim3(1), dim3(256), 0, st, b, d + o / 4, (int)((nb + 3) / 4));
+    }
+    return hipGetLastError() != hipSuccess;
+  }
   DevBuf<float> d_w, d_g, d_m, d_v;      // parameters (blob order), their gradient, Adam's moments
   int step = 0;
   float lr = 1e-4f, wd = 1e-4f;
@@ -999,7 +1020,8 @@ struct Trainer {
   // Several independent chains (the same chain of different ReLU layers) as ONE launch forward and one backward: blockIdx.y =
   // chain, the descriptors uploaded once and read from memory by both launches.  Returns the outputs per chain.
   struct Job { std::vector<Spec> specs; long n; const List* list; };
-  PinnedBuf<TChain> desc;                // pinned, device-visible descriptor slots of the step in flight (every step ends in a sync)
+  PinnedBuf<TChain> desc;                // pinned, device-visible descriptor slots of the step in flight: read by the kernels where the step ends in a
+                                         // sync; an `ordered` step only fills them on the host and its kernels read a device copy (chain_multi)
   int ndesc = 0;
   static constexpr int kDescCap = 8 * T_MAXL;
   std::vector<std::vector<TT>> chain_multi(const std::vector<Job>& jobs) {
@@ -1043,6 +1065,11 @@ struct Trainer {
       outs.push_back(out);
     }
     const TChain* d_cs = slots + base;
+    if (ordered) {                       // the pinned slots are rewritten by the next step: this step's kernels read a device copy
+      TChain* d = reinterpret_cast<TChain*>(arena.alloc((sizeof(TChain) * nj + 3) / 4));
+      if (!d || put(d, slots + base, sizeof(TChain) * nj)) { arena.err = true; return std::vector<std::vector<TT>>(nj, std::vector<TT>(TC_MAXOPS)); }
+      d_cs = d;
+    }
     const int R = maxrows <= 16L * n_cu ? TL_ROWS_TINY : (maxrows <= 128L * n_cu ? TL_ROWS_SMALL : TL_ROWS);
     const dim3 grid((unsigned)((maxrows + R - 1) / R), (unsigned)nj);
     const size_t lds = ((size_t)(Kmax | 1) * 64 + (size_t)R * Kmax + (size_t)R * 64) * 4;
@@ -1080,8 +1107,12 @@ struct Trainer {
     TLin* d_ops = reinterpret_cast<TLin*>(arena.alloc(op_floats));
     int* d_first = reinterpret_cast<int*>(arena.alloc(first_floats));
     if (!d_ops || !d_first) return 1;
-    if (hipMemcpyAsync(d_ops, wops.data(), sizeof(TLin) * nops, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
-    if (hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (nops + 1), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+    if (ordered) {
+      if (put(d_ops, wops.data(), sizeof(TLin) * nops) || put(d_first, h_first.data(), sizeof(int) * (nops + 1))) return 1;
+    } else {
+      if (hipMemcpyAsync(d_ops, wops.data(), sizeof(TLin) * nops, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+      if (hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (nops + 1), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+    }
     hipLaunchKernelGGL(k_tlin_bwd_w_all, dim3((unsigned)h_first[nops], 3), dim3(256), 0, st, d_ops, d_first, nops);
     hipLaunchKernelGGL(k_tlin_reduce_all_wide, dim3((64 * 193 + 255) / 256, (unsigned)L_COUNT), dim3(256), 0, st, d_ops, nops);
     return 0;

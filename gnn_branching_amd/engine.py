@@ -736,7 +736,8 @@ class ScorerEngine:
     def get_weights(self):
         """The GNN parameters as a flat float32 array in checkpoint order (see state_blob)."""
         out = np.empty(GNN_BLOB_FLOATS, dtype=np.float32)
-        _lib.check(self.lib.gnnb_get_weights(self.h, out.ctypes.data_as(C.c_void_p), out.size), "gnnb_get_weights")
+        with torch.cuda.device(self.device):                      # (after a step in repack mode "device" it synchronises and reads the device)
+            _lib.check(self.lib.gnnb_get_weights(self.h, out.ctypes.data_as(C.c_void_p), out.size), "gnnb_get_weights")
         return out
 
     def set_weights(self, blob):
@@ -745,11 +746,53 @@ class ScorerEngine:
             _lib.check(self.lib.gnnb_set_weights(self.h, blob.ctypes.data_as(C.c_void_p), blob.size), "gnnb_set_weights")
         self._blob = blob
 
-    def online_create(self, lr=1e-4, wd=1e-4):
-        """torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd) of graph_score_online.py:15."""
+    REPACK_MODES = {"host": 0, "device": 1}
+
+    @classmethod
+    def _repack_mode(cls, repack, what):
+        if not isinstance(repack, str) or repack not in cls.REPACK_MODES:
+            raise ValueError(f"{what}: repack = {repack!r} ('host' or 'device')")
+        return cls.REPACK_MODES[repack]
+
+    def online_create(self, lr=1e-4, wd=1e-4, repack="host"):
+        """torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd) of graph_score_online.py:15.  repack: where the scorer's operand
+        packs are rebuilt after a step, see ``set_repack``."""
+        mode = self._repack_mode(repack, "online_create")
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gnnb_online_create(self.h, lr, wd), "gnnb_online_create")
         self._online = True
+        self.repack_mode = "host"
+        if mode:
+            self.set_repack(repack)
+
+    def set_repack(self, mode):
+        """gnnb_online_set_repack: "host" (the default) rebuilds the packs on the host after a learning step, which synchronises the
+        stream; "device" builds them on the step's stream -- ``online_step_rows`` and ``imitation_step_rows`` then return without
+        waiting, and a scorer call on ANOTHER stream must be ordered behind the step by the caller (the packs are rewritten in place)."""
+        m = self._repack_mode(mode, "set_repack")
+        if not getattr(self, "_online", False):
+            raise RuntimeError("set_repack: call online_create first")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gnnb_online_set_repack(self.h, m), "gnnb_online_set_repack")
+        self.repack_mode = mode
+
+    def repack(self, stream=None):
+        """gnnb_repack: the device pack builder from the trainer's parameters on ``stream`` (a torch stream; None: the current one).
+        Stream-ordered, no synchronisation."""
+        if not getattr(self, "_online", False):
+            raise RuntimeError("repack: call online_create first")
+        with torch.cuda.device(self.device):
+            st = (torch.cuda.current_stream() if stream is None else stream).cuda_stream
+            _lib.check(self.lib.gnnb_repack(self.h, C.c_void_p(st)), "gnnb_repack")
+
+    def pack_image(self, which):
+        """gnnb_pack_image: operand pack ``which`` (0..13) as it stands in device memory (float32 array), after a device synchronise."""
+        n = C.c_size_t(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gnnb_pack_image(self.h, int(which), None, 0, C.byref(n)), "gnnb_pack_image")      # (the size query)
+            out = np.empty(n.value, dtype=np.float32)
+            _lib.check(self.lib.gnnb_pack_image(self.h, int(which), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), "gnnb_pack_image")
+        return out
 
     def online_step(self, args, kw_index, improvement, apply=True, want_scores=False):
         """graph_score_online.py:62-77 for the batch ``args`` (the argument tuple of GraphNet.forward): kw_index (B) flat
@@ -782,7 +825,8 @@ class ScorerEngine:
         K-row device batch ``batch`` (a ``_lib.Batch`` over device tensors, as ``make_batch`` builds it), with nothing crossing the link.
         kw_index (n,) int32 / improvement (n,) fp32: device tensors; loss: None, or a (n,) fp32 device tensor that receives the losses;
         status: None, or a zeroed (1,) int32 device tensor whose bit 3 (value 8) reports a row that named no undecided node or no row of
-        the batch (that row's loss is NaN, the others are not affected).  Synchronises the stream, as ``online_step`` does."""
+        the batch (that row's loss is NaN, the others are not affected).  Synchronises the stream, as ``online_step`` does, in repack
+        mode "host"; in mode "device" (``set_repack``) a step with apply is only issued: loss and status are valid once the stream gets there."""
         if not getattr(self, "_online", False):
             raise RuntimeError("online_step_rows: call online_create first")
         n, i32, f32 = int(rows.numel()), torch.int32, torch.float32
@@ -802,8 +846,8 @@ class ScorerEngine:
         """gnnb_imitation_step_rows on the current stream: ``online_step_rows`` under the table loss (include/gnnb.h states the rule).
         rows (n,) int32 and table (K, R) fp64 (row = batch row, NaN: not a candidate -- what ``strong_pick`` leaves in ``table``) are
         device tensors; loss (n,) fp32, report (n, 4) int32 [teacher, pick, n_cand, n_viol], regret (n,) fp64 and status (1,) int32
-        (zeroed by the caller; bit 3: a refused row) are None or device tensors that receive them.  Synchronises the stream, as
-        ``online_step_rows`` does."""
+        (zeroed by the caller; bit 3: a refused row) are None or device tensors that receive them.  Synchronises the stream where
+        ``online_step_rows`` does: in repack mode "host", not in mode "device"."""
         if not getattr(self, "_online", False):
             raise RuntimeError("imitation_step_rows: call online_create first")
         margin = self._margin(margin, "imitation_step_rows")
@@ -865,7 +909,8 @@ class ScorerEngine:
     def online_grad(self):
         """d loss / d parameters of the last online_step or imitation step, flat float32 array in checkpoint order."""
         out = np.empty(GNN_BLOB_FLOATS, dtype=np.float32)
-        _lib.check(self.lib.gnnb_online_grad(self.h, out.ctypes.data_as(C.c_void_p), out.size), "gnnb_online_grad")
+        with torch.cuda.device(self.device):                      # (in repack mode "device" it synchronises the device first)
+            _lib.check(self.lib.gnnb_online_grad(self.h, out.ctypes.data_as(C.c_void_p), out.size), "gnnb_online_grad")
         return out
 
     # ---- BaBSR fallback scorer (SURVEY 8(f) N3) -------------------------------------------------

@@ -242,6 +242,16 @@ BRANCHINGS = ("gnn", "babsr", "strong")
 STRONG_CHUNK_DEFAULT = 256          # strong_chunk's default, candidates per bounding chunk: the best of 32..256 measured
 
 
+REPACKS = ("host", "device")
+
+
+def _check_repack(repack):
+    """repack: where the scorer's operand packs are rebuilt after a learning step."""
+    if not isinstance(repack, str) or repack not in REPACKS:
+        raise ValueError(f"repack = {repack!r}: 'host' (the packs are rebuilt on the host, the step waits for the stream) or 'device' "
+                         "(they are built on the stream, the step's status is read with the next round's state record)")
+
+
 def _check_branching(branching, branching_threshold, online_threshold):
     """The branching mode, before a device is touched."""
     if not isinstance(branching, str) or branching not in BRANCHINGS:
@@ -343,11 +353,13 @@ class _Round:
     """What a one-job and a many-job run share: the rows of a round, and the existing batch entry points on them."""
     branching, strong_on, imitate, learning = "gnn", False, None, False      # (what a run is before ``_set_options``: everything off)
     strong_G, cand_src = 0, None    # (section 7.14: the scorer's count of a ``Shortlist`` and the union's sources; off unless a run sets them)
+    repack, pending_step = "host", None      # (section 7.15: "device" where a run asks for it; the step whose status has not been read yet)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
                      online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
-                     imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None):
-        """The options of a run, checked in ONE order -- imitate, branching, strong, witness, restarts, threshold, online -- and stored with
+                     imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None,
+                     repack="host"):
+        """The options of a run, checked in ONE order -- imitate, branching, strong, witness, restarts, threshold, online, repack -- and stored with
         everything derived from them, before anything touches ``choice`` or a device; a constructor passes the keywords it has and the
         others stay off.  Everything behind it (``_engine_of``, ``_buffers``, ``_launch``, the loops) reads the run, never an argument:
         ``strong_on`` (a round computes the table of section 7.11: "strong", an audit, or ``imitate``), ``strong_M`` (BaBSR's count; 0: none) and
@@ -360,6 +372,9 @@ class _Round:
         _check_restarts(pgd_restarts, pgd_seed, pgd_steps)
         _check_threshold(branching_threshold, kwbd_threshold)
         _check_online(online_threshold, branching_threshold, kwbd_threshold, choice)
+        _check_repack(repack)
+        if repack != "host":                                      # (set only where given, as strong_G)
+            self.repack = repack
         self.branching, self.threshold, self.online = branching, branching_threshold, online_threshold
         self.kwbd_threshold = kwbd_threshold if online_threshold is None else KWBD_NEVER
         self.sparsest_layer, self.decision_threshold = sparsest_layer, decision_threshold
@@ -380,6 +395,44 @@ class _Round:
         """The engine of the run: the model's, or for a run that learns (online or by imitation) ``choice._eng()``, the engine with its
         optimizer."""
         return choice._eng() if self.learns else choice.model.engine()
+
+    def _use_repack(self):
+        """Behind ``_engine_of``: a run that learns puts its engine into the run's repack mode.  The engine outlives the run, so every
+        such run sets the mode, "host" included (``close`` puts it back when the run ends)."""
+        if self.learns:
+            self.eng.set_repack(self.repack)
+
+    def close(self):
+        """The end of a run for whoever drives a run class directly (``branch_and_bound_frontier`` and the ``verify_properties*`` call it):
+        the engine, which outlives the run, goes back to repack mode "host"."""
+        if self.learns and self.repack != "host":
+            self.eng.set_repack("host")
+
+    def _step_issued(self, keep=()):
+        """Behind a learning step in "device" mode: the step was only issued.  Its status word, and what the trace shows of it, are read
+        with the NEXT round's state record or at the end of the run (``_settle_step``).  keep: names of device tensors the next launch
+        overwrites before that read; the trace then reads copies made here, on the stream."""
+        if self.repack == "device":
+            self.pending_step = {"round": self.round, "fill": [], "kept": {name: getattr(self, name).clone() for name in keep}}
+
+    def _settle_step(self):
+        """The deferred half of a "device"-mode learning step, behind a read that has already waited for the stream: the step's status
+        word (bit 3 raises, naming the round that learnt) and the trace entries of that round."""
+        p, self.pending_step = self.pending_step, None
+        if p is None:
+            return
+        if int(self.step_status.cpu()[0]) & 8:
+            raise RuntimeError(f"{self._refusal()} -- in the learning step of round {p['round']}")
+        for fill in p["fill"]:
+            fill(p["kept"])
+
+    def _refusal(self):
+        """What status bit 3 of the run's learning step means: the imitation step's text, or the online step's (``FrontierRun._raise_for``
+        words the same refusal for a run that reads it at its end)."""
+        if self.imitate is None:
+            return "gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask"
+        return ("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
+                "row's mask, or holds an infinite improvement")
 
     def _witness_buffers(self, segments):
         """Per segment the incumbent's value (+inf: none yet; the record's global_ub after every commit) and its point."""
@@ -654,12 +707,12 @@ class _Round:
         self._choose(n, M)
 
     def check_status(self):
+        self._settle_step()
         self._raise_for(int(self.status_all.cpu()[0]))
 
     def _raise_for(self, st):
         if st & 8 and self.imitate is not None:
-            raise RuntimeError("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
-                               "row's mask, or holds an infinite improvement")
+            raise RuntimeError(_Round._refusal(self))
         from .engine import _raise_for_status
         _raise_for_status(st)
 
@@ -679,6 +732,7 @@ class _Round:
                                      report=self.im_report[:k], regret=self.im_regret[:k], status=self.step_status)
         self.status_all |= self.step_status
         self.imitation_steps, self.imitation_rows = self.imitation_steps + 1, self.imitation_rows + k
+        self._step_issued()
 
 
 class FrontierRun(_Round):
@@ -699,13 +753,13 @@ class FrontierRun(_Round):
 
     def __init__(self, lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, decision_bound=None, capacity=None, branching_threshold=None,
                  kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, online_threshold=None, max_rounds=0, witness=None,
-                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT,
-                 strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
+                 pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, repack="host", imitate=None,
+                 imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
         self.capacity = _check_args(K, n_iter, lr, eps, max_rounds, capacity)       # (max_rounds: the loop's, checked here with the rest)
         self._set_options(choice, branching=branching, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold, sparsest_layer=sparsest_layer,
                           decision_threshold=decision_threshold, online_threshold=online_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step,
                           pgd_restarts=pgd_restarts, pgd_seed=pgd_seed, imitate=imitate, imitate_margin=imitate_margin,
-                          strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit)
+                          strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit, repack=repack)
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
@@ -740,6 +794,7 @@ class FrontierRun(_Round):
             self.learn_imp, self.loss = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float32, device=dev)
             self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
         self._imitation_buffers(K)
+        self._use_repack()                                        # last: nothing behind it can fail and leave the engine in the run's mode
 
     def _commit(self, slots):
         self.eng.frontier_commit(self.pool, slots, *self.Ch.children(), self.pool.state, eps=self.eps, decision_bound=self.decision_bound,
@@ -821,6 +876,7 @@ class FrontierRun(_Round):
                                   status=self.step_status)
         self.status_all |= self.step_status
         self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
+        self._step_issued(("learn_rows", "learn_kw", "learn_imp"))
 
     def read_learn(self):
         """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
@@ -840,6 +896,7 @@ class FrontierRun(_Round):
         An online round with m > 0 then reads n_learn and takes its learning step (``_learn``); a learning round of ``imitate`` takes its
         step (``_imitate``)."""
         st = self.pool.state.cpu().tolist()
+        self._settle_step()                                       # ("device" mode: the previous round's step, read behind this record)
         if self.learn_pending:
             self._learn()
         self._step_behind_read()
@@ -849,8 +906,8 @@ class FrontierRun(_Round):
 def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, decision_bound=None, capacity=None, log=print,
                               trace=None, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001, stats=None,
                               online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0,
-                              imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None, strong_chunk=STRONG_CHUNK_DEFAULT,
-                              strong_audit=None, branching="gnn"):
+                              repack="host", imitate=None, imitate_margin=IMITATE_MARGIN_DEFAULT, strong_candidates=None,
+                              strong_chunk=STRONG_CHUNK_DEFAULT, strong_audit=None, branching="gnn"):
     """Branch and bound with the open domains in device memory, K of them expanded per round.
 
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
@@ -961,10 +1018,17 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     whose model is a GraphNet and is refused with "babsr".  No read is added.  Audit dicts of such a run also hold "sources" (per candidate
     1: BaBSR's shortlist only, 2: the GNN's only, 3: both) and a traced strong round "strong_sources".
 
+    repack (it matters to a run that learns, with ``online_threshold`` or ``imitate``): "host" (default) rebuilds
+    the scorer's operand packs on the host after every learning step, which waits for the stream.  "device" builds them on the stream:
+    the step is only issued, and a learning round adds no host wait of its own.  Its status word, and the loss, report and regret a traced
+    round shows, are then read with the NEXT round's state record, or at the end of the run for the last round; the RuntimeError for
+    status bit 3 is raised at that read and names the round that learnt.  Decisions, bounds, losses and parameters are those of "host"
+    wherever the two builders' packs give the same scores (a folded pack entry may differ by one fp32 unit in the last place).
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
-                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, imitate, imitate_margin,
-                      strong_candidates, strong_chunk, strong_audit, branching)      # (checks every argument before it touches a device)
+                      decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, repack, imitate,
+                      imitate_margin, strong_candidates, strong_chunk, strong_audit, branching)      # (checks every argument before it touches a device)
     run.keep_pairs = trace is not None
     try:
         out = _one_job_loop(run, max_rounds, log, trace, stats)
@@ -974,6 +1038,7 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     finally:
         if run.online_steps or run.imitation_steps:               # the nn.Module mirrors the device, as GraphChoice.online_learning leaves it
             choice.model.load_blob(run.eng.get_weights())
+        run.close()
 
 
 def _one_job_loop(run, max_rounds, log, trace, stats):
@@ -995,7 +1060,7 @@ def _one_job_loop(run, max_rounds, log, trace, stats):
         st = run.read_state()
         if t is not None:
             if run.online is not None:
-                t.update(_online_trace(run, st))
+                t.update(_online_trace(run, st, t))
             _report_read(run, t, 0, 0, k, st, _witness_values(run))
         _check_record(st)
         _tally_entry(run, tally, 0, k, st)
@@ -1051,8 +1116,16 @@ def _report_read(run, t, seg, row0, k, st, values):
     a, b = row0, row0 + k
     if run.imitate is not None:
         if run.last_imitation:
-            t.update(imitation_loss=run.im_loss[a:b].cpu().tolist(), imitation_regret=run.im_regret[a:b].cpu().tolist(),
-                     imitation_report=run.im_report[a:b].cpu().tolist())
+            def fill(kept=None):
+                t.update(imitation_loss=run.im_loss[a:b].cpu().tolist(), imitation_regret=run.im_regret[a:b].cpu().tolist(),
+                         imitation_report=run.im_report[a:b].cpu().tolist())
+            # repack "device": with the next round's state record.  (getattr: tests/test_frontier_cpu.py reports through a stand-in run
+            # that is no _Round and holds only what the report read before this option)
+            pending = getattr(run, "pending_step", None)
+            if pending is not None:
+                pending["fill"].append(fill)
+            else:
+                fill()
         t.update(global_lb=_global_lb(st), global_ub=st[_lib.FS_GLOBAL_UB])
     if run.witness_on:
         t.update(global_ub=st[_lib.FS_GLOBAL_UB], witness_value=values[seg])
@@ -1112,13 +1185,23 @@ def _strong_rows(run, k, row0=0):
     return rows
 
 
-def _online_trace(run, st):
+def _online_trace(run, st, t=None):
     """The online mode's part of a round's trace, behind ``read_state`` (device-to-host copies): the learn rows of the round just read, the
-    flat indices of their KW nodes, improve and the loss of each row in the step; the bounds of the record ``st``."""
+    flat indices of their KW nodes, improve and the loss of each row in the step; the bounds of the record ``st``.  Behind a step that was
+    only issued (repack "device") the step's four keys go into the round's dict ``t`` with the next round's state record, from the
+    copies ``_step_issued`` kept (the next launch overwrites the learn rows)."""
     n = run.last_learn if run.m else 0
-    return {"global_lb": _global_lb(st), "global_ub": st[_lib.FS_GLOBAL_UB],
-            "learn_rows": run.learn_rows[:n].cpu().tolist(), "learn_kw": run.learn_kw[:n].cpu().tolist(),
-            "learn_improve": run.learn_imp[:n].cpu().tolist(), "loss": run.loss[:n].cpu().tolist()}
+    out = {"global_lb": _global_lb(st), "global_ub": st[_lib.FS_GLOBAL_UB]}
+
+    def step_part(kept):
+        return {"learn_rows": kept["learn_rows"][:n].cpu().tolist(), "learn_kw": kept["learn_kw"][:n].cpu().tolist(),
+                "learn_improve": kept["learn_imp"][:n].cpu().tolist(), "loss": run.loss[:n].cpu().tolist()}
+    pending = getattr(run, "pending_step", None)                  # (as in _report_read)
+    if pending is not None and n and t is not None:
+        pending["fill"].append(lambda kept: t.update(step_part(kept)))
+    else:
+        out.update(step_part({"learn_rows": run.learn_rows, "learn_kw": run.learn_kw, "learn_imp": run.learn_imp}))
+    return out
 
 
 def _threshold_trace(run, k, e=0, row0=0):
@@ -1275,6 +1358,7 @@ class JobsRun(_Round):
         self.K, self.S, self.cap, self.n_iter, self.lr, self.eps = K, segments, cap, n_iter, float(lr), float(eps)
         self.fixed = list(fixed_layers)
         eng = self.eng = self._engine_of(choice)
+        self._use_repack()
         eng.bind(self.fixed, in_shape)
         dev, self.lib, self.ng = eng.device, eng.lib, len(eng.sizes)
         f64, f32, i32 = torch.float64, torch.float32, torch.int32
@@ -1488,6 +1572,7 @@ class StrongJobsRun(JobsRun):
     def read_state(self):
         """``JobsRun.read_state``; a learning round then takes its step (``_imitate``), behind the records."""
         st = super().read_state()
+        self._settle_step()                                       # ("device" mode: the previous round's step, read behind these records)
         self._step_behind_read()
         return st
 
@@ -1627,6 +1712,7 @@ def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=
     finally:
         if run.imitation_steps:                                   # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it
             choice.model.load_blob(run.eng.get_weights())
+        run.close()
 
 
 def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):

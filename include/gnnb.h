@@ -678,6 +678,38 @@ int gnnb_set_weights(gnnb_t* h, const float* w_blob, size_t n_floats);
  * moments start at zero).  Calling it again resets the optimizer state. */
 int gnnb_online_create(gnnb_t* h, float lr, float weight_decay);
 
+/* ---- where the scorer's operand packs are rebuilt after a learning step ----
+ * gnnb_online_set_repack: mode 0 (the default; gnnb_online_create resets to it) is the host builder: a step with apply = 1 copies the
+ * parameters to the host, synchronises, folds and permutes them into the 14 packs there and copies the packs back.  Mode 1 is the device
+ * builder: two launches on the step's stream (k_repack_fold, k_repack_emit) read the trainer's parameters and rewrite the packs in
+ * place; no parameter and no pack crosses the link.  The two builders run the same sums (fp64 accumulator, k ascending, rounded to
+ * fp32 at the same points); every copied or permuted value is bit-identical, a folded entry may differ by one fp32 unit in the last
+ * place.  Switching to mode 1 rebuilds the packs from the trainer's parameters at once (back to 0: with the host builder), so a handle's
+ * packs always come from its mode's builder; both switches synchronise the device.  GNNB_E_INVALID for a null handle or a mode other than
+ * 0 and 1, GNNB_E_STATE before gnnb_online_create.
+ * In mode 1:
+ *   - gnnb_online_step_rows and gnnb_imitation_step_rows with apply = 1 end with the Adam step followed by the pack rebuild on `stream`
+ *     and return WITHOUT synchronising: loss, report_i, regret and status are device arrays, valid once `stream` reaches that point.  A
+ *     second step may be issued on the same stream at once; the step keeps nothing on the host that the next would overwrite.
+ *   - gnnb_online_step still synchronises `stream` (its loss is a host array) but moves no parameters or packs over the link.
+ *   - gnnb_set_weights copies the blob to the trainer and runs the device builder; gnnb_get_weights synchronises the device and reads the
+ *     parameters back from the trainer (the handle's host copy is stale after a step).
+ * Ordering rule: the packs are rewritten IN PLACE on `stream`.  A gnnb_forward (or any other scorer call) of the same handle on another
+ * stream must be ordered behind the step by the caller (an event, or a synchronise); on the same stream the order is the stream's.
+ * gnnb_repack: the device builder alone, from the trainer's parameters, on `stream`; stream-ordered, allocates nothing, does not
+ * synchronise.  GNNB_E_STATE before gnnb_online_create.
+ * gnnb_pack_image: inspection.  Pack `which` (0..13: embed, pre_fwd, pre_bwd, pre_inp, prop, upd_fwd_e, upd_fwd_i, upd_fwd_f, upd_bwd,
+ * upd_bwd_b, upd_inp, post_inp, score_b, score_f) as it stands in device memory, after a device synchronise, into host_buf (cap floats);
+ * *n_floats (may be NULL) receives the pack's size whenever `which` is valid; a null host_buf with cap = 0 and a non-null n_floats is a
+ * size query and succeeds without touching the device.  GNNB_E_INVALID for a null handle, any other null buffer, `which` outside 0..13,
+ * or cap below the size. */
+int gnnb_online_set_repack(gnnb_t* h, int mode);
+int gnnb_repack(gnnb_t* h, void* stream);
+int gnnb_pack_image(const gnnb_t* h, int which, float* host_buf, size_t cap, size_t* n_floats);
+/* Inspection: fills the handle's pack block with NaNs (every byte 0xff), device-synchronising -- so that a test of a pack builder shows
+ * that it writes every float.  The scorer is unusable until the packs are rebuilt (gnnb_set_weights, gnnb_repack). */
+int gnnb_debug_poison_packs(gnnb_t* h);
+
 /* GraphChoice.online_learning (graph_score_online.py:62-77) for B subproblems (the reference: B = 1; B > 1 sums the B
  * losses):  loss_b = max_j scores_b[j] - scores_b[kw_b] + improvement_b;  backward through GraphNet.forward;  one Adam step;
  * the scorer (gnnb_forward) uses the new parameters from the next call on.
@@ -702,8 +734,9 @@ int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const int32_t* kw_i
  * A device-fed index is checked on the device: a kw_index outside [0, R) or naming a node whose mask entry is 0, and a rows entry outside
  * [0, K), give that row loss = NaN and no gradient and set status bit 3 (value 8); nothing is read out of bounds and the other rows are not
  * affected (a rows entry that names no row is skipped: its sample runs on row 0's inputs under an empty mask).  GNNB_E_INVALID for n < 1 or n > K, a null handle or argument and gnnb_online_step's limits (taps, 8 ReLU layers, a
- * zero-tap network); GNNB_E_STATE before gnnb_bind_network or gnnb_online_create.  Synchronises `stream` before returning, where
- * gnnb_online_step does (the scorer's packs are rebuilt on the host from the new parameters): inside a frontier run a learning round is
+ * zero-tap network); GNNB_E_STATE before gnnb_bind_network or gnnb_online_create.  In repack mode 0 (the default) it synchronises `stream`
+ * before returning, where gnnb_online_step does (the scorer's packs are rebuilt on the host from the new parameters); in mode 1 with
+ * apply = 1 it does not synchronise (gnnb_online_set_repack above).  Inside a frontier run a learning round is
  * rare by construction -- a GNN node has to lose online_threshold times first -- and every other round stays free of it. */
 int gnnb_online_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, const int32_t* kw_index, const float* improvement,
                           float* loss, int32_t* status, int apply, void* stream);
@@ -736,7 +769,8 @@ int gnnb_imitation_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32
 int gnnb_imitation_loss(gnnb_t* h, const float* scores, const float* mask, const double* table, int n, double margin, float* loss, float* ds,
                         int32_t* report_i, double* regret, int32_t* status, void* stream);
 
-/* d loss / d parameters of the last gnnb_online_step, gnnb_online_step_rows or gnnb_imitation_step_rows (before weight decay), HOST, blob order. */
+/* d loss / d parameters of the last gnnb_online_step, gnnb_online_step_rows or gnnb_imitation_step_rows (before weight decay), HOST, blob order.
+ * In repack mode 1, where a step may only have been issued, it synchronises the device first. */
 int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats);
 
 const char* gnnb_last_error(void);
