@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -29,6 +29,9 @@ the M undecided nodes of highest BaBSR score as candidates (without it every und
 --frontier K --imitate N (with the GNN or --branching strong) makes every N-th round a learning round: its parents'
 strong-branching table stays on the device and the GNN takes one Adam step towards ranking the table's best candidate first, by
 --imitate-margin M times the difference of the improvements.
+--imitate N --replay C keeps the labelled states: a learning round stores its parents and their table rows in a
+device-resident replay buffer of C slots and takes --replay-steps steps (default 1; 0 collects only, with a frozen GNN), each on
+--replay-batch entries (default 8) drawn from everything stored so far.
 --props N with --branching strong, or with --imitate N, runs both for every property in one pool (frontier.verify_properties_strong,
 DESIGN.md section 7.13): the candidates of all properties' parents are bounded in the same chunks, and a learning round -- every N-th round
 the run launches -- takes ONE step over the parents of all the properties in flight, which share the GNN.
@@ -72,6 +75,9 @@ def main():
     ap.add_argument("--gnn-candidates", type=int, default=None, metavar="G", help="with --branching strong or --imitate N: also bound the G undecided nodes of highest GNN score")
     ap.add_argument("--imitate", type=int, default=None, metavar="N", help="with --frontier K: every N-th round learns the GNN from its strong-branching table")
     ap.add_argument("--imitate-margin", type=float, default=None, metavar="M", help="with --imitate N: the margin per unit of improvement (default 1.0)")
+    ap.add_argument("--replay", type=int, default=None, metavar="C", help="with --imitate N: learn from a device-resident replay buffer of C labelled states")
+    ap.add_argument("--replay-batch", type=int, default=None, metavar="B", help="with --replay C: entries per step (default 8, 256 at most)")
+    ap.add_argument("--replay-steps", type=int, default=None, metavar="S", help="with --replay C: steps per learning round (default 1; 0: collect only)")
     ap.add_argument("--repack", default=None, choices=("host", "device"),
                     help="with --frontier K and --online N or --imitate N, one property: where the scorer's packs are rebuilt after a learning step "
                          "(device: on the stream, the step does not wait; DESIGN.md section 7.15)")
@@ -81,6 +87,19 @@ def main():
         ap.error("--imitate N needs --frontier K and N >= 1, and takes no --branching babsr, --threshold or --online")
     if args.imitate_margin is not None and (args.imitate is None or not args.imitate_margin >= 0):
         ap.error("--imitate-margin M needs --imitate N, and M >= 0")
+    if args.replay is not None and (args.imitate is None or not 1 <= args.replay <= 65536):
+        ap.error("--replay C needs --imitate N, and 1 <= C <= 65536")
+    if (args.replay_batch is not None or args.replay_steps is not None) and args.replay is None:
+        ap.error("--replay-batch and --replay-steps need --replay C")
+    if args.replay_batch is not None and not 1 <= args.replay_batch <= min(256, args.replay):
+        ap.error("--replay-batch B: 1 <= B <= min(256, C)")
+    if args.replay_steps is not None and args.replay_steps < 0:
+        ap.error("--replay-steps S: S >= 0")
+    imitate = args.imitate
+    if args.replay is not None:                                  # the value of imitate that keeps the labelled states
+        from gnn_branching_amd.frontier import Replay
+        imitate = Replay(every=args.imitate, capacity=args.replay, batch=min(args.replay, 8) if args.replay_batch is None else args.replay_batch,
+                         steps=1 if args.replay_steps is None else args.replay_steps)
     if args.repack is not None and (args.frontier is None or args.props is not None or (args.online is None and args.imitate is None)):
         ap.error("--repack needs --frontier K with --online N or --imitate N, and one property (no --props)")
     if args.branching is not None and args.frontier is None:
@@ -138,7 +157,7 @@ def main():
         if branching == "strong" or args.imitate is not None:
             margin = {} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}
             results = verify_properties_strong(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
-                                               stats=stats, learned=learned, imitate=args.imitate, strong_candidates=candidates, branching=branching,
+                                               stats=stats, learned=learned, imitate=imitate, strong_candidates=candidates, branching=branching,
                                                **margin)
         elif branching == "babsr":
             results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
@@ -158,6 +177,8 @@ def main():
             print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
         if args.imitate is not None:
             print(f"{learned['imitation_steps']} imitation steps over {learned['imitation_rows']} parent rows in {learned['rounds']} rounds of the pool")
+            if args.replay is not None:
+                print(f"replay buffer: {learned['replay_stored']} states stored, {learned['replay_skipped']} skipped, {learned['replay_filled']} held")
         return
     layers = nets.load_verified_net(args.net, 3, 5)
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
@@ -170,7 +191,7 @@ def main():
         choice = (OnlineGraphChoice if learns else GraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         stats = {}
         if args.imitate is not None:
-            upper.update(imitate=args.imitate, **({} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}))
+            upper.update(imitate=imitate, **({} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}))
         if args.repack is not None:
             upper.update(repack=args.repack)
         glb, gub, rounds, bounded, reason = branch_and_bound_frontier(lp, choice, layers, K=args.frontier, decision_bound=0.0,
@@ -183,6 +204,8 @@ def main():
             kw += f"; {stats['online_steps']} learning steps over {stats['online_rows']} learn rows"
         if args.imitate is not None:
             kw += f"; {stats['imitation_steps']} imitation steps over {stats['imitation_rows']} parent rows"
+            if args.replay is not None:
+                kw += f" drawn from a replay buffer ({stats['replay_stored']} states stored, {stats['replay_skipped']} skipped, {stats['replay_filled']} held)"
         if args.witness:
             kw += witness_of(upper["witness"][0], layers[:-1], layers[-1])
         by = "" if args.branching is None else f"{stats['branches']} branches by {branching}, "

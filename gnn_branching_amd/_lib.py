@@ -13,7 +13,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("GNNB_LIB", os.path.join(CSRC, "libgnnb.so"))     # GNNB_LIB: dev override (ablation builds)
-SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_kw.h", "gnnb_k_dual.h", "gnnb_k_net.h", "gnnb_k_frontier.h", "gnnb_k_starts.h", "gnnb_k_strong.h", "gnnb_k_repack.h"]
+SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_kw.h", "gnnb_k_dual.h", "gnnb_k_net.h", "gnnb_k_frontier.h", "gnnb_k_starts.h", "gnnb_k_strong.h", "gnnb_k_repack.h", "gnnb_k_replay.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread"]
 
 GNNB_CONV, GNNB_LINEAR, GNNB_RELU, GNNB_FLATTEN = 0, 1, 2, 3
@@ -165,6 +165,10 @@ SYMBOLS = [
     ("gnnb_pack_image", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gnnb_debug_poison_packs", C.c_int, [C.c_void_p]),
     ("gnnb_imitation_loss", C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p]),
+    ("gnnb_replay_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_replay_push", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Batch), C.c_int] + [C.c_void_p] * 3 +
+     [C.c_void_p]),
+    ("gnnb_replay_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("gnnb_online_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("gnnb_last_error", C.c_char_p, []),
     ("gnnb_abi_version", C.c_int, []),

@@ -67,6 +67,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_starts.h"
 #include "gnnb_k_strong.h"
 #include "gnnb_k_repack.h"
+#include "gnnb_k_replay.h"
 
 #define N_PACKS 14   // == PK_COUNT
 enum { PK_EMBED, PK_PRE_FWD, PK_PRE_BWD, PK_PRE_INP, PK_PROP, PK_UPD_FWD_E, PK_UPD_FWD_I, PK_UPD_FWD_F, PK_UPD_BWD, PK_UPD_BWD_B,
@@ -229,6 +230,7 @@ struct gnnb_handle : BoundNet {
   DevBuf<float> repack_scr;
   DevBuf<RepackSeg> repack_segs;
   int repack_nseg = 0, repack_nblocks = 0;
+  DevBuf<int> replay_slot;      // gnnb_replay_push: the ring slot of every listed row (k_replay_rank writes it, k_replay_store reads it)
   DevBuf<float> d_zero;         // 64 zero floats: where masked gather loads point
   // List counters of a forward (64 ints) live HERE, not in the caller's workspace: a control block per workspace address (CTL_SLOTS
   // of them, least recently used replaced), zero whenever no forward is running on it -- the last workgroup of k_score, the last
@@ -2923,43 +2925,93 @@ extern "C" int gnnb_online_step(gnnb_t* h, const gnnb_batch* in, int B, const in
   return GNNB_OK;
 }
 
+// ---- THE list of the tensors a learning step reads of a batch on the bound network ----
+// In this order: lb[k], ub[k] of every graph layer; per ReLU layer dual[k - 1] and the two primals on either side of it; the last primal;
+// x_lp, prop_w, prop_b; the mask.  w: floats per row.  step_rows_device gathers exactly these rows, gnnb_replay_push stores exactly
+// these rows and gnnb_replay_bytes adds up exactly these widths, so the three cannot drift apart.
+enum { ST_LB, ST_UB, ST_DUAL, ST_PRIMAL, ST_XLP, ST_PROPW, ST_PROPB, ST_MASK };
+struct StepTensor { int group, k; long w; };
+static std::vector<StepTensor> step_tensors(const gnnb_t* h, int n_primal) {
+  const int NG = (int)h->N.size(), L = NG - 2;
+  std::vector<StepTensor> out;
+  for (int k = 0; k < NG; ++k) { out.push_back({ST_LB, k, h->N[k]}); out.push_back({ST_UB, k, h->N[k]}); }
+  std::vector<char> done(n_primal, 0);
+  for (int k = 1; k <= L; ++k) {
+    out.push_back({ST_DUAL, k - 1, 3L * h->N[k]});
+    for (int q : {h->relu_q[k] - 1, h->relu_q[k]})
+      if (!done[q]) { out.push_back({ST_PRIMAL, q, h->N[k]}); done[q] = 1; }
+  }
+  if (!done[n_primal - 1]) out.push_back({ST_PRIMAL, n_primal - 1, 1});
+  out.push_back({ST_XLP, 0, h->N[0]});
+  out.push_back({ST_PROPW, 0, h->N[L]});
+  out.push_back({ST_PROPB, 0, 1});
+  out.push_back({ST_MASK, 0, h->R});
+  return out;
+}
+static const float* step_tensor(const gnnb_batch& b, const StepTensor& e) {
+  switch (e.group) {
+    case ST_LB: return b.lb[e.k];
+    case ST_UB: return b.ub[e.k];
+    case ST_DUAL: return b.dual[e.k];
+    case ST_PRIMAL: return b.primal[e.k];
+    case ST_XLP: return b.x_lp;
+    case ST_PROPW: return b.prop_w;
+    case ST_PROPB: return b.prop_b;
+    default: return b.mask;
+  }
+}
+// A batch whose pointer tables are its own copies, so that entries can be pointed elsewhere (`b` is the batch to hand on).
+struct BatchView {
+  std::vector<const float*> lb, ub, dual, primal;
+  gnnb_batch b;
+  explicit BatchView(const gnnb_batch& in)
+      : lb(in.lb, in.lb + in.n_graph), ub(in.ub, in.ub + in.n_graph), dual(in.dual, in.dual + in.n_relu), primal(in.primal, in.primal + in.n_primal), b(in) {
+    b.lb = lb.data(); b.ub = ub.data(); b.dual = dual.data(); b.primal = primal.data();
+  }
+  BatchView(const BatchView&) = delete;
+  void set(const StepTensor& e, const float* p) {
+    switch (e.group) {
+      case ST_LB: lb[e.k] = p; break;
+      case ST_UB: ub[e.k] = p; break;
+      case ST_DUAL: dual[e.k] = p; break;
+      case ST_PRIMAL: primal[e.k] = p; break;
+      case ST_XLP: b.x_lp = p; break;
+      case ST_PROPW: b.prop_w = p; break;
+      case ST_PROPB: b.prop_b = p; break;
+      default: b.mask = p; break;
+    }
+  }
+};
+
 // The body gnnb_online_step_rows and gnnb_imitation_step_rows share behind their checks: the gather, then online_step_device under `lf`.
 // lf.table is the (K, R) table of the SOURCE batch: its listed rows are gathered with the other tensors (a fp64 row is 2 R floats to
 // k_trows_gather), and the step reads the gathered copy.
 static int step_rows_device(gnnb_t* h, const gnnb_batch* in, int K, const int32_t* rows, int n, StepLoss lf, float* loss, int32_t* status, int apply,
                             void* stream, const char* who) {
   using namespace gnnb_train;
-  const int NG = (int)h->N.size(), L = NG - 2, R = h->R;
+  const int R = h->R;
   Trainer& t = *h->trainer;
   hipStream_t st = (hipStream_t)stream;
   if (t.arena.reset(st)) return fail(GNNB_E_HIP, "%s: arena reset failed", who);
   TGather g{};
   g.K = K; g.rows = rows; g.status = status;
-  auto dense = [&](const float* src, long w) -> const float* {          // the n listed rows of a (K, w) tensor
-    float* d = t.arena.alloc((size_t)n * w);
-    g.t[g.nt++] = TGatherT{src, d, (int)w};
-    return d;
-  };
-  std::vector<const float*> lb(NG), ub(NG), dual(L), primal(in->primal, in->primal + in->n_primal);      // (entries the step does not read stay)
-  for (int k = 0; k < NG; ++k) { lb[k] = dense(in->lb[k], h->N[k]); ub[k] = dense(in->ub[k], h->N[k]); }
-  std::vector<char> done(in->n_primal, 0);
-  for (int k = 1; k <= L; ++k) {
-    dual[k - 1] = dense(in->dual[k - 1], 3L * h->N[k]);
-    for (int q : {h->relu_q[k] - 1, h->relu_q[k]})
-      if (!done[q]) { primal[q] = dense(in->primal[q], h->N[k]); done[q] = 1; }
+  BatchView dn(*in);                                                    // (entries the step does not read stay)
+  for (const StepTensor& e : step_tensors(h, in->n_primal)) {           // the n listed rows of every (K, w) tensor the step reads
+    float* d = t.arena.alloc((size_t)n * e.w);
+    if (e.group == ST_MASK) g.mask_t = g.nt;
+    g.t[g.nt++] = TGatherT{step_tensor(*in, e), d, (int)e.w};
+    dn.set(e, d);
   }
-  if (!done[in->n_primal - 1]) primal[in->n_primal - 1] = dense(in->primal[in->n_primal - 1], 1);
-  gnnb_batch dn = *in;
-  dn.lb = lb.data(); dn.ub = ub.data(); dn.dual = dual.data(); dn.primal = primal.data();
-  dn.x_lp = dense(in->x_lp, h->N[0]); dn.prop_w = dense(in->prop_w, h->N[L]); dn.prop_b = dense(in->prop_b, 1);
-  g.mask_t = g.nt;
-  dn.mask = dense(in->mask, R);
-  if (lf.table) lf.table = reinterpret_cast<const double*>(dense(reinterpret_cast<const float*>(lf.table), 2L * R));
+  if (lf.table) {
+    float* d = t.arena.alloc((size_t)n * 2 * R);
+    g.t[g.nt++] = TGatherT{reinterpret_cast<const float*>(lf.table), d, 2 * R};
+    lf.table = reinterpret_cast<const double*>(d);
+  }
   if (t.arena.err) return fail(GNNB_E_NOMEM, "%s: out of device memory", who);
   Launcher run{h, st};
   run.run(PC_TROWS_GATHER, [&] { hipLaunchKernelGGL(k_trows_gather, dim3(n, TG_SPLIT), dim3(TG_THREADS), 0, st, g); });
   if (run.rc) return run.rc;
-  return online_step_device(h, &dn, n, lf, nullptr, loss, nullptr, status, apply, st, true, who);
+  return online_step_device(h, &dn.b, n, lf, nullptr, loss, nullptr, status, apply, st, true, who);
 }
 
 // gnnb_online_step on the rows rows[0..n) of the K-row device batch `in`, in list order, nothing crossing the link: k_trows_gather copies
@@ -3009,6 +3061,63 @@ extern "C" int gnnb_imitation_loss(gnnb_t* h, const float* scores, const float* 
   hipStream_t st = (hipStream_t)stream;
   gnnb_train::TLossTable la{scores, mask, table, ds, loss, report_i, regret, status, h->R, margin};
   hipLaunchKernelGGL(gnnb_train::k_tloss_table, dim3(n), dim3(256), 0, st, la);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GNNB_E_HIP, "%s: the launch failed: %s", who, hipGetErrorString(e));
+  return GNNB_OK;
+}
+
+// ---- the replay buffer (gnnb_k_replay.h) ----
+// What gnnb_replay_push, gnnb_replay_sample and gnnb_replay_bytes share: the capacity's range.
+static int refuse_capacity(int C, const char* who) {
+  if (C < 1 || C > RP_MAX_CAPACITY) return fail(GNNB_E_INVALID, "%s: C = %d slots (1 <= C <= %d)", who, C, RP_MAX_CAPACITY);
+  return GNNB_OK;
+}
+
+extern "C" size_t gnnb_replay_bytes(const gnnb_t* h, int C) {
+  if (!h || !h->bound || C < 1 || C > RP_MAX_CAPACITY) return 0;
+  size_t floats = 2 * (size_t)h->R;                                     // the table's fp64 row
+  for (const StepTensor& e : step_tensors(h, h->n_fixed + 1)) floats += (size_t)e.w;
+  return (size_t)C * floats * sizeof(float);
+}
+
+extern "C" int gnnb_replay_push(gnnb_t* h, const gnnb_batch* src, int K, const double* src_table, const int32_t* rows, int n, const gnnb_batch* dst,
+                                int C, double* dst_table, int32_t* state, int32_t* status, void* stream) {
+  const char* who = "gnnb_replay_push";
+  if (int rc = refuse_capacity(C, who)) return rc;
+  if (K < 1 || n < 1 || n > K || n > C)
+    return fail(GNNB_E_INVALID, "%s: n = %d rows of a batch of K = %d into C = %d slots (1 <= n <= K, n <= C)", who, n, K, C);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!src || !src_table || !rows || !dst || !dst_table || !state) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  if (!h->bound) return fail(GNNB_E_STATE, "%s: call gnnb_bind_network first", who);
+  if (int rc = refuse_batch(h, src, K, kNeedsOnline, who)) return rc;
+  if (int rc = refuse_batch(h, dst, C, kNeedsOnline, who)) return rc;
+  if (src->n_primal != dst->n_primal)
+    return fail(GNNB_E_INVALID, "%s: the source batch has %d primal tensors, the buffer %d", who, src->n_primal, dst->n_primal);
+  const int L = (int)h->N.size() - 2, R = h->R;
+  if (L > T_MAXL) return fail(GNNB_E_INVALID, "%s: more than %d ReLU layers", who, T_MAXL);
+  hipStream_t st = (hipStream_t)stream;
+  if (h->replay_slot.size() < (size_t)n) HIPCHK(h->replay_slot.alloc((size_t)(n < 1024 ? 1024 : n)));
+  ReplayStore g{};
+  g.rows = rows; g.slot = h->replay_slot.get();
+  for (const StepTensor& e : step_tensors(h, src->n_primal))
+    g.t[g.nt++] = gnnb_train::TGatherT{step_tensor(*src, e), const_cast<float*>(step_tensor(*dst, e)), (int)e.w};
+  g.t[g.nt++] = gnnb_train::TGatherT{reinterpret_cast<const float*>(src_table), reinterpret_cast<float*>(dst_table), 2 * R};
+  ReplayRank a{src_table, src->mask, rows, n, K, R, C, h->replay_slot.get(), state, status};
+  hipLaunchKernelGGL(k_replay_rank, dim3(1), dim3(RP_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_replay_store, dim3(n, TG_SPLIT), dim3(TG_THREADS), 0, st, g);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GNNB_E_HIP, "%s: a launch failed: %s", who, hipGetErrorString(e));
+  return GNNB_OK;
+}
+
+extern "C" int gnnb_replay_sample(gnnb_t* h, const int32_t* state, int C, int n, uint64_t seed, uint64_t draw, int32_t* idx, void* stream) {
+  const char* who = "gnnb_replay_sample";
+  if (int rc = refuse_capacity(C, who)) return rc;
+  if (n < 1 || n > RP_MAX_SAMPLE) return fail(GNNB_E_INVALID, "%s: n = %d slots (1 <= n <= %d)", who, n, RP_MAX_SAMPLE);
+  if (!h) return fail(GNNB_E_INVALID, "%s: null handle", who);
+  if (!state || !idx) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  ReplaySample a{state, C, n, (unsigned long long)seed, (unsigned long long)draw, idx};
+  hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(RP_THREADS), 0, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GNNB_E_HIP, "%s: the launch failed: %s", who, hipGetErrorString(e));
   return GNNB_OK;

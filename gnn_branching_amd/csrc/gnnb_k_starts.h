@@ -25,6 +25,8 @@ __host__ __device__ __forceinline__ unsigned long long ns_mix(unsigned long long
   return z ^ (z >> 31);
 }
 
+#ifdef __HIPCC__      // (a plain C++ compiler takes the hash above alone: csrc/gnnb_replay_test.cpp)
+
 struct NetStartsArgs {
   const float* x0; const double* x_lo; const double* x_hi;      // (B, N_0) x 3
   float* starts;                                                // (B, R + 1, N_0)
@@ -109,3 +111,5 @@ __global__ __launch_bounds__(FR_THREADS) void k_net_starts_pick(NetPickArgs a) {
     if (a.start_index) a.start_index[b] = win;
   }
 }
+
+#endif  // __HIPCC__

@@ -906,6 +906,31 @@ class ScorerEngine:
                    self._rows(regret, n, 1, f64, "regret").data_ptr(), self._rows(status, 1, 1, i32, "status").data_ptr())
         return loss, ds, report, regret, status
 
+    # ---- the replay buffer (frontier.ReplayBuffer owns the tensors) ----------
+    def replay_bytes(self, capacity):
+        """gnnb_replay_bytes: the bytes of a buffer's batch tensors and table for ``capacity`` slots on the bound network (0: no network
+        bound, or a capacity outside 1..65536)."""
+        return int(self.lib.gnnb_replay_bytes(self.h, int(capacity)))
+
+    def replay_push(self, src, K, rows, n, table, dst, capacity, dst_table, state, status=None):
+        """gnnb_replay_push on the current stream: the useful ones of the rows ``rows[:n]`` ((n,) int32 device tensor, list order) of the
+        K-row device batch ``src`` (a ``_lib.Batch``) and its (K, R) fp64 ``table`` go into the ring of ``capacity`` rows ``dst`` (a
+        ``_lib.Batch`` over the buffer's tensors) and ``dst_table`` ((capacity, R) fp64); ``state``: the buffer's (4,) int32 word; status:
+        None, or a (1,) int32 device tensor whose bit 3 reports a refused row.  Device work only; needs no trainer."""
+        n, K, cap, i32, f64 = int(n), int(K), int(capacity), torch.int32, torch.float64
+        self._call("gnnb_replay_push", C.byref(src), K, self._rows(table, max(K, 0), self.R, f64, "table").data_ptr(),
+                   self._rows(rows, max(n, 0), 1, i32, "rows").data_ptr(), n, C.byref(dst), cap,
+                   self._rows(dst_table, max(cap, 0), self.R, f64, "dst_table").data_ptr(), self._rows(state, 4, 1, i32, "state").data_ptr(),
+                   None if status is None else self._rows(status, 1, 1, i32, "status").data_ptr())
+
+    def replay_sample(self, state, capacity, n, seed, draw, idx):
+        """gnnb_replay_sample on the current stream: ``idx[:n]`` ((n,) int32 device tensor) receives min(n, filled) distinct slots of the
+        filled part of a buffer of ``capacity`` slots -- ``filled`` is read from ``state`` on the device -- and -1 beyond; a pure function
+        of (filled, n, seed, draw) (include/gnnb.h states the keys).  Device work only."""
+        n, i32 = int(n), torch.int32
+        self._call("gnnb_replay_sample", self._rows(state, 4, 1, i32, "state").data_ptr(), int(capacity), n, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                   C.c_uint64(int(draw) & (2 ** 64 - 1)), self._rows(idx, max(n, 0), 1, i32, "idx").data_ptr())
+
     def online_grad(self):
         """d loss / d parameters of the last online_step or imitation step, flat float32 array in checkpoint order."""
         out = np.empty(GNN_BLOB_FLOATS, dtype=np.float32)

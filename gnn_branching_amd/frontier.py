@@ -37,6 +37,10 @@ bounded in shared chunks, each candidate's child rows taking their own job's box
 
 ``strong_candidates=Shortlist(babsr=M, gnn=G)`` shortlists the candidates by the GNN's own scores as well, or by
 them alone (``gnnb_strong_list_union``, ``gnnb_strong_list``), so that the table always labels the scorer's own decision.
+
+``imitate=Replay(every=N, ...)`` keeps the labelled states: a learning round stores its useful rows in a
+device-resident ``ReplayBuffer`` (``gnnb_replay_push``) and its steps run on minibatches drawn from it (``gnnb_replay_sample``), which mix
+depths, properties and jobs; ``steps=0`` only collects, for ``replay.train_epochs`` to train on later.
 """
 import ctypes as C
 import math
@@ -221,8 +225,11 @@ IMITATE_MARGIN_DEFAULT = 1.0
 
 def _check_imitate(imitate, imitate_margin, branching, branching_threshold, online_threshold, choice):
     """The imitation options of DESIGN.md section 7.12 (None: off), before a device is touched."""
-    if imitate is not None and (not isinstance(imitate, int) or isinstance(imitate, bool) or imitate < 1):
-        raise ValueError(f"imitate = {imitate!r}: None, or an integer N >= 1 (every N-th round learns)")
+    replay = isinstance(imitate, Replay)
+    if replay:
+        _check_replay(imitate)
+    elif imitate is not None and (not isinstance(imitate, int) or isinstance(imitate, bool) or imitate < 1):
+        raise ValueError(f"imitate = {imitate!r}: None, an integer N >= 1 (every N-th round learns) or a Replay")
     if isinstance(imitate_margin, bool) or not isinstance(imitate_margin, (int, float)) or not imitate_margin >= 0:
         raise ValueError(f"imitate_margin = {imitate_margin!r}: a real number >= 0")
     if imitate is None:
@@ -233,6 +240,8 @@ def _check_imitate(imitate, imitate_margin, branching, branching_threshold, onli
         raise ValueError('imitate with branching="babsr": a BaBSR run never prepares the GNN\'s inputs; imitate is legal with "gnn" and "strong"')
     if branching_threshold is not None or online_threshold is not None:
         raise ValueError("imitate takes no branching_threshold and no online_threshold: a round learns from one loss, the table's")
+    if replay and imitate.steps == 0:                             # (collection only: no optimizer, any choice)
+        return
     from .graphnet.graph_score_online import GraphChoice
     if not isinstance(choice, GraphChoice):
         raise TypeError(f"imitate needs a graphnet.graph_score_online.GraphChoice (it owns the optimizer's lr / wd), not {type(choice).__name__}")
@@ -302,6 +311,196 @@ def _check_shortlist(s, branching, choice):
                          f"not {type(choice).__name__}")
 
 
+REPLAY_BATCH_MAX = 256              # gnnb_replay_sample's n
+REPLAY_CAPACITY_MAX = 65536         # gnnb_replay_push's C
+
+
+class ReplayBuffer:
+    """A device-resident ring of ``capacity`` labelled states of the network ``engine`` is bound to: a scorer
+    batch of ``capacity`` rows -- exactly the tensors a learning step reads, ``batch`` is the ``_lib.Batch`` over them --, the
+    strong-branching ``table`` (capacity, R) fp64 and the ``state`` word int32[4] = [head, filled, stored, skipped] on the device.
+    ``head`` / ``filled`` / ``stored`` / ``skipped`` are the HOST's copy of that word as of the last ``read_state``.  engine: the engine
+    whose handle runs the buffer's launches; any engine bound to the same network on the same device will do, and may be assigned."""
+
+    def __init__(self, engine, capacity):
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= REPLAY_CAPACITY_MAX:
+            raise ValueError(f"ReplayBuffer: capacity = {capacity!r} (an integer in 1..{REPLAY_CAPACITY_MAX})")
+        if getattr(engine, "sizes", None) is None:
+            raise ValueError("ReplayBuffer: the engine has no network bound (ScorerEngine.bind)")
+        self.engine, self.capacity, self.device = engine, capacity, engine.device
+        self.sizes, self.R = list(engine.sizes), engine.R
+        fixed = engine._net_keepalive
+        n, dev, sizes, f32 = capacity, engine.device, self.sizes, torch.float32
+        self.lb = [torch.zeros(n, s, dtype=f32, device=dev) for s in sizes]
+        self.ub = [torch.zeros(n, s, dtype=f32, device=dev) for s in sizes]
+        self.dual = [torch.zeros(n, 3 * s, dtype=f32, device=dev) for s in sizes[1:-1]]
+        self.prims, self.prim_rows, k = [], [], 0
+        for q, l in enumerate(fixed):                             # primals[q]: as ``_Rows`` holds them; the step reads those next to a ReLU
+            nxt = fixed[q + 1] if q + 1 < len(fixed) else None
+            if type(l) is nn.ReLU or type(nxt) is nn.ReLU:
+                k += type(nxt) is nn.ReLU
+                self.prims.append(torch.zeros(n, sizes[k], dtype=f32, device=dev))
+                self.prim_rows.append(True)
+            else:
+                self.prims.append(torch.zeros(1, dtype=f32, device=dev))
+                self.prim_rows.append(False)
+        self.prims.append(torch.zeros(n, 1, dtype=f32, device=dev))
+        self.prim_rows.append(True)
+        self.x_lp = torch.zeros(n, sizes[0], dtype=f32, device=dev)
+        self.prop_w = torch.zeros(n, sizes[-2], dtype=f32, device=dev)
+        self.prop_b = torch.zeros(n, 1, dtype=f32, device=dev)
+        self.mask = torch.zeros(n, self.R, dtype=f32, device=dev)
+        self.table = torch.full((n, self.R), float("nan"), dtype=torch.float64, device=dev)
+        self.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        want = engine.replay_bytes(capacity)                      # the library's own list of the tensors a step reads
+        have = sum(t.numel() * t.element_size() for t in self.row_tensors())
+        if have != want:
+            raise RuntimeError(f"ReplayBuffer: {have} bytes of row tensors, gnnb_replay_bytes says {want}")
+        self._tables = [table(g) for g in (self.lb, self.ub, self.dual, self.prims)]
+        self.batch = _lib.Batch(*self._tables, self.x_lp.data_ptr(), self.prop_w.data_ptr(), self.prop_b.data_ptr(), self.mask.data_ptr(),
+                                len(self.lb), len(self.dual), len(self.prims))
+        self.head = self.filled = self.stored = self.skipped = 0
+        self._idx = torch.zeros(REPLAY_BATCH_MAX, dtype=torch.int32, device=dev)
+
+    def row_tensors(self):
+        """Every tensor with one row per slot, the table last: what ``split``, ``save`` and ``load`` move."""
+        prims = [t for t, rows in zip(self.prims, self.prim_rows) if rows]
+        return self.lb + self.ub + self.dual + prims + [self.x_lp, self.prop_w, self.prop_b, self.mask, self.table]
+
+    def push(self, batch, K, rows, n, table, status=None):
+        """``ScorerEngine.replay_push`` into this buffer: the useful ones of the rows ``rows[:n]`` of the K-row device batch ``batch`` and
+        its (K, R) ``table``.  Device work only; ``read_state`` brings the counts over."""
+        self.engine.replay_push(batch, K, rows, n, table, self.batch, self.capacity, self.table, self.state, status)
+
+    def read_state(self):
+        """The state word as [head, filled, stored, skipped]: the one 16-byte device-to-host copy.  Updates the host's copy."""
+        st = self.state.cpu().tolist()
+        self.head, self.filled, self.stored, self.skipped = st
+        return st
+
+    def _write_state(self, head, filled):
+        self.head, self.filled, self.stored, self.skipped = head, filled, 0, 0
+        self.state.copy_(torch.tensor([head, filled, 0, 0], dtype=torch.int32))
+
+    def sample(self, n, seed, draw, out=None):
+        """``ScorerEngine.replay_sample``: n (1..256) distinct filled slots of draw number ``draw`` under ``seed`` into ``out`` (None: the
+        buffer's own index tensor), -1 beyond the filled part.  Device work only; returns the (n,) int32 device tensor."""
+        out = self._idx[:n] if out is None else out
+        self.engine.replay_sample(self.state, self.capacity, n, seed, draw, out)
+        return out
+
+    def step(self, n, margin, seed, draw, apply=True, loss=None, report=None, regret=None, status=None, out=None):
+        """``sample`` and then ``ScorerEngine.imitation_step_rows`` on the sampled slots of the buffer's batch and table: one learning step
+        on a minibatch (needs an engine with an optimizer).  Returns the sampled slots (device).  No host wait in repack mode "device"."""
+        idx = self.sample(n, seed, draw, out)
+        self.engine.imitation_step_rows(self.batch, self.capacity, idx, self.table, margin, loss=loss, report=report, regret=regret, status=status,
+                                        apply=apply)
+        return idx
+
+    def evaluate(self, margin=1.0, chunk=64):
+        """The numbers a step would report for every filled slot under the engine's current parameters, nothing applied: the
+        ``apply=False`` step over the slots 0..filled - 1 in chunks.  Returns (loss (filled,) fp32, report (filled, 4) int32, regret
+        (filled,) fp64) as CPU tensors."""
+        self.read_state()
+        n, dev = self.filled, self.device
+        loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        report = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+        regret = torch.zeros(n, dtype=torch.float64, device=dev)
+        rows = torch.arange(n, dtype=torch.int32, device=dev)
+        for a in range(0, n, chunk):
+            b = min(n, a + chunk)
+            self.engine.imitation_step_rows(self.batch, self.capacity, rows[a:b], self.table, margin, loss=loss[a:b], report=report[a:b],
+                                            regret=regret[a:b], apply=False)
+        return loss.cpu(), report.cpu(), regret.cpu()
+
+    def order(self):
+        """The filled slots from the oldest entry to the newest (host list; as of the last ``read_state``)."""
+        return [(self.head - self.filled + i) % self.capacity for i in range(self.filled)]
+
+    def split(self, fraction):
+        """Offline: the newest floor(fraction * filled) entries move to a second buffer, which is returned (capacity: their number, 1 at
+        least); this buffer keeps the others, oldest first from slot 0.  Torch indexing; reads the state first."""
+        if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not 0 <= fraction <= 1:
+            raise ValueError(f"split: fraction = {fraction!r} (a number in 0..1)")
+        self.read_state()
+        order = self.order()
+        m = int(math.floor(fraction * self.filled))
+        keep, move = order[:self.filled - m], order[self.filled - m:]
+        other = ReplayBuffer(self.engine, max(1, m))
+        dev = self.device
+        ki, mi = torch.tensor(keep, dtype=torch.long, device=dev), torch.tensor(move, dtype=torch.long, device=dev)
+        for mine, theirs in zip(self.row_tensors(), other.row_tensors()):
+            theirs[:m] = mine[mi]
+            mine[:len(keep)] = mine[ki]
+        other._write_state(m % other.capacity, m)
+        self._write_state(len(keep) % self.capacity, len(keep))
+        return other
+
+    def save(self, path):
+        """The buffer as a file: its row tensors (CPU), the state word and the bound network's layer sizes."""
+        self.read_state()
+        torch.save({"format": "gnnb_replay_buffer/1", "sizes": self.sizes, "R": self.R, "capacity": self.capacity,
+                    "widths": [int(t.shape[1]) for t in self.row_tensors()], "state": [self.head, self.filled, self.stored, self.skipped],
+                    "tensors": [t.cpu() for t in self.row_tensors()]}, path)
+
+    @classmethod
+    def load(cls, engine, path):
+        """The buffer of a ``save`` file on the network ``engine`` is bound to; a file from another network is a ValueError."""
+        d = torch.load(path, map_location="cpu")
+        if not isinstance(d, dict) or d.get("format") != "gnnb_replay_buffer/1":
+            raise ValueError(f"ReplayBuffer.load: {path} is no replay buffer file")
+        if getattr(engine, "sizes", None) is None:
+            raise ValueError("ReplayBuffer.load: the engine has no network bound (ScorerEngine.bind)")
+        if list(d["sizes"]) != list(engine.sizes) or d["R"] != engine.R:
+            raise ValueError(f"ReplayBuffer.load: {path} holds states of a network with layer sizes {list(d['sizes'])}, "
+                             f"the engine is bound to {list(engine.sizes)}")
+        buf = cls(engine, int(d["capacity"]))
+        mine = buf.row_tensors()
+        if [int(t.shape[1]) for t in mine] != list(d["widths"]):
+            raise ValueError(f"ReplayBuffer.load: {path} holds rows of other widths than the bound network's")
+        for t, src in zip(mine, d["tensors"]):
+            t.copy_(src)
+        st = [int(v) for v in d["state"]]
+        buf._write_state(st[0], st[1])
+        return buf
+
+
+class Replay:
+    """A value of ``imitate`` that keeps the labelled states.  every: N >= 1, every N-th launched round is a
+    learning round, as ``imitate=N``.  A learning round pushes its parent rows and their table into ``buffer`` (None: the run makes a
+    ``ReplayBuffer`` of ``capacity`` slots; ``run.buffer`` is it) and then takes ``steps`` steps, each on min(batch, filled) entries
+    drawn afresh under ``seed`` with a draw counter that runs through the whole run.  steps = 0 only collects: no optimizer, no
+    parameter moves, any choice."""
+
+    def __init__(self, every, buffer=None, capacity=1024, batch=8, steps=1, seed=0):
+        self.every, self.buffer, self.capacity, self.batch, self.steps, self.seed = every, buffer, capacity, batch, steps, seed
+
+    def __repr__(self):
+        return (f"Replay(every={self.every!r}, buffer={'None' if self.buffer is None else 'ReplayBuffer'}, capacity={self.capacity!r}, "
+                f"batch={self.batch!r}, steps={self.steps!r}, seed={self.seed!r})")
+
+
+def _check_replay(r):
+    """A ``Replay`` as the value of ``imitate``, before a device is touched."""
+    def count(v, least):
+        return isinstance(v, int) and not isinstance(v, bool) and v >= least
+    if not count(r.every, 1) or not count(r.capacity, 1) or not count(r.batch, 1):
+        raise ValueError(f"imitate = {r!r}: every, capacity and batch are integers >= 1")
+    if not count(r.steps, 0):
+        raise ValueError(f"imitate = {r!r}: steps is an integer >= 0 (0: collect only)")
+    if not count(r.seed, 0) or r.seed >= 2 ** 64:
+        raise ValueError(f"imitate = {r!r}: seed is an integer in 0..2^64 - 1")
+    if r.buffer is not None and not isinstance(r.buffer, ReplayBuffer):
+        raise ValueError(f"imitate = {r!r}: buffer is None or a ReplayBuffer, not {type(r.buffer).__name__}")
+    capacity = r.capacity if r.buffer is None else r.buffer.capacity
+    if capacity > REPLAY_CAPACITY_MAX:
+        raise ValueError(f"imitate = {r!r}: capacity {capacity} > {REPLAY_CAPACITY_MAX}")
+    if r.batch > REPLAY_BATCH_MAX:
+        raise ValueError(f"imitate = {r!r}: batch {r.batch} > {REPLAY_BATCH_MAX}, the most one draw holds")
+    if r.batch > capacity:
+        raise ValueError(f"imitate = {r!r}: batch {r.batch} > capacity {capacity}")
+
+
 def _check_strong(strong_candidates, strong_chunk, strong_audit, branching, branching_threshold, online_threshold, imitate=None, choice=None):
     """The strong-branching options of DESIGN.md sections 7.11 and 7.14, before a device is touched."""
     if isinstance(strong_candidates, Shortlist):
@@ -354,6 +553,7 @@ class _Round:
     branching, strong_on, imitate, learning = "gnn", False, None, False      # (what a run is before ``_set_options``: everything off)
     strong_G, cand_src = 0, None    # (section 7.14: the scorer's count of a ``Shortlist`` and the union's sources; off unless a run sets them)
     repack, pending_step = "host", None      # (section 7.15: "device" where a run asks for it; the step whose status has not been read yet)
+    replay, last_replay = None, None         # (section 7.16: the ``Replay`` of a run whose ``imitate`` is one; what its last learning round did)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
                      online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
@@ -382,7 +582,11 @@ class _Round:
             self.sparsest_layer, self.decision_threshold = int(sparsest_layer), float(decision_threshold)
         self.witness_on, self.witness_to, self.pgd_steps, self.pgd_step = witness is not None, witness, pgd_steps, float(pgd_step)
         self.restarts, self.pgd_seed = pgd_restarts or 0, pgd_seed
-        self.imitate, self.imitate_margin, self.learns = imitate, float(imitate_margin), online_threshold is not None or imitate is not None
+        self.imitate, self.imitate_margin = imitate, float(imitate_margin)
+        replay = imitate if isinstance(imitate, Replay) else None
+        if replay is not None:                                    # (set only where given, as strong_G: section 7.16)
+            self.replay, self.buffer = replay, None
+        self.learns = online_threshold is not None or (imitate is not None and (replay is None or replay.steps > 0))      # (steps = 0 only collects)
         self.strong_on = branching == "strong" or strong_audit is not None or imitate is not None
         self.strong_M, G = _shortlist_counts(strong_candidates)
         self.strong_chunk, self.strong_audit = strong_chunk, strong_audit
@@ -535,14 +739,37 @@ class _Round:
         self.im_loss, self.im_regret = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
         self.im_report = torch.zeros(n, 4, dtype=torch.int32, device=dev)
         self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        rp = self.replay
+        if rp is None:
+            return
+        # section 7.16: the buffer (the caller's, or the run's own), the word a push reports refused rows in, per step of a learning
+        # round the drawn slots and what the step reports of them, and the run's draw counter and totals
+        buf = rp.buffer
+        if buf is None:
+            buf = ReplayBuffer(self.eng, rp.capacity)
+        elif buf.sizes != list(self.eng.sizes) or buf.device != dev:
+            raise ValueError(f"imitate = {rp!r}: the buffer holds states of a network with layer sizes {buf.sizes} on {buf.device}, the run's "
+                             f"has {list(self.eng.sizes)} on {dev}")
+        else:
+            buf.engine = self.eng
+        if n_parents > buf.capacity:
+            raise ValueError(f"imitate = {rp!r}: a round has up to {n_parents} parent rows, the buffer {buf.capacity} slots; one push takes "
+                             "at most as many rows as the buffer holds")
+        self.buffer, S, b = buf, max(1, rp.steps), rp.batch
+        self.push_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rp_idx = torch.full((S, b), -1, dtype=torch.int32, device=dev)
+        self.rp_loss, self.rp_regret = torch.zeros(S, b, dtype=torch.float32, device=dev), torch.zeros(S, b, dtype=torch.float64, device=dev)
+        self.rp_report = torch.zeros(S, b, 4, dtype=torch.int32, device=dev)
+        self.draw = self.replay_stored = self.replay_skipped = self.replay_filled = 0
 
     def _begin_round(self, k):
         """The top of ``launch_round``: launched round number ``round`` of the run (1-based; root phases do not count), of k parent rows over
         all its entries.  With ``imitate`` = N it is a learning round when that number is a multiple of N: its table stays, and its step
         runs behind the read of the state.  No candidate has been counted yet (``cand_entry``)."""
         self.round += 1
-        self.learning = self.imitate_pending = self.imitate is not None and self.round % self.imitate == 0
-        self.k, self.last_imitation, self.cand_entry = k, 0, None
+        every = self.replay.every if self.replay is not None else self.imitate
+        self.learning = self.imitate_pending = every is not None and self.round % every == 0
+        self.k, self.last_imitation, self.cand_entry, self.last_replay = k, 0, None, None
 
     def _step_behind_read(self):
         """Behind the read of the state: a learning round takes its step (``_imitate``)."""
@@ -689,6 +916,9 @@ class _Round:
         if self.witness_on:
             self._witness(n, self.M)
         self._commit(slots)
+        if self.learning and self.replay is not None:             # section 7.16: the round's labelled rows go into the buffer, device work only
+            self.buffer.push(P.fwd_batch, n, self.im_rows[:n], n, self.im_table, status=self.push_status)
+            self.status_all |= self.push_status
 
     def _fall_back(self, n):
         """The threshold mode between the bounding of pair A and the commit (DESIGN.md sections 7.5 and 7.6): BaBSR on the n parent rows,
@@ -724,6 +954,8 @@ class _Round:
         weight decay alone.  The next round's forward scores with the new parameters.  ``k``: the number of parent rows of the round (of
         all its entries, in a many-jobs run)."""
         self.imitate_pending, self.last_imitation = False, 0
+        if self.replay is not None:
+            return self._replay_steps()
         if self.strong_n <= 0:
             return
         k = self.last_imitation = self.k
@@ -732,6 +964,33 @@ class _Round:
                                      report=self.im_report[:k], regret=self.im_regret[:k], status=self.step_status)
         self.status_all |= self.step_status
         self.imitation_steps, self.imitation_rows = self.imitation_steps + 1, self.imitation_rows + k
+        self._step_issued()
+
+
+    def _replay_steps(self):
+        """``_imitate`` of a run with ``imitate=Replay(...)``.  The round's push is already on the stream
+        (``_launch``).  When the round listed a candidate the host reads the buffer's state word -- 16 bytes right behind the state
+        record -- and with ``filled`` >= 1 issues ``steps`` steps, each on min(batch, filled) entries drawn afresh with the run's draw
+        counter.  In repack mode "device" the steps are issued back to back without a host wait; status, losses and reports are read
+        with the next round's record (``_step_issued``)."""
+        rp, buf = self.replay, self.buffer
+        if self.strong_n <= 0:                                    # (no candidate anywhere: the push stored nothing)
+            self.replay_skipped += self.k
+            return
+        _, filled, stored, skipped = buf.read_state()
+        self.replay_stored, self.replay_skipped, self.replay_filled = self.replay_stored + stored, self.replay_skipped + skipped, filled
+        self.last_replay = {"stored": stored, "skipped": skipped, "filled": filled, "steps": 0, "batch": 0}
+        if rp.steps == 0 or filled < 1:
+            return
+        b = self.last_imitation = min(rp.batch, filled)
+        self.step_status.zero_()
+        for s in range(rp.steps):
+            buf.step(b, self.imitate_margin, rp.seed, self.draw, loss=self.rp_loss[s, :b], report=self.rp_report[s, :b], regret=self.rp_regret[s, :b],
+                     status=self.step_status, out=self.rp_idx[s, :b])
+            self.draw += 1
+        self.status_all |= self.step_status
+        self.last_replay.update(steps=rp.steps, batch=b)
+        self.imitation_steps, self.imitation_rows = self.imitation_steps + rp.steps, self.imitation_rows + rp.steps * b
         self._step_issued()
 
 
@@ -991,7 +1250,11 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     ``trace``'s: off in a timed run.
 
     imitate, imitate_margin (with ``imitate`` at None no launch, read, buffer or argument of a round changes).
-    imitate: None, or an integer N >= 1: every round whose 1-based number is a multiple of N is a LEARNING round.  Legal with ``branching``
+    imitate: None, an integer N >= 1, or a ``Replay`` (``Replay(every=N, buffer=None, capacity=1024, batch=8, steps=1,
+    seed=0)`` -- a learning round pushes its parent rows and their table into a device-resident ``ReplayBuffer``, reads the buffer's 16-byte
+    state word behind the state record and takes ``steps`` steps on min(batch, filled) freshly drawn entries; ``steps=0`` only collects, with
+    any choice and no optimizer; stats gain "replay_stored", "replay_skipped" and "replay_filled", a traced learning round "replay_idx",
+    "replay_loss", "replay_report" and "replay_regret" per step).  With an integer: every round whose 1-based number is a multiple of N is a LEARNING round.  Legal with ``branching``
     "gnn" and "strong" and together with ``strong_audit``, ``strong_candidates`` and ``strong_chunk``, which shape the table as they shape
     a strong round's; not with "babsr", a ``branching_threshold`` or an ``online_threshold``.  ``choice`` must be a
     ``graphnet.graph_score_online.GraphChoice`` (it owns lr and wd).  A learning round leaves its table -- per parent the improvement of
@@ -1076,6 +1339,8 @@ def _one_job_loop(run, max_rounds, log, trace, stats):
             stats.update(strong_bounded=tally["strong_bounded"])
         if run.imitate is not None:
             stats.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows)
+        if run.replay is not None:
+            stats.update(replay_stored=run.replay_stored, replay_skipped=run.replay_skipped, replay_filled=run.replay_filled)
     return global_lb, global_ub, tally["rounds"], tally["domains_bounded"], reason
 
 
@@ -1114,7 +1379,22 @@ def _report_read(run, t, seg, row0, k, st, values):
     and report of the entry's rows; in a run with ``imitate`` the bounds of the entry's record ``st`` after the round; in a run with a
     witness global_ub and the device's copy of it, element ``seg`` of ``values`` (``_witness_values``)."""
     a, b = row0, row0 + k
-    if run.imitate is not None:
+    replay = getattr(run, "last_replay", None)                    # (section 7.16: a learning round of a run with a buffer that read its state)
+    if replay is not None:
+        t.update(replay_stored=replay["stored"], replay_skipped=replay["skipped"], replay_filled=replay["filled"])
+        if replay["steps"]:
+            S, n = replay["steps"], replay["batch"]
+
+            def fill_replay(kept=None):                           # the per-step draws and what each step reported of them
+                t.update(replay_idx=run.rp_idx[:S, :n].cpu().tolist(), replay_loss=run.rp_loss[:S, :n].cpu().tolist(),
+                         replay_regret=run.rp_regret[:S, :n].cpu().tolist(), replay_report=run.rp_report[:S, :n].cpu().tolist())
+            pending = getattr(run, "pending_step", None)
+            if pending is not None:
+                pending["fill"].append(fill_replay)
+            else:
+                fill_replay()
+        t.update(global_lb=_global_lb(st), global_ub=st[_lib.FS_GLOBAL_UB])
+    elif run.imitate is not None:
         if run.last_imitation:
             def fill(kept=None):
                 t.update(imitation_loss=run.im_loss[a:b].cpu().tolist(), imitation_regret=run.im_regret[a:b].cpu().tolist(),
@@ -1796,4 +2076,6 @@ def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):
         stats.extend({key: t[key] for key in keys} for t in tally)
     if learned is not None:
         learned.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows, rounds=run.round)
+        if run.replay is not None:
+            learned.update(replay_stored=run.replay_stored, replay_skipped=run.replay_skipped, replay_filled=run.replay_filled)
     return results

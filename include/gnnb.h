@@ -769,6 +769,39 @@ int gnnb_imitation_step_rows(gnnb_t* h, const gnnb_batch* in, int K, const int32
 int gnnb_imitation_loss(gnnb_t* h, const float* scores, const float* mask, const double* table, int n, double margin, float* loss, float* ds,
                         int32_t* report_i, double* regret, int32_t* status, void* stream);
 
+/* ---- the replay buffer: learn the scorer from stored strong tables ----
+ * A labelled state -- a row of a scorer batch and its row of gnnb_strong_pick's table -- is worth more than the one step of the round that
+ * made it.  A replay BUFFER is caller-owned DEVICE memory: a gnnb_batch of C rows (of every tensor gnnb_imitation_step_rows reads: the
+ * bounds of every graph layer, dual, the primals on either side of a ReLU layer and the last, x_lp, prop_w, prop_b, mask; any other
+ * primal entry needs a non-null pointer that is never read), a table (C, R) fp64 and a state word int32[4] = {head, filled, stored,
+ * skipped} that the caller zeroes once.  The step on a minibatch is the existing gnnb_imitation_step_rows(h, &buffer, C, idx, n,
+ * buffer_table, ...): its workspaces scale with n, never with C.
+ *
+ * gnnb_replay_push: of the rows rows[0..n) (device int32, in list order) of the K-row device batch `src` and its table src_table (K, R),
+ * row i is STORED iff its table row has at least two candidates (entries that are not NaN), every candidate is finite and every candidate
+ * names an undecided node of the row's mask.  A row with 0 or 1 candidates is skipped silently (a step gets no gradient from it).  A row
+ * the step would refuse (a candidate at a decided node, tau = +-inf) and a rows entry outside [0, K) are skipped and set bit 3 (value 8)
+ * of *status (device int32[1] or NULL).  The r-th stored row of the call goes to slot (head + r) mod C; then head = (head + stored) mod C,
+ * filled = min(C, filled + stored), and stored / skipped hold the call's counts.  No other slot is written.  Two launches (k_replay_rank,
+ * k_replay_store) on `stream`, no synchronisation, no trainer needed (a bound handle collects).  GNNB_E_INVALID, before any launch, for C
+ * outside 1..65536, K < 1, n < 1, n > K, n > C, a null handle or argument, and whatever gnnb_online_step_rows' batch check refuses of `src`
+ * or `dst`; GNNB_E_STATE before gnnb_bind_network.
+ *
+ * gnnb_replay_sample: idx (device int32 (n), 1 <= n <= 256) receives min(n, filled) DISTINCT slots of [0, filled), `filled` read from the
+ * device state word, and -1 in the entries beyond (the step skips such a row, with status bit 3).  A pure function of (filled, n, seed,
+ * draw): with ns_mix the splitmix64 finaliser and G = 0x9E3779B97F4A7C15,
+ *   base = ns_mix(seed ^ ns_mix(draw + 1));  key_j = ns_mix(base + G (j + 1))  (mod 2^64);
+ *   idx = the j in [0, filled) with the smallest (key_j, j), in ascending order of (key_j, j).
+ * One launch of one workgroup on `stream`, no synchronisation.  GNNB_E_INVALID for C outside 1..65536, n outside 1..256, a null handle or
+ * argument.
+ *
+ * gnnb_replay_bytes: the bytes of a buffer's batch tensors and table for C slots on the bound network (the state word not counted);
+ * 0 for a null or unbound handle or a C outside 1..65536. */
+size_t gnnb_replay_bytes(const gnnb_t* h, int C);
+int gnnb_replay_push(gnnb_t* h, const gnnb_batch* src, int K, const double* src_table, const int32_t* rows, int n, const gnnb_batch* dst, int C,
+                     double* dst_table, int32_t* state, int32_t* status, void* stream);
+int gnnb_replay_sample(gnnb_t* h, const int32_t* state, int C, int n, uint64_t seed, uint64_t draw, int32_t* idx, void* stream);
+
 /* d loss / d parameters of the last gnnb_online_step, gnnb_online_step_rows or gnnb_imitation_step_rows (before weight decay), HOST, blob order.
  * In repack mode 1, where a step may only have been issued, it synchronises the device first. */
 int gnnb_online_grad(const gnnb_t* h, float* grad, size_t n_floats);
