@@ -857,6 +857,14 @@ class _Round:
             self.eng.net_descend_starts(self.fixed, None, self.starts[:B], Ch.box[0], Ch.box[1], self.pgd_steps, self.pgd_step, x_best=Ch.x_ub,
                                         value=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_starts, in_shape=self.in_shape)
 
+    def _at_least_the_parent_s(self, Ch, slots, n):
+        """Behind the bounding of the 2n children of the n parents in ``slots``: a child's bound is at least its parent's.  The child is a
+        part of the parent, so the parent's bound holds for it; the 20 warm-started steps can end below it (the split node's new
+        multiplier starts at 0), and without this the lowest open bound falls when such a parent is replaced by its children.  Device
+        work only."""
+        parent = self.pool.bound[slots[:n].long().clamp(min=0)].repeat_interleave(2)
+        torch.maximum(Ch.bound[:2 * n], parent, out=Ch.bound[:2 * n])
+
     def _ub_points(self, Ch):
         """The points the rows' ubv are the network's values at."""
         return Ch.x_lp if self.pgd_steps is None else Ch.x_ub
@@ -911,6 +919,7 @@ class _Round:
             self.parent_bound = pool.bound[slots[:n].long().clamp(min=0)]
         eng.frontier_expand(pool, slots, P.dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
         self._bound_children(Ch, 2 * n, warm=True)
+        self._at_least_the_parent_s(Ch, slots, n)
         if self.threshold is not None:
             self._fall_back(n)
         if self.witness_on:
@@ -934,6 +943,7 @@ class _Round:
             return
         eng.frontier_expand(pool, self.sel_slots[:M], self.sel_dec, ChB.mask, ChB.plb, ChB.pub, ChB.split, ChB.alpha, ChB.beta, ChB.live)
         self._bound_children(ChB, 2 * M, warm=True)
+        self._at_least_the_parent_s(ChB, self.sel_slots, M)
         self._choose(n, M)
 
     def check_status(self):
@@ -1172,7 +1182,8 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     lp: a ``LayerGraphLP`` (its input box is the root); choice: a ``GraphChoice`` (the GNN; its engine runs every step);
     layers: the network's layers with the folded property layer last.  Per round the up-to-K open domains of lowest bound (equal bounds:
     lowest slot) are split at the GNN's decision, their 2K children bounded by ``gnnb_kw_bounds`` and ``n_iter`` warm-started steps of
-    ``gnnb_dual_ascent``, and kept or closed by ``branch_and_bound``'s rule against the global upper bound after the round's minimum.
+    ``gnnb_dual_ascent`` (a child whose steps end below its parent's bound takes the parent's: it holds for every part of the parent, and
+    global_lb then never falls from round to round), and kept or closed by ``branch_and_bound``'s rule against the global upper bound after the round's minimum.
     The loop stops under ``branch_and_bound``'s conditions: no open domain ("exhausted"), global_ub - global_lb <= eps ("gap"), the
     sign of (minimum - decision_bound) known ("decision"), or after ``max_rounds`` ("max_rounds").  capacity: slots of the pool (None:
     max(1024, 4K + 1)).  A round of k parents needs k slots above the slots in use (its 2k children reuse the parents' slots first): when

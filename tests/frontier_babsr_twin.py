@@ -9,7 +9,7 @@ import torch
 
 from gnn_branching_amd import bab_caller, lp_producer
 from gnn_branching_amd.plnn.kw_score_conv import decide
-from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, toy, ub64
+from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, toy, ub64
 
 SPARSEST = 0
 DTHR = 2.0 ** -10                   # a threshold fp32 holds exactly: a score AT it is a case of its own
@@ -143,7 +143,7 @@ def babsr_twin(K, rounds, prop=None, eps=None, sparsest=0, dthr=0.001):
         for d in picked:                                   # row order: the counter is carried from parent to parent
             (kw,), (icp,) = bab_caller.BatchedGraphChoice.kw_decision_many(choice, [as_sub(d)], fixed, [icp], order, sparsest, dthr)
             decs.append([int(kw[0]), int(kw[1])])
-        children = children_of(zip(picked, decs))
+        children = at_least_the_parents(children_of(zip(picked, decs)), [d for d in picked for _ in (0, 1)])
         gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
         closed = keep_or_close(children, gub, closed)
         branches += len(picked)

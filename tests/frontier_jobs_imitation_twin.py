@@ -7,7 +7,7 @@ import torch
 
 from gnn_branching_amd import _lib, bab_caller, lp_producer, nets
 from gnn_branching_amd.frontier import _start_record, _stop_reason, plan_round
-from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, toy, ub64
+from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, toy, ub64
 from tests.imitation_twin import NAN
 from tests.test_gpu_frontier_jobs import JOBS
 
@@ -119,7 +119,7 @@ def host_loop(ids, K, segments, cap, max_rounds, imitate, branching, audit, marg
         outs, at = [], 0
         for s, picked, _, tab in round_entries:
             job, k = state[s], len(picked)
-            children = job.children_of(zip(picked, decs[at:at + k]))
+            children = at_least_the_parents(job.children_of(zip(picked, decs[at:at + k])), [d for d in picked for _ in (0, 1)])
             job.gub = min([job.gub] + [ub64(job.lp, c) for c in children if c is not None])
             job.keep_or_close(children)                       # commit first, then learn
             outs.append({"job": seg_job[s], "segment": s, "round": job.rounds, "run_round": run_round, "decisions": decs[at:at + k],

@@ -10,7 +10,7 @@ import torch
 
 from gnn_branching_amd import bab_caller
 from tests.frontier_strong_twin import NAN, candidates_of, host_pieces, improvement_of, node_of
-from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, ub64
+from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, ub64
 
 
 def union_of(amb_row, score_a, top_a, score_b, top_b):
@@ -112,7 +112,7 @@ def shortlist_twin(K, rounds, babsr=None, gnn=None, prop=None, eps=None, commit=
         tables = [table_of(d, cands) for d, (cands, _) in zip(picked, lists)]
         decs = [t[0] for t in tables] if commit == "strong" else gnn_decs
         assert all(d != [-1, -1] for d in decs), "a picked domain of the twin has no decision"
-        children = children_of(zip(picked, decs))
+        children = at_least_the_parents(children_of(zip(picked, decs)), [d for d in picked for _ in (0, 1)])
         gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
         closed = keep_or_close(children, gub, closed)
         branches += len(picked)

@@ -12,7 +12,7 @@ import torch
 
 from gnn_branching_amd import bab_caller
 from gnn_branching_amd.bab_caller import gnn_improvement
-from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, toy, ub64
+from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, toy, ub64
 
 NAN = float("nan")
 
@@ -177,7 +177,7 @@ def strong_twin(K, rounds, top_m=0, prop=None, eps=None, commit=None):
         tables = [strong_decision(d, relu, children_of, babsr_scores, top_m) for d in picked]
         decs = [t[0] for t in tables] if commit is None else [list(d) for d in commit[len(out["decisions"])]]
         assert all(d != [-1, -1] for d in decs), "a picked domain of the twin has no decision"
-        children = children_of(zip(picked, decs))
+        children = at_least_the_parents(children_of(zip(picked, decs)), [d for d in picked for _ in (0, 1)])
         gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
         closed = keep_or_close(children, gub, closed)
         branches += len(picked)

@@ -84,6 +84,16 @@ def ub64(lp, sub):
     return float(act.reshape(()))
 
 
+def at_least_the_parents(children, parents):
+    """A round's children, each with a bound no lower than its parent's (``frontier._Round._at_least_the_parent_s``): 20 warm-started
+    steps can end below the parent's bound, which holds for every part of the parent.  parents: one per child.  The candidates of a
+    strong table keep their own values, on the device as here."""
+    for c, d in zip(children, parents):
+        if c is not None and c.lb < d.lb:
+            c.lb = d.lb
+    return children
+
+
 def masked(bounds, infeasible, live=None):
     return [INF if (inf or (live is not None and not live[c])) else b for c, (b, inf) in enumerate(zip(bounds, infeasible))]
 
@@ -132,7 +142,7 @@ def twin(K, rounds, threshold=None, kwbd=10, online_threshold=None, sides=False,
                 m = [t.clone() for t in d.mask]
                 m[dec[0]][dec[1]] = c
                 items.append((m, d, dec[0]))
-        return lp.solve_many(items, lp="dual_device", n_iter=N_ITER, lr=LR)
+        return at_least_the_parents(lp.solve_many(items, lp="dual_device", n_iter=N_ITER, lr=LR), [d for _, d, _ in items])
 
     def bounds_of(subs):
         return [INF if c is None else c.lb for c in subs]

@@ -461,7 +461,7 @@ def host_loop(K, rounds, imitate, branching, tables, margin=1.0):
     ``imitate``, behind the commit ONE ``ScorerEngine.imitation_step`` on the picked parents' own forward arguments and their tables.
     tables: per round, per picked parent, the audit's row (candidates, improvements, strong_decision): the table is an input here."""
     from gnn_branching_amd import bab_caller, lp_producer
-    from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, toy, ub64
+    from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, toy, ub64
     lp, choice, root_mask = toy(online=True)
     eng = choice._eng()
     w_start = eng.get_weights().copy()
@@ -513,7 +513,7 @@ def host_loop(K, rounds, imitate, branching, tables, margin=1.0):
         else:
             decs = [lp_producer.gnn_scorer(choice, lp)(picked[0], fixed)] if K == 1 else bab_caller.BatchedGraphChoice.decision_many(choice, subs, fixed)
             decs = [[int(d[0]), int(d[1])] for d in decs]
-        children = children_of(zip(picked, decs))
+        children = at_least_the_parents(children_of(zip(picked, decs)), [d for d in picked for _ in (0, 1)])
         gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
         closed = keep_or_close(children, gub, closed)       # commit first, then learn
         loss, report, regret = [], [], []

@@ -325,7 +325,7 @@ def replay_host_loop(K, rounds, branching, tables, margin, repack):
     table rows are pushed (tests/replay_twin.py's rule), then ``steps`` times a draw of min(batch, filled) entries is collated and given
     to ``ScorerEngine.imitation_step``, on an engine in the run's repack mode (as tests/test_gpu_frontier_repack.py's twins are)."""
     from gnn_branching_amd import bab_caller, lp_producer
-    from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, toy, ub64
+    from tests.frontier_twin import EPS_BAB, INF, LR, N_ITER, at_least_the_parents, toy, ub64
     lp, choice, root_mask = toy(online=True)
     eng = choice._eng()
     eng.set_repack(repack)
@@ -378,7 +378,7 @@ def replay_host_loop(K, rounds, branching, tables, margin, repack):
         else:
             decs = [lp_producer.gnn_scorer(choice, lp)(picked[0], fixed)] if K == 1 else bab_caller.BatchedGraphChoice.decision_many(choice, subs, fixed)
             decs = [[int(d[0]), int(d[1])] for d in decs]
-        children = children_of(zip(picked, decs))
+        children = at_least_the_parents(children_of(zip(picked, decs)), [d for d in picked for _ in (0, 1)])
         gub = min([gub] + [ub64(lp, c) for c in children if c is not None])
         closed = keep_or_close(children, gub, closed)       # commit first, then learn
         idx, loss, report, regret = [], [], [], []
