@@ -3,7 +3,7 @@
 Same constructor, ``decision``, ``online_learning`` and ``del_score`` as reference graph_score_online.py:7-90, so
 ``plnn/relu_conv_online.py`` (call sites :109, :117, :208, :230, :239) can use it unchanged.  ``decision`` is the scorer's
 fused forward; ``online_learning`` re-runs the forward of the LAST decision in training form on the device, walks it
-backwards and applies one Adam step (libgnnb.so ``gnnb_online_step``, csrc/gnnb_train.h) -- the reference keeps the
+backwards and applies one Adam step (libgnnb.so ``gnnb_online_step``, csrc/gnnb_step.h) -- the reference keeps the
 autograd graph of the decision alive instead (``self.scores``), which ``del_score`` then frees.
 """
 import sys

@@ -1,5 +1,5 @@
 """Learning online inside the device-resident frontier, on the MI355X (gnn_branching_amd/frontier.py;
-csrc/gnnb_k_frontier.h k_frontier_learn; csrc/gnnb_train.h k_trows_gather):
+csrc/gnnb_k_frontier.h k_frontier_learn; csrc/gnnb_k_train.h k_trows_gather):
 
 1. gnnb_frontier_learn against a Python restatement made of bab_caller.resolve_online and the flat ReLU index, exact, on synthetic rows
    that take every branch of the rule;

@@ -1,4 +1,4 @@
-"""The imitation step on the MI355X (csrc/gnnb_train.h k_tloss_table, k_tscore_bwd_w_dense; gnnb_imitation_step_rows,
+"""The imitation step on the MI355X (csrc/gnnb_k_train.h k_tloss_table, k_tscore_bwd_w_dense; gnnb_imitation_step_rows,
 gnnb_imitation_loss; ``branch_and_bound_frontier(imitate=N)``).
 
 1. the loss rule, exact against its restatement (tests/imitation_twin.py), through gnnb_imitation_loss on crafted arrays;

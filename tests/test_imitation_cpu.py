@@ -38,10 +38,10 @@ def test_new_symbols_are_declared_bound_and_exported(lib):
     for n in NEW:
         assert n in names and hasattr(lib, n) and n + "(" in header, n
     assert lib.gnnb_abi_version() == 2 and "GNNB_ABI_VERSION 2" in header.replace("  ", " ")
-    source = open(_lib.CSRC + "/gnnb_train.h").read()
+    source = open(_lib.CSRC + "/gnnb_k_train.h").read()        # (the training kernels; gnnb_train.h, which includes it, holds their host side)
     for k in ("k_tloss_table", "k_tscore_bwd_w_dense"):
         assert "void " + k + "(" in source, k
-    assert "gnnb_train.h" in _lib.SOURCES
+    assert "gnnb_train.h" in _lib.SOURCES and "gnnb_k_train.h" in _lib.SOURCES
 
 
 def test_no_option_and_no_profile_class_was_added(lib):

@@ -1,4 +1,4 @@
-"""The learning step (csrc/gnnb_train.h: gnnb_online_step, gnnb_online_step_rows, gnnb_imitation_step_rows) on input shapes and conv
+"""The learning step (csrc/gnnb_step.h: gnnb_online_step, gnnb_online_step_rows, gnnb_imitation_step_rows) on input shapes and conv
 geometries other than 3x32x32.  The training kernels work out layer extents, tap lists, tap counts and row offsets on their own, apart
 from the forward scorer's plan, so the networks tests/test_gpu_forward_geometry.py added for the scorer (tests/common.py FWD_ARCHS: stride >
 kernel on edge 1, a 1x1 convolution, odd extents with origin -1 on a transposed 4/2/1, windows larger than the image, a convolution as
@@ -230,7 +230,7 @@ def test_online_step_rounds(name, T, monkeypatch):
     inp_f enters the scores through the longest path of the step (mu[0] of round 0, then every sweep of all three rounds in sequence),
     and the error was the rounding inside every sum of products on that path: an fp32 oracle with its Linears evaluated in fp64 and
     rounded once has a tenth to a quarter of the plain fp32 oracle's error on these tensors, one whose Linears merely add in another
-    order has the same error.  The kernels now accumulate every such sum in fp64 and round once (csrc/gnnb_train.h, "Precision")."""
+    order has the same error.  The kernels now accumulate every such sum in fp64 and round once (csrc/gnnb_k_train.h, "Precision")."""
     online_case(name, T, monkeypatch)
 
 

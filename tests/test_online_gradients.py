@@ -1,4 +1,4 @@
-"""The online-learning step (gnnb_train.h, gnnb_online_step) tensor by tensor against fp64 autograd.
+"""The online-learning step (gnnb_step.h gnnb_online_step, on the tape of gnnb_train.h) tensor by tensor against fp64 autograd.
 
 tests/test_online.py bounds the gradient error by 2e-4 of the largest entry of the whole 52-tensor blob, which leaves every tensor whose
 own entries are smaller than that unchecked (the input-layer chains, on some networks all twelve inp_* tensors).  Here each tensor
@@ -48,7 +48,7 @@ PROPS = [(3, 5), (1, 7), (0, 2), (8, 4), (6, 9)]
 
 
 def tile_rows(nrows, n_cu):
-    """Rows per block Trainer::chain / chain_multi pick (gnnb_train.h)."""
+    """Rows per block Trainer::chain / chain_multi pick (gnnb_train.h tile_rows)."""
     return 4 if nrows <= 16 * n_cu else (8 if nrows <= 128 * n_cu else 32)
 
 
@@ -433,7 +433,7 @@ def test_no_state_carried_between_steps():
 
 @pytest.mark.gpu
 def test_step_is_deterministic():
-    """gnnb_train.h promises fixed-order sums: the same step twice gives bit-equal gradients."""
+    """gnnb_k_train.h promises fixed-order sums: the same step twice gives bit-equal gradients."""
     state = state_of("random")
     batch = make("cifar_base_kw", 17, seed=31)
     kws, imps = middle_kw(batch.masks), imps_for(17)

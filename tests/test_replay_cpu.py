@@ -59,10 +59,12 @@ def test_no_option_and_no_profile_class_was_added(lib):
 
 
 def test_one_list_of_step_tensors_serves_the_gather_the_store_and_the_size(lib):
-    """The tensors a step reads are listed by ONE function of gnnb.hip; the gather, the push and gnnb_replay_bytes call it."""
-    src = open(_lib.CSRC + "/gnnb.hip").read()
+    """The tensors a step reads are listed by ONE function (gnnb_step.h, with the step; gnnb.hip includes it); the gather (step_rows), the
+    push and gnnb_replay_bytes (gnnb.hip) call it."""
+    assert "gnnb_step.h" in _lib.SOURCES
+    src = open(_lib.CSRC + "/gnnb_step.h").read() + open(_lib.CSRC + "/gnnb.hip").read()
     assert src.count("static std::vector<StepTensor> step_tensors(") == 1 and src.count(" : step_tensors(h, ") == 3
-    body = src[src.index("static int step_rows_device("):src.index('extern "C" int gnnb_online_step_rows(')]
+    body = src[src.index("static int step_rows("):src.index('extern "C" int gnnb_online_step_rows(')]
     assert "step_tensors(h, in->n_primal)" in body and "in->dual[" not in body and "in->primal[" not in body
 
 
