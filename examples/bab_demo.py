@@ -62,6 +62,9 @@ def main():
     ap.add_argument("--babsr", action="store_true", help="branch with the BaBSR heuristic instead of the GNN")
     ap.add_argument("--bounds", default="kw", choices=("kw", "interval", "kw_device"),
                     help="intermediate bounds: host fp64 Wong-Kolter, interval arithmetic, or Wong-Kolter on the GPU (gnnb_kw_bounds)")
+    ap.add_argument("--tighten", type=int, default=0, metavar="N",
+                    help="tighten the root's intermediate bounds by N steps of dual ascent per ambiguous node (gnnb_kw_tighten with --frontier or "
+                         "--bounds kw_device, the host twin with --bounds kw); every child inherits them")
     ap.add_argument("--threshold", type=float, default=None, help="branching_threshold of the GNN + KW fall-back loop (the reference uses 0.2)")
     ap.add_argument("--frontier", type=int, default=None, metavar="K", help="device-resident frontier: expand the K most promising domains per round")
     ap.add_argument("--online", type=int, default=None, metavar="N", help="with --frontier K --threshold T: learn online, online_threshold N (the reference uses 5)")
@@ -156,15 +159,15 @@ def main():
         max_rounds, stats, learned = max(1, args.nodes // (2 * args.frontier)), [], {}
         if branching == "strong" or args.imitate is not None:
             margin = {} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}
-            results = verify_properties_strong(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
+            results = verify_properties_strong(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
                                                stats=stats, learned=learned, imitate=imitate, strong_candidates=candidates, branching=branching,
                                                **margin)
         elif branching == "babsr":
-            results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+            results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         elif args.threshold is None:
-            results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+            results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         else:
-            results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
+            results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
                                                   stats=stats)
         for j, (name, (glb, gub, rounds, bounded, reason)) in enumerate(zip(names, results)):
             kw = ""
@@ -184,7 +187,7 @@ def main():
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
     if args.frontier is not None:
         from gnn_branching_amd.frontier import branch_and_bound_frontier
-        lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device")
+        lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device", tighten_root=args.tighten)
         learns = args.online is not None or args.imitate is not None
         if learns:
             from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice
@@ -213,7 +216,9 @@ def main():
             by += f"{stats['strong_bounded']} candidate children bounded, "
         print(f"after {rounds} rounds ({by}{bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict}")
         return
-    lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds)
+    if args.tighten and args.bounds == "interval":
+        ap.error("--tighten tightens Wong-Kolter bounds: it needs --bounds kw or kw_device (or --frontier)")
+    lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds=args.bounds, tighten_root=args.tighten)
     root_mask = [torch.full((int(np.prod(lp.shapes[i + 1])),), -1, dtype=torch.long) for i in lp.pre_relu_indices]
     root = lp.solve(root_mask)
     print(f"root: lb {root.lb:.5f} ub {root.ub:.5f}, undecided ReLUs per layer {[int((m == -1).sum()) for m in root.mask]}")

@@ -13,7 +13,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("GNNB_LIB", os.path.join(CSRC, "libgnnb.so"))     # GNNB_LIB: dev override (ablation builds)
-SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_train.h", "gnnb_step.h", "gnnb_k_kw.h", "gnnb_k_dual.h", "gnnb_k_net.h", "gnnb_k_frontier.h", "gnnb_k_starts.h", "gnnb_k_strong.h", "gnnb_k_repack.h", "gnnb_k_replay.h"]
+SOURCES = ["gnnb.hip", "gnnb_dev.h", "gnnb_k_mlp.h", "gnnb_k_gather.h", "gnnb_k_fusedq.h", "gnnb_k_edges.h", "gnnb_k_misc.h", "gnnb_pack.h", "gnnb_mem.h", "gnnb_train.h", "gnnb_k_train.h", "gnnb_step.h", "gnnb_k_kw.h", "gnnb_k_dual.h", "gnnb_k_tighten.h", "gnnb_k_net.h", "gnnb_k_frontier.h", "gnnb_k_starts.h", "gnnb_k_strong.h", "gnnb_k_repack.h", "gnnb_k_replay.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread"]
 
 GNNB_CONV, GNNB_LINEAR, GNNB_RELU, GNNB_FLATTEN = 0, 1, 2, 3
@@ -96,6 +96,10 @@ SYMBOLS = [
     ("gnnb_kw_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_kw_bounds", C.c_int, [C.c_void_p, C.POINTER(KwBatch), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_kw_tighten_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_kw_tighten", C.c_int, [C.c_void_p, C.POINTER(KwBatch), C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
     ("gnnb_dual_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_dual_ascent", C.c_int, [C.c_void_p, C.POINTER(DualBatch), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -63,6 +63,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "gnnb_k_misc.h"
 #include "gnnb_k_kw.h"
 #include "gnnb_k_dual.h"
+#include "gnnb_k_tighten.h"
 #include "gnnb_k_net.h"
 #include "gnnb_k_frontier.h"
 #include "gnnb_k_starts.h"
@@ -1621,33 +1622,34 @@ static int kw_preflight(const gnnb_t* h, const char* who, const int* n_graph, si
   return GNNB_OK;
 }
 
-extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32,
-                              float* const* ub32, int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream) {
+// Everything gnnb_kw_bounds (and gnnb_kw_tighten, for the same arguments) checks before a launch, and the kernels' arguments
+static int kw_make_args(gnnb_t* h, const char* who, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32,
+                        float* const* ub32, int32_t* infeasible, void* workspace, size_t workspace_bytes, KwArgs* out, size_t* lds_out) {
   size_t lds = 0;
-  if (int rc = kw_preflight(h, "gnnb_kw_bounds", in ? &in->n_graph : nullptr, &lds)) return rc;
+  if (int rc = kw_preflight(h, who, in ? &in->n_graph : nullptr, &lds)) return rc;
   if (!lb || !ub || !infeasible || !workspace || B < 1 || B > 65535)      // (65535: k_kw_layer's grid is (N_k, B))
-    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null argument or batch size %d outside 1..65535", B);
-  if (!in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null input pointer");
+    return fail(GNNB_E_INVALID, "%s: null argument or batch size %d outside 1..65535", who, B);
+  if (!in->x_lo || !in->x_hi || !in->prop_w || !in->prop_b || !in->mask) return fail(GNNB_E_INVALID, "%s: null input pointer", who);
   if ((in->parent_lb == nullptr) != (in->parent_ub == nullptr) || (in->parent_lb && !in->split_layer))
-    return fail(GNNB_E_INVALID, "gnnb_kw_bounds: parent bounds need both tables and split_layer");
-  if ((lb32 == nullptr) != (ub32 == nullptr)) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: lb32 and ub32 go together");
+    return fail(GNNB_E_INVALID, "%s: parent bounds need both tables and split_layer", who);
+  if ((lb32 == nullptr) != (ub32 == nullptr)) return fail(GNNB_E_INVALID, "%s: lb32 and ub32 go together", who);
   const KwWs ws = kw_ws_layout(h, B);
-  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_kw_bounds: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
   KwArgs a{};
   a.net = h->kw_net;
   a.B = B;
   const int L = a.net.L, K = L + 1, NL = a.net.N[L];      // graph layers 0..K, K the property node
   for (int k = 1; k <= K; ++k) {
-    if (!lb[k - 1] || !ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null output pointer for graph layer %d", k);
+    if (!lb[k - 1] || !ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null output pointer for graph layer %d", who, k);
     a.lb[k] = lb[k - 1]; a.ub[k] = ub[k - 1];
     if (in->parent_lb) {
-      if (!in->parent_lb[k - 1] || !in->parent_ub[k - 1]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null parent pointer for graph layer %d", k);
+      if (!in->parent_lb[k - 1] || !in->parent_ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null parent pointer for graph layer %d", who, k);
       a.plb[k] = in->parent_lb[k - 1]; a.pub[k] = in->parent_ub[k - 1];
     }
   }
   for (int k = 0; k <= K; ++k)
     if (lb32) {
-      if (!lb32[k] || !ub32[k]) return fail(GNNB_E_INVALID, "gnnb_kw_bounds: null fp32 output pointer for graph layer %d", k);
+      if (!lb32[k] || !ub32[k]) return fail(GNNB_E_INVALID, "%s: null fp32 output pointer for graph layer %d", who, k);
       a.lb32[k] = lb32[k]; a.ub32[k] = ub32[k];
     }
   a.x_lo = in->x_lo; a.x_hi = in->x_hi; a.prop_w = in->prop_w; a.prop_b = in->prop_b; a.mask = in->mask;
@@ -1658,14 +1660,119 @@ extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double*
   P.w = a.pw; P.bias = a.pw + NL; P.wb = P.bb = NL + 1; P.kind = 1;
   P.n_in = NL; P.n_out = 1;
   a.infeasible = infeasible;
-  hipStream_t st = (hipStream_t)stream;
-  Launcher run{h, st};
+  *out = a;
+  *lds_out = lds;
+  return GNNB_OK;
+}
+
+// graph layers 1..L+1 of one chain (k_kw_flag is the caller's)
+static void kw_launch_chain(Launcher& run, const KwArgs& a, size_t lds) {
+  hipStream_t st = run.st;
+  const int B = a.B, K = a.net.L + 1, NL = a.net.N[a.net.L];
   const int span = std::max(std::max(a.net.N[0], a.net.N[1]), NL + 1);
   const long nthreads = (long)span * B;
   run.run(PC_KW_FIRST, [&] { hipLaunchKernelGGL(k_kw_first, dim3((unsigned)((nthreads + KW_THREADS - 1) / KW_THREADS)), dim3(KW_THREADS), 0, st, a, span); });
   for (int k = 2; k <= K; ++k)
     run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(a.net.N[k], B), dim3(KW_THREADS), lds, st, a, k); });
+}
+
+extern "C" int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32,
+                              float* const* ub32, int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream) {
+  KwArgs a{};
+  size_t lds = 0;
+  if (int rc = kw_make_args(h, "gnnb_kw_bounds", in, B, lb, ub, lb32, ub32, infeasible, workspace, workspace_bytes, &a, &lds)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  kw_launch_chain(run, a, lds);
   run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+
+// ================================================================================================================
+// Intermediate bounds tightened by per-node dual ascent (gnnb_k_tighten.h; lp_producer.py LayerGraphLP.kw_bounds(tighten=n); DESIGN.md
+// section 7.18)
+// ================================================================================================================
+struct TightenWs { size_t dg, plo, pup, state, total; int st_off[MAXL + 2], cap[MAXL + 2]; };   // byte offsets (the node flags at 0); per graph layer
+static TightenWs tighten_ws_layout(const gnnb_t* h, int B) {                                   // where the state lives and its doubles per node
+  const KwNet& net = h->kw_net;
+  auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  size_t nodes = 0, spill = 0;
+  for (int k = 1; k <= net.L; ++k) nodes += (size_t)net.N[k];
+  nodes += 1;                                             // the property node
+  TightenWs w{};
+  const size_t base = kw_lds_doubles(net.maxNr);
+  for (int k = 2; k <= net.L; ++k) {
+    const size_t need = tighten_state_doubles(net, k);
+    const bool in_lds = (base + need) * sizeof(double) <= 65536;
+    w.cap[k] = (int)need;
+    w.st_off[k] = in_lds ? (int)base : -1;
+    if (!in_lds) spill = std::max(spill, need * (size_t)net.N[k]);
+  }
+  w.dg = pad((size_t)B * net.R);
+  w.plo = w.dg + pad((size_t)B * net.R * 2 * sizeof(double));
+  w.pup = w.plo + pad((size_t)B * nodes * sizeof(double));
+  w.state = w.pup + pad((size_t)B * nodes * sizeof(double));
+  w.total = w.state + pad((size_t)B * spill * sizeof(double));
+  return w;
+}
+
+extern "C" size_t gnnb_kw_tighten_workspace_bytes(const gnnb_t* h, int B) {
+  if (!h || !h->bound || B < 1) return 0;
+  return tighten_ws_layout(h, B).total;
+}
+
+extern "C" int gnnb_kw_tighten(gnnb_t* h, const gnnb_kw_batch* in, int B, int n_iter, double lr, double* const* lb, double* const* ub,
+                               float* const* lb32, float* const* ub32, int32_t* infeasible, int32_t* counts, void* kw_workspace,
+                               size_t kw_workspace_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+  TightenArgs t{};
+  size_t lds = 0;
+  if (h && (n_iter < 0 || !(lr > 0.0) || !std::isfinite(lr)))
+    return fail(GNNB_E_INVALID, "gnnb_kw_tighten: %d iterations with step %g (at least 0; positive and finite)", n_iter, lr);
+  if (int rc = kw_make_args(h, "gnnb_kw_tighten", in, B, lb, ub, lb32, ub32, infeasible, kw_workspace, kw_workspace_bytes, &t.kw, &lds)) return rc;
+  if (!workspace) return fail(GNNB_E_INVALID, "gnnb_kw_tighten: null workspace");
+  const TightenWs ws = tighten_ws_layout(h, B);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "gnnb_kw_tighten: workspace %zu bytes, need %zu", workspace_bytes, ws.total);
+  const KwArgs& a = t.kw;
+  const int L = a.net.L, K = L + 1;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  if (n_iter == 0) {                                      // gnnb_kw_bounds, launch for launch
+    kw_launch_chain(run, a, lds);
+    run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
+    if (counts && !run.rc) HIPCHK(hipMemsetAsync(counts, 0, (size_t)B * 2 * sizeof(int32_t), st));
+    return run.rc;
+  }
+  // the plain chain first, into the workspace: what every layer of the tightened chain is met with
+  KwArgs p = a;
+  p.dg = (double*)((char*)workspace + ws.dg);
+  size_t at = 0;
+  for (int k = 1; k <= K; ++k) {
+    p.lb[k] = (double*)((char*)workspace + ws.plo) + at;
+    p.ub[k] = (double*)((char*)workspace + ws.pup) + at;
+    t.plo[k] = p.lb[k]; t.pup[k] = p.ub[k];
+    at += (size_t)B * a.net.N[k];
+  }
+  for (int k = 0; k <= K; ++k) p.lb32[k] = p.ub32[k] = nullptr;
+  kw_launch_chain(run, p, lds);
+  t.n_iter = n_iter; t.lr = lr;
+  t.ran = (int8_t*)workspace;
+  t.ws = (double*)((char*)workspace + ws.state);
+  t.counts = counts;
+  const int span = std::max(std::max(a.net.N[0], a.net.N[1]), a.net.N[L] + 1);
+  const long nthreads = (long)span * B;
+  run.run(PC_KW_FIRST, [&] { hipLaunchKernelGGL(k_kw_first, dim3((unsigned)((nthreads + KW_THREADS - 1) / KW_THREADS)), dim3(KW_THREADS), 0, st, a, span); });
+  for (int k = 2; k <= K; ++k) {
+    const unsigned meet = (unsigned)(((long)a.net.N[k] * B + KW_THREADS - 1) / KW_THREADS);
+    run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_layer, dim3(a.net.N[k], B), dim3(KW_THREADS), lds, st, a, k); });
+    run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_meet, dim3(meet), dim3(KW_THREADS), 0, st, t, k); });
+    if (k <= L) {
+      const size_t tl = lds + (ws.st_off[k] >= 0 ? (size_t)ws.cap[k] * sizeof(double) : 0);
+      run.run(PC_KW_LAYER, [&] { hipLaunchKernelGGL(k_kw_tighten, dim3(a.net.N[k], B), dim3(KW_THREADS), tl, st, t, k, ws.st_off[k], ws.cap[k]); });
+    }
+  }
+  run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_flag, dim3(B), dim3(KW_THREADS), 0, st, a); });
+  if (counts) run.run(PC_KW_FLAG, [&] { hipLaunchKernelGGL(k_kw_tighten_count, dim3(B), dim3(KW_THREADS), 0, st, t); });
   return run.rc;
 }
 

@@ -106,10 +106,10 @@ __device__ double dual_backward(const DualArgs& a, int b, int tid, double* lds, 
   return c;
 }
 
-// (A_k q)_j of a conv edge, one thread per node
-__device__ __forceinline__ double dual_conv_at(const KwEdge& E, int j, const double* q) {
+// (A_k q)_j of a conv edge of domain b, one thread per node; q holds rows y0.. / columns x0.. of every input channel, qh x qw per channel
+__device__ __forceinline__ double dual_conv_window_at(const KwEdge& E, int b, int j, const double* q, int y0, int x0, int qh, int qw) {
   const int hw = E.h_out * E.w_out, co = j / hw, oy = (j % hw) / E.w_out, ox = j % E.w_out;
-  const double* w = E.w + (long)co * E.c_in * E.kh * E.kw;
+  const double* w = E.w + (long)b * E.wb + (long)co * E.c_in * E.kh * E.kw;
   double acc = 0.0;
   for (int ci = 0; ci < E.c_in; ++ci)
     for (int ky = 0; ky < E.kh; ++ky) {
@@ -118,10 +118,15 @@ __device__ __forceinline__ double dual_conv_at(const KwEdge& E, int j, const dou
       for (int kx = 0; kx < E.kw; ++kx) {
         const int ix = ox * E.stride - E.pad + kx;
         if (ix < 0 || ix >= E.w_in) continue;
-        acc += w[(ci * E.kh + ky) * E.kw + kx] * q[((long)ci * E.h_in + iy) * E.w_in + ix];
+        acc += w[(ci * E.kh + ky) * E.kw + kx] * q[((long)ci * qh + iy - y0) * qw + ix - x0];
       }
     }
   return acc;
+}
+
+// ... of a shared edge over the whole input layer
+__device__ __forceinline__ double dual_conv_at(const KwEdge& E, int j, const double* q) {
+  return dual_conv_window_at(E, 0, j, q, 0, 0, E.h_in, E.w_in);
 }
 
 enum { DUAL_STEP = 1, DUAL_GRAD = 2, DUAL_RECOVER = 4 };

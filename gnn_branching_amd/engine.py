@@ -54,11 +54,12 @@ class BabsrResult:
 class KwBoundsResult:
     """Device outputs of one gnnb_kw_bounds call: fp64 bounds of graph layers 1..L+1 (lists of (B, N_k) tensors, split mask applied),
     optionally their fp32 copies laid out as GraphNet.forward's lower_bounds_all / upper_bounds_all (graph layers 0..L+1, layer 0 =
-    the box, in the shape x_lo was given in), and the (B,) int32 infeasible flags.  Nothing is synchronised."""
-    __slots__ = ("lb", "ub", "lb32", "ub32", "infeasible")
+    the box, in the shape x_lo was given in), and the (B,) int32 infeasible flags; counts: None, or gnnb_kw_tighten's (B, 2) int32.
+    Nothing is synchronised."""
+    __slots__ = ("lb", "ub", "lb32", "ub32", "infeasible", "counts")
 
-    def __init__(self, lb, ub, lb32, ub32, infeasible):
-        self.lb, self.ub, self.lb32, self.ub32, self.infeasible = lb, ub, lb32, ub32, infeasible
+    def __init__(self, lb, ub, lb32, ub32, infeasible, counts=None):
+        self.lb, self.ub, self.lb32, self.ub32, self.infeasible, self.counts = lb, ub, lb32, ub32, infeasible, counts
 
 
 class DualAscentResult:
@@ -968,8 +969,12 @@ class ScorerEngine:
             raise ValueError(f"masks has {tuple(mask.shape)}, expected ({B}, {self.R})")
         return (B, xl, xu, mask) + self._prop(prop_layers)
 
-    def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False):
-        """gnnb_kw_bounds on the current stream.  x_lo / x_hi: (B, C, H, W) input boxes (fp64 on the device), or (B, N_0) when the first
+    def kw_tighten_workspace(self, B):
+        return self._workspace("kw_tighten", B, "gnnb_kw_tighten_workspace_bytes")
+
+    def kw_bounds(self, fixed_layers, prop_layers, x_lo, x_hi, masks, parents=None, split_layers=None, want_fp32=False, tighten=0, lr=0.1):
+        """gnnb_kw_bounds on the current stream; with ``tighten`` = n > 0 gnnb_kw_tighten: the bounds of the ambiguous nodes of graph layers
+        2..L tightened by n steps (``lr``) of dual ascent per node, and ``KwBoundsResult.counts`` (B, 2) int32: the nodes it ran for / decided.  x_lo / x_hi: (B, C, H, W) input boxes (fp64 on the device), or (B, N_0) when the first
         layer is not a Conv2d (the input shape is read from the box); prop_layers: B Linear(N_L, 1); masks: (B, R) in {-1, 0, 1}, flat
         ReLU order; parents: None or (lbs, ubs), each n_graph-1 tensors (B, N_k) of graph layers 1..L+1 (fp64); split_layers: (B,) ReLU
         layer of each domain's split, -1 = no parent.  Returns a KwBoundsResult."""
@@ -994,6 +999,14 @@ class ScorerEngine:
         infeasible = torch.empty(B, dtype=torch.int32, device=dev)
         ws = self.kw_workspace(B)
         kb = _lib.KwBatch(xl.data_ptr(), xu.data_ptr(), pw.data_ptr(), pb.data_ptr(), mask.data_ptr(), table(plb), table(pub), ptr(split), ng)
+        if tighten < 0:
+            raise ValueError(f"tighten = {tighten} < 0")
+        if tighten > 0:
+            counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+            tws = self.kw_tighten_workspace(B)
+            self._call("gnnb_kw_tighten", C.byref(kb), B, int(tighten), float(lr), table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(),
+                       counts.data_ptr(), ws.data_ptr(), ws.numel(), tws.data_ptr(), tws.numel())
+            return KwBoundsResult(lb, ub, lb32, ub32, infeasible, counts)
         self._call("gnnb_kw_bounds", C.byref(kb), B, table(lb), table(ub), table(lb32), table(ub32), infeasible.data_ptr(), ws.data_ptr(), ws.numel())
         return KwBoundsResult(lb, ub, lb32, ub32, infeasible)
 

@@ -261,6 +261,12 @@ def _check_repack(repack):
                          "(they are built on the stream, the step's status is read with the next round's state record)")
 
 
+def _check_tighten(tighten_root):
+    """tighten_root: the iterations of ``gnnb_kw_tighten`` on the root's intermediate bounds; 0: ``gnnb_kw_bounds``."""
+    if isinstance(tighten_root, bool) or not isinstance(tighten_root, int) or tighten_root < 0:
+        raise ValueError(f"tighten_root = {tighten_root!r}: an integer >= 0")
+
+
 def _check_branching(branching, branching_threshold, online_threshold):
     """The branching mode, before a device is touched."""
     if not isinstance(branching, str) or branching not in BRANCHINGS:
@@ -554,6 +560,7 @@ class _Round:
     strong_G, cand_src = 0, None    # (section 7.14: the scorer's count of a ``Shortlist`` and the union's sources; off unless a run sets them)
     repack, pending_step = "host", None      # (section 7.15: "device" where a run asks for it; the step whose status has not been read yet)
     replay, last_replay = None, None         # (section 7.16: the ``Replay`` of a run whose ``imitate`` is one; what its last learning round did)
+    tighten_root = 0                         # (section 7.18: iterations of gnnb_kw_tighten on the roots' intermediate bounds; 0: gnnb_kw_bounds)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
                      online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
@@ -668,6 +675,14 @@ class _Round:
             self.starts = torch.zeros(n_children, n_starts, eng.sizes[0], dtype=torch.float32, device=dev)
             self.ws_starts = torch.empty(max(1, self.lib.gnnb_net_descend_starts_workspace_bytes(eng.h, n_children, n_starts)), dtype=torch.uint8, device=dev)
         self.keep_pairs, self.pair_a = False, None
+
+    def set_tighten_root(self, n):
+        """DESIGN.md section 7.18, before the first root phase: the roots' intermediate bounds come from ``gnnb_kw_tighten`` at n iterations
+        (0: ``gnnb_kw_bounds``, and nothing is allocated).  The workspace is sized for the largest root phase (``root_rows``); no round uses it."""
+        _check_tighten(n)
+        self.tighten_root = n
+        if n:
+            self.ws_tighten = self._ws("gnnb_kw_tighten_workspace_bytes", self.root_rows)
 
     def _ws(self, sizer, B):
         return torch.empty(max(1, getattr(self.lib, sizer)(self.eng.h, B)), dtype=torch.uint8, device=self.eng.device)
@@ -835,15 +850,21 @@ class _Round:
         if self.learning and not self.strong_G:
             self._scorer_inputs(n)
 
-    def _bound_children(self, Ch, B, warm):
-        """gnnb_kw_bounds, gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
+    def _bound_children(self, Ch, B, warm, tighten=0):
+        """gnnb_kw_bounds (with ``tighten`` = n > 0, the root phase's: gnnb_kw_tighten at n iterations),
+        gnnb_dual_ascent and gnnb_net_eval over the first B rows of the child rows ``Ch``.  With ``pgd_steps``
         gnnb_net_descend from the rows' x_lp takes gnnb_net_eval's place: its f(x0) is that value, ubv the best value
         it reached and x_ub the point.  With ``pgd_restarts`` gnnb_net_starts and gnnb_net_descend_starts take its place in turn (section 7.9):
         the descent from the LP point and from ``restarts`` uniform points of the row's box, ubv the least of their best values."""
         lib, h = self.lib, self.eng.h
         with torch.cuda.device(self.eng.device):
-            _lib.check(lib.gnnb_kw_bounds(h, C.byref(Ch.kw_batch), B, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
-                                          self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
+            if tighten:
+                _lib.check(lib.gnnb_kw_tighten(h, C.byref(Ch.kw_batch), B, tighten, self.lr, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), None,
+                                               self.ws_kw.data_ptr(), self.ws_kw.numel(), self.ws_tighten.data_ptr(), self.ws_tighten.numel(),
+                                               self._stream()), "gnnb_kw_tighten")
+            else:
+                _lib.check(lib.gnnb_kw_bounds(h, C.byref(Ch.kw_batch), B, Ch.t_lb, Ch.t_ub, None, None, Ch.infeasible.data_ptr(), self.ws_kw.data_ptr(),
+                                              self.ws_kw.numel(), self._stream()), "gnnb_kw_bounds")
             _lib.check(lib.gnnb_dual_ascent(h, C.byref(Ch.dual_batch), B, self.n_iter, self.lr, Ch.alpha.data_ptr(), Ch.beta.data_ptr(), int(warm),
                                             Ch.bound.data_ptr(), None, None, Ch.t_dual, Ch.t_prims, Ch.x_lp.data_ptr(), None, self.ws_dual.data_ptr(),
                                             self.ws_dual.numel(), self._stream()), "gnnb_dual_ascent")
@@ -1032,6 +1053,8 @@ class FrontierRun(_Round):
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
+        tighten_root = getattr(lp, "tighten_root", 0)             # (section 7.18: the option travels on the root's description)
+        _check_tighten(tighten_root)
         self.K, self.n_iter, self.lr, self.eps, self.decision_bound = K, n_iter, float(lr), float(eps), decision_bound
         self.fixed, self.prop_layer = layers[:-1], layers[-1]
         eng = self.eng = self._engine_of(choice)
@@ -1046,6 +1069,8 @@ class FrontierRun(_Round):
         self.pw = self.prop_layer.weight.detach().reshape(1, -1).to(dev, torch.float32).expand(n, -1).contiguous()
         self.pb = self.prop_layer.bias.detach().reshape(1).to(dev, torch.float32).expand(n).contiguous()
         self._buffers(K, n, in_shape, (self.x_lo, self.x_hi, self.pw, self.pb))
+        self.root_rows = 1
+        self.set_tighten_root(tighten_root)
         self._witness_buffers(1)
         self.slots = None
         self.m, self.m_e, self.M = 0, [0], 0                      # (m_e, M: the round as a plan of one entry)
@@ -1076,7 +1101,7 @@ class FrontierRun(_Round):
         Ch.mask[:1].fill_(-1)
         Ch.split[:2].fill_(-1)
         Ch.live[:2] = torch.tensor([1, 0], dtype=torch.int32).to(Ch.live.device)
-        self._bound_children(Ch, 1, warm=False)
+        self._bound_children(Ch, 1, warm=False, tighten=self.tighten_root)
         if self.witness_on:
             self._witness(1, 0)
         self._commit(self.root_slot)
@@ -1298,6 +1323,12 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     round shows, are then read with the NEXT round's state record, or at the end of the run for the last round; the RuntimeError for
     status bit 3 is raised at that read and names the round that learnt.  Decisions, bounds, losses and parameters are those of "host"
     wherever the two builders' packs give the same scores (a folded pack entry may differ by one fp32 unit in the last place).
+
+    lp.tighten_root (``LayerGraphLP(..., tighten_root=n)`` -- this parameter list is fixed, so the option travels on
+    the root's description; with 0, the default, no launch, read, buffer or argument of the run changes).  An integer n >= 1: the root's
+    intermediate bounds come from ``gnnb_kw_tighten`` at n iterations (step ``lr``) -- every ambiguous node of graph layers 2..L
+    bounded by its own slope-optimised dual ascent -- in place of ``gnnb_kw_bounds``.  Every child copies or intersects its parent's bounds,
+    so the whole tree inherits them; no round runs the tightening, and it adds no read.
 
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
@@ -1672,6 +1703,7 @@ class JobsRun(_Round):
         self.x_lo, self.x_hi = torch.zeros(2 * n, N0, dtype=f64, device=dev), torch.zeros(2 * n, N0, dtype=f64, device=dev)
         self.pw, self.pb = torch.zeros(2 * n, NL, dtype=f32, device=dev), torch.zeros(2 * n, dtype=f32, device=dev)
         self._buffers(n, 2 * n, in_shape, (self.px_lo, self.px_hi, self.ppw, self.ppb))
+        self.root_rows = 2 * S
         self.ws_commit = self._ws("gnnb_frontier_commit_jobs_workspace_bytes", n)
         self._witness_buffers(S)
         if self.witness_on:
@@ -1748,7 +1780,7 @@ class JobsRun(_Round):
         Ch.mask[:2 * E].fill_(-1)
         Ch.split[:2 * E].fill_(-1)
         Ch.live[:2 * E] = self.root_live[:2 * E]
-        self._bound_children(Ch, 2 * E, warm=False)
+        self._bound_children(Ch, 2 * E, warm=False, tighten=self.tighten_root)
         if self.witness_on:
             self._witness(E, 0)
         self._commit(self.slots[:E])
@@ -1871,10 +1903,13 @@ class StrongJobsRun(JobsRun):
 class FrontierJobs(list):
     """A list of ``FrontierJob`` together with the upper-bound options of the run that verifies them: how
     ``verify_properties`` and ``verify_properties_threshold`` take ``branch_and_bound_frontier``'s witness, pgd_steps and pgd_step.  (Their
-    own parameter lists are fixed.)  pgd_restarts / pgd_seed: the restart options of section 7.9.  witness: None, or a list that receives one entry per job, in job order, when the run ends."""
+    own parameter lists are fixed.)  pgd_restarts / pgd_seed: the restart options of section 7.9.  witness: None, or a list that receives one entry per job, in job order, when the run ends.
+    tighten_root: ``branch_and_bound_frontier``'s (section 7.18), for the root of every job."""
 
-    def __init__(self, jobs, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0):
+    def __init__(self, jobs, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, tighten_root=0):
         super().__init__(jobs)
+        _check_tighten(tighten_root)
+        self.tighten_root = tighten_root                                       # (section 7.18)
         self.witness, self.pgd_steps, self.pgd_step = witness, pgd_steps, pgd_step
         self.pgd_restarts, self.pgd_seed = pgd_restarts, pgd_seed              # (section 7.9)
 
@@ -1884,6 +1919,11 @@ def _options_of(jobs):
     if not isinstance(jobs, FrontierJobs):
         return {}
     return {"witness": jobs.witness, "pgd_steps": jobs.pgd_steps, "pgd_step": jobs.pgd_step, "pgd_restarts": jobs.pgd_restarts, "pgd_seed": jobs.pgd_seed}
+
+
+def _tighten_of(jobs):
+    """``FrontierJobs.tighten_root`` (0 for any other sequence of jobs); ``_Round.set_tighten_root`` checks it."""
+    return jobs.tighten_root if isinstance(jobs, FrontierJobs) else 0
 
 
 def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print, trace=None):
@@ -1902,10 +1942,11 @@ def verify_properties(choice, fixed_layers, jobs, K=16, segments=None, capacity=
     and a job's witness and bounds are what it gets alone with the same options.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    options = _options_of(jobs)
+    options, tighten_root = _options_of(jobs), _tighten_of(jobs)
+    _check_tighten(tighten_root)                                 # (before the run touches a device, as every option)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, **options)
-    return _verify_jobs(run, choice, jobs, max_rounds, log, trace)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, tighten_root=tighten_root)
 
 
 def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4,
@@ -1925,13 +1966,14 @@ def verify_properties_threshold(choice, fixed_layers, jobs, branching_threshold,
     the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    options = _options_of(jobs)
+    options, tighten_root = _options_of(jobs), _tighten_of(jobs)
+    _check_tighten(tighten_root)                                 # (before the run touches a device, as every option)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if branching_threshold is None:
         raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
     run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold,
                   sparsest_layer=sparsest_layer, decision_threshold=decision_threshold, **options)
-    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, tighten_root=tighten_root)
 
 
 def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, sparsest_layer=0,
@@ -1946,11 +1988,12 @@ def verify_properties_babsr(choice, fixed_layers, jobs, K=16, segments=None, cap
     "decisions" are BaBSR's.  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    options = _options_of(jobs)
+    options, tighten_root = _options_of(jobs), _tighten_of(jobs)
+    _check_tighten(tighten_root)                                 # (before the run touches a device, as every option)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     run = JobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, sparsest_layer=sparsest_layer, decision_threshold=decision_threshold,
                   branching="babsr", **options)
-    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, tighten_root=tighten_root)
 
 
 def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, capacity=None, n_iter=20, lr=0.1, eps=1e-4, max_rounds=50, log=print,
@@ -1985,20 +2028,23 @@ def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, ca
     and "round".  A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
 
     Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
-    options = _options_of(jobs)
+    options, tighten_root = _options_of(jobs), _tighten_of(jobs)
+    _check_tighten(tighten_root)                                 # (before the run touches a device, as every option)
     jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
     if learned is not None and not isinstance(learned, dict):
         raise ValueError(f"learned = {learned!r}: None, or a dict that receives the run's learning counts")
     run = StrongJobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, imitate=imitate, imitate_margin=imitate_margin,
                         strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit, branching=branching, **options)
-    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, learned)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, learned, tighten_root)
 
 
-def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=None):
+def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=None, tighten_root=0):
     """``_jobs_loop`` on a checked run, for ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr`` and
-    ``verify_properties_strong``; when the run ends (or raises) after a learning step, ``choice.model`` receives the device's parameters."""
+    ``verify_properties_strong``; when the run ends (or raises) after a learning step, ``choice.model`` receives the device's parameters.
+    tighten_root: the ``FrontierJobs``' (``_tighten_of``)."""
     run.keep_pairs = trace is not None
     try:
+        run.set_tighten_root(tighten_root)
         return _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned)
     finally:
         if run.imitation_steps:                                   # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it

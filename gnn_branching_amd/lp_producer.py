@@ -27,6 +27,7 @@ points, KW within interval, LP bound with KW >= LP bound with interval, primal f
 reported duals, monotonicity under branching, incremental == inherited below the split.
 The LP is host-side CPU code, like the reference's; the GPU scores and, with ``bounds="kw_device"``, computes the intermediate bounds.
 """
+import copy
 from dataclasses import dataclass
 from typing import List
 
@@ -92,6 +93,7 @@ class DualAscentHost:
     values: List[float]              # g of every iterate, the entry point first
     grad_alpha: torch.Tensor         # supergradient at the entry point
     grad_beta: torch.Tensor
+    min_lambda: float = float("inf")  # smallest non-zero |lambda| of any node or input at any evaluation, where it was asked for
 
 
 def _check_parent(parent, split_layer):
@@ -114,9 +116,14 @@ def _clamp_by_mask(m, lo, up):
 class LayerGraphLP:
     """LP relaxation of ``layers`` (net.layers with the folded Linear(., 1) property layer last) over an input box."""
 
-    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm", engine=None):
+    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm", engine=None, tighten_root=0):
         """``bounds``: "kw" (host fp64 Wong-Kolter), "interval", or "kw_device" (the same bounds on the GPU; ``engine``: the
-        ScorerEngine to run them on, None = a GNN-free one created on first use)."""
+        ScorerEngine to run them on, None = a GNN-free one created on first use).  ``tighten_root`` = n > 0: a
+        domain without a parent gets ``kw_bounds(tighten=n)`` -- every child then inherits the tightened bounds through its parent's --
+        in ``bounds`` ("kw" and "kw_device") and as the root of ``frontier.branch_and_bound_frontier``."""
+        if isinstance(tighten_root, bool) or not isinstance(tighten_root, int) or tighten_root < 0:
+            raise ValueError(f"tighten_root = {tighten_root!r}: an integer >= 0")
+        self.tighten_root = tighten_root
         self.retry_stats = {"infeasible_first": 0, "flipped_to_feasible": 0}      # see solve(): the widened re-solve of an 'infeasible' IPM answer
         self.lp_method = lp_method
         if bounds not in ("kw", "interval", "kw_device"):
@@ -222,7 +229,72 @@ class LayerGraphLP:
         up = up + flat.clamp(min=0) @ xu + flat.clamp(max=0) @ xl
         return lo.reshape(self.shapes[q + 1]), up.reshape(self.shapes[q + 1])
 
-    def kw_bounds(self, mask, parent=None, split_layer=None):
+    def _cone(self, q, j):
+        """Per ReLU layer below the affine layer ``self.layers[q]`` a flat bool tensor: the nodes output node j of that layer can
+        depend on, by k_kw_layer's box rule -- through a conv the rows and columns of the receptive fields (all channels, clipped to the
+        image), through a Linear map the whole layer."""
+        cones, box = [], None                       # box: (y0, y1, x0, x1) of the layer the walk stands on, None = the whole layer
+        for i in range(q, -1, -1):
+            l = self.layers[i]
+            if type(l) is nn.Conv2d:
+                (_, hi, wi), (_, ho, wo) = self.shapes[i], self.shapes[i + 1]
+                if i == q:
+                    oy, ox = (j % (ho * wo)) // wo, j % wo
+                    box = (oy, oy, ox, ox)
+                elif box is None:
+                    box = (0, ho - 1, 0, wo - 1)
+                (sy, sx), (py, px), (ky, kx) = l.stride, l.padding, l.kernel_size
+                box = (max(0, box[0] * sy - py), min(hi - 1, box[1] * sy - py + ky - 1),
+                       max(0, box[2] * sx - px), min(wi - 1, box[3] * sx - px + kx - 1))
+            elif type(l) is nn.Linear:
+                box = None
+            elif type(l) is nn.ReLU:
+                c = torch.zeros(self.shapes[i], dtype=torch.bool)
+                if box is None:
+                    c[...] = True
+                else:
+                    c[:, box[0]:box[1] + 1, box[2]:box[3] + 1] = True
+                cones.append(c.reshape(-1))
+        return cones[::-1]
+
+    def _tighten_layer(self, q, r, lbs, ubs, nl, nu, mask, n_iter, lr, objectives=None):
+        """Slope-optimised bounds of the affine layer ``self.layers[q]`` (the pre-activation of ReLU layer r):
+        for every node that (nl, nu) leave ambiguous and both signs, ``n_iter`` steps of ``dual_ascent_host``'s recursion on the network
+        cut off below the layer with the row sign * A_q[j, :] as its property layer; beta is free on the split nodes of the node's cone
+        (``_cone``: no other node appears in its LP).  Returns (nl, nu, nodes run, nodes decided).  ``objectives``: a list that receives
+        (q + 1, node, sign, the smallest non-zero |lambda| any evaluation met) of every ascent (a kink of g lies where lambda changes sign)."""
+        _, A, bias = self.mats[q]
+        m = mask[r].reshape(-1)
+        fl, fu = nl.reshape(-1).clone(), nu.reshape(-1).clone()
+        nodes = torch.nonzero((m == -1) & (fl < 0) & (fu > 0)).reshape(-1).tolist()
+        if not nodes:
+            return nl, nu, 0, 0
+        view = copy.copy(self)
+        n_in = int(np.prod(self.shapes[q]))
+        head = nn.Linear(n_in, 1).double()
+        flat = len(self.shapes[q]) != 1
+        view.layers = self.layers[:q] + ([Flatten()] if flat else []) + [head]
+        view.shapes = self.shapes[:q + 1] + ([(n_in,)] if flat else []) + [(1,)]
+        view.pre_relu_indices = [i for i in self.pre_relu_indices if i < q]
+        sub = mask[:r]
+        decided = 0
+        for j in nodes:
+            cone = self._cone(q, j)
+            row = torch.from_numpy(A.getrow(j).toarray()[0])
+            best = []
+            for sign in (1.0, -1.0):
+                with torch.no_grad():
+                    head.weight.copy_((sign * row)[None])
+                    head.bias.fill_(sign * float(bias[j]))
+                da = view._ascent(view._dual_states((lbs, ubs), sub, cone), None, None, n_iter, lr, track_lambda=objectives is not None)
+                best.append(da.bound)
+                if objectives is not None:
+                    objectives.append((q + 1, j, sign, da.min_lambda))
+            fl[j], fu[j] = max(float(fl[j]), best[0]), min(float(fu[j]), -best[1])
+            decided += not (fl[j] < 0 and fu[j] > 0)
+        return fl.reshape(nl.shape), fu.reshape(nu.shape), len(nodes), decided
+
+    def kw_bounds(self, mask, parent=None, split_layer=None, tighten=0, lr=0.1, report=None):
         """Intermediate bounds of the domain ``mask``: for every affine layer the Wong-Kolter bounds (``_kw_layer``, built on the
         tightened bounds of the layers below, as the reference's DualNetwork does with zl / zu) intersected with interval
         arithmetic, then the split mask applied to the pre-activation bounds.
@@ -230,12 +302,21 @@ class LayerGraphLP:
         ``parent`` = (lbs, ubs) of the parent domain and ``split_layer`` = index of the ReLU layer the child was split on: the
         incremental form of update_kw_bounds (dual_network_linear_approximation.py:296-451) -- every bound up to and including
         that layer's pre-activation is the parent's (only the split node is clamped, :311-318), later layers are recomputed and
-        intersected with the parent's bounds (:398-399).  Returns (lbs, ubs) like ``interval_bounds``."""
+        intersected with the parent's bounds (:398-399).  Returns (lbs, ubs) like ``interval_bounds``.
+
+        ``tighten`` = n > 0: every recomputed pre-activation layer above the first then has the bounds of its ambiguous nodes raised by
+        n steps of dual ascent per node and sign (``_tighten_layer``, step ``lr``) before the layer above reads them.  Every layer
+        above the first is also met with its ``tighten=0`` bounds, so no bound is ever looser than those.  ``report``: a dict that
+        receives "counts" = [nodes the ascent ran for, nodes it decided] and "objectives" (``_tighten_layer``)."""
         _check_parent(parent, split_layer)
+        if tighten < 0 or (tighten > 0 and not (lr > 0 and np.isfinite(lr))):
+            raise ValueError(f"tighten = {tighten} must be >= 0 and lr = {lr} a positive finite number")
         lbs, ubs = [self.input_lb.clone()], [self.input_ub.clone()]
         keep_upto = self.pre_relu_indices[split_layer] if parent is not None else -1
         r = 0
         first_affine = True
+        ran, objectives = [0, 0], []
+        plain = self.kw_bounds(mask, parent, split_layer) if tighten > 0 else None
         for q, l in enumerate(self.layers):
             lo, up = lbs[-1], ubs[-1]
             if type(l) in (nn.Conv2d, nn.Linear):
@@ -248,6 +329,13 @@ class LayerGraphLP:
                         nl, nu = torch.maximum(nl, kl), torch.minimum(nu, ku)
                     if parent is not None:
                         nl, nu = torch.maximum(nl, parent[0][q + 1].double()), torch.minimum(nu, parent[1][q + 1].double())
+                    if plain is not None and not first_affine:
+                        # the fixed slope u / (u - l) moves with the bounds below and the KW bound above is not monotone in it: the
+                        # plain chain's bounds are met so that no bound is looser than with tighten=0
+                        nl, nu = torch.maximum(nl, plain[0][q + 1]), torch.minimum(nu, plain[1][q + 1])
+                        if q + 1 < len(self.layers):
+                            nl, nu, n_run, n_dec = self._tighten_layer(q, r, lbs, ubs, nl, nu, mask, tighten, lr, objectives)
+                            ran = [ran[0] + n_run, ran[1] + n_dec]
                 first_affine = False
             elif type(l) is nn.ReLU:
                 lo, up = _clamp_by_mask(mask[r].reshape(lo.shape), lo, up)
@@ -258,6 +346,8 @@ class LayerGraphLP:
                 nl, nu = lo.reshape(-1), up.reshape(-1)
             lbs.append(nl)
             ubs.append(nu)
+        if report is not None:
+            report["counts"], report["objectives"] = ran, objectives
         return lbs, ubs
 
     def kw_device_bounds(self, items):
@@ -266,8 +356,9 @@ class LayerGraphLP:
         fp64; post-ReLU entries clamped, flattened entries reshaped)."""
         return self._kw_device(items)[0]
 
-    def _kw_device(self, items):
-        """``kw_device_bounds`` and what its device call read and wrote: (host lists, KwBoundsResult, (fixed, prop, x_lo, x_hi, masks))."""
+    def _kw_device(self, items, tighten=0):
+        """``kw_device_bounds`` and what its device call read and wrote: (host lists, KwBoundsResult, (fixed, prop, x_lo, x_hi, masks)).
+        ``tighten``: ``ScorerEngine.kw_bounds``' (gnnb_kw_tighten)."""
         for _, p, s in items:
             _check_parent(p, s)
         if self.engine is None:
@@ -285,7 +376,7 @@ class LayerGraphLP:
                                           for _, p, s in items]) for i, z in zip(gidx, zero)] for side in (0, 1))
             split = torch.tensor([s if p is not None else -1 for _, p, s in items], dtype=torch.int32)
         fixed, prop = self.layers[:-1], [self.layers[-1]] * B
-        res = eng.kw_bounds(fixed, prop, x_lo, x_hi, masks, parents, split)
+        res = eng.kw_bounds(fixed, prop, x_lo, x_hi, masks, parents, split, tighten=tighten)
         glb = [t.cpu() for t in res.lb]
         gub = [t.cpu() for t in res.ub]
         out = []
@@ -306,15 +397,18 @@ class LayerGraphLP:
         return out, res, (fixed, prop, x_lo, x_hi, masks)
 
     # ---- dual ascent on the LP: the host twin of gnnb_dual_ascent ---------------------------
-    def _dual_states(self, bounds, mask):
+    def _dual_states(self, bounds, mask, cone=None):
         """Per ReLU layer (amb, passing, s, t, m) flat: ambiguous = mask -1 and l < 0 < u with the upper relaxation s pre + t,
-        s = u / (u - l), t = -l s; passing = mask 1, or undecided with l >= 0; everything else is blocked."""
+        s = u / (u - l), t = -l s; passing = mask 1, or undecided with l >= 0; everything else is blocked.  ``cone``: per ReLU layer
+        the nodes whose split carries a multiplier (``_tighten_layer``); a split node outside it keeps its state and has no beta."""
         out = []
         for r, i in enumerate(self.pre_relu_indices):
             l, u = bounds[0][i].reshape(-1).double(), bounds[1][i].reshape(-1).double()
             m = mask[r].reshape(-1)
             amb = (m == -1) & (l < 0) & (u > 0)
             passing = (m == 1) | ((m == -1) & (l >= 0))
+            if cone is not None:
+                m = torch.where(cone[r], m, torch.full_like(m, -1))
             out.append((amb, passing) + _relaxation(l, u, amb) + (m,))
         return out
 
@@ -406,7 +500,10 @@ class LayerGraphLP:
 
     def dual_start(self, bounds, mask, alpha=None, beta=None):
         """The entry point of the ascent: alpha = u / (u - l) on ambiguous nodes and beta = 0, or the projection of a given point."""
-        states = self._dual_states(bounds, mask)
+        return self._start(self._dual_states(bounds, mask), alpha, beta)
+
+    @staticmethod
+    def _start(states, alpha, beta):
         m = torch.cat([st[4] for st in states])
         if alpha is None:
             return torch.cat([st[2] for st in states]), torch.zeros(len(m), dtype=torch.float64)
@@ -417,16 +514,23 @@ class LayerGraphLP:
         bias corrections from running products), after each a clamp of alpha to [0, 1] and beta to [0, inf), n_iter + 1 evaluations, the
         best kept.  Returns a DualAscentHost: bound, alpha, beta (the best point), values (g of every iterate), grad_alpha / grad_beta (the
         supergradient at the entry point)."""
+        return self._ascent(self._dual_states(bounds, mask), alpha, beta, n_iter, lr)
+
+    def _ascent(self, states, alpha, beta, n_iter, lr, track_lambda=False):
+        """``dual_ascent_host`` on given node states (``_dual_states``).  ``track_lambda``: also fill ``min_lambda`` (``_tighten_layer``'s
+        report; otherwise it stays +inf and nothing is scanned)."""
         with torch.no_grad():
-            states = self._dual_states(bounds, mask)
-            al, be = self.dual_start(bounds, mask, alpha, beta)
+            al, be = self._start(states, alpha, beta)
             ma, va, mb, vb = (torch.zeros_like(al) for _ in range(4))
             b1, b2, eps = 0.9, 0.999, 1e-8
             omb1, omb2 = 1.0 - b1, 1.0 - b2
             b1t = b2t = 1.0
-            best, best_pt, values, g0 = None, None, [], None
+            best, best_pt, values, g0, tiny = None, None, [], None, float("inf")
             for it in range(n_iter + 1):
                 g, lams, lam0 = self._dual_backward(states, al, be)
+                if track_lambda:
+                    mags = torch.cat(lams + [lam0]).abs()
+                    tiny = min(tiny, float(mags[mags > 0].min()) if bool((mags > 0).any()) else tiny)
                 g = float(g)
                 values.append(g)
                 if best is None or g > best:
@@ -444,7 +548,7 @@ class LayerGraphLP:
                 mb, vb = b1 * mb + omb1 * gb, b2 * vb + omb2 * (gb * gb)
                 al = (al + lr * ((ma / (1.0 - b1t)) / ((va / (1.0 - b2t)).sqrt() + eps))).clamp(0, 1)
                 be = (be + lr * ((mb / (1.0 - b1t)) / ((vb / (1.0 - b2t)).sqrt() + eps))).clamp(min=0)
-            return DualAscentHost(best, best_pt[0], best_pt[1], values, g0[0], g0[1])
+            return DualAscentHost(best, best_pt[0], best_pt[1], values, g0[0], g0[1], tiny)
 
     def dual_recover(self, bounds, mask, alpha, beta):
         """The scorer's inputs at (alpha, beta), fp64, as k_dual_ascent's recovery pass writes them in fp32: dict with x_lp, per ReLU
@@ -467,9 +571,10 @@ class LayerGraphLP:
         _check_parent(parent, split_layer)
         if self.bound_mode == "interval":
             return self.interval_bounds(mask)
+        tighten = self.tighten_root if parent is None else 0
         if self.bound_mode == "kw_device":
-            return self.kw_device_bounds([(mask, parent, split_layer)])[0]
-        return self.kw_bounds(mask, parent, split_layer)
+            return self._kw_device([(mask, parent, split_layer)], tighten)[0][0]
+        return self.kw_bounds(mask, parent, split_layer, tighten=tighten)
 
     # ---- the LP -----------------------------------------------------------------------------
     def solve(self, mask, parent=None, split_layer=None):

@@ -196,6 +196,31 @@ size_t gnnb_kw_workspace_bytes(const gnnb_t* h, int B);
 int gnnb_kw_bounds(gnnb_t* h, const gnnb_kw_batch* in, int B, double* const* lb, double* const* ub, float* const* lb32, float* const* ub32,
                    int32_t* infeasible, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gnnb_kw_bounds with the bounds of every ambiguous node (mask -1, l < 0 < u) of graph layers 2..L tightened by dual ascent, fp64
+ * (restated on the host by LayerGraphLP.kw_bounds(tighten=n)).  Layers go in order.  Behind the Wong-Kolter pass
+ * of a layer, its bounds are met with gnnb_kw_bounds' own (computed first, into the workspace), then every node that is still ambiguous
+ * runs, for its lower and for its upper bound, n_iter steps of gnnb_dual_ascent's recursion (projected Adam, step lr, n_iter + 1
+ * evaluations, the best kept; start alpha = u / (u - l), beta = 0) on the network cut off below the layer with +e_j / -e_j in place of
+ * the property row; beta is free on the split nodes of the node's receptive field.  The layer's mask, relaxation and fp32 copies are
+ * then redone from the tightened bounds before the layer above reads them.  Layers a child copies from its parent are not touched; layer
+ * 1 is exact and the property layer is gnnb_dual_ascent's.  No bound is looser than gnnb_kw_bounds'; n_iter = 0 launches what
+ * gnnb_kw_bounds launches and equals it bit for bit.  A domain's bounds do not depend on B or on its place in the batch. */
+
+/* Bytes of device workspace gnnb_kw_tighten needs for a batch of B besides gnnb_kw_bounds' (0 for a null or unbound handle): per
+ * domain R flag bytes, 2 R + 2 (N_1 + .. + N_L + 1) doubles of the plain chain, and for the layers whose per-node state (7 n + n_0
+ * doubles, n / n_0: the nodes / inputs of the node's receptive field) does not fit in LDS behind the two lambda buffers, the largest
+ * N_k (7 n + n_0). */
+size_t gnnb_kw_tighten_workspace_bytes(const gnnb_t* h, int B);
+
+/* in, lb, ub, lb32, ub32, infeasible, kw_workspace: gnnb_kw_bounds' arguments, with its checks.  counts: NULL, or device (B, 2) int32:
+ * per domain the nodes the ascent ran for and how many of them it decided (no longer l < 0 < u).  Stream-ordered, no allocation, no
+ * synchronisation; the workspaces need no initialisation.  Refused before any launch: GNNB_E_INVALID for a null handle or argument,
+ * B < 1, n_iter < 0, lr not a positive finite number or a network whose widest ReLU layer exceeds 4096 nodes; GNNB_E_STATE before
+ * gnnb_bind_network; GNNB_E_NOMEM for a short workspace. */
+int gnnb_kw_tighten(gnnb_t* h, const gnnb_kw_batch* in, int B, int n_iter, double lr, double* const* lb, double* const* ub,
+                    float* const* lb32, float* const* ub32, int32_t* infeasible, int32_t* counts, void* kw_workspace,
+                    size_t kw_workspace_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Lower bounds of B BaB domains by dual ascent on their LP relaxation, fp64 -- stands in for the LP the reference builds and solves
  * with Gurobi (plnn/conv_kwinter_gen.py:179-555: build_the_model, its optimum and the primal / dual point GraphChoice.decision reads)
  * wherever the optimum is wanted to a few digits; restated on the host by gnn_branching_amd/lp_producer.py LayerGraphLP.dual_value /
