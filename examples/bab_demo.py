@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--threshold 0.2 --online 5 | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -14,7 +14,9 @@ takes one Adam step over its learn rows on the device.  With --props N it
 verifies N properties in one frontier (frontier.verify_properties): the image of seed --seed + j // 9 against the j % 9-th class other than
 the true one, every round's launches serving all the properties in flight; one verdict line per property.  --props N with --threshold T runs
 the fall-back for every property (frontier.verify_properties_threshold): each has its own intercept counter and table of
-inefficient points, and one round bounds the second pairs of all the properties' selected parents together.  --witness (with --frontier)
+inefficient points, and one round bounds the second pairs of all the properties' selected parents together.  --props N with --threshold T
+--online M learns online over all of them (frontier.verify_properties_online): every property has its own table of
+wrong GNN points, and a round takes ONE Adam step over the learn rows of all the properties in flight, which share the GNN.  --witness (with --frontier)
 also returns the input point the upper bound belongs to -- the counter-example, when the verdict is one -- and prints the network's value
 at it; --pgd N lowers every child's upper bound by up to N projected gradient steps on the network from its LP point (DESIGN.md section 7.8);
 --restarts R with --pgd N also descends from R uniform points of every child's box and keeps the least value (section 7.9; --pgd 0: the points alone).
@@ -82,7 +84,7 @@ def main():
     ap.add_argument("--replay-batch", type=int, default=None, metavar="B", help="with --replay C: entries per step (default 8, 256 at most)")
     ap.add_argument("--replay-steps", type=int, default=None, metavar="S", help="with --replay C: steps per learning round (default 1; 0: collect only)")
     ap.add_argument("--repack", default=None, choices=("host", "device"),
-                    help="with --frontier K and --online N or --imitate N, one property: where the scorer's packs are rebuilt after a learning step "
+                    help="with --frontier K and --online N (also with --props) or --imitate N (one property): where the scorer's packs are rebuilt after a learning step "
                          "(device: on the stream, the step does not wait; DESIGN.md section 7.15)")
     args = ap.parse_args()
     if args.imitate is not None and (args.frontier is None or args.imitate < 1 or args.branching == "babsr" or args.threshold is not None
@@ -103,8 +105,9 @@ def main():
         from gnn_branching_amd.frontier import Replay
         imitate = Replay(every=args.imitate, capacity=args.replay, batch=min(args.replay, 8) if args.replay_batch is None else args.replay_batch,
                          steps=1 if args.replay_steps is None else args.replay_steps)
-    if args.repack is not None and (args.frontier is None or args.props is not None or (args.online is None and args.imitate is None)):
-        ap.error("--repack needs --frontier K with --online N or --imitate N, and one property (no --props)")
+    if args.repack is not None and (args.frontier is None or (args.props is not None and args.online is None) or
+                                    (args.online is None and args.imitate is None)):
+        ap.error("--repack needs --frontier K with --online N or --imitate N, and one property (no --props) unless it is --online N")
     if args.branching is not None and args.frontier is None:
         ap.error("--branching needs --frontier K (--babsr is the host loop's BaBSR)")
     if args.branching == "babsr" and (args.threshold is not None or args.online is not None):
@@ -137,14 +140,14 @@ def main():
         return f"; network value at the witness {float(act.reshape(())):.5f}"
     if args.props is not None and (args.frontier is None or args.props < 1):
         ap.error("--props N needs --frontier K and N >= 1")
-    if args.online is not None and (args.frontier is None or args.threshold is None or args.props is not None or args.online < 1):
-        ap.error("--online N needs --frontier K --threshold T, N >= 1, and no --props (the jobs of one pool share one GNN)")
+    if args.online is not None and (args.frontier is None or args.threshold is None or args.online < 1):
+        ap.error("--online N needs --frontier K --threshold T and N >= 1")
 
     def verdict_of(glb, gub):
         return "property holds" if glb >= 0 else ("counter-example found" if gub < 0 else "undecided within the node budget")
     if args.props is not None:
-        from gnn_branching_amd.frontier import (FrontierJob, FrontierJobs, verify_properties, verify_properties_babsr, verify_properties_strong,
-                                                verify_properties_threshold)
+        from gnn_branching_amd.frontier import (FrontierJob, FrontierJobs, verify_properties, verify_properties_babsr, verify_properties_online,
+                                                verify_properties_strong, verify_properties_threshold)
         wrong, jobs, names = [c for c in range(10) if c != 3], [], []
         for j in range(args.props):
             seed, cls = args.seed + j // 9, wrong[j % 9]
@@ -153,9 +156,10 @@ def main():
             jobs.append(FrontierJob(x - args.eps, x + args.eps, prop[-1], 0.0))
             names.append(f"seed {seed} class 3 vs {cls}")
         lp = lp_producer.LayerGraphLP(prop, x - args.eps, x + args.eps, bounds="kw_device")
-        if args.imitate is not None:                             # the properties of a pool share the GNN that learns
+        learns = args.imitate is not None or args.online is not None
+        if learns:                                               # the properties of a pool share the GNN that learns
             from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice
-        choice = (GraphChoice if args.imitate is None else OnlineGraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
+        choice = (OnlineGraphChoice if learns else GraphChoice)([torch.zeros(int(np.prod(lp.shapes[i + 1]))) for i in lp.pre_relu_indices], CKPT)
         max_rounds, stats, learned = max(1, args.nodes // (2 * args.frontier)), [], {}
         if branching == "strong" or args.imitate is not None:
             margin = {} if args.imitate_margin is None else {"imitate_margin": args.imitate_margin}
@@ -166,6 +170,10 @@ def main():
             results = verify_properties_babsr(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
         elif args.threshold is None:
             results = verify_properties(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), K=args.frontier, max_rounds=max_rounds, log=lambda s: None)
+        elif args.online is not None:
+            results = verify_properties_online(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), args.threshold, args.online,
+                                               K=args.frontier, max_rounds=max_rounds, log=lambda s: None, stats=stats, learned=learned,
+                                               **({} if args.repack is None else {"repack": args.repack}))
         else:
             results = verify_properties_threshold(choice, prop[:-1], FrontierJobs(jobs, **upper, tighten_root=args.tighten), args.threshold, K=args.frontier, max_rounds=max_rounds, log=lambda s: None,
                                                   stats=stats)
@@ -173,11 +181,15 @@ def main():
             kw = ""
             if stats and "kw_bounded" in stats[j]:
                 kw = f"; {stats[j]['kw_bounded']} of {stats[j]['branches']} parents bounded a KW decision, {stats[j]['kw_used']} kept it"
+                if "online_rows" in stats[j]:
+                    kw += f", {stats[j]['online_rows']} learn rows"
             if stats and "strong_bounded" in stats[j]:
                 kw = f"; {stats[j]['branches']} branches by {branching}, {stats[j]['strong_bounded']} candidate children bounded"
             if args.witness:
                 kw += witness_of(upper["witness"][j], prop[:-1], jobs[j].prop_layer)
             print(f"{name}: after {rounds} rounds ({bounded} domains bounded, stopped on: {reason}{kw}): lb {glb:.5f} ub {gub:.5f} -> {verdict_of(glb, gub)}")
+        if args.online is not None:
+            print(f"{learned['online_steps']} learning steps over {learned['online_rows']} learn rows in {learned['rounds']} rounds of the pool")
         if args.imitate is not None:
             print(f"{learned['imitation_steps']} imitation steps over {learned['imitation_rows']} parent rows in {learned['rounds']} rounds of the pool")
             if args.replay is not None:

@@ -150,6 +150,9 @@ SYMBOLS = [
     ("gnnb_strong_pick", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_void_p]),
     ("gnnb_strong_rows_jobs", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]),
     ("gnnb_frontier_learn", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]),
+    ("gnnb_frontier_learn_jobs_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("gnnb_frontier_learn_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5 +
+     [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_witness", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gnnb_frontier_witness_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_int, C.c_void_p, C.POINTER(Children), C.POINTER(WitnessSrc), C.c_void_p,
                                              C.c_void_p, C.c_void_p]),

@@ -2531,6 +2531,56 @@ extern "C" int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decision
   return run.rc;
 }
 
+// ---- the learn rows of every job of a many-jobs online round: the walk above per plan entry on the segment's
+// table wrong[segment]; the learn rows of all entries form one dense list in plan order ----
+struct FrLearnWs { size_t st_kw, st_imp, n_stage, total; };              // byte offsets in gnnb_frontier_learn_jobs' workspace: the staged rows at 0
+static FrLearnWs fr_learn_ws_layout(int n) {
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  FrLearnWs w;
+  w.st_kw = up((size_t)n * sizeof(int32_t));
+  w.st_imp = w.st_kw + up((size_t)n * sizeof(int32_t));
+  w.n_stage = w.st_imp + up((size_t)n * sizeof(float));
+  w.total = w.n_stage + up((size_t)n * sizeof(int32_t));                 // (an entry holds at least one row: n_entries <= n)
+  return w;
+}
+
+extern "C" size_t gnnb_frontier_learn_jobs_workspace_bytes(const gnnb_t* h, int n) {
+  if (!h || !h->bound || n < 1) return 0;
+  return fr_learn_ws_layout(n).total;
+}
+
+extern "C" int gnnb_frontier_learn_jobs(gnnb_t* h, const gnnb_plan* plan, const int32_t* gnn_decisions, const int32_t* kw_decisions,
+                                        const int32_t* used_kw, const double* gnn_improvement, const double* kw_improvement, int online_threshold,
+                                        int32_t* wrong, int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* learn_entry,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "gnnb_frontier_learn_jobs";
+  FrLearnSelArgs sel{};
+  const int ng = h && h->bound ? h->kw_net.L + 2 : 0;
+  if (int rc = fr_plan(h, who, plan, &ng, &sel.j)) return rc;
+  if (online_threshold < 1) return fail(GNNB_E_INVALID, "%s: online_threshold = %d (>= 1)", who, online_threshold);
+  if (!gnn_decisions || !kw_decisions || !used_kw || !gnn_improvement || !kw_improvement || !wrong || !learn_rows || !learn_kw || !learn_imp ||
+      !learn_entry || !workspace)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  const int n = sel.j.n;
+  const FrLearnWs ws = fr_learn_ws_layout(n);
+  if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
+  char* w = (char*)workspace;
+  int32_t* n_stage = (int32_t*)(w + ws.n_stage);
+  FrLearnArgs a{};
+  a.s = fr_shape(h);
+  a.K = n; a.gnn_dec = gnn_decisions; a.kw_dec = kw_decisions; a.used = used_kw; a.gnn_imp = gnn_improvement; a.kw_imp = kw_improvement;
+  a.online_threshold = online_threshold;
+  a.wrong = wrong; a.learn_rows = (int32_t*)w; a.learn_kw = (int32_t*)(w + ws.st_kw); a.learn_imp = (float*)(w + ws.st_imp); a.n_learn = nullptr;
+  sel.n_stage = n_stage; sel.st_rows = a.learn_rows; sel.st_kw = a.learn_kw; sel.st_imp = a.learn_imp;
+  sel.learn_rows = learn_rows; sel.learn_kw = learn_kw; sel.learn_imp = learn_imp; sel.learn_entry = learn_entry;
+  const FrPlan j = sel.j;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_LEARN, [&] { hipLaunchKernelGGL(k_frontier_learn_jobs, dim3(j.n_entries), dim3(64), 0, st, a, j, n_stage); });
+  run.run(PC_FR_LEARN, [&] { hipLaunchKernelGGL(k_frontier_learn_compact, dim3(1), dim3(FR_THREADS), 0, st, sel); });
+  return run.rc;
+}
+
 // ---- the witness of the upper bound (reference plnn/branch_and_bound.py:157 global_ub_point) ----
 // The checks gnnb_frontier_witness and gnnb_frontier_witness_jobs share on the children and a gnnb_witness_src over n parents, m of them selected.
 static int fr_witness_in(const gnnb_t* h, const char* who, int n, int m, const gnnb_children* ch, const gnnb_witness_src* src, double* best_value,

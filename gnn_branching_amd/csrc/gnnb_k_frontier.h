@@ -1,7 +1,7 @@
 // gnnb_k_frontier.h -- the per-round steps of a branch-and-bound loop whose open domains stay in device memory:
 // gnnb_frontier_gather, gnnb_frontier_expand, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
 // a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, their many-job form of section 7.6, and the selection
-// of the rows an online round learns from, section 7.7: gnnb_frontier_learn; the witness of the upper bound, section 7.8:
+// of the rows an online round learns from, section 7.7: gnnb_frontier_learn, per job of a pool, section 7.19: gnnb_frontier_learn_jobs; the witness of the upper bound, section 7.8:
 // gnnb_frontier_witness; and BaBSR alone in the GNN's place, section 7.10: gnnb_frontier_babsr_decide).  Between them run the existing
 // batch kernels (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched, and
 // the network's value at a round's points: gnnb_net_eval or the descent that can take its place, gnnb_net_descend (gnnb_k_net.h).
@@ -682,12 +682,16 @@ __device__ __forceinline__ int fr_staged(const FrSelArgs& a, int e, int* row0) {
   return min(max(a.m_stage[e], 0), k);
 }
 
-__global__ __launch_bounds__(FR_THREADS) void k_frontier_select_jobs(FrSelArgs a) {
-  __shared__ int cnt[FR_THREADS + 1];
-  const int tid = threadIdx.x, E = a.j.n_entries;
+// The compaction k_frontier_select_jobs and k_frontier_learn_compact (section 7.19) share, for ONE workgroup of FR_THREADS threads: entry e
+// staged `staged(e, &row0)` items at rows [row0, row0 + that) of its staging lists; count_entry receives the counts and, last, their sum
+// (at most n), and `copy(p, d)` moves staged item p to place d of the dense lists, d the exclusive prefix sum in plan order.  Each thread
+// owns a contiguous run of entries; the FR_THREADS partial sums are added by one thread in a fixed order.  cnt: FR_THREADS + 1 ints of LDS.
+template <class Staged, class Copy>
+__device__ __forceinline__ void fr_compact_entries(int E, int n, int32_t* count_entry, int* cnt, Staged staged, Copy copy) {
+  const int tid = threadIdx.x;
   const int per = (E + FR_THREADS - 1) / FR_THREADS, e0 = min(tid * per, E), e1 = min(e0 + per, E);
   int row0, sum = 0;
-  for (int e = e0; e < e1; ++e) sum += fr_staged(a, e, &row0);
+  for (int e = e0; e < e1; ++e) sum += staged(e, &row0);
   cnt[tid + 1] = sum;
   if (tid == 0) cnt[0] = 0;
   __syncthreads();
@@ -696,16 +700,21 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_select_jobs(FrSelArgs a
   __syncthreads();
   int q = cnt[tid];
   for (int e = e0; e < e1; ++e) {
-    const int m = fr_staged(a, e, &row0);
-    a.m_entry[e] = m;
-    for (int i = 0; i < m && q + i < a.j.n; ++i) {
-      const int p = row0 + i, d = q + i;
-      a.sel_rows[d] = a.st_rows[p]; a.sel_slots[d] = a.st_slots[p];
-      a.sel_dec[2L * d] = a.st_dec[2L * p]; a.sel_dec[2L * d + 1] = a.st_dec[2L * p + 1];
-    }
+    const int m = staged(e, &row0);
+    count_entry[e] = m;
+    for (int i = 0; i < m && q + i < n; ++i) copy(row0 + i, q + i);
     q += m;
   }
-  if (tid == 0) a.m_entry[E] = min(cnt[FR_THREADS], a.j.n);
+  if (tid == 0) count_entry[E] = min(cnt[FR_THREADS], n);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_select_jobs(FrSelArgs a) {
+  __shared__ int cnt[FR_THREADS + 1];
+  fr_compact_entries(a.j.n_entries, a.j.n, a.m_entry, cnt, [&](int e, int* row0) { return fr_staged(a, e, row0); },
+                     [&](int p, int d) {
+                       a.sel_rows[d] = a.st_rows[p]; a.sel_slots[d] = a.st_slots[p];
+                       a.sel_dec[2L * d] = a.st_dec[2L * p]; a.sel_dec[2L * d + 1] = a.st_dec[2L * p + 1];
+                     });
 }
 
 // The box and property row of segment `seg` into row c of a set of child rows: N_0 doubles twice, N_L floats, one float, over the FR_SPLIT
@@ -793,21 +802,72 @@ struct FrLearnArgs {
 };
 static_assert(sizeof(FrLearnArgs) <= 4096, "kernel arguments: 4 KiB");
 
-__global__ __launch_bounds__(64) void k_frontier_learn(FrLearnArgs a) {
+// What one job's walk sees: its rows [row0, row0 + k) of the round, the first place out0 of the lists it writes, its table and its count.
+struct FrLearnView {
+  int row0, k, out0;
+  int32_t* wrong; int32_t* count;
+};
+
+__device__ __forceinline__ void fr_learn_walk(const FrLearnArgs& a, const FrLearnView& v) {
   if (threadIdx.x != 0) return;
   int n = 0;
-  for (int i = 0; i < a.K; ++i) {
-    if (!a.used[i]) continue;
+  for (int i = 0; i < v.k; ++i) {
+    const int row = v.row0 + i;
+    if (!a.used[row]) continue;
     int gnn, kw;
-    if (!fr_node(a.s, a.gnn_dec[2L * i], a.gnn_dec[2L * i + 1], &gnn) || !fr_node(a.s, a.kw_dec[2L * i], a.kw_dec[2L * i + 1], &kw)) continue;
-    const int count = a.wrong[gnn] + 1;
-    a.wrong[gnn] = count;
+    if (!fr_node(a.s, a.gnn_dec[2L * row], a.gnn_dec[2L * row + 1], &gnn) || !fr_node(a.s, a.kw_dec[2L * row], a.kw_dec[2L * row + 1], &kw)) continue;
+    const int count = v.wrong[gnn] + 1;
+    v.wrong[gnn] = count;
     if (count < a.online_threshold) continue;
-    a.learn_rows[n] = i; a.learn_kw[n] = kw;
-    a.learn_imp[n] = a.kw_imp[i] - a.gnn_imp[i] > 0.1 ? 1.0f : 0.0f;                 // :203-206, strictly greater
+    const int q = v.out0 + n;
+    a.learn_rows[q] = row; a.learn_kw[q] = kw;
+    a.learn_imp[q] = a.kw_imp[row] - a.gnn_imp[row] > 0.1 ? 1.0f : 0.0f;             // :203-206, strictly greater
     ++n;
   }
-  *a.n_learn = n;
+  *v.count = n;
+}
+
+__global__ __launch_bounds__(64) void k_frontier_learn(FrLearnArgs a) {
+  const FrLearnView v{0, a.K, 0, a.wrong, a.n_learn};
+  fr_learn_walk(a, v);
+}
+
+// ---- the learn rows of every job of a many-jobs online round ------------------------------------------------
+// The walk above per plan entry {segment, row0, k}, against the segment's own table wrong[segment] (the reference builds one GraphChoice,
+// and with it one wrong_pts_dc, per property):
+//
+//   * k_frontier_learn_jobs     one workgroup per entry, thread 0 walking the entry's rows (fr_learn_walk).  The learn rows -- GLOBAL row
+//                               numbers row0 + i -- go to STAGING lists at the entry's own rows [row0, row0 + n_e), their number to
+//                               n_stage[entry]: no entry needs another's count.
+//   * k_frontier_learn_compact  ONE workgroup: fr_compact_entries, k_frontier_select_jobs' scheme -- learn_entry = {n_e per entry, N = their
+//                               sum} and entry e's staged slice to its place in the dense lists, in plan order.  Entries of the dense
+//                               lists from N on are not written.
+//
+// Both launch under k_frontier_learn's profile class.  In FrLearnArgs the lists are the staging lists, K is n and wrong is (S, R).
+
+struct FrLearnSelArgs {
+  FrPlan j;
+  const int32_t* n_stage; const int32_t* st_rows; const int32_t* st_kw; const float* st_imp;     // staging: (n_entries), (n), (n), (n)
+  int32_t* learn_rows; int32_t* learn_kw; float* learn_imp; int32_t* learn_entry;                // (n), (n), (n), (n_entries + 1)
+};
+static_assert(sizeof(FrLearnArgs) + sizeof(FrPlan) + sizeof(int32_t*) <= 4096 && sizeof(FrLearnSelArgs) <= 4096, "kernel arguments: 4 KiB");
+
+__global__ __launch_bounds__(64) void k_frontier_learn_jobs(FrLearnArgs a, FrPlan j, int32_t* n_stage) {
+  int seg, row0, k;
+  if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
+  const FrLearnView v{row0, k, row0, a.wrong + (long)seg * a.s.R, n_stage + blockIdx.x};
+  fr_learn_walk(a, v);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_learn_compact(FrLearnSelArgs a) {
+  __shared__ int cnt[FR_THREADS + 1];
+  fr_compact_entries(a.j.n_entries, a.j.n, a.learn_entry, cnt,
+                     [&](int e, int* row0) {                // n_e as the walk staged it (0 for an entry the host would have refused)
+                       int seg, k;
+                       if (!fr_entry(a.j, e, &seg, row0, &k)) return 0;
+                       return min(max(a.n_stage[e], 0), k);
+                     },
+                     [&](int p, int d) { a.learn_rows[d] = a.st_rows[p]; a.learn_kw[d] = a.st_kw[p]; a.learn_imp[d] = a.st_imp[p]; });
 }
 
 // ---- the witness of the upper bound -------------------------------------------------------------------------

@@ -1538,6 +1538,25 @@ class ScorerEngine:
                    self._rows(ineff, S, self.R, i32, "ineff").data_ptr(), self._rows(kw_improvement, n, 1, torch.float64, "kw_improvement").data_ptr(),
                    self._rows(used_kw, n, 1, i32, "used_kw").data_ptr(), self._rows(decisions, n, 2, i32, "decisions").data_ptr())
 
+    def frontier_learn_jobs(self, plan, gnn_decisions, kw_decisions, used_kw, gnn_improvement, kw_improvement, online_threshold, wrong, learn_rows,
+                            learn_kw, learn_imp, learn_entry, workspace=None):
+        """gnnb_frontier_learn_jobs on the current stream, behind ``frontier_choose_jobs``: ``frontier_learn`` per
+        plan entry on its rows with its segment's table wrong[segment] ((segments, R) int32).  The learn rows of all entries form one dense
+        list in plan order -- learn_rows (GLOBAL rows of the n-row parent batch), learn_kw (n,) int32, learn_imp (n,) fp32 -- and
+        learn_entry (n_entries + 1,) int32 receives the count per entry, then their sum N."""
+        if self.sizes is None:
+            raise RuntimeError("bind a network first")
+        pl, n, S, E = self._plan(plan), max(int(plan.n), 0), max(int(plan.segments), 0), max(int(plan.n_entries), 0)
+        i32, f64 = torch.int32, torch.float64
+        ws = self._workspace("learn_jobs", max(n, 1), "gnnb_frontier_learn_jobs_workspace_bytes") if workspace is None else workspace
+        self._call("gnnb_frontier_learn_jobs", C.byref(pl), self._rows(gnn_decisions, n, 2, i32, "gnn_decisions").data_ptr(),
+                   self._rows(kw_decisions, n, 2, i32, "kw_decisions").data_ptr(), self._rows(used_kw, n, 1, i32, "used_kw").data_ptr(),
+                   self._rows(gnn_improvement, n, 1, f64, "gnn_improvement").data_ptr(),
+                   self._rows(kw_improvement, n, 1, f64, "kw_improvement").data_ptr(), int(online_threshold),
+                   self._rows(wrong, S, self.R, i32, "wrong").data_ptr(), self._rows(learn_rows, n, 1, i32, "learn_rows").data_ptr(),
+                   self._rows(learn_kw, n, 1, i32, "learn_kw").data_ptr(), self._rows(learn_imp, n, 1, torch.float32, "learn_imp").data_ptr(),
+                   self._rows(learn_entry, E + 1, 1, i32, "learn_entry").data_ptr(), ws.data_ptr(), ws.numel())
+
     def frontier_witness_jobs(self, plan, children, x_a, best_value, best_point, M=0, m_entry=None, x_b=None, used_kw=None, sel_rows=None):
         """gnnb_frontier_witness_jobs on the current stream: ``frontier_witness`` per plan entry on its rows of ``children`` (2n rows) and
         its range of the dense lists (M, m_entry: ``frontier_fallback_jobs``'), with best_value[segment] ((segments,) fp64) and

@@ -17,6 +17,8 @@ its segment a job runs the rule above unchanged, so it gets the result ``branch_
 ``branch_and_bound_frontier(..., branching_threshold=T, online_threshold=N)`` is the reference's online loop
 (``lp_producer.branch_and_bound_online``) on the same round: a parent whose KW pair won counts its GNN decision as a wrong point, from the
 N-th time on it is a learn row, and behind the commit the round takes one Adam step over its learn rows on the device.
+``verify_properties_online`` runs that loop for many jobs in one pool: a wrong-point table per job
+(``gnnb_frontier_learn_jobs``) and ONE step per round over the learn rows of all jobs in flight, which share the scorer.
 
 ``branch_and_bound_frontier(..., branching="babsr")`` and ``verify_properties_babsr`` are the reference's
 ``relu_bab`` on the same round: every parent is split at the BaBSR heuristic's decision (``gnnb_babsr``, ``gnnb_frontier_babsr_decide``), one
@@ -560,6 +562,8 @@ class _Round:
     strong_G, cand_src = 0, None    # (section 7.14: the scorer's count of a ``Shortlist`` and the union's sources; off unless a run sets them)
     repack, pending_step = "host", None      # (section 7.15: "device" where a run asks for it; the step whose status has not been read yet)
     replay, last_replay = None, None         # (section 7.16: the ``Replay`` of a run whose ``imitate`` is one; what its last learning round did)
+    online, learn_pending = None, False      # (sections 7.7 and 7.19: the online threshold of a run that learns online; a selection not yet read)
+    last_learn = online_steps = online_rows = 0      # (the learn rows of the last round that read them; the steps of the run and their rows)
     tighten_root = 0                         # (section 7.18: iterations of gnnb_kw_tighten on the roots' intermediate bounds; 0: gnnb_kw_bounds)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
@@ -638,8 +642,8 @@ class _Round:
             fill(p["kept"])
 
     def _refusal(self):
-        """What status bit 3 of the run's learning step means: the imitation step's text, or the online step's (``FrontierRun._raise_for``
-        words the same refusal for a run that reads it at its end)."""
+        """What status bit 3 of the run's learning step means: the imitation step's text, or the online step's (``_raise_for`` raises the
+        same text for a run that reads it at its end)."""
         if self.imitate is None:
             return "gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask"
         return ("gnnb_imitation_step_rows refused a row (status bit 3): its table names a candidate that is no undecided node of the "
@@ -972,10 +976,38 @@ class _Round:
         self._raise_for(int(self.status_all.cpu()[0]))
 
     def _raise_for(self, st):
-        if st & 8 and self.imitate is not None:
+        if st & 8 and (self.imitate is not None or self.online is not None):      # (bit 3 is a learning step's: the imitation step's, or the online step's)
             raise RuntimeError(_Round._refusal(self))
         from .engine import _raise_for_status
         _raise_for_status(st)
+
+    def _online_buffers(self, n_parents, tables, counts):
+        """The online mode's state for rounds of up to n_parents parent rows (DESIGN.md sections 7.7 and 7.19).  tables: the shape of
+        ``wrong``, the wrong-point table(s) -- (R,) for one job, (segments, R) for a pool; counts: the length of ``learn_count``, the count
+        array a round with M > 0 reads behind the state record (1: n_learn; segments + 1: learn_entry).  The dense lists of a round's learn
+        rows, what the step reports per learn row, and the step's status word."""
+        dev, n, i32, f32 = self.eng.device, n_parents, torch.int32, torch.float32
+        self.wrong = torch.zeros(tables, dtype=i32, device=dev)
+        self.learn_rows, self.learn_kw, self.learn_count = (torch.zeros(c, dtype=i32, device=dev) for c in (n, n, counts))
+        self.learn_imp, self.loss = torch.zeros(n, dtype=f32, device=dev), torch.zeros(n, dtype=f32, device=dev)
+        self.step_status = torch.zeros(1, dtype=i32, device=dev)
+
+    def _learn(self):
+        """The learning half of an online round with M > 0 (DESIGN.md sections 7.7 and 7.19), behind the commit and the read of the state
+        record: the read of the count array (``read_learn``: 4 bytes of n_learn in a one-job run, 4 (entries + 1) bytes of learn_entry in a
+        pool) and, with N > 0 learn rows, ONE step over them on the parent rows' scorer inputs, which the round's gather and
+        gnnb_dual_ascent(n_iter 0) left in ``P`` (intact until the next gather).  ``k``: the parent rows of the round (of all its entries,
+        in a many-jobs run), which the learn rows are rows of.  The next round's forward scores with the new parameters."""
+        self.learn_pending = False
+        n = self.last_learn = self.read_learn()
+        if n == 0:
+            return
+        self.step_status.zero_()
+        self.eng.online_step_rows(self.P.fwd_batch, self.k, self.learn_rows[:n], self.learn_kw[:n], self.learn_imp[:n], loss=self.loss[:n],
+                                  status=self.step_status)
+        self.status_all |= self.step_status
+        self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
+        self._step_issued(("learn_rows", "learn_kw", "learn_imp"))
 
     def _imitate(self):
         """The learning half of a learning round, behind the commit and the read of the state record.  When the
@@ -1081,12 +1113,9 @@ class FrontierRun(_Round):
             self._babsr_buffers(K, (1,))
         if self.strong_on:                                        # the candidates' rows: the run's one box and property, 2 * strong_chunk times
             self._strong_buffers(K, tuple(t[:1].expand(2 * strong_chunk, *t.shape[1:]).contiguous() for t in (self.x_lo, self.x_hi, self.pw, self.pb)))
-        self.learn_pending, self.last_learn, self.online_steps, self.online_rows = False, 0, 0, 0
-        if self.online is not None:
-            self.wrong = torch.zeros(eng.R, dtype=torch.int32, device=dev)
-            self.learn_rows, self.learn_kw, self.n_learn = (torch.zeros(n, dtype=torch.int32, device=dev) for n in (K, K, 1))
-            self.learn_imp, self.loss = torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, dtype=torch.float32, device=dev)
-            self.step_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.online is not None:                               # one table for the run's one job, one count: n_learn
+            self._online_buffers(K, (eng.R,), 1)
+            self.n_learn = self.learn_count
         self._imitation_buffers(K)
         self._use_repack()                                        # last: nothing behind it can fail and leave the engine in the run's mode
 
@@ -1157,29 +1186,9 @@ class FrontierRun(_Round):
             return None
         return self.best_point[0].cpu().reshape(self.in_shape)
 
-    def _learn(self):
-        """The learning half of an online round with m > 0, behind the commit and the read of the state record: the read of n_learn
-        (4 bytes) and, with n_learn > 0, ONE step over the learn rows on the parent rows' scorer inputs, which the round's gather and
-        gnnb_dual_ascent(n_iter 0) left in ``P`` (intact until the next gather).  The next round's forward scores with the new parameters."""
-        self.learn_pending = False
-        n = self.last_learn = self.read_learn()
-        if n == 0:
-            return
-        self.step_status.zero_()
-        self.eng.online_step_rows(self.P.fwd_batch, self.k, self.learn_rows[:n], self.learn_kw[:n], self.learn_imp[:n], loss=self.loss[:n],
-                                  status=self.step_status)
-        self.status_all |= self.step_status
-        self.online_steps, self.online_rows = self.online_steps + 1, self.online_rows + n
-        self._step_issued(("learn_rows", "learn_kw", "learn_imp"))
-
     def read_learn(self):
         """n_learn, the number of learn rows: the 4 bytes an online round with m > 0 reads behind the state record."""
         return int(self.n_learn.cpu()[0])
-
-    def _raise_for(self, st):
-        if st & 8 and self.imitate is None:
-            raise RuntimeError("gnnb_online_step_rows refused a learn row (status bit 3): its KW decision names no undecided node of the row's mask")
-        super()._raise_for(st)
 
     def read_selected(self):
         """m, the number of parents whose KW decision gets bounded: the 4 bytes a threshold round reads between its halves."""
@@ -1524,6 +1533,24 @@ def _online_trace(run, st, t=None):
     else:
         out.update(step_part({"learn_rows": run.learn_rows, "learn_kw": run.learn_kw, "learn_imp": run.learn_imp}))
     return out
+
+
+def _online_entry_trace(run, t, e, row0, st):
+    """``_online_trace`` for entry number ``e`` of a many-jobs round, into the entry's dict ``t``: the entry's
+    slice of the dense lists -- it starts at the sum of the counts of the entries before it (``learn_e``), and "learn_rows" count from
+    the entry's first row ``row0``, as "selected" does -- and the bounds of the entry's record ``st``.  Behind a step that was only issued
+    the four keys arrive with the next round's records, from the copies ``_step_issued`` kept."""
+    a = sum(run.learn_e[:e])
+    b = a + run.learn_e[e]
+    t.update(global_lb=_global_lb(st), global_ub=st[_lib.FS_GLOBAL_UB])
+
+    def fill(kept):
+        t.update(learn_rows=[r - row0 for r in kept["learn_rows"][a:b].cpu().tolist()], learn_kw=kept["learn_kw"][a:b].cpu().tolist(),
+                 learn_improve=kept["learn_imp"][a:b].cpu().tolist(), loss=run.loss[a:b].cpu().tolist())
+    if run.pending_step is not None and run.learn_e[-1]:
+        run.pending_step["fill"].append(fill)
+    else:
+        fill({"learn_rows": run.learn_rows, "learn_kw": run.learn_kw, "learn_imp": run.learn_imp})
 
 
 def _threshold_trace(run, k, e=0, row0=0):
@@ -1900,6 +1927,68 @@ class StrongJobsRun(JobsRun):
         return st
 
 
+class OnlineJobsRun(JobsRun):
+    """The device side of ``verify_properties_online``: ``JobsRun`` in threshold mode with section 7.7's online
+    learning per job.  Every segment owns a wrong-point table ``wrong[segment]`` ((R,) int32, zero when its job is admitted); behind the
+    choice ``gnnb_frontier_learn_jobs`` selects the learn rows per plan entry into ONE dense list over all jobs, and a round with M > 0
+    reads ``learn_entry`` (4 (entries + 1) bytes) behind the records and, with N > 0, takes ONE ``gnnb_online_step_rows`` over the learn
+    rows of all jobs in flight, which share the scorer.  The constructor takes ``JobsRun``'s parameters, then ``online_threshold`` and
+    ``repack``; ``kwbd_threshold`` stays at its default (the online loop has no table of inefficient KW points: the run uses KWBD_NEVER)."""
+
+    def __init__(self, choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps, branching_threshold=None, kwbd_threshold=KWBD_DEFAULT,
+                 sparsest_layer=0, decision_threshold=0.001, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None,
+                 pgd_seed=0, branching="gnn", online_threshold=None, repack="host"):
+        if online_threshold is None:
+            raise ValueError("online_threshold = None: an integer >= 1 (JobsRun runs the jobs without online learning)")
+        self._set_options(choice, branching=branching, branching_threshold=branching_threshold, kwbd_threshold=kwbd_threshold, sparsest_layer=sparsest_layer,
+                          decision_threshold=decision_threshold, online_threshold=online_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step,
+                          pgd_restarts=pgd_restarts, pgd_seed=pgd_seed, repack=repack)
+        self._make(choice, fixed_layers, jobs, in_shape, K, segments, cap, n_iter, lr, eps)      # (``JobsRun``'s, on the options set here)
+        n = segments * K
+        self._online_buffers(n, (segments, self.eng.R), segments + 1)      # one table per segment; the count array is learn_entry
+        self.learn_entry, self.learn_e = self.learn_count, [0]
+        self.ws_learn = self._ws("gnnb_frontier_learn_jobs_workspace_bytes", n)
+
+    def admit(self, seg, job):
+        """``JobsRun.admit``; the job starts with its own table of wrong points: zero, device-side."""
+        super().admit(seg, job)
+        self.wrong[seg].zero_()
+
+    def launch_round(self, entries):
+        self.learn_e, self.last_learn = [0] * (len(entries) + 1), 0      # (a round with M = 0 selects nothing and reads nothing)
+        super().launch_round(entries)
+
+    def _choose(self, n, M):
+        """``JobsRun._choose``, then the learn rows of every entry (section 7.19): read behind the records."""
+        super()._choose(n, M)
+        self.eng.frontier_learn_jobs(self.plan, self.P.dec, self.kw_dec, self.used_kw, self.gnn_imp, self.kw_imp, self.online, self.wrong,
+                                     self.learn_rows, self.learn_kw, self.learn_imp, self.learn_entry, workspace=self.ws_learn)
+        self.learn_pending = True
+
+    def read_learn(self):
+        """The learn rows per plan entry, then their sum N: the 4 (entries + 1) bytes an online round with M > 0 reads behind the records
+        (``learn_e`` keeps the list)."""
+        self.learn_e = self.learn_entry[:self.plan.n_entries + 1].cpu().tolist()
+        return self.learn_e[-1]
+
+    def _learn(self):
+        try:
+            super()._learn()
+        except RuntimeError as e:                                 # (GNNB_E_NOMEM: the step's buffers grow with the rows of a round)
+            if "(-4)" not in str(e):
+                raise
+            raise RuntimeError(f"the online step over {self.last_learn} learn rows of the {self.k} parent rows of a round found no device memory: "
+                               f"lower segments or K (segments * K = {self.S * self.K} rows at most per step)") from e
+
+    def read_state(self):
+        """``JobsRun.read_state``; an online round with M > 0 then reads learn_entry and takes its learning step (``_learn``)."""
+        st = super().read_state()
+        self._settle_step()                                       # ("device" mode: the previous round's step, read behind these records)
+        if self.learn_pending:
+            self._learn()
+        return st
+
+
 class FrontierJobs(list):
     """A list of ``FrontierJob`` together with the upper-bound options of the run that verifies them: how
     ``verify_properties`` and ``verify_properties_threshold`` take ``branch_and_bound_frontier``'s witness, pgd_steps and pgd_step.  (Their
@@ -2038,16 +2127,65 @@ def verify_properties_strong(choice, fixed_layers, jobs, K=16, segments=None, ca
     return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, learned, tighten_root)
 
 
+def verify_properties_online(choice, fixed_layers, jobs, branching_threshold, online_threshold, K=16, segments=None, capacity=None, n_iter=20, lr=0.1,
+                             eps=1e-4, max_rounds=50, sparsest_layer=0, decision_threshold=0.001, repack="host", log=print, trace=None, stats=None,
+                             learned=None):
+    """``verify_properties_threshold`` with the reference's online learning for every job: the many-jobs form of
+    ``branch_and_bound_frontier(..., branching_threshold=T, online_threshold=N)``.  A round is the threshold round with
+    ``kwbd_threshold = 2**31 - 1`` (the online loop has no table of inefficient KW points, so the function takes no ``kwbd_threshold``:
+    every parent with a KW decision gets its second pair bounded) plus section 7.7's learning per job.
+
+    Every job has its own table of wrong GNN points (the reference builds one ``GraphChoice``, and with it one ``wrong_pts_dc``, per
+    property), zero when it is admitted, read and updated in the job's parent row order within a round and carried from round to round:
+    a parent that took its KW pair counts its GNN decision, and from the ``online_threshold``-th count of a node on it is a learn row
+    (``gnnb_frontier_learn_jobs``).  The learn rows of all jobs form ONE dense list in plan-entry order.  Commit first, then learn: a round
+    with M > 0 selected parents reads one more array behind the records -- the learn rows per plan entry and their sum N, 4 (entries + 1)
+    bytes -- and with N > 0 ONE ``gnnb_online_step_rows`` takes an Adam step on the summed loss of the learn rows of all jobs, all scored
+    with the round's opening parameters; the next round of every job scores with the new ones.  A round with M = 0 launches and reads
+    nothing new.
+
+    The jobs of a pool share ONE scorer: from the run's first step on a job's result depends on what else is in flight (which rows shared
+    its steps, and when it was admitted); before that step, and in a run that never learns, it does not, and every job gets the result
+    ``branch_and_bound_frontier(..., branching_threshold=T, online_threshold=N)`` gives it alone.  ``choice`` must be a
+    ``graphnet.graph_score_online.GraphChoice``; when the run ends (or raises) after a step ``choice.model`` receives the device's
+    parameters.  repack: ``branch_and_bound_frontier``'s (section 7.15): with "device" the step is only issued, and its status and traced
+    losses are read with the next round's records.  A step that finds no device memory raises a RuntimeError that says to lower
+    ``segments`` or ``K``.
+
+    stats: None, or a list that receives per job, in job order, the threshold mode's dict plus "online_rows", the learn rows that were
+    the job's.  learned: None, or a dict that receives "online_steps", "online_rows" and "rounds" (launched) of the run.  trace:
+    ``verify_properties_threshold``'s keys per round and per entry plus the entry's slice of the lists -- "learn_rows" (counted from the
+    entry's first row, as "selected"), "learn_kw", "learn_improve", "loss" -- and the entry's "global_lb" / "global_ub" after the round.
+    A ``FrontierJobs`` carries the witness and descent options, as for ``verify_properties``.
+
+    Returns a list, in job order, of (global_lb, global_ub, rounds, domains_bounded, reason)."""
+    options, tighten_root = _options_of(jobs), _tighten_of(jobs)
+    _check_tighten(tighten_root)                                 # (before the run touches a device, as every option)
+    jobs, S, cap, in_shape = _check_jobs_args(jobs, K, segments, capacity, n_iter, lr, eps, max_rounds)
+    if branching_threshold is None:
+        raise ValueError("branching_threshold = None: a number with 0 < branching_threshold <= 1 (verify_properties runs without the fall-back)")
+    _check_threshold(branching_threshold, KWBD_DEFAULT)
+    if online_threshold is None:
+        raise ValueError("online_threshold = None: an integer >= 1 (verify_properties_threshold runs without online learning)")
+    _check_online(online_threshold, branching_threshold, KWBD_DEFAULT, choice)
+    _check_repack(repack)
+    if learned is not None and not isinstance(learned, dict):
+        raise ValueError(f"learned = {learned!r}: None, or a dict that receives the run's learning counts")
+    run = OnlineJobsRun(choice, fixed_layers, jobs, in_shape, K, S, cap, n_iter, lr, eps, branching_threshold=branching_threshold,
+                        sparsest_layer=sparsest_layer, decision_threshold=decision_threshold, online_threshold=online_threshold, repack=repack, **options)
+    return _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats, learned, tighten_root)
+
+
 def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=None, tighten_root=0):
-    """``_jobs_loop`` on a checked run, for ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr`` and
-    ``verify_properties_strong``; when the run ends (or raises) after a learning step, ``choice.model`` receives the device's parameters.
+    """``_jobs_loop`` on a checked run, for ``verify_properties``, ``verify_properties_threshold``, ``verify_properties_babsr``,
+    ``verify_properties_strong`` and ``verify_properties_online``; when the run ends (or raises) after a learning step, ``choice.model`` receives the device's parameters.
     tighten_root: the ``FrontierJobs``' (``_tighten_of``)."""
     run.keep_pairs = trace is not None
     try:
         run.set_tighten_root(tighten_root)
         return _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned)
     finally:
-        if run.imitation_steps:                                   # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it
+        if run.imitation_steps or getattr(run, "online_steps", 0):             # the nn.Module mirrors the device, as branch_and_bound_frontier leaves it
             choice.model.load_blob(run.eng.get_weights())
         run.close()
 
@@ -2055,10 +2193,12 @@ def _verify_jobs(run, choice, jobs, max_rounds, log, trace, stats=None, learned=
 def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):
     """``_verify_jobs``' loop on its run, which knows the rest: K, the segments and their capacity, eps, and what is on -- ``threshold``
     (a round has a second half, and stats are the threshold mode's), ``branching`` and ``strong_on`` (theirs), ``witness_on``.  stats:
-    None, or the list that receives per job the mode's part of its tally; learned: None, or the dict that receives the run's
-    "imitation_steps", "imitation_rows" and launched "rounds"."""
+    None, or the list that receives per job the mode's part of its tally (in an online run, section 7.19, the threshold mode's plus
+    "online_rows", the job's learn rows summed from ``learn_e``); learned: None, or the dict that receives the run's "imitation_steps",
+    "imitation_rows" and launched "rounds" (an online run's: "online_steps", "online_rows", "rounds")."""
     F, K, S, cap, thr = _lib, run.K, run.S, run.cap, run.threshold is not None
     results, tally = [None] * len(jobs), [None] * len(jobs)
+    online, online_rows = getattr(run, "online", None) is not None, [0] * len(jobs)      # (section 7.19: the learn rows that were each job's)
     seg_job, rec, capacity_stop = [None] * S, [None] * S, [False] * S
     waiting = list(range(len(jobs)))
 
@@ -2112,11 +2252,15 @@ def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):
         st = run.read_state()
         if trace is not None:
             values = _witness_values(run)
-            for (s, row0, k), t in zip(entries, traced):
+            for e, ((s, row0, k), t) in enumerate(zip(entries, traced)):
+                if online:
+                    _online_entry_trace(run, t, e, row0, st[s])
                 _report_read(run, t, s, row0, k, st[s], values)
         for e, (s, _, k) in enumerate(entries):
             j = seg_job[s]
             rec[s] = st[s]
+            if online:
+                online_rows[j] += run.learn_e[e]
             _check_record(rec[s])
             _tally_entry(run, tally[j], e, k, rec[s])
             log(f"job {j} round {tally[j]['rounds']} picked {k} kept {int(rec[s][F.FS_KEPT])} closed {int(rec[s][F.FS_CLOSED])} "
@@ -2127,11 +2271,14 @@ def _jobs_loop(run, jobs, max_rounds, log, trace, stats, learned):
         run.witness_to.extend(None if math.isinf(results[j][1]) else points[j].reshape(run.in_shape) for j in range(len(jobs)))
     if stats is not None and thr:
         used = run.job_used.cpu().tolist()
-        stats.extend({**{key: t[key] for key in ("branches", "kw_bounded", "domains_bounded")}, "kw_used": int(used[j])} for j, t in enumerate(tally))
+        stats.extend({**{key: t[key] for key in ("branches", "kw_bounded", "domains_bounded")}, "kw_used": int(used[j]),
+                      **({"online_rows": online_rows[j]} if online else {})} for j, t in enumerate(tally))
     elif stats is not None:                                       # BaBSR: the first two; a run with a table: all three
         keys = ("branches", "domains_bounded", "strong_bounded")[:3 if run.strong_on else 2]
         stats.extend({key: t[key] for key in keys} for t in tally)
-    if learned is not None:
+    if learned is not None and online:
+        learned.update(online_steps=run.online_steps, online_rows=run.online_rows, rounds=run.round)
+    elif learned is not None:
         learned.update(imitation_steps=run.imitation_steps, imitation_rows=run.imitation_rows, rounds=run.round)
         if run.replay is not None:
             learned.update(replay_stored=run.replay_stored, replay_skipped=run.replay_skipped, replay_filled=run.replay_filled)

@@ -660,6 +660,23 @@ int gnnb_frontier_learn(gnnb_t* h, int K, const int32_t* gnn_decisions, const in
                         const double* gnn_improvement, const double* kw_improvement, int online_threshold, int32_t* wrong,
                         int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* n_learn, void* stream);
 
+/* ---- online learning for every job of a many-jobs round ----
+ * gnnb_frontier_learn per plan entry {segment, row0, k}, after gnnb_frontier_choose_jobs: on the entry's rows [row0, row0 + k), in row order,
+ * exactly the walk above against the segment's own table wrong[segment] (wrong: device (segments, R) int32; a segment's row is zero when
+ * its job is admitted).  The learn rows of all entries form ONE dense list, in plan-entry order and within an entry in row order:
+ * learn_rows holds GLOBAL row numbers (row0 + i, rows of the n-row parent batch), learn_kw and learn_imp as above (device (n) each), and
+ * learn_entry (device (n_entries + 1) int32) the count of every entry followed by their sum N.  Entries of the lists from N on are not
+ * written.  An entry's slice and its table do not depend on the other entries, their number or their order.  workspace: at least
+ * gnnb_frontier_learn_jobs_workspace_bytes(h, n) bytes (0 for a null or unbound handle or n < 1), the entries' staging lists.
+ * Stream-ordered, no allocation, no synchronisation, no atomics, no workgroup waits on another.  Before any launch: GNNB_E_INVALID for
+ * everything the plan checks refuse (a null plan, no entry, n outside 1..32767, a null handle, entries that do not tile the rows),
+ * online_threshold < 1 or a null argument, GNNB_E_NOMEM for a short workspace, GNNB_E_STATE before gnnb_bind_network. */
+size_t gnnb_frontier_learn_jobs_workspace_bytes(const gnnb_t* h, int n);
+int gnnb_frontier_learn_jobs(gnnb_t* h, const gnnb_plan* plan, const int32_t* gnn_decisions, const int32_t* kw_decisions,
+                             const int32_t* used_kw, const double* gnn_improvement, const double* kw_improvement, int online_threshold,
+                             int32_t* wrong, int32_t* learn_rows, int32_t* learn_kw, float* learn_imp, int32_t* learn_entry, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- the witness of the upper bound ----
  * Every loop of the reference returns global_ub_point next to global_ub (plnn/branch_and_bound.py:157, plnn/relu_conv_gnnkwthreshold.py:
  * 209-214 and :268, plnn/relu_conv_online.py:225-228 and :276; experiments/bab_mip.py:50 stores it).  gnnb_frontier_witness keeps that point
