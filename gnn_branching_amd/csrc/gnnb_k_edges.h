@@ -426,9 +426,12 @@ typedef unsigned short top_idx_t;      // live-row lists of k_top: 16-bit (layer
 // TS (4 / 2 / 1): row tiles this workgroup computes, t0 .. t0 + TS - 1 (k_top_split: a sample's rows spread over 4 / TS workgroups by
 // OUTPUT tile, every sum in the order of the unsplit kernel -- the results do not depend on the split); the weight load narrows
 // with it (16 / 8 / 4 bytes per lane and list entry).
-template <int TS, class Store1>
+// tail() runs once between the k-loop and the first phase of the reduction: the registers of x, A and the operand pieces are dead
+// there, so what the caller requests from memory in it travels under the reduction's four phases.
+struct NoHook { __device__ void operator()() const {} };
+template <int TS, class Store1, class Tail = NoHook>
 __device__ __forceinline__ void dense_fwd_sample_bf3(const DenseLArgs& a, int b, float* scratch, float* spart, Store1 store,
-                                                     const top_idx_t* klist, int K_eff, float* s_fin, int t0 = 0) {
+                                                     const top_idx_t* klist, int K_eff, float* s_fin, int t0 = 0, Tail tail = Tail()) {
   const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int Kw = klist ? K_eff : a.K;
@@ -543,6 +546,7 @@ __device__ __forceinline__ void dense_fwd_sample_bf3(const DenseLArgs& a, int b,
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  tail();
   // ---- the 8 partial sums of every tile meet in LDS, two tiles per phase; every wave adds up a quarter of a tile in wave order
   // (phase p: row tile t0 + p % TS ... the pair (row tile, channel tile 0 / 1): the same two tiles, the same order, for every TS)
   float (*sc)[2][16][64] = reinterpret_cast<float (*)[2][16][64]>(scratch);
@@ -596,7 +600,6 @@ __device__ __forceinline__ void dense_fwd_sample_bf3(const DenseLArgs& a, int b,
 // the rows the plain form stores.  node(arow, in_range) is called when a tile starts (it requests what the node's chain needs from
 // memory), epi(arow, in_range, X, s, what node() returned) when its MFMAs are done; mid() runs once behind the barrier that ends the
 // image build (Cr is dead from there on).  `store` is unused.
-struct NoHook { __device__ void operator()() const {} };
 // k_top keeps the rows of layer L in LDS as C[row][64]: a row is 64 banks, and the update phases put node 4 j + t on lane j, so the 16
 // lanes of a ds_read_b128 group all hit the same four banks (F2 + B1: 1.1 M conflict cycles per launch, profiles/r04_k_top_lds_conflicts_by_phase.txt).
 // The column index of row n is therefore XOR-ed with 4 ((n >> 2) & 15): 16-byte pieces stay whole, the 16 lanes of a group spread over
@@ -828,7 +831,10 @@ struct TopArgs {
   float* sb_out;            // (B, K) bias-sum scalars of the transposed edge written by B2 (its live-row walk), or null (k_livesum has them)
   const float *lb, *ub;     // bounds of layer L, flat (B*N)
   const float *lbm, *ubm;   // bounds of layer L-1, flat (B*K): its dead rows (all zero) are skipped by the forward edge
-  const float *prop_w, *prop_b, *lbK, *ubK, *z_out;
+  // (the second half of the block starts on a 64-byte line: the scalar loads of the arguments then group so that the kernel keeps fewer of
+  // them alive -- k_top<4> 26 scalar spills with it, 42 without, the parent 28: profiles/top_roundtrips_ab.txt section 2)
+  alignas(64) const float* prop_w;
+  const float *prop_b, *lbK, *ubK, *z_out;
   float* mu_prop;           // (B, 64)
   float* mu;                // (B, N, 64) rows of layer L (backward-produced)
   int* status;
@@ -843,7 +849,10 @@ struct TopArgs {
 #define TOP_A_FLOATS (PackUpd::FLOATS > DENSE_FWD_LDS_FLOATS ? PackUpd::FLOATS : DENSE_FWD_LDS_FLOATS)
 #define TOP_FIXED_FLOATS (TOP_A_FLOATS + PackProp::FLOATS + DENSE_BWD_ROWS * 64 + 8 * 64 + 128 + 64 + 64)
 #define TOP_LDS_FLOATS 40960                   // all 160 KB: what the fixed regions leave holds the live-row lists
-#define TOP_K2_INTS (128 + 48)                  // spare
+#define TOP_K2_INTS (128 + 48)                  // small words behind `spart`: await()'s flag, W_prop[b]; the rest spare
+#define TOP_K2_FLAG 0                           //   word await() hands its verdict to the workgroup in
+#define TOP_K2_PW 48                            //   [128] W_prop[b] of this sample (floats)
+static_assert(TOP_K2_FLAG < TOP_K2_PW && TOP_K2_PW + 128 <= TOP_K2_INTS, "k_top: the small words do not overlap");
 #define TOP_LIST_INTS (TOP_LDS_FLOATS - TOP_FIXED_FLOATS - TOP_K2_INTS)
 // the live-row list of layer L-1 (16-bit entries): behind the fixed regions when it fits (then the transposed edge walks only
 // live rows too), else in the region PackProp takes after F1, else the edge walks every row
@@ -894,6 +903,7 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
   const int N = a.N;
   FT_DECL;
   for (int i = tid; i < DENSE_BWD_ROWS * 16; i += 512) reinterpret_cast<f32x4*>(Cr)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* pw = a.prop_w + (long)b * N;
   // live source rows of layer L-1 (the dead ones are all zero: ~45 % of the forward edge's k-steps), compacted in node order.
   // The list goes behind the fixed regions when it fits there (then the transposed edge B2 also uses it, to compute only the
   // live rows of layer L-1), else into the region PackProp takes after F1.
@@ -927,13 +937,24 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
 #if defined(TOP_STOP) && TOP_STOP == 1     // dev, timing only (TOP_STOP = 1 / 2 / 3: leave before F1 / after F1 / before B2)
   if (a.N > 0) return;
 #endif
+  // What F3, B1 and B2 want of layer L's bounds and of the property weights is requested once, between F1's k-loop and its reduction (the
+  // registers of the loop are dead there, the reduction's four phases cover the round trip), with thread `tid` on node `tid` (N <= 128).
+  // Behind F1 the weights W_prop[b] go to LDS (F3's partial sums and B1's rank-1 edge read them there), the liveness of the nodes stays
+  // as the wave's ballot (B2's bias sums), and sp = sum_n W_prop[n] live_n lies in `spart` long before F3 adds it up.
+  float lbt = 0.0f, ubt = 0.0f, pwt = 0.0f;
+  auto request = [&]() {
+    if (tid < N) {
+      const long gt = (long)b * N + tid;
+      lbt = a.lb[gt]; ubt = a.ub[gt]; pwt = pw[tid];
+    }
+  };
   // ---- F1: this workgroup's rows of C <- W_L . mu_{L-1}
   const bool own_s = compact && !a.sf;                    // the bias sums of the forward edge come out of F1's own walk (-> xs)
 #if defined(TOP_ABL) && (TOP_ABL & 2)     // dev, timing only: no F1
   if (K_eff < 0)
 #endif
   dense_fwd_sample_bf3<TS>(a.df, b, A, part_, [&](int row, int ch, float v) { Cr[row * 64 + (ch ^ csw(row))] = v; }, compact ? klist : nullptr, K_eff,
-                           own_s ? xs : nullptr, t0);
+                           own_s ? xs : nullptr, t0, request);
 #if defined(TOP_STOP) && TOP_STOP == 2
   if (a.N > 0) { if (Cr[tid] == 12345.0f) a.mu_prop[0] = 1.0f; return; }      // (dev stop: any read of C keeps F1 alive)
 #endif
@@ -944,10 +965,20 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
   const bool upd_wave = wave < 4 && wave >= t0 && wave < t0 + TS && wave < N;
   const bool valid = upd_wave && n < N;
   const long g = (long)b * N + (valid ? n : 0);
-  const float* pw = a.prop_w + (long)b * N;
   const float s_own = (own_s && valid) ? xs[n] : 0.0f;      // (xs is rewritten in F3, behind a barrier)
   Ratio r{};
   if (upd_wave) r = compute_ratio(a.lb[g], a.ub[g]);
+  float* pwl = spart + 8 + TOP_K2_PW;          // [128] W_prop[b], in the small words
+  const bool lvt = tid < N && node_is_live(lbt, ubt);
+  const unsigned long long liveL = __ballot(lvt);       // (bit l: node 64 wave + l)
+  {
+    float sp = 0.0f;
+    if (tid < N) sp += lvt ? pwt : 0.0f;       // (0.0f + x as the sum over m = tid, tid + 512, ... had it: N <= 128)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sp += __shfl_xor(sp, o);
+    if (lane == 0) spart[wave] = sp;
+    if (tid < 128) pwl[tid] = pwt;             // (read behind the barrier that ends the staging)
+  }
   auto load_row = [&](Frag& x_, int row) {       // fragment <- row of C in LDS (columns swizzled: csw)
     const float* p = Cr + row * 64;
     const int sw = csw(row);
@@ -1004,7 +1035,7 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
     if (tid == 0) __hip_atomic_fetch_add(a.xflag + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   auto await = [&](int target) -> bool {
-    int* okp = reinterpret_cast<int*>(spart + 8);      // (first of the TOP_K2_INTS spare words)
+    int* okp = reinterpret_cast<int*>(spart + 8) + TOP_K2_FLAG;
     if (tid == 0) {
       int ok = 0;
       for (int it = 0; it < TOP_POLL_CAP; ++it) {
@@ -1047,7 +1078,27 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
   if (a.N > 0) return;
 #endif
   FT_MARK(2);        // staging the forward pack
-  if (wave >= 4) prefetch_b();
+  const float* Pp = a.pack_p;                 // the property node's weights (PackProp, 51 KB) come straight from L2
+  // F3's operands are sample constants and weights: waves 4..7, which only hold the backward image through F2, request them beside it
+  // and take the hidden layer's k-split (wave 4 + q: rows 32 q ..); waves 0..3 request their rows of the last layer behind the chain,
+  // two barriers ahead of their use.  (An `else`: nothing of this is live in the chain's registers.)
+  float w3r[8], w2r[32], w1r[4], f[4], b1r = 0.0f, v2r = 0.0f, b2r = 0.0f, b3r = 0.0f;
+  auto request_w3 = [&]() {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w3r[q] = Pp[PackProp::W3T + (8 * wave + q) * 64 + lane];
+    if (wave == 0) b3r = Pp[PackProp::B3 + lane];
+  };
+  if (wave >= 4) {
+    prefetch_b();
+    request_w3();
+#pragma unroll
+    for (int q = 0; q < 32; ++q) w2r[q] = Pp[PackProp::W2T + (32 * (wave - 4) + q) * 64 + lane];
+    f[0] = a.lbK[b]; f[1] = a.ubK[b]; f[2] = a.z_out[b]; f[3] = a.prop_b[b];
+    b1r = Pp[PackProp::B1 + lane];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w1r[k] = Pp[PackProp::W1T + k * 64 + lane];
+    if (wave == 4) { v2r = Pp[PackProp::V2 + lane]; b2r = Pp[PackProp::B2 + lane]; }
+  } else
   if (upd_wave) {
     Frag X, E;
     load_row(X, valid ? n : 0);
@@ -1057,6 +1108,7 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
       store_row(E, Cr + n * 64, csw(n));
     }
   }
+  if (wave < 4) request_w3();                  // (used behind the second barrier of F3)
   __syncthreads();
   if (wave >= 4) commit_b();                   // (nothing reads the image again before the barriers of F3)
 #if defined(TOP_STOP) && TOP_STOP == 6
@@ -1065,24 +1117,16 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
   FT_MARK(3);        // F2 chain
 
   // ---- F3: property node (k_prop).  Wave w sums W_prop[m] . row m over m = w, w + 8, ... (one row tile: w % 4), the 8 partial
-  // vectors are added in wave order; its three small layers are split over the waves by k (every weight row is requested at
-  // once: one L2 round trip per layer instead of a serial 196-step chain on one wave).
+  // vectors are added in wave order; its three small layers are split over the waves by k (the hidden layer over waves 4..7, the
+  // last one over all eight; every weight row was requested during F2, instead of a serial 196-step chain on one wave).
   {
     const bool mine = (wave & 3) >= t0 && (wave & 3) < t0 + TS;
     if (mine) {
       float acc = 0.0f;
-      for (int m = wave; m < N; m += 8) acc = fmaf(pw[m], Cr[m * 64 + (lane ^ csw(m))], acc);
+      for (int m = wave; m < N; m += 8) acc = fmaf(pwl[m], Cr[m * 64 + (lane ^ csw(m))], acc);
       if (S == 1) part_[wave * 64 + lane] = acc;
       else __hip_atomic_store(a.xbuf + ((long)b * 8 + wave) * 64 + lane, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    float sp = 0.0f;
-    for (int m = tid; m < N; m += 512) {
-      const long gm = (long)b * N + m;
-      sp += node_is_live(a.lb[gm], a.ub[gm]) ? pw[m] : 0.0f;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sp += __shfl_xor(sp, o);
-    if (lane == 0) spart[wave] = sp;
   }
   if (S > 1) {
     arrive();
@@ -1090,36 +1134,29 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
     part_[wave * 64 + lane] = __hip_atomic_load(a.xbuf + ((long)b * 8 + wave) * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
-  const float* Pp = a.pack_p;                 // the property node's weights (PackProp, 51 KB) come straight from L2
-  float w3r[8];                                // this wave's 8 rows of the last layer, requested now
-#pragma unroll
-  for (int q = 0; q < 8; ++q) w3r[q] = Pp[PackProp::W3T + (8 * wave + q) * 64 + lane];
-  if (wave < 4) {
-    float w2r[32];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) w2r[q] = Pp[PackProp::W2T + (32 * wave + q) * 64 + lane];
+  if (wave >= 4) {
+    const int wq = wave - 4;
     float nbv = 0.0f, spt = 0.0f;
 #pragma unroll
     for (int w8 = 0; w8 < 8; ++w8) { nbv += part_[w8 * 64 + lane]; spt += spart[w8]; }
-    const float f[4] = {a.lbK[b], a.ubK[b], a.z_out[b], a.prop_b[b]};
-    float h1 = Pp[PackProp::B1 + lane];
+    float h1 = b1r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) h1 = fmaf(Pp[PackProp::W1T + k * 64 + lane], f[k], h1);
+    for (int k = 0; k < 4; ++k) h1 = fmaf(w1r[k], f[k], h1);
     // element k of the hidden layer's input [relu(h1), nb] is held by lane k % 64: through LDS (every wave writes the same values)
     xs[lane] = relu_nan(h1);
     xs[64 + lane] = nbv;
     __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0): this wave's LDS writes are visible to its own reads
-    float h2 = wave == 0 ? fmaf(spt, Pp[PackProp::V2 + lane], Pp[PackProp::B2 + lane]) : 0.0f;
+    float h2 = wq == 0 ? fmaf(spt, v2r, b2r) : 0.0f;
 #pragma unroll
-    for (int q = 0; q < 32; ++q) h2 = fmaf(w2r[q], xs[32 * wave + q], h2);
-    part2[wave * 64 + lane] = h2;
+    for (int q = 0; q < 32; ++q) h2 = fmaf(w2r[q], xs[32 * wq + q], h2);
+    part2[wq * 64 + lane] = h2;
   }
   __syncthreads();
   {
     const float h2 = ((part2[lane] + part2[64 + lane]) + part2[128 + lane]) + part2[192 + lane];
     xs[lane] = relu_nan(h2);                           // (every wave writes the same values)
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    float o = wave == 0 ? Pp[PackProp::B3 + lane] : 0.0f;
+    float o = b3r;
 #pragma unroll
     for (int q = 0; q < 8; ++q) o = fmaf(w3r[q], xs[8 * wave + q], o);
     part3[wave * 64 + lane] = o;
@@ -1141,7 +1178,7 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
   // ---- B1: backward node update of layer L; its aggregate is the rank-1 edge from the property node
   if (upd_wave) {
     Frag X, E;
-    const float wn = valid ? pw[n] : 0.0f;
+    const float wn = valid ? pwl[n] : 0.0f;
     {
       const f32x4* o4 = reinterpret_cast<const f32x4*>(outv + 4 * h);
 #pragma unroll
@@ -1167,10 +1204,7 @@ __device__ __forceinline__ void top_sample(const TopArgs& a, const int b, const 
     }
   }
   // which rows of C count for B2's bias sums (xs: free since F3): the live nodes of layer L
-  if (tid < 128) {
-    const long gm = (long)b * N + (tid < N ? tid : 0);
-    xs[tid] = (tid < N && node_is_live(a.lb[gm], a.ub[gm])) ? 1.0f : 0.0f;
-  }
+  if (tid < 128) xs[tid] = (((h ? (unsigned)(liveL >> 32) : (unsigned)liveL) >> j) & 1u) ? 1.0f : 0.0f;      // (32-bit halves: no 64-bit lane index kept)
   if (S > 1) {
     arrive();                                          // this workgroup's rows of layer L are in a.mu
     if (!await(a.xbase + 2 * S)) return;
