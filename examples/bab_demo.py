@@ -1,6 +1,6 @@
 """Branch-and-bound on one robustness property with the MI355X scorer and the Gurobi-free LP producer.
 
-    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--threshold 0.2 --online 5 | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]]] [--bounds kw_device]
+    python examples/bab_demo.py [--net cifar_base_kw] [--eps 0.03] [--nodes 40] [--babsr | --threshold 0.2 | --frontier 16 [--threshold 0.2 [--online 5] | --branching babsr | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]] [--props 18 [--threshold 0.2 --online 5 | --branching strong [--candidates 16] [--gnn-candidates 4] | --imitate 1 [--imitate-margin 1.0] [--replay 1024 [--replay-batch 8] [--replay-steps 1]] [--candidates 16] [--gnn-candidates 4]]] [--witness] [--pgd 4 [--restarts 16]] [--split-depth 4]] [--bounds kw_device]
 
 --threshold T runs the reference loop's own control flow (relu_conv_gnnkwthreshold.py:150-199): a GNN decision whose improvement of the bound is
 below T makes the loop ask the BaBSR heuristic too (on the device), bound its children and keep the better pair; try --eps 0.09.
@@ -37,6 +37,8 @@ device-resident replay buffer of C slots and takes --replay-steps steps (default
 --props N with --branching strong, or with --imitate N, runs both for every property in one pool (frontier.verify_properties_strong,
 DESIGN.md section 7.13): the candidates of all properties' parents are bounded in the same chunks, and a learning round -- every N-th round
 the run launches -- takes ONE step over the parents of all the properties in flight, which share the GNN.
+--frontier K --split-depth D (one property, the GNN's branching) fills the rounds that have fewer than K parents:
+each parent is split on up to D of its best-scored undecided ReLUs at once, 2^d children per parent on the round's 2K child rows.
 
 Prints the trace of plnn/relu_conv_gnnkwthreshold.py:202 for every branch.  Needs the GPU library (no CPU fallback)."""
 import argparse
@@ -83,6 +85,8 @@ def main():
     ap.add_argument("--replay", type=int, default=None, metavar="C", help="with --imitate N: learn from a device-resident replay buffer of C labelled states")
     ap.add_argument("--replay-batch", type=int, default=None, metavar="B", help="with --replay C: entries per step (default 8, 256 at most)")
     ap.add_argument("--replay-steps", type=int, default=None, metavar="S", help="with --replay C: steps per learning round (default 1; 0: collect only)")
+    ap.add_argument("--split-depth", type=int, default=None, metavar="D",
+                    help="with --frontier K: split each parent of an underfilled round on up to D ReLUs at once (1..8)")
     ap.add_argument("--repack", default=None, choices=("host", "device"),
                     help="with --frontier K and --online N (also with --props) or --imitate N (one property): where the scorer's packs are rebuilt after a learning step "
                          "(device: on the stream, the step does not wait; DESIGN.md section 7.15)")
@@ -118,6 +122,9 @@ def main():
         ap.error("--candidates M needs --branching strong or --imitate N, and M >= 1")
     if args.gnn_candidates is not None and ((args.branching != "strong" and args.imitate is None) or args.gnn_candidates < 1):
         ap.error("--gnn-candidates G needs --branching strong or --imitate N, and G >= 1")
+    if args.split_depth is not None and (args.frontier is None or args.props is not None or not 1 <= args.split_depth <= 8 or args.branching in ("babsr", "strong")
+                                         or args.threshold is not None or args.online is not None or args.imitate is not None):
+        ap.error("--split-depth D needs --frontier K and 1 <= D <= 8, and takes no --props, --branching babsr / strong, --threshold, --online or --imitate")
     branching = args.branching or "gnn"
     candidates = args.candidates
     if args.gnn_candidates is not None:                          # the value of strong_candidates that names both shortlists
@@ -199,7 +206,7 @@ def main():
     x = torch.from_numpy(np.random.RandomState(args.seed).standard_normal((3, 32, 32)).astype(np.float32))
     if args.frontier is not None:
         from gnn_branching_amd.frontier import branch_and_bound_frontier
-        lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device", tighten_root=args.tighten)
+        lp = lp_producer.LayerGraphLP(layers, x - args.eps, x + args.eps, bounds="kw_device", tighten_root=args.tighten, split_depth=args.split_depth)
         learns = args.online is not None or args.imitate is not None
         if learns:
             from gnn_branching_amd.graphnet.graph_score_online import GraphChoice as OnlineGraphChoice

@@ -121,6 +121,12 @@ SYMBOLS = [
     ("gnnb_frontier_commit_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("gnnb_frontier_commit", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.POINTER(Children), C.c_double, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gnnb_frontier_expand_depth", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    ("gnnb_frontier_commit_depth_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    ("gnnb_frontier_commit_depth", C.c_int, [C.c_void_p, C.POINTER(Pool), C.c_void_p, C.c_int, C.c_int, C.POINTER(Children), C.c_double,
+                                             C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gnnb_frontier_pick_jobs", C.c_int, [C.c_void_p, C.POINTER(Pool), C.POINTER(Plan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gnnb_frontier_rows_jobs", C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p] + [C.c_void_p] * 12 + [C.c_void_p]),
     ("gnnb_frontier_commit_jobs_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int]),

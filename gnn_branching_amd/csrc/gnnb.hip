@@ -2035,17 +2035,17 @@ extern "C" int gnnb_net_descend_starts(gnnb_t* h, const float* starts, int n_sta
 }
 
 struct FrWs { size_t undecided, dest, total; };     // byte offsets in gnnb_frontier_commit's workspace: the resolved masks at 0
-static FrWs fr_ws_layout(const gnnb_t* h, int K) {
+static FrWs fr_ws_layout(const gnnb_t* h, int rows) {       // rows: the child rows of the commit (2K; K << depth in a round of section 7.20)
   FrWs w;
-  w.undecided = ((size_t)2 * K * h->R + 255) & ~(size_t)255;
-  w.dest = w.undecided + (((size_t)2 * K * sizeof(int32_t) + 255) & ~(size_t)255);
-  w.total = w.dest + (((size_t)2 * K * sizeof(int32_t) + 255) & ~(size_t)255);
+  w.undecided = ((size_t)rows * h->R + 255) & ~(size_t)255;
+  w.dest = w.undecided + (((size_t)rows * sizeof(int32_t) + 255) & ~(size_t)255);
+  w.total = w.dest + (((size_t)rows * sizeof(int32_t) + 255) & ~(size_t)255);
   return w;
 }
 
 extern "C" size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K) {
   if (!h || !h->bound || K < 1) return 0;
-  return fr_ws_layout(h, K).total;
+  return fr_ws_layout(h, 2 * K).total;
 }
 
 // A gnnb_children / gnnb_children_rw checked against the pool's n_graph, as the kernels' struct of it (lb / ub of graph layer k at [k]).
@@ -2063,16 +2063,16 @@ static int fr_children(const gnnb_t* h, const char* who, const Ch* ch, int n_gra
   return GNNB_OK;
 }
 
-// What gnnb_frontier_commit and gnnb_frontier_commit_jobs share once their own preflight is through: the 2n children of the parents in
-// slots[0..n), checked, then resolve, decide (the caller's launch: one workgroup on the pool, or one per plan entry) and store.
-// plan: null, or the plan whose segments the pool must hold.
+// What gnnb_frontier_commit, gnnb_frontier_commit_jobs and gnnb_frontier_commit_depth share once their own preflight is through: the
+// `rows` children (2n; n << depth) of the parents in slots[0..n), checked, then resolve, decide (the caller's launch: one workgroup on the
+// pool, or one per plan entry) and store.  plan: null, or the plan whose segments the pool must hold.
 template <class Decide>
-static int fr_commit(gnnb_t* h, const char* who, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, int n, const gnnb_children* ch,
-                     double eps, double* state, void* workspace, size_t workspace_bytes, void* stream, Decide decide) {
+static int fr_commit(gnnb_t* h, const char* who, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, int n, int rows,
+                     const gnnb_children* ch, double eps, double* state, void* workspace, size_t workspace_bytes, void* stream, Decide decide) {
   FrCommitArgs a{};
   if (int rc = fr_children(h, who, ch, pool->n_graph, &a.ch)) return rc;
   if (!(eps >= 0.0)) return fail(GNNB_E_INVALID, "%s: eps = %g", who, eps);
-  const FrWs ws = fr_ws_layout(h, n);
+  const FrWs ws = fr_ws_layout(h, rows);
   if (workspace_bytes < ws.total) return fail(GNNB_E_NOMEM, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, ws.total);
   a.s = fr_shape(h);
   if (int rc = plan ? fr_plan_pool(h, who, plan, pool, &a.p) : fr_pool(h, who, pool, &a.p)) return rc;
@@ -2082,9 +2082,9 @@ static int fr_commit(gnnb_t* h, const char* who, const gnnb_pool* pool, const gn
   a.dest = (int32_t*)((char*)workspace + ws.dest);
   hipStream_t st = (hipStream_t)stream;
   Launcher run{h, st};
-  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(2 * n), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_RESOLVE, [&] { hipLaunchKernelGGL(k_frontier_resolve, dim3(rows), dim3(FR_THREADS), 0, st, a); });
   decide(run, st, a);
-  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(2 * n, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  run.run(PC_FR_STORE, [&] { hipLaunchKernelGGL(k_frontier_store, dim3(rows, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
   return run.rc;
 }
 
@@ -2093,10 +2093,58 @@ extern "C" int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int3
   const char* who = "gnnb_frontier_commit";
   if (int rc = frontier_preflight(h, who, K, pool ? &pool->n_graph : nullptr)) return rc;
   if (!slots || !ch || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
-  return fr_commit(h, who, pool, nullptr, slots, K, ch, eps, state, workspace, workspace_bytes, stream,
+  return fr_commit(h, who, pool, nullptr, slots, K, 2 * K, ch, eps, state, workspace, workspace_bytes, stream,
                    [&](Launcher& run, hipStream_t st, FrCommitArgs& a) {
                      a.decision_bound = decision_bound;
                      run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide, dim3(1), dim3(FR_THREADS), 0, st, a); });
+                   });
+}
+
+// ---- several ReLUs per parent while a round is underfilled: C = 2^depth children per parent ----
+static int fr_depth_preflight(const gnnb_t* h, const char* who, int K, int depth, const int* n_graph) {
+  if (depth < 1 || depth > FR_MAX_DEPTH) return fail(GNNB_E_INVALID, "%s: depth = %d outside 1..%d", who, depth, FR_MAX_DEPTH);
+  if (K >= 1 && ((long)K << depth) > 65534)           // (the sizes first: they need no handle.  K < 1: frontier_preflight's)
+    return fail(GNNB_E_INVALID, "%s: K = %d parents at depth %d are %ld child rows, above 65534", who, K, depth, (long)K << depth);
+  return frontier_preflight(h, who, K, n_graph);
+}
+
+extern "C" int gnnb_frontier_expand_depth(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, int depth, const int32_t* cand0,
+                                          const int32_t* cand_dec, int8_t* mask, double* const* parent_lb, double* const* parent_ub,
+                                          int32_t* split_layer, double* alpha, double* beta, int32_t* live, void* stream) {
+  const char* who = "gnnb_frontier_expand_depth";
+  if (int rc = fr_depth_preflight(h, who, K, depth, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !cand0 || !cand_dec || !mask || !parent_lb || !parent_ub || !split_layer || !alpha || !beta || !live)
+    return fail(GNNB_E_INVALID, "%s: null argument", who);
+  FrExpandDepthArgs a{};
+  a.s = fr_shape(h);
+  if (int rc = fr_pool(h, who, pool, &a.p)) return rc;
+  for (int k = 1; k <= a.s.L + 1; ++k) {
+    if (!parent_lb[k - 1] || !parent_ub[k - 1]) return fail(GNNB_E_INVALID, "%s: null output pointer for graph layer %d", who, k);
+    a.ch.lb[k] = parent_lb[k - 1]; a.ch.ub[k] = parent_ub[k - 1];
+  }
+  a.slots = slots; a.cand0 = cand0; a.cand_dec = cand_dec; a.K = K; a.depth = depth;
+  a.ch.mask = mask; a.split = split_layer; a.ch.alpha = alpha; a.ch.beta = beta; a.live = live;
+  hipStream_t st = (hipStream_t)stream;
+  Launcher run{h, st};
+  run.run(PC_FR_EXPAND, [&] { hipLaunchKernelGGL(k_frontier_expand_depth, dim3(K << depth, FR_SPLIT), dim3(FR_THREADS), 0, st, a); });
+  return run.rc;
+}
+
+extern "C" size_t gnnb_frontier_commit_depth_workspace_bytes(const gnnb_t* h, int K, int depth) {
+  if (!h || !h->bound || K < 1 || depth < 1 || depth > FR_MAX_DEPTH || ((long)K << depth) > 65534) return 0;
+  return fr_ws_layout(h, K << depth).total;
+}
+
+extern "C" int gnnb_frontier_commit_depth(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, int depth, const gnnb_children* ch,
+                                          double eps, double decision_bound, double* state, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  const char* who = "gnnb_frontier_commit_depth";
+  if (int rc = fr_depth_preflight(h, who, K, depth, pool ? &pool->n_graph : nullptr)) return rc;
+  if (!slots || !ch || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
+  return fr_commit(h, who, pool, nullptr, slots, K, K << depth, ch, eps, state, workspace, workspace_bytes, stream,
+                   [&](Launcher& run, hipStream_t st, FrCommitArgs& a) {
+                     a.decision_bound = decision_bound;
+                     run.run(PC_FR_DECIDE, [&] { hipLaunchKernelGGL(k_frontier_decide_depth, dim3(1), dim3(FR_THREADS), 0, st, a, depth); });
                    });
 }
 
@@ -2159,7 +2207,7 @@ extern "C" int gnnb_frontier_rows_jobs(gnnb_t* h, const gnnb_plan* plan, const i
 
 extern "C" size_t gnnb_frontier_commit_jobs_workspace_bytes(const gnnb_t* h, int n) {
   if (!h || !h->bound || n < 1) return 0;
-  return fr_ws_layout(h, n).total;
+  return fr_ws_layout(h, 2 * n).total;
 }
 
 extern "C" int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const gnnb_plan* plan, const int32_t* slots, const gnnb_children* ch,
@@ -2169,7 +2217,7 @@ extern "C" int gnnb_frontier_commit_jobs(gnnb_t* h, const gnnb_pool* pool, const
   FrPlan j{};
   if (int rc = fr_plan(h, who, plan, pool ? &pool->n_graph : nullptr, &j)) return rc;
   if (!slots || !ch || !decision_bound || !state || !workspace) return fail(GNNB_E_INVALID, "%s: null argument", who);
-  return fr_commit(h, who, pool, plan, slots, j.n, ch, eps, state, workspace, workspace_bytes, stream,
+  return fr_commit(h, who, pool, plan, slots, j.n, 2 * j.n, ch, eps, state, workspace, workspace_bytes, stream,
                    [&](Launcher& run, hipStream_t st, FrCommitArgs& a) {
                      run.run(PC_FR_DECIDE_JOBS, [&] { hipLaunchKernelGGL(k_frontier_decide_jobs, dim3(j.n_entries), dim3(FR_THREADS), 0, st, a, j, decision_bound); });
                    });

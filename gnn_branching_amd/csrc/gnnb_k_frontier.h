@@ -2,7 +2,8 @@
 // gnnb_frontier_gather, gnnb_frontier_expand, gnnb_frontier_commit (and, at the end of this file, the BaBSR fall-back below
 // a branching threshold of section 7.5: gnnb_frontier_fallback, gnnb_frontier_choose, their many-job form of section 7.6, and the selection
 // of the rows an online round learns from, section 7.7: gnnb_frontier_learn, per job of a pool, section 7.19: gnnb_frontier_learn_jobs; the witness of the upper bound, section 7.8:
-// gnnb_frontier_witness; and BaBSR alone in the GNN's place, section 7.10: gnnb_frontier_babsr_decide).  Between them run the existing
+// gnnb_frontier_witness; BaBSR alone in the GNN's place, section 7.10: gnnb_frontier_babsr_decide; and a round that splits each parent on
+// several ReLUs, section 7.20: gnnb_frontier_expand_depth, gnnb_frontier_commit_depth).  Between them run the existing
 // batch kernels (gnnb_dual_ascent at n_iter = 0 for the scorer's inputs, gnnb_forward, gnnb_kw_bounds, gnnb_dual_ascent), untouched, and
 // the network's value at a round's points: gnnb_net_eval or the descent that can take its place, gnnb_net_descend (gnnb_k_net.h).
 //
@@ -193,7 +194,8 @@ __device__ __forceinline__ double fr_block_min(double* red, double v, int tid) {
 
 // What one job's commit sees of the pool and the children: the slots [base, base + cap) (in_use and every destination above the parents'
 // slots count from base), the parents' rows [row0, row0 + K) of `slots`, their children [2 row0, 2 row0 + 2K), the job's record and
-// decision bound.  k_frontier_decide is the view {0, pool capacity, 0, K, state, decision_bound}.
+// decision bound.  k_frontier_decide is the view {0, pool capacity, 0, K, state, decision_bound}.  With C children per parent (fr_decide's
+// argument; 2 but for a round of section 7.20) the children are rows [C row0, C row0 + C K).
 struct FrView {
   int base, cap, row0, K;
   double* state;
@@ -203,11 +205,12 @@ struct FrView {
 __device__ __forceinline__ bool fr_view_ok(const FrView& v, int s) { return s >= v.base && s < v.base + v.cap; }
 
 // global_ub, keep or close every child of the view, its parents' slots freed, the kept children's destination slots by a prefix sum
-// over the 2K keep flags in child order, the record.  One workgroup; red: FR_THREADS doubles, cnt: FR_THREADS + 1 ints of LDS.
-__device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v, double* red, int* cnt) {
-  const int tid = threadIdx.x, K = v.K, n = 2 * K;
+// over the C K keep flags in child order, the record.  C: the children per parent (parent i's are rows C i .. C i + C - 1).  One
+// workgroup; red: FR_THREADS doubles, cnt: FR_THREADS + 1 ints of LDS.
+__device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v, int C, double* red, int* cnt) {
+  const int tid = threadIdx.x, K = v.K, n = C * K;
   const int32_t* slots = a.slots + v.row0;
-  const long ch0 = 2L * v.row0;                         // the view's first child row
+  const long ch0 = (long)C * v.row0;                    // the view's first child row
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   const int in_use = min(max((int)v.state[FS_IN_USE], 0), v.cap);
   // 2. the incumbent: every live feasible child's network value at its LP point
@@ -229,7 +232,10 @@ __device__ __forceinline__ void fr_decide(const FrCommitArgs& a, const FrView& v
   }
   for (int i = tid; i < K; i += FR_THREADS) {           // a parent without a live child (decision [-1, -1]) is closed at its own bound
     const int s = slots[i];
-    if (fr_view_ok(v, s) && !a.ch.live[ch0 + 2 * i] && !a.ch.live[ch0 + 2 * i + 1]) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
+    if (!fr_view_ok(v, s)) continue;
+    int live = 0;
+    for (int j = 0; j < C; ++j) live |= a.ch.live[ch0 + (long)C * i + j];
+    if (!live) { closed = fmin(closed, a.p.bound[s]); ++n_closed; }
   }
   // 6. the parents leave the pool
   for (int i = tid; i < K; i += FR_THREADS)
@@ -294,7 +300,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide(FrCommitArgs a) 
   __shared__ double red[FR_THREADS];
   __shared__ int cnt[FR_THREADS + 1];
   const FrView v{0, a.p.cap, 0, a.K, a.state, a.decision_bound};
-  fr_decide(a, v, red, cnt);
+  fr_decide(a, v, 2, red, cnt);
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_frontier_store(FrCommitArgs a) {
@@ -410,7 +416,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_decide_jobs(FrCommitArg
   int seg, row0, k;
   if (!fr_entry(j, blockIdx.x, &seg, &row0, &k)) return;
   const FrView v{seg * j.seg_cap, j.seg_cap, row0, k, a.state + (long)seg * FS_COUNT, decision_bound[seg]};
-  fr_decide(a, v, red, cnt);
+  fr_decide(a, v, 2, red, cnt);
 }
 
 // ---- the BaBSR fall-back below a branching threshold ---------------------------------------------------------
@@ -966,4 +972,67 @@ __global__ __launch_bounds__(FR_THREADS) void k_frontier_witness_jobs(FrWitnessA
   }
   const FrWitView v{row0, k, sel0, m, a.best_value + seg, a.best_point + (long)seg * a.N0};
   fr_witness(a, v, rv, ri);
+}
+
+// ---- several ReLUs per parent while a round is underfilled ---------------------------------------------------
+// A round of K parents at DEPTH d gives every parent C = 2^d child rows, [C i, C i + C), from the candidate list gnnb_strong_list wrote
+// for it (cand0 (K + 1): the exclusive prefix of the rows' counts; cand_dec (n, 2): [layer, idx] in ascending flat index).
+//
+//   * k_frontier_expand_depth   K parents + their lists -> C K child rows.  With m_i listed nodes, row C i + j is live for j < 2^m_i: the
+//                               parent's mask with the b-th listed node set to bit b of j (0 blocked, 1 passing), split_layer the lowest
+//                               layer among the nodes.  Every other row of a parent in the pool -- j >= 2^m_i, and all C rows where m_i is 0
+//                               or above d, the list leaves [0, cand0[K]) or names no node of the network -- is a complete row with the
+//                               parent's mask, split_layer = L - 1 and live = 0; a slot outside the pool gives k_frontier_expand's unread
+//                               rows (live = 0, split_layer = -1).  fr_copy_row is the copy, the mask entries are set by the threads that
+//                               copied them.  At d = 1 with the list {decisions[i]} it writes what k_frontier_expand writes.
+//   * k_frontier_decide_depth   ONE workgroup: fr_decide on the view of the whole pool with C children per parent.  k_frontier_resolve and
+//                               k_frontier_store run per child row as they are.
+
+#define FR_MAX_DEPTH 8          // C <= 256 children per parent
+
+struct FrExpandDepthArgs {
+  FrShape s; FrPool p;
+  const int32_t* slots; const int32_t* cand0; const int32_t* cand_dec; int K, depth;
+  FrDomains ch;                                         // the K << depth children; lb / ub: gnnb_kw_bounds' parent tables
+  int32_t* split; int32_t* live;
+};
+static_assert(sizeof(FrExpandDepthArgs) <= 4096 && sizeof(FrCommitArgs) + sizeof(int) <= 4096, "kernel arguments: 4 KiB");
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_expand_depth(FrExpandDepthArgs a) {
+  const int c = blockIdx.x, i = c >> a.depth, j = c & ((1 << a.depth) - 1), t0 = blockIdx.y * FR_THREADS + threadIdx.x, dt = FR_SPLIT * FR_THREADS;
+  const int s = a.slots[i];
+  if (!fr_slot_ok(a.p, s)) {                            // no such parent: a dead row nobody reads
+    if (t0 == 0) { a.live[c] = 0; a.split[c] = -1; }
+    return;
+  }
+  const int q0 = a.cand0[i], m = a.cand0[i + 1] - q0;
+  bool listed = q0 >= 0 && m >= 1 && m <= a.depth && q0 + m <= a.cand0[a.K];
+  int node[FR_MAX_DEPTH], lay = a.s.L;
+#pragma unroll
+  for (int b = 0; b < FR_MAX_DEPTH; ++b) {              // (unrolled: node[] stays in registers)
+    node[b] = -1;
+    if (listed && b < m) {
+      const int l = a.cand_dec[2L * (q0 + b)];
+      if (fr_node(a.s, l, a.cand_dec[2L * (q0 + b) + 1], &node[b])) lay = min(lay, l);
+      else listed = false;
+    }
+  }
+  const bool live = listed && j < (1 << m);
+  fr_copy_row(a.s, a.ch, c, a.p, a.p.mask, s);
+  if (live) {
+#pragma unroll
+    for (int b = 0; b < FR_MAX_DEPTH; ++b)              // by the thread that copied the entry: no second pass
+      if (b < m && node[b] % dt == t0) a.ch.mask[(long)c * a.s.R + node[b]] = (int8_t)((j >> b) & 1);
+  }
+  if (t0 == 0) {
+    a.live[c] = live ? 1 : 0;
+    a.split[c] = live ? lay : a.s.L - 1;                // a dead row keeps every bound of its parent
+  }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_frontier_decide_depth(FrCommitArgs a, int depth) {
+  __shared__ double red[FR_THREADS];
+  __shared__ int cnt[FR_THREADS + 1];
+  const FrView v{0, a.p.cap, 0, a.K, a.state, a.decision_bound};
+  fr_decide(a, v, 1 << depth, red, cnt);
 }

@@ -1222,6 +1222,38 @@ class ScorerEngine:
         self._call("gnnb_frontier_commit", C.byref(st), self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, C.byref(ch), float(eps),
                    float("nan") if decision_bound is None else float(decision_bound), state.data_ptr(), ws.data_ptr(), ws.numel())
 
+    def frontier_expand_depth(self, pool, slots, depth, cand0, cand_dec, mask, parent_lb, parent_ub, split_layer, alpha, beta, live):
+        """gnnb_frontier_expand_depth on the current stream: C = 2^depth child rows per parent in ``slots`` from
+        the candidate lists ``strong_list`` wrote (cand0 (K + 1,) int32, cand_dec (n, 2) int32 with n = cand0[K], read on the device).
+        Parent i with m listed nodes gets live rows C i + j, j < 2^m, its mask with the b-th listed node set to bit b of j; its other
+        rows, and every row of a parent with 0 or more than ``depth`` nodes, are dead rows with the parent's mask.  The outputs are
+        ``frontier_expand``'s with K * C rows.  Nothing is copied."""
+        K, depth = int(slots.numel()), int(depth)
+        st, keep = self._pool(pool)
+        R, n, i32, f64 = self.R, max(K, 0) << min(max(depth, 0), 8), torch.int32, torch.float64
+        args = (self._rows(slots, K, 1, i32, "slots").data_ptr(), K, depth, self._rows(cand0, K + 1, 1, i32, "cand0").data_ptr(),
+                self._rows(cand_dec, 1, 2, i32, "cand_dec").data_ptr(), self._rows(mask, n, R, torch.int8, "mask").data_ptr(),
+                self._layer_rows(parent_lb, n, 1, f64, "parent_lb"), self._layer_rows(parent_ub, n, 1, f64, "parent_ub"),
+                self._rows(split_layer, n, 1, i32, "split_layer").data_ptr(), self._rows(alpha, n, R, f64, "alpha").data_ptr(),
+                self._rows(beta, n, R, f64, "beta").data_ptr(), self._rows(live, n, 1, i32, "live").data_ptr())
+        self._call("gnnb_frontier_expand_depth", C.byref(st), *args)
+
+    def frontier_commit_depth(self, pool, slots, depth, mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live, state, eps=1e-4,
+                              decision_bound=None, workspace=None):
+        """gnnb_frontier_commit_depth on the current stream: ``frontier_commit``'s rule on the K * 2^depth child
+        rows ``frontier_expand_depth`` laid out; a kept child of rank r goes to slots[r] for r < K, else to slot in_use + (r - K)."""
+        K, depth = int(slots.numel()), int(depth)
+        st, keep = self._pool(pool)
+        n = max(K, 0) << min(max(depth, 0), 8)
+        ch, keep_ch = self._children(_ChildRows(mask, lb, ub, infeasible, bound, alpha, beta, ub_value, live), n)
+        self._rows(state, _lib.FRONTIER_STATE_DOUBLES, 1, torch.float64, "state")
+        if workspace is None:
+            need = self.lib.gnnb_frontier_commit_depth_workspace_bytes(self.h, K, depth)
+            workspace = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        self._call("gnnb_frontier_commit_depth", C.byref(st), self._rows(slots, K, 1, torch.int32, "slots").data_ptr(), K, depth, C.byref(ch),
+                   float(eps), float("nan") if decision_bound is None else float(decision_bound), state.data_ptr(), workspace.data_ptr(),
+                   workspace.numel())
+
     def babsr_rows(self, lb32, ub32, prop_w, scorer_mask, B, scores, intercepts):
         """gnnb_babsr on the current stream over the first B of the parent rows ``frontier_gather`` wrote (lb32 / ub32: graph layers
         0..L+1 fp32; prop_w (B, N_L) fp32; scorer_mask (B, R) fp32) into scores / intercepts (B, R) fp32.  Nothing is copied."""

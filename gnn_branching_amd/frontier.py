@@ -43,6 +43,10 @@ them alone (``gnnb_strong_list_union``, ``gnnb_strong_list``), so that the table
 ``imitate=Replay(every=N, ...)`` keeps the labelled states: a learning round stores its useful rows in a
 device-resident ``ReplayBuffer`` (``gnnb_replay_push``) and its steps run on minibatches drawn from it (``gnnb_replay_sample``), which mix
 depths, properties and jobs; ``steps=0`` only collects, for ``replay.train_epochs`` to train on later.
+
+``branch_and_bound_frontier`` on a ``LayerGraphLP(..., split_depth=D)`` fills an underfilled round: while k parents leave child rows
+unused, each is split on its d best-scored undecided ReLUs at once (``round_depth``; ``gnnb_strong_list`` on the scorer's scores,
+``gnnb_frontier_expand_depth``, ``gnnb_frontier_commit_depth``), 2^d children per parent on the same 2K child rows.
 """
 import ctypes as C
 import math
@@ -554,6 +558,27 @@ def _check_restarts(pgd_restarts, pgd_seed, pgd_steps):
 
 
 PGD_RESTARTS_MAX = 4096             # gnnb_net_starts' R
+SPLIT_DEPTH_MAX = 8                 # gnnb_frontier_expand_depth's depth
+
+
+def _check_split_depth(split_depth, branching="gnn", branching_threshold=None, online_threshold=None, imitate=None, strong_audit=None,
+                       strong_candidates=None):
+    """``lp.split_depth`` (None: off) and what it does not go with, before a device is touched.  A parent's 2^d children
+    come from ONE list of its d nodes, the scorer's: a mode that names one node per parent by another rule (BaBSR, the strong table), that
+    compares two PAIRS of children (the threshold and online modes) or that labels one decision per parent (imitate, an audit, a
+    ``Shortlist``) has no meaning for them yet."""
+    if split_depth is None:
+        return
+    if isinstance(split_depth, bool) or not isinstance(split_depth, int) or not 1 <= split_depth <= SPLIT_DEPTH_MAX:
+        raise ValueError(f"split_depth = {split_depth!r}: None, or an integer in 1..{SPLIT_DEPTH_MAX} (a bool is refused)")
+    if branching != "gnn":
+        raise ValueError(f'split_depth with branching={branching!r}: the nodes of a deep split are the ones the GNN scores highest; only branching="gnn"')
+    for name, value in (("branching_threshold", branching_threshold), ("online_threshold", online_threshold), ("imitate", imitate),
+                        ("strong_audit", strong_audit)):
+        if value is not None:
+            raise ValueError(f"split_depth takes no {name}: it compares or labels the two children of ONE decision per parent")
+    if isinstance(strong_candidates, Shortlist):
+        raise ValueError(f"split_depth takes no Shortlist (strong_candidates = {strong_candidates!r}): the run's one candidate list holds the nodes of the split")
 
 
 class _Round:
@@ -565,6 +590,7 @@ class _Round:
     online, learn_pending = None, False      # (sections 7.7 and 7.19: the online threshold of a run that learns online; a selection not yet read)
     last_learn = online_steps = online_rows = 0      # (the learn rows of the last round that read them; the steps of the run and their rows)
     tighten_root = 0                         # (section 7.18: iterations of gnnb_kw_tighten on the roots' intermediate bounds; 0: gnnb_kw_bounds)
+    split_depth, depth = None, 0             # (section 7.20: the most nodes a parent is split on in one round; the launched round's d, 0: the two-children round)
 
     def _set_options(self, choice, *, branching="gnn", branching_threshold=None, kwbd_threshold=KWBD_DEFAULT, sparsest_layer=0, decision_threshold=0.001,
                      online_threshold=None, witness=None, pgd_steps=None, pgd_step=PGD_STEP_DEFAULT, pgd_restarts=None, pgd_seed=0, imitate=None,
@@ -747,6 +773,18 @@ class _Round:
             self.cand_src = torch.zeros(cap, dtype=i32, device=dev)
         self.strong_bounded = 0
 
+    def _depth_buffers(self, n_parents):
+        """The state of a run with ``split_depth`` = D for rounds of up to n_parents parents: the candidate lists
+        ``gnnb_strong_list`` writes at top_m = d <= D and its workspace.  The child side keeps its size: a round has k 2^d <= 2K child rows,
+        and the commit's workspace is sized by the rows."""
+        if self.split_depth is None:
+            return
+        dev, n, i32 = self.eng.device, n_parents, torch.int32
+        cap = n * min(self.eng.R, self.split_depth)
+        self.cand0 = torch.zeros(n + 1, dtype=i32, device=dev)
+        self.cand_row, self.cand_slot, self.cand_dec = (torch.zeros(s, dtype=i32, device=dev) for s in ((cap,), (cap,), (cap, 2)))
+        self.ws_strong = self._ws("gnnb_strong_list_workspace_bytes", n)
+
     def _imitation_buffers(self, n_parents):
         """The state of a run with ``imitate`` for learning rounds of up to n_parents parent rows: the table a
         learning round keeps, the rows its step takes (all of them, in row order) and what the step reports per row."""
@@ -882,13 +920,13 @@ class _Round:
             self.eng.net_descend_starts(self.fixed, None, self.starts[:B], Ch.box[0], Ch.box[1], self.pgd_steps, self.pgd_step, x_best=Ch.x_ub,
                                         value=Ch.ubv, prop=Ch.box[2:], workspace=self.ws_starts, in_shape=self.in_shape)
 
-    def _at_least_the_parent_s(self, Ch, slots, n):
-        """Behind the bounding of the 2n children of the n parents in ``slots``: a child's bound is at least its parent's.  The child is a
+    def _at_least_the_parent_s(self, Ch, slots, n, C=2):
+        """Behind the bounding of the C n children of the n parents in ``slots`` (C = 2 but in a round of section 7.20): a child's bound is at least its parent's.  The child is a
         part of the parent, so the parent's bound holds for it; the 20 warm-started steps can end below it (the split node's new
         multiplier starts at 0), and without this the lowest open bound falls when such a parent is replaced by its children.  Device
         work only."""
-        parent = self.pool.bound[slots[:n].long().clamp(min=0)].repeat_interleave(2)
-        torch.maximum(Ch.bound[:2 * n], parent, out=Ch.bound[:2 * n])
+        parent = self.pool.bound[slots[:n].long().clamp(min=0)].repeat_interleave(C)
+        torch.maximum(Ch.bound[:C * n], parent, out=Ch.bound[:C * n])
 
     def _ub_points(self, Ch):
         """The points the rows' ubv are the network's values at."""
@@ -929,6 +967,8 @@ class _Round:
         """The launches of a round over the n parents in ``slots`` (their boxes: the parent rows' own), from the gather to the commit."""
         P, Ch, eng, pool = self.P, self.Ch, self.eng, self.pool
         eng.frontier_gather(pool, slots, P.box[0], P.box[1], P.mask, P.lb, P.ub, P.lb32, P.ub32, P.alpha, P.beta, P.amb)
+        if self.depth:
+            return self._launch_depth(slots, n, self.depth)
         if self.branching == "gnn":
             self._score_parents(n)
         else:
@@ -953,6 +993,22 @@ class _Round:
         if self.learning and self.replay is not None:             # section 7.16: the round's labelled rows go into the buffer, device work only
             self.buffer.push(P.fwd_batch, n, self.im_rows[:n], n, self.im_table, status=self.push_status)
             self.status_all |= self.push_status
+
+    def _launch_depth(self, slots, n, d):
+        """A round of a ``split_depth`` run behind its gather: every one of the n parents is split on its d
+        best-scored undecided nodes -- ``gnnb_strong_list`` on the scores ``gnnb_forward`` just wrote, whose first-ranked node is the
+        forward's own decision -- into C = 2^d child rows, which are bounded, held to the parent's bound and committed as any round's
+        are.  The witness is a minimum over the C n rows (``gnnb_frontier_witness`` with C n / 2 row pairs and no pair B)."""
+        P, Ch, eng, pool, C = self.P, self.Ch, self.eng, self.pool, 1 << d
+        self._score_parents(n)
+        eng.strong_list(pool, slots, P.amb, P.scores, d, self.cand0, self.cand_row, self.cand_slot, self.cand_dec, workspace=self.ws_strong)
+        eng.frontier_expand_depth(pool, slots, d, self.cand0, self.cand_dec, Ch.mask, Ch.plb, Ch.pub, Ch.split, Ch.alpha, Ch.beta, Ch.live)
+        self._bound_children(Ch, C * n, warm=True)
+        self._at_least_the_parent_s(Ch, slots, n, C)
+        if self.witness_on:
+            self._witness(C * n // 2, 0)
+        self.eng.frontier_commit_depth(pool, slots, d, *Ch.children(), pool.state, eps=self.eps, decision_bound=self.decision_bound,
+                                       workspace=self.ws_commit)
 
     def _fall_back(self, n):
         """The threshold mode between the bounding of pair A and the commit (DESIGN.md sections 7.5 and 7.6): BaBSR on the n parent rows,
@@ -1082,6 +1138,10 @@ class FrontierRun(_Round):
                           decision_threshold=decision_threshold, online_threshold=online_threshold, witness=witness, pgd_steps=pgd_steps, pgd_step=pgd_step,
                           pgd_restarts=pgd_restarts, pgd_seed=pgd_seed, imitate=imitate, imitate_margin=imitate_margin,
                           strong_candidates=strong_candidates, strong_chunk=strong_chunk, strong_audit=strong_audit, repack=repack)
+        split_depth = getattr(lp, "split_depth", None)            # (section 7.20: the option travels on the root's description, as tighten_root does)
+        _check_split_depth(split_depth, branching, branching_threshold, online_threshold, imitate, strong_audit, strong_candidates)
+        if split_depth is not None:                               # (set only where given, as strong_G)
+            self.split_depth = split_depth
         layers = list(layers)
         if type(layers[-1]) is not nn.Linear or layers[-1].out_features != 1:
             raise ValueError("the last layer must be the folded property layer Linear(., 1)")
@@ -1117,6 +1177,7 @@ class FrontierRun(_Round):
             self._online_buffers(K, (eng.R,), 1)
             self.n_learn = self.learn_count
         self._imitation_buffers(K)
+        self._depth_buffers(K)
         self._use_repack()                                        # last: nothing behind it can fail and leave the engine in the run's mode
 
     def _commit(self, slots):
@@ -1145,9 +1206,11 @@ class FrontierRun(_Round):
         key = torch.where(pool.open[:in_use] > 0, pool.bound[:in_use], float("inf"))
         return torch.sort(key, stable=True).indices[:k].to(torch.int32).contiguous()
 
-    def launch_round(self, k, in_use):
-        """One round over the k <= K open domains of lowest bound.  Device work only."""
+    def launch_round(self, k, in_use, depth=0):
+        """One round over the k <= K open domains of lowest bound.  Device work only.  depth: 0, or in a ``split_depth`` run the round's d
+        (``round_depth``): 2^d children per parent."""
         self.slots = self.pick(k, in_use)
+        self.depth = depth
         self._begin_round(k)
         self._launch(self.slots, k)
 
@@ -1339,6 +1402,20 @@ def branch_and_bound_frontier(lp, choice, layers, K=16, n_iter=20, lr=0.1, eps=1
     bounded by its own slope-optimised dual ascent -- in place of ``gnnb_kw_bounds``.  Every child copies or intersects its parent's bounds,
     so the whole tree inherits them; no round runs the tightening, and it adds no read.
 
+    lp.split_depth (``LayerGraphLP(..., split_depth=D)`` -- this parameter list is fixed, so the option travels on
+    the root's description, as ``tighten_root`` does; with None, the default, no launch, read, buffer or argument of a round changes).  An
+    integer D in 1..8 (a bool is refused): the most ReLUs a parent is split on in one round.  A round of k parents runs at the depth d = ``round_depth(k, K, D, open,
+    capacity)``, the largest d <= D whose k 2^d children fit the round's 2K child rows and the pool; a full round (k = K) is depth 1.  Parent
+    i is split on the first d undecided nodes in the order (score descending, flat index ascending) of ``gnnb_forward``'s scores
+    (``gnnb_strong_list``; the first of them is the forward's own decision; a parent with m < d undecided nodes on its m) and gets the 2^d
+    children of every assignment of those nodes (``gnnb_frontier_expand_depth``), all bounded, held to the parent's bound and kept or closed
+    by the round's one rule (``gnnb_frontier_commit_depth``); the children of a deep split are not re-scored in between.  The pool is
+    compacted when the slots in use leave no room for the (2^d - 1) k children beyond the parents' slots, and the run stops ("capacity")
+    when not even d = 1 fits.  No read is added.  A traced round also carries "depth" and "nodes" (per parent the [layer, idx] pairs of its
+    split, in ascending flat index) and its children's lists hold 2^d entries per parent; "decisions" stay ``gnnb_forward``'s.  Only with
+    ``branching="gnn"``; it takes no ``branching_threshold``, ``online_threshold``, ``imitate``, ``strong_audit`` or ``Shortlist``, with or
+    without ``witness``, ``pgd_steps``, ``pgd_restarts``, ``decision_bound`` and ``lp.tighten_root``.
+
     Returns (global_lb, global_ub, rounds, domains_bounded, reason)."""
     run = FrontierRun(lp, choice, layers, K, n_iter, lr, eps, decision_bound, capacity, branching_threshold, kwbd_threshold, sparsest_layer,
                       decision_threshold, online_threshold, max_rounds, witness, pgd_steps, pgd_step, pgd_restarts, pgd_seed, repack, imitate,
@@ -1363,13 +1440,16 @@ def _one_job_loop(run, max_rounds, log, trace, stats):
     log(f"root lb {_global_lb(st):.5f} ub {st[S.FS_GLOBAL_UB]:.5f}")
     while True:
         global_lb, global_ub, n_open, in_use = _global_lb(st), st[S.FS_GLOBAL_UB], int(st[S.FS_N_OPEN]), int(st[S.FS_IN_USE])
-        reason, k, compact = _one_job_round(st, run.K, run.capacity, run.eps, run.decision_bound, tally["rounds"], max_rounds)
+        if run.split_depth is None:
+            (reason, k, compact), d = _one_job_round(st, run.K, run.capacity, run.eps, run.decision_bound, tally["rounds"], max_rounds), 0
+        else:                                                     # section 7.20: the round's depth and its capacity arithmetic
+            reason, k, compact, d = _one_job_round_depth(st, run.K, run.split_depth, run.capacity, run.eps, run.decision_bound, tally["rounds"], max_rounds)
         if reason is not None:
             break
         if compact:                                               # the kept children beyond the k parents' slots go above in_use
             run.pool.compact(n_open)
             in_use = n_open
-        run.launch_round(k, in_use)
+        run.launch_round(k, in_use, d) if d else run.launch_round(k, in_use)
         t = _report_launched(run, trace, 0, 0, k, {})
         st = run.read_state()
         if t is not None:
@@ -1633,6 +1713,31 @@ def _one_job_round(st, K, capacity, eps, decision_bound, rounds, max_rounds):
     return None, entries[0][2], compact[0]
 
 
+def round_depth(k, K, D, n_open, cap):
+    """The depth of a round of k parents in a run with ``split_depth`` = D: a pure function of what the host
+    holds.  The largest d in 1..D with k 2^d <= 2K (the round's child rows) and n_open + (2^d - 1) k <= cap (a compacted pool holds every
+    child: k of them reuse the parents' slots); 0 when not even d = 1 fits -- the "capacity" stop.  k = K gives 1 at most."""
+    best = 0
+    for d in range(1, D + 1):
+        if k << d <= 2 * K and n_open + ((1 << d) - 1) * k <= cap:
+            best = d
+    return best
+
+
+def _one_job_round_depth(st, K, D, capacity, eps, decision_bound, rounds, max_rounds):
+    """``_one_job_round`` for a run with ``split_depth`` = D: (reason, k, compact, d) -- a stop reason, or None and a round of k parents at
+    depth d after a compaction of the pool if ``compact`` (slots in use + (2^d - 1) k > capacity).  At D = 1 it is ``_one_job_round``."""
+    reason = _stop_reason(st, eps, decision_bound, rounds, max_rounds)
+    if reason is not None:
+        return reason, 0, False, 0
+    n_open, in_use = int(st[_lib.FS_N_OPEN]), int(st[_lib.FS_IN_USE])
+    k = min(K, n_open)
+    d = round_depth(k, K, D, n_open, capacity)
+    if d == 0:
+        return "capacity", 0, False, 0
+    return None, k, in_use + ((1 << d) - 1) * k > capacity, d
+
+
 def _check_record(st):
     if st[_lib.FS_OVERFLOW] != 0 or math.isnan(st[_lib.FS_GLOBAL_UB]):
         raise RuntimeError(f"frontier state record is inconsistent: {st}")
@@ -1640,10 +1745,17 @@ def _check_record(st):
 
 def _trace_rows(run, a, b):
     """A round's trace of the parent rows [a, b) and their children (device-to-host copies)."""
-    P, Ch, c, d = run.P, run.Ch, 2 * a, 2 * b
-    return {"slots": run.slots[a:b].cpu().tolist(), "parent_bounds": P.bound[a:b].cpu().tolist(), "decisions": P.dec[a:b].cpu().tolist(),
-            "child_bounds": Ch.bound[c:d].cpu().tolist(), "child_ub": Ch.ubv[c:d].cpu().tolist(), "live": Ch.live[c:d].cpu().tolist(),
-            "infeasible": Ch.infeasible[c:d].cpu().tolist()}
+    depth = getattr(run, "depth", 0)                               # (section 7.20: 2^depth children per parent; a stand-in run has none)
+    P, Ch, C = run.P, run.Ch, 1 << depth if depth else 2
+    c, d = C * a, C * b
+    t = {"slots": run.slots[a:b].cpu().tolist(), "parent_bounds": P.bound[a:b].cpu().tolist(), "decisions": P.dec[a:b].cpu().tolist(),
+         "child_bounds": Ch.bound[c:d].cpu().tolist(), "child_ub": Ch.ubv[c:d].cpu().tolist(), "live": Ch.live[c:d].cpu().tolist(),
+         "infeasible": Ch.infeasible[c:d].cpu().tolist()}
+    if depth:
+        c0 = run.cand0[a:b + 1].cpu().tolist()
+        dec = run.cand_dec[c0[0]:c0[-1]].cpu().tolist()
+        t.update(depth=depth, nodes=[dec[q0 - c0[0]:q1 - c0[0]] for q0, q1 in zip(c0, c0[1:])])
+    return t
 
 
 class RoundPlan:

@@ -116,11 +116,16 @@ def _clamp_by_mask(m, lo, up):
 class LayerGraphLP:
     """LP relaxation of ``layers`` (net.layers with the folded Linear(., 1) property layer last) over an input box."""
 
-    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm", engine=None, tighten_root=0):
+    def __init__(self, layers, input_lb, input_ub, bounds="kw", lp_method="highs-ipm", engine=None, tighten_root=0, split_depth=None):
         """``bounds``: "kw" (host fp64 Wong-Kolter), "interval", or "kw_device" (the same bounds on the GPU; ``engine``: the
         ScorerEngine to run them on, None = a GNN-free one created on first use).  ``tighten_root`` = n > 0: a
         domain without a parent gets ``kw_bounds(tighten=n)`` -- every child then inherits the tightened bounds through its parent's --
-        in ``bounds`` ("kw" and "kw_device") and as the root of ``frontier.branch_and_bound_frontier``."""
+        in ``bounds`` ("kw" and "kw_device") and as the root of ``frontier.branch_and_bound_frontier``.  ``split_depth`` = D in 1..8
+        (None: off): ``frontier.branch_and_bound_frontier`` on this root splits each parent of an underfilled round
+        on up to D ReLUs at once; nothing else reads it."""
+        if split_depth is not None and (isinstance(split_depth, bool) or not isinstance(split_depth, int) or not 1 <= split_depth <= 8):
+            raise ValueError(f"split_depth = {split_depth!r}: None, or an integer in 1..8")
+        self.split_depth = split_depth
         if isinstance(tighten_root, bool) or not isinstance(tighten_root, int) or tighten_root < 0:
             raise ValueError(f"tighten_root = {tighten_root!r}: an integer >= 0")
         self.tighten_root = tighten_root

@@ -398,6 +398,39 @@ size_t gnnb_frontier_commit_workspace_bytes(const gnnb_t* h, int K);
 int gnnb_frontier_commit(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, const gnnb_children* children, double eps,
                          double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- several ReLUs per parent while a round is underfilled (frontier.py split_depth) ----
+ * A round of K parents at DEPTH d (1..8) gives every parent C = 2^d child rows, [C i, C i + C), so that few parents still fill the child
+ * side's rows; K << d is at most 65534.  Everything between the two calls (gnnb_kw_bounds, gnnb_dual_ascent, gnnb_net_eval, ...) runs on
+ * the K << d rows unchanged.
+ *
+ * gnnb_frontier_expand_depth.  cand0: device (K + 1) int32 and cand_dec: device (n, 2) int32 as gnnb_strong_list writes them (n =
+ * cand0[K]; parent i's nodes are entries [cand0[i], cand0[i+1]) in ascending flat index) -- with scores = gnnb_forward's scores_padded and
+ * top_m = d the d undecided nodes the scorer ranks first, the first of them gnnb_forward's own decision.  With m_i = cand0[i+1] -
+ * cand0[i], row C i + j is LIVE for j < 2^m_i: mask = the parent's with the b-th listed node (b = 0..m_i-1) set to bit b of j (0 blocked,
+ * 1 passing); split_layer = the lowest layer among the m_i nodes; alpha / beta and the parent_lb / parent_ub rows = the parent's.  Every
+ * other row of a parent in the pool is DEAD -- rows j >= 2^m_i, and all C rows when m_i = 0, m_i > d, the entries leave [0, n) or one of
+ * them names no node of the network: the parent's mask, split_layer = L-1, live = 0, complete rows the batch entry points can run on.  A
+ * slot outside the pool yields gnnb_frontier_expand's unread rows: live = 0, split_layer = -1, nothing else written.  At d = 1 with cand0
+ * = {0, 1, .., K} and cand_dec = decisions every output is gnnb_frontier_expand's, bit for bit.  The other arguments are
+ * gnnb_frontier_expand's, with K << d rows.
+ *
+ * gnnb_frontier_commit_depth.  gnnb_frontier_commit's rule on the (K << d) child rows: every live child is resolved and kept or closed
+ * as there; a parent none of whose C rows is live lowers closed_lb by its own bound; ranks run in child order over all rows, the kept
+ * child of rank r goes to slots[r] for r < K and to in_use + (r - K) from there on, so a round needs in_use + (C - 1) K <= capacity to
+ * lose no child (state[8] counts the ones that found no slot; they are closed at their bound).  At d = 1 it is gnnb_frontier_commit, bit
+ * for bit.  children: K << d rows.
+ *
+ * Both: stream-ordered, no allocation, no synchronisation, no atomics, no workgroup waits on another.  GNNB_E_INVALID before any launch
+ * for a null handle or argument, K outside 1..32767, depth outside 1..8, K << depth above 65534 or a network past the 4096-node cap;
+ * GNNB_E_STATE before gnnb_bind_network; GNNB_E_NOMEM for a short workspace (gnnb_frontier_commit_depth_workspace_bytes; 0 for a null or
+ * unbound handle or sizes that would be refused). */
+int gnnb_frontier_expand_depth(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, int depth, const int32_t* cand0,
+                               const int32_t* cand_dec, int8_t* mask, double* const* parent_lb, double* const* parent_ub,
+                               int32_t* split_layer, double* alpha, double* beta, int32_t* live, void* stream);
+size_t gnnb_frontier_commit_depth_workspace_bytes(const gnnb_t* h, int K, int depth);
+int gnnb_frontier_commit_depth(gnnb_t* h, const gnnb_pool* pool, const int32_t* slots, int K, int depth, const gnnb_children* children,
+                               double eps, double decision_bound, double* state, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- many jobs in one pool (gnn_branching_amd/frontier.py verify_properties runs the loop) ----
  * A JOB is a box, a property row and a decision bound on the bound network.  The pool is `segments` segments of `seg_cap` slots (segment
  * s: slots [s seg_cap, (s+1) seg_cap)), gnnb_pool.capacity = segments * seg_cap; a segment holds one job at a time and has its own state
